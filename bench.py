@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: captions/sec of the full adversarial G+D train step (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]            # N=1 directly;
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   # N=1 directly;
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W   # N>1: one rank per GPU over RCCL
 
@@ -32,6 +32,7 @@ sys.path.insert(0, ROOT)
 CFG2 = dict(B=64, S=224, L=20, V=10000, E=512, H=512, NL=1)
 MFMA_BF16_PEAK_TFLOPS = 2500.0       # MI355X_MICROARCH.md: ~2.5 PFLOP/s dense bf16
 HBM_PEAK_GBS = 8000.0                # MI355X_MICROARCH.md: 8 TB/s HBM3E
+DUMP_MAX_ELEMS = 4 << 20             # --dump-outputs: float32 elements per file (3 files, <= 48 MB in all)
 
 
 def log(msg):
@@ -57,7 +58,12 @@ def parse():
                         "cfg5: SeqGAN policy gradient + 16 Monte-Carlo roll-outs per prefix, 32 captions/GPU (BASELINE configs[3], [4]: "
                         "global batch 256 on 8 GPUs)")
     p.add_argument("--mc-rollouts", type=int, default=16)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): losses = the (g_loss, "
+                        "d_loss) pair the step returns, gen_params / disc_params = the master weights its optimizer steps wrote")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     if a.batch is None:                        # BASELINE configs[1..2]: 64 per GPU; configs[3], [4]: global batch 256 over 8 GPUs
         a.batch = CFG2["B"] if a.workload == "cfg2" else 32
     return a
@@ -172,6 +178,33 @@ def roofline_probe(inst, args, cgan, step=None):
     return {"kernel": "gemm_kernel<bf16,f32,NT,64x64|128x128> highway [%d,%d,%d]" % (M, N, K), "bound": "mfma",
             "achieved": round(achieved, 2), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
             "frac": round(achieved / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": None, "ms_per_launch": round(ms, 5)}
+
+
+def dump_outputs(path, inst, losses):
+    """--dump-outputs: the last timed step's results, read after the timed region.  The parameter arenas are flat float32 buffers; one
+    larger than DUMP_MAX_ELEMS is written as a fixed sample (seeded, sorted indices: the same elements in every run of the same
+    workload)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"losses": losses, "gen_params": inst.gen_arena.flat, "disc_params": inst.disc_arena.flat}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(1008))[:DUMP_MAX_ELEMS].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+    log(f"outputs of the last timed step written to {path}: " + ", ".join(sorted(arrays)))
+
+
+def ensure_library():
+    """Compile the HIP library only when it is missing or older than a source or header: a built tree may be read-only to the user
+    who benchmarks it, and a build takes a lock file beside the objects."""
+    import glob
+    import importlib
+    b = importlib.import_module("gan_image_captioning_amd.build")
+    deps = glob.glob(os.path.join(b.CSRC, "*.hip")) + glob.glob(os.path.join(b.CSRC, "*.h")) + [os.path.join(ROOT, "include", "gicap.h")]
+    if not os.path.exists(b.LIB) or any(os.path.getmtime(d) > os.path.getmtime(b.LIB) for d in deps):
+        b.build()
 
 
 def usable_cores() -> int:
@@ -293,8 +326,7 @@ def main():
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {a.gpus} (or without torchrun)")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
-    import importlib
-    importlib.import_module("gan_image_captioning_amd.build").build()
+    ensure_library()
     cgan = a.cgan if a.cgan is not None else (1 if encoder_available() else 0)
     inst, args = build_instructor(a, cgan)
     dev = args.device
@@ -304,8 +336,9 @@ def main():
     n_batches, adv_epochs = 50, args.adv_epochs
 
     def step(k):
-        inst.adv_step(images, captions, L, train=True, next_images=images if (cgan and not a.no_prefetch) else None)
+        losses = inst.adv_step(images, captions, L, train=True, next_images=images if (cgan and not a.no_prefetch) else None)
         inst.update_temperature(0 + (k + 1) / n_batches, adv_epochs)      # training.py:183
+        return losses
 
     log(f"instructor ready (cgan={cgan}, dtype={a.dtype}); warm-up {a.warmup} steps")
     for k in range(a.warmup):
@@ -317,7 +350,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(a.steps):
-        step(a.warmup + k)
+        losses = step(a.warmup + k)
     t_enq = time.perf_counter() - t0           # host time to enqueue the K steps (the GPU runs behind it)
     torch.cuda.synchronize()
     if world > 1:
@@ -345,6 +378,8 @@ def main():
                    "conditional_gan": cgan, "encoder": a.encoder if cgan else None, "step_impl": a.step_impl,
                    "parallelism": "dp%d" % world},
     }
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, inst, losses)        # before the roofline probe: it runs further train steps
     log(f"timed region done: {elapsed / a.steps * 1e3:.3f} ms/step; roofline probe")
     if not a.no_roofline:
         # the in-step measurement runs train steps: only without data parallelism (the other ranks have left; a step would wait for

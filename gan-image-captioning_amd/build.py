@@ -34,9 +34,25 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _sources():
+    srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [
+        os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "gicap.h")]
+    return srcs, hdrs
+
+
+def up_to_date() -> bool:
+    """The library exists and is newer than every source and header."""
+    srcs, hdrs = _sources()
+    return not _stale(LIB, srcs + hdrs)
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile what is stale.  An exclusive file lock serialises concurrent callers (one rank per GPU under torchrun)."""
+    """Compile what is stale.  An exclusive file lock serialises concurrent callers (one rank per GPU under torchrun).  A current
+    library is returned without writing anything: a built tree may be read-only to the user who runs it."""
     import fcntl
+    if not force and up_to_date():
+        return LIB
     os.makedirs(OBJDIR, exist_ok=True)
     with open(os.path.join(OBJDIR, ".lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -47,9 +63,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 def _build_locked(force: bool, verbose: bool) -> str:
-    srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [
-        os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "gicap.h")]
+    srcs, hdrs = _sources()
     objdir = OBJDIR
     hipcc = _hipcc()
 
@@ -67,12 +81,16 @@ def _build_locked(force: bool, verbose: bool) -> str:
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(6, len(srcs))) as ex:
         objs = list(ex.map(compile_one, srcs))
     if force or _stale(LIB, objs):
-        cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB, *objs]
+        tmp = f"{LIB}.{os.getpid()}.tmp"          # linked beside and renamed: a caller that finds LIB current never sees a partial file
+        cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp, *objs]
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
+            if os.path.exists(tmp):
+                os.remove(tmp)
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+        os.replace(tmp, LIB)
     return LIB
 
 

@@ -35,11 +35,12 @@ class FusedAdvStep:
         self._disc_grads = None
         self.overlap = not os.environ.get("GIC_NO_STREAM_OVERLAP")
         self.trace = None
-        self.use_graph = not (os.environ.get("GIC_NO_STEP_GRAPH") or os.environ.get("GIC_NO_GRAPH"))
-        if self.attn and not os.environ.get("GIC_STEP_GRAPH_ATTN"):
-            # the attention step replays as graphs too (host enqueue 2.10 -> 0.43 ms per step) but measured 3.87 ms per step against
-            # 3.74 for eager launches at cfg4 (same box, back to back): eager is the default there, GIC_STEP_GRAPH_ATTN=1 opts in
-            self.use_graph = False
+        # Replayed step graphs are opt-in.  LSTM step (GIC_STEP_GRAPH=1): at cfg2 (B=64, V=10000) the segments replayed on their three
+        # streams left non-finite decoder gradients from the first replay on (the same kernels as eager launches give finite ones; the
+        # replay test's cfg1 shapes do not show it), and eager launches measured 2.41 ms per step against 2.47 replayed.  Attention step
+        # (GIC_STEP_GRAPH_ATTN=1): host enqueue 2.10 -> 0.43 ms per step, but 3.87 ms per step against 3.74 for eager launches at cfg4.
+        want = os.environ.get("GIC_STEP_GRAPH_ATTN" if self.attn else "GIC_STEP_GRAPH")
+        self.use_graph = bool(want) and not (os.environ.get("GIC_NO_STEP_GRAPH") or os.environ.get("GIC_NO_GRAPH"))
         self._graphs: Dict[tuple, dict] = {}
         self._warm: set = set()
 
@@ -107,9 +108,10 @@ class FusedAdvStep:
           G path (D(gen) input-gradient, decoder / encoder-head backward)  ||  D path (backward real + fake, D's Adam)
         D's weights are not updated before the G path has finished reading them; both paths join before G's Adam.
 
-        A training step with device-drawn noise is replayed as six linear hipGraphs from its third call on (``_call_graph``): everything
-        behind the trunk features -- ~110 launches on three streams -- with the per-step scalars (temperature, noise seeds) read from
-        device memory (engine.StepScalarsBuffer); GIC_NO_STEP_GRAPH=1 (or GIC_NO_GRAPH=1) keeps the eager launches.  Returned tensors
+        With GIC_STEP_GRAPH=1 (opt-in, see __init__), a training step with device-drawn noise is replayed as six linear hipGraphs from its
+        third call on (``_call_graph``): everything behind the trunk features -- ~110 launches on three streams -- with the per-step
+        scalars (temperature, noise seeds) read from device memory (engine.StepScalarsBuffer); GIC_NO_STEP_GRAPH=1 (or GIC_NO_GRAPH=1)
+        keeps the eager launches either way.  Returned tensors
         of a replayed step live in the graphs' memory pools and are overwritten by the next step."""
         B, L = captions.shape[0], int(max_caption_len)
         engine.require_gpu(captions, images)

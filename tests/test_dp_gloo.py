@@ -52,7 +52,9 @@ def _unflat(flat, like, names):
 
 
 def _worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    # gloo even where a GPU is visible (from_env would pick RCCL there): this is the CPU rehearsal
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
+                      GIC_DIST_BACKEND="gloo")
     torch.set_num_threads(2)
     from gan_image_captioning_amd import parallel
     info = parallel.DistInfo.from_env()

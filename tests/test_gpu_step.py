@@ -394,7 +394,7 @@ def test_cfg2_composed_step_bf16_vs_oracle():
 
 
 def test_step_graph_replay_equals_eager_launches(monkeypatch):
-    """The train step replayed as six linear hipGraphs (FusedAdvStep._call_graph: temperature and noise seeds read from device memory,
+    """The train step replayed as six linear hipGraphs (GIC_STEP_GRAPH=1, FusedAdvStep._call_graph: temperature and noise seeds read from device memory,
     gicap.h gic_step_scalars) against the same step as eager launches (GIC_NO_STEP_GRAPH=1): fp32, device-drawn noise from the same
     seed sequence, five steps (eager, capture, three replays) with the temperature changing every step (training.py:183).  Step 0's
     losses and token ids are exact; later steps carry the f32-atomic summation order of D's weight gradients (not reproducible run to
@@ -410,6 +410,7 @@ def test_step_graph_replay_equals_eager_launches(monkeypatch):
             monkeypatch.setenv("GIC_NO_STEP_GRAPH", "1")
         else:
             monkeypatch.delenv("GIC_NO_STEP_GRAPH", raising=False)
+            monkeypatch.setenv("GIC_STEP_GRAPH", "1")      # opt-in (fused_step.py)
         inst, args = make_instructor(m, "fused")
         assert inst.fused.use_graph == (mode == "graph")
         dev = args.device
