@@ -185,6 +185,10 @@ _SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p]),
     "gic_xent": (C.c_int, [c_void_p, C.c_int, C.c_int64, C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_rollout_rewards": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
+    "gic_set_deterministic": (C.c_int, [C.c_int]),
+    "gic_get_deterministic": (C.c_int, []),
+    "gic_bn_stats_slab_floats": (C.c_int, [C.c_int64, C.c_int32, c_void_p]),
+    "gic_bn_stats": (C.c_int, [c_void_p, C.c_int, C.c_int64, C.c_int32, c_void_p, c_void_p, c_void_p]),
     "gic_clip_adam_partials": (C.c_int64, [C.c_int64]),
     "gic_clip_adam": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
                                 C.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),

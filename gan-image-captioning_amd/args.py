@@ -85,6 +85,9 @@ _NATIVE = [
     ("--resume", str, "", "checkpoint to start from: adv_model.ckpt ({generator, discriminator}) or pretrained_model.ckpt "
                           "(generator state dict), in the reference's format (training.py:118,225-226); the reference cannot resume"),
     ("--seed", int, 1008, "RNG seed (src/main.py:14 fixes 1008)"),
+    ("--deterministic", int, 0, "bit-reproducible train steps (the reference's cudnn.deterministic, src/main.py:22-23): fixed-order "
+                                "reductions instead of f32 atomics; 0 leaves the process-wide mode as it is (GIC_DETERMINISTIC=1 sets it "
+                                "at load)", {"choices": [0, 1]}),
     ("--num-workers", int, 4, "DataLoader workers (training.py:28-32 uses 4)"),
 ]
 

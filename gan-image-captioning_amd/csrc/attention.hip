@@ -434,6 +434,14 @@ int attn_bwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S
 
 using namespace gic;
 
+// The attention decoder's per-step products add f32 partials atomically (split-K into a zeroed C): it has no deterministic form,
+// so the deterministic mode refuses it instead of leaving it silently run-to-run variable.
+static int attn_det_refused(const char* what) {
+  if (!gic::det_mode()) return GIC_STATUS_OK;
+  gic::set_last_error("%s: the attention decoder is not available in the deterministic mode (gic_set_deterministic)", what);
+  return GIC_STATUS_UNSUPPORTED;
+}
+
 extern "C" {
 
 int gic_attn_prepare(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, void* stream_) {
@@ -458,6 +466,7 @@ int gic_attn_sample_fwd(const gic_attn_dims* dims, const gic_attn_params* P, con
                         void* out, int64_t* ids, const float* h0, const float* c0, const gic_step_scalars* dev_scalars, int seed_slot,
                         void* stream) {
   ACtx c;
+  GIC_PROPAGATE(attn_det_refused("attn_sample_fwd"));
   GIC_PROPAGATE(check_attn_dims(dims, c));
   GIC_CHECK_ARG(!dev_scalars || (seed_slot >= 0 && seed_slot < GIC_STEP_SEEDS), "attn_sample_fwd: seed_slot out of range");
   const float* t_dev = dev_scalars ? &dev_scalars->temperature : nullptr;
@@ -474,6 +483,7 @@ int gic_attn_sample_bwd(const gic_attn_dims* dims, const gic_attn_params* P, con
                         const gic_attn_bwd_ws* ws, const void* fmap, const void* probs, const int64_t* ids, const void* d_out,
                         float temperature, int pretrain, const gic_attn_grads* G, const gic_step_scalars* dev_scalars, void* stream) {
   ACtx c;
+  GIC_PROPAGATE(attn_det_refused("attn_sample_bwd"));
   GIC_PROPAGATE(check_attn_dims(dims, c));
   const float* t_dev = dev_scalars ? &dev_scalars->temperature : nullptr;
   GIC_CHECK_ARG(P && S && st && ws && fmap && probs && ids && d_out && G, "attn_sample_bwd: null argument");

@@ -721,6 +721,8 @@ int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, co
 int embed_scatter_time(const float* dx, long ld, const int64_t* ids, float* d_embed, int B, int L, int E, int V, hipStream_t stream, long ids_stride) {
   if (ids_stride <= 0) ids_stride = L;
   GIC_PROPAGATE(fill_zero(d_embed, (size_t)V * E * sizeof(float), stream));
+  if (L > 1 && det_mode())
+    return det_scatter(dx, DT_F32, ld, B, ids, B, ids_stride, 1, (long)(L - 1) * B, d_embed, E, 1, E, V, stream);
   if (L > 1) {
     const long total = (long)(L - 1) * B * E;
     const int grid = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);

@@ -417,7 +417,7 @@ __global__ __launch_bounds__(256) void disc_conv_pool_bwd_x_small_kernel(const f
 template <typename TA, int MAXT>
 __global__ __launch_bounds__(256) void disc_conv_pool_bwd_w_kernel(const float* __restrict__ dpooled, const TA* __restrict__ pooled,
                                                                      const uint8_t* __restrict__ argmax, const float* __restrict__ emb,
-                                                                     ConvMeta cm, int L, int De, int R, long rows) {
+                                                                     ConvMeta cm, int L, int De, int R, long rows, float* __restrict__ part) {
   __shared__ float red[4][64][MAXT + 1];
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6, s = cm.s;
   const int col = blockIdx.x * 64 + cx;
@@ -444,7 +444,10 @@ __global__ __launch_bounds__(256) void disc_conv_pool_bwd_w_kernel(const float* 
 #pragma unroll
   for (int j = 0; j <= MAXT; ++j) red[ry][cx][j] = acc[j];
   __syncthreads();
-  if (ry == 0 && col < cm.F) {
+  if (ry == 0 && col < cm.F && part) {       // deterministic mode: this block row's partials, folded in row order by disc_wgrad_fold
+    float* pp = part + ((long)blockIdx.y * cm.F + col) * (MAXT + 1);
+    for (int j = 0; j <= MAXT; ++j) pp[j] = red[0][cx][j] + red[1][cx][j] + red[2][cx][j] + red[3][cx][j];
+  } else if (ry == 0 && col < cm.F) {
     for (int j = 0; j < taps; ++j)
       atomicAdd(&cm.dw[k][(long)ch * taps + j], red[0][cx][j] + red[1][cx][j] + red[2][cx][j] + red[3][cx][j]);
     atomicAdd(&cm.db[k][ch], red[0][cx][MAXT] + red[1][cx][MAXT] + red[2][cx][MAXT] + red[3][cx][MAXT]);
@@ -460,7 +463,7 @@ __global__ __launch_bounds__(256) void disc_conv_pool_bwd_w_kernel(const float* 
 template <typename TA, int MAXT>
 __global__ __launch_bounds__(256) void disc_conv_pool_bwd_w_lds_kernel(const float* __restrict__ dpooled, const TA* __restrict__ pooled,
                                                                          const uint8_t* __restrict__ argmax, const float* __restrict__ emb,
-                                                                         ConvMeta cm, int L, int De, int R, int ncap) {
+                                                                         ConvMeta cm, int L, int De, int R, int ncap, float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float xs[];       // [R][LP], LP = L + MAXT | 1 (zero beyond L)
   __shared__ float red[4][64][MAXT + 1];
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
@@ -508,7 +511,10 @@ __global__ __launch_bounds__(256) void disc_conv_pool_bwd_w_lds_kernel(const flo
 #pragma unroll
   for (int j = 0; j <= MAXT; ++j) red[ry][cx][j] = acc[j];
   __syncthreads();
-  if (ry == 0 && okc) {
+  if (ry == 0 && okc && part) {             // deterministic mode: this block row's partials, folded in row order by disc_wgrad_fold
+    float* pp = part + ((long)blockIdx.y * cm.F + col) * (MAXT + 1);
+    for (int j = 0; j <= MAXT; ++j) pp[j] = red[0][cx][j] + red[1][cx][j] + red[2][cx][j] + red[3][cx][j];
+  } else if (ry == 0 && okc) {
     for (int j = 0; j < taps; ++j)
       atomicAdd(&cm.dw[k][(long)ch * taps + j], red[0][cx][j] + red[1][cx][j] + red[2][cx][j] + red[3][cx][j]);
     atomicAdd(&cm.db[k][ch], red[0][cx][MAXT] + red[1][cx][MAXT] + red[2][cx][MAXT] + red[3][cx][MAXT]);
@@ -529,7 +535,8 @@ __global__ void disc_out_fwd_kernel(const float* __restrict__ feat, const float*
 template <typename TA>
 __global__ __launch_bounds__(256) void disc_out_bwd_kernel(const float* __restrict__ dlogits, const float* __restrict__ feat,
                                                              const float* __restrict__ w, TA* __restrict__ dfeat,
-                                                             float* __restrict__ dw, float* __restrict__ db, long rows) {
+                                                             float* __restrict__ dw, float* __restrict__ db, long rows,
+                                                             float* __restrict__ part) {
   __shared__ float red[2][128];
   const int j = threadIdx.x & 127, half = threadIdx.x >> 7;
   float aw = 0.f, ab = 0.f;
@@ -543,11 +550,42 @@ __global__ __launch_bounds__(256) void disc_out_bwd_kernel(const float* __restri
   if (!dw) return;
   red[half][j] = aw;
   __syncthreads();
-  if (half == 0 && j < kOutDim) atomicAdd(&dw[j], red[0][j] + red[1][j]);
+  if (half == 0 && j < kOutDim) {
+    if (part) part[(long)blockIdx.x * (kOutDim + 1) + j] = red[0][j] + red[1][j];      // deterministic mode: disc_out_fold
+    else atomicAdd(&dw[j], red[0][j] + red[1][j]);
+  }
   __syncthreads();
   red[half][j] = ab;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(db, red[0][0] + red[1][0]);
+  if (threadIdx.x == 0) {
+    if (part) part[(long)blockIdx.x * (kOutDim + 1) + kOutDim] = red[0][0] + red[1][0];
+    else atomicAdd(db, red[0][0] + red[1][0]);
+  }
+}
+
+// Deterministic mode: dw[j] += sum over the nb blocks' partials part[b][j] in block order (j == kOutDim: db)
+__global__ void disc_out_fold_kernel(const float* __restrict__ part, int nb, float* __restrict__ dw, float* __restrict__ db) {
+  const int j = threadIdx.x;
+  if (j > kOutDim) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int b = 0; b < nb; ++b) s += part[(long)b * (kOutDim + 1) + j];
+  if (j < kOutDim) dw[j] += s; else db[0] += s;
+}
+
+// Deterministic mode: the conv weight / bias gradients from part[gy][F][mt1] (mt1 = the kernel's MAXT + 1; entry MAXT = bias) in
+// block-row order: one thread per (filter, tap)
+__global__ void disc_wgrad_fold_kernel(const float* __restrict__ part, int gy, int mt1, ConvMeta cm) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)cm.F * mt1) return;
+  const int col = (int)(i / mt1), j = (int)(i % mt1);
+  const int k = conv_of(cm, col), taps = cm.fsize[k] * cm.s, ch = col - cm.foff[k];
+  if (j >= taps && j != mt1 - 1) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int y = 0; y < gy; ++y) s += part[((long)y * cm.F + col) * mt1 + j];
+  if (j == mt1 - 1) cm.db[k][ch] += s;
+  else cm.dw[k][(long)ch * taps + j] += s;
 }
 
 // ---- highway backward pointwise (discriminator.py:53-58 differentiated):
@@ -781,9 +819,23 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
     if (inp_ids) GIC_PROPAGATE(fill_zero(G->emb, (size_t)c.De * c.V * sizeof(float), stream));
   }
   // 1. out2logits backward
-  hipLaunchKernelGGL((disc_out_bwd_kernel<TA>), dim3(256), dim3(256), 0, stream, d_logits, (const float*)st->feat, P->o2l_w,
-                     (TA*)ws->dfeat, G ? G->o2l_w : nullptr, G ? G->o2l_b : nullptr, MR);
+  // deterministic mode: the blocks' partials of the output-layer gradients go to ws->dydrop (free until step 2 writes it, MR * Fp
+  // floats) and are folded in block order, with as many blocks as it holds partials for (the kernel strides its rows over the grid);
+  // room for one block only: that block adds into the zeroed / accumulated gradient alone (one add per address, no order).  The conv
+  // weight gradients (step 4) and the column sums reuse dydrop / dh the same way (each free at that point).
+  const bool det = G && det_mode();
+  const long dy_floats = MR * c.Fp;
+  int out_blocks = 256;
+  if (det && (long)out_blocks * (kOutDim + 1) > dy_floats) out_blocks = (int)(dy_floats / (kOutDim + 1));
+  if (out_blocks < 1) out_blocks = 1;
+  const bool out_part = det && out_blocks > 1;
+  hipLaunchKernelGGL((disc_out_bwd_kernel<TA>), dim3(out_blocks), dim3(256), 0, stream, d_logits, (const float*)st->feat, P->o2l_w,
+                     (TA*)ws->dfeat, G ? G->o2l_w : nullptr, G ? G->o2l_b : nullptr, MR, out_part ? ws->dydrop : nullptr);
   GIC_CHECK_LAUNCH("disc_out_bwd");
+  if (out_part) {
+    hipLaunchKernelGGL(disc_out_fold_kernel, dim3(1), dim3(128), 0, stream, (const float*)ws->dydrop, out_blocks, G->o2l_w, G->o2l_b);
+    GIC_CHECK_LAUNCH("disc_out_fold");
+  }
   // 2. feature2out backward
   {
     GemmDesc g;   // dydrop[MR, Fp] = dfeat[MR,104] f2o_w[104, Fp]
@@ -795,7 +847,9 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
       w.A = ws->dfeat; w.lda = kOutPad; w.a_kc = 0; w.B = st->ydrop; w.ldb = c.Fp; w.b_kc = 0; w.C = G->f2o_w; w.ldc = c.F;
       w.M = kOutDim; w.N = c.F; w.K = (int)MR; w.in_dtype = c.dt; w.out_dtype = DT_F32; w.accumulate = accumulate;
       GIC_PROPAGATE(gemm(w, stream));
-      GIC_PROPAGATE(colsum(ws->dfeat, c.dt, kOutPad, MR, kOutDim, G->f2o_b, nullptr, accumulate, stream));
+      // (ws->dh is free until step 3 writes it: the deterministic mode's column-sum partials)
+      GIC_PROPAGATE(colsum(ws->dfeat, c.dt, kOutPad, MR, kOutDim, G->f2o_b, nullptr, accumulate, stream, (float*)ws->dh,
+                           (long)(MR * c.Fp * dtype_size(c.dt) / sizeof(float))));
     }
   }
   // 3. highway backward
@@ -821,7 +875,8 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
       w.A = ws->dh; w.lda = c.Fp; w.a_kc = 0; w.B = st->pooled; w.ldb = c.Fp; w.b_kc = 0; w.C = G->hw_w; w.ldc = c.F;
       w.M = c.F; w.N = c.F; w.K = (int)MR; w.in_dtype = c.dt; w.out_dtype = DT_F32; w.accumulate = accumulate;
       GIC_PROPAGATE(gemm(w, stream));
-      GIC_PROPAGATE(colsum(ws->dh, c.dt, c.Fp, MR, c.F, G->hw_b, nullptr, accumulate, stream));
+      // (ws->dydrop is free after the highway backward: the deterministic mode's column-sum partials)
+      GIC_PROPAGATE(colsum(ws->dh, c.dt, c.Fp, MR, c.F, G->hw_b, nullptr, accumulate, stream, ws->dydrop, (long)(MR * c.Fp)));
     }
   }
   // 4. conv / pool backward
@@ -831,18 +886,31 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
     int mt = 0;
     for (int k = 0; k < c.cm.nconv; ++k) mt = c.cm.fsize[k] * c.s > mt ? c.cm.fsize[k] * c.s : mt;
     static const bool no_lds = getenv("GIC_NO_DISC_BWDW_LDS") != nullptr;
-    if (mt <= 8 && c.s == 1 && c.R <= 64 && c.R <= c.De && MR % c.R == 0 && c.L <= 64 && !no_lds) {
-      const int ncap = (int)(MR / c.R);
-      hipLaunchKernelGGL((disc_conv_pool_bwd_w_lds_kernel<TA, 8>), dim3(cdiv(c.F, 64), ncap < 64 ? ncap : 64), dim3(256),
+    const bool lds = mt <= 8 && c.s == 1 && c.R <= 64 && c.R <= c.De && MR % c.R == 0 && c.L <= 64 && !no_lds;
+    const int ncap = (int)(MR / c.R);
+    const int mt1 = (mt <= 8 ? 8 : kMaxTaps) + 1;
+    int rows_y = lds ? (ncap < 64 ? ncap : 64) : gy;
+    // deterministic mode: as many block rows as dydrop holds partials for (the kernels stride over gridDim.y); one block row adds
+    // alone (one add per address)
+    if (det && (long)rows_y * c.F * mt1 > dy_floats) rows_y = (int)(dy_floats / ((long)c.F * mt1));
+    if (rows_y < 1) rows_y = 1;
+    gy = lds ? gy : rows_y;
+    float* part = det && rows_y > 1 ? ws->dydrop : nullptr;
+    if (lds) {
+      hipLaunchKernelGGL((disc_conv_pool_bwd_w_lds_kernel<TA, 8>), dim3(cdiv(c.F, 64), rows_y), dim3(256),
                          (size_t)c.R * ((c.L + 8) | 1) * sizeof(float), stream, (const float*)ws->dpooled, (const TA*)st->pooled,
-                         (const uint8_t*)st->argmax, (const float*)st->emb, c.cm, c.L, c.De, c.R, ncap);
+                         (const uint8_t*)st->argmax, (const float*)st->emb, c.cm, c.L, c.De, c.R, ncap, part);
     } else if (mt <= 8)
       hipLaunchKernelGGL((disc_conv_pool_bwd_w_kernel<TA, 8>), dim3(cdiv(c.F, 64), gy), dim3(256), 0, stream, (const float*)ws->dpooled,
-                         (const TA*)st->pooled, (const uint8_t*)st->argmax, (const float*)st->emb, c.cm, c.L, c.De, c.R, MR);
+                         (const TA*)st->pooled, (const uint8_t*)st->argmax, (const float*)st->emb, c.cm, c.L, c.De, c.R, MR, part);
     else
       hipLaunchKernelGGL((disc_conv_pool_bwd_w_kernel<TA, kMaxTaps>), dim3(cdiv(c.F, 64), gy), dim3(256), 0, stream, (const float*)ws->dpooled,
-                         (const TA*)st->pooled, (const uint8_t*)st->argmax, (const float*)st->emb, c.cm, c.L, c.De, c.R, MR);
+                         (const TA*)st->pooled, (const uint8_t*)st->argmax, (const float*)st->emb, c.cm, c.L, c.De, c.R, MR, part);
     GIC_CHECK_LAUNCH("disc_conv_pool_bwd_w");
+    if (part) {
+      hipLaunchKernelGGL(disc_wgrad_fold_kernel, dim3(cdiv((long)c.F * mt1, 256)), dim3(256), 0, stream, (const float*)ws->dydrop, rows_y, mt1, c.cm);
+      GIC_CHECK_LAUNCH("disc_wgrad_fold");
+    }
   }
   const int n_out = c.L * c.s;
   size_t conv_w_total = 0;
@@ -868,18 +936,26 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
       // mixed batch (one backward for the step's real and fake passes): the first half of the captions came in as token ids,
       // the second half as soft rows; the gathered half scatters first (G->emb zeroed above or accumulated into)
       const long half = c.rowsBL / 2;
-      hipLaunchKernelGGL(disc_emb_scatter_kernel, dim3(grid1d(half * c.De)), dim3(256), 0, stream, (const float*)nullptr,
-                         (const void*)ws->demb, c.dt, inp_ids, G->emb, half, c.De, c.V);
-      GIC_CHECK_LAUNCH("disc_emb_scatter");
+      if (det_mode()) {
+        GIC_PROPAGATE(det_scatter(ws->demb, c.dt, c.De, 0, inp_ids, (int)half, 1, 0, half, G->emb, 1, c.V, c.De, c.V, stream));
+      } else {
+        hipLaunchKernelGGL(disc_emb_scatter_kernel, dim3(grid1d(half * c.De)), dim3(256), 0, stream, (const float*)nullptr,
+                           (const void*)ws->demb, c.dt, inp_ids, G->emb, half, c.De, c.V);
+        GIC_CHECK_LAUNCH("disc_emb_scatter");
+      }
       GemmDesc w;   // dW_emb[De, V] += demb[half:]^T inp
       w.A = (const char*)ws->demb + (size_t)half * c.De * dtype_size(c.dt); w.lda = c.De; w.a_kc = 0; w.B = inp_soft; w.ldb = ld_inp; w.b_kc = 0;
       w.C = G->emb; w.ldc = c.V;
       w.M = c.De; w.N = c.V; w.K = (int)half; w.in_dtype = c.dt; w.out_dtype = DT_F32; w.accumulate = 1;
       GIC_PROPAGATE(gemm(w, stream));
     } else if (inp_ids) {
-      hipLaunchKernelGGL(disc_emb_scatter_kernel, dim3(grid1d(c.rowsBL * c.De)), dim3(256), 0, stream, (const float*)nullptr,
-                         (const void*)ws->demb, c.dt, inp_ids, G->emb, c.rowsBL, c.De, c.V);
-      GIC_CHECK_LAUNCH("disc_emb_scatter");
+      if (det_mode()) {
+        GIC_PROPAGATE(det_scatter(ws->demb, c.dt, c.De, 0, inp_ids, (int)c.rowsBL, 1, 0, c.rowsBL, G->emb, 1, c.V, c.De, c.V, stream));
+      } else {
+        hipLaunchKernelGGL(disc_emb_scatter_kernel, dim3(grid1d(c.rowsBL * c.De)), dim3(256), 0, stream, (const float*)nullptr,
+                           (const void*)ws->demb, c.dt, inp_ids, G->emb, c.rowsBL, c.De, c.V);
+        GIC_CHECK_LAUNCH("disc_emb_scatter");
+      }
     } else {
       GemmDesc w;   // dW_emb[De, V] = demb^T inp
       w.A = ws->demb; w.lda = c.De; w.a_kc = 0; w.B = inp_soft; w.ldb = ld_inp; w.b_kc = 0; w.C = G->emb; w.ldc = c.V;

@@ -18,6 +18,7 @@
 #include "conv1x1_pix.h"
 #include "conv_stem.h"
 #include "bn_fold.h"
+#include "kernels.h"
 
 #include <stdlib.h>
 
@@ -1180,6 +1181,9 @@ int launch(const GemmDesc& d, hipStream_t stream) {
       splits = 768 / tiles;                      // K = 2B*R = 8192): ~3 blocks per CU, 87 -> 47 us (tools/gemm_hw_bench.py)
     }
     if (splits < 1) splits = 1;
+    // deterministic mode: two splits add onto a zeroed C in either order to the same bits, ((0 + a) + b == (0 + b) + a); more
+    // splits, or two onto a C being accumulated into, do not
+    if (det_mode()) splits = (d.accumulate || splits < 2) ? 1 : 2;
   }
   int per = cdiv(nk, splits);
   splits = cdiv(nk, per);

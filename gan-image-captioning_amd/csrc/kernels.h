@@ -8,9 +8,10 @@ namespace gic {
 // dst[r*ldd + c] = cast(src[r*lds + c])
 int cast2d(const void* src, int src_dtype, long lds, void* dst, int dst_dtype, long ldd, long rows, long cols,
            hipStream_t stream);
-// out[c] (+)= sum_r A[r*lda + c]   (A in `dtype`, out f32; out2 optional second destination)
+// out[c] (+)= sum_r A[r*lda + c]   (A in `dtype`, out f32; out2 optional second destination).  scratch (optional, scratch_floats
+// f32): room for the deterministic mode's per-block-row partials (without it that mode runs at most two block rows)
 int colsum(const void* A, int dtype, long lda, long rows, long cols, float* out, float* out2, int accumulate,
-           hipStream_t stream);
+           hipStream_t stream, float* scratch = nullptr, long scratch_floats = 0);
 int embedding_fwd(const float* weight, const int64_t* ids, float* out, long n, int V, int E, hipStream_t stream);
 int embedding_bwd(const float* d_out, const int64_t* ids, float* d_weight, long n, int V, int E, int zero_first,
                   hipStream_t stream);
@@ -21,6 +22,11 @@ int transpose2d(const void* src, void* dst, int dtype, long rows, long cols, hip
 // decoder.hip internals shared with attention.hip
 int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, const void* d_out, float temperature, const float* t_dev, int pretrain,
                        void* dlogits_ws, const void* wout, const void* hout, float* dhout, float* d_wout, float* d_bout, hipStream_t stream);
+// determinism.hip: the process-wide deterministic mode (gic_set_deterministic) and its ordered embedding scatter:
+// dst[id(r) * d_id + e * d_e] += sum over tokens r of src[(r + row_off) * ld + e] (ascending r), id(r) = ids[(r % B) * s_b + (r / B) * s_t]
+int det_mode();
+int det_scatter(const void* src, int dt, long ld, long row_off, const int64_t* ids, int B, long s_b, long s_t, long n, float* dst,
+                long d_id, long d_e, int E, int V, hipStream_t stream);
 int embed_scatter_time(const float* dx, long ld, const int64_t* ids, float* d_embed, int B, int L, int E, int V, hipStream_t stream, long ids_stride = 0);
 
 }  // namespace gic

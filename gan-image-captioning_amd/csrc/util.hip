@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void cast2d_f32_bf16_vec_kernel(const float* _
 // ---- column sums: block = 64 columns x 4 row-lanes; rows strided over gridDim.y blocks, f32 atomics across them
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ A, long lda, long rows, long cols,
-                                                       float* __restrict__ out, float* __restrict__ out2) {
+                                                       float* __restrict__ out, float* __restrict__ out2, float* __restrict__ part) {
   __shared__ float red[4][64];
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
   const long c = (long)blockIdx.x * 64 + cx;
@@ -85,6 +85,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ A, lo
   __syncthreads();
   if (ry == 0 && c < cols) {
     const float t = red[0][cx] + red[1][cx] + red[2][cx] + red[3][cx];
+    if (part) { part[(long)blockIdx.y * cols + c] = t; return; }     // deterministic mode: colsum_fold_kernel adds them in row order
     atomicAdd(&out[c], t);
     if (out2) atomicAdd(&out2[c], t);
   }
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ A, lo
 // per thread; block = 32 column groups x 8 row lanes.  (The scalar kernel above keeps one 2-byte load per thread in flight.)
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_vec_kernel(const T* __restrict__ A, long lda, long rows, long cols,
-                                                           float* __restrict__ out, float* __restrict__ out2) {
+                                                           float* __restrict__ out, float* __restrict__ out2, float* __restrict__ part) {
   constexpr int VN = 16 / (int)sizeof(T);
   __shared__ float red[8][32][VN + 1];
   const int cg = threadIdx.x & 31, ry = threadIdx.x >> 5;
@@ -128,10 +129,22 @@ __global__ __launch_bounds__(256) void colsum_vec_kernel(const T* __restrict__ A
       float t = 0.f;
 #pragma unroll
       for (int q = 0; q < 8; ++q) t += red[q][cg][k];
+      if (part) { part[(long)blockIdx.y * cols + c0 + k] = t; continue; }
       atomicAdd(&out[c0 + k], t);
       if (out2) atomicAdd(&out2[c0 + k], t);
     }
   }
+}
+
+// Deterministic mode: out[c] (and out2[c]) += the gy block rows' partials part[y][c], added in row order
+__global__ void colsum_fold_kernel(const float* __restrict__ part, int gy, long cols, float* __restrict__ out, float* __restrict__ out2) {
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= cols) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int y = 0; y < gy; ++y) s += part[(long)y * cols + c];
+  out[c] += s;
+  if (out2) out2[c] += s;
 }
 
 __global__ void embedding_fwd_kernel(const float* __restrict__ w, const int64_t* __restrict__ ids, float* __restrict__ out,
@@ -209,8 +222,30 @@ int cast2d(const void* src, int sdt, long lds, void* dst, int ddt, long ldd, lon
   return GIC_OK;
 }
 
+// Deterministic mode.  With scratch for a [gy][cols] slab: every block row stores its partials and colsum_fold_kernel adds them in
+// row order (gy capped at 64: the fold walks them serially).  Without: at most two block rows add into each column, and two only onto
+// the zeroed output, (0 + a) + b == (0 + b) + a, while three or more f32 adds (or two onto a value being accumulated into) depend on
+// their order.
+static int colsum_fold(const float* part, int gy, long cols, float* out, float* out2, hipStream_t stream) {
+  hipLaunchKernelGGL(colsum_fold_kernel, dim3((unsigned)cdiv(cols, 256)), dim3(256), 0, stream, part, gy, cols, out, out2);
+  GIC_CHECK_LAUNCH("colsum_fold");
+  return GIC_OK;
+}
+
+static int det_colsum_rows(int gy, int accumulate, long cols, long scratch_floats, bool* slab) {
+  int g = gy < 64 ? gy : 64;
+  if (g > 1 && scratch_floats / cols >= 2) {
+    if (g > scratch_floats / cols) g = (int)(scratch_floats / cols);
+    *slab = true;
+    return g;
+  }
+  *slab = false;
+  const int cap = accumulate ? 1 : 2;
+  return gy < cap ? gy : cap;
+}
+
 int colsum(const void* A, int dtype, long lda, long rows, long cols, float* out, float* out2, int accumulate,
-           hipStream_t stream) {
+           hipStream_t stream, float* scratch, long scratch_floats) {
   GIC_CHECK_ARG(A && out, "colsum: null pointer");
   if (cols == 0) return GIC_OK;
   if (!accumulate) {
@@ -219,28 +254,35 @@ int colsum(const void* A, int dtype, long lda, long rows, long cols, float* out,
   }
   if (rows == 0) return GIC_OK;
   const int vn = 16 / dtype_size(dtype);
+  bool slab = false;
+  float* part = nullptr;
+  if (!scratch) scratch_floats = 0;
   if (cols % vn == 0 && lda % vn == 0 && (((uintptr_t)A) & 15) == 0) {
     const int gx = cdiv(cols / vn, 32);
     int gy = cdiv(rows, 8 * 8);
     const int want = 2048 / (gx < 1 ? 1 : gx);
     gy = gy > want ? (want < 1 ? 1 : want) : gy;
+    if (det_mode()) gy = det_colsum_rows(gy, accumulate, cols, scratch_floats, &slab);
+    part = slab ? scratch : nullptr;
     if (dtype == DT_F32)
-      hipLaunchKernelGGL((colsum_vec_kernel<float>), dim3(gx, gy), dim3(256), 0, stream, (const float*)A, lda, rows, cols, out, out2);
+      hipLaunchKernelGGL((colsum_vec_kernel<float>), dim3(gx, gy), dim3(256), 0, stream, (const float*)A, lda, rows, cols, out, out2, part);
     else
-      hipLaunchKernelGGL((colsum_vec_kernel<bf16_t>), dim3(gx, gy), dim3(256), 0, stream, (const bf16_t*)A, lda, rows, cols, out, out2);
+      hipLaunchKernelGGL((colsum_vec_kernel<bf16_t>), dim3(gx, gy), dim3(256), 0, stream, (const bf16_t*)A, lda, rows, cols, out, out2, part);
     GIC_CHECK_LAUNCH("colsum");
-    return GIC_OK;
+    return slab ? colsum_fold(part, gy, cols, out, out2, stream) : GIC_OK;
   }
   const int gx = cdiv(cols, 64);
   int gy = cdiv(rows, 4 * 16);
   const int want = 1024 / (gx < 1 ? 1 : gx);
   gy = gy > want ? (want < 1 ? 1 : want) : gy;
+  if (det_mode()) gy = det_colsum_rows(gy, accumulate, cols, scratch_floats, &slab);
+  part = slab ? scratch : nullptr;
   if (dtype == DT_F32)
-    hipLaunchKernelGGL((colsum_kernel<float>), dim3(gx, gy), dim3(256), 0, stream, (const float*)A, lda, rows, cols, out, out2);
+    hipLaunchKernelGGL((colsum_kernel<float>), dim3(gx, gy), dim3(256), 0, stream, (const float*)A, lda, rows, cols, out, out2, part);
   else
-    hipLaunchKernelGGL((colsum_kernel<bf16_t>), dim3(gx, gy), dim3(256), 0, stream, (const bf16_t*)A, lda, rows, cols, out, out2);
+    hipLaunchKernelGGL((colsum_kernel<bf16_t>), dim3(gx, gy), dim3(256), 0, stream, (const bf16_t*)A, lda, rows, cols, out, out2, part);
   GIC_CHECK_LAUNCH("colsum");
-  return GIC_OK;
+  return slab ? colsum_fold(part, gy, cols, out, out2, stream) : GIC_OK;
 }
 
 int embedding_fwd(const float* weight, const int64_t* ids, float* out, long n, int V, int E, hipStream_t stream) {
@@ -256,6 +298,7 @@ int embedding_bwd(const float* d_out, const int64_t* ids, float* d_weight, long 
   GIC_CHECK_ARG(d_out && ids && d_weight, "embedding_bwd: null pointer");
   if (zero_first) GIC_PROPAGATE(fill_zero(d_weight, (size_t)V * E * sizeof(float), stream));
   if (n * E == 0) return GIC_OK;
+  if (det_mode()) return det_scatter(d_out, DT_F32, E, 0, ids, (int)n, 1, 0, n, d_weight, E, 1, E, V, stream);
   hipLaunchKernelGGL(embedding_bwd_kernel, dim3(grid_for(n * E)), dim3(256), 0, stream, d_out, ids, d_weight, n, V, E);
   GIC_CHECK_LAUNCH("embedding_bwd");
   return GIC_OK;

@@ -105,6 +105,7 @@ class TrunkPlan:
         self.b2b_only = int(os.environ.get("GIC_B2B_ONLY", "0"))     # tuning: 0 = every boundary the kernels take, 1 = the 28 x 28 blocks only,
         # 2 = all but the 56 x 56 boundary into 128 output channels
         self._nrep = {}
+        self._det = False        # deterministic mode of the current pass (engine.set_deterministic): set by forward()
         self.use_graph = not os.environ.get("GIC_NO_GRAPH")
         self.pending_tracked = 0
         self.conv_trace = None      # measurement (bench.py): a list -> (layer name, start event, stop event) per convolution launch
@@ -135,8 +136,13 @@ class TrunkPlan:
         self._wkey = key
 
     # ---------------------------------------------------------------- buffers for one (batch, image size)
+    def _bkey(self, N: int, S: int) -> tuple:
+        """Buffer-set key: (N, S), and (N, S, "det") for the deterministic mode's own set (its statistics run with one replica)."""
+        return (N, S, "det") if self._det else (N, S)
+
     def _buffers(self, N: int, S: int, dev) -> dict:
-        key = (N, S)
+        key = self._bkey(N, S)
+        self._cur = key
         if key in self._bufs:
             self._nrep = self._bufs[key]["nrep"]
             self._running_table(self._bufs[key], dev)
@@ -184,6 +190,16 @@ class TrunkPlan:
         for s in self.steps:
             tiles = -(-rows[s.name] // 128) * -(-s.cout // 128)
             b["nrep"][s.name] = STATS_REPLICAS if tiles > 1024 else (mid if tiles > 256 else lo)
+        if self._det:
+            # deterministic mode: every layer's sums come from gic_bn_stats (fixed order, one replica) through one scratch slab that
+            # the layers take in turn (they run in order on one stream)
+            need = C.c_int64()
+            slab = 0
+            for s in self.steps:
+                _check(L.load().gic_bn_stats_slab_floats(rows[s.name], s.cout, C.byref(need)), "gic_bn_stats_slab_floats")
+                slab = max(slab, need.value)
+                b["nrep"][s.name] = 1
+            b["det_slab"] = torch.empty(slab, device=dev, dtype=torch.float32)
         self._running_table(b, dev)
         self._bufs[key] = b
         self._nrep = b["nrep"]
@@ -218,6 +234,15 @@ class TrunkPlan:
 
     def _conv(self, s: _ConvStep, x: torch.Tensor, y: torch.Tensor, stats: Optional[torch.Tensor], N, H, W, cin=None, kw=None, pad=None):
         st = None if stats is None else stats.data_ptr() + 4 * s.stats_off
+        if self._det and st is not None:
+            # deterministic mode: the convolution without its atomic statistics epilogue, then the ordered column sums of its output
+            with self._traced(s.name):
+                _check(L.load().gic_conv2d(ptr(x), ptr(s.w), ptr(y), None, 1, self.dtype, N, H, W, cin if cin is not None else s.cin, s.cout, s.k,
+                                           kw if kw is not None else s.k, s.stride, pad if pad is not None else s.pad, stream_ptr()), "gic_conv2d " + s.name)
+            b = self._bufs[self._cur]
+            _check(L.load().gic_bn_stats(ptr(y), self.dtype, y.numel() // s.cout, s.cout, ptr(b["det_slab"]), st, stream_ptr()),
+                   "gic_bn_stats " + s.name)
+            return
         with self._traced(s.name):
             _check(L.load().gic_conv2d(ptr(x), ptr(s.w), ptr(y), st, self._nrep[s.name], self.dtype, N, H, W, cin if cin is not None else s.cin, s.cout, s.k,
                                        kw if kw is not None else s.k, s.stride, pad if pad is not None else s.pad, stream_ptr()), "gic_conv2d " + s.name)
@@ -225,7 +250,7 @@ class TrunkPlan:
     def _bn_relu_conv(self, prev: _ConvStep, y_prev, z_prev, s: _ConvStep, y, stats, training: bool, N, H, W, rows_prev) -> None:
         """z = relu(bn_prev(y_prev)); y = conv_s(z).  In bf16 training mode the normalisation rides in the convolution's A-operand
         path (gic_conv2d_bn_in: z_prev is never written); otherwise bn_act + convolution."""
-        if training and self.fuse_in and s.fused_in is not False and self.dtype != L.F32:
+        if training and self.fuse_in and s.fused_in is not False and self.dtype != L.F32 and not self._det:
             base = stats.data_ptr()
             with self._traced(s.name):
                 status = L.load().gic_conv2d_bn_in(ptr(y_prev), base + 4 * prev.stats_off, self._nrep[prev.name], ptr(prev.bn.weight.detach()),
@@ -277,7 +302,7 @@ class TrunkPlan:
 
     def _b2b_ok(self, blk: dict, nxt: Optional[dict], rows_: int, training: bool) -> bool:
         """conv3 of `blk` + the block output + conv1 of `nxt` as gic_conv1x1_bn_in_stats + gic_conv_b2b (shapes the kernels exist for)."""
-        if not (training and self.fuse_res and self.fuse_b2b and self.fuse_in and self.dtype != L.F32) or nxt is None or rows_ in blk.get("b2b_refused", ()):
+        if not (training and self.fuse_res and self.fuse_b2b and self.fuse_in and self.dtype != L.F32 and not self._det) or nxt is None or rows_ in blk.get("b2b_refused", ()):
             return False
         if blk["kind"] != "bottleneck" or nxt["kind"] != "bottleneck":
             return False
@@ -343,6 +368,8 @@ class TrunkPlan:
             raise ValueError("image size must be even")
         dev = images.device
         lib = L.load()
+        self._det = engine.deterministic()
+        self._cur = self._bkey(N, S)
         self._pack_weights(dev)
         b = self._buffers(N, S, dev)
         # the caller's image tensor changes from batch to batch: packed into the plan's own NHWC4 buffer outside the graph
@@ -354,7 +381,7 @@ class TrunkPlan:
 
     def last_map(self, N: int, S: int) -> torch.Tensor:
         """The last block's output [N, h, w, C] of the most recent pass at this shape (the plan's live buffer: clone to keep)."""
-        return self._bufs[(N, S)]["blocks"][-1]["out"]
+        return self._bufs[self._bkey(N, S)]["blocks"][-1]["out"]
 
     def _launch_trunk(self, b: dict, N: int, S: int, training: bool) -> None:
         """Everything behind the packed image runs on the plan's own buffers with fixed arguments: ~105 launches that
@@ -362,7 +389,7 @@ class TrunkPlan:
         The key covers every pointer baked into the graph."""
         if not self.use_graph:
             return self._run_trunk(b, N, S, training)
-        key = (N, S, bool(training), self._wkey)       # _wkey carries the trunk's pointer epoch: every pointer baked into the graph
+        key = (N, S, bool(training), self._det, self._wkey)       # _wkey carries the trunk's pointer epoch: every pointer baked into the graph
         g = self._graphs.get(key)
         if g is not None:
             g.replay()
@@ -401,7 +428,7 @@ class TrunkPlan:
                "gic_bn_relu_maxpool")
         x = b["x0"]
         pend = None     # a block output not yet materialised: (last step, raw output, shortcut, shortcut step | None, rows, out buffer)
-        fuse_res = training and self.fuse_res and self.dtype != L.F32
+        fuse_res = training and self.fuse_res and self.dtype != L.F32 and not self._det
 
         def flush():
             nonlocal pend

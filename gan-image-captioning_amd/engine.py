@@ -21,6 +21,17 @@ DTYPE_BY_NAME = {"fp32": L.F32, "f32": L.F32, "float32": L.F32, "bf16": L.BF16, 
 _param_epoch = 0   # bumped by optimizers that update weights through raw pointers
 
 
+def set_deterministic(on: bool) -> None:
+    """Process-wide deterministic mode (gic_set_deterministic): with it on, the same inputs, weights, seeds, shapes, library
+    build and device model give bit-identical results; no f32 sum has a run-to-run order.  Cached trunk and step graphs key on
+    the mode, so a change takes effect at the next call.  GIC_DETERMINISTIC=1 turns it on when the library is loaded."""
+    L.check(L.load().gic_set_deterministic(int(bool(on))), "gic_set_deterministic")
+
+
+def deterministic() -> bool:
+    return bool(L.load().gic_get_deterministic())
+
+
 def bump_param_epoch() -> None:
     global _param_epoch
     _param_epoch += 1

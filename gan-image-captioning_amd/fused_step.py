@@ -284,7 +284,7 @@ class FusedAdvStep:
     # ---------------------------------------------------------------- the step as replayed hipGraphs
     def _graph_key(self, B: int, L: int) -> tuple:
         a = self.args
-        return (B, L, self.cgan, a.adv_loss_type, int(getattr(a, "real_as_ids", 1)), self.gen_arena.flat.data_ptr(), self.disc_arena.flat.data_ptr(),
+        return (B, L, engine.deterministic(), self.cgan, a.adv_loss_type, int(getattr(a, "real_as_ids", 1)), self.gen_arena.flat.data_ptr(), self.disc_arena.flat.data_ptr(),
                 id(self.gen_opt), id(self.disc_opt), self.gen_opt.lr, self.gen_opt.clip_norm, self.disc_opt.lr, self.disc_opt.clip_norm,
                 self.den.drop_p, bool(self.gen.training), bool(self.disc.training))
 

@@ -87,6 +87,11 @@ class GANInstructor:
         if self.attention:
             if getattr(args, "adv_mode", "relgan") != "relgan":
                 raise ValueError("--decoder attention is trained with the relaxation (--adv-mode relgan)")
+        if int(getattr(args, "deterministic", 0)):
+            engine.set_deterministic(True)
+        if self.attention and engine.deterministic():
+            # the attention decoder's split-K products (attention.hip) still add f32 partials atomically
+            raise ValueError("--decoder attention is not available with --deterministic 1 (or GIC_DETERMINISTIC=1)")
         if self.dist.world_size > 1:
             parallel.broadcast_module(self.gen, self.dist)
             parallel.broadcast_module(self.disc, self.dist)

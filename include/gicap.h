@@ -494,6 +494,22 @@ int gic_bn1d_bwd(const float* dy, const float* xhat, const float* invstd, const 
 int gic_colsum(const void* A, int dtype, int64_t lda, int64_t rows, int64_t cols, float* out, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Deterministic mode (torch.backends.cudnn.deterministic, src/main.py:22-23).  Process-wide, host-only (no GPU needed), off by
+ * default; GIC_DETERMINISTIC=1 in the environment turns it on when the library is loaded.  While it is on, every entry point
+ * that accepts the call gives bit-identical results for the same inputs, shapes, library build and device model: each f32 sum
+ * that several workgroups contribute to has a fixed order (no racing f32 atomics).  Entry points without a deterministic form
+ * return GIC_STATUS_UNSUPPORTED instead (gic_attn_sample_fwd / gic_attn_sample_bwd), as do the embedding scatters beyond their
+ * limit (more than 8192 tokens, or V > 2^19).  It does not hold across GPU models or library builds.
+ * The mode is read when work is enqueued: a captured graph keeps the kernels of the mode it was captured in.
+ * gic_set_deterministic returns 0; gic_get_deterministic returns the current mode (0 / 1). */
+int gic_set_deterministic(int on);
+int gic_get_deterministic(void);
+/* BatchNorm batch statistics of y [rows, C] (C % 8 == 0) in a fixed order: stats[0..C) = column sums, stats[C..2C) = sums of
+ * squares (one replica: consumers take nrep = 1).  slab is f32 scratch of gic_bn_stats_slab_floats(rows, C) floats. */
+int gic_bn_stats_slab_floats(int64_t rows, int32_t C, int64_t* out);
+int gic_bn_stats(const void* y, int dtype, int64_t rows, int32_t C, float* slab, float* stats, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * get_losses (src/utils.py:10-53): losses[0]=g_loss, losses[1]=d_loss (device scalars) and, when the
  * d_* pointers are non-NULL, the gradients of d_loss w.r.t. (d_real, d_fake) and of g_loss w.r.t.
  * (g_out, and for rsgan d_real/d_fake through dg_real/dg_fake).
