@@ -52,6 +52,12 @@ class DecoderSampleOpts(C.Structure):
                 ("dev_scalars", c_void_p), ("seed_slot", C.c_int32)]
 
 
+class DecoderBeamOpts(C.Structure):
+    """gic_decoder_beam_opts (gic_decoder_beam_search)."""
+    _fields_ = [("beam", C.c_int32), ("eos_id", C.c_int32), ("pad_id", C.c_int32), ("length_penalty", C.c_float),
+                ("h0", c_void_p), ("c0", c_void_p)]
+
+
 STEP_SEEDS = 6
 
 
@@ -148,6 +154,9 @@ _SIGNATURES = {
     "gic_step_scalars_set": (C.c_int, [c_void_p, _P(StepScalars), c_void_p]),
     "gic_debug_decoder_step": (None, [C.c_int]),
     "gic_decoder_fused_rollout_rows": (C.c_int, [_P(DecoderDims), c_void_p]),
+    "gic_decoder_beam_ws_bytes": (C.c_int, [_P(DecoderDims), C.c_int32, c_void_p]),
+    "gic_decoder_beam_search": (C.c_int, [_P(DecoderDims), _P(DecoderParams), _P(DecoderShadow), _P(DecoderBeamOpts), c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_attn_prepare": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), c_void_p]),
     "gic_attn_sample_fwd": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), c_void_p, c_void_p, c_void_p, C.c_uint64,
                                       C.c_float, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int, c_void_p]),

@@ -89,6 +89,8 @@ _NATIVE = [
                                 "reductions instead of f32 atomics; 0 leaves the process-wide mode as it is (GIC_DETERMINISTIC=1 sets it "
                                 "at load)", {"choices": [0, 1]}),
     ("--num-workers", int, 4, "DataLoader workers (training.py:28-32 uses 4)"),
+    ("--eval-beam-size", int, 0, "beam size of the BLEU-4 evaluation (GANInstructor.evaluate) after each adversarial epoch's validation; "
+                                 "0 = off"),
 ]
 
 

@@ -1,0 +1,96 @@
+// Beam-search caption decode (gicap.h gic_decoder_beam_search): per-tile partials, per-image selection, final sort.
+//
+// One decode step over rows = B*k (row r = image r / k, beam r % k) is NL + 2 launches on the fused path:
+//   lstm_step (per layer)  the recurrent state is read from row parent[r] (reorder without a copy), layer 0's input is embed[token[r]]
+//   vocab_step_beam        the vocabulary product of vocab_step; epilogue: per (row, 64-wide tile) max, sum of exp and the tile's top-k
+//                          (logit, index) pairs, each in a fixed slot (no atomics)
+//   beam_select            one workgroup per image: merges the tile partials of its k rows (logsumexp, row top-k), builds the <= k*k
+//                          candidates, keeps the k best, writes the new scores / tokens / parents / history
+// and one launch after the last step (beam_finalize).  The generic path (shapes the fused kernels decline) replaces the first two by
+// beam_gather + the library GEMM + LSTM pointwise per layer, and the GEMM + beam_tile_topk.
+// The global top-k of a row is a subset of the union of its tile top-k sets, so the tile partials lose nothing.
+// Once every image has finished, the beam kernels of each later step (lstm_step's beam form, vocab_step_beam, beam_gather,
+// beam_tile_topk, beam_select) read the count of finished images and return at once: the launch count stays fixed.  On the generic
+// path the library GEMMs and the LSTM pointwise launches between them still run in full on stale rows; nothing reads their results.
+// The generic path's GEMMs never split K, so neither path adds f32 partials atomically.
+#pragma once
+#include <climits>
+
+#include "common.h"
+#include "decoder_step.h"
+
+namespace gic {
+
+constexpr int kBeamMax = 8;
+constexpr int kBeamTile = 64;     // vocabulary entries per tile partial (= kVocabTile)
+
+// (logit, index) order of the candidate lists: larger logit first, equal logits -> lower index (sample's first maximal index)
+__device__ __forceinline__ bool beam_better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
+
+// insert (v, i) into the sorted list (lv, li)[K]: static indices only (the lists stay in registers)
+template <int K>
+__device__ __forceinline__ void beam_insert(float (&lv)[K], int (&li)[K], float v, int i) {
+#pragma unroll
+  for (int q = 0; q < K; ++q) {
+    if (beam_better(v, i, lv[q], li[q])) {
+      const float tv = lv[q]; const int ti = li[q];
+      lv[q] = v; li[q] = i; v = tv; i = ti;
+    }
+  }
+}
+
+// butterfly merge of the lists held by lane groups: after the levels [lo, hi) every lane of a 2^hi group holds the group's top-K.
+// The lists of two partners come from disjoint index sets, so the union's top-K is well defined and both partners agree on it.
+template <int K, int LO, int HI>
+__device__ __forceinline__ void beam_merge_levels(float (&lv)[K], int (&li)[K]) {
+#pragma unroll
+  for (int o = 1 << LO; o < (1 << HI); o <<= 1) {
+    float pv[K]; int pi[K];
+#pragma unroll
+    for (int q = 0; q < K; ++q) { pv[q] = __shfl_xor(lv[q], o, 64); pi[q] = __shfl_xor(li[q], o, 64); }
+#pragma unroll
+    for (int q = 0; q < K; ++q) beam_insert<K>(lv, li, pv[q], pi[q]);
+  }
+}
+
+// (max, sum of exp(x - max)) of two parts; symmetric in its arguments, so butterfly partners compute the same bits
+__device__ __forceinline__ void lse_combine(float& m, float& s, float m2, float s2) {
+  const float mn = fmaxf(m, m2);
+  s = (m == -INFINITY ? 0.f : s * expf(m - mn)) + (m2 == -INFINITY ? 0.f : s2 * expf(m2 - mn));
+  m = mn;
+}
+
+// One (row, 64-entry tile) held by 8 consecutive lanes, 8 entries each (index INT_MAX / value -inf past V): the tile's max, sum of
+// exp and top-K, written by the group's first lane to slot (row, tile) of the partials.
+template <int K>
+__device__ __forceinline__ void beam_tile_reduce8(const float (&x)[8], const int (&ix)[8], bool store, long slot, float* part_m, float* part_s,
+                                                  float* part_v, int* part_i) {
+  float m = x[0];
+#pragma unroll
+  for (int e = 1; e < 8; ++e) m = fmaxf(m, x[e]);
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s += x[e] == -INFINITY ? 0.f : expf(x[e] - m);
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) s += __shfl_xor(s, o, 64);
+  float lv[K]; int li[K];
+#pragma unroll
+  for (int q = 0; q < K; ++q) { lv[q] = -INFINITY; li[q] = INT_MAX; }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) beam_insert<K>(lv, li, x[e], ix[e]);
+  beam_merge_levels<K, 0, 3>(lv, li);
+  if (store) {
+    part_m[slot] = m;
+    part_s[slot] = s;
+#pragma unroll
+    for (int q = 0; q < K; ++q) { part_v[slot * K + q] = lv[q]; part_i[slot * K + q] = li[q]; }
+  }
+}
+
+// the fused vocabulary product of vocab_step with the beam epilogue (decoder_step.hip): a.B = rows, a.part_m / part_s [rows][nblk],
+// a.part_v / part_i [rows][nblk][K]; a.stop / stop_at; the sampling fields (u, seed, temperature, out, rowkey) are unused
+int vocab_step_beam(const VocabStepArgs& a, int K, int dtype, hipStream_t stream);
+
+}  // namespace gic

@@ -716,6 +716,20 @@ int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, co
   return colsum(dlog, dt, V, BL, V, d_bout, nullptr, 0, stream);
 }
 
+// the roll-out's LSTM pointwise step for the beam search's generic path (beam.hip): c_prev / c_new [rows, H], h into h_next (and h_up)
+int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_new, void* h_next, long ld_next, void* h_up, long ld_up,
+                       int rows, int H, hipStream_t stream) {
+  const dim3 grid((unsigned)cdiv((long)rows * H, 256));
+  if (dt == DT_F32)
+    hipLaunchKernelGGL((lstm_pointwise_fwd_kernel<float>), grid, dim3(256), 0, stream, gpre, c_prev, (float*)nullptr, c_new, (float*)h_next, ld_next,
+                       (float*)h_up, ld_up, (float*)nullptr, 0l, rows, H);
+  else
+    hipLaunchKernelGGL((lstm_pointwise_fwd_kernel<bf16_t>), grid, dim3(256), 0, stream, gpre, c_prev, (float*)nullptr, c_new, (bf16_t*)h_next,
+                       ld_next, (bf16_t*)h_up, ld_up, (bf16_t*)nullptr, 0l, rows, H);
+  GIC_CHECK_LAUNCH("lstm_pointwise_fwd");
+  return GIC_OK;
+}
+
 // d_embed[ids[b, t-1]] += dx_t (t >= 1) over a zeroed table (generator.py:75: the index is detached); dx rows at dx + (t*B + b)*ld,
 // ids rows ids_stride apart (0: L)
 int embed_scatter_time(const float* dx, long ld, const int64_t* ids, float* d_embed, int B, int L, int E, int V, hipStream_t stream, long ids_stride) {

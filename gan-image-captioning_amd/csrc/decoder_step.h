@@ -39,6 +39,10 @@ struct LstmStepArgs {
   const float* embed = nullptr; int V = 0;
   const unsigned long long* rowkey = nullptr;      // [B] argmax keys of step t-1 (vocab_step's atomicMax; see row_key())
   const int64_t* force_ids = nullptr; long force_stride = 0; const int32_t* force_len = nullptr; int tprev = 0;
+  // beam search (beam.h), all optional: with every one null the kernel is the roll-out's
+  const int32_t* parent = nullptr;   // [B]: the h part of xh_t and c_prev are read from row parent[r]
+  const int32_t* token = nullptr;    // [B]: the gathered x part is embed[token[r]] (needs `gather`)
+  const int32_t* stop = nullptr; int stop_at = 0;  // *stop >= stop_at: return at once (every beam has finished)
   int dbg = 0;
 };
 
@@ -55,6 +59,8 @@ struct VocabStepArgs {
   void* out = nullptr; long out_stride = 0;  // act: out + b*out_stride + v (e or raw logits); null: ids only
   float* part_m = nullptr; float* part_s = nullptr; int nblk = 0;   // [B][nblk] per-tile max / sum of exp
   unsigned long long* rowkey = nullptr;      // [B], zeroed by the caller: atomicMax of (ordered tile max, ~first maximal index)
+  float* part_v = nullptr; int32_t* part_i = nullptr;   // beam epilogue only (vocab_step_beam): [B][nblk][K] tile top-K pairs
+  const int32_t* stop = nullptr; int stop_at = 0;         // beam epilogue only: *stop >= stop_at -> return at once
   int B = 0, V = 0, H = 0;
   int dbg = 0;
 };

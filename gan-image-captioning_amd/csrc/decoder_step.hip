@@ -9,6 +9,7 @@
 
 #include <stdlib.h>
 
+#include "beam.h"
 #include "kernels.h"
 
 namespace gic {
@@ -129,8 +130,10 @@ template <> __device__ __forceinline__ u32x4 pack_f32_chunk<bf16_t>(const f32x4&
 // The 8 waves split the k-steps of a chunk; their partial sums meet in LDS (the staging area, reused) and 256 threads apply the
 // cell nonlinearities.
 // (device body: workgroup (bx, by) of the launch grid)
-template <typename TA>
-__device__ __forceinline__ void lstm_step_body(const LstmStepArgs& a, const int KC, const int bx, const int by, unsigned char* ls_smem, int* ids_s) {
+// BEAM: the beam-search reorder (decoder_step.h LstmStepArgs.parent / token / stop); false is the roll-out's kernel exactly
+template <typename TA, bool BEAM = false>
+__device__ __forceinline__ void lstm_step_body(const LstmStepArgs& a, const int KC, const int bx, const int by, unsigned char* ls_smem, int* ids_s,
+                                               int* par_s = nullptr) {
   constexpr int SZ = sizeof(TA), VE = 16 / SZ;
   const int hs = KC * SZ + 16;                              // LDS row stride: 16-byte skew against bank conflicts
   unsigned char* sA = ls_smem;
@@ -139,6 +142,11 @@ __device__ __forceinline__ void lstm_step_body(const LstmStepArgs& a, const int 
   const int j0 = bx * kUnitsPerBlock;
   const int b0 = by * kStepRows;
   DSTAMP(0, 0);
+  if constexpr (BEAM) {
+    if (a.stop && *a.stop >= a.stop_at) return;                // (block-uniform: every image has finished)
+    if (tid < kStepRows) par_s[tid] = a.parent ? a.parent[min(b0 + tid, a.B - 1)] : min(b0 + tid, a.B - 1);
+    if (!a.gather) __syncthreads();
+  }
 
   if (a.gather) {
     // next-input token of each row: the forced trajectory, else the first maximal index of the previous step's logits
@@ -149,6 +157,7 @@ __device__ __forceinline__ void lstm_step_body(const LstmStepArgs& a, const int 
       if (b < a.B) {
         const bool forced = a.force_ids && (!a.force_len || a.tprev < a.force_len[b]);
         if (forced) id = (int)a.force_ids[(long)b * a.force_stride + a.tprev];
+        else if (BEAM && a.token) id = a.token[b];
         else if (a.rowkey) id = row_key_index(a.rowkey[b]);
         id = id < 0 ? 0 : (id >= a.V ? a.V - 1 : id);
       }
@@ -170,7 +179,7 @@ __device__ __forceinline__ void lstm_step_body(const LstmStepArgs& a, const int 
   if (pok) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) pbias[g] = a.bsum[g * a.H + pj];
-    pc = a.c_prev[(long)pb * a.H + pj];
+    pc = a.c_prev[(long)(BEAM ? par_s[tid >> 2] : pb) * a.H + pj];
   }
 
   f32x4 acc[4];
@@ -228,7 +237,9 @@ __device__ __forceinline__ void lstm_step_body(const LstmStepArgs& a, const int 
           for (int i = 0; i < 8; ++i) {
             prh[i] = rowh; pch[i] = cch;
             const int r = min((rowh + rot) & (kStepRows - 1), rlast);
-            v[i] = *(gptr_u4)(xh + (long)(b0 + r) * a.ldx + kc0 + xc + cch * VE);
+            const int col = kc0 + xc + cch * VE;
+            const int src = BEAM && col >= a.din ? par_s[r] : b0 + r;      // the h part of a beam row: its parent's (a piece never straddles)
+            v[i] = *(gptr_u4)(xh + (long)src * a.ldx + col);
             rowh += drowh; cch += dcch;
             if (cch >= cprh) { cch -= cprh; ++rowh; }
             if (rowh >= kStepRows) rowh = kStepRows - 1;
@@ -321,6 +332,14 @@ __global__ __launch_bounds__(512) void lstm_step_kernel(const LstmStepArgs a, co
   lstm_step_body<TA>(a, KC, blockIdx.x, blockIdx.y, ls_smem, ids_s);
 }
 
+template <typename TA>
+__global__ __launch_bounds__(512) void lstm_step_beam_kernel(const LstmStepArgs a, const int KC) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ls_smem[];
+  __shared__ int ids_s[kStepRows];
+  __shared__ int par_s[kStepRows];
+  lstm_step_body<TA, true>(a, KC, blockIdx.x, blockIdx.y, ls_smem, ids_s, par_s);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // vocab_step: logits^T tile [64 vocabulary entries x 64 batch rows] = W_out[v0:v0+64, :] . h_t^T on MFMA (generator.py:68),
 // then y = (o + b_out + gumbel(u)) * T (generator.py:69, 84-96), the tile's softmax partials and e = exp(y - tile max).
@@ -328,7 +347,9 @@ __global__ __launch_bounds__(512) void lstm_step_kernel(const LstmStepArgs a, co
 // waves = 4 vocabulary sub-tiles x 2 K halves of a chunk; the halves trade two batch sub-tiles each, so that all eight waves
 // share the transcendental-heavy epilogue.  In the C tile a lane holds 4 CONSECUTIVE vocabulary entries of one batch row: one
 // Philox4x32 call (or one 16-byte load of explicit uniforms) and one vector store of e per lane and batch sub-tile.
-template <typename TA, bool FAST>
+// BEAMK > 0: the beam-search epilogue (beam.h) in place of the sampling one -- raw logits y = o + b_out, per (row, tile) max, sum of
+// exp and top-BEAMK pairs in fixed slots; the product and its operand order are the roll-out's, so a beam's logits are sample's bits
+template <typename TA, bool FAST, int BEAMK = 0>
 __device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const int KC, const int bx, const int by, unsigned char* vs_smem) {
   constexpr int SZ = sizeof(TA), VE = 16 / SZ;
   const int H = a.H, V = a.V;
@@ -347,6 +368,9 @@ __device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const in
   const int mt = w >> 1, kh = w & 1;
   const int v0 = bx * kVocabTile, b0 = by * kStepRows;
   DSTAMP(1, 0);
+  if constexpr (BEAMK > 0) {
+    if (a.stop && *a.stop >= a.stop_at) return;                // (block-uniform: every image has finished)
+  }
 
   // ---- epilogue operands that depend on nothing computed here: requested now
   const int vq = v0 + mt * 16 + lg * 4;
@@ -354,7 +378,7 @@ __device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const in
   f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
   if (qok) bias4 = *(gptr_f4)(a.bias + vq);
   f32x4 u4[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-  if (a.u && !a.pretrain && qok) {
+  if (BEAMK == 0 && a.u && !a.pretrain && qok) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int b = b0 + (2 * kh + i) * 16 + lr;
@@ -468,6 +492,29 @@ __device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const in
   float y[2][4];
   bool bok[2];
   int brow[2];
+  if constexpr (BEAMK > 0) {
+    // ---- beam epilogue: the tile's raw logits through LDS [64 rows][64 entries (+1 skew)], then 8 lanes per row
+    __syncthreads();                                       // every wave has read its partner's partial sums from sX
+    float* tl = (float*)vs_smem;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int col = (2 * kh + i) * 16 + lr;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tl[col * (kVocabTile + 1) + mt * 16 + lg * 4 + r] = qok ? own[i][r] + bia[r] : -INFINITY;
+    }
+    __syncthreads();
+    const int row = tid >> 3, seg = tid & 7;
+    float x[8];
+    int ix[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int v = v0 + seg * 8 + e;
+      x[e] = tl[row * (kVocabTile + 1) + seg * 8 + e];
+      ix[e] = v < V ? v : INT_MAX;
+    }
+    beam_tile_reduce8<BEAMK>(x, ix, seg == 0 && b0 + row < a.B, (long)(b0 + row) * a.nblk + bx, a.part_m, a.part_s, a.part_v, a.part_i);
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int nt = 2 * kh + i;
@@ -561,6 +608,12 @@ template <typename TA, bool FAST>
 __global__ __launch_bounds__(512) void vocab_step_kernel(const VocabStepArgs a, const int KC) {
   extern __shared__ __attribute__((aligned(16))) unsigned char vs_smem[];
   vocab_step_body<TA, FAST>(a, KC, blockIdx.x, blockIdx.y, vs_smem);
+}
+
+template <typename TA, int K>
+__global__ __launch_bounds__(512) void vocab_step_beam_kernel(const VocabStepArgs a, const int KC) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char vs_smem[];
+  vocab_step_body<TA, false, K>(a, KC, blockIdx.x, blockIdx.y, vs_smem);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -724,15 +777,26 @@ int decoder_step_max_rows() {
 
 int lstm_step(const LstmStepArgs& a, int dtype, hipStream_t stream) {
   GIC_CHECK_ARG(a.xh_t && a.xh_next && a.wcat && a.bsum && a.c_prev && a.c_new, "lstm_step: null buffer");
+  const bool beam = a.parent || a.token || a.stop;
   GIC_CHECK_ARG(a.B > 0 && a.H > 0 && a.din > 0 && a.ldx == (long)a.din + a.H && a.ldx % 8 == 0 && a.din % 8 == 0 && a.gw % 8 == 0 && a.gw <= a.din,
                 "lstm_step: bad dims");
-  GIC_CHECK_ARG(!a.gather || (a.embed && a.V > 0 && (a.rowkey || a.force_ids)), "lstm_step: bad gather arguments");
+  GIC_CHECK_ARG(!a.gather || (a.embed && a.V > 0 && (a.rowkey || a.force_ids || a.token)), "lstm_step: bad gather arguments");
   const dim3 grid((unsigned)cdiv(a.H, kUnitsPerBlock), (unsigned)cdiv(a.B, kStepRows));
   LstmStepArgs b = a;
   b.dbg = g_step_dbg;
   const int KC = lstm_chunk(dtype, (int)a.ldx);
   const size_t lds = lstm_lds_bytes(dtype, (int)a.ldx);
-  if (dtype == DT_F32) {
+  if (beam) {
+    if (dtype == DT_F32) {
+      static LdsGrant b32;
+      GIC_PROPAGATE(allow_lds(lstm_step_beam_kernel<float>, lds, b32));
+      hipLaunchKernelGGL((lstm_step_beam_kernel<float>), grid, dim3(512), lds, stream, b, KC);
+    } else {
+      static LdsGrant b16;
+      GIC_PROPAGATE(allow_lds(lstm_step_beam_kernel<bf16_t>, lds, b16));
+      hipLaunchKernelGGL((lstm_step_beam_kernel<bf16_t>), grid, dim3(512), lds, stream, b, KC);
+    }
+  } else if (dtype == DT_F32) {
     static LdsGrant g32;
     GIC_PROPAGATE(allow_lds(lstm_step_kernel<float>, lds, g32));
     hipLaunchKernelGGL((lstm_step_kernel<float>), grid, dim3(512), lds, stream, b, KC);
@@ -776,6 +840,44 @@ int vocab_step(const VocabStepArgs& a0, int dtype, hipStream_t stream) {
   }
   GIC_CHECK_LAUNCH("vocab_step");
   return GIC_OK;
+}
+
+template <int K>
+int vocab_beam_launch(const VocabStepArgs& a, int dtype, size_t lds, int KC, dim3 grid, hipStream_t stream) {
+  if (dtype == DT_F32) {
+    static LdsGrant g32;
+    GIC_PROPAGATE(allow_lds(vocab_step_beam_kernel<float, K>, lds, g32));
+    hipLaunchKernelGGL((vocab_step_beam_kernel<float, K>), grid, dim3(512), lds, stream, a, KC);
+  } else {
+    static LdsGrant g16;
+    GIC_PROPAGATE(allow_lds(vocab_step_beam_kernel<bf16_t, K>, lds, g16));
+    hipLaunchKernelGGL((vocab_step_beam_kernel<bf16_t, K>), grid, dim3(512), lds, stream, a, KC);
+  }
+  GIC_CHECK_LAUNCH("vocab_step_beam");
+  return GIC_OK;
+}
+
+int vocab_step_beam(const VocabStepArgs& a0, int K, int dtype, hipStream_t stream) {
+  VocabStepArgs a = a0;
+  a.dbg = 0; a.pretrain = 1; a.u = nullptr; a.out = nullptr; a.rowkey = nullptr;
+  GIC_CHECK_ARG(a.h && a.wout && a.bias && a.part_m && a.part_s && a.part_v && a.part_i, "vocab_step_beam: null buffer");
+  GIC_CHECK_ARG(a.B > 0 && a.V >= 4 && a.V % 4 == 0 && a.H % 8 == 0 && a.ldh % 8 == 0 && K >= 1 && K <= kBeamMax, "vocab_step_beam: bad dims");
+  GIC_CHECK_ARG(a.nblk == cdiv(a.V, kVocabTile), "vocab_step_beam: nblk must be ceil(V / %d)", kVocabTile);
+  const size_t tile = (size_t)kStepRows * (kVocabTile + 1) * sizeof(float);
+  size_t lds = vocab_lds_bytes(dtype, a.H);
+  if (lds < tile) lds = tile;
+  const int KC = vocab_chunk(dtype, a.H);
+  const dim3 grid((unsigned)a.nblk, (unsigned)cdiv(a.B, kStepRows));
+  switch (K) {
+    case 1: return vocab_beam_launch<1>(a, dtype, lds, KC, grid, stream);
+    case 2: return vocab_beam_launch<2>(a, dtype, lds, KC, grid, stream);
+    case 3: return vocab_beam_launch<3>(a, dtype, lds, KC, grid, stream);
+    case 4: return vocab_beam_launch<4>(a, dtype, lds, KC, grid, stream);
+    case 5: return vocab_beam_launch<5>(a, dtype, lds, KC, grid, stream);
+    case 6: return vocab_beam_launch<6>(a, dtype, lds, KC, grid, stream);
+    case 7: return vocab_beam_launch<7>(a, dtype, lds, KC, grid, stream);
+    default: return vocab_beam_launch<8>(a, dtype, lds, KC, grid, stream);
+  }
 }
 
 int sample_finish(const SampleFinishArgs& a, int dtype, hipStream_t stream) {

@@ -26,6 +26,7 @@ struct GemmDesc {
   const float* bias = nullptr;   // per output column n (optional)
   int accumulate = 0;            // C += result
   int c_zeroed = 0;              // caller guarantees C is all zero: a split-K launch skips its own zero fill
+  int no_split = 0;              // never split K (no f32 atomics: the same bits on every call, in or out of the deterministic mode)
   float alpha = 1.f;
   int epi = EPI_PLAIN;
   // ---- EPI_HIGHWAY (discriminator.py:53-58): h = acc+bias; y = sig(h)*relu(h) + (1-sig(h))*x; C = y*keep*keep_scale

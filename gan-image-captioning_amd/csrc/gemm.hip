@@ -1165,7 +1165,7 @@ int launch(const GemmDesc& d, hipStream_t stream) {
   // split-K only where the tile grid leaves most of the 256 CUs idle and K is deep enough to share
   int splits = 1;
   // (bf16 compute mode only: the f32 parity mode stays bit-reproducible run to run, atomics reorder the f32 sum)
-  if (EPI == EPI_PLAIN && sizeof(TI) == 2 && sizeof(TO) == 4) {
+  if (EPI == EPI_PLAIN && sizeof(TI) == 2 && sizeof(TO) == 4 && !d.no_split) {
     if (tiles < 24 && nk >= 8) {                 // skinny recurrent / head products: fill the chip
       splits = 256 / tiles;
       if (splits > nk / 2) splits = nk / 2;

@@ -520,6 +520,52 @@ class DecoderEngine:
         d_c0 = torch.stack([ws["dc"][l] for l in range(self.NL)]).contiguous()
         return d_h0, d_c0
 
+    def beam_ws_bytes(self, B: int, Lc: int, beam: int) -> int:
+        """Bytes of gic_decoder_beam_search's workspace (host-only query; the library's own path choice sizes it)."""
+        out = C.c_uint64(0)
+        L.check(L.load().gic_decoder_beam_ws_bytes(C.byref(self.dims(B, Lc)), int(beam), C.byref(out)), "gic_decoder_beam_ws_bytes")
+        return int(out.value)
+
+    def beam_fused(self, B: int, beam: int) -> bool:
+        """True if the search runs on the fused step kernels (B * beam rows within fused_rollout_rows())."""
+        return B * beam <= self.fused_rollout_rows()
+
+    def beam_search(self, params, features: torch.Tensor, Lc: int, beam: int, eos_id: int = 2, pad_id: int = 0,
+                    length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None):
+        """gic_decoder_beam_search: (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam]), beams best first.
+        ``states`` = (h0, c0), each f32 [NL, B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned)."""
+        self.check_params(params)
+        require_gpu(features)
+        B = features.shape[0]
+        if features.shape != (B, self.E) or features.dtype != torch.float32:
+            raise ValueError(f"features must be float32 [B,{self.E}], got {tuple(features.shape)} {features.dtype}")
+        features = features.contiguous()
+        dev = features.device
+        self.prepare(params)
+        nbytes = self.beam_ws_bytes(B, Lc, beam)
+        if ws is None or ws.numel() < nbytes or ws.data_ptr() % 256:
+            ws = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
+            off = (-ws.data_ptr()) % 256
+            ws = ws[off:off + nbytes]
+        opts = L.DecoderBeamOpts()
+        opts.beam, opts.eos_id, opts.pad_id, opts.length_penalty = int(beam), int(eos_id), int(pad_id), float(length_penalty)
+        keep = []
+        if states is not None:
+            h0, c0 = (t.detach().to(torch.float32).contiguous() for t in states)
+            if tuple(h0.shape) != (self.NL, B, self.H) or tuple(c0.shape) != (self.NL, B, self.H):
+                raise ValueError(f"states must be (h0, c0), each [num_layers={self.NL}, B={B}, H={self.H}]")
+            require_gpu(h0, c0)
+            opts.h0, opts.c0 = ptr(h0), ptr(c0)
+            keep += [h0, c0]
+        ids = torch.empty(B, beam, Lc, device=dev, dtype=torch.int64)
+        scores = torch.empty(B, beam, device=dev, dtype=torch.float32)
+        lengths = torch.empty(B, beam, device=dev, dtype=torch.int32)
+        d = self.dims(B, Lc)
+        L.check(L.load().gic_decoder_beam_search(
+            C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws), ptr(features),
+            ptr(ids), ptr(scores), ptr(lengths), stream_ptr()), "gic_decoder_beam_search")
+        return ids, scores, lengths
+
     def _cast_like(self, t: torch.Tensor) -> torch.Tensor:
         t = t.contiguous()
         dst = torch.empty(t.shape, device=t.device, dtype=self.act)

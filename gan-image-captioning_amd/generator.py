@@ -202,6 +202,19 @@ class Decoder(nn.Module):
                                             features, *params)
         return pred, (h_n, c_n)
 
+    def beam_search(self, features, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None, return_beams=False):
+        """Beam-search caption decode (gicap.h gic_decoder_beam_search): token log-probabilities of sample(pretrain=True)'s
+        distribution, ``beam_size`` (1..8) hypotheses per image, <E> = ``eos_id`` ends a beam, <PAD> (0) after it; final order by
+        score / length**length_penalty.  Returns detached (ids int64 [B, L], scores f32 [B], lengths int32 [B]) of the best beam, or
+        all beams ([B, k, L], [B, k], [B, k]) with ``return_beams``.  ``max_caption_len`` None = args.max_seq_len."""
+        L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
+        with torch.no_grad():
+            ids, scores, lengths = self.engine().beam_search([p.detach() for p in self.param_list()], features.detach().float(), L,
+                                                             int(beam_size), int(eos_id), 0, float(length_penalty), states=states)
+        if return_beams:
+            return ids, scores, lengths
+        return ids[:, 0], scores[:, 0], lengths[:, 0]
+
     def add_gumbel(self, o_t, eps=1e-10, gpu=0):
         """o_t + Gumbel(0,1) noise (generator.py:84-96); on the hot path this is fused into sample()."""
         u = torch.empty_like(o_t, dtype=torch.float32).uniform_(0, 1)
@@ -273,6 +286,10 @@ class AttnDecoder(nn.Module):
     def param_list(self) -> List[nn.Parameter]:
         return [self.embed.weight] + self.lstm.layer_params(0) + [self.linear.weight, self.linear.bias, self.attn.w_f, self.attn.b_f,
                                                                    self.attn.w_h, self.attn.w_a]
+
+    def beam_search(self, *args, **kwargs):
+        raise NotImplementedError("beam search is implemented for the LSTM decoder only (--decoder lstm); the attention decoder "
+                                  "(--decoder attention) has no beam decode")
 
     def sample(self, features, fmap=None, states=None, pretrain=False, max_caption_len=34, noise_u=None):
         """(outputs [B,L,V], ids [B,L]) as Decoder.sample; ``fmap`` [B, P, C]: the trunk's last feature map (no gradient into it)."""
@@ -458,6 +475,17 @@ class Generator(nn.Module):
             self.decoder = Decoder(args)
         self.args = args
         self.init_params()
+
+    def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False):
+        """Captions for ``images`` by beam search: features as the trainer forms them (training.py:66-68) -- the encoder in the
+        module's current mode, or embed(<S>) with --conditional-gan 0 -- under no-grad, then ``decoder.beam_search``."""
+        with torch.no_grad():
+            if self.args.conditional_gan:
+                features = self.encoder(images)
+            else:
+                features = self.decoder.embed(torch.ones(len(images), dtype=torch.long, device=images.device))
+            return self.decoder.beam_search(features, beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id,
+                                            length_penalty=length_penalty, return_beams=return_beams)
 
     def forward(self, images, caps, lengths, pretrain=False):
         if self.args.conditional_gan:

@@ -324,7 +324,61 @@ class GANInstructor:
             if adv_epoch % self.args.adv_log_step == 0 or adv_epoch == self.args.adv_epochs - 1:
                 self.log.info("[ADV] epoch %d (temperature: %.4f):\n\t g_loss: %.4f | %.4f \n\t d_loss: %.4f | %.4f" % (
                     adv_epoch, self.gen.decoder.temperature, train_g_loss, val_g_loss, train_d_loss, val_d_loss))
+            if int(getattr(self.args, "eval_beam_size", 0)) > 0 and self.dist.rank == 0:
+                self.evaluate("val", beam_size=int(self.args.eval_beam_size))
             self.writer.flush()
+
+    def evaluate(self, what="val", beam_size=3, max_caption_len=None, batch_size=None):
+        """BLEU-4 of beam-search captions against the dev (``what="val"``) or train captions: the captions are grouped by image
+        (``filepath`` + ``filename`` for COCO_data, one image per item otherwise), every image is loaded and decoded once in eval
+        mode, ids map through ``index_to_word`` with <S>, <E>, <PAD> stripped.  Captions are decoded up to ``max_caption_len``
+        steps, by default max(args.max_seq_len, longest reference of the batch + 2): a batch's collate length, so that a short
+        --max-seq-len cannot truncate every candidate below its references.  Logs the score and writes the scalar
+        ``BLEU4_<what>``."""
+        from .tasks import COCO_data, SPECIALS
+        from .utils import bleu_score
+        ds = self.dev_dataset if what == "val" else self.train_dataset
+        groups, order = {}, []
+        for i in range(len(ds)):
+            if isinstance(ds, COCO_data):
+                e = ds.captions[i]
+                key = (e["filepath"], e["filename"])
+            else:
+                key = i
+            if key not in groups:
+                groups[key] = []
+                order.append(key)
+            groups[key].append(i)
+        coco = isinstance(ds, COCO_data)
+        unk = ds.word_to_index.get("<UNK>", 3)
+        # a COCO caption's token ids as __getitem__ forms them, read from the entry (no image load)
+        coco_ids = lambda e: [t if isinstance(t, int) else ds.word_to_index.get(t, unk) for t in e["tokens"]]   # noqa: E731
+        i2w = ds.index_to_word
+        strip = {ds.word_to_index[w] for w in SPECIALS[:3] if w in ds.word_to_index}
+        words = lambda ids: [i2w.get(int(t), str(int(t))) for t in ids if int(t) not in strip]   # noqa: E731
+        was_training = self.gen.training
+        self.gen.eval()
+        bs = int(batch_size or getattr(self.args, "adv_eval_batch_size", 32))
+        cands, refs = [], []
+        try:
+            for s in range(0, len(order), bs):
+                keys = order[s:s + bs]
+                firsts = [ds[groups[k][0]] for k in keys]          # one image load per image
+                images = torch.stack([it[0] for it in firsts]).to(self.args.device)
+                caps = [[coco_ids(ds.captions[j]) for j in groups[k]] if coco else [it[1]] for k, it in zip(keys, firsts)]
+                L = max_caption_len or max(int(getattr(self.args, "max_seq_len", 0) or 0),
+                                           max(len(c) for group in caps for c in group) + 2)
+                ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L)
+                ids, lengths = ids.cpu(), lengths.cpu()
+                for b, group in enumerate(caps):
+                    cands.append(words(ids[b, :int(lengths[b])].tolist()))
+                    refs.append([words(c) for c in group])
+        finally:
+            self.gen.train(was_training)
+        score = bleu_score(cands, refs)
+        self.log.info("[EVAL] BLEU-4 (%s, beam %d): %.4f", what, beam_size, score)
+        self.writer.add_scalar(f"BLEU4_{what}", score, max(self.adv_epoch, 0))
+        return score
 
 
 class _XentFn(torch.autograd.Function):

@@ -77,6 +77,49 @@ def get_fixed_temperature(temper, i, N, adapt):
     raise Exception("Unknown adapt type!")
 
 
+def _ngrams(tokens, n):
+    counts = {}
+    for i in range(len(tokens) - n + 1):
+        g = tuple(tokens[i:i + n])
+        counts[g] = counts.get(g, 0) + 1
+    return counts
+
+
+def bleu_score(candidate_corpus, references_corpus, max_n=4, weights=(0.25,) * 4):
+    """Corpus BLEU with the semantics of torchtext.data.metrics.bleu_score (imported by the reference, training.py:13):
+
+        p_n  = sum_c sum_g min(count_c(g), max_r count_r(g)) / sum_c max(len(c) - n + 1, 0)      (n = 1 .. max_n)
+        BP   = exp(min(1 - r / c, 0)),  c = sum len(candidate), r = sum over candidates of the closest reference length
+        BLEU = BP * exp(sum_n w_n log p_n),  and 0.0 if any p_n has no clipped match.
+
+    ``candidate_corpus``: list of token lists; ``references_corpus``: list (one per candidate) of lists of token lists."""
+    if len(weights) != max_n:
+        raise ValueError("weights must have max_n entries")
+    if len(candidate_corpus) != len(references_corpus):
+        raise ValueError("one list of references per candidate")
+    clipped = [0] * max_n
+    total = [0] * max_n
+    c_len = r_len = 0
+    for cand, refs in zip(candidate_corpus, references_corpus):
+        cand = list(cand)
+        c_len += len(cand)
+        lens = [len(r) for r in refs]
+        r_len += min(lens, key=lambda x: (abs(len(cand) - x), x))
+        for n in range(1, max_n + 1):
+            cc = _ngrams(cand, n)
+            ref_max = {}
+            for r in refs:
+                for g, k in _ngrams(list(r), n).items():
+                    ref_max[g] = max(ref_max.get(g, 0), k)
+            clipped[n - 1] += sum(min(k, ref_max.get(g, 0)) for g, k in cc.items())
+            total[n - 1] += max(len(cand) - n + 1, 0)
+    if min(clipped) == 0:
+        return 0.0
+    log_p = sum(w * math.log(clipped[i] / total[i]) for i, w in enumerate(weights))
+    bp = math.exp(min(1.0 - r_len / c_len, 0.0))
+    return bp * math.exp(log_p)
+
+
 def create_logger(name, silent=False, to_disk=False, log_file=None):
     """Message-only logger to stdout and/or file(s) (utils.py:78-103)."""
     log = logging.getLogger(name)

@@ -190,6 +190,31 @@ void gic_debug_decoder_step(int mask);
  * (Decoder.sample, src/generator.py:55-81, takes any vocabulary / embedding size). */
 int gic_decoder_fused_rollout_rows(const gic_decoder_dims* dims, int32_t* out_rows);
 
+/* Beam-search caption decode (the reference's unbuilt evaluation step; no sampling noise, no temperature: sample(pretrain=True)'s
+ * distribution).  dims->B = images, dims->L = maximum caption length.  Rows = B * beam (row r = image r / beam, beam r % beam).
+ * Step 0 feeds `features` [B,E] with (h0, c0) (zeros when NULL), every later step embed(token) of the beam's previous token from its
+ * PARENT's state.  Token log-probability = logit - logsumexp(logits), the score is the running f32 sum.  Only beam 0 is live at step 0.
+ * A live beam proposes its top-`beam` tokens by raw logit (ties to the lower id); a finished beam (it emitted eos_id) proposes itself
+ * once, with pad_id and its score unchanged; per image the best `beam` of these candidates are kept (ties to the lower (parent beam,
+ * rank)).  The search stops after L steps or once every beam of every image has finished.  A beam's length counts the tokens up to and
+ * including its eos_id (L if none).  Outputs, beams sorted by score / length^length_penalty (descending, ties to the lower beam index):
+ * ids int64 [B,beam,L] (pad_id after eos_id), scores f32 [B,beam] (raw sums), lengths int32 [B,beam].  No f32 atomics: two calls on the
+ * same inputs give the same bits.  The fused step kernels run where gic_decoder_fused_rollout_rows admits B * beam rows, else the
+ * generic products (any V). */
+typedef struct gic_decoder_beam_opts {
+  int32_t beam;                          /* 1..8 (and <= V) */
+  int32_t eos_id;                        /* [0, V); <E> = 2 */
+  int32_t pad_id;                        /* [0, V); <PAD> = 0 */
+  float length_penalty;                  /* alpha of the final order; 0 = raw scores */
+  const float* h0;                       /* [NL,B,H] initial hidden state or NULL = zeros */
+  const float* c0;                       /* [NL,B,H] initial cell state or NULL = zeros */
+} gic_decoder_beam_opts;
+/* Bytes of the (256-byte aligned) workspace of gic_decoder_beam_search for these dims and beam size.  Host-only: no GPU needed. */
+int gic_decoder_beam_ws_bytes(const gic_decoder_dims* dims, int32_t beam, uint64_t* out);
+int gic_decoder_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* params, const gic_decoder_shadow* shadow,
+                            const gic_decoder_beam_opts* opts, void* ws, const float* features, int64_t* ids, float* scores,
+                            int32_t* lengths, void* stream);
+
 /* Decoder.forward, the teacher-forced decode (src/generator.py:39-53; the reference's training never calls it).
  * dims->L = T = caption length + 1 time steps: step 0 is fed `features`, step t > 0 embed(caps[b, t-1]) (caps int64 [B, T-1]).
  * lengths int32 [B] (each 1..T) with pack_padded_sequence semantics: a row past its length keeps its state and contributes a
