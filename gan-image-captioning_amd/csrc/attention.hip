@@ -22,37 +22,6 @@
 namespace gic {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) u32x4* gptr_u4;
-
-// 16 bytes of compute-dtype values as floats: NV = 8 (bf16) or 4 (f32)
-template <typename TA> struct Vec16;
-template <> struct Vec16<bf16_t> {
-  static constexpr int NV = 8;
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[8]) {
-    const bf16x8 x = __builtin_bit_cast(bf16x8, *(gptr_u4)p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)x[i];
-  }
-  static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[8]) {
-    bf16x8 x;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = (bf16_t)v[i];
-    *(bf16x8*)p = x;
-  }
-};
-template <> struct Vec16<float> {
-  static constexpr int NV = 4;
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    const f32x4 x = *(const __attribute__((address_space(1))) f32x4*)p;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = x[i];
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
-    *(f32x4*)p = (f32x4){v[0], v[1], v[2], v[3]};
-  }
-};
-
 constexpr int kAttnMaxP = 1024;      // positions per caption (LDS tables)
 constexpr int kAttnMaxA = 2048;      // attention width (LDS table)
 
@@ -253,12 +222,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdArgs a) {
   }
 }
 
-struct ACtx {
-  int B, L, V, E, H, C, P, A, dt;
-  long ldx() const { return (long)E + C + H; }
-  int din() const { return E + C; }
-  size_t asz() const { return (size_t)dtype_size(dt); }
-};
+}  // namespace
 
 int check_attn_dims(const gic_attn_dims* d, ACtx& c) {
   GIC_CHECK_ARG(d, "attn: null dims");
@@ -270,6 +234,8 @@ int check_attn_dims(const gic_attn_dims* d, ACtx& c) {
   c = ACtx{d->B, d->L, d->V, d->E, d->H, d->C, d->P, d->A, d->dtype};
   return GIC_OK;
 }
+
+namespace {
 
 template <typename TA>
 int attn_fwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st, const float* features,

@@ -16,6 +16,7 @@
 #pragma once
 #include <climits>
 
+#include "../../include/gicap.h"
 #include "common.h"
 #include "decoder_step.h"
 
@@ -92,5 +93,27 @@ __device__ __forceinline__ void beam_tile_reduce8(const float (&x)[8], const int
 // the fused vocabulary product of vocab_step with the beam epilogue (decoder_step.hip): a.B = rows, a.part_m / part_s [rows][nblk],
 // a.part_v / part_i [rows][nblk][K]; a.stop / stop_at; the sampling fields (u, seed, temperature, out, rowkey) are unused
 int vocab_step_beam(const VocabStepArgs& a, int K, int dtype, hipStream_t stream);
+
+// ---- the parts of a search that the LSTM decoder (beam.hip) and the attention decoder (attn_beam.hip) share
+struct BeamLayerPtrs { void* xh[GIC_MAX_LAYERS]; float* c[GIC_MAX_LAYERS]; };
+
+// the search state in the workspace: score f32, fin / len / tok / par i32 [rows]; htok / hpar i32 [L][rows]; last / done i32 [B]; count i32
+struct BeamState { float* score; int* fin; int* len; int* tok; int* par; int* htok; int* hpar; int* last; int* done; int* count; };
+
+struct BeamSelectArgs {
+  const float* part_m; const float* part_s; const float* part_v; const int* part_i;
+  float* score; int* fin; int* len; int* tok; int* par; int* htok; int* hpar; int* last; int* done; int* count;
+  int nblk, rows, t, eos, pad;
+};
+
+// slot 0 of every layer into the K rows of each image (layer 0's input row [0, din0): features in [0, E), zeros behind; h part = h0 or 0;
+// c = c0 or 0; h0 / c0 f32 [NL, B, H] or null) and the state at t = 0: only beam 0 live, par[r] = r
+int beam_init(const BeamLayerPtrs& slot0, int NL, int din0, int E, int H, int B, int K, int dtype, const float* features, const float* h0,
+              const float* c0, const BeamState& s, hipStream_t stream);
+int beam_select(const BeamSelectArgs& a, int K, int B, hipStream_t stream);
+// ids / scores / lengths of the K beams of each image, best first; anc: null or i32 [B, K, L], the row (image * K + beam) of step t whose
+// logits gave the t-th token of each returned beam (-1 past the last step that ran)
+int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length_penalty, int64_t* ids, float* scores, int32_t* lengths,
+                  int32_t* anc, hipStream_t stream);
 
 }  // namespace gic

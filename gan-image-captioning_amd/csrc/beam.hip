@@ -66,20 +66,20 @@ int beam_dims(const gic_decoder_dims* dims, int K, BeamDims& d) {
   return GIC_OK;
 }
 
-struct LayerPtrs { void* xh[GIC_MAX_LAYERS]; float* c[GIC_MAX_LAYERS]; };
+using LayerPtrs = BeamLayerPtrs;
 
-// slot 0 of every layer: x part of layer 0 = the image's features, h part = h0 (or 0), c = c0 (or 0); beam state at t = 0: only
-// beam 0 live (the others at -inf, so the k beams never copy one hypothesis)
+// slot 0 of every layer: x part of layer 0 = the image's features (zeros in [E, din0)), h part = h0 (or 0), c = c0 (or 0); beam state at
+// t = 0: only beam 0 live (the others at -inf, so the k beams never copy one hypothesis)
 template <typename TA>
-__global__ __launch_bounds__(256) void beam_init_kernel(LayerPtrs p, int NL, int E, int H, int B, int K, const float* __restrict__ features,
+__global__ __launch_bounds__(256) void beam_init_kernel(LayerPtrs p, int NL, int din0, int E, int H, int B, int K, const float* __restrict__ features,
                                                         const float* __restrict__ h0, const float* __restrict__ c0, float* score, int* fin, int* len,
                                                         int* tok, int* par, int* last, int* done, int* count) {
   const int r = blockIdx.x, img = r / K, tid = threadIdx.x;
   for (int l = 0; l < NL; ++l) {
-    const int din = l == 0 ? E : H;
+    const int din = l == 0 ? din0 : H;
     const long ld = din + H;
     TA* x = (TA*)p.xh[l] + (long)r * ld;
-    for (int e = tid; e < din; e += 256) x[e] = from_f32<TA>(l == 0 ? features[(long)img * E + e] : 0.f);
+    for (int e = tid; e < din; e += 256) x[e] = from_f32<TA>(l == 0 && e < E ? features[(long)img * E + e] : 0.f);
     for (int j = tid; j < H; j += 256) {
       const long s = ((long)l * B + img) * H + j;
       x[din + j] = from_f32<TA>(h0 ? h0[s] : 0.f);
@@ -135,11 +135,7 @@ __global__ __launch_bounds__(512) void beam_tile_topk_kernel(const float* __rest
   beam_tile_reduce8<K>(x, ix, seg == 0 && row < rows, (long)rr * nblk + blockIdx.x, part_m, part_s, part_v, part_i);
 }
 
-struct SelectArgs {
-  const float* part_m; const float* part_s; const float* part_v; const int* part_i;
-  float* score; int* fin; int* len; int* tok; int* par; int* htok; int* hpar; int* last; int* done; int* count;
-  int nblk, rows, t, eos, pad;
-};
+using SelectArgs = BeamSelectArgs;
 
 // (candidate score, lane) order of the selection: valid first, larger score, then the lower (parent beam, rank) = lower lane
 __device__ __forceinline__ bool sel_better(bool va, float a, int la, bool vb, float b, int lb) {
@@ -228,7 +224,7 @@ __global__ __launch_bounds__(512) void beam_select_kernel(const SelectArgs a) {
 __global__ __launch_bounds__(64) void beam_finalize_kernel(const float* __restrict__ score, const int* __restrict__ len, const int* __restrict__ htok,
                                                            const int* __restrict__ hpar, const int* __restrict__ last, int K, int L, int rows, int pad,
                                                            float alpha, int64_t* __restrict__ ids, float* __restrict__ scores_out,
-                                                           int32_t* __restrict__ lengths_out) {
+                                                           int32_t* __restrict__ lengths_out, int32_t* __restrict__ anc) {
   extern __shared__ int hs[];                              // [L][K] tokens, then [L][K] parent beams
   __shared__ int rank_s[kBeamMax];
   const int img = blockIdx.x, tid = threadIdx.x;
@@ -253,14 +249,19 @@ __global__ __launch_bounds__(64) void beam_finalize_kernel(const float* __restri
   __syncthreads();
   for (int i = tid; i < K * L; i += 64) {                  // positions past the last step that ran
     const int j = i / L, t = i % L;
-    if (t > tl) ids[((long)img * K + rank_s[j]) * L + t] = pad;
+    if (t > tl) {
+      ids[((long)img * K + rank_s[j]) * L + t] = pad;
+      if (anc) anc[((long)img * K + rank_s[j]) * L + t] = -1;
+    }
   }
   if (tid < K) {
     int64_t* row = ids + ((long)img * K + rank_s[tid]) * L;
+    int32_t* arow = anc ? anc + ((long)img * K + rank_s[tid]) * L : nullptr;
     int cur = tid;
     for (int t = tl; t >= 0; --t) {
       row[t] = hs[t * K + cur];
       cur = hs[L * K + t * K + cur];
+      if (arow) arow[t] = img * K + cur;              // the parent row of step t: its logits gave this token
     }
   }
 }
@@ -271,6 +272,8 @@ int select_launch(const SelectArgs& s, int B, hipStream_t stream) {
   GIC_CHECK_LAUNCH("beam_select");
   return GIC_OK;
 }
+}  // namespace
+
 int beam_select(const SelectArgs& s, int K, int B, hipStream_t stream) {
   switch (K) {
     case 1: return select_launch<1>(s, B, stream);
@@ -283,6 +286,32 @@ int beam_select(const SelectArgs& s, int K, int B, hipStream_t stream) {
     default: return select_launch<8>(s, B, stream);
   }
 }
+
+int beam_init(const BeamLayerPtrs& slot0, int NL, int din0, int E, int H, int B, int K, int dtype, const float* features, const float* h0,
+              const float* c0, const BeamState& s, hipStream_t stream) {
+  const dim3 grid((unsigned)(B * K));
+  if (dtype == DT_F32)
+    hipLaunchKernelGGL((beam_init_kernel<float>), grid, dim3(256), 0, stream, slot0, NL, din0, E, H, B, K, features, h0, c0, s.score, s.fin,
+                       s.len, s.tok, s.par, s.last, s.done, s.count);
+  else
+    hipLaunchKernelGGL((beam_init_kernel<bf16_t>), grid, dim3(256), 0, stream, slot0, NL, din0, E, H, B, K, features, h0, c0, s.score, s.fin,
+                       s.len, s.tok, s.par, s.last, s.done, s.count);
+  GIC_CHECK_LAUNCH("beam_init");
+  return GIC_OK;
+}
+
+int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length_penalty, int64_t* ids, float* scores, int32_t* lengths,
+                  int32_t* anc, hipStream_t stream) {
+  const size_t lds = (size_t)2 * L * K * sizeof(int);
+  static LdsGrant gfin;
+  GIC_CHECK_ARG(grant_lds(beam_finalize_kernel, lds, gfin), "beam_finalize: cannot reserve %zu bytes of LDS", lds);
+  hipLaunchKernelGGL(beam_finalize_kernel, dim3((unsigned)B), dim3(64), lds, stream, s.score, s.len, s.htok, s.hpar, s.last, K, L, B * K, pad,
+                     length_penalty, ids, scores, lengths, anc);
+  GIC_CHECK_LAUNCH("beam_finalize");
+  return GIC_OK;
+}
+
+namespace {
 
 template <int K>
 int topk_launch(const float* logits, const BeamDims& d, float* pm, float* ps, float* pv, int* pi, const int* count, hipStream_t stream) {
@@ -321,9 +350,8 @@ int beam_search_t(const BeamDims& d, const gic_decoder_params* P, const gic_deco
   int* htok = (int*)(ws + lay.htok); int* hpar = (int*)(ws + lay.hpar);
   int* last = (int*)(ws + lay.last); int* done = (int*)(ws + lay.done); int* count = (int*)(ws + lay.count);
 
-  hipLaunchKernelGGL((beam_init_kernel<TA>), dim3((unsigned)R), dim3(256), 0, stream, slot[0], NL, d.E, H, d.B, d.K, features, o->h0, o->c0, score,
-                     fin, len, tok, par, last, done, count);
-  GIC_CHECK_LAUNCH("beam_init");
+  const BeamState st{score, fin, len, tok, par, htok, hpar, last, done, count};
+  GIC_PROPAGATE(beam_init(slot[0], NL, d.E, d.E, H, d.B, d.K, d.dt, features, o->h0, o->c0, st, stream));
   SelectArgs sa{pm, ps, pv, pi, score, fin, len, tok, par, htok, hpar, last, done, count, d.nblk, R, 0, o->eos_id, o->pad_id};
   for (int t = 0; t < d.L; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
@@ -378,13 +406,7 @@ int beam_search_t(const BeamDims& d, const gic_decoder_params* P, const gic_deco
     sa.t = t;
     GIC_PROPAGATE(beam_select(sa, d.K, d.B, stream));
   }
-  const size_t lds = (size_t)2 * d.L * d.K * sizeof(int);
-  static LdsGrant gfin;
-  GIC_CHECK_ARG(grant_lds(beam_finalize_kernel, lds, gfin), "beam_finalize: cannot reserve %zu bytes of LDS", lds);
-  hipLaunchKernelGGL(beam_finalize_kernel, dim3((unsigned)d.B), dim3(64), lds, stream, score, len, htok, hpar, last, d.K, d.L, R, o->pad_id,
-                     o->length_penalty, ids, scores, lengths);
-  GIC_CHECK_LAUNCH("beam_finalize");
-  return GIC_OK;
+  return beam_finalize(st, d.B, d.K, d.L, o->pad_id, o->length_penalty, ids, scores, lengths, nullptr, stream);
 }
 
 }  // namespace

@@ -16,6 +16,8 @@
 #pragma once
 #include "common.h"
 
+struct gic_attn_dims;
+
 namespace gic {
 
 constexpr int kStepRows = 64;      // batch rows per block (4 MFMA tiles)
@@ -104,5 +106,43 @@ void decoder_step_debug(int v);                             // phase-ablation kn
 int lstm_step(const LstmStepArgs& a, int dtype, hipStream_t stream);
 int vocab_step(const VocabStepArgs& a, int dtype, hipStream_t stream);
 int sample_finish(const SampleFinishArgs& a, int dtype, hipStream_t stream);
+
+// ---- the attention decoder's (attention.hip) shapes, shared with its beam search (attn_beam.hip)
+struct ACtx {
+  int B, L, V, E, H, C, P, A, dt;
+  long ldx() const { return (long)E + C + H; }        // xh row [x | z | h]
+  int din() const { return E + C; }
+  size_t asz() const { return (size_t)dtype_size(dt); }
+};
+int check_attn_dims(const gic_attn_dims* d, ACtx& c);   // V % 4, E / H / C / A % 8, P <= 1024, A <= 2048
+
+// 16 bytes of compute-dtype values as floats: NV = 8 (bf16) or 4 (f32)
+template <typename TA> struct Vec16;
+template <> struct Vec16<bf16_t> {
+  static constexpr int NV = 8;
+  typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+  static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[8]) {
+    const bf16x8 x = __builtin_bit_cast(bf16x8, *(const __attribute__((address_space(1))) u4*)p);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (float)x[i];
+  }
+  static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[8]) {
+    bf16x8 x;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = (bf16_t)v[i];
+    *(bf16x8*)p = x;
+  }
+};
+template <> struct Vec16<float> {
+  static constexpr int NV = 4;
+  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
+    const f32x4 x = *(const __attribute__((address_space(1))) f32x4*)p;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = x[i];
+  }
+  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
+    *(f32x4*)p = (f32x4){v[0], v[1], v[2], v[3]};
+  }
+};
 
 }  // namespace gic

@@ -914,13 +914,7 @@ class AttnDecoderEngine:
         B = features.shape[0]
         if tuple(features.shape) != (B, self.E) or features.dtype != torch.float32:
             raise ValueError(f"features must be float32 [B,{self.E}]")
-        if tuple(fmap.shape) != (B, self.P, self.C):
-            raise ValueError(f"fmap must be [B, P={self.P}, C={self.C}], got {tuple(fmap.shape)}")
-        fmap = fmap.contiguous()
-        if fmap.dtype != self.act:
-            dst = torch.empty(fmap.shape, device=fmap.device, dtype=self.act)
-            cast2d(fmap.float() if fmap.dtype not in (torch.float32, torch.bfloat16) else fmap, dst, B * self.P, self.C, self.C, self.C)
-            fmap = dst
+        fmap = self._act_fmap(fmap, B)
         if noise_u is not None:
             if tuple(noise_u.shape) != (Lc, B, self.V) or noise_u.dtype != torch.float32:
                 raise ValueError(f"noise_u must be float32 [L={Lc},B={B},V={self.V}]")
@@ -943,6 +937,63 @@ class AttnDecoderEngine:
             "gic_attn_sample_fwd")
         st["fmap"] = fmap
         return out, ids, st
+
+    def _act_fmap(self, fmap: torch.Tensor, B: int) -> torch.Tensor:
+        """``fmap`` [B, P, C] as a contiguous tensor of the compute dtype (cast on the GPU when it is not)."""
+        if tuple(fmap.shape) != (B, self.P, self.C):
+            raise ValueError(f"fmap must be [B, P={self.P}, C={self.C}], got {tuple(fmap.shape)}")
+        fmap = fmap.contiguous()
+        if fmap.dtype != self.act:
+            dst = torch.empty(fmap.shape, device=fmap.device, dtype=self.act)
+            cast2d(fmap.float() if fmap.dtype not in (torch.float32, torch.bfloat16) else fmap, dst, B * self.P, self.C, self.C, self.C)
+            fmap = dst
+        return fmap
+
+    def beam_ws_bytes(self, B: int, Lc: int, beam: int) -> int:
+        """Bytes of gic_attn_beam_search's workspace (host-only query)."""
+        out = C.c_uint64(0)
+        L.check(L.load().gic_attn_beam_ws_bytes(C.byref(self.dims(B, Lc)), int(beam), C.byref(out)), "gic_attn_beam_ws_bytes")
+        return int(out.value)
+
+    def beam_search(self, params, features, fmap, Lc: int, beam: int, eos_id: int = 2, pad_id: int = 0, length_penalty: float = 0.0,
+                    states=None, ws: Optional[torch.Tensor] = None, want_alphas: bool = False):
+        """gic_attn_beam_search: (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam][, alphas f32 [B, beam, Lc, P]]),
+        beams best first.  ``fmap`` [B, P, C] is cast to the compute dtype as in sample_fwd.  ``states`` = (h0, c0), each [1, B, H] or
+        [B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned)."""
+        self.check_params(params)
+        require_gpu(features, fmap)
+        B = features.shape[0]
+        if tuple(features.shape) != (B, self.E) or features.dtype != torch.float32:
+            raise ValueError(f"features must be float32 [B,{self.E}]")
+        fmap = self._act_fmap(fmap, B)
+        features = features.contiguous()
+        dev = features.device
+        self.prepare(params)
+        nbytes = self.beam_ws_bytes(B, Lc, beam)
+        if ws is None or ws.numel() < nbytes or ws.data_ptr() % 256:
+            ws = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
+            off = (-ws.data_ptr()) % 256
+            ws = ws[off:off + nbytes]
+        opts = L.DecoderBeamOpts()
+        opts.beam, opts.eos_id, opts.pad_id, opts.length_penalty = int(beam), int(eos_id), int(pad_id), float(length_penalty)
+        keep = []
+        if states is not None:
+            h0, c0 = (t.detach().to(torch.float32).reshape(-1, self.H).contiguous() for t in states)
+            if tuple(h0.shape) != (B, self.H) or tuple(c0.shape) != (B, self.H):
+                raise ValueError(f"states must be (h0, c0), each [1, B={B}, H={self.H}]")
+            require_gpu(h0, c0)
+            opts.h0, opts.c0 = ptr(h0), ptr(c0)
+            keep += [h0, c0]
+        ids = torch.empty(B, beam, Lc, device=dev, dtype=torch.int64)
+        scores = torch.empty(B, beam, device=dev, dtype=torch.float32)
+        lengths = torch.empty(B, beam, device=dev, dtype=torch.int32)
+        alphas = torch.empty(B, beam, Lc, self.P, device=dev, dtype=torch.float32) if want_alphas else None
+        L.check(L.load().gic_attn_beam_search(
+            C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
+            ptr(features), ptr(fmap), ptr(ids), ptr(scores), ptr(lengths), ptr(alphas), stream_ptr()), "gic_attn_beam_search")
+        if want_alphas:
+            return ids, scores, lengths, alphas
+        return ids, scores, lengths
 
     def alloc_bwd_ws(self, B: int, Lc: int, dev):
         f32 = torch.float32

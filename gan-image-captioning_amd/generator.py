@@ -287,9 +287,24 @@ class AttnDecoder(nn.Module):
         return [self.embed.weight] + self.lstm.layer_params(0) + [self.linear.weight, self.linear.bias, self.attn.w_f, self.attn.b_f,
                                                                    self.attn.w_h, self.attn.w_a]
 
-    def beam_search(self, *args, **kwargs):
-        raise NotImplementedError("beam search is implemented for the LSTM decoder only (--decoder lstm); the attention decoder "
-                                  "(--decoder attention) has no beam decode")
+    def beam_search(self, features, fmap=None, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None,
+                    return_beams=False, return_alphas=False):
+        """Beam-search caption decode with attention (gicap.h gic_attn_beam_search): Decoder.beam_search's search over the token
+        log-probabilities of sample(features, fmap, pretrain=True).  ``fmap`` [B, P, C]: the trunk's last feature map
+        (Encoder.forward_with_map).  Returns detached (ids int64 [B, L], scores f32 [B], lengths int32 [B]) of the best beam, or all beams
+        ([B, k, L], [B, k], [B, k]) with ``return_beams``; ``return_alphas`` appends the attention weights with which each token was
+        produced, f32 [B, L, P] (all beams: [B, k, L, P]), zero past a beam's length.  ``states`` = (h0, c0), each [1, B, H]."""
+        if fmap is None:                # (checked before anything touches self: the LSTM decoder's call form has no map)
+            raise NotImplementedError("the attention decoder's beam search needs the trunk's feature map: beam_search(features, fmap), "
+                                      "or Generator.caption(images)")
+        L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
+        with torch.no_grad():
+            out = self.engine().beam_search([p.detach() for p in self.param_list()], features.detach().float(), fmap.detach(), L,
+                                            int(beam_size), int(eos_id), 0, float(length_penalty), states=states,
+                                            want_alphas=bool(return_alphas))
+        if return_beams:
+            return out
+        return tuple(t[:, 0] for t in out)
 
     def sample(self, features, fmap=None, states=None, pretrain=False, max_caption_len=34, noise_u=None):
         """(outputs [B,L,V], ids [B,L]) as Decoder.sample; ``fmap`` [B, P, C]: the trunk's last feature map (no gradient into it)."""
@@ -476,10 +491,18 @@ class Generator(nn.Module):
         self.args = args
         self.init_params()
 
-    def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False):
+    def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False, return_alphas=False):
         """Captions for ``images`` by beam search: features as the trainer forms them (training.py:66-68) -- the encoder in the
-        module's current mode, or embed(<S>) with --conditional-gan 0 -- under no-grad, then ``decoder.beam_search``."""
+        module's current mode, or embed(<S>) with --conditional-gan 0 -- under no-grad, then ``decoder.beam_search``.  With
+        --decoder attention the encoder also gives the feature map, and ``return_alphas`` appends the attention weights
+        (AttnDecoder.beam_search)."""
         with torch.no_grad():
+            if isinstance(self.decoder, AttnDecoder):
+                features, fmap = self.encoder.forward_with_map(images)
+                return self.decoder.beam_search(features, fmap, beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id,
+                                                length_penalty=length_penalty, return_beams=return_beams, return_alphas=return_alphas)
+            if return_alphas:
+                raise ValueError("attention weights exist for --decoder attention only")
             if self.args.conditional_gan:
                 features = self.encoder(images)
             else:

@@ -339,6 +339,18 @@ int gic_attn_sample_bwd(const gic_attn_dims* dims, const gic_attn_params* params
                         const gic_attn_state* state, const gic_attn_bwd_ws* ws, const void* fmap, const void* probs,
                         const int64_t* ids, const void* d_out, float temperature, int pretrain, const gic_attn_grads* grads,
                         const gic_step_scalars* dev_scalars, void* stream);
+/* Beam-search caption decode with the attention decoder: the semantics of gic_decoder_beam_search (candidates, tie order, eos_id /
+ * pad_id, early stop, lengths, final order) with the step of gic_attn_sample_fwd(pretrain = 1): the attention of a beam at step t
+ * uses its h_{t-1}, which is its parent's state; the LSTM input is [x_t ; z_t] with x_0 = features and x_t = embed(the beam's previous
+ * token).  opts->h0 / c0: f32 [B, H] or NULL.  fmap act [B,P,C] as for gic_attn_sample_fwd (shadow refreshed by gic_attn_prepare).
+ * ids / scores / lengths as gic_decoder_beam_search; alphas f32 [B, beam, L, P] or NULL: alphas[b, r, t, :] = the attention weights
+ * with which the t-th token of the r-th returned beam was produced, zero for t >= lengths[b, r].  Limits: those of gic_attn_sample_fwd
+ * and of gic_decoder_beam_search (beam 1..8 and <= V, L <= 1024, B * beam <= 2^24).  No f32 atomics: two calls on the same inputs
+ * give the same bits, and the deterministic mode accepts the call and gives the same bits as outside it. */
+int gic_attn_beam_ws_bytes(const gic_attn_dims* dims, int32_t beam, uint64_t* out);      /* host-only: no GPU needed */
+int gic_attn_beam_search(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                         const gic_decoder_beam_opts* opts, void* ws, const float* features, const void* fmap, int64_t* ids,
+                         float* scores, int32_t* lengths, float* alphas, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Discriminator.forward (src/discriminator.py:34-62) forward + backward.
@@ -523,7 +535,7 @@ int gic_colsum(const void* A, int dtype, int64_t lda, int64_t rows, int64_t cols
  * default; GIC_DETERMINISTIC=1 in the environment turns it on when the library is loaded.  While it is on, every entry point
  * that accepts the call gives bit-identical results for the same inputs, shapes, library build and device model: each f32 sum
  * that several workgroups contribute to has a fixed order (no racing f32 atomics).  Entry points without a deterministic form
- * return GIC_STATUS_UNSUPPORTED instead (gic_attn_sample_fwd / gic_attn_sample_bwd), as do the embedding scatters beyond their
+ * return GIC_STATUS_UNSUPPORTED instead (gic_attn_sample_fwd / gic_attn_sample_bwd; the attention decoder's beam search is accepted), as do the embedding scatters beyond their
  * limit (more than 8192 tokens, or V > 2^19).  It does not hold across GPU models or library builds.
  * The mode is read when work is enqueued: a captured graph keeps the kernels of the mode it was captured in.
  * gic_set_deterministic returns 0; gic_get_deterministic returns the current mode (0 / 1). */
