@@ -89,6 +89,11 @@ _NATIVE = [
                                 "reductions instead of f32 atomics; 0 leaves the process-wide mode as it is (GIC_DETERMINISTIC=1 sets it "
                                 "at load)", {"choices": [0, 1]}),
     ("--num-workers", int, 4, "DataLoader workers (training.py:28-32 uses 4)"),
+    ("--pretrain-mode", str, "sample", "MLE pre-training input: sample = the reference's free-running roll-out (sample(pretrain=True), "
+                                       "training.py:66-83); teacher = teacher forcing, decoder.forward(features, captions[:, :-1], lengths)",
+     {"choices": ["sample", "teacher"]}),
+    ("--attn-reg", float, 0.0, "weight of the doubly stochastic attention penalty mean_b sum_i (1 - sum_t alpha_bti)^2 added to the "
+                               "pre-training loss (--decoder attention --pretrain-mode teacher only)"),
     ("--eval-beam-size", int, 0, "beam size of the BLEU-4 evaluation (GANInstructor.evaluate) after each adversarial epoch's validation; "
                                  "0 = off"),
 ]

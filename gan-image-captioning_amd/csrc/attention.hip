@@ -126,6 +126,8 @@ struct AttnBwdArgs {
   void* dhproj;                      // act [B, A] of this step (operand of the W_h weight gradient and of dh_{t-1} += dhp W_h)
   float* dwa_rows;                   // [B, A] accumulated over the steps (zeroed by the caller): d w_a per caption
   float* dz_zero;                    // [B, C] or null: zeroed by attn_bwd after its last reader (the next step's split-K product adds into it)
+  const float* dalpha_add;           // null, or d alphas of this step added to d alpha: caption b's row at dalpha_add + b * dalpha_ld
+  long dalpha_ld;
   int P, A, H, C;
 };
 
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(256) void attn_dalpha_kernel(const AttnBwdArgs a, i
     for (int q = 0; q < NV; ++q) s += v[q] * dz[c0 + q];
   }
   s = wave_sum(s);
-  if (lane == 0) a.dalpha[row] = s;
+  if (lane == 0) a.dalpha[row] = a.dalpha_add ? s + a.dalpha_add[b * a.dalpha_ld + (row - (long)b * a.P)] : s;
 }
 
 // softmax backward + tanh backward for a slice of 64*NV attention columns of one caption (grid = A/(64 NV) x B): de is recomputed per
@@ -307,14 +309,12 @@ int attn_fwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S
   return sample_finish(f, c.dt, stream);
 }
 
+// the recurrent part of the backward (decoder_step.h attn_bwd_recurrent)
 template <typename TA>
-int attn_bwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st, const gic_attn_bwd_ws* ws,
-               const void* fmap, const void* probs, const int64_t* ids, const void* d_out, float temperature, int pretrain,
-               const gic_attn_grads* G, const float* t_dev, hipStream_t stream) {
+int attn_bwd_rec_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st, const gic_attn_bwd_ws* ws,
+                   const void* fmap, const int64_t* ids, long ids_stride, const float* d_alphas, const gic_attn_grads* G, hipStream_t stream) {
   const int B = c.B, L = c.L, V = c.V, E = c.E, H = c.H, C = c.C, A = c.A;
   const long ld = c.ldx(), BL = (long)B * L;
-  GIC_PROPAGATE(decoder_output_bwd(c.dt, B, L, V, H, probs, d_out, temperature, t_dev, pretrain, ws->dlogits, S->wout, st->hout, ws->dhout,
-                                   G->w_out, G->b_out, stream));
   GIC_PROPAGATE(fill_zero(ws->dc, (size_t)B * H * sizeof(float), stream));
   GIC_PROPAGATE(fill_zero(ws->dfproj, (size_t)B * c.P * A * sizeof(float), stream));
   GIC_PROPAGATE(fill_zero(ws->dwa_rows, (size_t)B * A * sizeof(float), stream));
@@ -344,6 +344,7 @@ int attn_bwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S
     f.w_a = P->w_a; f.dalpha = ws->dalpha; f.dfproj = ws->dfproj; f.dhproj = (TA*)ws->dhproj + (long)t * B * A; f.dwa_rows = ws->dwa_rows;
     f.P = c.P; f.A = A; f.H = H; f.C = C;
     f.dz_zero = (C % 4 == 0) ? ws->dz : nullptr;
+    f.dalpha_add = d_alphas ? d_alphas + (long)t * c.P : nullptr; f.dalpha_ld = (long)L * c.P;
     hipLaunchKernelGGL((attn_dalpha_kernel<TA>), dim3((unsigned)cdiv((long)B * c.P, 4)), dim3(256), 0, stream, f, B);
     GIC_CHECK_LAUNCH("attn_dalpha");
     hipLaunchKernelGGL((attn_bwd_kernel<TA>), dim3((unsigned)cdiv(A, kCols), (unsigned)B), dim3(256), lds, stream, f);
@@ -363,7 +364,7 @@ int attn_bwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S
     GIC_PROPAGATE(gemm(g, stream));
   }
   GIC_PROPAGATE(cast2d(ws->dx, DT_F32, E, G->features, DT_F32, E, B, E, stream));
-  GIC_PROPAGATE(embed_scatter_time(ws->dx, E, ids, G->embed, B, L, E, V, stream));
+  GIC_PROPAGATE(embed_scatter_time(ws->dx, E, ids, G->embed, B, L, E, V, stream, ids_stride));
   {  // LSTM weight gradients over all L*B rows
     GemmDesc w;
     w.A = ws->dgates; w.lda = 4 * H; w.a_kc = 0; w.b_kc = 0; w.ldb = ld; w.M = 4 * H; w.K = (int)BL; w.in_dtype = c.dt; w.out_dtype = DT_F32;
@@ -395,7 +396,23 @@ int attn_bwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S
   return colsum(ws->dwa_rows, DT_F32, A, B, A, G->w_a, nullptr, 0, stream);
 }
 
+template <typename TA>
+int attn_bwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st, const gic_attn_bwd_ws* ws,
+               const void* fmap, const void* probs, const int64_t* ids, const void* d_out, float temperature, int pretrain,
+               const gic_attn_grads* G, const float* t_dev, hipStream_t stream) {
+  GIC_PROPAGATE(decoder_output_bwd(c.dt, c.B, c.L, c.V, c.H, probs, d_out, temperature, t_dev, pretrain, ws->dlogits, S->wout, st->hout,
+                                   ws->dhout, G->w_out, G->b_out, stream));
+  return attn_bwd_rec_t<TA>(c, P, S, st, ws, fmap, ids, 0, nullptr, G, stream);
+}
+
 }  // namespace
+
+int attn_bwd_recurrent(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st, const gic_attn_bwd_ws* ws,
+                       const void* fmap, const int64_t* ids, long ids_stride, const float* d_alphas, const gic_attn_grads* G, hipStream_t stream) {
+  if (c.dt == DT_F32) return attn_bwd_rec_t<float>(c, P, S, st, ws, fmap, ids, ids_stride, d_alphas, G, stream);
+  return attn_bwd_rec_t<bf16_t>(c, P, S, st, ws, fmap, ids, ids_stride, d_alphas, G, stream);
+}
+
 }  // namespace gic
 
 using namespace gic;

@@ -1,0 +1,289 @@
+// Teacher-forced decode with the attention decoder (gicap.h gic_attn_forward_tf / gic_attn_forward_tf_bwd): gic_decoder_forward_tf's
+// packed-sequence semantics with the step of attention.hip.  The inputs are known before the loop, so:
+//   before the loop  x rows of every step gathered once (embed_rows_tf), fp = fmap W_f^T + b_f (one product over B * P rows)
+//   per step t       hp GEMM        hp [B, A] = h_{t-1} W_h^T (the library GEMM, never split over K)
+//                    attn_tf_energy e[b, i] = w_a . tanh(fp_i + hp_b): workgroup = (caption, 8 positions)
+//                    attn_tf_ctx    alpha = softmax_i e[b, :], z_b = sum_i alpha_bi a_i: workgroup = (caption, 32 channel pieces); every
+//                                   workgroup of a caption forms the same softmax, 8 position groups each sum a share of the positions,
+//                                   and the 8 partial sums meet in LDS in group order
+//                    lstm_step      the roll-out's fused step in its packed form (decoder_step.h LstmStepArgs.pack_len): a row past its
+//                                   length keeps (h, c), writes a zero output row and zero gates
+//   after the loop   one vocabulary product over B * Tmax rows, then the Gumbel-softmax epilogue of gic_decoder_forward_tf.
+// A caption past its length returns from both attention kernels at once (one zero alpha row).  No f32 atomics: each energy, alpha and z
+// value is written by one thread, partial sums are added in a fixed order and no GEMM splits K, so the forward gives the same bits on
+// every call in either mode.
+// Backward: decoder_output_bwd over B * Tmax rows, dhout zeroed past the lengths, then the reverse recurrence of gic_attn_sample_bwd
+// (attention.hip attn_bwd_recurrent) with the d alphas added in front of the softmax backward; the zero alpha rows of padded steps make
+// their attention terms vanish, and their zero gates / zero dhout rows make the LSTM terms vanish.
+#include "../../include/gicap.h"
+#include "decoder_step.h"
+#include "kernels.h"
+
+namespace gic {
+namespace {
+
+constexpr int kTfEnergyPos = 8;                    // positions per attn_tf_energy workgroup (2 per wave)
+constexpr int kTfCtxPieces = 32;                   // 16-byte channel pieces per attn_tf_ctx workgroup
+constexpr int kTfCtxGroups = 256 / kTfCtxPieces;   // its position groups
+
+struct AttnTfArgs {
+  const void* fproj;                 // act [B, P, A]
+  const void* fmap;                  // act [B, P, C]
+  const float* w_a;                  // [A]
+  const float* hp;                   // [B, A]: h_{t-1} W_h^T
+  const int32_t* lengths; int t;     // caption b takes part while t < lengths[b]
+  float* e;                          // [B, P] energies
+  void* z; long ldx;                 // act: caption b's z at z + b * ldx
+  float* alpha;                      // [B, P]: this step's slot of state->alpha
+  float* alphas; long alphas_ld;     // the caller's alphas at step t (caption b at + b * alphas_ld), or null
+  int P, A, C;
+};
+
+// e[b, i] for caption blockIdx.x and positions blockIdx.y * 8 .. + 7: wave w takes positions w and w + 4, a lane the 16-byte pieces
+// lane, lane + 64, ... of a position's fp row
+template <typename TA>
+__global__ __launch_bounds__(256) void attn_tf_energy_kernel(const AttnTfArgs a) {
+  constexpr int NV = Vec16<TA>::NV;
+  constexpr int kPW = kTfEnergyPos / 4;
+  const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (a.t >= a.lengths[b]) return;
+  const TA* fp = (const TA*)a.fproj + (long)b * a.P * a.A;
+  const float* hp = a.hp + (long)b * a.A;
+  const int i0 = blockIdx.y * kTfEnergyPos + w;
+  float s[kPW];
+#pragma unroll
+  for (int u = 0; u < kPW; ++u) s[u] = 0.f;
+  for (int j0 = lane * NV; j0 < a.A; j0 += 64 * NV) {
+    float v[kPW][NV];
+#pragma unroll
+    for (int u = 0; u < kPW; ++u) {                         // unconditional loads (a position past P re-reads the last one)
+      const int i = min(i0 + 4 * u, a.P - 1);
+      Vec16<TA>::load(fp + (long)i * a.A + j0, v[u]);
+    }
+    float wa[NV], h[NV];
+#pragma unroll
+    for (int q = 0; q < NV; ++q) { wa[q] = a.w_a[j0 + q]; h[q] = hp[j0 + q]; }
+#pragma unroll
+    for (int u = 0; u < kPW; ++u)
+#pragma unroll
+      for (int q = 0; q < NV; ++q) s[u] += wa[q] * tanhf(v[u][q] + h[q]);
+  }
+#pragma unroll
+  for (int u = 0; u < kPW; ++u) {
+    const int i = i0 + 4 * u;
+    const float t = wave_sum(s[u]);
+    if (lane == 0 && i < a.P) a.e[(long)b * a.P + i] = t;
+  }
+}
+
+// z of caption blockIdx.x for the channel pieces blockIdx.y * 32 .. + 31 (LDS: alpha [P], then the partials [kTfCtxGroups][32 * NV])
+template <typename TA>
+__global__ __launch_bounds__(256) void attn_tf_ctx_kernel(const AttnTfArgs a) {
+  constexpr int NV = Vec16<TA>::NV;
+  constexpr int W = kTfCtxPieces * NV;                     // channels per workgroup
+  constexpr int kZ = 8;                                    // positions in flight per thread
+  extern __shared__ float tfc_s[];
+  float* al_s = tfc_s;
+  float* part_s = tfc_s + ((a.P + 3) & ~3);
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  float* alpha = blockIdx.y == 0 ? a.alpha + (long)b * a.P : nullptr;
+  float* alphas = blockIdx.y == 0 && a.alphas ? a.alphas + (long)b * a.alphas_ld : nullptr;
+  if (a.t >= a.lengths[b]) {                               // past the caption's length: a zero alpha row, z stays zero
+    if (alpha)
+      for (int i = tid; i < a.P; i += 256) {
+        alpha[i] = 0.f;
+        if (alphas) alphas[i] = 0.f;
+      }
+    return;
+  }
+  // alpha = softmax over the P positions by wave 0 (the same bits in every workgroup of the caption)
+  if (tid < 64) {
+    const float* er = a.e + (long)b * a.P;
+    float m = -INFINITY;
+    for (int i = lane; i < a.P; i += 64) m = fmaxf(m, er[i]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int i = lane; i < a.P; i += 64) {
+      const float x = expf(er[i] - m);
+      al_s[i] = x;
+      s += x;
+    }
+    s = wave_sum(s);
+    for (int i = lane; i < a.P; i += 64) {
+      const float al = al_s[i] / s;
+      al_s[i] = al;
+      if (alpha) alpha[i] = al;
+      if (alphas) alphas[i] = al;
+    }
+  }
+  __syncthreads();
+  // thread = (position group g, channel piece p): group g sums the positions g, g + 8, ...
+  const int p = tid % kTfCtxPieces, g = tid / kTfCtxPieces;
+  const int c0 = (blockIdx.y * kTfCtxPieces + p) * NV;
+  const TA* fm = (const TA*)a.fmap + (long)b * a.P * a.C + (c0 < a.C ? c0 : 0);
+  float acc[NV];
+#pragma unroll
+  for (int q = 0; q < NV; ++q) acc[q] = 0.f;
+  for (int i0 = g; i0 < a.P; i0 += kTfCtxGroups * kZ) {
+    float v[kZ][NV];
+#pragma unroll
+    for (int u = 0; u < kZ; ++u) {                          // unconditional loads (a position past P re-reads the group's first)
+      const int i = i0 + u * kTfCtxGroups;
+      Vec16<TA>::load(fm + (long)(i < a.P ? i : i0) * a.C, v[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < kZ; ++u) {
+      const int i = i0 + u * kTfCtxGroups;
+      const float al = i < a.P ? al_s[i] : 0.f;
+#pragma unroll
+      for (int q = 0; q < NV; ++q) acc[q] += al * v[u][q];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NV; ++q) part_s[g * W + p * NV + q] = acc[q];
+  __syncthreads();
+  const int cl = blockIdx.y * W + tid;                     // the groups' partial sums, added in group order by the channel's owner
+  if (tid < W && cl < a.C) {
+    float z = part_s[tid];
+#pragma unroll
+    for (int gg = 1; gg < kTfCtxGroups; ++gg) z += part_s[gg * W + tid];
+    ((TA*)a.z)[(long)b * a.ldx + cl] = from_f32<TA>(z);
+  }
+}
+
+template <typename TA>
+int attn_tf_step(const AttnTfArgs& f, int B, hipStream_t stream) {
+  constexpr int NV = Vec16<TA>::NV;
+  const size_t lds = (size_t)(((f.P + 3) & ~3) + kTfCtxGroups * kTfCtxPieces * NV) * sizeof(float);
+  static LdsGrant gc;
+  GIC_CHECK_ARG(grant_lds(attn_tf_ctx_kernel<TA>, lds, gc), "attn_tf_ctx: cannot reserve %zu bytes of LDS", lds);
+  hipLaunchKernelGGL((attn_tf_energy_kernel<TA>), dim3((unsigned)B, (unsigned)cdiv(f.P, kTfEnergyPos)), dim3(256), 0, stream, f);
+  GIC_CHECK_LAUNCH("attn_tf_energy");
+  hipLaunchKernelGGL((attn_tf_ctx_kernel<TA>), dim3((unsigned)B, (unsigned)cdiv(f.C, kTfCtxPieces * NV)), dim3(256), lds, stream, f);
+  GIC_CHECK_LAUNCH("attn_tf_ctx");
+  return GIC_OK;
+}
+
+// floats of logits_ws: the logits [B * Tmax, V] after the loop, the energies [B, P] during it
+size_t tf_ws_floats(const ACtx& c, int Tmax) {
+  const size_t lg = (size_t)c.B * Tmax * c.V, en = (size_t)c.B * c.P;
+  return lg > en ? lg : en;
+}
+
+template <typename TA>
+int attn_tf_fwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st, const float* features,
+                  const void* fmap, const int64_t* caps, const int32_t* lengths, int Tmax, const float* noise_u, uint64_t seed,
+                  float temperature, int pretrain, float* logits_ws, void* out, float* alphas, float* h_n, float* c_n, hipStream_t stream) {
+  const int B = c.B, T = c.L, V = c.V, E = c.E, H = c.H;
+  const long ld = c.ldx();
+  // slots 0..Tmax of xh start at zero (z of padded rows stays zero: finite operands of the weight gradients), c_0 = 0, x_0 = features,
+  // x_t = embed(caps[:, t-1])
+  GIC_PROPAGATE(fill_zero(st->xh, (size_t)(Tmax + 1) * B * ld * c.asz(), stream));
+  GIC_PROPAGATE(fill_zero(st->c, (size_t)B * H * sizeof(float), stream));
+  GIC_PROPAGATE(cast2d(features, DT_F32, E, st->xh, c.dt, ld, B, E, stream));
+  GIC_PROPAGATE(embed_rows_tf(c.dt, P->embed, caps, st->xh, ld, B, T - 1, E, V, stream));
+  {  // fp = fmap W_f^T + b_f
+    GemmDesc g;
+    g.A = fmap; g.lda = c.C; g.B = S->wf; g.ldb = c.C; g.C = st->fproj; g.ldc = c.A;
+    g.M = B * c.P; g.N = c.A; g.K = c.C; g.in_dtype = c.dt; g.out_dtype = c.dt; g.bias = P->b_f;
+    g.no_split = 1;
+    GIC_PROPAGATE(gemm(g, stream));
+  }
+  for (int t = 0; t < Tmax; ++t) {
+    TA* xh_t = (TA*)st->xh + (long)t * B * ld;
+    float* hp = st->hproj + (long)t * B * c.A;
+    {  // hp [B, A] = h_{t-1} W_h^T
+      GemmDesc g;
+      g.A = xh_t + c.din(); g.lda = ld; g.B = S->wh; g.ldb = H; g.C = hp; g.ldc = c.A;
+      g.M = B; g.N = c.A; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32;
+      g.no_split = 1;
+      GIC_PROPAGATE(gemm(g, stream));
+    }
+    AttnTfArgs f;
+    f.fproj = st->fproj; f.fmap = fmap; f.w_a = P->w_a; f.hp = hp; f.lengths = lengths; f.t = t; f.e = logits_ws;
+    f.z = xh_t + E; f.ldx = ld; f.alpha = st->alpha + (long)t * B * c.P;
+    f.alphas = alphas ? alphas + (long)t * c.P : nullptr; f.alphas_ld = (long)Tmax * c.P;
+    f.P = c.P; f.A = c.A; f.C = c.C;
+    GIC_PROPAGATE(attn_tf_step<TA>(f, B, stream));
+    LstmStepArgs a;
+    a.xh_t = xh_t; a.xh_next = xh_t + (long)B * ld; a.wcat = S->wcat; a.bsum = S->bsum;
+    a.c_prev = st->c + (long)t * B * H; a.c_new = st->c + (long)(t + 1) * B * H;
+    a.gates = st->gates + (long)t * B * 4 * H;
+    a.h_out = (TA*)st->hout + (long)t * H; a.ld_out = (long)Tmax * H;        // hout viewed as [B, Tmax, H]
+    a.B = B; a.H = H; a.din = c.din(); a.ldx = ld; a.gw = E;
+    a.pack_len = lengths; a.pack_t = t;
+    GIC_PROPAGATE(lstm_step(a, c.dt, stream));
+  }
+  const long rows = (long)B * Tmax;
+  {  // one projection over all B * Tmax rows
+    GemmDesc g;
+    g.A = st->hout; g.lda = H; g.B = S->wout; g.ldb = H; g.C = logits_ws; g.ldc = V;
+    g.M = (int)rows; g.N = V; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = P->b_out;
+    g.no_split = 1;
+    GIC_PROPAGATE(gemm(g, stream));
+  }
+  GIC_PROPAGATE(gumbel_softmax_rows(c.dt, logits_ws, noise_u, seed, (uint64_t)0x7466, temperature, pretrain, out, rows, V, stream));
+  // slot Tmax holds every row's state at its own last step (rows past their length kept it)
+  GIC_PROPAGATE(cast2d((const TA*)st->xh + (long)Tmax * B * ld + c.din(), c.dt, ld, h_n, DT_F32, H, B, H, stream));
+  return cast2d(st->c + (long)Tmax * B * H, DT_F32, H, c_n, DT_F32, H, B, H, stream);
+}
+
+}  // namespace
+}  // namespace gic
+
+using namespace gic;
+
+extern "C" {
+
+int gic_attn_forward_tf_ws_bytes(const gic_attn_dims* dims, int Tmax, uint64_t* out) {
+  ACtx c;
+  GIC_PROPAGATE(check_attn_dims(dims, c));
+  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "attn_forward_tf_ws_bytes: Tmax must be in 1..L (= caption length + 1)");
+  GIC_CHECK_ARG(out, "attn_forward_tf_ws_bytes: null out");
+  *out = (uint64_t)tf_ws_floats(c, Tmax) * sizeof(float);
+  return GIC_OK;
+}
+
+int gic_attn_forward_tf(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st,
+                        const float* features, const void* fmap, const int64_t* caps, const int32_t* lengths, int Tmax, const float* noise_u,
+                        uint64_t seed, float temperature, int pretrain, float* logits_ws, void* out, float* alphas, float* h_n, float* c_n,
+                        void* stream) {
+  ACtx c;
+  GIC_PROPAGATE(check_attn_dims(dims, c));
+  GIC_CHECK_ARG(P && S && st && features && fmap && lengths && logits_ws && out && h_n && c_n, "attn_forward_tf: null argument");
+  GIC_CHECK_ARG(c.L == 1 || caps, "attn_forward_tf: caps is null");
+  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "attn_forward_tf: Tmax must be in 1..L (= caption length + 1)");
+  GIC_CHECK_ARG(P->embed && P->b_out && P->b_f && P->w_a && S->wcat && S->bsum && S->wout && S->wf && S->wh, "attn_forward_tf: null weights");
+  GIC_CHECK_ARG(st->xh && st->gates && st->c && st->hout && st->fproj && st->alpha && st->hproj, "attn_forward_tf: null state buffer");
+  if (c.dt == DT_F32)
+    return attn_tf_fwd_t<float>(c, P, S, st, features, fmap, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, out, alphas,
+                                h_n, c_n, (hipStream_t)stream);
+  return attn_tf_fwd_t<bf16_t>(c, P, S, st, features, fmap, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, out, alphas,
+                               h_n, c_n, (hipStream_t)stream);
+}
+
+int gic_attn_forward_tf_bwd(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st,
+                            const gic_attn_bwd_ws* ws, const void* fmap, const void* pred, const int64_t* caps, const int32_t* lengths, int Tmax,
+                            const void* d_pred, const float* d_alphas, float temperature, int pretrain, const gic_attn_grads* G, void* stream_) {
+  ACtx c;
+  GIC_PROPAGATE(check_attn_dims(dims, c));
+  GIC_CHECK_ARG(P && S && st && ws && fmap && pred && lengths && d_pred && G, "attn_forward_tf_bwd: null argument");
+  GIC_CHECK_ARG(c.L == 1 || caps, "attn_forward_tf_bwd: caps is null");
+  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "attn_forward_tf_bwd: Tmax must be in 1..L (= caption length + 1)");
+  GIC_CHECK_ARG(S->wcat_t && S->wout && S->wh && P->w_a, "attn_forward_tf_bwd: null weights");
+  GIC_CHECK_ARG(st->xh && st->gates && st->c && st->hout && st->fproj && st->alpha && st->hproj, "attn_forward_tf_bwd: null state buffer");
+  GIC_CHECK_ARG(ws->dlogits && ws->dhout && ws->dgates && ws->dc && ws->dz && ws->dalpha && ws->dh_extra && ws->dhproj && ws->dfproj && ws->dwa_rows && ws->dx &&
+                (c.dt == DT_F32 || ws->dfproj_act), "attn_forward_tf_bwd: null workspace buffer");
+  GIC_CHECK_ARG(G->embed && G->w_ih && G->w_hh && G->b_ih && G->b_hh && G->w_out && G->b_out && G->w_f && G->b_f && G->w_h && G->w_a && G->features,
+                "attn_forward_tf_bwd: null gradient buffer");
+  hipStream_t stream = (hipStream_t)stream_;
+  const int T = c.L;
+  // the saved state and every [B, Tmax, .] tensor are laid out for Tmax steps: the sampled path's backward runs on that view
+  c.L = Tmax;
+  GIC_PROPAGATE(decoder_output_bwd(c.dt, c.B, Tmax, c.V, c.H, pred, d_pred, temperature, nullptr, pretrain, ws->dlogits, S->wout, st->hout,
+                                   ws->dhout, G->w_out, G->b_out, stream));
+  GIC_PROPAGATE(zero_past_length(ws->dhout, lengths, c.B, Tmax, c.H, stream));
+  return attn_bwd_recurrent(c, P, S, st, ws, fmap, caps, T - 1, d_alphas, G, stream);
+}
+
+}  // extern "C"

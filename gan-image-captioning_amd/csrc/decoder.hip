@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void gumbel_softmax_argmax_kernel(
     const long f = force_ids[(long)b * ids_stride];
     best_i = (int)(f < 0 ? 0 : (f >= V ? V - 1 : f));
   }
-  if (tid == 0) ids[(long)b * ids_stride] = best_i;
+  if (tid == 0 && ids) ids[(long)b * ids_stride] = best_i;
   if (x_next)
     for (int e = tid; e < E; e += 256) x_next[(long)b * ld_x + e] = from_f32<TA>(embed[(long)best_i * E + e]);
 }
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(1024) void gumbel_softmax_argmax_reg_kernel(
     const long f = force_ids[(long)b * ids_stride];
     best_i = (int)(f < 0 ? 0 : (f >= V ? V - 1 : f));
   }
-  if (tid == 0) ids[(long)b * ids_stride] = best_i;
+  if (tid == 0 && ids) ids[(long)b * ids_stride] = best_i;
   if (x_next)
     for (int e = tid; e < E; e += 1024) x_next[(long)b * ld_x + e] = from_f32<TA>(embed[(long)best_i * E + e]);
 }
@@ -808,6 +808,42 @@ __global__ void zero_past_length_kernel(float* __restrict__ dhout, const int32_t
     if (t >= lengths[b]) dhout[i] = 0.f;
   }
 }
+
+namespace gic {
+
+int embed_rows_tf(int dt, const float* embed, const int64_t* caps, void* xh0, long ld, int B, int Tm1, int E, int V, hipStream_t stream) {
+  if (Tm1 < 1) return GIC_OK;
+  const long total = (long)Tm1 * B * E;
+  const dim3 grid((unsigned)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256));
+  if (dt == DT_F32) hipLaunchKernelGGL((embed_rows_tf_kernel<float>), grid, dim3(256), 0, stream, embed, caps, (float*)xh0, ld, B, Tm1, E, V);
+  else hipLaunchKernelGGL((embed_rows_tf_kernel<bf16_t>), grid, dim3(256), 0, stream, embed, caps, (bf16_t*)xh0, ld, B, Tm1, E, V);
+  GIC_CHECK_LAUNCH("embed_rows_tf");
+  return GIC_OK;
+}
+
+int zero_past_length(float* dhout, const int32_t* lengths, int B, int Tmax, int H, hipStream_t stream) {
+  const long total = (long)B * Tmax * H;
+  hipLaunchKernelGGL(zero_past_length_kernel, dim3((unsigned)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256)), dim3(256), 0, stream,
+                     dhout, lengths, B, Tmax, H);
+  GIC_CHECK_LAUNCH("zero_past_length");
+  return GIC_OK;
+}
+
+int gumbel_softmax_rows(int dt, float* logits, const float* u, uint64_t seed, uint64_t rng_stream, float temperature, int pretrain, void* out,
+                        long rows, int V, hipStream_t stream) {
+  if (dt == DT_F32)
+    hipLaunchKernelGGL((gumbel_softmax_argmax_kernel<float>), dim3((unsigned)rows), dim3(256), 0, stream, logits, u, seed, rng_stream, temperature,
+                       pretrain, (float*)out, (long)V, (int64_t*)nullptr, (long)1, (const float*)nullptr, (float*)nullptr, (long)0, V, 0,
+                       (const int64_t*)nullptr, (const int32_t*)nullptr, 0);
+  else
+    hipLaunchKernelGGL((gumbel_softmax_argmax_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, stream, logits, u, seed, rng_stream,
+                       temperature, pretrain, (bf16_t*)out, (long)V, (int64_t*)nullptr, (long)1, (const float*)nullptr, (bf16_t*)nullptr, (long)0,
+                       V, 0, (const int64_t*)nullptr, (const int32_t*)nullptr, 0);
+  GIC_CHECK_LAUNCH("gumbel_softmax (teacher forced)");
+  return GIC_OK;
+}
+
+}  // namespace gic
 
 template <typename TA>
 int forward_tf_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,

@@ -17,6 +17,11 @@
 #include "common.h"
 
 struct gic_attn_dims;
+struct gic_attn_params;
+struct gic_attn_shadow;
+struct gic_attn_state;
+struct gic_attn_bwd_ws;
+struct gic_attn_grads;
 
 namespace gic {
 
@@ -45,6 +50,9 @@ struct LstmStepArgs {
   const int32_t* parent = nullptr;   // [B]: the h part of xh_t and c_prev are read from row parent[r]
   const int32_t* token = nullptr;    // [B]: the gathered x part is embed[token[r]] (needs `gather`)
   const int32_t* stop = nullptr; int stop_at = 0;  // *stop >= stop_at: return at once (every beam has finished)
+  // teacher-forced decode (attn_tf.hip), optional: with pack_len, a row with pack_t >= pack_len[b] keeps (h, c) (pack_padded_sequence)
+  // and writes a zero h_out row and zero gates; not combined with the beam arguments
+  const int32_t* pack_len = nullptr; int pack_t = 0;
   int dbg = 0;
 };
 
@@ -115,6 +123,11 @@ struct ACtx {
   size_t asz() const { return (size_t)dtype_size(dt); }
 };
 int check_attn_dims(const gic_attn_dims* d, ACtx& c);   // V % 4, E / H / C / A % 8, P <= 1024, A <= 2048
+// attention.hip: everything of gic_attn_sample_bwd after the output layer's backward (ws->dhout filled) over c.L steps -- the reverse
+// recurrence, the batched weight gradients, d features and the embedding scatter over ids (rows ids_stride apart; 0 = c.L).
+// d_alphas: f32 [B, c.L, P] added to d alpha before the softmax backward, or null.
+int attn_bwd_recurrent(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st, const gic_attn_bwd_ws* ws,
+                       const void* fmap, const int64_t* ids, long ids_stride, const float* d_alphas, const gic_attn_grads* G, hipStream_t stream);
 
 // 16 bytes of compute-dtype values as floats: NV = 8 (bf16) or 4 (f32)
 template <typename TA> struct Vec16;

@@ -131,7 +131,8 @@ template <> __device__ __forceinline__ u32x4 pack_f32_chunk<bf16_t>(const f32x4&
 // cell nonlinearities.
 // (device body: workgroup (bx, by) of the launch grid)
 // BEAM: the beam-search reorder (decoder_step.h LstmStepArgs.parent / token / stop); false is the roll-out's kernel exactly
-template <typename TA, bool BEAM = false>
+// PACK: the teacher-forced decode's packed rows (LstmStepArgs.pack_len / pack_t); false is the roll-out's kernel exactly
+template <typename TA, bool BEAM = false, bool PACK = false>
 __device__ __forceinline__ void lstm_step_body(const LstmStepArgs& a, const int KC, const int bx, const int by, unsigned char* ls_smem, int* ids_s,
                                                int* par_s = nullptr) {
   constexpr int SZ = sizeof(TA), VE = 16 / SZ;
@@ -297,7 +298,18 @@ __device__ __forceinline__ void lstm_step_body(const LstmStepArgs& a, const int 
   __syncthreads();
   DSTAMP(0, 5);
 
-  if (pok) {
+  if (PACK && pok && a.pack_t >= a.pack_len[pb]) {            // past the row's length: (h, c) kept, zero output and gates
+    const long bh = (long)pb * a.H + pj;
+    if (a.gates) {
+      float* go = a.gates + (long)pb * 4 * a.H + pj;
+      go[0] = 0.f; go[a.H] = 0.f; go[2 * a.H] = 0.f; go[3 * a.H] = 0.f;
+    }
+    a.c_new[bh] = pc;
+    const TA hv = xh[(long)pb * a.ldx + a.din + pj];
+    ((TA*)a.xh_next)[(long)pb * a.ldx + a.din + pj] = hv;
+    if (a.h_up) ((TA*)a.h_up)[(long)pb * a.ld_up + pj] = hv;
+    if (a.h_out) ((TA*)a.h_out)[(long)pb * a.ld_out + pj] = from_f32<TA>(0.f);
+  } else if (pok) {
     const int rb = tid >> 2, u = tid & 3;
     const int b = pb, j = pj;
     float g4[4];
@@ -330,6 +342,13 @@ __global__ __launch_bounds__(512) void lstm_step_kernel(const LstmStepArgs a, co
   extern __shared__ __attribute__((aligned(16))) unsigned char ls_smem[];
   __shared__ int ids_s[kStepRows];
   lstm_step_body<TA>(a, KC, blockIdx.x, blockIdx.y, ls_smem, ids_s);
+}
+
+template <typename TA>
+__global__ __launch_bounds__(512) void lstm_step_pack_kernel(const LstmStepArgs a, const int KC) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ls_smem[];
+  __shared__ int ids_s[kStepRows];
+  lstm_step_body<TA, false, true>(a, KC, blockIdx.x, blockIdx.y, ls_smem, ids_s);
 }
 
 template <typename TA>
@@ -786,7 +805,18 @@ int lstm_step(const LstmStepArgs& a, int dtype, hipStream_t stream) {
   b.dbg = g_step_dbg;
   const int KC = lstm_chunk(dtype, (int)a.ldx);
   const size_t lds = lstm_lds_bytes(dtype, (int)a.ldx);
-  if (beam) {
+  GIC_CHECK_ARG(!(beam && a.pack_len), "lstm_step: packed rows and the beam arguments do not combine");
+  if (a.pack_len) {
+    if (dtype == DT_F32) {
+      static LdsGrant p32;
+      GIC_PROPAGATE(allow_lds(lstm_step_pack_kernel<float>, lds, p32));
+      hipLaunchKernelGGL((lstm_step_pack_kernel<float>), grid, dim3(512), lds, stream, b, KC);
+    } else {
+      static LdsGrant p16;
+      GIC_PROPAGATE(allow_lds(lstm_step_pack_kernel<bf16_t>, lds, p16));
+      hipLaunchKernelGGL((lstm_step_pack_kernel<bf16_t>), grid, dim3(512), lds, stream, b, KC);
+    }
+  } else if (beam) {
     if (dtype == DT_F32) {
       static LdsGrant b32;
       GIC_PROPAGATE(allow_lds(lstm_step_beam_kernel<float>, lds, b32));

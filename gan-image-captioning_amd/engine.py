@@ -995,6 +995,85 @@ class AttnDecoderEngine:
             return ids, scores, lengths, alphas
         return ids, scores, lengths
 
+    def tf_ws_bytes(self, B: int, T: int, Tmax: int) -> int:
+        """Bytes of gic_attn_forward_tf's logits_ws (host-only query)."""
+        out = C.c_uint64(0)
+        L.check(L.load().gic_attn_forward_tf_ws_bytes(C.byref(self.dims(B, T)), int(Tmax), C.byref(out)), "gic_attn_forward_tf_ws_bytes")
+        return int(out.value)
+
+    def forward_tf(self, params, features, fmap, caps: torch.Tensor, lengths, temperature: float, pretrain: bool = False,
+                   noise_u: Optional[torch.Tensor] = None, seed: int = 0, want_alphas: bool = False, keep_state: bool = False):
+        """gic_attn_forward_tf: the teacher-forced decode (DecoderEngine.forward_tf with the attention step).  ``caps`` int64 [B, T-1],
+        ``lengths`` B values in 1..T, ``fmap`` [B, P, C] (cast to the compute dtype as in sample_fwd).  Returns (pred act [B, Tmax, V],
+        (h_n, c_n) f32 [1, B, H], alphas f32 [B, Tmax, P] or None); with ``keep_state`` also what ``forward_tf_bwd`` needs."""
+        self.check_params(params)
+        require_gpu(features, fmap, caps, noise_u)
+        B, Lc = caps.shape
+        T = Lc + 1
+        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lens) != B or min(lens) < 1 or max(lens) > T:
+            raise ValueError(f"lengths must hold {B} values in 1..{T}")
+        Tmax = max(lens)
+        if tuple(features.shape) != (B, self.E) or features.dtype != torch.float32 or caps.dtype != torch.int64:
+            raise ValueError(f"features must be float32 [B, {self.E}] and caps int64 [B, L]")
+        if noise_u is not None:
+            if tuple(noise_u.shape) != (B, Tmax, self.V):
+                raise ValueError(f"noise_u must be [B, max(lengths)={Tmax}, V]")
+            noise_u = noise_u.contiguous().float()
+        fmap = self._act_fmap(fmap, B)
+        dev = features.device
+        self.prepare(params)
+        st = self.alloc_state(B, T, dev)
+        out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
+        h_n = torch.empty(1, B, self.H, device=dev, dtype=torch.float32)
+        c_n = torch.empty_like(h_n)
+        alphas = torch.empty(B, Tmax, self.P, device=dev, dtype=torch.float32) if want_alphas else None
+        logits_ws = torch.empty(self.tf_ws_bytes(B, T, Tmax) // 4, device=dev, dtype=torch.float32)
+        len_dev = torch.tensor(lens, dtype=torch.int32, device=dev)
+        caps = caps.contiguous()
+        L.check(L.load().gic_attn_forward_tf(
+            C.byref(self.dims(B, T)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
+            ptr(features.contiguous()), ptr(fmap), ptr(caps), ptr(len_dev), Tmax, ptr(noise_u), int(seed) & (2 ** 64 - 1),
+            float(temperature), int(bool(pretrain)), ptr(logits_ws), ptr(out), ptr(alphas), ptr(h_n), ptr(c_n), stream_ptr()),
+            "gic_attn_forward_tf")
+        if keep_state:
+            st["fmap"] = fmap
+            return out, (h_n, c_n), alphas, {"st": st, "caps": caps, "len_dev": len_dev, "Tmax": Tmax, "T": T}
+        return out, (h_n, c_n), alphas
+
+    def forward_tf_bwd(self, params, saved, pred: torch.Tensor, d_pred: Optional[torch.Tensor], temperature: float, pretrain: bool = False,
+                       d_alphas: Optional[torch.Tensor] = None, ws=None, grads=None) -> List[torch.Tensor]:
+        """gic_attn_forward_tf_bwd: gradients of a loss on ``pred`` (``d_pred``; None = zeros) and on the alphas (``d_alphas`` f32
+        [B, Tmax, P] or None) of the ``forward_tf(..., keep_state=True)`` call that returned ``saved``; ordered as ``sample_bwd``'s
+        (parameters in NAMES order, then d features)."""
+        B, Tmax, dev = pred.shape[0], saved["Tmax"], pred.device
+        if d_pred is None:
+            d_pred = torch.zeros(pred.shape, device=dev, dtype=self.act)
+        if tuple(d_pred.shape) != tuple(pred.shape):
+            raise ValueError("d_pred must have pred's shape")
+        if d_pred.dtype != self.act:
+            t = d_pred.contiguous()
+            dst = torch.empty(t.shape, device=dev, dtype=self.act)
+            cast2d(t, dst, t.numel() // self.V, self.V, self.V, self.V)
+            d_pred = dst
+        d_pred = d_pred.contiguous()
+        if d_alphas is not None:
+            if tuple(d_alphas.shape) != (B, Tmax, self.P):
+                raise ValueError(f"d_alphas must be [B, max(lengths)={Tmax}, P={self.P}]")
+            d_alphas = d_alphas.contiguous().float()
+        self.prepare(params)
+        ws = ws if ws is not None else self.alloc_bwd_ws(B, saved["T"], dev)
+        w = L.AttnBwdWs()
+        for k, v in ws.items():
+            setattr(w, k, ptr(v))
+        grads = grads if grads is not None else [torch.empty_like(p) for p in params] + [torch.empty(B, self.E, device=dev, dtype=torch.float32)]
+        L.check(L.load().gic_attn_forward_tf_bwd(
+            C.byref(self.dims(B, saved["T"])), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)),
+            C.byref(self._state_struct(saved["st"])), C.byref(w), ptr(saved["st"]["fmap"]), ptr(pred), ptr(saved["caps"]),
+            ptr(saved["len_dev"]), Tmax, ptr(d_pred), ptr(d_alphas), float(temperature), int(bool(pretrain)),
+            C.byref(self._pstruct(grads[:-1], L.AttnGrads, grads[-1])), stream_ptr()), "gic_attn_forward_tf_bwd")
+        return grads
+
     def alloc_bwd_ws(self, B: int, Lc: int, dev):
         f32 = torch.float32
         return {

@@ -241,6 +241,28 @@ class _AttnSampleFn(torch.autograd.Function):
         return (None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
 
 
+class _AttnForwardTfFn(torch.autograd.Function):
+    """AttnDecoder.forward with autograd: gic_attn_forward_tf / gic_attn_forward_tf_bwd; the alphas are differentiable too."""
+
+    @staticmethod
+    def forward(ctx, eng, temperature, pretrain, caps, lengths, noise_u, seed, fmap, features, *params):
+        dparams = [p.detach() for p in params]
+        pred, (h_n, c_n), alphas, saved = eng.forward_tf(dparams, features.detach().float(), fmap.detach(), caps, lengths, temperature,
+                                                         pretrain, noise_u, seed, want_alphas=True, keep_state=True)
+        ctx.eng, ctx.temperature, ctx.pretrain, ctx.saved, ctx.dparams = eng, temperature, pretrain, saved, dparams
+        ctx.save_for_backward(pred)
+        ctx.mark_non_differentiable(h_n, c_n)
+        ctx.set_materialize_grads(False)
+        return pred, h_n, c_n, alphas
+
+    @staticmethod
+    def backward(ctx, d_pred, _d_h, _d_c, d_alphas):
+        (pred,) = ctx.saved_tensors
+        grads = ctx.eng.forward_tf_bwd(ctx.dparams, ctx.saved, pred, d_pred, ctx.temperature, ctx.pretrain, d_alphas=d_alphas)
+        ctx.saved = None
+        return (None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
+
+
 class _AttnParams(nn.Module):
     """Additive (Show-Attend-Tell) attention parameters: e_i = w_a . tanh(W_f a_i + b_f + W_h h)."""
 
@@ -305,6 +327,31 @@ class AttnDecoder(nn.Module):
         if return_beams:
             return out
         return tuple(t[:, 0] for t in out)
+
+    def forward(self, features, fmap, caps, lengths, pretrain=False, noise_u=None, return_alphas=False):
+        """Teacher-forced decode (Decoder.forward with the attention step, gicap.h gic_attn_forward_tf): step 0 is fed ``features``,
+        step t > 0 embed(caps[:, t-1]), packed with ``lengths`` (each 1..caps.shape[1] + 1).  Returns (pred [B, max(lengths), V],
+        (h_n, c_n) [1, B, H]) with pred = logits (pretrain) or softmax((logits + gumbel) * temperature); ``return_alphas`` appends the
+        attention weights f32 [B, max(lengths), P] (zero past a caption's length), differentiable like ``pred``.  Gradients flow to the
+        decoder parameters and ``features`` (padded positions reach the projection's bias only); the returned hidden state is not
+        differentiated.  ``fmap`` [B, P, C]: the trunk's last feature map (no gradient into it).  ``noise_u`` [B, max(lengths), V]
+        replaces the device draw."""
+        if fmap is None:
+            raise ValueError("the attention decoder needs the trunk's feature map: forward(features, fmap, caps, lengths)")
+        seed = 0 if noise_u is not None else SEEDS.next()
+        params = self.param_list()
+        if not torch.is_grad_enabled() or not (features.requires_grad or any(p.requires_grad for p in params)):
+            with torch.no_grad():
+                pred, hc, alphas = self.engine().forward_tf([p.detach() for p in params], features.detach().float(), fmap.detach(), caps,
+                                                            lengths, float(self.temperature), bool(pretrain), noise_u, seed,
+                                                            want_alphas=bool(return_alphas))
+        else:
+            pred, h_n, c_n, alphas = _AttnForwardTfFn.apply(self.engine(), float(self.temperature), bool(pretrain), caps, lengths, noise_u,
+                                                            seed, fmap, features, *params)
+            hc = (h_n, c_n)
+        if return_alphas:
+            return pred, hc, alphas
+        return pred, hc
 
     def sample(self, features, fmap=None, states=None, pretrain=False, max_caption_len=34, noise_u=None):
         """(outputs [B,L,V], ids [B,L]) as Decoder.sample; ``fmap`` [B, P, C]: the trunk's last feature map (no gradient into it)."""
@@ -511,6 +558,9 @@ class Generator(nn.Module):
                                             length_penalty=length_penalty, return_beams=return_beams)
 
     def forward(self, images, caps, lengths, pretrain=False):
+        if isinstance(self.decoder, AttnDecoder):
+            features, fmap = self.encoder.forward_with_map(images)
+            return self.decoder(features, fmap, caps, lengths, pretrain)
         if self.args.conditional_gan:
             features = self.encoder(images)
         else:

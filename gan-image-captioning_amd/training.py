@@ -77,6 +77,12 @@ def _lookahead(loader, device):
 class GANInstructor:
     def __init__(self, args, train_dataset, dev_dataset):
         self.args = args
+        self.pretrain_mode = getattr(args, "pretrain_mode", "sample")
+        self.attn_reg = float(getattr(args, "attn_reg", 0.0))
+        if self.pretrain_mode not in ("sample", "teacher"):
+            raise ValueError(f"--pretrain-mode must be sample or teacher, got {self.pretrain_mode!r}")
+        if self.attn_reg != 0.0 and not (getattr(args, "decoder", "lstm") == "attention" and self.pretrain_mode == "teacher"):
+            raise ValueError("--attn-reg applies to --decoder attention --pretrain-mode teacher only")
         self.dist = parallel.DistInfo.from_env()
         from .generator import SEEDS
         SEEDS.rank = self.dist.rank            # replicas share weights and the torch seed, not the device noise streams
@@ -165,14 +171,35 @@ class GANInstructor:
         opt.step()
 
     # ------------------------------------------------------------------ MLE pre-training (training.py:48-126)
-    def pretrain_step(self, images, captions, max_caption_len, train=True, next_images=None):
+    def pretrain_step(self, images, captions, max_caption_len, train=True, next_images=None, lengths=None):
         feats = self._features(images, captions.shape[0], next_images)
+        if self.pretrain_mode == "teacher":
+            return self._pretrain_step_teacher(feats, captions, lengths, train)
         if self.attention:
             gen_captions, _ids = self.gen.decoder.sample(feats[0], fmap=feats[1], pretrain=True, max_caption_len=max_caption_len)
         else:
             gen_captions, _ids = self.gen.decoder.sample(feats, pretrain=True, max_caption_len=max_caption_len)
         flat = gen_captions.reshape(-1, gen_captions.size(-1))
         loss = _XentFn.apply(flat, captions.reshape(-1))                   # nn.CrossEntropyLoss(), training.py:81-83
+        if train:
+            self.optimize(self.pretrain_opt, loss, self.gen)
+        return loss
+
+    def _pretrain_step_teacher(self, feats, captions, lengths, train):
+        """--pretrain-mode teacher: pred = decoder.forward(features[, fmap], captions[:, :-1], lengths, pretrain=True), the same
+        cross entropy against captions as the free-running step; with --attn-reg lam, + lam * mean_b sum_i (1 - sum_t alpha_bti)^2."""
+        if lengths is None:
+            lengths = torch.full((captions.shape[0],), captions.shape[1], dtype=torch.int32)
+        caps = captions[:, :-1]
+        if self.attention:
+            pred, _, alphas = self.gen.decoder(feats[0], feats[1], caps, lengths, pretrain=True, return_alphas=True)
+        else:
+            pred, _ = self.gen.decoder(feats, caps, lengths, pretrain=True)
+            alphas = None
+        flat = pred.reshape(-1, pred.size(-1))
+        loss = _XentFn.apply(flat, captions[:, :pred.shape[1]].reshape(-1))
+        if self.attn_reg:
+            loss = loss + self.attn_reg * ((1.0 - alphas.sum(1)) ** 2).sum(1).mean()
         if train:
             self.optimize(self.pretrain_opt, loss, self.gen)
         return loss
@@ -186,7 +213,8 @@ class GANInstructor:
                 tqdm(total=total, disable=self.dist.rank != 0) as progress:
             for (images, captions, lengths, max_caption_len), nxt in _lookahead(loader, self.args.device):
                 loss = self.pretrain_step(images, captions, max_caption_len, train=(what == "train"),
-                                          next_images=nxt[0] if nxt is not None and nxt[0].shape == images.shape else None)
+                                          next_images=nxt[0] if nxt is not None and nxt[0].shape == images.shape else None,
+                                          lengths=lengths)
                 val = loss.item()
                 if val != val:      # gic_xent poisons the loss when a target is outside [0, V) (nn.CrossEntropyLoss would raise)
                     raise ValueError("pre-train loss is NaN: a caption token is outside [0, vocab_size=%d) or the logits overflowed"

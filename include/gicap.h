@@ -352,6 +352,31 @@ int gic_attn_beam_search(const gic_attn_dims* dims, const gic_attn_params* param
                          const gic_decoder_beam_opts* opts, void* ws, const float* features, const void* fmap, int64_t* ids,
                          float* scores, int32_t* lengths, float* alphas, void* stream);
 
+/* Teacher-forced decode with the attention decoder: the semantics of gic_decoder_forward_tf with the step of gic_attn_sample_fwd.
+ * dims->L = T = caption length + 1: step 0 is fed `features`, step t > 0 embed(caps[b, t-1]) (caps int64 [B, T-1]; may be NULL when
+ * T = 1); the attention of step t uses h_{t-1} and the LSTM input is [x_t ; z_t].  lengths int32 [B] (each 1..T) with
+ * pack_padded_sequence semantics: a row with t >= lengths[b] keeps (h, c), its LSTM output is zero (its `out` row is b_out with
+ * pretrain, else softmax((b_out + g) * temperature)) and its alphas row is zero.  Tmax = max(lengths) (the host knows it).
+ * out act [B, Tmax, V] as gic_decoder_forward_tf (noise_u f32 [B, Tmax, V], ONE draw, or Philox(seed) when NULL).  alphas: f32
+ * [B, Tmax, P] attention weights, or NULL.  h_n / c_n: f32 [B, H], each row's state at ITS last step.  state: as for
+ * gic_attn_sample_fwd with L = T (every buffer, gates included, is needed by gic_attn_forward_tf_bwd).  logits_ws: f32 scratch of
+ * gic_attn_forward_tf_ws_bytes bytes (the energies during the recurrence, the logits after it).  No f32 atomics and no split-K: two
+ * calls on the same inputs give the same bits, and the deterministic mode accepts the call. */
+int gic_attn_forward_tf_ws_bytes(const gic_attn_dims* dims, int Tmax, uint64_t* out);      /* host-only: no GPU needed */
+int gic_attn_forward_tf(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                        const gic_attn_state* state, const float* features, const void* fmap, const int64_t* caps, const int32_t* lengths,
+                        int Tmax, const float* noise_u, uint64_t seed, float temperature, int pretrain, float* logits_ws, void* out,
+                        float* alphas, float* h_n, float* c_n, void* stream);
+/* Gradients of a loss on `out` (d_pred act [B, Tmax, V]; pred = that call's `out`) and, optionally, on the attention weights (d_alphas
+ * f32 [B, Tmax, P] or NULL) of the gic_attn_forward_tf call that filled `state` (same dims, fmap, caps, lengths, Tmax, temperature,
+ * pretrain).  Padded positions pass gradient to b_out only.  ws / grads as for gic_attn_sample_bwd with L = T (grads->embed:
+ * scatter-add over caps; grads->features = d features).  (h_n, c_n) is not differentiated.  Accepted in the deterministic mode,
+ * where two calls give the same bits. */
+int gic_attn_forward_tf_bwd(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                            const gic_attn_state* state, const gic_attn_bwd_ws* ws, const void* fmap, const void* pred, const int64_t* caps,
+                            const int32_t* lengths, int Tmax, const void* d_pred, const float* d_alphas, float temperature, int pretrain,
+                            const gic_attn_grads* grads, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Discriminator.forward (src/discriminator.py:34-62) forward + backward.
  */
@@ -535,7 +560,7 @@ int gic_colsum(const void* A, int dtype, int64_t lda, int64_t rows, int64_t cols
  * default; GIC_DETERMINISTIC=1 in the environment turns it on when the library is loaded.  While it is on, every entry point
  * that accepts the call gives bit-identical results for the same inputs, shapes, library build and device model: each f32 sum
  * that several workgroups contribute to has a fixed order (no racing f32 atomics).  Entry points without a deterministic form
- * return GIC_STATUS_UNSUPPORTED instead (gic_attn_sample_fwd / gic_attn_sample_bwd; the attention decoder's beam search is accepted), as do the embedding scatters beyond their
+ * return GIC_STATUS_UNSUPPORTED instead (gic_attn_sample_fwd / gic_attn_sample_bwd; the attention decoder's beam search and teacher-forced decode are accepted), as do the embedding scatters beyond their
  * limit (more than 8192 tokens, or V > 2^19).  It does not hold across GPU models or library builds.
  * The mode is read when work is enqueued: a captured graph keeps the kernels of the mode it was captured in.
  * gic_set_deterministic returns 0; gic_get_deterministic returns the current mode (0 / 1). */
