@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: captions/sec of the full adversarial G+D train step (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   # N=1 directly;
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   # N=1 directly;
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W   # N>1: one rank per GPU over RCCL
 
@@ -11,10 +11,11 @@ in HBM: (encoder fwd) + Decoder.sample + 3x Discriminator.forward + losses + D b
 224x224 images, caption length 20, V=10000, E=H=512, 1 LSTM layer, bf16 MFMA operands with f32
 accumulation / master weights / optimizer state.  Weak scaling: every rank processes its own 64 captions.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus:
-  "roofline":     the dominant kernel replayed under HIP events on its launch stream
+Prints ONE JSON line (rank 0) with the driver's contract.  A plain run does nothing else: it sets up, warms up, times the K
+steps, writes --dump-outputs if asked and prints the line.  With --full the line also carries:
+  "roofline":     the dominant kernel replayed under HIP events on its launch stream (skip: --no-roofline)
   "cpu_baseline": the CPU oracle (oracle/cpu_step.py, a port pinned to the reference's golden vectors)
-                  timed on this box's host cores on a bounded sample (rank 0, N=1 only)
+                  timed on this box's host cores on a bounded sample (rank 0, N=1 only; skip: --no-cpu-baseline)
 """
 from __future__ import annotations
 
@@ -49,9 +50,11 @@ def parse():
     p.add_argument("--encoder", default="resnet50", choices=["resnet18", "resnet50"])
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--step-impl", default="fused", choices=["fused", "autograd"])
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-roofline", action="store_true", help="skip the roofline probe (profiling runs: only the timed steps' kernels)")
-    p.add_argument("--cpu-steps", type=int, default=20, help="timed CPU-oracle steps (after one warm-up; BASELINE.md section 2: median of >= 20)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline figure, also measure the roofline probe and the CPU baseline (minutes; off by default)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline probe (profiling runs: only the timed steps' kernels)")
+    p.add_argument("--cpu-steps", type=int, default=20, help="with --full: timed CPU-oracle steps (after one warm-up; BASELINE.md section 2: median of >= 20)")
     p.add_argument("--no-prefetch", action="store_true", help="do not hand the next batch's images to the step (no trunk prefetch)")
     p.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg4", "cfg5"],
                    help="cfg2 (default, the headline: BASELINE configs[1..2], 64 captions/GPU); cfg4: visual-attention decoder, 32 captions/GPU; "
@@ -380,12 +383,13 @@ def main():
     }
     if a.dump_outputs:
         dump_outputs(a.dump_outputs, inst, losses)        # before the roofline probe: it runs further train steps
-    log(f"timed region done: {elapsed / a.steps * 1e3:.3f} ms/step; roofline probe")
-    if not a.no_roofline:
+    log(f"timed region done: {elapsed / a.steps * 1e3:.3f} ms/step")
+    if a.full and not a.no_roofline:
+        log("roofline probe")
         # the in-step measurement runs train steps: only without data parallelism (the other ranks have left; a step would wait for
         # them in its all-reduce) -- with N > 1 the line carries the isolated replay of rank 0
         out["roofline"] = roofline_probe(inst, args, cgan, step if (a.workload != "cfg4" and world == 1) else None)
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a, cgan)
     print(json.dumps(out), flush=True)
 

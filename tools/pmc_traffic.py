@@ -1,7 +1,7 @@
 """HBM bytes per launch of the trunk kernels from two rocprofv3 PMC passes (tools only).
 
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d A -o run -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d B -o run -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d A -o run -- python3 bench.py --steps 3 --warmup 2 --full --no-cpu-baseline
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d B -o run -- python3 bench.py --steps 3 --warmup 2 --full --no-cpu-baseline
   python tools/pmc_traffic.py A/run_counter_collection.csv B/run_counter_collection.csv > profiles/rNN_pmc_traffic.json
 
 bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024 (MI355X_MICROARCH.md: counters are in KB; gfx950 FETCH_SIZE reports half of a wide
@@ -25,7 +25,7 @@ def per_kernel(path, counter):
     return acc
 f, w = per_kernel(sys.argv[1], "FETCH_SIZE"), per_kernel(sys.argv[2], "WRITE_SIZE")
 out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace) -- python3 bench.py --steps 3 --warmup 2 "
-                 "--no-cpu-baseline; MI355X, cfg2 ResNet-50 bf16; aggregated by tools/pmc_traffic.py",
+                 "--full --no-cpu-baseline; MI355X, cfg2 ResNet-50 bf16; aggregated by tools/pmc_traffic.py",
        "correction": "bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024  (MI355X_MICROARCH.md: gfx950 FETCH_SIZE reports 1/2 of a wide coalesced read; counters are in KB)"}
 for key, label in (("conv", "conv_bnstats"), ("bn_act", "bn_act")):
     if key in f and key in w:
