@@ -58,6 +58,12 @@ class DecoderBeamOpts(C.Structure):
                 ("h0", c_void_p), ("c0", c_void_p)]
 
 
+class SampleOpts(C.Structure):
+    """gic_sample_opts (gic_sample_logits, gic_decoder_sample_captions, gic_attn_sample_captions)."""
+    _fields_ = [("num_samples", C.c_int32), ("top_k", C.c_int32), ("top_p", C.c_float), ("temperature", C.c_float),
+                ("eos_id", C.c_int32), ("pad_id", C.c_int32), ("h0", c_void_p), ("c0", c_void_p)]
+
+
 STEP_SEEDS = 6
 
 
@@ -165,6 +171,14 @@ _SIGNATURES = {
     "gic_attn_beam_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int32, c_void_p]),
     "gic_attn_beam_search": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(DecoderBeamOpts), c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_sample_logits": (C.c_int, [c_void_p, C.c_int64, C.c_int32, C.c_int32, _P(SampleOpts), c_void_p, C.c_uint64, C.c_uint64, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
+    "gic_decoder_sample_ws_bytes": (C.c_int, [_P(DecoderDims), C.c_int32, c_void_p]),
+    "gic_decoder_sample_captions": (C.c_int, [_P(DecoderDims), _P(DecoderParams), _P(DecoderShadow), _P(SampleOpts), c_void_p, c_void_p,
+                                              c_void_p, C.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_attn_sample_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int32, c_void_p]),
+    "gic_attn_sample_captions": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(SampleOpts), c_void_p, c_void_p, c_void_p,
+                                           c_void_p, C.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_attn_forward_tf_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int, c_void_p]),
     "gic_attn_forward_tf": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), c_void_p, c_void_p, c_void_p, c_void_p,
                                       C.c_int, c_void_p, C.c_uint64, C.c_float, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

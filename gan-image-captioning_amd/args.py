@@ -96,6 +96,11 @@ _NATIVE = [
                                "pre-training loss (--decoder attention --pretrain-mode teacher only)"),
     ("--eval-beam-size", int, 0, "beam size of the BLEU-4 evaluation (GANInstructor.evaluate) after each adversarial epoch's validation; "
                                  "0 = off"),
+    ("--eval-num-samples", int, 0, "sampled captions per image of the diversity evaluation (GANInstructor.evaluate_diversity: BLEU-4, "
+                                   "mBLEU-4, distinct-1/2, vocabulary) after each adversarial epoch's validation; 0 = off"),
+    ("--eval-top-k", int, 0, "top-k truncation of the diversity evaluation's sampling; 0 = off"),
+    ("--eval-top-p", float, 1.0, "top-p (nucleus) truncation of the diversity evaluation's sampling; 1.0 = off"),
+    ("--eval-sample-temperature", float, 1.0, "sampling temperature of the diversity evaluation (divides the logits; not --temperature)"),
 ]
 
 

@@ -69,18 +69,6 @@ int attn_beam_dims(const gic_attn_dims* dims, int K, AttnBeamDims& d) {
   return GIC_OK;
 }
 
-struct AttnBeamArgs {
-  const void* fproj;                 // act [B, P, A]
-  const void* fmap;                  // act [B, P, C]
-  const float* w_a;                  // [A]
-  const float* hp;                   // [rows, A]: h W_h^T of the rows before the reorder
-  const int* par;                    // [rows]
-  float* e;                          // [rows, P] energies
-  void* z; long ldx;                 // act: row r's z at z + r * ldx
-  float* alpha;                      // [rows, P]: this step's slot of the alpha history, or null
-  const int* stop; int stop_at;      // *stop >= stop_at: every image has finished
-  int P, A, C;
-};
 
 // e[r, i] for the k rows of image blockIdx.x and positions blockIdx.y * 8 .. + 7: wave w takes positions w and w + 4, a lane the 16-byte
 // pieces lane, lane + 64, ... of a position's fp row; the k parents' hp rows are staged in LDS
@@ -244,7 +232,7 @@ int attn_beam_step_launch(const AttnBeamArgs& f, int B, hipStream_t stream) {
 }
 
 template <typename TA>
-int attn_beam_step(const AttnBeamArgs& f, int K, int B, hipStream_t stream) {
+int attn_beam_step_t(const AttnBeamArgs& f, int K, int B, hipStream_t stream) {
   switch (K) {
     case 1: return attn_beam_step_launch<TA, 1>(f, B, stream);
     case 2: return attn_beam_step_launch<TA, 2>(f, B, stream);
@@ -302,7 +290,7 @@ int attn_beam_t(const AttnBeamDims& d, const gic_attn_params* P, const gic_attn_
     f.z = xh_t + c.E; f.ldx = ldx; f.alpha = alphas ? ahist + (long)t * R * c.P : nullptr;
     f.stop = st.count; f.stop_at = B;
     f.P = c.P; f.A = c.A; f.C = c.C;
-    GIC_PROPAGATE(attn_beam_step<TA>(f, d.K, B, stream));
+    GIC_PROPAGATE(attn_beam_step_t<TA>(f, d.K, B, stream));
     LstmStepArgs a;
     a.xh_t = xh_t; a.xh_next = slot[nxt].xh[0]; a.wcat = S->wcat; a.bsum = S->bsum;
     a.c_prev = slot[cur].c[0]; a.c_new = slot[nxt].c[0];
@@ -329,6 +317,12 @@ int attn_beam_t(const AttnBeamDims& d, const gic_attn_params* P, const gic_attn_
 }
 
 }  // namespace
+
+int attn_beam_step(const AttnBeamArgs& f, int K, int B, int dtype, hipStream_t stream) {
+  GIC_CHECK_ARG(K >= 1 && K <= kBeamMax, "attn_beam_step: K must be 1..%d", kBeamMax);
+  return dtype == DT_F32 ? attn_beam_step_t<float>(f, K, B, stream) : attn_beam_step_t<bf16_t>(f, K, B, stream);
+}
+
 }  // namespace gic
 
 using namespace gic;

@@ -107,13 +107,29 @@ struct BeamSelectArgs {
 };
 
 // slot 0 of every layer into the K rows of each image (layer 0's input row [0, din0): features in [0, E), zeros behind; h part = h0 or 0;
-// c = c0 or 0; h0 / c0 f32 [NL, B, H] or null) and the state at t = 0: only beam 0 live, par[r] = r
+// c = c0 or 0; h0 / c0 f32 [NL, B, H] or null) and the state at t = 0: only beam 0 live (all_live: every row live, sample.hip), par[r] = r
 int beam_init(const BeamLayerPtrs& slot0, int NL, int din0, int E, int H, int B, int K, int dtype, const float* features, const float* h0,
-              const float* c0, const BeamState& s, hipStream_t stream);
+              const float* c0, const BeamState& s, hipStream_t stream, bool all_live = false);
 int beam_select(const BeamSelectArgs& a, int K, int B, hipStream_t stream);
 // ids / scores / lengths of the K beams of each image, best first; anc: null or i32 [B, K, L], the row (image * K + beam) of step t whose
 // logits gave the t-th token of each returned beam (-1 past the last step that ran)
 int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length_penalty, int64_t* ids, float* scores, int32_t* lengths,
                   int32_t* anc, hipStream_t stream);
+
+// ---- the attention kernels of one step of attn_beam.hip, shared with the attention decoder's sampler (sample.hip)
+struct AttnBeamArgs {
+  const void* fproj;                 // act [B, P, A]
+  const void* fmap;                  // act [B, P, C]
+  const float* w_a;                  // [A]
+  const float* hp;                   // [rows, A]: h W_h^T of the rows before the reorder
+  const int* par;                    // [rows]
+  float* e;                          // [rows, P] energies
+  void* z; long ldx;                 // act: row r's z at z + r * ldx
+  float* alpha;                      // [rows, P]: this step's slot of the alpha history, or null
+  const int* stop; int stop_at;      // *stop >= stop_at: every image has finished
+  int P, A, C;
+};
+// attn_beam_energy then attn_beam_ctx for the K rows of each of the B images (rows = B * K)
+int attn_beam_step(const AttnBeamArgs& f, int K, int B, int dtype, hipStream_t stream);
 
 }  // namespace gic

@@ -73,7 +73,7 @@ using LayerPtrs = BeamLayerPtrs;
 template <typename TA>
 __global__ __launch_bounds__(256) void beam_init_kernel(LayerPtrs p, int NL, int din0, int E, int H, int B, int K, const float* __restrict__ features,
                                                         const float* __restrict__ h0, const float* __restrict__ c0, float* score, int* fin, int* len,
-                                                        int* tok, int* par, int* last, int* done, int* count) {
+                                                        int* tok, int* par, int* last, int* done, int* count, int all_live) {
   const int r = blockIdx.x, img = r / K, tid = threadIdx.x;
   for (int l = 0; l < NL; ++l) {
     const int din = l == 0 ? din0 : H;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void beam_init_kernel(LayerPtrs p, int NL, int
     }
   }
   if (tid == 0) {
-    score[r] = r % K == 0 ? 0.f : -INFINITY;
+    score[r] = all_live || r % K == 0 ? 0.f : -INFINITY;
     fin[r] = 0; len[r] = 0; tok[r] = 0; par[r] = r;
     if (r % K == 0) { last[img] = -1; done[img] = 0; }
     if (r == 0) *count = 0;
@@ -288,14 +288,14 @@ int beam_select(const SelectArgs& s, int K, int B, hipStream_t stream) {
 }
 
 int beam_init(const BeamLayerPtrs& slot0, int NL, int din0, int E, int H, int B, int K, int dtype, const float* features, const float* h0,
-              const float* c0, const BeamState& s, hipStream_t stream) {
+              const float* c0, const BeamState& s, hipStream_t stream, bool all_live) {
   const dim3 grid((unsigned)(B * K));
   if (dtype == DT_F32)
     hipLaunchKernelGGL((beam_init_kernel<float>), grid, dim3(256), 0, stream, slot0, NL, din0, E, H, B, K, features, h0, c0, s.score, s.fin,
-                       s.len, s.tok, s.par, s.last, s.done, s.count);
+                       s.len, s.tok, s.par, s.last, s.done, s.count, (int)all_live);
   else
     hipLaunchKernelGGL((beam_init_kernel<bf16_t>), grid, dim3(256), 0, stream, slot0, NL, din0, E, H, B, K, features, h0, c0, s.score, s.fin,
-                       s.len, s.tok, s.par, s.last, s.done, s.count);
+                       s.len, s.tok, s.par, s.last, s.done, s.count, (int)all_live);
   GIC_CHECK_LAUNCH("beam_init");
   return GIC_OK;
 }

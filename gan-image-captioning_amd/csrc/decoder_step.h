@@ -70,7 +70,8 @@ struct VocabStepArgs {
   float* part_m = nullptr; float* part_s = nullptr; int nblk = 0;   // [B][nblk] per-tile max / sum of exp
   unsigned long long* rowkey = nullptr;      // [B], zeroed by the caller: atomicMax of (ordered tile max, ~first maximal index)
   float* part_v = nullptr; int32_t* part_i = nullptr;   // beam epilogue only (vocab_step_beam): [B][nblk][K] tile top-K pairs
-  const int32_t* stop = nullptr; int stop_at = 0;         // beam epilogue only: *stop >= stop_at -> return at once
+  const int32_t* stop = nullptr; int stop_at = 0;         // beam / logits epilogues only: *stop >= stop_at -> return at once
+  float* logits = nullptr; long ld_logits = 0;            // logits epilogue only (vocab_step_logits): f32 o + b_out [B][ld_logits]
   int B = 0, V = 0, H = 0;
   int dbg = 0;
 };
@@ -114,6 +115,9 @@ void decoder_step_debug(int v);                             // phase-ablation kn
 int lstm_step(const LstmStepArgs& a, int dtype, hipStream_t stream);
 int vocab_step(const VocabStepArgs& a, int dtype, hipStream_t stream);
 int sample_finish(const SampleFinishArgs& a, int dtype, hipStream_t stream);
+// the vocabulary product of vocab_step with the logits epilogue: a.logits = o + b_out in f32, the roll-out's bits before its noise
+// (caption sampling, sample.hip); a.stop / stop_at; the sampling and beam fields are unused
+int vocab_step_logits(const VocabStepArgs& a, int dtype, hipStream_t stream);
 
 // ---- the attention decoder's (attention.hip) shapes, shared with its beam search (attn_beam.hip)
 struct ACtx {

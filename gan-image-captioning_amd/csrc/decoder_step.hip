@@ -367,7 +367,8 @@ __global__ __launch_bounds__(512) void lstm_step_beam_kernel(const LstmStepArgs 
 // share the transcendental-heavy epilogue.  In the C tile a lane holds 4 CONSECUTIVE vocabulary entries of one batch row: one
 // Philox4x32 call (or one 16-byte load of explicit uniforms) and one vector store of e per lane and batch sub-tile.
 // BEAMK > 0: the beam-search epilogue (beam.h) in place of the sampling one -- raw logits y = o + b_out, per (row, tile) max, sum of
-// exp and top-BEAMK pairs in fixed slots; the product and its operand order are the roll-out's, so a beam's logits are sample's bits
+// exp and top-BEAMK pairs in fixed slots; the product and its operand order are the roll-out's, so a beam's logits are sample's bits.
+// BEAMK < 0: the logits epilogue (vocab_step_logits) -- y = o + b_out stored in f32, one 16-byte store per lane and batch sub-tile
 template <typename TA, bool FAST, int BEAMK = 0>
 __device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const int KC, const int bx, const int by, unsigned char* vs_smem) {
   constexpr int SZ = sizeof(TA), VE = 16 / SZ;
@@ -387,8 +388,8 @@ __device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const in
   const int mt = w >> 1, kh = w & 1;
   const int v0 = bx * kVocabTile, b0 = by * kStepRows;
   DSTAMP(1, 0);
-  if constexpr (BEAMK > 0) {
-    if (a.stop && *a.stop >= a.stop_at) return;                // (block-uniform: every image has finished)
+  if constexpr (BEAMK != 0) {
+    if (a.stop && *a.stop >= a.stop_at) return;                // (block-uniform: every image / row has finished)
   }
 
   // ---- epilogue operands that depend on nothing computed here: requested now
@@ -511,6 +512,15 @@ __device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const in
   float y[2][4];
   bool bok[2];
   int brow[2];
+  if constexpr (BEAMK < 0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int b = b0 + (2 * kh + i) * 16 + lr;
+      if (b < a.B && qok)
+        *(f32x4*)(a.logits + (long)b * a.ld_logits + vq) = (f32x4){own[i][0] + bia[0], own[i][1] + bia[1], own[i][2] + bia[2], own[i][3] + bia[3]};
+    }
+    return;
+  }
   if constexpr (BEAMK > 0) {
     // ---- beam epilogue: the tile's raw logits through LDS [64 rows][64 entries (+1 skew)], then 8 lanes per row
     __syncthreads();                                       // every wave has read its partner's partial sums from sX
@@ -627,6 +637,12 @@ template <typename TA, bool FAST>
 __global__ __launch_bounds__(512) void vocab_step_kernel(const VocabStepArgs a, const int KC) {
   extern __shared__ __attribute__((aligned(16))) unsigned char vs_smem[];
   vocab_step_body<TA, FAST>(a, KC, blockIdx.x, blockIdx.y, vs_smem);
+}
+
+template <typename TA>
+__global__ __launch_bounds__(512) void vocab_step_logits_kernel(const VocabStepArgs a, const int KC) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char vs_smem[];
+  vocab_step_body<TA, false, -1>(a, KC, blockIdx.x, blockIdx.y, vs_smem);
 }
 
 template <typename TA, int K>
@@ -869,6 +885,29 @@ int vocab_step(const VocabStepArgs& a0, int dtype, hipStream_t stream) {
     hipLaunchKernelGGL((vocab_step_kernel<bf16_t, true>), grid, dim3(512), lds, stream, a, KC);
   }
   GIC_CHECK_LAUNCH("vocab_step");
+  return GIC_OK;
+}
+
+int vocab_step_logits(const VocabStepArgs& a0, int dtype, hipStream_t stream) {
+  VocabStepArgs a = a0;
+  a.dbg = 0; a.pretrain = 1; a.u = nullptr; a.out = nullptr; a.rowkey = nullptr;
+  GIC_CHECK_ARG(a.h && a.wout && a.bias && a.logits, "vocab_step_logits: null buffer");
+  GIC_CHECK_ARG(a.B > 0 && a.V >= 4 && a.V % 4 == 0 && a.H % 8 == 0 && a.ldh % 8 == 0 && a.ld_logits >= a.V && a.ld_logits % 4 == 0,
+                "vocab_step_logits: bad dims");
+  GIC_CHECK_ARG(((uintptr_t)a.logits & 15) == 0, "vocab_step_logits: logits must be 16-byte aligned");
+  const size_t lds = vocab_lds_bytes(dtype, a.H);
+  const int KC = vocab_chunk(dtype, a.H);
+  const dim3 grid((unsigned)cdiv(a.V, kVocabTile), (unsigned)cdiv(a.B, kStepRows));
+  if (dtype == DT_F32) {
+    static LdsGrant g32;
+    GIC_PROPAGATE(allow_lds(vocab_step_logits_kernel<float>, lds, g32));
+    hipLaunchKernelGGL((vocab_step_logits_kernel<float>), grid, dim3(512), lds, stream, a, KC);
+  } else {
+    static LdsGrant g16;
+    GIC_PROPAGATE(allow_lds(vocab_step_logits_kernel<bf16_t>, lds, g16));
+    hipLaunchKernelGGL((vocab_step_logits_kernel<bf16_t>), grid, dim3(512), lds, stream, a, KC);
+  }
+  GIC_CHECK_LAUNCH("vocab_step_logits");
   return GIC_OK;
 }
 

@@ -170,6 +170,56 @@ def embedding_bwd(d_out: torch.Tensor, ids: torch.Tensor, V: int, d_weight: Opti
     return d_weight
 
 
+def sample_opts(num_samples: int = 1, top_k: int = 0, top_p: float = 1.0, temperature: float = 1.0, eos_id: int = 2,
+                pad_id: int = 0) -> L.SampleOpts:
+    """gic_sample_opts (h0 / c0 unset); the library checks the values."""
+    o = L.SampleOpts()
+    o.num_samples, o.top_k, o.top_p, o.temperature = int(num_samples), int(top_k), float(top_p), float(temperature)
+    o.eos_id, o.pad_id = int(eos_id), int(pad_id)
+    return o
+
+
+def sample_logits(logits: torch.Tensor, top_k: int = 0, top_p: float = 1.0, temperature: float = 1.0,
+                  noise_u: Optional[torch.Tensor] = None, seed: int = 0, stream_id: int = 0):
+    """gic_sample_logits: one temperature / top-k / top-p draw per row of f32 logits [rows, V] (rows may be strided).  ``noise_u``
+    f32 [rows, V] or None = Philox(seed, stream_id, row).  Returns (ids int64 [rows], logp f32 [rows] = l_tok - logsumexp(l),
+    kept int32 [rows] = the size of the kept set)."""
+    require_gpu(logits, noise_u)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError("logits must be float32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    if noise_u is not None:
+        if tuple(noise_u.shape) != (rows, V) or noise_u.dtype != torch.float32:
+            raise ValueError(f"noise_u must be float32 [{rows}, {V}]")
+        noise_u = noise_u.contiguous()
+    dev = logits.device
+    ids = torch.empty(rows, device=dev, dtype=torch.int64)
+    logp = torch.empty(rows, device=dev, dtype=torch.float32)
+    kept = torch.empty(rows, device=dev, dtype=torch.int32)
+    o = sample_opts(1, top_k, top_p, temperature)
+    L.check(L.load().gic_sample_logits(ptr(logits), int(logits.stride(0)), int(rows), int(V), C.byref(o), ptr(noise_u),
+                                       int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 64 - 1), ptr(ids), ptr(logp), ptr(kept),
+                                       stream_ptr()), "gic_sample_logits")
+    return ids, logp, kept
+
+
+def _aligned_ws(ws: Optional[torch.Tensor], nbytes: int, dev) -> torch.Tensor:
+    if ws is None or ws.numel() < nbytes or ws.data_ptr() % 256:
+        ws = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
+        off = (-ws.data_ptr()) % 256
+        ws = ws[off:off + nbytes]
+    return ws
+
+
+def _sample_noise(noise_u: Optional[torch.Tensor], Lc: int, rows: int, V: int) -> Optional[torch.Tensor]:
+    if noise_u is None:
+        return None
+    require_gpu(noise_u)
+    if tuple(noise_u.shape) != (Lc, rows, V) or noise_u.dtype != torch.float32:
+        raise ValueError(f"noise_u must be float32 [L={Lc}, B*n={rows}, V={V}]")
+    return noise_u.contiguous()
+
+
 def gan_losses(loss_type: str, d_real, d_fake, g_out, want_grads: bool = True):
     """Returns (losses[2] device tensor: [g_loss, d_loss], grads dict or None)."""
     if loss_type not in L.LOSS_TYPES:
@@ -564,6 +614,49 @@ class DecoderEngine:
         L.check(L.load().gic_decoder_beam_search(
             C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws), ptr(features),
             ptr(ids), ptr(scores), ptr(lengths), stream_ptr()), "gic_decoder_beam_search")
+        return ids, scores, lengths
+
+    def sample_ws_bytes(self, B: int, Lc: int, num_samples: int) -> int:
+        """Bytes of gic_decoder_sample_captions' workspace (host-only query; the library's own path choice sizes it)."""
+        out = C.c_uint64(0)
+        L.check(L.load().gic_decoder_sample_ws_bytes(C.byref(self.dims(B, Lc)), int(num_samples), C.byref(out)),
+                "gic_decoder_sample_ws_bytes")
+        return int(out.value)
+
+    def sample_captions(self, params, features: torch.Tensor, Lc: int, num_samples: int, top_k: int = 0, top_p: float = 1.0,
+                        temperature: float = 1.0, eos_id: int = 2, pad_id: int = 0, seed: int = 0,
+                        noise_u: Optional[torch.Tensor] = None, states=None, ws: Optional[torch.Tensor] = None):
+        """gic_decoder_sample_captions: (ids int64 [B, n, Lc], scores f32 [B, n], lengths int32 [B, n]) in row order.  ``noise_u`` f32
+        [Lc, B*n, V] or None = Philox(seed).  ``states`` = (h0, c0), each f32 [NL, B, H].  ``ws``: a uint8 workspace of at least
+        sample_ws_bytes() bytes (256-aligned)."""
+        self.check_params(params)
+        require_gpu(features)
+        B = features.shape[0]
+        if features.shape != (B, self.E) or features.dtype != torch.float32:
+            raise ValueError(f"features must be float32 [B,{self.E}], got {tuple(features.shape)} {features.dtype}")
+        features = features.contiguous()
+        dev = features.device
+        n = int(num_samples)
+        noise_u = _sample_noise(noise_u, Lc, B * n, self.V)
+        opts = sample_opts(n, top_k, top_p, temperature, eos_id, pad_id)
+        nbytes = self.sample_ws_bytes(B, Lc, n)          # (checks the dims and n before anything runs)
+        self.prepare(params)
+        ws = _aligned_ws(ws, nbytes, dev)
+        keep = []
+        if states is not None:
+            h0, c0 = (t.detach().to(torch.float32).contiguous() for t in states)
+            if tuple(h0.shape) != (self.NL, B, self.H) or tuple(c0.shape) != (self.NL, B, self.H):
+                raise ValueError(f"states must be (h0, c0), each [num_layers={self.NL}, B={B}, H={self.H}]")
+            require_gpu(h0, c0)
+            opts.h0, opts.c0 = ptr(h0), ptr(c0)
+            keep += [h0, c0]
+        ids = torch.empty(B, n, Lc, device=dev, dtype=torch.int64)
+        scores = torch.empty(B, n, device=dev, dtype=torch.float32)
+        lengths = torch.empty(B, n, device=dev, dtype=torch.int32)
+        L.check(L.load().gic_decoder_sample_captions(
+            C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
+            ptr(features), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()),
+            "gic_decoder_sample_captions")
         return ids, scores, lengths
 
     def _cast_like(self, t: torch.Tensor) -> torch.Tensor:
@@ -993,6 +1086,49 @@ class AttnDecoderEngine:
             ptr(features), ptr(fmap), ptr(ids), ptr(scores), ptr(lengths), ptr(alphas), stream_ptr()), "gic_attn_beam_search")
         if want_alphas:
             return ids, scores, lengths, alphas
+        return ids, scores, lengths
+
+    def sample_ws_bytes(self, B: int, Lc: int, num_samples: int) -> int:
+        """Bytes of gic_attn_sample_captions' workspace (host-only query)."""
+        out = C.c_uint64(0)
+        L.check(L.load().gic_attn_sample_ws_bytes(C.byref(self.dims(B, Lc)), int(num_samples), C.byref(out)), "gic_attn_sample_ws_bytes")
+        return int(out.value)
+
+    def sample_captions(self, params, features, fmap, Lc: int, num_samples: int, top_k: int = 0, top_p: float = 1.0,
+                        temperature: float = 1.0, eos_id: int = 2, pad_id: int = 0, seed: int = 0,
+                        noise_u: Optional[torch.Tensor] = None, states=None, ws: Optional[torch.Tensor] = None):
+        """gic_attn_sample_captions: (ids int64 [B, n, Lc], scores f32 [B, n], lengths int32 [B, n]) in row order.  ``fmap`` [B, P, C]
+        is cast to the compute dtype as in sample_fwd.  ``noise_u`` f32 [Lc, B*n, V] or None = Philox(seed).  ``states`` = (h0, c0),
+        each [1, B, H] or [B, H]."""
+        self.check_params(params)
+        require_gpu(features, fmap)
+        B = features.shape[0]
+        if tuple(features.shape) != (B, self.E) or features.dtype != torch.float32:
+            raise ValueError(f"features must be float32 [B,{self.E}]")
+        n = int(num_samples)
+        noise_u = _sample_noise(noise_u, Lc, B * n, self.V)
+        opts = sample_opts(n, top_k, top_p, temperature, eos_id, pad_id)
+        nbytes = self.sample_ws_bytes(B, Lc, n)
+        fmap = self._act_fmap(fmap, B)
+        features = features.contiguous()
+        dev = features.device
+        self.prepare(params)
+        ws = _aligned_ws(ws, nbytes, dev)
+        keep = []
+        if states is not None:
+            h0, c0 = (t.detach().to(torch.float32).reshape(-1, self.H).contiguous() for t in states)
+            if tuple(h0.shape) != (B, self.H) or tuple(c0.shape) != (B, self.H):
+                raise ValueError(f"states must be (h0, c0), each [1, B={B}, H={self.H}]")
+            require_gpu(h0, c0)
+            opts.h0, opts.c0 = ptr(h0), ptr(c0)
+            keep += [h0, c0]
+        ids = torch.empty(B, n, Lc, device=dev, dtype=torch.int64)
+        scores = torch.empty(B, n, device=dev, dtype=torch.float32)
+        lengths = torch.empty(B, n, device=dev, dtype=torch.int32)
+        L.check(L.load().gic_attn_sample_captions(
+            C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
+            ptr(features), ptr(fmap), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()),
+            "gic_attn_sample_captions")
         return ids, scores, lengths
 
     def tf_ws_bytes(self, B: int, T: int, Tmax: int) -> int:

@@ -215,6 +215,21 @@ class Decoder(nn.Module):
             return ids, scores, lengths
         return ids[:, 0], scores[:, 0], lengths[:, 0]
 
+    def sample_captions(self, features, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
+                        noise_u=None, states=None):
+        """Caption sampling (gicap.h gic_decoder_sample_captions): ``num_samples`` (1..8) captions per image drawn from softmax(logits /
+        ``temperature``) truncated to the ``top_k`` largest logits (0 = off) and then to the nucleus of mass ``top_p`` (1 = off); ties at
+        either boundary are kept.  <E> = ``eos_id`` ends a caption, <PAD> (0) after it.  ``temperature`` is the sampling temperature,
+        not args.temperature.  ``noise_u`` f32 [L, B*n, V] replaces the device draw (Philox(seed); ``seed`` None = the next of SEEDS).
+        Returns detached (ids int64 [B, n, L], scores f32 [B, n] = the model's log-probability of each caption, lengths int32 [B, n]),
+        in draw order.  ``max_caption_len`` None = args.max_seq_len."""
+        L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
+        seed = (0 if noise_u is not None else SEEDS.next()) if seed is None else int(seed)
+        with torch.no_grad():
+            return self.engine().sample_captions([p.detach() for p in self.param_list()], features.detach().float(), L, int(num_samples),
+                                                 int(top_k), float(top_p), float(temperature), int(eos_id), 0, seed, noise_u,
+                                                 states=states)
+
     def add_gumbel(self, o_t, eps=1e-10, gpu=0):
         """o_t + Gumbel(0,1) noise (generator.py:84-96); on the hot path this is fused into sample()."""
         u = torch.empty_like(o_t, dtype=torch.float32).uniform_(0, 1)
@@ -327,6 +342,20 @@ class AttnDecoder(nn.Module):
         if return_beams:
             return out
         return tuple(t[:, 0] for t in out)
+
+    def sample_captions(self, features, fmap=None, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2,
+                        seed=None, noise_u=None, states=None):
+        """Caption sampling with attention (gicap.h gic_attn_sample_captions): Decoder.sample_captions with the step of sample(features,
+        fmap).  ``fmap`` [B, P, C]: the trunk's last feature map (Encoder.forward_with_map).  ``states`` = (h0, c0), each [1, B, H]."""
+        if fmap is None:                # (checked before anything touches self: the LSTM decoder's call form has no map)
+            raise NotImplementedError("the attention decoder's sampling needs the trunk's feature map: sample_captions(features, fmap), "
+                                      "or Generator.sample_captions(images)")
+        L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
+        seed = (0 if noise_u is not None else SEEDS.next()) if seed is None else int(seed)
+        with torch.no_grad():
+            return self.engine().sample_captions([p.detach() for p in self.param_list()], features.detach().float(), fmap.detach(), L,
+                                                 int(num_samples), int(top_k), float(top_p), float(temperature), int(eos_id), 0, seed,
+                                                 noise_u, states=states)
 
     def forward(self, features, fmap, caps, lengths, pretrain=False, noise_u=None, return_alphas=False):
         """Teacher-forced decode (Decoder.forward with the attention step, gicap.h gic_attn_forward_tf): step 0 is fed ``features``,
@@ -556,6 +585,23 @@ class Generator(nn.Module):
                 features = self.decoder.embed(torch.ones(len(images), dtype=torch.long, device=images.device))
             return self.decoder.beam_search(features, beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id,
                                             length_penalty=length_penalty, return_beams=return_beams)
+
+    def sample_captions(self, images, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
+                        noise_u=None):
+        """``num_samples`` sampled captions per image (decoder.sample_captions), with the features formed as ``caption`` forms them:
+        the encoder in the module's current mode, or embed(<S>) with --conditional-gan 0, under no-grad; with --decoder attention the
+        encoder also gives the feature map.  Returns (ids [B, n, L], scores [B, n], lengths [B, n])."""
+        kw = dict(num_samples=num_samples, top_k=top_k, top_p=top_p, temperature=temperature, max_caption_len=max_caption_len,
+                  eos_id=eos_id, seed=seed, noise_u=noise_u)
+        with torch.no_grad():
+            if isinstance(self.decoder, AttnDecoder):
+                features, fmap = self.encoder.forward_with_map(images)
+                return self.decoder.sample_captions(features, fmap, **kw)
+            if self.args.conditional_gan:
+                features = self.encoder(images)
+            else:
+                features = self.decoder.embed(torch.ones(len(images), dtype=torch.long, device=images.device))
+            return self.decoder.sample_captions(features, **kw)
 
     def forward(self, images, caps, lengths, pretrain=False):
         if isinstance(self.decoder, AttnDecoder):

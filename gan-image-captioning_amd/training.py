@@ -354,6 +354,10 @@ class GANInstructor:
                     adv_epoch, self.gen.decoder.temperature, train_g_loss, val_g_loss, train_d_loss, val_d_loss))
             if int(getattr(self.args, "eval_beam_size", 0)) > 0 and self.dist.rank == 0:
                 self.evaluate("val", beam_size=int(self.args.eval_beam_size))
+            if int(getattr(self.args, "eval_num_samples", 0)) > 0 and self.dist.rank == 0:
+                self.evaluate_diversity("val", num_samples=int(self.args.eval_num_samples), top_k=int(getattr(self.args, "eval_top_k", 0)),
+                                        top_p=float(getattr(self.args, "eval_top_p", 1.0)),
+                                        temperature=float(getattr(self.args, "eval_sample_temperature", 1.0)))
             self.writer.flush()
 
     def evaluate(self, what="val", beam_size=3, max_caption_len=None, batch_size=None):
@@ -363,27 +367,8 @@ class GANInstructor:
         steps, by default max(args.max_seq_len, longest reference of the batch + 2): a batch's collate length, so that a short
         --max-seq-len cannot truncate every candidate below its references.  Logs the score and writes the scalar
         ``BLEU4_<what>``."""
-        from .tasks import COCO_data, SPECIALS
         from .utils import bleu_score
-        ds = self.dev_dataset if what == "val" else self.train_dataset
-        groups, order = {}, []
-        for i in range(len(ds)):
-            if isinstance(ds, COCO_data):
-                e = ds.captions[i]
-                key = (e["filepath"], e["filename"])
-            else:
-                key = i
-            if key not in groups:
-                groups[key] = []
-                order.append(key)
-            groups[key].append(i)
-        coco = isinstance(ds, COCO_data)
-        unk = ds.word_to_index.get("<UNK>", 3)
-        # a COCO caption's token ids as __getitem__ forms them, read from the entry (no image load)
-        coco_ids = lambda e: [t if isinstance(t, int) else ds.word_to_index.get(t, unk) for t in e["tokens"]]   # noqa: E731
-        i2w = ds.index_to_word
-        strip = {ds.word_to_index[w] for w in SPECIALS[:3] if w in ds.word_to_index}
-        words = lambda ids: [i2w.get(int(t), str(int(t))) for t in ids if int(t) not in strip]   # noqa: E731
+        ds, groups, order, coco, coco_ids, words = self._eval_groups(what)
         was_training = self.gen.training
         self.gen.eval()
         bs = int(batch_size or getattr(self.args, "adv_eval_batch_size", 32))
@@ -407,6 +392,74 @@ class GANInstructor:
         self.log.info("[EVAL] BLEU-4 (%s, beam %d): %.4f", what, beam_size, score)
         self.writer.add_scalar(f"BLEU4_{what}", score, max(self.adv_epoch, 0))
         return score
+
+    def _eval_groups(self, what):
+        """The evaluation's dataset and its captions grouped by image (``filepath`` + ``filename`` for COCO_data, one image per item
+        otherwise): (ds, groups {key: [item]}, keys in first-seen order, is_coco, a COCO entry's token ids as __getitem__ forms them
+        (no image load), ids -> words with <S>, <E>, <PAD> stripped)."""
+        from .tasks import COCO_data, SPECIALS
+        ds = self.dev_dataset if what == "val" else self.train_dataset
+        groups, order = {}, []
+        for i in range(len(ds)):
+            if isinstance(ds, COCO_data):
+                e = ds.captions[i]
+                key = (e["filepath"], e["filename"])
+            else:
+                key = i
+            if key not in groups:
+                groups[key] = []
+                order.append(key)
+            groups[key].append(i)
+        coco = isinstance(ds, COCO_data)
+        unk = ds.word_to_index.get("<UNK>", 3)
+        coco_ids = lambda e: [t if isinstance(t, int) else ds.word_to_index.get(t, unk) for t in e["tokens"]]   # noqa: E731
+        i2w = ds.index_to_word
+        strip = {ds.word_to_index[w] for w in SPECIALS[:3] if w in ds.word_to_index}
+        words = lambda ids: [i2w.get(int(t), str(int(t))) for t in ids if int(t) not in strip]   # noqa: E731
+        return ds, groups, order, coco, coco_ids, words
+
+    def evaluate_diversity(self, what="val", num_samples=5, top_k=0, top_p=1.0, temperature=1.0, seed=1234, max_caption_len=None,
+                           batch_size=None):
+        """Caption diversity of ``num_samples`` sampled captions per image (Generator.sample_captions), on the images of ``evaluate``
+        (grouped and loaded once each, the generator in eval mode, the same caption length rule): ``bleu4`` = BLEU-4 of each image's
+        first sample against its references, ``mbleu4`` = each sample against the other samples of its image (lower = more diverse),
+        ``distinct1`` / ``distinct2`` = unique / total uni- and bigrams over all samples, ``vocab`` = distinct words used.  Logs the
+        values and writes the scalars ``<Name>_<what>`` (BLEU4S, mBLEU4, Distinct1, Distinct2, Vocab).  ``seed`` fixes the draws."""
+        from .utils import bleu_score, distinct_n, mbleu4
+        ds, groups, order, coco, coco_ids, words = self._eval_groups(what)
+        was_training = self.gen.training
+        self.gen.eval()
+        bs = int(batch_size or getattr(self.args, "adv_eval_batch_size", 32))
+        firsts_c, refs, samples = [], [], []
+        try:
+            for bi, s in enumerate(range(0, len(order), bs)):
+                keys = order[s:s + bs]
+                firsts = [ds[groups[k][0]] for k in keys]          # one image load per image
+                images = torch.stack([it[0] for it in firsts]).to(self.args.device)
+                caps = [[coco_ids(ds.captions[j]) for j in groups[k]] if coco else [it[1]] for k, it in zip(keys, firsts)]
+                L = max_caption_len or max(int(getattr(self.args, "max_seq_len", 0) or 0),
+                                           max(len(c) for group in caps for c in group) + 2)
+                ids, _, lengths = self.gen.sample_captions(images, num_samples=num_samples, top_k=top_k, top_p=top_p,
+                                                           temperature=temperature, max_caption_len=L, seed=int(seed) + bi)
+                ids, lengths = ids.cpu(), lengths.cpu()
+                for b, group in enumerate(caps):
+                    smp = [words(ids[b, j, :int(lengths[b, j])].tolist()) for j in range(ids.shape[1])]
+                    samples.append(smp)
+                    firsts_c.append(smp[0])
+                    refs.append([words(c) for c in group])
+        finally:
+            self.gen.train(was_training)
+        flat = [c for group in samples for c in group]
+        out = {"bleu4": bleu_score(firsts_c, refs), "mbleu4": mbleu4(samples), "distinct1": distinct_n(flat, 1),
+               "distinct2": distinct_n(flat, 2), "vocab": len({w for c in flat for w in c})}
+        self.log.info("[EVAL] diversity (%s, n %d, top-k %d, top-p %.3f, temperature %.3f): BLEU-4 %.4f | mBLEU-4 %.4f | distinct-1 %.4f"
+                      " | distinct-2 %.4f | vocab %d", what, num_samples, top_k, top_p, temperature, out["bleu4"], out["mbleu4"],
+                      out["distinct1"], out["distinct2"], out["vocab"])
+        step = max(self.adv_epoch, 0)
+        for name, key in (("BLEU4S", "bleu4"), ("mBLEU4", "mbleu4"), ("Distinct1", "distinct1"), ("Distinct2", "distinct2"),
+                          ("Vocab", "vocab")):
+            self.writer.add_scalar(f"{name}_{what}", out[key], step)
+        return out
 
 
 class _XentFn(torch.autograd.Function):

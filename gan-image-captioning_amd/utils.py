@@ -120,6 +120,33 @@ def bleu_score(candidate_corpus, references_corpus, max_n=4, weights=(0.25,) * 4
     return bp * math.exp(log_p)
 
 
+def distinct_n(captions, n):
+    """Distinct-n of a corpus: the number of unique n-grams over the total number of n-grams, across all ``captions`` (token
+    lists); 0.0 when no caption has n tokens."""
+    seen, total = set(), 0
+    for c in captions:
+        c = list(c)
+        for i in range(len(c) - n + 1):
+            seen.add(tuple(c[i:i + n]))
+            total += 1
+    return len(seen) / total if total else 0.0
+
+
+def mbleu4(samples_per_image):
+    """mBLEU-4 (self-BLEU within an image): corpus ``bleu_score`` with each sample as the candidate and the other samples of its
+    image as its references.  ``samples_per_image``: one list of token lists per image; images with fewer than 2 samples are
+    skipped (0.0 if none is left).  1.0 when the samples of every image are identical (of 4 tokens or more): lower is more diverse."""
+    cands, refs = [], []
+    for group in samples_per_image:
+        group = [list(c) for c in group]
+        if len(group) < 2:
+            continue
+        for i, c in enumerate(group):
+            cands.append(c)
+            refs.append(group[:i] + group[i + 1:])
+    return bleu_score(cands, refs) if cands else 0.0
+
+
 def create_logger(name, silent=False, to_disk=False, log_file=None):
     """Message-only logger to stdout and/or file(s) (utils.py:78-103)."""
     log = logging.getLogger(name)

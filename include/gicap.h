@@ -352,6 +352,54 @@ int gic_attn_beam_search(const gic_attn_dims* dims, const gic_attn_params* param
                          const gic_decoder_beam_opts* opts, void* ws, const float* features, const void* fmap, int64_t* ids,
                          float* scores, int32_t* lengths, float* alphas, void* stream);
 
+/* Caption sampling: n = num_samples captions per image by temperature / top-k / top-p (nucleus) sampling, for either decoder.
+ * Rows = B * n: row r belongs to image r / n and is sample r % n; every row is live from step 0.  Step 0 is fed `features` with
+ * (h0, c0) or zeros, step t > 0 embed(the row's own previous token); the attention decoder follows the step of gic_attn_sample_fwd
+ * (the attention at step t uses h_{t-1}, the LSTM input is [x_t ; z_t]).  Per step and row, with l = the f32 logits o + b_out (never
+ * rounded to bf16 before the draw) and tau = temperature (the conventional sampling temperature, dividing the logits):
+ *   top-k (top_k = 0: off)   K = {v : l_v >= l_(k)}, l_(k) the k-th largest logit; ties at the boundary are kept.
+ *   top-p (top_p = 1: off)   after top-k, with q = softmax(l / tau) renormalised over K: beta = the largest value such that
+ *                            sum_{v in K, l_v >= beta} q_v >= top_p; kept = {v in K : l_v >= beta} (ties kept).
+ *   draw                     token = argmax over kept v of l_v / tau + g(u_v), g(u) = -log(-log(u + 1e-10) + 1e-10), ties to the lower id:
+ *                            an exact draw from the truncated, tempered distribution.  u = noise_u f32 [L, B*n, V] (the order of
+ *                            gic_decoder_sample_fwd's noise), or Philox keyed by (seed, t, r) when noise_u is NULL: a row's noise does not
+ *                            depend on the batch's other rows.
+ * A row that emits eos_id has finished: afterwards it emits pad_id and its score and length stay fixed.  The decode stops after L steps
+ * or once every row has finished.  Outputs in row order (not sorted): ids int64 [B, n, L]; lengths int32 [B, n] (tokens up to and
+ * including eos_id, L if none); scores f32 [B, n] = the running sum of l_tok - logsumexp(l), the model's untempered, untruncated
+ * log-probability (the units of the beam scores).  No f32 atomics and no split-K: two calls on the same inputs and seed give the same
+ * bits; the deterministic mode accepts every call and gives the same bits inside it as outside it.  Every argument check runs before
+ * any launch: num_samples outside 1..8, top_k < 0 or > V, top_p NaN / <= 0 / > 1, temperature not finite or <= 0, eos_id / pad_id
+ * outside [0, V), L > 1024, rows > 2^24 or a workspace that is not 256-byte aligned return GIC_STATUS_INVALID_ARG. */
+typedef struct gic_sample_opts {
+  int32_t num_samples;                   /* n: 1..8 captions per image (gic_sample_logits ignores it) */
+  int32_t top_k;                         /* 0 = off, else 1..V */
+  float top_p;                           /* (0, 1]; 1 = off */
+  float temperature;                     /* > 0 and finite; divides the logits */
+  int32_t eos_id;                        /* [0, V); <E> = 2 (gic_sample_logits ignores it) */
+  int32_t pad_id;                        /* [0, V); <PAD> = 0 (gic_sample_logits ignores it) */
+  const float* h0;                       /* initial hidden state or NULL = zeros: [NL,B,H] (LSTM decoder), [B,H] (attention decoder) */
+  const float* c0;                       /* initial cell state, as h0 */
+} gic_sample_opts;
+/* One truncated draw per row of f32 logits [rows, ld] (ld >= V; rows 1..2^24, V >= 2): the per-step selection of the decoders above.
+ * noise_u f32 [rows, V] or NULL = Philox keyed by (seed, stream_id, r).  ids int64 [rows]; logp f32 [rows] = l_tok - logsumexp(l) (or
+ * NULL); kept int32 [rows] = the size of the kept set (or NULL). */
+int gic_sample_logits(const float* logits, int64_t ld, int32_t rows, int32_t V, const gic_sample_opts* opts, const float* noise_u,
+                      uint64_t seed, uint64_t stream_id, int64_t* ids, float* logp, int32_t* kept, void* stream);
+/* Bytes of the (256-byte aligned) workspaces of the two sampling decodes for these dims and num_samples.  Host-only: no GPU needed. */
+int gic_decoder_sample_ws_bytes(const gic_decoder_dims* dims, int32_t num_samples, uint64_t* out);
+int gic_attn_sample_ws_bytes(const gic_attn_dims* dims, int32_t num_samples, uint64_t* out);
+/* The LSTM decoder's sampling decode: the fused step kernels where gic_decoder_fused_rollout_rows admits B * n rows, else the generic
+ * products (any V). */
+int gic_decoder_sample_captions(const gic_decoder_dims* dims, const gic_decoder_params* params, const gic_decoder_shadow* shadow,
+                                const gic_sample_opts* opts, void* ws, const float* features, const float* noise_u, uint64_t seed,
+                                int64_t* ids, float* scores, int32_t* lengths, void* stream);
+/* The attention decoder's sampling decode: fmap act [B,P,C] as for gic_attn_sample_fwd (shadow refreshed by gic_attn_prepare); the limits
+ * of gic_attn_sample_fwd apply. */
+int gic_attn_sample_captions(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                             const gic_sample_opts* opts, void* ws, const float* features, const void* fmap, const float* noise_u,
+                             uint64_t seed, int64_t* ids, float* scores, int32_t* lengths, void* stream);
+
 /* Teacher-forced decode with the attention decoder: the semantics of gic_decoder_forward_tf with the step of gic_attn_sample_fwd.
  * dims->L = T = caption length + 1: step 0 is fed `features`, step t > 0 embed(caps[b, t-1]) (caps int64 [B, T-1]; may be NULL when
  * T = 1); the attention of step t uses h_{t-1} and the LSTM input is [x_t ; z_t].  lengths int32 [B] (each 1..T) with
