@@ -15,6 +15,7 @@
 // The generic path's GEMMs never split K, so neither path adds f32 partials atomically.
 #pragma once
 #include <climits>
+#include <type_traits>
 
 #include "../../include/gicap.h"
 #include "common.h"
@@ -94,10 +95,11 @@ __device__ __forceinline__ void beam_tile_reduce8(const float (&x)[8], const int
 // a.part_v / part_i [rows][nblk][K]; a.stop / stop_at; the sampling fields (u, seed, temperature, out, rowkey) are unused
 int vocab_step_beam(const VocabStepArgs& a, int K, int dtype, hipStream_t stream);
 
-// ---- the parts of a search that the LSTM decoder (beam.hip) and the attention decoder (attn_beam.hip) share
+// ---- the kernels of a caption decode (decode.hip drives them: one step loop for both decoders and both heads)
 struct BeamLayerPtrs { void* xh[GIC_MAX_LAYERS]; float* c[GIC_MAX_LAYERS]; };
 
-// the search state in the workspace: score f32, fin / len / tok / par i32 [rows]; htok / hpar i32 [L][rows]; last / done i32 [B]; count i32
+// the search state in the workspace: score f32, fin / len / tok / par i32 [rows]; htok / hpar i32 [L][rows] (hpar: beam only);
+// last / done i32 [B]; count i32
 struct BeamState { float* score; int* fin; int* len; int* tok; int* par; int* htok; int* hpar; int* last; int* done; int* count; };
 
 struct BeamSelectArgs {
@@ -106,17 +108,40 @@ struct BeamSelectArgs {
   int nblk, rows, t, eos, pad;
 };
 
-// slot 0 of every layer into the K rows of each image (layer 0's input row [0, din0): features in [0, E), zeros behind; h part = h0 or 0;
-// c = c0 or 0; h0 / c0 f32 [NL, B, H] or null) and the state at t = 0: only beam 0 live (all_live: every row live, sample.hip), par[r] = r
+// f(std::integral_constant<int, K>()) for the beam width or sample count K = 1..kBeamMax (callers check the range first)
+template <typename F>
+int with_beam_k(int K, F&& f) {
+  switch (K) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 5: return f(std::integral_constant<int, 5>());
+    case 6: return f(std::integral_constant<int, 6>());
+    case 7: return f(std::integral_constant<int, 7>());
+    default: return f(std::integral_constant<int, 8>());
+  }
+}
+
+// beam.hip.  beam_init: slot 0 of every layer into the K rows of each image (layer 0's input row [0, din0): features in [0, E), zeros
+// behind; h part = h0 or 0; c = c0 or 0; h0 / c0 f32 [NL, B, H] or null) and the state at t = 0: only beam 0 live (all_live: every row
+// live, the sampler), par[r] = r
 int beam_init(const BeamLayerPtrs& slot0, int NL, int din0, int E, int H, int B, int K, int dtype, const float* features, const float* h0,
               const float* c0, const BeamState& s, hipStream_t stream, bool all_live = false);
+// the generic path's GEMM input rows of t > 0: [x | h] of every layer from row par[r] of the previous output slot, x of layer 0 =
+// embed[tok[r]]; c likewise
+int beam_gather(const BeamLayerPtrs& in, const BeamLayerPtrs& out, int NL, int E, int H, int rows, int dtype, const float* embed, const int* tok,
+                const int* par, const int* stop, int stop_at, hipStream_t stream);
+// the generic path's tile partials of f32 logits [rows, V] (the fused path's are vocab_step_beam's epilogue)
+int beam_tile_topk(const float* logits, int rows, int V, int K, float* part_m, float* part_s, float* part_v, int* part_i, const int* stop,
+                   int stop_at, hipStream_t stream);
 int beam_select(const BeamSelectArgs& a, int K, int B, hipStream_t stream);
 // ids / scores / lengths of the K beams of each image, best first; anc: null or i32 [B, K, L], the row (image * K + beam) of step t whose
 // logits gave the t-th token of each returned beam (-1 past the last step that ran)
 int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length_penalty, int64_t* ids, float* scores, int32_t* lengths,
                   int32_t* anc, hipStream_t stream);
 
-// ---- the attention kernels of one step of attn_beam.hip, shared with the attention decoder's sampler (sample.hip)
+// attn_beam.hip: the attention kernels of one step (K rows per image, row r reads hp of row par[r]; the sampler's par[r] = r)
 struct AttnBeamArgs {
   const void* fproj;                 // act [B, P, A]
   const void* fmap;                  // act [B, P, C]
@@ -131,5 +156,16 @@ struct AttnBeamArgs {
 };
 // attn_beam_energy then attn_beam_ctx for the K rows of each of the B images (rows = B * K)
 int attn_beam_step(const AttnBeamArgs& f, int K, int B, int dtype, hipStream_t stream);
+// alphas f32 [B, K, L, P] of the returned beams: row anc[b, j, t] of step t of the history ahist [L][rows][P] for t < lengths[b, j], else 0
+int attn_beam_alphas(const float* ahist, const int* anc, const int* lengths, int rows, int L, int P, float* alphas, hipStream_t stream);
+
+// sample.hip: the option checks of gic_sample_logits (decode = false) and the samplers (eos_id / pad_id too)
+int check_sample_opts(const gic_sample_opts* o, int V, bool decode, const char* who);
+// sample_select over f32 logits [rows, V] at step t: draws the next token of every live row into the state (score, len, tok, htok slot t,
+// fin and count on <E>); noise_u f32 [L, rows, V] or null -> Philox(seed, stream t)
+int sample_step(const float* logits, int rows, int V, const gic_sample_opts* o, const float* noise_u, uint64_t seed, int t, const BeamState& st,
+                hipStream_t stream);
+// ids [rows][L] = each row's history up to its length, pad behind; scores / lengths [rows]
+int sample_finalize(const BeamState& st, int rows, int L, int pad, int64_t* ids, float* scores, int32_t* lengths, hipStream_t stream);
 
 }  // namespace gic

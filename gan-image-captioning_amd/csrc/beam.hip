@@ -1,70 +1,11 @@
-// Beam-search caption decode (gicap.h gic_decoder_beam_search); design notes in beam.h.
-//
-// Scratch (one caller-owned workspace, gic_decoder_beam_ws_bytes; every region 256-byte aligned), rows = B * k:
-//   xh[l]     act [2][rows][Din_l + H]   fused path: slots t % 2 / (t + 1) % 2 hold [x_t | h_{t-1}] / h_t (read from parent rows);
-//                                        generic path: slot 0 = the gathered GEMM input, slot 1 = the pointwise output
-//   c[l]      f32 [2][rows][H]           as xh
-//   gpre, logits (generic path only)     f32 [rows][4H], [rows][V]
-//   part_m, part_s f32 [rows][nblk]; part_v f32, part_i i32 [rows][nblk][k]     tile partials (nblk = ceil(V / 64))
-//   score f32, fin / len / tok / par i32 [rows]; hist_tok / hist_par i32 [L][rows]; last / img_done i32 [B]; count i32 [1]
+// Beam-search kernels (beam.h): init, the generic path's gather and tile top-k, the per-image selection, the final sort.  The step loop
+// that drives them, and the workspace they share, is decode.hip's.
 #include "../../include/gicap.h"
 #include "beam.h"
 #include "kernels.h"
 
 namespace gic {
-
-int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_new, void* h_next, long ld_next, void* h_up, long ld_up,
-                       int rows, int H, hipStream_t stream);      // decoder.hip
-
 namespace {
-
-struct BeamDims {
-  int B, L, V, E, H, NL, dt, K, rows, nblk;
-  bool fused;
-  int din(int l) const { return l == 0 ? E : H; }
-  long ldx(int l) const { return (long)din(l) + H; }
-  size_t asz() const { return (size_t)dtype_size(dt); }
-};
-
-struct BeamLayout {
-  size_t xh[GIC_MAX_LAYERS], c[GIC_MAX_LAYERS], gpre, logits, pm, ps, pv, pi, score, fin, len, tok, par, htok, hpar, last, done, count, total;
-};
-
-BeamLayout beam_layout(const BeamDims& d) {
-  BeamLayout o{};
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t p = at; at += (bytes + 255) & ~(size_t)255; return p; };
-  const size_t R = d.rows, pn = (size_t)d.rows * d.nblk;
-  for (int l = 0; l < d.NL; ++l) {
-    o.xh[l] = take(2 * R * d.ldx(l) * d.asz());
-    o.c[l] = take(2 * R * d.H * 4);
-  }
-  o.gpre = d.fused ? 0 : take(R * 4 * d.H * 4);
-  o.logits = d.fused ? 0 : take(R * d.V * 4);
-  o.pm = take(pn * 4); o.ps = take(pn * 4);
-  o.pv = take(pn * d.K * 4); o.pi = take(pn * d.K * 4);
-  o.score = take(R * 4); o.fin = take(R * 4); o.len = take(R * 4); o.tok = take(R * 4); o.par = take(R * 4);
-  o.htok = take((size_t)d.L * R * 4); o.hpar = take((size_t)d.L * R * 4);
-  o.last = take((size_t)d.B * 4); o.done = take((size_t)d.B * 4); o.count = take(4);
-  o.total = at;
-  return o;
-}
-
-int beam_dims(const gic_decoder_dims* dims, int K, BeamDims& d) {
-  GIC_CHECK_ARG(dims, "decoder_beam: null dims");
-  GIC_CHECK_ARG(dims->B > 0 && dims->L > 0 && dims->V > 1 && dims->E > 0 && dims->H > 0, "decoder_beam: bad dims");
-  GIC_CHECK_ARG(dims->NL >= 1 && dims->NL <= GIC_MAX_LAYERS, "decoder_beam: gen_num_layers must be 1..%d", GIC_MAX_LAYERS);
-  GIC_CHECK_ARG(dims->dtype == DT_F32 || dims->dtype == DT_BF16, "decoder_beam: bad dtype");
-  GIC_CHECK_ARG(K >= 1 && K <= kBeamMax, "decoder_beam: beam size must be 1..%d, got %d", kBeamMax, K);
-  GIC_CHECK_ARG(K <= dims->V, "decoder_beam: beam size %d exceeds the vocabulary (%d)", K, dims->V);
-  GIC_CHECK_ARG(dims->L <= 1024, "decoder_beam: at most 1024 steps");
-  GIC_CHECK_ARG((long)dims->B * K <= (1l << 24), "decoder_beam: too many rows");
-  d.B = dims->B; d.L = dims->L; d.V = dims->V; d.E = dims->E; d.H = dims->H; d.NL = dims->NL; d.dt = dims->dtype; d.K = K;
-  d.rows = d.B * K;
-  d.nblk = cdiv(d.V, kBeamTile);
-  d.fused = d.rows <= decoder_step_max_rows() && decoder_step_supported(d.dt, d.V, d.E, d.H, d.NL);
-  return GIC_OK;
-}
 
 using LayerPtrs = BeamLayerPtrs;
 
@@ -266,25 +207,35 @@ __global__ __launch_bounds__(64) void beam_finalize_kernel(const float* __restri
   }
 }
 
-template <int K>
-int select_launch(const SelectArgs& s, int B, hipStream_t stream) {
-  hipLaunchKernelGGL((beam_select_kernel<K>), dim3(B), dim3(512), 0, stream, s);
-  GIC_CHECK_LAUNCH("beam_select");
-  return GIC_OK;
-}
 }  // namespace
 
 int beam_select(const SelectArgs& s, int K, int B, hipStream_t stream) {
-  switch (K) {
-    case 1: return select_launch<1>(s, B, stream);
-    case 2: return select_launch<2>(s, B, stream);
-    case 3: return select_launch<3>(s, B, stream);
-    case 4: return select_launch<4>(s, B, stream);
-    case 5: return select_launch<5>(s, B, stream);
-    case 6: return select_launch<6>(s, B, stream);
-    case 7: return select_launch<7>(s, B, stream);
-    default: return select_launch<8>(s, B, stream);
-  }
+  return with_beam_k(K, [&](auto k) -> int {
+    hipLaunchKernelGGL((beam_select_kernel<k>), dim3(B), dim3(512), 0, stream, s);
+    GIC_CHECK_LAUNCH("beam_select");
+    return GIC_OK;
+  });
+}
+
+int beam_gather(const BeamLayerPtrs& in, const BeamLayerPtrs& out, int NL, int E, int H, int rows, int dtype, const float* embed, const int* tok,
+                const int* par, const int* stop, int stop_at, hipStream_t stream) {
+  if (dtype == DT_F32)
+    hipLaunchKernelGGL((beam_gather_kernel<float>), dim3((unsigned)rows), dim3(256), 0, stream, in, out, NL, E, H, embed, tok, par, stop, stop_at);
+  else
+    hipLaunchKernelGGL((beam_gather_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, stream, in, out, NL, E, H, embed, tok, par, stop, stop_at);
+  GIC_CHECK_LAUNCH("beam_gather");
+  return GIC_OK;
+}
+
+int beam_tile_topk(const float* logits, int rows, int V, int K, float* part_m, float* part_s, float* part_v, int* part_i, const int* stop,
+                   int stop_at, hipStream_t stream) {
+  const int nblk = cdiv(V, kBeamTile);
+  return with_beam_k(K, [&](auto k) -> int {
+    hipLaunchKernelGGL((beam_tile_topk_kernel<k>), dim3((unsigned)nblk, (unsigned)cdiv(rows, 64)), dim3(512), 0, stream, logits, rows, V, nblk,
+                       part_m, part_s, part_v, part_i, stop, stop_at);
+    GIC_CHECK_LAUNCH("beam_tile_topk");
+    return GIC_OK;
+  });
 }
 
 int beam_init(const BeamLayerPtrs& slot0, int NL, int din0, int E, int H, int B, int K, int dtype, const float* features, const float* h0,
@@ -311,133 +262,4 @@ int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length
   return GIC_OK;
 }
 
-namespace {
-
-template <int K>
-int topk_launch(const float* logits, const BeamDims& d, float* pm, float* ps, float* pv, int* pi, const int* count, hipStream_t stream) {
-  hipLaunchKernelGGL((beam_tile_topk_kernel<K>), dim3((unsigned)d.nblk, (unsigned)cdiv(d.rows, 64)), dim3(512), 0, stream, logits, d.rows, d.V,
-                     d.nblk, pm, ps, pv, pi, count, d.B);
-  GIC_CHECK_LAUNCH("beam_tile_topk");
-  return GIC_OK;
-}
-int beam_tile_topk(const float* logits, const BeamDims& d, float* pm, float* ps, float* pv, int* pi, const int* count, hipStream_t stream) {
-  switch (d.K) {
-    case 1: return topk_launch<1>(logits, d, pm, ps, pv, pi, count, stream);
-    case 2: return topk_launch<2>(logits, d, pm, ps, pv, pi, count, stream);
-    case 3: return topk_launch<3>(logits, d, pm, ps, pv, pi, count, stream);
-    case 4: return topk_launch<4>(logits, d, pm, ps, pv, pi, count, stream);
-    case 5: return topk_launch<5>(logits, d, pm, ps, pv, pi, count, stream);
-    case 6: return topk_launch<6>(logits, d, pm, ps, pv, pi, count, stream);
-    case 7: return topk_launch<7>(logits, d, pm, ps, pv, pi, count, stream);
-    default: return topk_launch<8>(logits, d, pm, ps, pv, pi, count, stream);
-  }
-}
-
-template <typename TA>
-int beam_search_t(const BeamDims& d, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_beam_opts* o, unsigned char* ws,
-                  const float* features, int64_t* ids, float* scores, int32_t* lengths, hipStream_t stream) {
-  const BeamLayout lay = beam_layout(d);
-  const int R = d.rows, H = d.H, NL = d.NL;
-  LayerPtrs slot[2];
-  for (int l = 0; l < NL; ++l)
-    for (int s = 0; s < 2; ++s) {
-      slot[s].xh[l] = (TA*)(ws + lay.xh[l]) + (long)s * R * d.ldx(l);
-      slot[s].c[l] = (float*)(ws + lay.c[l]) + (long)s * R * H;
-    }
-  float* pm = (float*)(ws + lay.pm); float* ps = (float*)(ws + lay.ps); float* pv = (float*)(ws + lay.pv); int* pi = (int*)(ws + lay.pi);
-  float* score = (float*)(ws + lay.score);
-  int* fin = (int*)(ws + lay.fin); int* len = (int*)(ws + lay.len); int* tok = (int*)(ws + lay.tok); int* par = (int*)(ws + lay.par);
-  int* htok = (int*)(ws + lay.htok); int* hpar = (int*)(ws + lay.hpar);
-  int* last = (int*)(ws + lay.last); int* done = (int*)(ws + lay.done); int* count = (int*)(ws + lay.count);
-
-  const BeamState st{score, fin, len, tok, par, htok, hpar, last, done, count};
-  GIC_PROPAGATE(beam_init(slot[0], NL, d.E, d.E, H, d.B, d.K, d.dt, features, o->h0, o->c0, st, stream));
-  SelectArgs sa{pm, ps, pv, pi, score, fin, len, tok, par, htok, hpar, last, done, count, d.nblk, R, 0, o->eos_id, o->pad_id};
-  for (int t = 0; t < d.L; ++t) {
-    const int cur = t & 1, nxt = cur ^ 1;
-    if (d.fused) {
-      for (int l = 0; l < NL; ++l) {
-        LstmStepArgs a;
-        a.xh_t = slot[cur].xh[l]; a.xh_next = slot[nxt].xh[l];
-        a.wcat = S->wcat[l]; a.bsum = S->bsum[l];
-        a.c_prev = slot[cur].c[l]; a.c_new = slot[nxt].c[l];
-        if (l + 1 < NL) { a.h_up = slot[cur].xh[l + 1]; a.ld_up = d.ldx(l + 1); }
-        a.B = R; a.H = H; a.din = d.din(l); a.ldx = d.ldx(l);
-        a.stop = count; a.stop_at = d.B;
-        if (t > 0) {
-          a.parent = par;
-          if (l == 0) { a.gather = 1; a.embed = P->embed; a.V = d.V; a.token = tok; }
-        }
-        GIC_PROPAGATE(lstm_step(a, d.dt, stream));
-      }
-      VocabStepArgs v;
-      v.h = (const TA*)slot[nxt].xh[NL - 1] + d.din(NL - 1); v.ldh = d.ldx(NL - 1);
-      v.wout = S->wout; v.bias = P->b_out;
-      v.part_m = pm; v.part_s = ps; v.part_v = pv; v.part_i = pi; v.nblk = d.nblk;
-      v.stop = count; v.stop_at = d.B;
-      v.B = R; v.V = d.V; v.H = H;
-      GIC_PROPAGATE(vocab_step_beam(v, d.K, d.dt, stream));
-    } else {
-      if (t > 0) {
-        hipLaunchKernelGGL((beam_gather_kernel<TA>), dim3((unsigned)R), dim3(256), 0, stream, slot[0], slot[1], NL, d.E, H, P->embed, tok, par,
-                           count, d.B);
-        GIC_CHECK_LAUNCH("beam_gather");
-      }
-      float* gpre = (float*)(ws + lay.gpre);
-      for (int l = 0; l < NL; ++l) {
-        const long ld = d.ldx(l);
-        GemmDesc g;
-        g.A = slot[0].xh[l]; g.lda = ld; g.B = S->wcat[l]; g.ldb = ld; g.C = gpre; g.ldc = 4 * H;
-        g.M = R; g.N = 4 * H; g.K = (int)ld; g.in_dtype = d.dt; g.out_dtype = DT_F32; g.bias = S->bsum[l];
-        g.no_split = 1;                                    // no split-K atomics: a one-ulp reorder could flip a selection
-        GIC_PROPAGATE(gemm(g, stream));
-        GIC_PROPAGATE(lstm_pointwise_fwd(d.dt, gpre, slot[0].c[l], slot[1].c[l], (TA*)slot[1].xh[l] + d.din(l), ld,
-                                         l + 1 < NL ? slot[0].xh[l + 1] : nullptr, l + 1 < NL ? d.ldx(l + 1) : 0, R, H, stream));
-      }
-      float* logits = (float*)(ws + lay.logits);
-      GemmDesc g;
-      g.A = (const TA*)slot[1].xh[NL - 1] + d.din(NL - 1); g.lda = d.ldx(NL - 1);
-      g.B = S->wout; g.ldb = H; g.C = logits; g.ldc = d.V;
-      g.M = R; g.N = d.V; g.K = H; g.in_dtype = d.dt; g.out_dtype = DT_F32; g.bias = P->b_out;
-      g.no_split = 1;
-      GIC_PROPAGATE(gemm(g, stream));
-      GIC_PROPAGATE(beam_tile_topk(logits, d, pm, ps, pv, pi, count, stream));
-    }
-    sa.t = t;
-    GIC_PROPAGATE(beam_select(sa, d.K, d.B, stream));
-  }
-  return beam_finalize(st, d.B, d.K, d.L, o->pad_id, o->length_penalty, ids, scores, lengths, nullptr, stream);
-}
-
-}  // namespace
 }  // namespace gic
-
-using namespace gic;
-
-extern "C" {
-
-int gic_decoder_beam_ws_bytes(const gic_decoder_dims* dims, int32_t beam, uint64_t* out) {
-  BeamDims d;
-  GIC_PROPAGATE(beam_dims(dims, beam, d));
-  GIC_CHECK_ARG(out, "decoder_beam_ws_bytes: null out");
-  *out = (uint64_t)beam_layout(d).total;
-  return GIC_OK;
-}
-
-int gic_decoder_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_beam_opts* o,
-                            void* ws, const float* features, int64_t* ids, float* scores, int32_t* lengths, void* stream) {
-  GIC_CHECK_ARG(o, "decoder_beam_search: null options");
-  BeamDims d;
-  GIC_PROPAGATE(beam_dims(dims, o->beam, d));
-  GIC_CHECK_ARG(P && S && ws && features && ids && scores && lengths, "decoder_beam_search: null argument");
-  GIC_CHECK_ARG(P->embed && P->b_out && S->wout, "decoder_beam_search: null embedding / output layer");
-  for (int l = 0; l < d.NL; ++l) GIC_CHECK_ARG(S->wcat[l] && S->bsum[l], "decoder_beam_search: null layer %d weights", l);
-  GIC_CHECK_ARG(o->eos_id >= 0 && o->eos_id < d.V, "decoder_beam_search: eos_id %d outside [0, %d)", o->eos_id, d.V);
-  GIC_CHECK_ARG(o->pad_id >= 0 && o->pad_id < d.V, "decoder_beam_search: pad_id %d outside [0, %d)", o->pad_id, d.V);
-  GIC_CHECK_ARG(o->length_penalty == o->length_penalty, "decoder_beam_search: length_penalty is NaN");
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "decoder_beam_search: the workspace must be 256-byte aligned");
-  if (d.dt == DT_F32) return beam_search_t<float>(d, P, S, o, (unsigned char*)ws, features, ids, scores, lengths, (hipStream_t)stream);
-  return beam_search_t<bf16_t>(d, P, S, o, (unsigned char*)ws, features, ids, scores, lengths, (hipStream_t)stream);
-}
-
-}  // extern "C"

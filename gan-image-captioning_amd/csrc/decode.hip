@@ -1,0 +1,401 @@
+// Caption decode (gicap.h gic_decoder_beam_search, gic_attn_beam_search, gic_decoder_sample_captions, gic_attn_sample_captions and their
+// *_ws_bytes): one step loop for both decoders and both heads.  Rows = B * K (row r = image r / K, beam or sample r % K).
+//
+// A search is a recurrence and a head, chosen at the entry point:
+//   LstmFused    lstm_step's beam form per layer: h / c read from row parent[r], layer 0's x = embed[token[r]]
+//   LstmGeneric  where the fused kernels decline the shapes: beam_gather, then per layer the library GEMM and lstm_pointwise_fwd
+//   Attn         the fproj GEMM once; per step the hp GEMM, attn_beam_step (attn_beam.hip) and lstm_step's beam form
+// and
+//   BeamHead     vocab_step_beam (generic path: the GEMM into logits + beam_tile_topk), beam_select; beam_finalize (beam.h)
+//   SampleHead   vocab_step_logits (generic path: the GEMM into logits), sample_step; sample_finalize (sample.hip)
+// A sampled row is its own parent: beam_init sets par[r] = r and only beam_select writes it again, so both heads run the same
+// recurrences.  The beam head stops once B images have finished, the sampler once B * K rows have: from then on the kernels of every
+// later step read the count and return at once (the launch count stays fixed; the generic path's GEMMs and pointwise launches still
+// run on stale rows that nothing reads).  No GEMM of a decode splits K, so no f32 partials are added atomically: a one-ulp reorder could
+// flip a selection, and two calls give the same bits.
+//
+// Scratch (one caller-owned workspace; every region 256-byte aligned), in this order, each region only where it is listed:
+//   xh[l]   act [2][rows][din_l + H]   slots t % 2 / (t + 1) % 2 hold [x_t | h_{t-1}] / h_t (attention: x_t = [x | z]); generic path:
+//                                      slot 0 = the gathered GEMM input, slot 1 = the pointwise output
+//   c[l]    f32 [2][rows][H]           as xh
+//   gpre    f32 [rows][4H]             LSTM generic path
+//   fproj act [B][P][A], hp f32 [rows][A], e f32 [rows][P]                 attention
+//   ahist   f32 [L][rows][P]           attention beam: the alpha history
+//   logits  f32 [rows][V]              sampler; beam on the generic path
+//   part_m, part_s f32 [rows][nblk]; part_v f32, part_i i32 [rows][nblk][K]          beam: tile partials (nblk = ceil(V / 64))
+//   score f32, fin / len / tok / par i32 [rows]; hist_tok i32 [L][rows]; hist_par i32 [L][rows] (beam); anc i32 [B][K][L] (attention
+//   beam); last / done i32 [B]; count i32
+#include "../../include/gicap.h"
+#include "beam.h"
+#include "kernels.h"
+
+namespace gic {
+namespace {
+
+struct DecodeDims {
+  int B, L, V, E, H, NL, dt;
+  int C, P, A;                   // the attention decoder's (C = 0: the LSTM decoder)
+  int K, rows, nblk;             // beams or samples per image, rows = B * K, nblk = ceil(V / 64)
+  bool fused;                    // the fused step kernels take the shapes (always with attention)
+  int din(int l) const { return l == 0 ? E + C : H; }
+  long ldx(int l) const { return (long)din(l) + H; }
+  size_t asz() const { return (size_t)dtype_size(dt); }
+  bool attn() const { return C > 0; }
+  void* act(void* p, long n) const { return (char*)p + n * asz(); }      // p + n compute-dtype values
+};
+
+// the limits every decode shares, after the decoder's own shape checks (who: the prefix of the error text)
+int decode_dims(DecodeDims& d, int K, bool beam, const char* who) {
+  if (beam) {
+    GIC_CHECK_ARG(K >= 1 && K <= kBeamMax, "%s: beam size must be 1..%d, got %d", who, kBeamMax, K);
+    GIC_CHECK_ARG(K <= d.V, "%s: beam size %d exceeds the vocabulary (%d)", who, K, d.V);
+  } else {
+    GIC_CHECK_ARG(K >= 1 && K <= kBeamMax, "%s: num_samples must be 1..%d, got %d", who, kBeamMax, K);
+  }
+  GIC_CHECK_ARG(d.L <= 1024, "%s: at most 1024 steps", who);
+  GIC_CHECK_ARG((long)d.B * K <= (1l << 24), "%s: too many rows", who);
+  d.K = K;
+  d.rows = d.B * K;
+  d.nblk = cdiv(d.V, kBeamTile);
+  d.fused = d.attn() || (d.rows <= decoder_step_max_rows() && decoder_step_supported(d.dt, d.V, d.E, d.H, d.NL));
+  return GIC_OK;
+}
+
+int lstm_dims(const gic_decoder_dims* dims, int K, bool beam, const char* who, DecodeDims& d) {
+  GIC_CHECK_ARG(dims, "%s: null dims", who);
+  GIC_CHECK_ARG(dims->B > 0 && dims->L > 0 && dims->V > 1 && dims->E > 0 && dims->H > 0, "%s: bad dims", who);
+  GIC_CHECK_ARG(dims->NL >= 1 && dims->NL <= GIC_MAX_LAYERS, "%s: gen_num_layers must be 1..%d", who, GIC_MAX_LAYERS);
+  GIC_CHECK_ARG(dims->dtype == DT_F32 || dims->dtype == DT_BF16, "%s: bad dtype", who);
+  d = DecodeDims{dims->B, dims->L, dims->V, dims->E, dims->H, dims->NL, dims->dtype};
+  return decode_dims(d, K, beam, who);
+}
+
+int attn_dims(const gic_attn_dims* dims, int K, bool beam, const char* who, DecodeDims& d) {
+  ACtx c;
+  GIC_PROPAGATE(check_attn_dims(dims, c));
+  d = DecodeDims{c.B, c.L, c.V, c.E, c.H, 1, c.dt, c.C, c.P, c.A};
+  return decode_dims(d, K, beam, who);
+}
+
+struct DecodeBufs {
+  BeamLayerPtrs slot[2];
+  float* gpre; void* fproj; float* hp; float* e; float* ahist; float* logits;
+  float* pm; float* ps; float* pv; int* pi;
+  BeamState st;
+  int* anc;
+  size_t total;
+};
+
+// the regions of the header comment in the workspace ws (null: only the total is meaningful)
+DecodeBufs decode_layout(const DecodeDims& d, bool beam, void* ws) {
+  DecodeBufs o{};
+  size_t at = 0;
+  auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)ws + at); at += (bytes + 255) & ~(size_t)255; return p; };
+  const size_t R = d.rows, pn = R * d.nblk, LR = (size_t)d.L * R;
+  for (int l = 0; l < d.NL; ++l) {
+    const size_t xb = R * d.ldx(l) * d.asz();
+    char* xh = (char*)take(2 * xb);
+    float* c = (float*)take(2 * R * d.H * 4);
+    for (int s = 0; s < 2; ++s) { o.slot[s].xh[l] = xh + s * xb; o.slot[s].c[l] = c + s * R * d.H; }
+  }
+  if (!d.fused) o.gpre = (float*)take(R * 4 * d.H * 4);
+  if (d.attn()) {
+    o.fproj = take((size_t)d.B * d.P * d.A * d.asz());
+    o.hp = (float*)take(R * d.A * 4);
+    o.e = (float*)take(R * d.P * 4);
+    if (beam) o.ahist = (float*)take(LR * d.P * 4);
+  }
+  if (!beam || !d.fused) o.logits = (float*)take(R * d.V * 4);
+  if (beam) {
+    o.pm = (float*)take(pn * 4); o.ps = (float*)take(pn * 4);
+    o.pv = (float*)take(pn * d.K * 4); o.pi = (int*)take(pn * d.K * 4);
+  }
+  BeamState& s = o.st;
+  s.score = (float*)take(R * 4);
+  s.fin = (int*)take(R * 4); s.len = (int*)take(R * 4); s.tok = (int*)take(R * 4); s.par = (int*)take(R * 4);
+  s.htok = (int*)take(LR * 4);
+  if (beam) s.hpar = (int*)take(LR * 4);
+  if (beam && d.attn()) o.anc = (int*)take(LR * 4);
+  s.last = (int*)take((size_t)d.B * 4); s.done = (int*)take((size_t)d.B * 4); s.count = (int*)take(4);
+  o.total = at;
+  return o;
+}
+
+// what every part of one search reads
+struct Search {
+  const DecodeDims& d;
+  const DecodeBufs& w;
+  int stop_at;                   // the finished count (w.st.count) that ends the search
+  hipStream_t stream;
+};
+
+// lstm_step's beam form for layer l of step t, slot t % 2 -> (t + 1) % 2: from t = 1 on, h / c come from row parent[r] and layer 0's x
+// part [0, gw) (gw = 0: all of it) is embed[token[r]]
+int lstm_beam_step(const Search& s, int t, int l, const void* wcat, const float* bsum, const float* embed, int gw) {
+  const DecodeDims& d = s.d;
+  const BeamLayerPtrs &cur = s.w.slot[t & 1], &nxt = s.w.slot[(t & 1) ^ 1];
+  LstmStepArgs a;
+  a.xh_t = cur.xh[l]; a.xh_next = nxt.xh[l];
+  a.wcat = wcat; a.bsum = bsum;
+  a.c_prev = cur.c[l]; a.c_new = nxt.c[l];
+  if (l + 1 < d.NL) { a.h_up = cur.xh[l + 1]; a.ld_up = d.ldx(l + 1); }
+  a.B = d.rows; a.H = d.H; a.din = d.din(l); a.ldx = d.ldx(l); a.gw = gw;
+  a.stop = s.w.st.count; a.stop_at = s.stop_at;
+  if (t > 0) {
+    a.parent = s.w.st.par;
+    if (l == 0) { a.gather = 1; a.embed = embed; a.V = d.V; a.token = s.w.st.tok; }
+  }
+  return lstm_step(a, d.dt, s.stream);
+}
+
+// ---- recurrences: begin() once after beam_init, step(t) leaves the top layer's h_t in slot (t + 1) % 2 (kFused) or slot 1
+struct LstmFused {
+  static constexpr bool kFused = true;
+  const gic_decoder_params* P; const gic_decoder_shadow* S;
+  int begin(const Search&) const { return GIC_OK; }
+  int step(const Search& s, int t) const {
+    for (int l = 0; l < s.d.NL; ++l) GIC_PROPAGATE(lstm_beam_step(s, t, l, S->wcat[l], S->bsum[l], P->embed, 0));
+    return GIC_OK;
+  }
+};
+
+struct LstmGeneric {
+  static constexpr bool kFused = false;
+  const gic_decoder_params* P; const gic_decoder_shadow* S;
+  int begin(const Search&) const { return GIC_OK; }
+  int step(const Search& s, int t) const {
+    const DecodeDims& d = s.d;
+    const BeamLayerPtrs &in = s.w.slot[0], &out = s.w.slot[1];
+    if (t > 0) GIC_PROPAGATE(beam_gather(in, out, d.NL, d.E, d.H, d.rows, d.dt, P->embed, s.w.st.tok, s.w.st.par, s.w.st.count, s.stop_at, s.stream));
+    for (int l = 0; l < d.NL; ++l) {
+      const long ld = d.ldx(l);
+      GemmDesc g;
+      g.A = in.xh[l]; g.lda = ld; g.B = S->wcat[l]; g.ldb = ld; g.C = s.w.gpre; g.ldc = 4 * d.H;
+      g.M = d.rows; g.N = 4 * d.H; g.K = (int)ld; g.in_dtype = d.dt; g.out_dtype = DT_F32; g.bias = S->bsum[l];
+      g.no_split = 1;
+      GIC_PROPAGATE(gemm(g, s.stream));
+      GIC_PROPAGATE(lstm_pointwise_fwd(d.dt, s.w.gpre, in.c[l], out.c[l], d.act(out.xh[l], d.din(l)), ld, l + 1 < d.NL ? in.xh[l + 1] : nullptr,
+                                       l + 1 < d.NL ? d.ldx(l + 1) : 0, d.rows, d.H, s.stream));
+    }
+    return GIC_OK;
+  }
+};
+
+struct Attn {
+  static constexpr bool kFused = true;
+  const gic_attn_params* P; const gic_attn_shadow* S;
+  const void* fmap;
+  bool history;                  // each step's alpha rows into ahist (for the alphas of the returned beams)
+  int begin(const Search& s) const {        // fp = fmap W_f^T + b_f, once per image
+    const DecodeDims& d = s.d;
+    GemmDesc g;
+    g.A = fmap; g.lda = d.C; g.B = S->wf; g.ldb = d.C; g.C = s.w.fproj; g.ldc = d.A;
+    g.M = d.B * d.P; g.N = d.A; g.K = d.C; g.in_dtype = d.dt; g.out_dtype = d.dt; g.bias = P->b_f;
+    g.no_split = 1;
+    return gemm(g, s.stream);
+  }
+  int step(const Search& s, int t) const {
+    const DecodeDims& d = s.d;
+    void* xh_t = s.w.slot[t & 1].xh[0];
+    GemmDesc g;                  // hp [rows, A] = h_{t-1} W_h^T, the rows as the previous step left them (the attention kernels read row parent[r])
+    g.A = d.act(xh_t, d.din(0)); g.lda = d.ldx(0); g.B = S->wh; g.ldb = d.H; g.C = s.w.hp; g.ldc = d.A;
+    g.M = d.rows; g.N = d.A; g.K = d.H; g.in_dtype = d.dt; g.out_dtype = DT_F32;
+    g.no_split = 1;
+    GIC_PROPAGATE(gemm(g, s.stream));
+    AttnBeamArgs f;
+    f.fproj = s.w.fproj; f.fmap = fmap; f.w_a = P->w_a; f.hp = s.w.hp; f.par = s.w.st.par; f.e = s.w.e;
+    f.z = d.act(xh_t, d.E); f.ldx = d.ldx(0); f.alpha = history ? s.w.ahist + (long)t * d.rows * d.P : nullptr;
+    f.stop = s.w.st.count; f.stop_at = s.stop_at;
+    f.P = d.P; f.A = d.A; f.C = d.C;
+    GIC_PROPAGATE(attn_beam_step(f, d.K, d.B, d.dt, s.stream));
+    return lstm_beam_step(s, t, 0, S->wcat, S->bsum, P->embed, d.E);
+  }
+};
+
+// ---- heads: vocab() finishes the fused vocabulary product's arguments and runs it, logits() follows the generic path's GEMM into
+// w.logits, select(t) picks the step's tokens, finish() writes the outputs
+struct BeamHead {
+  static constexpr bool kBeam = true;
+  const gic_decoder_beam_opts* o;
+  int64_t* ids; float* scores; int32_t* lengths;
+  float* alphas;                 // attention: f32 [B, K, L, P] or null
+  int vocab(VocabStepArgs& v, const Search& s) const {
+    v.part_m = s.w.pm; v.part_s = s.w.ps; v.part_v = s.w.pv; v.part_i = s.w.pi; v.nblk = s.d.nblk;
+    return vocab_step_beam(v, s.d.K, s.d.dt, s.stream);
+  }
+  int logits(const Search& s) const {
+    return beam_tile_topk(s.w.logits, s.d.rows, s.d.V, s.d.K, s.w.pm, s.w.ps, s.w.pv, s.w.pi, s.w.st.count, s.stop_at, s.stream);
+  }
+  int select(const Search& s, int t) const {
+    const BeamState& st = s.w.st;
+    const BeamSelectArgs a{s.w.pm, s.w.ps, s.w.pv, s.w.pi, st.score, st.fin, st.len, st.tok, st.par, st.htok, st.hpar, st.last, st.done,
+                           st.count, s.d.nblk, s.d.rows, t, o->eos_id, o->pad_id};
+    return beam_select(a, s.d.K, s.d.B, s.stream);
+  }
+  int finish(const Search& s) const {
+    const DecodeDims& d = s.d;
+    GIC_PROPAGATE(beam_finalize(s.w.st, d.B, d.K, d.L, o->pad_id, o->length_penalty, ids, scores, lengths, alphas ? s.w.anc : nullptr, s.stream));
+    return alphas ? attn_beam_alphas(s.w.ahist, s.w.anc, lengths, d.rows, d.L, d.P, alphas, s.stream) : GIC_OK;
+  }
+};
+
+struct SampleHead {
+  static constexpr bool kBeam = false;
+  const gic_sample_opts* o;
+  const float* noise_u; uint64_t seed;
+  int64_t* ids; float* scores; int32_t* lengths;
+  int vocab(VocabStepArgs& v, const Search& s) const {
+    v.logits = s.w.logits; v.ld_logits = s.d.V;
+    return vocab_step_logits(v, s.d.dt, s.stream);
+  }
+  int logits(const Search&) const { return GIC_OK; }
+  int select(const Search& s, int t) const { return sample_step(s.w.logits, s.d.rows, s.d.V, o, noise_u, seed, t, s.w.st, s.stream); }
+  int finish(const Search& s) const { return sample_finalize(s.w.st, s.d.rows, s.d.L, o->pad_id, ids, scores, lengths, s.stream); }
+};
+
+// one search: beam_init and the recurrence's begin(), then per step the recurrence, the vocabulary product and the head's selection
+template <typename Rec, typename Head>
+int decode(const DecodeDims& d, const Rec& rec, const Head& head, void* ws, const float* features, const float* h0, const float* c0,
+           void* stream) {
+  const DecodeBufs w = decode_layout(d, Head::kBeam, ws);
+  const Search s{d, w, Head::kBeam ? d.B : d.rows, (hipStream_t)stream};
+  GIC_PROPAGATE(beam_init(w.slot[0], d.NL, d.din(0), d.E, d.H, d.B, d.K, d.dt, features, h0, c0, w.st, s.stream, !Head::kBeam));
+  GIC_PROPAGATE(rec.begin(s));
+  const int top = d.NL - 1;
+  for (int t = 0; t < d.L; ++t) {
+    GIC_PROPAGATE(rec.step(s, t));
+    const void* h = d.act(w.slot[Rec::kFused ? (t & 1) ^ 1 : 1].xh[top], d.din(top));
+    if constexpr (Rec::kFused) {
+      VocabStepArgs v;
+      v.h = h; v.ldh = d.ldx(top);
+      v.wout = rec.S->wout; v.bias = rec.P->b_out;
+      v.stop = w.st.count; v.stop_at = s.stop_at;
+      v.B = d.rows; v.V = d.V; v.H = d.H;
+      GIC_PROPAGATE(head.vocab(v, s));
+    } else {
+      GemmDesc g;
+      g.A = h; g.lda = d.ldx(top); g.B = rec.S->wout; g.ldb = d.H; g.C = w.logits; g.ldc = d.V;
+      g.M = d.rows; g.N = d.V; g.K = d.H; g.in_dtype = d.dt; g.out_dtype = DT_F32; g.bias = rec.P->b_out;
+      g.no_split = 1;
+      GIC_PROPAGATE(gemm(g, s.stream));
+      GIC_PROPAGATE(head.logits(s));
+    }
+    GIC_PROPAGATE(head.select(s, t));
+  }
+  return head.finish(s);
+}
+
+template <typename Head>
+int lstm_decode(const DecodeDims& d, const gic_decoder_params* P, const gic_decoder_shadow* S, const Head& head, void* ws, const float* features,
+                const float* h0, const float* c0, void* stream) {
+  if (d.fused) return decode(d, LstmFused{P, S}, head, ws, features, h0, c0, stream);
+  return decode(d, LstmGeneric{P, S}, head, ws, features, h0, c0, stream);
+}
+
+// ---- the entry points' argument checks beyond the shapes (bufs: the caller's buffer pointers are all set)
+int check_lstm_args(const gic_decoder_params* P, const gic_decoder_shadow* S, int NL, bool bufs, const char* who) {
+  GIC_CHECK_ARG(P && S && bufs, "%s: null argument", who);
+  GIC_CHECK_ARG(P->embed && P->b_out && S->wout, "%s: null embedding / output layer", who);
+  for (int l = 0; l < NL; ++l) GIC_CHECK_ARG(S->wcat[l] && S->bsum[l], "%s: null layer %d weights", who, l);
+  return GIC_OK;
+}
+
+int check_attn_args(const gic_attn_params* P, const gic_attn_shadow* S, bool bufs, const char* who) {
+  GIC_CHECK_ARG(P && S && bufs, "%s: null argument", who);
+  GIC_CHECK_ARG(P->embed && P->b_out && P->b_f && P->w_a && S->wcat && S->bsum && S->wout && S->wf && S->wh, "%s: null weights", who);
+  return GIC_OK;
+}
+
+int check_beam_opts(const gic_decoder_beam_opts* o, int V, const char* who) {
+  GIC_CHECK_ARG(o->eos_id >= 0 && o->eos_id < V, "%s: eos_id %d outside [0, %d)", who, o->eos_id, V);
+  GIC_CHECK_ARG(o->pad_id >= 0 && o->pad_id < V, "%s: pad_id %d outside [0, %d)", who, o->pad_id, V);
+  GIC_CHECK_ARG(o->length_penalty == o->length_penalty, "%s: length_penalty is NaN", who);
+  return GIC_OK;
+}
+
+}  // namespace
+}  // namespace gic
+
+using namespace gic;
+
+extern "C" {
+
+int gic_decoder_beam_ws_bytes(const gic_decoder_dims* dims, int32_t beam, uint64_t* out) {
+  DecodeDims d;
+  GIC_PROPAGATE(lstm_dims(dims, beam, true, "decoder_beam", d));
+  GIC_CHECK_ARG(out, "decoder_beam_ws_bytes: null out");
+  *out = (uint64_t)decode_layout(d, true, nullptr).total;
+  return GIC_OK;
+}
+
+int gic_decoder_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_beam_opts* o,
+                            void* ws, const float* features, int64_t* ids, float* scores, int32_t* lengths, void* stream) {
+  GIC_CHECK_ARG(o, "decoder_beam_search: null options");
+  DecodeDims d;
+  GIC_PROPAGATE(lstm_dims(dims, o->beam, true, "decoder_beam", d));
+  GIC_PROPAGATE(check_lstm_args(P, S, d.NL, ws && features && ids && scores && lengths, "decoder_beam_search"));
+  GIC_PROPAGATE(check_beam_opts(o, d.V, "decoder_beam_search"));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "decoder_beam_search: the workspace must be 256-byte aligned");
+  return lstm_decode(d, P, S, BeamHead{o, ids, scores, lengths, nullptr}, ws, features, o->h0, o->c0, stream);
+}
+
+int gic_attn_beam_ws_bytes(const gic_attn_dims* dims, int32_t beam, uint64_t* out) {
+  DecodeDims d;
+  GIC_PROPAGATE(attn_dims(dims, beam, true, "attn_beam", d));
+  GIC_CHECK_ARG(out, "attn_beam_ws_bytes: null out");
+  *out = (uint64_t)decode_layout(d, true, nullptr).total;
+  return GIC_OK;
+}
+
+int gic_attn_beam_search(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_decoder_beam_opts* o, void* ws,
+                         const float* features, const void* fmap, int64_t* ids, float* scores, int32_t* lengths, float* alphas, void* stream) {
+  GIC_CHECK_ARG(o, "attn_beam_search: null options");
+  DecodeDims d;
+  GIC_PROPAGATE(attn_dims(dims, o->beam, true, "attn_beam", d));
+  GIC_PROPAGATE(check_attn_args(P, S, ws && features && fmap && ids && scores && lengths, "attn_beam_search"));
+  GIC_PROPAGATE(check_beam_opts(o, d.V, "attn_beam_search"));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "attn_beam_search: the workspace must be 256-byte aligned");
+  return decode(d, Attn{P, S, fmap, alphas != nullptr}, BeamHead{o, ids, scores, lengths, alphas}, ws, features, o->h0, o->c0, stream);
+}
+
+int gic_decoder_sample_ws_bytes(const gic_decoder_dims* dims, int32_t num_samples, uint64_t* out) {
+  DecodeDims d;
+  GIC_PROPAGATE(lstm_dims(dims, num_samples, false, "decoder_sample", d));
+  GIC_CHECK_ARG(out, "decoder_sample_ws_bytes: null out");
+  *out = (uint64_t)decode_layout(d, false, nullptr).total;
+  return GIC_OK;
+}
+
+int gic_decoder_sample_captions(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_sample_opts* o,
+                                void* ws, const float* features, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
+                                int32_t* lengths, void* stream) {
+  GIC_CHECK_ARG(o, "decoder_sample_captions: null options");
+  DecodeDims d;
+  GIC_PROPAGATE(lstm_dims(dims, o->num_samples, false, "decoder_sample", d));
+  GIC_PROPAGATE(check_sample_opts(o, d.V, true, "decoder_sample_captions"));
+  GIC_PROPAGATE(check_lstm_args(P, S, d.NL, ws && features && ids && scores && lengths, "decoder_sample_captions"));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "decoder_sample_captions: the workspace must be 256-byte aligned");
+  return lstm_decode(d, P, S, SampleHead{o, noise_u, seed, ids, scores, lengths}, ws, features, o->h0, o->c0, stream);
+}
+
+int gic_attn_sample_ws_bytes(const gic_attn_dims* dims, int32_t num_samples, uint64_t* out) {
+  DecodeDims d;
+  GIC_PROPAGATE(attn_dims(dims, num_samples, false, "attn_sample", d));
+  GIC_CHECK_ARG(out, "attn_sample_ws_bytes: null out");
+  *out = (uint64_t)decode_layout(d, false, nullptr).total;
+  return GIC_OK;
+}
+
+int gic_attn_sample_captions(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_sample_opts* o, void* ws,
+                             const float* features, const void* fmap, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
+                             int32_t* lengths, void* stream) {
+  GIC_CHECK_ARG(o, "attn_sample_captions: null options");
+  DecodeDims d;
+  GIC_PROPAGATE(attn_dims(dims, o->num_samples, false, "attn_sample", d));
+  GIC_PROPAGATE(check_sample_opts(o, d.V, true, "attn_sample_captions"));
+  GIC_PROPAGATE(check_attn_args(P, S, ws && features && fmap && ids && scores && lengths, "attn_sample_captions"));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "attn_sample_captions: the workspace must be 256-byte aligned");
+  return decode(d, Attn{P, S, fmap, false}, SampleHead{o, noise_u, seed, ids, scores, lengths}, ws, features, o->h0, o->c0, stream);
+}
+
+}  // extern "C"

@@ -716,7 +716,6 @@ int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, co
   return colsum(dlog, dt, V, BL, V, d_bout, nullptr, 0, stream);
 }
 
-// the roll-out's LSTM pointwise step for the beam search's generic path (beam.hip): c_prev / c_new [rows, H], h into h_next (and h_up)
 int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_new, void* h_next, long ld_next, void* h_up, long ld_up,
                        int rows, int H, hipStream_t stream) {
   const dim3 grid((unsigned)cdiv((long)rows * H, 256));

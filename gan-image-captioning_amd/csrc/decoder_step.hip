@@ -937,16 +937,7 @@ int vocab_step_beam(const VocabStepArgs& a0, int K, int dtype, hipStream_t strea
   if (lds < tile) lds = tile;
   const int KC = vocab_chunk(dtype, a.H);
   const dim3 grid((unsigned)a.nblk, (unsigned)cdiv(a.B, kStepRows));
-  switch (K) {
-    case 1: return vocab_beam_launch<1>(a, dtype, lds, KC, grid, stream);
-    case 2: return vocab_beam_launch<2>(a, dtype, lds, KC, grid, stream);
-    case 3: return vocab_beam_launch<3>(a, dtype, lds, KC, grid, stream);
-    case 4: return vocab_beam_launch<4>(a, dtype, lds, KC, grid, stream);
-    case 5: return vocab_beam_launch<5>(a, dtype, lds, KC, grid, stream);
-    case 6: return vocab_beam_launch<6>(a, dtype, lds, KC, grid, stream);
-    case 7: return vocab_beam_launch<7>(a, dtype, lds, KC, grid, stream);
-    default: return vocab_beam_launch<8>(a, dtype, lds, KC, grid, stream);
-  }
+  return with_beam_k(K, [&](auto k) { return vocab_beam_launch<k>(a, dtype, lds, KC, grid, stream); });
 }
 
 int sample_finish(const SampleFinishArgs& a, int dtype, hipStream_t stream) {

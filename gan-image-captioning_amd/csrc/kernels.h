@@ -22,6 +22,10 @@ int transpose2d(const void* src, void* dst, int dtype, long rows, long cols, hip
 // decoder.hip internals shared with attention.hip
 int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, const void* d_out, float temperature, const float* t_dev, int pretrain,
                        void* dlogits_ws, const void* wout, const void* hout, float* dhout, float* d_wout, float* d_bout, hipStream_t stream);
+// the roll-out's LSTM pointwise step (decoder.hip) for the caption decode's generic LSTM path (decode.hip): gate pre-activations
+// gpre f32 [rows, 4H], c_prev / c_new [rows, H], h into h_next (and h_up when not null)
+int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_new, void* h_next, long ld_next, void* h_up, long ld_up,
+                       int rows, int H, hipStream_t stream);
 // determinism.hip: the process-wide deterministic mode (gic_set_deterministic) and its ordered embedding scatter:
 // dst[id(r) * d_id + e * d_e] += sum over tokens r of src[(r + row_off) * ld + e] (ascending r), id(r) = ids[(r % B) * s_b + (r / B) * s_t]
 int det_mode();

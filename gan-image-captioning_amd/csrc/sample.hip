@@ -11,19 +11,9 @@
 // Every block reduction is a wave butterfly then the 8 wave values added in wave order: no LDS or global f32 atomics, so the
 // boundaries do not depend on the order in which waves arrive, and two calls give the same bits.
 //
-// The decoders (one step = the recurrence, the vocabulary product into f32 logits, sample_select):
-//   LSTM       lstm_step's beam form with parent = own row and token = the sampled token, vocab_step_logits (decoder_step.hip);
-//              where the fused kernels decline the shapes, sample_gather + the no-split library GEMMs + LSTM pointwise (beam.hip's
-//              generic path with beam width 1)
-//   attention  attn_beam.hip's step with K = n and parent = own row: hp GEMM, attn_beam_energy / attn_beam_ctx (an image's fproj / fmap
-//              read once for its n rows), lstm_step's beam form, vocab_step_logits
-// Once every row has finished, the kernels of each later step read the finished count and return at once (the launch count stays
-// fixed; on the generic path the library GEMMs still run on stale rows that nothing reads).
-//
-// Scratch (one caller-owned workspace, gic_*_sample_ws_bytes; every region 256-byte aligned), rows = B * n:
-//   LSTM: xh[l] act [2][rows][Din_l + H], c[l] f32 [2][rows][H] (beam.hip's slots), gpre f32 [rows][4H] (generic path only)
-//   attention: xh act [2][rows][E + C + H], c f32 [2][rows][H], fproj act [B][P][A], hp f32 [rows][A], e f32 [rows][P]
-//   both: logits f32 [rows][V]; score f32, fin / len / tok / par i32 [rows]; hist_tok i32 [L][rows]; last / done i32 [B]; count i32
+// The samplers (gic_decoder_sample_captions, gic_attn_sample_captions) are decode.hip's step loop with this head: the vocabulary product
+// into f32 logits (vocab_step_logits, or the library GEMM on the LSTM generic path), then sample_step; sample_finalize after the last
+// step.  Every row is live from step 0 and is its own parent.
 #include <climits>
 
 #include "../../include/gicap.h"
@@ -31,13 +21,8 @@
 #include "kernels.h"
 
 namespace gic {
-
-int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_new, void* h_next, long ld_next, void* h_up, long ld_up,
-                       int rows, int H, hipStream_t stream);      // decoder.hip
-
 namespace {
 
-constexpr int kSampleMax = 8;
 constexpr int kSelThreads = 512;
 constexpr int kSelWaves = kSelThreads / 64;
 constexpr int kSelQuads = 8;                     // quads of logits per thread held in registers: 512 * 8 * 4 = 16384 entries
@@ -281,6 +266,8 @@ __global__ __launch_bounds__(256) void sample_finalize_kernel(const float* __res
   if (t == 0) { scores[r] = score[r]; lengths[r] = n; }
 }
 
+}  // namespace
+
 int sample_finalize(const BeamState& st, int rows, int L, int pad, int64_t* ids, float* scores, int32_t* lengths, hipStream_t stream) {
   hipLaunchKernelGGL(sample_finalize_kernel, dim3((unsigned)cdiv((long)rows * L, 256)), dim3(256), 0, stream, st.score, st.len, st.htok, rows, L,
                      pad, ids, scores, lengths);
@@ -288,31 +275,8 @@ int sample_finalize(const BeamState& st, int rows, int L, int pad, int64_t* ids,
   return GIC_OK;
 }
 
-// generic path, t > 0: the GEMM input rows [x | h] of every layer from the previous step's output of the same row, layer 0's x part =
-// embed[token]; the cell state likewise (beam.hip's beam_gather with parent = own row)
-template <typename TA>
-__global__ __launch_bounds__(256) void sample_gather_kernel(BeamLayerPtrs in, BeamLayerPtrs out, int NL, int E, int H, const float* __restrict__ embed,
-                                                            const int* __restrict__ tok, const int* stop, int stop_at) {
-  if (*stop >= stop_at) return;
-  const int r = blockIdx.x, tid = threadIdx.x, id = tok[r];
-  for (int l = 0; l < NL; ++l) {
-    const int din = l == 0 ? E : H;
-    const long ld = din + H;
-    TA* dst = (TA*)in.xh[l] + (long)r * ld;
-    const TA* src = (const TA*)out.xh[l] + (long)r * ld;
-    if (l == 0)
-      for (int e = tid; e < E; e += 256) dst[e] = from_f32<TA>(embed[(long)id * E + e]);
-    for (int j = tid; j < H; j += 256) {
-      dst[din + j] = src[din + j];
-      in.c[l][(long)r * H + j] = out.c[l][(long)r * H + j];
-    }
-  }
-}
-
-// the option checks shared by the three entry points (V = the vocabulary)
 int check_sample_opts(const gic_sample_opts* o, int V, bool decode, const char* who) {
   GIC_CHECK_ARG(o, "%s: null options", who);
-  if (decode) GIC_CHECK_ARG(o->num_samples >= 1 && o->num_samples <= kSampleMax, "%s: num_samples must be 1..%d, got %d", who, kSampleMax, o->num_samples);
   GIC_CHECK_ARG(o->top_k >= 0 && o->top_k <= V, "%s: top_k must be 0..V (%d), got %d", who, V, o->top_k);
   GIC_CHECK_ARG(o->top_p == o->top_p && o->top_p > 0.f && o->top_p <= 1.f, "%s: top_p must be in (0, 1], got %g", who, (double)o->top_p);
   GIC_CHECK_ARG(std::isfinite(o->temperature) && o->temperature > 0.f, "%s: temperature must be finite and > 0, got %g", who, (double)o->temperature);
@@ -323,232 +287,17 @@ int check_sample_opts(const gic_sample_opts* o, int V, bool decode, const char* 
   return GIC_OK;
 }
 
-SelArgs sel_step(const float* logits, int rows, int V, const gic_sample_opts* o, const float* noise_u, uint64_t seed, int t,
-                 const BeamState& st) {
+int sample_step(const float* logits, int rows, int V, const gic_sample_opts* o, const float* noise_u, uint64_t seed, int t, const BeamState& st,
+                hipStream_t stream) {
   SelArgs s{};
   s.logits = logits; s.ld = V; s.rows = rows; s.V = V; s.top_k = o->top_k; s.top_p = o->top_p; s.temperature = o->temperature;
   s.u = noise_u ? noise_u + (long)t * rows * V : nullptr; s.ldu = V;
   s.seed = seed; s.stream = (uint64_t)t;
   s.tok = st.tok; s.fin = st.fin; s.len = st.len; s.score = st.score; s.htok = st.htok + (long)t * rows; s.count = st.count;
   s.eos = o->eos_id; s.t = t;
-  return s;
+  return sample_select(s, stream);
 }
 
-// ---------------------------------------------------------------- the LSTM decoder
-struct SampleDims {
-  int B, L, V, E, H, NL, dt, n, rows;
-  bool fused;
-  int din(int l) const { return l == 0 ? E : H; }
-  long ldx(int l) const { return (long)din(l) + H; }
-  size_t asz() const { return (size_t)dtype_size(dt); }
-};
-
-struct SampleLayout {
-  size_t xh[GIC_MAX_LAYERS], c[GIC_MAX_LAYERS], gpre, logits, score, fin, len, tok, par, htok, last, done, count, total;
-};
-
-SampleLayout sample_layout(const SampleDims& d) {
-  SampleLayout o{};
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t p = at; at += (bytes + 255) & ~(size_t)255; return p; };
-  const size_t R = d.rows;
-  for (int l = 0; l < d.NL; ++l) {
-    o.xh[l] = take(2 * R * d.ldx(l) * d.asz());
-    o.c[l] = take(2 * R * d.H * 4);
-  }
-  o.gpre = d.fused ? 0 : take(R * 4 * d.H * 4);
-  o.logits = take(R * d.V * 4);
-  o.score = take(R * 4); o.fin = take(R * 4); o.len = take(R * 4); o.tok = take(R * 4); o.par = take(R * 4);
-  o.htok = take((size_t)d.L * R * 4);
-  o.last = take((size_t)d.B * 4); o.done = take((size_t)d.B * 4); o.count = take(4);
-  o.total = at;
-  return o;
-}
-
-int sample_dims(const gic_decoder_dims* dims, int n, SampleDims& d) {
-  GIC_CHECK_ARG(dims, "decoder_sample: null dims");
-  GIC_CHECK_ARG(dims->B > 0 && dims->L > 0 && dims->V > 1 && dims->E > 0 && dims->H > 0, "decoder_sample: bad dims");
-  GIC_CHECK_ARG(dims->NL >= 1 && dims->NL <= GIC_MAX_LAYERS, "decoder_sample: gen_num_layers must be 1..%d", GIC_MAX_LAYERS);
-  GIC_CHECK_ARG(dims->dtype == DT_F32 || dims->dtype == DT_BF16, "decoder_sample: bad dtype");
-  GIC_CHECK_ARG(n >= 1 && n <= kSampleMax, "decoder_sample: num_samples must be 1..%d, got %d", kSampleMax, n);
-  GIC_CHECK_ARG(dims->L <= 1024, "decoder_sample: at most 1024 steps");
-  GIC_CHECK_ARG((long)dims->B * n <= (1l << 24), "decoder_sample: too many rows");
-  d.B = dims->B; d.L = dims->L; d.V = dims->V; d.E = dims->E; d.H = dims->H; d.NL = dims->NL; d.dt = dims->dtype; d.n = n;
-  d.rows = d.B * n;
-  d.fused = d.rows <= decoder_step_max_rows() && decoder_step_supported(d.dt, d.V, d.E, d.H, d.NL);
-  return GIC_OK;
-}
-
-template <typename TA>
-int decoder_sample_t(const SampleDims& d, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_sample_opts* o, unsigned char* ws,
-                     const float* features, const float* noise_u, uint64_t seed, int64_t* ids, float* scores, int32_t* lengths, hipStream_t stream) {
-  const SampleLayout lay = sample_layout(d);
-  const int R = d.rows, H = d.H, NL = d.NL;
-  BeamLayerPtrs slot[2];
-  for (int l = 0; l < NL; ++l)
-    for (int s = 0; s < 2; ++s) {
-      slot[s].xh[l] = (TA*)(ws + lay.xh[l]) + (long)s * R * d.ldx(l);
-      slot[s].c[l] = (float*)(ws + lay.c[l]) + (long)s * R * H;
-    }
-  float* logits = (float*)(ws + lay.logits);
-  const BeamState st{(float*)(ws + lay.score), (int*)(ws + lay.fin), (int*)(ws + lay.len), (int*)(ws + lay.tok), (int*)(ws + lay.par),
-                     (int*)(ws + lay.htok), nullptr, (int*)(ws + lay.last), (int*)(ws + lay.done), (int*)(ws + lay.count)};
-  GIC_PROPAGATE(beam_init(slot[0], NL, d.E, d.E, H, d.B, d.n, d.dt, features, o->h0, o->c0, st, stream, true));
-  for (int t = 0; t < d.L; ++t) {
-    const int cur = t & 1, nxt = cur ^ 1;
-    if (d.fused) {
-      for (int l = 0; l < NL; ++l) {
-        LstmStepArgs a;
-        a.xh_t = slot[cur].xh[l]; a.xh_next = slot[nxt].xh[l];
-        a.wcat = S->wcat[l]; a.bsum = S->bsum[l];
-        a.c_prev = slot[cur].c[l]; a.c_new = slot[nxt].c[l];
-        if (l + 1 < NL) { a.h_up = slot[cur].xh[l + 1]; a.ld_up = d.ldx(l + 1); }
-        a.B = R; a.H = H; a.din = d.din(l); a.ldx = d.ldx(l);
-        a.stop = st.count; a.stop_at = R;
-        if (t > 0) {
-          a.parent = st.par;                     // = own row
-          if (l == 0) { a.gather = 1; a.embed = P->embed; a.V = d.V; a.token = st.tok; }
-        }
-        GIC_PROPAGATE(lstm_step(a, d.dt, stream));
-      }
-      VocabStepArgs v;
-      v.h = (const TA*)slot[nxt].xh[NL - 1] + d.din(NL - 1); v.ldh = d.ldx(NL - 1);
-      v.wout = S->wout; v.bias = P->b_out;
-      v.logits = logits; v.ld_logits = d.V;
-      v.stop = st.count; v.stop_at = R;
-      v.B = R; v.V = d.V; v.H = H;
-      GIC_PROPAGATE(vocab_step_logits(v, d.dt, stream));
-    } else {
-      if (t > 0) {
-        hipLaunchKernelGGL((sample_gather_kernel<TA>), dim3((unsigned)R), dim3(256), 0, stream, slot[0], slot[1], NL, d.E, H, P->embed, st.tok,
-                           st.count, R);
-        GIC_CHECK_LAUNCH("sample_gather");
-      }
-      float* gpre = (float*)(ws + lay.gpre);
-      for (int l = 0; l < NL; ++l) {
-        const long ld = d.ldx(l);
-        GemmDesc g;
-        g.A = slot[0].xh[l]; g.lda = ld; g.B = S->wcat[l]; g.ldb = ld; g.C = gpre; g.ldc = 4 * H;
-        g.M = R; g.N = 4 * H; g.K = (int)ld; g.in_dtype = d.dt; g.out_dtype = DT_F32; g.bias = S->bsum[l];
-        g.no_split = 1;                          // no split-K atomics: the same bits on every call
-        GIC_PROPAGATE(gemm(g, stream));
-        GIC_PROPAGATE(lstm_pointwise_fwd(d.dt, gpre, slot[0].c[l], slot[1].c[l], (TA*)slot[1].xh[l] + d.din(l), ld,
-                                         l + 1 < NL ? slot[0].xh[l + 1] : nullptr, l + 1 < NL ? d.ldx(l + 1) : 0, R, H, stream));
-      }
-      GemmDesc g;
-      g.A = (const TA*)slot[1].xh[NL - 1] + d.din(NL - 1); g.lda = d.ldx(NL - 1);
-      g.B = S->wout; g.ldb = H; g.C = logits; g.ldc = d.V;
-      g.M = R; g.N = d.V; g.K = H; g.in_dtype = d.dt; g.out_dtype = DT_F32; g.bias = P->b_out;
-      g.no_split = 1;
-      GIC_PROPAGATE(gemm(g, stream));
-    }
-    GIC_PROPAGATE(sample_select(sel_step(logits, R, d.V, o, noise_u, seed, t, st), stream));
-  }
-  return sample_finalize(st, R, d.L, o->pad_id, ids, scores, lengths, stream);
-}
-
-// ---------------------------------------------------------------- the attention decoder
-struct AttnSampleDims {
-  ACtx c;
-  int n, rows;
-};
-
-struct AttnSampleLayout {
-  size_t xh, c, fproj, hp, e, logits, score, fin, len, tok, par, htok, last, done, count, total;
-};
-
-AttnSampleLayout attn_sample_layout(const AttnSampleDims& d) {
-  AttnSampleLayout o{};
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t p = at; at += (bytes + 255) & ~(size_t)255; return p; };
-  const ACtx& c = d.c;
-  const size_t R = d.rows;
-  o.xh = take(2 * R * c.ldx() * c.asz());
-  o.c = take(2 * R * c.H * 4);
-  o.fproj = take((size_t)c.B * c.P * c.A * c.asz());
-  o.hp = take(R * c.A * 4);
-  o.e = take(R * c.P * 4);
-  o.logits = take(R * c.V * 4);
-  o.score = take(R * 4); o.fin = take(R * 4); o.len = take(R * 4); o.tok = take(R * 4); o.par = take(R * 4);
-  o.htok = take((size_t)c.L * R * 4);
-  o.last = take((size_t)c.B * 4); o.done = take((size_t)c.B * 4); o.count = take(4);
-  o.total = at;
-  return o;
-}
-
-int attn_sample_dims(const gic_attn_dims* dims, int n, AttnSampleDims& d) {
-  GIC_PROPAGATE(check_attn_dims(dims, d.c));
-  GIC_CHECK_ARG(n >= 1 && n <= kSampleMax, "attn_sample: num_samples must be 1..%d, got %d", kSampleMax, n);
-  GIC_CHECK_ARG(d.c.L <= 1024, "attn_sample: at most 1024 steps");
-  GIC_CHECK_ARG((long)d.c.B * n <= (1l << 24), "attn_sample: too many rows");
-  d.n = n;
-  d.rows = d.c.B * n;
-  return GIC_OK;
-}
-
-template <typename TA>
-int attn_sample_t(const AttnSampleDims& d, const gic_attn_params* P, const gic_attn_shadow* S, const gic_sample_opts* o, unsigned char* ws,
-                  const float* features, const void* fmap, const float* noise_u, uint64_t seed, int64_t* ids, float* scores, int32_t* lengths,
-                  hipStream_t stream) {
-  const AttnSampleLayout lay = attn_sample_layout(d);
-  const ACtx& c = d.c;
-  const int R = d.rows, H = c.H, B = c.B;
-  const long ldx = c.ldx();
-  BeamLayerPtrs slot[2] = {};
-  for (int s = 0; s < 2; ++s) {
-    slot[s].xh[0] = (TA*)(ws + lay.xh) + (long)s * R * ldx;
-    slot[s].c[0] = (float*)(ws + lay.c) + (long)s * R * H;
-  }
-  const BeamState st{(float*)(ws + lay.score), (int*)(ws + lay.fin), (int*)(ws + lay.len), (int*)(ws + lay.tok), (int*)(ws + lay.par),
-                     (int*)(ws + lay.htok), nullptr, (int*)(ws + lay.last), (int*)(ws + lay.done), (int*)(ws + lay.count)};
-  void* fproj = ws + lay.fproj;
-  float* hp = (float*)(ws + lay.hp);
-  float* logits = (float*)(ws + lay.logits);
-
-  GIC_PROPAGATE(beam_init(slot[0], 1, c.din(), c.E, H, B, d.n, c.dt, features, o->h0, o->c0, st, stream, true));
-  {  // fp = fmap W_f^T + b_f, once per image
-    GemmDesc g;
-    g.A = fmap; g.lda = c.C; g.B = S->wf; g.ldb = c.C; g.C = fproj; g.ldc = c.A;
-    g.M = B * c.P; g.N = c.A; g.K = c.C; g.in_dtype = c.dt; g.out_dtype = c.dt; g.bias = P->b_f;
-    g.no_split = 1;
-    GIC_PROPAGATE(gemm(g, stream));
-  }
-  for (int t = 0; t < c.L; ++t) {
-    const int cur = t & 1, nxt = cur ^ 1;
-    TA* xh_t = (TA*)slot[cur].xh[0];
-    {  // hp [rows, A] = h_{t-1} W_h^T
-      GemmDesc g;
-      g.A = xh_t + c.din(); g.lda = ldx; g.B = S->wh; g.ldb = H; g.C = hp; g.ldc = c.A;
-      g.M = R; g.N = c.A; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32;
-      g.no_split = 1;
-      GIC_PROPAGATE(gemm(g, stream));
-    }
-    AttnBeamArgs f;
-    f.fproj = fproj; f.fmap = fmap; f.w_a = P->w_a; f.hp = hp; f.par = st.par; f.e = (float*)(ws + lay.e);
-    f.z = xh_t + c.E; f.ldx = ldx; f.alpha = nullptr;
-    f.stop = st.count; f.stop_at = R;
-    f.P = c.P; f.A = c.A; f.C = c.C;
-    GIC_PROPAGATE(attn_beam_step(f, d.n, B, c.dt, stream));
-    LstmStepArgs a;
-    a.xh_t = xh_t; a.xh_next = slot[nxt].xh[0]; a.wcat = S->wcat; a.bsum = S->bsum;
-    a.c_prev = slot[cur].c[0]; a.c_new = slot[nxt].c[0];
-    a.B = R; a.H = H; a.din = c.din(); a.ldx = ldx; a.gw = c.E;
-    a.stop = st.count; a.stop_at = R;
-    if (t > 0) { a.parent = st.par; a.gather = 1; a.embed = P->embed; a.V = c.V; a.token = st.tok; }
-    GIC_PROPAGATE(lstm_step(a, c.dt, stream));
-    VocabStepArgs v;
-    v.h = (const TA*)slot[nxt].xh[0] + c.din(); v.ldh = ldx;
-    v.wout = S->wout; v.bias = P->b_out;
-    v.logits = logits; v.ld_logits = c.V;
-    v.stop = st.count; v.stop_at = R;
-    v.B = R; v.V = c.V; v.H = H;
-    GIC_PROPAGATE(vocab_step_logits(v, c.dt, stream));
-    GIC_PROPAGATE(sample_select(sel_step(logits, R, c.V, o, noise_u, seed, t, st), stream));
-  }
-  return sample_finalize(st, R, c.L, o->pad_id, ids, scores, lengths, stream);
-}
-
-}  // namespace
 }  // namespace gic
 
 using namespace gic;
@@ -565,53 +314,6 @@ int gic_sample_logits(const float* logits, int64_t ld, int32_t rows, int32_t V, 
   s.u = noise_u; s.ldu = V; s.seed = seed; s.stream = stream_id;
   s.ids = ids; s.logp = logp; s.kept = kept;
   return sample_select(s, (hipStream_t)stream);
-}
-
-int gic_decoder_sample_ws_bytes(const gic_decoder_dims* dims, int32_t num_samples, uint64_t* out) {
-  SampleDims d;
-  GIC_PROPAGATE(sample_dims(dims, num_samples, d));
-  GIC_CHECK_ARG(out, "decoder_sample_ws_bytes: null out");
-  *out = (uint64_t)sample_layout(d).total;
-  return GIC_OK;
-}
-
-int gic_decoder_sample_captions(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_sample_opts* o,
-                                void* ws, const float* features, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
-                                int32_t* lengths, void* stream) {
-  GIC_CHECK_ARG(o, "decoder_sample_captions: null options");
-  SampleDims d;
-  GIC_PROPAGATE(sample_dims(dims, o->num_samples, d));
-  GIC_PROPAGATE(check_sample_opts(o, d.V, true, "decoder_sample_captions"));
-  GIC_CHECK_ARG(P && S && ws && features && ids && scores && lengths, "decoder_sample_captions: null argument");
-  GIC_CHECK_ARG(P->embed && P->b_out && S->wout, "decoder_sample_captions: null embedding / output layer");
-  for (int l = 0; l < d.NL; ++l) GIC_CHECK_ARG(S->wcat[l] && S->bsum[l], "decoder_sample_captions: null layer %d weights", l);
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "decoder_sample_captions: the workspace must be 256-byte aligned");
-  if (d.dt == DT_F32)
-    return decoder_sample_t<float>(d, P, S, o, (unsigned char*)ws, features, noise_u, seed, ids, scores, lengths, (hipStream_t)stream);
-  return decoder_sample_t<bf16_t>(d, P, S, o, (unsigned char*)ws, features, noise_u, seed, ids, scores, lengths, (hipStream_t)stream);
-}
-
-int gic_attn_sample_ws_bytes(const gic_attn_dims* dims, int32_t num_samples, uint64_t* out) {
-  AttnSampleDims d;
-  GIC_PROPAGATE(attn_sample_dims(dims, num_samples, d));
-  GIC_CHECK_ARG(out, "attn_sample_ws_bytes: null out");
-  *out = (uint64_t)attn_sample_layout(d).total;
-  return GIC_OK;
-}
-
-int gic_attn_sample_captions(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_sample_opts* o, void* ws,
-                             const float* features, const void* fmap, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
-                             int32_t* lengths, void* stream) {
-  GIC_CHECK_ARG(o, "attn_sample_captions: null options");
-  AttnSampleDims d;
-  GIC_PROPAGATE(attn_sample_dims(dims, o->num_samples, d));
-  GIC_PROPAGATE(check_sample_opts(o, d.c.V, true, "attn_sample_captions"));
-  GIC_CHECK_ARG(P && S && ws && features && fmap && ids && scores && lengths, "attn_sample_captions: null argument");
-  GIC_CHECK_ARG(P->embed && P->b_out && P->b_f && P->w_a && S->wcat && S->bsum && S->wout && S->wf && S->wh, "attn_sample_captions: null weights");
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "attn_sample_captions: the workspace must be 256-byte aligned");
-  if (d.c.dt == DT_F32)
-    return attn_sample_t<float>(d, P, S, o, (unsigned char*)ws, features, fmap, noise_u, seed, ids, scores, lengths, (hipStream_t)stream);
-  return attn_sample_t<bf16_t>(d, P, S, o, (unsigned char*)ws, features, fmap, noise_u, seed, ids, scores, lengths, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -211,6 +211,31 @@ def _aligned_ws(ws: Optional[torch.Tensor], nbytes: int, dev) -> torch.Tensor:
     return ws
 
 
+def _decode_features(features: torch.Tensor, E: int) -> torch.Tensor:
+    """The decode methods' features: float32 [B, E], contiguous."""
+    if tuple(features.shape) != (features.shape[0], E) or features.dtype != torch.float32:
+        raise ValueError(f"features must be float32 [B,{E}], got {tuple(features.shape)} {features.dtype}")
+    return features.contiguous()
+
+
+def _decode_states(opts, states, shape, err: str):
+    """(h0, c0), each f32 of ``shape``, into opts.h0 / opts.c0 (None: zeros).  Returns the tensors the call reads."""
+    if states is None:
+        return ()
+    h0, c0 = (t.detach().to(torch.float32).contiguous() for t in states)
+    if tuple(h0.shape) != shape or tuple(c0.shape) != shape:
+        raise ValueError(err)
+    require_gpu(h0, c0)
+    opts.h0, opts.c0 = ptr(h0), ptr(c0)
+    return h0, c0
+
+
+def _decode_outputs(B: int, n: int, Lc: int, dev):
+    """ids int64 [B, n, Lc], scores f32 [B, n], lengths int32 [B, n]."""
+    return (torch.empty(B, n, Lc, device=dev, dtype=torch.int64), torch.empty(B, n, device=dev, dtype=torch.float32),
+            torch.empty(B, n, device=dev, dtype=torch.int32))
+
+
 def _sample_noise(noise_u: Optional[torch.Tensor], Lc: int, rows: int, V: int) -> Optional[torch.Tensor]:
     if noise_u is None:
         return None
@@ -570,6 +595,10 @@ class DecoderEngine:
         d_c0 = torch.stack([ws["dc"][l] for l in range(self.NL)]).contiguous()
         return d_h0, d_c0
 
+    def _states(self, opts, states, B: int):
+        shape = (self.NL, B, self.H)
+        return _decode_states(opts, states, shape, f"states must be (h0, c0), each [num_layers={self.NL}, B={B}, H={self.H}]")
+
     def beam_ws_bytes(self, B: int, Lc: int, beam: int) -> int:
         """Bytes of gic_decoder_beam_search's workspace (host-only query; the library's own path choice sizes it)."""
         out = C.c_uint64(0)
@@ -586,30 +615,14 @@ class DecoderEngine:
         ``states`` = (h0, c0), each f32 [NL, B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned)."""
         self.check_params(params)
         require_gpu(features)
-        B = features.shape[0]
-        if features.shape != (B, self.E) or features.dtype != torch.float32:
-            raise ValueError(f"features must be float32 [B,{self.E}], got {tuple(features.shape)} {features.dtype}")
-        features = features.contiguous()
-        dev = features.device
+        features = _decode_features(features, self.E)
+        B, dev = features.shape[0], features.device
         self.prepare(params)
-        nbytes = self.beam_ws_bytes(B, Lc, beam)
-        if ws is None or ws.numel() < nbytes or ws.data_ptr() % 256:
-            ws = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
-            off = (-ws.data_ptr()) % 256
-            ws = ws[off:off + nbytes]
+        ws = _aligned_ws(ws, self.beam_ws_bytes(B, Lc, beam), dev)
         opts = L.DecoderBeamOpts()
         opts.beam, opts.eos_id, opts.pad_id, opts.length_penalty = int(beam), int(eos_id), int(pad_id), float(length_penalty)
-        keep = []
-        if states is not None:
-            h0, c0 = (t.detach().to(torch.float32).contiguous() for t in states)
-            if tuple(h0.shape) != (self.NL, B, self.H) or tuple(c0.shape) != (self.NL, B, self.H):
-                raise ValueError(f"states must be (h0, c0), each [num_layers={self.NL}, B={B}, H={self.H}]")
-            require_gpu(h0, c0)
-            opts.h0, opts.c0 = ptr(h0), ptr(c0)
-            keep += [h0, c0]
-        ids = torch.empty(B, beam, Lc, device=dev, dtype=torch.int64)
-        scores = torch.empty(B, beam, device=dev, dtype=torch.float32)
-        lengths = torch.empty(B, beam, device=dev, dtype=torch.int32)
+        keep = self._states(opts, states, B)
+        ids, scores, lengths = _decode_outputs(B, beam, Lc, dev)
         d = self.dims(B, Lc)
         L.check(L.load().gic_decoder_beam_search(
             C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws), ptr(features),
@@ -631,28 +644,16 @@ class DecoderEngine:
         sample_ws_bytes() bytes (256-aligned)."""
         self.check_params(params)
         require_gpu(features)
-        B = features.shape[0]
-        if features.shape != (B, self.E) or features.dtype != torch.float32:
-            raise ValueError(f"features must be float32 [B,{self.E}], got {tuple(features.shape)} {features.dtype}")
-        features = features.contiguous()
-        dev = features.device
+        features = _decode_features(features, self.E)
+        B, dev = features.shape[0], features.device
         n = int(num_samples)
         noise_u = _sample_noise(noise_u, Lc, B * n, self.V)
         opts = sample_opts(n, top_k, top_p, temperature, eos_id, pad_id)
         nbytes = self.sample_ws_bytes(B, Lc, n)          # (checks the dims and n before anything runs)
         self.prepare(params)
         ws = _aligned_ws(ws, nbytes, dev)
-        keep = []
-        if states is not None:
-            h0, c0 = (t.detach().to(torch.float32).contiguous() for t in states)
-            if tuple(h0.shape) != (self.NL, B, self.H) or tuple(c0.shape) != (self.NL, B, self.H):
-                raise ValueError(f"states must be (h0, c0), each [num_layers={self.NL}, B={B}, H={self.H}]")
-            require_gpu(h0, c0)
-            opts.h0, opts.c0 = ptr(h0), ptr(c0)
-            keep += [h0, c0]
-        ids = torch.empty(B, n, Lc, device=dev, dtype=torch.int64)
-        scores = torch.empty(B, n, device=dev, dtype=torch.float32)
-        lengths = torch.empty(B, n, device=dev, dtype=torch.int32)
+        keep = self._states(opts, states, B)
+        ids, scores, lengths = _decode_outputs(B, n, Lc, dev)
         L.check(L.load().gic_decoder_sample_captions(
             C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
             ptr(features), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()),
@@ -1042,6 +1043,10 @@ class AttnDecoderEngine:
             fmap = dst
         return fmap
 
+    def _states(self, opts, states, B: int):
+        states = None if states is None else [t.reshape(-1, self.H) for t in states]
+        return _decode_states(opts, states, (B, self.H), f"states must be (h0, c0), each [1, B={B}, H={self.H}]")
+
     def beam_ws_bytes(self, B: int, Lc: int, beam: int) -> int:
         """Bytes of gic_attn_beam_search's workspace (host-only query)."""
         out = C.c_uint64(0)
@@ -1055,31 +1060,15 @@ class AttnDecoderEngine:
         [B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned)."""
         self.check_params(params)
         require_gpu(features, fmap)
-        B = features.shape[0]
-        if tuple(features.shape) != (B, self.E) or features.dtype != torch.float32:
-            raise ValueError(f"features must be float32 [B,{self.E}]")
+        features = _decode_features(features, self.E)
+        B, dev = features.shape[0], features.device
         fmap = self._act_fmap(fmap, B)
-        features = features.contiguous()
-        dev = features.device
         self.prepare(params)
-        nbytes = self.beam_ws_bytes(B, Lc, beam)
-        if ws is None or ws.numel() < nbytes or ws.data_ptr() % 256:
-            ws = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
-            off = (-ws.data_ptr()) % 256
-            ws = ws[off:off + nbytes]
+        ws = _aligned_ws(ws, self.beam_ws_bytes(B, Lc, beam), dev)
         opts = L.DecoderBeamOpts()
         opts.beam, opts.eos_id, opts.pad_id, opts.length_penalty = int(beam), int(eos_id), int(pad_id), float(length_penalty)
-        keep = []
-        if states is not None:
-            h0, c0 = (t.detach().to(torch.float32).reshape(-1, self.H).contiguous() for t in states)
-            if tuple(h0.shape) != (B, self.H) or tuple(c0.shape) != (B, self.H):
-                raise ValueError(f"states must be (h0, c0), each [1, B={B}, H={self.H}]")
-            require_gpu(h0, c0)
-            opts.h0, opts.c0 = ptr(h0), ptr(c0)
-            keep += [h0, c0]
-        ids = torch.empty(B, beam, Lc, device=dev, dtype=torch.int64)
-        scores = torch.empty(B, beam, device=dev, dtype=torch.float32)
-        lengths = torch.empty(B, beam, device=dev, dtype=torch.int32)
+        keep = self._states(opts, states, B)
+        ids, scores, lengths = _decode_outputs(B, beam, Lc, dev)
         alphas = torch.empty(B, beam, Lc, self.P, device=dev, dtype=torch.float32) if want_alphas else None
         L.check(L.load().gic_attn_beam_search(
             C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
@@ -1102,29 +1091,17 @@ class AttnDecoderEngine:
         each [1, B, H] or [B, H]."""
         self.check_params(params)
         require_gpu(features, fmap)
-        B = features.shape[0]
-        if tuple(features.shape) != (B, self.E) or features.dtype != torch.float32:
-            raise ValueError(f"features must be float32 [B,{self.E}]")
+        features = _decode_features(features, self.E)
+        B, dev = features.shape[0], features.device
         n = int(num_samples)
         noise_u = _sample_noise(noise_u, Lc, B * n, self.V)
         opts = sample_opts(n, top_k, top_p, temperature, eos_id, pad_id)
         nbytes = self.sample_ws_bytes(B, Lc, n)
         fmap = self._act_fmap(fmap, B)
-        features = features.contiguous()
-        dev = features.device
         self.prepare(params)
         ws = _aligned_ws(ws, nbytes, dev)
-        keep = []
-        if states is not None:
-            h0, c0 = (t.detach().to(torch.float32).reshape(-1, self.H).contiguous() for t in states)
-            if tuple(h0.shape) != (B, self.H) or tuple(c0.shape) != (B, self.H):
-                raise ValueError(f"states must be (h0, c0), each [1, B={B}, H={self.H}]")
-            require_gpu(h0, c0)
-            opts.h0, opts.c0 = ptr(h0), ptr(c0)
-            keep += [h0, c0]
-        ids = torch.empty(B, n, Lc, device=dev, dtype=torch.int64)
-        scores = torch.empty(B, n, device=dev, dtype=torch.float32)
-        lengths = torch.empty(B, n, device=dev, dtype=torch.int32)
+        keep = self._states(opts, states, B)
+        ids, scores, lengths = _decode_outputs(B, n, Lc, dev)
         L.check(L.load().gic_attn_sample_captions(
             C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
             ptr(features), ptr(fmap), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()),
