@@ -217,6 +217,9 @@ _SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p]),
     "gic_xent": (C.c_int, [c_void_p, C.c_int, C.c_int64, C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_rollout_rewards": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
+    "gic_cider_d": (C.c_int, [c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int32, C.c_int32, c_void_p, C.c_int64, c_void_p, c_void_p,
+                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p, C.c_int64, C.c_float, C.c_int32, c_void_p,
+                              c_void_p]),
     "gic_set_deterministic": (C.c_int, [C.c_int]),
     "gic_get_deterministic": (C.c_int, []),
     "gic_bn_stats_slab_floats": (C.c_int, [C.c_int64, C.c_int32, c_void_p]),
@@ -227,6 +230,7 @@ _SIGNATURES = {
 }
 
 ABI_VERSION = 4               # GIC_ABI_VERSION of include/gicap.h
+CIDER_MAX_LEN, CIDER_MAX_REFS, CIDER_MAX_VOCAB = 64, 32, 32768      # GIC_CIDER_MAX_LEN / _MAX_REFS / _MAX_VOCAB
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _lib = None
 

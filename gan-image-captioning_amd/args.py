@@ -101,6 +101,14 @@ _NATIVE = [
     ("--eval-top-k", int, 0, "top-k truncation of the diversity evaluation's sampling; 0 = off"),
     ("--eval-top-p", float, 1.0, "top-p (nucleus) truncation of the diversity evaluation's sampling; 1.0 = off"),
     ("--eval-sample-temperature", float, 1.0, "sampling temperature of the diversity evaluation (divides the logits; not --temperature)"),
+    ("--scst-epochs", int, 0, "epochs of self-critical sequence training (CIDEr-D reward, scst.py) after MLE pre-training and before the "
+                              "adversarial loop; 0 = off"),
+    ("--scst-samples", int, 5, "sampled captions per image of an SCST step (1..8)"),
+    ("--scst-baseline", str, "greedy", "SCST baseline: greedy = the CIDEr-D of the greedy caption; mean = the mean reward of the image's "
+                                       "other samples (needs --scst-samples >= 2)", {"choices": ["greedy", "mean"]}),
+    ("--scst-lr", float, 5e-5, "learning rate of SCST (its own clip + Adam over the generator's parameters)"),
+    ("--eval-cider-beam-size", int, 0, "beam size of the CIDEr-D evaluation (GANInstructor.evaluate_cider) after each adversarial epoch's "
+                                       "validation; 0 = off"),
 ]
 
 

@@ -291,6 +291,43 @@ def rollout_rewards(mc_logits: Optional[torch.Tensor], full_logits: torch.Tensor
     return out
 
 
+def _tf_lengths(lengths, B: int, T: int, tmax: Optional[int]):
+    """(Tmax, lengths int32) of a teacher-forced decode: max(lengths) read on the host, or with ``tmax`` the device lengths as given
+    (each must be in 1..T; not read back)."""
+    if tmax is not None:
+        if not (torch.is_tensor(lengths) and lengths.is_cuda and lengths.numel() == B) or not 1 <= int(tmax) <= T:
+            raise ValueError(f"tmax needs device lengths [{B}] and a value in 1..{T}")
+        return int(tmax), lengths.to(torch.int32).contiguous()
+    lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(lens) != B or min(lens) < 1 or max(lens) > T:
+        raise ValueError(f"lengths must hold {B} values in 1..{T}")
+    return max(lens), torch.tensor(lens, dtype=torch.int32)
+
+
+def cider_d(cand_ids: torch.Tensor, cand_len: torch.Tensor, cand_img: torch.Tensor, ref_ids: torch.Tensor, ref_len: torch.Tensor,
+            ref_off: torch.Tensor, max_refs: int, keys: torch.Tensor, idf: torch.Tensor, log_n: float, V: int) -> torch.Tensor:
+    """gic_cider_d: CIDEr-D f32 [n_cand] of candidates int64 [n_cand, Lc] (cand_len / cand_img int32 [n_cand]) against the references
+    int64 [n_ref, Lr] (ref_len int32 [n_ref]; image b owns rows ref_off[b] .. ref_off[b+1], int32 [B+1]), with the document-frequency
+    table keys int64 [K] (the uint64 keys of gicap.h, all below 2^62) / idf f32 [K].  ``max_refs``: the largest reference count of
+    one image (host-known).  One launch, no host sync."""
+    require_gpu(cand_ids, cand_len, cand_img, ref_ids, ref_len, ref_off, keys, idf)
+    if cand_ids.dim() != 2 or ref_ids.dim() != 2 or cand_ids.dtype != torch.int64 or ref_ids.dtype != torch.int64:
+        raise ValueError("cand_ids and ref_ids must be int64 [rows, L]")
+    n_cand, Lc = cand_ids.shape
+    n_ref, Lr = ref_ids.shape
+    B = ref_off.numel() - 1
+    i32 = lambda t: t.to(torch.int32).contiguous()        # noqa: E731
+    cand_ids, ref_ids = cand_ids.contiguous(), ref_ids.contiguous()
+    cand_len, cand_img, ref_len, ref_off = i32(cand_len), i32(cand_img), i32(ref_len), i32(ref_off)
+    if cand_len.numel() != n_cand or cand_img.numel() != n_cand or ref_len.numel() != n_ref:
+        raise ValueError("cand_len / cand_img need one value per candidate and ref_len one per reference")
+    scores = torch.empty(n_cand, device=cand_ids.device, dtype=torch.float32)
+    L.check(L.load().gic_cider_d(ptr(cand_ids), Lc, ptr(cand_len), ptr(cand_img), n_cand, Lc, ptr(ref_ids), Lr, ptr(ref_len), ptr(ref_off),
+                                 n_ref, Lr, B, int(max_refs), ptr(keys.contiguous()), ptr(idf.contiguous()), keys.numel(), float(log_n),
+                                 int(V), ptr(scores), stream_ptr()), "gic_cider_d")
+    return scores
+
+
 # ------------------------------------------------------------------------------------------ decoder
 class DecoderEngine:
     """Decoder.sample forward/backward (reference src/generator.py:55-96) on the HIP library."""
@@ -504,17 +541,16 @@ class DecoderEngine:
         return (None if ids_only else out), ids, st
 
     def forward_tf(self, params, features: torch.Tensor, caps: torch.Tensor, lengths, temperature: float, pretrain: bool = False,
-                   noise_u: Optional[torch.Tensor] = None, seed: int = 0, keep_state: bool = False):
+                   noise_u: Optional[torch.Tensor] = None, seed: int = 0, keep_state: bool = False, tmax: Optional[int] = None):
         """gic_decoder_forward_tf: Decoder.forward (teacher forcing, generator.py:39-53).
-        Returns (pred act [B, max(lengths), V], (h_n, c_n) f32 [NL, B, H]); with ``keep_state`` also what ``forward_tf_bwd`` needs."""
+        Returns (pred act [B, max(lengths), V], (h_n, c_n) f32 [NL, B, H]); with ``keep_state`` also what ``forward_tf_bwd`` needs.
+        ``tmax``: decode that many steps and take ``lengths`` as device int32 values in 1..T unread (no host sync); pred is then
+        [B, tmax, V]."""
         self.check_params(params)
         require_gpu(features, caps, noise_u)
         B, Lc = caps.shape
         T = Lc + 1
-        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if len(lens) != B or min(lens) < 1 or max(lens) > T:
-            raise ValueError(f"lengths must hold {B} values in 1..{T}")
-        Tmax = max(lens)
+        Tmax, len_dev = _tf_lengths(lengths, B, T, tmax)
         dev = features.device
         if features.shape != (B, self.E) or caps.dtype != torch.int64:
             raise ValueError("features must be [B, E] and caps int64 [B, L]")
@@ -527,7 +563,7 @@ class DecoderEngine:
         c_n = torch.empty_like(h_n)
         logits_ws = torch.empty(B * Tmax, self.V, device=dev, dtype=torch.float32)
         ids_ws = torch.empty(B * Tmax, device=dev, dtype=torch.int64)
-        len_dev = torch.tensor(lens, dtype=torch.int32, device=dev)
+        len_dev = len_dev.to(dev)
         d = self.dims(B, T)
         L.check(L.load().gic_decoder_forward_tf(
             C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
@@ -1115,18 +1151,17 @@ class AttnDecoderEngine:
         return int(out.value)
 
     def forward_tf(self, params, features, fmap, caps: torch.Tensor, lengths, temperature: float, pretrain: bool = False,
-                   noise_u: Optional[torch.Tensor] = None, seed: int = 0, want_alphas: bool = False, keep_state: bool = False):
+                   noise_u: Optional[torch.Tensor] = None, seed: int = 0, want_alphas: bool = False, keep_state: bool = False,
+                   tmax: Optional[int] = None):
         """gic_attn_forward_tf: the teacher-forced decode (DecoderEngine.forward_tf with the attention step).  ``caps`` int64 [B, T-1],
         ``lengths`` B values in 1..T, ``fmap`` [B, P, C] (cast to the compute dtype as in sample_fwd).  Returns (pred act [B, Tmax, V],
-        (h_n, c_n) f32 [1, B, H], alphas f32 [B, Tmax, P] or None); with ``keep_state`` also what ``forward_tf_bwd`` needs."""
+        (h_n, c_n) f32 [1, B, H], alphas f32 [B, Tmax, P] or None); with ``keep_state`` also what ``forward_tf_bwd`` needs.  ``tmax``
+        as DecoderEngine.forward_tf."""
         self.check_params(params)
         require_gpu(features, fmap, caps, noise_u)
         B, Lc = caps.shape
         T = Lc + 1
-        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if len(lens) != B or min(lens) < 1 or max(lens) > T:
-            raise ValueError(f"lengths must hold {B} values in 1..{T}")
-        Tmax = max(lens)
+        Tmax, len_dev = _tf_lengths(lengths, B, T, tmax)
         if tuple(features.shape) != (B, self.E) or features.dtype != torch.float32 or caps.dtype != torch.int64:
             raise ValueError(f"features must be float32 [B, {self.E}] and caps int64 [B, L]")
         if noise_u is not None:
@@ -1142,7 +1177,7 @@ class AttnDecoderEngine:
         c_n = torch.empty_like(h_n)
         alphas = torch.empty(B, Tmax, self.P, device=dev, dtype=torch.float32) if want_alphas else None
         logits_ws = torch.empty(self.tf_ws_bytes(B, T, Tmax) // 4, device=dev, dtype=torch.float32)
-        len_dev = torch.tensor(lens, dtype=torch.int32, device=dev)
+        len_dev = len_dev.to(dev)
         caps = caps.contiguous()
         L.check(L.load().gic_attn_forward_tf(
             C.byref(self.dims(B, T)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),

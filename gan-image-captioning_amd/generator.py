@@ -133,10 +133,10 @@ class _ForwardTfFn(torch.autograd.Function):
     """Decoder.forward with autograd (generator.py:39-53): gic_decoder_forward_tf / gic_decoder_forward_tf_bwd."""
 
     @staticmethod
-    def forward(ctx, eng, temperature, pretrain, caps, lengths, noise_u, seed, features, *params):
+    def forward(ctx, eng, temperature, pretrain, caps, lengths, noise_u, seed, tmax, features, *params):
         dparams = [p.detach() for p in params]
         pred, (h_n, c_n), saved = eng.forward_tf(dparams, features.detach().float(), caps, lengths, temperature, pretrain, noise_u, seed,
-                                                 keep_state=True)
+                                                 keep_state=True, tmax=tmax)
         ctx.eng, ctx.temperature, ctx.pretrain, ctx.saved, ctx.dparams = eng, temperature, pretrain, saved, dparams
         ctx.save_for_backward(pred)
         ctx.mark_non_differentiable(h_n, c_n)
@@ -147,7 +147,7 @@ class _ForwardTfFn(torch.autograd.Function):
         (pred,) = ctx.saved_tensors
         grads = ctx.eng.forward_tf_bwd(ctx.dparams, ctx.saved, pred, d_pred, ctx.temperature, ctx.pretrain)
         ctx.saved = None
-        return (None, None, None, None, None, None, None, grads[-1], *grads[:-1])
+        return (None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
 
 
 class Decoder(nn.Module):
@@ -185,21 +185,22 @@ class Decoder(nn.Module):
         return _SampleFn.apply(self.engine(), float(self.temperature), bool(pretrain), int(max_caption_len), noise_u, seed,
                                h0, c0, features, *self.param_list())
 
-    def forward(self, features, caps, lengths, pretrain=False, noise_u=None):
+    def forward(self, features, caps, lengths, pretrain=False, noise_u=None, max_length=None):
         """Teacher-forced decode (generator.py:39-53): inputs [features ; embed(caps)] packed with ``lengths``; returns
         (pred [B, max(lengths), V], (h_n, c_n)) with pred = logits (pretrain) or softmax((logits + gumbel) * temperature).
         Dead on the reference's training path (training.py never calls it), kept for the module surface.  Gradients flow through
         ``pred`` to the decoder parameters and ``features`` (padded positions reach the projection's bias only, as
         pad_packed_sequence's zeros do); the returned hidden state is not differentiated.  ``noise_u`` [B, max(lengths), V]
-        replaces the device draw (parity runs)."""
+        replaces the device draw (parity runs).  ``max_length``: decode that many steps with ``lengths`` a device tensor that is not
+        read back (no host sync; pred is [B, max_length, V], rows past a length as above)."""
         seed = 0 if noise_u is not None else SEEDS.next()
         params = self.param_list()
         if not torch.is_grad_enabled() or not (features.requires_grad or any(p.requires_grad for p in params)):
             with torch.no_grad():
                 return self.engine().forward_tf([p.detach() for p in params], features, caps, lengths, float(self.temperature),
-                                                bool(pretrain), noise_u, seed)
+                                                bool(pretrain), noise_u, seed, tmax=max_length)
         pred, h_n, c_n = _ForwardTfFn.apply(self.engine(), float(self.temperature), bool(pretrain), caps, lengths, noise_u, seed,
-                                            features, *params)
+                                            max_length, features, *params)
         return pred, (h_n, c_n)
 
     def beam_search(self, features, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None, return_beams=False):
@@ -260,10 +261,10 @@ class _AttnForwardTfFn(torch.autograd.Function):
     """AttnDecoder.forward with autograd: gic_attn_forward_tf / gic_attn_forward_tf_bwd; the alphas are differentiable too."""
 
     @staticmethod
-    def forward(ctx, eng, temperature, pretrain, caps, lengths, noise_u, seed, fmap, features, *params):
+    def forward(ctx, eng, temperature, pretrain, caps, lengths, noise_u, seed, tmax, fmap, features, *params):
         dparams = [p.detach() for p in params]
         pred, (h_n, c_n), alphas, saved = eng.forward_tf(dparams, features.detach().float(), fmap.detach(), caps, lengths, temperature,
-                                                         pretrain, noise_u, seed, want_alphas=True, keep_state=True)
+                                                         pretrain, noise_u, seed, want_alphas=True, keep_state=True, tmax=tmax)
         ctx.eng, ctx.temperature, ctx.pretrain, ctx.saved, ctx.dparams = eng, temperature, pretrain, saved, dparams
         ctx.save_for_backward(pred)
         ctx.mark_non_differentiable(h_n, c_n)
@@ -275,7 +276,7 @@ class _AttnForwardTfFn(torch.autograd.Function):
         (pred,) = ctx.saved_tensors
         grads = ctx.eng.forward_tf_bwd(ctx.dparams, ctx.saved, pred, d_pred, ctx.temperature, ctx.pretrain, d_alphas=d_alphas)
         ctx.saved = None
-        return (None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
+        return (None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
 
 
 class _AttnParams(nn.Module):
@@ -357,14 +358,14 @@ class AttnDecoder(nn.Module):
                                                  int(num_samples), int(top_k), float(top_p), float(temperature), int(eos_id), 0, seed,
                                                  noise_u, states=states)
 
-    def forward(self, features, fmap, caps, lengths, pretrain=False, noise_u=None, return_alphas=False):
+    def forward(self, features, fmap, caps, lengths, pretrain=False, noise_u=None, return_alphas=False, max_length=None):
         """Teacher-forced decode (Decoder.forward with the attention step, gicap.h gic_attn_forward_tf): step 0 is fed ``features``,
         step t > 0 embed(caps[:, t-1]), packed with ``lengths`` (each 1..caps.shape[1] + 1).  Returns (pred [B, max(lengths), V],
         (h_n, c_n) [1, B, H]) with pred = logits (pretrain) or softmax((logits + gumbel) * temperature); ``return_alphas`` appends the
         attention weights f32 [B, max(lengths), P] (zero past a caption's length), differentiable like ``pred``.  Gradients flow to the
         decoder parameters and ``features`` (padded positions reach the projection's bias only); the returned hidden state is not
         differentiated.  ``fmap`` [B, P, C]: the trunk's last feature map (no gradient into it).  ``noise_u`` [B, max(lengths), V]
-        replaces the device draw."""
+        replaces the device draw.  ``max_length`` as Decoder.forward."""
         if fmap is None:
             raise ValueError("the attention decoder needs the trunk's feature map: forward(features, fmap, caps, lengths)")
         seed = 0 if noise_u is not None else SEEDS.next()
@@ -373,10 +374,10 @@ class AttnDecoder(nn.Module):
             with torch.no_grad():
                 pred, hc, alphas = self.engine().forward_tf([p.detach() for p in params], features.detach().float(), fmap.detach(), caps,
                                                             lengths, float(self.temperature), bool(pretrain), noise_u, seed,
-                                                            want_alphas=bool(return_alphas))
+                                                            want_alphas=bool(return_alphas), tmax=max_length)
         else:
             pred, h_n, c_n, alphas = _AttnForwardTfFn.apply(self.engine(), float(self.temperature), bool(pretrain), caps, lengths, noise_u,
-                                                            seed, fmap, features, *params)
+                                                            seed, max_length, fmap, features, *params)
             hc = (h_n, c_n)
         if return_alphas:
             return pred, hc, alphas

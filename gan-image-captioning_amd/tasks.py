@@ -142,3 +142,56 @@ def synthetic_batch(batch: int, vocab_size: int, image_size: int, caption_len: i
         images = images.to(device) if images is not None else None
         captions, lengths = captions.to(device), lengths.to(device)
     return images, captions, lengths, caption_len
+
+
+def group_by_image(ds) -> Tuple[dict, list]:
+    """The items of ``ds`` grouped by image: ``filepath`` + ``filename`` for COCO_data, one image per item otherwise.  Returns
+    (groups {key: [item index]}, keys in first-seen order)."""
+    groups, order = {}, []
+    for i in range(len(ds)):
+        if isinstance(ds, COCO_data):
+            e = ds.captions[i]
+            key = (e["filepath"], e["filename"])
+        else:
+            key = i
+        if key not in groups:
+            groups[key] = []
+            order.append(key)
+        groups[key].append(i)
+    return groups, order
+
+
+class ImageGroups(Dataset):
+    """Image-grouped view of a caption dataset (the grouping of ``group_by_image``): item k = (image, [reference token lists]) of the
+    k-th image; the image is loaded once per image.  ``references()`` gives every image's token lists without loading images (COCO)."""
+
+    def __init__(self, ds):
+        self.ds = ds
+        self.groups, self.order = group_by_image(ds)
+        self.coco = isinstance(ds, COCO_data)
+
+    def __len__(self):
+        return len(self.order)
+
+    def _tokens(self, i):
+        unk = self.ds.word_to_index.get("<UNK>", 3)
+        return [t if isinstance(t, int) else self.ds.word_to_index.get(t, unk) for t in self.ds.captions[i]["tokens"]]
+
+    def __getitem__(self, k):
+        items = self.groups[self.order[k]]
+        image, first = self.ds[items[0]]
+        return image, [self._tokens(i) for i in items] if self.coco else [first]
+
+    def references(self) -> List[List[List[int]]]:
+        if self.coco:
+            return [[self._tokens(i) for i in self.groups[k]] for k in self.order]
+        return [[self.ds[self.groups[k][0]][1]] for k in self.order]
+
+
+def collate_groups(batch: Sequence[Tuple[torch.Tensor, List[List[int]]]]):
+    """(images f32 [B,3,S,S], refs) with refs = (ids int64 [n_ref, Lr] zero-padded, lengths int32 [n_ref], offsets int32 [B+1],
+    max references per image): the references packed for gic_cider_d (cider.RefBatch.pack)."""
+    from .cider import RefBatch
+    images = torch.stack([image for image, _ in batch])
+    r = RefBatch.pack([refs for _, refs in batch])
+    return images, (r.ids, r.lengths, r.offsets, r.max_refs)

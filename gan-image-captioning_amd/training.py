@@ -142,6 +142,8 @@ class GANInstructor:
         self.gen_steps = 0
         self.disc_steps = 0
         self.adv_epoch = -1
+        self.scst_steps = 0
+        self._cider = {}
 
     # ------------------------------------------------------------------ shared pieces
     def _features(self, images, batch, next_images=None):
@@ -333,8 +335,55 @@ class GANInstructor:
         if self.model_dir and self.dist.rank == 0:
             torch.save(obj, os.path.join(self.model_dir, name))
 
+    # ------------------------------------------------------------------ self-critical sequence training (scst.py)
+    def scst_train(self, epochs):
+        """``epochs`` SCST epochs over the training images (grouped by image, --adv-train-batch-size images per step): CIDEr-D
+        rewards with df from the training references.  After each epoch the greedy CIDEr-D on val decides whether the generator is
+        saved as ``scst_model.ckpt`` (the generator's state dict: --resume loads it as pretrained weights).  Returns the best val
+        CIDEr-D."""
+        from .cider import CiderD, RefBatch
+        from .scst import SCSTStep
+        from .tasks import ImageGroups, collate_groups
+        args = self.args
+        groups = ImageGroups(self.train_dataset)
+        step = SCSTStep(self, CiderD(groups.references(), args.vocab_size, args.device), int(getattr(args, "scst_samples", 5)),
+                        getattr(args, "scst_baseline", "greedy"), float(getattr(args, "scst_lr", 5e-5)))
+        dp = self.dist.world_size > 1
+        loader = DataLoader(groups, shuffle=not dp, batch_size=args.adv_train_batch_size, collate_fn=collate_groups,
+                            num_workers=int(getattr(args, "num_workers", 4)),
+                            sampler=parallel.shard_sampler(groups, self.dist, True) if dp else None)
+        L = int(args.max_seq_len)
+        best = None
+        self.log.info("Starting SCST (%d samples, %s baseline)...", step.n, step.baseline)
+        for epoch in range(epochs):
+            self.gen.train()
+            self._reshuffle(loader, "train")
+            rewards = []
+            with torch.enable_grad(), tqdm(total=len(groups), disable=self.dist.rank != 0) as progress:
+                for images, (ids, lens, off, max_refs) in loader:
+                    refs = RefBatch(ids, lens, off, max_refs).to(args.device)
+                    out = step(images.to(args.device) if self.cgan else None, refs, L)
+                    loss, r, b = torch.stack([out["loss"].float(), out["reward"], out["baseline"]]).tolist()   # the step's one sync
+                    rewards.append(r)
+                    self.writer.add_scalar("SCST_train_reward", r, self.scst_steps)
+                    self.scst_steps += 1
+                    progress.update(len(images) * self.dist.world_size)
+                    progress.set_postfix(reward=r, baseline=b, loss=loss)
+            self.gen.eval()
+            val = self.evaluate_cider("val", beam_size=1) if self.dist.rank == 0 else 0.0
+            self.writer.add_scalar("SCST_val_cider", val, epoch)
+            if best is None or val > best:
+                best = val
+                self._save(self.gen.state_dict(), "scst_model.ckpt")
+                self.log.info("Saving Best model [CIDEr-D = {}] at SCST epoch {}".format(best, epoch))
+            self.log.info("[SCST] epoch %d: train reward %.4f | val CIDEr-D (greedy) %.4f", epoch, float(np.mean(rewards)), val)
+            self.writer.flush()
+        return best
+
     def _run(self):
         self.pretrain_generator(self.args.pretrain_epochs)
+        if int(getattr(self.args, "scst_epochs", 0)) > 0:
+            self.scst_train(int(self.args.scst_epochs))
         self.log.info("Starting Adversarial Training...")
         best_loss = None
         for adv_epoch in range(self.args.adv_epochs):
@@ -354,6 +403,8 @@ class GANInstructor:
                     adv_epoch, self.gen.decoder.temperature, train_g_loss, val_g_loss, train_d_loss, val_d_loss))
             if int(getattr(self.args, "eval_beam_size", 0)) > 0 and self.dist.rank == 0:
                 self.evaluate("val", beam_size=int(self.args.eval_beam_size))
+            if int(getattr(self.args, "eval_cider_beam_size", 0)) > 0 and self.dist.rank == 0:
+                self.evaluate_cider("val", beam_size=int(self.args.eval_cider_beam_size))
             if int(getattr(self.args, "eval_num_samples", 0)) > 0 and self.dist.rank == 0:
                 self.evaluate_diversity("val", num_samples=int(self.args.eval_num_samples), top_k=int(getattr(self.args, "eval_top_k", 0)),
                                         top_p=float(getattr(self.args, "eval_top_p", 1.0)),
@@ -368,11 +419,25 @@ class GANInstructor:
         --max-seq-len cannot truncate every candidate below its references.  Logs the score and writes the scalar
         ``BLEU4_<what>``."""
         from .utils import bleu_score
-        ds, groups, order, coco, coco_ids, words = self._eval_groups(what)
+        words = self._eval_groups(what)[-1]
+        cands, refs = [], []
+        for ids, lengths, caps in self._beam_decode(what, beam_size, max_caption_len, batch_size):
+            ids, lengths = ids.cpu(), lengths.cpu()
+            for b, group in enumerate(caps):
+                cands.append(words(ids[b, :int(lengths[b])].tolist()))
+                refs.append([words(c) for c in group])
+        score = bleu_score(cands, refs)
+        self.log.info("[EVAL] BLEU-4 (%s, beam %d): %.4f", what, beam_size, score)
+        self.writer.add_scalar(f"BLEU4_{what}", score, max(self.adv_epoch, 0))
+        return score
+
+    def _beam_decode(self, what, beam_size, max_caption_len=None, batch_size=None):
+        """The decode loop of ``evaluate`` / ``evaluate_cider``: every image of the split once (``_eval_groups``), the generator in eval
+        mode; yields per batch (ids [b, L] and lengths [b] on the device, the images' reference token lists)."""
+        ds, groups, order, coco, coco_ids, _ = self._eval_groups(what)
         was_training = self.gen.training
         self.gen.eval()
         bs = int(batch_size or getattr(self.args, "adv_eval_batch_size", 32))
-        cands, refs = [], []
         try:
             for s in range(0, len(order), bs):
                 keys = order[s:s + bs]
@@ -382,34 +447,35 @@ class GANInstructor:
                 L = max_caption_len or max(int(getattr(self.args, "max_seq_len", 0) or 0),
                                            max(len(c) for group in caps for c in group) + 2)
                 ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L)
-                ids, lengths = ids.cpu(), lengths.cpu()
-                for b, group in enumerate(caps):
-                    cands.append(words(ids[b, :int(lengths[b])].tolist()))
-                    refs.append([words(c) for c in group])
+                yield ids, lengths, caps
         finally:
             self.gen.train(was_training)
-        score = bleu_score(cands, refs)
-        self.log.info("[EVAL] BLEU-4 (%s, beam %d): %.4f", what, beam_size, score)
-        self.writer.add_scalar(f"BLEU4_{what}", score, max(self.adv_epoch, 0))
+
+    def evaluate_cider(self, what="val", beam_size=3, max_caption_len=None, batch_size=None):
+        """CIDEr-D of the beam-search captions of ``evaluate`` (the same images, grouping and caption length rule), scored on the GPU
+        (gic_cider_d) with document frequencies from the evaluated split's references (the coco-caption convention).  Logs the score
+        and writes the scalar ``CIDErD_<what>``."""
+        from .cider import CiderD, RefBatch
+        from .tasks import ImageGroups
+        if what not in self._cider:
+            ds = self.dev_dataset if what == "val" else self.train_dataset
+            self._cider[what] = CiderD(ImageGroups(ds).references(), self.args.vocab_size, self.args.device)
+        scorer = self._cider[what]
+        scores = []
+        for ids, lengths, caps in self._beam_decode(what, beam_size, max_caption_len, batch_size):
+            scores.append(scorer.score(ids, lengths, RefBatch.pack(caps).to(self.args.device)))
+        score = float(torch.cat(scores).double().mean()) if scores else 0.0
+        self.log.info("[EVAL] CIDEr-D (%s, beam %d): %.4f", what, beam_size, score)
+        self.writer.add_scalar(f"CIDErD_{what}", score, max(self.adv_epoch, 0))
         return score
 
     def _eval_groups(self, what):
         """The evaluation's dataset and its captions grouped by image (``filepath`` + ``filename`` for COCO_data, one image per item
         otherwise): (ds, groups {key: [item]}, keys in first-seen order, is_coco, a COCO entry's token ids as __getitem__ forms them
         (no image load), ids -> words with <S>, <E>, <PAD> stripped)."""
-        from .tasks import COCO_data, SPECIALS
+        from .tasks import COCO_data, SPECIALS, group_by_image
         ds = self.dev_dataset if what == "val" else self.train_dataset
-        groups, order = {}, []
-        for i in range(len(ds)):
-            if isinstance(ds, COCO_data):
-                e = ds.captions[i]
-                key = (e["filepath"], e["filename"])
-            else:
-                key = i
-            if key not in groups:
-                groups[key] = []
-                order.append(key)
-            groups[key].append(i)
+        groups, order = group_by_image(ds)
         coco = isinstance(ds, COCO_data)
         unk = ds.word_to_index.get("<UNK>", 3)
         coco_ids = lambda e: [t if isinstance(t, int) else ds.word_to_index.get(t, unk) for t in e["tokens"]]   # noqa: E731

@@ -642,6 +642,32 @@ int gic_xent(const void* logits, int dtype, int64_t rows, int32_t V, const int64
 int gic_rollout_rewards(const float* mc_logits, const float* full_logits, float* rewards, int B, int L, int N, int R, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CIDEr-D (Vedantam et al. 2015, the coco-caption CiderScorer; no reference counterpart) of token-id captions, for SCST rewards and
+ * evaluation.  A caption's tokens are its first `len` ids with <PAD> = 0, <S> = 1 and <E> = 2 removed.  For
+ * n = 1..4, vec_n[g] = count(g) * idf(g), idf(g) = log N - log max(1, df(g)) from the document-frequency table (keys / idf, built on the
+ * host from a reference corpus of N images; an n-gram absent from it has idf = log_n); length = the caption's number of bigrams;
+ * sim_n(c, r) = sum_g min(vec_n^c[g], vec_n^r[g]) * vec_n^r[g] / (|vec_n^c| |vec_n^r|) (the division only when both norms are non-zero)
+ * * exp(-(len_c - len_r)^2 / 72); score(c) = 10 * mean_n(sum_{r in R} sim_n(c, r)) / |R| (0 for an image without references).
+ *   table    keys uint64 [K] sorted ascending, unique: bits 60..61 = n - 1, then the n token ids (15 bits each) from bit 45 down, the
+ *            unused slots zero; idf f32 [K]; log_n = log N.
+ *   cand     cand_ids int64 [n_cand, ld_cand] (row c: Lc ids), cand_len int32 [n_cand], cand_img int32 [n_cand] in [0, B) (a
+ *            candidate outside it scores NaN); scores f32 [n_cand].
+ *   refs     ref_ids int64 [n_ref, ld_ref] (row: Lr ids), ref_len int32 [n_ref]; image b owns rows ref_off[b] .. ref_off[b+1]
+ *            (ref_off int32 [B+1]) and at most max_refs of them (the host knows the largest count; an image with more, or offsets
+ *            outside [0, n_ref], scores NaN and nothing past them is read).  Lengths are clamped to [0, Lc] / [0, Lr].
+ * Limits: Lc, Lr <= GIC_CIDER_MAX_LEN, max_refs <= GIC_CIDER_MAX_REFS and V <= GIC_CIDER_MAX_VOCAB (the 15-bit keys) -- beyond them
+ * GIC_STATUS_UNSUPPORTED; negative sizes, V < 1, a stride below its row length, a log_n that is negative or not finite, B = 0 with
+ * candidates and NULL pointers GIC_STATUS_INVALID_ARG; all checked before any launch.  No workspace.  Fixed-order sums and no atomics:
+ * two calls give the same bits, and the deterministic mode accepts every call. */
+#define GIC_CIDER_MAX_LEN 64
+#define GIC_CIDER_MAX_REFS 32
+#define GIC_CIDER_MAX_VOCAB 32768
+int gic_cider_d(const int64_t* cand_ids, int64_t ld_cand, const int32_t* cand_len, const int32_t* cand_img, int32_t n_cand, int32_t Lc,
+                const int64_t* ref_ids, int64_t ld_ref, const int32_t* ref_len, const int32_t* ref_off, int32_t n_ref, int32_t Lr,
+                int32_t B, int32_t max_refs, const uint64_t* keys, const float* idf, int64_t K, float log_n, int32_t V, float* scores,
+                void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * optimize(): clip_grad_norm_ + Adam (src/training.py:194-199, :24-26) over a flat f32 parameter arena.
  * step_count: device int64 (incremented here); norm_out: device f32 (pre-clip global L2 norm);
  * partials: device f32 scratch [gic_clip_adam_partials(n)].  Hyper-parameters are doubles: torch.optim.Adam forms
