@@ -58,6 +58,11 @@ class DecoderBeamOpts(C.Structure):
                 ("h0", c_void_p), ("c0", c_void_p)]
 
 
+class DiverseBeamOpts(C.Structure):
+    """gic_diverse_beam_opts (gic_decoder_diverse_beam_search, gic_attn_diverse_beam_search)."""
+    _fields_ = [("beam", DecoderBeamOpts), ("groups", C.c_int32), ("diversity", C.c_float)]
+
+
 class SampleOpts(C.Structure):
     """gic_sample_opts (gic_sample_logits, gic_decoder_sample_captions, gic_attn_sample_captions)."""
     _fields_ = [("num_samples", C.c_int32), ("top_k", C.c_int32), ("top_p", C.c_float), ("temperature", C.c_float),
@@ -171,6 +176,10 @@ _SIGNATURES = {
     "gic_attn_beam_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int32, c_void_p]),
     "gic_attn_beam_search": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(DecoderBeamOpts), c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_decoder_diverse_beam_search": (C.c_int, [_P(DecoderDims), _P(DecoderParams), _P(DecoderShadow), _P(DiverseBeamOpts), c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_attn_diverse_beam_search": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(DiverseBeamOpts), c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_sample_logits": (C.c_int, [c_void_p, C.c_int64, C.c_int32, C.c_int32, _P(SampleOpts), c_void_p, C.c_uint64, C.c_uint64, c_void_p,
                                     c_void_p, c_void_p, c_void_p]),
     "gic_decoder_sample_ws_bytes": (C.c_int, [_P(DecoderDims), C.c_int32, c_void_p]),

@@ -107,6 +107,10 @@ _NATIVE = [
     ("--scst-baseline", str, "greedy", "SCST baseline: greedy = the CIDEr-D of the greedy caption; mean = the mean reward of the image's "
                                        "other samples (needs --scst-samples >= 2)", {"choices": ["greedy", "mean"]}),
     ("--scst-lr", float, 5e-5, "learning rate of SCST (its own clip + Adam over the generator's parameters)"),
+    ("--eval-diverse-beam-size", int, 0, "beam size of the diverse-beam-search diversity evaluation (GANInstructor.evaluate_diverse_beam: "
+                                         "BLEU-4, mBLEU-4, distinct-1/2, vocabulary) after each adversarial epoch's validation; 0 = off"),
+    ("--eval-diverse-groups", int, 2, "groups of that evaluation's diverse beam search (must divide --eval-diverse-beam-size)"),
+    ("--eval-diversity-strength", float, 0.5, "Hamming diversity penalty (lambda >= 0) of that evaluation's diverse beam search"),
     ("--eval-cider-beam-size", int, 0, "beam size of the CIDEr-D evaluation (GANInstructor.evaluate_cider) after each adversarial epoch's "
                                        "validation; 0 = off"),
 ]

@@ -106,6 +106,8 @@ struct BeamSelectArgs {
   const float* part_m; const float* part_s; const float* part_v; const int* part_i;
   float* score; int* fin; int* len; int* tok; int* par; int* htok; int* hpar; int* last; int* done; int* count;
   int nblk, rows, t, eos, pad;
+  int groups;                        // diverse beam search: G groups of K / G beams (1 = plain beam search, diversity unused)
+  float diversity;                   // lambda >= 0: the Hamming penalty of a token per earlier group's selection of it this step
 };
 
 // f(std::integral_constant<int, K>()) for the beam width or sample count K = 1..kBeamMax (callers check the range first)
@@ -124,10 +126,11 @@ int with_beam_k(int K, F&& f) {
 }
 
 // beam.hip.  beam_init: slot 0 of every layer into the K rows of each image (layer 0's input row [0, din0): features in [0, E), zeros
-// behind; h part = h0 or 0; c = c0 or 0; h0 / c0 f32 [NL, B, H] or null) and the state at t = 0: only beam 0 live (all_live: every row
-// live, the sampler), par[r] = r
+// behind; h part = h0 or 0; c = c0 or 0; h0 / c0 f32 [NL, B, H] or null) and the state at t = 0: beam j live (score 0) where
+// j % live_stride == 0, the others at -inf (live_stride K: beam search, K / G: the first beam of each diverse group, 1: the sampler),
+// par[r] = r
 int beam_init(const BeamLayerPtrs& slot0, int NL, int din0, int E, int H, int B, int K, int dtype, const float* features, const float* h0,
-              const float* c0, const BeamState& s, hipStream_t stream, bool all_live = false);
+              const float* c0, const BeamState& s, hipStream_t stream, int live_stride);
 // the generic path's GEMM input rows of t > 0: [x | h] of every layer from row par[r] of the previous output slot, x of layer 0 =
 // embed[tok[r]]; c likewise
 int beam_gather(const BeamLayerPtrs& in, const BeamLayerPtrs& out, int NL, int E, int H, int rows, int dtype, const float* embed, const int* tok,
@@ -135,11 +138,13 @@ int beam_gather(const BeamLayerPtrs& in, const BeamLayerPtrs& out, int NL, int E
 // the generic path's tile partials of f32 logits [rows, V] (the fused path's are vocab_step_beam's epilogue)
 int beam_tile_topk(const float* logits, int rows, int V, int K, float* part_m, float* part_s, float* part_v, int* part_i, const int* stop,
                    int stop_at, hipStream_t stream);
+// a.groups == 1: plain beam search; else diverse beam search (the caller checks that a.groups divides K)
 int beam_select(const BeamSelectArgs& a, int K, int B, hipStream_t stream);
-// ids / scores / lengths of the K beams of each image, best first; anc: null or i32 [B, K, L], the row (image * K + beam) of step t whose
-// logits gave the t-th token of each returned beam (-1 past the last step that ran)
-int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length_penalty, int64_t* ids, float* scores, int32_t* lengths,
-                  int32_t* anc, hipStream_t stream);
+// ids / scores / lengths of the K beams of each image, sorted within each group of `width` consecutive beams (width K: one sort of
+// all K, beam search; K / G: the diverse groups, group g in slots g * width ..), best first; anc: null or i32 [B, K, L], the row
+// (image * K + beam) of step t whose logits gave the t-th token of each returned beam (-1 past the last step that ran)
+int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length_penalty, int width, int64_t* ids, float* scores,
+                  int32_t* lengths, int32_t* anc, hipStream_t stream);
 
 // attn_beam.hip: the attention kernels of one step (K rows per image, row r reads hp of row par[r]; the sampler's par[r] = r)
 struct AttnBeamArgs {

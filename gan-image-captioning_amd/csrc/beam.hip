@@ -10,11 +10,12 @@ namespace {
 using LayerPtrs = BeamLayerPtrs;
 
 // slot 0 of every layer: x part of layer 0 = the image's features (zeros in [E, din0)), h part = h0 (or 0), c = c0 (or 0); beam state at
-// t = 0: only beam 0 live (the others at -inf, so the k beams never copy one hypothesis)
+// t = 0: beam j live where j % live_stride == 0 (the others at -inf, so the beams of a search, or of a diverse group, never copy one
+// hypothesis)
 template <typename TA>
 __global__ __launch_bounds__(256) void beam_init_kernel(LayerPtrs p, int NL, int din0, int E, int H, int B, int K, const float* __restrict__ features,
                                                         const float* __restrict__ h0, const float* __restrict__ c0, float* score, int* fin, int* len,
-                                                        int* tok, int* par, int* last, int* done, int* count, int all_live) {
+                                                        int* tok, int* par, int* last, int* done, int* count, int live_stride) {
   const int r = blockIdx.x, img = r / K, tid = threadIdx.x;
   for (int l = 0; l < NL; ++l) {
     const int din = l == 0 ? din0 : H;
@@ -28,7 +29,7 @@ __global__ __launch_bounds__(256) void beam_init_kernel(LayerPtrs p, int NL, int
     }
   }
   if (tid == 0) {
-    score[r] = all_live || r % K == 0 ? 0.f : -INFINITY;
+    score[r] = (r % K) % live_stride == 0 ? 0.f : -INFINITY;
     fin[r] = 0; len[r] = 0; tok[r] = 0; par[r] = r;
     if (r % K == 0) { last[img] = -1; done[img] = 0; }
     if (r == 0) *count = 0;
@@ -83,8 +84,12 @@ __device__ __forceinline__ bool sel_better(bool va, float a, int la, bool vb, fl
   return va && (!vb || a > b || (a == b && la < lb));
 }
 
-// one workgroup per image: wave w < K merges row (image, w)'s tile partials into its logsumexp and top-K; wave 0 selects
-template <int K>
+// one workgroup per image: wave w < K merges row (image, w)'s tile partials into its logsumexp and top-K; wave 0 selects.  DIVERSE:
+// the G = a.groups groups of Kg = K / G beams select in order g = 0..G-1, each over the candidates of its own Kg parents (lane = local
+// parent * K + rank, at most Kg * K <= 64 lanes), ranked by score + logp - diversity * h(token), where h counts the earlier groups' picks
+// of the token from live parents at this step; the kept score is the raw score + logp.  Plain beam search (G = 1) is the other
+// instantiation, so its selection is the one it always was
+template <int K, bool DIVERSE>
 __global__ __launch_bounds__(512) void beam_select_kernel(const SelectArgs a) {
   __shared__ float cv[K][K], lse_s[K];
   __shared__ int ci[K][K];
@@ -116,36 +121,80 @@ __global__ __launch_bounds__(512) void beam_select_kernel(const SelectArgs a) {
   }
   __syncthreads();
   if (w != 0) return;
-  // ---- candidates: lane = p * K + q (parent beam p, rank q in its row)
-  const int p = lane / K, q = lane % K;
-  const bool in = lane < K * K;
-  const int pr = img * K + (in ? p : 0);
-  const bool pfin = a.fin[pr] != 0;
-  const float ps = a.score[pr];
-  const int plen = a.len[pr];
-  bool valid = in && (!pfin || q == 0);
-  float cs = -INFINITY;
-  int ct = a.pad;
-  if (valid) {
-    if (pfin) cs = ps;
-    else { cs = ps + (cv[p][q] - lse_s[p]); ct = ci[p][q]; }
-  }
-  // ---- K rounds of a wave argmax with exclusion; lane n keeps the n-th winner
   float my_s = 0.f; int my_t = 0, my_p = 0, my_fin = 0, my_len = 0;
-#pragma unroll
-  for (int n = 0; n < K; ++n) {
-    bool bv = valid; float bs = cs; int bl = lane;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const bool ov = __shfl_xor((int)bv, o, 64) != 0;
-      const float os = __shfl_xor(bs, o, 64);
-      const int ol = __shfl_xor(bl, o, 64);
-      if (sel_better(ov, os, ol, bv, bs, bl)) { bv = ov; bs = os; bl = ol; }
+  if constexpr (!DIVERSE) {
+    // ---- candidates: lane = p * K + q (parent beam p, rank q in its row)
+    const int p = lane / K, q = lane % K;
+    const bool in = lane < K * K;
+    const int pr = img * K + (in ? p : 0);
+    const bool pfin = a.fin[pr] != 0;
+    const float ps = a.score[pr];
+    const int plen = a.len[pr];
+    bool valid = in && (!pfin || q == 0);
+    float cs = -INFINITY;
+    int ct = a.pad;
+    if (valid) {
+      if (pfin) cs = ps;
+      else { cs = ps + (cv[p][q] - lse_s[p]); ct = ci[p][q]; }
     }
-    const float ws = __shfl(cs, bl, 64);
-    const int wt = __shfl(ct, bl, 64), wp = __shfl(p, bl, 64), wf = __shfl((int)pfin, bl, 64), wlen = __shfl(plen, bl, 64);
-    if (lane == bl) valid = false;
-    if (lane == n) { my_s = ws; my_t = wt; my_p = wp; my_fin = wf || wt == a.eos; my_len = wf ? wlen : a.t + 1; }
+    // ---- K rounds of a wave argmax with exclusion; lane n keeps the n-th winner
+#pragma unroll
+    for (int n = 0; n < K; ++n) {
+      bool bv = valid; float bs = cs; int bl = lane;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const bool ov = __shfl_xor((int)bv, o, 64) != 0;
+        const float os = __shfl_xor(bs, o, 64);
+        const int ol = __shfl_xor(bl, o, 64);
+        if (sel_better(ov, os, ol, bv, bs, bl)) { bv = ov; bs = os; bl = ol; }
+      }
+      const float ws = __shfl(cs, bl, 64);
+      const int wt = __shfl(ct, bl, 64), wp = __shfl(p, bl, 64), wf = __shfl((int)pfin, bl, 64), wlen = __shfl(plen, bl, 64);
+      if (lane == bl) valid = false;
+      if (lane == n) { my_s = ws; my_t = wt; my_p = wp; my_fin = wf || wt == a.eos; my_len = wf ? wlen : a.t + 1; }
+    }
+  } else {
+    const int Kg = K / a.groups;
+    int my_h = -1;                                         // this lane's kept token if it counts toward h (its parent was live), else -1
+    for (int g = 0; g < a.groups; ++g) {
+      // ---- the group's candidates: lane = pl * K + q (parent beam p = g * Kg + pl, rank q in its row)
+      const int pl = lane / K, q = lane % K, p = g * Kg + pl;
+      const bool in = lane < Kg * K;
+      const int pr = img * K + (in ? p : 0);
+      const bool pfin = a.fin[pr] != 0;
+      const float ps = a.score[pr];
+      const int plen = a.len[pr];
+      bool valid = in && (!pfin || q == 0);
+      float cs = -INFINITY;
+      int ct = a.pad;
+      if (valid) {
+        if (pfin) cs = ps;
+        else { cs = ps + (cv[p][q] - lse_s[p]); ct = ci[p][q]; }
+      }
+      // h: the picks of the groups before g (lanes 0 .. g * Kg - 1 hold them) that carry this token; a finished parent's pad proposal
+      // is neither counted nor penalised
+      int h = 0;
+      for (int j = 0; j < g * Kg; ++j) h += __shfl(my_h, j, 64) == ct ? 1 : 0;
+      const float key = valid && !pfin ? cs - a.diversity * (float)h : cs;
+      // ---- Kg rounds of a wave argmax with exclusion over the keys; lane g * Kg + n keeps the n-th winner
+      for (int n = 0; n < Kg; ++n) {
+        bool bv = valid; float bs = key; int bl = lane;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const bool ov = __shfl_xor((int)bv, o, 64) != 0;
+          const float os = __shfl_xor(bs, o, 64);
+          const int ol = __shfl_xor(bl, o, 64);
+          if (sel_better(ov, os, ol, bv, bs, bl)) { bv = ov; bs = os; bl = ol; }
+        }
+        const float ws = __shfl(cs, bl, 64);
+        const int wt = __shfl(ct, bl, 64), wp = __shfl(p, bl, 64), wf = __shfl((int)pfin, bl, 64), wlen = __shfl(plen, bl, 64);
+        if (lane == bl) valid = false;
+        if (lane == g * Kg + n) {
+          my_s = ws; my_t = wt; my_p = wp; my_fin = wf || wt == a.eos; my_len = wf ? wlen : a.t + 1;
+          my_h = wf ? -1 : wt;
+        }
+      }
+    }
   }
   const int all_fin = __all(lane >= K || my_fin);
   if (lane < K) {
@@ -160,10 +209,11 @@ __global__ __launch_bounds__(512) void beam_select_kernel(const SelectArgs a) {
   }
 }
 
-// one workgroup per image: walk each beam's parent pointers back through the history, sort the K beams by score / length^alpha
-// (descending, ties to the lower beam index), write ids [B, K, L] (pad after <E> and after the last step run), scores, lengths
+// one workgroup per image: walk each beam's parent pointers back through the history, sort each group of W consecutive beams by
+// score / length^alpha (descending, ties to the lower beam index; W = K: one group) into the group's slots, write ids [B, K, L] (pad
+// after <E> and after the last step run), scores, lengths
 __global__ __launch_bounds__(64) void beam_finalize_kernel(const float* __restrict__ score, const int* __restrict__ len, const int* __restrict__ htok,
-                                                           const int* __restrict__ hpar, const int* __restrict__ last, int K, int L, int rows, int pad,
+                                                           const int* __restrict__ hpar, const int* __restrict__ last, int K, int W, int L, int rows, int pad,
                                                            float alpha, int64_t* __restrict__ ids, float* __restrict__ scores_out,
                                                            int32_t* __restrict__ lengths_out, int32_t* __restrict__ anc) {
   extern __shared__ int hs[];                              // [L][K] tokens, then [L][K] parent beams
@@ -176,10 +226,10 @@ __global__ __launch_bounds__(64) void beam_finalize_kernel(const float* __restri
     hs[L * K + i] = hpar[(long)t * rows + img * K + j];
   }
   if (tid < K) {
-    const int r = img * K + tid;
+    const int r = img * K + tid, g0 = tid - tid % W;
     const float ns = score[r] / powf((float)len[r], alpha);
-    int rank = 0;
-    for (int i = 0; i < K; ++i) {
+    int rank = g0;
+    for (int i = g0; i < g0 + W; ++i) {
       const float o = score[img * K + i] / powf((float)len[img * K + i], alpha);
       rank += (o > ns || (o == ns && i < tid)) ? 1 : 0;
     }
@@ -211,7 +261,8 @@ __global__ __launch_bounds__(64) void beam_finalize_kernel(const float* __restri
 
 int beam_select(const SelectArgs& s, int K, int B, hipStream_t stream) {
   return with_beam_k(K, [&](auto k) -> int {
-    hipLaunchKernelGGL((beam_select_kernel<k>), dim3(B), dim3(512), 0, stream, s);
+    if (s.groups > 1) hipLaunchKernelGGL((beam_select_kernel<k, true>), dim3(B), dim3(512), 0, stream, s);
+    else hipLaunchKernelGGL((beam_select_kernel<k, false>), dim3(B), dim3(512), 0, stream, s);
     GIC_CHECK_LAUNCH("beam_select");
     return GIC_OK;
   });
@@ -239,24 +290,24 @@ int beam_tile_topk(const float* logits, int rows, int V, int K, float* part_m, f
 }
 
 int beam_init(const BeamLayerPtrs& slot0, int NL, int din0, int E, int H, int B, int K, int dtype, const float* features, const float* h0,
-              const float* c0, const BeamState& s, hipStream_t stream, bool all_live) {
+              const float* c0, const BeamState& s, hipStream_t stream, int live_stride) {
   const dim3 grid((unsigned)(B * K));
   if (dtype == DT_F32)
     hipLaunchKernelGGL((beam_init_kernel<float>), grid, dim3(256), 0, stream, slot0, NL, din0, E, H, B, K, features, h0, c0, s.score, s.fin,
-                       s.len, s.tok, s.par, s.last, s.done, s.count, (int)all_live);
+                       s.len, s.tok, s.par, s.last, s.done, s.count, live_stride);
   else
     hipLaunchKernelGGL((beam_init_kernel<bf16_t>), grid, dim3(256), 0, stream, slot0, NL, din0, E, H, B, K, features, h0, c0, s.score, s.fin,
-                       s.len, s.tok, s.par, s.last, s.done, s.count, (int)all_live);
+                       s.len, s.tok, s.par, s.last, s.done, s.count, live_stride);
   GIC_CHECK_LAUNCH("beam_init");
   return GIC_OK;
 }
 
-int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length_penalty, int64_t* ids, float* scores, int32_t* lengths,
-                  int32_t* anc, hipStream_t stream) {
+int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length_penalty, int width, int64_t* ids, float* scores,
+                  int32_t* lengths, int32_t* anc, hipStream_t stream) {
   const size_t lds = (size_t)2 * L * K * sizeof(int);
   static LdsGrant gfin;
   GIC_CHECK_ARG(grant_lds(beam_finalize_kernel, lds, gfin), "beam_finalize: cannot reserve %zu bytes of LDS", lds);
-  hipLaunchKernelGGL(beam_finalize_kernel, dim3((unsigned)B), dim3(64), lds, stream, s.score, s.len, s.htok, s.hpar, s.last, K, L, B * K, pad,
+  hipLaunchKernelGGL(beam_finalize_kernel, dim3((unsigned)B), dim3(64), lds, stream, s.score, s.len, s.htok, s.hpar, s.last, K, width, L, B * K, pad,
                      length_penalty, ids, scores, lengths, anc);
   GIC_CHECK_LAUNCH("beam_finalize");
   return GIC_OK;

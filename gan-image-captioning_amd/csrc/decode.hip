@@ -1,12 +1,14 @@
-// Caption decode (gicap.h gic_decoder_beam_search, gic_attn_beam_search, gic_decoder_sample_captions, gic_attn_sample_captions and their
-// *_ws_bytes): one step loop for both decoders and both heads.  Rows = B * K (row r = image r / K, beam or sample r % K).
+// Caption decode (gicap.h gic_decoder_beam_search, gic_attn_beam_search, gic_decoder_diverse_beam_search, gic_attn_diverse_beam_search,
+// gic_decoder_sample_captions, gic_attn_sample_captions and their *_ws_bytes): one step loop for both decoders and both heads.
+// Rows = B * K (row r = image r / K, beam or sample r % K).
 //
 // A search is a recurrence and a head, chosen at the entry point:
 //   LstmFused    lstm_step's beam form per layer: h / c read from row parent[r], layer 0's x = embed[token[r]]
 //   LstmGeneric  where the fused kernels decline the shapes: beam_gather, then per layer the library GEMM and lstm_pointwise_fwd
 //   Attn         the fproj GEMM once; per step the hp GEMM, attn_beam_step (attn_beam.hip) and lstm_step's beam form
 // and
-//   BeamHead     vocab_step_beam (generic path: the GEMM into logits + beam_tile_topk), beam_select; beam_finalize (beam.h)
+//   BeamHead     vocab_step_beam (generic path: the GEMM into logits + beam_tile_topk), beam_select; beam_finalize (beam.h); with
+//                G > 1 groups the diverse search: the same kernels, beam_select's group-sequential form and a per-group final order
 //   SampleHead   vocab_step_logits (generic path: the GEMM into logits), sample_step; sample_finalize (sample.hip)
 // A sampled row is its own parent: beam_init sets par[r] = r and only beam_select writes it again, so both heads run the same
 // recurrences.  The beam head stops once B images have finished, the sampler once B * K rows have: from then on the kernels of every
@@ -25,6 +27,8 @@
 //   part_m, part_s f32 [rows][nblk]; part_v f32, part_i i32 [rows][nblk][K]          beam: tile partials (nblk = ceil(V / 64))
 //   score f32, fin / len / tok / par i32 [rows]; hist_tok i32 [L][rows]; hist_par i32 [L][rows] (beam); anc i32 [B][K][L] (attention
 //   beam); last / done i32 [B]; count i32
+#include <cfloat>
+
 #include "../../include/gicap.h"
 #include "beam.h"
 #include "kernels.h"
@@ -219,6 +223,9 @@ struct BeamHead {
   const gic_decoder_beam_opts* o;
   int64_t* ids; float* scores; int32_t* lengths;
   float* alphas;                 // attention: f32 [B, K, L, P] or null
+  int groups = 1;                // diverse beam search: G groups of K / G beams (1: beam search)
+  float diversity = 0.f;         // and its Hamming penalty lambda
+  int live_stride(const DecodeDims& d) const { return d.K / groups; }
   int vocab(VocabStepArgs& v, const Search& s) const {
     v.part_m = s.w.pm; v.part_s = s.w.ps; v.part_v = s.w.pv; v.part_i = s.w.pi; v.nblk = s.d.nblk;
     return vocab_step_beam(v, s.d.K, s.d.dt, s.stream);
@@ -229,12 +236,13 @@ struct BeamHead {
   int select(const Search& s, int t) const {
     const BeamState& st = s.w.st;
     const BeamSelectArgs a{s.w.pm, s.w.ps, s.w.pv, s.w.pi, st.score, st.fin, st.len, st.tok, st.par, st.htok, st.hpar, st.last, st.done,
-                           st.count, s.d.nblk, s.d.rows, t, o->eos_id, o->pad_id};
+                           st.count, s.d.nblk, s.d.rows, t, o->eos_id, o->pad_id, groups, diversity};
     return beam_select(a, s.d.K, s.d.B, s.stream);
   }
   int finish(const Search& s) const {
     const DecodeDims& d = s.d;
-    GIC_PROPAGATE(beam_finalize(s.w.st, d.B, d.K, d.L, o->pad_id, o->length_penalty, ids, scores, lengths, alphas ? s.w.anc : nullptr, s.stream));
+    GIC_PROPAGATE(beam_finalize(s.w.st, d.B, d.K, d.L, o->pad_id, o->length_penalty, d.K / groups, ids, scores, lengths,
+                                alphas ? s.w.anc : nullptr, s.stream));
     return alphas ? attn_beam_alphas(s.w.ahist, s.w.anc, lengths, d.rows, d.L, d.P, alphas, s.stream) : GIC_OK;
   }
 };
@@ -244,6 +252,7 @@ struct SampleHead {
   const gic_sample_opts* o;
   const float* noise_u; uint64_t seed;
   int64_t* ids; float* scores; int32_t* lengths;
+  int live_stride(const DecodeDims&) const { return 1; }        // every row live from step 0
   int vocab(VocabStepArgs& v, const Search& s) const {
     v.logits = s.w.logits; v.ld_logits = s.d.V;
     return vocab_step_logits(v, s.d.dt, s.stream);
@@ -259,7 +268,7 @@ int decode(const DecodeDims& d, const Rec& rec, const Head& head, void* ws, cons
            void* stream) {
   const DecodeBufs w = decode_layout(d, Head::kBeam, ws);
   const Search s{d, w, Head::kBeam ? d.B : d.rows, (hipStream_t)stream};
-  GIC_PROPAGATE(beam_init(w.slot[0], d.NL, d.din(0), d.E, d.H, d.B, d.K, d.dt, features, h0, c0, w.st, s.stream, !Head::kBeam));
+  GIC_PROPAGATE(beam_init(w.slot[0], d.NL, d.din(0), d.E, d.H, d.B, d.K, d.dt, features, h0, c0, w.st, s.stream, head.live_stride(d)));
   GIC_PROPAGATE(rec.begin(s));
   const int top = d.NL - 1;
   for (int t = 0; t < d.L; ++t) {
@@ -313,6 +322,14 @@ int check_beam_opts(const gic_decoder_beam_opts* o, int V, const char* who) {
   return GIC_OK;
 }
 
+int check_diverse_opts(const gic_diverse_beam_opts* o, int V, const char* who) {
+  GIC_PROPAGATE(check_beam_opts(&o->beam, V, who));
+  GIC_CHECK_ARG(o->groups >= 1 && o->beam.beam % o->groups == 0, "%s: groups must be >= 1 and divide the beam size %d, got %d", who,
+                o->beam.beam, o->groups);
+  GIC_CHECK_ARG(o->diversity >= 0.f && o->diversity <= FLT_MAX, "%s: diversity must be finite and >= 0", who);
+  return GIC_OK;
+}
+
 }  // namespace
 }  // namespace gic
 
@@ -356,6 +373,33 @@ int gic_attn_beam_search(const gic_attn_dims* dims, const gic_attn_params* P, co
   GIC_PROPAGATE(check_beam_opts(o, d.V, "attn_beam_search"));
   GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "attn_beam_search: the workspace must be 256-byte aligned");
   return decode(d, Attn{P, S, fmap, alphas != nullptr}, BeamHead{o, ids, scores, lengths, alphas}, ws, features, o->h0, o->c0, stream);
+}
+
+// the diverse searches share the beam searches' workspace: gic_*_beam_ws_bytes for the same beam size
+int gic_decoder_diverse_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
+                                    const gic_diverse_beam_opts* o, void* ws, const float* features, int64_t* ids, float* scores,
+                                    int32_t* lengths, void* stream) {
+  GIC_CHECK_ARG(o, "decoder_diverse_beam_search: null options");
+  DecodeDims d;
+  GIC_PROPAGATE(lstm_dims(dims, o->beam.beam, true, "decoder_diverse_beam", d));
+  GIC_PROPAGATE(check_lstm_args(P, S, d.NL, ws && features && ids && scores && lengths, "decoder_diverse_beam_search"));
+  GIC_PROPAGATE(check_diverse_opts(o, d.V, "decoder_diverse_beam_search"));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "decoder_diverse_beam_search: the workspace must be 256-byte aligned");
+  return lstm_decode(d, P, S, BeamHead{&o->beam, ids, scores, lengths, nullptr, o->groups, o->diversity}, ws, features, o->beam.h0,
+                     o->beam.c0, stream);
+}
+
+int gic_attn_diverse_beam_search(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_diverse_beam_opts* o,
+                                 void* ws, const float* features, const void* fmap, int64_t* ids, float* scores, int32_t* lengths,
+                                 float* alphas, void* stream) {
+  GIC_CHECK_ARG(o, "attn_diverse_beam_search: null options");
+  DecodeDims d;
+  GIC_PROPAGATE(attn_dims(dims, o->beam.beam, true, "attn_diverse_beam", d));
+  GIC_PROPAGATE(check_attn_args(P, S, ws && features && fmap && ids && scores && lengths, "attn_diverse_beam_search"));
+  GIC_PROPAGATE(check_diverse_opts(o, d.V, "attn_diverse_beam_search"));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "attn_diverse_beam_search: the workspace must be 256-byte aligned");
+  return decode(d, Attn{P, S, fmap, alphas != nullptr}, BeamHead{&o->beam, ids, scores, lengths, alphas, o->groups, o->diversity}, ws,
+                features, o->beam.h0, o->beam.c0, stream);
 }
 
 int gic_decoder_sample_ws_bytes(const gic_decoder_dims* dims, int32_t num_samples, uint64_t* out) {

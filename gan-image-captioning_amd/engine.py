@@ -236,6 +236,13 @@ def _decode_outputs(B: int, n: int, Lc: int, dev):
             torch.empty(B, n, device=dev, dtype=torch.int32))
 
 
+def _diverse_opts(beam_opts, groups: int, diversity: float):
+    """gic_diverse_beam_opts around filled gic_decoder_beam_opts (a copy: the library reads h0 / c0 from it)."""
+    o = L.DiverseBeamOpts()
+    o.beam, o.groups, o.diversity = beam_opts, int(groups), float(diversity)
+    return o
+
+
 def _sample_noise(noise_u: Optional[torch.Tensor], Lc: int, rows: int, V: int) -> Optional[torch.Tensor]:
     if noise_u is None:
         return None
@@ -649,6 +656,16 @@ class DecoderEngine:
                     length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None):
         """gic_decoder_beam_search: (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam]), beams best first.
         ``states`` = (h0, c0), each f32 [NL, B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned)."""
+        return self._beam(params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, None)
+
+    def diverse_beam_search(self, params, features: torch.Tensor, Lc: int, beam: int, groups: int, diversity: float, eos_id: int = 2,
+                            pad_id: int = 0, length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None):
+        """gic_decoder_diverse_beam_search: ``beam`` beams in ``groups`` groups (which must divide ``beam``) with the Hamming penalty
+        ``diversity``; (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam]) in group-major order, each group's
+        beams best first.  ``states`` and ``ws`` (beam_ws_bytes() for the same beam) as for beam_search."""
+        return self._beam(params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, (groups, diversity))
+
+    def _beam(self, params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, diverse):
         self.check_params(params)
         require_gpu(features)
         features = _decode_features(features, self.E)
@@ -660,9 +677,12 @@ class DecoderEngine:
         keep = self._states(opts, states, B)
         ids, scores, lengths = _decode_outputs(B, beam, Lc, dev)
         d = self.dims(B, Lc)
-        L.check(L.load().gic_decoder_beam_search(
-            C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws), ptr(features),
-            ptr(ids), ptr(scores), ptr(lengths), stream_ptr()), "gic_decoder_beam_search")
+        if diverse is None:
+            fn, name, o = L.load().gic_decoder_beam_search, "gic_decoder_beam_search", opts
+        else:
+            fn, name, o = L.load().gic_decoder_diverse_beam_search, "gic_decoder_diverse_beam_search", _diverse_opts(opts, *diverse)
+        L.check(fn(C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(o), ptr(ws), ptr(features),
+                   ptr(ids), ptr(scores), ptr(lengths), stream_ptr()), name)
         return ids, scores, lengths
 
     def sample_ws_bytes(self, B: int, Lc: int, num_samples: int) -> int:
@@ -1094,6 +1114,17 @@ class AttnDecoderEngine:
         """gic_attn_beam_search: (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam][, alphas f32 [B, beam, Lc, P]]),
         beams best first.  ``fmap`` [B, P, C] is cast to the compute dtype as in sample_fwd.  ``states`` = (h0, c0), each [1, B, H] or
         [B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned)."""
+        return self._beam(params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, None)
+
+    def diverse_beam_search(self, params, features, fmap, Lc: int, beam: int, groups: int, diversity: float, eos_id: int = 2,
+                            pad_id: int = 0, length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None,
+                            want_alphas: bool = False):
+        """gic_attn_diverse_beam_search: beam_search's outputs for ``beam`` beams in ``groups`` groups (which must divide ``beam``)
+        with the Hamming penalty ``diversity``, in group-major order, each group's beams best first."""
+        return self._beam(params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas,
+                          (groups, diversity))
+
+    def _beam(self, params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, diverse):
         self.check_params(params)
         require_gpu(features, fmap)
         features = _decode_features(features, self.E)
@@ -1106,9 +1137,12 @@ class AttnDecoderEngine:
         keep = self._states(opts, states, B)
         ids, scores, lengths = _decode_outputs(B, beam, Lc, dev)
         alphas = torch.empty(B, beam, Lc, self.P, device=dev, dtype=torch.float32) if want_alphas else None
-        L.check(L.load().gic_attn_beam_search(
-            C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
-            ptr(features), ptr(fmap), ptr(ids), ptr(scores), ptr(lengths), ptr(alphas), stream_ptr()), "gic_attn_beam_search")
+        if diverse is None:
+            fn, name, o = L.load().gic_attn_beam_search, "gic_attn_beam_search", opts
+        else:
+            fn, name, o = L.load().gic_attn_diverse_beam_search, "gic_attn_diverse_beam_search", _diverse_opts(opts, *diverse)
+        L.check(fn(C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(o), ptr(ws),
+                   ptr(features), ptr(fmap), ptr(ids), ptr(scores), ptr(lengths), ptr(alphas), stream_ptr()), name)
         if want_alphas:
             return ids, scores, lengths, alphas
         return ids, scores, lengths

@@ -203,15 +203,22 @@ class Decoder(nn.Module):
                                             max_length, features, *params)
         return pred, (h_n, c_n)
 
-    def beam_search(self, features, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None, return_beams=False):
+    def beam_search(self, features, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None, return_beams=False,
+                    beam_groups=1, diversity=0.0):
         """Beam-search caption decode (gicap.h gic_decoder_beam_search): token log-probabilities of sample(pretrain=True)'s
         distribution, ``beam_size`` (1..8) hypotheses per image, <E> = ``eos_id`` ends a beam, <PAD> (0) after it; final order by
         score / length**length_penalty.  Returns detached (ids int64 [B, L], scores f32 [B], lengths int32 [B]) of the best beam, or
-        all beams ([B, k, L], [B, k], [B, k]) with ``return_beams``.  ``max_caption_len`` None = args.max_seq_len."""
+        all beams ([B, k, L], [B, k], [B, k]) with ``return_beams``.  ``max_caption_len`` None = args.max_seq_len.  ``beam_groups``
+        > 1 or ``diversity`` > 0: diverse beam search (gic_decoder_diverse_beam_search), ``beam_groups`` groups of beam_size /
+        beam_groups beams with the Hamming penalty ``diversity``; the beams come in group-major order, the best beam is group 0's."""
         L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
         with torch.no_grad():
-            ids, scores, lengths = self.engine().beam_search([p.detach() for p in self.param_list()], features.detach().float(), L,
-                                                             int(beam_size), int(eos_id), 0, float(length_penalty), states=states)
+            args = ([p.detach() for p in self.param_list()], features.detach().float(), L, int(beam_size))
+            if int(beam_groups) == 1 and float(diversity) == 0.0:
+                ids, scores, lengths = self.engine().beam_search(*args, int(eos_id), 0, float(length_penalty), states=states)
+            else:
+                ids, scores, lengths = self.engine().diverse_beam_search(*args, int(beam_groups), float(diversity), int(eos_id), 0,
+                                                                         float(length_penalty), states=states)
         if return_beams:
             return ids, scores, lengths
         return ids[:, 0], scores[:, 0], lengths[:, 0]
@@ -326,20 +333,25 @@ class AttnDecoder(nn.Module):
                                                                    self.attn.w_h, self.attn.w_a]
 
     def beam_search(self, features, fmap=None, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None,
-                    return_beams=False, return_alphas=False):
+                    return_beams=False, return_alphas=False, beam_groups=1, diversity=0.0):
         """Beam-search caption decode with attention (gicap.h gic_attn_beam_search): Decoder.beam_search's search over the token
         log-probabilities of sample(features, fmap, pretrain=True).  ``fmap`` [B, P, C]: the trunk's last feature map
         (Encoder.forward_with_map).  Returns detached (ids int64 [B, L], scores f32 [B], lengths int32 [B]) of the best beam, or all beams
         ([B, k, L], [B, k], [B, k]) with ``return_beams``; ``return_alphas`` appends the attention weights with which each token was
-        produced, f32 [B, L, P] (all beams: [B, k, L, P]), zero past a beam's length.  ``states`` = (h0, c0), each [1, B, H]."""
+        produced, f32 [B, L, P] (all beams: [B, k, L, P]), zero past a beam's length.  ``states`` = (h0, c0), each [1, B, H].
+        ``beam_groups`` / ``diversity``: diverse beam search (gic_attn_diverse_beam_search) as in Decoder.beam_search."""
         if fmap is None:                # (checked before anything touches self: the LSTM decoder's call form has no map)
             raise NotImplementedError("the attention decoder's beam search needs the trunk's feature map: beam_search(features, fmap), "
                                       "or Generator.caption(images)")
         L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
         with torch.no_grad():
-            out = self.engine().beam_search([p.detach() for p in self.param_list()], features.detach().float(), fmap.detach(), L,
-                                            int(beam_size), int(eos_id), 0, float(length_penalty), states=states,
-                                            want_alphas=bool(return_alphas))
+            args = ([p.detach() for p in self.param_list()], features.detach().float(), fmap.detach(), L, int(beam_size))
+            if int(beam_groups) == 1 and float(diversity) == 0.0:
+                out = self.engine().beam_search(*args, int(eos_id), 0, float(length_penalty), states=states,
+                                                want_alphas=bool(return_alphas))
+            else:
+                out = self.engine().diverse_beam_search(*args, int(beam_groups), float(diversity), int(eos_id), 0, float(length_penalty),
+                                                        states=states, want_alphas=bool(return_alphas))
         if return_beams:
             return out
         return tuple(t[:, 0] for t in out)
@@ -568,16 +580,18 @@ class Generator(nn.Module):
         self.args = args
         self.init_params()
 
-    def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False, return_alphas=False):
+    def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False, return_alphas=False,
+                beam_groups=1, diversity=0.0):
         """Captions for ``images`` by beam search: features as the trainer forms them (training.py:66-68) -- the encoder in the
         module's current mode, or embed(<S>) with --conditional-gan 0 -- under no-grad, then ``decoder.beam_search``.  With
         --decoder attention the encoder also gives the feature map, and ``return_alphas`` appends the attention weights
-        (AttnDecoder.beam_search)."""
+        (AttnDecoder.beam_search).  ``beam_groups`` / ``diversity``: diverse beam search (Decoder.beam_search)."""
         with torch.no_grad():
             if isinstance(self.decoder, AttnDecoder):
                 features, fmap = self.encoder.forward_with_map(images)
                 return self.decoder.beam_search(features, fmap, beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id,
-                                                length_penalty=length_penalty, return_beams=return_beams, return_alphas=return_alphas)
+                                                length_penalty=length_penalty, return_beams=return_beams, return_alphas=return_alphas,
+                                                beam_groups=beam_groups, diversity=diversity)
             if return_alphas:
                 raise ValueError("attention weights exist for --decoder attention only")
             if self.args.conditional_gan:
@@ -585,7 +599,8 @@ class Generator(nn.Module):
             else:
                 features = self.decoder.embed(torch.ones(len(images), dtype=torch.long, device=images.device))
             return self.decoder.beam_search(features, beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id,
-                                            length_penalty=length_penalty, return_beams=return_beams)
+                                            length_penalty=length_penalty, return_beams=return_beams, beam_groups=beam_groups,
+                                            diversity=diversity)
 
     def sample_captions(self, images, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
                         noise_u=None):

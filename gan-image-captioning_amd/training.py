@@ -409,6 +409,10 @@ class GANInstructor:
                 self.evaluate_diversity("val", num_samples=int(self.args.eval_num_samples), top_k=int(getattr(self.args, "eval_top_k", 0)),
                                         top_p=float(getattr(self.args, "eval_top_p", 1.0)),
                                         temperature=float(getattr(self.args, "eval_sample_temperature", 1.0)))
+            if int(getattr(self.args, "eval_diverse_beam_size", 0)) > 0 and self.dist.rank == 0:
+                self.evaluate_diverse_beam("val", beam_size=int(self.args.eval_diverse_beam_size),
+                                           groups=int(getattr(self.args, "eval_diverse_groups", 2)),
+                                           diversity=float(getattr(self.args, "eval_diversity_strength", 0.5)))
             self.writer.flush()
 
     def evaluate(self, what="val", beam_size=3, max_caption_len=None, batch_size=None):
@@ -432,21 +436,29 @@ class GANInstructor:
         return score
 
     def _beam_decode(self, what, beam_size, max_caption_len=None, batch_size=None):
-        """The decode loop of ``evaluate`` / ``evaluate_cider``: every image of the split once (``_eval_groups``), the generator in eval
-        mode; yields per batch (ids [b, L] and lengths [b] on the device, the images' reference token lists)."""
+        """The decode of ``evaluate`` / ``evaluate_cider``: the best beam of each image (``_decode_batches``)."""
+        def decode(images, L, _):
+            ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L)
+            return ids, lengths
+        return self._decode_batches(what, decode, max_caption_len, batch_size)
+
+    def _decode_batches(self, what, decode, max_caption_len=None, batch_size=None):
+        """The decode loop of the evaluations: every image of the split once (``_eval_groups``), the generator in eval mode;
+        ``decode(images, L, batch_index)`` gives (ids, lengths) of the batch.  Yields per batch (ids and lengths on the device, the
+        images' reference token lists)."""
         ds, groups, order, coco, coco_ids, _ = self._eval_groups(what)
         was_training = self.gen.training
         self.gen.eval()
         bs = int(batch_size or getattr(self.args, "adv_eval_batch_size", 32))
         try:
-            for s in range(0, len(order), bs):
+            for bi, s in enumerate(range(0, len(order), bs)):
                 keys = order[s:s + bs]
                 firsts = [ds[groups[k][0]] for k in keys]          # one image load per image
                 images = torch.stack([it[0] for it in firsts]).to(self.args.device)
                 caps = [[coco_ids(ds.captions[j]) for j in groups[k]] if coco else [it[1]] for k, it in zip(keys, firsts)]
                 L = max_caption_len or max(int(getattr(self.args, "max_seq_len", 0) or 0),
                                            max(len(c) for group in caps for c in group) + 2)
-                ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L)
+                ids, lengths = decode(images, L, bi)
                 yield ids, lengths, caps
         finally:
             self.gen.train(was_training)
@@ -491,41 +503,54 @@ class GANInstructor:
         first sample against its references, ``mbleu4`` = each sample against the other samples of its image (lower = more diverse),
         ``distinct1`` / ``distinct2`` = unique / total uni- and bigrams over all samples, ``vocab`` = distinct words used.  Logs the
         values and writes the scalars ``<Name>_<what>`` (BLEU4S, mBLEU4, Distinct1, Distinct2, Vocab).  ``seed`` fixes the draws."""
-        from .utils import bleu_score, distinct_n, mbleu4
-        ds, groups, order, coco, coco_ids, words = self._eval_groups(what)
-        was_training = self.gen.training
-        self.gen.eval()
-        bs = int(batch_size or getattr(self.args, "adv_eval_batch_size", 32))
-        firsts_c, refs, samples = [], [], []
-        try:
-            for bi, s in enumerate(range(0, len(order), bs)):
-                keys = order[s:s + bs]
-                firsts = [ds[groups[k][0]] for k in keys]          # one image load per image
-                images = torch.stack([it[0] for it in firsts]).to(self.args.device)
-                caps = [[coco_ids(ds.captions[j]) for j in groups[k]] if coco else [it[1]] for k, it in zip(keys, firsts)]
-                L = max_caption_len or max(int(getattr(self.args, "max_seq_len", 0) or 0),
-                                           max(len(c) for group in caps for c in group) + 2)
-                ids, _, lengths = self.gen.sample_captions(images, num_samples=num_samples, top_k=top_k, top_p=top_p,
-                                                           temperature=temperature, max_caption_len=L, seed=int(seed) + bi)
-                ids, lengths = ids.cpu(), lengths.cpu()
-                for b, group in enumerate(caps):
-                    smp = [words(ids[b, j, :int(lengths[b, j])].tolist()) for j in range(ids.shape[1])]
-                    samples.append(smp)
-                    firsts_c.append(smp[0])
-                    refs.append([words(c) for c in group])
-        finally:
-            self.gen.train(was_training)
-        flat = [c for group in samples for c in group]
-        out = {"bleu4": bleu_score(firsts_c, refs), "mbleu4": mbleu4(samples), "distinct1": distinct_n(flat, 1),
-               "distinct2": distinct_n(flat, 2), "vocab": len({w for c in flat for w in c})}
+        def decode(images, L, bi):
+            ids, _, lengths = self.gen.sample_captions(images, num_samples=num_samples, top_k=top_k, top_p=top_p, temperature=temperature,
+                                                       max_caption_len=L, seed=int(seed) + bi)
+            return ids, lengths
+        out = self._diversity(what, decode, max_caption_len, batch_size)
         self.log.info("[EVAL] diversity (%s, n %d, top-k %d, top-p %.3f, temperature %.3f): BLEU-4 %.4f | mBLEU-4 %.4f | distinct-1 %.4f"
                       " | distinct-2 %.4f | vocab %d", what, num_samples, top_k, top_p, temperature, out["bleu4"], out["mbleu4"],
                       out["distinct1"], out["distinct2"], out["vocab"])
-        step = max(self.adv_epoch, 0)
-        for name, key in (("BLEU4S", "bleu4"), ("mBLEU4", "mbleu4"), ("Distinct1", "distinct1"), ("Distinct2", "distinct2"),
-                          ("Vocab", "vocab")):
-            self.writer.add_scalar(f"{name}_{what}", out[key], step)
+        self._write_diversity(out, what, ("BLEU4S", "mBLEU4", "Distinct1", "Distinct2", "Vocab"))
         return out
+
+    def evaluate_diverse_beam(self, what="val", beam_size=4, groups=2, diversity=0.5, length_penalty=0.0, max_caption_len=None,
+                              batch_size=None):
+        """The metrics of ``evaluate_diversity`` for the ``beam_size`` captions per image of diverse beam search (Generator.caption
+        with ``groups`` groups and the Hamming penalty ``diversity``), on the same images with the same caption length rule:
+        ``bleu4`` of slot 0 (group 0's best beam), ``mbleu4`` / ``distinct1`` / ``distinct2`` / ``vocab`` over the beams.  Logs the
+        values and writes the scalars ``<Name>_<what>`` (BLEU4DBS, mBLEU4DBS, Distinct1DBS, Distinct2DBS, VocabDBS)."""
+        def decode(images, L, _):
+            ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L, length_penalty=length_penalty,
+                                               return_beams=True, beam_groups=groups, diversity=diversity)
+            return ids, lengths
+        out = self._diversity(what, decode, max_caption_len, batch_size)
+        self.log.info("[EVAL] diverse beam (%s, beam %d, groups %d, diversity %.3f): BLEU-4 %.4f | mBLEU-4 %.4f | distinct-1 %.4f"
+                      " | distinct-2 %.4f | vocab %d", what, beam_size, groups, diversity, out["bleu4"], out["mbleu4"],
+                      out["distinct1"], out["distinct2"], out["vocab"])
+        self._write_diversity(out, what, ("BLEU4DBS", "mBLEU4DBS", "Distinct1DBS", "Distinct2DBS", "VocabDBS"))
+        return out
+
+    def _diversity(self, what, decode, max_caption_len, batch_size):
+        """The metrics of ``evaluate_diversity`` over the captions [b, n, L] that ``decode`` gives per batch (``_decode_batches``)."""
+        from .utils import bleu_score, distinct_n, mbleu4
+        words = self._eval_groups(what)[-1]
+        firsts_c, refs, samples = [], [], []
+        for ids, lengths, caps in self._decode_batches(what, decode, max_caption_len, batch_size):
+            ids, lengths = ids.cpu(), lengths.cpu()
+            for b, group in enumerate(caps):
+                smp = [words(ids[b, j, :int(lengths[b, j])].tolist()) for j in range(ids.shape[1])]
+                samples.append(smp)
+                firsts_c.append(smp[0])
+                refs.append([words(c) for c in group])
+        flat = [c for group in samples for c in group]
+        return {"bleu4": bleu_score(firsts_c, refs), "mbleu4": mbleu4(samples), "distinct1": distinct_n(flat, 1),
+                "distinct2": distinct_n(flat, 2), "vocab": len({w for c in flat for w in c})}
+
+    def _write_diversity(self, out, what, names):
+        step = max(self.adv_epoch, 0)
+        for name, key in zip(names, ("bleu4", "mbleu4", "distinct1", "distinct2", "vocab")):
+            self.writer.add_scalar(f"{name}_{what}", out[key], step)
 
 
 class _XentFn(torch.autograd.Function):

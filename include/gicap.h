@@ -352,6 +352,39 @@ int gic_attn_beam_search(const gic_attn_dims* dims, const gic_attn_params* param
                          const gic_decoder_beam_opts* opts, void* ws, const float* features, const void* fmap, int64_t* ids,
                          float* scores, int32_t* lengths, float* alphas, void* stream);
 
+/* Diverse beam search (Vijayakumar et al., AAAI 2018, Algorithm 1 with the Hamming diversity) for either decoder: K = beam.beam beams
+ * (1..8 and <= V) in G = groups groups of K' = K / G (G must divide K), diversity strength lambda = diversity (finite, >= 0).  Row r
+ * belongs to image r / K, beam j = r % K, group j / K'.  The recurrences, token log-probabilities, eos_id / pad_id, early stop, lengths
+ * and pad handling are those of gic_decoder_beam_search / gic_attn_beam_search.
+ *   start      at step 0 beam 0 of every group is live with score 0, the group's other beams have score -inf.
+ *   step t     the groups select in order g = 0..G-1, each among the candidates of beam search over its own K' rows: a live row
+ *              proposes its top-K tokens by raw logit (ties to the lower id), a finished row proposes itself once, with pad_id and its
+ *              score unchanged.  A live row's candidate (parent p, token v) is ranked by score[p] + logp(v) - lambda * h_g(v), h_g(v) =
+ *              the number of candidates with token v that groups 0..g-1 selected at this step from live parents (eos_id counts like any
+ *              token); a finished row's pad proposal is neither counted nor penalised.  Each group keeps its best K' (ties to the lower
+ *              (parent beam within the group, rank)).
+ *   score      the kept score is the raw sum score[p] + logp(v): the penalty steers step t's selection only and is never accumulated
+ *              (the paper's Algorithm 1; Hugging Face's group beam search accumulates it instead).
+ * Each row's top-K by raw logit holds every winner: at most K - K' distinct tokens are penalised, so at least K' unpenalised tokens of
+ * the list outrank every token outside it.  G = 1 is gic_*_beam_search, bit for bit, for any lambda; lambda = 0 makes the groups
+ * independent beam searches of width K'.  Outputs in group-major order: slots g * K' .. g * K' + K' - 1 of ids int64 [B,K,L] (pad_id after
+ * eos_id), scores f32 [B,K] (raw log-probability sums), lengths int32 [B,K] and (attention, or NULL) alphas f32 [B,K,L,P] hold group g's
+ * beams, sorted by score / length^length_penalty (ties to the lower beam index).  The workspace is that of gic_decoder_beam_ws_bytes /
+ * gic_attn_beam_ws_bytes for the same beam size.  Every argument check runs before any launch and returns GIC_STATUS_INVALID_ARG:
+ * those of the beam searches, groups < 1 or not dividing K, diversity NaN, negative or infinite.  Integer atomics only: two calls on
+ * the same inputs give the same bits, and the deterministic mode accepts the call and gives the same bits as outside it. */
+typedef struct gic_diverse_beam_opts {
+  gic_decoder_beam_opts beam;            /* beam = K, eos_id, pad_id, length_penalty, h0 / c0 as for the beam searches */
+  int32_t groups;                        /* G: 1..K, divides K */
+  float diversity;                       /* lambda: finite, >= 0 */
+} gic_diverse_beam_opts;
+int gic_decoder_diverse_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* params, const gic_decoder_shadow* shadow,
+                                    const gic_diverse_beam_opts* opts, void* ws, const float* features, int64_t* ids, float* scores,
+                                    int32_t* lengths, void* stream);
+int gic_attn_diverse_beam_search(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                                 const gic_diverse_beam_opts* opts, void* ws, const float* features, const void* fmap, int64_t* ids,
+                                 float* scores, int32_t* lengths, float* alphas, void* stream);
+
 /* Caption sampling: n = num_samples captions per image by temperature / top-k / top-p (nucleus) sampling, for either decoder.
  * Rows = B * n: row r belongs to image r / n and is sample r % n; every row is live from step 0.  Step 0 is fed `features` with
  * (h0, c0) or zeros, step t > 0 embed(the row's own previous token); the attention decoder follows the step of gic_attn_sample_fwd
@@ -608,7 +641,7 @@ int gic_colsum(const void* A, int dtype, int64_t lda, int64_t rows, int64_t cols
  * default; GIC_DETERMINISTIC=1 in the environment turns it on when the library is loaded.  While it is on, every entry point
  * that accepts the call gives bit-identical results for the same inputs, shapes, library build and device model: each f32 sum
  * that several workgroups contribute to has a fixed order (no racing f32 atomics).  Entry points without a deterministic form
- * return GIC_STATUS_UNSUPPORTED instead (gic_attn_sample_fwd / gic_attn_sample_bwd; the attention decoder's beam search and teacher-forced decode are accepted), as do the embedding scatters beyond their
+ * return GIC_STATUS_UNSUPPORTED instead (gic_attn_sample_fwd / gic_attn_sample_bwd; the attention decoder's beam searches and teacher-forced decode are accepted), as do the embedding scatters beyond their
  * limit (more than 8192 tokens, or V > 2^19).  It does not hold across GPU models or library builds.
  * The mode is read when work is enqueued: a captured graph keeps the kernels of the mode it was captured in.
  * gic_set_deterministic returns 0; gic_get_deterministic returns the current mode (0 / 1). */
