@@ -2,167 +2,22 @@
 // packed-sequence semantics with the step of attention.hip.  The inputs are known before the loop, so:
 //   before the loop  x rows of every step gathered once (embed_rows_tf), fp = fmap W_f^T + b_f (one product over B * P rows)
 //   per step t       hp GEMM        hp [B, A] = h_{t-1} W_h^T (the library GEMM, never split over K)
-//                    attn_tf_energy e[b, i] = w_a . tanh(fp_i + hp_b): workgroup = (caption, 8 positions)
-//                    attn_tf_ctx    alpha = softmax_i e[b, :], z_b = sum_i alpha_bi a_i: workgroup = (caption, 32 channel pieces); every
-//                                   workgroup of a caption forms the same softmax, 8 position groups each sum a share of the positions,
-//                                   and the 8 partial sums meet in LDS in group order
+//                    attn_step      the caption decode's attention kernels (attn_beam.hip) in their packed form at k = 1:
+//                                   attn_step_energy per (caption, 8 positions), attn_step_ctx per (caption, 32 channel pieces); a
+//                                   caption past its length returns from both at once (one zero alpha row)
 //                    lstm_step      the roll-out's fused step in its packed form (decoder_step.h LstmStepArgs.pack_len): a row past its
 //                                   length keeps (h, c), writes a zero output row and zero gates
 //   after the loop   one vocabulary product over B * Tmax rows, then the Gumbel-softmax epilogue of gic_decoder_forward_tf.
-// A caption past its length returns from both attention kernels at once (one zero alpha row).  No f32 atomics: each energy, alpha and z
-// value is written by one thread, partial sums are added in a fixed order and no GEMM splits K, so the forward gives the same bits on
-// every call in either mode.
+// No f32 atomics and no GEMM splits K, so the forward gives the same bits on every call in either mode.
 // Backward: decoder_output_bwd over B * Tmax rows, dhout zeroed past the lengths, then the reverse recurrence of gic_attn_sample_bwd
 // (attention.hip attn_bwd_recurrent) with the d alphas added in front of the softmax backward; the zero alpha rows of padded steps make
 // their attention terms vanish, and their zero gates / zero dhout rows make the LSTM terms vanish.
 #include "../../include/gicap.h"
-#include "decoder_step.h"
+#include "beam.h"
 #include "kernels.h"
 
 namespace gic {
 namespace {
-
-constexpr int kTfEnergyPos = 8;                    // positions per attn_tf_energy workgroup (2 per wave)
-constexpr int kTfCtxPieces = 32;                   // 16-byte channel pieces per attn_tf_ctx workgroup
-constexpr int kTfCtxGroups = 256 / kTfCtxPieces;   // its position groups
-
-struct AttnTfArgs {
-  const void* fproj;                 // act [B, P, A]
-  const void* fmap;                  // act [B, P, C]
-  const float* w_a;                  // [A]
-  const float* hp;                   // [B, A]: h_{t-1} W_h^T
-  const int32_t* lengths; int t;     // caption b takes part while t < lengths[b]
-  float* e;                          // [B, P] energies
-  void* z; long ldx;                 // act: caption b's z at z + b * ldx
-  float* alpha;                      // [B, P]: this step's slot of state->alpha
-  float* alphas; long alphas_ld;     // the caller's alphas at step t (caption b at + b * alphas_ld), or null
-  int P, A, C;
-};
-
-// e[b, i] for caption blockIdx.x and positions blockIdx.y * 8 .. + 7: wave w takes positions w and w + 4, a lane the 16-byte pieces
-// lane, lane + 64, ... of a position's fp row
-template <typename TA>
-__global__ __launch_bounds__(256) void attn_tf_energy_kernel(const AttnTfArgs a) {
-  constexpr int NV = Vec16<TA>::NV;
-  constexpr int kPW = kTfEnergyPos / 4;
-  const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (a.t >= a.lengths[b]) return;
-  const TA* fp = (const TA*)a.fproj + (long)b * a.P * a.A;
-  const float* hp = a.hp + (long)b * a.A;
-  const int i0 = blockIdx.y * kTfEnergyPos + w;
-  float s[kPW];
-#pragma unroll
-  for (int u = 0; u < kPW; ++u) s[u] = 0.f;
-  for (int j0 = lane * NV; j0 < a.A; j0 += 64 * NV) {
-    float v[kPW][NV];
-#pragma unroll
-    for (int u = 0; u < kPW; ++u) {                         // unconditional loads (a position past P re-reads the last one)
-      const int i = min(i0 + 4 * u, a.P - 1);
-      Vec16<TA>::load(fp + (long)i * a.A + j0, v[u]);
-    }
-    float wa[NV], h[NV];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) { wa[q] = a.w_a[j0 + q]; h[q] = hp[j0 + q]; }
-#pragma unroll
-    for (int u = 0; u < kPW; ++u)
-#pragma unroll
-      for (int q = 0; q < NV; ++q) s[u] += wa[q] * tanhf(v[u][q] + h[q]);
-  }
-#pragma unroll
-  for (int u = 0; u < kPW; ++u) {
-    const int i = i0 + 4 * u;
-    const float t = wave_sum(s[u]);
-    if (lane == 0 && i < a.P) a.e[(long)b * a.P + i] = t;
-  }
-}
-
-// z of caption blockIdx.x for the channel pieces blockIdx.y * 32 .. + 31 (LDS: alpha [P], then the partials [kTfCtxGroups][32 * NV])
-template <typename TA>
-__global__ __launch_bounds__(256) void attn_tf_ctx_kernel(const AttnTfArgs a) {
-  constexpr int NV = Vec16<TA>::NV;
-  constexpr int W = kTfCtxPieces * NV;                     // channels per workgroup
-  constexpr int kZ = 8;                                    // positions in flight per thread
-  extern __shared__ float tfc_s[];
-  float* al_s = tfc_s;
-  float* part_s = tfc_s + ((a.P + 3) & ~3);
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  float* alpha = blockIdx.y == 0 ? a.alpha + (long)b * a.P : nullptr;
-  float* alphas = blockIdx.y == 0 && a.alphas ? a.alphas + (long)b * a.alphas_ld : nullptr;
-  if (a.t >= a.lengths[b]) {                               // past the caption's length: a zero alpha row, z stays zero
-    if (alpha)
-      for (int i = tid; i < a.P; i += 256) {
-        alpha[i] = 0.f;
-        if (alphas) alphas[i] = 0.f;
-      }
-    return;
-  }
-  // alpha = softmax over the P positions by wave 0 (the same bits in every workgroup of the caption)
-  if (tid < 64) {
-    const float* er = a.e + (long)b * a.P;
-    float m = -INFINITY;
-    for (int i = lane; i < a.P; i += 64) m = fmaxf(m, er[i]);
-    m = wave_max(m);
-    float s = 0.f;
-    for (int i = lane; i < a.P; i += 64) {
-      const float x = expf(er[i] - m);
-      al_s[i] = x;
-      s += x;
-    }
-    s = wave_sum(s);
-    for (int i = lane; i < a.P; i += 64) {
-      const float al = al_s[i] / s;
-      al_s[i] = al;
-      if (alpha) alpha[i] = al;
-      if (alphas) alphas[i] = al;
-    }
-  }
-  __syncthreads();
-  // thread = (position group g, channel piece p): group g sums the positions g, g + 8, ...
-  const int p = tid % kTfCtxPieces, g = tid / kTfCtxPieces;
-  const int c0 = (blockIdx.y * kTfCtxPieces + p) * NV;
-  const TA* fm = (const TA*)a.fmap + (long)b * a.P * a.C + (c0 < a.C ? c0 : 0);
-  float acc[NV];
-#pragma unroll
-  for (int q = 0; q < NV; ++q) acc[q] = 0.f;
-  for (int i0 = g; i0 < a.P; i0 += kTfCtxGroups * kZ) {
-    float v[kZ][NV];
-#pragma unroll
-    for (int u = 0; u < kZ; ++u) {                          // unconditional loads (a position past P re-reads the group's first)
-      const int i = i0 + u * kTfCtxGroups;
-      Vec16<TA>::load(fm + (long)(i < a.P ? i : i0) * a.C, v[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < kZ; ++u) {
-      const int i = i0 + u * kTfCtxGroups;
-      const float al = i < a.P ? al_s[i] : 0.f;
-#pragma unroll
-      for (int q = 0; q < NV; ++q) acc[q] += al * v[u][q];
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < NV; ++q) part_s[g * W + p * NV + q] = acc[q];
-  __syncthreads();
-  const int cl = blockIdx.y * W + tid;                     // the groups' partial sums, added in group order by the channel's owner
-  if (tid < W && cl < a.C) {
-    float z = part_s[tid];
-#pragma unroll
-    for (int gg = 1; gg < kTfCtxGroups; ++gg) z += part_s[gg * W + tid];
-    ((TA*)a.z)[(long)b * a.ldx + cl] = from_f32<TA>(z);
-  }
-}
-
-template <typename TA>
-int attn_tf_step(const AttnTfArgs& f, int B, hipStream_t stream) {
-  constexpr int NV = Vec16<TA>::NV;
-  const size_t lds = (size_t)(((f.P + 3) & ~3) + kTfCtxGroups * kTfCtxPieces * NV) * sizeof(float);
-  static LdsGrant gc;
-  GIC_CHECK_ARG(grant_lds(attn_tf_ctx_kernel<TA>, lds, gc), "attn_tf_ctx: cannot reserve %zu bytes of LDS", lds);
-  hipLaunchKernelGGL((attn_tf_energy_kernel<TA>), dim3((unsigned)B, (unsigned)cdiv(f.P, kTfEnergyPos)), dim3(256), 0, stream, f);
-  GIC_CHECK_LAUNCH("attn_tf_energy");
-  hipLaunchKernelGGL((attn_tf_ctx_kernel<TA>), dim3((unsigned)B, (unsigned)cdiv(f.C, kTfCtxPieces * NV)), dim3(256), lds, stream, f);
-  GIC_CHECK_LAUNCH("attn_tf_ctx");
-  return GIC_OK;
-}
 
 // floats of logits_ws: the logits [B * Tmax, V] after the loop, the energies [B, P] during it
 size_t tf_ws_floats(const ACtx& c, int Tmax) {
@@ -199,12 +54,13 @@ int attn_tf_fwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow
       g.no_split = 1;
       GIC_PROPAGATE(gemm(g, stream));
     }
-    AttnTfArgs f;
-    f.fproj = st->fproj; f.fmap = fmap; f.w_a = P->w_a; f.hp = hp; f.lengths = lengths; f.t = t; f.e = logits_ws;
+    AttnStepArgs f{};                // par and stop stay null: the packed form reads lengths instead
+    f.fproj = st->fproj; f.fmap = fmap; f.w_a = P->w_a; f.hp = hp; f.e = logits_ws;
     f.z = xh_t + E; f.ldx = ld; f.alpha = st->alpha + (long)t * B * c.P;
-    f.alphas = alphas ? alphas + (long)t * c.P : nullptr; f.alphas_ld = (long)Tmax * c.P;
     f.P = c.P; f.A = c.A; f.C = c.C;
-    GIC_PROPAGATE(attn_tf_step<TA>(f, B, stream));
+    f.lengths = lengths; f.t = t;
+    f.alphas = alphas ? alphas + (long)t * c.P : nullptr; f.alphas_ld = (long)Tmax * c.P;
+    GIC_PROPAGATE(attn_step(f, 1, B, c.dt, stream));
     LstmStepArgs a;
     a.xh_t = xh_t; a.xh_next = xh_t + (long)B * ld; a.wcat = S->wcat; a.bsum = S->bsum;
     a.c_prev = st->c + (long)t * B * H; a.c_new = st->c + (long)(t + 1) * B * H;

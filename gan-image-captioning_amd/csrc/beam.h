@@ -146,8 +146,9 @@ int beam_select(const BeamSelectArgs& a, int K, int B, hipStream_t stream);
 int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length_penalty, int width, int64_t* ids, float* scores,
                   int32_t* lengths, int32_t* anc, hipStream_t stream);
 
-// attn_beam.hip: the attention kernels of one step (K rows per image, row r reads hp of row par[r]; the sampler's par[r] = r)
-struct AttnBeamArgs {
+// attn_beam.hip: the attention kernels of one step (K rows per image, row r reads hp of row par[r]; the sampler's par[r] = r).  With
+// lengths set, the packed form of teacher forcing (K = 1): row b = caption b reads its own hp row and takes part while t < lengths[b]
+struct AttnStepArgs {
   const void* fproj;                 // act [B, P, A]
   const void* fmap;                  // act [B, P, C]
   const float* w_a;                  // [A]
@@ -155,12 +156,15 @@ struct AttnBeamArgs {
   const int* par;                    // [rows]
   float* e;                          // [rows, P] energies
   void* z; long ldx;                 // act: row r's z at z + r * ldx
-  float* alpha;                      // [rows, P]: this step's slot of the alpha history, or null
+  float* alpha;                      // [rows, P]: this step's slot of the alpha history, or null (packed form: never null)
   const int* stop; int stop_at;      // *stop >= stop_at: every image has finished
   int P, A, C;
+  const int32_t* lengths = nullptr;  // packed form: [B]; par and stop unused
+  int t = 0;                         // packed form: the step
+  float* alphas = nullptr; long alphas_ld = 0;   // packed form: the caller's alphas at step t (caption b at + b * alphas_ld), or null
 };
-// attn_beam_energy then attn_beam_ctx for the K rows of each of the B images (rows = B * K)
-int attn_beam_step(const AttnBeamArgs& f, int K, int B, int dtype, hipStream_t stream);
+// attn_step_energy then attn_step_ctx for the K rows of each of the B images (rows = B * K)
+int attn_step(const AttnStepArgs& f, int K, int B, int dtype, hipStream_t stream);
 // alphas f32 [B, K, L, P] of the returned beams: row anc[b, j, t] of step t of the history ahist [L][rows][P] for t < lengths[b, j], else 0
 int attn_beam_alphas(const float* ahist, const int* anc, const int* lengths, int rows, int L, int P, float* alphas, hipStream_t stream);
 

@@ -5,7 +5,7 @@
 // A search is a recurrence and a head, chosen at the entry point:
 //   LstmFused    lstm_step's beam form per layer: h / c read from row parent[r], layer 0's x = embed[token[r]]
 //   LstmGeneric  where the fused kernels decline the shapes: beam_gather, then per layer the library GEMM and lstm_pointwise_fwd
-//   Attn         the fproj GEMM once; per step the hp GEMM, attn_beam_step (attn_beam.hip) and lstm_step's beam form
+//   Attn         the fproj GEMM once; per step the hp GEMM, attn_step (attn_beam.hip) and lstm_step's beam form
 // and
 //   BeamHead     vocab_step_beam (generic path: the GEMM into logits + beam_tile_topk), beam_select; beam_finalize (beam.h); with
 //                G > 1 groups the diverse search: the same kernels, beam_select's group-sequential form and a per-group final order
@@ -206,12 +206,12 @@ struct Attn {
     g.M = d.rows; g.N = d.A; g.K = d.H; g.in_dtype = d.dt; g.out_dtype = DT_F32;
     g.no_split = 1;
     GIC_PROPAGATE(gemm(g, s.stream));
-    AttnBeamArgs f;
+    AttnStepArgs f;
     f.fproj = s.w.fproj; f.fmap = fmap; f.w_a = P->w_a; f.hp = s.w.hp; f.par = s.w.st.par; f.e = s.w.e;
     f.z = d.act(xh_t, d.E); f.ldx = d.ldx(0); f.alpha = history ? s.w.ahist + (long)t * d.rows * d.P : nullptr;
     f.stop = s.w.st.count; f.stop_at = s.stop_at;
     f.P = d.P; f.A = d.A; f.C = d.C;
-    GIC_PROPAGATE(attn_beam_step(f, d.K, d.B, d.dt, s.stream));
+    GIC_PROPAGATE(attn_step(f, d.K, d.B, d.dt, s.stream));
     return lstm_beam_step(s, t, 0, S->wcat, S->bsum, P->embed, d.E);
   }
 };

@@ -842,13 +842,12 @@ int gumbel_softmax_rows(int dt, float* logits, const float* u, uint64_t seed, ui
   return GIC_OK;
 }
 
-}  // namespace gic
+namespace {
 
 template <typename TA>
 int forward_tf_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
                  const float* features, const int64_t* caps, const int32_t* lengths, int Tmax, const float* noise_u, uint64_t seed,
-                 float temperature, int pretrain, float* logits_ws, int64_t* ids_ws, void* out, float* h_n, float* c_n,
-                 hipStream_t stream) {
+                 float temperature, int pretrain, float* logits_ws, void* out, float* h_n, float* c_n, hipStream_t stream) {
   const int B = c.B, T = c.L, V = c.V, E = c.E, H = c.H, NL = c.NL;
   const int pw_grid = cdiv((long)B * H, 256);
   for (int l = 0; l < NL; ++l) {
@@ -856,12 +855,7 @@ int forward_tf_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
     GIC_PROPAGATE(fill_zero(st->c[l], (size_t)B * H * sizeof(float), stream));
   }
   GIC_PROPAGATE(cast2d(features, DT_F32, E, st->xh[0], c.dt, c.ldx(0), B, E, stream));
-  if (T > 1) {
-    const long total = (long)(T - 1) * B * E;
-    hipLaunchKernelGGL((embed_rows_tf_kernel<TA>), dim3((unsigned)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256)), dim3(256), 0,
-                       stream, P->embed, caps, (TA*)st->xh[0], c.ldx(0), B, T - 1, E, V);
-    GIC_CHECK_LAUNCH("embed_rows_tf");
-  }
+  GIC_PROPAGATE(embed_rows_tf(c.dt, P->embed, caps, st->xh[0], c.ldx(0), B, T - 1, E, V, stream));
   for (int t = 0; t < Tmax; ++t) {
     for (int l = 0; l < NL; ++l) {
       const long ld = c.ldx(l);
@@ -888,16 +882,16 @@ int forward_tf_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
     g.M = (int)rows; g.N = V; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = P->b_out;
     GIC_PROPAGATE(gemm(g, stream));
   }
-  hipLaunchKernelGGL((gumbel_softmax_argmax_kernel<TA>), dim3((unsigned)rows), dim3(256), 0, stream, logits_ws, noise_u, seed, (uint64_t)0x7466,
-                     temperature, pretrain, (TA*)out, (long)V, ids_ws, (long)1, P->embed, (TA*)nullptr, (long)0, V, E,
-                     (const int64_t*)nullptr, (const int32_t*)nullptr, 0);
-  GIC_CHECK_LAUNCH("gumbel_softmax (teacher forced)");
+  GIC_PROPAGATE(gumbel_softmax_rows(c.dt, logits_ws, noise_u, seed, (uint64_t)0x7466, temperature, pretrain, out, rows, V, stream));
   for (int l = 0; l < NL; ++l) {
     GIC_PROPAGATE(cast2d((const TA*)st->xh[l] + (long)Tmax * B * c.ldx(l) + c.din(l), c.dt, c.ldx(l), h_n + (long)l * B * H, DT_F32, H, B, H, stream));
     GIC_PROPAGATE(cast2d(st->c[l] + (long)Tmax * B * H, DT_F32, H, c_n + (long)l * B * H, DT_F32, H, B, H, stream));
   }
   return GIC_OK;
 }
+
+}  // namespace
+}  // namespace gic
 
 extern "C" {
 
@@ -914,10 +908,10 @@ int gic_decoder_forward_tf(const gic_decoder_dims* dims, const gic_decoder_param
   for (int l = 0; l < c.NL; ++l)
     GIC_CHECK_ARG(st->xh[l] && st->c[l] && S->wcat[l] && S->bsum[l], "decoder_forward_tf: null layer %d buffer", l);
   if (c.dt == DT_F32)
-    return forward_tf_t<float>(c, P, S, st, features, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, ids_ws, out,
-                               h_n, c_n, (hipStream_t)stream);
-  return forward_tf_t<bf16_t>(c, P, S, st, features, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, ids_ws, out,
-                              h_n, c_n, (hipStream_t)stream);
+    return forward_tf_t<float>(c, P, S, st, features, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, out, h_n, c_n,
+                               (hipStream_t)stream);
+  return forward_tf_t<bf16_t>(c, P, S, st, features, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, out, h_n, c_n,
+                              (hipStream_t)stream);
 }
 
 int gic_decoder_forward_tf_bwd(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
@@ -939,12 +933,7 @@ int gic_decoder_forward_tf_bwd(const gic_decoder_dims* dims, const gic_decoder_p
   c.L = Tmax;
   GIC_PROPAGATE(decoder_output_bwd(c.dt, c.B, Tmax, c.V, c.H, pred, d_pred, temperature, nullptr, pretrain, ws->dlogits, S->wout, st->hout, ws->dhout,
                                    G->w_out, G->b_out, stream));
-  {
-    const long total = (long)c.B * Tmax * c.H;
-    hipLaunchKernelGGL(zero_past_length_kernel, dim3((unsigned)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256)), dim3(256), 0, stream,
-                       ws->dhout, lengths, c.B, Tmax, c.H);
-    GIC_CHECK_LAUNCH("zero_past_length");
-  }
+  GIC_PROPAGATE(zero_past_length(ws->dhout, lengths, c.B, Tmax, c.H, stream));
   // caps stands in for the sampled ids (the input of step t is embed(caps[b, t-1])); sample_bwd_t itself never reads them
   const int s = (c.dt == DT_F32)
                     ? sample_bwd_t<float>(c, P, S, st, ws, pred, caps, d_pred, temperature, nullptr, pretrain, G, GIC_DECODER_BWD_RECURRENT, stream)

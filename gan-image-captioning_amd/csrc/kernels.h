@@ -31,8 +31,9 @@ int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_
 int det_mode();
 int det_scatter(const void* src, int dt, long ld, long row_off, const int64_t* ids, int B, long s_b, long s_t, long n, float* dst,
                 long d_id, long d_e, int E, int V, hipStream_t stream);
-// the teacher-forced decode's pieces (decoder.hip), shared with attn_tf.hip: x rows of slots 1..Tm1 of xh0 = embed(caps[b, t-1]) (caps
-// rows Tm1 apart); rows of dhout [B, Tmax, H] past their length zeroed; per-row Gumbel-softmax of logits [rows, V] into out (no ids)
+// the teacher-forced decode's pieces (decoder.hip), for gic_decoder_forward_tf and attn_tf.hip: x rows of slots 1..Tm1 of xh0 =
+// embed(caps[b, t-1]) (caps rows Tm1 apart); rows of dhout [B, Tmax, H] past their length zeroed; per-row Gumbel-softmax of logits
+// [rows, V] into out (no ids)
 int embed_rows_tf(int dt, const float* embed, const int64_t* caps, void* xh0, long ld, int B, int Tm1, int E, int V, hipStream_t stream);
 int zero_past_length(float* dhout, const int32_t* lengths, int B, int Tmax, int H, hipStream_t stream);
 int gumbel_softmax_rows(int dt, float* logits, const float* u, uint64_t seed, uint64_t rng_stream, float temperature, int pretrain, void* out,

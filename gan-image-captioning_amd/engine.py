@@ -148,6 +148,15 @@ def cast2d(src: torch.Tensor, dst: torch.Tensor, rows: int, cols: int, lds: int,
     return dst
 
 
+def _to_act(t: torch.Tensor, act: torch.dtype) -> torch.Tensor:
+    """``t`` contiguous in the compute dtype ``act`` (cast on the GPU where it differs)."""
+    t = t.contiguous()
+    if t.dtype == act:
+        return t
+    n = t.shape[-1]
+    return cast2d(t, torch.empty(t.shape, device=t.device, dtype=act), t.numel() // n, n, n, n)
+
+
 def embedding_fwd(weight: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     require_gpu(weight, ids)
     ids = ids.contiguous()
@@ -588,9 +597,7 @@ class DecoderEngine:
         B, Tmax, dev = pred.shape[0], saved["Tmax"], pred.device
         if tuple(d_pred.shape) != tuple(pred.shape):
             raise ValueError("d_pred must have pred's shape")
-        if d_pred.dtype != self.act:
-            d_pred = self._cast_like(d_pred)
-        d_pred = d_pred.contiguous()
+        d_pred = _to_act(d_pred, self.act)
         self.prepare(params)
         ws = ws if ws is not None else self.alloc_bwd_ws(B, Tmax, dev)
         grads = grads if grads is not None else self.alloc_grads(params, B)
@@ -612,9 +619,7 @@ class DecoderEngine:
         the initial states, read back with ``state_grads(ws)`` (gicap.h)."""
         B, Lc = ids.shape
         dev = out.device
-        if d_out.dtype != self.act:
-            d_out = self._cast_like(d_out)
-        d_out = d_out.contiguous()
+        d_out = _to_act(d_out, self.act)
         self.prepare(params)
         ws = ws if ws is not None else self.alloc_bwd_ws(B, Lc, dev)
         grads = grads if grads is not None else self.alloc_grads(params, B)
@@ -715,13 +720,6 @@ class DecoderEngine:
             ptr(features), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()),
             "gic_decoder_sample_captions")
         return ids, scores, lengths
-
-    def _cast_like(self, t: torch.Tensor) -> torch.Tensor:
-        t = t.contiguous()
-        dst = torch.empty(t.shape, device=t.device, dtype=self.act)
-        n = t.shape[-1]
-        cast2d(t, dst, t.numel() // n, n, n, n)
-        return dst
 
 
 # ------------------------------------------------------------------------------------------ discriminator
@@ -1233,12 +1231,7 @@ class AttnDecoderEngine:
             d_pred = torch.zeros(pred.shape, device=dev, dtype=self.act)
         if tuple(d_pred.shape) != tuple(pred.shape):
             raise ValueError("d_pred must have pred's shape")
-        if d_pred.dtype != self.act:
-            t = d_pred.contiguous()
-            dst = torch.empty(t.shape, device=dev, dtype=self.act)
-            cast2d(t, dst, t.numel() // self.V, self.V, self.V, self.V)
-            d_pred = dst
-        d_pred = d_pred.contiguous()
+        d_pred = _to_act(d_pred, self.act)
         if d_alphas is not None:
             if tuple(d_alphas.shape) != (B, Tmax, self.P):
                 raise ValueError(f"d_alphas must be [B, max(lengths)={Tmax}, P={self.P}]")
@@ -1278,12 +1271,7 @@ class AttnDecoderEngine:
         B, Lc = ids.shape
         dev = out.device
         f32 = torch.float32
-        if d_out.dtype != self.act:
-            t = d_out.contiguous()
-            dst = torch.empty(t.shape, device=dev, dtype=self.act)
-            cast2d(t, dst, t.numel() // self.V, self.V, self.V, self.V)
-            d_out = dst
-        d_out = d_out.contiguous()
+        d_out = _to_act(d_out, self.act)
         self.prepare(params)
         ws = ws if ws is not None else self.alloc_bwd_ws(B, Lc, dev)
         w = L.AttnBwdWs()
