@@ -598,7 +598,8 @@ int gic_conv1x1_res_in(const void* in, const float* in_stats, int in_nrep, const
  *                             it to the next conv1 (w1n act [C1N, 4*C2]): y1n act [rows, C1N] and its column sums into stats1.
  *                             All BatchNorms on batch statistics over `count` rows.
  * Both return GIC_STATUS_UNSUPPORTED (nothing launched) in f32 mode and for shapes they have no kernel for (C2 in {64, 128},
- * C1N in {64, 128}, rows % 64 == 0, enough rows for the streaming kernel): the caller runs gic_conv2d_bn_in + gic_conv1x1_res_in. */
+ * (C2, C1N) in {(64, 64), (64, 128), (128, 128), (128, 256)}, rows % 128 == 0, rows * 4 * C2 * 2 < 2^31 bytes, enough rows for the
+ * streaming kernel): the caller runs gic_conv2d_bn_in + gic_conv1x1_res_in. */
 int gic_conv1x1_bn_in_stats(const void* in, const float* in_stats, int in_nrep, const float* in_gamma, const float* in_beta, float in_count,
                             const void* w, float* stats, int stats_nrep, int dtype, int64_t rows, int Cin, int Cout, void* stream);
 int gic_conv_b2b(const void* y2, const float* stats2, int nrep2, const float* gamma2, const float* beta2, const void* w3, const float* stats3,
