@@ -144,6 +144,8 @@ _P = C.POINTER
 _SIGNATURES = {
     "gic_abi_version": (C.c_int, []),
     "gic_last_error": (C.c_char_p, []),
+    "gic_debug_route_only": (None, [C.c_int]),
+    "gic_debug_last_route": (C.c_char_p, []),
     "gic_gemm": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                            C.c_int, C.c_int, C.c_int, C.c_int, c_void_p, C.c_int, C.c_float, c_void_p]),
     "gic_cast2d": (C.c_int, [c_void_p, C.c_int, C.c_int64, c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, c_void_p]),
@@ -214,6 +216,7 @@ _SIGNATURES = {
     "gic_conv_b2b": (C.c_int, [c_void_p, c_void_p, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                      C.c_int, c_void_p, c_void_p, C.c_float, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int,
                      c_void_p]),
+    "gic_conv_b2b_supported": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int]),
     "gic_conv2d": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_int, C.c_int] + [C.c_int] * 9 + [c_void_p]),
     "gic_bn_act": (C.c_int, [c_void_p] * 12 + [C.c_int, C.c_float, C.c_int, c_void_p, C.c_int, C.c_int64, C.c_int, c_void_p]),
     "gic_bn_relu_maxpool": (C.c_int, [c_void_p] * 6 + [C.c_int, C.c_float, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
@@ -238,7 +241,7 @@ _SIGNATURES = {
                                 C.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
-ABI_VERSION = 4               # GIC_ABI_VERSION of include/gicap.h
+ABI_VERSION = 5               # GIC_ABI_VERSION of include/gicap.h
 CIDER_MAX_LEN, CIDER_MAX_REFS, CIDER_MAX_VOCAB = 64, 32, 32768      # GIC_CIDER_MAX_LEN / _MAX_REFS / _MAX_VOCAB
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _lib = None

@@ -20,16 +20,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // everything the kernel reads from its arguments, compact (one batch of scalar loads at the top)
-struct PanelDesc {
-  const void* A; const void* B; void* C; float* stats;
-  const float* in_stats; const float* in_gamma; const float* in_beta;
-  int M, N, lda, ldb, ldc, stats_nrep, in_nrep;
-  float in_inv_count;
-  int share_a;
-  int tiles_m, tiles_n, groups, per_group;   // row tiles, 64-wide output-channel tiles, groups of them, tiles per group
-  unsigned a_bytes, b_bytes;
-};
-
 // KT = K / 64 (4); ABN: BatchNorm + ReLU of the input on load.  8 waves as 4 (M) x 2 (N): a wave owns 32 x 32 of a 128 x 64 output tile.
 template <int KT, bool ABN>
 __global__ __launch_bounds__(512) void conv1x1_panel_kernel(const PanelDesc d) {
@@ -197,29 +187,22 @@ __global__ __launch_bounds__(512) void conv1x1_panel_kernel(const PanelDesc d) {
 }
 
 template <int KT, bool ABN>
-bool launch_panel(const PanelDesc& pd, hipStream_t stream) {
-  constexpr size_t lds = (size_t)KT * 128 * 128 + 2 * (size_t)KT * 64 * 128 + 128 * (64 * 2 + 16) + 8 * 32 * 2 * 4 + (ABN ? 64 * KT * 8 : 0);
+bool launch_panel(const PanelPlan& p, hipStream_t stream) {
   static LdsGrant granted;
-  if (!grant_lds(conv1x1_panel_kernel<KT, ABN>, lds, granted)) return false;
-  hipLaunchKernelGGL((conv1x1_panel_kernel<KT, ABN>), dim3((unsigned)(pd.tiles_m * pd.groups)), dim3(512), lds, stream, pd);
+  if (!grant_lds(conv1x1_panel_kernel<KT, ABN>, p.lds, granted)) return false;
+  hipLaunchKernelGGL((conv1x1_panel_kernel<KT, ABN>), dim3(p.grid), dim3(512), p.lds, stream, p.d);
   return true;
 }
 
 }  // namespace
 
-bool try_conv1x1_panel(const GemmDesc& d, hipStream_t stream) {
+bool select_conv1x1_panel(const GemmDesc& d, PanelPlan& p) {
   static const bool off = getenv("GIC_NO_CONV1X1_PANEL") != nullptr;
-  if (off || !d.conv || d.epi != EPI_BNSTATS || !d.stats || d.res) return false;
-  if (d.in_dtype != DT_BF16 || d.out_dtype != DT_BF16) return false;
+  if (off || d.res) return false;
   if (d.cKH != 1 || d.cKW != 1 || d.cStride != 1 || d.cPad != 0) return false;
-  if (d.K != 256 || d.cCin != d.K || d.lda != d.K || d.N < 512 || d.N % 64) return false;      // the panel pays where it serves many tiles
-  if (d.ldc % 8 || d.ldb % 8 || (((uintptr_t)d.C) & 15) || (((uintptr_t)d.A) & 15) || (((uintptr_t)d.B) & 15)) return false;
-  if (d.bias || d.alpha != 1.f || d.accumulate) return false;
-  const bool abn = d.in_stats != nullptr;
-  if (abn && (!d.in_gamma || !d.in_beta || d.in_inv_count <= 0.f || d.in_nrep < 1)) return false;
-  const long a_elems = (long)d.M * d.K, b_elems = (long)(d.N - 1) * d.ldb + d.K;
-  if (a_elems * 2 >= (1l << 31) || b_elems * 2 >= (1l << 31)) return false;
-  PanelDesc pd;
+  if (d.K != 256 || d.cCin != d.K || d.lda != d.K || d.N < 512 || d.N % 64 || d.ldc % 8 || d.ldb % 8) return false;      // the panel pays where it serves many tiles
+  PanelDesc& pd = p.d;
+  if (!conv_base(d, (long)d.M * d.K, (long)(d.N - 1) * d.ldb + d.K, pd)) return false;
   pd.tiles_m = cdiv(d.M, 128);
   pd.tiles_n = d.N / 64;
   // about one workgroup per CU: split the output-channel tiles of a row tile over as many groups as that leaves room for
@@ -229,12 +212,14 @@ bool try_conv1x1_panel(const GemmDesc& d, hipStream_t stream) {
   pd.per_group = cdiv(pd.tiles_n, groups);
   pd.groups = cdiv(pd.tiles_n, pd.per_group);
   pd.share_a = xcd_share_a(2l * d.M * d.K, 2l * d.N * d.K, pd.groups);
-  pd.A = d.A; pd.B = d.B; pd.C = d.C; pd.stats = d.stats;
-  pd.in_stats = d.in_stats; pd.in_gamma = d.in_gamma; pd.in_beta = d.in_beta;
-  pd.M = d.M; pd.N = d.N; pd.lda = (int)d.lda; pd.ldb = (int)d.ldb; pd.ldc = (int)d.ldc;
-  pd.stats_nrep = d.stats_nrep < 1 ? 1 : d.stats_nrep; pd.in_nrep = d.in_nrep; pd.in_inv_count = d.in_inv_count;
-  pd.a_bytes = (unsigned)(a_elems * 2); pd.b_bytes = (unsigned)(b_elems * 2);
-  return abn ? launch_panel<4, true>(pd, stream) : launch_panel<4, false>(pd, stream);
+  p.KT = 4; p.abn = d.in_stats != nullptr;
+  p.grid = (unsigned)(pd.tiles_m * pd.groups);
+  p.lds = (size_t)p.KT * 128 * 128 + 2 * (size_t)p.KT * 64 * 128 + 128 * (64 * 2 + 16) + 8 * 32 * 2 * 4 + (p.abn ? 64 * p.KT * 8 : 0);
+  return true;
+}
+
+bool launch_conv1x1_panel(const PanelPlan& p, hipStream_t stream) {
+  return p.abn ? launch_panel<4, true>(p, stream) : launch_panel<4, false>(p, stream);
 }
 
 }  // namespace gic

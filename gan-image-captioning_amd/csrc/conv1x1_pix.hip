@@ -59,15 +59,6 @@ __device__ __forceinline__ float pix_reduce_scatter16(const float (&v)[16], cons
   return (up ? x[1] : x[0]) + pix_dpp<0xB1>(up ? x[0] : x[1]);
 }
 
-struct PixDesc {
-  const void* A; const void* B; void* C; float* stats;
-  const float* in_stats; const float* in_gamma; const float* in_beta;
-  int M, N, stats_nrep, in_nrep;
-  float in_inv_count;
-  int tiles_m, per_group;              // row tiles of 128 pixels; 64-channel tiles per workgroup (grid = tiles_m * groups)
-  unsigned a_bytes, b_bytes, c_bytes;
-};
-
 // K input channels; NSTG ring stages of 64-channel weight tiles; TURN: column sums through the turning scratch (else: DPP butterfly)
 template <int K, int NSTG, bool TURN>
 __global__ __launch_bounds__(512) void conv1x1_pix_kernel(const PixDesc d) {
@@ -235,29 +226,24 @@ __global__ __launch_bounds__(512) void conv1x1_pix_kernel(const PixDesc d) {
 }
 
 template <int K, int NSTG, bool TURN>
-bool launch_pix(const PixDesc& pd, int groups, hipStream_t stream) {
-  const size_t lds = (size_t)NSTG * 64 * K * 2 + (size_t)K * 8 + (TURN ? 8 * 16 * 272 : 0);
-  if (lds > 160 * 1024) return false;
+bool launch_pix(const PixPlan& p, hipStream_t stream) {
   static LdsGrant granted;
-  if (!grant_lds(conv1x1_pix_kernel<K, NSTG, TURN>, lds, granted)) return false;
-  hipLaunchKernelGGL((conv1x1_pix_kernel<K, NSTG, TURN>), dim3((unsigned)(pd.tiles_m * groups)), dim3(512), lds, stream, pd);
+  if (!grant_lds(conv1x1_pix_kernel<K, NSTG, TURN>, p.lds, granted)) return false;
+  hipLaunchKernelGGL((conv1x1_pix_kernel<K, NSTG, TURN>), dim3(p.grid), dim3(512), p.lds, stream, p.d);
   return true;
 }
 
 }  // namespace
 
-bool try_conv1x1_pix(const GemmDesc& d, hipStream_t stream) {
+bool select_conv1x1_pix(const GemmDesc& d, PixPlan& p) {
   static const bool off = getenv("GIC_NO_CONV1X1_PIX") != nullptr;
-  if (off || !d.conv || d.epi != EPI_BNSTATS || !d.stats || d.res || !d.in_stats) return false;      // (the input's BatchNorm rides in: conv3 of a bottleneck)
-  if (d.in_dtype != DT_BF16 || d.out_dtype != DT_BF16) return false;
+  if (off || d.res || !d.in_stats || d.stats_only) return false;      // (the input's BatchNorm rides in: conv3 of a bottleneck)
   if (d.cKH != 1 || d.cKW != 1 || d.cStride != 1 || d.cPad != 0) return false;
   if ((d.K != 256 && d.K != 512) || d.cCin != d.K || d.lda != d.K || d.ldb != d.K || d.N < 512 || d.N % 64 || d.ldc != d.N || d.M < 128) return false;
-  if ((((uintptr_t)d.C) & 15) || (((uintptr_t)d.A) & 15) || (((uintptr_t)d.B) & 15)) return false;
-  if (d.bias || d.alpha != 1.f || d.accumulate || d.stats_only) return false;
-  if (!d.in_gamma || !d.in_beta || d.in_inv_count <= 0.f || d.in_nrep < 1) return false;
-  const long a_bytes = (long)d.M * d.K * 2, b_bytes = (long)d.N * d.K * 2, c_bytes = (long)d.M * d.N * 2;
-  if (a_bytes >= (1l << 31) || b_bytes >= (1l << 31) || c_bytes >= (1l << 31)) return false;
-  PixDesc pd;
+  const long c_bytes = (long)d.M * d.N * 2;
+  PixDesc& pd = p.d;
+  if (c_bytes >= (1l << 31) || !conv_base(d, (long)d.M * d.K, (long)d.N * d.K, pd)) return false;
+  pd.c_bytes = (unsigned)c_bytes;
   pd.tiles_m = cdiv(d.M, 128);
   const int tiles_n = d.N / 64;
   // about one workgroup per CU (a workgroup keeps its pixels in registers: every further group of a row tile loads them again)
@@ -268,12 +254,15 @@ bool try_conv1x1_pix(const GemmDesc& d, hipStream_t stream) {
   if (cdiv(tiles_n, groups) > 8) groups = cdiv(tiles_n, 8);            // (the kernel's MAXT)
   pd.per_group = cdiv(tiles_n, groups);
   groups = cdiv(tiles_n, pd.per_group);
-  pd.A = d.A; pd.B = d.B; pd.C = d.C; pd.stats = d.stats;
-  pd.in_stats = d.in_stats; pd.in_gamma = d.in_gamma; pd.in_beta = d.in_beta;
-  pd.M = d.M; pd.N = d.N; pd.stats_nrep = d.stats_nrep < 1 ? 1 : d.stats_nrep; pd.in_nrep = d.in_nrep; pd.in_inv_count = d.in_inv_count;
-  pd.a_bytes = (unsigned)a_bytes; pd.b_bytes = (unsigned)b_bytes; pd.c_bytes = (unsigned)c_bytes;
   // (K = 512: two 64 KB stages leave no room for the turning scratch: its column sums take the butterfly)
-  return d.K == 256 ? launch_pix<256, 3, true>(pd, groups, stream) : launch_pix<512, 2, false>(pd, groups, stream);
+  p.K = d.K; p.NSTG = d.K == 256 ? 3 : 2; p.turn = d.K == 256;
+  p.grid = (unsigned)(pd.tiles_m * groups);
+  p.lds = (size_t)p.NSTG * 64 * p.K * 2 + (size_t)p.K * 8 + (p.turn ? 8 * 16 * 272 : 0);
+  return p.lds <= 160 * 1024;
+}
+
+bool launch_conv1x1_pix(const PixPlan& p, hipStream_t stream) {
+  return p.K == 256 ? launch_pix<256, 3, true>(p, stream) : launch_pix<512, 2, false>(p, stream);
 }
 
 }  // namespace gic

@@ -23,17 +23,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // everything the kernel reads from its arguments, compact (one batch of scalar loads at the top)
-struct StreamDesc {
-  const void* A; const void* B; void* C; float* stats;
-  const float* in_stats; const float* in_gamma; const float* in_beta;
-  int M, N, lda, ldb, ldc, stats_nrep, in_nrep;
-  float in_inv_count;
-  int share_a;
-  int stats_only;                      // column sums only: no C stores
-  int tiles_m, tiles_n, groups;        // row tiles, output-channel tiles, workgroups per output-channel tile (grid = groups * tiles_n)
-  unsigned a_bytes, b_bytes;
-};
-
 // BN output channels per workgroup; KT = K / 64; ABN: BatchNorm + ReLU of the input on load; STATS: the column sums ONLY (the first pass of
 // conv_b2b.hip's pair: no C tile in LDS, no stores -- which leaves room for 256 output channels per workgroup, so that a row tile is
 // fetched and normalised once for all of them)
@@ -248,61 +237,59 @@ __global__ __launch_bounds__(512) void conv1x1_stream_kernel(const StreamDesc d)
 }
 
 template <int BN, int KT, bool ABN, bool STATS = false>
-bool launch_stream(const StreamDesc& sd, hipStream_t stream) {
-  constexpr int NS = KT == 1 ? 4 : 2;
-  constexpr size_t lds = (size_t)NS * KT * 128 * 128 + (size_t)KT * BN * 128 + (STATS ? 0 : (KT == 1 ? 2 : 1) * 128 * (BN * 2 + 16)) + 4 * BN * 2 * 4 +
-                         (ABN ? 64 * KT * 8 : 0);
-  static_assert(lds <= 160 * 1024, "conv1x1_stream LDS budget");
+bool launch_stream(const StreamPlan& p, hipStream_t stream) {
   static LdsGrant granted;
-  if (!grant_lds(conv1x1_stream_kernel<BN, KT, ABN, STATS>, lds, granted)) return false;
-  hipLaunchKernelGGL((conv1x1_stream_kernel<BN, KT, ABN, STATS>), dim3((unsigned)(sd.groups * sd.tiles_n)), dim3(512), lds, stream, sd);
+  if (!grant_lds(conv1x1_stream_kernel<BN, KT, ABN, STATS>, p.lds, granted)) return false;
+  hipLaunchKernelGGL((conv1x1_stream_kernel<BN, KT, ABN, STATS>), dim3(p.grid), dim3(512), p.lds, stream, p.d);
   return true;
 }
 
 }  // namespace
 
-bool try_conv1x1_stream(const GemmDesc& d, hipStream_t stream) {
+bool select_conv1x1_stream(const GemmDesc& d, StreamPlan& p) {
   static const bool off = getenv("GIC_NO_CONV1X1_STREAM") != nullptr;
   static const int min_tiles = [] { const char* e = getenv("GIC_STREAM_MIN_TILES"); return e ? atoi(e) : 1024; }();
-  if (off || !d.conv || d.epi != EPI_BNSTATS || !d.stats || d.res) return false;
-  if (d.in_dtype != DT_BF16 || d.out_dtype != DT_BF16) return false;
+  if (off || d.res) return false;
   if (d.cKH != 1 || d.cKW != 1 || d.cStride != 1 || d.cPad != 0) return false;
   if ((d.K != 64 && d.K != 128) || d.cCin != d.K || d.lda != d.K) return false;
-  if (d.N % 8 || d.ldc % 8 || d.ldb % 8 || (((uintptr_t)d.C) & 15) || (((uintptr_t)d.A) & 15) || (((uintptr_t)d.B) & 15)) return false;
-  if (d.bias || d.alpha != 1.f || d.accumulate) return false;
-  const bool abn = d.in_stats != nullptr;
-  if (abn && (!d.in_gamma || !d.in_beta || d.in_inv_count <= 0.f || d.in_nrep < 1)) return false;
-  const long a_elems = (long)d.M * d.K, b_elems = (long)(d.N - 1) * d.ldb + d.K;
-  if (a_elems * 2 >= (1l << 31) || b_elems * 2 >= (1l << 31) || (long)d.M * d.ldc * 2 >= (1l << 40)) return false;
+  if (d.N % 8 || d.ldc % 8 || d.ldb % 8 || (long)d.M * d.ldc * 2 >= (1l << 40)) return false;
+  StreamDesc& sd = p.d;
+  if (!conv_base(d, (long)d.M * d.K, (long)(d.N - 1) * d.ldb + d.K, sd)) return false;
   static const bool bn64 = getenv("GIC_STREAM_BN64") != nullptr;
   static const int wg_per_cu = [] { const char* e = getenv("GIC_STREAM_WG_PER_CU"); return e ? atoi(e) : 1; }();
-  const bool n128 = d.N >= 128 && !bn64;
+  p.abn = d.in_stats != nullptr;
   // the statistics-only pass (input normalised on load, output channels a multiple of 256): 256 channels per workgroup
-  const bool stats256 = d.stats_only && abn && d.N % 256 == 0;
-  if (d.stats_only && !stats256) return false;
-  StreamDesc sd;
+  p.stats = d.stats_only && p.abn && d.N % 256 == 0;
+  if (d.stats_only && !p.stats) return false;
+  p.BN = p.stats ? 256 : (d.N >= 128 && !bn64 ? 128 : 64);
+  p.KT = d.K / 64;
   sd.tiles_m = cdiv(d.M, 128);
-  sd.tiles_n = stats256 ? d.N / 256 : (n128 ? cdiv(d.N, 128) : cdiv(d.N, 64));
+  sd.tiles_n = cdiv(d.N, p.BN);
   // streaming pays where a workgroup walks several row tiles; small grids stay with tile8 (counted in 128-wide tiles for both forms)
-  if ((long)sd.tiles_m * (stats256 ? d.N / 128 : sd.tiles_n) < min_tiles) return false;
+  if ((long)sd.tiles_m * (p.stats ? d.N / 128 : sd.tiles_n) < min_tiles) return false;
   int groups = 256 * wg_per_cu / sd.tiles_n;           // one persistent workgroup per CU (the ring + the C tile fill most of its LDS)
   if (groups < 1) groups = 1;
   if (groups > sd.tiles_m) groups = sd.tiles_m;
   sd.groups = groups;
   sd.share_a = xcd_share_a(2l * d.M * d.K, 2l * d.N * d.K, sd.tiles_n);
-  sd.A = d.A; sd.B = d.B; sd.C = d.C; sd.stats = d.stats; sd.stats_only = d.stats_only;
-  sd.in_stats = d.in_stats; sd.in_gamma = d.in_gamma; sd.in_beta = d.in_beta;
-  sd.M = d.M; sd.N = d.N; sd.lda = (int)d.lda; sd.ldb = (int)d.ldb; sd.ldc = (int)d.ldc;
-  sd.stats_nrep = d.stats_nrep < 1 ? 1 : d.stats_nrep; sd.in_nrep = d.in_nrep; sd.in_inv_count = d.in_inv_count;
-  sd.a_bytes = (unsigned)(a_elems * 2); sd.b_bytes = (unsigned)(b_elems * 2);
-  const int kt = d.K / 64;
-  if (stats256) return kt == 1 ? launch_stream<256, 1, true, true>(sd, stream) : launch_stream<256, 2, true, true>(sd, stream);
-  if (abn) {
-    if (n128) return kt == 1 ? launch_stream<128, 1, true>(sd, stream) : launch_stream<128, 2, true>(sd, stream);
-    return kt == 1 ? launch_stream<64, 1, true>(sd, stream) : launch_stream<64, 2, true>(sd, stream);
+  sd.stats_only = d.stats_only;
+  p.grid = (unsigned)(sd.groups * sd.tiles_n);
+  const int NS = p.KT == 1 ? 4 : 2;                    // (the kernel's ring stages)
+  p.lds = (size_t)NS * p.KT * 128 * 128 + (size_t)p.KT * p.BN * 128 + (p.stats ? 0 : (p.KT == 1 ? 2 : 1) * 128 * (p.BN * 2 + 16)) + 4 * p.BN * 2 * 4 +
+          (p.abn ? 64 * p.KT * 8 : 0);
+  return true;
+}
+
+bool launch_conv1x1_stream(const StreamPlan& p, hipStream_t stream) {
+  const bool kt1 = p.KT == 1;
+  if (p.stats) return kt1 ? launch_stream<256, 1, true, true>(p, stream) : launch_stream<256, 2, true, true>(p, stream);
+  switch (p.BN + p.abn) {
+    case 128 + 1: return kt1 ? launch_stream<128, 1, true>(p, stream) : launch_stream<128, 2, true>(p, stream);
+    case 64 + 1: return kt1 ? launch_stream<64, 1, true>(p, stream) : launch_stream<64, 2, true>(p, stream);
+    case 128 + 0: return kt1 ? launch_stream<128, 1, false>(p, stream) : launch_stream<128, 2, false>(p, stream);
+    case 64 + 0: return kt1 ? launch_stream<64, 1, false>(p, stream) : launch_stream<64, 2, false>(p, stream);
   }
-  if (n128) return kt == 1 ? launch_stream<128, 1, false>(sd, stream) : launch_stream<128, 2, false>(sd, stream);
-  return kt == 1 ? launch_stream<64, 1, false>(sd, stream) : launch_stream<64, 2, false>(sd, stream);
+  return false;
 }
 
 }  // namespace gic

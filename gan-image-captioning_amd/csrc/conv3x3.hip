@@ -20,9 +20,7 @@
 // normalised tensor).
 #include <stdlib.h>
 
-#include <map>
 #include <mutex>
-#include <tuple>
 
 #include "conv3x3.h"
 #include "bn_fold.h"
@@ -58,20 +56,6 @@ __device__ __forceinline__ int fdiv(int a, int b, float inv) {
   q += (r >= b) - (r < 0);
   return q;
 }
-
-// Everything the kernel reads from its arguments, compact and in one struct: the scalar loads of a few adjacent cache lines leave in one
-// batch at the top (fields of the 384-byte GemmDesc, fetched where first used, cost the prologue five serial round trips: ~1.2 us).
-struct PatchDesc {
-  const void* A; const void* B; void* C; float* stats;
-  const float* in_stats; const float* in_gamma; const float* in_beta;
-  int M, N, H, W, Cin, ldb, ldc, stats_nrep, in_nrep;
-  float in_inv_count;
-  int tiles_m;              // row tiles
-  int tiles_n;              // > 0: output-channel tiles, and those of one row tile are neighbours on an XCD; 0: the row tiles of a channel tile are
-  int tpi;                  // > 0: tiles never cross an image (tpi tiles per image, the last one short); 0: 128 consecutive rows of M
-  int nchunks;              // Cin / 64
-  unsigned a_bytes, b_bytes;
-};
 
 // BN output channels per workgroup (64 | 128); P = 16-byte patch pieces per thread and chunk (patch buffer = P * 8 KB = 64 P pixels);
 // MULTI: more than one 64-channel chunk (double-buffered patch, the next chunk's pieces issued during the first P taps);
@@ -339,12 +323,13 @@ __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const PatchDesc d) {
 
 // largest patch (pixels) over the row tiles of an [Nimg, H, W] output: global tiling (128 consecutive rows) or per-image tiling
 int max_patch_pixels(int Nimg, int H, int W, bool per_image) {
+  struct Entry { int Nimg, H, W, per_image, px; };
+  static Entry cache[64];                    // a trunk has a handful of distinct maps; a shape past the last slot is computed every time
+  static int used = 0;
   static std::mutex mu;
-  static std::map<std::tuple<int, int, int, bool>, int> cache;
   std::lock_guard<std::mutex> lock(mu);
-  const auto key = std::make_tuple(Nimg, H, W, per_image);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
+  for (int i = 0; i < used; ++i)
+    if (cache[i].Nimg == Nimg && cache[i].H == H && cache[i].W == W && cache[i].per_image == (int)per_image) return cache[i].px;
   const long HW = (long)H * W, M = HW * Nimg;
   const int PH = H + 2, PW = W + 2;
   int best = 0;
@@ -359,66 +344,70 @@ int max_patch_pixels(int Nimg, int H, int W, bool per_image) {
   } else {
     for (long b = 0; b < M; b += 128) tile(b, b + 128 < M ? b + 128 : M);
   }
-  cache[key] = best;
+  if (used < 64) cache[used++] = {Nimg, H, W, (int)per_image, best};
   return best;
 }
 
 template <int BN, int P, bool MULTI, bool ABN>
-bool launch_patch(const PatchDesc& pd, long tiles, hipStream_t stream) {
-  constexpr size_t core = (size_t)(MULTI ? 2 : 1) * P * 8192 + 3 * BN * 128;
-  const size_t lds = core + (ABN ? (size_t)pd.Cin * 8 : 0);
+bool launch_patch(const PatchPlan& p, hipStream_t stream) {
   static LdsGrant granted;
-  if (!grant_lds(conv3x3_patch_kernel<BN, P, MULTI, ABN>, lds, granted)) return false;
-  hipLaunchKernelGGL((conv3x3_patch_kernel<BN, P, MULTI, ABN>), dim3((unsigned)tiles), dim3(512), lds, stream, pd);
+  if (!grant_lds(conv3x3_patch_kernel<BN, P, MULTI, ABN>, p.lds, granted)) return false;
+  hipLaunchKernelGGL((conv3x3_patch_kernel<BN, P, MULTI, ABN>), dim3(p.grid), dim3(512), p.lds, stream, p.d);
   return true;
 }
 
 template <int BN, bool ABN>
-bool pick_patch(const PatchDesc& pd, int P, long tiles, hipStream_t stream) {
-  if (pd.nchunks == 1) return P <= 6 ? launch_patch<BN, 6, false, ABN>(pd, tiles, stream) : (P <= 8 ? launch_patch<BN, 8, false, ABN>(pd, tiles, stream) : false);
-  if (P <= 4) return launch_patch<BN, 4, true, ABN>(pd, tiles, stream);
-  if (P == 5) return launch_patch<BN, 5, true, ABN>(pd, tiles, stream);
-  if (P == 6) return launch_patch<BN, 6, true, ABN>(pd, tiles, stream);
+bool launch_patch_p(const PatchPlan& p, hipStream_t stream) {
+  switch (p.P * 2 + p.multi) {
+    case 6 * 2 + 0: return launch_patch<BN, 6, false, ABN>(p, stream);
+    case 8 * 2 + 0: return launch_patch<BN, 8, false, ABN>(p, stream);
+    case 4 * 2 + 1: return launch_patch<BN, 4, true, ABN>(p, stream);
+    case 5 * 2 + 1: return launch_patch<BN, 5, true, ABN>(p, stream);
+    case 6 * 2 + 1: return launch_patch<BN, 6, true, ABN>(p, stream);
+  }
   return false;
 }
 
 }  // namespace
 
-bool try_conv3x3_patch(const GemmDesc& d, hipStream_t stream) {
+bool select_conv3x3_patch(const GemmDesc& d, PatchPlan& p) {
   static const bool off = getenv("GIC_NO_CONV3X3_PATCH") != nullptr;
-  if (off || !d.conv || d.epi != EPI_BNSTATS || !d.stats) return false;
-  if (d.in_dtype != DT_BF16 || d.out_dtype != DT_BF16) return false;
+  if (off || d.res) return false;
   if (d.cKH != 3 || d.cKW != 3 || d.cStride != 1 || d.cPad != 1 || d.cHo != d.cH || d.cWo != d.cW) return false;
-  if (d.cCin % 64 || d.cCin > 1024 || d.N % 8 || d.ldc % 8 || (((uintptr_t)d.C) & 15) || (((uintptr_t)d.A) & 15) || (((uintptr_t)d.B) & 15)) return false;
-  if (d.K != 9 * d.cCin || d.ldb % 8 || d.bias || d.alpha != 1.f || d.accumulate || d.res) return false;
-  const bool abn = d.in_stats != nullptr;
-  if (abn && (!d.in_gamma || !d.in_beta || d.in_inv_count <= 0.f || d.in_nrep < 1)) return false;
+  if (d.cCin % 64 || d.cCin > 1024 || d.N % 8 || d.ldc % 8 || d.K != 9 * d.cCin || d.ldb % 8) return false;
   const long HW = (long)d.cH * d.cW;
   if (HW <= 0 || d.M % HW || d.M >= (1 << 23)) return false;             // (the kernel's float-reciprocal divisions are exact below 2^23)
   const int Nimg = (int)(d.M / HW);
   const long a_elems = (long)d.M * d.cCin, b_elems = (long)(d.N - 1) * d.ldb + d.K;
-  if (a_elems * 2 >= (1l << 31) || b_elems * 2 >= (1l << 31)) return false;
-  PatchDesc pa;
-  pa.A = d.A; pa.B = d.B; pa.C = d.C; pa.stats = d.stats;
-  pa.in_stats = d.in_stats; pa.in_gamma = d.in_gamma; pa.in_beta = d.in_beta;
-  pa.M = d.M; pa.N = d.N; pa.H = d.cH; pa.W = d.cW; pa.Cin = d.cCin; pa.ldb = (int)d.ldb; pa.ldc = (int)d.ldc;
-  pa.stats_nrep = d.stats_nrep < 1 ? 1 : d.stats_nrep; pa.in_nrep = d.in_nrep; pa.in_inv_count = d.in_inv_count;
+  PatchDesc& pa = p.d;
+  if (!conv_base(d, a_elems, b_elems, pa)) return false;
+  pa.H = d.cH; pa.W = d.cW; pa.Cin = d.cCin;
   pa.nchunks = d.cCin / 64;
   // tiles that never cross an image need two halo rows less; taken where the short last tile of an image costs <= 5 % more tiles
   const int tpi = cdiv(HW, 128);
   const bool per_image = (double)tpi * 128 <= 1.05 * (double)HW;
-  const int max_pix = max_patch_pixels(Nimg, d.cH, d.cW, per_image);
-  const int P = (max_pix + 63) / 64;
+  const int pieces = (max_patch_pixels(Nimg, d.cH, d.cW, per_image) + 63) / 64;
   pa.tpi = per_image ? tpi : 0;
   pa.tiles_m = per_image ? tpi * Nimg : cdiv(d.M, 128);
   // output-channel tile: 128 where that still leaves about a workgroup per CU, else 64
   const bool n128 = d.N >= 128 && (long)pa.tiles_m * cdiv(d.N, 128) >= 160;
-  const long tiles = (long)pa.tiles_m * (n128 ? cdiv(d.N, 128) : cdiv(d.N, 64));
-  pa.a_bytes = (unsigned)(a_elems * 2); pa.b_bytes = (unsigned)(b_elems * 2);
   const int tiles_n = n128 ? cdiv(d.N, 128) : cdiv(d.N, 64);
   pa.tiles_n = xcd_share_a(a_elems * 2, b_elems * 2, tiles_n) ? tiles_n : 0;
-  if (abn) return n128 ? pick_patch<128, true>(pa, P, tiles, stream) : pick_patch<64, true>(pa, P, tiles, stream);
-  return n128 ? pick_patch<128, false>(pa, P, tiles, stream) : pick_patch<64, false>(pa, P, tiles, stream);
+  // the instantiated patch buffers: one chunk 6 | 8 pieces per thread, several chunks (double-buffered) 4 | 5 | 6
+  p.multi = pa.nchunks != 1;
+  if (p.multi) p.P = pieces <= 4 ? 4 : pieces;
+  else p.P = pieces <= 6 ? 6 : 8;
+  if (pieces > (p.multi ? 6 : 8)) return false;
+  p.BN = n128 ? 128 : 64;
+  p.abn = d.in_stats != nullptr;
+  p.grid = (unsigned)((long)pa.tiles_m * tiles_n);
+  p.lds = (size_t)(p.multi ? 2 : 1) * p.P * 8192 + 3 * (size_t)p.BN * 128 + (p.abn ? (size_t)pa.Cin * 8 : 0);
+  return true;
+}
+
+bool launch_conv3x3_patch(const PatchPlan& p, hipStream_t stream) {
+  if (p.abn) return p.BN == 128 ? launch_patch_p<128, true>(p, stream) : launch_patch_p<64, true>(p, stream);
+  return p.BN == 128 ? launch_patch_p<128, false>(p, stream) : launch_patch_p<64, false>(p, stream);
 }
 
 }  // namespace gic

@@ -17,7 +17,12 @@ struct B2bDesc {
   unsigned y2_bytes, res_bytes, y1n_bytes = 0;
 };
 
-// false: shapes it has no instantiation for (the caller runs the separate launches)
-bool try_conv_b2b(const B2bDesc& d, int C2, int C1N, hipStream_t stream);
+struct B2bPlan { B2bDesc d; int C2, C1N; bool ident; int tiles, per_cu; size_t lds; };   // conv_b2b_kernel<C2, C1N, IDENT>, grid = min(tiles, CUs * per_cu)
+
+// The shapes the kernel is instantiated for and can address: what gic_conv_b2b_supported answers and select_conv_b2b starts with
+bool conv_b2b_shape_ok(long rows, int C2, int C1N);
+// false: no instantiation for these shapes or operands (the caller runs the separate launches).  Fills d's byte extents.
+bool select_conv_b2b(const B2bDesc& d, int C2, int C1N, B2bPlan& p);
+bool launch_conv_b2b(const B2bPlan& p, hipStream_t stream);
 
 }  // namespace gic

@@ -354,43 +354,51 @@ __global__ __launch_bounds__(512) void conv_b2b_kernel(const B2bDesc d) {
 }
 
 template <int C2, int C1N, bool IDENT>
-bool launch_b2b(const B2bDesc& d, hipStream_t stream) {
-  constexpr int C3 = 4 * C2;
-  constexpr bool RES = C2 == 64;
-  constexpr int NT = 512;
-  constexpr size_t lds = (RES ? C3 / 64 : 3) * (size_t)(64 * C2 * 2 + C1N * 128) + (size_t)(C2 + 2 * C3) * 8;
-  static_assert(lds <= 160 * 1024, "conv_b2b LDS budget");
+bool launch_b2b(const B2bPlan& p, hipStream_t stream) {
   static LdsGrant granted;
-  if (!grant_lds(conv_b2b_kernel<C2, C1N, IDENT>, lds, granted)) return false;
-  // persistent workgroups per CU: as many as the LDS lets share a CU, two at most (measured: 3 and 4 lose)
-  static const int per_cu = [] { const char* e = getenv("GIC_B2B_WG_PER_CU"); return e && atoi(e) > 0 ? atoi(e) : (lds > 80 * 1024 ? 1 : 2); }();
+  if (!grant_lds(conv_b2b_kernel<C2, C1N, IDENT>, p.lds, granted)) return false;
   static const int cus = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); n = 256; }
     return n;
   }();
-  const int tiles = d.M / (NT / 4);
-  const int grid = tiles < cus * per_cu ? tiles : cus * per_cu;
-  hipLaunchKernelGGL((conv_b2b_kernel<C2, C1N, IDENT>), dim3((unsigned)grid), dim3(NT), lds, stream, d);
+  const int grid = p.tiles < cus * p.per_cu ? p.tiles : cus * p.per_cu;
+  hipLaunchKernelGGL((conv_b2b_kernel<C2, C1N, IDENT>), dim3((unsigned)grid), dim3(512), p.lds, stream, p.d);
   return true;
 }
 
 }  // namespace
 
-bool try_conv_b2b(const B2bDesc& d, int C2, int C1N, hipStream_t stream) {
+bool conv_b2b_shape_ok(long rows, int C2, int C1N) {
   static const bool off = getenv("GIC_NO_CONV_B2B") != nullptr;
-  if (off || d.M <= 0 || d.M % 128 || d.nrep1 < 1) return false;
-  B2bDesc dd = d;
-  dd.y1n_bytes = (unsigned)((long)d.M * C1N * 2);
-  const long C3 = 4l * C2;
-  if ((long)d.M * C3 * 2 >= (1l << 31)) return false;                    // 32-bit byte offsets into every activation
-  for (const void* p : {d.y2, d.w3, d.res, d.w1n, (const void*)d.out, (const void*)d.y1n})
-    if (!p || (((uintptr_t)p) & 15)) return false;
-  const bool ident = d.res_stats == nullptr;
-  if (C2 == 64 && C1N == 64) return ident ? launch_b2b<64, 64, true>(dd, stream) : launch_b2b<64, 64, false>(dd, stream);
-  if (C2 == 64 && C1N == 128) return ident ? launch_b2b<64, 128, true>(dd, stream) : launch_b2b<64, 128, false>(dd, stream);
-  if (C2 == 128 && C1N == 128) return ident ? launch_b2b<128, 128, true>(dd, stream) : launch_b2b<128, 128, false>(dd, stream);
-  if (C2 == 128 && C1N == 256) return ident ? launch_b2b<128, 256, true>(dd, stream) : launch_b2b<128, 256, false>(dd, stream);
+  if (off || rows <= 0 || rows % 128) return false;
+  if (!((C2 == 64 && (C1N == 64 || C1N == 128)) || (C2 == 128 && (C1N == 128 || C1N == 256)))) return false;
+  return rows * 4 * C2 * 2 < (1l << 31);                                 // 32-bit byte offsets into every activation
+}
+
+bool select_conv_b2b(const B2bDesc& d, int C2, int C1N, B2bPlan& p) {
+  if (!conv_b2b_shape_ok(d.M, C2, C1N) || d.nrep1 < 1) return false;
+  for (const void* q : {d.y2, d.w3, d.res, d.w1n, (const void*)d.out, (const void*)d.y1n})
+    if (!q || (((uintptr_t)q) & 15)) return false;
+  const int C3 = 4 * C2;
+  p.d = d;
+  p.d.y2_bytes = (unsigned)((long)d.M * C2 * 2); p.d.res_bytes = (unsigned)((long)d.M * C3 * 2); p.d.y1n_bytes = (unsigned)((long)d.M * C1N * 2);
+  p.C2 = C2; p.C1N = C1N; p.ident = d.res_stats == nullptr;
+  p.lds = (C2 == 64 ? C3 / 64 : 3) * (size_t)(64 * C2 * 2 + C1N * 128) + (size_t)(C2 + 2 * C3) * 8;
+  // persistent workgroups per CU: as many as the LDS lets share a CU, two at most (measured: 3 and 4 lose)
+  static const int wg_per_cu = [] { const char* e = getenv("GIC_B2B_WG_PER_CU"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
+  p.per_cu = wg_per_cu ? wg_per_cu : (p.lds > 80 * 1024 ? 1 : 2);
+  p.tiles = d.M / 128;
+  return true;
+}
+
+bool launch_conv_b2b(const B2bPlan& p, hipStream_t stream) {
+  switch (p.C2 + p.C1N) {                                                // (the four pairs of conv_b2b_shape_ok have distinct sums)
+    case 64 + 64: return p.ident ? launch_b2b<64, 64, true>(p, stream) : launch_b2b<64, 64, false>(p, stream);
+    case 64 + 128: return p.ident ? launch_b2b<64, 128, true>(p, stream) : launch_b2b<64, 128, false>(p, stream);
+    case 128 + 128: return p.ident ? launch_b2b<128, 128, true>(p, stream) : launch_b2b<128, 128, false>(p, stream);
+    case 128 + 256: return p.ident ? launch_b2b<128, 256, true>(p, stream) : launch_b2b<128, 256, false>(p, stream);
+  }
   return false;
 }
 

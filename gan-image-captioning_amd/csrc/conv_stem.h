@@ -4,8 +4,16 @@
 
 namespace gic {
 
-// Launches the streaming stem kernel if the convolution qualifies (window 7 x 8 over a pre-padded NHWC4 bf16 image, stride 2, 64 output
-// channels, output rows of <= 128 pixels, BatchNorm-sum epilogue) and returns true; false: nothing launched.
-bool try_conv_stem(const GemmDesc& d, hipStream_t stream);
+struct StemDesc : ConvBase {
+  int Nimg, H, W, Ho, Wo;
+  int ranges, rows_per_range;            // workgroups per image, output rows per workgroup
+};
+
+struct StemPlan { StemDesc d; unsigned grid; size_t lds; };
+
+// Qualifies: window 7 x 8 over a pre-padded NHWC4 bf16 image, stride 2, 64 output channels, output rows of <= 128 pixels, BatchNorm-sum
+// epilogue.
+bool select_conv_stem(const GemmDesc& d, StemPlan& p);
+bool launch_conv_stem(const StemPlan& p, hipStream_t stream);
 
 }  // namespace gic

@@ -20,13 +20,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-struct StemDesc {
-  const void* A; const void* B; void* C; float* stats;
-  int Nimg, H, W, Ho, Wo, ldc, stats_nrep;
-  int ranges, rows_per_range;            // workgroups per image, output rows per workgroup
-  unsigned a_bytes, b_bytes;
-};
-
 constexpr int kRing = 16;                // input-row slots (7 in use + 8 in flight)
 constexpr int kSlot = 2048;              // bytes per slot: two whole LDS-DMA wave instructions (a row is W * 8 <= 2048 bytes)
 constexpr int kAhead = 3;                // output rows whose input rows are in flight beyond the prologue's
@@ -143,34 +136,33 @@ __global__ __launch_bounds__(512) void conv_stem_kernel(const StemDesc d) {
 
 }  // namespace
 
-bool try_conv_stem(const GemmDesc& d, hipStream_t stream) {
+bool select_conv_stem(const GemmDesc& d, StemPlan& p) {
   static const bool off = getenv("GIC_NO_CONV_STEM") != nullptr;
-  if (off || !d.conv || d.epi != EPI_BNSTATS || !d.stats || d.in_stats || d.res) return false;
-  if (d.in_dtype != DT_BF16 || d.out_dtype != DT_BF16) return false;
+  if (off || d.in_stats || d.res) return false;
   if (d.cKH != 7 || d.cKW != 8 || d.cCin != 4 || d.cStride != 2 || d.cPad != 0 || d.N != 64 || d.K != 224 || d.ldb != 224) return false;
   if (d.cW % 2 || d.cW * 8 > kSlot || d.cWo > 128 || d.cWo < 1 || d.ldc % 8) return false;
   if (2 * (d.cWo - 1) + 8 > d.cW || 2 * (d.cHo - 1) + 7 > d.cH) return false;                 // windows inside the (pre-padded) image
-  if ((((uintptr_t)d.C) & 15) || (((uintptr_t)d.A) & 15) || (((uintptr_t)d.B) & 15) || d.bias || d.alpha != 1.f || d.accumulate) return false;
   const long HoWo = (long)d.cHo * d.cWo;
   if (HoWo <= 0 || d.M % HoWo) return false;
-  StemDesc sd;
+  StemDesc& sd = p.d;
   sd.Nimg = (int)(d.M / HoWo);
-  const long a_elems = (long)sd.Nimg * d.cH * d.cW * 4, b_elems = 64l * 224;
-  if (a_elems * 2 >= (1l << 31)) return false;
+  if (!conv_base(d, (long)sd.Nimg * d.cH * d.cW * 4, 64l * 224, sd)) return false;
   // about one persistent workgroup per CU: split every image's output rows into ranges
   int ranges = 256 / sd.Nimg;
   if (ranges < 1) ranges = 1;
   if (ranges > d.cHo) ranges = d.cHo;
   sd.rows_per_range = cdiv(d.cHo, ranges);
   sd.ranges = cdiv(d.cHo, sd.rows_per_range);
-  sd.A = d.A; sd.B = d.B; sd.C = d.C; sd.stats = d.stats;
-  sd.H = d.cH; sd.W = d.cW; sd.Ho = d.cHo; sd.Wo = d.cWo; sd.ldc = (int)d.ldc;
-  sd.stats_nrep = d.stats_nrep < 1 ? 1 : d.stats_nrep;
-  sd.a_bytes = (unsigned)(a_elems * 2); sd.b_bytes = (unsigned)(b_elems * 2);
-  constexpr size_t lds = (size_t)kRing * kSlot + 7 * 4 * 64 * 16 + 2 * 128 * (64 * 2 + 16) + 2 * 64 * 2 * 4;
+  sd.H = d.cH; sd.W = d.cW; sd.Ho = d.cHo; sd.Wo = d.cWo;
+  p.grid = (unsigned)(sd.Nimg * sd.ranges);
+  p.lds = (size_t)kRing * kSlot + 7 * 4 * 64 * 16 + 2 * 128 * (64 * 2 + 16) + 2 * 64 * 2 * 4;
+  return true;
+}
+
+bool launch_conv_stem(const StemPlan& p, hipStream_t stream) {
   static LdsGrant granted;
-  if (!grant_lds(conv_stem_kernel, lds, granted)) return false;
-  hipLaunchKernelGGL(conv_stem_kernel, dim3((unsigned)(sd.Nimg * sd.ranges)), dim3(512), lds, stream, sd);
+  if (!grant_lds(conv_stem_kernel, p.lds, granted)) return false;
+  hipLaunchKernelGGL(conv_stem_kernel, dim3(p.grid), dim3(512), p.lds, stream, p.d);
   return true;
 }
 

@@ -345,6 +345,26 @@ BnSrc make_src(const float* stats, int nrep, const float* gamma, const float* be
   return s;
 }
 
+// The implicit-GEMM descriptor of an NHWC convolution (gemm.h): dimensions, window, and the BatchNorm-sum epilogue when `stats` is given
+GemmDesc conv_desc(const void* in, const void* w, void* out, float* stats, int stats_nrep, int dtype, int N, int H, int W, int Cin, int Cout,
+                   int KH, int KW, int stride, int pad) {
+  const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+  GemmDesc g;
+  g.A = in; g.B = w; g.C = out;
+  g.M = N * Ho * Wo; g.N = Cout; g.K = KH * KW * Cin;
+  g.lda = Cin; g.ldb = g.K; g.ldc = Cout;
+  g.in_dtype = dtype; g.out_dtype = dtype;
+  g.conv = 1; g.cH = H; g.cW = W; g.cCin = Cin; g.cHo = Ho; g.cWo = Wo; g.cKH = KH; g.cKW = KW; g.cStride = stride; g.cPad = pad;
+  g.epi = stats ? EPI_BNSTATS : EPI_PLAIN;
+  g.stats = stats;
+  g.stats_nrep = stats_nrep < 1 ? 1 : stats_nrep;
+  return g;
+}
+
+void bn_on_load(GemmDesc& g, const float* in_stats, int in_nrep, const float* in_gamma, const float* in_beta, float in_count) {
+  g.in_stats = in_stats; g.in_nrep = in_nrep; g.in_gamma = in_gamma; g.in_beta = in_beta; g.in_inv_count = 1.f / in_count;
+}
+
 }  // namespace
 }  // namespace gic
 
@@ -386,16 +406,7 @@ int gic_conv2d(const void* in, const void* w, void* out, float* stats, int stats
   GIC_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0, "conv2d: bad dims");
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   GIC_CHECK_ARG(Ho > 0 && Wo > 0, "conv2d: empty output");
-  GemmDesc g;
-  g.A = in; g.B = w; g.C = out;
-  g.M = N * Ho * Wo; g.N = Cout; g.K = KH * KW * Cin;
-  g.lda = Cin; g.ldb = g.K; g.ldc = Cout;
-  g.in_dtype = dtype; g.out_dtype = dtype;
-  g.conv = 1; g.cH = H; g.cW = W; g.cCin = Cin; g.cHo = Ho; g.cWo = Wo; g.cKH = KH; g.cKW = KW; g.cStride = stride; g.cPad = pad;
-  g.epi = stats ? EPI_BNSTATS : EPI_PLAIN;
-  g.stats = stats;
-  g.stats_nrep = stats_nrep < 1 ? 1 : stats_nrep;
-  return gemm(g, (hipStream_t)stream);
+  return gemm(conv_desc(in, w, out, stats, stats_nrep, dtype, N, H, W, Cin, Cout, KH, KW, stride, pad), (hipStream_t)stream);
 }
 
 int gic_conv2d_bn_in(const void* in, const float* in_stats, int in_nrep, const float* in_gamma, const float* in_beta, float in_count,
@@ -406,16 +417,8 @@ int gic_conv2d_bn_in(const void* in, const float* in_stats, int in_nrep, const f
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   GIC_CHECK_ARG(Ho > 0 && Wo > 0, "conv2d_bn_in: empty output");
   if (dtype != DT_BF16) return GIC_ERR_UNSUPPORTED;
-  GemmDesc g;
-  g.A = in; g.B = w; g.C = out;
-  g.M = N * Ho * Wo; g.N = Cout; g.K = KH * KW * Cin;
-  g.lda = Cin; g.ldb = g.K; g.ldc = Cout;
-  g.in_dtype = dtype; g.out_dtype = dtype;
-  g.conv = 1; g.cH = H; g.cW = W; g.cCin = Cin; g.cHo = Ho; g.cWo = Wo; g.cKH = KH; g.cKW = KW; g.cStride = stride; g.cPad = pad;
-  g.epi = EPI_BNSTATS;
-  g.stats = stats;
-  g.stats_nrep = stats_nrep < 1 ? 1 : stats_nrep;
-  g.in_stats = in_stats; g.in_nrep = in_nrep; g.in_gamma = in_gamma; g.in_beta = in_beta; g.in_inv_count = 1.f / in_count;
+  GemmDesc g = conv_desc(in, w, out, stats, stats_nrep, dtype, N, H, W, Cin, Cout, KH, KW, stride, pad);
+  bn_on_load(g, in_stats, in_nrep, in_gamma, in_beta, in_count);
   return gemm(g, (hipStream_t)stream);
 }
 
@@ -424,18 +427,15 @@ int gic_conv1x1_bn_in_stats(const void* in, const float* in_stats, int in_nrep, 
   GIC_CHECK_ARG(in && in_stats && in_gamma && in_beta && w && stats && in_count > 0 && in_nrep >= 1 && rows > 0 && Cin > 0 && Cout > 0,
                 "conv1x1_bn_in_stats: bad argument");
   if (dtype != DT_BF16 || rows >= (1l << 31)) return GIC_ERR_UNSUPPORTED;
-  GemmDesc g;
-  g.A = in; g.B = w; g.C = (void*)in;                       // never written (stats_only): any non-null pointer
-  g.M = (int)rows; g.N = Cout; g.K = Cin;
-  g.lda = Cin; g.ldb = g.K; g.ldc = Cout;
-  g.in_dtype = dtype; g.out_dtype = dtype;
-  g.conv = 1; g.cH = 1; g.cW = (int)rows; g.cCin = Cin; g.cHo = 1; g.cWo = (int)rows; g.cKH = 1; g.cKW = 1; g.cStride = 1; g.cPad = 0;
-  g.epi = EPI_BNSTATS;
-  g.stats = stats;
-  g.stats_nrep = stats_nrep < 1 ? 1 : stats_nrep;
-  g.in_stats = in_stats; g.in_nrep = in_nrep; g.in_gamma = in_gamma; g.in_beta = in_beta; g.in_inv_count = 1.f / in_count;
+  // one image of 1 x rows pixels; C is never written (stats_only): any non-null pointer
+  GemmDesc g = conv_desc(in, w, (void*)in, stats, stats_nrep, dtype, 1, 1, (int)rows, Cin, Cout, 1, 1, 1, 0);
+  bn_on_load(g, in_stats, in_nrep, in_gamma, in_beta, in_count);
   g.stats_only = 1;
   return gemm(g, (hipStream_t)stream);
+}
+
+int gic_conv_b2b_supported(int dtype, int64_t rows, int C2, int C1N) {
+  return dtype == DT_BF16 && rows < (1l << 31) && conv_b2b_shape_ok(rows, C2, C1N);
 }
 
 int gic_conv_b2b(const void* y2, const float* stats2, int nrep2, const float* gamma2, const float* beta2, const void* w3, const float* stats3,
@@ -445,16 +445,22 @@ int gic_conv_b2b(const void* y2, const float* stats2, int nrep2, const float* ga
   GIC_CHECK_ARG(y2 && stats2 && gamma2 && beta2 && w3 && stats3 && gamma3 && beta3 && res && block_out && w1n && y1n && stats1 && count > 0 &&
                     nrep2 >= 1 && nrep3 >= 1 && rows > 0, "conv_b2b: bad argument");
   GIC_CHECK_ARG(!res_stats || (res_gamma && res_beta && res_nrep >= 1), "conv_b2b: the shortcut's BatchNorm needs gamma and beta");
-  if (dtype != DT_BF16 || rows >= (1l << 31)) return GIC_ERR_UNSUPPORTED;
+  const bool probe = route_only();
+  if (probe) snprintf(route_line(), kRouteLen, "unsupported");
+  if (!gic_conv_b2b_supported(dtype, rows, C2, C1N)) return GIC_ERR_UNSUPPORTED;
   B2bDesc d;
   d.y2 = y2; d.w3 = w3; d.res = res; d.w1n = w1n; d.out = block_out; d.y1n = y1n;
   d.stats2 = stats2; d.gamma2 = gamma2; d.beta2 = beta2; d.stats3 = stats3; d.gamma3 = gamma3; d.beta3 = beta3;
   d.res_stats = res_stats; d.res_gamma = res_gamma; d.res_beta = res_beta; d.stats1 = stats1;
   d.nrep2 = nrep2; d.nrep3 = nrep3; d.res_nrep = res_nrep; d.nrep1 = nrep1 < 1 ? 1 : nrep1;
   d.inv_count = 1.f / count; d.M = (int)rows;
-  if (rows * C2 * 2 >= (1l << 31) || rows * 4 * C2 * 2 >= (1l << 31)) return GIC_ERR_UNSUPPORTED;
-  d.y2_bytes = (unsigned)(rows * C2 * 2); d.res_bytes = (unsigned)(rows * 4 * C2 * 2);
-  if (!try_conv_b2b(d, C2, C1N, (hipStream_t)stream)) return GIC_ERR_UNSUPPORTED;
+  B2bPlan p;
+  if (!select_conv_b2b(d, C2, C1N, p)) return GIC_ERR_UNSUPPORTED;
+  if (probe) {
+    snprintf(route_line(), kRouteLen, "conv_b2b<%d,%d,%s> grid=min(%d,%d*cus) block=512 lds=%zu", p.C2, p.C1N, p.ident ? "true" : "false", p.tiles, p.per_cu, p.lds);
+    return GIC_OK;
+  }
+  if (!launch_conv_b2b(p, (hipStream_t)stream)) return GIC_ERR_UNSUPPORTED;
   GIC_CHECK_LAUNCH("conv_b2b");
   return GIC_OK;
 }
@@ -466,16 +472,8 @@ int gic_conv1x1_res_in(const void* in, const float* in_stats, int in_nrep, const
   GIC_CHECK_ARG(!res_stats || (res_gamma && res_beta && res_nrep >= 1), "conv1x1_res_in: the shortcut's BatchNorm needs gamma and beta");
   GIC_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv1x1_res_in: bad dims");
   if (dtype != DT_BF16) return GIC_ERR_UNSUPPORTED;
-  GemmDesc g;
-  g.A = in; g.B = w; g.C = out;
-  g.M = N * H * W; g.N = Cout; g.K = Cin;
-  g.lda = Cin; g.ldb = g.K; g.ldc = Cout;
-  g.in_dtype = dtype; g.out_dtype = dtype;
-  g.conv = 1; g.cH = H; g.cW = W; g.cCin = Cin; g.cHo = H; g.cWo = W; g.cKH = 1; g.cKW = 1; g.cStride = 1; g.cPad = 0;
-  g.epi = EPI_BNSTATS;
-  g.stats = stats;
-  g.stats_nrep = stats_nrep < 1 ? 1 : stats_nrep;
-  g.in_stats = in_stats; g.in_nrep = in_nrep; g.in_gamma = in_gamma; g.in_beta = in_beta; g.in_inv_count = 1.f / count;
+  GemmDesc g = conv_desc(in, w, out, stats, stats_nrep, dtype, N, H, W, Cin, Cout, 1, 1, 1, 0);
+  bn_on_load(g, in_stats, in_nrep, in_gamma, in_beta, count);
   g.res = res; g.res_stats = res_stats; g.res_nrep = res_nrep; g.res_gamma = res_gamma; g.res_beta = res_beta; g.res_inv_count = 1.f / count;
   g.out_wb = block_out;
   return gemm(g, (hipStream_t)stream);

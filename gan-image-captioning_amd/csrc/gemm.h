@@ -80,6 +80,35 @@ struct GemmDesc {
 // Enqueue on `stream`. Returns GIC_OK or a negative Status (message via gic_last_error()).
 int gemm(const GemmDesc& d, hipStream_t stream);
 
+// Every kernel family of the dispatch comes as a pair: select_*(shapes, plan) is a pure host function (no HIP call, no launch, no heap) that
+// answers false or fills a plan -- the kernel's descriptor, the template arguments as plain values, the grid and the dynamic LDS bytes --
+// and launch_*(plan, stream) asks for the LDS grant, switches on the variant and launches, with no condition on shapes or pointers of its
+// own (false: the grant was refused, the caller goes on to its next candidate).
+
+// What the trunk's convolution kernels (conv_stem / conv3x3 / conv1x1_stream / conv1x1_pix / conv1x1_panel .hip) share of a GemmDesc; their
+// descriptors derive from it.
+struct ConvBase {
+  const void* A; const void* B; void* C; float* stats;
+  const float* in_stats; const float* in_gamma; const float* in_beta;
+  int M, N, lda, ldb, ldc, stats_nrep, in_nrep;
+  float in_inv_count;
+  unsigned a_bytes, b_bytes;
+};
+
+// BatchNorm on load: the coefficients' sources are all there
+inline bool bn_in_args_ok(const GemmDesc& d) { return d.in_gamma && d.in_beta && d.in_inv_count > 0.f; }
+
+// The preconditions those kernels have in common -- a bf16 convolution with the BatchNorm-sum epilogue and nothing else in it (no bias, alpha
+// or accumulate), 16-byte aligned A, B and C, valid BatchNorm-on-load arguments if any, both operands (a_elems / b_elems elements, which the
+// caller derives from its own window) under 2 GiB -- and, when they hold, the shared fields.
+bool conv_base(const GemmDesc& d, long a_elems, long b_elems, ConvBase& b);
+
+// Route-only mode (gic_debug_route_only, util.hip): gemm(), gemm_gumbelmax() and gic_conv_b2b validate and select, write the plan as one
+// line into route_line() and return their status without touching the GPU.
+bool route_only();
+char* route_line();                    // thread-local, kRouteLen bytes
+constexpr int kRouteLen = 160;
+
 // The vocabulary product of an ids-only roll-out step fused with Gumbel-max (EPI_GUMBELMAX above): bf16 k-contiguous operands, M = V a
 // multiple of 4, many roll-out rows (the 8-wave kernel's grid conditions).  GIC_ERR_UNSUPPORTED (no message) when the shapes do not
 // qualify: the caller runs the product and the Gumbel-argmax kernel separately.

@@ -1058,114 +1058,100 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
   STAMP(5);
 }
 
-// Launch the 8-wave kernel if the product qualifies (bf16 k-contiguous operands under 2 GiB each, a plain / BatchNorm-sum
-// epilogue that overwrites a 16-byte-aligned C); returns false to fall back to gemm_kernel.
-template <typename TO, int EPI, bool CONV>
-bool try_tile8(const GemmDesc& d_in, hipStream_t stream) {
+// ---------------------------------------------------------------------------------------------------- selection (pure host code)
+
+// tile8_kernel<TO, BN, EPI, CONV, NS, ABN, ARES, AMAXK>; TO, EPI and CONV are the descriptor's
+struct Tile8Plan { int BN, NS; bool abn, ares; int amaxk; unsigned grid, a_bytes, b_bytes; };
+// gemm_kernel<TI, TO, AKC, BKC, BM, BM, VEC, EPI, CONV, PIPE> over dim3(tiles, splits), `per` K tiles per split; zero_grid > 0: C is
+// zero-filled first (split-K adds into it)
+struct Gemm4Plan { int bm; bool vec, pipe; int tiles, splits, per, zero_grid; };
+
+enum Family { F_NONE = 0, F_STEM, F_PATCH, F_STREAM, F_PIX, F_PANEL, F_TILE8, F_GEMM4 };
+
+struct Plan {
+  int family = F_NONE;
+  GemmDesc d;               // what the 8-wave and 4-wave kernels take as their argument (tile8: with n_fast chosen)
+  StemPlan stem; PatchPlan patch; StreamPlan strm; PixPlan pix; PanelPlan panel; Tile8Plan t8; Gemm4Plan g4;
+};
+
+bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+
+// The 8-wave kernel qualifies: bf16 k-contiguous operands under 2 GiB each, a plain / BatchNorm-sum epilogue that overwrites a 16-byte-aligned
+// C (or the highway epilogue).  false: fall back to gemm_kernel.
+bool select_tile8(const GemmDesc& d, Tile8Plan& p, int& n_fast) {
   static const bool off = getenv("GIC_NO_TILE8") != nullptr;
-  GemmDesc d = d_in;
-  constexpr int OVE = 16 / (int)sizeof(TO);
+  static const int big_min = env_int("GIC_TILE8_BIG_MIN", 160), ns2_tiles = env_int("GIC_TILE8_NS2_TILES", 256), min_nk = env_int("GIC_TILE8_MIN_NK", 1);
+  static const int res_ns = env_int("GIC_TILE8_RES_NS", 1), ns1_nk = env_int("GIC_TILE8_NS1_NK", 4);
+  const int OVE = 16 / dtype_size(d.out_dtype);
+  const bool highway = d.epi == EPI_HIGHWAY;
   if (off || d.M < 128) return false;
-  if (EPI != EPI_HIGHWAY && ((d.N % OVE) || (d.ldc % OVE) || (((uintptr_t)d.C) & 15))) return false;
-  if (EPI == EPI_HIGHWAY && d.in_dtype != DT_BF16) return false;
+  if (!highway && ((d.N % OVE) || (d.ldc % OVE) || !aligned16(d.C))) return false;
+  if (highway && d.in_dtype != DT_BF16) return false;
+  const long small_tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 64), big_tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
   // a plain product must fill the chip with 128-row tiles and be deep enough to amortise the ring (else: gemm_kernel, split-K)
-  if (!CONV && ((long)cdiv(d.M, 128) * cdiv(d.N, 64) < 128 || d.K < 256)) return false;
-  const long a_elems = CONV ? (long)(d.M / (d.cHo * d.cWo)) * d.cH * d.cW * d.cCin : (long)(d.M - 1) * d.lda + d.K;
+  if (!d.conv && (small_tiles < 128 || d.K < 256)) return false;
+  const long a_elems = d.conv ? (long)(d.M / (d.cHo * d.cWo)) * d.cH * d.cW * d.cCin : (long)(d.M - 1) * d.lda + d.K;
   const long b_elems = (long)(d.N - 1) * d.ldb + d.K;
   if (a_elems * 2 >= (1l << 31) || b_elems * 2 >= (1l << 31)) return false;
-  const long big_tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
-  static const int big_min = [] { const char* e = getenv("GIC_TILE8_BIG_MIN"); return e ? atoi(e) : 160; }();
-  static const int ns2_tiles = [] { const char* e = getenv("GIC_TILE8_NS2_TILES"); return e ? atoi(e) : 256; }();
-  static const int min_nk = [] { const char* e = getenv("GIC_TILE8_MIN_NK"); return e ? atoi(e) : 1; }();
-  if (cdiv(d.K, 64) < min_nk) return false;
-  const unsigned ab = (unsigned)(a_elems * 2), bb = (unsigned)(b_elems * 2);
-  // what an XCD's concurrent workgroups share (common.h): A bytes actually gathered (a strided 1x1 touches 1 / stride^2 of its input)
-  d.n_fast = xcd_share_a(2 * (a_elems < (long)d.M * d.K ? a_elems : (long)d.M * d.K), 2l * d.N * d.K, cdiv(d.N, d.N >= 128 ? 128 : 64));
+  const int nk = cdiv(d.K, 64);
+  if (nk < min_nk) return false;
+  p.a_bytes = (unsigned)(a_elems * 2); p.b_bytes = (unsigned)(b_elems * 2);
+  p.abn = p.ares = false; p.amaxk = 1024;
   // deep ring (4 stages, 128 KB: one block per CU) when the grid is about one block per CU; with several blocks per CU a
   // 2-stage ring (64 KB) lets two blocks share the CU so one block's epilogue runs under the other's K loop
-  if constexpr (EPI == EPI_BNSTATS && CONV) {
-    if (d.in_stats && d.res) {      // + residual on load: 1x1 / stride 1 / pad 0 only, one- or two-stage ring (two tiles per stage on the A side)
-      if (d.cKH != 1 || d.cKW != 1 || d.cStride != 1 || d.cPad != 0 || d.cCin % 8 || d.cCin > 2048 || !d.in_gamma || !d.in_beta ||
-          d.in_inv_count <= 0.f || (d.res_stats && (!d.res_gamma || !d.res_beta || d.res_inv_count <= 0.f)))
-        return false;
-      const bool n128 = d.N >= 128;
-      const long tiles = n128 ? big_tiles : (long)cdiv(d.M, 128) * cdiv(d.N, 64);
-      const dim3 grid((unsigned)tiles), block(512);
-      // ring-less (one stage: two A-side tiles + B): 2-3 workgroups share a CU and cover each other's DMA latency and LDS rewrite;
-      // the coefficient table is sized by the channel count (512 -> 8 KB, 2048 -> 32 KB)
-      static const int res_ns = [] { const char* e = getenv("GIC_TILE8_RES_NS"); return e ? atoi(e) : 1; }();
-      if (d.cCin <= 512) {
-        if (res_ns == 1) {
-          if (n128) hipLaunchKernelGGL((tile8_kernel<TO, 128, EPI, CONV, 1, true, true, 512>), grid, block, 0, stream, d, ab, bb);
-          else hipLaunchKernelGGL((tile8_kernel<TO, 64, EPI, CONV, 1, true, true, 512>), grid, block, 0, stream, d, ab, bb);
-        } else {
-          if (n128) hipLaunchKernelGGL((tile8_kernel<TO, 128, EPI, CONV, 2, true, true, 512>), grid, block, 0, stream, d, ab, bb);
-          else hipLaunchKernelGGL((tile8_kernel<TO, 64, EPI, CONV, 2, true, true, 512>), grid, block, 0, stream, d, ab, bb);
-        }
-      } else {
-        if (res_ns == 1) {
-          if (n128) hipLaunchKernelGGL((tile8_kernel<TO, 128, EPI, CONV, 1, true, true, 2048>), grid, block, 0, stream, d, ab, bb);
-          else hipLaunchKernelGGL((tile8_kernel<TO, 64, EPI, CONV, 1, true, true, 2048>), grid, block, 0, stream, d, ab, bb);
-        } else {
-          if (n128) hipLaunchKernelGGL((tile8_kernel<TO, 128, EPI, CONV, 2, true, true, 2048>), grid, block, 0, stream, d, ab, bb);
-          else hipLaunchKernelGGL((tile8_kernel<TO, 64, EPI, CONV, 2, true, true, 2048>), grid, block, 0, stream, d, ab, bb);
-        }
-      }
-      return true;
-    }
-    if (d.in_stats) {      // A-side BatchNorm + ReLU: whole 16-byte chunks per tap, channels within the LDS table
-      if (d.cCin % 8 || d.cCin > 1024 || !d.in_gamma || !d.in_beta || d.in_inv_count <= 0.f) return false;
-      const int nk = cdiv(d.K, 64);
-      const bool n128 = d.N >= 128 && big_tiles >= big_min;
-      const long tiles = n128 ? big_tiles : (long)cdiv(d.M, 128) * cdiv(d.N, 64);
-      const dim3 grid((unsigned)tiles), block(512);
-      if (nk <= 4 && tiles > 512) {
-        if (n128) hipLaunchKernelGGL((tile8_kernel<TO, 128, EPI, CONV, 1, true>), grid, block, 0, stream, d, ab, bb);
-        else hipLaunchKernelGGL((tile8_kernel<TO, 64, EPI, CONV, 1, true>), grid, block, 0, stream, d, ab, bb);
-      } else if (tiles > 256) {
-        if (n128) hipLaunchKernelGGL((tile8_kernel<TO, 128, EPI, CONV, 2, true>), grid, block, 0, stream, d, ab, bb);
-        else hipLaunchKernelGGL((tile8_kernel<TO, 64, EPI, CONV, 2, true>), grid, block, 0, stream, d, ab, bb);
-      } else {
-        if (n128) hipLaunchKernelGGL((tile8_kernel<TO, 128, EPI, CONV, 4, true>), grid, block, 0, stream, d, ab, bb);
-        else hipLaunchKernelGGL((tile8_kernel<TO, 64, EPI, CONV, 4, true>), grid, block, 0, stream, d, ab, bb);
-      }
-      return true;
-    }
-  }
-  static const int ns1_nk = [] { const char* e = getenv("GIC_TILE8_NS1_NK"); return e ? atoi(e) : 4; }();
-  const int nk8 = cdiv(d.K, 64);
-  if (EPI != EPI_HIGHWAY && nk8 <= ns1_nk && (d.N >= 128 ? big_tiles : (long)cdiv(d.M, 128) * cdiv(d.N, 64)) > 512) {
-    if (d.N >= 128) hipLaunchKernelGGL((tile8_kernel<TO, 128, EPI, CONV, 1>), dim3((unsigned)big_tiles), dim3(512), 0, stream, d, ab, bb);
-    else hipLaunchKernelGGL((tile8_kernel<TO, 64, EPI, CONV, 1>), dim3((unsigned)(cdiv(d.M, 128) * cdiv(d.N, 64))), dim3(512), 0, stream, d, ab, bb);
-    return true;
-  }
-  if (d.N >= 128 && big_tiles >= big_min) {
-    if (big_tiles > ns2_tiles) hipLaunchKernelGGL((tile8_kernel<TO, 128, EPI, CONV, 2>), dim3((unsigned)big_tiles), dim3(512), 0, stream, d, ab, bb);
-    else hipLaunchKernelGGL((tile8_kernel<TO, 128, EPI, CONV, 4>), dim3((unsigned)big_tiles), dim3(512), 0, stream, d, ab, bb);
+  bool n128;
+  if (d.epi == EPI_BNSTATS && d.conv && d.in_stats && d.res) {
+    // + residual on load: 1x1 / stride 1 / pad 0 only, one- or two-stage ring (two tiles per stage on the A side)
+    if (d.cKH != 1 || d.cKW != 1 || d.cStride != 1 || d.cPad != 0 || d.cCin % 8 || d.cCin > 2048 || !bn_in_args_ok(d) ||
+        (d.res_stats && (!d.res_gamma || !d.res_beta || d.res_inv_count <= 0.f)))
+      return false;
+    // ring-less (one stage: two A-side tiles + B): 2-3 workgroups share a CU and cover each other's DMA latency and LDS rewrite;
+    // the coefficient table is sized by the channel count (512 -> 8 KB, 2048 -> 32 KB)
+    n128 = d.N >= 128;
+    p.abn = p.ares = true; p.amaxk = d.cCin <= 512 ? 512 : 2048;
+    p.NS = res_ns == 1 ? 1 : 2;
+  } else if (d.epi == EPI_BNSTATS && d.conv && d.in_stats) {
+    // A-side BatchNorm + ReLU: whole 16-byte chunks per tap, channels within the LDS table
+    if (d.cCin % 8 || d.cCin > 1024 || !bn_in_args_ok(d)) return false;
+    n128 = d.N >= 128 && big_tiles >= big_min;
+    const long tiles = n128 ? big_tiles : small_tiles;
+    p.abn = true;
+    p.NS = nk <= 4 && tiles > 512 ? 1 : (tiles > 256 ? 2 : 4);
+  } else if (!highway && nk <= ns1_nk && (d.N >= 128 ? big_tiles : small_tiles) > 512) {
+    n128 = d.N >= 128;
+    p.NS = 1;
   } else {
-    const long tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 64);
-    if (tiles > ns2_tiles) hipLaunchKernelGGL((tile8_kernel<TO, 64, EPI, CONV, 2>), dim3((unsigned)tiles), dim3(512), 0, stream, d, ab, bb);
-    else hipLaunchKernelGGL((tile8_kernel<TO, 64, EPI, CONV, 4>), dim3((unsigned)tiles), dim3(512), 0, stream, d, ab, bb);
+    n128 = d.N >= 128 && big_tiles >= big_min;
+    p.NS = (n128 ? big_tiles : small_tiles) > ns2_tiles ? 2 : 4;
   }
+  p.BN = n128 ? 128 : 64;
+  p.grid = (unsigned)(n128 ? big_tiles : small_tiles);
+  // what an XCD's concurrent workgroups share (common.h): A bytes actually gathered (a strided 1x1 touches 1 / stride^2 of its input)
+  n_fast = xcd_share_a(2 * (a_elems < (long)d.M * d.K ? a_elems : (long)d.M * d.K), 2l * d.N * d.K, cdiv(d.N, d.N >= 128 ? 128 : 64));
   return true;
 }
 
-
-__global__ void zero2d_kernel(float* __restrict__ C, long ldc, int M, int N) {
-  const long total = (long)M * N;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
-    C[(i / N) * ldc + (i % N)] = 0.f;
+// 128x128 tiles only when there are enough of them to co-schedule two blocks per CU (latency hiding by TLP);
+// GIC_GEMM_BIG_MIN overrides the threshold for tuning runs.
+int big_tile_min() {
+  static const int v = env_int("GIC_GEMM_BIG_MIN", 192);
+  return v;
 }
 
-template <typename TI, typename TO, bool AKC, bool BKC, int BM, int BN, bool VEC, int EPI, bool CONV = false>
-int launch(const GemmDesc& d, hipStream_t stream) {
-  constexpr int BK = 128 / (int)sizeof(TI);
-  const int tiles = cdiv(d.M, BM) * cdiv(d.N, BN);
-  const int nk = cdiv(d.K, BK);
+// The 4-wave kernel takes every product the validation lets through: tile size, split-K and the pipeline
+void select_gemm4(const GemmDesc& d, bool vec, Gemm4Plan& p) {
+  // 128x128 tiles when they still give >= ~1 block per CU, else 64x64
+  const long big_tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
+  p.bm = big_tiles >= big_tile_min() && d.N >= 128 && (d.conv || d.M >= 128) ? 128 : 64;
+  p.vec = vec;
+  const bool bf16_in = d.in_dtype == DT_BF16;
+  p.tiles = cdiv(d.M, p.bm) * cdiv(d.N, p.bm);
+  const int tiles = p.tiles, nk = cdiv(d.K, bf16_in ? 64 : 32);
   // split-K only where the tile grid leaves most of the 256 CUs idle and K is deep enough to share
   int splits = 1;
   // (bf16 compute mode only: the f32 parity mode stays bit-reproducible run to run, atomics reorder the f32 sum)
-  if (EPI == EPI_PLAIN && sizeof(TI) == 2 && sizeof(TO) == 4 && !d.no_split) {
+  if (d.epi == EPI_PLAIN && bf16_in && d.out_dtype == DT_F32 && !d.no_split) {
     if (tiles < 24 && nk >= 8) {                 // skinny recurrent / head products: fill the chip
       splits = 256 / tiles;
       if (splits > nk / 2) splits = nk / 2;
@@ -1174,7 +1160,7 @@ int launch(const GemmDesc& d, hipStream_t stream) {
       splits = 512 / tiles;
       if (splits > nk / 8) splits = nk / 8;
       if (splits > 16) splits = 16;
-    } else if (!AKC && !BKC && tiles <= 192 && nk >= 16) {   // weight-gradient form (both operands row-major over K = B*L rows) over few tiles:
+    } else if (!d.a_kc && !d.b_kc && tiles <= 192 && nk >= 16) {   // weight-gradient form (both operands row-major over K = B*L rows) over few tiles:
       splits = 512 / tiles;                      // the D embedding gradient, 157 tiles x K = 1280
       if (splits > nk / 4) splits = nk / 4;
     } else if (tiles <= 320 && nk >= 64) {       // about one 4-wave block per CU over a very deep K (the highway weight gradient: 225 tiles,
@@ -1185,127 +1171,245 @@ int launch(const GemmDesc& d, hipStream_t stream) {
     // splits, or two onto a C being accumulated into, do not
     if (det_mode()) splits = (d.accumulate || splits < 2) ? 1 : 2;
   }
-  int per = cdiv(nk, splits);
-  splits = cdiv(nk, per);
-  if (splits > 1 && !d.accumulate && !d.c_zeroed) {
+  p.per = cdiv(nk, splits);
+  p.splits = cdiv(nk, p.per);
+  p.zero_grid = 0;
+  if (p.splits > 1 && !d.accumulate && !d.c_zeroed) {
     const long total = (long)d.M * d.N;
-    const int g = (int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
-    hipLaunchKernelGGL(zero2d_kernel, dim3(g), dim3(256), 0, stream, (float*)d.C, d.ldc, d.M, d.N);
+    p.zero_grid = (int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
   }
   // LDS-DMA ring (PIPE) vs register staging: the ring hides load latency when a CU holds ONE block (grid <= ~2 blocks
   // per CU) and K is deep; with many blocks per CU the register-staged kernel wins (2 co-resident blocks, 72 KB LDS each)
   // and for K of one or two tiles the ring's prologue is pure overhead.  Measured on MI355X (tools/gemm_bench.py).
-  constexpr bool CAN_PIPE = AKC && BKC && VEC;
   static const bool no_pipe = getenv("GIC_GEMM_NO_PIPE") != nullptr;
-  const bool pipe = CAN_PIPE && per >= 6 && (long)tiles * splits <= 2 * 256 + 8 && !no_pipe;
-  if constexpr (CAN_PIPE) {
-    if (pipe) {
-      hipLaunchKernelGGL((gemm_kernel<TI, TO, AKC, BKC, BM, BN, VEC, EPI, CONV, true>), dim3(tiles, splits), dim3(256), 0, stream, d, per);
-      GIC_CHECK_LAUNCH("gemm");
-      return GIC_OK;
+  p.pipe = d.a_kc && d.b_kc && vec && p.per >= 6 && (long)tiles * p.splits <= 2 * 256 + 8 && !no_pipe;
+}
+
+// The one list of candidates, in the order they are tried; `after`: the families up to and including it are skipped (the launch of that one
+// was refused its LDS grant).  GIC_OK with p.family set, or the status gemm() answers.
+int select(const GemmDesc& d, bool vec, int after, Plan& p) {
+  const bool bf16_in = d.in_dtype == DT_BF16, bf16_out = d.out_dtype == DT_BF16;
+  if (!((d.in_dtype == DT_F32 && d.out_dtype == DT_F32) || (bf16_in && (d.out_dtype == DT_F32 || bf16_out)))) {
+    set_last_error("gemm: unsupported dtypes in=%d out=%d", d.in_dtype, d.out_dtype);
+    return GIC_ERR_UNSUPPORTED;
+  }
+  if (d.conv) {
+    if (!vec || !d.a_kc || !d.b_kc) { set_last_error("gemm: convolution needs 16-B aligned NHWC / KRSC operands"); return GIC_ERR_UNSUPPORTED; }
+    if (bf16_in != bf16_out || (d.epi != EPI_BNSTATS && d.epi != EPI_PLAIN)) {
+      set_last_error("gemm: unsupported convolution epilogue / dtype");
+      return GIC_ERR_UNSUPPORTED;
     }
+  } else if (d.epi != EPI_PLAIN && d.epi != EPI_HIGHWAY) {
+    set_last_error("gemm: unknown epilogue %d", d.epi);
+    return GIC_ERR_UNSUPPORTED;
   }
-  hipLaunchKernelGGL((gemm_kernel<TI, TO, AKC, BKC, BM, BN, VEC, EPI, CONV, false>), dim3(tiles, splits), dim3(256), 0, stream, d, per);
-  GIC_CHECK_LAUNCH("gemm");
-  return GIC_OK;
-}
-
-// 128x128 tiles only when there are enough of them to co-schedule two blocks per CU (latency hiding by TLP);
-// GIC_GEMM_BIG_MIN overrides the threshold for tuning runs.
-int big_tile_min() {
-  static const int v = [] { const char* e = getenv("GIC_GEMM_BIG_MIN"); return e ? atoi(e) : 192; }();
-  return v;
-}
-
-template <typename TI, typename TO, bool AKC, bool BKC, int EPI>
-int pick_tile(const GemmDesc& d, bool vec, hipStream_t stream) {
-  // 128x128 tiles when they still give >= ~1 block per CU, else 64x64.
-  const long big_tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
-  const bool big = big_tiles >= big_tile_min() && d.M >= 128 && d.N >= 128;
-  if (big) {
-    return vec ? launch<TI, TO, AKC, BKC, 128, 128, true, EPI>(d, stream)
-               : launch<TI, TO, AKC, BKC, 128, 128, false, EPI>(d, stream);
-  }
-  return vec ? launch<TI, TO, AKC, BKC, 64, 64, true, EPI>(d, stream)
-             : launch<TI, TO, AKC, BKC, 64, 64, false, EPI>(d, stream);
-}
-
-template <typename TI, typename TO, int EPI>
-int pick_layout(const GemmDesc& d, bool vec, hipStream_t stream) {
-  if constexpr (sizeof(TI) == 2) {
-    if (d.a_kc && d.b_kc && vec && try_tile8<TO, EPI, false>(d, stream)) { GIC_CHECK_LAUNCH("gemm tile8"); return GIC_OK; }
-  }
-  if (d.a_kc && d.b_kc) return pick_tile<TI, TO, true, true, EPI>(d, vec, stream);
-  if constexpr (EPI == EPI_PLAIN) {
-    if (d.a_kc && !d.b_kc) return pick_tile<TI, TO, true, false, EPI>(d, vec, stream);
-    if (!d.a_kc && !d.b_kc) return pick_tile<TI, TO, false, false, EPI>(d, vec, stream);
-  }
-  set_last_error("gemm: unsupported layout a_kc=%d b_kc=%d epi=%d", d.a_kc, d.b_kc, d.epi);
-  return GIC_ERR_UNSUPPORTED;
-}
-
-template <typename TI, typename TO, int EPI>
-int pick_conv(const GemmDesc& d, hipStream_t stream) {
-  if constexpr (sizeof(TI) == 2 && sizeof(TO) == 2 && EPI == EPI_BNSTATS) {
+  auto take = [&](int family) { p.family = family; return GIC_OK; };
+  if (d.conv && bf16_out && d.epi == EPI_BNSTATS) {
+    // the stem (7 x 8 window over the zero-bordered NHWC4 image): input rows rolling through an LDS ring (conv_stem.hip)
+    if (after < F_STEM && select_conv_stem(d, p.stem)) return take(F_STEM);
     // 3x3 / stride 1: the input patch stays in LDS for all nine taps (conv3x3.hip).  BatchNorm on load of any other window than
     // 1x1 exists there only (tile8 would re-normalise the tile once per tap: slower than the separate pass it replaces).
-    // the stem (7 x 8 window over the zero-bordered NHWC4 image): input rows rolling through an LDS ring (conv_stem.hip)
-    if (try_conv_stem(d, stream)) { GIC_CHECK_LAUNCH("conv stem"); return GIC_OK; }
-    if (try_conv3x3_patch(d, stream)) { GIC_CHECK_LAUNCH("conv3x3 patch"); return GIC_OK; }
+    if (after < F_PATCH && select_conv3x3_patch(d, p.patch)) return take(F_PATCH);
     // shallow 1x1 layers over many rows: persistent workgroups, resident weights, A tiles streamed across row tiles (conv1x1_stream.hip)
-    if (try_conv1x1_stream(d, stream)) { GIC_CHECK_LAUNCH("conv1x1 stream"); return GIC_OK; }
-    if (d.stats_only) return GIC_ERR_UNSUPPORTED;               // (no message: callers probe)
+    if (after < F_STREAM && select_conv1x1_stream(d, p.strm)) return take(F_STREAM);
+    if (d.stats_only) return GIC_ERR_UNSUPPORTED;               // the statistics-only pass exists there only (no message: callers probe)
     // K = 256 | 512 of a normalised input into many output channels: the pixels in registers, weight tiles streamed (conv1x1_pix.hip)
-    if (try_conv1x1_pix(d, stream)) { GIC_CHECK_LAUNCH("conv1x1 pix"); return GIC_OK; }
+    if (after < F_PIX && select_conv1x1_pix(d, p.pix)) return take(F_PIX);
     // K = 256 into many output channels: the A panel of a row tile loaded / normalised once for all its channel tiles (conv1x1_panel.hip)
-    if (try_conv1x1_panel(d, stream)) { GIC_CHECK_LAUNCH("conv1x1 panel"); return GIC_OK; }
+    if (after < F_PANEL && select_conv1x1_panel(d, p.panel)) return take(F_PANEL);
     if (d.in_stats && d.cKH * d.cKW > 1) return GIC_ERR_UNSUPPORTED;
   }
-  if constexpr (sizeof(TI) == 2) {
-    if (try_tile8<TO, EPI, true>(d, stream)) { GIC_CHECK_LAUNCH("conv tile8"); return GIC_OK; }
+  // the 8-wave kernel: every other bf16 convolution and the wide, deep plain / highway products with k-contiguous operands
+  if (after < F_TILE8 && bf16_in && (d.conv || (d.a_kc && d.b_kc && vec))) {
+    p.d = d;
+    if (select_tile8(d, p.t8, p.d.n_fast)) return take(F_TILE8);
   }
-  if (d.in_stats) return GIC_ERR_UNSUPPORTED;                 // the A-side BatchNorm exists in tile8 only (no message: callers probe)
-  const long big_tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
-  if (big_tiles >= big_tile_min() && d.N >= 128) return launch<TI, TO, true, true, 128, 128, true, EPI, true>(d, stream);
-  return launch<TI, TO, true, true, 64, 64, true, EPI, true>(d, stream);
+  if (d.conv && d.in_stats) return GIC_ERR_UNSUPPORTED;         // the A-side BatchNorm exists in tile8 only (no message: callers probe)
+  // the 4-wave kernel: any layout of a plain product, k-contiguous operands otherwise
+  if (!(d.a_kc && d.b_kc) && (d.epi != EPI_PLAIN || d.b_kc)) {
+    set_last_error("gemm: unsupported layout a_kc=%d b_kc=%d epi=%d", d.a_kc, d.b_kc, d.epi);
+    return GIC_ERR_UNSUPPORTED;
+  }
+  p.d = d;
+  select_gemm4(d, vec, p.g4);
+  return take(F_GEMM4);
+}
+
+// gemm_gumbelmax's one candidate: the 8-wave kernel with 128 x 128 tiles
+bool select_gumbelmax(const GemmDesc& d0, Plan& p) {
+  static const bool off = getenv("GIC_NO_TILE8") != nullptr || getenv("GIC_NO_FUSED_GUMBELMAX") != nullptr;
+  GemmDesc& d = p.d = d0;
+  if (off || d.in_dtype != DT_BF16 || !d.a_kc || !d.b_kc || d.M < 128 || d.M % 4 || d.K % 8 || d.lda % 8 || d.ldb % 8 || !aligned16(d.A) ||
+      !aligned16(d.B) || !aligned16(d.gm_bias) || (d.gm_u && (!aligned16(d.gm_u) || d.gm_ldu % 4)) || !(d.gm_temperature > 0.f))
+    return false;
+  const long a_elems = (long)(d.M - 1) * d.lda + d.K, b_elems = (long)(d.N - 1) * d.ldb + d.K;
+  const long tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
+  if (a_elems * 2 >= (1l << 31) || b_elems * 2 >= (1l << 31) || d.N < 128 || tiles < 160) return false;
+  d.epi = EPI_GUMBELMAX;
+  d.n_fast = xcd_share_a(2l * d.M * d.K, 2l * d.N * d.K, cdiv(d.N, 128));
+  p.t8 = {128, tiles > 256 ? 2 : 4, false, false, 1024, (unsigned)tiles, (unsigned)(a_elems * 2), (unsigned)(b_elems * 2)};
+  p.family = F_TILE8;
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------- launch (no shape logic)
+
+__global__ void zero2d_kernel(float* __restrict__ C, long ldc, int M, int N) {
+  const long total = (long)M * N;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
+    C[(i / N) * ldc + (i % N)] = 0.f;
+}
+
+template <typename TO, int EPI, bool CONV, int BN, int NS, bool ABN = false, bool ARES = false, int AMAXK = 1024>
+void launch_tile8_as(const Plan& p, hipStream_t stream) {
+  // BatchNorm on load exists under the convolutions' BatchNorm-sum epilogue only; the ring-less form is never selected under the highway
+  // epilogue (a plain `if`: that instantiation stays in the code object, without a host stub)
+  if constexpr (!ABN || (EPI == EPI_BNSTATS && CONV))
+    if (EPI != EPI_HIGHWAY || NS != 1)
+      hipLaunchKernelGGL((tile8_kernel<TO, BN, EPI, CONV, NS, ABN, ARES, AMAXK>), dim3(p.t8.grid), dim3(512), 0, stream, p.d, p.t8.a_bytes, p.t8.b_bytes);
+}
+
+constexpr int t8_key(int BN, int NS, bool abn = false, bool ares = false, int amaxk = 1024) { return BN + NS * 256 + abn * 2048 + ares * 4096 + amaxk * 8192; }
+
+template <typename TO, int EPI, bool CONV>
+void launch_tile8_variant(const Plan& p, hipStream_t stream) {
+  const Tile8Plan& t = p.t8;
+  switch (t8_key(t.BN, t.NS, t.abn, t.ares, t.amaxk)) {
+#define GIC_T8(...) case t8_key(__VA_ARGS__): return launch_tile8_as<TO, EPI, CONV, __VA_ARGS__>(p, stream)
+    GIC_T8(128, 1); GIC_T8(128, 2); GIC_T8(128, 4); GIC_T8(64, 1); GIC_T8(64, 2); GIC_T8(64, 4);
+    GIC_T8(128, 1, true); GIC_T8(128, 2, true); GIC_T8(128, 4, true); GIC_T8(64, 1, true); GIC_T8(64, 2, true); GIC_T8(64, 4, true);
+    GIC_T8(128, 1, true, true, 512); GIC_T8(128, 2, true, true, 512); GIC_T8(64, 1, true, true, 512); GIC_T8(64, 2, true, true, 512);
+    GIC_T8(128, 1, true, true, 2048); GIC_T8(128, 2, true, true, 2048); GIC_T8(64, 1, true, true, 2048); GIC_T8(64, 2, true, true, 2048);
+#undef GIC_T8
+  }
+}
+
+void launch_tile8(const Plan& p, hipStream_t stream) {
+  const GemmDesc& d = p.d;
+  const bool bf16_out = d.out_dtype == DT_BF16;
+  if (d.epi == EPI_GUMBELMAX) {
+    if (p.t8.NS == 2) launch_tile8_as<float, EPI_GUMBELMAX, false, 128, 2>(p, stream);
+    else launch_tile8_as<float, EPI_GUMBELMAX, false, 128, 4>(p, stream);
+  } else if (d.conv) {
+    if (d.epi == EPI_BNSTATS) launch_tile8_variant<bf16_t, EPI_BNSTATS, true>(p, stream);
+    else launch_tile8_variant<bf16_t, EPI_PLAIN, true>(p, stream);
+  } else if (d.epi == EPI_HIGHWAY) {
+    if (bf16_out) launch_tile8_variant<bf16_t, EPI_HIGHWAY, false>(p, stream);
+    else launch_tile8_variant<float, EPI_HIGHWAY, false>(p, stream);
+  } else {
+    if (bf16_out) launch_tile8_variant<bf16_t, EPI_PLAIN, false>(p, stream);
+    else launch_tile8_variant<float, EPI_PLAIN, false>(p, stream);
+  }
+}
+
+template <typename TI, typename TO, bool AKC, bool BKC, int BM, bool VEC, int EPI, bool CONV>
+void launch_gemm4_as(const Plan& p, hipStream_t stream) {
+  const dim3 grid(p.g4.tiles, p.g4.splits);
+  if constexpr (AKC && BKC && VEC) {
+    if (p.g4.pipe) {
+      hipLaunchKernelGGL((gemm_kernel<TI, TO, AKC, BKC, BM, BM, VEC, EPI, CONV, true>), grid, dim3(256), 0, stream, p.d, p.g4.per);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((gemm_kernel<TI, TO, AKC, BKC, BM, BM, VEC, EPI, CONV, false>), grid, dim3(256), 0, stream, p.d, p.g4.per);
+}
+
+template <typename TI, typename TO, bool AKC, bool BKC, int EPI, bool CONV>
+void launch_gemm4_tile(const Plan& p, hipStream_t stream) {
+  const bool big = p.g4.bm == 128;
+  if (CONV || p.g4.vec) return big ? launch_gemm4_as<TI, TO, AKC, BKC, 128, true, EPI, CONV>(p, stream) : launch_gemm4_as<TI, TO, AKC, BKC, 64, true, EPI, CONV>(p, stream);
+  if constexpr (!CONV) return big ? launch_gemm4_as<TI, TO, AKC, BKC, 128, false, EPI, CONV>(p, stream) : launch_gemm4_as<TI, TO, AKC, BKC, 64, false, EPI, CONV>(p, stream);
 }
 
 template <typename TI, typename TO>
-int pick_epi(const GemmDesc& d, bool vec, hipStream_t stream) {
+void launch_gemm4_typed(const Plan& p, hipStream_t stream) {
+  const GemmDesc& d = p.d;
   if (d.conv) {
-    if (!vec || !d.a_kc || !d.b_kc) { set_last_error("gemm: convolution needs 16-B aligned NHWC / KRSC operands"); return GIC_ERR_UNSUPPORTED; }
     if constexpr (sizeof(TI) == sizeof(TO)) {
-      if (d.epi == EPI_BNSTATS) return pick_conv<TI, TO, EPI_BNSTATS>(d, stream);
-      if (d.epi == EPI_PLAIN) return pick_conv<TI, TO, EPI_PLAIN>(d, stream);
+      if (d.epi == EPI_BNSTATS) launch_gemm4_tile<TI, TO, true, true, EPI_BNSTATS, true>(p, stream);
+      else launch_gemm4_tile<TI, TO, true, true, EPI_PLAIN, true>(p, stream);
     }
-    set_last_error("gemm: unsupported convolution epilogue / dtype");
-    return GIC_ERR_UNSUPPORTED;
+  } else if (d.epi == EPI_HIGHWAY) {
+    launch_gemm4_tile<TI, TO, true, true, EPI_HIGHWAY, false>(p, stream);
+  } else if (d.a_kc) {
+    if (d.b_kc) launch_gemm4_tile<TI, TO, true, true, EPI_PLAIN, false>(p, stream);
+    else launch_gemm4_tile<TI, TO, true, false, EPI_PLAIN, false>(p, stream);
+  } else {
+    launch_gemm4_tile<TI, TO, false, false, EPI_PLAIN, false>(p, stream);
   }
-  if (d.epi == EPI_PLAIN) return pick_layout<TI, TO, EPI_PLAIN>(d, vec, stream);
-  if (d.epi == EPI_HIGHWAY) return pick_layout<TI, TO, EPI_HIGHWAY>(d, vec, stream);
-  set_last_error("gemm: unknown epilogue %d", d.epi);
-  return GIC_ERR_UNSUPPORTED;
 }
 
-bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+void launch_gemm4(const Plan& p, hipStream_t stream) {
+  const GemmDesc& d = p.d;
+  if (p.g4.zero_grid) hipLaunchKernelGGL(zero2d_kernel, dim3(p.g4.zero_grid), dim3(256), 0, stream, (float*)d.C, d.ldc, d.M, d.N);
+  if (d.in_dtype == DT_F32) launch_gemm4_typed<float, float>(p, stream);
+  else if (d.out_dtype == DT_F32) launch_gemm4_typed<bf16_t, float>(p, stream);
+  else launch_gemm4_typed<bf16_t, bf16_t>(p, stream);
+}
+
+// false: the kernel's LDS grant was refused (the caller selects again, past this family)
+bool launch(const Plan& p, hipStream_t stream) {
+  switch (p.family) {
+    case F_STEM: return launch_conv_stem(p.stem, stream);
+    case F_PATCH: return launch_conv3x3_patch(p.patch, stream);
+    case F_STREAM: return launch_conv1x1_stream(p.strm, stream);
+    case F_PIX: return launch_conv1x1_pix(p.pix, stream);
+    case F_PANEL: return launch_conv1x1_panel(p.panel, stream);
+    case F_TILE8: launch_tile8(p, stream); return true;
+    default: launch_gemm4(p, stream); return true;
+  }
+}
+
+const char* const kFamily[] = {"none", "conv stem", "conv3x3 patch", "conv1x1 stream", "conv1x1 pix", "conv1x1 panel", "gemm tile8", "gemm"};
+
+// The plan as one line: the kernel with its template arguments in their order, grid, block, dynamic LDS bytes and, for the 4-wave kernel,
+// the split of K
+void write_route(const Plan& p) {
+  char* s = route_line();
+  const GemmDesc& d = p.d;
+  const char* tn[] = {"f32", "bf16"};
+  auto b = [](bool v) { return v ? "true" : "false"; };
+  switch (p.family) {
+    case F_STEM: snprintf(s, kRouteLen, "conv_stem grid=%u block=512 lds=%zu", p.stem.grid, p.stem.lds); break;
+    case F_PATCH: snprintf(s, kRouteLen, "conv3x3_patch<%d,%d,%s,%s> grid=%u block=512 lds=%zu", p.patch.BN, p.patch.P, b(p.patch.multi), b(p.patch.abn), p.patch.grid, p.patch.lds); break;
+    case F_STREAM: snprintf(s, kRouteLen, "conv1x1_stream<%d,%d,%s,%s> grid=%u block=512 lds=%zu", p.strm.BN, p.strm.KT, b(p.strm.abn), b(p.strm.stats), p.strm.grid, p.strm.lds); break;
+    case F_PIX: snprintf(s, kRouteLen, "conv1x1_pix<%d,%d,%s> grid=%u block=512 lds=%zu", p.pix.K, p.pix.NSTG, b(p.pix.turn), p.pix.grid, p.pix.lds); break;
+    case F_PANEL: snprintf(s, kRouteLen, "conv1x1_panel<%d,%s> grid=%u block=512 lds=%zu", p.panel.KT, b(p.panel.abn), p.panel.grid, p.panel.lds); break;
+    case F_TILE8:
+      snprintf(s, kRouteLen, "tile8<%s,%d,%d,%s,%d,%s,%s,%d> grid=%u block=512 lds=0", d.epi == EPI_GUMBELMAX ? "f32" : tn[d.out_dtype], p.t8.BN, d.epi, b(d.conv),
+               p.t8.NS, b(p.t8.abn), b(p.t8.ares), p.t8.amaxk, p.t8.grid);
+      break;
+    default:
+      snprintf(s, kRouteLen, "gemm<%s,%s,%s,%s,%d,%d,%s,%d,%s,%s> grid=%dx%d block=256 lds=0 splits=%d per=%d pipe=%d zero=%d", tn[d.in_dtype], tn[d.out_dtype],
+               b(d.a_kc), b(d.b_kc), p.g4.bm, p.g4.bm, b(d.conv || p.g4.vec), d.epi, b(d.conv), b(p.g4.pipe), p.g4.tiles, p.g4.splits, p.g4.splits, p.g4.per,
+               (int)p.g4.pipe, p.g4.zero_grid);
+  }
+}
 
 }  // namespace
 
-int gemm_gumbelmax(const GemmDesc& d0, hipStream_t stream) {
-  GemmDesc d = d0;
-  static const bool off = getenv("GIC_NO_TILE8") != nullptr || getenv("GIC_NO_FUSED_GUMBELMAX") != nullptr;
+bool conv_base(const GemmDesc& d, long a_elems, long b_elems, ConvBase& b) {
+  if (!d.conv || d.epi != EPI_BNSTATS || !d.stats || d.in_dtype != DT_BF16 || d.out_dtype != DT_BF16) return false;
+  if (d.bias || d.alpha != 1.f || d.accumulate || !aligned16(d.A) || !aligned16(d.B) || !aligned16(d.C)) return false;
+  if (d.in_stats && (!bn_in_args_ok(d) || d.in_nrep < 1)) return false;
+  if (a_elems * 2 >= (1l << 31) || b_elems * 2 >= (1l << 31)) return false;
+  b.A = d.A; b.B = d.B; b.C = d.C; b.stats = d.stats;
+  b.in_stats = d.in_stats; b.in_gamma = d.in_gamma; b.in_beta = d.in_beta;
+  b.M = d.M; b.N = d.N; b.lda = (int)d.lda; b.ldb = (int)d.ldb; b.ldc = (int)d.ldc;
+  b.stats_nrep = d.stats_nrep < 1 ? 1 : d.stats_nrep; b.in_nrep = d.in_nrep; b.in_inv_count = d.in_inv_count;
+  b.a_bytes = (unsigned)(a_elems * 2); b.b_bytes = (unsigned)(b_elems * 2);
+  return true;
+}
+
+int gemm_gumbelmax(const GemmDesc& d, hipStream_t stream) {
   GIC_CHECK_ARG(d.A && d.B && d.gm_rowkey && d.gm_bias, "gemm_gumbelmax: null operand");
-  if (off || d.in_dtype != DT_BF16 || !d.a_kc || !d.b_kc || d.M < 128 || d.M % 4 || d.K % 8 || d.lda % 8 || d.ldb % 8 || !aligned16(d.A) ||
-      !aligned16(d.B) || !aligned16(d.gm_bias) || (d.gm_u && (!aligned16(d.gm_u) || d.gm_ldu % 4)) || !(d.gm_temperature > 0.f))
-    return GIC_ERR_UNSUPPORTED;
-  const long a_elems = (long)(d.M - 1) * d.lda + d.K, b_elems = (long)(d.N - 1) * d.ldb + d.K;
-  const long tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
-  if (a_elems * 2 >= (1l << 31) || b_elems * 2 >= (1l << 31) || d.N < 128 || tiles < 160) return GIC_ERR_UNSUPPORTED;
-  d.epi = EPI_GUMBELMAX;
-  d.n_fast = xcd_share_a(2l * d.M * d.K, 2l * d.N * d.K, cdiv(d.N, 128));
-  const unsigned ab = (unsigned)(a_elems * 2), bb = (unsigned)(b_elems * 2);
-  if (tiles > 256) hipLaunchKernelGGL((tile8_kernel<float, 128, EPI_GUMBELMAX, false, 2>), dim3((unsigned)tiles), dim3(512), 0, stream, d, ab, bb);
-  else hipLaunchKernelGGL((tile8_kernel<float, 128, EPI_GUMBELMAX, false, 4>), dim3((unsigned)tiles), dim3(512), 0, stream, d, ab, bb);
+  Plan p;
+  const bool ok = select_gumbelmax(d, p), probe = route_only();
+  if (probe && ok) write_route(p);
+  if (probe && !ok) snprintf(route_line(), kRouteLen, "unsupported");
+  if (!ok) return GIC_ERR_UNSUPPORTED;                     // (no message: callers probe)
+  if (probe) return GIC_OK;
+  launch_tile8(p, stream);
   GIC_CHECK_LAUNCH("gemm gumbelmax");
   return GIC_OK;
 }
@@ -1315,15 +1419,12 @@ int gemm(const GemmDesc& d0, hipStream_t stream) {
 #ifdef GIC_STAMPS
   { const char* e = getenv("GIC_GEMM_DBG"); if (e) d.dbg = atoi(e); }
 #endif
+  static const bool log = getenv("GIC_GEMM_LOG") != nullptr;      // one line per product on stderr (tools: which shapes a step issues, and their routes)
+  const bool probe = route_only();
+  if (probe) route_line()[0] = 0;
   GIC_CHECK_ARG(d.A && d.B && d.C, "gemm: null operand");
   GIC_CHECK_ARG(d.M >= 0 && d.N >= 0 && d.K >= 0, "gemm: negative dim");
   if (d.M == 0 || d.N == 0) return GIC_OK;
-  {  // GIC_GEMM_LOG=1: one line per product on stderr (tools: which shapes a step issues)
-    static const bool log = getenv("GIC_GEMM_LOG") != nullptr;
-    if (log && !d.conv)
-      fprintf(stderr, "[gemm] M=%d N=%d K=%d a_kc=%d b_kc=%d in=%d out=%d epi=%d acc=%d\n", d.M, d.N, d.K, d.a_kc, d.b_kc, d.in_dtype, d.out_dtype, d.epi,
-              d.accumulate);
-  }
   if (d.epi == EPI_HIGHWAY) GIC_CHECK_ARG(d.X, "gemm: highway epilogue needs X");      // Hpre may be null (forward only)
   const int sz = dtype_size(d.in_dtype);
   const int ve = 16 / sz;
@@ -1339,11 +1440,21 @@ int gemm(const GemmDesc& d0, hipStream_t stream) {
   // operands: a tail chunk reads into the row's padding (ld % ve == 0 >= M) and only feeds rows that are
   // never stored, so no condition on M / N.
   if (d.a_kc || d.b_kc) vec = vec && (d.K % ve == 0);
-  if (d.in_dtype == DT_F32 && d.out_dtype == DT_F32) return pick_epi<float, float>(d, vec, stream);
-  if (d.in_dtype == DT_BF16 && d.out_dtype == DT_F32) return pick_epi<bf16_t, float>(d, vec, stream);
-  if (d.in_dtype == DT_BF16 && d.out_dtype == DT_BF16) return pick_epi<bf16_t, bf16_t>(d, vec, stream);
-  set_last_error("gemm: unsupported dtypes in=%d out=%d", d.in_dtype, d.out_dtype);
-  return GIC_ERR_UNSUPPORTED;
+  Plan p;
+  for (int after = F_NONE;; after = p.family) {
+    const int rc = select(d, vec, after, p);
+    if (log || probe) {
+      if (rc == GIC_OK) write_route(p);
+      else snprintf(route_line(), kRouteLen, "unsupported");
+      if (log && !d.conv)
+        fprintf(stderr, "[gemm] M=%d N=%d K=%d a_kc=%d b_kc=%d in=%d out=%d epi=%d acc=%d -> %s\n", d.M, d.N, d.K, d.a_kc, d.b_kc, d.in_dtype, d.out_dtype,
+                d.epi, d.accumulate, route_line());
+    }
+    if (rc != GIC_OK || probe) return rc;
+    if (launch(p, stream)) break;
+  }
+  GIC_CHECK_LAUNCH(kFamily[p.family]);
+  return GIC_OK;
 }
 
 }  // namespace gic

@@ -16,6 +16,11 @@ void set_last_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+static thread_local bool g_route_only = false;
+static thread_local char g_route[kRouteLen] = "";
+bool route_only() { return g_route_only; }
+char* route_line() { return g_route; }
+
 namespace {
 
 // ---- 2-D cast/copy: one thread per element, coalesced along columns
@@ -311,6 +316,8 @@ extern "C" {
 
 int gic_abi_version(void) { return GIC_ABI_VERSION; }
 const char* gic_last_error(void) { return gic::g_last_error; }
+void gic_debug_route_only(int on) { gic::g_route_only = on != 0; }
+const char* gic_debug_last_route(void) { return gic::g_route; }
 
 int gic_gemm(const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
              int a_kc, int b_kc, int in_dtype, int out_dtype, const float* bias, int accumulate, float alpha,

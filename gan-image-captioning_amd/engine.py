@@ -60,6 +60,23 @@ class capture_guard:
         return False
 
 
+class route_only:
+    """Route-only mode of the calling thread (gicap.h gic_debug_route_only): inside, the library's GEMM / convolution entry points select
+    their kernel and return without touching the GPU; ``last()`` is the selection as one line.  Always cleared on exit."""
+
+    def __enter__(self):
+        L.load().gic_debug_route_only(1)
+        return self
+
+    def __exit__(self, *exc):
+        L.load().gic_debug_route_only(0)
+        return False
+
+    @staticmethod
+    def last() -> str:
+        return L.load().gic_debug_last_route().decode()
+
+
 class on_stream:
     """``with torch.cuda.stream(s)`` without its per-entry device query (torch's StreamContext asks the runtime for the device count
     on every construction: ~20 us, a dozen times per step).  Single device per process (one process per GPU)."""

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GIC_ABI_VERSION 4
+#define GIC_ABI_VERSION 5
 #define GIC_MAX_LAYERS 4
 #define GIC_MAX_CONVS 8
 
@@ -46,6 +46,15 @@ enum gic_loss_type {           /* src/utils.py:10-53 */
 int gic_abi_version(void);
 /* Message of the last failing call on this host thread ("" if none). */
 const char* gic_last_error(void);
+
+/* (ABI v5) Route-only mode, a per-thread debugging switch: while it is on, gic_gemm, every convolution entry point that goes through the
+ * GEMM dispatch (gic_conv2d, gic_conv2d_bn_in, gic_conv1x1_bn_in_stats, gic_conv1x1_res_in), the fused vocabulary product and gic_conv_b2b
+ * validate their arguments, select a kernel and return the status they would return -- GIC_STATUS_UNSUPPORTED included -- WITHOUT touching
+ * the GPU (pointers are only checked for null and alignment).  gic_debug_last_route() is this thread's last selection as one line: the
+ * kernel with its template arguments, grid, block, dynamic LDS bytes and, for the 4-wave kernel, splits / per / pipe, e.g.
+ * "tile8<bf16,128,2,true,2,true,false,1024> grid=1568 block=512 lds=0"; "unsupported" when nothing was selected. */
+void gic_debug_route_only(int on);
+const char* gic_debug_last_route(void);
 
 /* ------------------------------------------------------------------------------------------
  * Per-step scalars resident in DEVICE memory (ABI v3).  The values that change from one train step to the next -- the decoder's
@@ -606,6 +615,9 @@ int gic_conv_b2b(const void* y2, const float* stats2, int nrep2, const float* ga
                  int nrep3, const float* gamma3, const float* beta3, const void* res, const float* res_stats, int res_nrep,
                  const float* res_gamma, const float* res_beta, float count, void* block_out, const void* w1n, void* y1n, float* stats1,
                  int nrep1, int dtype, int64_t rows, int C2, int C1N, void* stream);
+/* (ABI v5) 1 if gic_conv_b2b has a kernel for these shapes (the list above), else 0: a host-only query, the very test gic_conv_b2b applies
+ * before it looks at its pointers. */
+int gic_conv_b2b_supported(int dtype, int64_t rows, int C2, int C1N);
 /* out = [relu]( bn(y) + (res ? bn_res(res) : 0) ) over rows x C.  A BatchNorm takes its mean/var from `stats` (raw sums over
  * `count` rows; train mode) or from run_mean/run_var (eval mode); res_gamma == NULL -> the residual is added as is. */
 int gic_bn_act(const void* y, const float* stats, const float* gamma, const float* beta, const float* run_mean,

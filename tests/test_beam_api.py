@@ -30,7 +30,7 @@ def test_symbols_declared_bound_exported():
         assert name in L.EXPORTED_SYMBOLS
         assert getattr(lib, name) is not None
     assert "gic_decoder_beam_opts" in hdr
-    assert lib.gic_abi_version() == 4
+    assert lib.gic_abi_version() == 5
 
 
 def _dims(B, Lc, V, E, H, NL, dt):

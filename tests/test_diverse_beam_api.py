@@ -29,7 +29,7 @@ def test_symbols_declared_bound_exported():
         assert re.search(r"\b%s\(" % name, hdr), name
         assert name in L.EXPORTED_SYMBOLS
         assert getattr(lib, name) is not None
-    assert lib.gic_abi_version() == 4
+    assert lib.gic_abi_version() == 5
 
 
 def test_struct_matches_header():

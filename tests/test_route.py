@@ -1,0 +1,236 @@
+"""Which kernel every dense product and trunk convolution takes, pinned without a GPU.
+
+Route-only mode (gicap.h gic_debug_route_only) makes the library's GEMM / convolution entry points validate and select, and then
+return without touching the GPU: the pointers below are fake, 16-byte aligned and never dereferenced.
+
+Every expected string is one row of a rocprofv3 kernel trace of the commit BEFORE selection and launch were separated (eager launches,
+MI355X): the kernel instantiation with its template arguments in their order, the grid in workgroups (the trace's Grid_Size / Workgroup_Size;
+for the 4-wave kernel tiles x splits) and the workgroup size.  The traced programs: `bench.py` cfg2 (its ResNet-50 trunk at 224 x 224, batch
+64, and the train step's products, whose shapes GIC_GEMM_LOG=1 listed), the trunk alone at 224 / 64 with GIC_NO_CONV_B2B=1 (the rows marked
+"b2b off": the only runs in which gic_conv1x1_res_in and conv3 through gic_conv2d_bn_in appear at that shape) and the trunk alone at 200 x 200,
+batch 3.  conv_b2b's grid is min(row tiles, workgroups per CU x CUs), resolved at launch: the traces show it on 256 CUs.  The trace does not
+report dynamic LDS, so the `lds=` figure of a route line is not asserted here."""
+import pytest
+
+from gan_image_captioning_amd import _lib as L
+from gan_image_captioning_amd import engine
+
+P = 0x7F0000010000          # a fake, aligned, non-null device pointer
+BF16, F32 = L.BF16, L.F32
+UNSUPPORTED = L.ERR_UNSUPPORTED
+
+
+def conv2d(N, H, cin, cout, k, stride, pad, W=None, kw=None, dtype=BF16):
+    return ("gic_conv2d", (P, P, P, P, 8, dtype, N, H, W or H, cin, cout, k, kw or k, stride, pad, None))
+
+
+def conv2d_bn_in(N, H, cin, cout, k, stride, pad):
+    return ("gic_conv2d_bn_in", (P, P, 8, P, P, float(N * H * H), P, P, P, 8, BF16, N, H, H, cin, cout, k, k, stride, pad, None))
+
+
+def conv3_stats(rows, cin, cout):
+    return ("gic_conv1x1_bn_in_stats", (P, P, 8, P, P, float(rows), P, P, 8, BF16, rows, cin, cout, None))
+
+
+def res_in(N, H, cin, cout, projection):
+    rs = P if projection else None
+    return ("gic_conv1x1_res_in", (P, P, 8, P, P, P, rs, 8, rs, rs, float(N * H * H), P, P, P, P, 8, BF16, N, H, H, cin, cout, None))
+
+
+def b2b(rows, c2, c1n, projection):
+    rs = P if projection else None
+    return ("gic_conv_b2b", (P, P, 8, P, P, P, P, 8, P, P, P, rs, 8, rs, rs, float(rows), P, P, P, P, 8, BF16, rows, c2, c1n, None))
+
+
+def route(call):
+    name, args = call
+    with engine.route_only() as r:
+        status = getattr(L.load(), name)(*args)
+        line = r.last()
+    return status, line
+
+
+def kernel_and_grid(line):
+    return line.split(" lds=")[0]
+
+
+R64 = 64 * 56 * 56           # rows of the 56 x 56 maps at batch 64: 200704; 28 x 28: 50176; 14 x 14: 12544; 7 x 7: 3136
+
+# ResNet-50 trunk, training, bf16, 224 x 224, batch 64: every distinct convolution through the entry point the plan uses for it
+TRUNK_224 = [
+    ("stem", conv2d(64, 230, 4, 64, 7, 2, 0, kw=8), "conv_stem grid=256 block=512"),
+    ("2.0.conv1", conv2d(64, 56, 64, 64, 1, 1, 0), "conv1x1_stream<64,1,false,false> grid=256 block=512"),
+    ("2.x.conv2", conv2d_bn_in(64, 56, 64, 64, 3, 1, 1), "conv3x3_patch<64,6,false,true> grid=1600 block=512"),
+    ("2.x.conv3 stats", conv3_stats(R64, 64, 256), "conv1x1_stream<256,1,true,true> grid=256 block=512"),
+    ("2.0.downsample", conv2d(64, 56, 64, 256, 1, 1, 0), "conv1x1_stream<128,1,false,false> grid=256 block=512"),
+    ("2.0 -> 2.1.conv1", b2b(R64, 64, 64, True), "conv_b2b<64,64,false> grid=min(1568,2*cus) block=512"),           # trace: 512
+    ("2.1 -> 2.2.conv1", b2b(R64, 64, 64, False), "conv_b2b<64,64,true> grid=min(1568,2*cus) block=512"),          # trace: 512
+    ("2.2 -> 3.0.conv1", b2b(R64, 64, 128, False), "conv_b2b<64,128,true> grid=min(1568,1*cus) block=512"),        # trace: 256
+    ("3.0.conv2 (stride 2)", conv2d(64, 56, 128, 128, 3, 2, 1), "tile8<bf16,128,2,true,2,false,false,1024> grid=392 block=512"),
+    ("3.x.conv3 stats", conv3_stats(R64 // 4, 128, 512), "conv1x1_stream<256,2,true,true> grid=256 block=512"),
+    ("3.0.downsample", conv2d(64, 56, 256, 512, 1, 2, 0), "tile8<bf16,128,2,true,1,false,false,1024> grid=1568 block=512"),
+    ("3.0 -> 3.1.conv1", b2b(R64 // 4, 128, 128, True), "conv_b2b<128,128,false> grid=min(392,1*cus) block=512"),   # trace: 256
+    ("3.x.conv2", conv2d_bn_in(64, 28, 128, 128, 3, 1, 1), "conv3x3_patch<128,5,true,true> grid=392 block=512"),
+    ("3.1 -> 3.2.conv1", b2b(R64 // 4, 128, 128, False), "conv_b2b<128,128,true> grid=min(392,1*cus) block=512"),   # trace: 256
+    ("3.3 -> 4.0.conv1", b2b(R64 // 4, 128, 256, False), "conv_b2b<128,256,true> grid=min(392,1*cus) block=512"),   # trace: 256
+    ("4.0.conv2 (stride 2)", conv2d(64, 28, 256, 256, 3, 2, 1), "tile8<bf16,128,2,true,4,false,false,1024> grid=196 block=512"),
+    ("4.x.conv3", conv2d_bn_in(64, 14, 256, 1024, 1, 1, 0), "conv1x1_pix<256,3,true> grid=196 block=512"),
+    ("4.0.downsample", conv2d(64, 28, 512, 1024, 1, 2, 0), "tile8<bf16,128,2,true,2,false,false,1024> grid=784 block=512"),
+    ("4.x.conv1", conv2d(64, 14, 1024, 256, 1, 1, 0), "tile8<bf16,128,2,true,4,false,false,1024> grid=196 block=512"),
+    ("4.x.conv2", conv2d_bn_in(64, 14, 256, 256, 3, 1, 1), "conv3x3_patch<128,4,true,true> grid=196 block=512"),
+    ("5.0.conv1", conv2d(64, 14, 1024, 512, 1, 1, 0), "tile8<bf16,128,2,true,2,false,false,1024> grid=392 block=512"),
+    ("5.0.conv2 (stride 2)", conv2d(64, 14, 512, 512, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=200 block=512"),
+    ("5.x.conv3", conv2d_bn_in(64, 7, 512, 2048, 1, 1, 0), "conv1x1_pix<512,2,false> grid=200 block=512"),
+    ("5.0.downsample", conv2d(64, 14, 1024, 2048, 1, 2, 0), "tile8<bf16,128,2,true,2,false,false,1024> grid=400 block=512"),
+    ("5.x.conv1", conv2d(64, 7, 2048, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=200 block=512"),
+    ("5.x.conv2", conv2d_bn_in(64, 7, 512, 512, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=200 block=512"),
+    # b2b off: the block output formed on load by the next conv1, conv3 with bn2 on load
+    ("b2b off 2.x.conv3", conv2d_bn_in(64, 56, 64, 256, 1, 1, 0), "conv1x1_stream<128,1,true,false> grid=256 block=512"),
+    ("b2b off 2.1.conv1", res_in(64, 56, 256, 64, True), "tile8<bf16,64,2,true,1,true,true,512> grid=1568 block=512"),
+    ("b2b off 2.2.conv1", res_in(64, 56, 256, 64, False), "tile8<bf16,64,2,true,1,true,true,512> grid=1568 block=512"),
+    ("b2b off 3.0.conv1", res_in(64, 56, 256, 128, False), "tile8<bf16,128,2,true,1,true,true,512> grid=1568 block=512"),
+    ("b2b off 3.x.conv3", conv2d_bn_in(64, 28, 128, 512, 1, 1, 0), "conv1x1_stream<128,2,true,false> grid=256 block=512"),
+    ("b2b off 3.x.conv1", res_in(64, 28, 512, 128, False), "tile8<bf16,128,2,true,1,true,true,512> grid=392 block=512"),
+]
+
+# the same trunk at 200 x 200, batch 3 (maps of 50, 25, 13 and 7 pixels: 7500, 1875, 507 and 147 rows, none a multiple of 128)
+TRUNK_200 = [
+    ("stem", conv2d(3, 206, 4, 64, 7, 2, 0, kw=8), "conv_stem grid=150 block=512"),
+    ("2.0.conv1", conv2d(3, 50, 64, 64, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=59 block=512"),
+    ("2.x.conv2", conv2d_bn_in(3, 50, 64, 64, 3, 1, 1), "conv3x3_patch<64,6,false,true> grid=60 block=512"),
+    ("2.x.conv3", conv2d_bn_in(3, 50, 64, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,true,false,1024> grid=236 block=512"),
+    ("2.0.downsample", conv2d(3, 50, 64, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=236 block=512"),
+    ("2.x.conv1", conv2d(3, 50, 256, 64, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=59 block=512"),
+    ("3.0.conv1", conv2d(3, 50, 256, 128, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=118 block=512"),
+    ("3.0.conv2 (stride 2)", conv2d(3, 50, 128, 128, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=30 block=512"),
+    ("3.x.conv3", conv2d_bn_in(3, 25, 128, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,true,false,1024> grid=120 block=512"),
+    ("3.0.downsample", conv2d(3, 50, 256, 512, 1, 2, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=120 block=512"),
+    ("3.x.conv1", conv2d(3, 25, 512, 128, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=30 block=512"),
+    ("3.x.conv2", conv2d_bn_in(3, 25, 128, 128, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=30 block=512"),
+    ("4.0.conv1", conv2d(3, 25, 512, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=60 block=512"),
+    ("4.0.conv2 (stride 2)", conv2d(3, 25, 256, 256, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512"),
+    ("4.x.conv3", conv2d_bn_in(3, 13, 256, 1024, 1, 1, 0), "conv1x1_pix<256,3,true> grid=64 block=512"),
+    ("4.0.downsample", conv2d(3, 25, 512, 1024, 1, 2, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=64 block=512"),
+    ("4.x.conv1", conv2d(3, 13, 1024, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512"),
+    ("4.x.conv2", conv2d_bn_in(3, 13, 256, 256, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=16 block=512"),
+    ("5.0.conv1", conv2d(3, 13, 1024, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=32 block=512"),
+    ("5.0.conv2 (stride 2)", conv2d(3, 13, 512, 512, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512"),
+    ("5.x.conv3", conv2d_bn_in(3, 7, 512, 2048, 1, 1, 0), "conv1x1_pix<512,2,false> grid=64 block=512"),
+    ("5.0.downsample", conv2d(3, 13, 1024, 2048, 1, 2, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=64 block=512"),
+    ("5.x.conv1", conv2d(3, 7, 2048, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512"),
+    ("5.x.conv2", conv2d_bn_in(3, 7, 512, 512, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=16 block=512"),
+]
+
+
+@pytest.mark.parametrize("name,call,expected", TRUNK_224, ids=[c[0] for c in TRUNK_224])
+def test_trunk_routes_at_224_batch_64(name, call, expected):
+    status, line = route(call)
+    assert status == 0, line
+    assert kernel_and_grid(line) == expected
+
+
+@pytest.mark.parametrize("name,call,expected", TRUNK_200, ids=[c[0] for c in TRUNK_200])
+def test_trunk_routes_at_200_batch_3(name, call, expected):
+    status, line = route(call)
+    assert status == 0, line
+    assert kernel_and_grid(line) == expected
+
+
+def test_rows_off_the_128_grid_decline_the_fused_pair():
+    """200 x 200, batch 3: conv_b2b and its query decline every boundary (the plan then puts the BatchNorm on load: the tile8 rows with
+    ABN above), and a 3x3 / stride 2 convolution has no BatchNorm on load (the plan runs gic_bn_act + gic_conv2d)."""
+    lib = L.load()
+    for rows, c2, c1n in ((7500, 64, 64), (7500, 64, 128), (1875, 128, 128), (1875, 128, 256)):
+        assert lib.gic_conv_b2b_supported(BF16, rows, c2, c1n) == 0
+        assert route(b2b(rows, c2, c1n, False)) == (UNSUPPORTED, "unsupported")
+    assert lib.gic_conv_b2b_supported(F32, R64, 64, 64) == 0
+    assert lib.gic_conv_b2b_supported(BF16, R64, 256, 256) == 0
+    assert route(conv2d_bn_in(3, 50, 128, 128, 3, 2, 1)) == (UNSUPPORTED, "unsupported")
+    assert route(conv3_stats(7500, 256, 1024)) == (UNSUPPORTED, "unsupported")       # the statistics-only pass exists for K = 64 | 128 only
+
+
+def gemm(M, N, K, a_kc, b_kc, in_dt, out_dt, acc):
+    up = lambda v: (v + 7) // 8 * 8                     # leading dimensions padded to whole 16-byte chunks, as the callers allocate them
+    return ("gic_gemm", (P, P, P, M, N, K, up(K if a_kc else M), up(K if b_kc else N), up(N), a_kc, b_kc, in_dt, out_dt, None, acc, 1.0, None))
+
+
+# every distinct plain product of one cfg2 train step: (M, N, K, a_kc, b_kc, in, out, accumulate) as GIC_GEMM_LOG=1 printed them
+CFG2_PRODUCTS = [
+    ((64, 512, 2048, 1, 1, BF16, F32, 0), "gemm<bf16,f32,true,true,64,64,true,0,false,false> grid=8x16 block=256", 16),
+    ((64, 10000, 1280, 0, 0, BF16, F32, 1), "gemm<bf16,f32,false,false,64,64,true,0,false,false> grid=157x3 block=256", 3),
+    ((100, 900, 8192, 0, 0, BF16, F32, 1), "gemm<bf16,f32,false,false,64,64,true,0,false,false> grid=30x16 block=256", 16),
+    ((512, 2048, 64, 0, 0, BF16, F32, 0), "gemm<bf16,f32,false,false,64,64,true,0,false,false> grid=256x1 block=256", 1),
+    ((900, 900, 8192, 0, 0, BF16, F32, 1), "gemm<bf16,f32,false,false,64,64,true,0,false,false> grid=225x3 block=256", 3),
+    ((1280, 64, 10000, 1, 1, BF16, F32, 0), "gemm<bf16,f32,true,true,64,64,true,0,false,true> grid=20x12 block=256", 12),
+    ((1280, 512, 2048, 1, 1, BF16, F32, 0), "gemm<bf16,f32,true,true,64,64,true,0,false,true> grid=160x3 block=256", 3),
+    ((1280, 512, 10000, 1, 0, BF16, F32, 0), "gemm<bf16,f32,true,false,64,64,true,0,false,false> grid=160x3 block=256", 3),
+    ((1280, 10000, 64, 1, 0, BF16, BF16, 0), "gemm<bf16,bf16,true,false,128,128,true,0,false,false> grid=790x1 block=256", 1),
+    ((2048, 512, 1280, 0, 0, BF16, F32, 0), "gemm<bf16,f32,false,false,64,64,true,0,false,false> grid=256x1 block=256", 1),
+    ((4096, 100, 960, 1, 1, BF16, F32, 0), "gemm<bf16,f32,true,true,64,64,true,0,false,true> grid=128x1 block=256", 1),
+    ((4096, 960, 104, 1, 0, BF16, F32, 0), "gemm<bf16,f32,true,false,128,128,true,0,false,false> grid=256x1 block=256", 1),
+    ((4096, 960, 960, 1, 1, BF16, F32, 1), "tile8<f32,128,0,false,4,false,false,1024> grid=256 block=512", None),
+    ((8192, 960, 104, 1, 0, BF16, F32, 0), "gemm<bf16,f32,true,false,128,128,true,0,false,false> grid=512x1 block=256", 1),
+    ((8192, 960, 960, 1, 1, BF16, F32, 1), "tile8<f32,128,0,false,2,false,false,1024> grid=512 block=512", None),
+    ((10000, 512, 1280, 0, 0, BF16, F32, 0), "gemm<bf16,f32,false,false,128,128,true,0,false,false> grid=316x1 block=256", 1),
+]
+
+
+def splits_of(line):
+    return int(line.split(" splits=")[1].split()[0])
+
+
+@pytest.mark.parametrize("shape,expected,splits", CFG2_PRODUCTS, ids=["x".join(map(str, c[0][:3])) for c in CFG2_PRODUCTS])
+def test_cfg2_product_routes(shape, expected, splits):
+    status, line = route(gemm(*shape))
+    assert status == 0, line
+    assert kernel_and_grid(line) == expected
+    if splits is not None:
+        assert splits_of(line) == splits
+        # deterministic mode: two splits onto a zeroed C at the most, none onto a C that is accumulated into
+        engine.set_deterministic(True)
+        try:
+            status, line = route(gemm(*shape))
+        finally:
+            engine.set_deterministic(False)
+        assert status == 0 and line.startswith("gemm<")
+        assert splits_of(line) == (1 if shape[7] or splits == 1 else 2)
+
+
+def test_fp32_takes_the_4_wave_kernel():
+    status, line = route(gemm(4096, 960, 960, 1, 1, F32, F32, 0))          # a shape tile8 takes in bf16
+    assert status == 0 and line.startswith("gemm<f32,f32,true,true,"), line
+    assert splits_of(line) == 1                                            # the parity mode never splits K
+    status, line = route(conv2d(64, 56, 64, 64, 1, 1, 0, dtype=F32))       # ... and one the streaming kernel takes
+    assert status == 0 and line.startswith("gemm<f32,f32,true,true,"), line
+
+
+def test_b2b_declines_what_its_byte_offsets_cannot_reach():
+    """rows * 4 * C2 * 2 >= 2^31: the library's query declines, and so does the plan's _b2b_ok (which used to restate the shape table
+    without this bound: the statistics-only pass then ran and gic_conv_b2b raised after it)."""
+    from gan_image_captioning_amd.trunk import ResNetTrunk
+    from gan_image_captioning_amd.encoder_engine import TrunkPlan
+    lib = L.load()
+    rows = (1 << 31) // (4 * 64 * 2)                  # 4194304, a multiple of 128
+    assert lib.gic_conv_b2b_supported(BF16, rows - 128, 64, 64) == 1
+    assert lib.gic_conv_b2b_supported(BF16, rows, 64, 64) == 0
+    assert route(b2b(rows, 64, 64, False)) == (UNSUPPORTED, "unsupported")
+    plan = TrunkPlan(ResNetTrunk("resnet50"), BF16)
+    blk, nxt = plan.blocks[0], plan.blocks[1]
+    assert plan._b2b_ok(blk, nxt, rows - 128, True)
+    assert not plan._b2b_ok(blk, nxt, rows, True)
+
+
+def test_route_only_is_cleared_on_exit():
+    lib = L.load()
+    empty = (P, P, P, 0, 8, 8, 8, 8, 8, 1, 1, BF16, F32, None, 0, 1.0, None)      # M = 0: GIC_OK with nothing to do, in either mode
+    with pytest.raises(RuntimeError):
+        with engine.route_only():
+            getattr(lib, "gic_gemm")(*gemm(64, 512, 2048, 1, 1, BF16, F32, 0)[1])
+            raise RuntimeError("boom")
+    line = engine.route_only.last()
+    assert line.startswith("gemm<")
+    assert lib.gic_gemm(*empty) == 0
+    assert engine.route_only.last() == line               # flag off: the call did not look at the route line
+    with engine.route_only() as r:
+        assert lib.gic_gemm(*empty) == 0
+        assert r.last() == ""                             # flag on: an empty product selects nothing

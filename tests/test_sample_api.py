@@ -133,7 +133,7 @@ def test_symbols_declared_bound_exported():
         assert name in L.EXPORTED_SYMBOLS
         assert getattr(lib, name) is not None
     assert "gic_sample_opts" in hdr
-    assert lib.gic_abi_version() == 4
+    assert lib.gic_abi_version() == 5
 
 
 @pytest.mark.parametrize("shape", [(64, 20, 10000, 512, 512, 1, 1), (4, 6, 50, 8, 16, 2, 0), (600, 6, 52, 8, 16, 1, 0)])
