@@ -69,6 +69,15 @@ class SampleOpts(C.Structure):
                 ("eos_id", C.c_int32), ("pad_id", C.c_int32), ("h0", c_void_p), ("c0", c_void_p)]
 
 
+MAX_SUPPRESS = 16
+
+
+class DecodeConstraints(C.Structure):
+    """gic_decode_constraints (the gic_*_constrained_* decodes)."""
+    _fields_ = [("no_repeat_ngram", C.c_int32), ("min_length", C.c_int32), ("num_suppress", C.c_int32),
+                ("suppress", C.c_int32 * MAX_SUPPRESS)]
+
+
 STEP_SEEDS = 6
 
 
@@ -190,6 +199,18 @@ _SIGNATURES = {
     "gic_attn_sample_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int32, c_void_p]),
     "gic_attn_sample_captions": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(SampleOpts), c_void_p, c_void_p, c_void_p,
                                            c_void_p, C.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_decode_constraints_ws_bytes": (C.c_int, [C.c_int64, C.c_int32, _P(DecodeConstraints), c_void_p]),
+    "gic_decoder_constrained_beam_search": (C.c_int, [_P(DecoderDims), _P(DecoderParams), _P(DecoderShadow), _P(DiverseBeamOpts),
+                                                      _P(DecodeConstraints), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p]),
+    "gic_attn_constrained_beam_search": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(DiverseBeamOpts), _P(DecodeConstraints),
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_decoder_constrained_sample_captions": (C.c_int, [_P(DecoderDims), _P(DecoderParams), _P(DecoderShadow), _P(SampleOpts),
+                                                          _P(DecodeConstraints), c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint64,
+                                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_attn_constrained_sample_captions": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(SampleOpts), _P(DecodeConstraints),
+                                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint64, c_void_p, c_void_p,
+                                                       c_void_p, c_void_p]),
     "gic_attn_forward_tf_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int, c_void_p]),
     "gic_attn_forward_tf": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), c_void_p, c_void_p, c_void_p, c_void_p,
                                       C.c_int, c_void_p, C.c_uint64, C.c_float, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -113,6 +113,11 @@ _NATIVE = [
     ("--eval-diversity-strength", float, 0.5, "Hamming diversity penalty (lambda >= 0) of that evaluation's diverse beam search"),
     ("--eval-cider-beam-size", int, 0, "beam size of the CIDEr-D evaluation (GANInstructor.evaluate_cider) after each adversarial epoch's "
                                        "validation; 0 = off"),
+    ("--eval-no-repeat-ngram", int, 0, "decode constraint of the evaluations (evaluate, evaluate_cider, evaluate_diversity, "
+                                       "evaluate_diverse_beam): no n-gram of this size occurs twice in a caption; 0 = off"),
+    ("--eval-min-length", int, 0, "decode constraint of the evaluations: <E> is not emitted before this many tokens; 0 = off"),
+    ("--eval-suppress-tokens", "intlist", "", "decode constraint of the evaluations: comma-separated token ids (at most 16) that are "
+                                              "never emitted, e.g. <S> and <UNK>; empty = none"),
 ]
 
 

@@ -91,9 +91,87 @@ __device__ __forceinline__ void beam_tile_reduce8(const float (&x)[8], const int
   }
 }
 
+// beam_tile_reduce8 with the top-K list built from (xs, ixs), the copy of (x, ix) in which the row's banned entries are (-inf, INT_MAX)
+// (decode constraints); the max and the sum stay those of the raw x.  A function of its own, so that the one above compiles as it did
+template <int K>
+__device__ __forceinline__ void beam_tile_reduce8_sel(const float (&x)[8], const float (&xs)[8], const int (&ixs)[8], bool store, long slot,
+                                                      float* part_m, float* part_s, float* part_v, int* part_i) {
+  float m = x[0];
+#pragma unroll
+  for (int e = 1; e < 8; ++e) m = fmaxf(m, x[e]);
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s += x[e] == -INFINITY ? 0.f : expf(x[e] - m);
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) s += __shfl_xor(s, o, 64);
+  float lv[K]; int li[K];
+#pragma unroll
+  for (int q = 0; q < K; ++q) { lv[q] = -INFINITY; li[q] = INT_MAX; }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) beam_insert<K>(lv, li, xs[e], ixs[e]);
+  beam_merge_levels<K, 0, 3>(lv, li);
+  if (store) {
+    part_m[slot] = m;
+    part_s[slot] = s;
+#pragma unroll
+    for (int q = 0; q < K; ++q) { part_v[slot * K + q] = lv[q]; part_i[slot * K + q] = li[q]; }
+  }
+}
+
+// ---- decode constraints (gicap.h gic_decode_constraints): the per-row ban lists, rebuilt before every step's vocabulary product
+constexpr int kBanSuppressMax = 16;
+// nban i32 [rows], ban i32 [rows][cap] (cap = S + 1 + L: the suppressed ids, <E>, one id per earlier position); null nban = no constraints
+struct BanLists { const int* nban = nullptr; const int* ban = nullptr; int cap = 0; };
+
+// the rule of a constraint set as the kernels that build the lists take it, and where they write: the lists of the NEXT step and (beam
+// search) the rows' flat histories hist i32 [2][rows][L], slot (tokens emitted) % 2, so that no step walks the parent pointers
+struct BanRule { int n = 0, min_length = 0, eos = 0, S = 0; int suppress[kBanSuppressMax] = {}; };
+struct BanOut { int* nban = nullptr; int* ban = nullptr; int* hist = nullptr; int cap = 0, L = 0; };
+
+// One wave: the ban list of a row that has emitted hs[0 .. t) and is about to emit its token of step t -- the suppressed ids, eos while
+// t + 1 < min_length, and with n >= 1 the token that followed every earlier occurrence of the row's last n - 1 tokens, compacted in
+// position order by a ballot (no atomics; at most S + 1 + t entries <= cap).  hs is in LDS, complete before the call (t = 0: unused)
+__device__ __forceinline__ void ban_list_wave(const int* hs, int t, int lane, const BanRule& c, int* __restrict__ out, int* __restrict__ nban) {
+#pragma unroll
+  for (int s = 0; s < kBanSuppressMax; ++s)
+    if (lane == s && s < c.S) out[s] = c.suppress[s];
+  int nb = c.S;
+  if (t + 1 < c.min_length) {
+    if (lane == 0) out[nb] = c.eos;
+    ++nb;
+  }
+  const int n = c.n, np = t - n + 1;                       // np earlier positions can start the row's last n - 1 tokens
+  if (n >= 1) {
+    for (int base = 0; base < np; base += 64) {
+      const int i = base + lane;
+      bool m = i < np;
+      for (int k = 0; m && k < n - 1; ++k) m = hs[i + k] == hs[np + k];
+      const unsigned long long mask = __ballot(m);
+      if (m) out[nb + __popcll(mask & ((1ull << lane) - 1ull))] = hs[i + n - 1];
+      nb += __popcll(mask);
+    }
+  }
+  if (lane == 0) *nban = nb;
+}
+
+// the copy of a lane's 8 entries v0 .. v0 + 7 in which the ids of the row's ban list are (-inf, INT_MAX): a walk over the row's short
+// list, not over a V-wide mask.  (Every lane reads every id itself: sharing a batch of 8 loads among the 8 lanes of a (row, tile) by
+// shuffles measured slower, +0.6 us per step at k = 1 -- the loads do not depend on each other and the list is L2-resident.)
+__device__ __forceinline__ void ban_apply8(float (&x)[8], int (&ix)[8], int v0, const int* __restrict__ list, int n) {
+  for (int i = 0; i < n; ++i) {
+    const int d = list[i] - v0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (d == e) { x[e] = -INFINITY; ix[e] = INT_MAX; }
+  }
+}
+
 // the fused vocabulary product of vocab_step with the beam epilogue (decoder_step.hip): a.B = rows, a.part_m / part_s [rows][nblk],
-// a.part_v / part_i [rows][nblk][K]; a.stop / stop_at; the sampling fields (u, seed, temperature, out, rowkey) are unused
-int vocab_step_beam(const VocabStepArgs& a, int K, int dtype, hipStream_t stream);
+// a.part_v / part_i [rows][nblk][K]; a.stop / stop_at; the sampling fields (u, seed, temperature, out, rowkey) are unused.  bans (decode
+// constraints): the epilogue that takes each row's top-K among the ids outside its ban list
+int vocab_step_beam(const VocabStepArgs& a, int K, int dtype, hipStream_t stream, const BanLists& bans = BanLists());
 
 // ---- the kernels of a caption decode (decode.hip drives them: one step loop for both decoders and both heads)
 struct BeamLayerPtrs { void* xh[GIC_MAX_LAYERS]; float* c[GIC_MAX_LAYERS]; };
@@ -137,9 +215,14 @@ int beam_gather(const BeamLayerPtrs& in, const BeamLayerPtrs& out, int NL, int E
                 const int* par, const int* stop, int stop_at, hipStream_t stream);
 // the generic path's tile partials of f32 logits [rows, V] (the fused path's are vocab_step_beam's epilogue)
 int beam_tile_topk(const float* logits, int rows, int V, int K, float* part_m, float* part_s, float* part_v, int* part_i, const int* stop,
-                   int stop_at, hipStream_t stream);
-// a.groups == 1: plain beam search; else diverse beam search (the caller checks that a.groups divides K)
-int beam_select(const BeamSelectArgs& a, int K, int B, hipStream_t stream);
+                   int stop_at, hipStream_t stream, const BanLists& bans = BanLists());
+// a.groups == 1: plain beam search; else diverse beam search (the caller checks that a.groups divides K).  bans (decode constraints,
+// bans.nban set): the kernel's tail builds the ban lists of step t + 1 by rule
+int beam_select(const BeamSelectArgs& a, int K, int B, hipStream_t stream, const BanOut& bans = BanOut(), const BanRule& rule = BanRule());
+// The ban lists of step 0 (decode constraints; empty histories), one wave per row.  The lists of step t + 1 are built by the tail of
+// step t's selection kernel (beam_select with bans set, sample_step with out set), which holds the row's new token and parent:
+// a launch per search, not per step
+int ban_init(const BanOut& out, const BanRule& rule, int rows, hipStream_t stream);
 // ids / scores / lengths of the K beams of each image, sorted within each group of `width` consecutive beams (width K: one sort of
 // all K, beam search; K / G: the diverse groups, group g in slots g * width ..), best first; anc: null or i32 [B, K, L], the row
 // (image * K + beam) of step t whose logits gave the t-th token of each returned beam (-1 past the last step that ran)
@@ -173,7 +256,7 @@ int check_sample_opts(const gic_sample_opts* o, int V, bool decode, const char* 
 // sample_select over f32 logits [rows, V] at step t: draws the next token of every live row into the state (score, len, tok, htok slot t,
 // fin and count on <E>); noise_u f32 [L, rows, V] or null -> Philox(seed, stream t)
 int sample_step(const float* logits, int rows, int V, const gic_sample_opts* o, const float* noise_u, uint64_t seed, int t, const BeamState& st,
-                hipStream_t stream);
+                hipStream_t stream, const BanLists& bans = BanLists(), const BanOut& out = BanOut(), const BanRule& rule = BanRule());
 // ids [rows][L] = each row's history up to its length, pad behind; scores / lengths [rows]
 int sample_finalize(const BeamState& st, int rows, int L, int pad, int64_t* ids, float* scores, int32_t* lengths, hipStream_t stream);
 

@@ -58,10 +58,15 @@ __global__ __launch_bounds__(256) void beam_gather_kernel(LayerPtrs in, LayerPtr
   }
 }
 
-// generic path: tile partials of an f32 logits matrix [rows, V] (any V: a ragged last tile reads -inf past V); 8 lanes per (row, tile)
-template <int K>
+// generic path: tile partials of an f32 logits matrix [rows, V] (any V: a ragged last tile reads -inf past V); 8 lanes per (row, tile).
+// BAN: the tile's top-K is taken from the copy without the row's banned ids (its max and sum of exp stay those of the raw values)
+// (Ban = BanLists, else the empty NoBan: the unconstrained instantiation keeps its argument layout)
+struct NoBan {};
+
+template <int K, bool BAN, typename Ban>
 __global__ __launch_bounds__(512) void beam_tile_topk_kernel(const float* __restrict__ logits, int rows, int V, int nblk, float* part_m,
-                                                             float* part_s, float* part_v, int* part_i, const int* stop, int stop_at) {
+                                                             float* part_s, float* part_v, int* part_i, const int* stop, int stop_at,
+                                                             const Ban bans) {
   if (*stop >= stop_at) return;
   const int tid = threadIdx.x, row = blockIdx.y * 64 + (tid >> 3), seg = tid & 7;
   const int v0 = blockIdx.x * kBeamTile + seg * 8;
@@ -74,7 +79,22 @@ __global__ __launch_bounds__(512) void beam_tile_topk_kernel(const float* __rest
     x[e] = v < V ? logits[(long)rr * V + v] : -INFINITY;
     ix[e] = v < V ? v : INT_MAX;
   }
-  beam_tile_reduce8<K>(x, ix, seg == 0 && row < rows, (long)rr * nblk + blockIdx.x, part_m, part_s, part_v, part_i);
+  if constexpr (BAN) {
+    float xs[8];
+    int ixs[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { xs[e] = x[e]; ixs[e] = ix[e]; }
+    ban_apply8(xs, ixs, v0, bans.ban + (long)rr * bans.cap, bans.nban[rr]);
+    beam_tile_reduce8_sel<K>(x, xs, ixs, seg == 0 && row < rows, (long)rr * nblk + blockIdx.x, part_m, part_s, part_v, part_i);
+  } else {
+    beam_tile_reduce8<K>(x, ix, seg == 0 && row < rows, (long)rr * nblk + blockIdx.x, part_m, part_s, part_v, part_i);
+  }
+}
+
+// one wave per row: the ban list of step 0
+__global__ __launch_bounds__(64) void ban_init_kernel(const BanOut o, const BanRule rule) {
+  const int r = blockIdx.x;
+  ban_list_wave(nullptr, 0, threadIdx.x, rule, o.ban + (long)r * o.cap, o.nban + r);
 }
 
 using SelectArgs = BeamSelectArgs;
@@ -88,9 +108,14 @@ __device__ __forceinline__ bool sel_better(bool va, float a, int la, bool vb, fl
 // the G = a.groups groups of Kg = K / G beams select in order g = 0..G-1, each over the candidates of its own Kg parents (lane = local
 // parent * K + rank, at most Kg * K <= 64 lanes), ranked by score + logp - diversity * h(token), where h counts the earlier groups' picks
 // of the token from live parents at this step; the kept score is the raw score + logp.  Plain beam search (G = 1) is the other
-// instantiation, so its selection is the one it always was
-template <int K, bool DIVERSE>
-__global__ __launch_bounds__(512) void beam_select_kernel(const SelectArgs a) {
+// instantiation, so its selection is the one it always was.
+// BAN (decode constraints; Ban = BanArgs, else NoBan): the kernel's tail builds the ban lists of step t + 1.  Every wave then runs the
+// selection (the same reads, the same result in every wave), wave 0 alone writes the state -- after a barrier, so that no wave still
+// reads what it overwrites -- and wave j < K takes beam j's parent and token from lane j of its own copy: no exchange through LDS
+struct BanArgs { BanOut out; BanRule rule; };
+
+template <int K, bool DIVERSE, bool BAN, typename Ban>
+__global__ __launch_bounds__(512) void beam_select_kernel(const SelectArgs a, const Ban ban) {
   __shared__ float cv[K][K], lse_s[K];
   __shared__ int ci[K][K];
   const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -120,7 +145,9 @@ __global__ __launch_bounds__(512) void beam_select_kernel(const SelectArgs a) {
     }
   }
   __syncthreads();
-  if (w != 0) return;
+  if constexpr (!BAN) {
+    if (w != 0) return;
+  }
   float my_s = 0.f; int my_t = 0, my_p = 0, my_fin = 0, my_len = 0;
   if constexpr (!DIVERSE) {
     // ---- candidates: lane = p * K + q (parent beam p, rank q in its row)
@@ -197,15 +224,41 @@ __global__ __launch_bounds__(512) void beam_select_kernel(const SelectArgs a) {
     }
   }
   const int all_fin = __all(lane >= K || my_fin);
-  if (lane < K) {
+  if constexpr (BAN) __syncthreads();
+  if (lane < K && (!BAN || w == 0)) {
     const int r = img * K + lane;
     a.score[r] = my_s; a.fin[r] = my_fin; a.len[r] = my_len; a.tok[r] = my_t; a.par[r] = img * K + my_p;
     a.htok[(long)a.t * a.rows + r] = my_t;
     a.hpar[(long)a.t * a.rows + r] = my_p;
   }
-  if (lane == 0) {
+  if (lane == 0 && (!BAN || w == 0)) {
     a.last[img] = a.t;
     if (all_fin) { a.done[img] = 1; atomicAdd(a.count, 1); }      // (integer count: the later launches of the search return at once)
+  }
+  if constexpr (BAN) {
+    // ---- wave j < K: the ban list of step t + 1 for the image's new beam j -- its history is its parent's flat history (slot t % 2)
+    // plus the token it just took, written to slot (t + 1) % 2 on the way.  A finished beam gets an empty list, a finished image
+    // none (nothing reads it), and the last step has no successor
+    __shared__ int hs[K][1024];                            // (L <= 1024: decode_dims)
+    const BanOut& o = ban.out;
+    const int tn = a.t + 1, L = o.L;                       // tokens emitted so far
+    const int j = w < K ? w : 0, r = img * K + j;
+    const int kp = __shfl(my_p, j, 64), kt = __shfl(my_t, j, 64), kf = __shfl(my_fin, j, 64);
+    const bool next = w < K && tn < L && !all_fin;
+    if (next && !kf) {
+      const int* src = o.hist + ((long)(a.t & 1) * a.rows + img * K + kp) * L;
+      int* dst = o.hist + ((long)(tn & 1) * a.rows + r) * L;
+      for (int i = lane; i < tn; i += 64) {
+        const int y = i < a.t ? src[i] : kt;
+        hs[j][i] = y;
+        dst[i] = y;
+      }
+    }
+    __syncthreads();
+    if (next) {
+      if (kf) { if (lane == 0) o.nban[r] = 0; }
+      else ban_list_wave(hs[j], tn, lane, ban.rule, o.ban + (long)r * o.cap, o.nban + r);
+    }
   }
 }
 
@@ -259,10 +312,17 @@ __global__ __launch_bounds__(64) void beam_finalize_kernel(const float* __restri
 
 }  // namespace
 
-int beam_select(const SelectArgs& s, int K, int B, hipStream_t stream) {
+int beam_select(const SelectArgs& s, int K, int B, hipStream_t stream, const BanOut& bans, const BanRule& rule) {
   return with_beam_k(K, [&](auto k) -> int {
-    if (s.groups > 1) hipLaunchKernelGGL((beam_select_kernel<k, true>), dim3(B), dim3(512), 0, stream, s);
-    else hipLaunchKernelGGL((beam_select_kernel<k, false>), dim3(B), dim3(512), 0, stream, s);
+    if (bans.nban) {
+      const BanArgs ban{bans, rule};
+      if (s.groups > 1) hipLaunchKernelGGL((beam_select_kernel<k, true, true, BanArgs>), dim3(B), dim3(512), 0, stream, s, ban);
+      else hipLaunchKernelGGL((beam_select_kernel<k, false, true, BanArgs>), dim3(B), dim3(512), 0, stream, s, ban);
+    } else if (s.groups > 1) {
+      hipLaunchKernelGGL((beam_select_kernel<k, true, false, NoBan>), dim3(B), dim3(512), 0, stream, s, NoBan());
+    } else {
+      hipLaunchKernelGGL((beam_select_kernel<k, false, false, NoBan>), dim3(B), dim3(512), 0, stream, s, NoBan());
+    }
     GIC_CHECK_LAUNCH("beam_select");
     return GIC_OK;
   });
@@ -279,14 +339,27 @@ int beam_gather(const BeamLayerPtrs& in, const BeamLayerPtrs& out, int NL, int E
 }
 
 int beam_tile_topk(const float* logits, int rows, int V, int K, float* part_m, float* part_s, float* part_v, int* part_i, const int* stop,
-                   int stop_at, hipStream_t stream) {
+                   int stop_at, hipStream_t stream, const BanLists& bans) {
   const int nblk = cdiv(V, kBeamTile);
   return with_beam_k(K, [&](auto k) -> int {
-    hipLaunchKernelGGL((beam_tile_topk_kernel<k>), dim3((unsigned)nblk, (unsigned)cdiv(rows, 64)), dim3(512), 0, stream, logits, rows, V, nblk,
-                       part_m, part_s, part_v, part_i, stop, stop_at);
+    const dim3 grid((unsigned)nblk, (unsigned)cdiv(rows, 64));
+    if (bans.nban)
+      hipLaunchKernelGGL((beam_tile_topk_kernel<k, true, BanLists>), grid, dim3(512), 0, stream, logits, rows, V, nblk, part_m, part_s, part_v,
+                         part_i, stop, stop_at, bans);
+    else
+      hipLaunchKernelGGL((beam_tile_topk_kernel<k, false, NoBan>), grid, dim3(512), 0, stream, logits, rows, V, nblk, part_m, part_s, part_v,
+                         part_i, stop, stop_at, NoBan());
     GIC_CHECK_LAUNCH("beam_tile_topk");
     return GIC_OK;
   });
+}
+
+int ban_init(const BanOut& out, const BanRule& rule, int rows, hipStream_t stream) {
+  GIC_CHECK_ARG(out.nban && out.ban && out.L >= 1 && out.L <= 1024 && rule.S >= 0 && rule.S <= kBanSuppressMax && out.cap >= rule.S + 1 + out.L,
+                "ban_init: bad dims");
+  hipLaunchKernelGGL(ban_init_kernel, dim3((unsigned)rows), dim3(64), 0, stream, out, rule);
+  GIC_CHECK_LAUNCH("ban_init");
+  return GIC_OK;
 }
 
 int beam_init(const BeamLayerPtrs& slot0, int NL, int din0, int E, int H, int B, int K, int dtype, const float* features, const float* h0,

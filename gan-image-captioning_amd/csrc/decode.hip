@@ -1,5 +1,6 @@
 // Caption decode (gicap.h gic_decoder_beam_search, gic_attn_beam_search, gic_decoder_diverse_beam_search, gic_attn_diverse_beam_search,
-// gic_decoder_sample_captions, gic_attn_sample_captions and their *_ws_bytes): one step loop for both decoders and both heads.
+// gic_decoder_sample_captions, gic_attn_sample_captions, their *_ws_bytes and the gic_*_constrained_* forms): one step loop for both
+// decoders and both heads.
 // Rows = B * K (row r = image r / K, beam or sample r % K).
 //
 // A search is a recurrence and a head, chosen at the entry point:
@@ -27,6 +28,13 @@
 //   part_m, part_s f32 [rows][nblk]; part_v f32, part_i i32 [rows][nblk][K]          beam: tile partials (nblk = ceil(V / 64))
 //   score f32, fin / len / tok / par i32 [rows]; hist_tok i32 [L][rows]; hist_par i32 [L][rows] (beam); anc i32 [B][K][L] (attention
 //   beam); last / done i32 [B]; count i32
+//
+// Decode constraints (gic_decode_constraints; the gic_*_constrained_* entry points): each live row's banned ids of the coming step lie
+// in the caller's second workspace (nban i32 [rows], ban i32 [rows][S + 1 + L], hist i32 [2][rows][L]).  ban_init writes step 0's
+// before the loop; the tail of step t's selection kernel (beam_select, sample_step), which holds every row's new token and parent,
+// writes step t + 1's: no launch is added to a step.  The step's consumers -- vocab_step_beam's epilogue, beam_tile_topk, sample_step
+// -- are the instantiations that read the lists; beam_select's selection is unchanged, since the tile partials it merges already
+// hold admissible tokens only.  With every constraint off the entry points run the unconstrained search itself.
 #include <cfloat>
 
 #include "../../include/gicap.h"
@@ -124,6 +132,57 @@ DecodeBufs decode_layout(const DecodeDims& d, bool beam, void* ws) {
   o.total = at;
   return o;
 }
+
+// decode constraints: the caller's struct and the regions of its workspace (cws)
+struct Constraints {
+  const gic_decode_constraints* c;
+  int* nban; int* ban; int* hist;
+  int cap;
+  size_t total;
+  int L;
+  BanLists lists() const { BanLists b; b.nban = nban; b.ban = ban; b.cap = cap; return b; }
+  BanOut out() const { BanOut b; b.nban = nban; b.ban = ban; b.hist = hist; b.cap = cap; b.L = L; return b; }
+  BanRule rule(int eos) const {
+    BanRule r;
+    r.n = c->no_repeat_ngram; r.min_length = c->min_length; r.eos = eos; r.S = c->num_suppress;
+    for (int i = 0; i < r.S; ++i) r.suppress[i] = c->suppress[i];
+    return r;
+  }
+};
+
+Constraints constraints_layout(const gic_decode_constraints* c, size_t rows, int L, void* cws) {
+  Constraints o{};
+  size_t at = 0;
+  auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)cws + at); at += (bytes + 255) & ~(size_t)255; return p; };
+  o.c = c;
+  o.L = L;
+  o.cap = c->num_suppress + 1 + L;
+  o.nban = (int*)take(rows * 4);
+  o.ban = (int*)take(rows * (size_t)o.cap * 4);
+  o.hist = (int*)take(2 * rows * (size_t)L * 4);
+  o.total = at;
+  return o;
+}
+
+// the checks of a constraint set for a decode of L steps over V tokens in which a row proposes K tokens (who: the prefix of the error text)
+int check_constraints(const gic_decode_constraints* c, int L, int V, int K, int eos, const char* who) {
+  GIC_CHECK_ARG(c, "%s: null constraints", who);
+  GIC_CHECK_ARG(c->no_repeat_ngram >= 0 && c->no_repeat_ngram <= L, "%s: no_repeat_ngram must be 0..L (%d), got %d", who, L, c->no_repeat_ngram);
+  GIC_CHECK_ARG(c->min_length >= 0 && c->min_length <= L, "%s: min_length must be 0..L (%d), got %d", who, L, c->min_length);
+  GIC_CHECK_ARG(c->num_suppress >= 0 && c->num_suppress <= kBanSuppressMax, "%s: num_suppress must be 0..%d, got %d", who, kBanSuppressMax,
+                c->num_suppress);
+  for (int i = 0; i < c->num_suppress; ++i) {
+    GIC_CHECK_ARG(c->suppress[i] >= 0 && c->suppress[i] < V, "%s: suppress[%d] = %d outside [0, %d)", who, i, c->suppress[i], V);
+    GIC_CHECK_ARG(c->suppress[i] != eos, "%s: suppress[%d] is eos_id (%d); min_length = L forbids it", who, i, eos);
+  }
+  const int n = c->no_repeat_ngram;
+  const long banned = c->num_suppress + 1 + (n >= 1 ? L - n : 0);      // the most ids one row's list can hold apart
+  GIC_CHECK_ARG((long)V - banned >= K, "%s: infeasible constraints: up to %ld of %d tokens banned (no_repeat_ngram %d, num_suppress %d, L %d) "
+                "leave fewer than the %d a row proposes", who, banned, V, n, c->num_suppress, L, K);
+  return GIC_OK;
+}
+
+bool constraints_off(const gic_decode_constraints* c) { return c->no_repeat_ngram == 0 && c->min_length == 0 && c->num_suppress == 0; }
 
 // what every part of one search reads
 struct Search {
@@ -225,18 +284,22 @@ struct BeamHead {
   float* alphas;                 // attention: f32 [B, K, L, P] or null
   int groups = 1;                // diverse beam search: G groups of K / G beams (1: beam search)
   float diversity = 0.f;         // and its Hamming penalty lambda
+  const Constraints* cons = nullptr;       // decode constraints (null: none)
   int live_stride(const DecodeDims& d) const { return d.K / groups; }
+  int eos() const { return o->eos_id; }
   int vocab(VocabStepArgs& v, const Search& s) const {
     v.part_m = s.w.pm; v.part_s = s.w.ps; v.part_v = s.w.pv; v.part_i = s.w.pi; v.nblk = s.d.nblk;
-    return vocab_step_beam(v, s.d.K, s.d.dt, s.stream);
+    return vocab_step_beam(v, s.d.K, s.d.dt, s.stream, cons ? cons->lists() : BanLists());
   }
   int logits(const Search& s) const {
-    return beam_tile_topk(s.w.logits, s.d.rows, s.d.V, s.d.K, s.w.pm, s.w.ps, s.w.pv, s.w.pi, s.w.st.count, s.stop_at, s.stream);
+    return beam_tile_topk(s.w.logits, s.d.rows, s.d.V, s.d.K, s.w.pm, s.w.ps, s.w.pv, s.w.pi, s.w.st.count, s.stop_at, s.stream,
+                          cons ? cons->lists() : BanLists());
   }
   int select(const Search& s, int t) const {
     const BeamState& st = s.w.st;
     const BeamSelectArgs a{s.w.pm, s.w.ps, s.w.pv, s.w.pi, st.score, st.fin, st.len, st.tok, st.par, st.htok, st.hpar, st.last, st.done,
                            st.count, s.d.nblk, s.d.rows, t, o->eos_id, o->pad_id, groups, diversity};
+    if (cons) return beam_select(a, s.d.K, s.d.B, s.stream, cons->out(), cons->rule(o->eos_id));
     return beam_select(a, s.d.K, s.d.B, s.stream);
   }
   int finish(const Search& s) const {
@@ -252,23 +315,30 @@ struct SampleHead {
   const gic_sample_opts* o;
   const float* noise_u; uint64_t seed;
   int64_t* ids; float* scores; int32_t* lengths;
+  const Constraints* cons = nullptr;       // decode constraints (null: none)
   int live_stride(const DecodeDims&) const { return 1; }        // every row live from step 0
+  int eos() const { return o->eos_id; }
   int vocab(VocabStepArgs& v, const Search& s) const {
     v.logits = s.w.logits; v.ld_logits = s.d.V;
     return vocab_step_logits(v, s.d.dt, s.stream);
   }
   int logits(const Search&) const { return GIC_OK; }
-  int select(const Search& s, int t) const { return sample_step(s.w.logits, s.d.rows, s.d.V, o, noise_u, seed, t, s.w.st, s.stream); }
+  int select(const Search& s, int t) const {
+    if (!cons) return sample_step(s.w.logits, s.d.rows, s.d.V, o, noise_u, seed, t, s.w.st, s.stream);
+    return sample_step(s.w.logits, s.d.rows, s.d.V, o, noise_u, seed, t, s.w.st, s.stream, cons->lists(), cons->out(), cons->rule(o->eos_id));
+  }
   int finish(const Search& s) const { return sample_finalize(s.w.st, s.d.rows, s.d.L, o->pad_id, ids, scores, lengths, s.stream); }
 };
 
-// one search: beam_init and the recurrence's begin(), then per step the recurrence, the vocabulary product and the head's selection
+// one search: beam_init (and step 0's ban lists) and the recurrence's begin(), then per step the recurrence, the vocabulary product
+// and the head's selection
 template <typename Rec, typename Head>
 int decode(const DecodeDims& d, const Rec& rec, const Head& head, void* ws, const float* features, const float* h0, const float* c0,
            void* stream) {
   const DecodeBufs w = decode_layout(d, Head::kBeam, ws);
   const Search s{d, w, Head::kBeam ? d.B : d.rows, (hipStream_t)stream};
   GIC_PROPAGATE(beam_init(w.slot[0], d.NL, d.din(0), d.E, d.H, d.B, d.K, d.dt, features, h0, c0, w.st, s.stream, head.live_stride(d)));
+  if (head.cons) GIC_PROPAGATE(ban_init(head.cons->out(), head.cons->rule(head.eos()), d.rows, s.stream));
   GIC_PROPAGATE(rec.begin(s));
   const int top = d.NL - 1;
   for (int t = 0; t < d.L; ++t) {
@@ -400,6 +470,95 @@ int gic_attn_diverse_beam_search(const gic_attn_dims* dims, const gic_attn_param
   GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "attn_diverse_beam_search: the workspace must be 256-byte aligned");
   return decode(d, Attn{P, S, fmap, alphas != nullptr}, BeamHead{&o->beam, ids, scores, lengths, alphas, o->groups, o->diversity}, ws,
                 features, o->beam.h0, o->beam.c0, stream);
+}
+
+int gic_decode_constraints_ws_bytes(int64_t rows, int32_t L, const gic_decode_constraints* c, uint64_t* out) {
+  GIC_CHECK_ARG(c && out, "decode_constraints_ws_bytes: null argument");
+  GIC_CHECK_ARG(rows >= 1 && rows <= (1l << 24) && L >= 1 && L <= 1024, "decode_constraints_ws_bytes: rows must be 1..2^24 and L 1..1024");
+  GIC_CHECK_ARG(c->num_suppress >= 0 && c->num_suppress <= kBanSuppressMax, "decode_constraints_ws_bytes: num_suppress must be 0..%d, got %d",
+                kBanSuppressMax, c->num_suppress);
+  *out = (uint64_t)constraints_layout(c, (size_t)rows, L, nullptr).total;
+  return GIC_OK;
+}
+
+int gic_decoder_constrained_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
+                                        const gic_diverse_beam_opts* o, const gic_decode_constraints* c, void* ws, void* cws,
+                                        const float* features, int64_t* ids, float* scores, int32_t* lengths, void* stream) {
+  const char* who = "decoder_constrained_beam_search";
+  GIC_CHECK_ARG(o, "%s: null options", who);
+  DecodeDims d;
+  GIC_PROPAGATE(lstm_dims(dims, o->beam.beam, true, "decoder_constrained_beam", d));
+  GIC_PROPAGATE(check_lstm_args(P, S, d.NL, ws && features && ids && scores && lengths, who));
+  GIC_PROPAGATE(check_diverse_opts(o, d.V, who));
+  GIC_PROPAGATE(check_constraints(c, d.L, d.V, d.K, o->beam.eos_id, who));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+  BeamHead head{&o->beam, ids, scores, lengths, nullptr, o->groups, o->diversity};
+  if (constraints_off(c)) return lstm_decode(d, P, S, head, ws, features, o->beam.h0, o->beam.c0, stream);
+  GIC_CHECK_ARG(cws && ((uintptr_t)cws & 255) == 0, "%s: the constraint workspace must be non-null and 256-byte aligned", who);
+  const Constraints k = constraints_layout(c, (size_t)d.rows, d.L, cws);
+  head.cons = &k;
+  return lstm_decode(d, P, S, head, ws, features, o->beam.h0, o->beam.c0, stream);
+}
+
+int gic_attn_constrained_beam_search(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S,
+                                     const gic_diverse_beam_opts* o, const gic_decode_constraints* c, void* ws, void* cws,
+                                     const float* features, const void* fmap, int64_t* ids, float* scores, int32_t* lengths, float* alphas,
+                                     void* stream) {
+  const char* who = "attn_constrained_beam_search";
+  GIC_CHECK_ARG(o, "%s: null options", who);
+  DecodeDims d;
+  GIC_PROPAGATE(attn_dims(dims, o->beam.beam, true, "attn_constrained_beam", d));
+  GIC_PROPAGATE(check_attn_args(P, S, ws && features && fmap && ids && scores && lengths, who));
+  GIC_PROPAGATE(check_diverse_opts(o, d.V, who));
+  GIC_PROPAGATE(check_constraints(c, d.L, d.V, d.K, o->beam.eos_id, who));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+  BeamHead head{&o->beam, ids, scores, lengths, alphas, o->groups, o->diversity};
+  const Attn rec{P, S, fmap, alphas != nullptr};
+  if (constraints_off(c)) return decode(d, rec, head, ws, features, o->beam.h0, o->beam.c0, stream);
+  GIC_CHECK_ARG(cws && ((uintptr_t)cws & 255) == 0, "%s: the constraint workspace must be non-null and 256-byte aligned", who);
+  const Constraints k = constraints_layout(c, (size_t)d.rows, d.L, cws);
+  head.cons = &k;
+  return decode(d, rec, head, ws, features, o->beam.h0, o->beam.c0, stream);
+}
+
+int gic_decoder_constrained_sample_captions(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
+                                            const gic_sample_opts* o, const gic_decode_constraints* c, void* ws, void* cws,
+                                            const float* features, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
+                                            int32_t* lengths, void* stream) {
+  const char* who = "decoder_constrained_sample_captions";
+  GIC_CHECK_ARG(o, "%s: null options", who);
+  DecodeDims d;
+  GIC_PROPAGATE(lstm_dims(dims, o->num_samples, false, "decoder_constrained_sample", d));
+  GIC_PROPAGATE(check_sample_opts(o, d.V, true, who));
+  GIC_PROPAGATE(check_lstm_args(P, S, d.NL, ws && features && ids && scores && lengths, who));
+  GIC_PROPAGATE(check_constraints(c, d.L, d.V, 1, o->eos_id, who));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+  SampleHead head{o, noise_u, seed, ids, scores, lengths};
+  if (constraints_off(c)) return lstm_decode(d, P, S, head, ws, features, o->h0, o->c0, stream);
+  GIC_CHECK_ARG(cws && ((uintptr_t)cws & 255) == 0, "%s: the constraint workspace must be non-null and 256-byte aligned", who);
+  const Constraints k = constraints_layout(c, (size_t)d.rows, d.L, cws);
+  head.cons = &k;
+  return lstm_decode(d, P, S, head, ws, features, o->h0, o->c0, stream);
+}
+
+int gic_attn_constrained_sample_captions(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_sample_opts* o,
+                                         const gic_decode_constraints* c, void* ws, void* cws, const float* features, const void* fmap,
+                                         const float* noise_u, uint64_t seed, int64_t* ids, float* scores, int32_t* lengths, void* stream) {
+  const char* who = "attn_constrained_sample_captions";
+  GIC_CHECK_ARG(o, "%s: null options", who);
+  DecodeDims d;
+  GIC_PROPAGATE(attn_dims(dims, o->num_samples, false, "attn_constrained_sample", d));
+  GIC_PROPAGATE(check_sample_opts(o, d.V, true, who));
+  GIC_PROPAGATE(check_attn_args(P, S, ws && features && fmap && ids && scores && lengths, who));
+  GIC_PROPAGATE(check_constraints(c, d.L, d.V, 1, o->eos_id, who));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+  SampleHead head{o, noise_u, seed, ids, scores, lengths};
+  const Attn rec{P, S, fmap, false};
+  if (constraints_off(c)) return decode(d, rec, head, ws, features, o->h0, o->c0, stream);
+  GIC_CHECK_ARG(cws && ((uintptr_t)cws & 255) == 0, "%s: the constraint workspace must be non-null and 256-byte aligned", who);
+  const Constraints k = constraints_layout(c, (size_t)d.rows, d.L, cws);
+  head.cons = &k;
+  return decode(d, rec, head, ws, features, o->h0, o->c0, stream);
 }
 
 int gic_decoder_sample_ws_bytes(const gic_decoder_dims* dims, int32_t num_samples, uint64_t* out) {

@@ -369,8 +369,11 @@ __global__ __launch_bounds__(512) void lstm_step_beam_kernel(const LstmStepArgs 
 // BEAMK > 0: the beam-search epilogue (beam.h) in place of the sampling one -- raw logits y = o + b_out, per (row, tile) max, sum of
 // exp and top-BEAMK pairs in fixed slots; the product and its operand order are the roll-out's, so a beam's logits are sample's bits.
 // BEAMK < 0: the logits epilogue (vocab_step_logits) -- y = o + b_out stored in f32, one 16-byte store per lane and batch sub-tile
-template <typename TA, bool FAST, int BEAMK = 0>
-__device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const int KC, const int bx, const int by, unsigned char* vs_smem) {
+// BAN (with BEAMK > 0): the tile's top-BEAMK pairs are taken from the copy without the ids of the row's ban list (bans, a kernel
+// argument of its own: VocabStepArgs and with it the other instantiations' argument layout stay as they were)
+template <typename TA, bool FAST, int BEAMK = 0, bool BAN = false>
+__device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const int KC, const int bx, const int by, unsigned char* vs_smem,
+                                                const BanLists& bans = BanLists()) {
   constexpr int SZ = sizeof(TA), VE = 16 / SZ;
   const int H = a.H, V = a.V;
   const int hs = KC * SZ + 16;                             // LDS row stride of both tiles: 16-B skew against bank conflicts
@@ -541,7 +544,17 @@ __device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const in
       x[e] = tl[row * (kVocabTile + 1) + seg * 8 + e];
       ix[e] = v < V ? v : INT_MAX;
     }
-    beam_tile_reduce8<BEAMK>(x, ix, seg == 0 && b0 + row < a.B, (long)(b0 + row) * a.nblk + bx, a.part_m, a.part_s, a.part_v, a.part_i);
+    if constexpr (BAN) {
+      float xs[8];
+      int ixs[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { xs[e] = x[e]; ixs[e] = ix[e]; }
+      const int br = min(b0 + row, a.B - 1);
+      ban_apply8(xs, ixs, v0 + seg * 8, bans.ban + (long)br * bans.cap, bans.nban[br]);
+      beam_tile_reduce8_sel<BEAMK>(x, xs, ixs, seg == 0 && b0 + row < a.B, (long)(b0 + row) * a.nblk + bx, a.part_m, a.part_s, a.part_v, a.part_i);
+    } else {
+      beam_tile_reduce8<BEAMK>(x, ix, seg == 0 && b0 + row < a.B, (long)(b0 + row) * a.nblk + bx, a.part_m, a.part_s, a.part_v, a.part_i);
+    }
     return;
   }
 #pragma unroll
@@ -649,6 +662,12 @@ template <typename TA, int K>
 __global__ __launch_bounds__(512) void vocab_step_beam_kernel(const VocabStepArgs a, const int KC) {
   extern __shared__ __attribute__((aligned(16))) unsigned char vs_smem[];
   vocab_step_body<TA, false, K>(a, KC, blockIdx.x, blockIdx.y, vs_smem);
+}
+
+template <typename TA, int K>
+__global__ __launch_bounds__(512) void vocab_step_beam_ban_kernel(const VocabStepArgs a, const int KC, const BanLists bans) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char vs_smem[];
+  vocab_step_body<TA, false, K, true>(a, KC, blockIdx.x, blockIdx.y, vs_smem, bans);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -912,7 +931,20 @@ int vocab_step_logits(const VocabStepArgs& a0, int dtype, hipStream_t stream) {
 }
 
 template <int K>
-int vocab_beam_launch(const VocabStepArgs& a, int dtype, size_t lds, int KC, dim3 grid, hipStream_t stream) {
+int vocab_beam_launch(const VocabStepArgs& a, int dtype, size_t lds, int KC, dim3 grid, hipStream_t stream, const BanLists& bans) {
+  if (bans.nban) {                                            // decode constraints: the epilogue that reads the ban lists
+    if (dtype == DT_F32) {
+      static LdsGrant b32;
+      GIC_PROPAGATE(allow_lds(vocab_step_beam_ban_kernel<float, K>, lds, b32));
+      hipLaunchKernelGGL((vocab_step_beam_ban_kernel<float, K>), grid, dim3(512), lds, stream, a, KC, bans);
+    } else {
+      static LdsGrant b16;
+      GIC_PROPAGATE(allow_lds(vocab_step_beam_ban_kernel<bf16_t, K>, lds, b16));
+      hipLaunchKernelGGL((vocab_step_beam_ban_kernel<bf16_t, K>), grid, dim3(512), lds, stream, a, KC, bans);
+    }
+    GIC_CHECK_LAUNCH("vocab_step_beam");
+    return GIC_OK;
+  }
   if (dtype == DT_F32) {
     static LdsGrant g32;
     GIC_PROPAGATE(allow_lds(vocab_step_beam_kernel<float, K>, lds, g32));
@@ -926,18 +958,19 @@ int vocab_beam_launch(const VocabStepArgs& a, int dtype, size_t lds, int KC, dim
   return GIC_OK;
 }
 
-int vocab_step_beam(const VocabStepArgs& a0, int K, int dtype, hipStream_t stream) {
+int vocab_step_beam(const VocabStepArgs& a0, int K, int dtype, hipStream_t stream, const BanLists& bans) {
   VocabStepArgs a = a0;
   a.dbg = 0; a.pretrain = 1; a.u = nullptr; a.out = nullptr; a.rowkey = nullptr;
   GIC_CHECK_ARG(a.h && a.wout && a.bias && a.part_m && a.part_s && a.part_v && a.part_i, "vocab_step_beam: null buffer");
   GIC_CHECK_ARG(a.B > 0 && a.V >= 4 && a.V % 4 == 0 && a.H % 8 == 0 && a.ldh % 8 == 0 && K >= 1 && K <= kBeamMax, "vocab_step_beam: bad dims");
   GIC_CHECK_ARG(a.nblk == cdiv(a.V, kVocabTile), "vocab_step_beam: nblk must be ceil(V / %d)", kVocabTile);
+  GIC_CHECK_ARG(!bans.nban || (bans.ban && bans.cap > 0), "vocab_step_beam: ban lists without their buffer");
   const size_t tile = (size_t)kStepRows * (kVocabTile + 1) * sizeof(float);
   size_t lds = vocab_lds_bytes(dtype, a.H);
   if (lds < tile) lds = tile;
   const int KC = vocab_chunk(dtype, a.H);
   const dim3 grid((unsigned)a.nblk, (unsigned)cdiv(a.B, kStepRows));
-  return with_beam_k(K, [&](auto k) { return vocab_beam_launch<k>(a, dtype, lds, KC, grid, stream); });
+  return with_beam_k(K, [&](auto k) { return vocab_beam_launch<k>(a, dtype, lds, KC, grid, stream, bans); });
 }
 
 int sample_finish(const SampleFinishArgs& a, int dtype, hipStream_t stream) {

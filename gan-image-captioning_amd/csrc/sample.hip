@@ -39,6 +39,13 @@ struct SelArgs {
   int eos, t;
 };
 
+// decode constraints, the BAN kernel's own argument (SelArgs, and with it sample_select_kernel's argument layout, stay as they were)
+struct SelBan {
+  BanLists bans;                                 // the row's banned ids leave the kept set
+  BanOut bout; BanRule rule;                     // and the kernel's tail builds the row's list of step t + 1 (bout.nban / ban; hist unused)
+  const int* hbase = nullptr;                    // the history [L][rows] whose slot t is SelArgs::htok
+};
+
 // unsigned order of the keys = float order of the values; -0 and +0 share a key, as they are equal values (NaN never occurs in
 // logits that came from finite weights)
 __device__ __forceinline__ unsigned okey(float x) {
@@ -112,7 +119,13 @@ __device__ __forceinline__ int sel_argmax(float v, int i, SelRed& s, int& ph) {
   return bi;
 }
 
-__global__ __launch_bounds__(kSelThreads) void sample_select_kernel(const SelArgs a) {
+// BAN: after the score's logsumexp (over the raw values) the entries of the row's ban list become -inf, before the top-k / top-p
+// bisections and the draw; the max under top-p's exponent is then the admissible entries' own.  The workgroup owns its row and its
+// history, so once the token is drawn its first wave builds the row's list of the next step (unless the row has just finished)
+struct NoBan {};
+
+template <bool BAN, typename Ban>
+__global__ __launch_bounds__(kSelThreads) void sample_select_kernel(const SelArgs a, const Ban c) {
   __shared__ SelRed red;
   int ph = 0;
   const int r = blockIdx.x, tid = threadIdx.x, V = a.V;
@@ -130,6 +143,21 @@ __global__ __launch_bounds__(kSelThreads) void sample_select_kernel(const SelArg
       const int v = 4 * (tid + j * kSelThreads) + e;
       x[j][e] = v < V ? lr[v] : -INFINITY;
     }
+  int nb = 0;
+  const int* bl = nullptr;
+  if constexpr (BAN) {
+    nb = c.bans.nban[r];
+    bl = c.bans.ban + (long)r * c.bans.cap;      // (read from L2 as it is: staging it in LDS measured slower)
+  }
+  bool masked = false;                           // BAN: the banned entries read as -inf from here on
+  auto streamed = [&](int v) {                   // an entry beyond the registers
+    float l = lr[v];
+    if constexpr (BAN) {
+      if (masked)
+        for (int i = 0; i < nb; ++i) l = bl[i] == v ? -INFINITY : l;
+    }
+    return l;
+  };
   // f(l, v, j, e) for every entry of the row this thread holds; j < 0 for the streamed entries beyond the registers
   auto each = [&](auto&& f) {
 #pragma unroll
@@ -142,7 +170,7 @@ __global__ __launch_bounds__(kSelThreads) void sample_select_kernel(const SelArg
     for (int q = kSelQuads * kSelThreads + tid; q < nq; q += kSelThreads)
       for (int e = 0; e < 4; ++e) {
         const int v = 4 * q + e;
-        if (v < V) f(lr[v], v, -1, e);
+        if (v < V) f(streamed(v), v, -1, e);
       }
   };
 
@@ -154,6 +182,21 @@ __global__ __launch_bounds__(kSelThreads) void sample_select_kernel(const SelArg
   each([&](float l, int, int, int) { s1 += expf(l - m); });
   const float lse = m + logf(sel_sum(s1, red, ph));
   const float tau = a.temperature;
+  if constexpr (BAN) {
+    for (int i = 0; i < nb; ++i) {
+      const int b = bl[i], q = b >> 2;
+      if (q % kSelThreads != tid) continue;
+#pragma unroll
+      for (int j = 0; j < kSelQuads; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (q / kSelThreads == j && (b & 3) == e) x[j][e] = -INFINITY;
+    }
+    masked = true;
+    m = -INFINITY;
+    each([&](float l, int, int, int) { m = fmaxf(m, l); });
+    m = sel_max(m, red, ph);
+  }
 
   // ---- top-k: the largest key T with #{key >= T} >= k
   unsigned thr = 0u;
@@ -198,7 +241,7 @@ __global__ __launch_bounds__(kSelThreads) void sample_select_kernel(const SelArg
   auto quad = [&](const float (&l)[4], int q) {
     bool any = false;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) any |= 4 * q + e < V && okey(l[e]) >= thr;
+    for (int e = 0; e < 4; ++e) any |= 4 * q + e < V && okey(l[e]) >= thr && (!BAN || l[e] != -INFINITY);
     if (!any) return;
     float u[4];
     if (a.u) {
@@ -212,7 +255,7 @@ __global__ __launch_bounds__(kSelThreads) void sample_select_kernel(const SelArg
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int v = 4 * q + e;
-      if (v < V && okey(l[e]) >= thr) {
+      if (v < V && okey(l[e]) >= thr && (!BAN || l[e] != -INFINITY)) {
         const float y = l[e] / tau + gumbel(u[e]);
         if (arg_better(y, v, best, bi)) { best = y; bi = v; }
       }
@@ -222,7 +265,7 @@ __global__ __launch_bounds__(kSelThreads) void sample_select_kernel(const SelArg
   for (int j = 0; j < kSelQuads; ++j) quad(x[j], tid + j * kSelThreads);
   for (int q = kSelQuads * kSelThreads + tid; q < nq; q += kSelThreads) {
     float l[4];
-    for (int e = 0; e < 4; ++e) l[e] = 4 * q + e < V ? lr[4 * q + e] : -INFINITY;
+    for (int e = 0; e < 4; ++e) l[e] = 4 * q + e < V ? streamed(4 * q + e) : -INFINITY;
     quad(l, q);
   }
   const int tok = sel_argmax(best, bi, red, ph);
@@ -230,6 +273,15 @@ __global__ __launch_bounds__(kSelThreads) void sample_select_kernel(const SelArg
   if (a.kept) {
     each([&](float l, int, int, int) { nkept += okey(l) >= thr ? 1 : 0; });
     nkept = sel_count(nkept, red, ph);
+  }
+  if constexpr (BAN) {
+    __shared__ int hs[1024];                     // (L <= 1024: decode_dims)
+    const int tn = a.t + 1;                      // tokens emitted so far
+    const bool next = tn < c.bout.L && tok != a.eos;          // (block-uniform: every thread holds the drawn token)
+    if (next && tid < 64)
+      for (int i = tid; i < tn; i += 64) hs[i] = i < a.t ? c.hbase[(long)i * a.rows + r] : tok;
+    __syncthreads();
+    if (next && tid < 64) ban_list_wave(hs, tn, tid, c.rule, c.bout.ban + (long)r * c.bout.cap, c.bout.nban + r);
   }
   if (tid != 0) return;
   const float lp = lr[tok] - lse;
@@ -248,8 +300,9 @@ __global__ __launch_bounds__(kSelThreads) void sample_select_kernel(const SelArg
   }
 }
 
-int sample_select(const SelArgs& s, hipStream_t stream) {
-  hipLaunchKernelGGL(sample_select_kernel, dim3((unsigned)s.rows), dim3(kSelThreads), 0, stream, s);
+int sample_select(const SelArgs& s, hipStream_t stream, const SelBan& c = SelBan()) {
+  if (c.bans.nban) hipLaunchKernelGGL((sample_select_kernel<true, SelBan>), dim3((unsigned)s.rows), dim3(kSelThreads), 0, stream, s, c);
+  else hipLaunchKernelGGL((sample_select_kernel<false, NoBan>), dim3((unsigned)s.rows), dim3(kSelThreads), 0, stream, s, NoBan());
   GIC_CHECK_LAUNCH("sample_select");
   return GIC_OK;
 }
@@ -288,14 +341,16 @@ int check_sample_opts(const gic_sample_opts* o, int V, bool decode, const char* 
 }
 
 int sample_step(const float* logits, int rows, int V, const gic_sample_opts* o, const float* noise_u, uint64_t seed, int t, const BeamState& st,
-                hipStream_t stream) {
+                hipStream_t stream, const BanLists& bans, const BanOut& out, const BanRule& rule) {
   SelArgs s{};
   s.logits = logits; s.ld = V; s.rows = rows; s.V = V; s.top_k = o->top_k; s.top_p = o->top_p; s.temperature = o->temperature;
   s.u = noise_u ? noise_u + (long)t * rows * V : nullptr; s.ldu = V;
   s.seed = seed; s.stream = (uint64_t)t;
   s.tok = st.tok; s.fin = st.fin; s.len = st.len; s.score = st.score; s.htok = st.htok + (long)t * rows; s.count = st.count;
   s.eos = o->eos_id; s.t = t;
-  return sample_select(s, stream);
+  SelBan c;
+  c.bans = bans; c.bout = out; c.rule = rule; c.hbase = st.htok;
+  return sample_select(s, stream, c);
 }
 
 }  // namespace gic

@@ -269,6 +269,30 @@ def _diverse_opts(beam_opts, groups: int, diversity: float):
     return o
 
 
+def decode_constraints(no_repeat_ngram: int = 0, min_length: int = 0, suppress_tokens=()):
+    """gic_decode_constraints, or None when every constraint is at its default (the caller then runs the unconstrained entry point);
+    the library checks the values against the decode's L, V and eos_id."""
+    if suppress_tokens is None:
+        raise ValueError("suppress_tokens must be a sequence of token ids (empty: none), got None")
+    sup = [int(v) for v in suppress_tokens]
+    if not int(no_repeat_ngram) and not int(min_length) and not sup:
+        return None
+    if len(sup) > L.MAX_SUPPRESS:
+        raise ValueError(f"suppress_tokens holds {len(sup)} ids, at most {L.MAX_SUPPRESS} (num_suppress)")
+    c = L.DecodeConstraints()
+    c.no_repeat_ngram, c.min_length, c.num_suppress = int(no_repeat_ngram), int(min_length), len(sup)
+    for i, v in enumerate(sup):
+        c.suppress[i] = v
+    return c
+
+
+def _constraints_ws(c, rows: int, Lc: int, dev) -> torch.Tensor:
+    """The 256-byte aligned workspace of the per-row ban lists (gic_decode_constraints_ws_bytes)."""
+    out = C.c_uint64(0)
+    L.check(L.load().gic_decode_constraints_ws_bytes(int(rows), int(Lc), C.byref(c), C.byref(out)), "gic_decode_constraints_ws_bytes")
+    return _aligned_ws(None, int(out.value), dev)
+
+
 def _sample_noise(noise_u: Optional[torch.Tensor], Lc: int, rows: int, V: int) -> Optional[torch.Tensor]:
     if noise_u is None:
         return None
@@ -675,19 +699,25 @@ class DecoderEngine:
         return B * beam <= self.fused_rollout_rows()
 
     def beam_search(self, params, features: torch.Tensor, Lc: int, beam: int, eos_id: int = 2, pad_id: int = 0,
-                    length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None):
+                    length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None, no_repeat_ngram: int = 0,
+                    min_length: int = 0, suppress_tokens=()):
         """gic_decoder_beam_search: (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam]), beams best first.
-        ``states`` = (h0, c0), each f32 [NL, B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned)."""
-        return self._beam(params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, None)
+        ``states`` = (h0, c0), each f32 [NL, B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned).
+        ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: decode constraints (gic_decode_constraints); any of them set runs
+        gic_decoder_constrained_beam_search."""
+        return self._beam(params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, None,
+                          decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
 
     def diverse_beam_search(self, params, features: torch.Tensor, Lc: int, beam: int, groups: int, diversity: float, eos_id: int = 2,
-                            pad_id: int = 0, length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None):
+                            pad_id: int = 0, length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None,
+                            no_repeat_ngram: int = 0, min_length: int = 0, suppress_tokens=()):
         """gic_decoder_diverse_beam_search: ``beam`` beams in ``groups`` groups (which must divide ``beam``) with the Hamming penalty
         ``diversity``; (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam]) in group-major order, each group's
-        beams best first.  ``states`` and ``ws`` (beam_ws_bytes() for the same beam) as for beam_search."""
-        return self._beam(params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, (groups, diversity))
+        beams best first.  ``states`` and ``ws`` (beam_ws_bytes() for the same beam) and the decode constraints as for beam_search."""
+        return self._beam(params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, (groups, diversity),
+                          decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
 
-    def _beam(self, params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, diverse):
+    def _beam(self, params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, diverse, cons=None):
         self.check_params(params)
         require_gpu(features)
         features = _decode_features(features, self.E)
@@ -699,6 +729,13 @@ class DecoderEngine:
         keep = self._states(opts, states, B)
         ids, scores, lengths = _decode_outputs(B, beam, Lc, dev)
         d = self.dims(B, Lc)
+        if cons is not None:
+            o = _diverse_opts(opts, *(diverse or (1, 0.0)))
+            cws = _constraints_ws(cons, B * int(beam), Lc, dev)
+            L.check(L.load().gic_decoder_constrained_beam_search(
+                C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(o), C.byref(cons), ptr(ws),
+                ptr(cws), ptr(features), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()), "gic_decoder_constrained_beam_search")
+            return ids, scores, lengths
         if diverse is None:
             fn, name, o = L.load().gic_decoder_beam_search, "gic_decoder_beam_search", opts
         else:
@@ -716,10 +753,13 @@ class DecoderEngine:
 
     def sample_captions(self, params, features: torch.Tensor, Lc: int, num_samples: int, top_k: int = 0, top_p: float = 1.0,
                         temperature: float = 1.0, eos_id: int = 2, pad_id: int = 0, seed: int = 0,
-                        noise_u: Optional[torch.Tensor] = None, states=None, ws: Optional[torch.Tensor] = None):
+                        noise_u: Optional[torch.Tensor] = None, states=None, ws: Optional[torch.Tensor] = None,
+                        no_repeat_ngram: int = 0, min_length: int = 0, suppress_tokens=()):
         """gic_decoder_sample_captions: (ids int64 [B, n, Lc], scores f32 [B, n], lengths int32 [B, n]) in row order.  ``noise_u`` f32
         [Lc, B*n, V] or None = Philox(seed).  ``states`` = (h0, c0), each f32 [NL, B, H].  ``ws``: a uint8 workspace of at least
-        sample_ws_bytes() bytes (256-aligned)."""
+        sample_ws_bytes() bytes (256-aligned).  ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: decode constraints
+        (gic_decode_constraints); any of them set runs gic_decoder_constrained_sample_captions."""
+        cons = decode_constraints(no_repeat_ngram, min_length, suppress_tokens)
         self.check_params(params)
         require_gpu(features)
         features = _decode_features(features, self.E)
@@ -732,6 +772,13 @@ class DecoderEngine:
         ws = _aligned_ws(ws, nbytes, dev)
         keep = self._states(opts, states, B)
         ids, scores, lengths = _decode_outputs(B, n, Lc, dev)
+        if cons is not None:
+            cws = _constraints_ws(cons, B * n, Lc, dev)
+            L.check(L.load().gic_decoder_constrained_sample_captions(
+                C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts),
+                C.byref(cons), ptr(ws), ptr(cws), ptr(features), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores),
+                ptr(lengths), stream_ptr()), "gic_decoder_constrained_sample_captions")
+            return ids, scores, lengths
         L.check(L.load().gic_decoder_sample_captions(
             C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
             ptr(features), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()),
@@ -1125,21 +1172,25 @@ class AttnDecoderEngine:
         return int(out.value)
 
     def beam_search(self, params, features, fmap, Lc: int, beam: int, eos_id: int = 2, pad_id: int = 0, length_penalty: float = 0.0,
-                    states=None, ws: Optional[torch.Tensor] = None, want_alphas: bool = False):
+                    states=None, ws: Optional[torch.Tensor] = None, want_alphas: bool = False, no_repeat_ngram: int = 0,
+                    min_length: int = 0, suppress_tokens=()):
         """gic_attn_beam_search: (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam][, alphas f32 [B, beam, Lc, P]]),
         beams best first.  ``fmap`` [B, P, C] is cast to the compute dtype as in sample_fwd.  ``states`` = (h0, c0), each [1, B, H] or
-        [B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned)."""
-        return self._beam(params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, None)
+        [B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned).  ``no_repeat_ngram`` / ``min_length`` /
+        ``suppress_tokens``: decode constraints (gic_decode_constraints); any of them set runs gic_attn_constrained_beam_search."""
+        return self._beam(params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, None,
+                          decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
 
     def diverse_beam_search(self, params, features, fmap, Lc: int, beam: int, groups: int, diversity: float, eos_id: int = 2,
                             pad_id: int = 0, length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None,
-                            want_alphas: bool = False):
+                            want_alphas: bool = False, no_repeat_ngram: int = 0, min_length: int = 0, suppress_tokens=()):
         """gic_attn_diverse_beam_search: beam_search's outputs for ``beam`` beams in ``groups`` groups (which must divide ``beam``)
-        with the Hamming penalty ``diversity``, in group-major order, each group's beams best first."""
+        with the Hamming penalty ``diversity``, in group-major order, each group's beams best first; the decode constraints as for
+        beam_search."""
         return self._beam(params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas,
-                          (groups, diversity))
+                          (groups, diversity), decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
 
-    def _beam(self, params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, diverse):
+    def _beam(self, params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, diverse, cons=None):
         self.check_params(params)
         require_gpu(features, fmap)
         features = _decode_features(features, self.E)
@@ -1152,6 +1203,14 @@ class AttnDecoderEngine:
         keep = self._states(opts, states, B)
         ids, scores, lengths = _decode_outputs(B, beam, Lc, dev)
         alphas = torch.empty(B, beam, Lc, self.P, device=dev, dtype=torch.float32) if want_alphas else None
+        if cons is not None:
+            o = _diverse_opts(opts, *(diverse or (1, 0.0)))
+            cws = _constraints_ws(cons, B * int(beam), Lc, dev)
+            L.check(L.load().gic_attn_constrained_beam_search(
+                C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(o), C.byref(cons),
+                ptr(ws), ptr(cws), ptr(features), ptr(fmap), ptr(ids), ptr(scores), ptr(lengths), ptr(alphas), stream_ptr()),
+                "gic_attn_constrained_beam_search")
+            return (ids, scores, lengths, alphas) if want_alphas else (ids, scores, lengths)
         if diverse is None:
             fn, name, o = L.load().gic_attn_beam_search, "gic_attn_beam_search", opts
         else:
@@ -1170,10 +1229,13 @@ class AttnDecoderEngine:
 
     def sample_captions(self, params, features, fmap, Lc: int, num_samples: int, top_k: int = 0, top_p: float = 1.0,
                         temperature: float = 1.0, eos_id: int = 2, pad_id: int = 0, seed: int = 0,
-                        noise_u: Optional[torch.Tensor] = None, states=None, ws: Optional[torch.Tensor] = None):
+                        noise_u: Optional[torch.Tensor] = None, states=None, ws: Optional[torch.Tensor] = None,
+                        no_repeat_ngram: int = 0, min_length: int = 0, suppress_tokens=()):
         """gic_attn_sample_captions: (ids int64 [B, n, Lc], scores f32 [B, n], lengths int32 [B, n]) in row order.  ``fmap`` [B, P, C]
         is cast to the compute dtype as in sample_fwd.  ``noise_u`` f32 [Lc, B*n, V] or None = Philox(seed).  ``states`` = (h0, c0),
-        each [1, B, H] or [B, H]."""
+        each [1, B, H] or [B, H].  ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: decode constraints
+        (gic_decode_constraints); any of them set runs gic_attn_constrained_sample_captions."""
+        cons = decode_constraints(no_repeat_ngram, min_length, suppress_tokens)
         self.check_params(params)
         require_gpu(features, fmap)
         features = _decode_features(features, self.E)
@@ -1187,6 +1249,13 @@ class AttnDecoderEngine:
         ws = _aligned_ws(ws, nbytes, dev)
         keep = self._states(opts, states, B)
         ids, scores, lengths = _decode_outputs(B, n, Lc, dev)
+        if cons is not None:
+            cws = _constraints_ws(cons, B * n, Lc, dev)
+            L.check(L.load().gic_attn_constrained_sample_captions(
+                C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts),
+                C.byref(cons), ptr(ws), ptr(cws), ptr(features), ptr(fmap), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids),
+                ptr(scores), ptr(lengths), stream_ptr()), "gic_attn_constrained_sample_captions")
+            return ids, scores, lengths
         L.check(L.load().gic_attn_sample_captions(
             C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
             ptr(features), ptr(fmap), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()),

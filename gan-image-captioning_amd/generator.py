@@ -204,39 +204,46 @@ class Decoder(nn.Module):
         return pred, (h_n, c_n)
 
     def beam_search(self, features, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None, return_beams=False,
-                    beam_groups=1, diversity=0.0):
+                    beam_groups=1, diversity=0.0, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """Beam-search caption decode (gicap.h gic_decoder_beam_search): token log-probabilities of sample(pretrain=True)'s
         distribution, ``beam_size`` (1..8) hypotheses per image, <E> = ``eos_id`` ends a beam, <PAD> (0) after it; final order by
         score / length**length_penalty.  Returns detached (ids int64 [B, L], scores f32 [B], lengths int32 [B]) of the best beam, or
         all beams ([B, k, L], [B, k], [B, k]) with ``return_beams``.  ``max_caption_len`` None = args.max_seq_len.  ``beam_groups``
         > 1 or ``diversity`` > 0: diverse beam search (gic_decoder_diverse_beam_search), ``beam_groups`` groups of beam_size /
-        beam_groups beams with the Hamming penalty ``diversity``; the beams come in group-major order, the best beam is group 0's."""
+        beam_groups beams with the Hamming penalty ``diversity``; the beams come in group-major order, the best beam is group 0's.
+        ``no_repeat_ngram`` (n: no n-gram occurs twice in a caption; 0 = off), ``min_length`` (<E> not before that many
+        tokens; 0 = off) and ``suppress_tokens`` (up to 16 ids never emitted): decode constraints (gicap.h gic_decode_constraints),
+        applied inside the search."""
         L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
         with torch.no_grad():
             args = ([p.detach() for p in self.param_list()], features.detach().float(), L, int(beam_size))
+            cons = dict(no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
             if int(beam_groups) == 1 and float(diversity) == 0.0:
-                ids, scores, lengths = self.engine().beam_search(*args, int(eos_id), 0, float(length_penalty), states=states)
+                ids, scores, lengths = self.engine().beam_search(*args, int(eos_id), 0, float(length_penalty), states=states, **cons)
             else:
                 ids, scores, lengths = self.engine().diverse_beam_search(*args, int(beam_groups), float(diversity), int(eos_id), 0,
-                                                                         float(length_penalty), states=states)
+                                                                         float(length_penalty), states=states, **cons)
         if return_beams:
             return ids, scores, lengths
         return ids[:, 0], scores[:, 0], lengths[:, 0]
 
     def sample_captions(self, features, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
-                        noise_u=None, states=None):
+                        noise_u=None, states=None, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """Caption sampling (gicap.h gic_decoder_sample_captions): ``num_samples`` (1..8) captions per image drawn from softmax(logits /
         ``temperature``) truncated to the ``top_k`` largest logits (0 = off) and then to the nucleus of mass ``top_p`` (1 = off); ties at
         either boundary are kept.  <E> = ``eos_id`` ends a caption, <PAD> (0) after it.  ``temperature`` is the sampling temperature,
         not args.temperature.  ``noise_u`` f32 [L, B*n, V] replaces the device draw (Philox(seed); ``seed`` None = the next of SEEDS).
         Returns detached (ids int64 [B, n, L], scores f32 [B, n] = the model's log-probability of each caption, lengths int32 [B, n]),
-        in draw order.  ``max_caption_len`` None = args.max_seq_len."""
+        in draw order.  ``max_caption_len`` None = args.max_seq_len.  ``no_repeat_ngram`` (n: no n-gram occurs twice in a caption; 0 = off), ``min_length`` (<E> not before that many
+        tokens; 0 = off) and ``suppress_tokens`` (up to 16 ids never emitted): decode constraints (gicap.h gic_decode_constraints),
+        the banned tokens
+        leave the distribution before top-k / top-p."""
         L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
         seed = (0 if noise_u is not None else SEEDS.next()) if seed is None else int(seed)
         with torch.no_grad():
             return self.engine().sample_captions([p.detach() for p in self.param_list()], features.detach().float(), L, int(num_samples),
                                                  int(top_k), float(top_p), float(temperature), int(eos_id), 0, seed, noise_u,
-                                                 states=states)
+                                                 states=states, no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
 
     def add_gumbel(self, o_t, eps=1e-10, gpu=0):
         """o_t + Gumbel(0,1) noise (generator.py:84-96); on the hot path this is fused into sample()."""
@@ -333,33 +340,37 @@ class AttnDecoder(nn.Module):
                                                                    self.attn.w_h, self.attn.w_a]
 
     def beam_search(self, features, fmap=None, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None,
-                    return_beams=False, return_alphas=False, beam_groups=1, diversity=0.0):
+                    return_beams=False, return_alphas=False, beam_groups=1, diversity=0.0, no_repeat_ngram=0, min_length=0,
+                    suppress_tokens=()):
         """Beam-search caption decode with attention (gicap.h gic_attn_beam_search): Decoder.beam_search's search over the token
         log-probabilities of sample(features, fmap, pretrain=True).  ``fmap`` [B, P, C]: the trunk's last feature map
         (Encoder.forward_with_map).  Returns detached (ids int64 [B, L], scores f32 [B], lengths int32 [B]) of the best beam, or all beams
         ([B, k, L], [B, k], [B, k]) with ``return_beams``; ``return_alphas`` appends the attention weights with which each token was
         produced, f32 [B, L, P] (all beams: [B, k, L, P]), zero past a beam's length.  ``states`` = (h0, c0), each [1, B, H].
-        ``beam_groups`` / ``diversity``: diverse beam search (gic_attn_diverse_beam_search) as in Decoder.beam_search."""
+        ``beam_groups`` / ``diversity``: diverse beam search (gic_attn_diverse_beam_search) as in Decoder.beam_search, and so are the
+        decode constraints ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``."""
         if fmap is None:                # (checked before anything touches self: the LSTM decoder's call form has no map)
             raise NotImplementedError("the attention decoder's beam search needs the trunk's feature map: beam_search(features, fmap), "
                                       "or Generator.caption(images)")
         L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
         with torch.no_grad():
             args = ([p.detach() for p in self.param_list()], features.detach().float(), fmap.detach(), L, int(beam_size))
+            cons = dict(no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
             if int(beam_groups) == 1 and float(diversity) == 0.0:
                 out = self.engine().beam_search(*args, int(eos_id), 0, float(length_penalty), states=states,
-                                                want_alphas=bool(return_alphas))
+                                                want_alphas=bool(return_alphas), **cons)
             else:
                 out = self.engine().diverse_beam_search(*args, int(beam_groups), float(diversity), int(eos_id), 0, float(length_penalty),
-                                                        states=states, want_alphas=bool(return_alphas))
+                                                        states=states, want_alphas=bool(return_alphas), **cons)
         if return_beams:
             return out
         return tuple(t[:, 0] for t in out)
 
     def sample_captions(self, features, fmap=None, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2,
-                        seed=None, noise_u=None, states=None):
+                        seed=None, noise_u=None, states=None, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """Caption sampling with attention (gicap.h gic_attn_sample_captions): Decoder.sample_captions with the step of sample(features,
-        fmap).  ``fmap`` [B, P, C]: the trunk's last feature map (Encoder.forward_with_map).  ``states`` = (h0, c0), each [1, B, H]."""
+        fmap).  ``fmap`` [B, P, C]: the trunk's last feature map (Encoder.forward_with_map).  ``states`` = (h0, c0), each [1, B, H].
+        ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: the decode constraints of Decoder.sample_captions."""
         if fmap is None:                # (checked before anything touches self: the LSTM decoder's call form has no map)
             raise NotImplementedError("the attention decoder's sampling needs the trunk's feature map: sample_captions(features, fmap), "
                                       "or Generator.sample_captions(images)")
@@ -368,7 +379,7 @@ class AttnDecoder(nn.Module):
         with torch.no_grad():
             return self.engine().sample_captions([p.detach() for p in self.param_list()], features.detach().float(), fmap.detach(), L,
                                                  int(num_samples), int(top_k), float(top_p), float(temperature), int(eos_id), 0, seed,
-                                                 noise_u, states=states)
+                                                 noise_u, states=states, no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
 
     def forward(self, features, fmap, caps, lengths, pretrain=False, noise_u=None, return_alphas=False, max_length=None):
         """Teacher-forced decode (Decoder.forward with the attention step, gicap.h gic_attn_forward_tf): step 0 is fed ``features``,
@@ -581,17 +592,19 @@ class Generator(nn.Module):
         self.init_params()
 
     def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False, return_alphas=False,
-                beam_groups=1, diversity=0.0):
+                beam_groups=1, diversity=0.0, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """Captions for ``images`` by beam search: features as the trainer forms them (training.py:66-68) -- the encoder in the
         module's current mode, or embed(<S>) with --conditional-gan 0 -- under no-grad, then ``decoder.beam_search``.  With
         --decoder attention the encoder also gives the feature map, and ``return_alphas`` appends the attention weights
-        (AttnDecoder.beam_search).  ``beam_groups`` / ``diversity``: diverse beam search (Decoder.beam_search)."""
+        (AttnDecoder.beam_search).  ``beam_groups`` / ``diversity``: diverse beam search (Decoder.beam_search).  ``no_repeat_ngram`` /
+        ``min_length`` / ``suppress_tokens``: decode constraints (Decoder.beam_search)."""
+        cons = dict(no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
         with torch.no_grad():
             if isinstance(self.decoder, AttnDecoder):
                 features, fmap = self.encoder.forward_with_map(images)
                 return self.decoder.beam_search(features, fmap, beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id,
                                                 length_penalty=length_penalty, return_beams=return_beams, return_alphas=return_alphas,
-                                                beam_groups=beam_groups, diversity=diversity)
+                                                beam_groups=beam_groups, diversity=diversity, **cons)
             if return_alphas:
                 raise ValueError("attention weights exist for --decoder attention only")
             if self.args.conditional_gan:
@@ -600,15 +613,16 @@ class Generator(nn.Module):
                 features = self.decoder.embed(torch.ones(len(images), dtype=torch.long, device=images.device))
             return self.decoder.beam_search(features, beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id,
                                             length_penalty=length_penalty, return_beams=return_beams, beam_groups=beam_groups,
-                                            diversity=diversity)
+                                            diversity=diversity, **cons)
 
     def sample_captions(self, images, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
-                        noise_u=None):
+                        noise_u=None, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """``num_samples`` sampled captions per image (decoder.sample_captions), with the features formed as ``caption`` forms them:
         the encoder in the module's current mode, or embed(<S>) with --conditional-gan 0, under no-grad; with --decoder attention the
-        encoder also gives the feature map.  Returns (ids [B, n, L], scores [B, n], lengths [B, n])."""
+        encoder also gives the feature map.  ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: decode constraints
+        (Decoder.sample_captions).  Returns (ids [B, n, L], scores [B, n], lengths [B, n])."""
         kw = dict(num_samples=num_samples, top_k=top_k, top_p=top_p, temperature=temperature, max_caption_len=max_caption_len,
-                  eos_id=eos_id, seed=seed, noise_u=noise_u)
+                  eos_id=eos_id, seed=seed, noise_u=noise_u, no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
         with torch.no_grad():
             if isinstance(self.decoder, AttnDecoder):
                 features, fmap = self.encoder.forward_with_map(images)

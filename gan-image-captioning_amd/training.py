@@ -420,8 +420,9 @@ class GANInstructor:
         (``filepath`` + ``filename`` for COCO_data, one image per item otherwise), every image is loaded and decoded once in eval
         mode, ids map through ``index_to_word`` with <S>, <E>, <PAD> stripped.  Captions are decoded up to ``max_caption_len``
         steps, by default max(args.max_seq_len, longest reference of the batch + 2): a batch's collate length, so that a short
-        --max-seq-len cannot truncate every candidate below its references.  Logs the score and writes the scalar
-        ``BLEU4_<what>``."""
+        --max-seq-len cannot truncate every candidate below its references.  --eval-no-repeat-ngram / --eval-min-length /
+        --eval-suppress-tokens constrain the decode (``_eval_constraints``), here and in the other evaluations.  Logs the score and
+        writes the scalar ``BLEU4_<what>``."""
         from .utils import bleu_score
         words = self._eval_groups(what)[-1]
         cands, refs = [], []
@@ -435,10 +436,17 @@ class GANInstructor:
         self.writer.add_scalar(f"BLEU4_{what}", score, max(self.adv_epoch, 0))
         return score
 
+    def _eval_constraints(self):
+        """The decode constraints of every evaluation (--eval-no-repeat-ngram, --eval-min-length, --eval-suppress-tokens) as the
+        keywords of Generator.caption / sample_captions."""
+        return dict(no_repeat_ngram=int(getattr(self.args, "eval_no_repeat_ngram", 0) or 0),
+                    min_length=int(getattr(self.args, "eval_min_length", 0) or 0),
+                    suppress_tokens=tuple(int(v) for v in (getattr(self.args, "eval_suppress_tokens", ()) or ())))
+
     def _beam_decode(self, what, beam_size, max_caption_len=None, batch_size=None):
         """The decode of ``evaluate`` / ``evaluate_cider``: the best beam of each image (``_decode_batches``)."""
         def decode(images, L, _):
-            ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L)
+            ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L, **self._eval_constraints())
             return ids, lengths
         return self._decode_batches(what, decode, max_caption_len, batch_size)
 
@@ -505,7 +513,7 @@ class GANInstructor:
         values and writes the scalars ``<Name>_<what>`` (BLEU4S, mBLEU4, Distinct1, Distinct2, Vocab).  ``seed`` fixes the draws."""
         def decode(images, L, bi):
             ids, _, lengths = self.gen.sample_captions(images, num_samples=num_samples, top_k=top_k, top_p=top_p, temperature=temperature,
-                                                       max_caption_len=L, seed=int(seed) + bi)
+                                                       max_caption_len=L, seed=int(seed) + bi, **self._eval_constraints())
             return ids, lengths
         out = self._diversity(what, decode, max_caption_len, batch_size)
         self.log.info("[EVAL] diversity (%s, n %d, top-k %d, top-p %.3f, temperature %.3f): BLEU-4 %.4f | mBLEU-4 %.4f | distinct-1 %.4f"
@@ -522,7 +530,7 @@ class GANInstructor:
         values and writes the scalars ``<Name>_<what>`` (BLEU4DBS, mBLEU4DBS, Distinct1DBS, Distinct2DBS, VocabDBS)."""
         def decode(images, L, _):
             ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L, length_penalty=length_penalty,
-                                               return_beams=True, beam_groups=groups, diversity=diversity)
+                                               return_beams=True, beam_groups=groups, diversity=diversity, **self._eval_constraints())
             return ids, lengths
         out = self._diversity(what, decode, max_caption_len, batch_size)
         self.log.info("[EVAL] diverse beam (%s, beam %d, groups %d, diversity %.3f): BLEU-4 %.4f | mBLEU-4 %.4f | distinct-1 %.4f"

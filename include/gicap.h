@@ -442,6 +442,57 @@ int gic_attn_sample_captions(const gic_attn_dims* dims, const gic_attn_params* p
                              const gic_sample_opts* opts, void* ws, const float* features, const void* fmap, const float* noise_u,
                              uint64_t seed, int64_t* ids, float* scores, int32_t* lengths, void* stream);
 
+/* Decode constraints for the beam, diverse-beam and sampling decodes of either decoder: what a caption may not contain.  A constraint
+ * set is (n = no_repeat_ngram, min_length, suppress[0..S), S = num_suppress).  A live row about to emit its token of step t (0-based)
+ * has the history y_0..y_{t-1} of the tokens it has emitted (in a beam search: the chain through the parent pointers, not the row
+ * index).  Its banned set is
+ *     banned = set(suppress)
+ *     if t + 1 < min_length: banned.add(eos_id)
+ *     if n >= 1 and t >= n - 1:
+ *         prefix = y[t-n+1 : t]                       (n-1 tokens; empty for n = 1)
+ *         for i in range(0, t - n + 1):
+ *             if y[i : i+n-1] == prefix: banned.add(y[i+n-1])
+ * (n = 1: every token already emitted).
+ *   beam, diverse beam   a live row proposes its top-K tokens by raw logit AMONG THE TOKENS NOT BANNED, ties to the lower id.  The token
+ *                        log-probability stays logit - logsumexp(all V logits): the constraint truncates the choice and never
+ *                        renormalises.  Finished rows, the pad proposal, the tie orders, the Hamming count of the diverse groups, early
+ *                        stop, lengths and the final order are those of the unconstrained searches.
+ *   sampling             the banned tokens are removed first; top-k takes the k largest of what remains and top-p is renormalised over
+ *                        that; the draw is the same Gumbel-max over the kept set; scores stay the running sum of l_tok - logsumexp(l)
+ *                        over the full vocabulary.
+ * A caption that cannot end before L steps has length L and no eos_id.  Limits: n and min_length in 0..L (0 = off), S in 0..16, every
+ * suppressed id in [0, V) and none equal to eos_id (min_length = L forbids eos_id), and enough admissible tokens for every row to
+ * propose K (the beam size; 1 for sampling): V - (S + 1 + max(0, L - n)) >= K when n >= 1, V - (S + 1) >= K when n = 0.  Every check
+ * runs before any launch and returns GIC_STATUS_INVALID_ARG.  With n = 0, min_length = 0, S = 0 every constrained entry point returns
+ * the bits of its unconstrained counterpart.
+ * cws: the per-row ban lists, a caller-owned 256-byte aligned buffer of gic_decode_constraints_ws_bytes(rows = B * K, L, c) bytes,
+ * separate from the search's own workspace `ws` (that of the unconstrained call).  The other arguments and the outputs are those of
+ * gic_*_diverse_beam_search (groups = 1: plain beam search) and gic_*_sample_captions.  Integer atomics only: two calls on the same
+ * inputs give the same bits, and the deterministic mode accepts the calls and gives the same bits as outside it. */
+typedef struct gic_decode_constraints {
+  int32_t no_repeat_ngram;               /* n: 0 = off, else 1..L */
+  int32_t min_length;                    /* 0 = off, else 1..L: eos_id is banned while t + 1 < min_length */
+  int32_t num_suppress;                  /* S: 0..16 */
+  int32_t suppress[16];                  /* the first S are read: ids in [0, V), never eos_id */
+} gic_decode_constraints;
+int gic_decode_constraints_ws_bytes(int64_t rows, int32_t L, const gic_decode_constraints* c, uint64_t* out);   /* host-only: no GPU needed */
+int gic_decoder_constrained_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* params, const gic_decoder_shadow* shadow,
+                                        const gic_diverse_beam_opts* opts, const gic_decode_constraints* c, void* ws, void* cws,
+                                        const float* features, int64_t* ids, float* scores, int32_t* lengths, void* stream);
+int gic_attn_constrained_beam_search(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                                     const gic_diverse_beam_opts* opts, const gic_decode_constraints* c, void* ws, void* cws,
+                                     const float* features, const void* fmap, int64_t* ids, float* scores, int32_t* lengths,
+                                     float* alphas, void* stream);
+int gic_decoder_constrained_sample_captions(const gic_decoder_dims* dims, const gic_decoder_params* params,
+                                            const gic_decoder_shadow* shadow, const gic_sample_opts* opts,
+                                            const gic_decode_constraints* c, void* ws, void* cws, const float* features,
+                                            const float* noise_u, uint64_t seed, int64_t* ids, float* scores, int32_t* lengths,
+                                            void* stream);
+int gic_attn_constrained_sample_captions(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                                         const gic_sample_opts* opts, const gic_decode_constraints* c, void* ws, void* cws,
+                                         const float* features, const void* fmap, const float* noise_u, uint64_t seed, int64_t* ids,
+                                         float* scores, int32_t* lengths, void* stream);
+
 /* Teacher-forced decode with the attention decoder: the semantics of gic_decoder_forward_tf with the step of gic_attn_sample_fwd.
  * dims->L = T = caption length + 1: step 0 is fed `features`, step t > 0 embed(caps[b, t-1]) (caps int64 [B, T-1]; may be NULL when
  * T = 1); the attention of step t uses h_{t-1} and the LSTM input is [x_t ; z_t].  lengths int32 [B] (each 1..T) with
