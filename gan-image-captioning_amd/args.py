@@ -107,12 +107,18 @@ _NATIVE = [
     ("--scst-baseline", str, "greedy", "SCST baseline: greedy = the CIDEr-D of the greedy caption; mean = the mean reward of the image's "
                                        "other samples (needs --scst-samples >= 2)", {"choices": ["greedy", "mean"]}),
     ("--scst-lr", float, 5e-5, "learning rate of SCST (its own clip + Adam over the generator's parameters)"),
+    ("--scst-cider-weight", float, 1.0, "weight of CIDEr-D in the SCST reward (metrics.RewardMix; scores in their native units)"),
+    ("--scst-bleu-weight", float, 0.0, "weight of the add-one smoothed sentence BLEU-4 in the SCST reward; with this and "
+                                       "--scst-rouge-weight 0 and --scst-cider-weight 1 the reward is the plain CIDEr-D scorer"),
+    ("--scst-rouge-weight", float, 0.0, "weight of ROUGE-L in the SCST reward"),
     ("--eval-diverse-beam-size", int, 0, "beam size of the diverse-beam-search diversity evaluation (GANInstructor.evaluate_diverse_beam: "
                                          "BLEU-4, mBLEU-4, distinct-1/2, vocabulary) after each adversarial epoch's validation; 0 = off"),
     ("--eval-diverse-groups", int, 2, "groups of that evaluation's diverse beam search (must divide --eval-diverse-beam-size)"),
     ("--eval-diversity-strength", float, 0.5, "Hamming diversity penalty (lambda >= 0) of that evaluation's diverse beam search"),
     ("--eval-cider-beam-size", int, 0, "beam size of the CIDEr-D evaluation (GANInstructor.evaluate_cider) after each adversarial epoch's "
                                        "validation; 0 = off"),
+    ("--eval-metrics-beam-size", int, 0, "beam size of the metrics-table evaluation (GANInstructor.evaluate_metrics: BLEU-1..4, ROUGE-L "
+                                         "and CIDEr-D scored on the GPU from one decode) after each adversarial epoch's validation; 0 = off"),
     ("--eval-no-repeat-ngram", int, 0, "decode constraint of the evaluations (evaluate, evaluate_cider, evaluate_diversity, "
                                        "evaluate_diverse_beam): no n-gram of this size occurs twice in a caption; 0 = off"),
     ("--eval-min-length", int, 0, "decode constraint of the evaluations: <E> is not emitted before this many tokens; 0 = off"),

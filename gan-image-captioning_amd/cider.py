@@ -122,6 +122,19 @@ class RefBatch:
                         self.offsets.to(device, non_blocking=True), self.max_refs)
 
 
+def flat_candidates(cand_ids: torch.Tensor, refs: RefBatch, cand_img: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two candidate shapes of the scorers as (ids [rows, L], image index int32 [rows]): [B, n, L] (n per image, image-major), or
+    [rows, L] with ``cand_img`` (None with rows = B: one per image)."""
+    dev = cand_ids.device
+    B = refs.num_images
+    if cand_ids.dim() == 3:
+        if cand_ids.shape[0] != B:
+            raise ValueError(f"candidates for {cand_ids.shape[0]} images, references for {B}")
+        n = cand_ids.shape[1]
+        return cand_ids.reshape(B * n, cand_ids.shape[2]), torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(n)
+    return cand_ids, (torch.arange(cand_ids.shape[0], device=dev, dtype=torch.int32) if cand_img is None else cand_img)
+
+
 class CiderD:
     """CIDEr-D scorer whose document frequencies come from ``corpus`` (per-image lists of reference token lists); holds the table on
     ``device``.  ``vocab_size`` above 32768 is refused (15-bit keys)."""
@@ -141,17 +154,7 @@ class CiderD:
         """CIDEr-D of candidates int64 [B, n, L] (n per image, image-major) or [rows, L] with ``cand_img`` int [rows] (None with
         rows = B: one per image) against ``refs`` (a RefBatch on the device, B images).  ``cand_lengths``: the ids before each length
         are the caption (specials are dropped).  Returns device f32 scores of ``cand_lengths``'s shape; no host sync."""
-        dev = cand_ids.device
-        B = refs.num_images
-        if cand_ids.dim() == 3:
-            if cand_ids.shape[0] != B:
-                raise ValueError(f"candidates for {cand_ids.shape[0]} images, references for {B}")
-            n = cand_ids.shape[1]
-            flat = cand_ids.reshape(B * n, cand_ids.shape[2])
-            img = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(n)
-        else:
-            flat = cand_ids
-            img = torch.arange(flat.shape[0], device=dev, dtype=torch.int32) if cand_img is None else cand_img
+        flat, img = flat_candidates(cand_ids, refs, cand_img)
         if flat.shape[1] > _lib.CIDER_MAX_LEN:
             raise ValueError(f"candidates of {flat.shape[1]} ids: CIDEr-D scores at most {_lib.CIDER_MAX_LEN}")
         out = engine.cider_d(flat, cand_lengths.reshape(-1), img, refs.ids, refs.lengths, refs.offsets, refs.max_refs, self.keys, self.idf,

@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "../../include/gicap.h"
+#include "caption_tokens.h"
 #include "common.h"
 
 namespace gic {
@@ -52,28 +53,6 @@ __device__ float lookup_idf(uint64_t key, const CiderArgs& a) {
     if (a.keys[mid] < key) lo = mid + 1; else hi = mid;
   }
   return (lo < a.K && a.keys[lo] == key) ? a.idf[lo] : a.log_n;
-}
-
-// A wave strips <PAD>/<S>/<E> from the first `len` ids of `row` into dst[0..count) (zeros after); returns count (wave-uniform).
-__device__ __forceinline__ int strip_row(const int64_t* row, int len, int* dst) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t t = lane < len ? row[lane] : 0;
-  const bool keep = lane < len && t > 2;
-  const uint64_t bal = __ballot(keep);
-  const int pos = __popcll(bal & ((1ull << lane) - 1ull));
-  const int cnt = __popcll(bal);
-  dst[lane] = 0;
-  if (lane < 4) dst[WAVE + lane] = 0;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  if (keep) dst[pos] = (int)(t & 0x7fff);
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  return cnt;
-}
-
-__device__ __forceinline__ uint64_t window(const int* tok, int p) {
-  return ((uint64_t)tok[p] << 45) | ((uint64_t)tok[p + 1] << 30) | ((uint64_t)tok[p + 2] << 15) | (uint64_t)tok[p + 3];
 }
 
 __global__ __launch_bounds__(kThreads) void cider_d_kernel(const CiderArgs a) {

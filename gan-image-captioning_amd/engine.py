@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -383,6 +383,32 @@ def cider_d(cand_ids: torch.Tensor, cand_len: torch.Tensor, cand_img: torch.Tens
                                  n_ref, Lr, B, int(max_refs), ptr(keys.contiguous()), ptr(idf.contiguous()), keys.numel(), float(log_n),
                                  int(V), ptr(scores), stream_ptr()), "gic_cider_d")
     return scores
+
+
+def caption_overlap(cand_ids: torch.Tensor, cand_len: torch.Tensor, cand_img: torch.Tensor, ref_ids: torch.Tensor, ref_len: torch.Tensor,
+                    ref_off: torch.Tensor, max_refs: int, V: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """gic_caption_overlap: (stats int32 [n_cand, 10], ROUGE-L f32 [n_cand], smoothed sentence BLEU-4 f32 [n_cand]) of candidates int64
+    [n_cand, Lc] against the references, both laid out as for ``cider_d``; the stats columns are the per-candidate integers of corpus
+    BLEU-1..4 (gicap.h).  One launch, no host sync."""
+    require_gpu(cand_ids, cand_len, cand_img, ref_ids, ref_len, ref_off)
+    if cand_ids.dim() != 2 or ref_ids.dim() != 2 or cand_ids.dtype != torch.int64 or ref_ids.dtype != torch.int64:
+        raise ValueError("cand_ids and ref_ids must be int64 [rows, L]")
+    n_cand, Lc = cand_ids.shape
+    n_ref, Lr = ref_ids.shape
+    B = ref_off.numel() - 1
+    i32 = lambda t: t.to(torch.int32).contiguous()        # noqa: E731
+    cand_ids, ref_ids = cand_ids.contiguous(), ref_ids.contiguous()
+    cand_len, cand_img, ref_len, ref_off = i32(cand_len), i32(cand_img), i32(ref_len), i32(ref_off)
+    if cand_len.numel() != n_cand or cand_img.numel() != n_cand or ref_len.numel() != n_ref:
+        raise ValueError("cand_len / cand_img need one value per candidate and ref_len one per reference")
+    dev = cand_ids.device
+    stats = torch.empty(n_cand, L.OVERLAP_STATS, device=dev, dtype=torch.int32)
+    rouge = torch.empty(n_cand, device=dev, dtype=torch.float32)
+    sbleu = torch.empty(n_cand, device=dev, dtype=torch.float32)
+    L.check(L.load().gic_caption_overlap(ptr(cand_ids), Lc, ptr(cand_len), ptr(cand_img), n_cand, Lc, ptr(ref_ids), Lr, ptr(ref_len),
+                                         ptr(ref_off), n_ref, Lr, B, int(max_refs), int(V), ptr(stats), ptr(rouge), ptr(sbleu),
+                                         stream_ptr()), "gic_caption_overlap")
+    return stats, rouge, sbleu
 
 
 # ------------------------------------------------------------------------------------------ decoder

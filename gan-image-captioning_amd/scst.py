@@ -5,7 +5,8 @@ One step (every tensor stays on the device; the caller reads the returned scalar
   1. features         GANInstructor._features with autograd, in the current train mode (encoder head / embed(<S>) / attention map)
   2. n samples        sample_captions at temperature 1, no truncation (the policy itself), up to max_caption_len steps
   3. baseline         greedy: beam search k = 1 on the detached features; mean: the mean reward of the image's other n - 1 samples
-  4. rewards          ONE gic_cider_d launch for the B*n samples (and the B greedy captions)
+  4. rewards          ONE gic_cider_d launch for the B*n samples (and the B greedy captions); with --scst-bleu-weight / --scst-rouge-weight
+                      a metrics.RewardMix adds one gic_caption_overlap launch (smoothed sentence BLEU-4, ROUGE-L) and the weighted sum
   5. teacher-forced   decoder.forward over the B*n samples (caps = ids[:, :-1], the sampled lengths, features repeated per sample),
                       max_length = L so that the device lengths are never read back
   6. loss             -(1/(B n)) sum_i (r_i - b_i) sum_{t < len_i} log p(y_it): gic_xent with row weights (r_i - b_i) * L (zero past a
@@ -14,13 +15,16 @@ One step (every tensor stays on the device; the caller reads the returned scalar
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import TYPE_CHECKING, Optional, Union
 
 import torch
 
 from . import engine
 from .cider import CiderD, RefBatch
 from .generator import SEEDS
+
+if TYPE_CHECKING:
+    from .metrics import RewardMix
 
 
 class _WeightedNLLFn(torch.autograd.Function):
@@ -38,10 +42,10 @@ class _WeightedNLLFn(torch.autograd.Function):
 
 
 class SCSTStep:
-    """SCST generator update bound to a GANInstructor (its generator, ``_features``, ``optimize`` and reducer) and a CIDEr-D scorer whose
-    table holds the training references' document frequencies."""
+    """SCST generator update bound to a GANInstructor (its generator, ``_features``, ``optimize`` and reducer) and a reward scorer: a
+    CIDEr-D scorer whose table holds the training references' document frequencies, or anything with its ``score`` (metrics.RewardMix)."""
 
-    def __init__(self, inst, scorer: CiderD, num_samples: int = 5, baseline: str = "greedy", lr: float = 5e-5):
+    def __init__(self, inst, scorer: Union[CiderD, "RewardMix"], num_samples: int = 5, baseline: str = "greedy", lr: float = 5e-5):
         from .optim import FusedClipAdam
         if baseline not in ("greedy", "mean"):
             raise ValueError(f"--scst-baseline must be greedy or mean, got {baseline!r}")

@@ -74,6 +74,21 @@ def _lookahead(loader, device):
     yield cur, None
 
 
+def scst_reward_scorer(args, corpus):
+    """The reward scorer of SCST from --scst-cider-weight / --scst-bleu-weight / --scst-rouge-weight, with document frequencies from
+    ``corpus`` (per-image lists of reference token lists): at the defaults (1, 0, 0) the plain ``CiderD`` -- the launches and the bits
+    of a CIDEr-only step -- else a ``metrics.RewardMix`` that builds only the scorers its weights use."""
+    from .cider import CiderD
+    from .metrics import OverlapScorer, RewardMix, _check_weights
+    w = _check_weights(getattr(args, "scst_cider_weight", 1.0), getattr(args, "scst_bleu_weight", 0.0),
+                       getattr(args, "scst_rouge_weight", 0.0))              # a bad weight fails before any table is built
+    if w == (1.0, 0.0, 0.0):
+        return CiderD(corpus, args.vocab_size, args.device)
+    cider = CiderD(corpus, args.vocab_size, args.device) if w[0] > 0.0 else None
+    overlap = OverlapScorer(args.vocab_size, args.device) if w[1] > 0.0 or w[2] > 0.0 else None
+    return RewardMix(cider, overlap, *w)
+
+
 class GANInstructor:
     def __init__(self, args, train_dataset, dev_dataset):
         self.args = args
@@ -338,15 +353,16 @@ class GANInstructor:
     # ------------------------------------------------------------------ self-critical sequence training (scst.py)
     def scst_train(self, epochs):
         """``epochs`` SCST epochs over the training images (grouped by image, --adv-train-batch-size images per step): CIDEr-D
-        rewards with df from the training references.  After each epoch the greedy CIDEr-D on val decides whether the generator is
+        rewards with df from the training references, or the mix of --scst-cider-weight / --scst-bleu-weight / --scst-rouge-weight
+        (``scst_reward_scorer``).  After each epoch the greedy CIDEr-D on val decides whether the generator is
         saved as ``scst_model.ckpt`` (the generator's state dict: --resume loads it as pretrained weights).  Returns the best val
         CIDEr-D."""
-        from .cider import CiderD, RefBatch
+        from .cider import RefBatch
         from .scst import SCSTStep
         from .tasks import ImageGroups, collate_groups
         args = self.args
         groups = ImageGroups(self.train_dataset)
-        step = SCSTStep(self, CiderD(groups.references(), args.vocab_size, args.device), int(getattr(args, "scst_samples", 5)),
+        step = SCSTStep(self, scst_reward_scorer(args, groups.references()), int(getattr(args, "scst_samples", 5)),
                         getattr(args, "scst_baseline", "greedy"), float(getattr(args, "scst_lr", 5e-5)))
         dp = self.dist.world_size > 1
         loader = DataLoader(groups, shuffle=not dp, batch_size=args.adv_train_batch_size, collate_fn=collate_groups,
@@ -405,6 +421,8 @@ class GANInstructor:
                 self.evaluate("val", beam_size=int(self.args.eval_beam_size))
             if int(getattr(self.args, "eval_cider_beam_size", 0)) > 0 and self.dist.rank == 0:
                 self.evaluate_cider("val", beam_size=int(self.args.eval_cider_beam_size))
+            if int(getattr(self.args, "eval_metrics_beam_size", 0)) > 0 and self.dist.rank == 0:
+                self.evaluate_metrics("val", beam_size=int(self.args.eval_metrics_beam_size))
             if int(getattr(self.args, "eval_num_samples", 0)) > 0 and self.dist.rank == 0:
                 self.evaluate_diversity("val", num_samples=int(self.args.eval_num_samples), top_k=int(getattr(self.args, "eval_top_k", 0)),
                                         top_p=float(getattr(self.args, "eval_top_p", 1.0)),
@@ -488,6 +506,45 @@ class GANInstructor:
         self.log.info("[EVAL] CIDEr-D (%s, beam %d): %.4f", what, beam_size, score)
         self.writer.add_scalar(f"CIDErD_{what}", score, max(self.adv_epoch, 0))
         return score
+
+    def evaluate_metrics(self, what="val", beam_size=3, max_caption_len=None, batch_size=None):
+        """The metrics table of the beam-search captions of ``evaluate`` (the same images, grouping, caption length rule and decode
+        constraints) from ONE decode pass, scored on the GPU: per batch one gic_caption_overlap launch (metrics.OverlapScorer) and one
+        gic_cider_d launch (the scorer of ``evaluate_cider``); the BLEU statistics accumulate on the device in int64 and the sums are
+        read with one sync at the end.  Returns {"bleu1", "bleu2", "bleu3", "bleu4", "rouge_l", "cider_d"}: corpus BLEU-n
+        (metrics.corpus_bleu), mean ROUGE-L and mean CIDEr-D.  Logs them on one line and writes the scalars ``BLEU1M_<what>`` ..
+        ``BLEU4M_<what>``, ``ROUGEL_<what>`` and ``CIDErDM_<what>``."""
+        from .cider import CiderD, RefBatch
+        from .metrics import STAT_COLUMNS, OverlapScorer, corpus_bleu
+        from .tasks import ImageGroups
+        dev = self.args.device
+        if what not in self._cider:                                          # the scorer of evaluate_cider, and its cache
+            ds = self.dev_dataset if what == "val" else self.train_dataset
+            self._cider[what] = CiderD(ImageGroups(ds).references(), self.args.vocab_size, dev)
+        cider = self._cider[what]
+        overlap = OverlapScorer(self.args.vocab_size, dev)
+        stats = torch.zeros(len(STAT_COLUMNS), dtype=torch.int64, device=dev)
+        rouge, cd = [], []
+        for ids, lengths, caps in self._beam_decode(what, beam_size, max_caption_len, batch_size):
+            refs = RefBatch.pack(caps).to(dev)
+            st, rl, _ = overlap.score(ids, lengths, refs)
+            rouge.append(rl)
+            cd.append(cider.score(ids, lengths, refs))
+            stats += st.sum(0, dtype=torch.int64)
+        if rouge:                                                            # the one sync: the sums (exact in float64) and the two means
+            means = torch.stack([torch.cat(rouge).double().mean(), torch.cat(cd).double().mean()])
+            *sums, rouge_l, cider_d = torch.cat([stats.double(), means]).tolist()
+        else:
+            sums, rouge_l, cider_d = [0] * len(STAT_COLUMNS), 0.0, 0.0
+        bleu = corpus_bleu(sums)
+        out = {"bleu1": bleu[0], "bleu2": bleu[1], "bleu3": bleu[2], "bleu4": bleu[3], "rouge_l": rouge_l, "cider_d": cider_d}
+        self.log.info("[EVAL] metrics (%s, beam %d): BLEU-1 %.4f | BLEU-2 %.4f | BLEU-3 %.4f | BLEU-4 %.4f | ROUGE-L %.4f | CIDEr-D %.4f",
+                      what, beam_size, out["bleu1"], out["bleu2"], out["bleu3"], out["bleu4"], out["rouge_l"], out["cider_d"])
+        step = max(self.adv_epoch, 0)
+        for name, key in (("BLEU1M", "bleu1"), ("BLEU2M", "bleu2"), ("BLEU3M", "bleu3"), ("BLEU4M", "bleu4"), ("ROUGEL", "rouge_l"),
+                          ("CIDErDM", "cider_d")):
+            self.writer.add_scalar(f"{name}_{what}", out[key], step)
+        return out
 
     def _eval_groups(self, what):
         """The evaluation's dataset and its captions grouped by image (``filepath`` + ``filename`` for COCO_data, one image per item

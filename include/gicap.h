@@ -765,6 +765,35 @@ int gic_cider_d(const int64_t* cand_ids, int64_t ld_cand, const int32_t* cand_le
                 void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * N-gram overlap metrics of token-id captions (no reference counterpart): the per-candidate terms of corpus
+ * BLEU-1..4 (Papineni et al. 2002, with the semantics of utils.bleu_score), ROUGE-L (Lin 2004, the coco-caption Rouge, beta = 1.2) and an
+ * add-one smoothed sentence BLEU-4 (Lin & Och 2004; NLTK's smoothing method 2) for rewards.  Candidates and references have exactly the
+ * layout, stripping (<PAD> = 0, <S> = 1, <E> = 2 removed from the first `len` ids) and clamping rules of gic_cider_d above; len_c / len_r
+ * below are the stripped lengths, count_x(g) the occurrences of the n-gram g in caption x, r ranges over the image's references.
+ *   stats    int32 [n_cand, GIC_OVERLAP_STATS]:
+ *              [0..3]  clipped_n, n = 1..4 = sum over the candidate's distinct n-grams g of min(count_c(g), max_r count_r(g))
+ *              [4..7]  total_n = max(len_c - n + 1, 0)
+ *              [8]     len_c
+ *              [9]     the closest reference length: the len_r of the minimum over r of (|len_c - len_r|, len_r) (ties: the shorter)
+ *            summed over a corpus they are the integers of corpus BLEU: p_n = sum clipped_n / sum total_n, BP = exp(min(1 - r/c, 0))
+ *            with c = sum [8] and r = sum [9].
+ *   rouge    f32 [n_cand]: with lcs_r the length of the longest common subsequence of the candidate and reference r, P = max_r lcs_r /
+ *            len_c, R = max_r lcs_r / len_r (a reference of length 0 contributes 0); (1 + beta^2) P R / (R + beta^2 P) when both are
+ *            positive, else 0.
+ *   sbleu    f32 [n_cand]: p_1 = clipped_1 / total_1, p_n = (clipped_n + 1) / (total_n + 1) for n = 2..4, BP = exp(min(1 - r/c, 0)) with
+ *            c = len_c and r = the closest reference length; BP * exp(1/4 sum_n log p_n), and 0 when clipped_1 = 0.
+ * An image without references gives all-zero stats and scores.  A candidate whose cand_img is outside [0, B), or whose image has more
+ * than max_refs references or offsets outside [0, n_ref], gets NaN scores and stats -1, and nothing past the offsets is read.
+ * Limits: Lc, Lr <= GIC_CIDER_MAX_LEN, max_refs <= GIC_CIDER_MAX_REFS and V <= GIC_CIDER_MAX_VOCAB -- beyond them GIC_STATUS_UNSUPPORTED;
+ * negative sizes, V < 1, a stride below its row length, B = 0 with candidates and NULL pointers GIC_STATUS_INVALID_ARG; all checked
+ * before any launch.  No idf table, no workspace.  Integer sums and fixed-order loops, no atomics: two calls give the same bits, and
+ * the deterministic mode accepts every call. */
+#define GIC_OVERLAP_STATS 10
+int gic_caption_overlap(const int64_t* cand_ids, int64_t ld_cand, const int32_t* cand_len, const int32_t* cand_img, int32_t n_cand,
+                        int32_t Lc, const int64_t* ref_ids, int64_t ld_ref, const int32_t* ref_len, const int32_t* ref_off, int32_t n_ref,
+                        int32_t Lr, int32_t B, int32_t max_refs, int32_t V, int32_t* stats, float* rouge, float* sbleu, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * optimize(): clip_grad_norm_ + Adam (src/training.py:194-199, :24-26) over a flat f32 parameter arena.
  * step_count: device int64 (incremented here); norm_out: device f32 (pre-clip global L2 norm);
  * partials: device f32 scratch [gic_clip_adam_partials(n)].  Hyper-parameters are doubles: torch.optim.Adam forms
