@@ -35,6 +35,14 @@
 // writes step t + 1's: no launch is added to a step.  The step's consumers -- vocab_step_beam's epilogue, beam_tile_topk, sample_step
 // -- are the instantiations that read the lists; beam_select's selection is unchanged, since the tile partials it merges already
 // hold admissible tokens only.  With every constraint off the entry points run the unconstrained search itself.
+//
+// Entry path: every extern "C" decode is a model (LstmModel / AttnModel: the decoder's dims, weights and, with attention, the feature
+// map; its shape check, its argument check, run()), the two prefixes of its error texts and one call of beam_entry or sample_entry;
+// the four *_ws_bytes are ws_bytes_entry.  Order of checks -- beam: null options, shapes, arguments and weights, options; sampler: null
+// options, shapes, options, arguments and weights; then for both (entry_tail) the constraints, the workspace's alignment, the
+// every-constraint-off shortcut, the constraint workspace.  That the two heads differ in whether the weights or the options come first
+// is history (the sampler was written after the beam search, with its own order), not design; callers may have come to rely on which
+// text a doubly wrong call gets, so both orders are kept and tests/test_decode_entry_errors.py pins them with a recorded table.
 #include <cfloat>
 
 #include "../../include/gicap.h"
@@ -400,6 +408,87 @@ int check_diverse_opts(const gic_diverse_beam_opts* o, int V, const char* who) {
   return GIC_OK;
 }
 
+// ---- the entry path (header comment): a model is the decoder's side of a call, the helpers below are the head's
+struct LstmModel {
+  const gic_decoder_dims* dims; const gic_decoder_params* P; const gic_decoder_shadow* S;
+  int shape(int K, bool beam, const char* who, DecodeDims& d) const { return lstm_dims(dims, K, beam, who, d); }
+  int check(const DecodeDims& d, bool bufs, const char* who) const { return check_lstm_args(P, S, d.NL, bufs, who); }
+  template <typename Head>
+  int run(const DecodeDims& d, const Head& head, void* ws, const float* features, void* stream) const {
+    return lstm_decode(d, P, S, head, ws, features, head.o->h0, head.o->c0, stream);
+  }
+};
+
+struct AttnModel {
+  const gic_attn_dims* dims; const gic_attn_params* P; const gic_attn_shadow* S;
+  const void* fmap;
+  bool history;                  // keep the alpha history (the beam searches that return alphas)
+  int shape(int K, bool beam, const char* who, DecodeDims& d) const { return attn_dims(dims, K, beam, who, d); }
+  int check(const DecodeDims&, bool bufs, const char* who) const { return check_attn_args(P, S, bufs && fmap, who); }
+  template <typename Head>
+  int run(const DecodeDims& d, const Head& head, void* ws, const float* features, void* stream) const {
+    return decode(d, Attn{P, S, fmap, history}, head, ws, features, head.o->h0, head.o->c0, stream);
+  }
+};
+
+// the prefixes of an entry point's error texts: its own and the one its shape checks have carried since they were written
+struct Who { const char* call; const char* dims; };
+
+// the buffers every decode takes
+struct Io {
+  void* ws; const float* features; int64_t* ids; float* scores; int32_t* lengths; void* stream;
+  bool set() const { return ws && features && ids && scores && lengths; }
+};
+
+// a constrained entry point's extra arguments (the other entry points pass none)
+struct ConsArgs { const gic_decode_constraints* c; void* cws; };
+
+template <typename Model>
+int ws_bytes_entry(const Model& m, int K, bool beam, const char* who, uint64_t* out) {
+  DecodeDims d;
+  GIC_PROPAGATE(m.shape(K, beam, who, d));
+  GIC_CHECK_ARG(out, "%s_ws_bytes: null out", who);
+  *out = (uint64_t)decode_layout(d, beam, nullptr).total;
+  return GIC_OK;
+}
+
+// what follows the model's and the options' checks in every entry point
+template <typename Model, typename Head>
+int entry_tail(const Model& m, const DecodeDims& d, Head head, const char* who, const ConsArgs* k, const Io& io) {
+  if (k) GIC_PROPAGATE(check_constraints(k->c, d.L, d.V, Head::kBeam ? d.K : 1, head.eos(), who));
+  GIC_CHECK_ARG(((uintptr_t)io.ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+  if (!k || constraints_off(k->c)) return m.run(d, head, io.ws, io.features, io.stream);
+  GIC_CHECK_ARG(k->cws && ((uintptr_t)k->cws & 255) == 0, "%s: the constraint workspace must be non-null and 256-byte aligned", who);
+  const Constraints cons = constraints_layout(k->c, (size_t)d.rows, d.L, k->cws);
+  head.cons = &cons;
+  return m.run(d, head, io.ws, io.features, io.stream);
+}
+
+// o: the plain search's options (one group, no diversity); dv: the diverse and constrained searches' (then o is unread)
+template <typename Model>
+int beam_entry(const Model& m, Who who, const gic_decoder_beam_opts* o, const gic_diverse_beam_opts* dv, const ConsArgs* k, const Io& io,
+               float* alphas) {
+  GIC_CHECK_ARG(o || dv, "%s: null options", who.call);
+  if (dv) o = &dv->beam;
+  DecodeDims d;
+  GIC_PROPAGATE(m.shape(o->beam, true, who.dims, d));
+  GIC_PROPAGATE(m.check(d, io.set(), who.call));        // the beam searches check the weights before the options (header comment)
+  GIC_PROPAGATE(dv ? check_diverse_opts(dv, d.V, who.call) : check_beam_opts(o, d.V, who.call));
+  const BeamHead head{o, io.ids, io.scores, io.lengths, alphas, dv ? dv->groups : 1, dv ? dv->diversity : 0.f};
+  return entry_tail(m, d, head, who.call, k, io);
+}
+
+template <typename Model>
+int sample_entry(const Model& m, Who who, const gic_sample_opts* o, const ConsArgs* k, const Io& io, const float* noise_u, uint64_t seed) {
+  GIC_CHECK_ARG(o, "%s: null options", who.call);
+  DecodeDims d;
+  GIC_PROPAGATE(m.shape(o->num_samples, false, who.dims, d));
+  GIC_PROPAGATE(check_sample_opts(o, d.V, true, who.call));      // the samplers check the options before the weights (header comment)
+  GIC_PROPAGATE(m.check(d, io.set(), who.call));
+  const SampleHead head{o, noise_u, seed, io.ids, io.scores, io.lengths};
+  return entry_tail(m, d, head, who.call, k, io);
+}
+
 }  // namespace
 }  // namespace gic
 
@@ -408,68 +497,19 @@ using namespace gic;
 extern "C" {
 
 int gic_decoder_beam_ws_bytes(const gic_decoder_dims* dims, int32_t beam, uint64_t* out) {
-  DecodeDims d;
-  GIC_PROPAGATE(lstm_dims(dims, beam, true, "decoder_beam", d));
-  GIC_CHECK_ARG(out, "decoder_beam_ws_bytes: null out");
-  *out = (uint64_t)decode_layout(d, true, nullptr).total;
-  return GIC_OK;
-}
-
-int gic_decoder_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_beam_opts* o,
-                            void* ws, const float* features, int64_t* ids, float* scores, int32_t* lengths, void* stream) {
-  GIC_CHECK_ARG(o, "decoder_beam_search: null options");
-  DecodeDims d;
-  GIC_PROPAGATE(lstm_dims(dims, o->beam, true, "decoder_beam", d));
-  GIC_PROPAGATE(check_lstm_args(P, S, d.NL, ws && features && ids && scores && lengths, "decoder_beam_search"));
-  GIC_PROPAGATE(check_beam_opts(o, d.V, "decoder_beam_search"));
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "decoder_beam_search: the workspace must be 256-byte aligned");
-  return lstm_decode(d, P, S, BeamHead{o, ids, scores, lengths, nullptr}, ws, features, o->h0, o->c0, stream);
+  return ws_bytes_entry(LstmModel{dims}, beam, true, "decoder_beam", out);
 }
 
 int gic_attn_beam_ws_bytes(const gic_attn_dims* dims, int32_t beam, uint64_t* out) {
-  DecodeDims d;
-  GIC_PROPAGATE(attn_dims(dims, beam, true, "attn_beam", d));
-  GIC_CHECK_ARG(out, "attn_beam_ws_bytes: null out");
-  *out = (uint64_t)decode_layout(d, true, nullptr).total;
-  return GIC_OK;
+  return ws_bytes_entry(AttnModel{dims}, beam, true, "attn_beam", out);
 }
 
-int gic_attn_beam_search(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_decoder_beam_opts* o, void* ws,
-                         const float* features, const void* fmap, int64_t* ids, float* scores, int32_t* lengths, float* alphas, void* stream) {
-  GIC_CHECK_ARG(o, "attn_beam_search: null options");
-  DecodeDims d;
-  GIC_PROPAGATE(attn_dims(dims, o->beam, true, "attn_beam", d));
-  GIC_PROPAGATE(check_attn_args(P, S, ws && features && fmap && ids && scores && lengths, "attn_beam_search"));
-  GIC_PROPAGATE(check_beam_opts(o, d.V, "attn_beam_search"));
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "attn_beam_search: the workspace must be 256-byte aligned");
-  return decode(d, Attn{P, S, fmap, alphas != nullptr}, BeamHead{o, ids, scores, lengths, alphas}, ws, features, o->h0, o->c0, stream);
+int gic_decoder_sample_ws_bytes(const gic_decoder_dims* dims, int32_t num_samples, uint64_t* out) {
+  return ws_bytes_entry(LstmModel{dims}, num_samples, false, "decoder_sample", out);
 }
 
-// the diverse searches share the beam searches' workspace: gic_*_beam_ws_bytes for the same beam size
-int gic_decoder_diverse_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
-                                    const gic_diverse_beam_opts* o, void* ws, const float* features, int64_t* ids, float* scores,
-                                    int32_t* lengths, void* stream) {
-  GIC_CHECK_ARG(o, "decoder_diverse_beam_search: null options");
-  DecodeDims d;
-  GIC_PROPAGATE(lstm_dims(dims, o->beam.beam, true, "decoder_diverse_beam", d));
-  GIC_PROPAGATE(check_lstm_args(P, S, d.NL, ws && features && ids && scores && lengths, "decoder_diverse_beam_search"));
-  GIC_PROPAGATE(check_diverse_opts(o, d.V, "decoder_diverse_beam_search"));
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "decoder_diverse_beam_search: the workspace must be 256-byte aligned");
-  return lstm_decode(d, P, S, BeamHead{&o->beam, ids, scores, lengths, nullptr, o->groups, o->diversity}, ws, features, o->beam.h0,
-                     o->beam.c0, stream);
-}
-
-int gic_attn_diverse_beam_search(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_diverse_beam_opts* o,
-                                 void* ws, const float* features, const void* fmap, int64_t* ids, float* scores, int32_t* lengths,
-                                 float* alphas, void* stream) {
-  GIC_CHECK_ARG(o, "attn_diverse_beam_search: null options");
-  DecodeDims d;
-  GIC_PROPAGATE(attn_dims(dims, o->beam.beam, true, "attn_diverse_beam", d));
-  GIC_PROPAGATE(check_attn_args(P, S, ws && features && fmap && ids && scores && lengths, "attn_diverse_beam_search"));
-  GIC_PROPAGATE(check_diverse_opts(o, d.V, "attn_diverse_beam_search"));
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "attn_diverse_beam_search: the workspace must be 256-byte aligned");
-  return decode(d, Attn{P, S, fmap, alphas != nullptr}, BeamHead{&o->beam, ids, scores, lengths, alphas, o->groups, o->diversity}, ws,
-                features, o->beam.h0, o->beam.c0, stream);
+int gic_attn_sample_ws_bytes(const gic_attn_dims* dims, int32_t num_samples, uint64_t* out) {
+  return ws_bytes_entry(AttnModel{dims}, num_samples, false, "attn_sample", out);
 }
 
 int gic_decode_constraints_ws_bytes(int64_t rows, int32_t L, const gic_decode_constraints* c, uint64_t* out) {
@@ -481,124 +521,79 @@ int gic_decode_constraints_ws_bytes(int64_t rows, int32_t L, const gic_decode_co
   return GIC_OK;
 }
 
+int gic_decoder_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_beam_opts* o,
+                            void* ws, const float* features, int64_t* ids, float* scores, int32_t* lengths, void* stream) {
+  return beam_entry(LstmModel{dims, P, S}, {"decoder_beam_search", "decoder_beam"}, o, nullptr, nullptr,
+                    {ws, features, ids, scores, lengths, stream}, nullptr);
+}
+
+int gic_attn_beam_search(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_decoder_beam_opts* o, void* ws,
+                         const float* features, const void* fmap, int64_t* ids, float* scores, int32_t* lengths, float* alphas, void* stream) {
+  return beam_entry(AttnModel{dims, P, S, fmap, alphas != nullptr}, {"attn_beam_search", "attn_beam"}, o, nullptr, nullptr,
+                    {ws, features, ids, scores, lengths, stream}, alphas);
+}
+
+// the diverse searches share the beam searches' workspace: gic_*_beam_ws_bytes for the same beam size
+int gic_decoder_diverse_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
+                                    const gic_diverse_beam_opts* o, void* ws, const float* features, int64_t* ids, float* scores,
+                                    int32_t* lengths, void* stream) {
+  return beam_entry(LstmModel{dims, P, S}, {"decoder_diverse_beam_search", "decoder_diverse_beam"}, nullptr, o, nullptr,
+                    {ws, features, ids, scores, lengths, stream}, nullptr);
+}
+
+int gic_attn_diverse_beam_search(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_diverse_beam_opts* o,
+                                 void* ws, const float* features, const void* fmap, int64_t* ids, float* scores, int32_t* lengths,
+                                 float* alphas, void* stream) {
+  return beam_entry(AttnModel{dims, P, S, fmap, alphas != nullptr}, {"attn_diverse_beam_search", "attn_diverse_beam"}, nullptr, o, nullptr,
+                    {ws, features, ids, scores, lengths, stream}, alphas);
+}
+
 int gic_decoder_constrained_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
                                         const gic_diverse_beam_opts* o, const gic_decode_constraints* c, void* ws, void* cws,
                                         const float* features, int64_t* ids, float* scores, int32_t* lengths, void* stream) {
-  const char* who = "decoder_constrained_beam_search";
-  GIC_CHECK_ARG(o, "%s: null options", who);
-  DecodeDims d;
-  GIC_PROPAGATE(lstm_dims(dims, o->beam.beam, true, "decoder_constrained_beam", d));
-  GIC_PROPAGATE(check_lstm_args(P, S, d.NL, ws && features && ids && scores && lengths, who));
-  GIC_PROPAGATE(check_diverse_opts(o, d.V, who));
-  GIC_PROPAGATE(check_constraints(c, d.L, d.V, d.K, o->beam.eos_id, who));
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
-  BeamHead head{&o->beam, ids, scores, lengths, nullptr, o->groups, o->diversity};
-  if (constraints_off(c)) return lstm_decode(d, P, S, head, ws, features, o->beam.h0, o->beam.c0, stream);
-  GIC_CHECK_ARG(cws && ((uintptr_t)cws & 255) == 0, "%s: the constraint workspace must be non-null and 256-byte aligned", who);
-  const Constraints k = constraints_layout(c, (size_t)d.rows, d.L, cws);
-  head.cons = &k;
-  return lstm_decode(d, P, S, head, ws, features, o->beam.h0, o->beam.c0, stream);
+  const ConsArgs k{c, cws};
+  return beam_entry(LstmModel{dims, P, S}, {"decoder_constrained_beam_search", "decoder_constrained_beam"}, nullptr, o, &k,
+                    {ws, features, ids, scores, lengths, stream}, nullptr);
 }
 
 int gic_attn_constrained_beam_search(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S,
                                      const gic_diverse_beam_opts* o, const gic_decode_constraints* c, void* ws, void* cws,
                                      const float* features, const void* fmap, int64_t* ids, float* scores, int32_t* lengths, float* alphas,
                                      void* stream) {
-  const char* who = "attn_constrained_beam_search";
-  GIC_CHECK_ARG(o, "%s: null options", who);
-  DecodeDims d;
-  GIC_PROPAGATE(attn_dims(dims, o->beam.beam, true, "attn_constrained_beam", d));
-  GIC_PROPAGATE(check_attn_args(P, S, ws && features && fmap && ids && scores && lengths, who));
-  GIC_PROPAGATE(check_diverse_opts(o, d.V, who));
-  GIC_PROPAGATE(check_constraints(c, d.L, d.V, d.K, o->beam.eos_id, who));
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
-  BeamHead head{&o->beam, ids, scores, lengths, alphas, o->groups, o->diversity};
-  const Attn rec{P, S, fmap, alphas != nullptr};
-  if (constraints_off(c)) return decode(d, rec, head, ws, features, o->beam.h0, o->beam.c0, stream);
-  GIC_CHECK_ARG(cws && ((uintptr_t)cws & 255) == 0, "%s: the constraint workspace must be non-null and 256-byte aligned", who);
-  const Constraints k = constraints_layout(c, (size_t)d.rows, d.L, cws);
-  head.cons = &k;
-  return decode(d, rec, head, ws, features, o->beam.h0, o->beam.c0, stream);
+  const ConsArgs k{c, cws};
+  return beam_entry(AttnModel{dims, P, S, fmap, alphas != nullptr}, {"attn_constrained_beam_search", "attn_constrained_beam"}, nullptr, o, &k,
+                    {ws, features, ids, scores, lengths, stream}, alphas);
+}
+
+int gic_decoder_sample_captions(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_sample_opts* o,
+                                void* ws, const float* features, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
+                                int32_t* lengths, void* stream) {
+  return sample_entry(LstmModel{dims, P, S}, {"decoder_sample_captions", "decoder_sample"}, o, nullptr,
+                      {ws, features, ids, scores, lengths, stream}, noise_u, seed);
+}
+
+int gic_attn_sample_captions(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_sample_opts* o, void* ws,
+                             const float* features, const void* fmap, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
+                             int32_t* lengths, void* stream) {
+  return sample_entry(AttnModel{dims, P, S, fmap, false}, {"attn_sample_captions", "attn_sample"}, o, nullptr,
+                      {ws, features, ids, scores, lengths, stream}, noise_u, seed);
 }
 
 int gic_decoder_constrained_sample_captions(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
                                             const gic_sample_opts* o, const gic_decode_constraints* c, void* ws, void* cws,
                                             const float* features, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
                                             int32_t* lengths, void* stream) {
-  const char* who = "decoder_constrained_sample_captions";
-  GIC_CHECK_ARG(o, "%s: null options", who);
-  DecodeDims d;
-  GIC_PROPAGATE(lstm_dims(dims, o->num_samples, false, "decoder_constrained_sample", d));
-  GIC_PROPAGATE(check_sample_opts(o, d.V, true, who));
-  GIC_PROPAGATE(check_lstm_args(P, S, d.NL, ws && features && ids && scores && lengths, who));
-  GIC_PROPAGATE(check_constraints(c, d.L, d.V, 1, o->eos_id, who));
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
-  SampleHead head{o, noise_u, seed, ids, scores, lengths};
-  if (constraints_off(c)) return lstm_decode(d, P, S, head, ws, features, o->h0, o->c0, stream);
-  GIC_CHECK_ARG(cws && ((uintptr_t)cws & 255) == 0, "%s: the constraint workspace must be non-null and 256-byte aligned", who);
-  const Constraints k = constraints_layout(c, (size_t)d.rows, d.L, cws);
-  head.cons = &k;
-  return lstm_decode(d, P, S, head, ws, features, o->h0, o->c0, stream);
+  const ConsArgs k{c, cws};
+  return sample_entry(LstmModel{dims, P, S}, {"decoder_constrained_sample_captions", "decoder_constrained_sample"}, o, &k,
+                      {ws, features, ids, scores, lengths, stream}, noise_u, seed);
 }
 
 int gic_attn_constrained_sample_captions(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_sample_opts* o,
                                          const gic_decode_constraints* c, void* ws, void* cws, const float* features, const void* fmap,
                                          const float* noise_u, uint64_t seed, int64_t* ids, float* scores, int32_t* lengths, void* stream) {
-  const char* who = "attn_constrained_sample_captions";
-  GIC_CHECK_ARG(o, "%s: null options", who);
-  DecodeDims d;
-  GIC_PROPAGATE(attn_dims(dims, o->num_samples, false, "attn_constrained_sample", d));
-  GIC_PROPAGATE(check_sample_opts(o, d.V, true, who));
-  GIC_PROPAGATE(check_attn_args(P, S, ws && features && fmap && ids && scores && lengths, who));
-  GIC_PROPAGATE(check_constraints(c, d.L, d.V, 1, o->eos_id, who));
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
-  SampleHead head{o, noise_u, seed, ids, scores, lengths};
-  const Attn rec{P, S, fmap, false};
-  if (constraints_off(c)) return decode(d, rec, head, ws, features, o->h0, o->c0, stream);
-  GIC_CHECK_ARG(cws && ((uintptr_t)cws & 255) == 0, "%s: the constraint workspace must be non-null and 256-byte aligned", who);
-  const Constraints k = constraints_layout(c, (size_t)d.rows, d.L, cws);
-  head.cons = &k;
-  return decode(d, rec, head, ws, features, o->h0, o->c0, stream);
-}
-
-int gic_decoder_sample_ws_bytes(const gic_decoder_dims* dims, int32_t num_samples, uint64_t* out) {
-  DecodeDims d;
-  GIC_PROPAGATE(lstm_dims(dims, num_samples, false, "decoder_sample", d));
-  GIC_CHECK_ARG(out, "decoder_sample_ws_bytes: null out");
-  *out = (uint64_t)decode_layout(d, false, nullptr).total;
-  return GIC_OK;
-}
-
-int gic_decoder_sample_captions(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_sample_opts* o,
-                                void* ws, const float* features, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
-                                int32_t* lengths, void* stream) {
-  GIC_CHECK_ARG(o, "decoder_sample_captions: null options");
-  DecodeDims d;
-  GIC_PROPAGATE(lstm_dims(dims, o->num_samples, false, "decoder_sample", d));
-  GIC_PROPAGATE(check_sample_opts(o, d.V, true, "decoder_sample_captions"));
-  GIC_PROPAGATE(check_lstm_args(P, S, d.NL, ws && features && ids && scores && lengths, "decoder_sample_captions"));
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "decoder_sample_captions: the workspace must be 256-byte aligned");
-  return lstm_decode(d, P, S, SampleHead{o, noise_u, seed, ids, scores, lengths}, ws, features, o->h0, o->c0, stream);
-}
-
-int gic_attn_sample_ws_bytes(const gic_attn_dims* dims, int32_t num_samples, uint64_t* out) {
-  DecodeDims d;
-  GIC_PROPAGATE(attn_dims(dims, num_samples, false, "attn_sample", d));
-  GIC_CHECK_ARG(out, "attn_sample_ws_bytes: null out");
-  *out = (uint64_t)decode_layout(d, false, nullptr).total;
-  return GIC_OK;
-}
-
-int gic_attn_sample_captions(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_sample_opts* o, void* ws,
-                             const float* features, const void* fmap, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
-                             int32_t* lengths, void* stream) {
-  GIC_CHECK_ARG(o, "attn_sample_captions: null options");
-  DecodeDims d;
-  GIC_PROPAGATE(attn_dims(dims, o->num_samples, false, "attn_sample", d));
-  GIC_PROPAGATE(check_sample_opts(o, d.V, true, "attn_sample_captions"));
-  GIC_PROPAGATE(check_attn_args(P, S, ws && features && fmap && ids && scores && lengths, "attn_sample_captions"));
-  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "attn_sample_captions: the workspace must be 256-byte aligned");
-  return decode(d, Attn{P, S, fmap, false}, SampleHead{o, noise_u, seed, ids, scores, lengths}, ws, features, o->h0, o->c0, stream);
+  const ConsArgs k{c, cws};
+  return sample_entry(AttnModel{dims, P, S, fmap, false}, {"attn_constrained_sample_captions", "attn_constrained_sample"}, o, &k,
+                      {ws, features, ids, scores, lengths, stream}, noise_u, seed);
 }
 
 }  // extern "C"

@@ -302,6 +302,80 @@ def _sample_noise(noise_u: Optional[torch.Tensor], Lc: int, rows: int, V: int) -
     return noise_u.contiguous()
 
 
+class _CaptionDecodes:
+    """Beam search, diverse beam search and caption sampling of both decoder engines (csrc/decode.hip).  The engine gives the symbol
+    prefix and its ``_states``; the attention engine also overrides the two methods through which the feature map and the alphas
+    enter a call."""
+
+    _PREFIX = ""                 # gic_decoder / gic_attn
+
+    def _decode_maps(self, fmap, B: int):
+        """The inputs a call takes after ``features``."""
+        return ()
+
+    def _beam_alphas(self, want: bool, B: int, beam, Lc: int, dev):
+        """The outputs a beam search takes after ``lengths`` (a tensor or None each)."""
+        return ()
+
+    def _ws_bytes(self, head: str, B: int, Lc: int, n: int) -> int:
+        name = f"{self._PREFIX}_{head}_ws_bytes"
+        out = C.c_uint64(0)
+        L.check(getattr(L.load(), name)(C.byref(self.dims(B, Lc)), int(n), C.byref(out)), name)
+        return int(out.value)
+
+    def _decode_call(self, what: str, params, B: int, Lc: int, opts, cons, rows: int, ws, ins, outs, draw=()):
+        """<prefix>_<what> of the library, looked up by name at call time.  ``cons`` (set with the constrained forms alone) and its
+        workspace follow the options; ``ins``: features and the maps, ``draw``: the sampler's (noise_u pointer, seed), ``outs``: ids to
+        lengths / alphas."""
+        name = f"{self._PREFIX}_{what}"
+        args = [C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts)]
+        if cons is not None:
+            cws = _constraints_ws(cons, rows, Lc, ws.device)
+            args += [C.byref(cons), ptr(ws), ptr(cws)]
+        else:
+            args += [ptr(ws)]
+        L.check(getattr(L.load(), name)(*args, *map(ptr, ins), *draw, *map(ptr, outs), stream_ptr()), name)
+
+    def _beam(self, params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, diverse, cons):
+        self.check_params(params)
+        require_gpu(features, fmap)
+        features = _decode_features(features, self.E)
+        B, dev = features.shape[0], features.device
+        maps = self._decode_maps(fmap, B)
+        self.prepare(params)
+        ws = _aligned_ws(ws, self.beam_ws_bytes(B, Lc, beam), dev)
+        opts = L.DecoderBeamOpts()
+        opts.beam, opts.eos_id, opts.pad_id, opts.length_penalty = int(beam), int(eos_id), int(pad_id), float(length_penalty)
+        keep = self._states(opts, states, B)                         # (h0, c0): referenced until the call has returned
+        outs = _decode_outputs(B, beam, Lc, dev) + self._beam_alphas(want_alphas, B, beam, Lc, dev)
+        if cons is not None:
+            what, o = "constrained_beam_search", _diverse_opts(opts, *(diverse or (1, 0.0)))
+        elif diverse is not None:
+            what, o = "diverse_beam_search", _diverse_opts(opts, *diverse)
+        else:
+            what, o = "beam_search", opts
+        self._decode_call(what, params, B, Lc, o, cons, B * int(beam), ws, (features, *maps), outs)
+        return outs if want_alphas else outs[:3]
+
+    def _sample(self, params, features, fmap, Lc, num_samples, top_k, top_p, temperature, eos_id, pad_id, seed, noise_u, states, ws, cons):
+        self.check_params(params)
+        require_gpu(features, fmap)
+        features = _decode_features(features, self.E)
+        B, dev = features.shape[0], features.device
+        n = int(num_samples)
+        noise_u = _sample_noise(noise_u, Lc, B * n, self.V)
+        opts = sample_opts(n, top_k, top_p, temperature, eos_id, pad_id)
+        nbytes = self.sample_ws_bytes(B, Lc, n)          # (checks the dims and n before anything runs)
+        maps = self._decode_maps(fmap, B)
+        self.prepare(params)
+        ws = _aligned_ws(ws, nbytes, dev)
+        keep = self._states(opts, states, B)                         # (h0, c0): referenced until the call has returned
+        outs = _decode_outputs(B, n, Lc, dev)
+        what = "sample_captions" if cons is None else "constrained_sample_captions"
+        self._decode_call(what, params, B, Lc, opts, cons, B * n, ws, (features, *maps), outs, (ptr(noise_u), int(seed) & (2 ** 64 - 1)))
+        return outs
+
+
 def gan_losses(loss_type: str, d_real, d_fake, g_out, want_grads: bool = True):
     """Returns (losses[2] device tensor: [g_loss, d_loss], grads dict or None)."""
     if loss_type not in L.LOSS_TYPES:
@@ -412,7 +486,7 @@ def caption_overlap(cand_ids: torch.Tensor, cand_len: torch.Tensor, cand_img: to
 
 
 # ------------------------------------------------------------------------------------------ decoder
-class DecoderEngine:
+class DecoderEngine(_CaptionDecodes):
     """Decoder.sample forward/backward (reference src/generator.py:55-96) on the HIP library."""
 
     def __init__(self, vocab: int, embed: int, hidden: int, layers: int, dtype: int):
@@ -714,11 +788,11 @@ class DecoderEngine:
         shape = (self.NL, B, self.H)
         return _decode_states(opts, states, shape, f"states must be (h0, c0), each [num_layers={self.NL}, B={B}, H={self.H}]")
 
+    _PREFIX = "gic_decoder"
+
     def beam_ws_bytes(self, B: int, Lc: int, beam: int) -> int:
         """Bytes of gic_decoder_beam_search's workspace (host-only query; the library's own path choice sizes it)."""
-        out = C.c_uint64(0)
-        L.check(L.load().gic_decoder_beam_ws_bytes(C.byref(self.dims(B, Lc)), int(beam), C.byref(out)), "gic_decoder_beam_ws_bytes")
-        return int(out.value)
+        return self._ws_bytes("beam", B, Lc, beam)
 
     def beam_fused(self, B: int, beam: int) -> bool:
         """True if the search runs on the fused step kernels (B * beam rows within fused_rollout_rows())."""
@@ -731,7 +805,7 @@ class DecoderEngine:
         ``states`` = (h0, c0), each f32 [NL, B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned).
         ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: decode constraints (gic_decode_constraints); any of them set runs
         gic_decoder_constrained_beam_search."""
-        return self._beam(params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, None,
+        return self._beam(params, features, None, Lc, beam, eos_id, pad_id, length_penalty, states, ws, False, None,
                           decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
 
     def diverse_beam_search(self, params, features: torch.Tensor, Lc: int, beam: int, groups: int, diversity: float, eos_id: int = 2,
@@ -740,42 +814,12 @@ class DecoderEngine:
         """gic_decoder_diverse_beam_search: ``beam`` beams in ``groups`` groups (which must divide ``beam``) with the Hamming penalty
         ``diversity``; (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam]) in group-major order, each group's
         beams best first.  ``states`` and ``ws`` (beam_ws_bytes() for the same beam) and the decode constraints as for beam_search."""
-        return self._beam(params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, (groups, diversity),
+        return self._beam(params, features, None, Lc, beam, eos_id, pad_id, length_penalty, states, ws, False, (groups, diversity),
                           decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
-
-    def _beam(self, params, features, Lc, beam, eos_id, pad_id, length_penalty, states, ws, diverse, cons=None):
-        self.check_params(params)
-        require_gpu(features)
-        features = _decode_features(features, self.E)
-        B, dev = features.shape[0], features.device
-        self.prepare(params)
-        ws = _aligned_ws(ws, self.beam_ws_bytes(B, Lc, beam), dev)
-        opts = L.DecoderBeamOpts()
-        opts.beam, opts.eos_id, opts.pad_id, opts.length_penalty = int(beam), int(eos_id), int(pad_id), float(length_penalty)
-        keep = self._states(opts, states, B)
-        ids, scores, lengths = _decode_outputs(B, beam, Lc, dev)
-        d = self.dims(B, Lc)
-        if cons is not None:
-            o = _diverse_opts(opts, *(diverse or (1, 0.0)))
-            cws = _constraints_ws(cons, B * int(beam), Lc, dev)
-            L.check(L.load().gic_decoder_constrained_beam_search(
-                C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(o), C.byref(cons), ptr(ws),
-                ptr(cws), ptr(features), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()), "gic_decoder_constrained_beam_search")
-            return ids, scores, lengths
-        if diverse is None:
-            fn, name, o = L.load().gic_decoder_beam_search, "gic_decoder_beam_search", opts
-        else:
-            fn, name, o = L.load().gic_decoder_diverse_beam_search, "gic_decoder_diverse_beam_search", _diverse_opts(opts, *diverse)
-        L.check(fn(C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(o), ptr(ws), ptr(features),
-                   ptr(ids), ptr(scores), ptr(lengths), stream_ptr()), name)
-        return ids, scores, lengths
 
     def sample_ws_bytes(self, B: int, Lc: int, num_samples: int) -> int:
         """Bytes of gic_decoder_sample_captions' workspace (host-only query; the library's own path choice sizes it)."""
-        out = C.c_uint64(0)
-        L.check(L.load().gic_decoder_sample_ws_bytes(C.byref(self.dims(B, Lc)), int(num_samples), C.byref(out)),
-                "gic_decoder_sample_ws_bytes")
-        return int(out.value)
+        return self._ws_bytes("sample", B, Lc, num_samples)
 
     def sample_captions(self, params, features: torch.Tensor, Lc: int, num_samples: int, top_k: int = 0, top_p: float = 1.0,
                         temperature: float = 1.0, eos_id: int = 2, pad_id: int = 0, seed: int = 0,
@@ -785,31 +829,8 @@ class DecoderEngine:
         [Lc, B*n, V] or None = Philox(seed).  ``states`` = (h0, c0), each f32 [NL, B, H].  ``ws``: a uint8 workspace of at least
         sample_ws_bytes() bytes (256-aligned).  ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: decode constraints
         (gic_decode_constraints); any of them set runs gic_decoder_constrained_sample_captions."""
-        cons = decode_constraints(no_repeat_ngram, min_length, suppress_tokens)
-        self.check_params(params)
-        require_gpu(features)
-        features = _decode_features(features, self.E)
-        B, dev = features.shape[0], features.device
-        n = int(num_samples)
-        noise_u = _sample_noise(noise_u, Lc, B * n, self.V)
-        opts = sample_opts(n, top_k, top_p, temperature, eos_id, pad_id)
-        nbytes = self.sample_ws_bytes(B, Lc, n)          # (checks the dims and n before anything runs)
-        self.prepare(params)
-        ws = _aligned_ws(ws, nbytes, dev)
-        keep = self._states(opts, states, B)
-        ids, scores, lengths = _decode_outputs(B, n, Lc, dev)
-        if cons is not None:
-            cws = _constraints_ws(cons, B * n, Lc, dev)
-            L.check(L.load().gic_decoder_constrained_sample_captions(
-                C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts),
-                C.byref(cons), ptr(ws), ptr(cws), ptr(features), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores),
-                ptr(lengths), stream_ptr()), "gic_decoder_constrained_sample_captions")
-            return ids, scores, lengths
-        L.check(L.load().gic_decoder_sample_captions(
-            C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
-            ptr(features), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()),
-            "gic_decoder_sample_captions")
-        return ids, scores, lengths
+        return self._sample(params, features, None, Lc, num_samples, top_k, top_p, temperature, eos_id, pad_id, seed, noise_u, states, ws,
+                            decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
 
 
 # ------------------------------------------------------------------------------------------ discriminator
@@ -1063,7 +1084,7 @@ def clip_adam(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, clip_no
 
 
 # ------------------------------------------------------------------------------------------ visual-attention decoder
-class AttnDecoderEngine:
+class AttnDecoderEngine(_CaptionDecodes):
     """gic_attn_sample_fwd / bwd (gicap.h): the reference's roll-out loop with soft attention over the trunk's feature map
     (BASELINE config 4; no reference counterpart, oracle/cpu_attention.py).
     params order: [embed, w_ih, w_hh, b_ih, b_hh, w_out, b_out, w_f, b_f, w_h, w_a]."""
@@ -1191,11 +1212,17 @@ class AttnDecoderEngine:
         states = None if states is None else [t.reshape(-1, self.H) for t in states]
         return _decode_states(opts, states, (B, self.H), f"states must be (h0, c0), each [1, B={B}, H={self.H}]")
 
+    _PREFIX = "gic_attn"
+
+    def _decode_maps(self, fmap, B: int):
+        return (self._act_fmap(fmap, B),)
+
+    def _beam_alphas(self, want: bool, B: int, beam, Lc: int, dev):
+        return (torch.empty(B, beam, Lc, self.P, device=dev, dtype=torch.float32) if want else None,)
+
     def beam_ws_bytes(self, B: int, Lc: int, beam: int) -> int:
         """Bytes of gic_attn_beam_search's workspace (host-only query)."""
-        out = C.c_uint64(0)
-        L.check(L.load().gic_attn_beam_ws_bytes(C.byref(self.dims(B, Lc)), int(beam), C.byref(out)), "gic_attn_beam_ws_bytes")
-        return int(out.value)
+        return self._ws_bytes("beam", B, Lc, beam)
 
     def beam_search(self, params, features, fmap, Lc: int, beam: int, eos_id: int = 2, pad_id: int = 0, length_penalty: float = 0.0,
                     states=None, ws: Optional[torch.Tensor] = None, want_alphas: bool = False, no_repeat_ngram: int = 0,
@@ -1216,42 +1243,9 @@ class AttnDecoderEngine:
         return self._beam(params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas,
                           (groups, diversity), decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
 
-    def _beam(self, params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, diverse, cons=None):
-        self.check_params(params)
-        require_gpu(features, fmap)
-        features = _decode_features(features, self.E)
-        B, dev = features.shape[0], features.device
-        fmap = self._act_fmap(fmap, B)
-        self.prepare(params)
-        ws = _aligned_ws(ws, self.beam_ws_bytes(B, Lc, beam), dev)
-        opts = L.DecoderBeamOpts()
-        opts.beam, opts.eos_id, opts.pad_id, opts.length_penalty = int(beam), int(eos_id), int(pad_id), float(length_penalty)
-        keep = self._states(opts, states, B)
-        ids, scores, lengths = _decode_outputs(B, beam, Lc, dev)
-        alphas = torch.empty(B, beam, Lc, self.P, device=dev, dtype=torch.float32) if want_alphas else None
-        if cons is not None:
-            o = _diverse_opts(opts, *(diverse or (1, 0.0)))
-            cws = _constraints_ws(cons, B * int(beam), Lc, dev)
-            L.check(L.load().gic_attn_constrained_beam_search(
-                C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(o), C.byref(cons),
-                ptr(ws), ptr(cws), ptr(features), ptr(fmap), ptr(ids), ptr(scores), ptr(lengths), ptr(alphas), stream_ptr()),
-                "gic_attn_constrained_beam_search")
-            return (ids, scores, lengths, alphas) if want_alphas else (ids, scores, lengths)
-        if diverse is None:
-            fn, name, o = L.load().gic_attn_beam_search, "gic_attn_beam_search", opts
-        else:
-            fn, name, o = L.load().gic_attn_diverse_beam_search, "gic_attn_diverse_beam_search", _diverse_opts(opts, *diverse)
-        L.check(fn(C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(o), ptr(ws),
-                   ptr(features), ptr(fmap), ptr(ids), ptr(scores), ptr(lengths), ptr(alphas), stream_ptr()), name)
-        if want_alphas:
-            return ids, scores, lengths, alphas
-        return ids, scores, lengths
-
     def sample_ws_bytes(self, B: int, Lc: int, num_samples: int) -> int:
         """Bytes of gic_attn_sample_captions' workspace (host-only query)."""
-        out = C.c_uint64(0)
-        L.check(L.load().gic_attn_sample_ws_bytes(C.byref(self.dims(B, Lc)), int(num_samples), C.byref(out)), "gic_attn_sample_ws_bytes")
-        return int(out.value)
+        return self._ws_bytes("sample", B, Lc, num_samples)
 
     def sample_captions(self, params, features, fmap, Lc: int, num_samples: int, top_k: int = 0, top_p: float = 1.0,
                         temperature: float = 1.0, eos_id: int = 2, pad_id: int = 0, seed: int = 0,
@@ -1261,32 +1255,8 @@ class AttnDecoderEngine:
         is cast to the compute dtype as in sample_fwd.  ``noise_u`` f32 [Lc, B*n, V] or None = Philox(seed).  ``states`` = (h0, c0),
         each [1, B, H] or [B, H].  ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: decode constraints
         (gic_decode_constraints); any of them set runs gic_attn_constrained_sample_captions."""
-        cons = decode_constraints(no_repeat_ngram, min_length, suppress_tokens)
-        self.check_params(params)
-        require_gpu(features, fmap)
-        features = _decode_features(features, self.E)
-        B, dev = features.shape[0], features.device
-        n = int(num_samples)
-        noise_u = _sample_noise(noise_u, Lc, B * n, self.V)
-        opts = sample_opts(n, top_k, top_p, temperature, eos_id, pad_id)
-        nbytes = self.sample_ws_bytes(B, Lc, n)
-        fmap = self._act_fmap(fmap, B)
-        self.prepare(params)
-        ws = _aligned_ws(ws, nbytes, dev)
-        keep = self._states(opts, states, B)
-        ids, scores, lengths = _decode_outputs(B, n, Lc, dev)
-        if cons is not None:
-            cws = _constraints_ws(cons, B * n, Lc, dev)
-            L.check(L.load().gic_attn_constrained_sample_captions(
-                C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts),
-                C.byref(cons), ptr(ws), ptr(cws), ptr(features), ptr(fmap), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids),
-                ptr(scores), ptr(lengths), stream_ptr()), "gic_attn_constrained_sample_captions")
-            return ids, scores, lengths
-        L.check(L.load().gic_attn_sample_captions(
-            C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(opts), ptr(ws),
-            ptr(features), ptr(fmap), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ids), ptr(scores), ptr(lengths), stream_ptr()),
-            "gic_attn_sample_captions")
-        return ids, scores, lengths
+        return self._sample(params, features, fmap, Lc, num_samples, top_k, top_p, temperature, eos_id, pad_id, seed, noise_u, states, ws,
+                            decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
 
     def tf_ws_bytes(self, B: int, T: int, Tmax: int) -> int:
         """Bytes of gic_attn_forward_tf's logits_ws (host-only query)."""

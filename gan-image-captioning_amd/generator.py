@@ -150,6 +150,30 @@ class _ForwardTfFn(torch.autograd.Function):
         return (None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
 
 
+def _beam_search(dec, features, maps, beam_size, max_caption_len, eos_id, length_penalty, states, return_beams, beam_groups, diversity, **kw):
+    """Decoder.beam_search / AttnDecoder.beam_search: ``maps`` = () or (fmap,), ``kw`` = the engine's further keywords (the decode
+    constraints, want_alphas).  One group without diversity is the plain search."""
+    L = int(dec.max_seq_length if max_caption_len is None else max_caption_len)
+    with torch.no_grad():
+        args = ([p.detach() for p in dec.param_list()], features.detach().float(), *(m.detach() for m in maps), L, int(beam_size))
+        if int(beam_groups) == 1 and float(diversity) == 0.0:
+            out = dec.engine().beam_search(*args, int(eos_id), 0, float(length_penalty), states=states, **kw)
+        else:
+            out = dec.engine().diverse_beam_search(*args, int(beam_groups), float(diversity), int(eos_id), 0, float(length_penalty),
+                                                   states=states, **kw)
+    return out if return_beams else tuple(t[:, 0] for t in out)
+
+
+def _sample_captions(dec, features, maps, num_samples, top_k, top_p, temperature, max_caption_len, eos_id, seed, noise_u, states, **cons):
+    """Decoder.sample_captions / AttnDecoder.sample_captions: ``maps`` = () or (fmap,)."""
+    L = int(dec.max_seq_length if max_caption_len is None else max_caption_len)
+    seed = (0 if noise_u is not None else SEEDS.next()) if seed is None else int(seed)
+    with torch.no_grad():
+        return dec.engine().sample_captions([p.detach() for p in dec.param_list()], features.detach().float(), *(m.detach() for m in maps), L,
+                                            int(num_samples), int(top_k), float(top_p), float(temperature), int(eos_id), 0, seed, noise_u,
+                                            states=states, **cons)
+
+
 class Decoder(nn.Module):
     """Embedding + LSTM + Linear caption decoder (generator.py:27-96)."""
 
@@ -214,18 +238,8 @@ class Decoder(nn.Module):
         ``no_repeat_ngram`` (n: no n-gram occurs twice in a caption; 0 = off), ``min_length`` (<E> not before that many
         tokens; 0 = off) and ``suppress_tokens`` (up to 16 ids never emitted): decode constraints (gicap.h gic_decode_constraints),
         applied inside the search."""
-        L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
-        with torch.no_grad():
-            args = ([p.detach() for p in self.param_list()], features.detach().float(), L, int(beam_size))
-            cons = dict(no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
-            if int(beam_groups) == 1 and float(diversity) == 0.0:
-                ids, scores, lengths = self.engine().beam_search(*args, int(eos_id), 0, float(length_penalty), states=states, **cons)
-            else:
-                ids, scores, lengths = self.engine().diverse_beam_search(*args, int(beam_groups), float(diversity), int(eos_id), 0,
-                                                                         float(length_penalty), states=states, **cons)
-        if return_beams:
-            return ids, scores, lengths
-        return ids[:, 0], scores[:, 0], lengths[:, 0]
+        return _beam_search(self, features, (), beam_size, max_caption_len, eos_id, length_penalty, states, return_beams, beam_groups, diversity,
+                            no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
 
     def sample_captions(self, features, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
                         noise_u=None, states=None, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
@@ -234,16 +248,11 @@ class Decoder(nn.Module):
         either boundary are kept.  <E> = ``eos_id`` ends a caption, <PAD> (0) after it.  ``temperature`` is the sampling temperature,
         not args.temperature.  ``noise_u`` f32 [L, B*n, V] replaces the device draw (Philox(seed); ``seed`` None = the next of SEEDS).
         Returns detached (ids int64 [B, n, L], scores f32 [B, n] = the model's log-probability of each caption, lengths int32 [B, n]),
-        in draw order.  ``max_caption_len`` None = args.max_seq_len.  ``no_repeat_ngram`` (n: no n-gram occurs twice in a caption; 0 = off), ``min_length`` (<E> not before that many
-        tokens; 0 = off) and ``suppress_tokens`` (up to 16 ids never emitted): decode constraints (gicap.h gic_decode_constraints),
-        the banned tokens
-        leave the distribution before top-k / top-p."""
-        L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
-        seed = (0 if noise_u is not None else SEEDS.next()) if seed is None else int(seed)
-        with torch.no_grad():
-            return self.engine().sample_captions([p.detach() for p in self.param_list()], features.detach().float(), L, int(num_samples),
-                                                 int(top_k), float(top_p), float(temperature), int(eos_id), 0, seed, noise_u,
-                                                 states=states, no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
+        in draw order.  ``max_caption_len`` None = args.max_seq_len.  ``no_repeat_ngram`` (n: no n-gram occurs twice in a caption; 0 =
+        off), ``min_length`` (<E> not before that many tokens; 0 = off) and ``suppress_tokens`` (up to 16 ids never emitted): decode
+        constraints (gicap.h gic_decode_constraints), the banned tokens leave the distribution before top-k / top-p."""
+        return _sample_captions(self, features, (), num_samples, top_k, top_p, temperature, max_caption_len, eos_id, seed, noise_u, states,
+                                no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
 
     def add_gumbel(self, o_t, eps=1e-10, gpu=0):
         """o_t + Gumbel(0,1) noise (generator.py:84-96); on the hot path this is fused into sample()."""
@@ -352,19 +361,9 @@ class AttnDecoder(nn.Module):
         if fmap is None:                # (checked before anything touches self: the LSTM decoder's call form has no map)
             raise NotImplementedError("the attention decoder's beam search needs the trunk's feature map: beam_search(features, fmap), "
                                       "or Generator.caption(images)")
-        L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
-        with torch.no_grad():
-            args = ([p.detach() for p in self.param_list()], features.detach().float(), fmap.detach(), L, int(beam_size))
-            cons = dict(no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
-            if int(beam_groups) == 1 and float(diversity) == 0.0:
-                out = self.engine().beam_search(*args, int(eos_id), 0, float(length_penalty), states=states,
-                                                want_alphas=bool(return_alphas), **cons)
-            else:
-                out = self.engine().diverse_beam_search(*args, int(beam_groups), float(diversity), int(eos_id), 0, float(length_penalty),
-                                                        states=states, want_alphas=bool(return_alphas), **cons)
-        if return_beams:
-            return out
-        return tuple(t[:, 0] for t in out)
+        return _beam_search(self, features, (fmap,), beam_size, max_caption_len, eos_id, length_penalty, states, return_beams, beam_groups,
+                            diversity, want_alphas=bool(return_alphas), no_repeat_ngram=no_repeat_ngram, min_length=min_length,
+                            suppress_tokens=suppress_tokens)
 
     def sample_captions(self, features, fmap=None, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2,
                         seed=None, noise_u=None, states=None, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
@@ -374,12 +373,8 @@ class AttnDecoder(nn.Module):
         if fmap is None:                # (checked before anything touches self: the LSTM decoder's call form has no map)
             raise NotImplementedError("the attention decoder's sampling needs the trunk's feature map: sample_captions(features, fmap), "
                                       "or Generator.sample_captions(images)")
-        L = int(self.max_seq_length if max_caption_len is None else max_caption_len)
-        seed = (0 if noise_u is not None else SEEDS.next()) if seed is None else int(seed)
-        with torch.no_grad():
-            return self.engine().sample_captions([p.detach() for p in self.param_list()], features.detach().float(), fmap.detach(), L,
-                                                 int(num_samples), int(top_k), float(top_p), float(temperature), int(eos_id), 0, seed,
-                                                 noise_u, states=states, no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
+        return _sample_captions(self, features, (fmap,), num_samples, top_k, top_p, temperature, max_caption_len, eos_id, seed, noise_u, states,
+                                no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
 
     def forward(self, features, fmap, caps, lengths, pretrain=False, noise_u=None, return_alphas=False, max_length=None):
         """Teacher-forced decode (Decoder.forward with the attention step, gicap.h gic_attn_forward_tf): step 0 is fed ``features``,
@@ -598,22 +593,16 @@ class Generator(nn.Module):
         --decoder attention the encoder also gives the feature map, and ``return_alphas`` appends the attention weights
         (AttnDecoder.beam_search).  ``beam_groups`` / ``diversity``: diverse beam search (Decoder.beam_search).  ``no_repeat_ngram`` /
         ``min_length`` / ``suppress_tokens``: decode constraints (Decoder.beam_search)."""
-        cons = dict(no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
+        kw = dict(beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id, length_penalty=length_penalty, return_beams=return_beams,
+                  beam_groups=beam_groups, diversity=diversity, no_repeat_ngram=no_repeat_ngram, min_length=min_length,
+                  suppress_tokens=suppress_tokens)
+        if return_alphas and not isinstance(self.decoder, AttnDecoder):
+            raise ValueError("attention weights exist for --decoder attention only")
         with torch.no_grad():
-            if isinstance(self.decoder, AttnDecoder):
-                features, fmap = self.encoder.forward_with_map(images)
-                return self.decoder.beam_search(features, fmap, beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id,
-                                                length_penalty=length_penalty, return_beams=return_beams, return_alphas=return_alphas,
-                                                beam_groups=beam_groups, diversity=diversity, **cons)
-            if return_alphas:
-                raise ValueError("attention weights exist for --decoder attention only")
-            if self.args.conditional_gan:
-                features = self.encoder(images)
-            else:
-                features = self.decoder.embed(torch.ones(len(images), dtype=torch.long, device=images.device))
-            return self.decoder.beam_search(features, beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id,
-                                            length_penalty=length_penalty, return_beams=return_beams, beam_groups=beam_groups,
-                                            diversity=diversity, **cons)
+            features, fmap = self._features(images)
+            if fmap is None:
+                return self.decoder.beam_search(features, **kw)
+            return self.decoder.beam_search(features, fmap, return_alphas=return_alphas, **kw)
 
     def sample_captions(self, images, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
                         noise_u=None, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
@@ -624,24 +613,21 @@ class Generator(nn.Module):
         kw = dict(num_samples=num_samples, top_k=top_k, top_p=top_p, temperature=temperature, max_caption_len=max_caption_len,
                   eos_id=eos_id, seed=seed, noise_u=noise_u, no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
         with torch.no_grad():
-            if isinstance(self.decoder, AttnDecoder):
-                features, fmap = self.encoder.forward_with_map(images)
-                return self.decoder.sample_captions(features, fmap, **kw)
-            if self.args.conditional_gan:
-                features = self.encoder(images)
-            else:
-                features = self.decoder.embed(torch.ones(len(images), dtype=torch.long, device=images.device))
-            return self.decoder.sample_captions(features, **kw)
+            features, fmap = self._features(images)
+            return self.decoder.sample_captions(features, *(() if fmap is None else (fmap,)), **kw)
 
     def forward(self, images, caps, lengths, pretrain=False):
+        features, fmap = self._features(images)
+        return self.decoder(features, *(() if fmap is None else (fmap,)), caps, lengths, pretrain)
+
+    def _features(self, images):
+        """(features, fmap or None) as the trainer forms them (training.py:66-68), in the caller's grad mode: the encoder in the module's
+        current mode, with the feature map for --decoder attention, or embed(<S>) with --conditional-gan 0."""
         if isinstance(self.decoder, AttnDecoder):
-            features, fmap = self.encoder.forward_with_map(images)
-            return self.decoder(features, fmap, caps, lengths, pretrain)
+            return self.encoder.forward_with_map(images)
         if self.args.conditional_gan:
-            features = self.encoder(images)
-        else:
-            features = self.decoder.embed(torch.ones(len(images), dtype=torch.long, device=images.device))
-        return self.decoder(features, caps, lengths, pretrain)
+            return self.encoder(images), None
+        return self.decoder.embed(torch.ones(len(images), dtype=torch.long, device=images.device)), None
 
     def init_params(self):
         """generator.py:116-123: every parameter with >= 1 dim (biases, BN affine and trunk convs included)."""
