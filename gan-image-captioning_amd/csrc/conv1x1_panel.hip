@@ -10,14 +10,18 @@
 
 #include "conv1x1_panel.h"
 #include "bn_fold.h"
+#include "conv_device.h"
 
 namespace gic {
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// LDS image of conv1x1_panel_kernel<KT, ABN>: [A panel: KT x 128 rows x 128 B | two weight stages of w_bytes | C tile: 128 rows of sc bytes |
+// column sums [8 waves][32][2] f32 | ABN: coefficient table [64 KT][2] f32]
+struct PanelLds { int w_bytes, sc, w0, c0, st0, coef0, bytes; };
+constexpr PanelLds panel_lds(int KT, bool ABN) {
+  const int w_bytes = KT * 64 * 128, sc = 64 * 2 + 16, w0 = KT * 128 * 128, c0 = w0 + 2 * w_bytes, st0 = c0 + 128 * sc, coef0 = st0 + 8 * 32 * 2 * 4;
+  return {w_bytes, sc, w0, c0, st0, coef0, coef0 + (ABN ? 64 * KT * 8 : 0)};
+}
 
 // everything the kernel reads from its arguments, compact (one batch of scalar loads at the top)
 // KT = K / 64 (4); ABN: BatchNorm + ReLU of the input on load.  8 waves as 4 (M) x 2 (N): a wave owns 32 x 32 of a 128 x 64 output tile.
@@ -28,9 +32,9 @@ __global__ __launch_bounds__(512) void conv1x1_panel_kernel(const PanelDesc d) {
   constexpr int CA = KT * 2;                                            // 16-byte pieces of the A panel per thread
   constexpr int CW = KT;                                                // ... of a weight tile (64 rows x 128 B per K tile)
   constexpr int CS = BM * BN * 2 / 16 / NT;                             // 16-byte stores of a C tile per thread (2)
-  constexpr int A_BYTES = KT * BM * 128, W_BYTES = KT * BN * 128;
-  constexpr int SC = BN * 2 + 16, C_BYTES = BM * SC;
-  constexpr int W0 = A_BYTES, C0 = W0 + 2 * W_BYTES, ST0 = C0 + C_BYTES, COEF0 = ST0 + 8 * (BN / 2) * 2 * 4;
+  constexpr PanelLds LY = panel_lds(KT, ABN);
+  constexpr int W_BYTES = LY.w_bytes, SC = LY.sc, W0 = LY.w0, C0 = LY.c0, ST0 = LY.st0, COEF0 = LY.coef0;
+  static_assert(lds_ok({W0, C0, ST0, COEF0}, LY.bytes), "LDS layout");
   constexpr unsigned OOB = 0x80000000u;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -70,31 +74,17 @@ __global__ __launch_bounds__(512) void conv1x1_panel_kernel(const PanelDesc d) {
 
   if constexpr (ABN) {
     float* coef = (float*)(smem + COEF0);
-    for (int c = tid; c < K; c += NT) {
-      const float gam = d.in_gamma[c], bet = d.in_beta[c];
-      float s1, s2;
-      fold_replicas(d.in_stats, d.in_nrep, K, c, s1, s2);
-      const float mean = s1 * d.in_inv_count;
-      const float var = fmaxf(s2 * d.in_inv_count - mean * mean, 0.f);
-      const float sc = gam * rsqrtf(var + 1e-5f);                        // kBnEps of encoder.hip (nn.BatchNorm2d default)
-      coef[2 * c] = sc;
-      coef[2 * c + 1] = bet - mean * sc;
-    }
+    for (int c = tid; c < K; c += NT) bn_scale_shift(d.in_stats, d.in_nrep, K, c, d.in_inv_count, d.in_gamma, d.in_beta, coef[2 * c], coef[2 * c + 1]);
     __syncthreads();
     wait_vm<CW>();                                                       // the panel has landed (the weight tile may be in flight)
     // a thread's pieces of K tile kt all hold channels kt*64 + kc .. + 7; rows past M were zero-filled and stay zero
 #pragma unroll
     for (int i = 0; i < CA; ++i) {
       if (bm0 + (tid >> 3) + 64 * (i & 1) >= M) continue;
-      const float4* cp = (const float4*)(coef + 2 * ((i >> 1) * 64 + kc));
-      const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
-      const float scl[8] = {c0.x, c0.z, c1.x, c1.z, c2.x, c2.z, c3.x, c3.z};
-      const float sft[8] = {c0.y, c0.w, c1.y, c1.w, c2.y, c2.w, c3.y, c3.w};
+      float scl[8], sft[8];
+      bn_unpack8(coef + 2 * ((i >> 1) * 64 + kc), scl, sft);
       bf16x8* p = (bf16x8*)(smem + (tid + NT * i) * 16);
-      bf16x8 v = *p;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (bf16_t)fmaxf((float)v[e] * scl[e] + sft[e], 0.f);
-      *p = v;
+      *p = bn_relu8(*p, scl, sft);
     }
   }
 
@@ -214,7 +204,7 @@ bool select_conv1x1_panel(const GemmDesc& d, PanelPlan& p) {
   pd.share_a = xcd_share_a(2l * d.M * d.K, 2l * d.N * d.K, pd.groups);
   p.KT = 4; p.abn = d.in_stats != nullptr;
   p.grid = (unsigned)(pd.tiles_m * pd.groups);
-  p.lds = (size_t)p.KT * 128 * 128 + 2 * (size_t)p.KT * 64 * 128 + 128 * (64 * 2 + 16) + 8 * 32 * 2 * 4 + (p.abn ? 64 * p.KT * 8 : 0);
+  p.lds = (size_t)panel_lds(p.KT, p.abn).bytes;
   return true;
 }
 

@@ -10,53 +10,24 @@
 // stores straight from the accumulators, one barrier per tile, no C tile.  The BatchNorm column sums of a tile: the wave's 64 x 16
 // tile is turned through a private LDS scratch (lane c then holds channel c of all 16 pixels), summed, kept in registers per tile and
 // folded across the eight waves once at the end (what the butterfly and the LDS atomics of the first versions cost).
-// K = 512: two 64 KB stages leave no room for the scratch; its column sums take the reduce-scatter butterfly of conv_b2b.hip on DPP.
+// K = 512: two 64 KB stages leave no room for the scratch; its column sums take conv_b2b.hip's reduce-scatter butterfly on DPP (conv_device.h).
 #include <stdlib.h>
 
 #include "conv1x1_pix.h"
 #include "bn_fold.h"
+#include "conv_device.h"
 
 namespace gic {
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kPixMaxTiles = 8;        // 64-channel tiles per workgroup at most: the kernel's registers for their column sums
 
-__device__ __forceinline__ u32x4 pix_load16(const __amdgpu_buffer_rsrc_t r, const int voff, const int soff) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-}
-__device__ __forceinline__ void pix_store16(const u32x4 v, const __amdgpu_buffer_rsrc_t r, const int voff, const int soff) {
-  // The tile offset rides in the per-lane offset, not in the scalar one: the compiler (hipcc 7.2) assumes a store of more than 8 bytes
-  // with an SGPR offset needs no wait state before a VALU instruction overwrites its data registers and schedules one right behind
-  // it; on gfx950 that instruction's result reached memory in place of the first dword (sporadically, lanes 12-15 of each row of 16).
-#ifdef GIC_STORE_SOFF                                                      // (measurement build: the form that exposes the hazard)
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0);
-#else
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff + soff, 0, 0);
-#endif
-}
-// lane l's value of its row-of-16 neighbour l ^ X on the VALU (DPP), and the reduce-scatter butterfly of conv_b2b.hip on them: the
-// column sums where the turning scratch does not fit the LDS (K = 512)
-template <int CTRL>
-__device__ __forceinline__ float pix_dpp(const float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float pix_xor4(const float v) {                 // lanes with bit 2 clear read l + 4 (row_ror:12, banks 0 and 2), the others l - 4
-  const int x = __builtin_bit_cast(int, v);
-  int a = __builtin_amdgcn_update_dpp(0, x, 0x12C, 0xF, 0x5, false);
-  a = __builtin_amdgcn_update_dpp(a, x, 0x124, 0xF, 0xA, false);
-  return __builtin_bit_cast(float, a);
-}
-__device__ __forceinline__ float pix_reduce_scatter16(const float (&v)[16], const int lr) {   // sum over the row's 16 lanes, value e landing in lane lr == e
-  float t[8], u[4], x[2];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { const bool up = lr & 8; t[i] = (up ? v[i + 8] : v[i]) + pix_dpp<0x128>(up ? v[i] : v[i + 8]); }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { const bool up = lr & 4; u[i] = (up ? t[i + 4] : t[i]) + pix_xor4(up ? t[i] : t[i + 4]); }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) { const bool up = lr & 2; x[i] = (up ? u[i + 2] : u[i]) + pix_dpp<0x4E>(up ? u[i] : u[i + 2]); }
-  const bool up = lr & 1;
-  return (up ? x[1] : x[0]) + pix_dpp<0xB1>(up ? x[0] : x[1]);
+// LDS image of conv1x1_pix_kernel<K, NSTG, TURN>: [ring of NSTG weight tiles of w_bytes (64 rows x K bf16) | coefficient table [K][2] f32 |
+// TURN: the turning scratch [8 waves][16 pixels][68] f32].  After the last tile the ring holds red [8 waves][kPixMaxTiles][64] float2.
+struct PixLds { int w_bytes, coef0, turn0, bytes, red_bytes; };
+constexpr PixLds pix_lds(int K, int NSTG, bool TURN) {
+  const int w_bytes = 64 * K * 2, coef0 = NSTG * w_bytes, turn0 = coef0 + K * 8;
+  return {w_bytes, coef0, turn0, turn0 + (TURN ? 8 * 16 * 272 : 0), 8 * kPixMaxTiles * 64 * 8};
 }
 
 // K input channels; NSTG ring stages of 64-channel weight tiles; TURN: column sums through the turning scratch (else: DPP butterfly)
@@ -64,13 +35,14 @@ template <int K, int NSTG, bool TURN>
 __global__ __launch_bounds__(512) void conv1x1_pix_kernel(const PixDesc d) {
   constexpr int NT = 512, KS = K / 32;
   constexpr int ROWB = K * 2, CH = ROWB / 16;                            // bytes / 16-byte pieces of a weight row
-  constexpr int W_BYTES = 64 * ROWB, PW = W_BYTES / 16 / NT;             // a 64-channel tile: 32 | 64 KB, 4 | 8 pieces per thread
-  constexpr int COEF0 = NSTG * W_BYTES;
-  constexpr int MAXT = 8;                                                // 64-channel tiles per workgroup at most (the host's per_group)
+  constexpr PixLds LY = pix_lds(K, NSTG, TURN);
+  constexpr int W_BYTES = LY.w_bytes, PW = W_BYTES / 16 / NT;            // a 64-channel tile: 32 | 64 KB, 4 | 8 pieces per thread
+  constexpr int MAXT = kPixMaxTiles;                                     // (the host's per_group)
   static_assert(PW <= 8, "piece offset array");
+  static_assert(lds_ok({W_BYTES, LY.coef0, LY.turn0}, LY.bytes) && LY.red_bytes <= LY.coef0, "LDS layout; the final fold of the column sums overlays the ring");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* coef = (float*)(smem + COEF0);                                  // [K][2] scale, shift of the input's BatchNorm
-  float* sT = coef + 2 * K;                                  // [8 waves][16 pixels][68] f32: a wave's tile, turned (below)
+  float* coef = (float*)(smem + LY.coef0);                               // [K][2] scale, shift of the input's BatchNorm
+  float* sT = (float*)(smem + LY.turn0);                                 // [8 waves][16 pixels][68] f32: a wave's tile, turned (below)
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int lr = lane & 15, lg = lane >> 4;
@@ -110,25 +82,22 @@ __global__ __launch_bounds__(512) void conv1x1_pix_kernel(const PixDesc d) {
   const int mc = mok ? m : d.M - 1;                                      // rows past M: a pixel of zeros after the normalisation (nothing summed), not stored
   bf16x8 fy[KS];
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) fy[ks] = __builtin_bit_cast(bf16x8, pix_load16(rsA, (mc * K + lg * 8) * 2, ks * 64));
+  for (int ks = 0; ks < KS; ++ks) fy[ks] = __builtin_bit_cast(bf16x8, buf_load16(rsA, (mc * K + lg * 8) * 2, ks * 64));
 
   // ---- the input's BatchNorm coefficients, the column-sum table
   for (int c = tid; c < K; c += NT) {
-    float s1, s2;
-    fold_replicas(d.in_stats, d.in_nrep, K, c, s1, s2);
-    const float mean = s1 * d.in_inv_count, var = fmaxf(s2 * d.in_inv_count - mean * mean, 0.f);
-    const float sc = d.in_gamma[c] * rsqrtf(var + 1e-5f);                // kBnEps of encoder.hip (nn.BatchNorm2d default)
+    float mean, rstd;
+    bn_moments(d.in_stats, d.in_nrep, K, c, d.in_inv_count, mean, rstd);
+    const float sc = d.in_gamma[c] * rstd;
     coef[2 * c] = sc; coef[2 * c + 1] = d.in_beta[c] - mean * sc;
   }
   __syncthreads();
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    const float4* cp = (const float4*)(coef + 2 * (ks * 32 + lg * 8));
-    const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
-    const float scl[8] = {c0.x, c0.z, c1.x, c1.z, c2.x, c2.z, c3.x, c3.z};
-    const float sft[8] = {c0.y, c0.w, c1.y, c1.w, c2.y, c2.w, c3.y, c3.w};
+    float scl[8], sft[8];
+    bn_unpack8(coef + 2 * (ks * 32 + lg * 8), scl, sft);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) fy[ks][e] = (bf16_t)fmaxf((float)fy[ks][e] * scl[e] + sft[e], 0.f);
+    for (int e = 0; e < 8; ++e) fy[ks][e] = (bf16_t)fmaxf((float)fy[ks][e] * scl[e] + sft[e], 0.f);   // (bn_fold.h's bn_relu8, in place: through the call the tile loop compiles differently)
     if (!mok) fy[ks] = __builtin_bit_cast(bf16x8, (u32x4){0u, 0u, 0u, 0u});
   }
 
@@ -177,8 +146,8 @@ __global__ __launch_bounds__(512) void conv1x1_pix_kernel(const PixDesc d) {
     bf16x8 o[2];
 #pragma unroll
     for (int e = 0; e < 16; ++e) o[e >> 3][e & 7] = (bf16_t)acc[e >> 2][e & 3];
-    pix_store16(__builtin_bit_cast(u32x4, o[0]), rsC, coff, (nt0 + t) * 128);
-    pix_store16(__builtin_bit_cast(u32x4, o[1]), rsC, coff + 16, (nt0 + t) * 128);
+    buf_store16(__builtin_bit_cast(u32x4, o[0]), rsC, coff, (nt0 + t) * 128);
+    buf_store16(__builtin_bit_cast(u32x4, o[1]), rsC, coff + 16, (nt0 + t) * 128);
     float s, q;
     if constexpr (TURN) {
     // LDS traffic issued behind the compiler's back: it would make an LDS write it knows of wait for every LDS-DMA in flight
@@ -202,7 +171,7 @@ __global__ __launch_bounds__(512) void conv1x1_pix_kernel(const PixDesc d) {
       float vs[16], vq[16];
 #pragma unroll
       for (int e = 0; e < 16; ++e) { vs[e] = acc[e >> 2][e & 3]; vq[e] = vs[e] * vs[e]; }
-      s = pix_reduce_scatter16(vs, lr); q = pix_reduce_scatter16(vq, lr);
+      s = row_reduce_scatter16(vs, lr); q = row_reduce_scatter16(vq, lr);
     }
     // kept in registers until the end (tile t's pair in slot t): LDS float atomics cost 9 of the first version's 29 us
 #pragma unroll
@@ -251,14 +220,14 @@ bool select_conv1x1_pix(const GemmDesc& d, PixPlan& p) {
   int groups = wg_target / pd.tiles_m;
   if (groups < 1) groups = 1;
   if (groups > tiles_n) groups = tiles_n;
-  if (cdiv(tiles_n, groups) > 8) groups = cdiv(tiles_n, 8);            // (the kernel's MAXT)
+  if (cdiv(tiles_n, groups) > kPixMaxTiles) groups = cdiv(tiles_n, kPixMaxTiles);
   pd.per_group = cdiv(tiles_n, groups);
   groups = cdiv(tiles_n, pd.per_group);
   // (K = 512: two 64 KB stages leave no room for the turning scratch: its column sums take the butterfly)
   p.K = d.K; p.NSTG = d.K == 256 ? 3 : 2; p.turn = d.K == 256;
   p.grid = (unsigned)(pd.tiles_m * groups);
-  p.lds = (size_t)p.NSTG * 64 * p.K * 2 + (size_t)p.K * 8 + (p.turn ? 8 * 16 * 272 : 0);
-  return p.lds <= 160 * 1024;
+  p.lds = (size_t)pix_lds(p.K, p.NSTG, p.turn).bytes;
+  return p.lds <= (size_t)kLdsMax;
 }
 
 bool launch_conv1x1_pix(const PixPlan& p, hipStream_t stream) {

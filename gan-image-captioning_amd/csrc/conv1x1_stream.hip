@@ -13,14 +13,19 @@
 
 #include "conv1x1_stream.h"
 #include "bn_fold.h"
+#include "conv_device.h"
 
 namespace gic {
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// LDS image of conv1x1_stream_kernel<BN, KT, ABN, STATS>: [ring of ns A tiles of a_bytes (ns - 1 in flight) | weights: KT x BN rows x 128 B |
+// unless STATS: one C tile (128 rows of sc bytes), two with KT == 1 | column sums [4 row waves][BN][2] f32 | ABN: coefficient table [64 KT][2] f32]
+struct StreamLds { int ns, a_bytes, sc, c_bytes, w0, c0, st0, coef0, bytes; };
+constexpr StreamLds stream_lds(int BN, int KT, bool ABN, bool STATS) {
+  const int ns = KT == 1 ? 4 : 2, a_bytes = KT * 128 * 128, sc = BN * 2 + 16, c_bytes = 128 * sc;
+  const int w0 = ns * a_bytes, c0 = w0 + KT * BN * 128, st0 = c0 + (STATS ? 0 : (KT == 1 ? 2 : 1) * c_bytes), coef0 = st0 + 4 * BN * 2 * 4;
+  return {ns, a_bytes, sc, c_bytes, w0, c0, st0, coef0, coef0 + (ABN ? 64 * KT * 8 : 0)};
+}
 
 // everything the kernel reads from its arguments, compact (one batch of scalar loads at the top)
 // BN output channels per workgroup; KT = K / 64; ABN: BatchNorm + ReLU of the input on load; STATS: the column sums ONLY (the first pass of
@@ -29,15 +34,15 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 template <int BN, int KT, bool ABN, bool STATS = false>
 __global__ __launch_bounds__(512) void conv1x1_stream_kernel(const StreamDesc d) {
   constexpr int BM = 128, NT = 512, K = 64 * KT;
-  constexpr int NS = KT == 1 ? 4 : 2;                                   // ring stages of A tiles (NS - 1 tiles in flight)
+  constexpr StreamLds LY = stream_lds(BN, KT, ABN, STATS);
+  constexpr int NS = LY.ns;                                             // ring stages of A tiles (NS - 1 tiles in flight)
   constexpr int TM = 2, TN = BN / 32;
   constexpr int CA = KT * 2;                                            // 16-byte pieces of an A tile per thread (128 rows x 128 B per K tile)
   constexpr int CW = KT * BN / 64;                                      // ... of the weight tile
   constexpr int CS = BM * BN * 2 / 16 / NT;                             // 16-byte stores of a C tile per thread
-  constexpr int A_BYTES = KT * BM * 128, W_BYTES = KT * BN * 128;
-  constexpr int SC = BN * 2 + 16, C_BYTES = BM * SC;
+  constexpr int A_BYTES = LY.a_bytes, SC = LY.sc, C_BYTES = LY.c_bytes, W0 = LY.w0, C0 = LY.c0, ST0 = LY.st0, COEF0 = LY.coef0;
   constexpr bool DBUF = KT == 1;                                        // two C tiles: one barrier per row tile, the stores of a tile run under the next tile's MFMAs
-  constexpr int W0 = NS * A_BYTES, C0 = W0 + W_BYTES, ST0 = C0 + (STATS ? 0 : (DBUF ? 2 : 1) * C_BYTES), COEF0 = ST0 + 4 * BN * 2 * 4;
+  static_assert(lds_ok({A_BYTES, C_BYTES, W0, C0, ST0, COEF0}, LY.bytes), "LDS layout");
   constexpr unsigned OOB = 0x80000000u;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -81,24 +86,19 @@ __global__ __launch_bounds__(512) void conv1x1_stream_kernel(const StreamDesc d)
   float scl[KT][8], sft[KT][8];
   if constexpr (ABN) {
     float* coef = (float*)(smem + COEF0);
-    for (int c = tid; c < K; c += NT) {
+    for (int c = tid; c < K; c += NT) {                                  // (bn_fold.h's bn_scale_shift, in place: through the call this kernel's registers are allocated differently)
       const float gam = d.in_gamma[c], bet = d.in_beta[c];
       float s1, s2;
       fold_replicas(d.in_stats, d.in_nrep, K, c, s1, s2);
       const float mean = s1 * d.in_inv_count;
       const float var = fmaxf(s2 * d.in_inv_count - mean * mean, 0.f);
-      const float sc = gam * rsqrtf(var + 1e-5f);                        // kBnEps of encoder.hip (nn.BatchNorm2d default)
+      const float sc = gam * rsqrtf(var + kBnEps);
       coef[2 * c] = sc;
       coef[2 * c + 1] = bet - mean * sc;
     }
     __syncthreads();
 #pragma unroll
-    for (int kt = 0; kt < KT; ++kt) {
-      const float4* cp = (const float4*)(coef + 2 * (kt * 64 + kc));
-      const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
-      scl[kt][0] = c0.x; scl[kt][1] = c0.z; scl[kt][2] = c1.x; scl[kt][3] = c1.z; scl[kt][4] = c2.x; scl[kt][5] = c2.z; scl[kt][6] = c3.x; scl[kt][7] = c3.z;
-      sft[kt][0] = c0.y; sft[kt][1] = c0.w; sft[kt][2] = c1.y; sft[kt][3] = c1.w; sft[kt][4] = c2.y; sft[kt][5] = c2.w; sft[kt][6] = c3.y; sft[kt][7] = c3.w;
-    }
+    for (int kt = 0; kt < KT; ++kt) bn_unpack8(coef + 2 * (kt * 64 + kc), scl[kt], sft[kt]);
   }
 
   float st_s[TN], st_q[TN];
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(512) void conv1x1_stream_kernel(const StreamDesc d)
         bf16x8* p = (bf16x8*)(smem + st * A_BYTES + (tid + NT * i) * 16);
         bf16x8 v = *p;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (bf16_t)fmaxf((float)v[e] * scl[i >> 1][e] + sft[i >> 1][e], 0.f);
+        for (int e = 0; e < 8; ++e) v[e] = (bf16_t)fmaxf((float)v[e] * scl[i >> 1][e] + sft[i >> 1][e], 0.f);   // (bn_relu8, in place: as above)
         *p = v;
       }
     }
@@ -274,9 +274,7 @@ bool select_conv1x1_stream(const GemmDesc& d, StreamPlan& p) {
   sd.share_a = xcd_share_a(2l * d.M * d.K, 2l * d.N * d.K, sd.tiles_n);
   sd.stats_only = d.stats_only;
   p.grid = (unsigned)(sd.groups * sd.tiles_n);
-  const int NS = p.KT == 1 ? 4 : 2;                    // (the kernel's ring stages)
-  p.lds = (size_t)NS * p.KT * 128 * 128 + (size_t)p.KT * p.BN * 128 + (p.stats ? 0 : (p.KT == 1 ? 2 : 1) * 128 * (p.BN * 2 + 16)) + 4 * p.BN * 2 * 4 +
-          (p.abn ? 64 * p.KT * 8 : 0);
+  p.lds = (size_t)stream_lds(p.BN, p.KT, p.abn, p.stats).bytes;
   return true;
 }
 

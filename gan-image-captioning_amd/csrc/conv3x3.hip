@@ -24,6 +24,7 @@
 
 #include "conv3x3.h"
 #include "bn_fold.h"
+#include "conv_device.h"
 
 namespace gic {
 #ifdef GIC_STAMPS
@@ -35,11 +36,17 @@ __device__ unsigned long long g_cstamp[2][8][2];     // [first | last workgroup]
 #endif
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 template <int N> __device__ __forceinline__ void wait_vm_lgkm() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// LDS image of conv3x3_patch_kernel<BN, P, MULTI, ABN>: [patch buffers of 64 P pixels x 128 B, two with MULTI | ring of ns weight tiles of BN rows
+// x 128 B | ABN: coefficient table [Cin][2] f32].  The epilogue overlays the patch and the ring with the C tile (128 rows of sc bytes) and, at
+// stat0, the column sums [8 waves][BN / 2][2] f32: epi_bytes together.
+struct PatchLds { int ns, patch, b_bytes, sc, ring0, coef0, bytes, stat0, epi_bytes; };
+constexpr PatchLds patch_lds(int BN, int P, bool MULTI, bool ABN, int Cin) {
+  const int ns = 3, patch = P * 8192, b_bytes = BN * 128, sc = BN * 2 + 16, ring0 = (MULTI ? 2 : 1) * patch, coef0 = ring0 + ns * b_bytes;
+  return {ns, patch, b_bytes, sc, ring0, coef0, coef0 + (ABN ? Cin * 8 : 0), 128 * sc, 128 * sc + 8 * (BN / 2) * 2 * 4};
+}
+constexpr int kPatchMaxCin = 1024;     // select_conv3x3_patch's bound: the largest coefficient table
 
 // Which of the 16 pixels of a fragment's segment MFMA row x holds.  ds_read_b128 serves a wave in groups of lanes {0-3, 12-15,
 // 20-27}, ...: rows 0-3 and 12-15 of one 16-byte channel chunk together with rows 4-11 of the NEXT chunk.  With pixel p's chunk c
@@ -62,14 +69,14 @@ __device__ __forceinline__ int fdiv(int a, int b, float inv) {
 // ABN: BatchNorm + ReLU of the input on load.
 template <int BN, int P, bool MULTI, bool ABN>
 __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const PatchDesc d) {
-  constexpr int BM = 128, NT = 512, NS = 3;
+  constexpr PatchLds LY = patch_lds(BN, P, MULTI, ABN, kPatchMaxCin);    // (the offsets do not depend on Cin)
+  constexpr int BM = 128, NT = 512, NS = LY.ns;
   constexpr int TM = 2, TN = BN / 32, CB = BN / 64;
-  constexpr int PATCH = P * 8192, B_BYTES = BN * 128, NBUF = MULTI ? 2 : 1;
-  constexpr int RING0 = NBUF * PATCH, COEF0 = RING0 + NS * B_BYTES;
-  constexpr int SC = BN * 2 + 16;
-  constexpr int EPI_BYTES = BM * SC + 8 * (BN / 2) * 2 * 4;
+  constexpr int PATCH = LY.patch, B_BYTES = LY.b_bytes, SC = LY.sc;
+  constexpr int RING0 = LY.ring0, COEF0 = LY.coef0;
   constexpr unsigned OOB = 0x80000000u;
-  static_assert(COEF0 >= EPI_BYTES, "the C tile of the epilogue overlays the patch and the ring");
+  static_assert(COEF0 >= LY.epi_bytes, "the C tile of the epilogue overlays the patch and the ring");
+  static_assert(lds_ok({PATCH, RING0, COEF0, LY.stat0}, LY.bytes), "LDS layout (with the largest coefficient table)");
   static_assert(!MULTI || P <= 10 - NS, "the next chunk's patch pieces must be older than the weight tile of its first tap");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -172,13 +179,13 @@ __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const PatchDesc d) {
   // ---- A-side BatchNorm + ReLU: [scale, shift] per input channel, then each thread normalises the pieces it DMA'd itself
   float* coef = (float*)(smem + COEF0);
   if constexpr (ABN) {
-    for (int c = tid; c < Cin; c += NT) {
+    for (int c = tid; c < Cin; c += NT) {                                // (bn_fold.h's bn_scale_shift, in place: through the call this kernel's registers are allocated differently)
       const float gam = d.in_gamma[c], bet = d.in_beta[c];               // in flight together with the replicas
       float s1, s2;
       fold_replicas(d.in_stats, d.in_nrep, Cin, c, s1, s2);
       const float mean = s1 * d.in_inv_count;
       const float var = fmaxf(s2 * d.in_inv_count - mean * mean, 0.f);
-      const float sc = gam * rsqrtf(var + 1e-5f);                        // kBnEps of encoder.hip (nn.BatchNorm2d default)
+      const float sc = gam * rsqrtf(var + kBnEps);
       coef[2 * c] = sc;
       coef[2 * c + 1] = bet - mean * sc;
     }
@@ -188,19 +195,15 @@ __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const PatchDesc d) {
     if constexpr (ABN) {
       // a thread's pieces all hold the same 8 channels of the chunk: q & 7 and (q >> 4) & 7 do not change with q += 512
       const int c16 = (tid & 7) ^ ((tid >> 4) & 7);
-      const float4* cp = (const float4*)(coef + 2 * (chunk * 64 + c16 * 8));
-      const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
-      const float scl[8] = {c0.x, c0.z, c1.x, c1.z, c2.x, c2.z, c3.x, c3.z};
-      const float sft[8] = {c0.y, c0.w, c1.y, c1.w, c2.y, c2.w, c3.y, c3.w};
+      float scl[8], sft[8];
+      bn_unpack8(coef + 2 * (chunk * 64 + c16 * 8), scl, sft);
       bf16x8 v[P];
 #pragma unroll
       for (int i = 0; i < P; ++i) v[i] = *(const bf16x8*)(smem + buf * PATCH + (tid + NT * i) * 16);
 #pragma unroll
       for (int i = 0; i < P; ++i) {
         if (poff[i] < 0) continue;                                       // halo and unused pieces stay zero
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[i][e] = (bf16_t)fmaxf((float)v[i][e] * scl[e] + sft[e], 0.f);
-        *(bf16x8*)(smem + buf * PATCH + (tid + NT * i) * 16) = v[i];
+        *(bf16x8*)(smem + buf * PATCH + (tid + NT * i) * 16) = bn_relu8(v[i], scl, sft);
       }
     }
   };
@@ -278,7 +281,7 @@ __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const PatchDesc d) {
   // ---- epilogue (as tile8): C tile through LDS (16-byte row stores), BatchNorm column sums folded across the workgroup
   bf16_t* __restrict__ C = (bf16_t*)d.C;
   unsigned char* sC = smem;
-  float* sStat = (float*)(smem + BM * SC);                               // [8 waves][BN/2][2]
+  float* sStat = (float*)(smem + LY.stat0);                              // [8 waves][BN/2][2]
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int nl = wc * (BN / 2) + j * 16 + lr;
@@ -374,7 +377,7 @@ bool select_conv3x3_patch(const GemmDesc& d, PatchPlan& p) {
   static const bool off = getenv("GIC_NO_CONV3X3_PATCH") != nullptr;
   if (off || d.res) return false;
   if (d.cKH != 3 || d.cKW != 3 || d.cStride != 1 || d.cPad != 1 || d.cHo != d.cH || d.cWo != d.cW) return false;
-  if (d.cCin % 64 || d.cCin > 1024 || d.N % 8 || d.ldc % 8 || d.K != 9 * d.cCin || d.ldb % 8) return false;
+  if (d.cCin % 64 || d.cCin > kPatchMaxCin || d.N % 8 || d.ldc % 8 || d.K != 9 * d.cCin || d.ldb % 8) return false;
   const long HW = (long)d.cH * d.cW;
   if (HW <= 0 || d.M % HW || d.M >= (1 << 23)) return false;             // (the kernel's float-reciprocal divisions are exact below 2^23)
   const int Nimg = (int)(d.M / HW);
@@ -401,8 +404,8 @@ bool select_conv3x3_patch(const GemmDesc& d, PatchPlan& p) {
   p.BN = n128 ? 128 : 64;
   p.abn = d.in_stats != nullptr;
   p.grid = (unsigned)((long)pa.tiles_m * tiles_n);
-  p.lds = (size_t)(p.multi ? 2 : 1) * p.P * 8192 + 3 * (size_t)p.BN * 128 + (p.abn ? (size_t)pa.Cin * 8 : 0);
-  return true;
+  p.lds = (size_t)patch_lds(p.BN, p.P, p.multi, p.abn, pa.Cin).bytes;
+  return p.lds <= (size_t)kLdsMax;
 }
 
 bool launch_conv3x3_patch(const PatchPlan& p, hipStream_t stream) {

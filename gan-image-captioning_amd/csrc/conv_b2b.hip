@@ -23,57 +23,18 @@
 
 #include "conv_b2b.h"
 #include "bn_fold.h"
+#include "conv_device.h"
 
 namespace gic {
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// 16-byte accesses through a buffer descriptor: per-lane byte offset + scalar byte offset
-__device__ __forceinline__ u32x4 buf_load16(const __amdgpu_buffer_rsrc_t r, const int voff, const int soff) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-}
-__device__ __forceinline__ void buf_store16(const u32x4 v, const __amdgpu_buffer_rsrc_t r, const int voff, const int soff) {
-  // The tile offset rides in the per-lane offset, not in the scalar one: the compiler (hipcc 7.2) assumes a store of more than 8 bytes
-  // with an SGPR offset needs no wait state before a VALU instruction overwrites its data registers and schedules one right behind
-  // it; on gfx950 that instruction's result reached memory in place of the first dword (sporadically, lanes 12-15 of each row of 16).
-#ifdef GIC_STORE_SOFF                                                      // (measurement build: the form that exposes the hazard)
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0);
-#else
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff + soff, 0, 0);
-#endif
-}
-
-// Lane l's value of its neighbour l ^ X inside its row of 16 lanes, on the VALU (DPP: fused into the addition that consumes it).
-// __shfl_xor is ds_bpermute_b32 -- an LDS instruction: 30 of them per reduce-scatter pair in four dependent stages, queued behind the
-// weight fragment reads of all eight waves.
-template <int CTRL>
-__device__ __forceinline__ float row_dpp(const float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row_xor8(const float v) { return row_dpp<0x128>(v); }                  // row_ror:8
-__device__ __forceinline__ float row_xor4(const float v) {                                              // lanes with bit 2 clear read l + 4 (row_ror:12,
-  const int x = __builtin_bit_cast(int, v);                                                             // banks 0 and 2), the others l - 4 (row_ror:4)
-  int a = __builtin_amdgcn_update_dpp(0, x, 0x12C, 0xF, 0x5, false);
-  a = __builtin_amdgcn_update_dpp(a, x, 0x124, 0xF, 0xA, false);
-  return __builtin_bit_cast(float, a);
-}
-__device__ __forceinline__ float row_xor2(const float v) { return row_dpp<0x4E>(v); }                   // quad_perm:[2,3,0,1]
-__device__ __forceinline__ float row_xor1(const float v) { return row_dpp<0xB1>(v); }                   // quad_perm:[1,0,3,2]
-
-// Sum over the 16 lanes of a row (lr) of 16 per-lane values, value e ending up in lane lr == e: a reduce-scatter butterfly, 15 lane
-// exchanges and 15 additions instead of 16 separate registers that live across the whole kernel.
-__device__ __forceinline__ float row_reduce_scatter16(const float (&v)[16], const int lr) {
-  float t[8], u[4], x[2];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { const bool up = lr & 8; t[i] = (up ? v[i + 8] : v[i]) + row_xor8(up ? v[i] : v[i + 8]); }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { const bool up = lr & 4; u[i] = (up ? t[i + 4] : t[i]) + row_xor4(up ? t[i] : t[i + 4]); }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) { const bool up = lr & 2; x[i] = (up ? u[i + 2] : u[i]) + row_xor2(up ? u[i] : u[i + 2]); }
-  const bool up = lr & 1;
-  return (up ? x[1] : x[0]) + row_xor1(up ? x[0] : x[1]);
+// LDS image of conv_b2b_kernel<C2, C1N, IDENT>: [weight stages (W3 chunk: 64 rows x C2 bf16 = w3_bytes, then W1n chunk: C1N rows x 128 B): all
+// 4 C2 / 64 chunks resident with C2 == 64, else a ring of nstg | coefficient tables [C2][2], [4 C2][2], [4 C2][2] f32: bn2, bn3, shortcut].
+// After the last tile the stages hold red [8 waves][2][C1N] f32.
+struct B2bLds { int nstg, w3_bytes, stage, coef0, bytes, red_bytes; };
+constexpr B2bLds b2b_lds(int C2, int C1N) {
+  const int nstg = 3, w3_bytes = 64 * C2 * 2, stage = w3_bytes + C1N * 128, coef0 = (C2 == 64 ? 4 * C2 / 64 : nstg) * stage;
+  return {nstg, w3_bytes, stage, coef0, coef0 + (C2 + 2 * 4 * C2) * 8, 8 * 2 * C1N * 4};
 }
 
 // C2: channels of y2 (64 | 128); C1N: output channels of the next conv1 (64 | 128); IDENT: identity shortcut (no BatchNorm of its own)
@@ -85,14 +46,15 @@ __global__ __launch_bounds__(512) void conv_b2b_kernel(const B2bDesc d) {
   // two-stage ring the L2-resident weight pieces of the next chunk sat in the queue behind the shortcut loads issued just before
   // them, which come from HBM, and every chunk's wait for its weights inherited a memory round trip.)
   constexpr bool RES = C2 == 64;
-  constexpr int NSTG = 3;
+  constexpr B2bLds LY = b2b_lds(C2, C1N);
+  constexpr int NSTG = LY.nstg, COEF0 = LY.coef0;
   constexpr int NT = 512, NW = NT / 64, BM = 16 * NW, C3 = 4 * C2, NC = C3 / 64, KS1 = C2 / 32, G2 = C1N / 64;
-  constexpr int W3_BYTES = 64 * C2 * 2, W1_BYTES = C1N * 128, STAGE = W3_BYTES + W1_BYTES;
+  constexpr int W3_BYTES = LY.w3_bytes, W1_BYTES = C1N * 128, STAGE = LY.stage;
   constexpr int PW3 = W3_BYTES / 16 / NT, PW1 = W1_BYTES / 16 / NT;       // DMA pieces per thread and chunk
-  constexpr int COEF0 = (RES ? NC : NSTG) * STAGE;
   constexpr int PW = PW3 + PW1;
   constexpr int ROW3 = C2 * 2, CH3 = ROW3 / 16;                           // bytes / 16-byte pieces of a W3 row (128 | 256 B)
   static_assert(PW3 >= 1 && PW1 >= 1, "piece counts");
+  static_assert(lds_ok({W3_BYTES, STAGE, COEF0}, LY.bytes) && LY.red_bytes <= COEF0, "LDS layout; the final fold of the column sums overlays the stages");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* coef2 = (float*)(smem + COEF0);                                 // [C2][2]  bn2 scale, shift
   float* coef3 = coef2 + 2 * C2;                                         // [C3][2]  bn3
@@ -161,19 +123,17 @@ __global__ __launch_bounds__(512) void conv_b2b_kernel(const B2bDesc d) {
     if (c < C2 + C3) {
       const bool two = c < C2;
       const int cc = two ? c : c - C2, Cn = two ? C2 : C3;
-      float s1, s2;
-      fold_replicas(two ? d.stats2 : d.stats3, two ? d.nrep2 : d.nrep3, Cn, cc, s1, s2);
-      const float mean = s1 * d.inv_count, var = fmaxf(s2 * d.inv_count - mean * mean, 0.f);
-      sc = (two ? d.gamma2 : d.gamma3)[cc] * rsqrtf(var + 1e-5f);        // kBnEps of encoder.hip (nn.BatchNorm2d default)
+      float mean, rstd;
+      bn_moments(two ? d.stats2 : d.stats3, two ? d.nrep2 : d.nrep3, Cn, cc, d.inv_count, mean, rstd);
+      sc = (two ? d.gamma2 : d.gamma3)[cc] * rstd;
       sh = (two ? d.beta2 : d.beta3)[cc] - mean * sc;
     } else {
       const int cc = c - C2 - C3;
       sc = 1.f; sh = 0.f;                                                // identity shortcut
       if (d.res_stats) {                                                 // projection shortcut: its own BatchNorm
-        float s1, s2;
-        fold_replicas(d.res_stats, d.res_nrep, C3, cc, s1, s2);
-        const float mean = s1 * d.inv_count, var = fmaxf(s2 * d.inv_count - mean * mean, 0.f);
-        sc = d.res_gamma[cc] * rsqrtf(var + 1e-5f);
+        float mean, rstd;
+        bn_moments(d.res_stats, d.res_nrep, C3, cc, d.inv_count, mean, rstd);
+        sc = d.res_gamma[cc] * rstd;
         sh = d.res_beta[cc] - mean * sc;
       }
     }
@@ -242,12 +202,9 @@ __global__ __launch_bounds__(512) void conv_b2b_kernel(const B2bDesc d) {
       if (c == 0) {
 #pragma unroll
         for (int ks = 0; ks < KS1; ++ks) {
-          const float4* cp = (const float4*)(coef2 + 2 * (ks * 32 + lg * 8));
-          const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
-          const float scl[8] = {c0.x, c0.z, c1.x, c1.z, c2.x, c2.z, c3.x, c3.z};
-          const float sft[8] = {c0.y, c0.w, c1.y, c1.w, c2.y, c2.w, c3.y, c3.w};
-#pragma unroll
-          for (int e = 0; e < 8; ++e) fy[ks][e] = (bf16_t)fmaxf((float)fyn[ks][e] * scl[e] + sft[e], 0.f);
+          float scl[8], sft[8];
+          bn_unpack8(coef2 + 2 * (ks * 32 + lg * 8), scl, sft);
+          fy[ks] = bn_relu8(fyn[ks], scl, sft);
         }
       }
       const unsigned char* sW3 = smem + (RES ? c : st) * STAGE;
@@ -384,7 +341,7 @@ bool select_conv_b2b(const B2bDesc& d, int C2, int C1N, B2bPlan& p) {
   p.d = d;
   p.d.y2_bytes = (unsigned)((long)d.M * C2 * 2); p.d.res_bytes = (unsigned)((long)d.M * C3 * 2); p.d.y1n_bytes = (unsigned)((long)d.M * C1N * 2);
   p.C2 = C2; p.C1N = C1N; p.ident = d.res_stats == nullptr;
-  p.lds = (C2 == 64 ? C3 / 64 : 3) * (size_t)(64 * C2 * 2 + C1N * 128) + (size_t)(C2 + 2 * C3) * 8;
+  p.lds = (size_t)b2b_lds(C2, C1N).bytes;
   // persistent workgroups per CU: as many as the LDS lets share a CU, two at most (measured: 3 and 4 lose)
   static const int wg_per_cu = [] { const char* e = getenv("GIC_B2B_WG_PER_CU"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
   p.per_cu = wg_per_cu ? wg_per_cu : (p.lds > 80 * 1024 ? 1 : 2);

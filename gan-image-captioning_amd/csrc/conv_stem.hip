@@ -11,24 +11,28 @@
 #include <stdlib.h>
 
 #include "conv_stem.h"
+#include "conv_device.h"
 
 namespace gic {
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 constexpr int kRing = 16;                // input-row slots (7 in use + 8 in flight)
 constexpr int kSlot = 2048;              // bytes per slot: two whole LDS-DMA wave instructions (a row is W * 8 <= 2048 bytes)
 constexpr int kAhead = 3;                // output rows whose input rows are in flight beyond the prologue's
 
+// LDS image of conv_stem_kernel: [ring of kRing input-row slots | weights [7][4][64][16 B] = 28 KB | two C tiles of 128 rows of sc bytes |
+// column sums [2 pixel halves][64][2] f32]
+struct StemLds { int sc, c_bytes, w0, c0, st0, bytes; };
+constexpr StemLds stem_lds() {
+  const int sc = 64 * 2 + 16, c_bytes = 128 * sc, w0 = kRing * kSlot, c0 = w0 + 7 * 4 * 64 * 16, st0 = c0 + 2 * c_bytes;
+  return {sc, c_bytes, w0, c0, st0, st0 + 2 * 64 * 2 * 4};
+}
+
 __global__ __launch_bounds__(512) void conv_stem_kernel(const StemDesc d) {
   constexpr int NT = 512, BN = 64, KR = 7;
-  constexpr int W_BYTES = KR * 4 * BN * 16;                             // [r][k-group][n][16 B] = 28 KB
-  constexpr int SC = BN * 2 + 16, C_BYTES = 128 * SC;
-  constexpr int W0 = kRing * kSlot, C0 = W0 + W_BYTES, ST0 = C0 + 2 * C_BYTES;
+  constexpr StemLds LY = stem_lds();
+  constexpr int SC = LY.sc, C_BYTES = LY.c_bytes, W0 = LY.w0, C0 = LY.c0, ST0 = LY.st0;
+  static_assert(lds_ok({C_BYTES, W0, C0, ST0}, LY.bytes), "LDS layout");
   constexpr int CS = 2;                                                 // 16-byte stores of a C tile per thread (Wo * 8 <= 1024 pieces)
   constexpr unsigned OOB = 0x80000000u;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -155,7 +159,7 @@ bool select_conv_stem(const GemmDesc& d, StemPlan& p) {
   sd.ranges = cdiv(d.cHo, sd.rows_per_range);
   sd.H = d.cH; sd.W = d.cW; sd.Ho = d.cHo; sd.Wo = d.cWo;
   p.grid = (unsigned)(sd.Nimg * sd.ranges);
-  p.lds = (size_t)kRing * kSlot + 7 * 4 * 64 * 16 + 2 * 128 * (64 * 2 + 16) + 2 * 64 * 2 * 4;
+  p.lds = (size_t)stem_lds().bytes;
   return true;
 }
 

@@ -15,7 +15,6 @@
 namespace gic {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) u32x4* gptr_u4;
 typedef const __attribute__((address_space(1))) f32x4* gptr_f4;
 

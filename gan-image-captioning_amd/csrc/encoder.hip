@@ -20,8 +20,6 @@
 namespace gic {
 namespace {
 
-constexpr float kBnEps = 1e-5f;
-
 // ---- NCHW f32 [N,3,S,S] -> [N, S+2*pad, Wp, 4] act, zero border and zero 4th channel.  A thread packs PX adjacent pixels (one 16-byte
 // store in bf16): unconditional loads from clamped coordinates (border pixels are zeroed by a select after the loads), 32-bit index math.
 template <typename TA, int PX>
@@ -90,13 +88,7 @@ struct BnSrc {            // y-side or residual-side BatchNorm inputs; stats == 
 __device__ __forceinline__ void bn_coeffs(const BnSrc& b, int c, int C, float inv_count, float& scale, float& shift) {
   float mean, var;
   if (b.stats) {
-    const float g = b.gamma[c], bt = b.beta[c];              // in flight together with the replicas (bn_fold.h)
-    float s1, s2;
-    fold_replicas(b.stats, b.nrep, C, c, s1, s2);
-    mean = s1 * inv_count;
-    var = fmaxf(s2 * inv_count - mean * mean, 0.f);
-    scale = g * rsqrtf(var + kBnEps);
-    shift = bt - mean * scale;
+    bn_scale_shift(b.stats, b.nrep, C, c, inv_count, b.gamma, b.beta, scale, shift);
     return;
   } else if (b.run_mean) {
     mean = b.run_mean[c]; var = b.run_var[c];

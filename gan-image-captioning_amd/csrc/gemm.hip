@@ -27,12 +27,10 @@ namespace gic {
 namespace {
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) u32x4* gptr_u4;
 
 // 16 zero bytes in global memory: the source of an LDS-DMA chunk that falls outside the operand (conv padding, M/K tails)
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 typedef const __attribute__((address_space(1))) void* gbl_void_ptr;
 
 #ifdef GIC_STAMPS
@@ -643,22 +641,18 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
     for (int c = tid; c < ABN_MAXK; c += NT) {
       float sc = 0.f, sh = 0.f;
       if (c < Cn) {
-        float s1, s2;
-        fold_replicas(d.in_stats, d.in_nrep, Cn, c, s1, s2);
-        const float mean = s1 * d.in_inv_count;
-        const float var = fmaxf(s2 * d.in_inv_count - mean * mean, 0.f);
-        sc = d.in_gamma[c] * rsqrtf(var + 1e-5f);              // kBnEps of encoder.hip (nn.BatchNorm2d default)
+        float mean, rstd;
+        bn_moments(d.in_stats, d.in_nrep, Cn, c, d.in_inv_count, mean, rstd);
+        sc = d.in_gamma[c] * rstd;
         sh = d.in_beta[c] - mean * sc;
       }
       coef[2 * c] = sc; coef[2 * c + 1] = sh;
       if constexpr (ARES) {      // the shortcut: its own BatchNorm (projection) or identity (scale 1, shift 0)
         float rs = 1.f, rt = 0.f;
         if (d.res_stats && c < Cn) {
-          float s1, s2;
-          fold_replicas(d.res_stats, d.res_nrep, Cn, c, s1, s2);
-          const float mean = s1 * d.res_inv_count;
-          const float var = fmaxf(s2 * d.res_inv_count - mean * mean, 0.f);
-          rs = d.res_gamma[c] * rsqrtf(var + 1e-5f);
+          float mean, rstd;
+          bn_moments(d.res_stats, d.res_nrep, Cn, c, d.res_inv_count, mean, rstd);
+          rs = d.res_gamma[c] * rstd;
           rt = d.res_beta[c] - mean * rs;
         }
         coef[2 * ABN_MAXK + 2 * c] = rs; coef[2 * ABN_MAXK + 2 * c + 1] = rt;
@@ -675,17 +669,10 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
         const int ch = CONV ? k % d.cCin : k;
         const int tap = CONV ? k / d.cCin : 0;
         const int ts = tap % (CONV ? d.cKW : 1), tr = tap / (CONV ? d.cKW : 1);
-        const float4* cp = (const float4*)(coef + 2 * ch);
-        const float4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
-        const float scl[8] = {c0.x, c0.z, c1.x, c1.z, c2.x, c2.z, c3.x, c3.z};
-        const float sft[8] = {c0.y, c0.w, c1.y, c1.w, c2.y, c2.w, c3.y, c3.w};
+        float scl[8], sft[8];
+        bn_unpack8(coef + 2 * ch, scl, sft);
         float rsc[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f}, rsf[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if constexpr (ARES) {
-          const float4* rp = (const float4*)(coef + 2 * ABN_MAXK + 2 * ch);
-          const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
-          rsc[0] = r0.x; rsc[1] = r0.z; rsc[2] = r1.x; rsc[3] = r1.z; rsc[4] = r2.x; rsc[5] = r2.z; rsc[6] = r3.x; rsc[7] = r3.z;
-          rsf[0] = r0.y; rsf[1] = r0.w; rsf[2] = r1.y; rsf[3] = r1.w; rsf[4] = r2.y; rsf[5] = r2.w; rsf[6] = r3.y; rsf[7] = r3.w;
-        }
+        if constexpr (ARES) bn_unpack8(coef + 2 * ABN_MAXK + 2 * ch, rsc, rsf);
 #pragma unroll
         for (int i = 0; i < CA; ++i) {
           // padding taps and rows past M were zero-filled by the DMA and stay zero (the reference pads the NORMALISED tensor)
@@ -700,8 +687,7 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
             // 1x1 / stride 1 / pad 0: operand row m, channels k..k+7 = element a_off[i] + k of the [M, Cin] block output
             if (wb) *(bf16x8*)((bf16_t*)d.out_wb + (long)a_off[i] + k) = v;
           } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (bf16_t)fmaxf((float)v[e] * scl[e] + sft[e], 0.f);
+            v = bn_relu8(v, scl, sft);
           }
           *p = v;
         }

@@ -9,7 +9,9 @@ for the 4-wave kernel tiles x splits) and the workgroup size.  The traced progra
 64, and the train step's products, whose shapes GIC_GEMM_LOG=1 listed), the trunk alone at 224 / 64 with GIC_NO_CONV_B2B=1 (the rows marked
 "b2b off": the only runs in which gic_conv1x1_res_in and conv3 through gic_conv2d_bn_in appear at that shape) and the trunk alone at 200 x 200,
 batch 3.  conv_b2b's grid is min(row tiles, workgroups per CU x CUs), resolved at launch: the traces show it on 256 CUs.  The trace does not
-report dynamic LDS, so the `lds=` figure of a route line is not asserted here."""
+report dynamic LDS: the expected `lds=` figure of a trunk row was recorded in route-only mode from the last commit whose select_* functions
+spelled the byte count out by hand (0 for tile8 and the 4-wave kernel, which size their LDS statically).  select_* now takes it from the
+layout the kernel addresses, so a figure that moves here is a kernel whose LDS image changed."""
 import pytest
 
 from gan_image_captioning_amd import _lib as L
@@ -54,86 +56,92 @@ def kernel_and_grid(line):
     return line.split(" lds=")[0]
 
 
+def lds_of(line):
+    return int(line.split(" lds=")[1].split()[0])
+
+
 R64 = 64 * 56 * 56           # rows of the 56 x 56 maps at batch 64: 200704; 28 x 28: 50176; 14 x 14: 12544; 7 x 7: 3136
 
 # ResNet-50 trunk, training, bf16, 224 x 224, batch 64: every distinct convolution through the entry point the plan uses for it
 TRUNK_224 = [
-    ("stem", conv2d(64, 230, 4, 64, 7, 2, 0, kw=8), "conv_stem grid=256 block=512"),
-    ("2.0.conv1", conv2d(64, 56, 64, 64, 1, 1, 0), "conv1x1_stream<64,1,false,false> grid=256 block=512"),
-    ("2.x.conv2", conv2d_bn_in(64, 56, 64, 64, 3, 1, 1), "conv3x3_patch<64,6,false,true> grid=1600 block=512"),
-    ("2.x.conv3 stats", conv3_stats(R64, 64, 256), "conv1x1_stream<256,1,true,true> grid=256 block=512"),
-    ("2.0.downsample", conv2d(64, 56, 64, 256, 1, 1, 0), "conv1x1_stream<128,1,false,false> grid=256 block=512"),
-    ("2.0 -> 2.1.conv1", b2b(R64, 64, 64, True), "conv_b2b<64,64,false> grid=min(1568,2*cus) block=512"),           # trace: 512
-    ("2.1 -> 2.2.conv1", b2b(R64, 64, 64, False), "conv_b2b<64,64,true> grid=min(1568,2*cus) block=512"),          # trace: 512
-    ("2.2 -> 3.0.conv1", b2b(R64, 64, 128, False), "conv_b2b<64,128,true> grid=min(1568,1*cus) block=512"),        # trace: 256
-    ("3.0.conv2 (stride 2)", conv2d(64, 56, 128, 128, 3, 2, 1), "tile8<bf16,128,2,true,2,false,false,1024> grid=392 block=512"),
-    ("3.x.conv3 stats", conv3_stats(R64 // 4, 128, 512), "conv1x1_stream<256,2,true,true> grid=256 block=512"),
-    ("3.0.downsample", conv2d(64, 56, 256, 512, 1, 2, 0), "tile8<bf16,128,2,true,1,false,false,1024> grid=1568 block=512"),
-    ("3.0 -> 3.1.conv1", b2b(R64 // 4, 128, 128, True), "conv_b2b<128,128,false> grid=min(392,1*cus) block=512"),   # trace: 256
-    ("3.x.conv2", conv2d_bn_in(64, 28, 128, 128, 3, 1, 1), "conv3x3_patch<128,5,true,true> grid=392 block=512"),
-    ("3.1 -> 3.2.conv1", b2b(R64 // 4, 128, 128, False), "conv_b2b<128,128,true> grid=min(392,1*cus) block=512"),   # trace: 256
-    ("3.3 -> 4.0.conv1", b2b(R64 // 4, 128, 256, False), "conv_b2b<128,256,true> grid=min(392,1*cus) block=512"),   # trace: 256
-    ("4.0.conv2 (stride 2)", conv2d(64, 28, 256, 256, 3, 2, 1), "tile8<bf16,128,2,true,4,false,false,1024> grid=196 block=512"),
-    ("4.x.conv3", conv2d_bn_in(64, 14, 256, 1024, 1, 1, 0), "conv1x1_pix<256,3,true> grid=196 block=512"),
-    ("4.0.downsample", conv2d(64, 28, 512, 1024, 1, 2, 0), "tile8<bf16,128,2,true,2,false,false,1024> grid=784 block=512"),
-    ("4.x.conv1", conv2d(64, 14, 1024, 256, 1, 1, 0), "tile8<bf16,128,2,true,4,false,false,1024> grid=196 block=512"),
-    ("4.x.conv2", conv2d_bn_in(64, 14, 256, 256, 3, 1, 1), "conv3x3_patch<128,4,true,true> grid=196 block=512"),
-    ("5.0.conv1", conv2d(64, 14, 1024, 512, 1, 1, 0), "tile8<bf16,128,2,true,2,false,false,1024> grid=392 block=512"),
-    ("5.0.conv2 (stride 2)", conv2d(64, 14, 512, 512, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=200 block=512"),
-    ("5.x.conv3", conv2d_bn_in(64, 7, 512, 2048, 1, 1, 0), "conv1x1_pix<512,2,false> grid=200 block=512"),
-    ("5.0.downsample", conv2d(64, 14, 1024, 2048, 1, 2, 0), "tile8<bf16,128,2,true,2,false,false,1024> grid=400 block=512"),
-    ("5.x.conv1", conv2d(64, 7, 2048, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=200 block=512"),
-    ("5.x.conv2", conv2d_bn_in(64, 7, 512, 512, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=200 block=512"),
+    ("stem", conv2d(64, 230, 4, 64, 7, 2, 0, kw=8), "conv_stem grid=256 block=512", 99328),
+    ("2.0.conv1", conv2d(64, 56, 64, 64, 1, 1, 0), "conv1x1_stream<64,1,false,false> grid=256 block=512", 112640),
+    ("2.x.conv2", conv2d_bn_in(64, 56, 64, 64, 3, 1, 1), "conv3x3_patch<64,6,false,true> grid=1600 block=512", 74240),
+    ("2.x.conv3 stats", conv3_stats(R64, 64, 256), "conv1x1_stream<256,1,true,true> grid=256 block=512", 107008),
+    ("2.0.downsample", conv2d(64, 56, 64, 256, 1, 1, 0), "conv1x1_stream<128,1,false,false> grid=256 block=512", 155648),
+    ("2.0 -> 2.1.conv1", b2b(R64, 64, 64, True), "conv_b2b<64,64,false> grid=min(1568,2*cus) block=512", 70144),           # trace: 512
+    ("2.1 -> 2.2.conv1", b2b(R64, 64, 64, False), "conv_b2b<64,64,true> grid=min(1568,2*cus) block=512", 70144),          # trace: 512
+    ("2.2 -> 3.0.conv1", b2b(R64, 64, 128, False), "conv_b2b<64,128,true> grid=min(1568,1*cus) block=512", 102912),        # trace: 256
+    ("3.0.conv2 (stride 2)", conv2d(64, 56, 128, 128, 3, 2, 1), "tile8<bf16,128,2,true,2,false,false,1024> grid=392 block=512", 0),
+    ("3.x.conv3 stats", conv3_stats(R64 // 4, 128, 512), "conv1x1_stream<256,2,true,true> grid=256 block=512", 140288),
+    ("3.0.downsample", conv2d(64, 56, 256, 512, 1, 2, 0), "tile8<bf16,128,2,true,1,false,false,1024> grid=1568 block=512", 0),
+    ("3.0 -> 3.1.conv1", b2b(R64 // 4, 128, 128, True), "conv_b2b<128,128,false> grid=min(392,1*cus) block=512", 107520),   # trace: 256
+    ("3.x.conv2", conv2d_bn_in(64, 28, 128, 128, 3, 1, 1), "conv3x3_patch<128,5,true,true> grid=392 block=512", 132096),
+    ("3.1 -> 3.2.conv1", b2b(R64 // 4, 128, 128, False), "conv_b2b<128,128,true> grid=min(392,1*cus) block=512", 107520),   # trace: 256
+    ("3.3 -> 4.0.conv1", b2b(R64 // 4, 128, 256, False), "conv_b2b<128,256,true> grid=min(392,1*cus) block=512", 156672),   # trace: 256
+    ("4.0.conv2 (stride 2)", conv2d(64, 28, 256, 256, 3, 2, 1), "tile8<bf16,128,2,true,4,false,false,1024> grid=196 block=512", 0),
+    ("4.x.conv3", conv2d_bn_in(64, 14, 256, 1024, 1, 1, 0), "conv1x1_pix<256,3,true> grid=196 block=512", 135168),
+    ("4.0.downsample", conv2d(64, 28, 512, 1024, 1, 2, 0), "tile8<bf16,128,2,true,2,false,false,1024> grid=784 block=512", 0),
+    ("4.x.conv1", conv2d(64, 14, 1024, 256, 1, 1, 0), "tile8<bf16,128,2,true,4,false,false,1024> grid=196 block=512", 0),
+    ("4.x.conv2", conv2d_bn_in(64, 14, 256, 256, 3, 1, 1), "conv3x3_patch<128,4,true,true> grid=196 block=512", 116736),
+    ("5.0.conv1", conv2d(64, 14, 1024, 512, 1, 1, 0), "tile8<bf16,128,2,true,2,false,false,1024> grid=392 block=512", 0),
+    ("5.0.conv2 (stride 2)", conv2d(64, 14, 512, 512, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=200 block=512", 0),
+    ("5.x.conv3", conv2d_bn_in(64, 7, 512, 2048, 1, 1, 0), "conv1x1_pix<512,2,false> grid=200 block=512", 135168),
+    ("5.0.downsample", conv2d(64, 14, 1024, 2048, 1, 2, 0), "tile8<bf16,128,2,true,2,false,false,1024> grid=400 block=512", 0),
+    ("5.x.conv1", conv2d(64, 7, 2048, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=200 block=512", 0),
+    ("5.x.conv2", conv2d_bn_in(64, 7, 512, 512, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=200 block=512", 94208),
     # b2b off: the block output formed on load by the next conv1, conv3 with bn2 on load
-    ("b2b off 2.x.conv3", conv2d_bn_in(64, 56, 64, 256, 1, 1, 0), "conv1x1_stream<128,1,true,false> grid=256 block=512"),
-    ("b2b off 2.1.conv1", res_in(64, 56, 256, 64, True), "tile8<bf16,64,2,true,1,true,true,512> grid=1568 block=512"),
-    ("b2b off 2.2.conv1", res_in(64, 56, 256, 64, False), "tile8<bf16,64,2,true,1,true,true,512> grid=1568 block=512"),
-    ("b2b off 3.0.conv1", res_in(64, 56, 256, 128, False), "tile8<bf16,128,2,true,1,true,true,512> grid=1568 block=512"),
-    ("b2b off 3.x.conv3", conv2d_bn_in(64, 28, 128, 512, 1, 1, 0), "conv1x1_stream<128,2,true,false> grid=256 block=512"),
-    ("b2b off 3.x.conv1", res_in(64, 28, 512, 128, False), "tile8<bf16,128,2,true,1,true,true,512> grid=392 block=512"),
+    ("b2b off 2.x.conv3", conv2d_bn_in(64, 56, 64, 256, 1, 1, 0), "conv1x1_stream<128,1,true,false> grid=256 block=512", 156160),
+    ("b2b off 2.1.conv1", res_in(64, 56, 256, 64, True), "tile8<bf16,64,2,true,1,true,true,512> grid=1568 block=512", 0),
+    ("b2b off 2.2.conv1", res_in(64, 56, 256, 64, False), "tile8<bf16,64,2,true,1,true,true,512> grid=1568 block=512", 0),
+    ("b2b off 3.0.conv1", res_in(64, 56, 256, 128, False), "tile8<bf16,128,2,true,1,true,true,512> grid=1568 block=512", 0),
+    ("b2b off 3.x.conv3", conv2d_bn_in(64, 28, 128, 512, 1, 1, 0), "conv1x1_stream<128,2,true,false> grid=256 block=512", 138240),
+    ("b2b off 3.x.conv1", res_in(64, 28, 512, 128, False), "tile8<bf16,128,2,true,1,true,true,512> grid=392 block=512", 0),
 ]
 
 # the same trunk at 200 x 200, batch 3 (maps of 50, 25, 13 and 7 pixels: 7500, 1875, 507 and 147 rows, none a multiple of 128)
 TRUNK_200 = [
-    ("stem", conv2d(3, 206, 4, 64, 7, 2, 0, kw=8), "conv_stem grid=150 block=512"),
-    ("2.0.conv1", conv2d(3, 50, 64, 64, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=59 block=512"),
-    ("2.x.conv2", conv2d_bn_in(3, 50, 64, 64, 3, 1, 1), "conv3x3_patch<64,6,false,true> grid=60 block=512"),
-    ("2.x.conv3", conv2d_bn_in(3, 50, 64, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,true,false,1024> grid=236 block=512"),
-    ("2.0.downsample", conv2d(3, 50, 64, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=236 block=512"),
-    ("2.x.conv1", conv2d(3, 50, 256, 64, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=59 block=512"),
-    ("3.0.conv1", conv2d(3, 50, 256, 128, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=118 block=512"),
-    ("3.0.conv2 (stride 2)", conv2d(3, 50, 128, 128, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=30 block=512"),
-    ("3.x.conv3", conv2d_bn_in(3, 25, 128, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,true,false,1024> grid=120 block=512"),
-    ("3.0.downsample", conv2d(3, 50, 256, 512, 1, 2, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=120 block=512"),
-    ("3.x.conv1", conv2d(3, 25, 512, 128, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=30 block=512"),
-    ("3.x.conv2", conv2d_bn_in(3, 25, 128, 128, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=30 block=512"),
-    ("4.0.conv1", conv2d(3, 25, 512, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=60 block=512"),
-    ("4.0.conv2 (stride 2)", conv2d(3, 25, 256, 256, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512"),
-    ("4.x.conv3", conv2d_bn_in(3, 13, 256, 1024, 1, 1, 0), "conv1x1_pix<256,3,true> grid=64 block=512"),
-    ("4.0.downsample", conv2d(3, 25, 512, 1024, 1, 2, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=64 block=512"),
-    ("4.x.conv1", conv2d(3, 13, 1024, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512"),
-    ("4.x.conv2", conv2d_bn_in(3, 13, 256, 256, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=16 block=512"),
-    ("5.0.conv1", conv2d(3, 13, 1024, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=32 block=512"),
-    ("5.0.conv2 (stride 2)", conv2d(3, 13, 512, 512, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512"),
-    ("5.x.conv3", conv2d_bn_in(3, 7, 512, 2048, 1, 1, 0), "conv1x1_pix<512,2,false> grid=64 block=512"),
-    ("5.0.downsample", conv2d(3, 13, 1024, 2048, 1, 2, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=64 block=512"),
-    ("5.x.conv1", conv2d(3, 7, 2048, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512"),
-    ("5.x.conv2", conv2d_bn_in(3, 7, 512, 512, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=16 block=512"),
+    ("stem", conv2d(3, 206, 4, 64, 7, 2, 0, kw=8), "conv_stem grid=150 block=512", 99328),
+    ("2.0.conv1", conv2d(3, 50, 64, 64, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=59 block=512", 0),
+    ("2.x.conv2", conv2d_bn_in(3, 50, 64, 64, 3, 1, 1), "conv3x3_patch<64,6,false,true> grid=60 block=512", 74240),
+    ("2.x.conv3", conv2d_bn_in(3, 50, 64, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,true,false,1024> grid=236 block=512", 0),
+    ("2.0.downsample", conv2d(3, 50, 64, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=236 block=512", 0),
+    ("2.x.conv1", conv2d(3, 50, 256, 64, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=59 block=512", 0),
+    ("3.0.conv1", conv2d(3, 50, 256, 128, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=118 block=512", 0),
+    ("3.0.conv2 (stride 2)", conv2d(3, 50, 128, 128, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=30 block=512", 0),
+    ("3.x.conv3", conv2d_bn_in(3, 25, 128, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,true,false,1024> grid=120 block=512", 0),
+    ("3.0.downsample", conv2d(3, 50, 256, 512, 1, 2, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=120 block=512", 0),
+    ("3.x.conv1", conv2d(3, 25, 512, 128, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=30 block=512", 0),
+    ("3.x.conv2", conv2d_bn_in(3, 25, 128, 128, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=30 block=512", 91136),
+    ("4.0.conv1", conv2d(3, 25, 512, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=60 block=512", 0),
+    ("4.0.conv2 (stride 2)", conv2d(3, 25, 256, 256, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512", 0),
+    ("4.x.conv3", conv2d_bn_in(3, 13, 256, 1024, 1, 1, 0), "conv1x1_pix<256,3,true> grid=64 block=512", 135168),
+    ("4.0.downsample", conv2d(3, 25, 512, 1024, 1, 2, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=64 block=512", 0),
+    ("4.x.conv1", conv2d(3, 13, 1024, 256, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512", 0),
+    ("4.x.conv2", conv2d_bn_in(3, 13, 256, 256, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=16 block=512", 92160),
+    ("5.0.conv1", conv2d(3, 13, 1024, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=32 block=512", 0),
+    ("5.0.conv2 (stride 2)", conv2d(3, 13, 512, 512, 3, 2, 1), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512", 0),
+    ("5.x.conv3", conv2d_bn_in(3, 7, 512, 2048, 1, 1, 0), "conv1x1_pix<512,2,false> grid=64 block=512", 135168),
+    ("5.0.downsample", conv2d(3, 13, 1024, 2048, 1, 2, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=64 block=512", 0),
+    ("5.x.conv1", conv2d(3, 7, 2048, 512, 1, 1, 0), "tile8<bf16,64,2,true,4,false,false,1024> grid=16 block=512", 0),
+    ("5.x.conv2", conv2d_bn_in(3, 7, 512, 512, 3, 1, 1), "conv3x3_patch<64,4,true,true> grid=16 block=512", 94208),
 ]
 
 
-@pytest.mark.parametrize("name,call,expected", TRUNK_224, ids=[c[0] for c in TRUNK_224])
-def test_trunk_routes_at_224_batch_64(name, call, expected):
+@pytest.mark.parametrize("name,call,expected,lds", TRUNK_224, ids=[c[0] for c in TRUNK_224])
+def test_trunk_routes_at_224_batch_64(name, call, expected, lds):
     status, line = route(call)
     assert status == 0, line
     assert kernel_and_grid(line) == expected
+    assert lds_of(line) == lds
 
 
-@pytest.mark.parametrize("name,call,expected", TRUNK_200, ids=[c[0] for c in TRUNK_200])
-def test_trunk_routes_at_200_batch_3(name, call, expected):
+@pytest.mark.parametrize("name,call,expected,lds", TRUNK_200, ids=[c[0] for c in TRUNK_200])
+def test_trunk_routes_at_200_batch_3(name, call, expected, lds):
     status, line = route(call)
     assert status == 0, line
     assert kernel_and_grid(line) == expected
+    assert lds_of(line) == lds
 
 
 def test_rows_off_the_128_grid_decline_the_fused_pair():
