@@ -486,17 +486,10 @@ int sample_fwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
       if (M > M_prev) {
         for (int l = 0; l < NL; ++l) {
           const long rowbytes = c.ldx(l) * (long)c.asz();
-          const int pb = rowbytes % 16 == 0 ? 16 : (rowbytes % 4 == 0 ? 4 : 2);      // rowbytes is a multiple of the element size
-          const long work = (long)(M - M_prev) * (rowbytes / pb);
-          const dim3 jgrid((unsigned)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256));
-          const unsigned char* jsrc = (const unsigned char*)opt->resume_from->xh[l] + (size_t)t * opt->resume_B * rowbytes;
-          unsigned char* jdst = (unsigned char*)st->xh[l] + (size_t)t * B * rowbytes;
-          const float* jsc = (const float*)(opt->resume_from->c[l] + (long)t * opt->resume_B * H);
-          float* jdc = st->c[l] + (long)t * B * H;
-          if (pb == 16) hipLaunchKernelGGL(rollout_join_kernel<16>, jgrid, dim3(256), 0, stream, jsrc, jdst, rowbytes, jsc, jdc, H, (long)M_prev, (long)M, opt->resume_B);
-          else if (pb == 4) hipLaunchKernelGGL(rollout_join_kernel<4>, jgrid, dim3(256), 0, stream, jsrc, jdst, rowbytes, jsc, jdc, H, (long)M_prev, (long)M, opt->resume_B);
-          else hipLaunchKernelGGL(rollout_join_kernel<2>, jgrid, dim3(256), 0, stream, jsrc, jdst, rowbytes, jsc, jdc, H, (long)M_prev, (long)M, opt->resume_B);
-          GIC_CHECK_LAUNCH("rollout_join");
+          GIC_PROPAGATE(rollout_join((const unsigned char*)opt->resume_from->xh[l] + (size_t)t * opt->resume_B * rowbytes,
+                                     (unsigned char*)st->xh[l] + (size_t)t * B * rowbytes, rowbytes,
+                                     (const float*)(opt->resume_from->c[l] + (long)t * opt->resume_B * H), st->c[l] + (long)t * B * H, H, M_prev, M,
+                                     opt->resume_B, stream));
         }
       }
       if (M == 0) continue;
@@ -532,9 +525,8 @@ int sample_fwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
       g.seed = seed; g.stream = (uint64_t)t;
       const int s = gemm_gumbelmax(g, stream);
       if (s == GIC_OK) {
-        hipLaunchKernelGGL((rollout_pick_kernel<TA>), dim3((unsigned)cdiv(M, 4)), dim3(256), 0, stream, (const unsigned long long*)g.gm_rowkey,
-                           ids + t, (long)L, P->embed, x_next, c.ldx(0), M, V, E, f_ids ? f_ids + t : nullptr, f_len, t);
-        GIC_CHECK_LAUNCH("rollout_pick");
+        GIC_PROPAGATE(rollout_pick(c.dt, (const unsigned long long*)g.gm_rowkey, ids + t, (long)L, P->embed, x_next, c.ldx(0), M, V, E,
+                                   f_ids ? f_ids + t : nullptr, f_len, t, stream));
         continue;
       }
       if (s != GIC_ERR_UNSUPPORTED) return s;
@@ -549,22 +541,8 @@ int sample_fwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
       g.M = M; g.N = V; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = P->b_out;
       GIC_PROPAGATE(gemm(g, stream));
     }
-    TA* out_t = out ? (TA*)out + (long)t * V : nullptr;
-    constexpr bool kFast = sizeof(TA) == 2;
-    if (V % 4 == 0 && V <= 4096) {
-      hipLaunchKernelGGL((gumbel_softmax_argmax_reg_kernel<TA, 1, kFast>), dim3(M), dim3(1024), 0, stream, (const float*)st->logits,
-                         u_t, seed, (uint64_t)t, temperature, pretrain, out_t, (long)L * V, ids + t, (long)L,
-                         P->embed, x_next, c.ldx(0), V, E, f_ids ? f_ids + t : nullptr, f_len, t);
-    } else if (V % 4 == 0 && V <= 16384) {
-      hipLaunchKernelGGL((gumbel_softmax_argmax_reg_kernel<TA, 4, kFast>), dim3(M), dim3(1024), 0, stream, (const float*)st->logits,
-                         u_t, seed, (uint64_t)t, temperature, pretrain, out_t, (long)L * V, ids + t, (long)L,
-                         P->embed, x_next, c.ldx(0), V, E, f_ids ? f_ids + t : nullptr, f_len, t);
-    } else {
-      hipLaunchKernelGGL((gumbel_softmax_argmax_kernel<TA>), dim3(M), dim3(256), 0, stream, st->logits, u_t, seed, (uint64_t)t,
-                         temperature, pretrain, out_t, (long)L * V, ids + t, (long)L, P->embed, x_next,
-                         c.ldx(0), V, E, f_ids ? f_ids + t : nullptr, f_len, t);
-    }
-    GIC_CHECK_LAUNCH("gumbel_softmax_argmax");
+    GIC_PROPAGATE(rollout_argmax(c.dt, st->logits, u_t, seed, (uint64_t)t, temperature, pretrain, out ? (TA*)out + (long)t * V : nullptr, (long)L * V,
+                                 ids + t, (long)L, P->embed, x_next, c.ldx(0), M, V, E, f_ids ? f_ids + t : nullptr, f_len, t, stream));
   }
   return GIC_OK;
 }
@@ -714,6 +692,63 @@ int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, co
   w.M = V; w.N = H; w.K = (int)BL; w.in_dtype = dt; w.out_dtype = DT_F32;
   GIC_PROPAGATE(gemm(w, stream));
   return colsum(dlog, dt, V, BL, V, d_bout, nullptr, 0, stream);
+}
+
+// ---- the generic roll-out's per-step launches, shared with the attention decoder's roll-out (attn_rollout.hip)
+int rollout_join(const unsigned char* src_xh, unsigned char* dst_xh, long rowbytes, const float* src_c, float* dst_c, int H, long r0, long r1,
+                 int srcB, hipStream_t stream) {
+  const int pb = rowbytes % 16 == 0 ? 16 : (rowbytes % 4 == 0 ? 4 : 2);      // rowbytes is a multiple of the element size
+  const long work = (r1 - r0) * (rowbytes / pb);
+  const dim3 jgrid((unsigned)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256));
+  if (pb == 16) hipLaunchKernelGGL(rollout_join_kernel<16>, jgrid, dim3(256), 0, stream, src_xh, dst_xh, rowbytes, src_c, dst_c, H, r0, r1, srcB);
+  else if (pb == 4) hipLaunchKernelGGL(rollout_join_kernel<4>, jgrid, dim3(256), 0, stream, src_xh, dst_xh, rowbytes, src_c, dst_c, H, r0, r1, srcB);
+  else hipLaunchKernelGGL(rollout_join_kernel<2>, jgrid, dim3(256), 0, stream, src_xh, dst_xh, rowbytes, src_c, dst_c, H, r0, r1, srcB);
+  GIC_CHECK_LAUNCH("rollout_join");
+  return GIC_OK;
+}
+
+int rollout_pick(int dt, const unsigned long long* rowkey, int64_t* ids, long ids_stride, const float* embed, void* x_next, long ld_x, int rows,
+                 int V, int E, const int64_t* force_ids, const int32_t* force_len, int t, hipStream_t stream) {
+  const dim3 grid((unsigned)cdiv(rows, 4));
+  if (dt == DT_F32)
+    hipLaunchKernelGGL((rollout_pick_kernel<float>), grid, dim3(256), 0, stream, rowkey, ids, ids_stride, embed, (float*)x_next, ld_x, rows, V, E,
+                       force_ids, force_len, t);
+  else
+    hipLaunchKernelGGL((rollout_pick_kernel<bf16_t>), grid, dim3(256), 0, stream, rowkey, ids, ids_stride, embed, (bf16_t*)x_next, ld_x, rows, V, E,
+                       force_ids, force_len, t);
+  GIC_CHECK_LAUNCH("rollout_pick");
+  return GIC_OK;
+}
+
+namespace {
+template <typename TA>
+int rollout_argmax_t(float* logits, const float* u, uint64_t seed, uint64_t rng_stream, float temperature, int pretrain, TA* out, long out_stride,
+                     int64_t* ids, long ids_stride, const float* embed, TA* x_next, long ld_x, int rows, int V, int E, const int64_t* force_ids,
+                     const int32_t* force_len, int t, hipStream_t stream) {
+  constexpr bool kFast = sizeof(TA) == 2;
+  if (V % 4 == 0 && V <= 4096) {
+    hipLaunchKernelGGL((gumbel_softmax_argmax_reg_kernel<TA, 1, kFast>), dim3(rows), dim3(1024), 0, stream, (const float*)logits, u, seed, rng_stream,
+                       temperature, pretrain, out, out_stride, ids, ids_stride, embed, x_next, ld_x, V, E, force_ids, force_len, t);
+  } else if (V % 4 == 0 && V <= 16384) {
+    hipLaunchKernelGGL((gumbel_softmax_argmax_reg_kernel<TA, 4, kFast>), dim3(rows), dim3(1024), 0, stream, (const float*)logits, u, seed, rng_stream,
+                       temperature, pretrain, out, out_stride, ids, ids_stride, embed, x_next, ld_x, V, E, force_ids, force_len, t);
+  } else {
+    hipLaunchKernelGGL((gumbel_softmax_argmax_kernel<TA>), dim3(rows), dim3(256), 0, stream, logits, u, seed, rng_stream, temperature, pretrain, out,
+                       out_stride, ids, ids_stride, embed, x_next, ld_x, V, E, force_ids, force_len, t);
+  }
+  GIC_CHECK_LAUNCH("gumbel_softmax_argmax");
+  return GIC_OK;
+}
+}  // namespace
+
+int rollout_argmax(int dt, float* logits, const float* u, uint64_t seed, uint64_t rng_stream, float temperature, int pretrain, void* out,
+                   long out_stride, int64_t* ids, long ids_stride, const float* embed, void* x_next, long ld_x, int rows, int V, int E,
+                   const int64_t* force_ids, const int32_t* force_len, int t, hipStream_t stream) {
+  if (dt == DT_F32)
+    return rollout_argmax_t<float>(logits, u, seed, rng_stream, temperature, pretrain, (float*)out, out_stride, ids, ids_stride, embed, (float*)x_next,
+                                   ld_x, rows, V, E, force_ids, force_len, t, stream);
+  return rollout_argmax_t<bf16_t>(logits, u, seed, rng_stream, temperature, pretrain, (bf16_t*)out, out_stride, ids, ids_stride, embed,
+                                  (bf16_t*)x_next, ld_x, rows, V, E, force_ids, force_len, t, stream);
 }
 
 int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_new, void* h_next, long ld_next, void* h_up, long ld_up,

@@ -113,5 +113,8 @@ constexpr int kRouteLen = 160;
 // multiple of 4, many roll-out rows (the 8-wave kernel's grid conditions).  GIC_ERR_UNSUPPORTED (no message) when the shapes do not
 // qualify: the caller runs the product and the Gumbel-argmax kernel separately.
 int gemm_gumbelmax(const GemmDesc& d, hipStream_t stream);
+// Pure host function: the smallest N from which gemm_gumbelmax takes an M x N x K product of these operand layouts (the selection's own
+// predicate, the GIC_NO_TILE8 / GIC_NO_FUSED_GUMBELMAX switches included), 0 = never.  Callers size the fallback's logits scratch by it.
+long gemm_gumbelmax_from_cols(int in_dtype, int M, int K, long lda, long ldb);
 
 }  // namespace gic

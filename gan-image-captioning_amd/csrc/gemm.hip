@@ -1221,16 +1221,26 @@ int select(const GemmDesc& d, bool vec, int after, Plan& p) {
   return take(F_GEMM4);
 }
 
+// The smallest column count N (roll-out rows) from which gemm_gumbelmax takes an M x N x K product of bf16 k-contiguous operands with
+// these leading dimensions (16-byte aligned pointers, a positive temperature and operands under 2 GiB presumed): at least 128 columns and
+// 160 tiles of 128 x 128.  0: never (f32, M below 128 or no multiple of 4, the GIC_NO_TILE8 / GIC_NO_FUSED_GUMBELMAX switches).
+long gumbelmax_from_cols(int in_dtype, int M, int K, long lda, long ldb) {
+  static const bool off = getenv("GIC_NO_TILE8") != nullptr || getenv("GIC_NO_FUSED_GUMBELMAX") != nullptr;
+  if (off || in_dtype != DT_BF16 || M < 128 || M % 4 || K % 8 || lda % 8 || ldb % 8 || ((long)(M - 1) * lda + K) * 2 >= (1l << 31)) return 0;
+  const long mt = cdiv(M, 128), nt = (160 + mt - 1) / mt;           // column tiles that make 160 tiles
+  return 128 * (nt - 1) + 1 > 128 ? 128 * (nt - 1) + 1 : 128;
+}
+
 // gemm_gumbelmax's one candidate: the 8-wave kernel with 128 x 128 tiles
 bool select_gumbelmax(const GemmDesc& d0, Plan& p) {
-  static const bool off = getenv("GIC_NO_TILE8") != nullptr || getenv("GIC_NO_FUSED_GUMBELMAX") != nullptr;
   GemmDesc& d = p.d = d0;
-  if (off || d.in_dtype != DT_BF16 || !d.a_kc || !d.b_kc || d.M < 128 || d.M % 4 || d.K % 8 || d.lda % 8 || d.ldb % 8 || !aligned16(d.A) ||
-      !aligned16(d.B) || !aligned16(d.gm_bias) || (d.gm_u && (!aligned16(d.gm_u) || d.gm_ldu % 4)) || !(d.gm_temperature > 0.f))
+  const long from = gumbelmax_from_cols(d.in_dtype, d.M, d.K, d.lda, d.ldb);
+  if (!from || d.N < from || !d.a_kc || !d.b_kc || !aligned16(d.A) || !aligned16(d.B) || !aligned16(d.gm_bias) ||
+      (d.gm_u && (!aligned16(d.gm_u) || d.gm_ldu % 4)) || !(d.gm_temperature > 0.f))
     return false;
   const long a_elems = (long)(d.M - 1) * d.lda + d.K, b_elems = (long)(d.N - 1) * d.ldb + d.K;
   const long tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
-  if (a_elems * 2 >= (1l << 31) || b_elems * 2 >= (1l << 31) || d.N < 128 || tiles < 160) return false;
+  if (b_elems * 2 >= (1l << 31)) return false;
   d.epi = EPI_GUMBELMAX;
   d.n_fast = xcd_share_a(2l * d.M * d.K, 2l * d.N * d.K, cdiv(d.N, 128));
   p.t8 = {128, tiles > 256 ? 2 : 4, false, false, 1024, (unsigned)tiles, (unsigned)(a_elems * 2), (unsigned)(b_elems * 2)};
@@ -1386,6 +1396,8 @@ bool conv_base(const GemmDesc& d, long a_elems, long b_elems, ConvBase& b) {
   b.a_bytes = (unsigned)(a_elems * 2); b.b_bytes = (unsigned)(b_elems * 2);
   return true;
 }
+
+long gemm_gumbelmax_from_cols(int in_dtype, int M, int K, long lda, long ldb) { return gumbelmax_from_cols(in_dtype, M, K, lda, ldb); }
 
 int gemm_gumbelmax(const GemmDesc& d, hipStream_t stream) {
   GIC_CHECK_ARG(d.A && d.B && d.gm_rowkey && d.gm_bias, "gemm_gumbelmax: null operand");

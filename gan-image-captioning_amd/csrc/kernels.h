@@ -26,6 +26,18 @@ int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, co
 // gpre f32 [rows, 4H], c_prev / c_new [rows, H], h into h_next (and h_up when not null)
 int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_new, void* h_next, long ld_next, void* h_up, long ld_up,
                        int rows, int H, hipStream_t stream);
+// the generic roll-out's per-step launches (decoder.hip), shared with the attention decoder's roll-out (attn_rollout.hip):
+//   rollout_join    rows [r0, r1) of dst_xh / dst_c = the rows r % srcB of src_xh / src_c (rows of rowbytes bytes / H floats)
+//   rollout_pick    after gemm_gumbelmax: ids[r * ids_stride] = the index of rowkey[r] (or the forced id) and its embedding row into x_next
+//   rollout_argmax  after the plain vocabulary product into logits f32 [rows, V]: the per-row Gumbel-softmax, its argmax into ids and the
+//                   embedding row into x_next; out (act, rows out_stride apart) may be null
+int rollout_join(const unsigned char* src_xh, unsigned char* dst_xh, long rowbytes, const float* src_c, float* dst_c, int H, long r0, long r1,
+                 int srcB, hipStream_t stream);
+int rollout_pick(int dt, const unsigned long long* rowkey, int64_t* ids, long ids_stride, const float* embed, void* x_next, long ld_x, int rows,
+                 int V, int E, const int64_t* force_ids, const int32_t* force_len, int t, hipStream_t stream);
+int rollout_argmax(int dt, float* logits, const float* u, uint64_t seed, uint64_t rng_stream, float temperature, int pretrain, void* out,
+                   long out_stride, int64_t* ids, long ids_stride, const float* embed, void* x_next, long ld_x, int rows, int V, int E,
+                   const int64_t* force_ids, const int32_t* force_len, int t, hipStream_t stream);
 // determinism.hip: the process-wide deterministic mode (gic_set_deterministic) and its ordered embedding scatter:
 // dst[id(r) * d_id + e * d_e] += sum over tokens r of src[(r + row_off) * ld + e] (ascending r), id(r) = ids[(r % B) * s_b + (r / B) * s_t]
 int det_mode();

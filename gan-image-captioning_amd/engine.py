@@ -1331,6 +1331,45 @@ class AttnDecoderEngine(_CaptionDecodes):
             C.byref(self._pstruct(grads[:-1], L.AttnGrads, grads[-1])), stream_ptr()), "gic_attn_forward_tf_bwd")
         return grads
 
+    def rollout_ws_bytes(self, B: int, Lc: int, rows: int) -> int:
+        """Bytes of gic_attn_rollout's workspace (host-only query)."""
+        out = C.c_uint64(0)
+        L.check(L.load().gic_attn_rollout_ws_bytes(C.byref(self.dims(B, Lc)), int(rows), C.byref(out)), "gic_attn_rollout_ws_bytes")
+        return int(out.value)
+
+    def rollout(self, params, tf_saved, Y: torch.Tensor, num_rollouts: int, noise_u: Optional[torch.Tensor] = None, seed: int = 0,
+                ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """gic_attn_rollout: the SeqGAN step's Monte-Carlo roll-outs of the captions ``Y`` int64 [B, L].  ``tf_saved``: what
+        ``forward_tf(params, features, fmap, Y[:, :-1], L, ..., keep_state=True)`` returned last (the roll-outs join at their prefix
+        length from its state and read its feature map).  Returns ids int64 [(L-1)*N*B, L], row (t-1)*N*B + n*B + b = roll-out n of
+        caption b with the prefix Y[b, :t].  ``noise_u`` f32 [L, (L-1)*N*B, V] or None = Philox(seed)."""
+        self.check_params(params)
+        require_gpu(Y, noise_u)
+        B, Lc = Y.shape
+        N = int(num_rollouts)
+        rows = (Lc - 1) * N * B
+        if Y.dtype != torch.int64 or N < 1 or Lc < 2:
+            raise ValueError("rollout: Y must be int64 [B, L] with L >= 2 and num_rollouts >= 1")
+        if tf_saved["T"] != Lc or tf_saved["Tmax"] != Lc or tuple(tf_saved["st"]["xh"].shape) != (Lc + 1, B, self.ldx):
+            raise ValueError(f"rollout: tf_saved must come from forward_tf along Y[:, :-1] with every length L={Lc}")
+        if noise_u is not None:
+            if tuple(noise_u.shape) != (Lc, rows, self.V) or noise_u.dtype != torch.float32:
+                raise ValueError(f"noise_u must be float32 [L={Lc}, rows={rows}, V={self.V}]")
+            noise_u = noise_u.contiguous()
+        dev = Y.device
+        self.prepare(params)
+        Y = Y.contiguous()
+        flen = torch.arange(1, Lc, device=dev, dtype=torch.int32).repeat_interleave(N * B)
+        act = _arr(C.c_int32, Lc, [min(t, Lc - 1) * N * B for t in range(Lc)])
+        ws = _aligned_ws(ws, self.rollout_ws_bytes(B, Lc, rows), dev)
+        ids = torch.empty(rows, Lc, device=dev, dtype=torch.int64)
+        st = tf_saved["st"]
+        L.check(L.load().gic_attn_rollout(
+            C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
+            ptr(st["fmap"]), ptr(Y), rows, ptr(flen), C.cast(act, C.c_void_p), ptr(noise_u), int(seed) & (2 ** 64 - 1), ptr(ws), ptr(ids),
+            stream_ptr()), "gic_attn_rollout")
+        return ids
+
     def alloc_bwd_ws(self, B: int, Lc: int, dev):
         f32 = torch.float32
         return {

@@ -401,6 +401,23 @@ class AttnDecoder(nn.Module):
             return pred, hc, alphas
         return pred, hc
 
+    def monte_carlo_rollouts(self, features, fmap, captions, num_rollouts, noise_u=None, seed=None):
+        """Monte-Carlo roll-outs of ``captions`` int64 [B, L] (gicap.h gic_attn_rollout), for a reward of the caller's own: for every
+        prefix length t = 1..L-1, ``num_rollouts`` completions of captions[:, :t] sampled from the decoder at temperature 1.  Returns
+        detached int64 [L-1, N, B, L]; [t-1, n, b] = roll-out n of caption b, which starts with captions[b, :t].  ``features`` [B, E],
+        ``fmap`` [B, P, C] as for ``sample``.  ``noise_u`` f32 [L, (L-1)*N*B, V] replaces the device draw (row (t-1)*N*B + n*B + b)."""
+        if fmap is None:
+            raise ValueError("the attention decoder needs the trunk's feature map: monte_carlo_rollouts(features, fmap, captions, n)")
+        B, Lc = captions.shape
+        eng = self.engine()
+        with torch.no_grad():
+            params = [p.detach() for p in self.param_list()]
+            saved = eng.forward_tf(params, features.detach().float(), fmap.detach(), captions[:, :-1], [Lc] * B, 1.0, pretrain=True,
+                                   keep_state=True)[3]
+            ids = eng.rollout(params, saved, captions, int(num_rollouts), noise_u=noise_u,
+                              seed=0 if noise_u is not None else (SEEDS.next() if seed is None else int(seed)))
+        return ids.view(Lc - 1, int(num_rollouts), B, Lc)
+
     def sample(self, features, fmap=None, states=None, pretrain=False, max_caption_len=34, noise_u=None):
         """(outputs [B,L,V], ids [B,L]) as Decoder.sample; ``fmap`` [B, P, C]: the trunk's last feature map (no gradient into it)."""
         if fmap is None:

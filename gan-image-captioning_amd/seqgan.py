@@ -13,6 +13,10 @@ Kernel sequence (all through libgicap.so; buffers from PyTorch's allocator):
   4. generator                   gic_decoder_sample_fwd along Y (logits, state kept) -> gic_xent with row weights = rewards (REINFORCE)
                                  -> gic_decoder_sample_bwd -> encoder head / start-token gradient -> clip + Adam
   5. discriminator               gic_disc_fwd / gic_disc_bwd on [real ; Y] ids in one batch, BCE (gic_gan_losses) -> clip + Adam
+--decoder attention (BASELINE config 4's decoder under this update): the same five phases with the attention decoder's calls --
+  1. gic_attn_sample_fwd (ids kept)   2. ONE gic_attn_rollout call: the roll-outs join at their prefix length from pass 4's state, rows
+  that share an image share its feature map (csrc/attn_rollout.hip)   4. gic_attn_forward_tf along Y (logits, state kept) -> gic_xent ->
+  gic_attn_forward_tf_bwd -> encoder head backward; 3. and 5. unchanged.  Definition: tests/attn_seqgan_oracle.py.
 Data parallel: D's and G's flat gradient arenas are all-reduced separately on the reducer's side stream (G's first: D's backward runs
 under it)."""
 from __future__ import annotations
@@ -33,6 +37,7 @@ class SeqGANStep:
         self.dec = gen.decoder.engine()
         self.den = disc.engine()
         self.N = int(getattr(args, "mc_rollouts", 16))
+        self.attn = getattr(args, "decoder", "lstm") == "attention"
         self._grads = None
 
     def bind_optimizers(self, gen_opt, disc_opt) -> "SeqGANStep":
@@ -51,15 +56,15 @@ class SeqGANStep:
                  u_mc: Optional[torch.Tensor] = None, keep_masks=None, opt_step: bool = True, next_images=None) -> dict:
         """One step.  ``u_sample`` [L,B,V] / ``u_mc`` [L,(L-1)*N*B,V] / ``keep_masks`` (2 x [B*R,F]: real, fake) make it deterministic
         (parity runs); otherwise noise is drawn on the device.  Returns device tensors: losses [g_loss, d_loss], ids (Y), rewards."""
-        gen, disc = self.gen, self.disc
+        if self.attn:
+            return self._attn_step(images, captions, int(max_caption_len), train, u_sample, u_mc, keep_masks, opt_step, next_images)
+        gen = self.gen
         B, L, N = captions.shape[0], int(max_caption_len), self.N
         dev = captions.device
         engine.require_gpu(captions, images)
         gparams = [p.detach() for p in gen.decoder.param_list()]
-        dparams = [p.detach() for p in disc.param_list()]
-        g_grads, d_grads = self._grad_lists()
-        dec, den = self.dec, self.den
-        R = den.R
+        g_grads = self._grad_lists()[0]
+        dec = self.dec
         if self.cgan:
             main = torch.cuda.current_stream(dev)
             start = main.record_event()
@@ -73,8 +78,8 @@ class SeqGANStep:
         _, Y, _ = dec.sample_fwd(gparams, feats, L, 1.0, noise_u=u_sample, seed=0 if u_sample is not None else SEEDS.next(), ids_only=True)
         # 4a. the generator's own pass along Y (logits; its recurrent state is kept: the roll-outs resume from it, the backward uses it)
         logits, _, st = dec.sample_fwd(gparams, feats, L, 1.0, pretrain=True, force_ids=Y)
-        # 2. + 3. roll-outs and rewards
-        mc_logits = None
+        # 2. roll-outs
+        mc_ids = None
         reps = (L - 1) * N
         if reps > 0:
             f_big = feats.repeat(reps, 1)
@@ -87,12 +92,32 @@ class SeqGANStep:
                 resume = (st, B, [min(t, L - 1) * N * B for t in range(L)])
             _, mc_ids, _ = dec.sample_fwd(gparams, f_big, L, 1.0, noise_u=u_mc, seed=0 if u_mc is not None else SEEDS.next(),
                                           ids_only=True, force_ids=force, force_len=flen, resume=resume)
+
+        def backward(dlog):
+            d_feat = torch.empty(B, dec.E, device=dev, dtype=torch.float32)
+            dec.sample_bwd(gparams, st, logits, Y, dlog.view(B, L, dec.V), 1.0, True, grads=g_grads + [d_feat])
+            if self.cgan:
+                gen.encoder.backward_fused(d_feat)
+            else:
+                engine.embedding_bwd(d_feat, ones, dec.V, d_weight=g_grads[0], zero_first=False)
+        return self._rewards_losses_updates(captions, Y, logits, mc_ids, L, train, keep_masks, opt_step, backward)
+
+    def _rewards_losses_updates(self, captions, Y, logits, mc_ids, L: int, train: bool, keep_masks, opt_step: bool, backward) -> dict:
+        """Phases 3, 4b and 5, shared by both decoders: rewards from D's scores of the roll-outs ``mc_ids`` and of Y, the REINFORCE loss on
+        ``logits`` along Y, D on [real ; Y]; ``backward(dlog)`` is the decoder's own backward into the generator arena."""
+        B, N = captions.shape[0], self.N
+        den = self.den
+        R = den.R
+        dparams = [p.detach() for p in self.disc.param_list()]
+        d_grads = self._grad_lists()[1]
+        mc_logits = None
+        if mc_ids is not None:
             mc_logits, _ = den.fwd(dparams, None, mc_ids, False, forward_only=True)     # rewards: no backward follows
         full_logits, _ = den.fwd(dparams, None, Y, False, forward_only=True)
         rewards = engine.rollout_rewards(mc_logits, full_logits, B, L, N, R)
         out = {"ids": Y, "rewards": rewards}
         # 4b. REINFORCE
-        g_loss, dlog = engine.xent(logits.view(B * L, dec.V), Y.reshape(-1), want_grad=train, row_weight=rewards.reshape(-1))
+        g_loss, dlog = engine.xent(logits.view(B * L, self.dec.V), Y.reshape(-1), want_grad=train, row_weight=rewards.reshape(-1))
         # 5. D on [real ; Y]
         km = keep_masks if keep_masks is not None else (None, None)
         both = torch.cat([captions, Y], 0)
@@ -104,12 +129,7 @@ class SeqGANStep:
         out["logits"] = logits
         if not train:
             return out
-        d_feat = torch.empty(B, dec.E, device=dev, dtype=torch.float32)
-        dec.sample_bwd(gparams, st, logits, Y, dlog.view(B, L, dec.V), 1.0, True, grads=g_grads + [d_feat])
-        if self.cgan:
-            gen.encoder.backward_fused(d_feat)
-        else:
-            engine.embedding_bwd(d_feat, ones, dec.V, d_weight=g_grads[0], zero_first=False)
+        backward(dlog)
         if self.reducer is not None:
             self.reducer.start(self.gen_arena.grad)
         den.bwd(dparams, dst, None, both, train, lgr["dd_real_fake"], True, False, grads=d_grads)
@@ -120,3 +140,36 @@ class SeqGANStep:
             self.disc_opt.step()
             self.gen_opt.step()
         return out
+
+    def _attn_step(self, images, captions, L: int, train: bool, u_sample, u_mc, keep_masks, opt_step: bool, next_images) -> dict:
+        """The step with the attention decoder (module docstring): the encoder always feeds it (features and the trunk's feature map);
+        its head is trained under --conditional-gan 1."""
+        gen = self.gen
+        B, N = captions.shape[0], self.N
+        dev = captions.device
+        engine.require_gpu(captions, images)
+        gparams = [p.detach() for p in gen.decoder.param_list()]
+        g_grads = self._grad_lists()[0]
+        dec = self.dec
+        main = torch.cuda.current_stream(dev)
+        start = main.record_event()
+        trunk, fmap = gen.encoder.take_trunk_with_map(images, train, main)
+        feats = gen.encoder.forward_fused(images, train, trunk_feats=trunk)
+        if next_images is not None:              # the frozen trunk's pass for the next batch runs under this step (generator.Encoder)
+            gen.encoder.prefetch_trunk(next_images, train, start, want_map=True)
+        fmap = fmap.view(B, -1, fmap.shape[-1])
+        # 1. Y ~ G
+        _, Y, _ = dec.sample_fwd(gparams, feats, fmap, L, 1.0, noise_u=u_sample, seed=0 if u_sample is not None else SEEDS.next())
+        # 4a. the generator's own pass along Y, teacher-forced (logits; the roll-outs resume from its state, the backward uses it)
+        logits, _, _, saved = dec.forward_tf(gparams, feats, fmap, Y[:, :-1], [L] * B, 1.0, pretrain=True, keep_state=True)
+        # 2. roll-outs
+        mc_ids = None
+        if (L - 1) * N > 0:
+            mc_ids = dec.rollout(gparams, saved, Y, N, noise_u=u_mc, seed=0 if u_mc is not None else SEEDS.next())
+
+        def backward(dlog):
+            d_feat = torch.empty(B, dec.E, device=dev, dtype=torch.float32)
+            dec.forward_tf_bwd(gparams, saved, logits, dlog.view(B, L, dec.V), 1.0, True, grads=g_grads + [d_feat])
+            if self.cgan:
+                gen.encoder.backward_fused(d_feat)
+        return self._rewards_losses_updates(captions, Y, logits, mc_ids, L, train, keep_masks, opt_step, backward)

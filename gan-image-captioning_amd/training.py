@@ -89,15 +89,22 @@ def scst_reward_scorer(args, corpus):
     return RewardMix(cider, overlap, *w)
 
 
+def check_modes(args):
+    """The instructor's checks of the mode flags, before anything touches the device: (pretrain_mode, attn_reg).  Either decoder
+    (--decoder lstm | attention) trains with either adversarial update (--adv-mode relgan | seqgan)."""
+    pretrain_mode = getattr(args, "pretrain_mode", "sample")
+    attn_reg = float(getattr(args, "attn_reg", 0.0))
+    if pretrain_mode not in ("sample", "teacher"):
+        raise ValueError(f"--pretrain-mode must be sample or teacher, got {pretrain_mode!r}")
+    if attn_reg != 0.0 and not (getattr(args, "decoder", "lstm") == "attention" and pretrain_mode == "teacher"):
+        raise ValueError("--attn-reg applies to --decoder attention --pretrain-mode teacher only")
+    return pretrain_mode, attn_reg
+
+
 class GANInstructor:
     def __init__(self, args, train_dataset, dev_dataset):
         self.args = args
-        self.pretrain_mode = getattr(args, "pretrain_mode", "sample")
-        self.attn_reg = float(getattr(args, "attn_reg", 0.0))
-        if self.pretrain_mode not in ("sample", "teacher"):
-            raise ValueError(f"--pretrain-mode must be sample or teacher, got {self.pretrain_mode!r}")
-        if self.attn_reg != 0.0 and not (getattr(args, "decoder", "lstm") == "attention" and self.pretrain_mode == "teacher"):
-            raise ValueError("--attn-reg applies to --decoder attention --pretrain-mode teacher only")
+        self.pretrain_mode, self.attn_reg = check_modes(args)
         self.dist = parallel.DistInfo.from_env()
         from .generator import SEEDS
         SEEDS.rank = self.dist.rank            # replicas share weights and the torch seed, not the device noise streams
@@ -105,9 +112,6 @@ class GANInstructor:
         self.disc = Discriminator(args).to(args.device)                   # training.py:20
         self.cgan = (args.conditional_gan == 1)
         self.attention = getattr(args, "decoder", "lstm") == "attention"
-        if self.attention:
-            if getattr(args, "adv_mode", "relgan") != "relgan":
-                raise ValueError("--decoder attention is trained with the relaxation (--adv-mode relgan)")
         if int(getattr(args, "deterministic", 0)):
             engine.set_deterministic(True)
         if self.attention and engine.deterministic():

@@ -518,6 +518,25 @@ int gic_attn_forward_tf_bwd(const gic_attn_dims* dims, const gic_attn_params* pa
                             const int32_t* lengths, int Tmax, const void* d_pred, const float* d_alphas, float temperature, int pretrain,
                             const gic_attn_grads* grads, void* stream);
 
+/* Monte-Carlo roll-outs of the attention decoder (the SeqGAN step's): the counterpart of gic_decoder_sample_fwd with force_ids,
+ * force_len, no_state and resume_from.  dims->B = images, dims->L = caption length.  `rows` roll-out rows, row r of image r % B: it
+ * copies force_ids[r % B, :force_len[r]] (force_ids int64 [B, L], the captions; force_len int32 [rows], ascending, each 1..L-1), joins
+ * at step t = force_len[r] from the recurrent state resume_from reached there -- the state of a gic_attn_forward_tf call along the
+ * captions with T = L and every length L (its xh, c and fproj are read) -- and from then on samples with Gumbel-max at temperature 1:
+ * argmax(o + b_out + gumbel(u)), the first maximal index.  host_active_rows: L host ints, [t] = the number of rows with force_len <= t
+ * ([0] == 0, non-decreasing, <= rows): at step t the first host_active_rows[t] rows run.  fmap act [B, P, C].  noise_u f32
+ * [L, rows, V] or NULL = Philox(seed, stream t) indexed as gic_decoder_sample_fwd indexes it.  ids int64 [rows, L] (entries a row
+ * never reaches are 0).  ws: gic_attn_rollout_ws_bytes bytes, 256-byte aligned; it is affine in rows and holds nothing per (row,
+ * position, channel): the image data is read from fproj / fmap, once per image.  The launch count per step does not depend on the
+ * rows.  Every argument check (the limits of gic_attn_sample_fwd; L 2..1024; rows 1..2^22 with rows * (E+C+H) below 2^30 and rows * 4H below 2^31)
+ * runs before any launch and returns GIC_STATUS_INVALID_ARG.  No f32 atomics and no split-K (the fused vocabulary product's integer
+ * atomicMax is order-independent): two calls give the same bits, and the deterministic mode accepts the call. */
+int gic_attn_rollout_ws_bytes(const gic_attn_dims* dims, int64_t rows, uint64_t* out);      /* host-only: no GPU needed */
+int gic_attn_rollout(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                     const gic_attn_state* resume_from, const void* fmap, const int64_t* force_ids, int64_t rows,
+                     const int32_t* force_len, const int32_t* host_active_rows, const float* noise_u, uint64_t seed, void* ws,
+                     int64_t* ids, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Discriminator.forward (src/discriminator.py:34-62) forward + backward.
  */
