@@ -982,6 +982,32 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
     STAMP(5);
     return;
   }
+  // bf16 C += result: straight from the f32 accumulators, rounded ONCE as gemm_kernel does.  (The staged tile below holds the product
+  // already rounded to bf16: adding C to that rounds twice and lands up to a whole bf16 ulp from the correctly rounded sum.)  Plain
+  // products only: no convolution entry point sets `accumulate` (conv_base declines it), so the staged loop's accumulate branch is
+  // live for f32 C alone, where the staged value is unrounded.
+  if constexpr (EPI == EPI_PLAIN && !CONV && sizeof(TO) == 2) {
+    if (d.accumulate) {
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const int n = bn0 + wc * (BN / 2) + j * 16 + lr;
+        if (n >= N) continue;
+        const float bias = d.bias ? d.bias[n] : 0.f;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int m = bm0 + wr * 32 + i * 16 + lg * 4 + r;
+            if (m >= M) continue;
+            const long o = (long)m * d.ldc + n;
+            C[o] = from_f32<TO>(d.alpha * acc[i][j][r] + bias + to_f32<TO>(C[o]));
+          }
+        }
+      }
+      STAMP(5);
+      return;
+    }
+  }
   // ---- epilogue: C tile through LDS (16-byte row stores), BatchNorm column sums folded across the block
   unsigned char* sC = smem;
   float* sStat = (float*)(smem + BM * SC);                   // [8 waves][BN/2][2]
@@ -1031,7 +1057,7 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
     const int m = bm0 + ml, n = bn0 + cc * OVE;
     if (m < M && n < N) {
       u32x4 v = *(const u32x4*)(sC + ml * SC + cc * 16);
-      if (d.accumulate) {                                    // C += result (f32 gradients accumulated across passes)
+      if (d.accumulate) {                                    // f32 C += result (gradients accumulated across passes); bf16: see above
         const u32x4 o = *(const u32x4*)(C + (long)m * d.ldc + n);
         TO* pv = (TO*)&v;
         const TO* po = (const TO*)&o;
@@ -1063,8 +1089,8 @@ struct Plan {
 bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
-// The 8-wave kernel qualifies: bf16 k-contiguous operands under 2 GiB each, a plain / BatchNorm-sum epilogue that overwrites a 16-byte-aligned
-// C (or the highway epilogue).  false: fall back to gemm_kernel.
+// The 8-wave kernel qualifies: bf16 k-contiguous operands under 2 GiB each, a plain (overwrite or accumulate, f32 or bf16 C) / BatchNorm-sum
+// epilogue onto a 16-byte-aligned C whose N and ldc are whole 16-byte chunks (or the highway epilogue).  false: fall back to gemm_kernel.
 bool select_tile8(const GemmDesc& d, Tile8Plan& p, int& n_fast) {
   static const bool off = getenv("GIC_NO_TILE8") != nullptr;
   static const int big_min = env_int("GIC_TILE8_BIG_MIN", 160), ns2_tiles = env_int("GIC_TILE8_NS2_TILES", 256), min_nk = env_int("GIC_TILE8_MIN_NK", 1);
@@ -1157,8 +1183,9 @@ void select_gemm4(const GemmDesc& d, bool vec, Gemm4Plan& p) {
     // splits, or two onto a C being accumulated into, do not
     if (det_mode()) splits = (d.accumulate || splits < 2) ? 1 : 2;
   }
-  p.per = cdiv(nk, splits);
-  p.splits = cdiv(nk, p.per);
+  // K = 0 (the empty sum, C = bias (+ C)): one split of no K tiles, the kernel's K loop does not run and its epilogue writes C
+  p.per = nk ? cdiv(nk, splits) : 1;
+  p.splits = nk ? cdiv(nk, p.per) : 1;
   p.zero_grid = 0;
   if (p.splits > 1 && !d.accumulate && !d.c_zeroed) {
     const long total = (long)d.M * d.N;

@@ -76,6 +76,8 @@ int gic_step_scalars_set(gic_step_scalars* dev, const gic_step_scalars* host_val
  * Generic dense contraction (used by the tests and by every entry point below).
  *   C[m,n] = alpha * sum_k A(m,k) B(n,k) + bias[n]  (+ C if accumulate)
  *   A(m,k) = a_kc ? A[m*lda+k] : A[k*lda+m];  B(n,k) = b_kc ? B[n*ldb+k] : B[k*ldb+n]
+ * M = 0 or N = 0: GIC_OK, nothing is done.  K = 0: the sum is empty, C = bias (+ C if accumulate) (0 where bias is NULL); A and B
+ * must be non-NULL but are never read.
  * Replaces the ATen GEMMs behind nn.Linear / nn.LSTM / autograd (generator.py:61,68;
  * discriminator.py:40,53,58,60).
  */
