@@ -11,6 +11,7 @@
 #include "conv1x1_panel.h"
 #include "bn_fold.h"
 #include "conv_device.h"
+#include "gemm_device.h"
 
 namespace gic {
 namespace {
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(512) void conv1x1_panel_kernel(const PanelDesc d) {
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)d.A, 0, (int)d.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)d.B, 0, (int)d.b_bytes, 0x00020000);
   const int wbase = (tid & ~63) * 16;
-  const int kc = ((tid & 7) ^ ((tid >> 4) & 7)) * 8;                    // this thread's 8 channels inside every 64-channel K tile
+  const int kc = swz_dma_chunk(tid) * 8;                                // this thread's 8 channels inside every 64-channel K tile
 
   // ---- prologue: the A panel (piece i: K tile i / 2, rows (tid >> 3) + 64 (i & 1)), the first weight tile
 #pragma unroll
@@ -115,17 +116,14 @@ __global__ __launch_bounds__(512) void conv1x1_panel_kernel(const PanelDesc d) {
 #pragma unroll
         for (int t = 0; t < TM; ++t) {
           const int row = wr * 32 + t * 16 + lr;
-          fa[t] = *(const bf16x8*)(smem + kt * (BM * 128) + row * 128 + (((ks * 4 + lg) ^ ((row >> 1) & 7)) << 4));
+          fa[t] = *(const bf16x8*)(smem + kt * (BM * 128) + row * 128 + swz_chunk(row, ks * 4 + lg));
         }
 #pragma unroll
         for (int t = 0; t < TN; ++t) {
           const int row = wc * (BN / 2) + t * 16 + lr;
-          fb[t] = *(const bf16x8*)(sW + kt * (BN * 128) + row * 128 + (((ks * 4 + lg) ^ ((row >> 1) & 7)) << 4));
+          fb[t] = *(const bf16x8*)(sW + kt * (BN * 128) + row * 128 + swz_chunk(row, ks * 4 + lg));
         }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+        mfma_block(acc, fa, fb);
       }
     }
     // C tile through LDS, BatchNorm column sums folded across the workgroup (as tile8)

@@ -14,6 +14,7 @@
 #include "conv1x1_stream.h"
 #include "bn_fold.h"
 #include "conv_device.h"
+#include "gemm_device.h"
 
 namespace gic {
 namespace {
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(512) void conv1x1_stream_kernel(const StreamDesc d)
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)d.B, 0, (int)d.b_bytes, 0x00020000);
   const int wbase = (tid & ~63) * 16;
   // piece i of a tile: K tile i / 2 (A) , rows (tid >> 3) + 64 (i & 1), physical slot tid & 7 = logical 16-byte chunk ^ ((row >> 1) & 7)
-  const int kc = ((tid & 7) ^ ((tid >> 4) & 7)) * 8;                    // this thread's 8 channels inside every 64-channel K tile
+  const int kc = swz_dma_chunk(tid) * 8;                                // this thread's 8 channels inside every 64-channel K tile
   auto issue_a = [&](const int tile, const int st) {
     const int bm0 = tile * BM;
 #pragma unroll
@@ -170,17 +171,14 @@ __global__ __launch_bounds__(512) void conv1x1_stream_kernel(const StreamDesc d)
 #pragma unroll
         for (int t = 0; t < TM; ++t) {
           const int row = wr * 32 + t * 16 + lr;
-          fa[t] = *(const bf16x8*)(sA + kt * (BM * 128) + row * 128 + (((ks * 4 + lg) ^ ((row >> 1) & 7)) << 4));
+          fa[t] = *(const bf16x8*)(sA + kt * (BM * 128) + row * 128 + swz_chunk(row, ks * 4 + lg));
         }
 #pragma unroll
         for (int t = 0; t < TN; ++t) {
           const int row = wc * (BN / 2) + t * 16 + lr;
-          fb[t] = *(const bf16x8*)(sW + kt * (BN * 128) + row * 128 + (((ks * 4 + lg) ^ ((row >> 1) & 7)) << 4));
+          fb[t] = *(const bf16x8*)(sW + kt * (BN * 128) + row * 128 + swz_chunk(row, ks * 4 + lg));
         }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+        mfma_block(acc, fa, fb);
       }
     }
     // C tile -> LDS, column sums into the registers that live across tiles

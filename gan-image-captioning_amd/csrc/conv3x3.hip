@@ -25,6 +25,7 @@
 #include "conv3x3.h"
 #include "bn_fold.h"
 #include "conv_device.h"
+#include "gemm_device.h"
 
 namespace gic {
 #ifdef GIC_STAMPS
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const PatchDesc d) {
   int poff[P];              // element offset of (pixel, chunk 0 channels of the piece) in the input, or -1: zero (halo / past the patch)
   {
     // pixel of piece i = (tid >> 3) + 64 i: (slot, column) and (image, padded row) advance by constants, one division each up front
-    const int c16 = (tid & 7) ^ ((tid >> 4) & 7);                       // (q & 7) ^ ((pp >> 1) & 7): the same for all of a thread's pieces
+    const int c16 = swz_dma_chunk(tid);                                 // (q & 7) ^ ((pp >> 1) & 7): the same for all of a thread's pieces
     const int dslot = fdiv(64, PW, iPW), dcol = 64 - dslot * PW;
     int pp = tid >> 3;
     int slot = fdiv(pp, PW, iPW), col = pp - slot * PW;
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const PatchDesc d) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void_ptr)(smem + buf * PATCH + i * (NT * 16) + wbase), 16, (int)voff, 0, 0, GIC_TRUNK_NT);
   };
   // ---- weight tile of one K step (tap, chunk): rows (tid >> 3) + 64 i of the BN output channels, 64 channels = 128 bytes each
-  const int kc = ((tid & 7) ^ ((tid >> 4) & 7)) * 8;
+  const int kc = swz_dma_chunk(tid) * 8;
   int b_off[CB];
 #pragma unroll
   for (int i = 0; i < CB; ++i) {
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const PatchDesc d) {
   auto normalise = [&](const int chunk, const int buf) {
     if constexpr (ABN) {
       // a thread's pieces all hold the same 8 channels of the chunk: q & 7 and (q >> 4) & 7 do not change with q += 512
-      const int c16 = (tid & 7) ^ ((tid >> 4) & 7);
+      const int c16 = swz_dma_chunk(tid);
       float scl[8], sft[8];
       bn_unpack8(coef + 2 * (chunk * 64 + c16 * 8), scl, sft);
       bf16x8 v[P];
@@ -227,21 +228,15 @@ __global__ __launch_bounds__(512) void conv3x3_patch_kernel(const PatchDesc d) {
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
       const int pp = pbase[t] + tapoff;
-      fa[t] = *(const bf16x8*)(patch + pp * 128 + (((ks * 4 + lg) ^ ((pp >> 1) & 7)) << 4));
+      fa[t] = *(const bf16x8*)(patch + pp * 128 + swz_chunk(pp, ks * 4 + lg));
     }
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
       const int row = wc * (BN / 2) + t * 16 + lr;
-      fb[t] = *(const bf16x8*)(sB + row * 128 + (((ks * 4 + lg) ^ ((row >> 1) & 7)) << 4));
+      fb[t] = *(const bf16x8*)(sB + row * 128 + swz_chunk(row, ks * 4 + lg));
     }
   };
-  auto mfma_half = [&](const bf16x8 (&fa)[TM], const bf16x8 (&fb)[TN]) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-  };
+  auto mfma_half = [&](const bf16x8 (&fa)[TM], const bf16x8 (&fb)[TN]) { mfma_block(acc, fa, fb); };
 
   // ---- K loop: chunk (64 channels) x tap (9, unrolled: ring stage = tap % 3 and every wait count is a constant).  Per step:
   //     wait (weight tile of this step) | barrier | read half 0 | mfma half 1 of the previous step | DMA: one patch piece of the

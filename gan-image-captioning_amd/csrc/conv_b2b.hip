@@ -24,6 +24,7 @@
 #include "conv_b2b.h"
 #include "bn_fold.h"
 #include "conv_device.h"
+#include "gemm_device.h"
 
 namespace gic {
 namespace {
@@ -256,7 +257,7 @@ __global__ __launch_bounds__(512) void conv_b2b_kernel(const B2bDesc d) {
 #pragma unroll
           for (int jb = 0; jb < 4; ++jb) {
             const int L = 64 * g + 16 * jb + lr, kp = lg * 2 + ks;       // 16-byte piece of the row: channels 16 lg + 8 ks .. + 7
-            const bf16x8 fw = *(const bf16x8*)(sW1 + L * 128 + ((kp ^ ((L >> 1) & 7)) << 4));
+            const bf16x8 fw = *(const bf16x8*)(sW1 + L * 128 + swz_chunk(L, kp));
             acc2[g][jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw, a2[ks], acc2[g][jb], 0, 0, 0);
           }
       }

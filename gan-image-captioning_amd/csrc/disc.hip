@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include "../../include/gicap.h"
 #include "kernels.h"
+#include "gemm_device.h"
 
 namespace gic {
 namespace {
@@ -704,10 +705,28 @@ int disc_head_fwd(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow
   return GIC_OK;
 }
 
+// highway + dropout (fused epilogue): st->pooled -> st->hpre, st->keep, st->ydrop
+int disc_highway_fwd(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S, const gic_disc_state* st, int train,
+                     const uint8_t* keep_mask, uint64_t seed, const uint64_t* seed_dev, hipStream_t stream) {
+  GemmDesc g;
+  g.A = st->pooled; g.lda = c.Fp; g.B = S->hw_w; g.ldb = c.Fp; g.C = st->ydrop; g.ldc = c.Fp;
+  g.M = (int)c.rowsBR; g.N = c.F; g.K = c.Fp; g.in_dtype = c.dt; g.out_dtype = c.dt; g.bias = P->hw_b;
+  g.epi = EPI_HIGHWAY; g.X = st->pooled; g.ldx = c.Fp; g.Hpre = st->hpre; g.ldh = c.Fp;
+  if (train) {
+    g.keep_scale = c.keep_scale(1);        // nn.Dropout(p), discriminator.py:10,30
+    g.drop_p = c.drop_p;
+    if (keep_mask) { g.mask = keep_mask; g.ldmask = c.F; } else { g.use_philox = 1; g.seed = seed; g.seed_dev = seed_dev; g.stream = 0x44495343ull; }
+    g.mask_out = st->keep; g.ldmask_out = c.Fp;
+  }
+  return gemm(g, stream);
+}
+
 template <typename TA>
 int disc_fwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S, const gic_disc_state* st,
                const void* inp_soft, long ld_inp, const int64_t* inp_ids, int train, const uint8_t* keep_mask,
                uint64_t seed, const uint64_t* seed_dev, float* logits, hipStream_t stream) {
+  // route-only mode (gemm.h): the selection of the highway product, the one product of this pass with an epilogue of its own; nothing is launched
+  if (route_only()) return disc_highway_fwd(c, P, S, st, train, keep_mask, seed, seed_dev, stream);
   // 1. embedding
   if (inp_ids) {
     hipLaunchKernelGGL(disc_emb_gather_kernel, dim3(grid1d(c.rowsBL * c.De)), dim3(256), 0, stream, P->emb, inp_ids, st->emb,
@@ -738,25 +757,13 @@ int disc_fwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
     hipLaunchKernelGGL((disc_conv_pool_fwd_kernel<TA, kMaxTaps>), dim3((unsigned)c.rowsBR), dim3(256), c.L * c.s * sizeof(float), stream,
                        (const float*)st->emb, c.cm, c.L, c.De, c.R, (TA*)st->pooled, st->argmax);
   GIC_CHECK_LAUNCH("disc_conv_pool_fwd");
-  // 3. highway + dropout (fused epilogue)
-  {
-    GemmDesc g;
-    g.A = st->pooled; g.lda = c.Fp; g.B = S->hw_w; g.ldb = c.Fp; g.C = st->ydrop; g.ldc = c.Fp;
-    g.M = (int)c.rowsBR; g.N = c.F; g.K = c.Fp; g.in_dtype = c.dt; g.out_dtype = c.dt; g.bias = P->hw_b;
-    g.epi = EPI_HIGHWAY; g.X = st->pooled; g.ldx = c.Fp; g.Hpre = st->hpre; g.ldh = c.Fp;
-    if (train) {
-      g.keep_scale = c.keep_scale(1);        // nn.Dropout(p), discriminator.py:10,30
-      g.drop_p = c.drop_p;
-      if (keep_mask) { g.mask = keep_mask; g.ldmask = c.F; } else { g.use_philox = 1; g.seed = seed; g.seed_dev = seed_dev; g.stream = 0x44495343ull; }
-      g.mask_out = st->keep; g.ldmask_out = c.Fp;
-    }
-    GIC_PROPAGATE(gemm(g, stream));
-  }
+  // 3. highway + dropout
+  GIC_PROPAGATE(disc_highway_fwd(c, P, S, st, train, keep_mask, seed, seed_dev, stream));
   return disc_head_fwd(c, P, S, st, logits, stream);
 }
 
 // The same highway output under ANOTHER dropout draw, from the saved pre-activation h and carry x (no GEMM):
-// y = sig(h) relu(h) + (1 - sig(h)) x, exactly the EPI_HIGHWAY epilogue incl. its Philox indexing (4 rows per draw).
+// the EPI_HIGHWAY epilogue's own gate and keep draw (gemm_device.h: 4 rows per Philox call).
 template <typename TA>
 __global__ void disc_highway_redrop_kernel(const float* __restrict__ hpre, const TA* __restrict__ pooled,
                                            const uint8_t* __restrict__ mask, int train, uint64_t seed_val, const uint64_t* __restrict__ seed_dev, float drop_p,
@@ -768,22 +775,13 @@ __global__ void disc_highway_redrop_kernel(const float* __restrict__ hpre, const
     const long m4 = i / F;
     const int n = (int)(i % F);
     float keep4[4] = {1.f, 1.f, 1.f, 1.f};
-    if (train && !mask) {
-      uint32_t r0, r1, r2, r3;
-      Philox::gen4(seed, 0x44495343ull, (uint64_t)m4 * (uint64_t)F + (uint64_t)n, r0, r1, r2, r3);
-      keep4[0] = Philox::u01(r0) >= drop_p ? 1.f : 0.f;
-      keep4[1] = Philox::u01(r1) >= drop_p ? 1.f : 0.f;
-      keep4[2] = Philox::u01(r2) >= drop_p ? 1.f : 0.f;
-      keep4[3] = Philox::u01(r3) >= drop_p ? 1.f : 0.f;
-    }
+    if (train && !mask) highway_keep4(seed, 0x44495343ull, (uint64_t)m4, F, n, drop_p, keep4);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const long m = m4 * 4 + r;
       if (m >= rows) break;
       const float h = hpre[m * Fp + n];
-      const float x = to_f32<TA>(pooled[m * Fp + n]);
-      const float sg = 1.f / (1.f + expf(-h));
-      const float y = sg * fmaxf(h, 0.f) + (1.f - sg) * x;
+      const float y = highway_gate(h, to_f32<TA>(pooled[m * Fp + n]));
       float keep = keep4[r];
       if (train && mask) keep = (float)mask[m * F + n];
       if (keep_out) keep_out[m * Fp + n] = (uint8_t)keep;

@@ -104,7 +104,8 @@ inline bool bn_in_args_ok(const GemmDesc& d) { return d.in_gamma && d.in_beta &&
 bool conv_base(const GemmDesc& d, long a_elems, long b_elems, ConvBase& b);
 
 // Route-only mode (gic_debug_route_only, util.hip): gemm(), gemm_gumbelmax() and gic_conv_b2b validate and select, write the plan as one
-// line into route_line() and return their status without touching the GPU.
+// line into route_line() and return their status without touching the GPU.  gic_disc_fwd (disc.hip) answers with the selection of its
+// highway product, the one caller of EPI_HIGHWAY, and launches none of its own kernels.
 bool route_only();
 char* route_line();                    // thread-local, kRouteLen bytes
 constexpr int kRouteLen = 160;

@@ -8,9 +8,14 @@
 //                 parity mode), register-staged double buffer or 3-stage LDS-DMA ring, split-K over gridDim.y (f32 atomics)
 //                 for skinny / deep-K products, highway epilogue, 16-byte accesses when shapes allow, scalar fallback.
 //   tile8_kernel  8 waves (4x2), 128x128 or 128x64 tile, bf16 k-contiguous operands only: buffer-descriptor LDS-DMA ring of 1 /
-//                 2 / 4 stages.  Every trunk convolution in bf16 mode and the wide plain / highway products.  See its header.
-// Both: XCD-aware block -> tile map (each of the 8 XCDs owns a contiguous run of tiles that share B panels in its L2), C tile
-// staged through LDS for 16-byte row stores, BatchNorm column sums folded across the block in the epilogue.
+//                 2 / 4 stages.  Every trunk convolution in bf16 mode and the wide plain / highway products (highway: row-padded
+//                 bf16 buffers only, select_tile8's highway_wide; every other highway product is gemm_kernel's).  See its header.
+// Both: XCD-aware block -> tile map (xcd_run: each of the 8 XCDs owns a contiguous run of tiles that share B panels in its L2), C
+// tile staged through LDS for 16-byte row stores, BatchNorm column sums folded across the block in the epilogue.
+// What the two share with each other and with the dynamic-LDS convolution kernels is in gemm_device.h (the LDS swizzle, the MFMA
+// block, the highway gate and keep draw, the convolution addressing); gemm_kernel's LDS image of an operand (its stores and fragment
+// reads) is written once (g4_*) and applied to A and to B.  The staged-C epilogues, gemm_kernel's `gload` and tile8's whole-tile `compute`
+// are each kernel's own text: DESIGN.md section 4.
 #include "gemm.h"
 #include "conv3x3.h"
 #include "conv1x1_stream.h"
@@ -18,6 +23,7 @@
 #include "conv1x1_pix.h"
 #include "conv_stem.h"
 #include "bn_fold.h"
+#include "gemm_device.h"
 #include "kernels.h"
 
 #include <stdlib.h>
@@ -46,6 +52,74 @@ namespace {
 #endif
 
 template <typename T> struct GlobalPtr { typedef const __attribute__((address_space(1))) T* type; };
+
+// ---- gemm_kernel's handling of ONE operand of a K tile, applied to A (rows m, BR = BM) and to B (rows n, BR = BN).  KC: k-contiguous
+// (LDS image [row][k]) or row-contiguous ([k][row]); S: the LDS row stride in bytes; 256 threads, chunk c = tid + 256 i.
+// Arguments, in this order wherever they occur: the LDS image; the operand (P, ld); its rows (row0 = the tile's first, R = the operand's
+// count); the K tile (k0 = its first k, K = the operand's depth); the thread (tid, or lr = lane & 15, lg = lane >> 4).
+// registers -> LDS image
+template <typename TI, bool KC, int BR, int S, int NC>
+__device__ __forceinline__ void g4_store(unsigned char* img, const u32x4 (&reg)[NC], const int tid) {
+#pragma unroll
+  for (int i = 0; i < NC; ++i) {
+    const int c = tid + i * 256;
+    if constexpr (KC) {
+      *(u32x4*)(img + (c >> 3) * S + (c & 7) * 16) = reg[i];
+    } else {
+      constexpr int CPR = BR / (16 / (int)sizeof(TI));
+      *(u32x4*)(img + (c / CPR) * S + (c % CPR) * 16) = reg[i];
+    }
+  }
+}
+// global -> LDS image, element by element (scalar fallback: unaligned operands)
+template <typename TI, bool KC, int BR, int S>
+__device__ __forceinline__ void g4_store_scalar(unsigned char* img, const typename GlobalPtr<TI>::type P, const long ld, const int row0,
+                                                const int R, const int k0, const int K, const int tid) {
+  constexpr int SZ = sizeof(TI), BK = 128 / SZ;
+  for (int e = tid; e < BR * BK; e += 256) {
+    TI v = (TI)0.f;
+    if constexpr (KC) {
+      const int row = e / BK, kk = e % BK;
+      const int r = row0 + row, k = k0 + kk;
+      if (r < R && k < K) v = P[(long)r * ld + k];
+      *(TI*)(img + row * S + kk * SZ) = v;
+    } else {
+      const int kk = e / BR, row = e % BR;
+      const int r = row0 + row, k = k0 + kk;
+      if (r < R && k < K) v = P[(long)k * ld + r];
+      *(TI*)(img + kk * S + row * SZ) = v;
+    }
+  }
+}
+// LDS image -> the bf16 fragment of rows r0 .. r0 + 15 for the 32-deep K step ks
+template <bool KC, bool PIPE, int S>
+__device__ __forceinline__ bf16x8 g4_frag_bf16(const unsigned char* img, const int r0, const int ks, const int lr, const int lg) {
+  if constexpr (PIPE) {
+    return *(const bf16x8*)(img + (r0 + lr) * 128 + swz_chunk(r0 + lr, ks * 4 + lg));
+  } else if constexpr (KC) {
+    return *(const bf16x8*)(img + (r0 + lr) * S + ks * 64 + lg * 16);
+  } else {
+    // [k][row] image: lane (q=lr>>2, p=lr&3) addresses row k0+q, cols 4p..4p+3; receives column lr
+    const unsigned char* p0 = img + (ks * 32 + lg * 8 + (lr >> 2)) * S + (r0 + 4 * (lr & 3)) * 2;
+    const bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)p0);
+    const bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p0 + 4 * S));
+    return __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
+  }
+}
+// ... and the f32 one: lane group lg owns k = 8*lg .. 8*lg+7 of the 32-wide tile
+template <bool KC, bool PIPE, int S>
+__device__ __forceinline__ void g4_frag_f32(float (&f)[8], const unsigned char* img, const int r0, const int lr, const int lg) {
+  if constexpr (KC) {
+    const int row = r0 + lr;
+    const float4 v0 = *(const float4*)(img + row * S + (PIPE ? swz_chunk(row, 2 * lg) : 2 * lg * 16));
+    const float4 v1 = *(const float4*)(img + row * S + (PIPE ? swz_chunk(row, 2 * lg + 1) : (2 * lg + 1) * 16));
+    f[0] = v0.x; f[1] = v0.y; f[2] = v0.z; f[3] = v0.w;
+    f[4] = v1.x; f[5] = v1.y; f[6] = v1.z; f[7] = v1.w;
+  } else {
+#pragma unroll
+    for (int s = 0; s < 8; ++s) f[s] = *(const float*)(img + (lg * 8 + s) * S + (r0 + lr) * 4);
+  }
+}
 
 // PIPE (k-contiguous, vectorised operands only): tiles reach LDS by LDS-DMA (global_load_lds, 16 B per lane, no VGPR
 // staging) into a 3-stage ring; the loads of tile k+2 are in flight under the MFMAs of tiles k and k+1 behind a COUNTED
@@ -81,12 +155,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
 
   // ---- XCD-aware tile assignment (bijective remap; blocks b and b+8 share an XCD)
   const int tiles_m = (d.M + BM - 1) / BM;
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-  }
+  const int bid = xcd_run(blockIdx.x, gridDim.x);
   const int bm0 = (bid % tiles_m) * BM;
   const int bn0 = (bid / tiles_m) * BN;
 
@@ -112,16 +181,12 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
 #pragma unroll
     for (int i = 0; i < CA; ++i) {
       const int m = bm0 + ((tid + i * 256) >> 3);
-      const int mm = m < M ? m : 0;
-      const int wo = mm % d.cWo, t = mm / d.cWo;
-      const int ho = t % d.cHo, n = t / d.cHo;
-      cv_hi0[i] = m < M ? ho * d.cStride - d.cPad : -(1 << 28);      // rows past M never validate
-      cv_wi0[i] = wo * d.cStride - d.cPad;
-      cv_base[i] = ((long)n * d.cH + cv_hi0[i]) * d.cW + cv_wi0[i];
+      const ConvOrigin<long> o = conv_origin<long>(m, m < M, d.cHo, d.cWo, d.cH, d.cW, d.cStride, d.cPad);
+      cv_hi0[i] = o.hi0; cv_wi0[i] = o.wi0; cv_base[i] = o.pix;
     }
     // PIPE: physical chunk slot tid&7 holds logical chunk (tid&7) ^ swizzle(row); the swizzle (row>>1)&7 is the same
     // for all of a thread's rows (they are 32 apart), so the thread still owns ONE k chunk per tile.
-    const int kchunk = PIPE ? ((tid & 7) ^ ((tid >> 4) & 7)) : (tid & 7);
+    const int kchunk = PIPE ? swz_dma_chunk(tid) : (tid & 7);
     const int k = blockIdx.y * k_tiles_per_split * BK + kchunk * VE;
     cv_c = k % d.cCin;
     const int t = k / d.cCin;
@@ -134,21 +199,27 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
   auto gload = [&](int kt) {
     if constexpr (VEC) {
       const int k0 = kt * BK;
+      if constexpr (CONV) {
 #pragma unroll
-      for (int i = 0; i < CA; ++i) {
-        const int c = tid + i * 256;
-        ra[i] = (u32x4){0u, 0u, 0u, 0u};
-        if constexpr (CONV) {
+        for (int i = 0; i < CA; ++i) {
+          ra[i] = (u32x4){0u, 0u, 0u, 0u};
           const int hi = cv_hi0[i] + cv_r, wi = cv_wi0[i] + cv_s;
           if (cv_r < d.cKH && hi >= 0 && hi < d.cH && wi >= 0 && wi < d.cW)
             ra[i] = *(gptr_u4)(A + (cv_base[i] + (long)cv_r * d.cW + cv_s) * d.cCin + cv_c);
-        } else if constexpr (AKC) {
-          const int m = bm0 + (c >> 3), k = k0 + (c & 7) * VE;
-          if (m < M && k < K) ra[i] = *(gptr_u4)(A + (long)m * lda + k);
-        } else {
-          constexpr int CPR = BM / VE;
-          const int k = k0 + c / CPR, m = bm0 + (c % CPR) * VE;
-          if (k < K && m < M) ra[i] = *(gptr_u4)(A + (long)k * lda + m);
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < CA; ++i) {
+          const int c = tid + i * 256;
+          ra[i] = (u32x4){0u, 0u, 0u, 0u};
+          if constexpr (AKC) {
+            const int m = bm0 + (c >> 3), k = k0 + (c & 7) * VE;
+            if (m < M && k < K) ra[i] = *(gptr_u4)(A + (long)m * lda + k);
+          } else {
+            constexpr int CPR = BM / VE;
+            const int k = k0 + c / CPR, m = bm0 + (c % CPR) * VE;
+            if (k < K && m < M) ra[i] = *(gptr_u4)(A + (long)k * lda + m);
+          }
         }
       }
 #pragma unroll
@@ -164,13 +235,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
           if (k < K && n < N) rb[i] = *(gptr_u4)(B + (long)k * ldb + n);
         }
       }
-      if constexpr (CONV) {       // advance this thread's (r, s, c) by one K tile
-        cv_c += BK;
-        while (cv_c >= d.cCin) {
-          cv_c -= d.cCin;
-          if (++cv_s == d.cKW) { cv_s = 0; ++cv_r; }
-        }
-      }
+      if constexpr (CONV) conv_tap_advance(cv_r, cv_s, cv_c, BK, d.cCin, d.cKW);
     }
   };
 
@@ -179,56 +244,11 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
     unsigned char* sA = smem + buf * BUF_BYTES;
     unsigned char* sB = sA + A_BYTES;
     if constexpr (VEC) {
-#pragma unroll
-      for (int i = 0; i < CA; ++i) {
-        const int c = tid + i * 256;
-        if constexpr (AKC) {
-          *(u32x4*)(sA + (c >> 3) * SA + (c & 7) * 16) = ra[i];
-        } else {
-          constexpr int CPR = BM / VE;
-          *(u32x4*)(sA + (c / CPR) * SA + (c % CPR) * 16) = ra[i];
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < CB; ++i) {
-        const int c = tid + i * 256;
-        if constexpr (BKC) {
-          *(u32x4*)(sB + (c >> 3) * SB + (c & 7) * 16) = rb[i];
-        } else {
-          constexpr int CPR = BN / VE;
-          *(u32x4*)(sB + (c / CPR) * SB + (c % CPR) * 16) = rb[i];
-        }
-      }
+      g4_store<TI, AKC, BM, SA>(sA, ra, tid);
+      g4_store<TI, BKC, BN, SB>(sB, rb, tid);
     } else {
-      const int k0 = kt * BK;
-      for (int e = tid; e < BM * BK; e += 256) {
-        TI v = (TI)0.f;
-        if constexpr (AKC) {
-          const int row = e / BK, kk = e % BK;
-          const int m = bm0 + row, k = k0 + kk;
-          if (m < M && k < K) v = A[(long)m * lda + k];
-          *(TI*)(sA + row * SA + kk * SZ) = v;
-        } else {
-          const int kk = e / BM, row = e % BM;
-          const int m = bm0 + row, k = k0 + kk;
-          if (m < M && k < K) v = A[(long)k * lda + m];
-          *(TI*)(sA + kk * SA + row * SZ) = v;
-        }
-      }
-      for (int e = tid; e < BN * BK; e += 256) {
-        TI v = (TI)0.f;
-        if constexpr (BKC) {
-          const int row = e / BK, kk = e % BK;
-          const int n = bn0 + row, k = k0 + kk;
-          if (n < N && k < K) v = B[(long)n * ldb + k];
-          *(TI*)(sB + row * SB + kk * SZ) = v;
-        } else {
-          const int kk = e / BN, row = e % BN;
-          const int n = bn0 + row, k = k0 + kk;
-          if (n < N && k < K) v = B[(long)k * ldb + n];
-          *(TI*)(sB + kk * SB + row * SZ) = v;
-        }
-      }
+      g4_store_scalar<TI, AKC, BM, SA>(sA, A, lda, bm0, M, kt * BK, K, tid);
+      g4_store_scalar<TI, BKC, BN, SB>(sB, B, ldb, bn0, N, kt * BK, K, tid);
     }
   };
 
@@ -239,7 +259,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
       unsigned char* sA = smem + buf * BUF_BYTES;
       unsigned char* sB = sA + A_BYTES;
       const int k0 = kt * BK;
-      const int kc = ((tid & 7) ^ ((tid >> 4) & 7)) * VE;         // logical k offset of this thread's chunk
+      const int kc = swz_dma_chunk(tid) * VE;                     // logical k offset of this thread's chunk
       const int wbase = (tid & ~63) * 16;
 #pragma unroll
       for (int i = 0; i < CA; ++i) {
@@ -263,13 +283,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
         if (n < N && k < K) src = (const TI*)d.B + (long)n * ldb + k;
         __builtin_amdgcn_global_load_lds((gbl_void_ptr)src, (lds_void_ptr)(sB + i * 4096 + wbase), 16, 0, 0);
       }
-      if constexpr (CONV) {
-        cv_c += BK;
-        while (cv_c >= d.cCin) {
-          cv_c -= d.cCin;
-          if (++cv_s == d.cKW) { cv_s = 0; ++cv_r; }
-        }
-      }
+      if constexpr (CONV) conv_tap_advance(cv_r, cv_s, cv_c, BK, d.cCin, d.cKW);
     }
   };
 
@@ -281,72 +295,18 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
       for (int ks = 0; ks < BK / 32; ++ks) {
         bf16x8 fa[TM], fb[TN];
 #pragma unroll
-        for (int t = 0; t < TM; ++t) {
-          const int r0 = wr * (BM / 2) + t * 16;
-          if constexpr (PIPE) {
-            fa[t] = *(const bf16x8*)(sA + (r0 + lr) * 128 + (((ks * 4 + lg) ^ (((r0 + lr) >> 1) & 7)) << 4));
-          } else if constexpr (AKC) {
-            fa[t] = *(const bf16x8*)(sA + (r0 + lr) * SA + ks * 64 + lg * 16);
-          } else {
-            // [k][m] image: lane (q=lr>>2, p=lr&3) addresses row k0+q, cols 4p..4p+3; receives column lr
-            const unsigned char* p0 = sA + (ks * 32 + lg * 8 + (lr >> 2)) * SA + (r0 + 4 * (lr & 3)) * 2;
-            bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)p0);
-            bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p0 + 4 * SA));
-            fa[t] = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
-          }
-        }
+        for (int t = 0; t < TM; ++t) fa[t] = g4_frag_bf16<AKC, PIPE, SA>(sA, wr * (BM / 2) + t * 16, ks, lr, lg);
 #pragma unroll
-        for (int t = 0; t < TN; ++t) {
-          const int r0 = wc * (BN / 2) + t * 16;
-          if constexpr (PIPE) {
-            fb[t] = *(const bf16x8*)(sB + (r0 + lr) * 128 + (((ks * 4 + lg) ^ (((r0 + lr) >> 1) & 7)) << 4));
-          } else if constexpr (BKC) {
-            fb[t] = *(const bf16x8*)(sB + (r0 + lr) * SB + ks * 64 + lg * 16);
-          } else {
-            const unsigned char* p0 = sB + (ks * 32 + lg * 8 + (lr >> 2)) * SB + (r0 + 4 * (lr & 3)) * 2;
-            bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)p0);
-            bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p0 + 4 * SB));
-            fb[t] = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+        for (int t = 0; t < TN; ++t) fb[t] = g4_frag_bf16<BKC, PIPE, SB>(sB, wc * (BN / 2) + t * 16, ks, lr, lg);
+        mfma_block(acc, fa, fb);
       }
     } else {
-      // f32: lane group lg owns k = 8*lg .. 8*lg+7 of the 32-wide tile; MFMA step s
-      // contracts k in {8g+s : g=0..3} (same map for A and B, so the sum covers all 32).
+      // f32: MFMA step s contracts k in {8g+s : g=0..3} (same map for A and B, so the sum covers all 32).
       float fa[TM][8], fb[TN][8];
 #pragma unroll
-      for (int t = 0; t < TM; ++t) {
-        const int r0 = wr * (BM / 2) + t * 16;
-        if constexpr (AKC) {
-          const int sw = PIPE ? (((r0 + lr) >> 1) & 7) : 0;
-          const float4 v0 = *(const float4*)(sA + (r0 + lr) * SA + (((2 * lg) ^ sw) << 4));
-          const float4 v1 = *(const float4*)(sA + (r0 + lr) * SA + (((2 * lg + 1) ^ sw) << 4));
-          fa[t][0] = v0.x; fa[t][1] = v0.y; fa[t][2] = v0.z; fa[t][3] = v0.w;
-          fa[t][4] = v1.x; fa[t][5] = v1.y; fa[t][6] = v1.z; fa[t][7] = v1.w;
-        } else {
+      for (int t = 0; t < TM; ++t) g4_frag_f32<AKC, PIPE, SA>(fa[t], sA, wr * (BM / 2) + t * 16, lr, lg);
 #pragma unroll
-          for (int s = 0; s < 8; ++s) fa[t][s] = *(const float*)(sA + (lg * 8 + s) * SA + (r0 + lr) * 4);
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < TN; ++t) {
-        const int r0 = wc * (BN / 2) + t * 16;
-        if constexpr (BKC) {
-          const int sw = PIPE ? (((r0 + lr) >> 1) & 7) : 0;
-          const float4 v0 = *(const float4*)(sB + (r0 + lr) * SB + (((2 * lg) ^ sw) << 4));
-          const float4 v1 = *(const float4*)(sB + (r0 + lr) * SB + (((2 * lg + 1) ^ sw) << 4));
-          fb[t][0] = v0.x; fb[t][1] = v0.y; fb[t][2] = v0.z; fb[t][3] = v0.w;
-          fb[t][4] = v1.x; fb[t][5] = v1.y; fb[t][6] = v1.z; fb[t][7] = v1.w;
-        } else {
-#pragma unroll
-          for (int s = 0; s < 8; ++s) fb[t][s] = *(const float*)(sB + (lg * 8 + s) * SB + (r0 + lr) * 4);
-        }
-      }
+      for (int t = 0; t < TN; ++t) g4_frag_f32<BKC, PIPE, SB>(fb[t], sB, wc * (BN / 2) + t * 16, lr, lg);
 #pragma unroll
       for (int s = 0; s < 8; ++s)
 #pragma unroll
@@ -472,14 +432,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
       const int mb = bm0 + wr * (BM / 2) + i * 16 + lg * 4;
       float keep4[4] = {1.f, 1.f, 1.f, 1.f};
       if constexpr (EPI == EPI_HIGHWAY) {
-        if (!d.mask && d.use_philox) {       // one Philox4x32 call serves the lane's 4 consecutive rows
-          uint32_t r0, r1, r2, r3;
-          Philox::gen4(d.seed_dev ? *d.seed_dev : d.seed, d.stream, (uint64_t)(mb >> 2) * (uint64_t)N + (uint64_t)n, r0, r1, r2, r3);
-          keep4[0] = Philox::u01(r0) >= d.drop_p ? 1.f : 0.f;
-          keep4[1] = Philox::u01(r1) >= d.drop_p ? 1.f : 0.f;
-          keep4[2] = Philox::u01(r2) >= d.drop_p ? 1.f : 0.f;
-          keep4[3] = Philox::u01(r3) >= d.drop_p ? 1.f : 0.f;
-        }
+        // one Philox4x32 call serves the lane's 4 consecutive rows
+        if (!d.mask && d.use_philox) highway_keep4(d.seed_dev ? *d.seed_dev : d.seed, d.stream, mb >> 2, N, n, d.drop_p, keep4);
       }
       float st_s = 0.f, st_q = 0.f;
 #pragma unroll
@@ -498,9 +452,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
           if (d.accumulate) v += to_f32<TO>(C[o]);
           C[o] = from_f32<TO>(v);
         } else {   // EPI_HIGHWAY
-          const float x = to_f32<TI>(((const TI*)d.X)[(long)m * d.ldx + n]);
-          const float sg = 1.f / (1.f + expf(-v));
-          const float y = sg * fmaxf(v, 0.f) + (1.f - sg) * x;
+          const float y = highway_gate(v, to_f32<TI>(((const TI*)d.X)[(long)m * d.ldx + n]));
           if (d.Hpre) d.Hpre[(long)m * d.ldh + n] = v;          // (null: forward only, nothing saved for a backward pass)
           float keep = keep4[r];
           if (d.mask) keep = (float)d.mask[(long)m * d.ldmask + n];
@@ -564,7 +516,7 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
   const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void*)(ARES ? d.res : d.A), 0, (int)a_bytes, 0x00020000);
 
   // ---- per-thread chunk coordinates: rows (tid>>3) + 64 i, physical chunk slot tid&7 = logical chunk ^ swizzle(row)
-  const int kc = ((tid & 7) ^ ((tid >> 4) & 7)) * 8;           // logical k offset (elements) inside a K tile
+  const int kc = swz_dma_chunk(tid) * 8;                       // logical k offset (elements) inside a K tile
   int a_off[CA], a_hi0[CA], a_wi0[CA];
   bool a_ok[CA];
   int cv_r = 0, cv_s = 0, cv_c = 0;
@@ -573,12 +525,9 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
     const int m = bm0 + (tid >> 3) + i * 64;
     a_ok[i] = m < M;
     if constexpr (CONV) {
-      const int mm = a_ok[i] ? m : 0;
-      const int wo = mm % d.cWo, t = mm / d.cWo;
-      const int ho = t % d.cHo, n = t / d.cHo;
-      a_hi0[i] = a_ok[i] ? ho * d.cStride - d.cPad : -(1 << 28);      // rows past M never validate
-      a_wi0[i] = wo * d.cStride - d.cPad;
-      a_off[i] = ((n * d.cH + a_hi0[i]) * d.cW + a_wi0[i]) * d.cCin;
+      const ConvOrigin<int> o = conv_origin<int>(m, a_ok[i], d.cHo, d.cWo, d.cH, d.cW, d.cStride, d.cPad);      // (operands under 2 GiB)
+      a_hi0[i] = o.hi0; a_wi0[i] = o.wi0;
+      a_off[i] = o.pix * d.cCin;
     } else {
       a_hi0[i] = a_wi0[i] = 0;
       a_off[i] = m * (int)d.lda;
@@ -624,13 +573,7 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
       const unsigned voff = (b_ok[i] & kok) ? (unsigned)(b_off[i] + k) * 2u : OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_void_ptr)(sB + i * (NT * 16) + wbase), 16, (int)voff, 0, 0, 0);
     }
-    if constexpr (CONV) {
-      cv_c += BK;
-      while (cv_c >= d.cCin) {
-        cv_c -= d.cCin;
-        if (++cv_s == d.cKW) { cv_s = 0; ++cv_r; }
-      }
-    }
+    if constexpr (CONV) conv_tap_advance(cv_r, cv_s, cv_c, BK, d.cCin, d.cKW);
   };
 
   // ---- A-side BatchNorm + ReLU: per-channel [scale, shift] from the producer's sums, then each thread normalises the chunks it
@@ -701,6 +644,8 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
+  // a whole K tile (the ring-less and 2-stage loops): ALL its fragment reads, then all its MFMAs (read_half / mfma_half below interleave
+  // the two halves for the deep ring)
   auto compute = [&](int st) {
     const unsigned char* sA = smem + st * STAGE;
     const unsigned char* sB = sA + A_BYTES;
@@ -710,21 +655,16 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
 #pragma unroll
       for (int t = 0; t < TM; ++t) {
         const int row = wr * 32 + t * 16 + lr;
-        fa[ks][t] = *(const bf16x8*)(sA + row * 128 + (((ks * 4 + lg) ^ ((row >> 1) & 7)) << 4));
+        fa[ks][t] = *(const bf16x8*)(sA + row * 128 + swz_chunk(row, ks * 4 + lg));
       }
 #pragma unroll
       for (int t = 0; t < TN; ++t) {
         const int row = wc * (BN / 2) + t * 16 + lr;
-        fb[ks][t] = *(const bf16x8*)(sB + row * 128 + (((ks * 4 + lg) ^ ((row >> 1) & 7)) << 4));
+        fb[ks][t] = *(const bf16x8*)(sB + row * 128 + swz_chunk(row, ks * 4 + lg));
       }
     }
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks][i], fb[ks][j], acc[i][j], 0, 0, 0);
+    for (int ks = 0; ks < 2; ++ks) mfma_block(acc, fa[ks], fb[ks]);
   };
 
   // fragment reads / MFMAs of one 32-deep half (ks) of a K tile, as separate phases for the software pipeline below
@@ -734,21 +674,15 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
       const int row = wr * 32 + t * 16 + lr;
-      fa[t] = *(const bf16x8*)(sA + row * 128 + (((ks * 4 + lg) ^ ((row >> 1) & 7)) << 4));
+      fa[t] = *(const bf16x8*)(sA + row * 128 + swz_chunk(row, ks * 4 + lg));
     }
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
       const int row = wc * (BN / 2) + t * 16 + lr;
-      fb[t] = *(const bf16x8*)(sB + row * 128 + (((ks * 4 + lg) ^ ((row >> 1) & 7)) << 4));
+      fb[t] = *(const bf16x8*)(sB + row * 128 + swz_chunk(row, ks * 4 + lg));
     }
   };
-  auto mfma_half = [&](const bf16x8 (&fa)[TM], const bf16x8 (&fb)[TN]) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-  };
+  auto mfma_half = [&](const bf16x8 (&fa)[TM], const bf16x8 (&fb)[TN]) { mfma_block(acc, fa, fb); };
 
   // ---- K loop: NS-1 tiles in flight.  Tiles past the end of K are all-OOB DMAs (zero fill, no traffic), so the count
   // of outstanding DMAs is the same in every iteration.
@@ -879,104 +813,57 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
   TO* __restrict__ C = (TO*)d.C;
   if constexpr (EPI == EPI_HIGHWAY) {
     // h = acc + bias (saved); y = sig(h) relu(h) + (1 - sig(h)) x; C = y * keep * keep_scale.
-    // Row-padded operands (every leading dimension covers whole 8-column groups, as the discriminator's Fp-padded buffers do):
-    // h goes through LDS and each thread owns a 4-row x 8-column patch = one Philox draw per column (4 rows each), 16-byte
-    // accesses to X / Hpre / C and 8-byte ones to the keep mask.  Pad columns of C are written as zero.
-    const int n8 = (N + 7) & ~7;
-    const bool wide = sizeof(TO) == 2 && d.ldc >= n8 && d.ldx >= n8 && d.ldh >= n8 && (!d.mask_out || d.ldmask_out >= n8) &&
-                      d.ldc % 8 == 0 && d.ldx % 8 == 0 && d.ldh % 4 == 0 && (!d.mask_out || d.ldmask_out % 8 == 0) &&
-                      ((((uintptr_t)d.C) | ((uintptr_t)d.X) | ((uintptr_t)d.Hpre)) & 15) == 0 && (((uintptr_t)d.mask_out) & 7) == 0;
-    if (wide) {
-      constexpr int SH = BN + 4;
-      float* sH = (float*)smem;
+    // Row-padded bf16 operands only (select_tile8's highway_wide: every leading dimension covers whole 8-column groups, as the
+    // discriminator's Fp-padded buffers do; anything else is gemm_kernel's): h goes through LDS and each thread owns a 4-row x 8-column
+    // patch = one Philox draw per column (4 rows each), 16-byte accesses to X / Hpre / C and 8-byte ones to the keep mask.  Pad columns
+    // of C are written as zero.
+    static_assert(sizeof(TO) == 2, "the highway epilogue writes bf16 rows");
+    constexpr int SH = BN + 4;
+    float* sH = (float*)smem;
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int nl = wc * (BN / 2) + j * 16 + lr;
-        const float bias = (d.bias && bn0 + nl < N) ? d.bias[bn0 + nl] : 0.f;
+    for (int j = 0; j < TN; ++j) {
+      const int nl = wc * (BN / 2) + j * 16 + lr;
+      const float bias = (d.bias && bn0 + nl < N) ? d.bias[bn0 + nl] : 0.f;
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+      for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) sH[(wr * 32 + i * 16 + lg * 4 + r) * SH + nl] = d.alpha * acc[i][j][r] + bias;
+        for (int r = 0; r < 4; ++r) sH[(wr * 32 + i * 16 + lg * 4 + r) * SH + nl] = d.alpha * acc[i][j][r] + bias;
+    }
+    __syncthreads();
+    constexpr int CG = BN / 8;
+    const int pc = tid % CG, pr = tid / CG;
+    const int n0 = bn0 + pc * 8, m0 = bm0 + pr * 4;
+    if (pr < BM / 4 && n0 < N && m0 < M) {
+      float keep[8][4];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        keep[e][0] = keep[e][1] = keep[e][2] = keep[e][3] = 1.f;
+        if (!d.mask && d.use_philox && n0 + e < N) highway_keep4(d.seed_dev ? *d.seed_dev : d.seed, d.stream, m0 >> 2, N, n0 + e, d.drop_p, keep[e]);
       }
-      __syncthreads();
-      constexpr int CG = BN / 8;
-      const int pc = tid % CG, pr = tid / CG;
-      const int n0 = bn0 + pc * 8, m0 = bm0 + pr * 4;
-      if (pr < BM / 4 && n0 < N && m0 < M) {
-        float keep[4][8];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + r;
+        if (m >= M) break;
+        const float4 h0 = *(const float4*)(sH + (pr * 4 + r) * SH + pc * 8), h1 = *(const float4*)(sH + (pr * 4 + r) * SH + pc * 8 + 4);
+        const float h[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+        const bf16x8 xv = *(const bf16x8*)((const bf16_t*)d.X + (long)m * d.ldx + n0);
+        bf16x8 yv;
+        unsigned long long kb = 0ull;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          keep[0][e] = keep[1][e] = keep[2][e] = keep[3][e] = 1.f;
-          if (!d.mask && d.use_philox && n0 + e < N) {
-            uint32_t r0, r1, r2, r3;
-            Philox::gen4(d.seed_dev ? *d.seed_dev : d.seed, d.stream, (uint64_t)(m0 >> 2) * (uint64_t)N + (uint64_t)(n0 + e), r0, r1, r2, r3);
-            keep[0][e] = Philox::u01(r0) >= d.drop_p ? 1.f : 0.f;
-            keep[1][e] = Philox::u01(r1) >= d.drop_p ? 1.f : 0.f;
-            keep[2][e] = Philox::u01(r2) >= d.drop_p ? 1.f : 0.f;
-            keep[3][e] = Philox::u01(r3) >= d.drop_p ? 1.f : 0.f;
-          }
+          const bool live = n0 + e < N;
+          const float y = highway_gate(h[e], (float)xv[e]);
+          float k = keep[e][r];
+          if (d.mask && live) k = (float)d.mask[(long)m * d.ldmask + n0 + e];
+          kb |= (unsigned long long)(live ? (unsigned)k : 0u) << (8 * e);
+          yv[e] = (bf16_t)(live ? y * k * d.keep_scale : 0.f);
         }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + r;
-          if (m >= M) break;
-          const float4 h0 = *(const float4*)(sH + (pr * 4 + r) * SH + pc * 8), h1 = *(const float4*)(sH + (pr * 4 + r) * SH + pc * 8 + 4);
-          const float h[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-          const bf16x8 xv = *(const bf16x8*)((const bf16_t*)d.X + (long)m * d.ldx + n0);
-          bf16x8 yv;
-          unsigned long long kb = 0ull;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const bool live = n0 + e < N;
-            const float sg = 1.f / (1.f + expf(-h[e]));
-            const float y = sg * fmaxf(h[e], 0.f) + (1.f - sg) * (float)xv[e];
-            float k = keep[r][e];
-            if (d.mask && live) k = (float)d.mask[(long)m * d.ldmask + n0 + e];
-            kb |= (unsigned long long)(live ? (unsigned)k : 0u) << (8 * e);
-            yv[e] = (bf16_t)(live ? y * k * d.keep_scale : 0.f);
-          }
-          if (d.Hpre) {
-            *(float4*)(d.Hpre + (long)m * d.ldh + n0) = h0;
-            *(float4*)(d.Hpre + (long)m * d.ldh + n0 + 4) = h1;
-          }
-          if (d.mask_out) *(unsigned long long*)(d.mask_out + (long)m * d.ldmask_out + n0) = kb;
-          *(bf16x8*)((bf16_t*)C + (long)m * d.ldc + n0) = yv;
+        if (d.Hpre) {
+          *(float4*)(d.Hpre + (long)m * d.ldh + n0) = h0;
+          *(float4*)(d.Hpre + (long)m * d.ldh + n0 + 4) = h1;
         }
-      }
-      STAMP(5);
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = bn0 + wc * (BN / 2) + j * 16 + lr;
-        if (n >= N) continue;
-        const float bias = d.bias ? d.bias[n] : 0.f;
-        const int mb = bm0 + wr * 32 + i * 16 + lg * 4;
-        float keep4[4] = {1.f, 1.f, 1.f, 1.f};
-        if (!d.mask && d.use_philox) {       // one Philox4x32 call serves the lane's 4 consecutive rows
-          uint32_t r0, r1, r2, r3;
-          Philox::gen4(d.seed_dev ? *d.seed_dev : d.seed, d.stream, (uint64_t)(mb >> 2) * (uint64_t)N + (uint64_t)n, r0, r1, r2, r3);
-          keep4[0] = Philox::u01(r0) >= d.drop_p ? 1.f : 0.f;
-          keep4[1] = Philox::u01(r1) >= d.drop_p ? 1.f : 0.f;
-          keep4[2] = Philox::u01(r2) >= d.drop_p ? 1.f : 0.f;
-          keep4[3] = Philox::u01(r3) >= d.drop_p ? 1.f : 0.f;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = mb + r;
-          if (m >= M) continue;
-          const float v = d.alpha * acc[i][j][r] + bias;
-          const float x = to_f32<bf16_t>(((const bf16_t*)d.X)[(long)m * d.ldx + n]);
-          const float sg = 1.f / (1.f + expf(-v));
-          const float y = sg * fmaxf(v, 0.f) + (1.f - sg) * x;
-          if (d.Hpre) d.Hpre[(long)m * d.ldh + n] = v;          // (null: forward only, nothing saved for a backward pass)
-          float keep = keep4[r];
-          if (d.mask) keep = (float)d.mask[(long)m * d.ldmask + n];
-          if (d.mask_out) d.mask_out[(long)m * d.ldmask_out + n] = (uint8_t)keep;
-          C[(long)m * d.ldc + n] = from_f32<TO>(y * keep * d.keep_scale);
-        }
+        if (d.mask_out) *(unsigned long long*)(d.mask_out + (long)m * d.ldmask_out + n0) = kb;
+        *(bf16x8*)((bf16_t*)C + (long)m * d.ldc + n0) = yv;
       }
     }
     STAMP(5);
@@ -1051,6 +938,7 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
       }
     }
   }
+  // (its own row-store loop: the f32 accumulate branch exists here only)
   constexpr int CPR = BN / OVE;                              // 16-B chunks per tile row
   for (int c = tid; c < BM * CPR; c += NT) {
     const int ml = c / CPR, cc = c % CPR;
@@ -1089,8 +977,23 @@ struct Plan {
 bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
+// Elements spanned by a k-contiguous [rows, K] operand with leading dimension ld: what a buffer descriptor over it must cover
+long kc_extent(int rows, long ld, int K) { return (long)(rows - 1) * ld + K; }
+bool under_2g(long bf16_elems) { return bf16_elems * 2 < (1l << 31); }
+
+// What tile8's highway epilogue presumes (its 4-row x 8-column patches): bf16 C, every leading dimension covering whole 8-column groups
+// and divisible as its 16- / 8-byte accesses need, 16-byte aligned C / X / Hpre, an 8-byte aligned mask_out.  The discriminator's
+// Fp-padded buffers; any other highway product is gemm_kernel's.
+bool highway_wide(const GemmDesc& d) {
+  const int n8 = (d.N + 7) & ~7;
+  return d.out_dtype == DT_BF16 && d.ldc >= n8 && d.ldx >= n8 && d.ldh >= n8 && (!d.mask_out || d.ldmask_out >= n8) &&
+         d.ldc % 8 == 0 && d.ldx % 8 == 0 && d.ldh % 4 == 0 && (!d.mask_out || d.ldmask_out % 8 == 0) &&
+         aligned16(d.C) && aligned16(d.X) && aligned16(d.Hpre) && (((uintptr_t)d.mask_out) & 7) == 0;
+}
+
 // The 8-wave kernel qualifies: bf16 k-contiguous operands under 2 GiB each, a plain (overwrite or accumulate, f32 or bf16 C) / BatchNorm-sum
-// epilogue onto a 16-byte-aligned C whose N and ldc are whole 16-byte chunks (or the highway epilogue).  false: fall back to gemm_kernel.
+// epilogue onto a 16-byte-aligned C whose N and ldc are whole 16-byte chunks (or the row-padded highway epilogue).  false: fall back to
+// gemm_kernel.
 bool select_tile8(const GemmDesc& d, Tile8Plan& p, int& n_fast) {
   static const bool off = getenv("GIC_NO_TILE8") != nullptr;
   static const int big_min = env_int("GIC_TILE8_BIG_MIN", 160), ns2_tiles = env_int("GIC_TILE8_NS2_TILES", 256), min_nk = env_int("GIC_TILE8_MIN_NK", 1);
@@ -1099,13 +1002,13 @@ bool select_tile8(const GemmDesc& d, Tile8Plan& p, int& n_fast) {
   const bool highway = d.epi == EPI_HIGHWAY;
   if (off || d.M < 128) return false;
   if (!highway && ((d.N % OVE) || (d.ldc % OVE) || !aligned16(d.C))) return false;
-  if (highway && d.in_dtype != DT_BF16) return false;
+  if (highway && (d.in_dtype != DT_BF16 || !highway_wide(d))) return false;
   const long small_tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 64), big_tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
   // a plain product must fill the chip with 128-row tiles and be deep enough to amortise the ring (else: gemm_kernel, split-K)
   if (!d.conv && (small_tiles < 128 || d.K < 256)) return false;
-  const long a_elems = d.conv ? (long)(d.M / (d.cHo * d.cWo)) * d.cH * d.cW * d.cCin : (long)(d.M - 1) * d.lda + d.K;
-  const long b_elems = (long)(d.N - 1) * d.ldb + d.K;
-  if (a_elems * 2 >= (1l << 31) || b_elems * 2 >= (1l << 31)) return false;
+  const long a_elems = d.conv ? (long)(d.M / (d.cHo * d.cWo)) * d.cH * d.cW * d.cCin : kc_extent(d.M, d.lda, d.K);
+  const long b_elems = kc_extent(d.N, d.ldb, d.K);
+  if (!under_2g(a_elems) || !under_2g(b_elems)) return false;
   const int nk = cdiv(d.K, 64);
   if (nk < min_nk) return false;
   p.a_bytes = (unsigned)(a_elems * 2); p.b_bytes = (unsigned)(b_elems * 2);
@@ -1144,18 +1047,13 @@ bool select_tile8(const GemmDesc& d, Tile8Plan& p, int& n_fast) {
   return true;
 }
 
-// 128x128 tiles only when there are enough of them to co-schedule two blocks per CU (latency hiding by TLP);
-// GIC_GEMM_BIG_MIN overrides the threshold for tuning runs.
-int big_tile_min() {
-  static const int v = env_int("GIC_GEMM_BIG_MIN", 192);
-  return v;
-}
-
 // The 4-wave kernel takes every product the validation lets through: tile size, split-K and the pipeline
 void select_gemm4(const GemmDesc& d, bool vec, Gemm4Plan& p) {
-  // 128x128 tiles when they still give >= ~1 block per CU, else 64x64
+  // 128x128 tiles only when there are enough of them to co-schedule two blocks per CU (latency hiding by TLP), else 64x64;
+  // GIC_GEMM_BIG_MIN overrides the threshold for tuning runs
+  static const int big_min = env_int("GIC_GEMM_BIG_MIN", 192);
   const long big_tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
-  p.bm = big_tiles >= big_tile_min() && d.N >= 128 && (d.conv || d.M >= 128) ? 128 : 64;
+  p.bm = big_tiles >= big_min && d.N >= 128 && (d.conv || d.M >= 128) ? 128 : 64;
   p.vec = vec;
   const bool bf16_in = d.in_dtype == DT_BF16;
   p.tiles = cdiv(d.M, p.bm) * cdiv(d.N, p.bm);
@@ -1253,7 +1151,7 @@ int select(const GemmDesc& d, bool vec, int after, Plan& p) {
 // 160 tiles of 128 x 128.  0: never (f32, M below 128 or no multiple of 4, the GIC_NO_TILE8 / GIC_NO_FUSED_GUMBELMAX switches).
 long gumbelmax_from_cols(int in_dtype, int M, int K, long lda, long ldb) {
   static const bool off = getenv("GIC_NO_TILE8") != nullptr || getenv("GIC_NO_FUSED_GUMBELMAX") != nullptr;
-  if (off || in_dtype != DT_BF16 || M < 128 || M % 4 || K % 8 || lda % 8 || ldb % 8 || ((long)(M - 1) * lda + K) * 2 >= (1l << 31)) return 0;
+  if (off || in_dtype != DT_BF16 || M < 128 || M % 4 || K % 8 || lda % 8 || ldb % 8 || !under_2g(kc_extent(M, lda, K))) return 0;
   const long mt = cdiv(M, 128), nt = (160 + mt - 1) / mt;           // column tiles that make 160 tiles
   return 128 * (nt - 1) + 1 > 128 ? 128 * (nt - 1) + 1 : 128;
 }
@@ -1265,9 +1163,9 @@ bool select_gumbelmax(const GemmDesc& d0, Plan& p) {
   if (!from || d.N < from || !d.a_kc || !d.b_kc || !aligned16(d.A) || !aligned16(d.B) || !aligned16(d.gm_bias) ||
       (d.gm_u && (!aligned16(d.gm_u) || d.gm_ldu % 4)) || !(d.gm_temperature > 0.f))
     return false;
-  const long a_elems = (long)(d.M - 1) * d.lda + d.K, b_elems = (long)(d.N - 1) * d.ldb + d.K;
+  const long a_elems = kc_extent(d.M, d.lda, d.K), b_elems = kc_extent(d.N, d.ldb, d.K);
   const long tiles = (long)cdiv(d.M, 128) * cdiv(d.N, 128);
-  if (b_elems * 2 >= (1l << 31)) return false;
+  if (!under_2g(b_elems)) return false;
   d.epi = EPI_GUMBELMAX;
   d.n_fast = xcd_share_a(2l * d.M * d.K, 2l * d.N * d.K, cdiv(d.N, 128));
   p.t8 = {128, tiles > 256 ? 2 : 4, false, false, 1024, (unsigned)tiles, (unsigned)(a_elems * 2), (unsigned)(b_elems * 2)};
@@ -1317,8 +1215,7 @@ void launch_tile8(const Plan& p, hipStream_t stream) {
     if (d.epi == EPI_BNSTATS) launch_tile8_variant<bf16_t, EPI_BNSTATS, true>(p, stream);
     else launch_tile8_variant<bf16_t, EPI_PLAIN, true>(p, stream);
   } else if (d.epi == EPI_HIGHWAY) {
-    if (bf16_out) launch_tile8_variant<bf16_t, EPI_HIGHWAY, false>(p, stream);
-    else launch_tile8_variant<float, EPI_HIGHWAY, false>(p, stream);
+    launch_tile8_variant<bf16_t, EPI_HIGHWAY, false>(p, stream);        // (select_tile8's highway_wide: bf16 C)
   } else {
     if (bf16_out) launch_tile8_variant<bf16_t, EPI_PLAIN, false>(p, stream);
     else launch_tile8_variant<float, EPI_PLAIN, false>(p, stream);

@@ -204,6 +204,51 @@ def test_cfg2_product_routes(shape, expected, splits):
         assert splits_of(line) == (1 if shape[7] or splits == 1 else 2)
 
 
+def disc_fwd(rows, train=1, dtype=BF16, **state):
+    """gic_disc_fwd over rows = B * R feature rows of cfg2's discriminator (F = 900 filters in Fp = 960 columns, R = 64): in route-only mode
+    the call selects its highway product (M = rows, N = F, K = Fp: the one caller of the highway epilogue) and launches nothing.  `state`
+    replaces buffers of the saved state (hpre, keep, ydrop ...); every other pointer is P."""
+    d, prm, sh, st = L.DiscDims(), L.DiscParams(), L.DiscShadow(), L.DiscState()
+    d.B, d.L, d.V, d.De, d.R, d.nconv = rows // 64, 20, 10000, 64, 64, 1
+    d.fsize[0], d.nfilt[0] = 2, 900                     # (the filter bank does not enter the highway product: one bank of all F filters)
+    d.F, d.Fp, d.dtype, d.drop_p = 900, 960, dtype, 0.2
+    for s in (prm, sh, st):
+        for name, ctype in s._fields_:
+            setattr(s, name, P if ctype is L.c_void_p else ctype(P))
+    for name, ptr in state.items():
+        setattr(st, name, ptr)
+    return ("gic_disc_fwd", (d, prm, sh, st, None, 0, P, train, None, 1, P, None, 0, None))
+
+
+# the discriminator passes of one cfg2 train step: B = 64 captions, and the real + fake pair of 128
+@pytest.mark.parametrize("rows,expected", [(4096, "tile8<bf16,128,1,false,4,false,false,1024> grid=256 block=512"),
+                                           (8192, "tile8<bf16,128,1,false,2,false,false,1024> grid=512 block=512")])
+def test_cfg2_highway_routes(rows, expected):
+    for train in (1, 0):
+        status, line = route(disc_fwd(rows, train))
+        assert status == 0, line
+        assert kernel_and_grid(line) == expected
+    # a forward that no backward follows saves no pre-activation: the same kernel, which skips the store
+    status, line = route(disc_fwd(rows, 0, hpre=None, argmax=None))
+    assert status == 0 and kernel_and_grid(line) == expected, line
+
+
+@pytest.mark.parametrize("state", [{"hpre": P + 8}, {"ydrop": P + 8}, {"keep": P + 4}], ids=lambda s: next(iter(s)))
+def test_highway_off_its_row_padded_form_takes_the_4_wave_kernel(state):
+    """tile8's highway epilogue owns 4-row x 8-column patches with 16-byte accesses to C / X / Hpre and 8-byte ones to the keep mask: a
+    buffer that is not aligned for them sends the product to gemm_kernel, whose highway epilogue is element-wise."""
+    status, line = route(disc_fwd(4096, 1, **state))
+    assert status == 0, line
+    assert kernel_and_grid(line) == "gemm<bf16,bf16,true,true,128,128,true,1,false,true> grid=256x1 block=256"     # (K = 15 tiles over 256 blocks: the LDS-DMA ring)
+    status, line = route(disc_fwd(4096, 1))
+    assert status == 0 and line.startswith("tile8<bf16,128,1,"), line
+
+
+def test_fp32_highway_takes_the_4_wave_kernel():
+    status, line = route(disc_fwd(4096, 1, dtype=F32))
+    assert status == 0 and line.startswith("gemm<f32,f32,true,true,128,128,true,1,false,"), line
+
+
 def test_fp32_takes_the_4_wave_kernel():
     status, line = route(gemm(4096, 960, 960, 1, 1, F32, F32, 0))          # a shape tile8 takes in bf16
     assert status == 0 and line.startswith("gemm<f32,f32,true,true,"), line
