@@ -593,7 +593,10 @@ typedef struct gic_disc_bwd_ws {
 } gic_disc_bwd_ws;
 
 /* Byte sizes in field order: gic_disc_state -> emb, pooled, argmax, hpre, keep, ydrop, feat (7 values; ydrop must start zeroed:
- * its pad columns are read); gic_disc_bwd_ws -> dfeat, dh, dydrop, dpooled, demb (5 values).  Host-only. */
+ * its pad columns are read); gic_disc_bwd_ws -> dfeat, dh, dydrop, dpooled, demb (5 values).  Host-only.
+ * Pad columns F .. Fp-1: gic_disc_fwd writes those of pooled and argmax as zero and leaves ydrop's zero; gic_disc_bwd writes those of dh,
+ * dydrop and dpooled as zero.  Those of hpre and keep are never read as values and may be left unwritten (the highway epilogues store
+ * live columns only, or whole 8-column groups up to the one that holds column F-1): a caller must not rely on their contents. */
 int gic_disc_state_bytes(const gic_disc_dims* dims, uint64_t* out);
 int gic_disc_bwd_ws_bytes(const gic_disc_dims* dims, uint64_t* out);
 

@@ -563,8 +563,9 @@ def test_bf16_discriminator_at_bench_batch(E, dev):
 def test_forward_only_discriminator_convolution_in_bf16_matches_the_fp32_kernels(E, dev):
     """The reward-evaluation form of Discriminator.forward (eval mode, nothing kept for a backward pass) runs its convolution + ReLU +
     max-over-time with bf16 products on the 32x32x16 MFMA (disc.hip); the same forward WITH a saved state runs the fp32-product kernel
-    (discriminator.py:40-47 as the reference computes it).  Same parameters and ids, 70 captions x 64 representations (a partial
-    32-pair workgroup at the end), odd and even window counts: pooled features agree to bf16 rounding of the embedding and the
+    (discriminator.py:40-47 as the reference computes it).  Same parameters and ids, 70 captions x 64 representations (4480 pairs =
+    140 whole 32-pair workgroups: a partial one is run by tests/test_gpu_disc_stages.py), odd and even window counts: pooled features
+    agree to bf16 rounding of the embedding and the
     filter weights, logits to the bf16 budget of the rest of the reward path, and both stay close to the fp32 oracle."""
     g = Golden("cfg1")
     _, dp = initial_params(g)
