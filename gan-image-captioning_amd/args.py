@@ -119,6 +119,13 @@ _NATIVE = [
                                        "validation; 0 = off"),
     ("--eval-metrics-beam-size", int, 0, "beam size of the metrics-table evaluation (GANInstructor.evaluate_metrics: BLEU-1..4, ROUGE-L "
                                          "and CIDEr-D scored on the GPU from one decode) after each adversarial epoch's validation; 0 = off"),
+    ("--disc-cond", str, "none", "image conditioning of the discriminator: none = D scores the caption alone (the reference); projection = D "
+                                 "scores (image, caption) pairs, logits += F^-1/2 <highway output, img_proj(pooled trunk feature)> "
+                                 "(needs --conditional-gan 1; not with --adv-mode seqgan)", {"choices": ["none", "projection"]}),
+    ("--disc-mismatch-weight", float, 0.5, "w of d_loss = (1 - w) d(real, fake) + w d(real, wrong) under --disc-cond projection: wrong = the "
+                                           "real captions against the batch's images rolled by one; 0 <= w < 1, 0 = no third D pass"),
+    ("--eval-match", int, 0, "image-caption match evaluation (GANInstructor.evaluate_match: pair accuracy and margin of the match term, "
+                             "--disc-cond projection) after each adversarial epoch's validation", {"choices": [0, 1]}),
     ("--eval-no-repeat-ngram", int, 0, "decode constraint of the evaluations (evaluate, evaluate_cider, evaluate_diversity, "
                                        "evaluate_diverse_beam): no n-gram of this size occurs twice in a caption; 0 = off"),
     ("--eval-min-length", int, 0, "decode constraint of the evaluations: <E> is not emitted before this many tokens; 0 = off"),

@@ -805,7 +805,8 @@ int disc_fwd_redrop_t(const DCtx& c, const gic_disc_params* P, const gic_disc_sh
 template <typename TA>
 int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S, const gic_disc_state* st,
                const gic_disc_bwd_ws* ws, const void* inp_soft, long ld_inp, const int64_t* inp_ids, int train,
-               const float* d_logits, const gic_disc_grads* G, int accumulate, void* d_inp, long ld_dinp, hipStream_t stream) {
+               const float* d_logits, const gic_disc_grads* G, int accumulate, void* d_inp, long ld_dinp, hipStream_t stream,
+               const float* cond_q = nullptr, float cond_scale = 0.f, float* cond_dq = nullptr) {
   const long MR = c.rowsBR;
   if (G && !accumulate) {   // atomically-accumulated small grads start from zero
     GIC_PROPAGATE(fill_zero(G->o2l_w, kOutDim * sizeof(float), stream));
@@ -834,11 +835,15 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
     hipLaunchKernelGGL(disc_out_fold_kernel, dim3(1), dim3(128), 0, stream, (const float*)ws->dydrop, out_blocks, G->o2l_w, G->o2l_b);
     GIC_CHECK_LAUNCH("disc_out_fold");
   }
+  // 1b. conditioned D (disc_cond.hip): the match term's share of dydrop and d_q.  Behind disc_out_fold: the deterministic mode's
+  // partials of step 1 lived in dydrop until then.  The feature2out product below then adds onto it
+  if (cond_q)
+    GIC_PROPAGATE(disc_match_bwd(c.dt, st->ydrop, cond_q, d_logits, cond_scale, ws->dydrop, cond_dq, c.B, c.R, c.F, c.Fp, stream));
   // 2. feature2out backward
   {
-    GemmDesc g;   // dydrop[MR, Fp] = dfeat[MR,104] f2o_w[104, Fp]
+    GemmDesc g;   // dydrop[MR, Fp] (+)= dfeat[MR,104] f2o_w[104, Fp]
     g.A = ws->dfeat; g.lda = kOutPad; g.a_kc = 1; g.B = S->f2o_w; g.ldb = c.Fp; g.b_kc = 0; g.C = ws->dydrop; g.ldc = c.Fp;
-    g.M = (int)MR; g.N = c.Fp; g.K = kOutPad; g.in_dtype = c.dt; g.out_dtype = DT_F32;
+    g.M = (int)MR; g.N = c.Fp; g.K = kOutPad; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.accumulate = cond_q ? 1 : 0;
     GIC_PROPAGATE(gemm(g, stream));
     if (G) {
       GemmDesc w;   // dW_f2o[100, F] = dfeat^T ydrop
@@ -1055,23 +1060,41 @@ int gic_disc_fwd_redrop(const gic_disc_dims* dims, const gic_disc_params* P, con
   return disc_fwd_redrop_t<bf16_t>(c, P, S, src, dst, train, keep_mask, seed, seed_dev, logits, (hipStream_t)stream);
 }
 
+static int disc_bwd_entry(const char* what, const gic_disc_dims* dims, const gic_disc_params* P, const gic_disc_shadow* S, const gic_disc_state* st,
+                          const gic_disc_bwd_ws* ws, const void* inp_soft, int64_t ld_inp, const int64_t* inp_ids, int train,
+                          const float* d_logits, const gic_disc_grads* G, int accumulate, void* d_inp, int64_t ld_dinp, const float* q, float scale,
+                          float* d_q, void* stream) {
+  DCtx c;
+  GIC_PROPAGATE(make_ctx(dims, P, G, c));
+  GIC_CHECK_ARG(P && S && st && ws && d_logits, "%s: null argument", what);
+  GIC_CHECK_ARG(inp_soft || inp_ids, "%s: pass inp_soft, inp_ids, or both (mixed batch: ids for the first B/2 captions)", what);
+  GIC_CHECK_ARG(!(inp_soft && inp_ids) || (G && !d_inp && c.B % 2 == 0), "%s: a mixed batch needs an even B, grads and no d_inp", what);
+  GIC_CHECK_ARG(ws->dfeat && ws->dh && ws->dydrop && ws->dpooled && ws->demb, "%s: null workspace buffer", what);
+  GIC_CHECK_ARG(!d_inp || (inp_soft && ld_dinp >= c.V), "%s: d_inp needs a soft input and ld_dinp >= V", what);
+  GIC_CHECK_ARG(q || !d_q, "%s: d_q without q", what);
+  GIC_CHECK_ARG(!q || (st->ydrop && scale == scale), "%s: the match term needs state->ydrop and a scale that is not NaN", what);
+  if (G) {
+    GIC_CHECK_ARG(G->emb && G->hw_w && G->hw_b && G->f2o_w && G->f2o_b && G->o2l_w && G->o2l_b, "%s: null grad buffer", what);
+    for (int k = 0; k < c.cm.nconv; ++k) GIC_CHECK_ARG(G->conv_w[k] && G->conv_b[k], "%s: null conv %d grad buffer", what, k);
+  }
+  if (c.dt == DT_F32)
+    return disc_bwd_t<float>(c, P, S, st, ws, inp_soft, ld_inp, inp_ids, train, d_logits, G, accumulate, d_inp, ld_dinp, (hipStream_t)stream, q, scale, d_q);
+  return disc_bwd_t<bf16_t>(c, P, S, st, ws, inp_soft, ld_inp, inp_ids, train, d_logits, G, accumulate, d_inp, ld_dinp, (hipStream_t)stream, q, scale, d_q);
+}
+
 int gic_disc_bwd(const gic_disc_dims* dims, const gic_disc_params* P, const gic_disc_shadow* S, const gic_disc_state* st,
                  const gic_disc_bwd_ws* ws, const void* inp_soft, int64_t ld_inp, const int64_t* inp_ids, int train,
                  const float* d_logits, const gic_disc_grads* G, int accumulate, void* d_inp, int64_t ld_dinp, void* stream) {
-  DCtx c;
-  GIC_PROPAGATE(make_ctx(dims, P, G, c));
-  GIC_CHECK_ARG(P && S && st && ws && d_logits, "disc_bwd: null argument");
-  GIC_CHECK_ARG(inp_soft || inp_ids, "disc_bwd: pass inp_soft, inp_ids, or both (mixed batch: ids for the first B/2 captions)");
-  GIC_CHECK_ARG(!(inp_soft && inp_ids) || (G && !d_inp && c.B % 2 == 0), "disc_bwd: a mixed batch needs an even B, grads and no d_inp");
-  GIC_CHECK_ARG(ws->dfeat && ws->dh && ws->dydrop && ws->dpooled && ws->demb, "disc_bwd: null workspace buffer");
-  GIC_CHECK_ARG(!d_inp || (inp_soft && ld_dinp >= c.V), "disc_bwd: d_inp needs a soft input and ld_dinp >= V");
-  if (G) {
-    GIC_CHECK_ARG(G->emb && G->hw_w && G->hw_b && G->f2o_w && G->f2o_b && G->o2l_w && G->o2l_b, "disc_bwd: null grad buffer");
-    for (int k = 0; k < c.cm.nconv; ++k) GIC_CHECK_ARG(G->conv_w[k] && G->conv_b[k], "disc_bwd: null conv %d grad buffer", k);
-  }
-  if (c.dt == DT_F32)
-    return disc_bwd_t<float>(c, P, S, st, ws, inp_soft, ld_inp, inp_ids, train, d_logits, G, accumulate, d_inp, ld_dinp, (hipStream_t)stream);
-  return disc_bwd_t<bf16_t>(c, P, S, st, ws, inp_soft, ld_inp, inp_ids, train, d_logits, G, accumulate, d_inp, ld_dinp, (hipStream_t)stream);
+  return disc_bwd_entry("disc_bwd", dims, P, S, st, ws, inp_soft, ld_inp, inp_ids, train, d_logits, G, accumulate, d_inp, ld_dinp, nullptr, 0.f,
+                        nullptr, stream);
+}
+
+int gic_disc_bwd_cond(const gic_disc_dims* dims, const gic_disc_params* P, const gic_disc_shadow* S, const gic_disc_state* st,
+                      const gic_disc_bwd_ws* ws, const void* inp_soft, int64_t ld_inp, const int64_t* inp_ids, int train,
+                      const float* d_logits, const gic_disc_grads* G, int accumulate, void* d_inp, int64_t ld_dinp, const float* q, float scale,
+                      float* d_q, void* stream) {
+  return disc_bwd_entry("disc_bwd_cond", dims, P, S, st, ws, inp_soft, ld_inp, inp_ids, train, d_logits, G, accumulate, d_inp, ld_dinp, q, scale,
+                        d_q, stream);
 }
 
 }  // extern "C"

@@ -52,4 +52,9 @@ int gumbel_softmax_rows(int dt, float* logits, const float* u, uint64_t seed, ui
                         long rows, int V, hipStream_t stream);
 int embed_scatter_time(const float* dx, long ld, const int64_t* ids, float* d_embed, int B, int L, int E, int V, hipStream_t stream, long ids_stride = 0);
 
+// disc_cond.hip: the conditioned discriminator's match-term backward for disc_bwd_t (disc.hip): dydrop[m, :] = scale g[m] q[m / R, :]
+// (f32 [B*R, Fp], pad columns zero) and, when d_q is not null, d_q[b, :] = scale sum_r g[b R + r] ydrop[b R + r, :F] (f32 [B, F])
+int disc_match_bwd(int dt, const void* ydrop, const float* q, const float* g, float scale, float* dydrop, float* d_q, int B, int R, int F,
+                   int Fp, hipStream_t stream);
+
 }  // namespace gic

@@ -4,6 +4,11 @@ state-dict keys (src/discriminator.py:9-86), computing through libgicap.so.
 ``forward(inp)`` accepts the reference's dense ``[B, L, V]`` float tensor (soft captions or a
 one-hot) and, as an extension, ``int64 [B, L]`` token ids (the one-hot product evaluated as a
 gather).  Gradients flow to the parameters and to a dense ``inp``.
+
+``--disc-cond projection`` (no reference counterpart) makes D score (image, caption) pairs in the
+projection form of Miyato & Koyama: ``logits += F^-1/2 <y, img_proj(pooled trunk feature)>`` with
+``y`` the dropped highway output that ``feature2out`` consumes.  ``forward`` then takes the pooled
+trunk features as ``image_features`` (detached: no gradient reaches the trunk or G's encoder head).
 """
 from __future__ import annotations
 
@@ -44,6 +49,62 @@ class _DiscFn(torch.autograd.Function):
         return (None, None, None, None, None, d_inp, *pg)
 
 
+class _DiscCondFn(torch.autograd.Function):
+    """_DiscFn with the projection match term: q = img_proj(pooled), logits += F^-1/2 <ydrop, q>."""
+
+    @staticmethod
+    def forward(ctx, eng, train, keep_mask, seed, want_param_grads, inp, pooled, proj_w, proj_b, *params):
+        dparams = [p.detach() for p in params]
+        is_ids = inp.dtype == torch.int64
+        soft = None if is_ids else eng.soft_input(inp.detach())
+        ids = inp if is_ids else None
+        q, pooled_act = eng.img_proj_fwd(proj_w.detach(), proj_b.detach(), pooled.detach())
+        logits, st = eng.fwd(dparams, soft, ids, train, keep_mask, seed, cond=q)
+        ctx.eng, ctx.train, ctx.st, ctx.dparams = eng, train, st, dparams
+        ctx.soft, ctx.ids, ctx.q, ctx.pooled = soft, ids, q, pooled_act
+        ctx.in_dtype = inp.dtype
+        ctx.want_param_grads = want_param_grads
+        return logits
+
+    @staticmethod
+    def backward(ctx, d_logits):
+        want_inp = ctx.needs_input_grad[5] and ctx.soft is not None
+        want_par = ctx.want_param_grads and any(ctx.needs_input_grad[7:])
+        grads, d_inp, d_q = ctx.eng.bwd(ctx.dparams, ctx.st, ctx.soft, ctx.ids, ctx.train, d_logits, want_par, want_inp, cond=ctx.q)
+        ctx.st = None
+        if d_inp is not None and d_inp.dtype != ctx.in_dtype:
+            d_inp = d_inp.to(ctx.in_dtype)
+        d_w = d_b = None
+        if want_par:
+            d_w = torch.empty(ctx.q.shape[1], ctx.pooled.shape[1], device=d_q.device, dtype=torch.float32)
+            d_b = torch.empty(ctx.q.shape[1], device=d_q.device, dtype=torch.float32)
+            ctx.eng.img_proj_bwd(d_q, ctx.pooled, d_w, d_b)
+        pg = grads if grads is not None else [None] * len(ctx.dparams)
+        return (None, None, None, None, None, d_inp, None, d_w, d_b, *pg)
+
+
+DISC_COND = ("none", "projection")
+
+
+def check_disc_cond(args) -> str:
+    """--disc-cond and what it needs, before any module is built."""
+    cond = getattr(args, "disc_cond", "none") or "none"
+    if cond not in DISC_COND:
+        raise ValueError(f"--disc-cond must be one of {DISC_COND}, got {cond!r}")
+    if cond == "projection":
+        if int(getattr(args, "conditional_gan", 0)) != 1:
+            raise ValueError("--disc-cond projection scores (image, caption) pairs: it needs --conditional-gan 1")
+        if getattr(args, "adv_mode", "relgan") == "seqgan":
+            raise ValueError("--disc-cond projection is not available with --adv-mode seqgan: the conditioned roll-out reward "
+                             "(reward rows that carry an image index) is a follow-up")
+        if not int(getattr(args, "real_as_ids", 1)):
+            raise ValueError("--disc-cond projection needs --real-as-ids 1: the conditioned step scores the real captions from token ids")
+        w = float(getattr(args, "disc_mismatch_weight", 0.5))
+        if not 0.0 <= w < 1.0:
+            raise ValueError(f"--disc-mismatch-weight must be in [0, 1), got {w}")
+    return cond
+
+
 class _ConvParams(nn.Module):
     """nn.Conv2d(1, n, (f, s), stride=(1, s)) parameter container (discriminator.py:22-25)."""
 
@@ -72,6 +133,11 @@ class Discriminator(nn.Module):
         self.highway = _LinearParams(self.feature_dim, self.feature_dim)
         self.feature2out = _LinearParams(self.feature_dim, 100)
         self.out2logits = _LinearParams(100, 1)
+        self.cond = check_disc_cond(args)
+        if self.cond == "projection":               # exists (state dict, param_list, arena) only when the flag is on
+            from .trunk import ARCHS
+            _, _, widths, expansion = ARCHS[getattr(args, "encoder_arch", "resnet18")]
+            self.img_proj = _LinearParams(widths[-1] * expansion, self.feature_dim)
         self.args = args
         self._engine: Optional[engine.DiscEngine] = None
         self._param_grads = True
@@ -88,8 +154,15 @@ class Discriminator(nn.Module):
         ps = [self.embeddings.weight]
         for c in self.convs:
             ps += [c.weight, c.bias]
-        return ps + [self.highway.weight, self.highway.bias, self.feature2out.weight, self.feature2out.bias,
-                     self.out2logits.weight, self.out2logits.bias]
+        ps += [self.highway.weight, self.highway.bias, self.feature2out.weight, self.feature2out.bias,
+               self.out2logits.weight, self.out2logits.bias]
+        if self.cond == "projection":               # behind the engine's parameters (DiscEngine.nparams() of them)
+            ps += [self.img_proj.weight, self.img_proj.bias]
+        return ps
+
+    def text_param_list(self) -> List[nn.Parameter]:
+        """The parameters of the caption path in the engine's order: param_list() without img_proj."""
+        return self.param_list()[:7 + 2 * len(self.convs)]
 
     @contextlib.contextmanager
     def input_grad_only(self):
@@ -102,10 +175,32 @@ class Discriminator(nn.Module):
         finally:
             self._param_grads = prev
 
-    def forward(self, inp, keep_mask=None):
-        """inp: float [B, L, V] (or int64 ids [B, L]) -> logits [B * num_rep] (discriminator.py:34-62)."""
+    def forward(self, inp, image_features=None, keep_mask=None):
+        """inp: float [B, L, V] (or int64 ids [B, L]) -> logits [B * num_rep] (discriminator.py:34-62).
+        image_features: the frozen trunk's pooled features [B, C] of the captions' images -- required by a module built with
+        --disc-cond projection, refused by any other."""
         seed = 0 if keep_mask is not None else SEEDS.next()
-        return _DiscFn.apply(self.engine(), self.training, keep_mask, seed, self._param_grads, inp, *self.param_list())
+        if self.cond != "projection":
+            if image_features is not None:
+                raise ValueError("image_features given to a discriminator built without --disc-cond projection")
+            return _DiscFn.apply(self.engine(), self.training, keep_mask, seed, self._param_grads, inp, *self.param_list())
+        if image_features is None:
+            raise ValueError("a discriminator built with --disc-cond projection needs image_features")
+        if image_features.shape[0] != inp.shape[0]:
+            raise ValueError(f"image_features has {image_features.shape[0]} rows for {inp.shape[0]} captions")
+        return _DiscCondFn.apply(self.engine(), self.training, keep_mask, seed, self._param_grads, inp, image_features.detach(),
+                                 self.img_proj.weight, self.img_proj.bias, *self.text_param_list())
+
+    def score(self, image_features, ids):
+        """Eval-mode score of (image, caption) pairs: the mean logit over the num_rep representations, [B]."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                logits = self.forward(ids, image_features)
+        finally:
+            self.train(was_training)
+        return logits.view(-1, int(self.args.disc_num_rep)).mean(1)
 
     def get_feature(self, inp):
         raise NotImplementedError("get_feature is unused by the reference trainer and broken there for num_rep > 1 "

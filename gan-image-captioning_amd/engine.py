@@ -396,6 +396,20 @@ def gan_losses(loss_type: str, d_real, d_fake, g_out, want_grads: bool = True):
     return losses, g
 
 
+def gan_losses_mismatch(w: float, losses, grads, losses_wrong, grads_wrong):
+    """gic_gan_losses_mismatch: d_loss = (1 - w) d(real, fake) + w d(real, wrong) from two ``gan_losses`` evaluations, in place:
+    ``losses[1]`` becomes the mix; ``grads["dd_real"]`` / ``["dd_fake"]`` (hence ``["dd_real_fake"]``) the mixed gradients of the real
+    and fake logits; ``grads_wrong["dd_fake"]`` the gradient of the wrong-pair logits.  ``grads`` / ``grads_wrong``: both or neither."""
+    if (grads is None) != (grads_wrong is None):
+        raise ValueError("gan_losses_mismatch: pass the gradients of both evaluations or of neither")
+    require_gpu(losses, losses_wrong)
+    g, gw = grads or {}, grads_wrong or {}
+    L.check(L.load().gic_gan_losses_mismatch(float(w), g["dd_real"].numel() if g else 1, ptr(losses), ptr(losses_wrong), ptr(g.get("dd_real")),
+                                             ptr(g.get("dd_fake")), ptr(gw.get("dd_real")), ptr(gw.get("dd_fake")), stream_ptr()),
+            "gic_gan_losses_mismatch")
+    return losses, grads, grads_wrong
+
+
 def xent(logits: torch.Tensor, targets: torch.Tensor, want_grad: bool = True, row_weight: Optional[torch.Tensor] = None):
     """CrossEntropyLoss(mean over all rows). logits [rows,V] (f32/bf16, contiguous). Returns (loss[1], d_logits|None).
     ``row_weight`` f32 [rows]: weighted form (policy-gradient loss, gicap.h)."""
@@ -974,8 +988,9 @@ class DiscEngine:
 
     def fwd(self, params, inp_soft: Optional[torch.Tensor], inp_ids: Optional[torch.Tensor], train: bool,
             keep_mask: Optional[torch.Tensor] = None, seed: int = 0, state=None, logits=None, forward_only: bool = False,
-            dev_scalars=None, seed_slot: int = 0):
-        """``dev_scalars`` / ``seed_slot``: the dropout seed is read from device memory (gic_step_scalars).  ``forward_only`` (eval mode only): nothing is saved for a backward pass (see alloc_state)."""
+            dev_scalars=None, seed_slot: int = 0, cond: Optional[torch.Tensor] = None):
+        """``dev_scalars`` / ``seed_slot``: the dropout seed is read from device memory (gic_step_scalars).  ``forward_only`` (eval mode only): nothing is saved for a backward pass (see alloc_state).
+        ``cond``: f32 [B, F], one row per caption (the image projection q of a conditioned D): the match term is added to the logits."""
         if forward_only and train:
             raise ValueError("forward_only is an eval-mode option: the train-mode forward saves its dropout mask for the backward")
         self.check_params(params)
@@ -999,7 +1014,35 @@ class DiscEngine:
             C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
             ptr(inp_soft), self.V, ptr(inp_ids), int(bool(train)), ptr(keep_mask), int(seed) & (2 ** 64 - 1), ptr(logits),
             dev_scalars.ptr if dev_scalars is not None else None, int(seed_slot), stream_ptr()), "gic_disc_fwd")
+        if cond is not None:
+            self.match_logits(st, cond, logits=logits, accumulate=True)
         return logits, st
+
+    def match_scale(self) -> float:
+        return float(self.F) ** -0.5
+
+    def _check_cond(self, q: torch.Tensor, B: int) -> torch.Tensor:
+        require_gpu(q)
+        if q.dtype != torch.float32:
+            raise ValueError("the image projection q must be float32")
+        if tuple(q.shape) != (B, self.F):
+            raise ValueError(f"the image projection q must be [captions={B}, F={self.F}], got {tuple(q.shape)}")
+        return q.contiguous()
+
+    def match_logits(self, state: dict, q: torch.Tensor, logits=None, accumulate: bool = False):
+        """gic_disc_match_fwd: the match term F^-1/2 <ydrop[m], q[m // R]> of a forward's state (a forward-only one included), alone or
+        (``accumulate``) added to ``logits``."""
+        MR = state["ydrop"].shape[0]
+        B = MR // self.R
+        q = self._check_cond(q, B)
+        if logits is None:
+            if accumulate:
+                raise ValueError("match_logits: accumulate needs logits")
+            logits = torch.empty(MR, device=q.device, dtype=torch.float32)
+        d = self.dims(B, max(self.fs))
+        L.check(L.load().gic_disc_match_fwd(C.byref(d), C.byref(self._state_struct(state)), ptr(q), self.match_scale(), int(bool(accumulate)),
+                                            ptr(logits), stream_ptr()), "gic_disc_match_fwd")
+        return logits
 
     def shared_state(self, src: dict, B: int, Lc: int, dev) -> dict:
         """State of a second forward on the same input: its own dropout / head buffers, the rest aliases ``src``."""
@@ -1010,8 +1053,8 @@ class DiscEngine:
         return st
 
     def fwd_redrop(self, params, src_state: dict, dst_state: dict, train: bool, keep_mask: Optional[torch.Tensor] = None,
-                   seed: int = 0, logits=None, dev_scalars=None, seed_slot: int = 0):
-        """gic_disc_fwd_redrop: D on the same input as the forward that filled ``src_state``, under another dropout draw."""
+                   seed: int = 0, logits=None, dev_scalars=None, seed_slot: int = 0, cond: Optional[torch.Tensor] = None):
+        """gic_disc_fwd_redrop: D on the same input as the forward that filled ``src_state``, under another dropout draw.  ``cond``: as in fwd."""
         self.check_params(params)
         MR = src_state["pooled"].shape[0]
         dev = src_state["pooled"].device
@@ -1028,6 +1071,8 @@ class DiscEngine:
             C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(src_state)),
             C.byref(self._state_struct(dst_state)), int(bool(train)), ptr(keep_mask), int(seed) & (2 ** 64 - 1), ptr(logits),
             dev_scalars.ptr if dev_scalars is not None else None, int(seed_slot), stream_ptr()), "gic_disc_fwd_redrop")
+        if cond is not None:
+            self.match_logits(dst_state, cond, logits=logits, accumulate=True)
         return logits, dst_state
 
     def split_state(self, st: dict):
@@ -1039,9 +1084,12 @@ class DiscEngine:
         return a, b
 
     def bwd(self, params, st, inp_soft, inp_ids, train: bool, d_logits: torch.Tensor, want_param_grads: bool,
-            want_input_grad: bool, grads=None, accumulate: bool = False, ws=None, d_inp=None):
+            want_input_grad: bool, grads=None, accumulate: bool = False, ws=None, d_inp=None, cond: Optional[torch.Tensor] = None, d_q=None,
+            cond_entry: bool = False):
         """Both ``inp_soft`` and ``inp_ids`` given: mixed batch (gicap.h) -- ``st`` holds the ids pass in its first half of the rows
-        and the soft pass in its second half; one backward serves both."""
+        and the soft pass in its second half; one backward serves both.
+        ``cond`` (the q the forward was given; a mixed batch: [q; q]): gic_disc_bwd_cond, and a third result ``d_q`` f32 [B, F].
+        ``cond_entry`` without ``cond``: gic_disc_bwd_cond with q = NULL (what must equal gic_disc_bwd; d_q is None)."""
         src = inp_soft if inp_soft is not None else inp_ids
         B, Lc = src.shape[0], src.shape[1]
         if inp_soft is not None and inp_ids is not None:
@@ -1062,12 +1110,49 @@ class DiscEngine:
             setattr(w, k, ptr(ws[k]))
         d = self.dims(B, Lc)
         gs = self._pstruct(grads, L.DiscGrads) if want_param_grads else None
+        if cond is not None or cond_entry:
+            if cond is not None:
+                cond = self._check_cond(cond, B)
+                d_q = d_q if d_q is not None else torch.empty(B, self.F, device=dev, dtype=torch.float32)
+            L.check(L.load().gic_disc_bwd_cond(
+                C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
+                C.byref(w), ptr(inp_soft), self.V, ptr(inp_ids), int(bool(train)), ptr(d_logits),
+                C.byref(gs) if gs is not None else None, int(bool(accumulate)), ptr(d_inp) if want_input_grad else None, self.V,
+                ptr(cond), self.match_scale(), ptr(d_q), stream_ptr()), "gic_disc_bwd_cond")
+            return (grads if want_param_grads else None), (d_inp if want_input_grad else None), d_q
         L.check(L.load().gic_disc_bwd(
             C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
             C.byref(w), ptr(inp_soft), self.V, ptr(inp_ids), int(bool(train)), ptr(d_logits),
             C.byref(gs) if gs is not None else None, int(bool(accumulate)), ptr(d_inp) if want_input_grad else None, self.V,
             stream_ptr()), "gic_disc_bwd")
         return (grads if want_param_grads else None), (d_inp if want_input_grad else None)
+
+
+    # ---- the conditioned D's image projection q = img_proj(pooled) (no kernel of its own: the generic GEMM and column sum)
+    def img_proj_fwd(self, weight: torch.Tensor, bias: torch.Tensor, pooled: torch.Tensor, out=None):
+        """q f32 [B, F] = pooled [B, C] W^T + b on the compute-dtype image of ``weight`` [F, C] (refreshed when the weight changes), f32
+        accumulate.  Returns (q, pooled in the compute dtype: what the backward reads)."""
+        require_gpu(weight, bias, pooled)
+        Fq, Cin = weight.shape
+        pooled = _to_act(pooled.reshape(pooled.shape[0], -1), self.act)
+        if Fq != self.F or pooled.shape[1] != Cin:
+            raise ValueError(f"img_proj: weight {tuple(weight.shape)} against F={self.F} and pooled features {tuple(pooled.shape)}")
+        key = _key([weight])
+        if getattr(self, "_proj_key", None) != key:
+            self._proj_w = weight if self.act == torch.float32 else cast2d(weight, torch.empty(Fq, Cin, device=weight.device, dtype=self.act), Fq, Cin, Cin, Cin)
+            self._proj_key = key
+        B = pooled.shape[0]
+        q = out if out is not None else torch.empty(B, Fq, device=pooled.device, dtype=torch.float32)
+        gemm(pooled, self._proj_w, q, B, Fq, Cin, Cin, Cin, Fq, True, True, bias=bias)
+        return q, pooled
+
+    def img_proj_bwd(self, d_q: torch.Tensor, pooled: torch.Tensor, d_weight: torch.Tensor, d_bias: torch.Tensor, accumulate: bool = False):
+        """d_weight [F, C] (+)= d_q^T pooled, d_bias [F] (+)= colsum(d_q): f32 products over the B captions."""
+        B, Fq = d_q.shape
+        Cin = pooled.shape[1]
+        p32 = _to_act(pooled, torch.float32)
+        gemm(d_q, p32, d_weight, Fq, Cin, B, Fq, Cin, Cin, False, False, accumulate=accumulate)
+        L.check(L.load().gic_colsum(ptr(d_q), L.F32, Fq, B, Fq, ptr(d_bias), int(bool(accumulate)), stream_ptr()), "gic_colsum")
 
 
 # ------------------------------------------------------------------------------------------ fused clip + Adam

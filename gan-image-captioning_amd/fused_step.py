@@ -27,6 +27,9 @@ class FusedAdvStep:
         self.gen_arena, self.disc_arena = gen_arena, disc_arena
         self.reducer = reducer
         self.cgan = int(args.conditional_gan) == 1
+        # --disc-cond projection: every D pass also takes q = img_proj(pooled trunk features); w > 0 adds the mismatched-pair pass
+        self.cond = getattr(disc, "cond", "none") == "projection"
+        self.mismatch_w = float(getattr(args, "disc_mismatch_weight", 0.5)) if self.cond else 0.0
         self.attn = hasattr(gen.decoder, "attn")         # visual-attention decoder (cfg4): the roll-out also takes the trunk's feature map
         self.dec = gen.decoder.engine()
         self.den = disc.engine()
@@ -41,6 +44,8 @@ class FusedAdvStep:
         # (GIC_STEP_GRAPH_ATTN=1): host enqueue 2.10 -> 0.43 ms per step, but 3.87 ms per step against 3.74 for eager launches at cfg4.
         want = os.environ.get("GIC_STEP_GRAPH_ATTN" if self.attn else "GIC_STEP_GRAPH")
         self.use_graph = bool(want) and not (os.environ.get("GIC_NO_STEP_GRAPH") or os.environ.get("GIC_NO_GRAPH"))
+        if self.cond:
+            self.use_graph = False               # the conditioned step is not captured: eager launches
         self._graphs: Dict[tuple, dict] = {}
         self._warm: set = set()
 
@@ -72,6 +77,15 @@ class FusedAdvStep:
             self._buf[key]["st_real"], self._buf[key]["st_fake"] = den.split_state(self._buf[key]["st_rf"])
             # D(gen) sees the same input as D(fake) (training.py:163-164): it shares everything up to the dropout draw
             self._buf[key]["st_gen"] = den.shared_state(self._buf[key]["st_fake"], B, L, dev)
+            if self.cond:
+                f32 = torch.float32
+                self._buf[key]["logits"] = torch.empty(4, B * den.R, device=dev, dtype=f32)         # real, fake, gen, wrong
+                self._buf[key]["q2"] = torch.empty(2 * B, den.F, device=dev, dtype=f32)             # [q; q] of the mixed real | fake batch
+                self._buf[key]["d_q"] = torch.empty(3 * B, den.F, device=dev, dtype=f32)            # d_q of real | fake | wrong
+                self._buf[key]["d_q_gen"] = torch.empty(B, den.F, device=dev, dtype=f32)
+                if self.mismatch_w > 0.0:
+                    self._buf[key]["st_wrong"] = den.alloc_state(B, L, dev)
+                    self._buf[key]["disc_ws_wrong"] = den.alloc_bwd_ws(B, L, dev)
         return self._buf[key]
 
     def _early_bucket(self):
@@ -114,6 +128,8 @@ class FusedAdvStep:
         keeps the eager launches either way.  Returned tensors
         of a replayed step live in the graphs' memory pools and are overwritten by the next step."""
         B, L = captions.shape[0], int(max_caption_len)
+        if self.mismatch_w > 0.0 and B < 2:
+            raise ValueError("--disc-mismatch-weight > 0 needs at least two captions per batch: the wrong pair is the next image of the batch")
         engine.require_gpu(captions, images)
         if (self.use_graph and train and opt_step and noise_u is None and keep_masks is None and self.reducer is None and self.overlap
                 and self.trace is None):
@@ -123,6 +139,9 @@ class FusedAdvStep:
         km = keep_masks if keep_masks is not None else (None, None, None)
         seeds = [0 if km[i] is not None else SEEDS.next() for i in range(3)]
         seeds.append(0 if noise_u is not None else SEEDS.next())
+        if self.mismatch_w > 0.0:                # the mismatched-pair pass: a fourth keep mask / dropout seed
+            km = tuple(km) + (None,) * (4 - len(km))
+            seeds.append(0 if km[3] is not None else SEEDS.next())
         ev_start = main.record_event()
         self._mark("start", main)
         trunk = (lambda: self._take_and_prefetch(images, train, main, ev_start, next_images, next_train)) if self.cgan else None
@@ -148,6 +167,12 @@ class FusedAdvStep:
         gparams = [p.detach() for p in gen.decoder.param_list()]
         dparams = [p.detach() for p in disc.param_list()]
         g_grads, d_grads = self._grad_lists()
+        cond = self.cond
+        if cond:                         # the engine's parameters first, img_proj behind them (Discriminator.param_list)
+            n_text = self.den.nparams()
+            (proj_w, proj_b), (proj_gw, proj_gb) = dparams[n_text:], d_grads[n_text:]
+            dparams, d_grads = dparams[:n_text], d_grads[:n_text]
+        q = None
         d_train = bool(train)            # dropout active in train mode only (disc.train()/eval(), training.py:215,219)
         overlap = self.overlap
         s_real, s_gen = self._streams(dev) if overlap else (main, main)
@@ -197,11 +222,23 @@ class FusedAdvStep:
 
         # ---- D(fake), D(gen) (training.py:163-164): one pass up to the highway layer, two dropout draws + heads
         main.wait_event(ev_dprep)
-        self.den.fwd(dparams, probs, None, d_train, km[1], seeds[1], state=buf["st_fake"], logits=lg[1], dev_scalars=scal, seed_slot=1)
-        self.den.fwd_redrop(dparams, buf["st_fake"], buf["st_gen"], d_train, km[2], seeds[2], logits=lg[2], dev_scalars=scal, seed_slot=2)
+        if cond:                                 # q = img_proj(pooled trunk features), detached: the step already owns them
+            q, pooled = self.den.img_proj_fwd(proj_w, proj_b, trunk_feats)
+        self.den.fwd(dparams, probs, None, d_train, km[1], seeds[1], state=buf["st_fake"], logits=lg[1], dev_scalars=scal, seed_slot=1, cond=q)
+        self.den.fwd_redrop(dparams, buf["st_fake"], buf["st_gen"], d_train, km[2], seeds[2], logits=lg[2], dev_scalars=scal, seed_slot=2, cond=q)
         self._mark("D(fake), D(gen) fwd done", main)
         main.wait_event(ev_real)
+        if cond:                                 # D(real)'s text path ran on its stream before the features existed: its match term now
+            self.den.match_logits(buf["st_real"], q, logits=lg[0], accumulate=True)
         losses, lgrads = engine.gan_losses(a.adv_loss_type, lg[0], lg[1], lg[2], want_grads=train)
+        lgrads_w = None
+        if self.mismatch_w > 0.0:
+            # mismatched pairs: the real captions against the batch's images rolled by one -- a third D pass with its own state and
+            # dropout draw; d_loss = (1 - w) d(real, fake) + w d(real, wrong), g_loss as it was
+            q_wrong = torch.roll(q, -1, 0)
+            self.den.fwd(dparams, real_soft, real_ids, d_train, km[3], seeds[4], state=buf["st_wrong"], logits=lg[3], cond=q_wrong)
+            losses_w, lgrads_w = engine.gan_losses(a.adv_loss_type, lg[0], lg[3], lg[2], want_grads=train)
+            engine.gan_losses_mismatch(self.mismatch_w, losses, lgrads, losses_w, lgrads_w)
         out = {"losses": losses, "ids": ids, "probs": probs, "logits": lg}
         if not train:
             return out
@@ -217,8 +254,13 @@ class FusedAdvStep:
                 self.gen_arena.grad.zero_()                        # utils.py:48: g_loss has no path to G
                 ev_dgen = s_gen.record_event()
             else:
-                self.den.bwd(dparams, buf["st_gen"], probs, None, d_train, lgrads["dg_out"], False, True,
-                             ws=buf["disc_ws_gen"], d_inp=buf["d_probs"])
+                if cond:
+                    q.record_stream(s_gen)
+                    self.den.bwd(dparams, buf["st_gen"], probs, None, d_train, lgrads["dg_out"], False, True,
+                                 ws=buf["disc_ws_gen"], d_inp=buf["d_probs"], cond=q, d_q=buf["d_q_gen"])
+                else:
+                    self.den.bwd(dparams, buf["st_gen"], probs, None, d_train, lgrads["dg_out"], False, True,
+                                 ws=buf["disc_ws_gen"], d_inp=buf["d_probs"])
                 ev_dgen = s_gen.record_event()                     # D's weights are free to change from here on
                 self._mark("D(gen) input-grad done [s_gen]", s_gen)
                 early = self._early_bucket() if (self.reducer is not None and not self.attn) else None
@@ -245,7 +287,21 @@ class FusedAdvStep:
 
         # ---- D path on the main stream: d_loss -> D parameters (training.py:168), then D's clip + Adam
         self.disc_arena.grad.zero_()          # ONE fill; both passes accumulate (instead of a fill per small gradient tensor)
-        if real_ids is not None:                # real (ids) and fake (soft) passes differentiated as one batch of 2B captions
+        if cond:
+            # the conditioned D (real_ids only, check_disc_cond): the mixed real | fake backward with [q; q], then the wrong pass's own;
+            # d_q of the three passes in one buffer, and d img_proj = d_q^T pooled over [pooled; pooled; rolled pooled]
+            torch.cat([q, q], 0, out=buf["q2"])
+            d_q = buf["d_q"]
+            self.den.bwd(dparams, buf["st_rf"], probs, real_ids, d_train, lgrads["dd_real_fake"], True, False,
+                         grads=d_grads, accumulate=True, ws=buf["disc_ws"], cond=buf["q2"], d_q=d_q[:2 * B])
+            if lgrads_w is not None:
+                self.den.bwd(dparams, buf["st_wrong"], real_soft, real_ids, d_train, lgrads_w["dd_fake"], True, False,
+                             grads=d_grads, accumulate=True, ws=buf["disc_ws_wrong"], cond=q_wrong, d_q=d_q[2 * B:])
+                pooled3 = torch.cat([pooled, pooled, torch.roll(pooled, -1, 0)], 0)
+            else:
+                d_q, pooled3 = d_q[:2 * B], torch.cat([pooled, pooled], 0)
+            self.den.img_proj_bwd(d_q, pooled3, proj_gw, proj_gb, accumulate=True)
+        elif real_ids is not None:              # real (ids) and fake (soft) passes differentiated as one batch of 2B captions
             self.den.bwd(dparams, buf["st_rf"], probs, real_ids, d_train, lgrads["dd_real_fake"], True, False,
                          grads=d_grads, accumulate=True, ws=buf["disc_ws"])
         else:                                   # --real-as-ids 0: two dense passes

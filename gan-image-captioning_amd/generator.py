@@ -477,6 +477,7 @@ class Encoder(nn.Module):
             if next_images is not None:
                 self.prefetch_trunk(next_images, self.training, start)
         feats = feats.reshape(feats.size(0), -1)
+        self.last_trunk = feats                                      # the pooled trunk features of this call (a conditioned D reads them)
         return _EncoderHeadFn.apply(_compute_dtype(self.args), self.training, self.bn.momentum, self.bn.eps, feats,
                                     self.linear.weight, self.linear.bias, self.bn.weight, self.bn.bias,
                                     self.bn.running_mean, self.bn.running_var)
@@ -505,6 +506,7 @@ class Encoder(nn.Module):
             if next_images is not None:
                 self.prefetch_trunk(next_images, self.training, start, want_map=True)
         feats = feats.reshape(feats.size(0), -1)
+        self.last_trunk = feats
         out = _EncoderHeadFn.apply(_compute_dtype(self.args), self.training, self.bn.momentum, self.bn.eps, feats,
                                    self.linear.weight, self.linear.bias, self.bn.weight, self.bn.bias,
                                    self.bn.running_mean, self.bn.running_var)

@@ -278,7 +278,12 @@ class GANInstructor:
 
     def _adv_step_autograd(self, images, captions, max_caption_len, train, noise_u=None, keep_masks=None, next_images=None):
         """The reference's flow through the module API + autograd, with the fixed order."""
-        km = keep_masks if keep_masks is not None else (None, None, None)
+        km = tuple(keep_masks) if keep_masks is not None else (None, None, None)
+        km = km + (None,) * (4 - len(km))
+        cond = self.disc.cond == "projection"
+        w = float(getattr(self.args, "disc_mismatch_weight", 0.5)) if cond else 0.0
+        if w > 0.0 and captions.shape[0] < 2:
+            raise ValueError("--disc-mismatch-weight > 0 needs at least two captions per batch: the wrong pair is the next image of the batch")
         with (torch.enable_grad() if train else torch.no_grad()):
             features = self._features(images, captions.shape[0], next_images if self.cgan else None)
             if self.attention:
@@ -290,11 +295,17 @@ class GANInstructor:
                 real = captions
             else:
                 real = F.one_hot(captions, self.args.vocab_size).float()                     # training.py:158
-            d_out_real = self.disc(real, keep_mask=km[0])                                    # training.py:162
-            d_out_fake = self.disc(fake_captions, keep_mask=km[1])                           # training.py:163
+            # --disc-cond projection: every D pass also sees the pooled trunk features of the batch's images (detached)
+            img = {"image_features": self.gen.encoder.last_trunk} if cond else {}
+            d_out_real = self.disc(real, keep_mask=km[0], **img)                             # training.py:162
+            d_out_fake = self.disc(fake_captions, keep_mask=km[1], **img)                    # training.py:163
             with self.disc.input_grad_only():
-                g_out = self.disc(gen_captions, keep_mask=km[2])                             # training.py:164
+                g_out = self.disc(gen_captions, keep_mask=km[2], **img)                      # training.py:164
             g_loss, d_loss = get_losses(d_out_real, d_out_fake, g_out, self.args.adv_loss_type, detach_d_for_g=True)
+            if w > 0.0:         # mismatched pairs: the real captions against the batch's images rolled by one, its own dropout draw
+                d_out_wrong = self.disc(real, image_features=torch.roll(img["image_features"], -1, 0), keep_mask=km[3])
+                _, d_wrong = get_losses(d_out_real, d_out_wrong, g_out, self.args.adv_loss_type, detach_d_for_g=True)
+                d_loss = (1.0 - w) * d_loss + w * d_wrong
         if train:
             self.disc_opt.zero_grad()
             self.gen_opt.zero_grad()
@@ -340,7 +351,15 @@ class GANInstructor:
         ckpt = torch.load(path, map_location=self.args.device)
         if isinstance(ckpt, dict) and set(ckpt) == {"generator", "discriminator"}:
             self.gen.load_state_dict(ckpt["generator"])
-            self.disc.load_state_dict(ckpt["discriminator"])
+            d_state = ckpt["discriminator"]
+            proj = ("img_proj.weight", "img_proj.bias")
+            if self.disc.cond == "projection" and not any(k in d_state for k in proj):
+                # a checkpoint of an unconditioned D: the text path loads, the image projection keeps its fresh initialisation
+                # (every other key mismatch stays an error)
+                own = self.disc.state_dict()
+                d_state = dict(d_state, **{k: own[k] for k in proj})
+                self.log.info("checkpoint %s holds no img_proj.*: the discriminator's image projection keeps its fresh initialisation", path)
+            self.disc.load_state_dict(d_state)
             kind = "adversarial"
         else:
             self.gen.load_state_dict(ckpt)
@@ -431,6 +450,8 @@ class GANInstructor:
                 self.evaluate_diversity("val", num_samples=int(self.args.eval_num_samples), top_k=int(getattr(self.args, "eval_top_k", 0)),
                                         top_p=float(getattr(self.args, "eval_top_p", 1.0)),
                                         temperature=float(getattr(self.args, "eval_sample_temperature", 1.0)))
+            if int(getattr(self.args, "eval_match", 0)) and self.dist.rank == 0:
+                self.evaluate_match("val")
             if int(getattr(self.args, "eval_diverse_beam_size", 0)) > 0 and self.dist.rank == 0:
                 self.evaluate_diverse_beam("val", beam_size=int(self.args.eval_diverse_beam_size),
                                            groups=int(getattr(self.args, "eval_diverse_groups", 2)),
@@ -457,6 +478,41 @@ class GANInstructor:
         self.log.info("[EVAL] BLEU-4 (%s, beam %d): %.4f", what, beam_size, score)
         self.writer.add_scalar(f"BLEU4_{what}", score, max(self.adv_epoch, 0))
         return score
+
+    def evaluate_match(self, what="val"):
+        """Image-caption match of the conditioned D (--disc-cond projection) over the adversarial eval (``what="val"``) or train loader:
+        per caption the match term F^-1/2 <y, q> (mean over the representations) with its own image against the batch's next image
+        (rolled by one).  Returns {"pair_acc": the share of captions whose own image scores strictly higher (a tie is no win),
+        "margin": the mean difference}.  Per batch one eval forward of D (forward only) and two gic_disc_match_fwd; the sums stay on the
+        device and are read with one sync.  Logs the values and writes the scalars ``MatchAcc_<what>`` / ``MatchMargin_<what>``."""
+        if self.disc.cond != "projection":
+            raise ValueError("evaluate_match needs a discriminator built with --disc-cond projection")
+        loader = self.adv_eval_loader if what == "val" else self.adv_train_loader
+        dev = self.args.device
+        den = self.disc.engine()
+        R = int(self.args.disc_num_rep)
+        sums = torch.zeros(2, dtype=torch.float64, device=dev)           # wins, sum of differences
+        n = 0
+        with torch.no_grad():
+            dparams = [p.detach() for p in self.disc.text_param_list()]
+            wp, bp = self.disc.img_proj.weight.detach(), self.disc.img_proj.bias.detach()
+            for batch in loader:
+                images, captions = batch[0].to(dev), batch[1].to(dev)
+                main = torch.cuda.current_stream(images.device)
+                q, _ = den.img_proj_fwd(wp, bp, self.gen.encoder.take_trunk(images, False, main))
+                _, st = den.fwd(dparams, None, captions, False, forward_only=True)
+                own = den.match_logits(st, q).view(-1, R).mean(1)
+                other = den.match_logits(st, torch.roll(q, -1, 0)).view(-1, R).mean(1)
+                diff = (own - other).double()
+                sums += torch.stack([(diff > 0).sum().double(), diff.sum()])
+                n += captions.shape[0]
+        wins, total = sums.tolist() if n else (0.0, 0.0)                  # the one sync
+        out = {"pair_acc": wins / n if n else 0.0, "margin": total / n if n else 0.0}
+        self.log.info("[EVAL] match (%s): pair accuracy %.4f | margin %.6f", what, out["pair_acc"], out["margin"])
+        step = max(self.adv_epoch, 0)
+        self.writer.add_scalar(f"MatchAcc_{what}", out["pair_acc"], step)
+        self.writer.add_scalar(f"MatchMargin_{what}", out["margin"], step)
+        return out
 
     def _eval_constraints(self):
         """The decode constraints of every evaluation (--eval-no-repeat-ngram, --eval-min-length, --eval-suppress-tokens) as the

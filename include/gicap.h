@@ -632,6 +632,27 @@ int gic_disc_bwd(const gic_disc_dims* dims, const gic_disc_params* params, const
                  const int64_t* inp_ids, int train, const float* d_logits, const gic_disc_grads* grads,
                  int accumulate, void* d_inp, int64_t ld_dinp, void* stream);
 
+/* Image-conditioned discriminator (--disc-cond projection; no reference counterpart): the projection match term
+ *   logits[m] (+)= scale * sum_{n<F} ydrop[m, n] * q[m / R, n]       q: f32 [B, F], one row per caption; scale = F^-1/2
+ * on state->ydrop of a gic_disc_fwd / gic_disc_fwd_redrop pass (a forward-only state included: only ydrop is read).
+ * accumulate != 0 adds to logits (the conditioned forward = gic_disc_fwd, then this), else logits is overwritten with the term alone. */
+int gic_disc_match_fwd(const gic_disc_dims* dims, const gic_disc_state* state, const float* q, float scale, int accumulate,
+                       float* logits, void* stream);
+/* gic_disc_bwd of logits that carry the match term: additionally d ydrop[m, :] += scale * d_logits[m] * q[m / R, :] before the highway
+ * backward, and d_q[b, :] = scale * sum_r d_logits[b R + r] * ydrop[b R + r, :F] (f32 [B, F], overwritten; may be NULL), summed in row
+ * order without atomics (the same bits in and out of deterministic mode).  A mixed batch passes q of its 2 * (B/2) captions.
+ * q == NULL (then d_q must be NULL): exactly gic_disc_bwd. */
+int gic_disc_bwd_cond(const gic_disc_dims* dims, const gic_disc_params* params, const gic_disc_shadow* shadow,
+                      const gic_disc_state* state, const gic_disc_bwd_ws* ws, const void* inp_soft, int64_t ld_inp,
+                      const int64_t* inp_ids, int train, const float* d_logits, const gic_disc_grads* grads,
+                      int accumulate, void* d_inp, int64_t ld_dinp, const float* q, float scale, float* d_q, void* stream);
+/* The D loss with mismatched pairs, d_loss = (1 - w) d(real, fake) + w d(real, wrong), from two gic_gan_losses evaluations a =
+ * (real, fake) and b = (real, wrong), in place: losses_a[1] becomes the mix, dd_real_a the mixed gradient w.r.t. the real logits,
+ * dd_fake_a is scaled by 1 - w and dd_fake_b (the gradient w.r.t. the wrong-pair logits) by w.  0 <= w < 1.  The four gradient
+ * vectors (f32 [n]) are all given or all NULL. */
+int gic_gan_losses_mismatch(float w, int64_t n, float* losses_a, const float* losses_b, float* dd_real_a, float* dd_fake_a,
+                            const float* dd_real_b, float* dd_fake_b, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Encoder (src/generator.py:8-25): ResNet trunk forward (frozen, BatchNorm on batch statistics) and the trainable
  * Linear + BatchNorm1d(momentum=0.01) head.  Activations are NHWC in the compute dtype ("act").
