@@ -2,6 +2,30 @@
 import torch
 
 from oracle import cpu_step as O
+from tests.disc_cases import SENTINEL
+
+U8_SENTINEL = 0xA5
+
+
+class Guarded:
+    """[rows, ld] with sentinel guard rows on either side (whole 16-byte multiples, so the live part keeps the allocation's
+    alignment); `off`: the live part starts that many elements later (a deliberately misaligned view)."""
+
+    def __init__(self, rows, ld, dtype, dev, fill, off=0):
+        esz = torch.empty((), dtype=dtype).element_size()
+        g = 1
+        while (g * ld * esz) % 16:
+            g += 1
+        self.sent = U8_SENTINEL if dtype == torch.uint8 else SENTINEL
+        self.flat = torch.full(((rows + 2 * g) * ld + off,), self.sent, dtype=dtype, device=dev)
+        self.lo = g * ld + off
+        self.live = self.flat[self.lo:self.lo + rows * ld].view(rows, ld) if ld > 1 else self.flat[self.lo:self.lo + rows]
+        self.live.fill_(fill)
+
+    def guards_intact(self):
+        n = self.live.numel()
+        outside = torch.cat([self.flat[:self.lo], self.flat[self.lo + n:]])
+        return bool((outside == self.sent).all())
 
 
 def dec_param_names(nl):

@@ -29,12 +29,12 @@ import torch
 from gan_image_captioning_amd import _lib as L
 from tests import disc_cases as D
 from tests.disc_cases import CASES, HIGHWAY, TD
+from tests.gpu_util import U8_SENTINEL, Guarded
 
 pytestmark = pytest.mark.gpu
 
 DT = {"f32": L.F32, "bf16": L.BF16}
 EXACT_SEED, ROUND_SEED = 101, 202
-U8_SENTINEL = 0xA5
 MAXIMA = {}          # (stage, kernel) -> largest err / bound: recorded, never asserted against
 
 
@@ -56,27 +56,6 @@ def _report_maxima():
     for key in sorted(MAXIMA):
         print(f"\n[disc stages] err/bound max {MAXIMA[key]:.4f}  {key[0]:<12} {key[1]}", end="")
     print()
-
-
-class Guarded:
-    """[rows, ld] with sentinel guard rows on either side (whole 16-byte multiples, so the live part keeps the allocation's
-    alignment); `off`: the live part starts that many elements later (a deliberately misaligned view)."""
-
-    def __init__(self, rows, ld, dtype, dev, fill, off=0):
-        esz = torch.empty((), dtype=dtype).element_size()
-        g = 1
-        while (g * ld * esz) % 16:
-            g += 1
-        self.sent = U8_SENTINEL if dtype == torch.uint8 else D.SENTINEL
-        self.flat = torch.full(((rows + 2 * g) * ld + off,), self.sent, dtype=dtype, device=dev)
-        self.lo = g * ld + off
-        self.live = self.flat[self.lo:self.lo + rows * ld].view(rows, ld) if ld > 1 else self.flat[self.lo:self.lo + rows]
-        self.live.fill_(fill)
-
-    def guards_intact(self):
-        n = self.live.numel()
-        outside = torch.cat([self.flat[:self.lo], self.flat[self.lo + n:]])
-        return bool((outside == self.sent).all())
 
 
 def make_engine(E, case, monkeypatch):
