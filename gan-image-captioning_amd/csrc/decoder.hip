@@ -562,7 +562,6 @@ int sample_bwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
   // 3. BPTT
   bool fused = decoder_step_supported(c.dt, 4, 8, H, NL) && H % 2 == 0 && B <= decoder_step_max_rows();
   for (int l = 0; l < NL; ++l) fused = fused && S->wcat_t[l] != nullptr;
-  for (int l = 0; l < NL; ++l) GIC_PROPAGATE(fill_zero(ws->dc[l], (size_t)B * H * sizeof(float), stream));
   if (fused) {
     // one launch per (step, layer): the recurrent (and, below the top layer, the upper layer's input) gradient product fused with
     // the cell's pointwise backward (decoder_step.h); the x-side input gradients leave the serial chain as ONE product afterwards
@@ -574,7 +573,8 @@ int sample_bwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
         if (t + 1 < L) { a.dg_next = (TA*)ws->dgates[l] + (long)(t + 1) * B * 4 * H; a.w_rec = (TA*)S->wcat_t[l] + (long)c.din(l) * 4 * H; }
         a.gates = st->gates[l] + (long)t * B * 4 * H;
         a.c_prev = st->c[l] + (long)t * B * H; a.c_cur = st->c[l] + (long)(t + 1) * B * H;
-        a.dc_state = ws->dc[l]; a.dgates = (TA*)ws->dgates[l] + (long)t * B * 4 * H;
+        a.dc_state = ws->dc[l]; a.dc_zero = t == L - 1;      // (no zero fill of dc in front of the chain)
+        a.dgates = (TA*)ws->dgates[l] + (long)t * B * 4 * H;
         a.B = B; a.H = H;
         GIC_PROPAGATE(lstm_bwd_step(a, c.dt, stream));
       }
@@ -595,6 +595,7 @@ int sample_bwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
     }
   } else {
   for (int l = 0; l < NL; ++l) {
+    GIC_PROPAGATE(fill_zero(ws->dc[l], (size_t)B * H * sizeof(float), stream));
     // all L+1 slots at once: slot L is the zero gradient behind the last step, slots < L are split-K accumulators
     GIC_PROPAGATE(fill_zero(ws->dxh[l], (size_t)(L + 1) * B * c.ldx(l) * sizeof(float), stream));
   }
@@ -627,6 +628,17 @@ int sample_bwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
     GemmDesc w;
     w.A = ws->dgates[l]; w.lda = 4 * H; w.a_kc = 0; w.b_kc = 0; w.ldb = ld;
     w.M = 4 * H; w.K = (int)BL; w.in_dtype = c.dt; w.out_dtype = DT_F32;
+    {  // dW_ih | dW_hh as ONE product over xh = [x | h] with the two bias gradients as its A column sums, where the kernel folds them and
+       // din sits on a tile boundary; else the two products and the column-sum pass
+      GemmDesc m = w;
+      m.B = st->xh[l]; m.N = (int)ld; m.C = G->w_ih[l]; m.ldc = c.din(l); m.C2 = G->w_hh[l]; m.ldc2 = H; m.n_split = c.din(l);
+      m.wgrad = 1; m.a_sum = G->b_ih[l]; m.a_sum2 = G->b_hh[l];
+      const int tn = wgrad_tile_n(m);
+      if (tn && c.din(l) % tn == 0 && wgrad_folds_a_sum(m)) {
+        GIC_PROPAGATE(gemm(m, stream));
+        continue;
+      }
+    }
     w.B = st->xh[l]; w.N = c.din(l); w.C = G->w_ih[l]; w.ldc = c.din(l);
     GIC_PROPAGATE(gemm(w, stream));
     w.B = (const TA*)st->xh[l] + c.din(l); w.N = H; w.C = G->w_hh[l]; w.ldc = H;
@@ -650,6 +662,34 @@ __global__ void embed_scatter_time_kernel(const float* __restrict__ dxh0, long l
     long id = ids[(long)b * ids_stride + (t - 1)];
     id = id < 0 ? 0 : (id >= V ? V - 1 : id);
     atomicAdd(&dw[id * E + e], dxh0[((long)t * B + b) * ld + e]);
+  }
+}
+
+// The same scatter with one wave per (t, b) row (E % 4 == 0, 16-byte aligned dx rows): the row's id is read and clamped once, dx comes
+// in 16-byte loads, and a wave's 256 loaded elements go out as four atomicAdd instructions whose 64 lanes sit on consecutive addresses
+// (lane i of instruction j takes element 64 j + i from lane 16 j + i / 4).  Row r = (t - 1) * B + b reads dx row r + B.
+__global__ __launch_bounds__(256) void embed_scatter_rows_kernel(const float* __restrict__ dxh0, long ld, const int64_t* __restrict__ ids, long ids_stride,
+                                                                 float* __restrict__ dw, int B, int L, int E, int V) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= (long)(L - 1) * B) return;                       // (wave-uniform)
+  const int tm1 = (int)(r / B), b = (int)(r - (long)tm1 * B);
+  long id = ids[(long)b * ids_stride + tm1];
+  id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+  const float* __restrict__ src = dxh0 + (r + B) * ld;
+  float* __restrict__ dst = dw + id * E;
+  const int src_lane = lane >> 2, comp = lane & 3;
+  for (int e0 = 0; e0 < E; e0 += 256) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (e0 + 4 * lane < E) v = *(const float4*)(src + e0 + 4 * lane);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float x = __shfl(v.x, 16 * j + src_lane, 64), y = __shfl(v.y, 16 * j + src_lane, 64);
+      const float z = __shfl(v.z, 16 * j + src_lane, 64), w = __shfl(v.w, 16 * j + src_lane, 64);
+      const float val = comp == 0 ? x : (comp == 1 ? y : (comp == 2 ? z : w));
+      const int e = e0 + 64 * j + lane;
+      if (e < E) atomicAdd(dst + e, val);
+    }
   }
 }
 
@@ -690,8 +730,10 @@ int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, co
   GemmDesc w;
   w.A = dlog; w.lda = V; w.a_kc = 0; w.B = hout; w.ldb = H; w.b_kc = 0; w.C = d_wout; w.ldc = H;
   w.M = V; w.N = H; w.K = (int)BL; w.in_dtype = dt; w.out_dtype = DT_F32;
+  w.wgrad = 1; w.a_sum = d_bout;       // db_out = colsum(d_logits), out of the A operand this product stages anyway
+  const bool folded = wgrad_folds_a_sum(w);
   GIC_PROPAGATE(gemm(w, stream));
-  return colsum(dlog, dt, V, BL, V, d_bout, nullptr, 0, stream);
+  return folded ? GIC_OK : colsum(dlog, dt, V, BL, V, d_bout, nullptr, 0, stream);
 }
 
 // ---- the generic roll-out's per-step launches, shared with the attention decoder's roll-out (attn_rollout.hip)
@@ -771,7 +813,11 @@ int embed_scatter_time(const float* dx, long ld, const int64_t* ids, float* d_em
   GIC_PROPAGATE(fill_zero(d_embed, (size_t)V * E * sizeof(float), stream));
   if (L > 1 && det_mode())
     return det_scatter(dx, DT_F32, ld, B, ids, B, ids_stride, 1, (long)(L - 1) * B, d_embed, E, 1, E, V, stream);
-  if (L > 1) {
+  if (L > 1 && E % 4 == 0 && ld % 4 == 0 && ((uintptr_t)dx & 15) == 0) {
+    const long rows = (long)(L - 1) * B;
+    hipLaunchKernelGGL(embed_scatter_rows_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, stream, dx, ld, ids, ids_stride, d_embed, B, L, E, V);
+    GIC_CHECK_LAUNCH("embed_scatter_rows");
+  } else if (L > 1) {
     const long total = (long)(L - 1) * B * E;
     const int grid = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
     hipLaunchKernelGGL(embed_scatter_time_kernel, dim3(grid), dim3(256), 0, stream, dx, ld, ids, ids_stride, d_embed, B, L, E, V);

@@ -101,6 +101,8 @@ struct LstmBwdStepArgs {
   const float* gates = nullptr;                         // [B, 4H] post-activation i,f,g,o of step t
   const float* c_prev = nullptr; const float* c_cur = nullptr;   // [B, H]
   float* dc_state = nullptr;                            // [B, H] in/out
+  int dc_zero = 0;                                      // != 0: dc_state is taken as zero instead of read (the first step of a chain, t = L-1:
+                                                        // no zero fill in front of the chain); it is written as always
   void* dgates = nullptr;                               // act [B, 4H] out
   int B = 0, H = 0;
 };

@@ -735,7 +735,8 @@ __global__ __launch_bounds__(512) void lstm_bwd_step_kernel(const LstmBwdStepArg
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) p_g[g] = a.gates[(long)pb * K + g * a.H + pj];
-    p_cc = a.c_cur[pbh]; p_cp = a.c_prev[pbh]; p_dc = a.dc_state[pbh];
+    p_cc = a.c_cur[pbh]; p_cp = a.c_prev[pbh];
+    if (!a.dc_zero) p_dc = a.dc_state[pbh];
   }
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const int nks = (K + 31) >> 5;

@@ -877,9 +877,11 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
       GemmDesc w;   // dW_hw[F,F] = dh^T pooled
       w.A = ws->dh; w.lda = c.Fp; w.a_kc = 0; w.B = st->pooled; w.ldb = c.Fp; w.b_kc = 0; w.C = G->hw_w; w.ldc = c.F;
       w.M = c.F; w.N = c.F; w.K = (int)MR; w.in_dtype = c.dt; w.out_dtype = DT_F32; w.accumulate = accumulate;
+      w.wgrad = 1; w.a_sum = G->hw_b;      // db_hw = colsum(dh), out of the A operand this product stages anyway
+      const bool folded = wgrad_folds_a_sum(w);
       GIC_PROPAGATE(gemm(w, stream));
       // (ws->dydrop is free after the highway backward: the deterministic mode's column-sum partials)
-      GIC_PROPAGATE(colsum(ws->dh, c.dt, c.Fp, MR, c.F, G->hw_b, nullptr, accumulate, stream, ws->dydrop, (long)(MR * c.Fp)));
+      if (!folded) GIC_PROPAGATE(colsum(ws->dh, c.dt, c.Fp, MR, c.F, G->hw_b, nullptr, accumulate, stream, ws->dydrop, (long)(MR * c.Fp)));
     }
   }
   // 4. conv / pool backward

@@ -8,6 +8,11 @@
 // so  forward  y = x W^T      : a_kc=1, b_kc=1   ("NT")
 //     dgrad    dx = dy W      : a_kc=1, b_kc=0   ("NN")
 //     wgrad    dW = dy^T x    : a_kc=0, b_kc=0   ("TN")
+// The wgrad form can carry two extras (fields at the end of GemmDesc): the column sums of A -- a_sum[m] (+)= sum_k A(m,k), the bias
+// gradient of the layer, out of the A chunks the product stages anyway -- and a second output matrix C2 for the columns from n_split on
+// (dW_ih | dW_hh of an LSTM layer over xh = [x | h] in one launch).  Conditions: bf16 operands, a_kc == 0 && b_kc == 0, EPI_PLAIN, no convolution, the
+// 16-byte vectorised path, deterministic mode off, c_zeroed == 0; n_split a multiple of the tile width.  wgrad_folds_a_sum() /
+// wgrad_tile_n() below are the rule as host predicates.
 #pragma once
 #include "common.h"
 
@@ -31,11 +36,12 @@ struct GemmDesc {
   int epi = EPI_PLAIN;
   // ---- EPI_HIGHWAY (discriminator.py:53-58): h = acc+bias; y = sig(h)*relu(h) + (1-sig(h))*x; C = y*keep*keep_scale
   const void* X = nullptr; long ldx = 0;        // carry input, in_dtype
-  float* Hpre = nullptr; long ldh = 0;          // pre-activation h (saved for backward)
+  union { float* Hpre = nullptr; float* a_sum2; };   // pre-activation h (saved for backward)          | a_sum2, below
+  union { long ldh = 0; long ldc2; };                //                                                | ldc2, below
   const uint8_t* mask = nullptr; long ldmask = 0;   // explicit keep mask (0/1) or null
   uint8_t* mask_out = nullptr; long ldmask_out = 0;   // keep mask actually used, written for backward (optional)
   float keep_scale = 1.f;                       // 1/(1-p) in train mode, 1 in eval
-  int use_philox = 0; float drop_p = 0.f; uint64_t seed = 0, stream = 0;
+  union { int use_philox = 0; int wgrad; }; float drop_p = 0.f; uint64_t seed = 0, stream = 0;
   const uint64_t* seed_dev = nullptr;           // non-null: the Philox seed is read from device memory (gic_step_scalars), `seed` is ignored
   // ---- implicit-GEMM convolution (conv != 0): A(m,k) is gathered from an NHWC activation `A`
   //      [Nimg, cH, cW, cCin] with m = (n, ho, wo) and k = (r, s, c); M = Nimg*cHo*cWo, K = cKH*cKW*cCin;
@@ -43,7 +49,7 @@ struct GemmDesc {
   int conv = 0;
   int cH = 0, cW = 0, cCin = 0, cHo = 0, cWo = 0, cKH = 0, cKW = 0, cStride = 1, cPad = 0;
   // ---- EPI_BNSTATS: C = result (+bias) and stats[n] += sum_m v, stats[N+n] += sum_m v^2 (f32 atomics)
-  float* stats = nullptr;   // [stats_nrep][2N]; block b adds into replica b % stats_nrep (readers sum the replicas)
+  union { float* stats = nullptr; float* a_sum; };   // [stats_nrep][2N]; block b adds into replica b % stats_nrep (readers sum the replicas) | a_sum, below
   int stats_nrep = 1;
   // ---- A-side BatchNorm + ReLU (tile8 convolutions with Cin % 8 == 0, Cin <= 1024): the input activation is read as
   //      relu(scale[c] * x + shift[c]) (zero padding applied AFTER it, as the reference pads the normalised tensor) with
@@ -61,7 +67,7 @@ struct GemmDesc {
   const float* res_stats = nullptr; int res_nrep = 1;
   const float* res_gamma = nullptr; const float* res_beta = nullptr;
   float res_inv_count = 0.f;
-  void* out_wb = nullptr;
+  union { void* out_wb = nullptr; void* C2; };       //                                                | C2, below
   // ---- EPI_GUMBELMAX (gemm_gumbelmax below): C is NOT written.  Rows m = vocabulary entries (A = W_out [V, H]), columns n = roll-out
   //      rows (B = their hidden states): key[n] = atomicMax over m of row_key((acc + gm_bias[m] + gumbel(u[n, m])) * gm_temperature, m)
   //      -- the token of an ids-only roll-out step (generator.py:68-73 with the softmax skipped: it is monotone) without the [rows, V]
@@ -72,9 +78,24 @@ struct GemmDesc {
   const float* gm_u = nullptr; long gm_ldu = 0;
   float gm_temperature = 1.f;
   int n_fast = 0;           // tile8: the output-channel tiles of a row tile are neighbours on one XCD (xcd_share_a) instead of the row tiles of a channel tile
-  int stats_only = 0;       // EPI_BNSTATS convolutions the streaming 1x1 kernel takes: the column sums only, C is NOT written (conv_b2b.hip's first pass);
+  union { int stats_only = 0; int n_split; };        // | n_split, below.  EPI_BNSTATS convolutions the streaming 1x1 kernel takes: the column sums only, C is NOT written (conv_b2b.hip's first pass);
                             // honoured by conv1x1_stream.hip alone: gemm() answers GIC_ERR_UNSUPPORTED when that kernel declines the shape
   int dbg = 0;              // phase-ablation knob, honoured only by -DGIC_STAMPS tool builds
+  // ---- weight-gradient extras: honoured by gemm_kernel's vectorised form of a plain bf16 product with a_kc == 0 && b_kc == 0 (16-byte aligned
+  //      operands, lda / ldb whole 16-byte chunks), outside the deterministic mode and without c_zeroed.
+  //      a_sum[m] (+)= sum_k A(m,k), a_sum2 (optional) receives the same values: overwritten or accumulated as `accumulate` says for C;
+  //      formed from the A chunks the workgroups of the first N tile stage anyway (a fixed-order sum without split-K, f32 atomics with
+  //      it, over the split-K zero-fill launch, which clears them with C).  OPTIONAL: where another kernel runs the product the pointers
+  //      are ignored, so a caller asks wgrad_folds_a_sum(d) and keeps its colsum() when the answer is false.
+  //      C2 / ldc2 / n_split: columns n >= n_split go to C2[m * ldc2 + (n - n_split)], the others to C: one product over adjacent column
+  //      ranges of one B for two output matrices.  n_split must be a multiple of the tile width (wgrad_tile_n(d)); gemm() answers
+  //      GIC_ERR_UNSUPPORTED where it cannot honour a C2.
+  //      `wgrad` != 0 says that the descriptor carries them: without it none of the fields below is looked at, whatever the unions hold.
+  //      STORAGE: int wgrad, float* a_sum, float* a_sum2, void* C2, long ldc2 and int n_split are the union members declared above, beside stats, Hpre,
+  //      out_wb, ldh, stats_only and use_philox -- fields of the BatchNorm-sum / highway epilogues and of convolutions, none of which a plain
+  //      m/n-contiguous product has.  The descriptor is every GEMM kernel's by-value argument: with five more fields its size moved the
+  //      scalar loads and waits of 16 instantiations that have nothing to do with them (tools/isa_diff.py --by-kernel); as unions every
+  //      existing instantiation keeps its instruction stream (profiles/wgrad_fold_isa.txt).  Set them on plain products only.
 };
 
 // Enqueue on `stream`. Returns GIC_OK or a negative Status (message via gic_last_error()).
@@ -102,6 +123,13 @@ inline bool bn_in_args_ok(const GemmDesc& d) { return d.in_gamma && d.in_beta &&
 // or accumulate), 16-byte aligned A, B and C, valid BatchNorm-on-load arguments if any, both operands (a_elems / b_elems elements, which the
 // caller derives from its own window) under 2 GiB -- and, when they hold, the shared fields.
 bool conv_base(const GemmDesc& d, long a_elems, long b_elems, ConvBase& b);
+
+// Pure host predicates beside the selection (no HIP call): would gemm(d) fold d.a_sum into the product; the tile width (64 | 128) the
+// 4-wave kernel would run d with where it can honour the weight-gradient extras at all, else 0 (C2 needs n_split % that == 0).
+bool wgrad_folds_a_sum(const GemmDesc& d);
+int wgrad_tile_n(const GemmDesc& d);
+// Launches of the weight-gradient-extras form since the library was loaded, and those of them that wrote two matrices (tests: which route ran)
+void wgrad_launch_counts(long* launches, long* two_matrix);
 
 // Route-only mode (gic_debug_route_only, util.hip): gemm(), gemm_gumbelmax() and gic_conv_b2b validate and select, write the plan as one
 // line into route_line() and return their status without touching the GPU.  gic_disc_fwd (disc.hip) answers with the selection of its

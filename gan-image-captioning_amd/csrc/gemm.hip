@@ -7,6 +7,9 @@
 //                 need no transposed copies in HBM), bf16 (v_mfma_f32_16x16x32_bf16) or exact f32 (v_mfma_f32_16x16x4_f32,
 //                 parity mode), register-staged double buffer or 3-stage LDS-DMA ring, split-K over gridDim.y (f32 atomics)
 //                 for skinny / deep-K products, highway epilogue, 16-byte accesses when shapes allow, scalar fallback.
+//                 The vectorised weight-gradient form (both operands row-major over K) has a second instantiation, EPI_WGRAD: the
+//                 column sums of A (the layer's bias gradient) out of the staged A chunks of the first N tile's workgroups, and a
+//                 second output matrix from column n_split on (gemm.h).
 //   tile8_kernel  8 waves (4x2), 128x128 or 128x64 tile, bf16 k-contiguous operands only: buffer-descriptor LDS-DMA ring of 1 /
 //                 2 / 4 stages.  Every trunk convolution in bf16 mode and the wide plain / highway products (highway: row-padded
 //                 bf16 buffers only, select_tile8's highway_wide; every other highway product is gemm_kernel's).  See its header.
@@ -27,6 +30,8 @@
 #include "kernels.h"
 
 #include <stdlib.h>
+#include <string.h>
+#include <atomic>
 
 namespace gic {
 
@@ -121,6 +126,21 @@ __device__ __forceinline__ void g4_frag_f32(float (&f)[8], const unsigned char* 
   }
 }
 
+// launches of the EPI_WGRAD form since the library was loaded, and those of them with a second output matrix (wgrad_launch_counts)
+std::atomic<long> g_wgrad_launches{0}, g_wgrad_two{0};
+
+// gemm_kernel's EPI argument for EPI_PLAIN with the weight-gradient extras of gemm.h (a_sum / a_sum2, C2 / n_split): never a descriptor's
+// epi, chosen by the launch (Gemm4Plan.wg) for the <AKC = false, BKC = false, VEC> form alone, so that every other instantiation keeps its
+// name and its code
+constexpr int EPI_WGRAD = 4;
+
+// one staged 16-byte chunk of an m-contiguous bf16 A (eight consecutive m of one k) added onto the thread's eight partial sums
+__device__ __forceinline__ void g4_chunk_add(float (&s)[8], const u32x4 r) {
+  const bf16x8 v = __builtin_bit_cast(bf16x8, r);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s[e] += (float)v[e];
+}
+
 // PIPE (k-contiguous, vectorised operands only): tiles reach LDS by LDS-DMA (global_load_lds, 16 B per lane, no VGPR
 // staging) into a 3-stage ring; the loads of tile k+2 are in flight under the MFMAs of tiles k and k+1 behind a COUNTED
 // s_waitcnt vmcnt and one raw s_barrier per K tile.  The LDS image is lane-linear per wave-instruction (128-byte rows, no
@@ -130,6 +150,8 @@ template <typename TI, typename TO, bool AKC, bool BKC, int BM, int BN, bool VEC
 __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k_tiles_per_split) {
   static_assert(!CONV || (AKC && BKC && VEC), "the implicit-GEMM convolution loader is k-contiguous and vectorised");
   static_assert(!PIPE || (AKC && BKC && VEC), "the LDS-DMA pipeline needs k-contiguous 16-byte chunks");
+  constexpr bool WG = EPI == EPI_WGRAD;
+  static_assert(!WG || (!AKC && !BKC && VEC && !CONV && !PIPE && sizeof(TI) == 2), "the weight-gradient extras exist in the vectorised m/n-contiguous bf16 form only");
   constexpr int SZ = sizeof(TI);
   constexpr int BK = 128 / SZ;          // K elements per tile
   constexpr int VE = 16 / SZ;           // elements per 16-byte chunk
@@ -171,6 +193,16 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
     for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   u32x4 ra[CA], rb[CB];
+
+  // ---- WG: column sums of A.  A thread's chunks all cover the same VE rows m (256 is a multiple of the BM / VE chunks of a k row), so it
+  // keeps VE partial sums over the k it stages; the workgroups of the first N tile do (every m belongs to exactly one of them per split)
+  float asum[WG ? VE : 1];
+  bool asum_on = false;
+  if constexpr (WG) {
+    asum_on = d.a_sum && bn0 == 0;
+#pragma unroll
+    for (int e = 0; e < VE; ++e) asum[e] = 0.f;
+  }
 
   // ---- implicit-GEMM convolution: per staged row (fixed per thread) the image and the top-left input pixel;
   // per thread ONE running (r, s, c) decomposition of its k (all of a thread's chunks share kc = tid & 7).
@@ -244,6 +276,12 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
     unsigned char* sA = smem + buf * BUF_BYTES;
     unsigned char* sB = sA + A_BYTES;
     if constexpr (VEC) {
+      if constexpr (WG) {
+        if (asum_on) {                                   // (zero-filled tail chunks add zero)
+#pragma unroll
+          for (int i = 0; i < CA; ++i) g4_chunk_add(asum, ra[i]);
+        }
+      }
       g4_store<TI, AKC, BM, SA>(sA, ra, tid);
       g4_store<TI, BKC, BN, SB>(sB, rb, tid);
     } else {
@@ -359,7 +397,38 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
 
   // ---- epilogue.  C/D map: col = lane&15, row = (lane>>4)*4 + reg
   TO* __restrict__ C = (TO*)d.C;
+  long ldc = d.ldc;
+#define LDC (WG ? ldc : d.ldc)      /* every other instantiation reads the descriptor where it always did: its instruction stream is unchanged */
   const bool split = gridDim.y > 1;
+
+  if constexpr (WG) {
+    // the tiles from column n_split on belong to C2 (n_split is a multiple of BN: a tile has one destination)
+    if (d.C2 && bn0 >= d.n_split) { C = (TO*)d.C2 - d.n_split; ldc = d.ldc2; }
+    if (asum_on) {                                       // block-uniform
+      // fold the partials of the 256 / CPR threads that share an m chunk through the epilogue's LDS area (the K loop's last barrier has
+      // retired the ring), in a fixed order; then one store, += or (split-K) atomicAdd per m
+      constexpr int CPR = BM / VE, G = 256 / CPR;
+      static_assert(G * BM * 4 <= SMEM_BYTES, "the column-sum partials must fit the LDS allocation");
+      float* sS = (float*)smem;                          // [G][BM]
+#pragma unroll
+      for (int e = 0; e < VE; ++e) sS[(tid / CPR) * BM + (tid % CPR) * VE + e] = asum[e];
+      __syncthreads();
+      if (tid < BM && bm0 + tid < M) {
+        float t = 0.f;
+#pragma unroll
+        for (int g = 0; g < G; ++g) t += sS[g * BM + tid];
+        const int m = bm0 + tid;
+        if (split) {
+          atomicAdd(d.a_sum + m, t);
+          if (d.a_sum2) atomicAdd(d.a_sum2 + m, t);
+        } else {
+          d.a_sum[m] = d.accumulate ? d.a_sum[m] + t : t;
+          if (d.a_sum2) d.a_sum2[m] = d.accumulate ? d.a_sum2[m] + t : t;
+        }
+      }
+      __syncthreads();                                   // the C tile is staged over this area
+    }
+  }
 
   // Staged path (conv / plain products that overwrite C): the tile goes through LDS so that every global store
   // is a 16-byte piece of a contiguous output row (a direct store of the MFMA layout writes 32-byte row
@@ -370,7 +439,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
     constexpr int OVE = 16 / OSZ;
     constexpr int SC = BN * OSZ + 16;                       // LDS row stride of the C tile
     static_assert(BM * SC + 4 * (BN / 2) * 2 * 4 <= SMEM_BYTES, "C tile + stats scratch must fit the LDS allocation");
-    const bool staged = !split && !d.accumulate && (N % OVE == 0) && (d.ldc % OVE == 0) && ((((uintptr_t)d.C) & 15) == 0);
+    const bool staged = !split && !d.accumulate && (N % OVE == 0) && (LDC % OVE == 0) && ((((uintptr_t)(WG ? (const void*)C : (const void*)d.C)) & 15) == 0);
     if (staged) {
       unsigned char* sC = smem;
       float* sStat = (float*)(smem + BM * SC);               // [4 waves][BN/2][2]
@@ -415,7 +484,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
       for (int c = tid; c < BM * CPR; c += 256) {
         const int ml = c / CPR, cc = c % CPR;
         const int m = bm0 + ml, n = bn0 + cc * OVE;
-        if (m < M && n < N) *(u32x4*)(C + (long)m * d.ldc + n) = *(const u32x4*)(sC + ml * SC + cc * 16);
+        if (m < M && n < N) *(u32x4*)(C + (long)m * LDC + n) = *(const u32x4*)(sC + ml * SC + cc * 16);
       }
       STAMP(5);
       return;
@@ -442,10 +511,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
         if (m >= M) continue;
         float v = d.alpha * acc[i][j][r] + bias;
         if constexpr (EPI == EPI_BNSTATS) {
-          C[(long)m * d.ldc + n] = from_f32<TO>(v);
+          C[(long)m * LDC + n] = from_f32<TO>(v);
           st_s += v; st_q += v * v;
-        } else if constexpr (EPI == EPI_PLAIN) {
-          const long o = (long)m * d.ldc + n;
+        } else if constexpr (EPI == EPI_PLAIN || WG) {
+          const long o = (long)m * LDC + n;
           if constexpr (sizeof(TO) == 4) {
             if (split) { atomicAdd((float*)&C[o], v); continue; }
           }
@@ -457,7 +526,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
           float keep = keep4[r];
           if (d.mask) keep = (float)d.mask[(long)m * d.ldmask + n];
           if (d.mask_out) d.mask_out[(long)m * d.ldmask_out + n] = (uint8_t)keep;
-          C[(long)m * d.ldc + n] = from_f32<TO>(y * keep * d.keep_scale);
+          C[(long)m * LDC + n] = from_f32<TO>(y * keep * d.keep_scale);
         }
       }
       if constexpr (EPI == EPI_BNSTATS) {
@@ -470,6 +539,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDesc d, const int k
     }
   }
 }
+#undef LDC
 
 // ------------------------------------------------------------------------------------------------------------------
 // tile8: the bf16 k-contiguous product / implicit-GEMM convolution with EIGHT waves per 128-row tile (2 per SIMD).
@@ -964,7 +1034,7 @@ __global__ __launch_bounds__(512) void tile8_kernel(const GemmDesc d, const unsi
 struct Tile8Plan { int BN, NS; bool abn, ares; int amaxk; unsigned grid, a_bytes, b_bytes; };
 // gemm_kernel<TI, TO, AKC, BKC, BM, BM, VEC, EPI, CONV, PIPE> over dim3(tiles, splits), `per` K tiles per split; zero_grid > 0: C is
 // zero-filled first (split-K adds into it)
-struct Gemm4Plan { int bm; bool vec, pipe; int tiles, splits, per, zero_grid; };
+struct Gemm4Plan { int bm; bool vec, pipe; int tiles, splits, per, zero_grid; bool wg; };      // wg: the EPI_WGRAD form (gemm.h's weight-gradient extras)
 
 enum Family { F_NONE = 0, F_STEM, F_PATCH, F_STREAM, F_PIX, F_PANEL, F_TILE8, F_GEMM4 };
 
@@ -1047,6 +1117,22 @@ bool select_tile8(const GemmDesc& d, Tile8Plan& p, int& n_fast) {
   return true;
 }
 
+// What the weight-gradient extras (a_sum / a_sum2, C2 / n_split) need of a product, the chosen tile apart: gemm_kernel's vectorised
+// m/n-contiguous plain form in bf16 compute mode, outside the deterministic mode (its sums are per-split atomics), over a C that the
+// launch itself zero-fills, and only for a descriptor that says `wgrad` (the extras' fields are union members, gemm.h).  The f32 parity
+// mode is left out: it is not required, and with an f32 form of this fold in the tree the eager-against-graph comparison of the f32 train
+// step (tests/test_gpu_step.py) failed in 3 of 6 runs where it passes without; the cause of that was not established.
+bool wgrad_form(const GemmDesc& d, bool vec) {
+  return d.wgrad && !d.conv && !d.a_kc && !d.b_kc && d.epi == EPI_PLAIN && d.in_dtype == DT_BF16 && vec && !d.c_zeroed && !det_mode();
+}
+// gemm()'s `vec` of a plain product: what the predicates below and gemm() itself both go by
+bool plain_vec(const GemmDesc& d) {
+  const int ve = 16 / dtype_size(d.in_dtype);
+  bool vec = aligned16(d.A) && aligned16(d.B) && (d.lda % ve == 0) && (d.ldb % ve == 0);
+  if (d.a_kc || d.b_kc) vec = vec && (d.K % ve == 0);
+  return vec;
+}
+
 // The 4-wave kernel takes every product the validation lets through: tile size, split-K and the pipeline
 void select_gemm4(const GemmDesc& d, bool vec, Gemm4Plan& p) {
   // 128x128 tiles only when there are enough of them to co-schedule two blocks per CU (latency hiding by TLP), else 64x64;
@@ -1094,6 +1180,7 @@ void select_gemm4(const GemmDesc& d, bool vec, Gemm4Plan& p) {
   // and for K of one or two tiles the ring's prologue is pure overhead.  Measured on MI355X (tools/gemm_bench.py).
   static const bool no_pipe = getenv("GIC_GEMM_NO_PIPE") != nullptr;
   p.pipe = d.a_kc && d.b_kc && vec && p.per >= 6 && (long)tiles * p.splits <= 2 * 256 + 8 && !no_pipe;
+  p.wg = wgrad_form(d, vec) && (d.a_sum || d.C2);      // (in that form alone the unions of gemm.h hold these)
 }
 
 // The one list of candidates, in the order they are tried; `after`: the families up to and including it are skipped (the launch of that one
@@ -1143,6 +1230,11 @@ int select(const GemmDesc& d, bool vec, int after, Plan& p) {
   }
   p.d = d;
   select_gemm4(d, vec, p.g4);
+  if (!d.conv && d.epi == EPI_PLAIN && d.C2 && !(p.g4.wg && d.n_split > 0 && d.n_split < d.N && d.n_split % p.g4.bm == 0)) {
+    // (a_sum alone is optional: a kernel that cannot fold it runs the product as ever, callers ask wgrad_folds_a_sum first)
+    set_last_error("gemm: a second output needs the vectorised weight-gradient form and n_split (%d) on a tile boundary (%d)", d.n_split, p.g4.bm);
+    return GIC_ERR_UNSUPPORTED;
+  }
   return take(F_GEMM4);
 }
 
@@ -1179,6 +1271,22 @@ __global__ void zero2d_kernel(float* __restrict__ C, long ldc, int M, int N) {
   const long total = (long)M * N;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
     C[(i / N) * ldc + (i % N)] = 0.f;
+}
+
+// split-K over the weight-gradient extras: both output matrices and the column sums start from zero
+__global__ void zero_wgrad_kernel(float* __restrict__ C, long ldc, float* __restrict__ C2, long ldc2, int n_split, float* __restrict__ s1,
+                                  float* __restrict__ s2, int M, int N) {
+  const long total = (long)M * N, i0 = (long)blockIdx.x * blockDim.x + threadIdx.x, step = (long)gridDim.x * blockDim.x;
+  for (long i = i0; i < total; i += step) {
+    const long m = i / N;
+    const int n = (int)(i - m * N);
+    if (C2 && n >= n_split) C2[m * ldc2 + (n - n_split)] = 0.f;
+    else C[m * ldc + n] = 0.f;
+  }
+  for (long m = i0; m < M; m += step) {
+    if (s1) s1[m] = 0.f;
+    if (s2) s2[m] = 0.f;
+  }
 }
 
 template <typename TO, int EPI, bool CONV, int BN, int NS, bool ABN = false, bool ARES = false, int AMAXK = 1024>
@@ -1238,7 +1346,7 @@ template <typename TI, typename TO, bool AKC, bool BKC, int EPI, bool CONV>
 void launch_gemm4_tile(const Plan& p, hipStream_t stream) {
   const bool big = p.g4.bm == 128;
   if (CONV || p.g4.vec) return big ? launch_gemm4_as<TI, TO, AKC, BKC, 128, true, EPI, CONV>(p, stream) : launch_gemm4_as<TI, TO, AKC, BKC, 64, true, EPI, CONV>(p, stream);
-  if constexpr (!CONV) return big ? launch_gemm4_as<TI, TO, AKC, BKC, 128, false, EPI, CONV>(p, stream) : launch_gemm4_as<TI, TO, AKC, BKC, 64, false, EPI, CONV>(p, stream);
+  if constexpr (!CONV && EPI != EPI_WGRAD) return big ? launch_gemm4_as<TI, TO, AKC, BKC, 128, false, EPI, CONV>(p, stream) : launch_gemm4_as<TI, TO, AKC, BKC, 64, false, EPI, CONV>(p, stream);
 }
 
 template <typename TI, typename TO>
@@ -1254,6 +1362,8 @@ void launch_gemm4_typed(const Plan& p, hipStream_t stream) {
   } else if (d.a_kc) {
     if (d.b_kc) launch_gemm4_tile<TI, TO, true, true, EPI_PLAIN, false>(p, stream);
     else launch_gemm4_tile<TI, TO, true, false, EPI_PLAIN, false>(p, stream);
+  } else if (p.g4.wg) {
+    if constexpr (sizeof(TI) == 2) launch_gemm4_tile<TI, TO, false, false, EPI_WGRAD, false>(p, stream);       // (wgrad_form: bf16, vectorised)
   } else {
     launch_gemm4_tile<TI, TO, false, false, EPI_PLAIN, false>(p, stream);
   }
@@ -1261,7 +1371,13 @@ void launch_gemm4_typed(const Plan& p, hipStream_t stream) {
 
 void launch_gemm4(const Plan& p, hipStream_t stream) {
   const GemmDesc& d = p.d;
-  if (p.g4.zero_grid) hipLaunchKernelGGL(zero2d_kernel, dim3(p.g4.zero_grid), dim3(256), 0, stream, (float*)d.C, d.ldc, d.M, d.N);
+  if (p.g4.wg) {
+    g_wgrad_launches.fetch_add(1, std::memory_order_relaxed);
+    if (d.C2) g_wgrad_two.fetch_add(1, std::memory_order_relaxed);
+  }
+  if (p.g4.zero_grid && p.g4.wg)
+    hipLaunchKernelGGL(zero_wgrad_kernel, dim3(p.g4.zero_grid), dim3(256), 0, stream, (float*)d.C, d.ldc, (float*)d.C2, d.ldc2, d.n_split, d.a_sum, d.a_sum2, d.M, d.N);
+  else if (p.g4.zero_grid) hipLaunchKernelGGL(zero2d_kernel, dim3(p.g4.zero_grid), dim3(256), 0, stream, (float*)d.C, d.ldc, d.M, d.N);
   if (d.in_dtype == DT_F32) launch_gemm4_typed<float, float>(p, stream);
   else if (d.out_dtype == DT_F32) launch_gemm4_typed<bf16_t, float>(p, stream);
   else launch_gemm4_typed<bf16_t, bf16_t>(p, stream);
@@ -1303,6 +1419,10 @@ void write_route(const Plan& p) {
       snprintf(s, kRouteLen, "gemm<%s,%s,%s,%s,%d,%d,%s,%d,%s,%s> grid=%dx%d block=256 lds=0 splits=%d per=%d pipe=%d zero=%d", tn[d.in_dtype], tn[d.out_dtype],
                b(d.a_kc), b(d.b_kc), p.g4.bm, p.g4.bm, b(d.conv || p.g4.vec), d.epi, b(d.conv), b(p.g4.pipe), p.g4.tiles, p.g4.splits, p.g4.splits, p.g4.per,
                (int)p.g4.pipe, p.g4.zero_grid);
+      if (p.g4.wg) {      // (a descriptor without the weight-gradient extras keeps its line)
+        const size_t n = strlen(s);
+        snprintf(s + n, kRouteLen - n, " a_sum=%d n_split=%d", d.a_sum ? (d.a_sum2 ? 2 : 1) : 0, d.C2 ? d.n_split : 0);
+      }
   }
 }
 
@@ -1319,6 +1439,21 @@ bool conv_base(const GemmDesc& d, long a_elems, long b_elems, ConvBase& b) {
   b.stats_nrep = d.stats_nrep < 1 ? 1 : d.stats_nrep; b.in_nrep = d.in_nrep; b.in_inv_count = d.in_inv_count;
   b.a_bytes = (unsigned)(a_elems * 2); b.b_bytes = (unsigned)(b_elems * 2);
   return true;
+}
+
+void wgrad_launch_counts(long* launches, long* two_matrix) {
+  if (launches) *launches = g_wgrad_launches.load(std::memory_order_relaxed);
+  if (two_matrix) *two_matrix = g_wgrad_two.load(std::memory_order_relaxed);
+}
+
+bool wgrad_folds_a_sum(const GemmDesc& d) { return d.a_sum && wgrad_form(d, plain_vec(d)); }
+
+int wgrad_tile_n(const GemmDesc& d) {
+  const bool vec = plain_vec(d);
+  if (!wgrad_form(d, vec)) return 0;
+  Gemm4Plan p;
+  select_gemm4(d, vec, p);
+  return p.bm;
 }
 
 long gemm_gumbelmax_from_cols(int in_dtype, int M, int K, long lda, long ldb) { return gumbelmax_from_cols(in_dtype, M, K, lda, ldb); }
@@ -1350,7 +1485,7 @@ int gemm(const GemmDesc& d0, hipStream_t stream) {
   if (d.epi == EPI_HIGHWAY) GIC_CHECK_ARG(d.X, "gemm: highway epilogue needs X");      // Hpre may be null (forward only)
   const int sz = dtype_size(d.in_dtype);
   const int ve = 16 / sz;
-  bool vec = aligned16(d.A) && aligned16(d.B) && (d.lda % ve == 0) && (d.ldb % ve == 0);
+  bool vec = plain_vec(d);
   if (d.conv) {
     // a 16-B chunk holds `ve` consecutive k = channels of one tap, or (pre-padded input, pad == 0) whole adjacent taps of one row
     const bool chunk_ok = (d.cCin % ve == 0) || (d.cPad == 0 && ve % d.cCin == 0 && (d.cKW * d.cCin) % ve == 0);
@@ -1358,10 +1493,9 @@ int gemm(const GemmDesc& d0, hipStream_t stream) {
     GIC_CHECK_ARG(d.epi != EPI_BNSTATS || d.stats, "gemm: EPI_BNSTATS needs a stats buffer");
     vec = aligned16(d.A) && aligned16(d.B) && (d.ldb % ve == 0);
   }
-  // k-contiguous operands: K must be a whole number of 16-B chunks (callers zero-pad K).  m/n-contiguous
+  // (plain_vec: k-contiguous operands: K must be a whole number of 16-B chunks (callers zero-pad K).  m/n-contiguous
   // operands: a tail chunk reads into the row's padding (ld % ve == 0 >= M) and only feeds rows that are
-  // never stored, so no condition on M / N.
-  if (d.a_kc || d.b_kc) vec = vec && (d.K % ve == 0);
+  // never stored, so no condition on M / N.)
   Plan p;
   for (int after = F_NONE;; after = p.family) {
     const int rc = select(d, vec, after, p);

@@ -329,6 +329,22 @@ int gic_gemm(const void* A, const void* B, void* C, int M, int N, int K, int64_t
   return gic::gemm(d, (hipStream_t)stream);
 }
 
+int gic_debug_wgrad_fold(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int a_kc, int b_kc, int in_dtype,
+                         int out_dtype) {
+  static float sum;       // (a non-null a_sum: never written, the predicates only look at the descriptor)
+  gic::GemmDesc d;
+  d.A = A; d.B = B; d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldb = ldb; d.a_kc = a_kc; d.b_kc = b_kc;
+  d.in_dtype = in_dtype; d.out_dtype = out_dtype; d.wgrad = 1; d.a_sum = &sum;
+  return gic::wgrad_folds_a_sum(d) ? gic::wgrad_tile_n(d) : 0;
+}
+
+void gic_debug_wgrad_launches(int64_t* launches, int64_t* two_matrix) {
+  long a = 0, b = 0;
+  gic::wgrad_launch_counts(&a, &b);
+  if (launches) *launches = a;
+  if (two_matrix) *two_matrix = b;
+}
+
 int gic_cast2d(const void* src, int src_dtype, int64_t lds, void* dst, int dst_dtype, int64_t ldd, int64_t rows,
                int64_t cols, void* stream) {
   return gic::cast2d(src, src_dtype, lds, dst, dst_dtype, ldd, rows, cols, (hipStream_t)stream);

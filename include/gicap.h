@@ -55,6 +55,16 @@ const char* gic_last_error(void);
  * "tile8<bf16,128,2,true,2,true,false,1024> grid=1568 block=512 lds=0"; "unsupported" when nothing was selected. */
 void gic_debug_route_only(int on);
 const char* gic_debug_last_route(void);
+/* Host-only: what the selection answers the library's own weight-gradient call sites (dW = dy^T x with the bias gradient as the column
+ * sums of dy) for a product of these operands: the tile width (64 | 128) of the 4-wave kernel that folds the column sums of A into the
+ * product -- a second output matrix may start at any multiple of it --, or 0: the product runs as ever and the separate column-sum pass
+ * stays (f32 operands, k-contiguous or unaligned operands, leading dimensions that are no whole 16-byte chunks, the deterministic mode).  Never touches
+ * the GPU; the pointers are only looked at for their alignment. */
+int gic_debug_wgrad_fold(const void* A, const void* B, int M, int N, int K, int64_t lda, int64_t ldb, int a_kc, int b_kc, int in_dtype,
+                         int out_dtype);
+/* How many weight-gradient products this process has launched in that folding form since the library was loaded, and how many of them
+ * wrote two output matrices (dW_ih | dW_hh as one product): what a test reads before and after a call to see which route it took. */
+void gic_debug_wgrad_launches(int64_t* launches, int64_t* two_matrix);
 
 /* ------------------------------------------------------------------------------------------
  * Per-step scalars resident in DEVICE memory (ABI v3).  The values that change from one train step to the next -- the decoder's
