@@ -236,6 +236,11 @@ _SIGNATURES = {
                                     C.c_int64, c_void_p, C.c_int, c_void_p, _P(DiscGrads), C.c_int, c_void_p, C.c_int64, c_void_p, C.c_float,
                                     c_void_p, c_void_p]),
     "gic_gan_losses_mismatch": (C.c_int, [C.c_float, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_disc_match_fwd_grouped": (C.c_int, [_P(DiscDims), _P(DiscState), c_void_p, C.c_int32, c_void_p, C.c_float, C.c_int, c_void_p, c_void_p]),
+    "gic_rerank": (C.c_int, [c_void_p, c_void_p, C.c_float, c_void_p, C.c_int32, C.c_float, c_void_p, c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                             C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_disc_rep_mean": (C.c_int, [_P(DiscDims), _P(DiscState), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_match_ranks": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int32, c_void_p, c_void_p, c_void_p]),
     "gic_pack_image": (C.c_int, [c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
     "gic_repack_conv_weight": (C.c_int, [c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
     "gic_conv2d_bn_in": (C.c_int, [c_void_p, c_void_p, C.c_int, c_void_p, c_void_p, C.c_float, c_void_p, c_void_p, c_void_p, C.c_int,

@@ -131,6 +131,12 @@ _NATIVE = [
     ("--eval-min-length", int, 0, "decode constraint of the evaluations: <E> is not emitted before this many tokens; 0 = off"),
     ("--eval-suppress-tokens", "intlist", "", "decode constraint of the evaluations: comma-separated token ids (at most 16) that are "
                                               "never emitted, e.g. <S> and <UNK>; empty = none"),
+    ("--eval-rerank-weight", float, 0.0, "weight of the discriminator's score in the beam evaluations (evaluate, evaluate_cider, "
+                                         "evaluate_metrics): the beams are re-ranked by log-probability + weight * D score "
+                                         "(Generator.caption rerank_disc); 0 = off"),
+    ("--eval-retrieval", int, 0, "image-caption retrieval evaluation (GANInstructor.evaluate_retrieval: R@1/5/10, median and mean rank in "
+                                 "both directions, --disc-cond projection) after each adversarial epoch's validation", {"choices": [0, 1]}),
+    ("--eval-retrieval-items", int, 1000, "items of the retrieval evaluation (the first of the split; 1000 = the COCO 1k protocol; at most 8192)"),
 ]
 
 

@@ -2,6 +2,7 @@
 // image's projection q = img_proj(pooled trunk feature), and its backward.  No reference counterpart.
 //
 //   logits[m] (+)= s <y[m, :F], q[m / R, :]>            s = F^-1/2, row m = b R + r, y = state->ydrop (what feature2out consumes)
+//   logits[m] (+)= s <y[m, :F], q[q_index[b], :]>       the grouped form (inference only): caption b against any of q's q_rows rows
 //   dydrop[m, n]  = s g[m] q[b, n]                      (f32, pad columns F .. Fp-1 zero; the feature2out input-gradient product of
 //                                                        disc_bwd_t then accumulates onto it)
 //   d_q[b, n]     = s sum_r g[b R + r] y[b R + r, n]    (r in index order: no atomics, the same bits in either mode)
@@ -14,13 +15,18 @@ namespace {
 
 // ---- forward.  grid = (captions, row groups); a workgroup stages q[b] once in LDS (zero beyond F) for all its rows; a wave owns a row at
 // a time: 16-byte loads along the row (64 lanes = 1 KiB per pass), a wave-level sum, lane 0 writes the logit.
+// q_index (NULL = the identity): caption b reads row q_index[b] of q's q_rows rows; an index outside [0, q_rows) is never dereferenced, the
+// caption's rows get NaN (workgroup-uniform).  K captions of one image = K consecutive workgroups staging the same row from L2.
 template <typename TA>
-__global__ __launch_bounds__(256) void disc_match_fwd_kernel(const TA* __restrict__ y, const float* __restrict__ q, float scale, int accumulate,
-                                                               float* __restrict__ logits, int R, int F, int Fp, int rows_per_block) {
+__global__ __launch_bounds__(256) void disc_match_fwd_kernel(const TA* __restrict__ y, const float* __restrict__ q, const int32_t* __restrict__ q_index,
+                                                               int q_rows, float scale, int accumulate, float* __restrict__ logits, int R, int F, int Fp,
+                                                               int rows_per_block) {
   extern __shared__ __attribute__((aligned(16))) float qs[];     // [Fp]
   constexpr int E = 16 / (int)sizeof(TA);                         // elements per 16-byte load
   const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int n = threadIdx.x; n < Fp; n += 256) qs[n] = n < F ? q[(long)b * F + n] : 0.f;
+  const int qb = q_index ? q_index[b] : b;
+  const bool in_range = (unsigned)qb < (unsigned)q_rows;
+  for (int n = threadIdx.x; n < Fp; n += 256) qs[n] = n < F && in_range ? q[(long)qb * F + n] : 0.f;
   __syncthreads();
   const int r0 = blockIdx.y * rows_per_block;
   const int r1 = r0 + rows_per_block < R ? r0 + rows_per_block : R;
@@ -35,7 +41,7 @@ __global__ __launch_bounds__(256) void disc_match_fwd_kernel(const TA* __restric
       for (int e = 0; e < E; ++e) acc += to_f32<TA>(v[e]) * qs[c + e];
     }
     acc = wave_sum(acc);
-    if (lane == 0) logits[m] = (accumulate ? logits[m] : 0.f) + scale * acc;
+    if (lane == 0) logits[m] = in_range ? (accumulate ? logits[m] : 0.f) + scale * acc : __builtin_nanf("");
   }
 }
 
@@ -95,6 +101,27 @@ int check_match_dims(const gic_disc_dims* d, const char* what) {
   return GIC_OK;
 }
 
+// The one launch of the match forward (gic_disc_match_fwd: the identity index over B rows of q; gic_disc_match_fwd_grouped).
+int launch_match_fwd(const gic_disc_dims* dims, const void* ydrop, const float* q, int q_rows, const int32_t* q_index, float scale, int accumulate,
+                     float* logits, hipStream_t stream, const char* what) {
+  const int B = dims->B, R = dims->R, F = dims->F, Fp = dims->Fp;
+  // rows per workgroup (a multiple of its four waves): halved until the grid has 512 workgroups, so that q[b] is staged as seldom as the
+  // device's occupancy allows (cfg2: 8 rows, two per wave)
+  int rpb = R;
+  while (rpb > 4 && (long)B * cdiv(R, rpb) < 512) rpb = (rpb + 1) / 2;
+  rpb = (rpb + 3) / 4 * 4;
+  const dim3 grid(B, cdiv(R, rpb));
+  const size_t lds = (size_t)Fp * sizeof(float);
+  if (dims->dtype == DT_F32)
+    hipLaunchKernelGGL((disc_match_fwd_kernel<float>), grid, dim3(256), lds, stream, (const float*)ydrop, q, q_index, q_rows, scale, accumulate,
+                       logits, R, F, Fp, rpb);
+  else
+    hipLaunchKernelGGL((disc_match_fwd_kernel<bf16_t>), grid, dim3(256), lds, stream, (const bf16_t*)ydrop, q, q_index, q_rows, scale, accumulate,
+                       logits, R, F, Fp, rpb);
+  GIC_CHECK_LAUNCH(what);
+  return GIC_OK;
+}
+
 }  // namespace
 
 int disc_match_bwd(int dt, const void* ydrop, const float* q, const float* g, float scale, float* dydrop, float* d_q, int B, int R, int F,
@@ -123,22 +150,22 @@ int gic_disc_match_fwd(const gic_disc_dims* dims, const gic_disc_state* state, c
   GIC_CHECK_ARG(state->ydrop, "disc_match_fwd: null state buffer (ydrop)");
   GIC_CHECK_ARG((((uintptr_t)state->ydrop) & 15) == 0, "disc_match_fwd: ydrop must be 16-byte aligned");
   GIC_CHECK_ARG(scale == scale, "disc_match_fwd: scale is NaN");
-  const int B = dims->B, R = dims->R, F = dims->F, Fp = dims->Fp;
-  // rows per workgroup (a multiple of its four waves): halved until the grid has 512 workgroups, so that q[b] is staged as seldom as the
-  // device's occupancy allows (cfg2: 8 rows, two per wave)
-  int rpb = R;
-  while (rpb > 4 && (long)B * cdiv(R, rpb) < 512) rpb = (rpb + 1) / 2;
-  rpb = (rpb + 3) / 4 * 4;
-  const dim3 grid(B, cdiv(R, rpb));
-  const size_t lds = (size_t)Fp * sizeof(float);
-  if (dims->dtype == DT_F32)
-    hipLaunchKernelGGL((disc_match_fwd_kernel<float>), grid, dim3(256), lds, (hipStream_t)stream, (const float*)state->ydrop, q, scale, accumulate,
-                       logits, R, F, Fp, rpb);
-  else
-    hipLaunchKernelGGL((disc_match_fwd_kernel<bf16_t>), grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)state->ydrop, q, scale, accumulate,
-                       logits, R, F, Fp, rpb);
-  GIC_CHECK_LAUNCH("disc_match_fwd");
-  return GIC_OK;
+  return launch_match_fwd(dims, state->ydrop, q, dims->B, nullptr, scale, accumulate, logits, (hipStream_t)stream, "disc_match_fwd");
+}
+
+int gic_disc_match_fwd_grouped(const gic_disc_dims* dims, const gic_disc_state* state, const float* q, int32_t q_rows, const int32_t* q_index,
+                               float scale, int accumulate, float* logits, void* stream) {
+  GIC_PROPAGATE(check_match_dims(dims, "disc_match_fwd_grouped"));
+  GIC_CHECK_ARG(state, "disc_match_fwd_grouped: null state");
+  GIC_CHECK_ARG(q, "disc_match_fwd_grouped: null q");
+  GIC_CHECK_ARG(logits, "disc_match_fwd_grouped: null logits");
+  GIC_CHECK_ARG(state->ydrop, "disc_match_fwd_grouped: null state buffer (ydrop)");
+  GIC_CHECK_ARG((((uintptr_t)state->ydrop) & 15) == 0, "disc_match_fwd_grouped: ydrop must be 16-byte aligned");
+  GIC_CHECK_ARG(scale == scale, "disc_match_fwd_grouped: scale is NaN");
+  GIC_CHECK_ARG(q_rows >= 1, "disc_match_fwd_grouped: q_rows=%d must be >= 1", q_rows);
+  GIC_CHECK_ARG(q_index || q_rows == dims->B, "disc_match_fwd_grouped: q_index is NULL (the identity), so q_rows=%d must equal B=%d", q_rows,
+                dims->B);
+  return launch_match_fwd(dims, state->ydrop, q, q_rows, q_index, scale, accumulate, logits, (hipStream_t)stream, "disc_match_fwd_grouped");
 }
 
 int gic_gan_losses_mismatch(float w, int64_t n, float* losses_a, const float* losses_b, float* dd_real_a, float* dd_fake_a,

@@ -191,16 +191,56 @@ class Discriminator(nn.Module):
         return _DiscCondFn.apply(self.engine(), self.training, keep_mask, seed, self._param_grads, inp, image_features.detach(),
                                  self.img_proj.weight, self.img_proj.bias, *self.text_param_list())
 
-    def score(self, image_features, ids):
-        """Eval-mode score of (image, caption) pairs: the mean logit over the num_rep representations, [B]."""
+    def score(self, image_features, ids, image_index=None):
+        """Eval-mode score of (image, caption) pairs: the mean logit over the num_rep representations.  Three forms:
+        ``ids`` [B, L] against ``image_features`` [B, C] -> [B];  ``ids`` [B, K, L], K captions per image -> [B, K] (image b serves its K
+        captions through an index, nothing is repeated);  ``ids`` [N, L] with ``image_index`` int [N] into ``image_features`` [G, C] -> [N].
+        A module built without --disc-cond projection takes ``image_features=None`` and scores the captions alone.  Runs under no-grad
+        on a forward-only state and restores the module's mode."""
+        logits, shape = self.score_logits(image_features, ids, image_index)
+        return logits.view(-1, int(self.args.disc_num_rep)).mean(1).view(shape)
+
+    def score_logits(self, image_features, ids, image_index=None):
+        """The logits behind ``score``: (f32 [captions * num_rep] in caption-major order, the shape of the score)."""
+        if ids.dtype != torch.int64 or ids.dim() not in (2, 3):
+            raise ValueError(f"score takes int64 token ids [B, L] or [B, K, L], got {ids.dtype} {tuple(ids.shape)}")
+        shape = tuple(ids.shape[:-1])
+        flat = ids.reshape(-1, ids.shape[-1])
+        if self.cond != "projection":
+            if image_features is not None:
+                raise ValueError("image_features given to a discriminator built without --disc-cond projection")
+            if image_index is not None:
+                raise ValueError("image_index given to a discriminator built without --disc-cond projection")
+        else:
+            if image_features is None:
+                raise ValueError("a discriminator built with --disc-cond projection needs image_features")
+            G = image_features.shape[0]
+            if ids.dim() == 3:
+                if image_index is not None:
+                    raise ValueError("image_index goes with ids [N, L]: ids [B, K, L] are indexed by their first dimension")
+                if G != ids.shape[0]:
+                    raise ValueError(f"image_features has {G} rows for {ids.shape[0]} images")
+                K = ids.shape[1]
+                image_index = None if K == 1 else torch.arange(G * K, device=ids.device, dtype=torch.int32) // K
+            elif image_index is not None:
+                if image_index.dim() != 1 or image_index.shape[0] != flat.shape[0] or image_index.dtype not in (torch.int32, torch.int64):
+                    raise ValueError(f"image_index must be an int tensor [{flat.shape[0]}], got {image_index.dtype} {tuple(image_index.shape)}")
+                image_index = image_index.to(device=ids.device, dtype=torch.int32).contiguous()
+            elif G != flat.shape[0]:
+                raise ValueError(f"image_features has {G} rows for {flat.shape[0]} captions")
         was_training = self.training
         self.eval()
         try:
             with torch.no_grad():
-                logits = self.forward(ids, image_features)
+                eng = self.engine()
+                q = None
+                if self.cond == "projection":
+                    q, _ = eng.img_proj_fwd(self.img_proj.weight.detach(), self.img_proj.bias.detach(), image_features.detach())
+                logits, _ = eng.fwd([p.detach() for p in self.text_param_list()], None, flat, False, forward_only=True, cond=q,
+                                    cond_index=image_index)
         finally:
             self.train(was_training)
-        return logits.view(-1, int(self.args.disc_num_rep)).mean(1)
+        return logits, shape
 
     def get_feature(self, inp):
         raise NotImplementedError("get_feature is unused by the reference trainer and broken there for num_rep > 1 "
@@ -214,3 +254,20 @@ class Discriminator(nn.Module):
                     torch.nn.init.uniform_(param, a=-0.05, b=0.05)
                 elif self.args.disc_init == "normal":
                     torch.nn.init.normal_(param, std=1 / math.sqrt(param.shape[0]))
+
+
+def rerank(disc, image_features, ids, scores, lengths, weight=1.0, length_penalty=0.0, alphas=None):
+    """Re-rank K candidate captions per image with a discriminator's score (Dai et al. 2017): ``ids`` int64 [B, K, L], ``scores`` f32
+    [B, K] (G's log-probabilities), ``lengths`` int32 [B, K], ``alphas`` f32 [B, K, L, P] or None; ``image_features`` [B, C] the pooled
+    trunk features of the images (None for a D built without --disc-cond projection).
+      final[b, k] = scores[b, k] / max(lengths[b, k], 1) ** length_penalty + weight * disc.score(...)[b, k]
+    One D forward over the B*K captions (no repeat of the features: Discriminator.score's [B, K, L] form) and one gic_rerank launch.
+    Returns a dict in the new order (final descending, ties to the lower input index, NaN last): ``ids``, ``scores`` (G's raw
+    log-probabilities), ``lengths``, ``alphas`` (None without), ``order`` int32 [B, K] (input indices), ``final`` and ``d`` f32 [B, K]."""
+    if ids.dim() != 3:
+        raise ValueError(f"rerank takes ids [B, K, L], got {tuple(ids.shape)}")
+    K = ids.shape[1]
+    if not 1 <= K <= 64:
+        raise ValueError(f"rerank orders 1..64 candidates per image, got {K}")
+    logits, _ = disc.score_logits(image_features, ids)
+    return engine.rerank(scores, lengths, logits, int(disc.args.disc_num_rep), float(weight), float(length_penalty), ids=ids, alphas=alphas)

@@ -410,6 +410,59 @@ def gan_losses_mismatch(w: float, losses, grads, losses_wrong, grads_wrong):
     return losses, grads, grads_wrong
 
 
+def rerank(lm_scores: torch.Tensor, lengths: torch.Tensor, d_logits: torch.Tensor, R: int, weight: float, length_penalty: float = 0.0,
+           ids: Optional[torch.Tensor] = None, alphas: Optional[torch.Tensor] = None):
+    """gic_rerank: K candidates per image ordered by lm / max(len,1)^length_penalty + weight * mean_r d_logits (ties to the lower input
+    index, NaN last).  lm_scores f32 [B, K], lengths int32 [B, K], d_logits f32 [B*K*R], ids int64 [B, K, L], alphas f32 [B, K, L, P].
+    Returns a dict: order int32 [B, K], final / d f32 [B, K] and scores, lengths, ids, alphas (where given), all in the new order."""
+    require_gpu(lm_scores, lengths, d_logits, ids, alphas)
+    if lm_scores.dim() != 2 or lm_scores.dtype != torch.float32:
+        raise ValueError("rerank: scores must be float32 [B, K]")
+    B, K = lm_scores.shape
+    if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B, K):
+        raise ValueError(f"rerank: lengths must be int32 [B={B}, K={K}]")
+    if d_logits.dtype != torch.float32 or d_logits.numel() != B * K * int(R):
+        raise ValueError(f"rerank: d_logits must be float32 with B*K*R={B * K * int(R)} elements")
+    Lc = P = 0
+    if ids is not None:
+        if ids.dtype != torch.int64 or ids.dim() != 3 or tuple(ids.shape[:2]) != (B, K):
+            raise ValueError(f"rerank: ids must be int64 [B={B}, K={K}, L]")
+        Lc = ids.shape[2]
+    if alphas is not None:
+        if ids is None or alphas.dtype != torch.float32 or alphas.dim() != 4 or tuple(alphas.shape[:3]) != (B, K, Lc):
+            raise ValueError(f"rerank: alphas must be float32 [B={B}, K={K}, L={Lc}, P] beside ids")
+        P = alphas.shape[3]
+    lm_scores, lengths, d_logits = lm_scores.contiguous(), lengths.contiguous(), d_logits.contiguous()
+    ids = ids.contiguous() if ids is not None else None
+    alphas = alphas.contiguous() if alphas is not None else None
+    dev = lm_scores.device
+    out = {"order": torch.empty(B, K, device=dev, dtype=torch.int32), "final": torch.empty(B, K, device=dev, dtype=torch.float32),
+           "d": torch.empty(B, K, device=dev, dtype=torch.float32), "scores": torch.empty_like(lm_scores), "lengths": torch.empty_like(lengths),
+           "ids": torch.empty_like(ids) if ids is not None and Lc else None, "alphas": torch.empty_like(alphas) if alphas is not None and P else None}
+    L.check(L.load().gic_rerank(ptr(lm_scores), ptr(lengths), float(length_penalty), ptr(d_logits), int(R), float(weight), ptr(ids), ptr(alphas),
+                                B, K, Lc, P, ptr(out["order"]), ptr(out["final"]), ptr(out["d"]), ptr(out["ids"]), ptr(out["scores"]),
+                                ptr(out["lengths"]), ptr(out["alphas"]), stream_ptr()), "gic_rerank")
+    return out
+
+
+def match_ranks(S: torch.Tensor, row_bias: Optional[torch.Tensor] = None, N: Optional[int] = None):
+    """gic_match_ranks: (rank_c2i, rank_i2c) int32 [N], 0-based, of the pair scores T[c, j] = S[c, j] + row_bias[c]: the number of other
+    candidates that are not strictly below the true pair (a tie or a NaN counts against it).  S f32 [>= N, ld] with unit column stride."""
+    require_gpu(S, row_bias)
+    if S.dim() != 2 or S.dtype != torch.float32 or S.stride(1) != 1:
+        raise ValueError("match_ranks: S must be a float32 matrix with unit column stride")
+    N = int(S.shape[0] if N is None else N)
+    if N > S.shape[0] or N > S.shape[1]:
+        raise ValueError(f"match_ranks: N={N} exceeds S {tuple(S.shape)}")
+    if row_bias is not None and (row_bias.dtype != torch.float32 or row_bias.numel() < N or not row_bias.is_contiguous()):
+        raise ValueError(f"match_ranks: row_bias must be contiguous float32 [N={N}]")
+    c2i = torch.empty(max(N, 0), device=S.device, dtype=torch.int32)
+    i2c = torch.empty(max(N, 0), device=S.device, dtype=torch.int32)
+    L.check(L.load().gic_match_ranks(ptr(S), S.stride(0) if S.shape[0] > 1 else max(S.shape[1], 1), ptr(row_bias), N, ptr(c2i), ptr(i2c),
+                                     stream_ptr()), "gic_match_ranks")
+    return c2i, i2c
+
+
 def xent(logits: torch.Tensor, targets: torch.Tensor, want_grad: bool = True, row_weight: Optional[torch.Tensor] = None):
     """CrossEntropyLoss(mean over all rows). logits [rows,V] (f32/bf16, contiguous). Returns (loss[1], d_logits|None).
     ``row_weight`` f32 [rows]: weighted form (policy-gradient loss, gicap.h)."""
@@ -988,15 +1041,21 @@ class DiscEngine:
 
     def fwd(self, params, inp_soft: Optional[torch.Tensor], inp_ids: Optional[torch.Tensor], train: bool,
             keep_mask: Optional[torch.Tensor] = None, seed: int = 0, state=None, logits=None, forward_only: bool = False,
-            dev_scalars=None, seed_slot: int = 0, cond: Optional[torch.Tensor] = None):
+            dev_scalars=None, seed_slot: int = 0, cond: Optional[torch.Tensor] = None, cond_index: Optional[torch.Tensor] = None):
         """``dev_scalars`` / ``seed_slot``: the dropout seed is read from device memory (gic_step_scalars).  ``forward_only`` (eval mode only): nothing is saved for a backward pass (see alloc_state).
-        ``cond``: f32 [B, F], one row per caption (the image projection q of a conditioned D): the match term is added to the logits."""
+        ``cond``: f32 [B, F], one row per caption (the image projection q of a conditioned D): the match term is added to the logits.
+        ``cond_index`` (inference only: no backward knows it): int32 [B], caption b is scored against ``cond[cond_index[b]]`` and ``cond``
+        is [q_rows, F] (match_logits)."""
         if forward_only and train:
             raise ValueError("forward_only is an eval-mode option: the train-mode forward saves its dropout mask for the backward")
+        if cond_index is not None and cond is None:
+            raise ValueError("cond_index without cond")
         self.check_params(params)
         src = inp_soft if inp_soft is not None else inp_ids
         require_gpu(src, keep_mask)
         B, Lc = src.shape[0], src.shape[1]
+        if cond is not None:
+            cond = self._check_cond(cond, B, cond_index)                 # before anything is launched
         dev = src.device
         if inp_ids is not None:
             if inp_ids.dtype != torch.int64:
@@ -1015,34 +1074,67 @@ class DiscEngine:
             ptr(inp_soft), self.V, ptr(inp_ids), int(bool(train)), ptr(keep_mask), int(seed) & (2 ** 64 - 1), ptr(logits),
             dev_scalars.ptr if dev_scalars is not None else None, int(seed_slot), stream_ptr()), "gic_disc_fwd")
         if cond is not None:
-            self.match_logits(st, cond, logits=logits, accumulate=True)
+            self.match_logits(st, cond, logits=logits, accumulate=True, q_index=cond_index)
         return logits, st
 
     def match_scale(self) -> float:
         return float(self.F) ** -0.5
 
-    def _check_cond(self, q: torch.Tensor, B: int) -> torch.Tensor:
-        require_gpu(q)
+    def _check_cond(self, q: torch.Tensor, B: int, q_index: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``q`` f32 [B, F], one row per caption; with ``q_index`` (int32 device tensor [B]) f32 [q_rows, F], q_rows >= 1."""
+        require_gpu(q, q_index)
         if q.dtype != torch.float32:
             raise ValueError("the image projection q must be float32")
-        if tuple(q.shape) != (B, self.F):
-            raise ValueError(f"the image projection q must be [captions={B}, F={self.F}], got {tuple(q.shape)}")
+        if q_index is None:
+            if tuple(q.shape) != (B, self.F):
+                raise ValueError(f"the image projection q must be [captions={B}, F={self.F}], got {tuple(q.shape)}")
+        else:
+            if q.dim() != 2 or q.shape[1] != self.F or q.shape[0] < 1:
+                raise ValueError(f"the image projection q must be [q_rows >= 1, F={self.F}] under an index, got {tuple(q.shape)}")
+            if q_index.dtype != torch.int32 or tuple(q_index.shape) != (B,) or not q_index.is_contiguous():
+                raise ValueError(f"the image index must be a contiguous int32 tensor [captions={B}], got {q_index.dtype} {tuple(q_index.shape)}")
         return q.contiguous()
 
-    def match_logits(self, state: dict, q: torch.Tensor, logits=None, accumulate: bool = False):
+    def match_logits(self, state: dict, q: torch.Tensor, logits=None, accumulate: bool = False, q_index: Optional[torch.Tensor] = None):
         """gic_disc_match_fwd: the match term F^-1/2 <ydrop[m], q[m // R]> of a forward's state (a forward-only one included), alone or
-        (``accumulate``) added to ``logits``."""
+        (``accumulate``) added to ``logits``.  ``q_index`` (int32 [captions]): gic_disc_match_fwd_grouped, caption b against
+        ``q[q_index[b]]`` of ``q`` [q_rows, F]; an index outside [0, q_rows) gives that caption NaN logits."""
         MR = state["ydrop"].shape[0]
         B = MR // self.R
-        q = self._check_cond(q, B)
+        q = self._check_cond(q, B, q_index)
         if logits is None:
             if accumulate:
                 raise ValueError("match_logits: accumulate needs logits")
             logits = torch.empty(MR, device=q.device, dtype=torch.float32)
         d = self.dims(B, max(self.fs))
+        if q_index is not None:
+            L.check(L.load().gic_disc_match_fwd_grouped(C.byref(d), C.byref(self._state_struct(state)), ptr(q), q.shape[0], ptr(q_index),
+                                                        self.match_scale(), int(bool(accumulate)), ptr(logits), stream_ptr()),
+                    "gic_disc_match_fwd_grouped")
+            return logits
         L.check(L.load().gic_disc_match_fwd(C.byref(d), C.byref(self._state_struct(state)), ptr(q), self.match_scale(), int(bool(accumulate)),
                                             ptr(logits), stream_ptr()), "gic_disc_match_fwd")
         return logits
+
+    def rep_mean(self, state: dict, logits: Optional[torch.Tensor] = None, ybar=None, lbar=None):
+        """gic_disc_rep_mean: (ybar f32 [B, F], lbar f32 [B] or None) = the means over the R representations of a forward's ``ydrop``
+        and of its base ``logits`` [B*R], summed in index order.  ``ybar`` / ``lbar``: destinations (rows of a larger buffer)."""
+        MR = state["ydrop"].shape[0]
+        B = MR // self.R
+        dev = state["ydrop"].device
+        require_gpu(state["ydrop"], logits, ybar, lbar)
+        ybar = ybar if ybar is not None else torch.empty(B, self.F, device=dev, dtype=torch.float32)
+        if logits is not None:
+            if logits.dtype != torch.float32 or logits.numel() != MR or not logits.is_contiguous():
+                raise ValueError(f"rep_mean: logits must be contiguous float32 [B*R={MR}]")
+            lbar = lbar if lbar is not None else torch.empty(B, device=dev, dtype=torch.float32)
+        for name, t, shape in (("ybar", ybar, (B, self.F)), ("lbar", lbar, (B,))):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError(f"rep_mean: {name} must be contiguous float32 {shape}")
+        d = self.dims(B, max(self.fs))
+        L.check(L.load().gic_disc_rep_mean(C.byref(d), C.byref(self._state_struct(state)), ptr(logits), ptr(ybar),
+                                           ptr(lbar) if logits is not None else None, stream_ptr()), "gic_disc_rep_mean")
+        return ybar, (lbar if logits is not None else None)
 
     def shared_state(self, src: dict, B: int, Lc: int, dev) -> dict:
         """State of a second forward on the same input: its own dropout / head buffers, the rest aliases ``src``."""

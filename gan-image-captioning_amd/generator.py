@@ -606,34 +606,68 @@ class Generator(nn.Module):
         self.init_params()
 
     def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False, return_alphas=False,
-                beam_groups=1, diversity=0.0, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
+                beam_groups=1, diversity=0.0, rerank_disc=None, rerank_weight=1.0, return_rerank=False, no_repeat_ngram=0, min_length=0,
+                suppress_tokens=()):
         """Captions for ``images`` by beam search: features as the trainer forms them (training.py:66-68) -- the encoder in the
         module's current mode, or embed(<S>) with --conditional-gan 0 -- under no-grad, then ``decoder.beam_search``.  With
         --decoder attention the encoder also gives the feature map, and ``return_alphas`` appends the attention weights
         (AttnDecoder.beam_search).  ``beam_groups`` / ``diversity``: diverse beam search (Decoder.beam_search).  ``no_repeat_ngram`` /
-        ``min_length`` / ``suppress_tokens``: decode constraints (Decoder.beam_search)."""
+        ``min_length`` / ``suppress_tokens``: decode constraints (Decoder.beam_search).
+        ``rerank_disc`` (a Discriminator; None = the search's own order, nothing else runs): the ``beam_size`` beams are re-ranked by
+        score / max(len, 1) ** length_penalty + ``rerank_weight`` * rerank_disc.score (discriminator.rerank: a conditioned D scores them
+        against this call's pooled trunk features, any other D the captions alone); the best caption, or all beams with
+        ``return_beams``, come in the new order, the attention weights with them; ``scores`` stay G's log-probabilities.
+        ``return_rerank`` appends (final [B, k], d [B, k]) in the new order."""
         kw = dict(beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id, length_penalty=length_penalty, return_beams=return_beams,
                   beam_groups=beam_groups, diversity=diversity, no_repeat_ngram=no_repeat_ngram, min_length=min_length,
                   suppress_tokens=suppress_tokens)
         if return_alphas and not isinstance(self.decoder, AttnDecoder):
             raise ValueError("attention weights exist for --decoder attention only")
+        if rerank_disc is None and return_rerank:
+            raise ValueError("return_rerank needs rerank_disc")
         with torch.no_grad():
             features, fmap = self._features(images)
+            if rerank_disc is not None:
+                kw["return_beams"] = True
             if fmap is None:
-                return self.decoder.beam_search(features, **kw)
-            return self.decoder.beam_search(features, fmap, return_alphas=return_alphas, **kw)
+                out = self.decoder.beam_search(features, **kw)
+            else:
+                out = self.decoder.beam_search(features, fmap, return_alphas=return_alphas, **kw)
+            if rerank_disc is None:
+                return out
+            r = self._rerank(rerank_disc, out, rerank_weight, length_penalty)
+        res = (r["ids"], r["scores"], r["lengths"]) + ((r["alphas"],) if return_alphas else ())
+        if not return_beams:
+            res = tuple(t[:, 0] for t in res)
+        return res + (((r["final"], r["d"]),) if return_rerank else ())
+
+    def _rerank(self, disc, cands, weight, length_penalty=0.0):
+        """discriminator.rerank of this call's candidates (ids, scores, lengths[, alphas]) against this call's pooled trunk features."""
+        from .discriminator import rerank
+        feats = None
+        if getattr(disc, "cond", "none") == "projection":
+            if not self.args.conditional_gan:
+                raise ValueError("a discriminator built with --disc-cond projection scores (image, caption) pairs: it needs --conditional-gan 1")
+            feats = self.encoder.last_trunk
+        return rerank(disc, feats, cands[0], cands[1], cands[2], weight=weight, length_penalty=length_penalty,
+                      alphas=cands[3] if len(cands) > 3 else None)
 
     def sample_captions(self, images, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
-                        noise_u=None, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
+                        noise_u=None, rerank_disc=None, rerank_weight=1.0, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """``num_samples`` sampled captions per image (decoder.sample_captions), with the features formed as ``caption`` forms them:
         the encoder in the module's current mode, or embed(<S>) with --conditional-gan 0, under no-grad; with --decoder attention the
         encoder also gives the feature map.  ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: decode constraints
-        (Decoder.sample_captions).  Returns (ids [B, n, L], scores [B, n], lengths [B, n])."""
+        (Decoder.sample_captions).  Returns (ids [B, n, L], scores [B, n], lengths [B, n]) in draw order; with ``rerank_disc``
+        (best-of-n) ordered by scores + ``rerank_weight`` * rerank_disc.score instead (``caption``)."""
         kw = dict(num_samples=num_samples, top_k=top_k, top_p=top_p, temperature=temperature, max_caption_len=max_caption_len,
                   eos_id=eos_id, seed=seed, noise_u=noise_u, no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
         with torch.no_grad():
             features, fmap = self._features(images)
-            return self.decoder.sample_captions(features, *(() if fmap is None else (fmap,)), **kw)
+            out = self.decoder.sample_captions(features, *(() if fmap is None else (fmap,)), **kw)
+            if rerank_disc is None:
+                return out
+            r = self._rerank(rerank_disc, out, rerank_weight)
+        return r["ids"], r["scores"], r["lengths"]
 
     def forward(self, images, caps, lengths, pretrain=False):
         features, fmap = self._features(images)

@@ -63,6 +63,19 @@ def corpus_bleu(stats_sum) -> List[float]:
     return out
 
 
+def retrieval_summary(ranks) -> dict:
+    """{"r1", "r5", "r10", "medr", "meanr"} of 0-based retrieval ranks (GANInstructor.evaluate_retrieval): R@K = the share of items whose
+    true pair is among the K best (rank < K), the median (the mean of the two middle ranks of an even count) and mean rank 1-based."""
+    r = sorted(int(v) for v in (ranks.tolist() if hasattr(ranks, "tolist") else ranks))
+    n = len(r)
+    if n == 0:
+        return {"r1": 0.0, "r5": 0.0, "r10": 0.0, "medr": 0.0, "meanr": 0.0}
+    out = {f"r{k}": sum(v < k for v in r) / n for k in (1, 5, 10)}
+    out["medr"] = 1.0 + (r[n // 2] if n % 2 else 0.5 * (r[n // 2 - 1] + r[n // 2]))
+    out["meanr"] = 1.0 + sum(r) / n
+    return out
+
+
 def _check_weights(w_cider, w_bleu, w_rouge) -> Tuple[float, float, float]:
     w = (float(w_cider), float(w_bleu), float(w_rouge))
     if any(not math.isfinite(v) or v < 0.0 for v in w):

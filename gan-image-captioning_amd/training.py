@@ -452,6 +452,8 @@ class GANInstructor:
                                         temperature=float(getattr(self.args, "eval_sample_temperature", 1.0)))
             if int(getattr(self.args, "eval_match", 0)) and self.dist.rank == 0:
                 self.evaluate_match("val")
+            if int(getattr(self.args, "eval_retrieval", 0)) and self.dist.rank == 0:
+                self.evaluate_retrieval("val", max_items=int(getattr(self.args, "eval_retrieval_items", 1000)))
             if int(getattr(self.args, "eval_diverse_beam_size", 0)) > 0 and self.dist.rank == 0:
                 self.evaluate_diverse_beam("val", beam_size=int(self.args.eval_diverse_beam_size),
                                            groups=int(getattr(self.args, "eval_diverse_groups", 2)),
@@ -475,7 +477,7 @@ class GANInstructor:
                 cands.append(words(ids[b, :int(lengths[b])].tolist()))
                 refs.append([words(c) for c in group])
         score = bleu_score(cands, refs)
-        self.log.info("[EVAL] BLEU-4 (%s, beam %d): %.4f", what, beam_size, score)
+        self.log.info("[EVAL] BLEU-4 (%s, %s): %.4f", what, self._beam_label(beam_size), score)
         self.writer.add_scalar(f"BLEU4_{what}", score, max(self.adv_epoch, 0))
         return score
 
@@ -514,6 +516,81 @@ class GANInstructor:
         self.writer.add_scalar(f"MatchMargin_{what}", out["margin"], step)
         return out
 
+    RETRIEVAL_MAX_ITEMS = 8192
+
+    def evaluate_retrieval(self, what="val", max_items=None):
+        """Image-caption retrieval of the conditioned D (--disc-cond projection) over the first N = min(max_items, len) items of the
+        adversarial eval (``what="val"``) or train loader (len = what the loader yields on this rank: its sampler's length, the shard
+        under data parallelism); item i is (image i, caption i).  The pair score of caption c and image j is
+        the mean over the representations of D's eval logit, T[c, j] = lbar[c] + F^-1/2 <ybar[c], q[j]> (linear in the logits).  Per
+        batch one trunk pass, one img_proj_fwd, one forward-only D forward and one gic_disc_rep_mean into [N, F] / [N] buffers; at the
+        end one f32 gic_gemm S = F^-1/2 Ybar Q^T, one gic_match_ranks and one sync.  A tie or a NaN counts against the true pair.
+        Returns {"n": N, "c2i": {"r1", "r5", "r10", "medr", "meanr"}, "i2c": {...}} (caption -> image and image -> caption, recalls as
+        fractions, ranks 1-based); logs them and writes the scalars ``Retr_c2i_R1_<what>`` ...  Refuses (ValueError, before anything
+        runs) a D without --disc-cond projection, --captions-per-image != 1 (a repeated image ties with itself) and N > 8192."""
+        from .metrics import retrieval_summary
+        if self.disc.cond != "projection":
+            raise ValueError("evaluate_retrieval needs a discriminator built with --disc-cond projection")
+        if int(getattr(self.args, "captions_per_image", 1)) != 1:
+            raise ValueError("evaluate_retrieval needs --captions-per-image 1: a repeated image ties with itself, and every tie counts "
+                             "against the true pair")
+        loader = self.adv_eval_loader if what == "val" else self.adv_train_loader
+        N = self._loader_items(loader)
+        N = N if max_items is None else min(int(max_items), N)
+        if N > self.RETRIEVAL_MAX_ITEMS:
+            raise ValueError(f"evaluate_retrieval: {N} items exceed {self.RETRIEVAL_MAX_ITEMS} (the score matrix would be "
+                             f"{4 * N * N / 1e6:.0f} MB): set max_items / --eval-retrieval-items")
+        if N < 1:
+            raise ValueError("evaluate_retrieval: no items")
+        dev = self.args.device
+        den = self.disc.engine()
+        nF = den.F
+        ybar = torch.empty(N, nF, dtype=torch.float32, device=dev)
+        lbar = torch.empty(N, dtype=torch.float32, device=dev)
+        qall = torch.empty(N, nF, dtype=torch.float32, device=dev)
+        n = 0
+        with torch.no_grad():
+            dparams = [p.detach() for p in self.disc.text_param_list()]
+            wp, bp = self.disc.img_proj.weight.detach(), self.disc.img_proj.bias.detach()
+            for batch in loader:
+                if n >= N:
+                    break
+                k = min(int(batch[1].shape[0]), N - n)
+                images, captions = batch[0][:k].to(dev), batch[1][:k].to(dev)
+                main = torch.cuda.current_stream(images.device)
+                den.img_proj_fwd(wp, bp, self.gen.encoder.take_trunk(images, False, main), out=qall[n:n + k])
+                logits, st = den.fwd(dparams, None, captions, False, forward_only=True)
+                den.rep_mean(st, logits, ybar=ybar[n:n + k], lbar=lbar[n:n + k])
+                n += k
+            if n < 1:
+                raise ValueError("evaluate_retrieval: the loader gave no items")
+            if n < N:                                                    # a loader that yields fewer items than it announced: rank those
+                self.log.info("[EVAL] retrieval (%s): the loader gave %d of %d items", what, n, N)
+                N, ybar, lbar, qall = n, ybar[:n], lbar[:n], qall[:n]
+            S = torch.empty(N, N, dtype=torch.float32, device=dev)
+            engine.gemm(ybar, qall, S, N, N, nF, nF, nF, N, True, True, alpha=den.match_scale())
+            c2i, i2c = engine.match_ranks(S, lbar)
+            ranks = torch.stack([c2i, i2c]).cpu()                        # the one sync
+        out = {"n": N, "c2i": retrieval_summary(ranks[0]), "i2c": retrieval_summary(ranks[1])}
+        step = max(self.adv_epoch, 0)
+        for d in ("c2i", "i2c"):
+            o = out[d]
+            self.log.info("[EVAL] retrieval %s (%s, %d items): R@1 %.4f | R@5 %.4f | R@10 %.4f | median rank %.1f | mean rank %.2f",
+                          d, what, N, o["r1"], o["r5"], o["r10"], o["medr"], o["meanr"])
+            for name, key in (("R1", "r1"), ("R5", "r5"), ("R10", "r10"), ("MedR", "medr"), ("MeanR", "meanr")):
+                self.writer.add_scalar(f"Retr_{d}_{name}_{what}", o[key], step)
+        return out
+
+    @staticmethod
+    def _loader_items(loader) -> int:
+        """The items ``loader`` will yield on this rank: the length of its sampler where it has one (under data parallelism the
+        DistributedSampler's shard, not the dataset), else of its dataset, else counted from its batches."""
+        for name in ("sampler", "dataset"):
+            src = getattr(loader, name, None)
+            if src is not None and hasattr(src, "__len__"):
+                return len(src)
+        return sum(int(b[1].shape[0]) for b in loader)
+
     def _eval_constraints(self):
         """The decode constraints of every evaluation (--eval-no-repeat-ngram, --eval-min-length, --eval-suppress-tokens) as the
         keywords of Generator.caption / sample_captions."""
@@ -521,10 +598,20 @@ class GANInstructor:
                     min_length=int(getattr(self.args, "eval_min_length", 0) or 0),
                     suppress_tokens=tuple(int(v) for v in (getattr(self.args, "eval_suppress_tokens", ()) or ())))
 
+    def _eval_rerank(self):
+        """--eval-rerank-weight as the keywords of Generator.caption: nothing when it is 0 (the search's own order, no D pass)."""
+        w = float(getattr(self.args, "eval_rerank_weight", 0.0) or 0.0)
+        return dict(rerank_disc=self.disc, rerank_weight=w) if w != 0.0 else {}
+
+    def _beam_label(self, beam_size):
+        """'beam k' of the evaluations' log lines, with the re-rank weight next to it when one is set."""
+        w = float(getattr(self.args, "eval_rerank_weight", 0.0) or 0.0)
+        return "beam %d" % beam_size if w == 0.0 else "beam %d, rerank weight %g" % (beam_size, w)
+
     def _beam_decode(self, what, beam_size, max_caption_len=None, batch_size=None):
         """The decode of ``evaluate`` / ``evaluate_cider``: the best beam of each image (``_decode_batches``)."""
         def decode(images, L, _):
-            ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L, **self._eval_constraints())
+            ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L, **self._eval_constraints(), **self._eval_rerank())
             return ids, lengths
         return self._decode_batches(what, decode, max_caption_len, batch_size)
 
@@ -563,7 +650,7 @@ class GANInstructor:
         for ids, lengths, caps in self._beam_decode(what, beam_size, max_caption_len, batch_size):
             scores.append(scorer.score(ids, lengths, RefBatch.pack(caps).to(self.args.device)))
         score = float(torch.cat(scores).double().mean()) if scores else 0.0
-        self.log.info("[EVAL] CIDEr-D (%s, beam %d): %.4f", what, beam_size, score)
+        self.log.info("[EVAL] CIDEr-D (%s, %s): %.4f", what, self._beam_label(beam_size), score)
         self.writer.add_scalar(f"CIDErD_{what}", score, max(self.adv_epoch, 0))
         return score
 
@@ -598,8 +685,8 @@ class GANInstructor:
             sums, rouge_l, cider_d = [0] * len(STAT_COLUMNS), 0.0, 0.0
         bleu = corpus_bleu(sums)
         out = {"bleu1": bleu[0], "bleu2": bleu[1], "bleu3": bleu[2], "bleu4": bleu[3], "rouge_l": rouge_l, "cider_d": cider_d}
-        self.log.info("[EVAL] metrics (%s, beam %d): BLEU-1 %.4f | BLEU-2 %.4f | BLEU-3 %.4f | BLEU-4 %.4f | ROUGE-L %.4f | CIDEr-D %.4f",
-                      what, beam_size, out["bleu1"], out["bleu2"], out["bleu3"], out["bleu4"], out["rouge_l"], out["cider_d"])
+        self.log.info("[EVAL] metrics (%s, %s): BLEU-1 %.4f | BLEU-2 %.4f | BLEU-3 %.4f | BLEU-4 %.4f | ROUGE-L %.4f | CIDEr-D %.4f",
+                      what, self._beam_label(beam_size), out["bleu1"], out["bleu2"], out["bleu3"], out["bleu4"], out["rouge_l"], out["cider_d"])
         step = max(self.adv_epoch, 0)
         for name, key in (("BLEU1M", "bleu1"), ("BLEU2M", "bleu2"), ("BLEU3M", "bleu3"), ("BLEU4M", "bleu4"), ("ROUGEL", "rouge_l"),
                           ("CIDErDM", "cider_d")):

@@ -663,6 +663,30 @@ int gic_disc_bwd_cond(const gic_disc_dims* dims, const gic_disc_params* params, 
 int gic_gan_losses_mismatch(float w, int64_t n, float* losses_a, const float* losses_b, float* dd_real_a, float* dd_fake_a,
                             const float* dd_real_b, float* dd_fake_b, void* stream);
 
+/* Inference uses of D (no reference counterpart; additions to ABI v5).
+ * The match term with an image index per caption: caption b (of dims->B) is scored against row q_index[b] of q (f32 [q_rows, F]),
+ *   logits[b R + r] (+)= scale * sum_{n<F} ydrop[b R + r, n] * q[q_index[b], n]
+ * q_index == NULL is the identity (then q_rows must equal B, and the result carries the bits of gic_disc_match_fwd).  An index outside
+ * [0, q_rows) is never dereferenced: the R logits of that caption become NaN.  One kernel serves both entries. */
+int gic_disc_match_fwd_grouped(const gic_disc_dims* dims, const gic_disc_state* state, const float* q, int32_t q_rows,
+                               const int32_t* q_index, float scale, int accumulate, float* logits, void* stream);
+/* Re-rank K candidates per image (K in 1..64) by G's length-normalised log-probability plus weight times D's score:
+ *   d[b,k] = (1/R) sum_r d_logits[(b K + k) R + r]   (r in index order)      final[b,k] = lm[b,k] / max(len,1)^length_penalty + weight d[b,k]
+ * (weight == 0: final is the first term alone, whatever d_logits holds).  order[b,:] = the input indices by final descending, ties to the
+ * lower input index, a NaN final last; final_scores, d_scores, out_ids [B,K,L], out_lm_scores, out_lengths and out_alphas [B,K,L,P] are
+ * the inputs' rows in that order (out_ids / out_lm_scores / out_lengths / out_alphas may be NULL; alphas == NULL or P == 0: none).  One
+ * workgroup per image, no atomics.  An output that overlaps an input or another output is refused (GIC_STATUS_INVALID_ARG). */
+int gic_rerank(const float* lm_scores, const int32_t* lengths, float length_penalty, const float* d_logits, int32_t R, float weight,
+               const int64_t* ids, const float* alphas, int32_t B, int32_t K, int32_t L, int32_t P, int32_t* order, float* final_scores,
+               float* d_scores, int64_t* out_ids, float* out_lm_scores, int32_t* out_lengths, float* out_alphas, void* stream);
+/* Means over the R representations of a forward's state: ybar[c, :] = (1/R) sum_r ydrop[c R + r, :F] (f32 [B, F]) and, when logits
+ * (f32 [B*R], the base logits) and lbar (f32 [B]) are given, lbar[c] = (1/R) sum_r logits[c R + r]; r in index order.  B <= 65535 per call. */
+int gic_disc_rep_mean(const gic_disc_dims* dims, const gic_disc_state* state, const float* logits, float* ybar, float* lbar, void* stream);
+/* Retrieval ranks (0-based) of N (image, caption) pairs from their score matrix: T[c,j] = S[c,j] + row_bias[c] (row_bias NULL = 0),
+ *   rank_c2i[c] = #{j != c : !(T[c,j] < T[c,c])}        rank_i2c[j] = #{c != j : !(T[c,j] < T[j,j])}
+ * so a tie or a NaN counts against the true pair.  S is f32 with row stride ld >= N; the counts are integers (order-free). */
+int gic_match_ranks(const float* S, int64_t ld, const float* row_bias, int32_t N, int32_t* rank_c2i, int32_t* rank_i2c, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Encoder (src/generator.py:8-25): ResNet trunk forward (frozen, BatchNorm on batch statistics) and the trainable
  * Linear + BatchNorm1d(momentum=0.01) head.  Activations are NHWC in the compute dtype ("act").
