@@ -115,6 +115,11 @@ class AttnBwdWs(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("dlogits", "dhout", "dgates", "dc", "dz", "dalpha", "dh_extra", "dhproj", "dfproj", "dfproj_act", "dwa_rows", "dx")]
 
 
+class SchedSampleOpts(C.Structure):       # gic_sched_sample_opts
+    _fields_ = [("prob", C.c_float), ("pick", C.c_int32), ("coin_u", c_void_p), ("noise_u", c_void_p), ("seed", C.c_uint64),
+                ("inputs", c_void_p), ("replaced", c_void_p)]
+
+
 class DiscDims(C.Structure):
     _fields_ = [("B", C.c_int32), ("L", C.c_int32), ("V", C.c_int32), ("De", C.c_int32), ("R", C.c_int32),
                 ("nconv", C.c_int32), ("fsize", C.c_int32 * MAX_CONVS), ("nfilt", C.c_int32 * MAX_CONVS),
@@ -219,6 +224,12 @@ _SIGNATURES = {
                                       c_void_p]),
     "gic_attn_forward_tf_bwd": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), _P(AttnBwdWs), c_void_p, c_void_p,
                                           c_void_p, c_void_p, C.c_int, c_void_p, c_void_p, C.c_float, C.c_int, _P(AttnGrads), c_void_p]),
+    "gic_decoder_forward_ss_ws_bytes": (C.c_int, [_P(DecoderDims), C.c_int, c_void_p]),
+    "gic_decoder_forward_ss": (C.c_int, [_P(DecoderDims), _P(DecoderParams), _P(DecoderShadow), _P(DecoderState), c_void_p, c_void_p,
+                                         c_void_p, C.c_int, _P(SchedSampleOpts), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_attn_forward_ss_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int, c_void_p]),
+    "gic_attn_forward_ss": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), c_void_p, c_void_p, c_void_p, c_void_p,
+                                      C.c_int, _P(SchedSampleOpts), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_attn_rollout_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int64, c_void_p]),
     "gic_attn_rollout": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), c_void_p, c_void_p, C.c_int64, c_void_p,
                                    c_void_p, c_void_p, C.c_uint64, c_void_p, c_void_p, c_void_p]),

@@ -92,6 +92,12 @@ _NATIVE = [
     ("--pretrain-mode", str, "sample", "MLE pre-training input: sample = the reference's free-running roll-out (sample(pretrain=True), "
                                        "training.py:66-83); teacher = teacher forcing, decoder.forward(features, captions[:, :-1], lengths)",
      {"choices": ["sample", "teacher"]}),
+    ("--scheduled-sampling-prob", float, 0.0, "scheduled sampling (Bengio et al., 2015) in --pretrain-mode teacher: each input token of a "
+                                              "training batch is the decoder's own pick from the previous step with this probability, "
+                                              "else the ground truth; 0 = off (pure teacher forcing).  Validation is never mixed"),
+    ("--scheduled-sampling-ramp-epochs", int, 0, "epoch e (0-based) trains with p_e = p * min(1, e / n); 0 = p throughout"),
+    ("--scheduled-sampling-pick", str, "sample", "the replaced token: sample = a draw from the previous step's softmax, argmax = its mode",
+     {"choices": ["sample", "argmax"]}),
     ("--attn-reg", float, 0.0, "weight of the doubly stochastic attention penalty mean_b sum_i (1 - sum_t alpha_bti)^2 added to the "
                                "pre-training loss (--decoder attention --pretrain-mode teacher only)"),
     ("--eval-beam-size", int, 0, "beam size of the BLEU-4 evaluation (GANInstructor.evaluate) after each adversarial epoch's validation; "

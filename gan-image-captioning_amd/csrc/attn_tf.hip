@@ -28,9 +28,15 @@ size_t tf_ws_floats(const ACtx& c, int Tmax) {
 template <typename TA>
 int attn_tf_fwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st, const float* features,
                   const void* fmap, const int64_t* caps, const int32_t* lengths, int Tmax, const float* noise_u, uint64_t seed,
-                  float temperature, int pretrain, float* logits_ws, void* out, float* alphas, float* h_n, float* c_n, hipStream_t stream) {
+                  float temperature, int pretrain, float* logits_ws, void* out, float* alphas, float* h_n, float* c_n, hipStream_t stream,
+                  const gic_sched_sample_opts* ss = nullptr) {
   const int B = c.B, T = c.L, V = c.V, E = c.E, H = c.H;
   const long ld = c.ldx();
+  // scheduled sampling (gic_attn_forward_ss): the logits of step t are formed inside the loop (so the energies sit behind them in the
+  // workspace) and ss_pick decides the x rows of slot t + 1 from them; rows it does not replace keep the teacher's embedding
+  float* energies = ss ? logits_ws + (size_t)B * Tmax * V : logits_ws;
+  const bool ss_fused = ss && ss_fused_logits(c.dt, B, V, E, H, 1);
+  if (ss) GIC_PROPAGATE(ss_tail(caps, ss->inputs, ss->replaced, B, T - 1, Tmax - 1, stream));
   // slots 0..Tmax of xh start at zero (z of padded rows stays zero: finite operands of the weight gradients), c_0 = 0, x_0 = features,
   // x_t = embed(caps[:, t-1])
   GIC_PROPAGATE(fill_zero(st->xh, (size_t)(Tmax + 1) * B * ld * c.asz(), stream));
@@ -55,7 +61,7 @@ int attn_tf_fwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow
       GIC_PROPAGATE(gemm(g, stream));
     }
     AttnStepArgs f{};                // par and stop stay null: the packed form reads lengths instead
-    f.fproj = st->fproj; f.fmap = fmap; f.w_a = P->w_a; f.hp = hp; f.e = logits_ws;
+    f.fproj = st->fproj; f.fmap = fmap; f.w_a = P->w_a; f.hp = hp; f.e = energies;
     f.z = xh_t + E; f.ldx = ld; f.alpha = st->alpha + (long)t * B * c.P;
     f.P = c.P; f.A = c.A; f.C = c.C;
     f.lengths = lengths; f.t = t;
@@ -69,9 +75,21 @@ int attn_tf_fwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow
     a.B = B; a.H = H; a.din = c.din(); a.ldx = ld; a.gw = E;
     a.pack_len = lengths; a.pack_t = t;
     GIC_PROPAGATE(lstm_step(a, c.dt, stream));
+    if (ss) {
+      GIC_PROPAGATE(ss_step_logits(c.dt, st->hout, t, Tmax, S->wout, P->b_out, logits_ws, B, V, H, ss_fused, stream));
+      if (t + 1 < Tmax) {
+        SsPickArgs k;
+        k.logits = logits_ws + (long)t * V; k.ld_logits = (long)Tmax * V;
+        k.caps = caps; k.lengths = lengths; k.coin_u = ss->coin_u; k.noise_u = ss->noise_u; k.seed = ss->seed;
+        k.prob = ss->prob; k.pick = ss->pick; k.t = t + 1; k.B = B; k.V = V; k.E = E; k.Tm1 = T - 1;
+        k.embed = P->embed; k.x_next = xh_t + (long)B * ld; k.ld_x = ld;
+        k.inputs = ss->inputs; k.replaced = ss->replaced;
+        GIC_PROPAGATE(ss_pick(k, c.dt, stream));
+      }
+    }
   }
   const long rows = (long)B * Tmax;
-  {  // one projection over all B * Tmax rows
+  if (!ss) {  // one projection over all B * Tmax rows
     GemmDesc g;
     g.A = st->hout; g.lda = H; g.B = S->wout; g.ldb = H; g.C = logits_ws; g.ldc = V;
     g.M = (int)rows; g.N = V; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = P->b_out;
@@ -116,6 +134,38 @@ int gic_attn_forward_tf(const gic_attn_dims* dims, const gic_attn_params* P, con
                                 h_n, c_n, (hipStream_t)stream);
   return attn_tf_fwd_t<bf16_t>(c, P, S, st, features, fmap, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, out, alphas,
                                h_n, c_n, (hipStream_t)stream);
+}
+
+int gic_attn_forward_ss_ws_bytes(const gic_attn_dims* dims, int Tmax, uint64_t* out) {
+  ACtx c;
+  GIC_PROPAGATE(check_attn_dims(dims, c));
+  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "attn_forward_ss_ws_bytes: Tmax must be in 1..L (= caption length + 1)");
+  GIC_CHECK_ARG(out, "attn_forward_ss_ws_bytes: null out");
+  *out = ((uint64_t)c.B * Tmax * c.V + (uint64_t)c.B * c.P) * sizeof(float);       // the f32 logits [B, Tmax, V], then the energies [B, P]
+  return GIC_OK;
+}
+
+int gic_attn_forward_ss(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st,
+                        const float* features, const void* fmap, const int64_t* caps, const int32_t* lengths, int Tmax,
+                        const gic_sched_sample_opts* opts, void* ws, void* out, float* alphas, float* h_n, float* c_n, void* stream) {
+  ACtx c;
+  if (det_mode()) {
+    set_last_error("attn_forward_ss: the attention decoder is not available in the deterministic mode (gic_set_deterministic)");
+    return GIC_STATUS_UNSUPPORTED;
+  }
+  GIC_PROPAGATE(check_attn_dims(dims, c));
+  GIC_CHECK_ARG(P && S && st && features && fmap && lengths && opts && ws && out && h_n && c_n, "attn_forward_ss: null argument");
+  GIC_CHECK_ARG(c.L == 1 || caps, "attn_forward_ss: caps is null");
+  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "attn_forward_ss: Tmax must be in 1..L (= caption length + 1)");
+  GIC_PROPAGATE(ss_check_opts(opts, c.L, "attn_forward_ss"));
+  GIC_CHECK_ARG(((uintptr_t)ws & 15) == 0, "attn_forward_ss: ws must be 16-byte aligned");
+  GIC_CHECK_ARG(P->embed && P->b_out && P->b_f && P->w_a && S->wcat && S->bsum && S->wout && S->wf && S->wh, "attn_forward_ss: null weights");
+  GIC_CHECK_ARG(st->xh && st->gates && st->c && st->hout && st->fproj && st->alpha && st->hproj, "attn_forward_ss: null state buffer");
+  if (c.dt == DT_F32)
+    return attn_tf_fwd_t<float>(c, P, S, st, features, fmap, caps, lengths, Tmax, nullptr, 0, 1.f, 1, (float*)ws, out, alphas, h_n, c_n,
+                                (hipStream_t)stream, opts);
+  return attn_tf_fwd_t<bf16_t>(c, P, S, st, features, fmap, caps, lengths, Tmax, nullptr, 0, 1.f, 1, (float*)ws, out, alphas, h_n, c_n,
+                               (hipStream_t)stream, opts);
 }
 
 int gic_attn_forward_tf_bwd(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st,

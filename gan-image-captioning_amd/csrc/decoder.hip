@@ -928,7 +928,8 @@ namespace {
 template <typename TA>
 int forward_tf_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
                  const float* features, const int64_t* caps, const int32_t* lengths, int Tmax, const float* noise_u, uint64_t seed,
-                 float temperature, int pretrain, float* logits_ws, void* out, float* h_n, float* c_n, hipStream_t stream) {
+                 float temperature, int pretrain, float* logits_ws, void* out, float* h_n, float* c_n, hipStream_t stream,
+                 const gic_sched_sample_opts* ss = nullptr) {
   const int B = c.B, T = c.L, V = c.V, E = c.E, H = c.H, NL = c.NL;
   const int pw_grid = cdiv((long)B * H, 256);
   for (int l = 0; l < NL; ++l) {
@@ -937,6 +938,10 @@ int forward_tf_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
   }
   GIC_PROPAGATE(cast2d(features, DT_F32, E, st->xh[0], c.dt, c.ldx(0), B, E, stream));
   GIC_PROPAGATE(embed_rows_tf(c.dt, P->embed, caps, st->xh[0], c.ldx(0), B, T - 1, E, V, stream));
+  // scheduled sampling (gic_decoder_forward_ss): the logits of step t are formed inside the loop and ss_pick decides the x rows of slot
+  // t + 1 from them; the rows it does not replace keep the teacher's embedding written above
+  const bool ss_fused = ss && ss_fused_logits(c.dt, B, V, E, H, NL);
+  if (ss) GIC_PROPAGATE(ss_tail(caps, ss->inputs, ss->replaced, B, T - 1, Tmax - 1, stream));
   for (int t = 0; t < Tmax; ++t) {
     for (int l = 0; l < NL; ++l) {
       const long ld = c.ldx(l);
@@ -945,6 +950,7 @@ int forward_tf_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
       GemmDesc g;
       g.A = xh_t; g.lda = ld; g.B = S->wcat[l]; g.ldb = ld; g.C = st->gpre; g.ldc = 4 * H;
       g.M = B; g.N = 4 * H; g.K = (int)ld; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = S->bsum[l];
+      g.no_split = ss != nullptr;          // the picks are discrete: the same inputs must give the same bits
       GIC_PROPAGATE(gemm(g, stream));
       TA* h_up = (l + 1 < NL) ? (TA*)st->xh[l + 1] + (long)t * B * c.ldx(l + 1) : nullptr;
       TA* h_out = (l + 1 == NL) ? (TA*)st->hout + (long)t * H : nullptr;            // hout viewed as [B, Tmax, H]
@@ -954,10 +960,22 @@ int forward_tf_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
                          lengths, t, B, H, st->gates[l] ? st->gates[l] + (long)t * B * 4 * H : nullptr);
       GIC_CHECK_LAUNCH("lstm_pointwise_tf");
     }
+    if (ss) {
+      GIC_PROPAGATE(ss_step_logits(c.dt, st->hout, t, Tmax, S->wout, P->b_out, logits_ws, B, V, H, ss_fused, stream));
+      if (t + 1 < Tmax) {
+        SsPickArgs a;
+        a.logits = logits_ws + (long)t * V; a.ld_logits = (long)Tmax * V;
+        a.caps = caps; a.lengths = lengths; a.coin_u = ss->coin_u; a.noise_u = ss->noise_u; a.seed = ss->seed;
+        a.prob = ss->prob; a.pick = ss->pick; a.t = t + 1; a.B = B; a.V = V; a.E = E; a.Tm1 = T - 1;
+        a.embed = P->embed; a.x_next = (TA*)st->xh[0] + (long)(t + 1) * B * c.ldx(0); a.ld_x = c.ldx(0);
+        a.inputs = ss->inputs; a.replaced = ss->replaced;
+        GIC_PROPAGATE(ss_pick(a, c.dt, stream));
+      }
+    }
   }
   // one projection over all B*Tmax rows, then (adversarial mode) Gumbel + softmax per row; the draw u is [B, Tmax, V]
   const long rows = (long)B * Tmax;
-  {
+  if (!ss) {
     GemmDesc g;
     g.A = st->hout; g.lda = H; g.B = S->wout; g.ldb = H; g.C = logits_ws; g.ldc = V;
     g.M = (int)rows; g.N = V; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = P->b_out;
@@ -993,6 +1011,35 @@ int gic_decoder_forward_tf(const gic_decoder_dims* dims, const gic_decoder_param
                                (hipStream_t)stream);
   return forward_tf_t<bf16_t>(c, P, S, st, features, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, out, h_n, c_n,
                               (hipStream_t)stream);
+}
+
+int gic_decoder_forward_ss_ws_bytes(const gic_decoder_dims* dims, int Tmax, uint64_t* out) {
+  Ctx c;
+  GIC_PROPAGATE(check_dims(dims, c));
+  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "decoder_forward_ss_ws_bytes: Tmax must be in 1..L (= caption length + 1)");
+  GIC_CHECK_ARG(out, "decoder_forward_ss_ws_bytes: null out");
+  *out = (((uint64_t)c.B * Tmax * c.V * sizeof(float)) + 15) & ~(uint64_t)15;        // the f32 logits [B, Tmax, V]
+  return GIC_OK;
+}
+
+int gic_decoder_forward_ss(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
+                           const gic_decoder_state* st, const float* features, const int64_t* caps, const int32_t* lengths, int Tmax,
+                           const gic_sched_sample_opts* opts, void* ws, void* out, float* h_n, float* c_n, void* stream) {
+  Ctx c;
+  GIC_PROPAGATE(check_dims(dims, c));
+  GIC_CHECK_ARG(P && S && st && features && lengths && opts && ws && out && h_n && c_n, "decoder_forward_ss: null argument");
+  GIC_CHECK_ARG(c.L == 1 || caps, "decoder_forward_ss: caps is null");
+  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "decoder_forward_ss: Tmax must be in 1..L (= caption length + 1)");
+  GIC_PROPAGATE(ss_check_opts(opts, c.L, "decoder_forward_ss"));
+  GIC_CHECK_ARG(((uintptr_t)ws & 15) == 0, "decoder_forward_ss: ws must be 16-byte aligned");
+  GIC_CHECK_ARG(P->embed && P->b_out && S->wout && st->hout && st->gpre, "decoder_forward_ss: null buffer");
+  for (int l = 0; l < c.NL; ++l)
+    GIC_CHECK_ARG(st->xh[l] && st->c[l] && S->wcat[l] && S->bsum[l], "decoder_forward_ss: null layer %d buffer", l);
+  if (c.dt == DT_F32)
+    return forward_tf_t<float>(c, P, S, st, features, caps, lengths, Tmax, nullptr, 0, 1.f, 1, (float*)ws, out, h_n, c_n, (hipStream_t)stream,
+                               opts);
+  return forward_tf_t<bf16_t>(c, P, S, st, features, caps, lengths, Tmax, nullptr, 0, 1.f, 1, (float*)ws, out, h_n, c_n, (hipStream_t)stream,
+                              opts);
 }
 
 int gic_decoder_forward_tf_bwd(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,

@@ -3,6 +3,8 @@
 #include "common.h"
 #include "gemm.h"
 
+struct gic_sched_sample_opts;
+
 namespace gic {
 
 // dst[r*ldd + c] = cast(src[r*lds + c])
@@ -51,6 +53,33 @@ int zero_past_length(float* dhout, const int32_t* lengths, int B, int Tmax, int 
 int gumbel_softmax_rows(int dt, float* logits, const float* u, uint64_t seed, uint64_t rng_stream, float temperature, int pretrain, void* out,
                         long rows, int V, hipStream_t stream);
 int embed_scatter_time(const float* dx, long ld, const int64_t* ids, float* d_embed, int B, int L, int E, int V, hipStream_t stream, long ids_stride = 0);
+
+// sched_sample.hip: scheduled sampling inside the teacher-forced decodes (gic_decoder_forward_ss, gic_attn_forward_ss).
+//   ss_check_opts    the argument checks of gic_sched_sample_opts (`what` names the entry point in the message)
+//   ss_fused_logits  whether the per-step vocabulary product is vocab_step_logits (decoder_step_supported and the rows fit) or the GEMM
+//   ss_step_logits   logits[b, t, :] = hout[b, t, :] W_out^T + b_out in f32 for every caption b (hout act [B, Tmax, H], logits [B, Tmax, V])
+//   ss_pick          between steps t-1 and t: coin, pick and the pick's embedding row into x_next (= x of slot t), one launch
+//   ss_tail          inputs[:, from:] = caps[:, from:], replaced = 0 there (the positions no step is fed from)
+struct SsPickArgs {
+  const float* logits = nullptr; long ld_logits = 0;    // f32 logits of step t-1: row b at logits + b * ld_logits
+  const int64_t* caps = nullptr;                        // [B, Tm1]
+  const int32_t* lengths = nullptr;                     // [B]
+  const float* coin_u = nullptr;                        // [B, Tm1] or null -> Philox(seed)
+  const float* noise_u = nullptr;                       // [Tm1, B, V] or null -> Philox(seed); unread when pick != 0
+  uint64_t seed = 0;
+  float prob = 0.f; int pick = 0;                       // 0 = sample (Gumbel-max), 1 = argmax
+  int t = 0;                                            // the step whose input is decided, 1..Tm1
+  int B = 0, V = 0, E = 0, Tm1 = 0;
+  const float* embed = nullptr;                         // f32 [V, E]
+  void* x_next = nullptr; long ld_x = 0;                // act rows of slot t: columns [0, E) of row b receive embed[pick]
+  int64_t* inputs = nullptr; int32_t* replaced = nullptr;   // [B, Tm1]; replaced may be null
+};
+int ss_check_opts(const gic_sched_sample_opts* o, int L, const char* what);
+bool ss_fused_logits(int dt, int B, int V, int E, int H, int NL);
+int ss_step_logits(int dt, const void* hout, int t, int Tmax, const void* wout, const float* b_out, float* logits, int B, int V, int H,
+                   bool fused, hipStream_t stream);
+int ss_pick(const SsPickArgs& a, int dt, hipStream_t stream);
+int ss_tail(const int64_t* caps, int64_t* inputs, int32_t* replaced, int B, int Tm1, int from, hipStream_t stream);
 
 // disc_cond.hip: the conditioned discriminator's match-term backward for disc_bwd_t (disc.hip): dydrop[m, :] = scale g[m] q[m / R, :]
 // (f32 [B*R, Fp], pad columns zero) and, when d_q is not null, d_q[b, :] = scale sum_r g[b R + r] ydrop[b R + r, :F] (f32 [B, F])

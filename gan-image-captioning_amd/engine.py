@@ -502,6 +502,33 @@ def _tf_lengths(lengths, B: int, T: int, tmax: Optional[int]):
     return max(lens), torch.tensor(lens, dtype=torch.int32)
 
 
+SS_PICKS = ("sample", "argmax")     # gic_sched_sample_opts.pick
+
+
+def _ss_opts(prob: float, pick: str, coin_u, noise_u, seed: int, B: int, Lc: int, V: int, dev):
+    """(gic_sched_sample_opts, inputs int64 [B, L], replaced int32 [B, L], the tensors the struct points into) of a scheduled-sampling
+    decode: ``coin_u`` f32 [B, L] and ``noise_u`` f32 [L, B, V] replace the device draws."""
+    prob = float(prob)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"sample_prob must be in [0, 1], got {prob}")
+    if pick not in SS_PICKS:
+        raise ValueError(f"pick must be one of {SS_PICKS}, got {pick!r}")
+    if coin_u is not None:
+        if tuple(coin_u.shape) != (B, Lc):
+            raise ValueError(f"coin_u must be [B, L] = [{B}, {Lc}]")
+        coin_u = coin_u.contiguous().float()
+    if noise_u is not None:
+        if tuple(noise_u.shape) != (Lc, B, V):
+            raise ValueError(f"noise_u must be [L, B, V] = [{Lc}, {B}, {V}]")
+        noise_u = noise_u.contiguous().float()
+    inputs = torch.empty(B, Lc, device=dev, dtype=torch.int64)
+    replaced = torch.empty(B, Lc, device=dev, dtype=torch.int32)
+    o = L.SchedSampleOpts()
+    o.prob, o.pick, o.coin_u, o.noise_u, o.seed = prob, SS_PICKS.index(pick), ptr(coin_u), ptr(noise_u), int(seed) & (2 ** 64 - 1)
+    o.inputs, o.replaced = ptr(inputs), ptr(replaced)
+    return o, inputs, replaced, (coin_u, noise_u)
+
+
 def cider_d(cand_ids: torch.Tensor, cand_len: torch.Tensor, cand_img: torch.Tensor, ref_ids: torch.Tensor, ref_len: torch.Tensor,
             ref_off: torch.Tensor, max_refs: int, keys: torch.Tensor, idf: torch.Tensor, log_n: float, V: int) -> torch.Tensor:
     """gic_cider_d: CIDEr-D f32 [n_cand] of candidates int64 [n_cand, Lc] (cand_len / cand_img int32 [n_cand]) against the references
@@ -797,6 +824,39 @@ class DecoderEngine(_CaptionDecodes):
         if keep_state:
             return out, (h_n, c_n), {"st": st, "caps": caps.contiguous(), "len_dev": len_dev, "Tmax": Tmax, "T": T}
         return out, (h_n, c_n)
+
+    def forward_scheduled(self, params, features: torch.Tensor, caps: torch.Tensor, lengths, sample_prob: float, pick: str = "sample",
+                          coin_u: Optional[torch.Tensor] = None, noise_u: Optional[torch.Tensor] = None, seed: int = 0,
+                          tmax: Optional[int] = None):
+        """gic_decoder_forward_ss: ``forward_tf(pretrain=True, keep_state=True)`` with scheduled sampling -- the input of step t >= 1 is
+        the model's own pick from step t-1's logits where coin < ``sample_prob`` (and t < lengths[b]), else caps[:, t-1].  Returns
+        (pred, (h_n, c_n), saved, inputs int64 [B, L], replaced int32 [B, L]); ``saved`` carries ``inputs`` as its captions, so
+        ``forward_tf_bwd`` runs on it unchanged.  ``coin_u`` f32 [B, L] / ``noise_u`` f32 [L, B, V] replace the device draws."""
+        self.check_params(params)
+        require_gpu(features, caps, coin_u, noise_u)
+        B, Lc = caps.shape
+        T = Lc + 1
+        Tmax, len_dev = _tf_lengths(lengths, B, T, tmax)
+        dev = features.device
+        if features.shape != (B, self.E) or caps.dtype != torch.int64:
+            raise ValueError("features must be [B, E] and caps int64 [B, L]")
+        o, inputs, replaced, keep = _ss_opts(sample_prob, pick, coin_u, noise_u, seed, B, Lc, self.V, dev)
+        self.prepare(params)
+        st = self.alloc_state(B, T, dev)
+        out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
+        h_n = torch.empty(self.NL, B, self.H, device=dev, dtype=torch.float32)
+        c_n = torch.empty_like(h_n)
+        d = self.dims(B, T)
+        nbytes = C.c_uint64(0)
+        L.check(L.load().gic_decoder_forward_ss_ws_bytes(C.byref(d), Tmax, C.byref(nbytes)), "gic_decoder_forward_ss_ws_bytes")
+        ws = torch.empty(max(int(nbytes.value) // 4, 1), device=dev, dtype=torch.float32)
+        len_dev = len_dev.to(dev)
+        L.check(L.load().gic_decoder_forward_ss(
+            C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
+            ptr(features.contiguous().float()), ptr(caps.contiguous()), ptr(len_dev), Tmax, C.byref(o), ptr(ws), ptr(out), ptr(h_n),
+            ptr(c_n), stream_ptr()), "gic_decoder_forward_ss")
+        del keep
+        return out, (h_n, c_n), {"st": st, "caps": inputs, "len_dev": len_dev, "Tmax": Tmax, "T": T}, inputs, replaced
 
     def forward_tf_bwd(self, params, saved, pred: torch.Tensor, d_pred: torch.Tensor, temperature: float, pretrain: bool = False,
                        ws=None, grads=None) -> List[torch.Tensor]:
@@ -1479,6 +1539,40 @@ class AttnDecoderEngine(_CaptionDecodes):
             st["fmap"] = fmap
             return out, (h_n, c_n), alphas, {"st": st, "caps": caps, "len_dev": len_dev, "Tmax": Tmax, "T": T}
         return out, (h_n, c_n), alphas
+
+    def forward_scheduled(self, params, features, fmap, caps: torch.Tensor, lengths, sample_prob: float, pick: str = "sample",
+                          coin_u: Optional[torch.Tensor] = None, noise_u: Optional[torch.Tensor] = None, seed: int = 0,
+                          tmax: Optional[int] = None):
+        """gic_attn_forward_ss: ``forward_tf(pretrain=True, want_alphas=True, keep_state=True)`` with scheduled sampling
+        (DecoderEngine.forward_scheduled).  Returns (pred, (h_n, c_n), alphas, saved, inputs, replaced)."""
+        self.check_params(params)
+        require_gpu(features, fmap, caps, coin_u, noise_u)
+        B, Lc = caps.shape
+        T = Lc + 1
+        Tmax, len_dev = _tf_lengths(lengths, B, T, tmax)
+        if tuple(features.shape) != (B, self.E) or features.dtype != torch.float32 or caps.dtype != torch.int64:
+            raise ValueError(f"features must be float32 [B, {self.E}] and caps int64 [B, L]")
+        fmap = self._act_fmap(fmap, B)
+        dev = features.device
+        o, inputs, replaced, keep = _ss_opts(sample_prob, pick, coin_u, noise_u, seed, B, Lc, self.V, dev)
+        self.prepare(params)
+        st = self.alloc_state(B, T, dev)
+        out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
+        h_n = torch.empty(1, B, self.H, device=dev, dtype=torch.float32)
+        c_n = torch.empty_like(h_n)
+        alphas = torch.empty(B, Tmax, self.P, device=dev, dtype=torch.float32)
+        d = self.dims(B, T)
+        nbytes = C.c_uint64(0)
+        L.check(L.load().gic_attn_forward_ss_ws_bytes(C.byref(d), Tmax, C.byref(nbytes)), "gic_attn_forward_ss_ws_bytes")
+        ws = torch.empty(int(nbytes.value) // 4, device=dev, dtype=torch.float32)
+        len_dev = len_dev.to(dev)
+        L.check(L.load().gic_attn_forward_ss(
+            C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
+            ptr(features.contiguous()), ptr(fmap), ptr(caps.contiguous()), ptr(len_dev), Tmax, C.byref(o), ptr(ws), ptr(out), ptr(alphas),
+            ptr(h_n), ptr(c_n), stream_ptr()), "gic_attn_forward_ss")
+        del keep
+        st["fmap"] = fmap
+        return out, (h_n, c_n), alphas, {"st": st, "caps": inputs, "len_dev": len_dev, "Tmax": Tmax, "T": T}, inputs, replaced
 
     def forward_tf_bwd(self, params, saved, pred: torch.Tensor, d_pred: Optional[torch.Tensor], temperature: float, pretrain: bool = False,
                        d_alphas: Optional[torch.Tensor] = None, ws=None, grads=None) -> List[torch.Tensor]:

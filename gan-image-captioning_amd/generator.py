@@ -150,6 +150,44 @@ class _ForwardTfFn(torch.autograd.Function):
         return (None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
 
 
+class _ForwardSsFn(torch.autograd.Function):
+    """Decoder.forward_scheduled with autograd: gic_decoder_forward_ss, then gic_decoder_forward_tf_bwd over the inputs it realised."""
+
+    @staticmethod
+    def forward(ctx, eng, sample_prob, pick, caps, lengths, coin_u, noise_u, seed, tmax, features, *params):
+        dparams = [p.detach() for p in params]
+        pred, (h_n, c_n), saved, inputs, replaced = eng.forward_scheduled(dparams, features.detach().float(), caps, lengths, sample_prob,
+                                                                           pick, coin_u, noise_u, seed, tmax=tmax)
+        ctx.eng, ctx.saved, ctx.dparams = eng, saved, dparams
+        ctx.save_for_backward(pred)
+        ctx.mark_non_differentiable(h_n, c_n, inputs, replaced)
+        return pred, h_n, c_n, inputs, replaced
+
+    @staticmethod
+    def backward(ctx, d_pred, _d_h, _d_c, _d_in, _d_rep):
+        (pred,) = ctx.saved_tensors
+        grads = ctx.eng.forward_tf_bwd(ctx.dparams, ctx.saved, pred, d_pred, 1.0, True)
+        ctx.saved = None
+        return (None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
+
+
+def _ss_args(sample_prob, pick, coin_u, noise_u, seed):
+    """(p, seed) of a forward_scheduled call, checked: ``seed`` None = the next of SEEDS (0 with both draws given)."""
+    p = float(sample_prob)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"sample_prob must be in [0, 1], got {sample_prob}")
+    if pick not in engine.SS_PICKS:
+        raise ValueError(f"pick must be one of {engine.SS_PICKS}, got {pick!r}")
+    if seed is None:
+        seed = 0 if (coin_u is not None and (noise_u is not None or pick == "argmax")) or p == 0.0 else SEEDS.next()
+    return p, int(seed)
+
+
+def _teacher_inputs(caps, vocab: int):
+    """(inputs, replaced) of a decode that replaced nothing: the clamped captions (embed_rows_tf's clamp) and zeros."""
+    return caps.clamp(0, vocab - 1), torch.zeros(caps.shape, dtype=torch.int32, device=caps.device)
+
+
 def _beam_search(dec, features, maps, beam_size, max_caption_len, eos_id, length_penalty, states, return_beams, beam_groups, diversity, **kw):
     """Decoder.beam_search / AttnDecoder.beam_search: ``maps`` = () or (fmap,), ``kw`` = the engine's further keywords (the decode
     constraints, want_alphas).  One group without diversity is the plain search."""
@@ -227,6 +265,30 @@ class Decoder(nn.Module):
                                             max_length, features, *params)
         return pred, (h_n, c_n)
 
+    def forward_scheduled(self, features, caps, lengths, sample_prob, pick="sample", coin_u=None, noise_u=None, seed=None, max_length=None,
+                          return_inputs=False):
+        """``forward(features, caps, lengths, pretrain=True)`` with scheduled sampling (Bengio et al., 2015; gicap.h
+        gic_decoder_forward_ss): the input of step t >= 1 is caps[:, t-1] with probability 1 - ``sample_prob``, else a token the decoder
+        picks from its own logits of step t-1 -- ``pick`` = "sample" (a draw from softmax(logits), by Gumbel-max) or "argmax"; positions
+        past a caption's length are never replaced.  Returns (pred = logits [B, max(lengths), V], (h_n, c_n)); ``return_inputs`` appends
+        (inputs int64 [B, L], replaced int32 [B, L]), the inputs the decode realised.  Gradients flow as in ``forward`` over those
+        inputs; none flows through the choice.  ``coin_u`` f32 [B, L] and ``noise_u`` f32 [L, B, V] replace the device draws
+        (Philox(``seed``); None = the next of SEEDS).  ``sample_prob`` = 0 is ``forward`` itself: nothing else is launched."""
+        p, seed = _ss_args(sample_prob, pick, coin_u, noise_u, seed)
+        if p == 0.0:
+            pred, hc = self.forward(features, caps, lengths, pretrain=True, max_length=max_length)
+            return (pred, hc, _teacher_inputs(caps, self.args.vocab_size)) if return_inputs else (pred, hc)
+        params = self.param_list()
+        if not torch.is_grad_enabled() or not (features.requires_grad or any(q.requires_grad for q in params)):
+            with torch.no_grad():
+                pred, hc, _, inputs, replaced = self.engine().forward_scheduled([q.detach() for q in params], features.detach().float(), caps,
+                                                                               lengths, p, pick, coin_u, noise_u, seed, tmax=max_length)
+        else:
+            pred, h_n, c_n, inputs, replaced = _ForwardSsFn.apply(self.engine(), p, pick, caps, lengths, coin_u, noise_u, seed, max_length,
+                                                                  features, *params)
+            hc = (h_n, c_n)
+        return (pred, hc, (inputs, replaced)) if return_inputs else (pred, hc)
+
     def beam_search(self, features, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None, return_beams=False,
                     beam_groups=1, diversity=0.0, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """Beam-search caption decode (gicap.h gic_decoder_beam_search): token log-probabilities of sample(pretrain=True)'s
@@ -300,6 +362,29 @@ class _AttnForwardTfFn(torch.autograd.Function):
         grads = ctx.eng.forward_tf_bwd(ctx.dparams, ctx.saved, pred, d_pred, ctx.temperature, ctx.pretrain, d_alphas=d_alphas)
         ctx.saved = None
         return (None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
+
+
+class _AttnForwardSsFn(torch.autograd.Function):
+    """AttnDecoder.forward_scheduled with autograd: gic_attn_forward_ss, then gic_attn_forward_tf_bwd over the inputs it realised."""
+
+    @staticmethod
+    def forward(ctx, eng, sample_prob, pick, caps, lengths, coin_u, noise_u, seed, tmax, fmap, features, *params):
+        dparams = [p.detach() for p in params]
+        pred, (h_n, c_n), alphas, saved, inputs, replaced = eng.forward_scheduled(dparams, features.detach().float(), fmap.detach(), caps,
+                                                                                   lengths, sample_prob, pick, coin_u, noise_u, seed,
+                                                                                   tmax=tmax)
+        ctx.eng, ctx.saved, ctx.dparams = eng, saved, dparams
+        ctx.save_for_backward(pred)
+        ctx.mark_non_differentiable(h_n, c_n, inputs, replaced)
+        ctx.set_materialize_grads(False)
+        return pred, h_n, c_n, alphas, inputs, replaced
+
+    @staticmethod
+    def backward(ctx, d_pred, _d_h, _d_c, d_alphas, _d_in, _d_rep):
+        (pred,) = ctx.saved_tensors
+        grads = ctx.eng.forward_tf_bwd(ctx.dparams, ctx.saved, pred, d_pred, 1.0, True, d_alphas=d_alphas)
+        ctx.saved = None
+        return (None, None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
 
 
 class _AttnParams(nn.Module):
@@ -400,6 +485,30 @@ class AttnDecoder(nn.Module):
         if return_alphas:
             return pred, hc, alphas
         return pred, hc
+
+    def forward_scheduled(self, features, fmap, caps, lengths, sample_prob, pick="sample", coin_u=None, noise_u=None, seed=None,
+                          max_length=None, return_alphas=False, return_inputs=False):
+        """``forward(features, fmap, caps, lengths, pretrain=True)`` with scheduled sampling (Decoder.forward_scheduled; gicap.h
+        gic_attn_forward_ss).  Returns (pred, (h_n, c_n)); ``return_alphas`` appends the attention weights (differentiable, as in
+        ``forward``), ``return_inputs`` then (inputs, replaced).  ``sample_prob`` = 0 is ``forward`` itself."""
+        if fmap is None:
+            raise ValueError("the attention decoder needs the trunk's feature map: forward_scheduled(features, fmap, caps, lengths, p)")
+        p, seed = _ss_args(sample_prob, pick, coin_u, noise_u, seed)
+        if p == 0.0:
+            pred, hc, alphas = self.forward(features, fmap, caps, lengths, pretrain=True, return_alphas=True, max_length=max_length)
+            inputs, replaced = _teacher_inputs(caps, self.args.vocab_size) if return_inputs else (None, None)
+        else:
+            params = self.param_list()
+            if not torch.is_grad_enabled() or not (features.requires_grad or any(q.requires_grad for q in params)):
+                with torch.no_grad():
+                    pred, hc, alphas, _, inputs, replaced = self.engine().forward_scheduled(
+                        [q.detach() for q in params], features.detach().float(), fmap.detach(), caps, lengths, p, pick, coin_u, noise_u, seed,
+                        tmax=max_length)
+            else:
+                pred, h_n, c_n, alphas, inputs, replaced = _AttnForwardSsFn.apply(self.engine(), p, pick, caps, lengths, coin_u, noise_u, seed,
+                                                                                  max_length, fmap, features, *params)
+                hc = (h_n, c_n)
+        return (pred, hc) + ((alphas,) if return_alphas else ()) + (((inputs, replaced),) if return_inputs else ())
 
     def monte_carlo_rollouts(self, features, fmap, captions, num_rollouts, noise_u=None, seed=None):
         """Monte-Carlo roll-outs of ``captions`` int64 [B, L] (gicap.h gic_attn_rollout), for a reward of the caller's own: for every

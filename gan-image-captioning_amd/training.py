@@ -101,10 +101,33 @@ def check_modes(args):
     return pretrain_mode, attn_reg
 
 
+def check_scheduled_sampling(args):
+    """The instructor's checks of the scheduled-sampling flags, before anything touches the device: (prob, ramp_epochs, pick)."""
+    p = float(getattr(args, "scheduled_sampling_prob", 0.0))
+    n = int(getattr(args, "scheduled_sampling_ramp_epochs", 0))
+    pick = getattr(args, "scheduled_sampling_pick", "sample")
+    if not 0.0 <= p <= 1.0:                       # false for NaN too
+        raise ValueError(f"--scheduled-sampling-prob must be in [0, 1], got {p}")
+    if n < 0:
+        raise ValueError(f"--scheduled-sampling-ramp-epochs must be >= 0, got {n}")
+    if pick not in ("sample", "argmax"):
+        raise ValueError(f"--scheduled-sampling-pick must be sample or argmax, got {pick!r}")
+    if p > 0.0 and getattr(args, "pretrain_mode", "sample") != "teacher":
+        raise ValueError("--scheduled-sampling-prob mixes the decoder's own tokens into teacher forcing: it needs --pretrain-mode teacher")
+    return p, n, pick
+
+
+def scheduled_sampling_prob(p: float, ramp_epochs: int, epoch: int) -> float:
+    """p_e = p * min(1, e / n) of epoch e (0-based); n = 0: p throughout."""
+    return p if ramp_epochs <= 0 else p * min(1.0, epoch / ramp_epochs)
+
+
 class GANInstructor:
     def __init__(self, args, train_dataset, dev_dataset):
         self.args = args
         self.pretrain_mode, self.attn_reg = check_modes(args)
+        self.ss_prob, self.ss_ramp, self.ss_pick = check_scheduled_sampling(args)
+        self.ss_prob_now = scheduled_sampling_prob(self.ss_prob, self.ss_ramp, 0)      # pretrain_generator sets it per epoch
         self.dist = parallel.DistInfo.from_env()
         from .generator import SEEDS
         SEEDS.rank = self.dist.rank            # replicas share weights and the torch seed, not the device noise streams
@@ -208,11 +231,20 @@ class GANInstructor:
 
     def _pretrain_step_teacher(self, feats, captions, lengths, train):
         """--pretrain-mode teacher: pred = decoder.forward(features[, fmap], captions[:, :-1], lengths, pretrain=True), the same
-        cross entropy against captions as the free-running step; with --attn-reg lam, + lam * mean_b sum_i (1 - sum_t alpha_bti)^2."""
+        cross entropy against captions as the free-running step; with --attn-reg lam, + lam * mean_b sum_i (1 - sum_t alpha_bti)^2.
+        With --scheduled-sampling-prob, a training step decodes through decoder.forward_scheduled at this epoch's probability."""
         if lengths is None:
             lengths = torch.full((captions.shape[0],), captions.shape[1], dtype=torch.int32)
         caps = captions[:, :-1]
-        if self.attention:
+        p = self.ss_prob_now if train else 0.0        # only training batches are mixed: the validation loss stays comparable
+        if p > 0.0:
+            if self.attention:
+                pred, _, alphas = self.gen.decoder.forward_scheduled(feats[0], feats[1], caps, lengths, p, pick=self.ss_pick,
+                                                                     return_alphas=True)
+            else:
+                pred, _ = self.gen.decoder.forward_scheduled(feats, caps, lengths, p, pick=self.ss_pick)
+                alphas = None
+        elif self.attention:
             pred, _, alphas = self.gen.decoder(feats[0], feats[1], caps, lengths, pretrain=True, return_alphas=True)
         else:
             pred, _ = self.gen.decoder(feats, caps, lengths, pretrain=True)
@@ -251,6 +283,10 @@ class GANInstructor:
         self.log.info("Pretraining Generator")
         total_loss, best_loss = 0, None
         for epoch in range(self.args.pretrain_epochs):
+            if self.ss_prob > 0.0:
+                self.ss_prob_now = scheduled_sampling_prob(self.ss_prob, self.ss_ramp, epoch)
+                self.log.info("Epoch {}: scheduled sampling probability {}".format(epoch, self.ss_prob_now))
+                self.writer.add_scalar("GenPreTraining_sched_prob", self.ss_prob_now, self.pretrain_steps)
             self.gen.train()
             train_epoch_loss = np.mean(self.genpretrain_loop("train"))
             total_loss += train_epoch_loss

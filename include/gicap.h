@@ -259,6 +259,38 @@ int gic_decoder_forward_tf_bwd(const gic_decoder_dims* dims, const gic_decoder_p
                                const int32_t* lengths, int Tmax, const void* d_pred, float temperature, int pretrain,
                                const gic_decoder_grads* grads, void* stream);
 
+/* Scheduled sampling (Bengio et al., 2015) inside the teacher-forced decode, for MLE pre-training: gic_decoder_forward_tf with
+ * pretrain != 0, except that the input of step t = 1..Tmax-1 of caption b is decided after step t-1:
+ *   replaced[b, t-1] = coin[b, t-1] < prob and t < lengths[b]
+ *   inputs[b, t-1]   = replaced ? m[b, t-1] : clamp(caps[b, t-1], 0, V-1)
+ *   m[b, t-1]        = argmax_v l[v] + g(u[t-1, b, v])   (pick 0; g(u) = -log(-log(u + 1e-10) + 1e-10))
+ *                    = argmax_v l[v]                      (pick 1)
+ * with l the f32 logits of step t-1 (bias included, before any rounding to the compute dtype); ties go to the lower id, a row with
+ * NaN logits picks some id in [0, V).  Step t is fed embed(inputs[b, t-1]); positions >= Tmax-1 of inputs are copies of caps and
+ * never count as replaced.  coin_u: f32 [B, T-1]; noise_u: f32 [T-1, B, V] (unread with pick 1); either NULL: Philox keyed by
+ * (seed, a stream tag of its own, t, b) -- a caption's draws do not depend on B.  The comparison coin < prob is made in f32.
+ * out: act [B, Tmax, V] raw logits; h_n / c_n as gic_decoder_forward_tf.  ws: scratch of gic_decoder_forward_ss_ws_bytes bytes, 16-byte
+ * aligned.  state: as for gic_decoder_forward_tf (state->gpre, and state->gates[k] for a backward pass).  The vocabulary product of
+ * a step runs inside the loop (the fused step kernels' logits epilogue where gic_decoder_fused_rollout_rows admits B, else the
+ * library GEMM); one launch per step (ss_pick) tosses the coin, picks and writes the pick's embedding row into the next step's
+ * input.  Backward: gic_decoder_forward_tf_bwd, unchanged, with `inputs` where it takes caps -- no gradient flows through the
+ * choice.  Any V, NL in 1..GIC_MAX_LAYERS.  Argument errors (NULL required pointers, prob outside [0, 1] or NaN, pick not 0 / 1, Tmax
+ * outside 1..L) return GIC_STATUS_INVALID_ARG before any launch.  No f32 atomics and no split-K: the same inputs give the same bits,
+ * in and out of the deterministic mode. */
+typedef struct gic_sched_sample_opts {
+  float prob;                            /* p in [0, 1] */
+  int32_t pick;                          /* 0 = sample, 1 = argmax */
+  const float* coin_u;                   /* f32 [B, T-1] or NULL */
+  const float* noise_u;                  /* f32 [T-1, B, V] or NULL */
+  uint64_t seed;                         /* Philox seed of whichever of the two is NULL */
+  int64_t* inputs;                       /* out, int64 [B, T-1], required (may be NULL when T = 1): the inputs the decode realised */
+  int32_t* replaced;                     /* out, int32 [B, T-1] (0 / 1) or NULL */
+} gic_sched_sample_opts;
+int gic_decoder_forward_ss_ws_bytes(const gic_decoder_dims* dims, int Tmax, uint64_t* out);      /* host-only: no GPU needed */
+int gic_decoder_forward_ss(const gic_decoder_dims* dims, const gic_decoder_params* params, const gic_decoder_shadow* shadow,
+                           const gic_decoder_state* state, const float* features, const int64_t* caps, const int32_t* lengths,
+                           int Tmax, const gic_sched_sample_opts* opts, void* ws, void* out, float* h_n, float* c_n, void* stream);
+
 /* d_out: act [B,L,V] gradient w.r.t. `out`; probs = the forward's `out`.
  * phases (bit mask; GIC_DECODER_BWD_ALL = both, in this order):
  *   GIC_DECODER_BWD_OUTPUT     softmax/Gumbel backward, d_hout, and the COMPLETE gradients of the vocabulary projection
@@ -529,6 +561,16 @@ int gic_attn_forward_tf_bwd(const gic_attn_dims* dims, const gic_attn_params* pa
                             const gic_attn_state* state, const gic_attn_bwd_ws* ws, const void* fmap, const void* pred, const int64_t* caps,
                             const int32_t* lengths, int Tmax, const void* d_pred, const float* d_alphas, float temperature, int pretrain,
                             const gic_attn_grads* grads, void* stream);
+/* Scheduled sampling inside the attention decoder's teacher-forced decode: gic_decoder_forward_ss's definition with the step of
+ * gic_attn_forward_tf (pretrain != 0), alphas included.  ws: scratch of gic_attn_forward_ss_ws_bytes bytes (the logits of every step
+ * and the energies of one), 16-byte aligned.  Backward: gic_attn_forward_tf_bwd, unchanged, with `inputs` where it takes caps.
+ * Argument errors as gic_decoder_forward_ss, plus the dims gic_attn_* refuse.  GIC_STATUS_UNSUPPORTED in the deterministic mode, as
+ * gic_attn_sample_fwd. */
+int gic_attn_forward_ss_ws_bytes(const gic_attn_dims* dims, int Tmax, uint64_t* out);      /* host-only: no GPU needed */
+int gic_attn_forward_ss(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                        const gic_attn_state* state, const float* features, const void* fmap, const int64_t* caps, const int32_t* lengths,
+                        int Tmax, const gic_sched_sample_opts* opts, void* ws, void* out, float* alphas, float* h_n, float* c_n,
+                        void* stream);
 
 /* Monte-Carlo roll-outs of the attention decoder (the SeqGAN step's): the counterpart of gic_decoder_sample_fwd with force_ids,
  * force_len, no_state and resume_from.  dims->B = images, dims->L = caption length.  `rows` roll-out rows, row r of image r % B: it
