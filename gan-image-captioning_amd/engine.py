@@ -1503,11 +1503,11 @@ class AttnDecoderEngine(_CaptionDecodes):
 
     def forward_tf(self, params, features, fmap, caps: torch.Tensor, lengths, temperature: float, pretrain: bool = False,
                    noise_u: Optional[torch.Tensor] = None, seed: int = 0, want_alphas: bool = False, keep_state: bool = False,
-                   tmax: Optional[int] = None):
+                   tmax: Optional[int] = None, state=None):
         """gic_attn_forward_tf: the teacher-forced decode (DecoderEngine.forward_tf with the attention step).  ``caps`` int64 [B, T-1],
         ``lengths`` B values in 1..T, ``fmap`` [B, P, C] (cast to the compute dtype as in sample_fwd).  Returns (pred act [B, Tmax, V],
         (h_n, c_n) f32 [1, B, H], alphas f32 [B, Tmax, P] or None); with ``keep_state`` also what ``forward_tf_bwd`` needs.  ``tmax``
-        as DecoderEngine.forward_tf."""
+        as DecoderEngine.forward_tf.  ``state``: a caller-owned state (alloc_state(B, T, dev)) as in sample_fwd."""
         self.check_params(params)
         require_gpu(features, fmap, caps, noise_u)
         B, Lc = caps.shape
@@ -1522,7 +1522,7 @@ class AttnDecoderEngine(_CaptionDecodes):
         fmap = self._act_fmap(fmap, B)
         dev = features.device
         self.prepare(params)
-        st = self.alloc_state(B, T, dev)
+        st = dict(state) if state is not None else self.alloc_state(B, T, dev)
         out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
         h_n = torch.empty(1, B, self.H, device=dev, dtype=torch.float32)
         c_n = torch.empty_like(h_n)
@@ -1542,9 +1542,9 @@ class AttnDecoderEngine(_CaptionDecodes):
 
     def forward_scheduled(self, params, features, fmap, caps: torch.Tensor, lengths, sample_prob: float, pick: str = "sample",
                           coin_u: Optional[torch.Tensor] = None, noise_u: Optional[torch.Tensor] = None, seed: int = 0,
-                          tmax: Optional[int] = None):
+                          tmax: Optional[int] = None, state=None):
         """gic_attn_forward_ss: ``forward_tf(pretrain=True, want_alphas=True, keep_state=True)`` with scheduled sampling
-        (DecoderEngine.forward_scheduled).  Returns (pred, (h_n, c_n), alphas, saved, inputs, replaced)."""
+        (DecoderEngine.forward_scheduled).  Returns (pred, (h_n, c_n), alphas, saved, inputs, replaced).  ``state`` as forward_tf."""
         self.check_params(params)
         require_gpu(features, fmap, caps, coin_u, noise_u)
         B, Lc = caps.shape
@@ -1556,7 +1556,7 @@ class AttnDecoderEngine(_CaptionDecodes):
         dev = features.device
         o, inputs, replaced, keep = _ss_opts(sample_prob, pick, coin_u, noise_u, seed, B, Lc, self.V, dev)
         self.prepare(params)
-        st = self.alloc_state(B, T, dev)
+        st = dict(state) if state is not None else self.alloc_state(B, T, dev)
         out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
         h_n = torch.empty(1, B, self.H, device=dev, dtype=torch.float32)
         c_n = torch.empty_like(h_n)

@@ -382,6 +382,52 @@ def forced_mask(case, X, t):
     return t < X["force_len"].long()
 
 
+def cell_forward(emit, bf, a, W, bs, gates, c_prev, c_next, h_view, am=None, after_c=None):
+    """One cell step by the rules of the module docstring (shared with tests/attn_cases.py): the gates from the device's input row
+    a [B, ldx] (fp64; `am`: a mutated copy that forms the reference instead), c from the device's gates, h from the device's c.
+    emit(stage, view, ref, bound) compares or fills."""
+    H, ldx = c_prev.shape[1], a.shape[1]
+    lip = torch.cat([torch.full((H,), 0.25), torch.full((H,), 0.25), torch.ones(H), torch.full((H,), 0.25)]).double()
+    kk = torch.cat([torch.full((H,), K_SIG), torch.full((H,), K_SIG), torch.full((H,), K_TANH), torch.full((H,), K_SIG)]).double()
+    pre = (a if am is None else am) @ W.t() + bs
+    pb = sum_bound(ldx, a.abs() @ W.abs().t() + bs.abs(), None)
+    ref = torch.cat([torch.sigmoid(pre[:, :2 * H]), torch.tanh(pre[:, 2 * H:3 * H]), torch.sigmoid(pre[:, 3 * H:])], 1)
+    emit("gates", gates, ref, lip * pb + kk * U * ref.abs())
+    G = gates.double()
+    gi, gf, gg, go = G[:, :H], G[:, H:2 * H], G[:, 2 * H:3 * H], G[:, 3 * H:]
+    cp = c_prev.double()
+    emit("c", c_next, gf * cp + gi * gg, 3 * U * ((gf * cp).abs() + (gi * gg).abs()))
+    if after_c is not None:
+        after_c()
+    h_ref = go * torch.tanh(c_next.double())
+    emit("h", h_view, h_ref, (K_TANH + 2) * U * h_ref.abs() + (U8 * h_ref.abs() if bf else 0.0))
+
+
+def cell_backward(emit, bf, dh, dhb, gates, c_prev, c_cur, carry, dgates, carry_f=True):
+    """d_gates of one cell step from dh [B, H] and its bound dhb, the saved gates and cell states and the cell-gradient carry (its
+    fp64 value, its bound); returns the carry of the step before (shared with tests/attn_cases.py).  carry_f False: the `dc_no_f`
+    mutation."""
+    H = c_prev.shape[1]
+    G = gates.double()
+    gi, gf, gg, go = G[:, :H], G[:, H:2 * H], G[:, 2 * H:3 * H], G[:, 3 * H:]
+    cp, tc = c_prev.double(), torch.tanh(c_cur.double())
+    q = 1 - tc * tc
+    S, Sb = carry
+    term = dh * go * q
+    D = S + term
+    # tanhf errs by K_TANH u |tc|, so 1 - tc^2 by (2 K_TANH + 1) u tc^2 + u (1 + tc^2); two products; the sum
+    Eb = Sb + dhb * (go * q).abs() + U * (dh * go).abs() * ((2 * K_TANH + 2) * tc * tc + 1) + 2 * U * term.abs() + U * (S.abs() + term.abs())
+    # d_gate = dc (or dh) times a product of three factors, one of them 1 - x (terms before the cancellation: 1 + |x|): 4 u
+    parts = [(D, Eb, gg * gi * (1 - gi), gg.abs() * gi * (1 + gi)),
+             (D, Eb, cp * gf * (1 - gf), cp.abs() * gf * (1 + gf)),
+             (D, Eb, gi * (1 - gg * gg), gi * (1 + gg * gg)),
+             (dh, dhb, tc * go * (1 - go), tc.abs() * go * (1 + go) * (1 + K_TANH / 4))]
+    ref = torch.cat([v * f for v, _, f, _ in parts], 1)
+    bnd = torch.cat([e * f.abs() + 4 * U * v.abs() * m for v, e, f, m in parts], 1)
+    emit("dgates", dgates, ref, bnd + (U8 * ref.abs() if bf else 0.0))
+    return (D * gf, Eb * gf.abs() + U * (D * gf).abs()) if carry_f else (D, Eb)
+
+
 def run_forward(case, P, img, X, st, rep=None, mut=None, exact=False, near=None):
     """Walk the forward stages over `st` (new_state's keys).  rep: check; None: fill.  `mut`: a mutation of the fill.  exact: the tie
     regime (ids are the FIRST maximal index, bit for bit).  near: a list that receives (rows without a clear margin, rows)."""
@@ -408,34 +454,27 @@ def run_forward(case, P, img, X, st, rep=None, mut=None, exact=False, near=None)
     for l in range(NL):
         same("slot0", st["xh"][l][0][:, c.din(l):], X["h0"][l].to(td) if X["h0"] is not None else torch.zeros(B, H, dtype=td))
         same("slot0", st["c"][l][0], X["c0"][l] if X["c0"] is not None else torch.zeros(B, H))
-    lip = torch.cat([torch.full((H,), 0.25), torch.full((H,), 0.25), torch.ones(H), torch.full((H,), 0.25)]).double()
-    kk = torch.cat([torch.full((H,), K_SIG), torch.full((H,), K_SIG), torch.full((H,), K_TANH), torch.full((H,), K_SIG)]).double()
     unclear = 0
     for t in range(L):
         # 4. the cell, layer by layer, each link from the device's own buffers upstream of it
         for l in range(NL):
             din, ldx = c.din(l), c.ldx(l)
-            a, W, bs = st["xh"][l][t].double(), img["wcat"][l].double(), img["bsum"][l].double()
-            am = a
+            a = st["xh"][l][t].double()
+            am = None
             if l == 0 and mut == "k_tail_missing":
                 am = a.clone()
                 am[:, ldx - 8:] = 0
             if l == 0 and mut == "seam_swapped":
                 am = a.clone()
                 am[:, din - 8:din], am[:, din:din + 8] = a[:, din:din + 8], a[:, din - 8:din]
-            pre = am @ W.t() + bs
-            pb = sum_bound(ldx, a.abs() @ W.abs().t() + bs.abs(), None)
-            ref = torch.cat([torch.sigmoid(pre[:, :2 * H]), torch.tanh(pre[:, 2 * H:3 * H]), torch.sigmoid(pre[:, 3 * H:])], 1)
-            emit("gates", st["gates"][l][t], ref, lip * pb + kk * U * ref.abs())
-            G = st["gates"][l][t].double()
-            gi, gf, gg, go = G[:, :H], G[:, H:2 * H], G[:, 2 * H:3 * H], G[:, 3 * H:]
-            cp = st["c"][l][t].double()
-            emit("c", st["c"][l][t + 1], gf * cp + gi * gg, 3 * U * ((gf * cp).abs() + (gi * gg).abs()))
-            if mut == "row64_unwritten" and rep is None and B > 64 and l == NL - 1 and t == L - 1:
-                st["c"][l][t + 1][64] = float("nan")
-            h_ref = go * torch.tanh(st["c"][l][t + 1].double())
+
+            def after_c(l=l, t=t):
+                if mut == "row64_unwritten" and rep is None and B > 64 and l == NL - 1 and t == L - 1:
+                    st["c"][l][t + 1][64] = float("nan")
+
             hv = st["xh"][l][t + 1][:, din:]
-            emit("h", hv, h_ref, (K_TANH + 2) * U * h_ref.abs() + r(h_ref))
+            cell_forward(emit, bf, a, img["wcat"][l].double(), img["bsum"][l].double(), st["gates"][l][t], st["c"][l][t], st["c"][l][t + 1], hv,
+                         am=am, after_c=after_c)
             up = st["xh"][l + 1][t][:, :H] if l + 1 < NL else st["hout"][:, t]
             same("h copies", up, hv)
             if mut == "h_up_ulp" and rep is None and l + 1 < NL:
@@ -581,24 +620,8 @@ def run_backward(case, P, img, X, st, ws, grads, rep=None, mut=None, state_grads
                     nx, Wr = ws["dgates"][l][t + 1].double(), Wt[l][din:]
                     dh, mag, n = dh + nx @ Wr.t(), mag + nx.abs() @ Wr.abs().t(), n + 4 * H
                 dhb = (n + 4) * U * mag
-                G = st["gates"][l][t].double()
-                gi, gf, gg, go = G[:, :H], G[:, H:2 * H], G[:, 2 * H:3 * H], G[:, 3 * H:]
-                cp, tc = st["c"][l][t].double(), torch.tanh(st["c"][l][t + 1].double())
-                q = 1 - tc * tc
-                S, Sb = carry[l]
-                term = dh * go * q
-                D = S + term
-                # tanhf errs by K_TANH u |tc|, so 1 - tc^2 by (2 K_TANH + 1) u tc^2 + u (1 + tc^2); two products; the sum
-                Eb = Sb + dhb * (go * q).abs() + U * (dh * go).abs() * ((2 * K_TANH + 2) * tc * tc + 1) + 2 * U * term.abs() + U * (S.abs() + term.abs())
-                # d_gate = dc (or dh) times a product of three factors, one of them 1 - x (terms before the cancellation: 1 + |x|): 4 u
-                parts = [(D, Eb, gg * gi * (1 - gi), gg.abs() * gi * (1 + gi)),
-                         (D, Eb, cp * gf * (1 - gf), cp.abs() * gf * (1 + gf)),
-                         (D, Eb, gi * (1 - gg * gg), gi * (1 + gg * gg)),
-                         (dh, dhb, tc * go * (1 - go), tc.abs() * go * (1 + go) * (1 + K_TANH / 4))]
-                ref = torch.cat([v * f for v, _, f, _ in parts], 1)
-                bnd = torch.cat([e * f.abs() + 4 * U * v.abs() * m for v, e, f, m in parts], 1)
-                emit("dgates", ws["dgates"][l][t], ref, bnd + r(ref))
-                carry[l] = (D, Eb) if mut == "dc_no_f" else (D * gf, Eb * gf.abs() + U * (D * gf).abs())
+                carry[l] = cell_backward(emit, bf, dh, dhb, st["gates"][l][t], st["c"][l][t], st["c"][l][t + 1], carry[l], ws["dgates"][l][t],
+                                         carry_f=mut != "dc_no_f")
         for l in range(NL):
             emit("dc", ws["dc"][l], carry[l][0], carry[l][1])
     # 10. the input gradients: d[x | h] = d_gates Wcat.  Fused: the x columns of layer 0 and (state gradients) the h columns of slot 0;
@@ -625,6 +648,8 @@ def run_backward(case, P, img, X, st, ws, grads, rep=None, mut=None, state_grads
                 rep.exact("dxh keep", (ws["dxh"][l] == DXH_FILL) | ~keep, "of what the route does not write changed")
     # 11. parameter and input gradients
     for l in range(NL):
+        if not any(want(s) for s in ("d_w_ih", "d_w_hh", "d_b_ih", "d_b_hh")):
+            break
         din = c.din(l)
         A, xh = ws["dgates"][l].double().reshape(BL, 4 * H), st["xh"][l][:L].double().reshape(BL, c.ldx(l))
         emit("d_w_ih", grads[1 + 4 * l], A.t() @ xh[:, :din], sum_bound(BL, A.abs().t() @ xh[:, :din].abs(), None))

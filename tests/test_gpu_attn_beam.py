@@ -107,14 +107,33 @@ def _check_vs_oracle(eng, params, feats, fmap, p_cpu, f_cpu, m_cpu, L, k, alpha=
     return ids, lengths, len(ok)
 
 
-@pytest.mark.parametrize("alpha", [0.0, 0.7])
-@pytest.mark.parametrize("k", [2, 3, 5, 8])
-def test_f32_matches_oracle(dev, k, alpha):
-    shape = (6, 10, 64, 16, 32, 40, 49, 24)
+ORACLE_SHAPE = (6, 10, 64, 16, 32, 40, 49, 24)
+# P = 70: no multiple of the 8-position energy group, more than a wave; C = 136: a partial last attn_step_ctx workgroup; A = 264: a
+# second width pass of the energy kernel (f32), K hp rows of 264 floats staged in LDS
+WIDE_SHAPE = (3, 6, 64, 8, 16, 136, 70, 264)
+
+
+@pytest.mark.parametrize("k,alpha,shape", [(k, a, ORACLE_SHAPE) for a in (0.0, 0.7) for k in (2, 3, 5, 8)] + [(2, 0.0, WIDE_SHAPE), (8, 0.0, WIDE_SHAPE)],
+                         ids=[f"{k}-{a}" for a in (0.0, 0.7) for k in (2, 3, 5, 8)] + ["2-0.0-wide", "8-0.0-wide"])
+def test_f32_matches_oracle(dev, k, alpha, shape):
     params, feats, fmap, p_cpu, f_cpu, m_cpu = _problem(shape, 100 + k, dev, eos_bias=1.5)
     eng = _engine(*shape[2:], 0)
     ids, lengths, _ = _check_vs_oracle(eng, params, feats, fmap, p_cpu, f_cpu, m_cpu, shape[1], k, alpha)
-    assert ids.shape == (6, k, 10)
+    assert ids.shape == (shape[0], k, shape[1])
+
+
+@pytest.mark.parametrize("dt", [0, 1], ids=["f32", "bf16"])
+def test_k8_at_the_widest_attention(dev, dt):
+    """k = 8 at A = 2048: attn_step_energy stages 8 hp rows of 2048 floats, the 64 KB LDS request.  The call returns its status cleanly
+    and every live alpha row sums to 1."""
+    shape = (1, 3, 64, 8, 16, 16, 3, 2048)
+    params, feats, fmap, *_ = _problem(shape, 2048, dev)
+    eng = _engine(*shape[2:], dt)
+    ids, scores, lengths, alphas = eng.beam_search(params, feats, fmap, shape[1], 8, want_alphas=True)
+    torch.cuda.synchronize()
+    assert ids.shape == (1, 8, 3) and alphas.shape == (1, 8, 3, 3) and bool(torch.isfinite(scores).all())
+    assert int(lengths.min()) >= 1
+    _check_alphas(alphas, lengths)
 
 
 def test_more_than_512_rows(dev):
