@@ -275,6 +275,8 @@ _SIGNATURES = {
     "gic_gan_losses": (C.c_int, [C.c_int, c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
     "gic_xent": (C.c_int, [c_void_p, C.c_int, C.c_int64, C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_xent_seq": (C.c_int, [c_void_p, C.c_int, C.c_int64, C.c_int32, c_void_p, C.c_int64, c_void_p, C.c_int64, C.c_float, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_rollout_rewards": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
     "gic_cider_d": (C.c_int, [c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int32, C.c_int32, c_void_p, C.c_int64, c_void_p, c_void_p,
                               C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p, C.c_int64, C.c_float, C.c_int32, c_void_p,

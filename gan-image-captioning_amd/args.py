@@ -143,6 +143,12 @@ _NATIVE = [
     ("--eval-retrieval", int, 0, "image-caption retrieval evaluation (GANInstructor.evaluate_retrieval: R@1/5/10, median and mean rank in "
                                  "both directions, --disc-cond projection) after each adversarial epoch's validation", {"choices": [0, 1]}),
     ("--eval-retrieval-items", int, 1000, "items of the retrieval evaluation (the first of the split; 1000 = the COCO 1k protocol; at most 8192)"),
+    ("--pretrain-ignore-pad", int, 0, "1 = the pre-training loss is the mean over the tokens that are not --padding-idx (gic_xent_seq); "
+                                      "0 = the reference's mean over all positions, <PAD> included", {"choices": [0, 1]}),
+    ("--label-smoothing", float, 0.0, "label smoothing of the pre-training loss, in [0, 1): the target distribution is (1 - eps) onehot + "
+                                      "eps / V (gic_xent_seq).  Training batches only: validation losses stay unsmoothed"),
+    ("--eval-perplexity", int, 0, "teacher-forced per-token perplexity of the validation captions (GANInstructor.evaluate_perplexity) after "
+                                  "each pre-training and adversarial epoch's validation", {"choices": [0, 1]}),
 ]
 
 

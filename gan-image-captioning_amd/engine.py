@@ -480,6 +480,47 @@ def xent(logits: torch.Tensor, targets: torch.Tensor, want_grad: bool = True, ro
     return buf[:1], dl
 
 
+def xent_seq(logits: torch.Tensor, targets: torch.Tensor, group: int, lengths: Optional[torch.Tensor] = None, ignore_index: int = -100,
+             smoothing: float = 0.0, row_weight: Optional[torch.Tensor] = None, want_grad: bool = True) -> Dict[str, Optional[torch.Tensor]]:
+    """gic_xent_seq: the masked, label-smoothed sequence cross entropy of logits [rows, V] (f32 / bf16, contiguous) against targets int64
+    [rows], ``group`` rows per caption.  A row counts when its target is not ``ignore_index`` and, with ``lengths`` int32 [rows / group],
+    its position is below its caption's length.  Returns device tensors {"loss": f32 [] (mean over the counted rows; 0 when there are
+    none), "count": f32 [], "row_nll": f32 [rows], "cap_nll": f32 [rows / group], "cap_tokens": int32 [rows / group], "d_logits": [rows, V]
+    or None}; the per-row / per-caption values are plain negative log-likelihoods (no smoothing, no weight), zero where not counted."""
+    require_gpu(logits, targets, lengths, row_weight)
+    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16) or not logits.is_contiguous():
+        raise ValueError("xent_seq: logits must be a contiguous float32 / bfloat16 matrix [rows, V]")
+    rows, V = logits.shape
+    group = int(group)
+    if targets.dtype != torch.int64 or targets.numel() != rows:
+        raise ValueError(f"xent_seq: targets must be int64 [rows={rows}]")
+    if group < 1 or rows % group:
+        raise ValueError(f"xent_seq: group={group} must be at least 1 and divide rows={rows}")
+    smoothing = float(smoothing)
+    if not 0.0 <= smoothing < 1.0:                  # false for NaN
+        raise ValueError(f"xent_seq: smoothing must be in [0, 1), got {smoothing}")
+    caps = rows // group
+    if lengths is not None:
+        if lengths.numel() != caps:
+            raise ValueError(f"xent_seq: lengths must hold one value per caption ({caps})")
+        lengths = lengths.to(torch.int32).contiguous()
+    if row_weight is not None:
+        if row_weight.numel() != rows:
+            raise ValueError("xent_seq: row_weight must hold one weight per row")
+        row_weight = row_weight.contiguous().float()
+    dev = logits.device
+    dt = L.F32 if logits.dtype == torch.float32 else L.BF16
+    loss = torch.empty(2, device=dev, dtype=torch.float32)
+    row_buf = torch.empty(2, rows, device=dev, dtype=torch.float32)          # row_nll, the rows' loss terms (scratch)
+    cap_nll = torch.empty(caps, device=dev, dtype=torch.float32)
+    cap_tokens = torch.empty(caps, device=dev, dtype=torch.int32)
+    dl = torch.empty_like(logits) if want_grad else None
+    L.check(L.load().gic_xent_seq(ptr(logits), dt, rows, V, ptr(targets.contiguous()), group, ptr(lengths), int(ignore_index), smoothing,
+                                  ptr(row_weight), ptr(loss), ptr(row_buf[0]), ptr(row_buf[1]), ptr(cap_nll), ptr(cap_tokens), ptr(dl),
+                                  stream_ptr()), "gic_xent_seq")
+    return {"loss": loss[0], "count": loss[1], "row_nll": row_buf[0], "cap_nll": cap_nll, "cap_tokens": cap_tokens, "d_logits": dl}
+
+
 def rollout_rewards(mc_logits: Optional[torch.Tensor], full_logits: torch.Tensor, B: int, Lc: int, N: int, R: int) -> torch.Tensor:
     """gic_rollout_rewards: f32 [B, L] Monte-Carlo rewards from D's logits on the roll-outs (gicap.h)."""
     require_gpu(mc_logits, full_logits)

@@ -212,6 +212,22 @@ def _sample_captions(dec, features, maps, num_samples, top_k, top_p, temperature
                                             states=states, **cons)
 
 
+def _log_likelihood(dec, features, maps, ids, lengths):
+    """Decoder.log_likelihood / AttnDecoder.log_likelihood: ``maps`` = () or (fmap,).  ``forward(features[, fmap], ids[:, :-1], lengths,
+    pretrain=True)``'s own no-grad decode (``_forward_no_grad``: logits need no device draw, so none is taken from SEEDS) over all L
+    positions with device lengths (no host sync), then gic_xent_seq masked by ``lengths``."""
+    if ids.dim() != 2 or ids.dtype != torch.int64 or ids.shape[1] < 2:
+        raise ValueError("log_likelihood: ids must be int64 [B, L] with L >= 2")
+    B, L = ids.shape
+    lengths = torch.as_tensor(lengths).to(device=ids.device, dtype=torch.int32).reshape(-1)
+    if lengths.numel() != B:
+        raise ValueError(f"log_likelihood: lengths must hold one value per caption ({B})")
+    with torch.no_grad():
+        pred = dec._forward_no_grad(features, *maps, ids[:, :-1].contiguous(), lengths.clamp(1, L), True, None, 0, L)[0]
+        out = engine.xent_seq(pred.reshape(B * L, pred.shape[-1]), ids.reshape(-1), L, lengths=lengths, want_grad=False)
+        return -out["cap_nll"], out["cap_tokens"]
+
+
 class Decoder(nn.Module):
     """Embedding + LSTM + Linear caption decoder (generator.py:27-96)."""
 
@@ -258,12 +274,16 @@ class Decoder(nn.Module):
         seed = 0 if noise_u is not None else SEEDS.next()
         params = self.param_list()
         if not torch.is_grad_enabled() or not (features.requires_grad or any(p.requires_grad for p in params)):
-            with torch.no_grad():
-                return self.engine().forward_tf([p.detach() for p in params], features, caps, lengths, float(self.temperature),
-                                                bool(pretrain), noise_u, seed, tmax=max_length)
+            return self._forward_no_grad(features, caps, lengths, pretrain, noise_u, seed, max_length)
         pred, h_n, c_n = _ForwardTfFn.apply(self.engine(), float(self.temperature), bool(pretrain), caps, lengths, noise_u, seed,
                                             max_length, features, *params)
         return pred, (h_n, c_n)
+
+    def _forward_no_grad(self, features, caps, lengths, pretrain, noise_u, seed, max_length):
+        """``forward`` without autograd, with the seed of its device draw given: (pred, (h_n, c_n)).  Also log_likelihood's decode."""
+        with torch.no_grad():
+            return self.engine().forward_tf([p.detach() for p in self.param_list()], features, caps, lengths, float(self.temperature),
+                                            bool(pretrain), noise_u, seed, tmax=max_length)
 
     def forward_scheduled(self, features, caps, lengths, sample_prob, pick="sample", coin_u=None, noise_u=None, seed=None, max_length=None,
                           return_inputs=False):
@@ -315,6 +335,13 @@ class Decoder(nn.Module):
         constraints (gicap.h gic_decode_constraints), the banned tokens leave the distribution before top-k / top-p."""
         return _sample_captions(self, features, (), num_samples, top_k, top_p, temperature, max_caption_len, eos_id, seed, noise_u, states,
                                 no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
+
+    def log_likelihood(self, features, ids, lengths):
+        """The decoder's log-probability of given captions, in the units of the beam and sample scores: (logp f32 [B], tokens int32 [B])
+        with logp[b] = sum_{t < lengths[b]} log p(ids[b, t] | features, ids[b, <t]) (position 0 included) and tokens[b] the positions
+        summed.  ``ids`` int64 [B, L], ``lengths`` [B].  Teacher-forced: ``forward(features, ids[:, :-1], lengths, pretrain=True)``
+        followed by gic_xent_seq, under no-grad; detached."""
+        return _log_likelihood(self, features, (), ids, lengths)
 
     def add_gumbel(self, o_t, eps=1e-10, gpu=0):
         """o_t + Gumbel(0,1) noise (generator.py:84-96); on the hot path this is fused into sample()."""
@@ -474,10 +501,7 @@ class AttnDecoder(nn.Module):
         seed = 0 if noise_u is not None else SEEDS.next()
         params = self.param_list()
         if not torch.is_grad_enabled() or not (features.requires_grad or any(p.requires_grad for p in params)):
-            with torch.no_grad():
-                pred, hc, alphas = self.engine().forward_tf([p.detach() for p in params], features.detach().float(), fmap.detach(), caps,
-                                                            lengths, float(self.temperature), bool(pretrain), noise_u, seed,
-                                                            want_alphas=bool(return_alphas), tmax=max_length)
+            pred, hc, alphas = self._forward_no_grad(features, fmap, caps, lengths, pretrain, noise_u, seed, max_length, return_alphas)
         else:
             pred, h_n, c_n, alphas = _AttnForwardTfFn.apply(self.engine(), float(self.temperature), bool(pretrain), caps, lengths, noise_u,
                                                             seed, max_length, fmap, features, *params)
@@ -485,6 +509,21 @@ class AttnDecoder(nn.Module):
         if return_alphas:
             return pred, hc, alphas
         return pred, hc
+
+    def _forward_no_grad(self, features, fmap, caps, lengths, pretrain, noise_u, seed, max_length, return_alphas=False):
+        """``forward`` without autograd, with the seed of its device draw given: (pred, (h_n, c_n), alphas or None).  Also
+        log_likelihood's decode."""
+        with torch.no_grad():
+            return self.engine().forward_tf([p.detach() for p in self.param_list()], features.detach().float(), fmap.detach(), caps, lengths,
+                                            float(self.temperature), bool(pretrain), noise_u, seed, want_alphas=bool(return_alphas),
+                                            tmax=max_length)
+
+    def log_likelihood(self, features, fmap, ids, lengths):
+        """Decoder.log_likelihood with the attention step: (logp f32 [B], tokens int32 [B]) of ``ids`` int64 [B, L] given ``features`` and
+        ``fmap`` [B, P, C]."""
+        if fmap is None:
+            raise ValueError("the attention decoder needs the trunk's feature map: log_likelihood(features, fmap, ids, lengths)")
+        return _log_likelihood(self, features, (fmap,), ids, lengths)
 
     def forward_scheduled(self, features, fmap, caps, lengths, sample_prob, pick="sample", coin_u=None, noise_u=None, seed=None,
                           max_length=None, return_alphas=False, return_inputs=False):
@@ -777,6 +816,25 @@ class Generator(nn.Module):
                 return out
             r = self._rerank(rerank_disc, out, rerank_weight)
         return r["ids"], r["scores"], r["lengths"]
+
+    def score_captions(self, images, ids, lengths):
+        """How likely given captions are under the generator: (logp, tokens) in the shape of ``lengths``, logp = the teacher-forced
+        log-probability of each caption given its image (decoder.log_likelihood: the units of the beam and sample scores), tokens = the
+        positions summed.  ``ids`` int64 [B, L] with ``lengths`` [B], or K captions per image, [B, K, L] with [B, K]: the image goes
+        through the encoder once and its features (and feature map) are repeated for its captions.  Features as ``caption`` forms them
+        (the encoder in the module's current mode, or embed(<S>) with --conditional-gan 0), under no-grad."""
+        lengths = torch.as_tensor(lengths).to(ids.device)
+        if ids.dim() not in (2, 3) or tuple(lengths.shape) != tuple(ids.shape[:-1]) or ids.shape[0] != len(images):
+            raise ValueError("score_captions: ids must be [B, L] with lengths [B], or [B, K, L] with lengths [B, K], B = len(images)")
+        K = ids.shape[1] if ids.dim() == 3 else 1
+        with torch.no_grad():
+            features, fmap = self._features(images)
+            if K > 1:
+                features = features.repeat_interleave(K, 0)
+                fmap = None if fmap is None else fmap.repeat_interleave(K, 0)
+            logp, tokens = self.decoder.log_likelihood(features, *(() if fmap is None else (fmap,)), ids.reshape(-1, ids.shape[-1]),
+                                                       lengths.reshape(-1))
+        return logp.view(lengths.shape), tokens.view(lengths.shape)
 
     def forward(self, images, caps, lengths, pretrain=False):
         features, fmap = self._features(images)

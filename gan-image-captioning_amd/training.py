@@ -12,6 +12,7 @@ same batch contract and logging, with these deliberate fixes:
 from __future__ import annotations
 
 import json
+import math
 import os
 from typing import Optional
 
@@ -117,6 +118,14 @@ def check_scheduled_sampling(args):
     return p, n, pick
 
 
+def check_seq_loss(args):
+    """The instructor's checks of the sequence-loss flags, before anything touches the device: (ignore_pad, label_smoothing)."""
+    eps = float(getattr(args, "label_smoothing", 0.0))
+    if not 0.0 <= eps < 1.0:                      # false for NaN too
+        raise ValueError(f"--label-smoothing must be in [0, 1), got {eps}")
+    return bool(int(getattr(args, "pretrain_ignore_pad", 0))), eps
+
+
 def scheduled_sampling_prob(p: float, ramp_epochs: int, epoch: int) -> float:
     """p_e = p * min(1, e / n) of epoch e (0-based); n = 0: p throughout."""
     return p if ramp_epochs <= 0 else p * min(1.0, epoch / ramp_epochs)
@@ -128,6 +137,7 @@ class GANInstructor:
         self.pretrain_mode, self.attn_reg = check_modes(args)
         self.ss_prob, self.ss_ramp, self.ss_pick = check_scheduled_sampling(args)
         self.ss_prob_now = scheduled_sampling_prob(self.ss_prob, self.ss_ramp, 0)      # pretrain_generator sets it per epoch
+        self.ignore_pad, self.label_smoothing = check_seq_loss(args)
         self.dist = parallel.DistInfo.from_env()
         from .generator import SEEDS
         SEEDS.rank = self.dist.rank            # replicas share weights and the torch seed, not the device noise streams
@@ -223,11 +233,21 @@ class GANInstructor:
             gen_captions, _ids = self.gen.decoder.sample(feats[0], fmap=feats[1], pretrain=True, max_caption_len=max_caption_len)
         else:
             gen_captions, _ids = self.gen.decoder.sample(feats, pretrain=True, max_caption_len=max_caption_len)
-        flat = gen_captions.reshape(-1, gen_captions.size(-1))
-        loss = _XentFn.apply(flat, captions.reshape(-1))                   # nn.CrossEntropyLoss(), training.py:81-83
+        loss = self._pretrain_loss(gen_captions, captions, train)         # nn.CrossEntropyLoss(), training.py:81-83
         if train:
             self.optimize(self.pretrain_opt, loss, self.gen)
         return loss
+
+    def _pretrain_loss(self, pred, targets, train):
+        """The pre-training loss of pred [B, T, V] against targets [B, T]: the reference's mean over all positions (_XentFn), or with
+        --pretrain-ignore-pad 1 / --label-smoothing > 0 the mean over the tokens that are not <PAD>, label-smoothed (_SeqXentFn).
+        Only training batches are smoothed: the validation loss stays comparable."""
+        flat = pred.reshape(-1, pred.size(-1))
+        eps = self.label_smoothing if train else 0.0
+        if not self.ignore_pad and self.label_smoothing == 0.0:
+            return _XentFn.apply(flat, targets.reshape(-1))
+        ignore = int(self.args.padding_idx) if self.ignore_pad else -100        # -100: no token has it, nothing is ignored
+        return _SeqXentFn.apply(flat, targets.reshape(-1), int(pred.shape[1]), None, ignore, eps)[0]
 
     def _pretrain_step_teacher(self, feats, captions, lengths, train):
         """--pretrain-mode teacher: pred = decoder.forward(features[, fmap], captions[:, :-1], lengths, pretrain=True), the same
@@ -249,8 +269,7 @@ class GANInstructor:
         else:
             pred, _ = self.gen.decoder(feats, caps, lengths, pretrain=True)
             alphas = None
-        flat = pred.reshape(-1, pred.size(-1))
-        loss = _XentFn.apply(flat, captions[:, :pred.shape[1]].reshape(-1))
+        loss = self._pretrain_loss(pred, captions[:, :pred.shape[1]], train)
         if self.attn_reg:
             loss = loss + self.attn_reg * ((1.0 - alphas.sum(1)) ** 2).sum(1).mean()
         if train:
@@ -292,6 +311,8 @@ class GANInstructor:
             total_loss += train_epoch_loss
             self.gen.eval()
             val_epoch_loss = np.mean(self.genpretrain_loop("val"))
+            if int(getattr(self.args, "eval_perplexity", 0)) and self.dist.rank == 0:
+                self.evaluate_perplexity("val")
             if best_loss is None or val_epoch_loss < best_loss:
                 best_loss = val_epoch_loss
                 self._save(self.gen.state_dict(), "pretrained_model.ckpt")                    # training.py:118
@@ -490,6 +511,8 @@ class GANInstructor:
                 self.evaluate_match("val")
             if int(getattr(self.args, "eval_retrieval", 0)) and self.dist.rank == 0:
                 self.evaluate_retrieval("val", max_items=int(getattr(self.args, "eval_retrieval_items", 1000)))
+            if int(getattr(self.args, "eval_perplexity", 0)) and self.dist.rank == 0:
+                self.evaluate_perplexity("val")
             if int(getattr(self.args, "eval_diverse_beam_size", 0)) > 0 and self.dist.rank == 0:
                 self.evaluate_diverse_beam("val", beam_size=int(self.args.eval_diverse_beam_size),
                                            groups=int(getattr(self.args, "eval_diverse_groups", 2)),
@@ -550,6 +573,41 @@ class GANInstructor:
         step = max(self.adv_epoch, 0)
         self.writer.add_scalar(f"MatchAcc_{what}", out["pair_acc"], step)
         self.writer.add_scalar(f"MatchMargin_{what}", out["margin"], step)
+        return out
+
+    def evaluate_perplexity(self, what="val"):
+        """Teacher-forced per-token perplexity of the generator over the pre-training eval (``what="val"``) or train loader: one
+        decoder.log_likelihood per batch (features as pretrain_step forms them, with the generator in eval mode for the pass, whatever mode
+        it was in, and put back afterwards; no label smoothing), the captions' negative
+        log-likelihoods and token counts (the positions t < length, <S> and <E> included) summed on the device and read with one
+        sync.  Returns {"nll_per_token", "perplexity" = exp(sum nll / sum tokens), "tokens", "captions"}; logs them and writes the scalar
+        ``Perplexity_<what>``."""
+        loader = self.pre_eval_loader if what == "val" else self.pre_train_loader
+        dev = self.args.device
+        sums = torch.zeros(2, dtype=torch.float64, device=dev)           # nll, tokens
+        n = 0
+        was_training = self.gen.training
+        self.gen.eval()                              # the encoder's BatchNorm on its running statistics, which stay as they are
+        try:
+            with torch.no_grad():
+                for batch in loader:
+                    images, captions, lengths = batch[0].to(dev), batch[1].to(dev), batch[2]
+                    feats = self._features(images, captions.shape[0])
+                    if self.attention:
+                        logp, tokens = self.gen.decoder.log_likelihood(feats[0], feats[1], captions, lengths)
+                    else:
+                        logp, tokens = self.gen.decoder.log_likelihood(feats, captions, lengths)
+                    sums += torch.stack([-logp.double().sum(), tokens.double().sum()])
+                    n += captions.shape[0]
+        finally:
+            self.gen.train(was_training)
+        nll, tokens = sums.tolist() if n else (0.0, 0.0)                  # the one sync
+        per_token = nll / tokens if tokens else 0.0
+        out = {"nll_per_token": per_token, "perplexity": math.exp(per_token) if per_token < 700.0 else float("inf"),
+               "tokens": int(tokens), "captions": n}
+        self.log.info("[EVAL] perplexity (%s): %.4f | nll per token %.6f | %d tokens in %d captions", what, out["perplexity"],
+                      out["nll_per_token"], out["tokens"], out["captions"])
+        self.writer.add_scalar(f"Perplexity_{what}", out["perplexity"], self.adv_epoch if self.adv_epoch >= 0 else self.pretrain_steps)
         return out
 
     RETRIEVAL_MAX_ITEMS = 8192
@@ -813,3 +871,20 @@ class _XentFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d):
         return ctx.dlog * d, None
+
+
+class _SeqXentFn(torch.autograd.Function):
+    """F.cross_entropy(ignore_index, label_smoothing) over the counted rows via gic_xent_seq (engine.xent_seq): returns (loss, cap_nll
+    [rows / group], cap_tokens [rows / group]); only the loss is differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, group, lengths=None, ignore_index=-100, smoothing=0.0):
+        out = engine.xent_seq(logits.detach().contiguous(), targets, group, lengths=lengths, ignore_index=ignore_index, smoothing=smoothing,
+                              want_grad=ctx.needs_input_grad[0])
+        ctx.dlog = out["d_logits"]
+        ctx.mark_non_differentiable(out["cap_nll"], out["cap_tokens"])
+        return out["loss"], out["cap_nll"], out["cap_tokens"]
+
+    @staticmethod
+    def backward(ctx, d, _d_nll, _d_tokens):
+        return ctx.dlog * d, None, None, None, None, None

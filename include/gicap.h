@@ -853,6 +853,28 @@ int gic_gan_losses(int loss_type, const float* d_real, const float* d_fake, cons
 int gic_xent(const void* logits, int dtype, int64_t rows, int32_t V, const int64_t* targets, float* loss,
              void* d_logits, const float* row_weight, void* stream);
 
+/* Masked, label-smoothed sequence cross entropy with per-caption log-likelihoods (no reference counterpart).
+ * logits [rows, V] (f32 / bf16, contiguous), targets int64 [rows]; `group` (>= 1, divides rows) = the rows per caption, row r is position
+ * t = r % group of caption b = r / group.  Row (b, t) is COUNTED when targets[r] != ignore_index (any value, -100 ignores nothing real)
+ * and, with lengths (optional, int32 [rows / group]), t < lengths[b].  With lp = log_softmax(logits[r]), eps = smoothing in [0, 1) and
+ * w = row_weight (optional, f32 [rows]; 1 without):
+ *   nll_r = -lp[t_r]     row_r = (1 - eps) nll_r + eps * (-mean_v lp[v])
+ *   row_nll f32 [rows]            nll_r of a counted row, else 0 (plain, unsmoothed: the log-likelihood output)
+ *   cap_nll f32 [rows / group]    the row_nll of caption b added in index order (optional)
+ *   cap_tokens int32 [rows/group] the counted rows of caption b (optional)
+ *   loss f32 [2]                  loss[0] = sum over the counted rows of w_r row_r / count, loss[1] = count = sum_b cap_tokens[b]
+ *   d_logits [rows, V] (optional, dtype of logits) = w_r (softmax - (1 - eps) onehot(t_r) - eps / V) / count, zeros in an uncounted row
+ * row_ws: f32 [rows] scratch.  Every output is written by the call.  With w = 1 this is F.cross_entropy(ignore_index, label_smoothing),
+ * values and gradient, with two differences: count = 0 gives loss[0] = 0 and a zero gradient (torch: NaN), and a counted target outside
+ * [0, V) makes loss[0] (and its row_nll / cap_nll) NaN as in gic_xent; it is never used as an index.  nll = (max - x_t) + log sum
+ * exp(x - max): a common offset of a row's logits costs no digits.  Three launches, no f32 atomics, no host synchronisation; every sum has
+ * a fixed order, so two calls give the same bits in either mode of gic_set_deterministic.  GIC_STATUS_INVALID_ARG, before any launch: a
+ * NULL logits / targets / loss / row_nll / row_ws, rows <= 0 (or beyond 2^24 - 1: a 256-thread workgroup per row, and the f32 count), V <= 0, group < 1, rows % group != 0, smoothing outside
+ * [0, 1) or NaN; GIC_STATUS_UNSUPPORTED: a dtype other than f32 / bf16. */
+int gic_xent_seq(const void* logits, int dtype, int64_t rows, int32_t V, const int64_t* targets, int64_t group,
+                 const int32_t* lengths, int64_t ignore_index, float smoothing, const float* row_weight, float* loss,
+                 float* row_nll, float* row_ws, float* cap_nll, int32_t* cap_tokens, void* d_logits, void* stream);
+
 /* SeqGAN Monte-Carlo rewards (BASELINE config 5; no reference counterpart): mc_logits f32 [(L-1), N, B, R] = D's logits on the
  * N roll-outs of every prefix length 1..L-1 (caption b, representation r), full_logits f32 [B, R] = D on the complete captions.
  * rewards f32 [B, L]: reward[b, t] = mean_{n,r} sigmoid(mc_logits[t, n, b, r]) for t < L-1, mean_r sigmoid(full_logits[b, r]) for
