@@ -154,6 +154,12 @@ class BnRunningDesc(C.Structure):
                 ("momentum", C.c_float), ("C", C.c_int32), ("nrep", C.c_int32)]
 
 
+class ImageSrc(C.Structure):
+    """gic_image_src (gic_image_preprocess): one source image of a ragged uint8 batch."""
+    _fields_ = [("offset", C.c_int64), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("row_stride", C.c_int32), ("box", C.c_float * 4), ("flip", C.c_int32), ("reserved", C.c_int32)]
+
+
 _P = C.POINTER
 _SIGNATURES = {
     "gic_abi_version": (C.c_int, []),
@@ -253,6 +259,9 @@ _SIGNATURES = {
     "gic_disc_rep_mean": (C.c_int, [_P(DiscDims), _P(DiscState), c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_match_ranks": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int32, c_void_p, c_void_p, c_void_p]),
     "gic_pack_image": (C.c_int, [c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
+    "gic_image_preprocess_ws_bytes": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_uint64)]),
+    "gic_image_preprocess": (C.c_int, [c_void_p, C.c_uint64, _P(ImageSrc), C.c_int32, C.c_int32, c_float_p, c_float_p, c_void_p, c_void_p,
+                                       c_void_p]),
     "gic_repack_conv_weight": (C.c_int, [c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
     "gic_conv2d_bn_in": (C.c_int, [c_void_p, c_void_p, C.c_int, c_void_p, c_void_p, C.c_float, c_void_p, c_void_p, c_void_p, C.c_int,
                          C.c_int] + [C.c_int] * 9 + [c_void_p]),

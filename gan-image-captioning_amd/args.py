@@ -149,6 +149,13 @@ _NATIVE = [
                                       "eps / V (gic_xent_seq).  Training batches only: validation losses stay unsmoothed"),
     ("--eval-perplexity", int, 0, "teacher-forced per-token perplexity of the validation captions (GANInstructor.evaluate_perplexity) after "
                                   "each pre-training and adversarial epoch's validation", {"choices": [0, 1]}),
+    ("--device-preprocess", int, 0, "1 = the datasets hand out the decoded uint8 images and one kernel (gic_image_preprocess) resizes, "
+                                    "normalises and, under --augment, crops and flips them on the GPU; 0 = the host path (PIL resize + "
+                                    "numpy per item)", {"choices": [0, 1]}),
+    ("--augment", str, "none", "train-time image augmentation (needs --device-preprocess 1): flip = horizontal flip with p = 0.5, crop = "
+                               "random resized crop (area fraction in --augment-crop-scale, aspect ratio in [3/4, 4/3]); validation and "
+                               "evaluation never augment", {"choices": ["none", "flip", "crop", "crop-flip"]}),
+    ("--augment-crop-scale", "floatpair", (0.5, 1.0), "lo,hi of the random resized crop's area fraction"),
 ]
 
 
@@ -158,12 +165,34 @@ def _intlist(text):
     return [int(v) for v in str(text).replace("[", "").replace("]", "").split(",") if v.strip()]
 
 
+def _floatpair(text):
+    if isinstance(text, (list, tuple)):
+        vals = [float(v) for v in text]
+    else:
+        vals = [float(v) for v in str(text).replace("(", "").replace(")", "").split(",") if v.strip()]
+    if len(vals) != 2 or not (0.0 < vals[0] <= vals[1] <= 1.0):
+        raise argparse.ArgumentTypeError(f"expected lo,hi with 0 < lo <= hi <= 1, got {text!r}")
+    return (vals[0], vals[1])
+
+
+AUGMENT_NEEDS_DEVICE = "--augment {augment} needs --device-preprocess 1: crops and flips are applied by the device image pipeline"
+
+
+def check_image_pipeline(args) -> None:
+    """--augment without --device-preprocess 1 is refused: the host path has no augmentation."""
+    augment = getattr(args, "augment", "none")
+    if augment != "none" and not int(getattr(args, "device_preprocess", 0)):
+        raise ValueError(AUGMENT_NEEDS_DEVICE.format(augment=augment))
+
+
 def _add(parser, rows):
     for row in rows:
         flag, typ, default, helptext = row[:4]
         extra = dict(row[4]) if len(row) > 4 else {}
         if typ == "intlist":
             typ = _intlist
+        elif typ == "floatpair":
+            typ = _floatpair
         parser.add_argument(flag, type=typ, default=default, help=helptext, **extra)
 
 
@@ -213,6 +242,7 @@ def make_experiment_dirs(args) -> None:
 
 def get_args(argv=None, make_dirs: bool = True):
     args = build_parser().parse_args(argv)
+    check_image_pipeline(args)
     if make_dirs:
         make_experiment_dirs(args)
     resolve_device(args)

@@ -196,6 +196,49 @@ def embedding_bwd(d_out: torch.Tensor, ids: torch.Tensor, V: int, d_weight: Opti
     return d_weight
 
 
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)        # tasks.IMAGENET_MEAN / _STD
+
+
+def image_srcs(descs):
+    """``(gic_image_src * N)`` from an iterable of ``(offset, height, width, channels, row_stride, (x0, y0, x1, y1), flip)`` rows (a
+    ctypes array of ``_lib.ImageSrc`` passes through)."""
+    if isinstance(descs, C.Array) and getattr(descs, "_type_", None) is L.ImageSrc:
+        return descs
+    rows = list(descs)
+    arr = (L.ImageSrc * max(1, len(rows)))()
+    for s, (offset, h, w, c, stride, box, flip) in zip(arr, rows):
+        s.offset, s.height, s.width, s.channels, s.row_stride, s.flip = int(offset), int(h), int(w), int(c), int(stride), int(flip)
+        for k in range(4):
+            s.box[k] = float(box[k])
+    return arr
+
+
+def image_preprocess_ws_bytes(N: int, S: int) -> int:
+    """Host-only size query of gic_image_preprocess's scratch."""
+    out = C.c_uint64(0)
+    L.check(L.load().gic_image_preprocess_ws_bytes(int(N), int(S), C.byref(out)), "gic_image_preprocess_ws_bytes")
+    return int(out.value)
+
+
+def image_preprocess(pixels_u8: torch.Tensor, descs, S: int, out: Optional[torch.Tensor] = None, mean=IMAGENET_MEAN,
+                     std=IMAGENET_STD) -> torch.Tensor:
+    """gic_image_preprocess on the current stream: a flat uint8 device tensor holding a ragged batch of HWC / HW images + their
+    descriptors (``image_srcs``) -> f32 [N,3,S,S]: crop box, flip, antialiased bilinear resize, grey -> 3 channels, normalisation."""
+    require_gpu(pixels_u8, out)
+    if pixels_u8.dtype != torch.uint8 or pixels_u8.dim() != 1 or not pixels_u8.is_contiguous():
+        raise ValueError("image_preprocess: pixels must be a flat contiguous uint8 tensor")
+    src = image_srcs(descs)
+    N = len(descs) if hasattr(descs, "__len__") else len(src)
+    if out is None:
+        out = torch.empty(max(N, 0), 3, int(S), int(S), device=pixels_u8.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (N, 3, int(S), int(S)) or not out.is_contiguous():
+        raise ValueError(f"image_preprocess: out must be a contiguous f32 [{N},3,{S},{S}] tensor")
+    ws = torch.empty(image_preprocess_ws_bytes(N, S), device=pixels_u8.device, dtype=torch.uint8)
+    L.check(L.load().gic_image_preprocess(ptr(pixels_u8), pixels_u8.numel(), src, N, int(S), _arr(C.c_float, 3, mean),
+                                          _arr(C.c_float, 3, std), ptr(out), ptr(ws), stream_ptr()), "gic_image_preprocess")
+    return out
+
+
 def sample_opts(num_samples: int = 1, top_k: int = 0, top_p: float = 1.0, temperature: float = 1.0, eos_id: int = 2,
                 pad_id: int = 0) -> L.SampleOpts:
     """gic_sample_opts (h0 / c0 unset); the library checks the values."""

@@ -25,23 +25,27 @@ def main(argv=None):
     torch.manual_seed(seed)
     if torch.cuda.is_available():
         torch.cuda.manual_seed_all(seed)
+    # --device-preprocess 1: raw uint8 items, resized / normalised / augmented on the GPU (tasks.RawImageBatch); only training augments
+    raw = bool(args.device_preprocess)
+    aug = {"augment": args.augment, "crop_scale": tuple(args.augment_crop_scale)} if raw else {}
+    pipe = ({"raw": True} if args.synthetic else {"device_preprocess": True}) if raw else {}
     if args.synthetic:
         if args.vocab_size <= 0:
             args.vocab_size = 10000
         n_train = args.synthetic_batches * args.adv_train_batch_size
-        train = SyntheticCaptionData(n_train, args.vocab_size, args.image_size, args.synthetic_caption_len, seed)
+        train = SyntheticCaptionData(n_train, args.vocab_size, args.image_size, args.synthetic_caption_len, seed, **pipe, **aug)
         val = SyntheticCaptionData(max(args.adv_eval_batch_size, n_train // 4), args.vocab_size, args.image_size,
-                                   args.synthetic_caption_len, seed + 1)
+                                   args.synthetic_caption_len, seed + 1, **pipe)
     else:
         train = COCO_data(args.data_dir + "/dataset_coco.json", args.data_dir, "train", args.image_size,
-                          args.captions_per_image, dataset_percent=args.dataset_percent)
+                          args.captions_per_image, dataset_percent=args.dataset_percent, **pipe, **aug)
         args.vocab_size = train.vocab_size                                       # main.py:38
         if getattr(args, "decoder", "lstm") == "attention" and args.vocab_size % 4:
             # the attention kernels (no reference counterpart) move vocabulary rows in 16-byte pieces: V is rounded up to a multiple
             # of 4; the extra classes never occur in the data (the LSTM decoder and the discriminator take any V)
             args.vocab_size += 4 - args.vocab_size % 4
         val = COCO_data(args.data_dir + "/dataset_coco.json", args.data_dir, "val", args.image_size, args.captions_per_image,
-                        vocab_dicts=(train.word_to_index, train.index_to_word), dataset_percent=args.dataset_percent)
+                        vocab_dicts=(train.word_to_index, train.index_to_word), dataset_percent=args.dataset_percent, **pipe)
     inst = GANInstructor(args, train, val)
     if getattr(args, "resume", ""):
         inst.load_checkpoint(args.resume)

@@ -23,12 +23,13 @@ from torch.utils.data import DataLoader
 from tqdm import tqdm
 
 from . import engine, parallel
+from .args import check_image_pipeline
 from .discriminator import Discriminator
 from .fused_step import FusedAdvStep
 from .seqgan import SeqGANStep
 from .generator import Generator
 from .optim import FusedClipAdam, ParamArena
-from .tasks import collate_fn
+from .tasks import make_collate, stack_images
 from .utils import create_logger, get_fixed_temperature, get_losses
 
 
@@ -138,6 +139,7 @@ class GANInstructor:
         self.ss_prob, self.ss_ramp, self.ss_pick = check_scheduled_sampling(args)
         self.ss_prob_now = scheduled_sampling_prob(self.ss_prob, self.ss_ramp, 0)      # pretrain_generator sets it per epoch
         self.ignore_pad, self.label_smoothing = check_seq_loss(args)
+        check_image_pipeline(args)
         self.dist = parallel.DistInfo.from_env()
         from .generator import SEEDS
         SEEDS.rank = self.dist.rank            # replicas share weights and the torch seed, not the device noise streams
@@ -180,7 +182,7 @@ class GANInstructor:
         # training.py:28-32 (shuffle=True for the two train loaders).  Under data parallelism the shuffling moves into the
         # DistributedSampler (the DataLoader itself must not shuffle when it is given a sampler); set_epoch() in the loops.
         mk = lambda ds, bs, shuffle: None if ds is None else DataLoader(   # noqa: E731
-            ds, shuffle=shuffle and not dp, batch_size=bs, collate_fn=collate_fn, num_workers=nw,
+            ds, shuffle=shuffle and not dp, batch_size=bs, collate_fn=make_collate(ds), num_workers=nw,
             sampler=parallel.shard_sampler(ds, self.dist, shuffle) if dp else None)
         self.pre_train_loader = mk(train_dataset, args.pre_train_batch_size, True)
         self.pre_eval_loader = mk(dev_dataset, args.pre_eval_batch_size, False)
@@ -439,13 +441,14 @@ class GANInstructor:
         CIDEr-D."""
         from .cider import RefBatch
         from .scst import SCSTStep
-        from .tasks import ImageGroups, collate_groups
+        from .tasks import ImageGroups
         args = self.args
         groups = ImageGroups(self.train_dataset)
         step = SCSTStep(self, scst_reward_scorer(args, groups.references()), int(getattr(args, "scst_samples", 5)),
                         getattr(args, "scst_baseline", "greedy"), float(getattr(args, "scst_lr", 5e-5)))
         dp = self.dist.world_size > 1
-        loader = DataLoader(groups, shuffle=not dp, batch_size=args.adv_train_batch_size, collate_fn=collate_groups,
+        loader = DataLoader(groups, shuffle=not dp, batch_size=args.adv_train_batch_size,
+                            collate_fn=make_collate(self.train_dataset, groups=True),
                             num_workers=int(getattr(args, "num_workers", 4)),
                             sampler=parallel.shard_sampler(groups, self.dist, True) if dp else None)
         L = int(args.max_seq_len)
@@ -721,7 +724,7 @@ class GANInstructor:
             for bi, s in enumerate(range(0, len(order), bs)):
                 keys = order[s:s + bs]
                 firsts = [ds[groups[k][0]] for k in keys]          # one image load per image
-                images = torch.stack([it[0] for it in firsts]).to(self.args.device)
+                images = stack_images([it[0] for it in firsts], getattr(ds, "image_size", None)).to(self.args.device)
                 caps = [[coco_ids(ds.captions[j]) for j in groups[k]] if coco else [it[1]] for k, it in zip(keys, firsts)]
                 L = max_caption_len or max(int(getattr(self.args, "max_seq_len", 0) or 0),
                                            max(len(c) for group in caps for c in group) + 2)

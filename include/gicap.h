@@ -735,6 +735,39 @@ int gic_match_ranks(const float* S, int64_t ld, const float* row_bias, int32_t N
  */
 /* NCHW f32 [N,3,S,S] -> zero-bordered NHWC4 act [N, S+2*pad, Wp, 4] (channel 3 = 0); Wp >= S+2*pad. */
 int gic_pack_image(const float* nchw, void* out, int dtype, int N, int S, int pad, int Wp, void* stream);
+
+/* Image pipeline: everything between the JPEG decode and that NCHW tensor (the Resize / ToTensor / Normalize of src/tasks.py:92-100,
+ * plus an optional crop box and horizontal flip) for a ragged batch of uint8 images in ONE kernel.
+ *
+ * Per axis (source length n, box [b0, b1) in source pixels, S outputs) the triangle filter with its support scaled by the downscale
+ * factor, separable, horizontal pass first, no 8-bit rounding between the passes:
+ *   scale = (b1 - b0) / S   fs = max(scale, 1)   c_i = b0 + (i + 0.5) scale
+ *   taps first = max(int(c_i - fs + 0.5), 0) .. last - 1, last = min(int(c_i + fs + 0.5), n)       clipped to the image, not the box
+ *   w_x = max(0, 1 - |x - c_i + 0.5| / fs), normalised to sum 1 over the taps
+ * = PIL Image.resize(BILINEAR, box=) up to its 8-bit roundings = F.interpolate(bilinear, antialias=True).  flip mirrors the output
+ * horizontally; a one-channel image feeds all three planes; out = (v / 255 - mean_c) / std_c.
+ *
+ * pixels: DEVICE bytes (any alignment; 4-byte aligned takes the dword-load path); src / mean / std: HOST; out_nchw: DEVICE f32
+ * [N,3,S,S], 16-byte aligned; ws: DEVICE scratch of gic_image_preprocess_ws_bytes(N, S) bytes, 16-byte aligned.  Every descriptor is
+ * checked on the host before anything is enqueued -- N in 1..65535, S in 1..1024, height / width in 1..16384, channels 1 | 3,
+ * row_stride >= width * channels, offset + (height-1) row_stride + width channels <= pixels_bytes, a finite ordered box inside the
+ * image, flip 0 | 1, std > 0; anything else GIC_STATUS_INVALID_ARG -- and the descriptors travel to ws as kernel arguments: no host
+ * memory is read after the call returns.  The kernel checks every load against pixels_bytes as well.  Centres and weight sums are
+ * float64, tap offsets f32 relative to the first tap, accumulation f32 in a fixed order, no atomics: two calls give the same bits,
+ * and any offset / row_stride gives the bits of any other. */
+typedef struct {            /* one source image; host array */
+  int64_t offset;           /* byte offset of pixel (0,0) in `pixels` */
+  int32_t height, width;    /* 1 .. 16384 */
+  int32_t channels;         /* 1 or 3, interleaved (HWC) */
+  int32_t row_stride;       /* bytes, >= width*channels */
+  float   box[4];           /* x0, y0, x1, y1 in source pixels, 0 <= x0 < x1 <= width (same for y); the whole image = 0,0,W,H */
+  int32_t flip;             /* 0 / 1: mirror the output horizontally */
+  int32_t reserved;
+} gic_image_src;
+/* Host-only (no GPU needed): bytes of `ws` for N images. */
+int gic_image_preprocess_ws_bytes(int32_t N, int32_t S, uint64_t* out);
+int gic_image_preprocess(const uint8_t* pixels, uint64_t pixels_bytes, const gic_image_src* src, int32_t N, int32_t S,
+                         const float mean[3], const float std[3], float* out_nchw, void* ws, void* stream);
 /* conv weight [Cout,Cin,KH,KW] f32 -> act [Cout,KH,KW_pad,Cin_pad] (zero padded). */
 int gic_repack_conv_weight(const float* w, void* out, int dtype, int Cout, int Cin, int KH, int KW, int Cin_pad, int KW_pad,
                            void* stream);
