@@ -290,6 +290,8 @@ _SIGNATURES = {
     "gic_cider_d": (C.c_int, [c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int32, C.c_int32, c_void_p, C.c_int64, c_void_p, c_void_p,
                               C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p, C.c_int64, C.c_float, C.c_int32, c_void_p,
                               c_void_p]),
+    "gic_cider_pairwise": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p, C.c_int64, C.c_float,
+                                     C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_caption_overlap": (C.c_int, [c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int32, C.c_int32, c_void_p, C.c_int64, c_void_p, c_void_p,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_set_deterministic": (C.c_int, [C.c_int]),
@@ -303,7 +305,8 @@ _SIGNATURES = {
 
 ABI_VERSION = 5               # GIC_ABI_VERSION of include/gicap.h
 CIDER_MAX_LEN, CIDER_MAX_REFS, CIDER_MAX_VOCAB = 64, 32, 32768      # GIC_CIDER_MAX_LEN / _MAX_REFS / _MAX_VOCAB
-OVERLAP_STATS = 10            # GIC_OVERLAP_STATS: clipped 1..4, total 1..4, length, closest reference length
+CIDER_PAIR_MAX_K, CIDER_PAIR_SQUARINGS = 32, 16      # GIC_CIDER_PAIR_MAX_K / _SQUARINGS
+OVERLAP_STATS = 10           # GIC_OVERLAP_STATS: clipped 1..4, total 1..4, length, closest reference length
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _lib = None
 

@@ -156,6 +156,12 @@ _NATIVE = [
                                "random resized crop (area fraction in --augment-crop-scale, aspect ratio in [3/4, 4/3]); validation and "
                                "evaluation never augment", {"choices": ["none", "flip", "crop", "crop-flip"]}),
     ("--augment-crop-scale", "floatpair", (0.5, 1.0), "lo,hi of the random resized crop's area fraction"),
+    ("--eval-consensus-samples", int, 0, "sampled captions per image of the consensus evaluation (GANInstructor.evaluate_consensus: CIDEr-D of "
+                                         "the first draw and of the consensus pick, Self-CIDEr of the samples; sampling as --eval-top-k / "
+                                         "--eval-top-p / --eval-sample-temperature set it) after each adversarial epoch's validation; "
+                                         "0 = off", {"choices": list(range(9))}),
+    ("--eval-consensus-weight", float, 1.0, "weight of a sample's consensus (its mean CIDEr-D against the image's other samples) beside "
+                                            "its log-probability in that evaluation's pick"),
 ]
 
 

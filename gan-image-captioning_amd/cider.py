@@ -160,3 +160,23 @@ class CiderD:
         out = engine.cider_d(flat, cand_lengths.reshape(-1), img, refs.ids, refs.lengths, refs.offsets, refs.max_refs, self.keys, self.idf,
                              self.log_n, self.V)
         return out.view(cand_lengths.shape)
+
+    def pairwise(self, ids: torch.Tensor, lengths: torch.Tensor, want_matrix: bool = True, want_consensus: bool = True,
+                 want_self_cider: bool = True) -> dict:
+        """CIDEr-D among the K captions of each image (gic_cider_pairwise; gicap.h): ``ids`` int64 [B, K, L],
+        ``lengths`` [B, K], K <= 32.  Returns {"matrix": f32 [B, K, K] -- caption i as the candidate against caption j as the single
+        reference, in CIDEr-D units --, "consensus": f32 [B, K], each caption's mean score against the K - 1 others (the
+        minimum-Bayes-risk pick is its argmax), "self_cider": f32 [B], the Self-CIDEr diversity of each set (Wang & Chan 2019; 0 =
+        all alike, 1 = nothing shared)}; an output that is not wanted is None.  One launch, no host sync."""
+        if ids.dim() != 3:
+            raise ValueError(f"pairwise takes ids [B, K, L], got {tuple(ids.shape)}")
+        if not 1 <= ids.shape[1] <= _lib.CIDER_PAIR_MAX_K:
+            raise ValueError(f"pairwise CIDEr-D compares 1..{_lib.CIDER_PAIR_MAX_K} captions per image, got {ids.shape[1]}")
+        if not 1 <= ids.shape[2] <= _lib.CIDER_MAX_LEN:
+            raise ValueError(f"captions of {ids.shape[2]} ids: CIDEr-D scores 1..{_lib.CIDER_MAX_LEN}")
+        return engine.cider_pairwise(ids, lengths, self.keys, self.idf, self.log_n, self.V, want_matrix=want_matrix,
+                                     want_consensus=want_consensus, want_self_cider=want_self_cider)
+
+    def self_cider(self, ids: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+        """The Self-CIDEr diversity f32 [B] of the caption sets ``ids`` [B, K, L] (``pairwise`` with that output alone)."""
+        return self.pairwise(ids, lengths, want_matrix=False, want_consensus=False)["self_cider"]

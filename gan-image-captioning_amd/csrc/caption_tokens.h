@@ -1,4 +1,4 @@
-// Caption tokens for the device-side metrics (cider.hip, overlap.hip): a wave strips a caption's specials into LDS, a caption position
+// Caption tokens for the device-side metrics (cider.hip, cider_pair.hip, overlap.hip): a wave strips a caption's specials into LDS, a caption position
 // is a lane, and every position packs the 4 tokens that start at it into one 64-bit window (15 bits per token).
 #pragma once
 #include "common.h"
@@ -32,6 +32,25 @@ __device__ __forceinline__ int strip_row(const int64_t* row, int len, int* dst) 
 // the 4 tokens from position p on, high to low, zero past the caption's end
 __device__ __forceinline__ uint64_t window(const int* tok, int p) {
   return ((uint64_t)tok[p] << 45) | ((uint64_t)tok[p + 1] << 30) | ((uint64_t)tok[p + 2] << 15) | (uint64_t)tok[p + 3];
+}
+
+// ---------------------------------------------------------------- CIDEr-D (cider.hip, cider_pair.hip)
+constexpr float kCiderTwoSigma2 = 2.f * 6.f * 6.f;      // sigma = 6
+
+// the host table's key of the n-gram at a window's start: the window's first n tokens, tagged with n - 1 in bits 60..61
+__device__ __forceinline__ uint64_t ngram_key(uint64_t win, int n) {
+  const int drop = 15 * (4 - n);
+  return ((uint64_t)(n - 1) << 60) | ((win >> drop) << drop);
+}
+
+// idf of a key: the table's value, or log N for an n-gram no document holds (df 0 -> log max(1, 0) = 0)
+__device__ inline float lookup_idf(uint64_t key, const uint64_t* keys, const float* idf, long n_keys, float log_n) {
+  long lo = 0, hi = n_keys;
+  while (lo < hi) {
+    const long mid = (lo + hi) >> 1;
+    if (keys[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return (lo < n_keys && keys[lo] == key) ? idf[lo] : log_n;
 }
 
 }  // namespace gic

@@ -25,7 +25,7 @@ constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / WAVE;
 constexpr int kMaxLen = GIC_CIDER_MAX_LEN;          // = WAVE: lane p is position p
 constexpr int kMaxRefs = GIC_CIDER_MAX_REFS;
-constexpr float kTwoSigma2 = 2.f * 6.f * 6.f;      // sigma = 6
+constexpr float kTwoSigma2 = kCiderTwoSigma2;
 static_assert(kMaxLen == WAVE, "a caption position is a lane");
 
 struct CiderArgs {
@@ -35,25 +35,12 @@ struct CiderArgs {
   float* scores;
 };
 
-__device__ __forceinline__ uint64_t ngram_key(uint64_t win, int n) {
-  const int drop = 15 * (4 - n);
-  return ((uint64_t)(n - 1) << 60) | ((win >> drop) << drop);
-}
-
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
   const unsigned lo = (unsigned)__shfl((int)(unsigned)v, src, WAVE), hi = (unsigned)__shfl((int)(unsigned)(v >> 32), src, WAVE);
   return ((uint64_t)hi << 32) | lo;
 }
 
-// idf of a key: the table's value, or log N for an n-gram no document holds (df 0 -> log max(1, 0) = 0)
-__device__ float lookup_idf(uint64_t key, const CiderArgs& a) {
-  long lo = 0, hi = a.K;
-  while (lo < hi) {
-    const long mid = (lo + hi) >> 1;
-    if (a.keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return (lo < a.K && a.keys[lo] == key) ? a.idf[lo] : a.log_n;
-}
+__device__ __forceinline__ float lookup_idf(uint64_t key, const CiderArgs& a) { return gic::lookup_idf(key, a.keys, a.idf, a.K, a.log_n); }
 
 __global__ __launch_bounds__(kThreads) void cider_d_kernel(const CiderArgs a) {
   __shared__ int rtok[kMaxRefs][kMaxLen + 4];

@@ -637,6 +637,30 @@ def cider_d(cand_ids: torch.Tensor, cand_len: torch.Tensor, cand_img: torch.Tens
     return scores
 
 
+def cider_pairwise(ids: torch.Tensor, lengths: torch.Tensor, keys: torch.Tensor, idf: torch.Tensor, log_n: float, V: int,
+                   want_matrix: bool = True, want_consensus: bool = True, want_self_cider: bool = True) -> dict:
+    """gic_cider_pairwise: CIDEr-D among the K captions of each image, ids int64 [B, K, L] with lengths int [B, K], under the
+    document-frequency table of ``cider_d``.  Returns {"matrix": f32 [B, K, K] (caption i as the candidate against caption j as the
+    single reference), "consensus": f32 [B, K] (the row mean without the diagonal), "self_cider": f32 [B]}; an output that is not
+    wanted is None and is not computed.  One launch, no host sync."""
+    require_gpu(ids, lengths, keys, idf)
+    if ids.dim() != 3 or ids.dtype != torch.int64:
+        raise ValueError("cider_pairwise: ids must be int64 [B, K, L]")
+    B, K, Lc = ids.shape
+    if tuple(lengths.shape) != (B, K):
+        raise ValueError(f"cider_pairwise: lengths must be [B={B}, K={K}]")
+    if not (want_matrix or want_consensus or want_self_cider):
+        raise ValueError("cider_pairwise: no output wanted")
+    ids, lengths, dev = ids.contiguous(), lengths.to(torch.int32).contiguous(), ids.device
+    out = {"matrix": torch.empty(B, K, K, device=dev, dtype=torch.float32) if want_matrix else None,
+           "consensus": torch.empty(B, K, device=dev, dtype=torch.float32) if want_consensus else None,
+           "self_cider": torch.empty(B, device=dev, dtype=torch.float32) if want_self_cider else None}
+    L.check(L.load().gic_cider_pairwise(ptr(ids), Lc, ptr(lengths), B, K, Lc, ptr(keys.contiguous()), ptr(idf.contiguous()), keys.numel(),
+                                        float(log_n), int(V), ptr(out["matrix"]), ptr(out["consensus"]), ptr(out["self_cider"]),
+                                        stream_ptr()), "gic_cider_pairwise")
+    return out
+
+
 def caption_overlap(cand_ids: torch.Tensor, cand_len: torch.Tensor, cand_img: torch.Tensor, ref_ids: torch.Tensor, ref_len: torch.Tensor,
                     ref_off: torch.Tensor, max_refs: int, V: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """gic_caption_overlap: (stats int32 [n_cand, 10], ROUGE-L f32 [n_cand], smoothed sentence BLEU-4 f32 [n_cand]) of candidates int64

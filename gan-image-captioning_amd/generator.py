@@ -754,8 +754,8 @@ class Generator(nn.Module):
         self.init_params()
 
     def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False, return_alphas=False,
-                beam_groups=1, diversity=0.0, rerank_disc=None, rerank_weight=1.0, return_rerank=False, no_repeat_ngram=0, min_length=0,
-                suppress_tokens=()):
+                beam_groups=1, diversity=0.0, rerank_disc=None, rerank_weight=1.0, return_rerank=False, consensus=None, consensus_weight=1.0,
+                return_consensus=False, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """Captions for ``images`` by beam search: features as the trainer forms them (training.py:66-68) -- the encoder in the
         module's current mode, or embed(<S>) with --conditional-gan 0 -- under no-grad, then ``decoder.beam_search``.  With
         --decoder attention the encoder also gives the feature map, and ``return_alphas`` appends the attention weights
@@ -765,7 +765,11 @@ class Generator(nn.Module):
         score / max(len, 1) ** length_penalty + ``rerank_weight`` * rerank_disc.score (discriminator.rerank: a conditioned D scores them
         against this call's pooled trunk features, any other D the captions alone); the best caption, or all beams with
         ``return_beams``, come in the new order, the attention weights with them; ``scores`` stay G's log-probabilities.
-        ``return_rerank`` appends (final [B, k], d [B, k]) in the new order."""
+        ``return_rerank`` appends (final [B, k], d [B, k]) in the new order.
+        ``consensus`` (a CiderD; None = nothing else runs): consensus (minimum-Bayes-risk) selection instead -- the beams are re-ranked by
+        score / max(len, 1) ** length_penalty + ``consensus_weight`` * each beam's mean CIDEr-D against the other beams
+        (CiderD.pairwise, then the same gic_rerank: its order, tie rule and outputs); ``return_consensus`` appends (final [B, k],
+        consensus [B, k]) in the new order.  One re-ranking at a time: ``consensus`` with ``rerank_disc`` is refused."""
         kw = dict(beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id, length_penalty=length_penalty, return_beams=return_beams,
                   beam_groups=beam_groups, diversity=diversity, no_repeat_ngram=no_repeat_ngram, min_length=min_length,
                   suppress_tokens=suppress_tokens)
@@ -773,21 +777,41 @@ class Generator(nn.Module):
             raise ValueError("attention weights exist for --decoder attention only")
         if rerank_disc is None and return_rerank:
             raise ValueError("return_rerank needs rerank_disc")
+        self._check_consensus(consensus, rerank_disc, return_consensus)
         with torch.no_grad():
             features, fmap = self._features(images)
-            if rerank_disc is not None:
+            if rerank_disc is not None or consensus is not None:
                 kw["return_beams"] = True
             if fmap is None:
                 out = self.decoder.beam_search(features, **kw)
             else:
                 out = self.decoder.beam_search(features, fmap, return_alphas=return_alphas, **kw)
-            if rerank_disc is None:
+            if rerank_disc is None and consensus is None:
                 return out
-            r = self._rerank(rerank_disc, out, rerank_weight, length_penalty)
+            if consensus is not None:
+                r = self._rerank_consensus(consensus, out, consensus_weight, length_penalty)
+            else:
+                r = self._rerank(rerank_disc, out, rerank_weight, length_penalty)
         res = (r["ids"], r["scores"], r["lengths"]) + ((r["alphas"],) if return_alphas else ())
         if not return_beams:
             res = tuple(t[:, 0] for t in res)
-        return res + (((r["final"], r["d"]),) if return_rerank else ())
+        return res + (((r["final"], r["d"]),) if return_rerank or return_consensus else ())
+
+    @staticmethod
+    def _check_consensus(consensus, rerank_disc, return_consensus=False):
+        if consensus is not None and rerank_disc is not None:
+            raise ValueError("consensus with rerank_disc: one re-ranking at a time")
+        if consensus is None and return_consensus:
+            raise ValueError("return_consensus needs consensus")
+
+    @staticmethod
+    def _rerank_consensus(scorer, cands, weight, length_penalty=0.0):
+        """engine.rerank of this call's candidates (ids, scores, lengths[, alphas]) with each candidate's consensus -- its mean CIDEr-D
+        against the image's other candidates (``scorer``: a CiderD) -- in the place of D's score (R = 1): ``d`` of the result."""
+        ids, scores, lengths = cands[0], cands[1], cands[2]
+        cons = scorer.pairwise(ids, lengths, want_matrix=False, want_self_cider=False)["consensus"]
+        return engine.rerank(scores, lengths, cons.view(-1), 1, float(weight), float(length_penalty), ids=ids,
+                             alphas=cands[3] if len(cands) > 3 else None)
 
     def _rerank(self, disc, cands, weight, length_penalty=0.0):
         """discriminator.rerank of this call's candidates (ids, scores, lengths[, alphas]) against this call's pooled trunk features."""
@@ -801,20 +825,23 @@ class Generator(nn.Module):
                       alphas=cands[3] if len(cands) > 3 else None)
 
     def sample_captions(self, images, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
-                        noise_u=None, rerank_disc=None, rerank_weight=1.0, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
+                        noise_u=None, rerank_disc=None, rerank_weight=1.0, consensus=None, consensus_weight=1.0, no_repeat_ngram=0,
+                        min_length=0, suppress_tokens=()):
         """``num_samples`` sampled captions per image (decoder.sample_captions), with the features formed as ``caption`` forms them:
         the encoder in the module's current mode, or embed(<S>) with --conditional-gan 0, under no-grad; with --decoder attention the
         encoder also gives the feature map.  ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: decode constraints
         (Decoder.sample_captions).  Returns (ids [B, n, L], scores [B, n], lengths [B, n]) in draw order; with ``rerank_disc``
-        (best-of-n) ordered by scores + ``rerank_weight`` * rerank_disc.score instead (``caption``)."""
+        (best-of-n) ordered by scores + ``rerank_weight`` * rerank_disc.score instead, with ``consensus`` (a CiderD) by scores +
+        ``consensus_weight`` * each sample's mean CIDEr-D against the other samples (``caption``); not both."""
         kw = dict(num_samples=num_samples, top_k=top_k, top_p=top_p, temperature=temperature, max_caption_len=max_caption_len,
                   eos_id=eos_id, seed=seed, noise_u=noise_u, no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
+        self._check_consensus(consensus, rerank_disc)
         with torch.no_grad():
             features, fmap = self._features(images)
             out = self.decoder.sample_captions(features, *(() if fmap is None else (fmap,)), **kw)
-            if rerank_disc is None:
+            if rerank_disc is None and consensus is None:
                 return out
-            r = self._rerank(rerank_disc, out, rerank_weight)
+            r = self._rerank_consensus(consensus, out, consensus_weight) if consensus is not None else self._rerank(rerank_disc, out, rerank_weight)
         return r["ids"], r["scores"], r["lengths"]
 
     def score_captions(self, images, ids, lengths):

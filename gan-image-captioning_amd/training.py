@@ -520,6 +520,11 @@ class GANInstructor:
                 self.evaluate_diverse_beam("val", beam_size=int(self.args.eval_diverse_beam_size),
                                            groups=int(getattr(self.args, "eval_diverse_groups", 2)),
                                            diversity=float(getattr(self.args, "eval_diversity_strength", 0.5)))
+            if int(getattr(self.args, "eval_consensus_samples", 0)) > 0 and self.dist.rank == 0:
+                self.evaluate_consensus("val", num_samples=int(self.args.eval_consensus_samples), top_k=int(getattr(self.args, "eval_top_k", 0)),
+                                        top_p=float(getattr(self.args, "eval_top_p", 1.0)),
+                                        temperature=float(getattr(self.args, "eval_sample_temperature", 1.0)),
+                                        weight=float(getattr(self.args, "eval_consensus_weight", 1.0)))
             self.writer.flush()
 
     def evaluate(self, what="val", beam_size=3, max_caption_len=None, batch_size=None):
@@ -838,6 +843,49 @@ class GANInstructor:
                       " | distinct-2 %.4f | vocab %d", what, beam_size, groups, diversity, out["bleu4"], out["mbleu4"],
                       out["distinct1"], out["distinct2"], out["vocab"])
         self._write_diversity(out, what, ("BLEU4DBS", "mBLEU4DBS", "Distinct1DBS", "Distinct2DBS", "VocabDBS"))
+        return out
+
+    def evaluate_consensus(self, what="val", num_samples=8, top_k=0, top_p=1.0, temperature=1.0, weight=1.0, seed=1234, max_caption_len=None,
+                           batch_size=None):
+        """Consensus (minimum-Bayes-risk) selection among ``num_samples`` sampled captions per image, and their Self-CIDEr diversity, on
+        the images, grouping, caption length rule and decode constraints of ``evaluate``, all scored on the GPU.  Per batch: one
+        sample_captions pass, one gic_cider_pairwise launch (each sample's consensus = its mean CIDEr-D against the image's other
+        samples, and the set's Self-CIDEr), the pick = the first of gic_rerank's order under log-probability + ``weight`` * consensus,
+        and one gic_cider_d launch (the scorer of ``evaluate_cider``) over the first draw and the pick.  Returns {"cider_d_first": the
+        mean CIDEr-D of the first draw, "cider_d_consensus": of the pick, "self_cider": the mean Self-CIDEr}; the sums accumulate on
+        the device and are read with one sync at the end.  Logs them on one line and writes the scalars ``CIDErDFirst_<what>``,
+        ``CIDErDConsensus_<what>`` and ``SelfCIDEr_<what>``.  ``seed`` fixes the draws."""
+        from .cider import CiderD, RefBatch
+        from .tasks import ImageGroups
+        dev = self.args.device
+        if what not in self._cider:                                          # the scorer of evaluate_cider, and its cache
+            ds = self.dev_dataset if what == "val" else self.train_dataset
+            self._cider[what] = CiderD(ImageGroups(ds).references(), self.args.vocab_size, dev)
+        scorer = self._cider[what]
+        drawn = {}
+
+        def decode(images, L, bi):
+            ids, drawn["scores"], lengths = self.gen.sample_captions(images, num_samples=num_samples, top_k=top_k, top_p=top_p,
+                                                                     temperature=temperature, max_caption_len=L, seed=int(seed) + bi,
+                                                                     **self._eval_constraints())
+            return ids, lengths
+        sums = torch.zeros(3, dtype=torch.float64, device=dev)              # CIDEr-D of the first draw, of the pick, Self-CIDEr
+        n_images = 0
+        for ids, lengths, caps in self._decode_batches(what, decode, max_caption_len, batch_size):
+            pw = scorer.pairwise(ids, lengths, want_matrix=False)
+            r = engine.rerank(drawn["scores"], lengths, pw["consensus"].view(-1), 1, float(weight), 0.0, ids=ids)
+            cand = torch.stack([ids[:, 0], r["ids"][:, 0]], 1)
+            cand_len = torch.stack([lengths[:, 0], r["lengths"][:, 0]], 1)
+            cd = scorer.score(cand, cand_len, RefBatch.pack(caps).to(dev))
+            sums += torch.cat([cd.double().sum(0), pw["self_cider"].double().sum().view(1)])
+            n_images += ids.shape[0]
+        first, picked, self_cider = (sums / max(n_images, 1)).tolist()         # the one sync
+        out = {"cider_d_first": first, "cider_d_consensus": picked, "self_cider": self_cider}
+        self.log.info("[EVAL] consensus (%s, n %d, top-k %d, top-p %.3f, temperature %.3f, weight %g): CIDEr-D first %.4f | CIDEr-D consensus"
+                      " %.4f | Self-CIDEr %.4f", what, num_samples, top_k, top_p, temperature, weight, first, picked, self_cider)
+        step = max(self.adv_epoch, 0)
+        for name, key in (("CIDErDFirst", "cider_d_first"), ("CIDErDConsensus", "cider_d_consensus"), ("SelfCIDEr", "self_cider")):
+            self.writer.add_scalar(f"{name}_{what}", out[key], step)
         return out
 
     def _diversity(self, what, decode, max_caption_len, batch_size):

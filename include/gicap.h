@@ -940,6 +940,26 @@ int gic_cider_d(const int64_t* cand_ids, int64_t ld_cand, const int32_t* cand_le
                 int32_t B, int32_t max_refs, const uint64_t* keys, const float* idf, int64_t K, float log_n, int32_t V, float* scores,
                 void* stream);
 
+/* Pairwise CIDEr-D among the K captions of each image (no reference counterpart; an addition to ABI v5), for
+ * consensus (minimum-Bayes-risk) selection and the Self-CIDEr diversity of Wang & Chan (CVPR 2019).  ids int64 [B, K, ld_ids] (row:
+ * L ids), lengths int32 [B, K] (clamped to [0, L]); tokens, vectors, idf table, length and sigma exactly as gic_cider_d above.
+ *   matrix     f32 [B, K, K]: M[b,i,j] = the CIDEr-D (0..10) of caption i as the candidate against caption j as the single reference.
+ *              Not symmetric (the clipping min(v_i, v_j) v_j is not); M[b,i,i] = 2.5 * #{n : vec_n of caption i is non-zero}.
+ *   consensus  f32 [B, K]: (1 / (K - 1)) sum_{j != i} M[b,i,j], j ascending; 0 for K = 1.
+ *   self_cider f32 [B]: with S = (M + M^T) / 20, clamp(-ln(lambda_max(S) / trace(S)) / ln K, 0, 1); 0 for K = 1 or trace(S) = 0.
+ *              lambda_max: GIC_CIDER_PAIR_SQUARINGS trace-normalised squarings of S, then the Rayleigh quotient of S at the row sums
+ *              of the power (= 2^squarings power-iteration steps from the all-ones vector), always that many, in a fixed order.
+ * Each output may be NULL (at least one is given).  One workgroup per image, one launch, no workspace, no atomics: two calls give the
+ * same bits, and the deterministic mode accepts every call.  Refused before any launch with GIC_STATUS_INVALID_ARG and a message that
+ * names the argument: K outside 1..GIC_CIDER_PAIR_MAX_K, L outside 1..GIC_CIDER_MAX_LEN, V outside 1..GIC_CIDER_MAX_VOCAB, B < 1,
+ * n_keys < 0, ld_ids < L, NULL ids / lengths / keys / idf (the table only with n_keys > 0), all three outputs NULL, a log_n that is
+ * negative or not finite. */
+#define GIC_CIDER_PAIR_MAX_K 32
+#define GIC_CIDER_PAIR_SQUARINGS 16
+int gic_cider_pairwise(const int64_t* ids, int64_t ld_ids, const int32_t* lengths, int32_t B, int32_t K, int32_t L, const uint64_t* keys,
+                       const float* idf, int64_t n_keys, float log_n, int32_t V, float* matrix, float* consensus, float* self_cider,
+                       void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * N-gram overlap metrics of token-id captions (no reference counterpart): the per-candidate terms of corpus
  * BLEU-1..4 (Papineni et al. 2002, with the semantics of utils.bleu_score), ROUGE-L (Lin 2004, the coco-caption Rouge, beta = 1.2) and an
