@@ -29,9 +29,9 @@ def step(gp, x, z_in, h, c):
     return h, c, h @ gp["decoder.linear.weight"].t() + gp["decoder.linear.bias"]
 
 
-def beam_search(params, features, fmap, k, L, eos_id=2, pad_id=0, length_penalty=0.0, states=None):
+def beam_search(params, features, fmap, k, L, eos_id=2, pad_id=0, length_penalty=0.0, states=None, trace=None):
     """Returns (ids int64 [B, k, L], scores f64 [B, k], lengths int64 [B, k], alphas f64 [B, k, L, P], margins: list of B
-    (selection, order) pairs).  ``states`` = (h0, c0), each [1, B, H] or [B, H]."""
+    (selection, order) pairs).  ``states`` = (h0, c0), each [1, B, H] or [B, H].  ``trace`` as in tests/beam_oracle.py."""
     gp = as_dict(params)
     feats = features.detach().double().cpu()
     fm = fmap.detach().double().cpu()
@@ -57,6 +57,7 @@ def beam_search(params, features, fmap, k, L, eos_id=2, pad_id=0, length_penalty
         alph = [[] for _ in range(k)]
         x = feats[b].repeat(k, 1)
         zero = torch.zeros(P, dtype=torch.float64)
+        pars = []
         for t in range(L):
             if all(fin):
                 for j in range(k):
@@ -79,6 +80,7 @@ def beam_search(params, features, fmap, k, L, eos_id=2, pad_id=0, length_penalty
             if len(cands) > k and cands[k][0] != -math.inf:
                 margin = min(margin, cands[k - 1][0] - cands[k][0])
             par = [e[1] for e in sel]
+            pars.append(par)
             h, c = h[par], c[par]
             new_fin, new_len, new_seqs, new_alph = [], [], [], []
             for (s, j, q, tok) in sel:
@@ -96,6 +98,8 @@ def beam_search(params, features, fmap, k, L, eos_id=2, pad_id=0, length_penalty
             if a_ != -math.inf:
                 order_margin = min(order_margin, abs(a_ - b_))
         margins.append((margin, order_margin))
+        if trace is not None:
+            trace.append(pars)
         for r, j in enumerate(order):
             ids[b, r] = torch.tensor(seqs[j])
             scores[b, r] = score[j]

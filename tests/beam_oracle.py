@@ -19,8 +19,9 @@ def lstm_cell(x, h, c, w_ih, w_hh, b_ih, b_hh):
     return torch.sigmoid(o) * torch.tanh(c), c
 
 
-def beam_search(params, features, k, L, eos_id=2, pad_id=0, length_penalty=0.0, states=None):
-    """Returns (ids int64 [B, k, L], scores f64 [B, k], lengths int64 [B, k], margins: list of B (selection, order) pairs)."""
+def beam_search(params, features, k, L, eos_id=2, pad_id=0, length_penalty=0.0, states=None, trace=None):
+    """Returns (ids int64 [B, k, L], scores f64 [B, k], lengths int64 [B, k], margins: list of B (selection, order) pairs).
+    ``trace``: a list that receives, per image, the chosen parent beams of every step that ran (a list of k-lists)."""
     p = [t.detach().double().cpu() for t in params]
     NL = (len(p) - 3) // 4
     embed, w_out, b_out = p[0], p[-2], p[-1]
@@ -40,6 +41,7 @@ def beam_search(params, features, k, L, eos_id=2, pad_id=0, length_penalty=0.0, 
         ln = [0] * k
         seqs = [[] for _ in range(k)]
         x = feats[b].repeat(k, 1)
+        pars = []
         for t in range(L):
             if all(fin):
                 for j in range(k):
@@ -65,6 +67,7 @@ def beam_search(params, features, k, L, eos_id=2, pad_id=0, length_penalty=0.0, 
             if len(cands) > k and cands[k][0] != -math.inf:
                 margin = min(margin, cands[k - 1][0] - cands[k][0])
             par = [e[1] for e in sel]
+            pars.append(par)
             h = [hl[par] for hl in h]
             c = [cl[par] for cl in c]
             new_fin, new_len, new_seqs = [], [], []
@@ -82,6 +85,8 @@ def beam_search(params, features, k, L, eos_id=2, pad_id=0, length_penalty=0.0, 
             if a_ != -math.inf:
                 order_margin = min(order_margin, abs(a_ - b_))
         margins.append((margin, order_margin))
+        if trace is not None:
+            trace.append(pars)
         for r, j in enumerate(order):
             ids[b, r] = torch.tensor(seqs[j])
             scores[b, r] = score[j]

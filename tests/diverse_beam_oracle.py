@@ -35,7 +35,7 @@ def select_group(score, fin, logits, logp, rows, k, kg, lam, h, pad_id):
     return [(e[0], e[1], e[3], e[4], e[5]) for e in cands[:kg]], margin
 
 
-def _search_image(stepper, k, G, lam, L, eos_id, pad_id, length_penalty, P=0):
+def _search_image(stepper, k, G, lam, L, eos_id, pad_id, length_penalty, P=0, trace=None):
     kg = k // G
     score = [0.0 if j % kg == 0 else -math.inf for j in range(k)]
     fin = [False] * k
@@ -44,6 +44,7 @@ def _search_image(stepper, k, G, lam, L, eos_id, pad_id, length_penalty, P=0):
     alph = [[] for _ in range(k)]
     zero = torch.zeros(P, dtype=torch.float64)
     margin = order_margin = math.inf
+    pars = []
     for t in range(L):
         if all(fin):
             for j in range(k):
@@ -69,7 +70,10 @@ def _search_image(stepper, k, G, lam, L, eos_id, pad_id, length_penalty, P=0):
             new_alph.append(alph[j] + [zero if (fin[j] or alpha is None) else alpha[j]])
         score = [e[0] for e in sel]
         fin, ln, seqs, alph = new_fin, new_len, new_seqs, new_alph
+        pars.append([e[1] for e in sel])
         stepper.reorder([e[1] for e in sel], [e[3] for e in sel])
+    if trace is not None:
+        trace.append(pars)
     norm = [score[j] / (ln[j] ** length_penalty) for j in range(k)]
     order = []
     for g in range(G):
@@ -142,9 +146,9 @@ def _collect(results, B, k, L, P=None):
     return ids, scores, lengths, alphas, margins
 
 
-def diverse_beam_search(params, features, k, groups, diversity, L, eos_id=2, pad_id=0, length_penalty=0.0, states=None):
+def diverse_beam_search(params, features, k, groups, diversity, L, eos_id=2, pad_id=0, length_penalty=0.0, states=None, trace=None):
     """The LSTM decoder (beam_oracle's parameter order).  Returns (ids int64 [B, k, L], scores f64 [B, k], lengths int64 [B, k],
-    margins: list of B (selection, order) pairs), in group-major order."""
+    margins: list of B (selection, order) pairs), in group-major order.  ``trace`` as in tests/beam_oracle.py."""
     p = [t.detach().double().cpu() for t in params]
     feats = features.detach().double().cpu()
     B = feats.shape[0]
@@ -153,12 +157,14 @@ def diverse_beam_search(params, features, k, groups, diversity, L, eos_id=2, pad
         h0 = c0 = None
         if states is not None:
             h0, c0 = states[0][:, b].double().cpu(), states[1][:, b].double().cpu()
-        res.append(_search_image(_LstmStepper(p, feats[b], k, h0, c0), k, groups, diversity, L, eos_id, pad_id, length_penalty))
+        res.append(_search_image(_LstmStepper(p, feats[b], k, h0, c0), k, groups, diversity, L, eos_id, pad_id, length_penalty,
+                                 trace=trace))
     ids, scores, lengths, _, margins = _collect(res, B, k, L)
     return ids, scores, lengths, margins
 
 
-def attn_diverse_beam_search(params, features, fmap, k, groups, diversity, L, eos_id=2, pad_id=0, length_penalty=0.0, states=None):
+def attn_diverse_beam_search(params, features, fmap, k, groups, diversity, L, eos_id=2, pad_id=0, length_penalty=0.0, states=None,
+                             trace=None):
     """The attention decoder (attn_beam_oracle's parameter order).  Returns (ids, scores, lengths, alphas f64 [B, k, L, P], margins)
     as attn_beam_oracle.beam_search, in group-major order."""
     gp = AO.as_dict(params)
@@ -172,5 +178,5 @@ def attn_diverse_beam_search(params, features, fmap, k, groups, diversity, L, eo
         if states is not None:
             h0, c0 = states[0].reshape(B, H)[b].double(), states[1].reshape(B, H)[b].double()
         res.append(_search_image(_AttnStepper(gp, feats[b], fm[b], k, h0, c0), k, groups, diversity, L, eos_id, pad_id, length_penalty,
-                                 P))
+                                 P, trace))
     return _collect(res, B, k, L, P)

@@ -519,7 +519,7 @@ def test_gpu_beam_case_is_decidable_and_binds(case):
     ids, _, lengths, margins = beam_oracle(case)[:4]
     check_invariants(ids, lengths, Lc, cons["no_repeat_ngram"], cons["min_length"], cons["suppress_tokens"])
     clear = sum(1 for sel, _ in margins if sel >= 1e-4)
-    assert 2 * clear >= B, f"{clear} of {B} images with a selection margin >= 1e-4: {margins}"
+    assert 4 * clear >= 3 * B, f"{clear} of {B} images with a selection margin >= 1e-4: {margins}"
     ids, _, lengths = beam_oracle(case, constrained=False)[:3]
     assert _violations(ids, lengths, cons) >= 1, "the unconstrained search already satisfies the constraints: they do not bind"
 
@@ -531,6 +531,6 @@ def test_gpu_sample_case_is_decidable_and_binds(case):
     assert CO.feasible(V, Lc, 1, cons["no_repeat_ngram"], cons["suppress_tokens"])
     ids, _, lengths, margin = sample_oracle(case)
     check_invariants(ids, lengths, Lc, cons["no_repeat_ngram"], cons["min_length"], cons["suppress_tokens"])
-    assert (margin > 1e-5).float().mean() > 0.5, margin
+    assert 4 * int((margin > 1e-5).sum()) >= 3 * margin.numel(), margin
     ids, _, lengths, _ = sample_oracle(case, constrained=False)
     assert _violations(ids, lengths, cons) >= 1, "the unconstrained draws already satisfy the constraints: they do not bind"

@@ -88,8 +88,9 @@ def _check_vs_oracle(eng, params, feats, fmap, p_cpu, f_cpu, m_cpu, L, k, alpha=
     ids_c, sc_c, len_c, al_c = ids.cpu(), scores.cpu().double(), lengths.cpu().long(), alphas.cpu().double()
     norm = sc_c / len_c.double() ** alpha
     assert (norm[:, :-1] >= norm[:, 1:] - 1e-6 * norm.abs()[:, 1:]).all()
+    # (at least 3/4 of the batch: every case of this file has a clear selection in every image of the oracle's run)
     ok = [b for b, (sel, _) in enumerate(margins) if sel >= 1e-4]
-    assert ok, f"no image with a clear selection to compare: margins {margins}"
+    assert 4 * len(ok) >= 3 * len(margins), f"{len(ok)} of {len(margins)} images with a clear selection to compare: margins {margins}"
     for b in ok:
         if margins[b][1] >= 1e-4:
             assert torch.equal(ids_c[b], rid[b]), b

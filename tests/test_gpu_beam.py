@@ -77,8 +77,9 @@ def _check_vs_oracle(eng, params, feats, L, k, alpha):
     assert (norm[:, :-1] >= norm[:, 1:] - 1e-6 * norm.abs()[:, 1:]).all()
     # images whose surviving hypotheses are decided by >= 1e-4 at every step: f32 keeps the same ones, with the same ids, lengths
     # and scores; where the final order is decided by >= 1e-4 too, in the same order (else compared as sets)
+    # (at least 3/4 of the batch: the count the oracle gives on the CPU -- cfg1 8 of 8, tiny_scaled 4 of 4, 3 of 4 at k = 8)
     ok = [b for b, (sel, _) in enumerate(margins) if sel >= 1e-4]
-    assert ok, f"no image with a clear selection to compare: margins {margins}"
+    assert 4 * len(ok) >= 3 * len(margins), f"{len(ok)} of {len(margins)} images with a clear selection to compare: margins {margins}"
     for b in ok:
         if margins[b][1] >= 1e-4:
             assert torch.equal(ids_c[b], rid[b]), b

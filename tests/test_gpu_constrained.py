@@ -78,7 +78,7 @@ def test_beam_f32_matches_oracle(dev, case):
     else:
         n = _compare(got, want[:3], want[3], k, G)
     print(f"{T._case_id(case)}: {n} of {B} images compared; margins {want[3]}")
-    assert 2 * n >= B, f"{n} of {B} images with a clear selection: margins {want[3]}"
+    assert 4 * n >= 3 * B, f"{n} of {B} images with a clear selection: margins {want[3]}"
 
 
 @pytest.mark.parametrize("case", T.SAMPLE_CASES, ids=T._case_id)
@@ -90,7 +90,7 @@ def test_sample_f32_matches_oracle(dev, case):
     rid, rsc, rlen, margin = T.sample_oracle(case)
     ok = margin > 1e-5
     print(f"{T._case_id(case)}: {int(ok.sum())} of {ok.numel()} rows compared")
-    assert ok.float().mean() > 0.5, margin
+    assert 4 * int(ok.sum()) >= 3 * ok.numel(), margin
     assert torch.equal(ids.cpu()[ok], rid[ok])
     assert torch.equal(lengths.cpu().long()[ok], rlen[ok])
     torch.testing.assert_close(scores.cpu().double()[ok], rsc[ok], rtol=1e-5, atol=1e-4)

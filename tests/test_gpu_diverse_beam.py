@@ -101,7 +101,8 @@ def test_lstm_f32_matches_oracle(dev, case, k, G, lam, alpha):
     _group_order(got[1], got[2], G, alpha)
     rid, rsc, rlen, margins = DO.diverse_beam_search([p.cpu() for p in params], feats.cpu(), k, G, lam, L, length_penalty=alpha)
     n = _compare(got, (rid, rsc, rlen), margins, k, G)
-    assert n >= 1, f"no image with a clear selection to compare: margins {margins}"
+    # (at least 3/4 of the batch: the oracle gives every image but for 3 of 4 at generic (8, 4) and 6 of 8 at fused (6, 2), (8, 4))
+    assert 4 * n >= 3 * m["B"], f"{n} of {m['B']} images with a clear selection to compare: margins {margins}"
 
 
 ATTN_CASES = [(2, 2, 1.0, 0.0), (4, 2, 0.5, 0.7), (6, 3, 2.0, 0.0), (8, 8, 0.7, 0.7), (8, 4, 1.5, 0.0)]
@@ -118,7 +119,7 @@ def test_attn_f32_matches_oracle(dev, k, G, lam, alpha):
     _group_order(got[1], got[2], G, alpha)
     rid, rsc, rlen, ral, margins = DO.attn_diverse_beam_search(p_cpu, f_cpu, m_cpu, k, G, lam, L, length_penalty=alpha)
     n = _compare(got, (rid, rsc, rlen), margins, k, G, got[3], ral)
-    assert n >= 1, f"no image with a clear selection to compare: margins {margins}"
+    assert 4 * n >= 3 * shape[0], f"{n} of {shape[0]} images with a clear selection to compare: margins {margins}"
 
 
 @pytest.mark.parametrize("dt", [0, 1], ids=["f32", "bf16"])
@@ -273,8 +274,8 @@ def test_early_stop(dev):
         torch.cuda.synchronize()
         want = DO.diverse_beam_search([p.cpu() for p in params], feats.cpu(), k, G, 0.5, 12)
         awant = DO.attn_diverse_beam_search(p_cpu, f_cpu, m_cpu, k, G, 0.5, shape[1])
-        assert _compare(got, want[:3], want[3], k, G) >= m["B"] // 2
-        assert _compare(agot, awant[:3], awant[4], k, G, agot[3], awant[3]) >= shape[0] // 2
+        assert 4 * _compare(got, want[:3], want[3], k, G) >= 3 * m["B"]
+        assert 4 * _compare(agot, awant[:3], awant[4], k, G, agot[3], awant[3]) >= 3 * shape[0]
         for ids, lengths in ((got[0], got[2]), (agot[0], agot[2])):
             assert int(lengths.max()) < ids.shape[2], lengths
             pos = torch.arange(ids.shape[2], device=dev)[None, None]
