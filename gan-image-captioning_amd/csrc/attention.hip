@@ -257,12 +257,9 @@ int attn_fwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S
     g.M = B * c.P; g.N = c.A; g.K = c.C; g.in_dtype = c.dt; g.out_dtype = c.dt; g.bias = P->b_f;
     GIC_PROPAGATE(gemm(g, stream));
   }
-  const int nblk = cdiv(V, kVocabTile);
-  const long per = (long)L * B * nblk;
-  float* part_m = st->part;
-  float* part_s = st->part + per;
-  unsigned long long* rowkey = (unsigned long long*)(st->part + ((2 * per + 1) & ~1l));
-  GIC_PROPAGATE(fill_zero(rowkey, (size_t)L * B * sizeof(unsigned long long), stream));
+  const StepScratch sc = decoder_step_scratch(st->part, B, L, V);
+  const StepDraw draw{noise_u, seed, temperature, pretrain, t_dev, seed_dev, out, ids};
+  GIC_PROPAGATE(fill_zero(sc.rowkey, sc.key_bytes(), stream));
   const size_t lds = (size_t)(c.A + c.P) * sizeof(float);
   static LdsGrant granted;
   if (!grant_lds(attn_fwd_kernel<TA>, lds, granted)) {
@@ -291,21 +288,14 @@ int attn_fwd_t(const ACtx& c, const gic_attn_params* P, const gic_attn_shadow* S
     a.gates = st->gates + (long)t * B * 4 * H;
     a.h_out = (TA*)st->hout + (long)t * H; a.ld_out = (long)L * H;
     a.B = B; a.H = H; a.din = c.din(); a.ldx = ld; a.gw = E;
-    if (t > 0) { a.gather = 1; a.embed = P->embed; a.V = V; a.rowkey = rowkey + (long)(t - 1) * B; a.tprev = t - 1; }
+    if (t > 0) { a.gather = 1; a.embed = P->embed; a.V = V; a.rowkey = sc.keys(t - 1); a.tprev = t - 1; }
     GIC_PROPAGATE(lstm_step(a, c.dt, stream));
-    VocabStepArgs v;
-    v.h = xh_t + (long)B * ld + c.din(); v.ldh = ld; v.wout = S->wout; v.bias = P->b_out;
-    v.u = noise_u ? noise_u + (long)t * B * V : nullptr;
-    v.seed = seed; v.rng_stream = (uint64_t)t; v.temperature = temperature; v.pretrain = pretrain;
-    v.t_dev = t_dev; v.seed_dev = seed_dev;
-    v.out = (TA*)out + (long)t * V; v.out_stride = (long)L * V;
-    v.part_m = part_m + (long)t * B * nblk; v.part_s = part_s + (long)t * B * nblk; v.rowkey = rowkey + (long)t * B;
-    v.nblk = nblk; v.B = B; v.V = V; v.H = H;
+    VocabStepArgs v = step_vocab_args(sc, draw, t, c.dt);
+    v.h = xh_t + (long)B * ld + c.din(); v.ldh = ld; v.wout = S->wout; v.bias = P->b_out; v.H = H;
     GIC_PROPAGATE(vocab_step(v, c.dt, stream));
   }
-  SampleFinishArgs f;
-  f.part_m = part_m; f.part_s = part_s; f.rowkey = rowkey; f.nblk = nblk; f.B = B; f.L = L; f.V = V; f.E = E;
-  f.pretrain = pretrain; f.out = out; f.ids = ids; f.embed = P->embed; f.xh0 = st->xh; f.ldx0 = ld;
+  SampleFinishArgs f = step_finish_args(sc, draw, E);
+  f.embed = P->embed; f.xh0 = st->xh; f.ldx0 = ld;
   return sample_finish(f, c.dt, stream);
 }
 

@@ -1,6 +1,6 @@
 // The attention kernels of a caption decode step (beam.h attn_step): the split attention step of every decode but the training
 // roll-out's (attention.hip).  decode.hip's step loop drives them for gic_attn_beam_search, gic_attn_diverse_beam_search and
-// gic_attn_sample_captions, attn_tf.hip's loop for gic_attn_forward_tf.  Rows = B * k (row r = image r / k, beam r % k).  One step:
+// gic_attn_sample_captions, teacher_forced.hip's AttnTf recurrence for gic_attn_forward_tf.  Rows = B * k (row r = image r / k, beam r % k).  One step:
 //   hp GEMM          hp [rows, A] = h W_h^T over the rows of the current slot, before the reorder (the library GEMM, never split over K)
 //   attn_step_energy e[r, i] = w_a . tanh(fp_i + hp[parent[r]]): workgroup = (image, 8 positions); each fp piece it loads feeds the k beams
 //   attn_step_ctx    alpha = softmax_i e[r, :], z_r = sum_i alpha_ri a_i: workgroup = (image, 32 channel pieces); every workgroup of an image

@@ -1,4 +1,7 @@
-// Generator hot loop: Decoder.sample forward / backward (reference src/generator.py:55-96).
+// Generator hot loop: Decoder.sample forward / backward (reference src/generator.py:55-96): the sampled roll-out (fused and generic),
+// its backward, the argmax / softmax kernels, the one generic LSTM cell kernel (lstm_pointwise_fwd: the roll-outs, decode.hip's
+// LstmGeneric and, with lengths, teacher_forced.hip's LSTM recurrence), prepare and the size queries.  The teacher-forced decode
+// (Decoder.forward) is teacher_forced.hip.
 //
 // Layout (DESIGN.md "decoder"): the recurrent side is time-major -- per layer one
 // XH buffer [(L+1), B, Din+H] holding [LSTM input | previous hidden] so that step t's
@@ -17,17 +20,32 @@ namespace {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
-// ---- LSTM pointwise forward: gates pre-activation [B,4H] (i,f,g,o blocks) -> gates, c, h (3 destinations)
+// ---- LSTM pointwise forward: gates pre-activation [B,4H] (i,f,g,o blocks) -> gates, c, h (3 destinations).  With lengths
+// (teacher-forced decode, pack_padded_sequence semantics; null: every row is live) a row with t >= lengths[b] keeps (h, c) -- h_prev
+// copied into h_next and h_up -- and writes a zero h_out row and zero gates
 template <typename TA>
 __global__ void lstm_pointwise_fwd_kernel(const float* __restrict__ gpre, const float* __restrict__ c_prev,
                                           float* __restrict__ gates, float* __restrict__ c_new,
                                           TA* __restrict__ h_next, long ld_next,      // XH_l[t+1][:, Din:]
                                           TA* __restrict__ h_up, long ld_up,          // XH_{l+1}[t][:, :H] or null
                                           TA* __restrict__ h_out, long ld_out,        // hout[b, t, :] or null
-                                          int B, int H) {
+                                          int B, int H, const int32_t* __restrict__ lengths, int t,
+                                          const TA* __restrict__ h_prev, long ld_prev) {     // XH_l[t][:, Din:], read with lengths only
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * H) return;
   const int b = idx / H, j = idx % H;
+  if (lengths && t >= lengths[b]) {
+    if (gates) {                       // never weighted by a non-zero gradient: finite is all that matters
+      float* go = gates + (long)b * 4 * H;
+      go[j] = 0.f; go[H + j] = 0.f; go[2 * H + j] = 0.f; go[3 * H + j] = 0.f;
+    }
+    c_new[idx] = c_prev[idx];
+    const TA hp = h_prev[(long)b * ld_prev + j];
+    h_next[(long)b * ld_next + j] = hp;
+    if (h_up) h_up[(long)b * ld_up + j] = hp;
+    if (h_out) h_out[(long)b * ld_out + j] = from_f32<TA>(0.f);
+    return;
+  }
   const float* g = gpre + (long)b * 4 * H;
   const float i_ = sigmoidf_(g[j]);
   const float f_ = sigmoidf_(g[H + j]);
@@ -363,24 +381,8 @@ __global__ __launch_bounds__(256) void rollout_pick_kernel(const unsigned long l
     for (int e = lane; e < E; e += 64) x_next[(long)b * ld_x + e] = from_f32<TA>(embed[(long)id * E + e]);
 }
 
-struct Ctx {
-  int B, L, V, E, H, NL, dt;
-  int din(int l) const { return l == 0 ? E : H; }
-  long ldx(int l) const { return (long)din(l) + H; }
-  size_t asz() const { return (size_t)dtype_size(dt); }
-};
-
-int check_dims(const gic_decoder_dims* d, Ctx& c) {
-  GIC_CHECK_ARG(d, "decoder: null dims");
-  GIC_CHECK_ARG(d->B > 0 && d->L > 0 && d->V > 1 && d->E > 0 && d->H > 0, "decoder: bad dims");
-  GIC_CHECK_ARG(d->NL >= 1 && d->NL <= GIC_MAX_LAYERS, "decoder: gen_num_layers must be 1..%d", GIC_MAX_LAYERS);
-  GIC_CHECK_ARG(d->dtype == DT_F32 || d->dtype == DT_BF16, "decoder: bad dtype");
-  c = Ctx{d->B, d->L, d->V, d->E, d->H, d->NL, d->dtype};
-  return GIC_OK;
-}
-
 // slot 0 of the recurrent buffers: initial (h, c) -- zeros, or the caller's states (generator.py:55,61) -- and features -> x_0
-int init_slot0(const Ctx& c, const gic_decoder_state* st, const float* features, const gic_decoder_sample_opts* opt, hipStream_t stream) {
+int init_slot0(const DCtx& c, const gic_decoder_state* st, const float* features, const gic_decoder_sample_opts* opt, hipStream_t stream) {
   const int B = c.B, E = c.E, H = c.H;
   for (int l = 0; l < c.NL; ++l) {
     if (opt && opt->h0) {
@@ -397,17 +399,16 @@ int init_slot0(const Ctx& c, const gic_decoder_state* st, const float* features,
 
 // The roll-out as two fused launches per step + one finishing launch (decoder_step.h).
 template <typename TA>
-int sample_fwd_fused(const Ctx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
+int sample_fwd_fused(const DCtx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
                      const float* noise_u, uint64_t seed, float temperature, int pretrain, void* out, int64_t* ids,
                      const gic_decoder_sample_opts* opt, hipStream_t stream) {
   const int B = c.B, L = c.L, V = c.V, H = c.H, NL = c.NL;
-  const int nblk = cdiv(V, kVocabTile);
-  const long per = (long)L * B * nblk;
-  float* part_m = st->part;
-  float* part_s = st->part + per;
-  unsigned long long* rowkey = (unsigned long long*)(st->part + ((2 * per + 1) & ~1l));      // [L][B], 8-byte aligned
+  const StepScratch sc = decoder_step_scratch(st->part, B, L, V);
+  const bool dev = opt && opt->dev_scalars;
+  const StepDraw draw{noise_u, seed, temperature, pretrain, dev ? &opt->dev_scalars->temperature : nullptr,
+                      dev ? &opt->dev_scalars->seed[opt->seed_slot] : nullptr, out, ids};
   // atomicMax targets start below every key
-  GIC_PROPAGATE(fill_zero(rowkey, (size_t)L * B * sizeof(unsigned long long), stream));
+  GIC_PROPAGATE(fill_zero(sc.rowkey, sc.key_bytes(), stream));
   const bool keep = !(opt && opt->no_state);
   for (int t = 0; t < L; ++t) {
     for (int l = 0; l < NL; ++l) {
@@ -423,38 +424,29 @@ int sample_fwd_fused(const Ctx& c, const gic_decoder_params* P, const gic_decode
       a.B = B; a.H = H; a.din = c.din(l); a.ldx = ld;
       if (l == 0 && t > 0) {
         a.gather = 1; a.embed = P->embed; a.V = V;
-        a.rowkey = rowkey + (long)(t - 1) * B;
+        a.rowkey = sc.keys(t - 1);
         if (opt && opt->force_ids) { a.force_ids = opt->force_ids; a.force_stride = L; a.force_len = opt->force_len; }
         a.tprev = t - 1;
       }
       GIC_PROPAGATE(lstm_step(a, c.dt, stream));
     }
-    VocabStepArgs v;
+    VocabStepArgs v = step_vocab_args(sc, draw, t, c.dt);
     const int l = NL - 1;
     v.h = (TA*)st->xh[l] + (long)(t + 1) * B * c.ldx(l) + c.din(l); v.ldh = c.ldx(l);
-    v.wout = S->wout; v.bias = P->b_out;
-    v.u = noise_u ? noise_u + (long)t * B * V : nullptr;
-    v.seed = seed; v.rng_stream = (uint64_t)t; v.temperature = temperature; v.pretrain = pretrain;
-    if (opt && opt->dev_scalars) { v.t_dev = &opt->dev_scalars->temperature; v.seed_dev = &opt->dev_scalars->seed[opt->seed_slot]; }
-    v.out = out ? (void*)((TA*)out + (long)t * V) : nullptr; v.out_stride = (long)L * V;
-    v.part_m = part_m + (long)t * B * nblk; v.part_s = part_s + (long)t * B * nblk; v.rowkey = rowkey + (long)t * B;
-    v.nblk = nblk; v.B = B; v.V = V; v.H = H;
+    v.wout = S->wout; v.bias = P->b_out; v.H = H;
     GIC_PROPAGATE(vocab_step(v, c.dt, stream));
   }
-  SampleFinishArgs f;
-  f.part_m = part_m; f.part_s = part_s; f.rowkey = rowkey; f.nblk = nblk; f.B = B; f.L = L; f.V = V; f.E = c.E;
-  f.pretrain = pretrain; f.out = out; f.ids = ids;
+  SampleFinishArgs f = step_finish_args(sc, draw, c.E);
   if (opt && opt->force_ids) { f.force_ids = opt->force_ids; f.force_len = opt->force_len; }
   if (keep) { f.embed = P->embed; f.xh0 = st->xh[0]; f.ldx0 = c.ldx(0); }
   return sample_finish(f, c.dt, stream);
 }
 
 template <typename TA>
-int sample_fwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
+int sample_fwd_t(const DCtx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
                  const float* features, const float* noise_u, uint64_t seed, float temperature, int pretrain,
                  void* out, int64_t* ids, const gic_decoder_sample_opts* opt, hipStream_t stream) {
   const int B = c.B, L = c.L, V = c.V, E = c.E, H = c.H, NL = c.NL;
-  const int pw_grid = cdiv((long)B * H, 256);
   GIC_PROPAGATE(init_slot0(c, st, features, opt, stream));
   // up to a few hundred rows the per-step products are latency-bound: the fused step kernels; beyond that (Monte-Carlo
   // roll-out batches) they are large GEMMs and the generic 128-row-tile kernels are the efficient form
@@ -494,7 +486,6 @@ int sample_fwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
       }
       if (M == 0) continue;
     }
-    const int pw_grid_t = cdiv((long)M * H, 256);
     for (int l = 0; l < NL; ++l) {
       const long ld = c.ldx(l);
       TA* xh_t = (TA*)st->xh[l] + (long)t * B * ld;
@@ -505,11 +496,9 @@ int sample_fwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
       GIC_PROPAGATE(gemm(g, stream));
       TA* h_up = (l + 1 < NL) ? (TA*)st->xh[l + 1] + (long)t * B * c.ldx(l + 1) : nullptr;
       TA* h_out = (l + 1 == NL && st->hout) ? (TA*)st->hout + (long)t * H : nullptr;
-      hipLaunchKernelGGL((lstm_pointwise_fwd_kernel<TA>), dim3(pw_grid_t), dim3(256), 0, stream,
-                         (const float*)st->gpre, (const float*)(st->c[l] + (long)t * B * H),
-                         keep ? st->gates[l] + (long)t * B * 4 * H : (float*)nullptr, st->c[l] + (long)(t + 1) * B * H,
-                         xh_n + c.din(l), ld, h_up, h_up ? c.ldx(l + 1) : 0, h_out, (long)L * H, M, H);
-      GIC_CHECK_LAUNCH("lstm_pointwise_fwd");
+      GIC_PROPAGATE(lstm_pointwise_fwd(c.dt, st->gpre, st->c[l] + (long)t * B * H, st->c[l] + (long)(t + 1) * B * H, xh_n + c.din(l), ld, h_up,
+                                       h_up ? c.ldx(l + 1) : 0, M, H, stream, h_out, (long)L * H,
+                                       keep ? st->gates[l] + (long)t * B * 4 * H : nullptr));
     }
     TA* x_next = (TA*)st->xh[0] + (long)(t + 1) * B * c.ldx(0);
     const float* u_t = noise_u ? noise_u + (long)t * B * V : nullptr;
@@ -548,7 +537,7 @@ int sample_fwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_sh
 }
 
 template <typename TA>
-int sample_bwd_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
+int sample_bwd_t(const DCtx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
                  const gic_decoder_bwd_ws* ws, const void* probs, const int64_t* ids, const void* d_out,
                  float temperature, const float* t_dev, int pretrain, const gic_decoder_grads* G, int phases, hipStream_t stream) {
   const int B = c.B, L = c.L, V = c.V, E = c.E, H = c.H, NL = c.NL;
@@ -794,14 +783,15 @@ int rollout_argmax(int dt, float* logits, const float* u, uint64_t seed, uint64_
 }
 
 int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_new, void* h_next, long ld_next, void* h_up, long ld_up,
-                       int rows, int H, hipStream_t stream) {
+                       int rows, int H, hipStream_t stream, void* h_out, long ld_out, float* gates, const int32_t* lengths, int t,
+                       const void* h_prev, long ld_prev) {
   const dim3 grid((unsigned)cdiv((long)rows * H, 256));
   if (dt == DT_F32)
-    hipLaunchKernelGGL((lstm_pointwise_fwd_kernel<float>), grid, dim3(256), 0, stream, gpre, c_prev, (float*)nullptr, c_new, (float*)h_next, ld_next,
-                       (float*)h_up, ld_up, (float*)nullptr, 0l, rows, H);
+    hipLaunchKernelGGL((lstm_pointwise_fwd_kernel<float>), grid, dim3(256), 0, stream, gpre, c_prev, gates, c_new, (float*)h_next, ld_next,
+                       (float*)h_up, ld_up, (float*)h_out, ld_out, rows, H, lengths, t, (const float*)h_prev, ld_prev);
   else
-    hipLaunchKernelGGL((lstm_pointwise_fwd_kernel<bf16_t>), grid, dim3(256), 0, stream, gpre, c_prev, (float*)nullptr, c_new, (bf16_t*)h_next,
-                       ld_next, (bf16_t*)h_up, ld_up, (bf16_t*)nullptr, 0l, rows, H);
+    hipLaunchKernelGGL((lstm_pointwise_fwd_kernel<bf16_t>), grid, dim3(256), 0, stream, gpre, c_prev, gates, c_new, (bf16_t*)h_next, ld_next,
+                       (bf16_t*)h_up, ld_up, (bf16_t*)h_out, ld_out, rows, H, lengths, t, (const bf16_t*)h_prev, ld_prev);
   GIC_CHECK_LAUNCH("lstm_pointwise_fwd");
   return GIC_OK;
 }
@@ -826,89 +816,6 @@ int embed_scatter_time(const float* dx, long ld, const int64_t* ids, float* d_em
   return GIC_OK;
 }
 
-}  // namespace gic
-
-using namespace gic;
-
-// ---- teacher-forced decode (Decoder.forward, generator.py:39-53): inputs known up front, packed-sequence semantics
-// x rows of slots 1..T-1 of XH_0: embed(caps[b, t-1])
-template <typename TA>
-__global__ void embed_rows_tf_kernel(const float* __restrict__ embed, const int64_t* __restrict__ caps, TA* __restrict__ xh0, long ld,
-                                     int B, int Tm1, int E, int V) {
-  const long total = (long)Tm1 * B * E;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int e = (int)(i % E);
-    const long r = i / E;
-    const int b = (int)(r % B), t = (int)(r / B) + 1;
-    long id = caps[(long)b * Tm1 + (t - 1)];
-    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
-    xh0[((long)t * B + b) * ld + e] = from_f32<TA>(embed[id * E + e]);
-  }
-}
-
-// LSTM pointwise with pack_padded_sequence semantics: a row past its length keeps (h, c) and outputs zero
-template <typename TA>
-__global__ void lstm_pointwise_tf_kernel(const float* __restrict__ gpre, const float* __restrict__ c_prev, const TA* __restrict__ h_prev,
-                                         long ld_prev, float* __restrict__ c_new, TA* __restrict__ h_next, long ld_next,
-                                         TA* __restrict__ h_up, long ld_up, TA* __restrict__ h_out, long ld_out,
-                                         const int32_t* __restrict__ lengths, int t, int B, int H, float* __restrict__ gates_out) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= B * H) return;
-  const int b = idx / H, j = idx % H;
-  float* go = gates_out ? gates_out + (long)b * 4 * H + j : nullptr;   // saved for gic_decoder_forward_tf_bwd, laid out as lstm_step saves them
-  if (t >= lengths[b]) {
-    if (go) { go[0] = 0.f; go[H] = 0.f; go[2 * H] = 0.f; go[3 * H] = 0.f; }   // never weighted by a non-zero gradient: finite is all that matters
-    c_new[idx] = c_prev[idx];
-    const TA hp = h_prev[(long)b * ld_prev + j];
-    h_next[(long)b * ld_next + j] = hp;
-    if (h_up) h_up[(long)b * ld_up + j] = hp;
-    if (h_out) h_out[(long)b * ld_out + j] = from_f32<TA>(0.f);
-    return;
-  }
-  const float* g = gpre + (long)b * 4 * H;
-  const float i_ = sigmoidf_(g[j]);
-  const float f_ = sigmoidf_(g[H + j]);
-  const float g_ = tanhf(g[2 * H + j]);
-  const float o_ = sigmoidf_(g[3 * H + j]);
-  const float c = f_ * c_prev[idx] + i_ * g_;
-  const float h = o_ * tanhf(c);
-  if (go) { go[0] = i_; go[H] = f_; go[2 * H] = g_; go[3 * H] = o_; }
-  c_new[idx] = c;
-  h_next[(long)b * ld_next + j] = from_f32<TA>(h);
-  if (h_up) h_up[(long)b * ld_up + j] = from_f32<TA>(h);
-  if (h_out) h_out[(long)b * ld_out + j] = from_f32<TA>(h);
-}
-
-// d_hout [B, Tmax, H]: rows past their sequence's length are pad_packed_sequence's constant zeros (generator.py:45): no gradient reaches the LSTM
-__global__ void zero_past_length_kernel(float* __restrict__ dhout, const int32_t* __restrict__ lengths, int B, int Tmax, int H) {
-  const long total = (long)B * Tmax * H;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long r = i / H;
-    const int b = (int)(r / Tmax), t = (int)(r % Tmax);
-    if (t >= lengths[b]) dhout[i] = 0.f;
-  }
-}
-
-namespace gic {
-
-int embed_rows_tf(int dt, const float* embed, const int64_t* caps, void* xh0, long ld, int B, int Tm1, int E, int V, hipStream_t stream) {
-  if (Tm1 < 1) return GIC_OK;
-  const long total = (long)Tm1 * B * E;
-  const dim3 grid((unsigned)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256));
-  if (dt == DT_F32) hipLaunchKernelGGL((embed_rows_tf_kernel<float>), grid, dim3(256), 0, stream, embed, caps, (float*)xh0, ld, B, Tm1, E, V);
-  else hipLaunchKernelGGL((embed_rows_tf_kernel<bf16_t>), grid, dim3(256), 0, stream, embed, caps, (bf16_t*)xh0, ld, B, Tm1, E, V);
-  GIC_CHECK_LAUNCH("embed_rows_tf");
-  return GIC_OK;
-}
-
-int zero_past_length(float* dhout, const int32_t* lengths, int B, int Tmax, int H, hipStream_t stream) {
-  const long total = (long)B * Tmax * H;
-  hipLaunchKernelGGL(zero_past_length_kernel, dim3((unsigned)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256)), dim3(256), 0, stream,
-                     dhout, lengths, B, Tmax, H);
-  GIC_CHECK_LAUNCH("zero_past_length");
-  return GIC_OK;
-}
-
 int gumbel_softmax_rows(int dt, float* logits, const float* u, uint64_t seed, uint64_t rng_stream, float temperature, int pretrain, void* out,
                         long rows, int V, hipStream_t stream) {
   if (dt == DT_F32)
@@ -923,152 +830,30 @@ int gumbel_softmax_rows(int dt, float* logits, const float* u, uint64_t seed, ui
   return GIC_OK;
 }
 
-namespace {
-
-template <typename TA>
-int forward_tf_t(const Ctx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
-                 const float* features, const int64_t* caps, const int32_t* lengths, int Tmax, const float* noise_u, uint64_t seed,
-                 float temperature, int pretrain, float* logits_ws, void* out, float* h_n, float* c_n, hipStream_t stream,
-                 const gic_sched_sample_opts* ss = nullptr) {
-  const int B = c.B, T = c.L, V = c.V, E = c.E, H = c.H, NL = c.NL;
-  const int pw_grid = cdiv((long)B * H, 256);
-  for (int l = 0; l < NL; ++l) {
-    GIC_PROPAGATE(fill_zero(st->xh[l], (size_t)B * c.ldx(l) * c.asz(), stream));
-    GIC_PROPAGATE(fill_zero(st->c[l], (size_t)B * H * sizeof(float), stream));
-  }
-  GIC_PROPAGATE(cast2d(features, DT_F32, E, st->xh[0], c.dt, c.ldx(0), B, E, stream));
-  GIC_PROPAGATE(embed_rows_tf(c.dt, P->embed, caps, st->xh[0], c.ldx(0), B, T - 1, E, V, stream));
-  // scheduled sampling (gic_decoder_forward_ss): the logits of step t are formed inside the loop and ss_pick decides the x rows of slot
-  // t + 1 from them; the rows it does not replace keep the teacher's embedding written above
-  const bool ss_fused = ss && ss_fused_logits(c.dt, B, V, E, H, NL);
-  if (ss) GIC_PROPAGATE(ss_tail(caps, ss->inputs, ss->replaced, B, T - 1, Tmax - 1, stream));
-  for (int t = 0; t < Tmax; ++t) {
-    for (int l = 0; l < NL; ++l) {
-      const long ld = c.ldx(l);
-      TA* xh_t = (TA*)st->xh[l] + (long)t * B * ld;
-      TA* xh_n = (TA*)st->xh[l] + (long)(t + 1) * B * ld;
-      GemmDesc g;
-      g.A = xh_t; g.lda = ld; g.B = S->wcat[l]; g.ldb = ld; g.C = st->gpre; g.ldc = 4 * H;
-      g.M = B; g.N = 4 * H; g.K = (int)ld; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = S->bsum[l];
-      g.no_split = ss != nullptr;          // the picks are discrete: the same inputs must give the same bits
-      GIC_PROPAGATE(gemm(g, stream));
-      TA* h_up = (l + 1 < NL) ? (TA*)st->xh[l + 1] + (long)t * B * c.ldx(l + 1) : nullptr;
-      TA* h_out = (l + 1 == NL) ? (TA*)st->hout + (long)t * H : nullptr;            // hout viewed as [B, Tmax, H]
-      hipLaunchKernelGGL((lstm_pointwise_tf_kernel<TA>), dim3(pw_grid), dim3(256), 0, stream, (const float*)st->gpre,
-                         (const float*)(st->c[l] + (long)t * B * H), (const TA*)(xh_t + c.din(l)), ld,
-                         st->c[l] + (long)(t + 1) * B * H, xh_n + c.din(l), ld, h_up, h_up ? c.ldx(l + 1) : 0, h_out, (long)Tmax * H,
-                         lengths, t, B, H, st->gates[l] ? st->gates[l] + (long)t * B * 4 * H : nullptr);
-      GIC_CHECK_LAUNCH("lstm_pointwise_tf");
-    }
-    if (ss) {
-      GIC_PROPAGATE(ss_step_logits(c.dt, st->hout, t, Tmax, S->wout, P->b_out, logits_ws, B, V, H, ss_fused, stream));
-      if (t + 1 < Tmax) {
-        SsPickArgs a;
-        a.logits = logits_ws + (long)t * V; a.ld_logits = (long)Tmax * V;
-        a.caps = caps; a.lengths = lengths; a.coin_u = ss->coin_u; a.noise_u = ss->noise_u; a.seed = ss->seed;
-        a.prob = ss->prob; a.pick = ss->pick; a.t = t + 1; a.B = B; a.V = V; a.E = E; a.Tm1 = T - 1;
-        a.embed = P->embed; a.x_next = (TA*)st->xh[0] + (long)(t + 1) * B * c.ldx(0); a.ld_x = c.ldx(0);
-        a.inputs = ss->inputs; a.replaced = ss->replaced;
-        GIC_PROPAGATE(ss_pick(a, c.dt, stream));
-      }
-    }
-  }
-  // one projection over all B*Tmax rows, then (adversarial mode) Gumbel + softmax per row; the draw u is [B, Tmax, V]
-  const long rows = (long)B * Tmax;
-  if (!ss) {
-    GemmDesc g;
-    g.A = st->hout; g.lda = H; g.B = S->wout; g.ldb = H; g.C = logits_ws; g.ldc = V;
-    g.M = (int)rows; g.N = V; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = P->b_out;
-    GIC_PROPAGATE(gemm(g, stream));
-  }
-  GIC_PROPAGATE(gumbel_softmax_rows(c.dt, logits_ws, noise_u, seed, (uint64_t)0x7466, temperature, pretrain, out, rows, V, stream));
-  for (int l = 0; l < NL; ++l) {
-    GIC_PROPAGATE(cast2d((const TA*)st->xh[l] + (long)Tmax * B * c.ldx(l) + c.din(l), c.dt, c.ldx(l), h_n + (long)l * B * H, DT_F32, H, B, H, stream));
-    GIC_PROPAGATE(cast2d(st->c[l] + (long)Tmax * B * H, DT_F32, H, c_n + (long)l * B * H, DT_F32, H, B, H, stream));
-  }
+int check_decoder_dims(const gic_decoder_dims* d, DCtx& c) {
+  GIC_CHECK_ARG(d, "decoder: null dims");
+  GIC_CHECK_ARG(d->B > 0 && d->L > 0 && d->V > 1 && d->E > 0 && d->H > 0, "decoder: bad dims");
+  GIC_CHECK_ARG(d->NL >= 1 && d->NL <= GIC_MAX_LAYERS, "decoder: gen_num_layers must be 1..%d", GIC_MAX_LAYERS);
+  GIC_CHECK_ARG(d->dtype == DT_F32 || d->dtype == DT_BF16, "decoder: bad dtype");
+  c = DCtx{d->B, d->L, d->V, d->E, d->H, d->NL, d->dtype};
   return GIC_OK;
 }
 
-}  // namespace
+// sample_bwd_t's recurrent phase never reads the probabilities, d_out or the ids; the scatter does read the ids
+int decoder_bwd_recurrent(const DCtx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
+                          const gic_decoder_bwd_ws* ws, const int64_t* ids, long ids_stride, const gic_decoder_grads* G, hipStream_t stream) {
+  const int s = (c.dt == DT_F32)
+                    ? sample_bwd_t<float>(c, P, S, st, ws, nullptr, ids, nullptr, 1.f, nullptr, 0, G, GIC_DECODER_BWD_RECURRENT, stream)
+                    : sample_bwd_t<bf16_t>(c, P, S, st, ws, nullptr, ids, nullptr, 1.f, nullptr, 0, G, GIC_DECODER_BWD_RECURRENT, stream);
+  GIC_PROPAGATE(s);
+  return embed_scatter_time((const float*)ws->dxh[0], c.ldx(0), ids, G->embed, c.B, c.L, c.E, c.V, stream, ids_stride);
+}
+
 }  // namespace gic
 
+using namespace gic;
+
 extern "C" {
-
-int gic_decoder_forward_tf(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
-                           const gic_decoder_state* st, const float* features, const int64_t* caps, const int32_t* lengths, int Tmax,
-                           const float* noise_u, uint64_t seed, float temperature, int pretrain, float* logits_ws, int64_t* ids_ws,
-                           void* out, float* h_n, float* c_n, void* stream) {
-  Ctx c;
-  GIC_PROPAGATE(check_dims(dims, c));
-  GIC_CHECK_ARG(P && S && st && features && lengths && logits_ws && ids_ws && out && h_n && c_n, "decoder_forward_tf: null argument");
-  GIC_CHECK_ARG(c.L == 1 || caps, "decoder_forward_tf: caps is null");
-  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "decoder_forward_tf: Tmax must be in 1..L (= caption length + 1)");
-  GIC_CHECK_ARG(P->embed && P->b_out && S->wout && st->hout && st->gpre, "decoder_forward_tf: null buffer");
-  for (int l = 0; l < c.NL; ++l)
-    GIC_CHECK_ARG(st->xh[l] && st->c[l] && S->wcat[l] && S->bsum[l], "decoder_forward_tf: null layer %d buffer", l);
-  if (c.dt == DT_F32)
-    return forward_tf_t<float>(c, P, S, st, features, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, out, h_n, c_n,
-                               (hipStream_t)stream);
-  return forward_tf_t<bf16_t>(c, P, S, st, features, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, out, h_n, c_n,
-                              (hipStream_t)stream);
-}
-
-int gic_decoder_forward_ss_ws_bytes(const gic_decoder_dims* dims, int Tmax, uint64_t* out) {
-  Ctx c;
-  GIC_PROPAGATE(check_dims(dims, c));
-  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "decoder_forward_ss_ws_bytes: Tmax must be in 1..L (= caption length + 1)");
-  GIC_CHECK_ARG(out, "decoder_forward_ss_ws_bytes: null out");
-  *out = (((uint64_t)c.B * Tmax * c.V * sizeof(float)) + 15) & ~(uint64_t)15;        // the f32 logits [B, Tmax, V]
-  return GIC_OK;
-}
-
-int gic_decoder_forward_ss(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
-                           const gic_decoder_state* st, const float* features, const int64_t* caps, const int32_t* lengths, int Tmax,
-                           const gic_sched_sample_opts* opts, void* ws, void* out, float* h_n, float* c_n, void* stream) {
-  Ctx c;
-  GIC_PROPAGATE(check_dims(dims, c));
-  GIC_CHECK_ARG(P && S && st && features && lengths && opts && ws && out && h_n && c_n, "decoder_forward_ss: null argument");
-  GIC_CHECK_ARG(c.L == 1 || caps, "decoder_forward_ss: caps is null");
-  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "decoder_forward_ss: Tmax must be in 1..L (= caption length + 1)");
-  GIC_PROPAGATE(ss_check_opts(opts, c.L, "decoder_forward_ss"));
-  GIC_CHECK_ARG(((uintptr_t)ws & 15) == 0, "decoder_forward_ss: ws must be 16-byte aligned");
-  GIC_CHECK_ARG(P->embed && P->b_out && S->wout && st->hout && st->gpre, "decoder_forward_ss: null buffer");
-  for (int l = 0; l < c.NL; ++l)
-    GIC_CHECK_ARG(st->xh[l] && st->c[l] && S->wcat[l] && S->bsum[l], "decoder_forward_ss: null layer %d buffer", l);
-  if (c.dt == DT_F32)
-    return forward_tf_t<float>(c, P, S, st, features, caps, lengths, Tmax, nullptr, 0, 1.f, 1, (float*)ws, out, h_n, c_n, (hipStream_t)stream,
-                               opts);
-  return forward_tf_t<bf16_t>(c, P, S, st, features, caps, lengths, Tmax, nullptr, 0, 1.f, 1, (float*)ws, out, h_n, c_n, (hipStream_t)stream,
-                              opts);
-}
-
-int gic_decoder_forward_tf_bwd(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
-                               const gic_decoder_state* st, const gic_decoder_bwd_ws* ws, const void* pred, const int64_t* caps,
-                               const int32_t* lengths, int Tmax, const void* d_pred, float temperature, int pretrain,
-                               const gic_decoder_grads* G, void* stream_) {
-  Ctx c;
-  GIC_PROPAGATE(check_dims(dims, c));
-  GIC_CHECK_ARG(P && S && st && ws && pred && lengths && d_pred && G, "decoder_forward_tf_bwd: null argument");
-  GIC_CHECK_ARG(c.L == 1 || caps, "decoder_forward_tf_bwd: caps is null");
-  GIC_CHECK_ARG(Tmax >= 1 && Tmax <= c.L, "decoder_forward_tf_bwd: Tmax must be in 1..L (= caption length + 1)");
-  GIC_CHECK_ARG(ws->dlogits && ws->dhout && st->hout && S->wout && G->embed && G->w_out && G->b_out && G->features, "decoder_forward_tf_bwd: null buffer");
-  for (int l = 0; l < c.NL; ++l)
-    GIC_CHECK_ARG(st->xh[l] && st->c[l] && st->gates[l] && ws->dgates[l] && ws->dxh[l] && ws->dc[l] && G->w_ih[l] && G->w_hh[l] && G->b_ih[l] && G->b_hh[l],
-                  "decoder_forward_tf_bwd: null layer %d buffer (the forward call must have been given state->gates)", l);
-  hipStream_t stream = (hipStream_t)stream_;
-  const int T = c.L;
-  // the saved state and every [B, Tmax, .] tensor are laid out for Tmax steps: run the sampled path's backward on that view
-  c.L = Tmax;
-  GIC_PROPAGATE(decoder_output_bwd(c.dt, c.B, Tmax, c.V, c.H, pred, d_pred, temperature, nullptr, pretrain, ws->dlogits, S->wout, st->hout, ws->dhout,
-                                   G->w_out, G->b_out, stream));
-  GIC_PROPAGATE(zero_past_length(ws->dhout, lengths, c.B, Tmax, c.H, stream));
-  // caps stands in for the sampled ids (the input of step t is embed(caps[b, t-1])); sample_bwd_t itself never reads them
-  const int s = (c.dt == DT_F32)
-                    ? sample_bwd_t<float>(c, P, S, st, ws, pred, caps, d_pred, temperature, nullptr, pretrain, G, GIC_DECODER_BWD_RECURRENT, stream)
-                    : sample_bwd_t<bf16_t>(c, P, S, st, ws, pred, caps, d_pred, temperature, nullptr, pretrain, G, GIC_DECODER_BWD_RECURRENT, stream);
-  GIC_PROPAGATE(s);
-  return embed_scatter_time((const float*)ws->dxh[0], c.ldx(0), caps, G->embed, c.B, Tmax, c.E, c.V, stream, T - 1);
-}
 
 void gic_debug_decoder_step(int v) { decoder_step_debug(v); }
 
@@ -1083,16 +868,16 @@ int gic_step_scalars_set(gic_step_scalars* dev, const gic_step_scalars* host_val
 }
 
 int gic_decoder_fused_rollout_rows(const gic_decoder_dims* dims, int32_t* out) {
-  Ctx c;
-  GIC_PROPAGATE(check_dims(dims, c));
+  DCtx c;
+  GIC_PROPAGATE(check_decoder_dims(dims, c));
   GIC_CHECK_ARG(out, "decoder_fused_rollout_rows: null out");
   *out = decoder_step_supported(c.dt, c.V, c.E, c.H, c.NL) ? decoder_step_max_rows() : 0;
   return GIC_OK;
 }
 
 int gic_decoder_state_bytes(const gic_decoder_dims* dims, uint64_t* out) {
-  Ctx c;
-  GIC_PROPAGATE(check_dims(dims, c));
+  DCtx c;
+  GIC_PROPAGATE(check_decoder_dims(dims, c));
   GIC_CHECK_ARG(out, "decoder_state_bytes: null out");
   const uint64_t B = c.B, L = c.L, H = c.H, a = c.asz();
   for (int l = 0; l < GIC_MAX_LAYERS; ++l) {
@@ -1109,8 +894,8 @@ int gic_decoder_state_bytes(const gic_decoder_dims* dims, uint64_t* out) {
 }
 
 int gic_decoder_bwd_ws_bytes(const gic_decoder_dims* dims, uint64_t* out) {
-  Ctx c;
-  GIC_PROPAGATE(check_dims(dims, c));
+  DCtx c;
+  GIC_PROPAGATE(check_decoder_dims(dims, c));
   GIC_CHECK_ARG(out, "decoder_bwd_ws_bytes: null out");
   const uint64_t B = c.B, L = c.L, H = c.H, a = c.asz();
   out[0] = B * L * (uint64_t)c.V * a;
@@ -1125,8 +910,8 @@ int gic_decoder_bwd_ws_bytes(const gic_decoder_dims* dims, uint64_t* out) {
 }
 
 int gic_decoder_prepare(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S, void* stream_) {
-  Ctx c;
-  GIC_PROPAGATE(check_dims(dims, c));
+  DCtx c;
+  GIC_PROPAGATE(check_decoder_dims(dims, c));
   GIC_CHECK_ARG(P && S, "decoder_prepare: null struct");
   hipStream_t stream = (hipStream_t)stream_;
   for (int l = 0; l < c.NL; ++l) {
@@ -1152,8 +937,8 @@ int gic_decoder_sample_fwd(const gic_decoder_dims* dims, const gic_decoder_param
                            const gic_decoder_state* st, const float* features, const float* noise_u, uint64_t seed,
                            float temperature, int pretrain, void* out, int64_t* ids, const gic_decoder_sample_opts* opt,
                            void* stream) {
-  Ctx c;
-  GIC_PROPAGATE(check_dims(dims, c));
+  DCtx c;
+  GIC_PROPAGATE(check_decoder_dims(dims, c));
   GIC_CHECK_ARG(P && S && st && features && ids, "decoder_sample_fwd: null argument");
   const bool keep = !(opt && opt->no_state);
   GIC_CHECK_ARG(!keep || (st->hout && out), "decoder_sample_fwd: out / state->hout may be NULL only for a stateless roll-out (opts->no_state)");
@@ -1179,9 +964,9 @@ int gic_decoder_sample_bwd(const gic_decoder_dims* dims, const gic_decoder_param
                            const gic_decoder_state* st, const gic_decoder_bwd_ws* ws, const void* probs,
                            const int64_t* ids, const void* d_out, float temperature, int pretrain,
                            const gic_decoder_grads* G, int phases, const gic_step_scalars* dev_scalars, void* stream_) {
-  Ctx c;
+  DCtx c;
   const float* t_dev = dev_scalars ? &dev_scalars->temperature : nullptr;
-  GIC_PROPAGATE(check_dims(dims, c));
+  GIC_PROPAGATE(check_decoder_dims(dims, c));
   GIC_CHECK_ARG(P && S && st && ws && probs && ids && d_out && G, "decoder_sample_bwd: null argument");
   GIC_CHECK_ARG(ws->dlogits && ws->dhout && G->embed && G->w_out && G->b_out && G->features, "decoder_sample_bwd: null buffer");
   for (int l = 0; l < c.NL; ++l)

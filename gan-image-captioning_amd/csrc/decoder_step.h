@@ -16,6 +16,12 @@
 #pragma once
 #include "common.h"
 
+struct gic_decoder_dims;
+struct gic_decoder_params;
+struct gic_decoder_shadow;
+struct gic_decoder_state;
+struct gic_decoder_bwd_ws;
+struct gic_decoder_grads;
 struct gic_attn_dims;
 struct gic_attn_params;
 struct gic_attn_shadow;
@@ -50,7 +56,7 @@ struct LstmStepArgs {
   const int32_t* parent = nullptr;   // [B]: the h part of xh_t and c_prev are read from row parent[r]
   const int32_t* token = nullptr;    // [B]: the gathered x part is embed[token[r]] (needs `gather`)
   const int32_t* stop = nullptr; int stop_at = 0;  // *stop >= stop_at: return at once (every beam has finished)
-  // teacher-forced decode (attn_tf.hip), optional: with pack_len, a row with pack_t >= pack_len[b] keeps (h, c) (pack_padded_sequence)
+  // teacher-forced decode (teacher_forced.hip AttnTf), optional: with pack_len, a row with pack_t >= pack_len[b] keeps (h, c) (pack_padded_sequence)
   // and writes a zero h_out row and zero gates; not combined with the beam arguments
   const int32_t* pack_len = nullptr; int pack_t = 0;
   int dbg = 0;
@@ -112,14 +118,50 @@ int lstm_bwd_step(const LstmBwdStepArgs& a, int dtype, hipStream_t stream);
 bool decoder_step_supported(int dtype, int V, int E, int H, int NL);
 // most batch rows the fused roll-out takes (GIC_FUSED_ROLLOUT_MAX_ROWS, default 512): beyond it the per-step products are large GEMMs
 int decoder_step_max_rows();
-size_t decoder_step_part_floats(int B, int L, int V);       // floats in the partials scratch: [2][L][B][nblk] floats + [L][B] 64-bit keys + 2 reserved words
+size_t decoder_step_part_floats(int B, int L, int V);       // floats in the partials scratch: [2][L][B][nblk] floats + [L][B] 64-bit keys + 4 reserved words
 void decoder_step_debug(int v);                             // phase-ablation knob of tools/rollout_bench.py (0 = normal)
+
+// The partials scratch (state->part) of a fused roll-out of L steps over B rows, carved: the one place that knows its layout
+// (decoder_step_part_floats sizes it).  The two fused roll-outs (decoder.hip sample_fwd_fused, attention.hip attn_fwd_t) zero the
+// keys once, take step t's vocab_step arguments and the sample_finish arguments from here and add their decoder's own fields.
+struct StepScratch {
+  float* part_m; float* part_s;      // [L][B][nblk] per-tile max / sum of exp
+  unsigned long long* rowkey;        // [L][B] argmax keys, 8-byte aligned: atomicMax targets, zeroed before step 0
+  int nblk, B, L, V;
+  unsigned long long* keys(int t) const { return rowkey + (long)t * B; }
+  size_t key_bytes() const { return (size_t)L * B * sizeof(unsigned long long); }
+};
+StepScratch decoder_step_scratch(float* part, int B, int L, int V);
+// what a roll-out draws with and writes, the same for every step: explicit uniforms [L, B, V] or Philox(seed, stream t), the scalars
+// (t_dev / seed_dev: read from device memory instead), out act [B, L, V] or null, ids [B, L]
+struct StepDraw {
+  const float* noise_u; uint64_t seed; float temperature; int pretrain;
+  const float* t_dev; const uint64_t* seed_dev;
+  void* out; int64_t* ids;
+};
+// step t's vocab_step arguments but the decoder's own (h, ldh, wout, bias, H); sample_finish's but force_ids / force_len and the
+// x rows (embed, xh0, ldx0)
+VocabStepArgs step_vocab_args(const StepScratch& s, const StepDraw& d, int t, int dtype);
+SampleFinishArgs step_finish_args(const StepScratch& s, const StepDraw& d, int E);
 int lstm_step(const LstmStepArgs& a, int dtype, hipStream_t stream);
 int vocab_step(const VocabStepArgs& a, int dtype, hipStream_t stream);
 int sample_finish(const SampleFinishArgs& a, int dtype, hipStream_t stream);
 // the vocabulary product of vocab_step with the logits epilogue: a.logits = o + b_out in f32, the roll-out's bits before its noise
 // (caption sampling, sample.hip); a.stop / stop_at; the sampling and beam fields are unused
 int vocab_step_logits(const VocabStepArgs& a, int dtype, hipStream_t stream);
+
+// ---- the LSTM decoder's (decoder.hip) shapes, shared with the teacher-forced decode (teacher_forced.hip)
+struct DCtx {
+  int B, L, V, E, H, NL, dt;
+  int din(int l) const { return l == 0 ? E : H; }
+  long ldx(int l) const { return (long)din(l) + H; }
+  size_t asz() const { return (size_t)dtype_size(dt); }
+};
+int check_decoder_dims(const gic_decoder_dims* d, DCtx& c);   // B, L, E, H > 0, V > 1, NL in 1..GIC_MAX_LAYERS
+// decoder.hip: the recurrent phase of gic_decoder_sample_bwd (ws->dhout filled) over c.L steps and the embedding scatter over ids
+// (rows ids_stride apart; 0 = c.L)
+int decoder_bwd_recurrent(const DCtx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,
+                          const gic_decoder_bwd_ws* ws, const int64_t* ids, long ids_stride, const gic_decoder_grads* G, hipStream_t stream);
 
 // ---- the attention decoder's (attention.hip) shapes, shared with its beam search (attn_beam.hip)
 struct ACtx {

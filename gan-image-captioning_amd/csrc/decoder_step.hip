@@ -817,9 +817,36 @@ bool decoder_step_supported(int dtype, int V, int E, int H, int NL) {
   return (V + kVocabTile - 1) / kVocabTile <= 1024;                    // sample_finish's scale table
 }
 
+// state->part: part_m | part_s (per = [L][B][nblk] floats each) | the 64-bit row keys [L][B] on the next 8-byte boundary
+static long step_key_offset(long per) { return (2 * per + 1) & ~1l; }
+
+StepScratch decoder_step_scratch(float* part, int B, int L, int V) {
+  const int nblk = cdiv(V, kVocabTile);
+  const long per = (long)L * B * nblk;
+  return StepScratch{part, part + per, (unsigned long long*)(part + step_key_offset(per)), nblk, B, L, V};
+}
+
 size_t decoder_step_part_floats(int B, int L, int V) {
-  // + the 64-bit row keys (8-byte aligned) + two reserved 32-bit words behind them (ABI v2 sizing, unused)
-  return (size_t)2 * L * B * ((V + kVocabTile - 1) / kVocabTile) + (size_t)2 * L * B + 4;
+  // the tile partials + the keys (two floats each) + four reserved 32-bit words behind them (ABI v2 sizing, unused)
+  return (size_t)step_key_offset((long)L * B * cdiv(V, kVocabTile)) + (size_t)2 * L * B + 4;
+}
+
+VocabStepArgs step_vocab_args(const StepScratch& s, const StepDraw& d, int t, int dtype) {
+  VocabStepArgs v;
+  v.u = d.noise_u ? d.noise_u + (long)t * s.B * s.V : nullptr;
+  v.seed = d.seed; v.rng_stream = (uint64_t)t; v.temperature = d.temperature; v.pretrain = d.pretrain;
+  v.t_dev = d.t_dev; v.seed_dev = d.seed_dev;
+  v.out = d.out ? (char*)d.out + (size_t)t * s.V * dtype_size(dtype) : nullptr; v.out_stride = (long)s.L * s.V;
+  v.part_m = s.part_m + (long)t * s.B * s.nblk; v.part_s = s.part_s + (long)t * s.B * s.nblk; v.rowkey = s.keys(t);
+  v.nblk = s.nblk; v.B = s.B; v.V = s.V;
+  return v;
+}
+
+SampleFinishArgs step_finish_args(const StepScratch& s, const StepDraw& d, int E) {
+  SampleFinishArgs f;
+  f.part_m = s.part_m; f.part_s = s.part_s; f.rowkey = s.rowkey; f.nblk = s.nblk; f.B = s.B; f.L = s.L; f.V = s.V; f.E = E;
+  f.pretrain = d.pretrain; f.out = d.out; f.ids = d.ids;
+  return f;
 }
 
 void decoder_step_debug(int v) { g_step_dbg = v; }

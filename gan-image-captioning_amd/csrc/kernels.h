@@ -24,10 +24,13 @@ int transpose2d(const void* src, void* dst, int dtype, long rows, long cols, hip
 // decoder.hip internals shared with attention.hip
 int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, const void* d_out, float temperature, const float* t_dev, int pretrain,
                        void* dlogits_ws, const void* wout, const void* hout, float* dhout, float* d_wout, float* d_bout, hipStream_t stream);
-// the roll-out's LSTM pointwise step (decoder.hip) for the caption decode's generic LSTM path (decode.hip): gate pre-activations
-// gpre f32 [rows, 4H], c_prev / c_new [rows, H], h into h_next (and h_up when not null)
+// the LSTM pointwise step (decoder.hip) of every generic path -- the roll-outs (decoder.hip, attn_rollout.hip), the caption decode's
+// LstmGeneric (decode.hip) and the teacher-forced LSTM recurrence (teacher_forced.hip): gate pre-activations gpre f32 [rows, 4H],
+// c_prev / c_new [rows, H], h into h_next (and h_up, h_out when not null), the activated gates into gates [rows, 4H] when not null.
+// With lengths (int32 [rows]; h_prev then = the act rows of h_{t-1}) a row with t >= lengths[b] keeps (h, c): pack_padded_sequence
 int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_new, void* h_next, long ld_next, void* h_up, long ld_up,
-                       int rows, int H, hipStream_t stream);
+                       int rows, int H, hipStream_t stream, void* h_out = nullptr, long ld_out = 0, float* gates = nullptr,
+                       const int32_t* lengths = nullptr, int t = 0, const void* h_prev = nullptr, long ld_prev = 0);
 // the generic roll-out's per-step launches (decoder.hip), shared with the attention decoder's roll-out (attn_rollout.hip):
 //   rollout_join    rows [r0, r1) of dst_xh / dst_c = the rows r % srcB of src_xh / src_c (rows of rowbytes bytes / H floats)
 //   rollout_pick    after gemm_gumbelmax: ids[r * ids_stride] = the index of rowkey[r] (or the forced id) and its embedding row into x_next
@@ -45,11 +48,8 @@ int rollout_argmax(int dt, float* logits, const float* u, uint64_t seed, uint64_
 int det_mode();
 int det_scatter(const void* src, int dt, long ld, long row_off, const int64_t* ids, int B, long s_b, long s_t, long n, float* dst,
                 long d_id, long d_e, int E, int V, hipStream_t stream);
-// the teacher-forced decode's pieces (decoder.hip), for gic_decoder_forward_tf and attn_tf.hip: x rows of slots 1..Tm1 of xh0 =
-// embed(caps[b, t-1]) (caps rows Tm1 apart); rows of dhout [B, Tmax, H] past their length zeroed; per-row Gumbel-softmax of logits
-// [rows, V] into out (no ids)
-int embed_rows_tf(int dt, const float* embed, const int64_t* caps, void* xh0, long ld, int B, int Tm1, int E, int V, hipStream_t stream);
-int zero_past_length(float* dhout, const int32_t* lengths, int B, int Tmax, int H, hipStream_t stream);
+// the teacher-forced decode's epilogue (teacher_forced.hip), beside the Gumbel-softmax kernel it launches (decoder.hip): per-row
+// Gumbel-softmax of logits [rows, V] into out (no ids)
 int gumbel_softmax_rows(int dt, float* logits, const float* u, uint64_t seed, uint64_t rng_stream, float temperature, int pretrain, void* out,
                         long rows, int V, hipStream_t stream);
 int embed_scatter_time(const float* dx, long ld, const int64_t* ids, float* d_embed, int B, int L, int E, int V, hipStream_t stream, long ids_stride = 0);

@@ -613,6 +613,98 @@ def _ss_opts(prob: float, pick: str, coin_u, noise_u, seed: int, B: int, Lc: int
     return o, inputs, replaced, (coin_u, noise_u)
 
 
+def step_part_floats(B: int, Lc: int, V: int) -> int:
+    """Floats of the fused step kernels' scratch (state ``part``): [2][L][B][ceil(V/64)] tile partials + [L][B] 64-bit argmax keys +
+    four reserved words -- decoder_step_part_floats of csrc/decoder_step.hip, the one owner of the layout (= gic_decoder_state_bytes'
+    figure)."""
+    return 2 * Lc * B * ((V + 63) // 64) + 2 * Lc * B + 4
+
+
+class _TeacherForced:
+    """forward_tf, forward_scheduled and forward_tf_bwd of both decoder engines (csrc/teacher_forced.hip).  The engine gives the symbol
+    prefix, ``NL`` (the leading dimension of the final states), ``_decode_maps`` (the feature map: the inputs a call takes after
+    ``features``), ``_tf_check_inputs(features, caps, B)`` (its own shape / dtype check and text), ``_tf_ws(B, T, Tmax, dev)`` (the
+    workspace tensors of the plain call, in argument order), ``_bwd_ws_struct(ws)`` and ``_GRADS`` (the backward's structs) and the
+    hooks below; its public methods keep their own signatures and pass what they lack as None."""
+
+    _TF_BWD_WS_STEPS = "Tmax"    # the key of ``saved`` that sizes a backward workspace allocated here
+
+    def _tf_alphas(self, want: bool, B: int, Tmax: int, dev):
+        """The outputs a forward call takes after ``out`` (a tensor or None each); they follow (h_n, c_n) in what it returns."""
+        return ()
+
+    def _tf_d_alphas(self, d_alphas, B: int, Tmax: int):
+        """The gradients a backward call takes after ``d_pred``."""
+        return ()
+
+    def alloc_grads(self, params, B: int) -> List[torch.Tensor]:
+        """[one gradient per parameter, in the parameters' order ..., d_features]"""
+        return [torch.empty_like(p) for p in params] + [torch.empty(B, self.E, device=params[0].device, dtype=torch.float32)]
+
+    def _tf_forward(self, params, features, fmap, caps, lengths, tmax, state, want_alphas, ss, noise_u=None, seed=0, temperature=1.0,
+                    pretrain=True):
+        """``ss``: None, or _ss_opts' arguments but the shapes (prob, pick, coin_u, noise_u, seed) -- then the scheduled-sampling call.
+        Returns (pred, (h_n, c_n), *alphas), saved[, inputs, replaced]."""
+        self.check_params(params)
+        require_gpu(features, fmap, caps, noise_u, *(ss[2:4] if ss else ()))
+        B, Lc = caps.shape
+        T = Lc + 1
+        Tmax, len_dev = _tf_lengths(lengths, B, T, tmax)
+        self._tf_check_inputs(features, caps, B)
+        if noise_u is not None:
+            if tuple(noise_u.shape) != (B, Tmax, self.V):
+                raise ValueError(f"noise_u must be [B, max(lengths)={Tmax}, V]")
+            noise_u = noise_u.contiguous().float()
+        maps = self._decode_maps(fmap, B)
+        dev = features.device
+        if ss:
+            o, inputs, replaced, keep = _ss_opts(*ss, B, Lc, self.V, dev)
+        self.prepare(params)
+        st = dict(state) if state is not None else self.alloc_state(B, T, dev)
+        out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
+        h_n = torch.empty(self.NL, B, self.H, device=dev, dtype=torch.float32)
+        c_n = torch.empty_like(h_n)
+        alphas = self._tf_alphas(want_alphas, B, Tmax, dev)
+        d = self.dims(B, T)
+        if ss:
+            name, nbytes = f"{self._PREFIX}_forward_ss", C.c_uint64(0)
+            L.check(getattr(L.load(), name + "_ws_bytes")(C.byref(d), Tmax, C.byref(nbytes)), name + "_ws_bytes")
+            ws = (torch.empty(max(int(nbytes.value) // 4, 1), device=dev, dtype=torch.float32),)
+            mode = (C.byref(o),)
+        else:
+            name, ws = f"{self._PREFIX}_forward_tf", self._tf_ws(B, T, Tmax, dev)
+            mode = (ptr(noise_u), int(seed) & (2 ** 64 - 1), float(temperature), int(bool(pretrain)))
+        len_dev, caps = len_dev.to(dev), caps.contiguous()
+        L.check(getattr(L.load(), name)(
+            C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
+            ptr(features.contiguous().float()), *map(ptr, maps), ptr(caps), ptr(len_dev), Tmax, *mode, *map(ptr, ws), ptr(out),
+            *map(ptr, alphas), ptr(h_n), ptr(c_n), stream_ptr()), name)
+        if maps:
+            st["fmap"] = maps[0]
+        saved = {"st": st, "caps": inputs if ss else caps, "len_dev": len_dev, "Tmax": Tmax, "T": T}
+        return (out, (h_n, c_n), *alphas), saved, *((inputs, replaced) if ss else ())
+
+    def _tf_backward(self, params, saved, pred, d_pred, d_alphas, temperature, pretrain, ws, grads):
+        B, Tmax, dev = pred.shape[0], saved["Tmax"], pred.device
+        if d_pred is None:
+            d_pred = torch.zeros(pred.shape, device=dev, dtype=self.act)
+        if tuple(d_pred.shape) != tuple(pred.shape):
+            raise ValueError("d_pred must have pred's shape")
+        d_pred = _to_act(d_pred, self.act)
+        d_alphas = self._tf_d_alphas(d_alphas, B, Tmax)
+        self.prepare(params)
+        ws = ws if ws is not None else self.alloc_bwd_ws(B, saved[self._TF_BWD_WS_STEPS], dev)
+        grads = grads if grads is not None else self.alloc_grads(params, B)
+        name = f"{self._PREFIX}_forward_tf_bwd"
+        st = saved["st"]
+        L.check(getattr(L.load(), name)(
+            C.byref(self.dims(B, saved["T"])), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)),
+            C.byref(self._state_struct(st)), C.byref(self._bwd_ws_struct(ws)), *map(ptr, self._decode_maps(st.get("fmap"), B)), ptr(pred),
+            ptr(saved["caps"]), ptr(saved["len_dev"]), Tmax, ptr(d_pred), *map(ptr, d_alphas), float(temperature), int(bool(pretrain)),
+            C.byref(self._pstruct(grads[:-1], self._GRADS, grads[-1])), stream_ptr()), name)
+        return grads
+
+
 def cider_d(cand_ids: torch.Tensor, cand_len: torch.Tensor, cand_img: torch.Tensor, ref_ids: torch.Tensor, ref_len: torch.Tensor,
             ref_off: torch.Tensor, max_refs: int, keys: torch.Tensor, idf: torch.Tensor, log_n: float, V: int) -> torch.Tensor:
     """gic_cider_d: CIDEr-D f32 [n_cand] of candidates int64 [n_cand, Lc] (cand_len / cand_img int32 [n_cand]) against the references
@@ -688,8 +780,10 @@ def caption_overlap(cand_ids: torch.Tensor, cand_len: torch.Tensor, cand_img: to
 
 
 # ------------------------------------------------------------------------------------------ decoder
-class DecoderEngine(_CaptionDecodes):
+class DecoderEngine(_CaptionDecodes, _TeacherForced):
     """Decoder.sample forward/backward (reference src/generator.py:55-96) on the HIP library."""
+
+    _GRADS = L.DecoderGrads
 
     def __init__(self, vocab: int, embed: int, hidden: int, layers: int, dtype: int):
         if not 1 <= layers <= L.MAX_LAYERS:
@@ -777,9 +871,7 @@ class DecoderEngine(_CaptionDecodes):
         }
 
     def part_floats(self, B: int, Lc: int) -> int:
-        """Floats of the fused step kernels' scratch: [2][L][B][ceil(V/64)] tile partials + [L][B] 64-bit argmax keys + two reserved
-        words (gicap.h; = gic_decoder_state_bytes' figure)."""
-        return 2 * Lc * B * ((self.V + 63) // 64) + 2 * Lc * B + 4
+        return step_part_floats(B, Lc, self.V)
 
     def fused_rollout_rows(self) -> int:
         """Largest batch the fused step kernels take for this decoder's shapes; 0: they decline them (gic_decoder_fused_rollout_rows:
@@ -822,11 +914,13 @@ class DecoderEngine(_CaptionDecodes):
             "dc": [torch.empty(B, self.H, device=dev, dtype=f32) for _ in range(self.NL)],
         }
 
-    def alloc_grads(self, params, B: int) -> List[torch.Tensor]:
-        """[d_embed, per-layer grads..., d_w_out, d_b_out, d_features]"""
-        g = [torch.empty_like(p) for p in params]
-        g.append(torch.empty(B, self.E, device=params[0].device, dtype=torch.float32))
-        return g
+    def _bwd_ws_struct(self, ws) -> L.DecoderBwdWs:
+        w = L.DecoderBwdWs()
+        w.dlogits, w.dhout = ptr(ws["dlogits"]), ptr(ws["dhout"])
+        w.dgates = _arr(C.c_void_p, L.MAX_LAYERS, [ptr(t) for t in ws["dgates"]])
+        w.dxh = _arr(C.c_void_p, L.MAX_LAYERS, [ptr(t) for t in ws["dxh"]])
+        w.dc = _arr(C.c_void_p, L.MAX_LAYERS, [ptr(t) for t in ws["dc"]])
+        return w
 
     def sample_fwd(self, params, features: torch.Tensor, Lc: int, temperature: float, pretrain: bool = False,
                    noise_u: Optional[torch.Tensor] = None, seed: int = 0, state=None, out=None, ids=None,
@@ -905,33 +999,15 @@ class DecoderEngine(_CaptionDecodes):
         Returns (pred act [B, max(lengths), V], (h_n, c_n) f32 [NL, B, H]); with ``keep_state`` also what ``forward_tf_bwd`` needs.
         ``tmax``: decode that many steps and take ``lengths`` as device int32 values in 1..T unread (no host sync); pred is then
         [B, tmax, V]."""
-        self.check_params(params)
-        require_gpu(features, caps, noise_u)
-        B, Lc = caps.shape
-        T = Lc + 1
-        Tmax, len_dev = _tf_lengths(lengths, B, T, tmax)
-        dev = features.device
+        head, saved = self._tf_forward(params, features, None, caps, lengths, tmax, None, False, None, noise_u, seed, temperature, pretrain)
+        return (*head, saved) if keep_state else head
+
+    def _tf_check_inputs(self, features, caps, B: int) -> None:
         if features.shape != (B, self.E) or caps.dtype != torch.int64:
             raise ValueError("features must be [B, E] and caps int64 [B, L]")
-        if noise_u is not None and tuple(noise_u.shape) != (B, Tmax, self.V):
-            raise ValueError(f"noise_u must be [B, max(lengths)={Tmax}, V]")
-        self.prepare(params)
-        st = self.alloc_state(B, T, dev)
-        out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
-        h_n = torch.empty(self.NL, B, self.H, device=dev, dtype=torch.float32)
-        c_n = torch.empty_like(h_n)
-        logits_ws = torch.empty(B * Tmax, self.V, device=dev, dtype=torch.float32)
-        ids_ws = torch.empty(B * Tmax, device=dev, dtype=torch.int64)
-        len_dev = len_dev.to(dev)
-        d = self.dims(B, T)
-        L.check(L.load().gic_decoder_forward_tf(
-            C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
-            ptr(features.contiguous().float()), ptr(caps.contiguous()), ptr(len_dev), Tmax,
-            ptr(noise_u.contiguous().float()) if noise_u is not None else None, int(seed) & (2 ** 64 - 1), float(temperature),
-            int(bool(pretrain)), ptr(logits_ws), ptr(ids_ws), ptr(out), ptr(h_n), ptr(c_n), stream_ptr()), "gic_decoder_forward_tf")
-        if keep_state:
-            return out, (h_n, c_n), {"st": st, "caps": caps.contiguous(), "len_dev": len_dev, "Tmax": Tmax, "T": T}
-        return out, (h_n, c_n)
+
+    def _tf_ws(self, B: int, T: int, Tmax: int, dev):
+        return (torch.empty(B * Tmax, self.V, device=dev, dtype=torch.float32), torch.empty(B * Tmax, device=dev, dtype=torch.int64))
 
     def forward_scheduled(self, params, features: torch.Tensor, caps: torch.Tensor, lengths, sample_prob: float, pick: str = "sample",
                           coin_u: Optional[torch.Tensor] = None, noise_u: Optional[torch.Tensor] = None, seed: int = 0,
@@ -940,54 +1016,14 @@ class DecoderEngine(_CaptionDecodes):
         the model's own pick from step t-1's logits where coin < ``sample_prob`` (and t < lengths[b]), else caps[:, t-1].  Returns
         (pred, (h_n, c_n), saved, inputs int64 [B, L], replaced int32 [B, L]); ``saved`` carries ``inputs`` as its captions, so
         ``forward_tf_bwd`` runs on it unchanged.  ``coin_u`` f32 [B, L] / ``noise_u`` f32 [L, B, V] replace the device draws."""
-        self.check_params(params)
-        require_gpu(features, caps, coin_u, noise_u)
-        B, Lc = caps.shape
-        T = Lc + 1
-        Tmax, len_dev = _tf_lengths(lengths, B, T, tmax)
-        dev = features.device
-        if features.shape != (B, self.E) or caps.dtype != torch.int64:
-            raise ValueError("features must be [B, E] and caps int64 [B, L]")
-        o, inputs, replaced, keep = _ss_opts(sample_prob, pick, coin_u, noise_u, seed, B, Lc, self.V, dev)
-        self.prepare(params)
-        st = self.alloc_state(B, T, dev)
-        out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
-        h_n = torch.empty(self.NL, B, self.H, device=dev, dtype=torch.float32)
-        c_n = torch.empty_like(h_n)
-        d = self.dims(B, T)
-        nbytes = C.c_uint64(0)
-        L.check(L.load().gic_decoder_forward_ss_ws_bytes(C.byref(d), Tmax, C.byref(nbytes)), "gic_decoder_forward_ss_ws_bytes")
-        ws = torch.empty(max(int(nbytes.value) // 4, 1), device=dev, dtype=torch.float32)
-        len_dev = len_dev.to(dev)
-        L.check(L.load().gic_decoder_forward_ss(
-            C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
-            ptr(features.contiguous().float()), ptr(caps.contiguous()), ptr(len_dev), Tmax, C.byref(o), ptr(ws), ptr(out), ptr(h_n),
-            ptr(c_n), stream_ptr()), "gic_decoder_forward_ss")
-        del keep
-        return out, (h_n, c_n), {"st": st, "caps": inputs, "len_dev": len_dev, "Tmax": Tmax, "T": T}, inputs, replaced
+        head, *rest = self._tf_forward(params, features, None, caps, lengths, tmax, None, False, (sample_prob, pick, coin_u, noise_u, seed))
+        return (*head, *rest)
 
     def forward_tf_bwd(self, params, saved, pred: torch.Tensor, d_pred: torch.Tensor, temperature: float, pretrain: bool = False,
                        ws=None, grads=None) -> List[torch.Tensor]:
         """gic_decoder_forward_tf_bwd: gradients of a loss on ``pred`` of the ``forward_tf(..., keep_state=True)`` call that returned
         ``saved``; the list is ordered as ``sample_bwd``'s (parameters, then d features)."""
-        B, Tmax, dev = pred.shape[0], saved["Tmax"], pred.device
-        if tuple(d_pred.shape) != tuple(pred.shape):
-            raise ValueError("d_pred must have pred's shape")
-        d_pred = _to_act(d_pred, self.act)
-        self.prepare(params)
-        ws = ws if ws is not None else self.alloc_bwd_ws(B, Tmax, dev)
-        grads = grads if grads is not None else self.alloc_grads(params, B)
-        w = L.DecoderBwdWs()
-        w.dlogits, w.dhout = ptr(ws["dlogits"]), ptr(ws["dhout"])
-        w.dgates = _arr(C.c_void_p, L.MAX_LAYERS, [ptr(t) for t in ws["dgates"]])
-        w.dxh = _arr(C.c_void_p, L.MAX_LAYERS, [ptr(t) for t in ws["dxh"]])
-        w.dc = _arr(C.c_void_p, L.MAX_LAYERS, [ptr(t) for t in ws["dc"]])
-        L.check(L.load().gic_decoder_forward_tf_bwd(
-            C.byref(self.dims(B, saved["T"])), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)),
-            C.byref(self._state_struct(saved["st"])), C.byref(w), ptr(pred), ptr(saved["caps"]), ptr(saved["len_dev"]), Tmax, ptr(d_pred),
-            float(temperature), int(bool(pretrain)), C.byref(self._pstruct(grads[:-1], L.DecoderGrads, grads[-1])), stream_ptr()),
-            "gic_decoder_forward_tf_bwd")
-        return grads
+        return self._tf_backward(params, saved, pred, d_pred, None, temperature, pretrain, ws, grads)
 
     def sample_bwd(self, params, st, out: torch.Tensor, ids: torch.Tensor, d_out: torch.Tensor, temperature: float,
                    pretrain: bool = False, ws=None, grads=None, phases: int = 3, dev_scalars=None) -> List[torch.Tensor]:
@@ -999,11 +1035,7 @@ class DecoderEngine(_CaptionDecodes):
         self.prepare(params)
         ws = ws if ws is not None else self.alloc_bwd_ws(B, Lc, dev)
         grads = grads if grads is not None else self.alloc_grads(params, B)
-        w = L.DecoderBwdWs()
-        w.dlogits, w.dhout = ptr(ws["dlogits"]), ptr(ws["dhout"])
-        w.dgates = _arr(C.c_void_p, L.MAX_LAYERS, [ptr(t) for t in ws["dgates"]])
-        w.dxh = _arr(C.c_void_p, L.MAX_LAYERS, [ptr(t) for t in ws["dxh"]])
-        w.dc = _arr(C.c_void_p, L.MAX_LAYERS, [ptr(t) for t in ws["dc"]])
+        w = self._bwd_ws_struct(ws)
         d = self.dims(B, Lc)
         L.check(L.load().gic_decoder_sample_bwd(
             C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
@@ -1429,12 +1461,15 @@ def clip_adam(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, clip_no
 
 
 # ------------------------------------------------------------------------------------------ visual-attention decoder
-class AttnDecoderEngine(_CaptionDecodes):
+class AttnDecoderEngine(_CaptionDecodes, _TeacherForced):
     """gic_attn_sample_fwd / bwd (gicap.h): the reference's roll-out loop with soft attention over the trunk's feature map
     (BASELINE config 4; no reference counterpart, oracle/cpu_attention.py).
     params order: [embed, w_ih, w_hh, b_ih, b_hh, w_out, b_out, w_f, b_f, w_h, w_a]."""
 
     NAMES = ("embed", "w_ih", "w_hh", "b_ih", "b_hh", "w_out", "b_out", "w_f", "b_f", "w_h", "w_a")
+    NL = 1                        # one LSTM layer: the final states are [1, B, H]
+    _GRADS = L.AttnGrads
+    _TF_BWD_WS_STEPS = "T"
 
     def __init__(self, vocab: int, embed: int, hidden: int, feat_c: int, positions: int, attn: int, dtype: int):
         self.V, self.E, self.H, self.C, self.P, self.A, self.dt = vocab, embed, hidden, feat_c, positions, attn, dtype
@@ -1490,13 +1525,12 @@ class AttnDecoderEngine(_CaptionDecodes):
 
     def alloc_state(self, B: int, Lc: int, dev):
         f32 = torch.float32
-        nblk = (self.V + 63) // 64
         return {
             "xh": torch.empty(Lc + 1, B, self.ldx, device=dev, dtype=self.act),
             "gates": torch.empty(Lc, B, 4 * self.H, device=dev, dtype=f32),
             "c": torch.empty(Lc + 1, B, self.H, device=dev, dtype=f32),
             "hout": torch.empty(B, Lc, self.H, device=dev, dtype=self.act),
-            "part": torch.empty(2 * Lc * B * nblk + 2 * Lc * B + 2, device=dev, dtype=f32),
+            "part": torch.empty(step_part_floats(B, Lc, self.V), device=dev, dtype=f32),
             "fproj": torch.empty(B, self.P, self.A, device=dev, dtype=self.act),
             "alpha": torch.empty(Lc, B, self.P, device=dev, dtype=f32),
             "hproj": torch.empty(Lc, B, self.A, device=dev, dtype=f32),
@@ -1616,99 +1650,47 @@ class AttnDecoderEngine(_CaptionDecodes):
         ``lengths`` B values in 1..T, ``fmap`` [B, P, C] (cast to the compute dtype as in sample_fwd).  Returns (pred act [B, Tmax, V],
         (h_n, c_n) f32 [1, B, H], alphas f32 [B, Tmax, P] or None); with ``keep_state`` also what ``forward_tf_bwd`` needs.  ``tmax``
         as DecoderEngine.forward_tf.  ``state``: a caller-owned state (alloc_state(B, T, dev)) as in sample_fwd."""
-        self.check_params(params)
-        require_gpu(features, fmap, caps, noise_u)
-        B, Lc = caps.shape
-        T = Lc + 1
-        Tmax, len_dev = _tf_lengths(lengths, B, T, tmax)
+        head, saved = self._tf_forward(params, features, fmap, caps, lengths, tmax, state, want_alphas, None, noise_u, seed, temperature,
+                                       pretrain)
+        return (*head, saved) if keep_state else head
+
+    def _tf_check_inputs(self, features, caps, B: int) -> None:
         if tuple(features.shape) != (B, self.E) or features.dtype != torch.float32 or caps.dtype != torch.int64:
             raise ValueError(f"features must be float32 [B, {self.E}] and caps int64 [B, L]")
-        if noise_u is not None:
-            if tuple(noise_u.shape) != (B, Tmax, self.V):
-                raise ValueError(f"noise_u must be [B, max(lengths)={Tmax}, V]")
-            noise_u = noise_u.contiguous().float()
-        fmap = self._act_fmap(fmap, B)
-        dev = features.device
-        self.prepare(params)
-        st = dict(state) if state is not None else self.alloc_state(B, T, dev)
-        out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
-        h_n = torch.empty(1, B, self.H, device=dev, dtype=torch.float32)
-        c_n = torch.empty_like(h_n)
-        alphas = torch.empty(B, Tmax, self.P, device=dev, dtype=torch.float32) if want_alphas else None
-        logits_ws = torch.empty(self.tf_ws_bytes(B, T, Tmax) // 4, device=dev, dtype=torch.float32)
-        len_dev = len_dev.to(dev)
-        caps = caps.contiguous()
-        L.check(L.load().gic_attn_forward_tf(
-            C.byref(self.dims(B, T)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
-            ptr(features.contiguous()), ptr(fmap), ptr(caps), ptr(len_dev), Tmax, ptr(noise_u), int(seed) & (2 ** 64 - 1),
-            float(temperature), int(bool(pretrain)), ptr(logits_ws), ptr(out), ptr(alphas), ptr(h_n), ptr(c_n), stream_ptr()),
-            "gic_attn_forward_tf")
-        if keep_state:
-            st["fmap"] = fmap
-            return out, (h_n, c_n), alphas, {"st": st, "caps": caps, "len_dev": len_dev, "Tmax": Tmax, "T": T}
-        return out, (h_n, c_n), alphas
+
+    def _tf_ws(self, B: int, T: int, Tmax: int, dev):
+        return (torch.empty(self.tf_ws_bytes(B, T, Tmax) // 4, device=dev, dtype=torch.float32),)
+
+    def _tf_alphas(self, want: bool, B: int, Tmax: int, dev):
+        return (torch.empty(B, Tmax, self.P, device=dev, dtype=torch.float32) if want else None,)
+
+    def _tf_d_alphas(self, d_alphas, B: int, Tmax: int):
+        if d_alphas is not None:
+            if tuple(d_alphas.shape) != (B, Tmax, self.P):
+                raise ValueError(f"d_alphas must be [B, max(lengths)={Tmax}, P={self.P}]")
+            d_alphas = d_alphas.contiguous().float()
+        return (d_alphas,)
+
+    def _bwd_ws_struct(self, ws) -> L.AttnBwdWs:
+        w = L.AttnBwdWs()
+        for k, v in ws.items():
+            setattr(w, k, ptr(v))
+        return w
 
     def forward_scheduled(self, params, features, fmap, caps: torch.Tensor, lengths, sample_prob: float, pick: str = "sample",
                           coin_u: Optional[torch.Tensor] = None, noise_u: Optional[torch.Tensor] = None, seed: int = 0,
                           tmax: Optional[int] = None, state=None):
         """gic_attn_forward_ss: ``forward_tf(pretrain=True, want_alphas=True, keep_state=True)`` with scheduled sampling
         (DecoderEngine.forward_scheduled).  Returns (pred, (h_n, c_n), alphas, saved, inputs, replaced).  ``state`` as forward_tf."""
-        self.check_params(params)
-        require_gpu(features, fmap, caps, coin_u, noise_u)
-        B, Lc = caps.shape
-        T = Lc + 1
-        Tmax, len_dev = _tf_lengths(lengths, B, T, tmax)
-        if tuple(features.shape) != (B, self.E) or features.dtype != torch.float32 or caps.dtype != torch.int64:
-            raise ValueError(f"features must be float32 [B, {self.E}] and caps int64 [B, L]")
-        fmap = self._act_fmap(fmap, B)
-        dev = features.device
-        o, inputs, replaced, keep = _ss_opts(sample_prob, pick, coin_u, noise_u, seed, B, Lc, self.V, dev)
-        self.prepare(params)
-        st = dict(state) if state is not None else self.alloc_state(B, T, dev)
-        out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
-        h_n = torch.empty(1, B, self.H, device=dev, dtype=torch.float32)
-        c_n = torch.empty_like(h_n)
-        alphas = torch.empty(B, Tmax, self.P, device=dev, dtype=torch.float32)
-        d = self.dims(B, T)
-        nbytes = C.c_uint64(0)
-        L.check(L.load().gic_attn_forward_ss_ws_bytes(C.byref(d), Tmax, C.byref(nbytes)), "gic_attn_forward_ss_ws_bytes")
-        ws = torch.empty(int(nbytes.value) // 4, device=dev, dtype=torch.float32)
-        len_dev = len_dev.to(dev)
-        L.check(L.load().gic_attn_forward_ss(
-            C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
-            ptr(features.contiguous()), ptr(fmap), ptr(caps.contiguous()), ptr(len_dev), Tmax, C.byref(o), ptr(ws), ptr(out), ptr(alphas),
-            ptr(h_n), ptr(c_n), stream_ptr()), "gic_attn_forward_ss")
-        del keep
-        st["fmap"] = fmap
-        return out, (h_n, c_n), alphas, {"st": st, "caps": inputs, "len_dev": len_dev, "Tmax": Tmax, "T": T}, inputs, replaced
+        head, *rest = self._tf_forward(params, features, fmap, caps, lengths, tmax, state, True, (sample_prob, pick, coin_u, noise_u, seed))
+        return (*head, *rest)
 
     def forward_tf_bwd(self, params, saved, pred: torch.Tensor, d_pred: Optional[torch.Tensor], temperature: float, pretrain: bool = False,
                        d_alphas: Optional[torch.Tensor] = None, ws=None, grads=None) -> List[torch.Tensor]:
         """gic_attn_forward_tf_bwd: gradients of a loss on ``pred`` (``d_pred``; None = zeros) and on the alphas (``d_alphas`` f32
         [B, Tmax, P] or None) of the ``forward_tf(..., keep_state=True)`` call that returned ``saved``; ordered as ``sample_bwd``'s
         (parameters in NAMES order, then d features)."""
-        B, Tmax, dev = pred.shape[0], saved["Tmax"], pred.device
-        if d_pred is None:
-            d_pred = torch.zeros(pred.shape, device=dev, dtype=self.act)
-        if tuple(d_pred.shape) != tuple(pred.shape):
-            raise ValueError("d_pred must have pred's shape")
-        d_pred = _to_act(d_pred, self.act)
-        if d_alphas is not None:
-            if tuple(d_alphas.shape) != (B, Tmax, self.P):
-                raise ValueError(f"d_alphas must be [B, max(lengths)={Tmax}, P={self.P}]")
-            d_alphas = d_alphas.contiguous().float()
-        self.prepare(params)
-        ws = ws if ws is not None else self.alloc_bwd_ws(B, saved["T"], dev)
-        w = L.AttnBwdWs()
-        for k, v in ws.items():
-            setattr(w, k, ptr(v))
-        grads = grads if grads is not None else [torch.empty_like(p) for p in params] + [torch.empty(B, self.E, device=dev, dtype=torch.float32)]
-        L.check(L.load().gic_attn_forward_tf_bwd(
-            C.byref(self.dims(B, saved["T"])), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)),
-            C.byref(self._state_struct(saved["st"])), C.byref(w), ptr(saved["st"]["fmap"]), ptr(pred), ptr(saved["caps"]),
-            ptr(saved["len_dev"]), Tmax, ptr(d_pred), ptr(d_alphas), float(temperature), int(bool(pretrain)),
-            C.byref(self._pstruct(grads[:-1], L.AttnGrads, grads[-1])), stream_ptr()), "gic_attn_forward_tf_bwd")
-        return grads
+        return self._tf_backward(params, saved, pred, d_pred, d_alphas, temperature, pretrain, ws, grads)
 
     def rollout_ws_bytes(self, B: int, Lc: int, rows: int) -> int:
         """Bytes of gic_attn_rollout's workspace (host-only query)."""
@@ -1770,14 +1752,11 @@ class AttnDecoderEngine(_CaptionDecodes):
         """Returns [grads in NAMES order ..., d_features].  ``ws`` (alloc_bwd_ws) / ``grads`` (12 tensors): caller-owned buffers."""
         B, Lc = ids.shape
         dev = out.device
-        f32 = torch.float32
         d_out = _to_act(d_out, self.act)
         self.prepare(params)
         ws = ws if ws is not None else self.alloc_bwd_ws(B, Lc, dev)
-        w = L.AttnBwdWs()
-        for k, v in ws.items():
-            setattr(w, k, ptr(v))
-        grads = grads if grads is not None else [torch.empty_like(p) for p in params] + [torch.empty(B, self.E, device=dev, dtype=f32)]
+        w = self._bwd_ws_struct(ws)
+        grads = grads if grads is not None else self.alloc_grads(params, B)
         L.check(L.load().gic_attn_sample_bwd(
             C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
             C.byref(w), ptr(st["fmap"]), ptr(out), ptr(ids), ptr(d_out), float(temperature), int(bool(pretrain)),

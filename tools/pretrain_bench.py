@@ -1,6 +1,6 @@
 """MLE pre-train step at cfg2 shapes: ms per step, HIP-synchronised wall clock (tools only)."""
-import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 a = bench.parse()
 inst, args = bench.build_instructor(a, 1 if a.cgan is None else a.cgan)

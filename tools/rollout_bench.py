@@ -1,7 +1,7 @@
 """Roll-out alone (tools only): Decoder.sample forward / backward at the benchmark's shapes under HIP events, fused step kernels vs the
 generic launches.  python tools/rollout_bench.py"""
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gan_image_captioning_amd import engine as E
 B, L, V, Em, H = 64, 20, 10000, 512, 512
 dev = torch.device("cuda:0")
