@@ -9,6 +9,7 @@ from tests import test_gpu_kernels as K
 from tests import test_gpu_seqgan as SG
 from tests import test_gpu_step as ST
 from tests import test_gpu_training as TR
+from tests.step_state import _restore, _snapshot, _state
 from tests.test_gpu_kernels import E, dev  # noqa: F401  (fixtures of the reused kernel tests)
 
 pytestmark = pytest.mark.gpu
@@ -21,38 +22,6 @@ def det():
     engine.set_deterministic(True)
     yield
     engine.set_deterministic(before)
-
-
-def _opts(inst):
-    return [v for v in vars(inst).values() if hasattr(v, "exp_avg") and hasattr(v, "step_count")]
-
-
-def _state(inst):
-    t = {"gen_flat": inst.gen_arena.flat, "disc_flat": inst.disc_arena.flat,
-         "gen_grad": inst.gen_arena.grad, "disc_grad": inst.disc_arena.grad}
-    for i, o in enumerate(_opts(inst)):
-        t[f"opt{i}_m"], t[f"opt{i}_v"], t[f"opt{i}_t"] = o.exp_avg, o.exp_avg_sq, o.step_count
-    for mod in ("gen", "disc"):
-        for n, b in getattr(inst, mod).named_buffers():
-            t[f"{mod}.{n}"] = b
-    return t
-
-
-def _snapshot(inst):
-    from gan_image_captioning_amd.generator import SEEDS
-    return {k: v.detach().clone() for k, v in _state(inst).items()}, SEEDS._n, inst.gen.decoder.temperature
-
-
-def _restore(inst, snap):
-    from gan_image_captioning_amd import engine
-    from gan_image_captioning_amd.generator import SEEDS
-    tensors, n, temp = snap
-    with torch.no_grad():
-        for k, v in _state(inst).items():
-            v.copy_(tensors[k])
-    engine.bump_param_epoch()
-    SEEDS.reset(n)
-    inst.gen.decoder.temperature = temp
 
 
 def _run(inst, step, n=3):
