@@ -196,10 +196,8 @@ int gic_match_ranks(const float* S, int64_t ld, const float* row_bias, int32_t N
   GIC_CHECK_ARG(ld >= N, "match_ranks: ld=%lld must be >= N=%d", (long long)ld, N);
   GIC_CHECK_ARG(rank_c2i != rank_i2c, "match_ranks: rank_c2i aliases rank_i2c");
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(rank_c2i, 0, (size_t)N * sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(rank_i2c, 0, (size_t)N * sizeof(int32_t), st) != hipSuccess) {
-    set_last_error("match_ranks: clearing the rank counters failed: %s", hipGetErrorString(hipGetLastError()));
-    return GIC_ERR_LAUNCH;
-  }
+  GIC_PROPAGATE(fill_zero(rank_c2i, (size_t)N * sizeof(int32_t), st));      // (the rank counters; fill_zero: a kernel node inside a capture)
+  GIC_PROPAGATE(fill_zero(rank_i2c, (size_t)N * sizeof(int32_t), st));
   hipLaunchKernelGGL(match_ranks_kernel, dim3(cdiv(N, 256), cdiv(N, RANK_ROWS)), dim3(256), 0, st, S, (long)ld, row_bias, N, rank_c2i, rank_i2c);
   GIC_CHECK_LAUNCH("match_ranks");
   return GIC_OK;

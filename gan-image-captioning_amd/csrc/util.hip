@@ -181,6 +181,15 @@ inline int grid_for(long total, int block = 256, int cap = 2048) {
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
+// fill_zero inside a stream capture: 4-byte words where the range allows them, bytes at its ends
+__global__ void fill_zero_kernel(unsigned char* __restrict__ p, long head, long words, long bytes) {
+  const long S = (long)gridDim.x * blockDim.x, i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned int* w = (unsigned int*)(p + head);
+  for (long i = i0; i < words; i += S) w[i] = 0u;
+  for (long i = i0; i < head; i += S) p[i] = 0;
+  for (long i = head + 4 * words + i0; i < bytes; i += S) p[i] = 0;
+}
+
 }  // namespace
 
 int transpose2d(const void* src, void* dst, int dtype, long rows, long cols, hipStream_t stream) {
@@ -196,6 +205,21 @@ int transpose2d(const void* src, void* dst, int dtype, long rows, long cols, hip
 
 int fill_zero(void* p, size_t bytes, hipStream_t stream) {
   if (bytes == 0) return GIC_OK;
+  // Inside a stream capture the fill is recorded as a kernel node, not a memset node.  Observed, with the cause in the runtime not
+  // identified: in a process that held a second instructor, in the deterministic and the default mode alike, the replayed train
+  // step (fused_step.py, GIC_STEP_GRAPH=1) came back from its first pure replay on with sums that had been added onto unzeroed
+  // memory -- d_embed, the bias column sums, the roll-out's argmax keys -- differently from run to run, while the same launches
+  // outside a graph, and the capturing call itself, gave the eager step's bits; with kernel nodes the replayed steps equal their twins
+  // (tests/test_gpu_device_noise.py).  The replay test of tests/test_gpu_step.py (one instructor, the default mode, 1e-4) had not
+  // shown it, so a kernel node may only have moved the timing of a race.  Eager launches keep hipMemsetAsync.
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive) {
+    const long n = (long)bytes, mis = (long)((4 - ((uintptr_t)p & 3)) & 3);      // bytes up to the first 4-byte boundary
+    const long head = mis < n ? mis : n, words = (n - head) / 4;
+    hipLaunchKernelGGL(fill_zero_kernel, dim3(grid_for(words > 0 ? words : n)), dim3(256), 0, stream, (unsigned char*)p, head, words, n);
+    GIC_CHECK_LAUNCH("fill_zero");
+    return GIC_OK;
+  }
   hipError_t e = hipMemsetAsync(p, 0, bytes, stream);
   if (e != hipSuccess) {
     set_last_error("memset failed: %s", hipGetErrorString(e));

@@ -40,7 +40,10 @@ class FusedAdvStep:
         self.trace = None
         # Replayed step graphs are opt-in.  LSTM step (GIC_STEP_GRAPH=1): at cfg2 (B=64, V=10000) the segments replayed on their three
         # streams left non-finite decoder gradients from the first replay on (the same kernels as eager launches give finite ones; the
-        # replay test's cfg1 shapes do not show it), and eager launches measured 2.41 ms per step against 2.47 replayed.  Attention step
+        # replay test's cfg1 shapes do not show it), and eager launches measured 2.41 ms per step against 2.47 replayed.  (Observed at
+        # cfg1 too, once the replayed step was compared bit for bit with an eager twin in the same process: sums added onto unzeroed
+        # memory from the first pure replay on.  It went away when fill_zero, csrc/util.hip, captured kernel nodes for memset nodes; the
+        # cause in the runtime is not identified, and whether this is cfg2's fault is not known: cfg2 has not been run again.)  Attention step
         # (GIC_STEP_GRAPH_ATTN=1): host enqueue 2.10 -> 0.43 ms per step, but 3.87 ms per step against 3.74 for eager launches at cfg4.
         want = os.environ.get("GIC_STEP_GRAPH_ATTN" if self.attn else "GIC_STEP_GRAPH")
         self.use_graph = bool(want) and not (os.environ.get("GIC_NO_STEP_GRAPH") or os.environ.get("GIC_NO_GRAPH"))
