@@ -120,6 +120,10 @@ class SchedSampleOpts(C.Structure):       # gic_sched_sample_opts
                 ("inputs", c_void_p), ("replaced", c_void_p)]
 
 
+class DecoderDropout(C.Structure):        # gic_decoder_dropout
+    _fields_ = [("p", C.c_float), ("seed", C.c_uint64), ("keep_u", c_void_p), ("hdrop", c_void_p)]
+
+
 class DiscDims(C.Structure):
     _fields_ = [("B", C.c_int32), ("L", C.c_int32), ("V", C.c_int32), ("De", C.c_int32), ("R", C.c_int32),
                 ("nconv", C.c_int32), ("fsize", C.c_int32 * MAX_CONVS), ("nfilt", C.c_int32 * MAX_CONVS),
@@ -236,6 +240,26 @@ _SIGNATURES = {
     "gic_attn_forward_ss_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int, c_void_p]),
     "gic_attn_forward_ss": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), c_void_p, c_void_p, c_void_p, c_void_p,
                                       C.c_int, _P(SchedSampleOpts), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_decoder_forward_tf_drop": (C.c_int, [_P(DecoderDims), _P(DecoderParams), _P(DecoderShadow), _P(DecoderState), c_void_p, c_void_p,
+                                              c_void_p, C.c_int, c_void_p, C.c_uint64, C.c_float, C.c_int, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, _P(DecoderDropout), c_void_p]),
+    "gic_decoder_forward_ss_drop": (C.c_int, [_P(DecoderDims), _P(DecoderParams), _P(DecoderShadow), _P(DecoderState), c_void_p, c_void_p,
+                                              c_void_p, C.c_int, _P(SchedSampleOpts), c_void_p, c_void_p, c_void_p, c_void_p,
+                                              _P(DecoderDropout), c_void_p]),
+    "gic_decoder_forward_tf_drop_bwd": (C.c_int, [_P(DecoderDims), _P(DecoderParams), _P(DecoderShadow), _P(DecoderState), _P(DecoderBwdWs),
+                                                  c_void_p, c_void_p, c_void_p, C.c_int, c_void_p, C.c_float, C.c_int, _P(DecoderGrads),
+                                                  _P(DecoderDropout), c_void_p]),
+    "gic_attn_forward_tf_drop": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), c_void_p, c_void_p, c_void_p, c_void_p,
+                                           C.c_int, c_void_p, C.c_uint64, C.c_float, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           _P(DecoderDropout), c_void_p]),
+    "gic_attn_forward_ss_drop": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), c_void_p, c_void_p, c_void_p, c_void_p,
+                                           C.c_int, _P(SchedSampleOpts), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _P(DecoderDropout),
+                                           c_void_p]),
+    "gic_attn_forward_tf_drop_bwd": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), _P(AttnBwdWs), c_void_p, c_void_p,
+                                               c_void_p, c_void_p, C.c_int, c_void_p, c_void_p, C.c_float, C.c_int, _P(AttnGrads),
+                                               _P(DecoderDropout), c_void_p]),
+    "gic_hidden_dropout": (C.c_int, [c_void_p, C.c_int, C.c_int64, C.c_int32, C.c_float, C.c_uint64, c_void_p, c_void_p, c_void_p]),
+    "gic_hidden_dropout_bwd": (C.c_int, [c_void_p, c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64, c_void_p, c_void_p]),
     "gic_attn_rollout_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int64, c_void_p]),
     "gic_attn_rollout": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), c_void_p, c_void_p, C.c_int64, c_void_p,
                                    c_void_p, c_void_p, C.c_uint64, c_void_p, c_void_p, c_void_p]),

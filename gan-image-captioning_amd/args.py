@@ -98,6 +98,8 @@ _NATIVE = [
     ("--scheduled-sampling-ramp-epochs", int, 0, "epoch e (0-based) trains with p_e = p * min(1, e / n); 0 = p throughout"),
     ("--scheduled-sampling-pick", str, "sample", "the replaced token: sample = a draw from the previous step's softmax, argmax = its mode",
      {"choices": ["sample", "argmax"]}),
+    ("--gen-dropout", float, 0.0, "output dropout of the caption decoder in --pretrain-mode teacher: the LSTM output is dropped with this "
+                                  "probability in front of the vocabulary projection, training batches only"),
     ("--attn-reg", float, 0.0, "weight of the doubly stochastic attention penalty mean_b sum_i (1 - sum_t alpha_bti)^2 added to the "
                                "pre-training loss (--decoder attention --pretrain-mode teacher only)"),
     ("--eval-beam-size", int, 0, "beam size of the BLEU-4 evaluation (GANInstructor.evaluate) after each adversarial epoch's validation; "

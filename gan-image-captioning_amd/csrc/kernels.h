@@ -4,6 +4,7 @@
 #include "gemm.h"
 
 struct gic_sched_sample_opts;
+struct gic_decoder_dropout;
 
 namespace gic {
 
@@ -80,6 +81,17 @@ int ss_step_logits(int dt, const void* hout, int t, int Tmax, const void* wout, 
                    bool fused, hipStream_t stream);
 int ss_pick(const SsPickArgs& a, int dt, hipStream_t stream);
 int ss_tail(const int64_t* caps, int64_t* inputs, int32_t* replaced, int B, int Tm1, int from, hipStream_t stream);
+
+// gen_dropout.hip: output dropout of the caption decoder (gic_decoder_dropout), the stage between hout and the vocabulary projection.
+//   drop_check          the argument checks of gic_decoder_dropout (`who` names the entry point in the message)
+//   hidden_dropout_fwd  y = keep ? x * s : 0 over x / y act [B, Tmax, H]: every row (step < 0) or the B rows of step `step`
+//   hidden_dropout_bwd  in place: dhout f32 [B, Tmax, H] = (t < lengths[b] && keep) ? dhout * s : 0
+// keep is drawn from Philox(seed) or read from keep_u (f32 [B, Tmax, H]); both index it by the flat element index (gen_dropout.hip)
+int drop_check(const gic_decoder_dropout* d, const char* who);
+int hidden_dropout_fwd(int dt, const void* x, void* y, const float* keep_u, uint64_t seed, float p, int B, int Tmax, int H, int step,
+                       hipStream_t stream);
+int hidden_dropout_bwd(float* dhout, const int32_t* lengths, const float* keep_u, uint64_t seed, float p, int B, int Tmax, int H,
+                       hipStream_t stream);
 
 // disc_cond.hip: the conditioned discriminator's match-term backward for disc_bwd_t (disc.hip): dydrop[m, :] = scale g[m] q[m / R, :]
 // (f32 [B*R, Fp], pad columns zero) and, when d_q is not null, d_q[b, :] = scale sum_r g[b R + r] ydrop[b R + r, :F] (f32 [B, F])

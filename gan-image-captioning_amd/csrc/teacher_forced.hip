@@ -30,6 +30,11 @@
 // in front of the softmax backward).  The zero alpha rows of padded steps make their attention terms vanish, their zero gates / zero
 // dhout rows the LSTM terms.
 //
+// Output dropout (gen_dropout.hip; the gic_*_drop entry points, io.drop / g.drop set): hidden_dropout_fwd writes drop->hdrop from hout
+// -- over all rows after the loop, or under scheduled sampling over the rows of step t in front of ss_step_logits -- and the vocabulary
+// product reads hdrop; the backward gives decoder_output_bwd hdrop for hout and runs hidden_dropout_bwd where zero_past_length stood.
+// Neither recurrence changes: the state keeps the undropped h.  With drop null not one launch, argument or check differs.
+//
 // Entry path: every extern "C" function is a model (LstmTrain / AttnTrain: the decoder's dims, weights, state and, with attention,
 // the feature map; its shape check, its buffer checks with its own texts, run()) and one call of forward_entry, backward_entry or
 // ws_bytes_entry.  Order of checks: shapes, null arguments, caps (L = 1 has no caption column), Tmax, then the scheduled-sampling
@@ -97,6 +102,7 @@ struct TfIo {
   void* out; float* h_n; float* c_n;
   const gic_sched_sample_opts* ss;         // scheduled sampling, or null
   hipStream_t stream;
+  const gic_decoder_dropout* drop = nullptr;      // output dropout (gen_dropout.hip), or null: the gic_*_drop entry points set it
 };
 
 void* act(const void* p, long n, size_t asz) { return (char*)p + n * (long)asz; }      // p + n compute-dtype values
@@ -206,6 +212,8 @@ int teacher_forced(const Rec& rec, const TfIo& io) {
   const int B = c.B, T = c.L, V = c.V, E = c.E, H = c.H, Tmax = io.Tmax;
   const gic_sched_sample_opts* ss = io.ss;
   const bool ss_fused = ss && ss_fused_logits(c.dt, B, V, E, H, rec.layers());
+  const gic_decoder_dropout* dr = io.drop;
+  const void* hproj = dr ? dr->hdrop : rec.st->hout;       // what the vocabulary projection consumes
   // ss_tail depends on nothing begin() enqueues and nothing there on it.  That it precedes the attention decoder's begin() and follows
   // the LSTM decoder's is history, not design: kept, so that a kernel trace of either call lists the launches it always listed
   auto tail = [&] { return ss ? ss_tail(io.caps, ss->inputs, ss->replaced, B, T - 1, Tmax - 1, io.stream) : (int)GIC_OK; };
@@ -215,7 +223,8 @@ int teacher_forced(const Rec& rec, const TfIo& io) {
   for (int t = 0; t < Tmax; ++t) {
     GIC_PROPAGATE(rec.step(io, t));
     if (!ss) continue;
-    GIC_PROPAGATE(ss_step_logits(c.dt, rec.st->hout, t, Tmax, rec.S->wout, rec.P->b_out, io.logits_ws, B, V, H, ss_fused, io.stream));
+    if (dr) GIC_PROPAGATE(hidden_dropout_fwd(c.dt, rec.st->hout, dr->hdrop, dr->keep_u, dr->seed, dr->p, B, Tmax, H, t, io.stream));
+    GIC_PROPAGATE(ss_step_logits(c.dt, hproj, t, Tmax, rec.S->wout, rec.P->b_out, io.logits_ws, B, V, H, ss_fused, io.stream));
     if (t + 1 < Tmax) {
       SsPickArgs a;
       a.logits = io.logits_ws + (long)t * V; a.ld_logits = (long)Tmax * V;
@@ -228,8 +237,9 @@ int teacher_forced(const Rec& rec, const TfIo& io) {
   }
   const long rows = (long)B * Tmax;
   if (!ss) {  // one projection over all B * Tmax rows
+    if (dr) GIC_PROPAGATE(hidden_dropout_fwd(c.dt, rec.st->hout, dr->hdrop, dr->keep_u, dr->seed, dr->p, B, Tmax, H, -1, io.stream));
     GemmDesc g;
-    g.A = rec.st->hout; g.lda = H; g.B = rec.S->wout; g.ldb = H; g.C = io.logits_ws; g.ldc = V;
+    g.A = hproj; g.lda = H; g.B = rec.S->wout; g.ldb = H; g.C = io.logits_ws; g.ldc = V;
     g.M = (int)rows; g.N = V; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = rec.P->b_out;
     g.no_split = Rec::kNoSplitVocab;
     GIC_PROPAGATE(gemm(g, io.stream));
@@ -248,6 +258,7 @@ struct TfGrad {
   const void* pred; const int64_t* caps; const int32_t* lengths; int Tmax;
   const void* d_pred; float temperature; int pretrain;
   hipStream_t stream;
+  const gic_decoder_dropout* drop = nullptr;      // the forward call's output dropout, or null
 };
 
 // ---- the entry path (header comment): a model is the decoder's side of a call
@@ -322,29 +333,33 @@ int open_entry(Model& m, const char* who, bool args, const int64_t* caps, int Tm
   return GIC_OK;
 }
 
-// gic_*_forward_tf (io.ss null) and gic_*_forward_ss (io.ss = the options, io.logits_ws = the caller's ws)
+// gic_*_forward_tf (io.ss null) and gic_*_forward_ss (io.ss = the options, io.logits_ws = the caller's ws); dropout: a gic_*_drop
+// entry point, whose io.drop is checked after everything its plain counterpart checks
 template <typename Model>
-int forward_entry(Model m, const char* who, bool args, const TfIo& io) {
+int forward_entry(Model m, const char* who, bool args, const TfIo& io, bool dropout = false) {
   GIC_PROPAGATE(open_entry(m, who, args && io.features && io.lengths && io.logits_ws && io.out && io.h_n && io.c_n, io.caps, io.Tmax));
   if (io.ss) {
     GIC_PROPAGATE(ss_check_opts(io.ss, m.c.L, who));
     GIC_CHECK_ARG(((uintptr_t)io.logits_ws & 15) == 0, "%s: ws must be 16-byte aligned", who);
   }
   GIC_PROPAGATE(m.check_fwd(who));
+  if (dropout) GIC_PROPAGATE(drop_check(io.drop, who));
   return m.run(io);
 }
 
 // the output layer over B * Tmax rows and the padded steps' zero gradient, then the decoder's recurrent backward on the Tmax view:
 // the saved state and every [B, Tmax, .] tensor are laid out for Tmax steps
 template <typename Model>
-int backward_entry(Model m, const char* who, const TfGrad& g) {
+int backward_entry(Model m, const char* who, const TfGrad& g, bool dropout = false) {
   GIC_PROPAGATE(open_entry(m, who, m.ws && m.G && g.pred && g.lengths && g.d_pred, g.caps, g.Tmax));
   GIC_PROPAGATE(m.check_bwd(who));
+  if (dropout) GIC_PROPAGATE(drop_check(g.drop, who));
   auto view = m.c;
   view.L = g.Tmax;
   GIC_PROPAGATE(decoder_output_bwd(view.dt, view.B, g.Tmax, view.V, view.H, g.pred, g.d_pred, g.temperature, nullptr, g.pretrain, m.ws->dlogits,
-                                   m.S->wout, m.st->hout, m.ws->dhout, m.G->w_out, m.G->b_out, g.stream));
-  GIC_PROPAGATE(zero_past_length(m.ws->dhout, g.lengths, view.B, g.Tmax, view.H, g.stream));
+                                   m.S->wout, g.drop ? g.drop->hdrop : m.st->hout, m.ws->dhout, m.G->w_out, m.G->b_out, g.stream));
+  if (g.drop) GIC_PROPAGATE(hidden_dropout_bwd(m.ws->dhout, g.lengths, g.drop->keep_u, g.drop->seed, g.drop->p, view.B, g.Tmax, view.H, g.stream));
+  else GIC_PROPAGATE(zero_past_length(m.ws->dhout, g.lengths, view.B, g.Tmax, view.H, g.stream));
   return m.recurrent_bwd(view, g);
 }
 
@@ -421,6 +436,61 @@ int gic_attn_forward_tf_bwd(const gic_attn_dims* dims, const gic_attn_params* P,
                             const void* d_pred, const float* d_alphas, float temperature, int pretrain, const gic_attn_grads* G, void* stream) {
   return backward_entry(AttnTrain{dims, P, S, st, fmap, nullptr, ws, G, d_alphas}, "attn_forward_tf_bwd",
                         {pred, caps, lengths, Tmax, d_pred, temperature, pretrain, (hipStream_t)stream});
+}
+
+// ---- the same calls with output dropout: the plain entry's arguments, then drop
+int gic_decoder_forward_tf_drop(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
+                                const gic_decoder_state* st, const float* features, const int64_t* caps, const int32_t* lengths, int Tmax,
+                                const float* noise_u, uint64_t seed, float temperature, int pretrain, float* logits_ws, int64_t* ids_ws,
+                                void* out, float* h_n, float* c_n, const gic_decoder_dropout* drop, void* stream) {
+  return forward_entry(LstmTrain{dims, P, S, st}, "decoder_forward_tf_drop", ids_ws != nullptr,
+                       {features, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, out, h_n, c_n, nullptr, (hipStream_t)stream, drop},
+                       true);
+}
+
+int gic_decoder_forward_ss_drop(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
+                                const gic_decoder_state* st, const float* features, const int64_t* caps, const int32_t* lengths, int Tmax,
+                                const gic_sched_sample_opts* opts, void* ws, void* out, float* h_n, float* c_n,
+                                const gic_decoder_dropout* drop, void* stream) {
+  return forward_entry(LstmTrain{dims, P, S, st}, "decoder_forward_ss_drop", opts != nullptr,
+                       {features, caps, lengths, Tmax, nullptr, 0, 1.f, 1, (float*)ws, out, h_n, c_n, opts, (hipStream_t)stream, drop}, true);
+}
+
+int gic_decoder_forward_tf_drop_bwd(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
+                                    const gic_decoder_state* st, const gic_decoder_bwd_ws* ws, const void* pred, const int64_t* caps,
+                                    const int32_t* lengths, int Tmax, const void* d_pred, float temperature, int pretrain,
+                                    const gic_decoder_grads* G, const gic_decoder_dropout* drop, void* stream) {
+  return backward_entry(LstmTrain{dims, P, S, st, ws, G}, "decoder_forward_tf_drop_bwd",
+                        {pred, caps, lengths, Tmax, d_pred, temperature, pretrain, (hipStream_t)stream, drop}, true);
+}
+
+int gic_attn_forward_tf_drop(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st,
+                             const float* features, const void* fmap, const int64_t* caps, const int32_t* lengths, int Tmax,
+                             const float* noise_u, uint64_t seed, float temperature, int pretrain, float* logits_ws, void* out, float* alphas,
+                             float* h_n, float* c_n, const gic_decoder_dropout* drop, void* stream) {
+  return forward_entry(AttnTrain{dims, P, S, st, fmap, alphas}, "attn_forward_tf_drop", true,
+                       {features, caps, lengths, Tmax, noise_u, seed, temperature, pretrain, logits_ws, out, h_n, c_n, nullptr, (hipStream_t)stream, drop},
+                       true);
+}
+
+int gic_attn_forward_ss_drop(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st,
+                             const float* features, const void* fmap, const int64_t* caps, const int32_t* lengths, int Tmax,
+                             const gic_sched_sample_opts* opts, void* ws, void* out, float* alphas, float* h_n, float* c_n,
+                             const gic_decoder_dropout* drop, void* stream) {
+  if (det_mode()) {
+    set_last_error("attn_forward_ss: the attention decoder is not available in the deterministic mode (gic_set_deterministic)");
+    return GIC_STATUS_UNSUPPORTED;
+  }
+  return forward_entry(AttnTrain{dims, P, S, st, fmap, alphas}, "attn_forward_ss_drop", opts != nullptr,
+                       {features, caps, lengths, Tmax, nullptr, 0, 1.f, 1, (float*)ws, out, h_n, c_n, opts, (hipStream_t)stream, drop}, true);
+}
+
+int gic_attn_forward_tf_drop_bwd(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_attn_state* st,
+                                 const gic_attn_bwd_ws* ws, const void* fmap, const void* pred, const int64_t* caps, const int32_t* lengths,
+                                 int Tmax, const void* d_pred, const float* d_alphas, float temperature, int pretrain,
+                                 const gic_attn_grads* G, const gic_decoder_dropout* drop, void* stream) {
+  return backward_entry(AttnTrain{dims, P, S, st, fmap, nullptr, ws, G, d_alphas}, "attn_forward_tf_drop_bwd",
+                        {pred, caps, lengths, Tmax, d_pred, temperature, pretrain, (hipStream_t)stream, drop}, true);
 }
 
 }  // extern "C"

@@ -613,6 +613,62 @@ def _ss_opts(prob: float, pick: str, coin_u, noise_u, seed: int, B: int, Lc: int
     return o, inputs, replaced, (coin_u, noise_u)
 
 
+def _drop_p(dropout) -> float:
+    p = float(dropout)
+    if not 0.0 <= p < 1.0:                        # false for NaN too
+        raise ValueError(f"dropout must be in [0, 1), got {dropout}")
+    return p
+
+
+def _drop_keep_u(keep_u, shape):
+    if keep_u is None:
+        return None
+    if tuple(keep_u.shape) != tuple(shape):
+        raise ValueError(f"keep_u must be {list(shape)}")
+    return keep_u.contiguous().float()
+
+
+def _drop_struct(d) -> L.DecoderDropout:
+    """gic_decoder_dropout of what ``saved`` carries: dict(p, seed, keep_u, hdrop)."""
+    o = L.DecoderDropout()
+    o.p, o.seed, o.keep_u, o.hdrop = d["p"], int(d["seed"]) & (2 ** 64 - 1), ptr(d["keep_u"]), ptr(d["hdrop"])
+    return o
+
+
+def hidden_dropout(x: torch.Tensor, p: float, seed: int = 0, keep_u: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """gic_hidden_dropout, the forward stage of the decoder's output dropout on its own: y = keep ? x * s : 0 with s = 1 / (1 - p) in
+    f32 over ``x`` f32 or bf16 [..., H] (contiguous; any H, any alignment), element (r, h) of the [rows, H] view drawn at the flat
+    index r * H + h from Philox(``seed``) or read from ``keep_u`` f32 of x's shape.  ``out``: a contiguous tensor of x's shape and dtype."""
+    require_gpu(x, keep_u, out)
+    if x.dtype not in (torch.float32, torch.bfloat16) or x.dim() < 1 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous float32 or bfloat16 tensor [..., H]")
+    keep_u = _drop_keep_u(keep_u, x.shape)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError("out must be contiguous with x's shape and dtype")
+    H = x.shape[-1]
+    L.check(L.load().gic_hidden_dropout(ptr(x), L.F32 if x.dtype == torch.float32 else L.BF16, x.numel() // max(H, 1), H, float(p),
+                                        int(seed) & (2 ** 64 - 1), ptr(keep_u), ptr(out), stream_ptr()), "gic_hidden_dropout")
+    return out
+
+
+def hidden_dropout_bwd(dhout: torch.Tensor, lengths, p: float, seed: int = 0, keep_u: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gic_hidden_dropout_bwd, in place on ``dhout`` f32 [B, Tmax, H] (contiguous): dhout = (t < lengths[b] && keep) ? dhout * s : 0 with
+    the mask of ``hidden_dropout(x [B, Tmax, H], p, seed, keep_u)``.  ``lengths``: B values.  Returns ``dhout``."""
+    require_gpu(dhout, keep_u)
+    if dhout.dtype != torch.float32 or dhout.dim() != 3 or not dhout.is_contiguous():
+        raise ValueError("dhout must be a contiguous float32 tensor [B, Tmax, H]")
+    B, Tmax, H = dhout.shape
+    keep_u = _drop_keep_u(keep_u, dhout.shape)
+    lens = torch.as_tensor(lengths).to(device=dhout.device, dtype=torch.int32).contiguous()
+    if lens.numel() != B:
+        raise ValueError(f"lengths must hold {B} values")
+    L.check(L.load().gic_hidden_dropout_bwd(ptr(dhout), ptr(lens), B, Tmax, H, float(p), int(seed) & (2 ** 64 - 1), ptr(keep_u),
+                                            stream_ptr()), "gic_hidden_dropout_bwd")
+    return dhout
+
+
 def step_part_floats(B: int, Lc: int, V: int) -> int:
     """Floats of the fused step kernels' scratch (state ``part``): [2][L][B][ceil(V/64)] tile partials + [L][B] 64-bit argmax keys +
     four reserved words -- decoder_step_part_floats of csrc/decoder_step.hip, the one owner of the layout (= gic_decoder_state_bytes'
@@ -642,11 +698,14 @@ class _TeacherForced:
         return [torch.empty_like(p) for p in params] + [torch.empty(B, self.E, device=params[0].device, dtype=torch.float32)]
 
     def _tf_forward(self, params, features, fmap, caps, lengths, tmax, state, want_alphas, ss, noise_u=None, seed=0, temperature=1.0,
-                    pretrain=True):
+                    pretrain=True, drop=(0.0, 0, None)):
         """``ss``: None, or _ss_opts' arguments but the shapes (prob, pick, coin_u, noise_u, seed) -- then the scheduled-sampling call.
+        ``drop``: (dropout, dropout_seed, keep_u) -- with dropout > 0 the gic_*_drop form of the call, whose ``hdrop`` is allocated
+        here and carried in ``saved["drop"]`` with (p, seed, keep_u) for the backward.
         Returns (pred, (h_n, c_n), *alphas), saved[, inputs, replaced]."""
         self.check_params(params)
-        require_gpu(features, fmap, caps, noise_u, *(ss[2:4] if ss else ()))
+        drop_p = _drop_p(drop[0])
+        require_gpu(features, fmap, caps, noise_u, *(ss[2:4] if ss else ()), *((drop[2],) if drop_p > 0.0 else ()))
         B, Lc = caps.shape
         T = Lc + 1
         Tmax, len_dev = _tf_lengths(lengths, B, T, tmax)
@@ -674,18 +733,34 @@ class _TeacherForced:
         else:
             name, ws = f"{self._PREFIX}_forward_tf", self._tf_ws(B, T, Tmax, dev)
             mode = (ptr(noise_u), int(seed) & (2 ** 64 - 1), float(temperature), int(bool(pretrain)))
+        dropped = None
+        if drop_p > 0.0:         # hdrop is the call's own: gic_decoder_state_bytes pins the state's list
+            dropped = {"p": drop_p, "seed": int(drop[1]), "keep_u": _drop_keep_u(drop[2], (B, Tmax, self.H)),
+                       "hdrop": torch.empty(B, Tmax, self.H, device=dev, dtype=self.act)}
+            name += "_drop"
+        tail = (C.byref(_drop_struct(dropped)),) if dropped else ()
         len_dev, caps = len_dev.to(dev), caps.contiguous()
         L.check(getattr(L.load(), name)(
             C.byref(d), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)), C.byref(self._state_struct(st)),
             ptr(features.contiguous().float()), *map(ptr, maps), ptr(caps), ptr(len_dev), Tmax, *mode, *map(ptr, ws), ptr(out),
-            *map(ptr, alphas), ptr(h_n), ptr(c_n), stream_ptr()), name)
+            *map(ptr, alphas), ptr(h_n), ptr(c_n), *tail, stream_ptr()), name)
         if maps:
             st["fmap"] = maps[0]
         saved = {"st": st, "caps": inputs if ss else caps, "len_dev": len_dev, "Tmax": Tmax, "T": T}
+        if dropped:
+            saved["drop"] = dropped
         return (out, (h_n, c_n), *alphas), saved, *((inputs, replaced) if ss else ())
 
-    def _tf_backward(self, params, saved, pred, d_pred, d_alphas, temperature, pretrain, ws, grads):
+    def _tf_backward(self, params, saved, pred, d_pred, d_alphas, temperature, pretrain, ws, grads, drop=(0.0, 0, None)):
+        """``drop``: (dropout, dropout_seed, keep_u); with dropout > 0 they stand in for what ``saved`` carries (the forward call must
+        have dropped: ``saved`` holds its hdrop), with 0 the forward call's own values are used."""
         B, Tmax, dev = pred.shape[0], saved["Tmax"], pred.device
+        dropped = saved.get("drop")
+        if _drop_p(drop[0]) > 0.0:
+            if dropped is None:
+                raise ValueError("forward_tf_bwd: dropout given, but the forward call that returned `saved` ran without it")
+            require_gpu(drop[2])
+            dropped = dict(dropped, p=float(drop[0]), seed=int(drop[1]), keep_u=_drop_keep_u(drop[2], (B, Tmax, self.H)))
         if d_pred is None:
             d_pred = torch.zeros(pred.shape, device=dev, dtype=self.act)
         if tuple(d_pred.shape) != tuple(pred.shape):
@@ -695,13 +770,14 @@ class _TeacherForced:
         self.prepare(params)
         ws = ws if ws is not None else self.alloc_bwd_ws(B, saved[self._TF_BWD_WS_STEPS], dev)
         grads = grads if grads is not None else self.alloc_grads(params, B)
-        name = f"{self._PREFIX}_forward_tf_bwd"
+        name = f"{self._PREFIX}_forward_tf_drop_bwd" if dropped else f"{self._PREFIX}_forward_tf_bwd"
+        tail = (C.byref(_drop_struct(dropped)),) if dropped else ()
         st = saved["st"]
         L.check(getattr(L.load(), name)(
             C.byref(self.dims(B, saved["T"])), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)),
             C.byref(self._state_struct(st)), C.byref(self._bwd_ws_struct(ws)), *map(ptr, self._decode_maps(st.get("fmap"), B)), ptr(pred),
             ptr(saved["caps"]), ptr(saved["len_dev"]), Tmax, ptr(d_pred), *map(ptr, d_alphas), float(temperature), int(bool(pretrain)),
-            C.byref(self._pstruct(grads[:-1], self._GRADS, grads[-1])), stream_ptr()), name)
+            C.byref(self._pstruct(grads[:-1], self._GRADS, grads[-1])), *tail, stream_ptr()), name)
         return grads
 
 
@@ -994,12 +1070,16 @@ class DecoderEngine(_CaptionDecodes, _TeacherForced):
         return (None if ids_only else out), ids, st
 
     def forward_tf(self, params, features: torch.Tensor, caps: torch.Tensor, lengths, temperature: float, pretrain: bool = False,
-                   noise_u: Optional[torch.Tensor] = None, seed: int = 0, keep_state: bool = False, tmax: Optional[int] = None):
+                   noise_u: Optional[torch.Tensor] = None, seed: int = 0, keep_state: bool = False, tmax: Optional[int] = None,
+                   dropout: float = 0.0, dropout_seed: int = 0, keep_u: Optional[torch.Tensor] = None):
         """gic_decoder_forward_tf: Decoder.forward (teacher forcing, generator.py:39-53).
         Returns (pred act [B, max(lengths), V], (h_n, c_n) f32 [NL, B, H]); with ``keep_state`` also what ``forward_tf_bwd`` needs.
         ``tmax``: decode that many steps and take ``lengths`` as device int32 values in 1..T unread (no host sync); pred is then
-        [B, tmax, V]."""
-        head, saved = self._tf_forward(params, features, None, caps, lengths, tmax, None, False, None, noise_u, seed, temperature, pretrain)
+        [B, tmax, V].  ``dropout`` p > 0: output dropout (gic_decoder_forward_tf_drop) -- the LSTM output is dropped with probability p
+        in front of the vocabulary projection, by Philox(``dropout_seed``) or ``keep_u`` f32 [B, max(lengths), H] (keep = u >= p); the
+        recurrence, h_n and c_n keep the undropped h.  ``saved["drop"]`` then carries (p, seed, keep_u, hdrop) for the backward."""
+        head, saved = self._tf_forward(params, features, None, caps, lengths, tmax, None, False, None, noise_u, seed, temperature, pretrain,
+                                       (dropout, dropout_seed, keep_u))
         return (*head, saved) if keep_state else head
 
     def _tf_check_inputs(self, features, caps, B: int) -> None:
@@ -1011,19 +1091,24 @@ class DecoderEngine(_CaptionDecodes, _TeacherForced):
 
     def forward_scheduled(self, params, features: torch.Tensor, caps: torch.Tensor, lengths, sample_prob: float, pick: str = "sample",
                           coin_u: Optional[torch.Tensor] = None, noise_u: Optional[torch.Tensor] = None, seed: int = 0,
-                          tmax: Optional[int] = None):
+                          tmax: Optional[int] = None, dropout: float = 0.0, dropout_seed: int = 0, keep_u: Optional[torch.Tensor] = None):
         """gic_decoder_forward_ss: ``forward_tf(pretrain=True, keep_state=True)`` with scheduled sampling -- the input of step t >= 1 is
         the model's own pick from step t-1's logits where coin < ``sample_prob`` (and t < lengths[b]), else caps[:, t-1].  Returns
         (pred, (h_n, c_n), saved, inputs int64 [B, L], replaced int32 [B, L]); ``saved`` carries ``inputs`` as its captions, so
-        ``forward_tf_bwd`` runs on it unchanged.  ``coin_u`` f32 [B, L] / ``noise_u`` f32 [L, B, V] replace the device draws."""
-        head, *rest = self._tf_forward(params, features, None, caps, lengths, tmax, None, False, (sample_prob, pick, coin_u, noise_u, seed))
+        ``forward_tf_bwd`` runs on it unchanged.  ``coin_u`` f32 [B, L] / ``noise_u`` f32 [L, B, V] replace the device draws.
+        ``dropout`` / ``dropout_seed`` / ``keep_u`` as forward_tf (gic_decoder_forward_ss_drop): the picks see the dropped logits."""
+        head, *rest = self._tf_forward(params, features, None, caps, lengths, tmax, None, False, (sample_prob, pick, coin_u, noise_u, seed),
+                                       drop=(dropout, dropout_seed, keep_u))
         return (*head, *rest)
 
     def forward_tf_bwd(self, params, saved, pred: torch.Tensor, d_pred: torch.Tensor, temperature: float, pretrain: bool = False,
-                       ws=None, grads=None) -> List[torch.Tensor]:
+                       ws=None, grads=None, dropout: float = 0.0, dropout_seed: int = 0,
+                       keep_u: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
         """gic_decoder_forward_tf_bwd: gradients of a loss on ``pred`` of the ``forward_tf(..., keep_state=True)`` call that returned
-        ``saved``; the list is ordered as ``sample_bwd``'s (parameters, then d features)."""
-        return self._tf_backward(params, saved, pred, d_pred, None, temperature, pretrain, ws, grads)
+        ``saved``; the list is ordered as ``sample_bwd``'s (parameters, then d features).  A forward call with dropout is followed by
+        gic_decoder_forward_tf_drop_bwd with the (p, seed, keep_u, hdrop) that ``saved`` carries; ``dropout`` > 0 with ``dropout_seed``
+        / ``keep_u`` stands in for the first three."""
+        return self._tf_backward(params, saved, pred, d_pred, None, temperature, pretrain, ws, grads, (dropout, dropout_seed, keep_u))
 
     def sample_bwd(self, params, st, out: torch.Tensor, ids: torch.Tensor, d_out: torch.Tensor, temperature: float,
                    pretrain: bool = False, ws=None, grads=None, phases: int = 3, dev_scalars=None) -> List[torch.Tensor]:
@@ -1645,13 +1730,15 @@ class AttnDecoderEngine(_CaptionDecodes, _TeacherForced):
 
     def forward_tf(self, params, features, fmap, caps: torch.Tensor, lengths, temperature: float, pretrain: bool = False,
                    noise_u: Optional[torch.Tensor] = None, seed: int = 0, want_alphas: bool = False, keep_state: bool = False,
-                   tmax: Optional[int] = None, state=None):
+                   tmax: Optional[int] = None, state=None, dropout: float = 0.0, dropout_seed: int = 0,
+                   keep_u: Optional[torch.Tensor] = None):
         """gic_attn_forward_tf: the teacher-forced decode (DecoderEngine.forward_tf with the attention step).  ``caps`` int64 [B, T-1],
         ``lengths`` B values in 1..T, ``fmap`` [B, P, C] (cast to the compute dtype as in sample_fwd).  Returns (pred act [B, Tmax, V],
         (h_n, c_n) f32 [1, B, H], alphas f32 [B, Tmax, P] or None); with ``keep_state`` also what ``forward_tf_bwd`` needs.  ``tmax``
-        as DecoderEngine.forward_tf.  ``state``: a caller-owned state (alloc_state(B, T, dev)) as in sample_fwd."""
+        as DecoderEngine.forward_tf.  ``state``: a caller-owned state (alloc_state(B, T, dev)) as in sample_fwd.  ``dropout`` /
+        ``dropout_seed`` / ``keep_u``: output dropout as DecoderEngine.forward_tf (gic_attn_forward_tf_drop)."""
         head, saved = self._tf_forward(params, features, fmap, caps, lengths, tmax, state, want_alphas, None, noise_u, seed, temperature,
-                                       pretrain)
+                                       pretrain, (dropout, dropout_seed, keep_u))
         return (*head, saved) if keep_state else head
 
     def _tf_check_inputs(self, features, caps, B: int) -> None:
@@ -1679,18 +1766,22 @@ class AttnDecoderEngine(_CaptionDecodes, _TeacherForced):
 
     def forward_scheduled(self, params, features, fmap, caps: torch.Tensor, lengths, sample_prob: float, pick: str = "sample",
                           coin_u: Optional[torch.Tensor] = None, noise_u: Optional[torch.Tensor] = None, seed: int = 0,
-                          tmax: Optional[int] = None, state=None):
+                          tmax: Optional[int] = None, state=None, dropout: float = 0.0, dropout_seed: int = 0,
+                          keep_u: Optional[torch.Tensor] = None):
         """gic_attn_forward_ss: ``forward_tf(pretrain=True, want_alphas=True, keep_state=True)`` with scheduled sampling
-        (DecoderEngine.forward_scheduled).  Returns (pred, (h_n, c_n), alphas, saved, inputs, replaced).  ``state`` as forward_tf."""
-        head, *rest = self._tf_forward(params, features, fmap, caps, lengths, tmax, state, True, (sample_prob, pick, coin_u, noise_u, seed))
+        (DecoderEngine.forward_scheduled).  Returns (pred, (h_n, c_n), alphas, saved, inputs, replaced).  ``state`` as forward_tf;
+        ``dropout`` / ``dropout_seed`` / ``keep_u`` as there (gic_attn_forward_ss_drop)."""
+        head, *rest = self._tf_forward(params, features, fmap, caps, lengths, tmax, state, True, (sample_prob, pick, coin_u, noise_u, seed),
+                                       drop=(dropout, dropout_seed, keep_u))
         return (*head, *rest)
 
     def forward_tf_bwd(self, params, saved, pred: torch.Tensor, d_pred: Optional[torch.Tensor], temperature: float, pretrain: bool = False,
-                       d_alphas: Optional[torch.Tensor] = None, ws=None, grads=None) -> List[torch.Tensor]:
+                       d_alphas: Optional[torch.Tensor] = None, ws=None, grads=None, dropout: float = 0.0, dropout_seed: int = 0,
+                       keep_u: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
         """gic_attn_forward_tf_bwd: gradients of a loss on ``pred`` (``d_pred``; None = zeros) and on the alphas (``d_alphas`` f32
         [B, Tmax, P] or None) of the ``forward_tf(..., keep_state=True)`` call that returned ``saved``; ordered as ``sample_bwd``'s
-        (parameters in NAMES order, then d features)."""
-        return self._tf_backward(params, saved, pred, d_pred, d_alphas, temperature, pretrain, ws, grads)
+        (parameters in NAMES order, then d features).  ``dropout`` / ``dropout_seed`` / ``keep_u`` as DecoderEngine.forward_tf_bwd."""
+        return self._tf_backward(params, saved, pred, d_pred, d_alphas, temperature, pretrain, ws, grads, (dropout, dropout_seed, keep_u))
 
     def rollout_ws_bytes(self, B: int, Lc: int, rows: int) -> int:
         """Bytes of gic_attn_rollout's workspace (host-only query)."""

@@ -133,10 +133,10 @@ class _ForwardTfFn(torch.autograd.Function):
     """Decoder.forward with autograd (generator.py:39-53): gic_decoder_forward_tf / gic_decoder_forward_tf_bwd."""
 
     @staticmethod
-    def forward(ctx, eng, temperature, pretrain, caps, lengths, noise_u, seed, tmax, features, *params):
+    def forward(ctx, eng, drop, temperature, pretrain, caps, lengths, noise_u, seed, tmax, features, *params):
         dparams = [p.detach() for p in params]
         pred, (h_n, c_n), saved = eng.forward_tf(dparams, features.detach().float(), caps, lengths, temperature, pretrain, noise_u, seed,
-                                                 keep_state=True, tmax=tmax)
+                                                 keep_state=True, tmax=tmax, **_drop_kw(drop))
         ctx.eng, ctx.temperature, ctx.pretrain, ctx.saved, ctx.dparams = eng, temperature, pretrain, saved, dparams
         ctx.save_for_backward(pred)
         ctx.mark_non_differentiable(h_n, c_n)
@@ -147,17 +147,17 @@ class _ForwardTfFn(torch.autograd.Function):
         (pred,) = ctx.saved_tensors
         grads = ctx.eng.forward_tf_bwd(ctx.dparams, ctx.saved, pred, d_pred, ctx.temperature, ctx.pretrain)
         ctx.saved = None
-        return (None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
+        return (None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
 
 
 class _ForwardSsFn(torch.autograd.Function):
     """Decoder.forward_scheduled with autograd: gic_decoder_forward_ss, then gic_decoder_forward_tf_bwd over the inputs it realised."""
 
     @staticmethod
-    def forward(ctx, eng, sample_prob, pick, caps, lengths, coin_u, noise_u, seed, tmax, features, *params):
+    def forward(ctx, eng, drop, sample_prob, pick, caps, lengths, coin_u, noise_u, seed, tmax, features, *params):
         dparams = [p.detach() for p in params]
         pred, (h_n, c_n), saved, inputs, replaced = eng.forward_scheduled(dparams, features.detach().float(), caps, lengths, sample_prob,
-                                                                           pick, coin_u, noise_u, seed, tmax=tmax)
+                                                                           pick, coin_u, noise_u, seed, tmax=tmax, **_drop_kw(drop))
         ctx.eng, ctx.saved, ctx.dparams = eng, saved, dparams
         ctx.save_for_backward(pred)
         ctx.mark_non_differentiable(h_n, c_n, inputs, replaced)
@@ -168,7 +168,7 @@ class _ForwardSsFn(torch.autograd.Function):
         (pred,) = ctx.saved_tensors
         grads = ctx.eng.forward_tf_bwd(ctx.dparams, ctx.saved, pred, d_pred, 1.0, True)
         ctx.saved = None
-        return (None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
+        return (None, None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
 
 
 def _ss_args(sample_prob, pick, coin_u, noise_u, seed):
@@ -181,6 +181,22 @@ def _ss_args(sample_prob, pick, coin_u, noise_u, seed):
     if seed is None:
         seed = 0 if (coin_u is not None and (noise_u is not None or pick == "argmax")) or p == 0.0 else SEEDS.next()
     return p, int(seed)
+
+
+def _drop_args(dropout, dropout_seed, keep_u):
+    """(p, seed, keep_u) of a decode's output dropout, checked: ``dropout_seed`` None = the next of SEEDS when a mask is drawn (p > 0
+    and no ``keep_u``) -- taken after the call's other seeds, so a call with ``dropout`` = 0 leaves the seed sequence as it was."""
+    p = float(dropout)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout must be in [0, 1), got {dropout}")
+    if dropout_seed is None:
+        dropout_seed = SEEDS.next() if p > 0.0 and keep_u is None else 0
+    return p, int(dropout_seed), keep_u
+
+
+def _drop_kw(drop):
+    """The engine keywords of ``_drop_args``' triple."""
+    return {"dropout": drop[0], "dropout_seed": drop[1], "keep_u": drop[2]}
 
 
 def _teacher_inputs(caps, vocab: int):
@@ -263,48 +279,57 @@ class Decoder(nn.Module):
         return _SampleFn.apply(self.engine(), float(self.temperature), bool(pretrain), int(max_caption_len), noise_u, seed,
                                h0, c0, features, *self.param_list())
 
-    def forward(self, features, caps, lengths, pretrain=False, noise_u=None, max_length=None):
+    def forward(self, features, caps, lengths, pretrain=False, noise_u=None, max_length=None, dropout=0.0, dropout_seed=None, keep_u=None):
         """Teacher-forced decode (generator.py:39-53): inputs [features ; embed(caps)] packed with ``lengths``; returns
         (pred [B, max(lengths), V], (h_n, c_n)) with pred = logits (pretrain) or softmax((logits + gumbel) * temperature).
         Dead on the reference's training path (training.py never calls it), kept for the module surface.  Gradients flow through
         ``pred`` to the decoder parameters and ``features`` (padded positions reach the projection's bias only, as
         pad_packed_sequence's zeros do); the returned hidden state is not differentiated.  ``noise_u`` [B, max(lengths), V]
         replaces the device draw (parity runs).  ``max_length``: decode that many steps with ``lengths`` a device tensor that is not
-        read back (no host sync; pred is [B, max_length, V], rows past a length as above)."""
+        read back (no host sync; pred is [B, max_length, V], rows past a length as above).  ``dropout`` p in [0, 1): output dropout --
+        the LSTM output is dropped with probability p (and the rest scaled by 1 / (1 - p)) in front of the vocabulary projection; the
+        recurrence and (h_n, c_n) keep the undropped h.  The mask is Philox(``dropout_seed``; None = the next of SEEDS) or ``keep_u`` f32
+        [B, max(lengths), H] (keep = u >= p).  It is the caller's switch, not the module's training flag: a no-grad call drops too."""
         seed = 0 if noise_u is not None else SEEDS.next()
+        drop = _drop_args(dropout, dropout_seed, keep_u)
         params = self.param_list()
         if not torch.is_grad_enabled() or not (features.requires_grad or any(p.requires_grad for p in params)):
-            return self._forward_no_grad(features, caps, lengths, pretrain, noise_u, seed, max_length)
-        pred, h_n, c_n = _ForwardTfFn.apply(self.engine(), float(self.temperature), bool(pretrain), caps, lengths, noise_u, seed,
+            return self._forward_no_grad(features, caps, lengths, pretrain, noise_u, seed, max_length, drop)
+        pred, h_n, c_n = _ForwardTfFn.apply(self.engine(), drop, float(self.temperature), bool(pretrain), caps, lengths, noise_u, seed,
                                             max_length, features, *params)
         return pred, (h_n, c_n)
 
-    def _forward_no_grad(self, features, caps, lengths, pretrain, noise_u, seed, max_length):
-        """``forward`` without autograd, with the seed of its device draw given: (pred, (h_n, c_n)).  Also log_likelihood's decode."""
+    def _forward_no_grad(self, features, caps, lengths, pretrain, noise_u, seed, max_length, drop=(0.0, 0, None)):
+        """``forward`` without autograd, with the seed of its device draw given: (pred, (h_n, c_n)).  Also log_likelihood's decode
+        (which never drops)."""
         with torch.no_grad():
             return self.engine().forward_tf([p.detach() for p in self.param_list()], features, caps, lengths, float(self.temperature),
-                                            bool(pretrain), noise_u, seed, tmax=max_length)
+                                            bool(pretrain), noise_u, seed, tmax=max_length, **_drop_kw(drop))
 
     def forward_scheduled(self, features, caps, lengths, sample_prob, pick="sample", coin_u=None, noise_u=None, seed=None, max_length=None,
-                          return_inputs=False):
+                          return_inputs=False, dropout=0.0, dropout_seed=None, keep_u=None):
         """``forward(features, caps, lengths, pretrain=True)`` with scheduled sampling (Bengio et al., 2015; gicap.h
         gic_decoder_forward_ss): the input of step t >= 1 is caps[:, t-1] with probability 1 - ``sample_prob``, else a token the decoder
         picks from its own logits of step t-1 -- ``pick`` = "sample" (a draw from softmax(logits), by Gumbel-max) or "argmax"; positions
         past a caption's length are never replaced.  Returns (pred = logits [B, max(lengths), V], (h_n, c_n)); ``return_inputs`` appends
         (inputs int64 [B, L], replaced int32 [B, L]), the inputs the decode realised.  Gradients flow as in ``forward`` over those
         inputs; none flows through the choice.  ``coin_u`` f32 [B, L] and ``noise_u`` f32 [L, B, V] replace the device draws
-        (Philox(``seed``); None = the next of SEEDS).  ``sample_prob`` = 0 is ``forward`` itself: nothing else is launched."""
+        (Philox(``seed``); None = the next of SEEDS).  ``sample_prob`` = 0 is ``forward`` itself: nothing else is launched.
+        ``dropout`` / ``dropout_seed`` / ``keep_u`` as ``forward``: the picks are made from the dropped logits."""
         p, seed = _ss_args(sample_prob, pick, coin_u, noise_u, seed)
         if p == 0.0:
-            pred, hc = self.forward(features, caps, lengths, pretrain=True, max_length=max_length)
+            pred, hc = self.forward(features, caps, lengths, pretrain=True, max_length=max_length, dropout=dropout,
+                                    dropout_seed=dropout_seed, keep_u=keep_u)
             return (pred, hc, _teacher_inputs(caps, self.args.vocab_size)) if return_inputs else (pred, hc)
+        drop = _drop_args(dropout, dropout_seed, keep_u)
         params = self.param_list()
         if not torch.is_grad_enabled() or not (features.requires_grad or any(q.requires_grad for q in params)):
             with torch.no_grad():
                 pred, hc, _, inputs, replaced = self.engine().forward_scheduled([q.detach() for q in params], features.detach().float(), caps,
-                                                                               lengths, p, pick, coin_u, noise_u, seed, tmax=max_length)
+                                                                               lengths, p, pick, coin_u, noise_u, seed, tmax=max_length,
+                                                                               **_drop_kw(drop))
         else:
-            pred, h_n, c_n, inputs, replaced = _ForwardSsFn.apply(self.engine(), p, pick, caps, lengths, coin_u, noise_u, seed, max_length,
+            pred, h_n, c_n, inputs, replaced = _ForwardSsFn.apply(self.engine(), drop, p, pick, caps, lengths, coin_u, noise_u, seed, max_length,
                                                                   features, *params)
             hc = (h_n, c_n)
         return (pred, hc, (inputs, replaced)) if return_inputs else (pred, hc)
@@ -373,10 +398,11 @@ class _AttnForwardTfFn(torch.autograd.Function):
     """AttnDecoder.forward with autograd: gic_attn_forward_tf / gic_attn_forward_tf_bwd; the alphas are differentiable too."""
 
     @staticmethod
-    def forward(ctx, eng, temperature, pretrain, caps, lengths, noise_u, seed, tmax, fmap, features, *params):
+    def forward(ctx, eng, drop, temperature, pretrain, caps, lengths, noise_u, seed, tmax, fmap, features, *params):
         dparams = [p.detach() for p in params]
         pred, (h_n, c_n), alphas, saved = eng.forward_tf(dparams, features.detach().float(), fmap.detach(), caps, lengths, temperature,
-                                                         pretrain, noise_u, seed, want_alphas=True, keep_state=True, tmax=tmax)
+                                                         pretrain, noise_u, seed, want_alphas=True, keep_state=True, tmax=tmax,
+                                                         **_drop_kw(drop))
         ctx.eng, ctx.temperature, ctx.pretrain, ctx.saved, ctx.dparams = eng, temperature, pretrain, saved, dparams
         ctx.save_for_backward(pred)
         ctx.mark_non_differentiable(h_n, c_n)
@@ -388,18 +414,18 @@ class _AttnForwardTfFn(torch.autograd.Function):
         (pred,) = ctx.saved_tensors
         grads = ctx.eng.forward_tf_bwd(ctx.dparams, ctx.saved, pred, d_pred, ctx.temperature, ctx.pretrain, d_alphas=d_alphas)
         ctx.saved = None
-        return (None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
+        return (None, None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
 
 
 class _AttnForwardSsFn(torch.autograd.Function):
     """AttnDecoder.forward_scheduled with autograd: gic_attn_forward_ss, then gic_attn_forward_tf_bwd over the inputs it realised."""
 
     @staticmethod
-    def forward(ctx, eng, sample_prob, pick, caps, lengths, coin_u, noise_u, seed, tmax, fmap, features, *params):
+    def forward(ctx, eng, drop, sample_prob, pick, caps, lengths, coin_u, noise_u, seed, tmax, fmap, features, *params):
         dparams = [p.detach() for p in params]
         pred, (h_n, c_n), alphas, saved, inputs, replaced = eng.forward_scheduled(dparams, features.detach().float(), fmap.detach(), caps,
                                                                                    lengths, sample_prob, pick, coin_u, noise_u, seed,
-                                                                                   tmax=tmax)
+                                                                                   tmax=tmax, **_drop_kw(drop))
         ctx.eng, ctx.saved, ctx.dparams = eng, saved, dparams
         ctx.save_for_backward(pred)
         ctx.mark_non_differentiable(h_n, c_n, inputs, replaced)
@@ -411,7 +437,7 @@ class _AttnForwardSsFn(torch.autograd.Function):
         (pred,) = ctx.saved_tensors
         grads = ctx.eng.forward_tf_bwd(ctx.dparams, ctx.saved, pred, d_pred, 1.0, True, d_alphas=d_alphas)
         ctx.saved = None
-        return (None, None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
+        return (None, None, None, None, None, None, None, None, None, None, None, grads[-1], *grads[:-1])
 
 
 class _AttnParams(nn.Module):
@@ -488,35 +514,38 @@ class AttnDecoder(nn.Module):
         return _sample_captions(self, features, (fmap,), num_samples, top_k, top_p, temperature, max_caption_len, eos_id, seed, noise_u, states,
                                 no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
 
-    def forward(self, features, fmap, caps, lengths, pretrain=False, noise_u=None, return_alphas=False, max_length=None):
+    def forward(self, features, fmap, caps, lengths, pretrain=False, noise_u=None, return_alphas=False, max_length=None, dropout=0.0,
+                dropout_seed=None, keep_u=None):
         """Teacher-forced decode (Decoder.forward with the attention step, gicap.h gic_attn_forward_tf): step 0 is fed ``features``,
         step t > 0 embed(caps[:, t-1]), packed with ``lengths`` (each 1..caps.shape[1] + 1).  Returns (pred [B, max(lengths), V],
         (h_n, c_n) [1, B, H]) with pred = logits (pretrain) or softmax((logits + gumbel) * temperature); ``return_alphas`` appends the
         attention weights f32 [B, max(lengths), P] (zero past a caption's length), differentiable like ``pred``.  Gradients flow to the
         decoder parameters and ``features`` (padded positions reach the projection's bias only); the returned hidden state is not
         differentiated.  ``fmap`` [B, P, C]: the trunk's last feature map (no gradient into it).  ``noise_u`` [B, max(lengths), V]
-        replaces the device draw.  ``max_length`` as Decoder.forward."""
+        replaces the device draw.  ``max_length`` and the output dropout (``dropout``, ``dropout_seed``, ``keep_u``) as Decoder.forward."""
         if fmap is None:
             raise ValueError("the attention decoder needs the trunk's feature map: forward(features, fmap, caps, lengths)")
         seed = 0 if noise_u is not None else SEEDS.next()
+        drop = _drop_args(dropout, dropout_seed, keep_u)
         params = self.param_list()
         if not torch.is_grad_enabled() or not (features.requires_grad or any(p.requires_grad for p in params)):
-            pred, hc, alphas = self._forward_no_grad(features, fmap, caps, lengths, pretrain, noise_u, seed, max_length, return_alphas)
+            pred, hc, alphas = self._forward_no_grad(features, fmap, caps, lengths, pretrain, noise_u, seed, max_length, return_alphas, drop)
         else:
-            pred, h_n, c_n, alphas = _AttnForwardTfFn.apply(self.engine(), float(self.temperature), bool(pretrain), caps, lengths, noise_u,
+            pred, h_n, c_n, alphas = _AttnForwardTfFn.apply(self.engine(), drop, float(self.temperature), bool(pretrain), caps, lengths, noise_u,
                                                             seed, max_length, fmap, features, *params)
             hc = (h_n, c_n)
         if return_alphas:
             return pred, hc, alphas
         return pred, hc
 
-    def _forward_no_grad(self, features, fmap, caps, lengths, pretrain, noise_u, seed, max_length, return_alphas=False):
+    def _forward_no_grad(self, features, fmap, caps, lengths, pretrain, noise_u, seed, max_length, return_alphas=False,
+                         drop=(0.0, 0, None)):
         """``forward`` without autograd, with the seed of its device draw given: (pred, (h_n, c_n), alphas or None).  Also
-        log_likelihood's decode."""
+        log_likelihood's decode (which never drops)."""
         with torch.no_grad():
             return self.engine().forward_tf([p.detach() for p in self.param_list()], features.detach().float(), fmap.detach(), caps, lengths,
                                             float(self.temperature), bool(pretrain), noise_u, seed, want_alphas=bool(return_alphas),
-                                            tmax=max_length)
+                                            tmax=max_length, **_drop_kw(drop))
 
     def log_likelihood(self, features, fmap, ids, lengths):
         """Decoder.log_likelihood with the attention step: (logp f32 [B], tokens int32 [B]) of ``ids`` int64 [B, L] given ``features`` and
@@ -526,25 +555,28 @@ class AttnDecoder(nn.Module):
         return _log_likelihood(self, features, (fmap,), ids, lengths)
 
     def forward_scheduled(self, features, fmap, caps, lengths, sample_prob, pick="sample", coin_u=None, noise_u=None, seed=None,
-                          max_length=None, return_alphas=False, return_inputs=False):
+                          max_length=None, return_alphas=False, return_inputs=False, dropout=0.0, dropout_seed=None, keep_u=None):
         """``forward(features, fmap, caps, lengths, pretrain=True)`` with scheduled sampling (Decoder.forward_scheduled; gicap.h
         gic_attn_forward_ss).  Returns (pred, (h_n, c_n)); ``return_alphas`` appends the attention weights (differentiable, as in
-        ``forward``), ``return_inputs`` then (inputs, replaced).  ``sample_prob`` = 0 is ``forward`` itself."""
+        ``forward``), ``return_inputs`` then (inputs, replaced).  ``sample_prob`` = 0 is ``forward`` itself.  Output dropout
+        (``dropout``, ``dropout_seed``, ``keep_u``) as Decoder.forward_scheduled."""
         if fmap is None:
             raise ValueError("the attention decoder needs the trunk's feature map: forward_scheduled(features, fmap, caps, lengths, p)")
         p, seed = _ss_args(sample_prob, pick, coin_u, noise_u, seed)
         if p == 0.0:
-            pred, hc, alphas = self.forward(features, fmap, caps, lengths, pretrain=True, return_alphas=True, max_length=max_length)
+            pred, hc, alphas = self.forward(features, fmap, caps, lengths, pretrain=True, return_alphas=True, max_length=max_length,
+                                            dropout=dropout, dropout_seed=dropout_seed, keep_u=keep_u)
             inputs, replaced = _teacher_inputs(caps, self.args.vocab_size) if return_inputs else (None, None)
         else:
+            drop = _drop_args(dropout, dropout_seed, keep_u)
             params = self.param_list()
             if not torch.is_grad_enabled() or not (features.requires_grad or any(q.requires_grad for q in params)):
                 with torch.no_grad():
                     pred, hc, alphas, _, inputs, replaced = self.engine().forward_scheduled(
                         [q.detach() for q in params], features.detach().float(), fmap.detach(), caps, lengths, p, pick, coin_u, noise_u, seed,
-                        tmax=max_length)
+                        tmax=max_length, **_drop_kw(drop))
             else:
-                pred, h_n, c_n, alphas, inputs, replaced = _AttnForwardSsFn.apply(self.engine(), p, pick, caps, lengths, coin_u, noise_u, seed,
+                pred, h_n, c_n, alphas, inputs, replaced = _AttnForwardSsFn.apply(self.engine(), drop, p, pick, caps, lengths, coin_u, noise_u, seed,
                                                                                   max_length, fmap, features, *params)
                 hc = (h_n, c_n)
         return (pred, hc) + ((alphas,) if return_alphas else ()) + (((inputs, replaced),) if return_inputs else ())

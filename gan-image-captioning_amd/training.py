@@ -119,6 +119,16 @@ def check_scheduled_sampling(args):
     return p, n, pick
 
 
+def check_gen_dropout(args) -> float:
+    """The instructor's check of --gen-dropout, before anything touches the device: p."""
+    p = float(getattr(args, "gen_dropout", 0.0))
+    if not 0.0 <= p < 1.0:                        # false for NaN too
+        raise ValueError(f"--gen-dropout must be in [0, 1), got {p}")
+    if p > 0.0 and getattr(args, "pretrain_mode", "sample") != "teacher":
+        raise ValueError("--gen-dropout drops the decoder's output in the teacher-forced decode: it needs --pretrain-mode teacher")
+    return p
+
+
 def check_seq_loss(args):
     """The instructor's checks of the sequence-loss flags, before anything touches the device: (ignore_pad, label_smoothing)."""
     eps = float(getattr(args, "label_smoothing", 0.0))
@@ -138,6 +148,7 @@ class GANInstructor:
         self.pretrain_mode, self.attn_reg = check_modes(args)
         self.ss_prob, self.ss_ramp, self.ss_pick = check_scheduled_sampling(args)
         self.ss_prob_now = scheduled_sampling_prob(self.ss_prob, self.ss_ramp, 0)      # pretrain_generator sets it per epoch
+        self.gen_dropout = check_gen_dropout(args)
         self.ignore_pad, self.label_smoothing = check_seq_loss(args)
         check_image_pipeline(args)
         self.dist = parallel.DistInfo.from_env()
@@ -254,22 +265,24 @@ class GANInstructor:
     def _pretrain_step_teacher(self, feats, captions, lengths, train):
         """--pretrain-mode teacher: pred = decoder.forward(features[, fmap], captions[:, :-1], lengths, pretrain=True), the same
         cross entropy against captions as the free-running step; with --attn-reg lam, + lam * mean_b sum_i (1 - sum_t alpha_bti)^2.
-        With --scheduled-sampling-prob, a training step decodes through decoder.forward_scheduled at this epoch's probability."""
+        With --scheduled-sampling-prob, a training step decodes through decoder.forward_scheduled at this epoch's probability; with
+        --gen-dropout, a training step drops the decoder's output in front of the vocabulary projection."""
         if lengths is None:
             lengths = torch.full((captions.shape[0],), captions.shape[1], dtype=torch.int32)
         caps = captions[:, :-1]
         p = self.ss_prob_now if train else 0.0        # only training batches are mixed: the validation loss stays comparable
+        drop = self.gen_dropout if train else 0.0     # ... and only training batches are dropped
         if p > 0.0:
             if self.attention:
                 pred, _, alphas = self.gen.decoder.forward_scheduled(feats[0], feats[1], caps, lengths, p, pick=self.ss_pick,
-                                                                     return_alphas=True)
+                                                                     return_alphas=True, dropout=drop)
             else:
-                pred, _ = self.gen.decoder.forward_scheduled(feats, caps, lengths, p, pick=self.ss_pick)
+                pred, _ = self.gen.decoder.forward_scheduled(feats, caps, lengths, p, pick=self.ss_pick, dropout=drop)
                 alphas = None
         elif self.attention:
-            pred, _, alphas = self.gen.decoder(feats[0], feats[1], caps, lengths, pretrain=True, return_alphas=True)
+            pred, _, alphas = self.gen.decoder(feats[0], feats[1], caps, lengths, pretrain=True, return_alphas=True, dropout=drop)
         else:
-            pred, _ = self.gen.decoder(feats, caps, lengths, pretrain=True)
+            pred, _ = self.gen.decoder(feats, caps, lengths, pretrain=True, dropout=drop)
             alphas = None
         loss = self._pretrain_loss(pred, captions[:, :pred.shape[1]], train)
         if self.attn_reg:

@@ -572,6 +572,62 @@ int gic_attn_forward_ss(const gic_attn_dims* dims, const gic_attn_params* params
                         int Tmax, const gic_sched_sample_opts* opts, void* ws, void* out, float* alphas, float* h_n, float* c_n,
                         void* stream);
 
+/* Output dropout of the caption decoder, for teacher-forced MLE pre-training: the LSTM output is dropped in front of the vocabulary
+ * projection, as Show-Attend-Tell's dropout(h) before fc; the recurrence keeps the undropped h.  With hout act [B, Tmax, H]:
+ *   keep[b, t, h]  = u[b, t, h] >= p
+ *   hdrop[b, t, :] = keep ? hout[b, t, :] * s : 0          s = 1.0f / (1.0f - p) in f32; the product is formed in f32 and rounded to
+ *                                                          the compute dtype
+ *   logits         = hdrop W_out^T + b_out
+ * Rows past a caption's length are zero in hout and stay zero.  u = keep_u, or Philox keyed by (seed, a stream tag of its own) and
+ * the flat index i = (b * Tmax + t) * H + h of the element: lane i & 3 of counter i >> 2.  The mask is not stored: the backward
+ * regenerates it from (seed, p) or reads keep_u again, so both calls must be given the same values.  hdrop is written by the forward
+ * call and read by the backward call (the gradient of W_out is taken against what the projection consumed).
+ * The gic_*_drop entry points take their plain counterpart's arguments with `drop` in front of `stream` and return its errors first;
+ * then a NULL drop, p outside (0, 1) or NaN, a NULL or misaligned hdrop return GIC_STATUS_INVALID_ARG before any launch.  They launch
+ * what the plain entry points launch plus one dropout kernel per call and direction (scheduled sampling: one per step, on the B rows
+ * of that step, in front of the step's logits -- the picks see the dropped logits); the backward's replaces the launch that zeroes
+ * d hout past the lengths.  No atomics: valid in the deterministic mode wherever the plain entry point is. */
+typedef struct gic_decoder_dropout {
+  float p;                               /* 0 < p < 1 */
+  uint64_t seed;                         /* Philox seed of the mask when keep_u is NULL */
+  const float* keep_u;                   /* f32 [B, Tmax, H] or NULL = device draw */
+  void* hdrop;                           /* compute dtype [B, Tmax, H], 16-byte aligned; forward writes, backward reads */
+} gic_decoder_dropout;
+int gic_decoder_forward_tf_drop(const gic_decoder_dims* dims, const gic_decoder_params* params, const gic_decoder_shadow* shadow,
+                                const gic_decoder_state* state, const float* features, const int64_t* caps, const int32_t* lengths,
+                                int Tmax, const float* noise_u, uint64_t seed, float temperature, int pretrain, float* logits_ws,
+                                int64_t* ids_ws, void* out, float* h_n, float* c_n, const gic_decoder_dropout* drop, void* stream);
+int gic_decoder_forward_ss_drop(const gic_decoder_dims* dims, const gic_decoder_params* params, const gic_decoder_shadow* shadow,
+                                const gic_decoder_state* state, const float* features, const int64_t* caps, const int32_t* lengths,
+                                int Tmax, const gic_sched_sample_opts* opts, void* ws, void* out, float* h_n, float* c_n,
+                                const gic_decoder_dropout* drop, void* stream);
+int gic_decoder_forward_tf_drop_bwd(const gic_decoder_dims* dims, const gic_decoder_params* params, const gic_decoder_shadow* shadow,
+                                    const gic_decoder_state* state, const gic_decoder_bwd_ws* ws, const void* pred, const int64_t* caps,
+                                    const int32_t* lengths, int Tmax, const void* d_pred, float temperature, int pretrain,
+                                    const gic_decoder_grads* grads, const gic_decoder_dropout* drop, void* stream);
+int gic_attn_forward_tf_drop(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                             const gic_attn_state* state, const float* features, const void* fmap, const int64_t* caps,
+                             const int32_t* lengths, int Tmax, const float* noise_u, uint64_t seed, float temperature, int pretrain,
+                             float* logits_ws, void* out, float* alphas, float* h_n, float* c_n, const gic_decoder_dropout* drop,
+                             void* stream);
+int gic_attn_forward_ss_drop(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                             const gic_attn_state* state, const float* features, const void* fmap, const int64_t* caps,
+                             const int32_t* lengths, int Tmax, const gic_sched_sample_opts* opts, void* ws, void* out, float* alphas,
+                             float* h_n, float* c_n, const gic_decoder_dropout* drop, void* stream);
+int gic_attn_forward_tf_drop_bwd(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                                 const gic_attn_state* state, const gic_attn_bwd_ws* ws, const void* fmap, const void* pred,
+                                 const int64_t* caps, const int32_t* lengths, int Tmax, const void* d_pred, const float* d_alphas,
+                                 float temperature, int pretrain, const gic_attn_grads* grads, const gic_decoder_dropout* drop,
+                                 void* stream);
+/* The two stages on their own.  gic_hidden_dropout: y = keep ? x * s : 0 over x / y of `dtype` [rows, H] (contiguous; any H and any
+ * alignment: 16-byte loads and stores where H % 4 == 0 (f32) / H % 8 == 0 (bf16) and both bases are 16-byte aligned, else scalar
+ * ones), element (r, h) drawn at i = r * H + h as above; keep_u f32 [rows, H] or NULL.  gic_hidden_dropout_bwd, in place on dhout
+ * f32 [B, Tmax, H]: dhout = (t < lengths[b] && keep) ? dhout * s : 0 (lengths int32 [B]). */
+int gic_hidden_dropout(const void* x, int dtype, int64_t rows, int32_t H, float p, uint64_t seed, const float* keep_u, void* y,
+                       void* stream);
+int gic_hidden_dropout_bwd(float* dhout, const int32_t* lengths, int32_t B, int32_t Tmax, int32_t H, float p, uint64_t seed,
+                           const float* keep_u, void* stream);
+
 /* Monte-Carlo roll-outs of the attention decoder (the SeqGAN step's): the counterpart of gic_decoder_sample_fwd with force_ids,
  * force_len, no_state and resume_from.  dims->B = images, dims->L = caption length.  `rows` roll-out rows, row r of image r % B: it
  * copies force_ids[r % B, :force_len[r]] (force_ids int64 [B, L], the captions; force_len int32 [rows], ascending, each 1..L-1), joins
