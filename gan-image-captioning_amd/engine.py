@@ -589,9 +589,9 @@ def _tf_lengths(lengths, B: int, T: int, tmax: Optional[int]):
 SS_PICKS = ("sample", "argmax")     # gic_sched_sample_opts.pick
 
 
-def _ss_opts(prob: float, pick: str, coin_u, noise_u, seed: int, B: int, Lc: int, V: int, dev):
+def _ss_opts(prob: float, pick: str, coin_u, noise_u, seed: int, B: int, Lc: int, V: int, dev, inputs=None, replaced=None):
     """(gic_sched_sample_opts, inputs int64 [B, L], replaced int32 [B, L], the tensors the struct points into) of a scheduled-sampling
-    decode: ``coin_u`` f32 [B, L] and ``noise_u`` f32 [L, B, V] replace the device draws."""
+    decode: ``coin_u`` f32 [B, L] and ``noise_u`` f32 [L, B, V] replace the device draws.  ``inputs`` / ``replaced``: the caller's."""
     prob = float(prob)
     if not 0.0 <= prob <= 1.0:
         raise ValueError(f"sample_prob must be in [0, 1], got {prob}")
@@ -605,8 +605,8 @@ def _ss_opts(prob: float, pick: str, coin_u, noise_u, seed: int, B: int, Lc: int
         if tuple(noise_u.shape) != (Lc, B, V):
             raise ValueError(f"noise_u must be [L, B, V] = [{Lc}, {B}, {V}]")
         noise_u = noise_u.contiguous().float()
-    inputs = torch.empty(B, Lc, device=dev, dtype=torch.int64)
-    replaced = torch.empty(B, Lc, device=dev, dtype=torch.int32)
+    inputs = inputs if inputs is not None else torch.empty(B, Lc, device=dev, dtype=torch.int64)
+    replaced = replaced if replaced is not None else torch.empty(B, Lc, device=dev, dtype=torch.int32)
     o = L.SchedSampleOpts()
     o.prob, o.pick, o.coin_u, o.noise_u, o.seed = prob, SS_PICKS.index(pick), ptr(coin_u), ptr(noise_u), int(seed) & (2 ** 64 - 1)
     o.inputs, o.replaced = ptr(inputs), ptr(replaced)
@@ -633,6 +633,21 @@ def _drop_struct(d) -> L.DecoderDropout:
     o = L.DecoderDropout()
     o.p, o.seed, o.keep_u, o.hdrop = d["p"], int(d["seed"]) & (2 ** 64 - 1), ptr(d["keep_u"]), ptr(d["hdrop"])
     return o
+
+
+def _tf_own(bufs, key: str, shape, dtype, dev, numel_only: bool = False):
+    """``bufs[key]`` checked (a caller-owned buffer of a teacher-forced call: contiguous, on ``dev``, of ``dtype`` and ``shape`` -- or
+    with ``numel_only`` of at least as many elements), or a fresh tensor where the caller gives none."""
+    t = bufs.get(key)
+    if t is None:
+        return torch.empty(*shape, device=dev, dtype=dtype)
+    n = 1
+    for v in shape:
+        n *= int(v)
+    fits = torch.is_tensor(t) and (t.numel() >= n if numel_only else tuple(t.shape) == tuple(int(v) for v in shape))
+    if not (fits and t.device == dev and t.dtype == dtype and t.is_contiguous()):
+        raise ValueError(f"buffers[{key!r}] must be a contiguous {dtype} tensor {list(shape)} on {dev}")
+    return t
 
 
 def hidden_dropout(x: torch.Tensor, p: float, seed: int = 0, keep_u: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
@@ -698,8 +713,11 @@ class _TeacherForced:
         return [torch.empty_like(p) for p in params] + [torch.empty(B, self.E, device=params[0].device, dtype=torch.float32)]
 
     def _tf_forward(self, params, features, fmap, caps, lengths, tmax, state, want_alphas, ss, noise_u=None, seed=0, temperature=1.0,
-                    pretrain=True, drop=(0.0, 0, None)):
+                    pretrain=True, drop=(0.0, 0, None), bufs=None):
         """``ss``: None, or _ss_opts' arguments but the shapes (prob, pick, coin_u, noise_u, seed) -- then the scheduled-sampling call.
+        ``bufs``: None, or a dict of caller-owned buffers that stand in for what is allocated here (each optional): ``out``, ``h_n``,
+        ``c_n``, ``hdrop`` (16-byte aligned), ``ws`` (the workspace tensors of the plain call in argument order, or the one f32 tensor
+        of the scheduled-sampling call, 16-byte aligned and at least *_forward_ss_ws_bytes large), ``inputs``, ``replaced``.
         ``drop``: (dropout, dropout_seed, keep_u) -- with dropout > 0 the gic_*_drop form of the call, whose ``hdrop`` is allocated
         here and carried in ``saved["drop"]`` with (p, seed, keep_u) for the backward.
         Returns (pred, (h_n, c_n), *alphas), saved[, inputs, replaced]."""
@@ -716,27 +734,35 @@ class _TeacherForced:
             noise_u = noise_u.contiguous().float()
         maps = self._decode_maps(fmap, B)
         dev = features.device
+        bufs = bufs or {}
         if ss:
-            o, inputs, replaced, keep = _ss_opts(*ss, B, Lc, self.V, dev)
+            o, inputs, replaced, keep = _ss_opts(*ss, B, Lc, self.V, dev, _tf_own(bufs, "inputs", (B, Lc), torch.int64, dev),
+                                                 _tf_own(bufs, "replaced", (B, Lc), torch.int32, dev))
         self.prepare(params)
         st = dict(state) if state is not None else self.alloc_state(B, T, dev)
-        out = torch.empty(B, Tmax, self.V, device=dev, dtype=self.act)
-        h_n = torch.empty(self.NL, B, self.H, device=dev, dtype=torch.float32)
-        c_n = torch.empty_like(h_n)
+        out = _tf_own(bufs, "out", (B, Tmax, self.V), self.act, dev)
+        h_n = _tf_own(bufs, "h_n", (self.NL, B, self.H), torch.float32, dev)
+        c_n = _tf_own(bufs, "c_n", (self.NL, B, self.H), torch.float32, dev)
         alphas = self._tf_alphas(want_alphas, B, Tmax, dev)
         d = self.dims(B, T)
         if ss:
             name, nbytes = f"{self._PREFIX}_forward_ss", C.c_uint64(0)
             L.check(getattr(L.load(), name + "_ws_bytes")(C.byref(d), Tmax, C.byref(nbytes)), name + "_ws_bytes")
-            ws = (torch.empty(max(int(nbytes.value) // 4, 1), device=dev, dtype=torch.float32),)
+            ws = (_tf_own(bufs, "ws", (max(int(nbytes.value) // 4, 1),), torch.float32, dev, numel_only=True),)
             mode = (C.byref(o),)
         else:
             name, ws = f"{self._PREFIX}_forward_tf", self._tf_ws(B, T, Tmax, dev)
+            if bufs.get("ws") is not None:
+                own = tuple(bufs["ws"])
+                if len(own) != len(ws) or any(not (a.device == b.device and a.dtype == b.dtype and a.is_contiguous() and a.numel() >= b.numel())
+                                              for a, b in zip(own, ws)):
+                    raise ValueError("buffers['ws'] must hold the call's workspace tensors: " + ", ".join(f"{b.dtype} x {b.numel()}" for b in ws))
+                ws = own
             mode = (ptr(noise_u), int(seed) & (2 ** 64 - 1), float(temperature), int(bool(pretrain)))
         dropped = None
         if drop_p > 0.0:         # hdrop is the call's own: gic_decoder_state_bytes pins the state's list
             dropped = {"p": drop_p, "seed": int(drop[1]), "keep_u": _drop_keep_u(drop[2], (B, Tmax, self.H)),
-                       "hdrop": torch.empty(B, Tmax, self.H, device=dev, dtype=self.act)}
+                       "hdrop": _tf_own(bufs, "hdrop", (B, Tmax, self.H), self.act, dev)}
             name += "_drop"
         tail = (C.byref(_drop_struct(dropped)),) if dropped else ()
         len_dev, caps = len_dev.to(dev), caps.contiguous()
@@ -1071,15 +1097,16 @@ class DecoderEngine(_CaptionDecodes, _TeacherForced):
 
     def forward_tf(self, params, features: torch.Tensor, caps: torch.Tensor, lengths, temperature: float, pretrain: bool = False,
                    noise_u: Optional[torch.Tensor] = None, seed: int = 0, keep_state: bool = False, tmax: Optional[int] = None,
-                   dropout: float = 0.0, dropout_seed: int = 0, keep_u: Optional[torch.Tensor] = None):
+                   state=None, buffers=None, dropout: float = 0.0, dropout_seed: int = 0, keep_u: Optional[torch.Tensor] = None):
         """gic_decoder_forward_tf: Decoder.forward (teacher forcing, generator.py:39-53).
         Returns (pred act [B, max(lengths), V], (h_n, c_n) f32 [NL, B, H]); with ``keep_state`` also what ``forward_tf_bwd`` needs.
         ``tmax``: decode that many steps and take ``lengths`` as device int32 values in 1..T unread (no host sync); pred is then
         [B, tmax, V].  ``dropout`` p > 0: output dropout (gic_decoder_forward_tf_drop) -- the LSTM output is dropped with probability p
         in front of the vocabulary projection, by Philox(``dropout_seed``) or ``keep_u`` f32 [B, max(lengths), H] (keep = u >= p); the
-        recurrence, h_n and c_n keep the undropped h.  ``saved["drop"]`` then carries (p, seed, keep_u, hdrop) for the backward."""
-        head, saved = self._tf_forward(params, features, None, caps, lengths, tmax, None, False, None, noise_u, seed, temperature, pretrain,
-                                       (dropout, dropout_seed, keep_u))
+        recurrence, h_n and c_n keep the undropped h.  ``saved["drop"]`` then carries (p, seed, keep_u, hdrop) for the backward.
+        ``state``: a caller-owned ``alloc_state(B, L + 1, dev)``; ``buffers``: caller-owned outputs and workspaces (_tf_forward)."""
+        head, saved = self._tf_forward(params, features, None, caps, lengths, tmax, state, False, None, noise_u, seed, temperature, pretrain,
+                                       (dropout, dropout_seed, keep_u), buffers)
         return (*head, saved) if keep_state else head
 
     def _tf_check_inputs(self, features, caps, B: int) -> None:
@@ -1091,14 +1118,16 @@ class DecoderEngine(_CaptionDecodes, _TeacherForced):
 
     def forward_scheduled(self, params, features: torch.Tensor, caps: torch.Tensor, lengths, sample_prob: float, pick: str = "sample",
                           coin_u: Optional[torch.Tensor] = None, noise_u: Optional[torch.Tensor] = None, seed: int = 0,
-                          tmax: Optional[int] = None, dropout: float = 0.0, dropout_seed: int = 0, keep_u: Optional[torch.Tensor] = None):
+                          tmax: Optional[int] = None, state=None, buffers=None, dropout: float = 0.0, dropout_seed: int = 0,
+                          keep_u: Optional[torch.Tensor] = None):
         """gic_decoder_forward_ss: ``forward_tf(pretrain=True, keep_state=True)`` with scheduled sampling -- the input of step t >= 1 is
         the model's own pick from step t-1's logits where coin < ``sample_prob`` (and t < lengths[b]), else caps[:, t-1].  Returns
         (pred, (h_n, c_n), saved, inputs int64 [B, L], replaced int32 [B, L]); ``saved`` carries ``inputs`` as its captions, so
         ``forward_tf_bwd`` runs on it unchanged.  ``coin_u`` f32 [B, L] / ``noise_u`` f32 [L, B, V] replace the device draws.
-        ``dropout`` / ``dropout_seed`` / ``keep_u`` as forward_tf (gic_decoder_forward_ss_drop): the picks see the dropped logits."""
-        head, *rest = self._tf_forward(params, features, None, caps, lengths, tmax, None, False, (sample_prob, pick, coin_u, noise_u, seed),
-                                       drop=(dropout, dropout_seed, keep_u))
+        ``dropout`` / ``dropout_seed`` / ``keep_u`` as forward_tf (gic_decoder_forward_ss_drop): the picks see the dropped logits.
+        ``state`` / ``buffers`` as forward_tf."""
+        head, *rest = self._tf_forward(params, features, None, caps, lengths, tmax, state, False, (sample_prob, pick, coin_u, noise_u, seed),
+                                       drop=(dropout, dropout_seed, keep_u), bufs=buffers)
         return (*head, *rest)
 
     def forward_tf_bwd(self, params, saved, pred: torch.Tensor, d_pred: torch.Tensor, temperature: float, pretrain: bool = False,
