@@ -164,6 +164,18 @@ class ImageSrc(C.Structure):
                 ("row_stride", C.c_int32), ("box", C.c_float * 4), ("flip", C.c_int32), ("reserved", C.c_int32)]
 
 
+ADAMW_MAX_RANGES = 256        # GIC_ADAMW_MAX_RANGES
+LR_SCHEDULES = {"none": 0, "linear": 1, "cosine": 2, "invsqrt": 3, "step": 4}      # GIC_LR_*
+
+
+class AdamwOpts(C.Structure):
+    """gic_adamw_opts (gic_clip_adamw)."""
+    _fields_ = [("weight_decay", C.c_double), ("ranges_host", c_void_p), ("ranges", c_void_p), ("n_ranges", C.c_int32),
+                ("schedule", C.c_int32), ("warmup_steps", C.c_int64), ("total_steps", C.c_int64), ("step_size", C.c_int64),
+                ("min_ratio", C.c_double), ("gamma", C.c_double), ("ema", c_void_p), ("ema_count", c_void_p), ("ema_decay", C.c_double),
+                ("ema_warmup", C.c_int32), ("reserved", C.c_int32), ("sched_out", c_void_p)]
+
+
 _P = C.POINTER
 _SIGNATURES = {
     "gic_abi_version": (C.c_int, []),
@@ -325,6 +337,8 @@ _SIGNATURES = {
     "gic_clip_adam_partials": (C.c_int64, [C.c_int64]),
     "gic_clip_adam": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
                                 C.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gic_clip_adamw": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                 C.c_double, c_void_p, c_void_p, c_void_p, _P(AdamwOpts), c_void_p]),
 }
 
 ABI_VERSION = 5               # GIC_ABI_VERSION of include/gicap.h

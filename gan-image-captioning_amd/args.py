@@ -119,6 +119,27 @@ _NATIVE = [
     ("--scst-bleu-weight", float, 0.0, "weight of the add-one smoothed sentence BLEU-4 in the SCST reward; with this and "
                                        "--scst-rouge-weight 0 and --scst-cider-weight 1 the reward is the plain CIDEr-D scorer"),
     ("--scst-rouge-weight", float, 0.0, "weight of ROUGE-L in the SCST reward"),
+    # optimizer: LR schedules, decoupled weight decay and a weight EMA, all evaluated inside the update kernel (optim.py); every
+    # default is off and leaves the optimizers on the plain clip + Adam entry point
+    ("--pretrain-lr-schedule", str, "none", "LR schedule of MLE pre-training over pretrain_epochs * len(pre-train loader) steps, after "
+                                            "--pretrain-lr-warmup-steps of linear warm-up", {"choices": ["none", "linear", "cosine", "invsqrt", "step"]}),
+    ("--adv-lr-schedule", str, "none", "LR schedule of the generator's and the discriminator's adversarial optimizers over adv_epochs * "
+                                       "len(adversarial train loader) steps", {"choices": ["none", "linear", "cosine", "invsqrt", "step"]}),
+    ("--pretrain-lr-warmup-steps", int, 0, "linear LR warm-up steps of MLE pre-training"),
+    ("--adv-lr-warmup-steps", int, 0, "linear LR warm-up steps of the adversarial optimizers"),
+    ("--lr-min-ratio", float, 0.0, "floor of every LR schedule as a fraction of the base rate, in [0, 1]"),
+    ("--lr-step-size", int, 0, "steps between two decays of the step schedule"),
+    ("--lr-step-gamma", float, 0.1, "factor of one decay of the step schedule"),
+    ("--gen-weight-decay", float, 0.0, "decoupled (AdamW) weight decay of the generator's matrices and embeddings (pre-training, SCST "
+                                       "and adversarial optimizers); biases and BatchNorm affine parameters do not decay"),
+    ("--disc-weight-decay", float, 0.0, "decoupled (AdamW) weight decay of the discriminator's embeddings, filters and matrices"),
+    ("--gen-ema-decay", float, 0.0, "decay of an exponential moving average of the trainable generator parameters, advanced by every "
+                                    "generator optimizer step; 0 = off"),
+    ("--gen-ema-warmup", int, 1, "1: the EMA's k-th update uses min(decay, (1 + k) / (10 + k)); 0: the constant decay", {"choices": [0, 1]}),
+    ("--eval-ema", int, 0, "1: every evaluate* method runs with the averaged generator (needs --gen-ema-decay > 0); validation losses "
+                           "and best-checkpoint selection stay on the live weights", {"choices": [0, 1]}),
+    ("--resume-train-state", str, "", "a <checkpoint>.train_state file written beside a model checkpoint: restores the optimizers' "
+                                      "moments and step counts and the EMA (loop epoch counters are not restored)"),
     ("--eval-diverse-beam-size", int, 0, "beam size of the diverse-beam-search diversity evaluation (GANInstructor.evaluate_diverse_beam: "
                                          "BLEU-4, mBLEU-4, distinct-1/2, vocabulary) after each adversarial epoch's validation; 0 = off"),
     ("--eval-diverse-groups", int, 2, "groups of that evaluation's diverse beam search (must divide --eval-diverse-beam-size)"),

@@ -1574,6 +1574,35 @@ def clip_adam(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, clip_no
     bump_param_epoch()
 
 
+def adamw_opts(weight_decay=0.0, ranges=(), ranges_dev=None, schedule="none", warmup_steps=0, total_steps=0, min_ratio=0.0,
+               step_size=0, gamma=0.1, ema=None, ema_count=None, ema_decay=0.0, ema_warmup=True, sched_out=None) -> L.AdamwOpts:
+    """gic_adamw_opts, built once per optimizer.  ``ranges``: the host table, a flat sequence s0, e0, s1, e1, ...; ``ranges_dev``: the
+    same values as a device int64 tensor.  The struct keeps the host table and every tensor alive."""
+    require_gpu(ranges_dev, ema, ema_count, sched_out)
+    flat = [int(x) for x in ranges]
+    if len(flat) % 2:
+        raise ValueError("decay ranges are (start, end) pairs")
+    if flat and (ranges_dev is None or ranges_dev.dtype != torch.int64 or ranges_dev.numel() != len(flat)):
+        raise ValueError("ranges_dev must be the int64 device copy of the decay ranges")
+    if schedule not in L.LR_SCHEDULES:
+        raise ValueError(f"unknown LR schedule {schedule!r}; choose from {sorted(L.LR_SCHEDULES)}")
+    host = _arr(C.c_int64, max(len(flat), 1), flat)
+    o = L.AdamwOpts(float(weight_decay), C.cast(host, C.c_void_p).value if flat else None, ptr(ranges_dev) if flat else None,
+                    len(flat) // 2, L.LR_SCHEDULES[schedule], int(warmup_steps), int(total_steps), int(step_size), float(min_ratio),
+                    float(gamma), ptr(ema), ptr(ema_count), float(ema_decay), int(bool(ema_warmup)), 0, ptr(sched_out))
+    o._keep = (host, ranges_dev, ema, ema_count, sched_out)
+    return o
+
+
+def clip_adamw(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, clip_norm, step_count, norm_out, partials, opts):
+    """gic_clip_adamw: clip_adam plus ``opts`` (adamw_opts): device-side LR schedule, decoupled weight decay, weight EMA."""
+    require_gpu(params, grads, exp_avg, exp_avg_sq, step_count, norm_out, partials)
+    L.check(L.load().gic_clip_adamw(ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), float(lr), float(beta1),
+                                    float(beta2), float(eps), float(clip_norm), ptr(step_count), ptr(norm_out), ptr(partials),
+                                    C.byref(opts), stream_ptr()), "gic_clip_adamw")
+    bump_param_epoch()
+
+
 # ------------------------------------------------------------------------------------------ visual-attention decoder
 class AttnDecoderEngine(_CaptionDecodes, _TeacherForced):
     """gic_attn_sample_fwd / bwd (gicap.h): the reference's roll-out loop with soft attention over the trunk's feature map

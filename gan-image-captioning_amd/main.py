@@ -49,6 +49,8 @@ def main(argv=None):
     inst = GANInstructor(args, train, val)
     if getattr(args, "resume", ""):
         inst.load_checkpoint(args.resume)
+    if getattr(args, "resume_train_state", ""):
+        inst.load_train_state(args.resume_train_state)
     inst._run()
     return inst
 

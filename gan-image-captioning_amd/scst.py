@@ -55,7 +55,9 @@ class SCSTStep:
             raise ValueError("--scst-baseline mean needs --scst-samples >= 2 (the other samples of the image)")
         self.inst, self.scorer = inst, scorer
         self.n, self.baseline = int(num_samples), baseline
-        self.opt = FusedClipAdam(inst.gen_arena, float(lr), inst.args.clip_norm)
+        # the constant --scst-lr, with the generator's weight decay and weight EMA (one per arena) where the instructor has them
+        self.opt = FusedClipAdam(inst.gen_arena, float(lr), inst.args.clip_norm, weight_decay=getattr(inst, "gen_weight_decay", 0.0),
+                                 ema=getattr(inst, "ema", None))
 
     def __call__(self, images, refs: RefBatch, max_caption_len: int, opt_step: bool = True, noise_u: Optional[torch.Tensor] = None,
                  seed: Optional[int] = None) -> dict:

@@ -11,6 +11,8 @@ same batch contract and logging, with these deliberate fixes:
 """
 from __future__ import annotations
 
+import contextlib
+import functools
 import json
 import math
 import os
@@ -28,7 +30,7 @@ from .discriminator import Discriminator
 from .fused_step import FusedAdvStep
 from .seqgan import SeqGANStep
 from .generator import Generator
-from .optim import FusedClipAdam, ParamArena
+from .optim import ArenaEMA, FusedClipAdam, LRSchedule, ParamArena
 from .tasks import make_collate, stack_images
 from .utils import create_logger, get_fixed_temperature, get_losses
 
@@ -137,12 +139,73 @@ def check_seq_loss(args):
     return bool(int(getattr(args, "pretrain_ignore_pad", 0))), eps
 
 
+def check_optimizer(args) -> dict:
+    """The instructor's checks of the optimizer flags, before anything touches the device: the schedules' shapes (their horizons come
+    from the loaders), the weight decays, the EMA decay / warm-up and --eval-ema.  The horizon check (linear / cosine need more
+    steps than their warm-up) is LRSchedule.validate's, at the optimizer's construction."""
+    r = float(getattr(args, "lr_min_ratio", 0.0))
+    if not 0.0 <= r <= 1.0:                       # false for NaN too
+        raise ValueError(f"--lr-min-ratio must be in [0, 1], got {r}")
+    S, gamma = int(getattr(args, "lr_step_size", 0)), float(getattr(args, "lr_step_gamma", 0.1))
+    shapes = {}
+    for phase in ("pretrain", "adv"):
+        kind, W = getattr(args, f"{phase}_lr_schedule", "none"), int(getattr(args, f"{phase}_lr_warmup_steps", 0))
+        if W < 0:
+            raise ValueError(f"--{phase}-lr-warmup-steps must be >= 0, got {W}")
+        if kind == "step" and S <= 0:
+            raise ValueError(f"--{phase}-lr-schedule step needs a positive --lr-step-size, got {S}")
+        shapes[phase] = LRSchedule(kind, W, 0, r, S, gamma)
+        if kind not in ("linear", "cosine"):
+            shapes[phase].validate()
+    wd = {}
+    for who in ("gen", "disc"):
+        wd[who] = float(getattr(args, f"{who}_weight_decay", 0.0))
+        if not wd[who] >= 0.0:
+            raise ValueError(f"--{who}-weight-decay must be >= 0, got {wd[who]}")
+    d = float(getattr(args, "gen_ema_decay", 0.0))
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"--gen-ema-decay must be in [0, 1), got {d}")
+    eval_ema = bool(int(getattr(args, "eval_ema", 0)))
+    if eval_ema and d == 0.0:
+        raise ValueError("--eval-ema 1 evaluates the averaged generator: it needs --gen-ema-decay > 0")
+    return {"pretrain": shapes["pretrain"], "adv": shapes["adv"], "gen_wd": wd["gen"], "disc_wd": wd["disc"], "ema_decay": d,
+            "ema_warmup": bool(int(getattr(args, "gen_ema_warmup", 1))), "eval_ema": eval_ema}
+
+
+def build_optimizers(args, oc, gen_arena, disc_arena, pretrain_steps, adv_steps):
+    """(pretrain_opt, gen_opt, disc_opt, ema) of the instructor (training.py:24-26) from ``oc = check_optimizer(args)`` and the two
+    phases' step counts, the schedules' horizons.  One ArenaEMA on gen_arena, advanced by every generator optimizer (SCST's too); D
+    gets schedule and decay and no EMA.  Neutral flags give neutral keywords: plain clip + Adam."""
+    pre_sched, adv_sched = oc["pretrain"]._replace(total=pretrain_steps), oc["adv"]._replace(total=adv_steps)
+    ema = ArenaEMA(gen_arena, oc["ema_decay"], oc["ema_warmup"]) if oc["ema_decay"] > 0.0 else None
+    g_kw = {"weight_decay": oc["gen_wd"], "ema": ema}
+    pretrain_opt = FusedClipAdam(gen_arena, args.pretrain_lr, args.clip_norm, schedule=pre_sched, **g_kw)
+    gen_opt = FusedClipAdam(gen_arena, args.gen_lr, args.clip_norm, schedule=adv_sched, **g_kw)
+    disc_opt = FusedClipAdam(disc_arena, args.disc_lr, args.clip_norm, schedule=adv_sched, weight_decay=oc["disc_wd"])
+    return pretrain_opt, gen_opt, disc_opt, ema
+
+
+def _on_eval_weights(method):
+    """An evaluate* method of GANInstructor: under --eval-ema 1 it runs with the averaged generator in the live parameters."""
+    @functools.wraps(method)
+    def run(self, *a, **kw):
+        with self._eval_weights():
+            return method(self, *a, **kw)
+    return run
+
+
 def scheduled_sampling_prob(p: float, ramp_epochs: int, epoch: int) -> float:
     """p_e = p * min(1, e / n) of epoch e (0-based); n = 0: p throughout."""
     return p if ramp_epochs <= 0 else p * min(1.0, epoch / ramp_epochs)
 
 
 class GANInstructor:
+    ema = None              # ArenaEMA of gen_arena under --gen-ema-decay
+    eval_ema = False        # --eval-ema
+    _ema_held = False       # True: evaluate* stays on the weights that are live now (nested evaluations, checkpoint selection)
+    scst_opt = None         # SCST's own optimizer over gen_arena, once scst_train has built it
+    _train_state = None     # a loaded --resume-train-state, for the optimizers built later (SCST)
+
     def __init__(self, args, train_dataset, dev_dataset):
         self.args = args
         self.pretrain_mode, self.attn_reg = check_modes(args)
@@ -151,6 +214,7 @@ class GANInstructor:
         self.gen_dropout = check_gen_dropout(args)
         self.ignore_pad, self.label_smoothing = check_seq_loss(args)
         check_image_pipeline(args)
+        oc = check_optimizer(args)
         self.dist = parallel.DistInfo.from_env()
         from .generator import SEEDS
         SEEDS.rank = self.dist.rank            # replicas share weights and the torch seed, not the device noise streams
@@ -177,16 +241,6 @@ class GANInstructor:
             g_params += list(self.gen.encoder.linear.parameters()) + list(self.gen.encoder.bn.parameters())
         self.gen_arena = ParamArena(g_params)
         self.disc_arena = ParamArena(self.disc.parameters())
-        self.pretrain_opt = FusedClipAdam(self.gen_arena, args.pretrain_lr, args.clip_norm)   # training.py:24
-        self.gen_opt = FusedClipAdam(self.gen_arena, args.gen_lr, args.clip_norm)             # training.py:25
-        self.disc_opt = FusedClipAdam(self.disc_arena, args.disc_lr, args.clip_norm)          # training.py:26
-        self.reducer = parallel.GradReducer(self.dist) if self.dist.world_size > 1 else None
-        self.fused = FusedAdvStep(self.gen, self.disc, self.gen_arena, self.disc_arena, args, self.reducer
-                                  ).bind_optimizers(self.gen_opt, self.disc_opt)
-        # --adv-mode seqgan: policy gradient + Monte-Carlo roll-outs (no reference counterpart; seqgan.py)
-        self.seqgan = SeqGANStep(self.gen, self.disc, self.gen_arena, self.disc_arena, args, self.reducer
-                                 ).bind_optimizers(self.gen_opt, self.disc_opt)
-
         self.train_dataset, self.dev_dataset = train_dataset, dev_dataset
         nw = int(getattr(args, "num_workers", 4))
         dp = self.dist.world_size > 1
@@ -200,6 +254,20 @@ class GANInstructor:
         self.adv_train_loader = mk(train_dataset, args.adv_train_batch_size, True)
         self.adv_eval_loader = mk(dev_dataset, args.adv_eval_batch_size, False)
         self._sampler_epoch = 0
+
+        # LR schedules over the phases' step counts, decoupled weight decay and G's weight EMA; with every flag at its default the
+        # optimizers are plain clip + Adam
+        steps = lambda epochs, loader: int(epochs) * (len(loader) if loader is not None else 0)      # noqa: E731
+        self.gen_weight_decay, self.eval_ema = oc["gen_wd"], oc["eval_ema"]
+        self.pretrain_opt, self.gen_opt, self.disc_opt, self.ema = build_optimizers(
+            args, oc, self.gen_arena, self.disc_arena, steps(args.pretrain_epochs, self.pre_train_loader),
+            steps(args.adv_epochs, self.adv_train_loader))
+        self.reducer = parallel.GradReducer(self.dist) if self.dist.world_size > 1 else None
+        self.fused = FusedAdvStep(self.gen, self.disc, self.gen_arena, self.disc_arena, args, self.reducer
+                                  ).bind_optimizers(self.gen_opt, self.disc_opt)
+        # --adv-mode seqgan: policy gradient + Monte-Carlo roll-outs (no reference counterpart; seqgan.py)
+        self.seqgan = SeqGANStep(self.gen, self.disc, self.gen_arena, self.disc_arena, args, self.reducer
+                                 ).bind_optimizers(self.gen_opt, self.disc_opt)
 
         self.model_dir = getattr(args, "model_dir", None)
         self.writer = _ScalarWriter(getattr(args, "save_dir", None) if rank0 and getattr(args, "log_file", None) else None)
@@ -309,6 +377,8 @@ class GANInstructor:
                 gen_loss.append(val)
                 self.writer.add_scalar("GenPreTraining_train_loss" if what == "train" else "GenPreTraining_val_loss",
                                        val, self.pretrain_steps)
+                if what == "train":        # lr * lambda(s) of the next step, against the number s of steps taken
+                    self.writer.add_scalar("GenPreTraining_lr", self.pretrain_opt.current_lr(), self.pretrain_opt.steps)
                 progress.update(len(images) * self.dist.world_size)
                 progress.set_postfix(loss=val)
         return gen_loss
@@ -409,6 +479,9 @@ class GANInstructor:
                 self.disc_steps += 1
                 self.writer.add_scalar("Generator_train_loss" if what == "train" else "Generator_val_loss", g_val, self.gen_steps)
                 self.gen_steps += 1
+                if what == "train":
+                    self.writer.add_scalar("Generator_lr", self.gen_opt.current_lr(), self.gen_opt.steps)
+                    self.writer.add_scalar("Discriminator_lr", self.disc_opt.current_lr(), self.disc_opt.steps)
                 gen_loss.append(g_val)
                 disc_loss.append(d_val)
                 progress.update(len(images) * self.dist.world_size)
@@ -419,7 +492,8 @@ class GANInstructor:
     def load_checkpoint(self, path: str) -> str:
         """Load weights written by ``_run`` here or by the reference (training.py:118: the generator's state dict;
         training.py:225-226: {"generator", "discriminator"}).  Values are copied into the existing parameter storage (the flat
-        arenas stay in place); optimizer moments start from zero, as after the reference's own cold start.  Returns the kind."""
+        arenas stay in place); optimizer moments start from zero, as after the reference's own cold start, and the EMA restarts from the
+        loaded weights, unless ``load_train_state`` follows (--resume-train-state).  Returns the kind."""
         ckpt = torch.load(path, map_location=self.args.device)
         if isinstance(ckpt, dict) and set(ckpt) == {"generator", "discriminator"}:
             self.gen.load_state_dict(ckpt["generator"])
@@ -438,12 +512,70 @@ class GANInstructor:
             kind = "pretrained"
         from . import engine
         engine.bump_param_epoch()          # compute-dtype weight images are stale
+        if self.ema is not None:
+            self.ema.reset()
         self.log.info("resumed %s weights from %s", kind, path)
         return kind
 
+    def _optimizers(self) -> dict:
+        opts = {"pretrain_opt": self.pretrain_opt, "gen_opt": self.gen_opt, "disc_opt": self.disc_opt}
+        if self.scst_opt is not None:
+            opts["scst_opt"] = self.scst_opt
+        return opts
+
+    def train_state(self) -> dict:
+        """What a model checkpoint leaves out: every optimizer's moments and step count, and the EMA's buffer and counter.  The
+        loops' epoch counters are not part of it."""
+        state = {name: opt.state_dict() for name, opt in self._optimizers().items()}
+        if self.ema is not None:
+            state["ema"] = self.ema.state_dict()
+        return state
+
+    def load_train_state(self, path: str) -> None:
+        """Restore a ``*.train_state`` file (after ``load_checkpoint``): the schedules' positions, Adam's bias correction and the
+        average continue where they were.  Optimizers absent from the file keep their fresh state; an EMA absent from it stays reset."""
+        state = torch.load(path, map_location=self.args.device)
+        for name, opt in self._optimizers().items():
+            if name in state:
+                opt.load_state_dict(state[name])
+        if self.ema is not None and "ema" in state:
+            self.ema.load_state_dict(state["ema"])
+        self._train_state = state
+        self.log.info("resumed optimizer state from %s", path)
+
+    @contextlib.contextmanager
+    def _eval_weights(self):
+        if not self.eval_ema or self._ema_held:
+            yield
+            return
+        self._ema_held = True
+        try:
+            with self.ema.swapped():
+                yield
+        finally:
+            self._ema_held = False
+
+    @contextlib.contextmanager
+    def _live_weights(self):
+        """Evaluations inside the block stay on the live weights (checkpoint selection)."""
+        held, self._ema_held = self._ema_held, True
+        try:
+            yield
+        finally:
+            self._ema_held = held
+
     def _save(self, obj, name):
+        """A model checkpoint, its ``<stem>.train_state`` and, with an EMA, ``<stem>_ema.ckpt``: the same format with the averaged
+        generator (buffers outside the arena, BatchNorm running statistics among them, are the live ones)."""
         if self.model_dir and self.dist.rank == 0:
             torch.save(obj, os.path.join(self.model_dir, name))
+            stem = name[:-len(".ckpt")] if name.endswith(".ckpt") else name
+            torch.save(self.train_state(), os.path.join(self.model_dir, stem + ".train_state"))
+            if self.ema is not None:
+                with self.ema.swapped():
+                    gen = self.gen.state_dict()
+                    avg = dict(obj, generator=gen) if set(obj) == {"generator", "discriminator"} else gen
+                    torch.save(avg, os.path.join(self.model_dir, stem + "_ema.ckpt"))
 
     # ------------------------------------------------------------------ self-critical sequence training (scst.py)
     def scst_train(self, epochs):
@@ -459,6 +591,9 @@ class GANInstructor:
         groups = ImageGroups(self.train_dataset)
         step = SCSTStep(self, scst_reward_scorer(args, groups.references()), int(getattr(args, "scst_samples", 5)),
                         getattr(args, "scst_baseline", "greedy"), float(getattr(args, "scst_lr", 5e-5)))
+        self.scst_opt = step.opt
+        if self._train_state is not None and "scst_opt" in self._train_state:
+            step.opt.load_state_dict(self._train_state["scst_opt"])
         dp = self.dist.world_size > 1
         loader = DataLoader(groups, shuffle=not dp, batch_size=args.adv_train_batch_size,
                             collate_fn=make_collate(self.train_dataset, groups=True),
@@ -482,7 +617,8 @@ class GANInstructor:
                     progress.update(len(images) * self.dist.world_size)
                     progress.set_postfix(reward=r, baseline=b, loss=loss)
             self.gen.eval()
-            val = self.evaluate_cider("val", beam_size=1) if self.dist.rank == 0 else 0.0
+            with self._live_weights():         # checkpoint selection stays on the live weights
+                val = self.evaluate_cider("val", beam_size=1) if self.dist.rank == 0 else 0.0
             self.writer.add_scalar("SCST_val_cider", val, epoch)
             if best is None or val > best:
                 best = val
@@ -540,6 +676,7 @@ class GANInstructor:
                                         weight=float(getattr(self.args, "eval_consensus_weight", 1.0)))
             self.writer.flush()
 
+    @_on_eval_weights
     def evaluate(self, what="val", beam_size=3, max_caption_len=None, batch_size=None):
         """BLEU-4 of beam-search captions against the dev (``what="val"``) or train captions: the captions are grouped by image
         (``filepath`` + ``filename`` for COCO_data, one image per item otherwise), every image is loaded and decoded once in eval
@@ -561,6 +698,7 @@ class GANInstructor:
         self.writer.add_scalar(f"BLEU4_{what}", score, max(self.adv_epoch, 0))
         return score
 
+    @_on_eval_weights
     def evaluate_match(self, what="val"):
         """Image-caption match of the conditioned D (--disc-cond projection) over the adversarial eval (``what="val"``) or train loader:
         per caption the match term F^-1/2 <y, q> (mean over the representations) with its own image against the batch's next image
@@ -596,6 +734,7 @@ class GANInstructor:
         self.writer.add_scalar(f"MatchMargin_{what}", out["margin"], step)
         return out
 
+    @_on_eval_weights
     def evaluate_perplexity(self, what="val"):
         """Teacher-forced per-token perplexity of the generator over the pre-training eval (``what="val"``) or train loader: one
         decoder.log_likelihood per batch (features as pretrain_step forms them, with the generator in eval mode for the pass, whatever mode
@@ -633,6 +772,7 @@ class GANInstructor:
 
     RETRIEVAL_MAX_ITEMS = 8192
 
+    @_on_eval_weights
     def evaluate_retrieval(self, what="val", max_items=None):
         """Image-caption retrieval of the conditioned D (--disc-cond projection) over the first N = min(max_items, len) items of the
         adversarial eval (``what="val"``) or train loader (len = what the loader yields on this rank: its sampler's length, the shard
@@ -751,6 +891,7 @@ class GANInstructor:
         finally:
             self.gen.train(was_training)
 
+    @_on_eval_weights
     def evaluate_cider(self, what="val", beam_size=3, max_caption_len=None, batch_size=None):
         """CIDEr-D of the beam-search captions of ``evaluate`` (the same images, grouping and caption length rule), scored on the GPU
         (gic_cider_d) with document frequencies from the evaluated split's references (the coco-caption convention).  Logs the score
@@ -769,6 +910,7 @@ class GANInstructor:
         self.writer.add_scalar(f"CIDErD_{what}", score, max(self.adv_epoch, 0))
         return score
 
+    @_on_eval_weights
     def evaluate_metrics(self, what="val", beam_size=3, max_caption_len=None, batch_size=None):
         """The metrics table of the beam-search captions of ``evaluate`` (the same images, grouping, caption length rule and decode
         constraints) from ONE decode pass, scored on the GPU: per batch one gic_caption_overlap launch (metrics.OverlapScorer) and one
@@ -823,6 +965,7 @@ class GANInstructor:
         words = lambda ids: [i2w.get(int(t), str(int(t))) for t in ids if int(t) not in strip]   # noqa: E731
         return ds, groups, order, coco, coco_ids, words
 
+    @_on_eval_weights
     def evaluate_diversity(self, what="val", num_samples=5, top_k=0, top_p=1.0, temperature=1.0, seed=1234, max_caption_len=None,
                            batch_size=None):
         """Caption diversity of ``num_samples`` sampled captions per image (Generator.sample_captions), on the images of ``evaluate``
@@ -841,6 +984,7 @@ class GANInstructor:
         self._write_diversity(out, what, ("BLEU4S", "mBLEU4", "Distinct1", "Distinct2", "Vocab"))
         return out
 
+    @_on_eval_weights
     def evaluate_diverse_beam(self, what="val", beam_size=4, groups=2, diversity=0.5, length_penalty=0.0, max_caption_len=None,
                               batch_size=None):
         """The metrics of ``evaluate_diversity`` for the ``beam_size`` captions per image of diverse beam search (Generator.caption
@@ -858,6 +1002,7 @@ class GANInstructor:
         self._write_diversity(out, what, ("BLEU4DBS", "mBLEU4DBS", "Distinct1DBS", "Distinct2DBS", "VocabDBS"))
         return out
 
+    @_on_eval_weights
     def evaluate_consensus(self, what="val", num_samples=8, top_k=0, top_p=1.0, temperature=1.0, weight=1.0, seed=1234, max_caption_len=None,
                            batch_size=None):
         """Consensus (minimum-Bayes-risk) selection among ``num_samples`` sampled captions per image, and their Self-CIDEr diversity, on

@@ -1056,6 +1056,45 @@ int gic_clip_adam(float* params, const float* grads, float* exp_avg, float* exp_
                   double beta1, double beta2, double eps, double clip_norm, int64_t* step_count, float* norm_out,
                   float* partials, void* stream);
 
+/* gic_clip_adam with a learning-rate schedule, decoupled weight decay (torch.optim.AdamW) over arena ranges and an exponential moving
+ * average of the parameters, all inside the same two launches.  With t the step counter after this call's increment and s = t - 1:
+ *   schedule   lr_t = lr * lambda(s) in float64 (torch.optim.lr_scheduler.LambdaLR: the t-th step uses lambda(t - 1)).  With W =
+ *              warmup_steps, T = total_steps, r = min_ratio, u = s - W, D = T - W:  s < W: (s + 1) / W;  else NONE 1;
+ *              LINEAR r + (1 - r) max(0, 1 - u/D);  COSINE r + (1 - r) (1 + cos(pi min(1, u/D))) / 2;
+ *              INVSQRT max(r, sqrt(max(W, 1) / (s + 1)));  STEP max(r, gamma^floor(u / step_size)).
+ *   decay      p *= (float)(1 - lr_t * weight_decay) before the Adam update, for the elements inside the range table only
+ *              (weight_decay = 0 or n_ranges = 0: nothing is multiplied).
+ *   Adam       as gic_clip_adam, with the step size lr_t / (1 - beta1^t).
+ *   EMA        with k = ema_count before the call (the call increments it, as it does step_count): d_k = ema_warmup ?
+ *              min(ema_decay, (1 + k) / (10 + k)) : ema_decay;  a = (float)(1 - d_k);  ema += (p_new - ema) * a.  ema NULL: none.
+ *   sched_out  optional device f32[2]: lr_t rounded to f32, and a (0 without an EMA).
+ * The range table holds n_ranges half-open element ranges [start, end) as int64 pairs, sorted, non-empty and disjoint, every boundary
+ * a multiple of 4 (arena slots are 16-byte aligned), at most GIC_ADAMW_MAX_RANGES of them.  It is passed twice: `ranges_host` (host
+ * memory) is validated on every call before anything is launched, `ranges` is its copy in device memory, which the kernel reads.
+ * Neutral options (weight_decay 0, GIC_LR_NONE, warmup_steps 0, no ema) give gic_clip_adam's outputs bit for bit.  Invalid options
+ * (negative weight_decay, min_ratio outside [0, 1], LINEAR / COSINE with total_steps <= warmup_steps, STEP without a positive
+ * step_size, ema_decay outside [0, 1), a refused table) return GIC_STATUS_INVALID_ARG with nothing launched.  No atomics. */
+#define GIC_ADAMW_MAX_RANGES 256
+enum { GIC_LR_NONE = 0, GIC_LR_LINEAR = 1, GIC_LR_COSINE = 2, GIC_LR_INVSQRT = 3, GIC_LR_STEP = 4 };
+typedef struct gic_adamw_opts {
+  double weight_decay;
+  const int64_t* ranges_host;   /* host   int64 [2 * n_ranges] */
+  const int64_t* ranges;        /* device int64 [2 * n_ranges], the same values */
+  int32_t n_ranges;
+  int32_t schedule;             /* GIC_LR_* */
+  int64_t warmup_steps, total_steps, step_size;
+  double min_ratio, gamma;
+  float* ema;                   /* device f32 [n] shadow arena, or NULL */
+  int64_t* ema_count;           /* device int64, with ema */
+  double ema_decay;
+  int32_t ema_warmup;
+  int32_t reserved;
+  float* sched_out;             /* device f32 [2], or NULL */
+} gic_adamw_opts;
+int gic_clip_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double lr,
+                   double beta1, double beta2, double eps, double clip_norm, int64_t* step_count, float* norm_out,
+                   float* partials, const gic_adamw_opts* opts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
