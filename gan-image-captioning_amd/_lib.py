@@ -78,6 +78,15 @@ class DecodeConstraints(C.Structure):
                 ("suppress", C.c_int32 * MAX_SUPPRESS)]
 
 
+MAX_ENSEMBLE = 4              # GIC_MAX_ENSEMBLE
+ENSEMBLE_MODES = {"prob": 0, "logprob": 1}       # GIC_ENSEMBLE_PROB / GIC_ENSEMBLE_LOGPROB
+
+
+class EnsembleOpts(C.Structure):
+    """gic_ensemble_opts (the gic_*_ensemble_* decodes)."""
+    _fields_ = [("M", C.c_int32), ("mode", C.c_int32), ("weights", C.c_float * MAX_ENSEMBLE)]
+
+
 STEP_SEEDS = 6
 
 
@@ -240,6 +249,23 @@ _SIGNATURES = {
     "gic_attn_constrained_sample_captions": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(SampleOpts), _P(DecodeConstraints),
                                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint64, c_void_p, c_void_p,
                                                        c_void_p, c_void_p]),
+    "gic_ensemble_mix": (C.c_int, [c_void_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, C.c_int32, c_void_p, c_void_p]),
+    "gic_decoder_ensemble_beam_ws_bytes": (C.c_int, [_P(DecoderDims), C.c_int32, C.c_int32, c_void_p]),
+    "gic_attn_ensemble_beam_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int32, C.c_int32, c_void_p]),
+    "gic_decoder_ensemble_sample_ws_bytes": (C.c_int, [_P(DecoderDims), C.c_int32, C.c_int32, c_void_p]),
+    "gic_attn_ensemble_sample_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int32, C.c_int32, c_void_p]),
+    "gic_decoder_ensemble_beam_search": (C.c_int, [_P(DecoderDims), C.c_int32, c_void_p, c_void_p, _P(EnsembleOpts), _P(DiverseBeamOpts),
+                                                   _P(DecodeConstraints), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p]),
+    "gic_attn_ensemble_beam_search": (C.c_int, [_P(AttnDims), C.c_int32, c_void_p, c_void_p, _P(EnsembleOpts), _P(DiverseBeamOpts),
+                                                _P(DecodeConstraints), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p]),
+    "gic_decoder_ensemble_sample_captions": (C.c_int, [_P(DecoderDims), C.c_int32, c_void_p, c_void_p, _P(EnsembleOpts), _P(SampleOpts),
+                                                       _P(DecodeConstraints), c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint64, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p]),
+    "gic_attn_ensemble_sample_captions": (C.c_int, [_P(AttnDims), C.c_int32, c_void_p, c_void_p, _P(EnsembleOpts), _P(SampleOpts),
+                                                    _P(DecodeConstraints), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint64,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "gic_attn_forward_tf_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int, c_void_p]),
     "gic_attn_forward_tf": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(AttnState), c_void_p, c_void_p, c_void_p, c_void_p,
                                       C.c_int, c_void_p, C.c_uint64, C.c_float, C.c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

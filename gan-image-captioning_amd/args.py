@@ -185,7 +185,65 @@ _NATIVE = [
                                          "0 = off", {"choices": list(range(9))}),
     ("--eval-consensus-weight", float, 1.0, "weight of a sample's consensus (its mean CIDEr-D against the image's other samples) beside "
                                             "its log-probability in that evaluation's pick"),
+    # decode-time ensemble of the evaluations (generator.Ensemble): members in the order live generator, checkpoints, EMA
+    ("--eval-ensemble", "pathlist", "", "comma-separated generator checkpoints (pretrained_model.ckpt, scst_model.ckpt, adv_model.ckpt, "
+                                        "*_ema.ckpt) that every evaluate* method ensembles with the live generator at decode time; "
+                                        "empty = off"),
+    ("--eval-ensemble-ema", int, 0, "1: the averaged generator joins the evaluations' ensemble as its last member (needs --gen-ema-decay "
+                                    "> 0; not with --eval-ema 1)", {"choices": [0, 1]}),
+    ("--eval-ensemble-weights", "floatlist", "", "comma-separated weights of the ensemble's members in the order live, checkpoints, EMA "
+                                                 "(each > 0; normalised to sum 1); empty = uniform"),
+    ("--eval-ensemble-mode", str, "prob", "how the members' next-token distributions are mixed: prob = the weighted arithmetic mean of the "
+                                          "probabilities, logprob = the weighted geometric mean", {"choices": ["prob", "logprob"]}),
 ]
+
+MAX_ENSEMBLE = 4          # gicap.h GIC_MAX_ENSEMBLE
+
+
+def _pathlist(text):
+    if isinstance(text, (list, tuple)):
+        return [str(v) for v in text]
+    return [v.strip() for v in str(text).split(",") if v.strip()]
+
+
+def _floatlist(text):
+    if isinstance(text, (list, tuple)):
+        return [float(v) for v in text]
+    try:
+        return [float(v) for v in str(text).split(",") if v.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected comma-separated numbers, got {text!r}")
+
+
+def check_eval_ensemble(args):
+    """The evaluations' ensemble as the flags ask for it: None with every flag at its default, else {"paths", "with_ema", "weights"
+    (None: uniform), "mode"}.  Refused: --eval-ensemble* with --eval-ema 1, --eval-ensemble-ema 1 without an EMA, more than
+    MAX_ENSEMBLE members, weights that are not one positive finite value per member, weights or a mode without any member to mix."""
+    paths = _pathlist(getattr(args, "eval_ensemble", "") or "")
+    with_ema = bool(int(getattr(args, "eval_ensemble_ema", 0) or 0))
+    weights = _floatlist(getattr(args, "eval_ensemble_weights", "") or "")
+    mode = getattr(args, "eval_ensemble_mode", "prob") or "prob"
+    if mode not in ("prob", "logprob"):
+        raise ValueError(f"--eval-ensemble-mode must be prob or logprob, got {mode!r}")
+    if not paths and not with_ema:
+        if weights or mode != "prob":
+            raise ValueError("--eval-ensemble-weights / --eval-ensemble-mode need an ensemble: set --eval-ensemble or --eval-ensemble-ema 1")
+        return None
+    if int(getattr(args, "eval_ema", 0) or 0):
+        raise ValueError("--eval-ensemble* with --eval-ema 1: the evaluations run either on the averaged generator alone (--eval-ema 1) or "
+                         "on an ensemble that may hold it as a member (--eval-ensemble-ema 1); use one of the two")
+    if with_ema and not float(getattr(args, "gen_ema_decay", 0.0) or 0.0) > 0.0:
+        raise ValueError("--eval-ensemble-ema 1 puts the averaged generator into the ensemble: it needs --gen-ema-decay > 0")
+    M = 1 + len(paths) + int(with_ema)
+    if M > MAX_ENSEMBLE:
+        raise ValueError(f"the evaluations' ensemble has {M} members (live, {len(paths)} checkpoints{', EMA' if with_ema else ''}); at most "
+                         f"{MAX_ENSEMBLE}")
+    if weights:
+        if len(weights) != M:
+            raise ValueError(f"--eval-ensemble-weights holds {len(weights)} values for {M} members (live, checkpoints, EMA)")
+        if not all(0.0 < w < float("inf") for w in weights):
+            raise ValueError("--eval-ensemble-weights must be finite and > 0")
+    return {"paths": paths, "with_ema": with_ema, "weights": weights or None, "mode": mode}
 
 
 def _intlist(text):
@@ -222,6 +280,10 @@ def _add(parser, rows):
             typ = _intlist
         elif typ == "floatpair":
             typ = _floatpair
+        elif typ == "pathlist":
+            typ = _pathlist
+        elif typ == "floatlist":
+            typ = _floatlist
         parser.add_argument(flag, type=typ, default=default, help=helptext, **extra)
 
 

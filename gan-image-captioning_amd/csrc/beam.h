@@ -260,4 +260,12 @@ int sample_step(const float* logits, int rows, int V, const gic_sample_opts* o, 
 // ids [rows][L] = each row's history up to its length, pad behind; scores / lengths [rows]
 int sample_finalize(const BeamState& st, int rows, int L, int pad, int64_t* ids, float* scores, int32_t* lengths, hipStream_t stream);
 
+// ---- ensemble.hip: the mixing step of the ensemble searches
+// M in 1..GIC_MAX_ENSEMBLE, mode, every weight finite and > 0 (who: the prefix of the error text)
+int check_ensemble_opts(const gic_ensemble_opts* o, const char* who);
+// z f32 [rows, V] = the members' logits f32 [M][rows][V] (member m at logits + m * mstride) mixed by o (weights normalised here);
+// stop (may be null) / stop_at as for the other step kernels
+int ensemble_mix(const float* logits, long mstride, int rows, int V, const gic_ensemble_opts& o, float* out, const int* stop, int stop_at,
+                 hipStream_t stream);
+
 }  // namespace gic

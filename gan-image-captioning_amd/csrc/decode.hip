@@ -36,6 +36,15 @@
 // -- are the instantiations that read the lists; beam_select's selection is unchanged, since the tile partials it merges already
 // hold admissible tokens only.  With every constraint off the entry points run the unconstrained search itself.
 //
+// Ensemble searches (the gic_*_ensemble_* entry points): M instances of one recurrence, each over its own recurrent regions, features
+// and feature map, around ONE search state and one set of tile partials (decode_ensemble).  Per step each member runs its recurrence and
+// writes its f32 logits into its slab (vocab_step_logits where the fused kernels take the shapes, else the GEMM), ensemble_mix
+// (ensemble.hip) writes the mixed logits into `logits`, and the heads take them as they take the generic path's: beam_tile_topk +
+// beam_select, or sample_step.  (Folding the tile top-k into the mix's second pass was built and measured slower: DESIGN.md section 27.)
+// Scratch: the regions above with the logits always present and without ahist / anc (member 0's recurrent regions are the ones
+// listed first), then slabs f32 [M][rows][V], then xh / c / gpre / fproj / hp / e of members 1..M-1.
+// The single-model entry points launch what they launched before.
+//
 // Entry path: every extern "C" decode is a model (LstmModel / AttnModel: the decoder's dims, weights and, with attention, the feature
 // map; its shape check, its argument check, run()), the two prefixes of its error texts and one call of beam_entry or sample_entry;
 // the four *_ws_bytes are ws_bytes_entry.  Order of checks -- beam: null options, shapes, arguments and weights, options; sampler: null
@@ -106,39 +115,78 @@ struct DecodeBufs {
   size_t total;
 };
 
-// the regions of the header comment in the workspace ws (null: only the total is meaningful)
-DecodeBufs decode_layout(const DecodeDims& d, bool beam, void* ws) {
-  DecodeBufs o{};
-  size_t at = 0;
-  auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)ws + at); at += (bytes + 255) & ~(size_t)255; return p; };
-  const size_t R = d.rows, pn = R * d.nblk, LR = (size_t)d.L * R;
+// carves 256-byte aligned regions out of a workspace (null: only the running total is meaningful)
+struct Carver {
+  void* ws; size_t at = 0;
+  void* take(size_t bytes) { void* p = (void*)((uintptr_t)ws + at); at += (bytes + 255) & ~(size_t)255; return p; }
+};
+
+// one recurrence's own regions (xh, c, gpre, fproj, hp, e), in the header comment's order
+void recurrent_layout(const DecodeDims& d, Carver& cv, DecodeBufs& o) {
+  const size_t R = d.rows;
   for (int l = 0; l < d.NL; ++l) {
     const size_t xb = R * d.ldx(l) * d.asz();
-    char* xh = (char*)take(2 * xb);
-    float* c = (float*)take(2 * R * d.H * 4);
+    char* xh = (char*)cv.take(2 * xb);
+    float* c = (float*)cv.take(2 * R * d.H * 4);
     for (int s = 0; s < 2; ++s) { o.slot[s].xh[l] = xh + s * xb; o.slot[s].c[l] = c + s * R * d.H; }
   }
-  if (!d.fused) o.gpre = (float*)take(R * 4 * d.H * 4);
+  if (!d.fused) o.gpre = (float*)cv.take(R * 4 * d.H * 4);
   if (d.attn()) {
-    o.fproj = take((size_t)d.B * d.P * d.A * d.asz());
-    o.hp = (float*)take(R * d.A * 4);
-    o.e = (float*)take(R * d.P * 4);
-    if (beam) o.ahist = (float*)take(LR * d.P * 4);
+    o.fproj = cv.take((size_t)d.B * d.P * d.A * d.asz());
+    o.hp = (float*)cv.take(R * d.A * 4);
+    o.e = (float*)cv.take(R * d.P * 4);
   }
-  if (!beam || !d.fused) o.logits = (float*)take(R * d.V * 4);
+}
+
+// the regions of the header comment (ensemble: always the logits, never the alpha history and the ancestors)
+DecodeBufs decode_layout(const DecodeDims& d, bool beam, Carver& cv, bool ensemble) {
+  DecodeBufs o{};
+  const size_t R = d.rows, pn = R * d.nblk, LR = (size_t)d.L * R;
+  recurrent_layout(d, cv, o);
+  if (d.attn() && beam && !ensemble) o.ahist = (float*)cv.take(LR * d.P * 4);
+  if (!beam || !d.fused || ensemble) o.logits = (float*)cv.take(R * d.V * 4);
   if (beam) {
-    o.pm = (float*)take(pn * 4); o.ps = (float*)take(pn * 4);
-    o.pv = (float*)take(pn * d.K * 4); o.pi = (int*)take(pn * d.K * 4);
+    o.pm = (float*)cv.take(pn * 4); o.ps = (float*)cv.take(pn * 4);
+    o.pv = (float*)cv.take(pn * d.K * 4); o.pi = (int*)cv.take(pn * d.K * 4);
   }
   BeamState& s = o.st;
-  s.score = (float*)take(R * 4);
-  s.fin = (int*)take(R * 4); s.len = (int*)take(R * 4); s.tok = (int*)take(R * 4); s.par = (int*)take(R * 4);
-  s.htok = (int*)take(LR * 4);
-  if (beam) s.hpar = (int*)take(LR * 4);
-  if (beam && d.attn()) o.anc = (int*)take(LR * 4);
-  s.last = (int*)take((size_t)d.B * 4); s.done = (int*)take((size_t)d.B * 4); s.count = (int*)take(4);
-  o.total = at;
+  s.score = (float*)cv.take(R * 4);
+  s.fin = (int*)cv.take(R * 4); s.len = (int*)cv.take(R * 4); s.tok = (int*)cv.take(R * 4); s.par = (int*)cv.take(R * 4);
+  s.htok = (int*)cv.take(LR * 4);
+  if (beam) s.hpar = (int*)cv.take(LR * 4);
+  if (beam && d.attn() && !ensemble) o.anc = (int*)cv.take(LR * 4);
+  s.last = (int*)cv.take((size_t)d.B * 4); s.done = (int*)cv.take((size_t)d.B * 4); s.count = (int*)cv.take(4);
+  o.total = cv.at;
   return o;
+}
+
+DecodeBufs decode_layout(const DecodeDims& d, bool beam, void* ws) {
+  Carver cv{ws};
+  return decode_layout(d, beam, cv, false);
+}
+
+// an ensemble search's workspace: the single search's regions with member 0's recurrence (w), the members' logits, then the
+// recurrent regions of members 1..M-1; mem[m] = w with member m's recurrent regions and its slab as the logits
+struct EnsembleBufs {
+  DecodeBufs w;
+  DecodeBufs mem[GIC_MAX_ENSEMBLE];
+  float* slabs;                  // f32 [M][rows][V]
+  size_t total;
+};
+
+EnsembleBufs ensemble_layout(const DecodeDims& d, bool beam, int M, void* ws) {
+  EnsembleBufs e{};
+  Carver cv{ws};
+  e.w = decode_layout(d, beam, cv, true);
+  const size_t slab = (size_t)d.rows * d.V;
+  e.slabs = (float*)cv.take((size_t)M * slab * 4);
+  for (int m = 0; m < M; ++m) {
+    e.mem[m] = e.w;
+    if (m > 0) recurrent_layout(d, cv, e.mem[m]);
+    e.mem[m].logits = e.slabs + m * slab;
+  }
+  e.total = cv.at;
+  return e;
 }
 
 // decode constraints: the caller's struct and the regions of its workspace (cws)
@@ -338,6 +386,34 @@ struct SampleHead {
   int finish(const Search& s) const { return sample_finalize(s.w.st, s.d.rows, s.d.L, o->pad_id, ids, scores, lengths, s.stream); }
 };
 
+// the step's vocabulary product of one recurrence: the fused product's arguments (the head finishes them), or the GEMM into w.logits
+template <typename Rec>
+const void* top_h(const Search& s, int t) {
+  const int top = s.d.NL - 1;
+  return s.d.act(s.w.slot[Rec::kFused ? (t & 1) ^ 1 : 1].xh[top], s.d.din(top));
+}
+
+template <typename Rec>
+VocabStepArgs vocab_args(const Search& s, const Rec& rec, int t) {
+  const DecodeDims& d = s.d;
+  VocabStepArgs v;
+  v.h = top_h<Rec>(s, t); v.ldh = d.ldx(d.NL - 1);
+  v.wout = rec.S->wout; v.bias = rec.P->b_out;
+  v.stop = s.w.st.count; v.stop_at = s.stop_at;
+  v.B = d.rows; v.V = d.V; v.H = d.H;
+  return v;
+}
+
+template <typename Rec>
+int logits_gemm(const Search& s, const Rec& rec, int t) {
+  const DecodeDims& d = s.d;
+  GemmDesc g;
+  g.A = top_h<Rec>(s, t); g.lda = d.ldx(d.NL - 1); g.B = rec.S->wout; g.ldb = d.H; g.C = s.w.logits; g.ldc = d.V;
+  g.M = d.rows; g.N = d.V; g.K = d.H; g.in_dtype = d.dt; g.out_dtype = DT_F32; g.bias = rec.P->b_out;
+  g.no_split = 1;
+  return gemm(g, s.stream);
+}
+
 // one search: beam_init (and step 0's ban lists) and the recurrence's begin(), then per step the recurrence, the vocabulary product
 // and the head's selection
 template <typename Rec, typename Head>
@@ -348,25 +424,48 @@ int decode(const DecodeDims& d, const Rec& rec, const Head& head, void* ws, cons
   GIC_PROPAGATE(beam_init(w.slot[0], d.NL, d.din(0), d.E, d.H, d.B, d.K, d.dt, features, h0, c0, w.st, s.stream, head.live_stride(d)));
   if (head.cons) GIC_PROPAGATE(ban_init(head.cons->out(), head.cons->rule(head.eos()), d.rows, s.stream));
   GIC_PROPAGATE(rec.begin(s));
-  const int top = d.NL - 1;
   for (int t = 0; t < d.L; ++t) {
     GIC_PROPAGATE(rec.step(s, t));
-    const void* h = d.act(w.slot[Rec::kFused ? (t & 1) ^ 1 : 1].xh[top], d.din(top));
     if constexpr (Rec::kFused) {
-      VocabStepArgs v;
-      v.h = h; v.ldh = d.ldx(top);
-      v.wout = rec.S->wout; v.bias = rec.P->b_out;
-      v.stop = w.st.count; v.stop_at = s.stop_at;
-      v.B = d.rows; v.V = d.V; v.H = d.H;
+      VocabStepArgs v = vocab_args(s, rec, t);
       GIC_PROPAGATE(head.vocab(v, s));
     } else {
-      GemmDesc g;
-      g.A = h; g.lda = d.ldx(top); g.B = rec.S->wout; g.ldb = d.H; g.C = w.logits; g.ldc = d.V;
-      g.M = d.rows; g.N = d.V; g.K = d.H; g.in_dtype = d.dt; g.out_dtype = DT_F32; g.bias = rec.P->b_out;
-      g.no_split = 1;
-      GIC_PROPAGATE(gemm(g, s.stream));
+      GIC_PROPAGATE(logits_gemm(s, rec, t));
       GIC_PROPAGATE(head.logits(s));
     }
+    GIC_PROPAGATE(head.select(s, t));
+  }
+  return head.finish(s);
+}
+
+// one ensemble search: M instances of one recurrence, each over its own recurrent regions and features, around one search state.  Per
+// step every member's f32 logits go into its slab (the fused product's logits form, else the GEMM), ensemble_mix writes the mixed
+// logits into w.logits, and the head takes them as it takes the generic path's
+template <typename Rec, typename Head>
+int decode_ensemble(const DecodeDims& d, const Rec* rec, const gic_ensemble_opts& eo, const Head& head, void* ws, const float* const* features,
+                    void* stream) {
+  const EnsembleBufs e = ensemble_layout(d, Head::kBeam, eo.M, ws);
+  const int stop_at = Head::kBeam ? d.B : d.rows;
+  const Search s{d, e.w, stop_at, (hipStream_t)stream};
+  for (int m = 0; m < eo.M; ++m)         // (every member writes the same initial search state)
+    GIC_PROPAGATE(beam_init(e.mem[m].slot[0], d.NL, d.din(0), d.E, d.H, d.B, d.K, d.dt, features[m], nullptr, nullptr, e.w.st, s.stream,
+                            head.live_stride(d)));
+  if (head.cons) GIC_PROPAGATE(ban_init(head.cons->out(), head.cons->rule(head.eos()), d.rows, s.stream));
+  for (int m = 0; m < eo.M; ++m) GIC_PROPAGATE(rec[m].begin(Search{d, e.mem[m], stop_at, s.stream}));
+  for (int t = 0; t < d.L; ++t) {
+    for (int m = 0; m < eo.M; ++m) {
+      const Search sm{d, e.mem[m], stop_at, s.stream};
+      GIC_PROPAGATE(rec[m].step(sm, t));
+      if constexpr (Rec::kFused) {
+        VocabStepArgs v = vocab_args(sm, rec[m], t);
+        v.logits = sm.w.logits; v.ld_logits = d.V;
+        GIC_PROPAGATE(vocab_step_logits(v, d.dt, s.stream));
+      } else {
+        GIC_PROPAGATE(logits_gemm(sm, rec[m], t));
+      }
+    }
+    GIC_PROPAGATE(ensemble_mix(e.slabs, (long)d.rows * d.V, d.rows, d.V, eo, e.w.logits, e.w.st.count, stop_at, s.stream));
+    GIC_PROPAGATE(head.logits(s));
     GIC_PROPAGATE(head.select(s, t));
   }
   return head.finish(s);
@@ -489,6 +588,111 @@ int sample_entry(const Model& m, Who who, const gic_sample_opts* o, const ConsAr
   return entry_tail(m, d, head, who.call, k, io);
 }
 
+// ---- the ensemble entry path: the members' side of a call (M of one decoder kind behind one set of dims), then the heads' own
+// checks.  Order: null options, the ensemble options (M, mode, weights), shapes, the head's options, the member arrays and every
+// member's weights and inputs, the constraints, the workspace's alignment, the constraint workspace
+struct LstmEnsemble {
+  const gic_decoder_dims* dims; const gic_decoder_params* const* P; const gic_decoder_shadow* const* S;
+  const float* const* features; const void* const* fmaps;
+  int shape(int K, bool beam, const char* who, DecodeDims& d) const { return lstm_dims(dims, K, beam, who, d); }
+  int check(const DecodeDims& d, int M, const char* who) const {
+    GIC_CHECK_ARG(P && S && features, "%s: null member array", who);
+    for (int m = 0; m < M; ++m) {
+      GIC_CHECK_ARG(P[m] && S[m] && features[m], "%s: null member %d", who, m);
+      GIC_PROPAGATE(check_lstm_args(P[m], S[m], d.NL, true, who));
+    }
+    return GIC_OK;
+  }
+  template <typename Head>
+  int run(const DecodeDims& d, const gic_ensemble_opts& eo, const Head& head, void* ws, void* stream) const {
+    if (d.fused) {
+      LstmFused r[GIC_MAX_ENSEMBLE];
+      for (int m = 0; m < eo.M; ++m) r[m] = LstmFused{P[m], S[m]};
+      return decode_ensemble(d, r, eo, head, ws, features, stream);
+    }
+    LstmGeneric r[GIC_MAX_ENSEMBLE];
+    for (int m = 0; m < eo.M; ++m) r[m] = LstmGeneric{P[m], S[m]};
+    return decode_ensemble(d, r, eo, head, ws, features, stream);
+  }
+};
+
+struct AttnEnsemble {
+  const gic_attn_dims* dims; const gic_attn_params* const* P; const gic_attn_shadow* const* S;
+  const float* const* features; const void* const* fmaps;
+  int shape(int K, bool beam, const char* who, DecodeDims& d) const { return attn_dims(dims, K, beam, who, d); }
+  int check(const DecodeDims&, int M, const char* who) const {
+    GIC_CHECK_ARG(P && S && features && fmaps, "%s: null member array", who);
+    for (int m = 0; m < M; ++m) {
+      GIC_CHECK_ARG(P[m] && S[m] && features[m] && fmaps[m], "%s: null member %d", who, m);
+      GIC_PROPAGATE(check_attn_args(P[m], S[m], true, who));
+    }
+    return GIC_OK;
+  }
+  template <typename Head>
+  int run(const DecodeDims& d, const gic_ensemble_opts& eo, const Head& head, void* ws, void* stream) const {
+    Attn r[GIC_MAX_ENSEMBLE];
+    for (int m = 0; m < eo.M; ++m) r[m] = Attn{P[m], S[m], fmaps[m], false};
+    return decode_ensemble(d, r, eo, head, ws, features, stream);
+  }
+};
+
+int check_ensemble_count(int M, const gic_ensemble_opts* eo, const char* who) {
+  GIC_PROPAGATE(check_ensemble_opts(eo, who));
+  GIC_CHECK_ARG(M == eo->M, "%s: M (%d) differs from the ensemble options' (%d)", who, M, eo->M);
+  return GIC_OK;
+}
+
+template <typename Members>
+int ensemble_ws_bytes_entry(const Members& e, int M, int K, bool beam, const char* who, uint64_t* out) {
+  GIC_CHECK_ARG(M >= 1 && M <= GIC_MAX_ENSEMBLE, "%s_ws_bytes: M must be 1..%d, got %d", who, GIC_MAX_ENSEMBLE, M);
+  DecodeDims d;
+  GIC_PROPAGATE(e.shape(K, beam, who, d));
+  GIC_CHECK_ARG(out, "%s_ws_bytes: null out", who);
+  *out = (uint64_t)ensemble_layout(d, beam, M, nullptr).total;
+  return GIC_OK;
+}
+
+template <typename Members, typename Head>
+int ensemble_tail(const Members& e, const DecodeDims& d, const gic_ensemble_opts& eo, Head head, const char* who, const gic_decode_constraints* c,
+                  void* ws, void* cws, void* stream) {
+  GIC_CHECK_ARG(ws && head.ids && head.scores && head.lengths, "%s: null argument", who);
+  GIC_PROPAGATE(e.check(d, eo.M, who));
+  if (c) GIC_PROPAGATE(check_constraints(c, d.L, d.V, Head::kBeam ? d.K : 1, head.eos(), who));
+  GIC_CHECK_ARG(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+  if (!c || constraints_off(c)) return e.run(d, eo, head, ws, stream);
+  GIC_CHECK_ARG(cws && ((uintptr_t)cws & 255) == 0, "%s: the constraint workspace must be non-null and 256-byte aligned", who);
+  const Constraints cons = constraints_layout(c, (size_t)d.rows, d.L, cws);
+  head.cons = &cons;
+  return e.run(d, eo, head, ws, stream);
+}
+
+template <typename Members>
+int ensemble_beam_entry(const Members& e, int M, const char* who, const gic_ensemble_opts* eo, const gic_diverse_beam_opts* dv,
+                        const gic_decode_constraints* c, void* ws, void* cws, int64_t* ids, float* scores, int32_t* lengths, void* stream) {
+  GIC_CHECK_ARG(dv, "%s: null options", who);
+  GIC_PROPAGATE(check_ensemble_count(M, eo, who));
+  DecodeDims d;
+  GIC_PROPAGATE(e.shape(dv->beam.beam, true, who, d));
+  GIC_PROPAGATE(check_diverse_opts(dv, d.V, who));
+  GIC_CHECK_ARG(!dv->beam.h0 && !dv->beam.c0, "%s: an ensemble search takes no initial states (h0 / c0 must be null)", who);
+  const BeamHead head{&dv->beam, ids, scores, lengths, nullptr, dv->groups, dv->diversity};
+  return ensemble_tail(e, d, *eo, head, who, c, ws, cws, stream);
+}
+
+template <typename Members>
+int ensemble_sample_entry(const Members& e, int M, const char* who, const gic_ensemble_opts* eo, const gic_sample_opts* o,
+                          const gic_decode_constraints* c, void* ws, void* cws, const float* noise_u, uint64_t seed, int64_t* ids,
+                          float* scores, int32_t* lengths, void* stream) {
+  GIC_CHECK_ARG(o, "%s: null options", who);
+  GIC_PROPAGATE(check_ensemble_count(M, eo, who));
+  DecodeDims d;
+  GIC_PROPAGATE(e.shape(o->num_samples, false, who, d));
+  GIC_PROPAGATE(check_sample_opts(o, d.V, true, who));
+  GIC_CHECK_ARG(!o->h0 && !o->c0, "%s: an ensemble search takes no initial states (h0 / c0 must be null)", who);
+  const SampleHead head{o, noise_u, seed, ids, scores, lengths};
+  return ensemble_tail(e, d, *eo, head, who, c, ws, cws, stream);
+}
+
 }  // namespace
 }  // namespace gic
 
@@ -594,6 +798,55 @@ int gic_attn_constrained_sample_captions(const gic_attn_dims* dims, const gic_at
   const ConsArgs k{c, cws};
   return sample_entry(AttnModel{dims, P, S, fmap, false}, {"attn_constrained_sample_captions", "attn_constrained_sample"}, o, &k,
                       {ws, features, ids, scores, lengths, stream}, noise_u, seed);
+}
+
+int gic_decoder_ensemble_beam_ws_bytes(const gic_decoder_dims* dims, int32_t M, int32_t beam, uint64_t* out) {
+  return ensemble_ws_bytes_entry(LstmEnsemble{dims}, M, beam, true, "decoder_ensemble_beam", out);
+}
+
+int gic_attn_ensemble_beam_ws_bytes(const gic_attn_dims* dims, int32_t M, int32_t beam, uint64_t* out) {
+  return ensemble_ws_bytes_entry(AttnEnsemble{dims}, M, beam, true, "attn_ensemble_beam", out);
+}
+
+int gic_decoder_ensemble_sample_ws_bytes(const gic_decoder_dims* dims, int32_t M, int32_t num_samples, uint64_t* out) {
+  return ensemble_ws_bytes_entry(LstmEnsemble{dims}, M, num_samples, false, "decoder_ensemble_sample", out);
+}
+
+int gic_attn_ensemble_sample_ws_bytes(const gic_attn_dims* dims, int32_t M, int32_t num_samples, uint64_t* out) {
+  return ensemble_ws_bytes_entry(AttnEnsemble{dims}, M, num_samples, false, "attn_ensemble_sample", out);
+}
+
+int gic_decoder_ensemble_beam_search(const gic_decoder_dims* dims, int32_t M, const gic_decoder_params* const* P,
+                                     const gic_decoder_shadow* const* S, const gic_ensemble_opts* eo, const gic_diverse_beam_opts* o,
+                                     const gic_decode_constraints* c, void* ws, void* cws, const float* const* features, int64_t* ids,
+                                     float* scores, int32_t* lengths, void* stream) {
+  return ensemble_beam_entry(LstmEnsemble{dims, P, S, features, nullptr}, M, "decoder_ensemble_beam_search", eo, o, c, ws, cws, ids, scores,
+                             lengths, stream);
+}
+
+int gic_attn_ensemble_beam_search(const gic_attn_dims* dims, int32_t M, const gic_attn_params* const* P, const gic_attn_shadow* const* S,
+                                  const gic_ensemble_opts* eo, const gic_diverse_beam_opts* o, const gic_decode_constraints* c, void* ws,
+                                  void* cws, const float* const* features, const void* const* fmaps, int64_t* ids, float* scores,
+                                  int32_t* lengths, void* stream) {
+  return ensemble_beam_entry(AttnEnsemble{dims, P, S, features, fmaps}, M, "attn_ensemble_beam_search", eo, o, c, ws, cws, ids, scores,
+                             lengths, stream);
+}
+
+int gic_decoder_ensemble_sample_captions(const gic_decoder_dims* dims, int32_t M, const gic_decoder_params* const* P,
+                                         const gic_decoder_shadow* const* S, const gic_ensemble_opts* eo, const gic_sample_opts* o,
+                                         const gic_decode_constraints* c, void* ws, void* cws, const float* const* features,
+                                         const float* noise_u, uint64_t seed, int64_t* ids, float* scores, int32_t* lengths, void* stream) {
+  return ensemble_sample_entry(LstmEnsemble{dims, P, S, features, nullptr}, M, "decoder_ensemble_sample_captions", eo, o, c, ws, cws, noise_u,
+                               seed, ids, scores, lengths, stream);
+}
+
+int gic_attn_ensemble_sample_captions(const gic_attn_dims* dims, int32_t M, const gic_attn_params* const* P,
+                                      const gic_attn_shadow* const* S, const gic_ensemble_opts* eo, const gic_sample_opts* o,
+                                      const gic_decode_constraints* c, void* ws, void* cws, const float* const* features,
+                                      const void* const* fmaps, const float* noise_u, uint64_t seed, int64_t* ids, float* scores,
+                                      int32_t* lengths, void* stream) {
+  return ensemble_sample_entry(AttnEnsemble{dims, P, S, features, fmaps}, M, "attn_ensemble_sample_captions", eo, o, c, ws, cws, noise_u, seed,
+                               ids, scores, lengths, stream);
 }
 
 }  // extern "C"

@@ -419,6 +419,136 @@ class _CaptionDecodes:
         return outs
 
 
+    # ---- ensemble searches (gic_*_ensemble_*): M members of one decoder kind and dims around one search state
+    def _ensemble_ws_bytes(self, head: str, B: int, Lc: int, M: int, n: int) -> int:
+        name = f"{self._PREFIX}_ensemble_{head}_ws_bytes"
+        out = C.c_uint64(0)
+        L.check(getattr(L.load(), name)(C.byref(self.dims(B, Lc)), int(M), int(n), C.byref(out)), name)
+        return int(out.value)
+
+    def ensemble_beam_ws_bytes(self, B: int, Lc: int, M: int, beam: int) -> int:
+        """Bytes of the ensemble beam search's workspace for M members (host-only query)."""
+        return self._ensemble_ws_bytes("beam", B, Lc, M, beam)
+
+    def ensemble_sample_ws_bytes(self, B: int, Lc: int, M: int, num_samples: int) -> int:
+        """Bytes of the ensemble sampling decode's workspace for M members (host-only query)."""
+        return self._ensemble_ws_bytes("sample", B, Lc, M, num_samples)
+
+    def _ensemble_members(self, members, features, fmaps):
+        """Checks the members [(engine, params)] against this engine (member 0's) and prepares them.  Returns (B, dev, the arrays of
+        M params / shadow structs / feature / map pointers, everything they point to)."""
+        members = list(members)
+        M = len(members)
+        if not 1 <= M <= L.MAX_ENSEMBLE:
+            raise ValueError(f"an ensemble has 1..{L.MAX_ENSEMBLE} members, got {M}")
+        if len(features) != M or (fmaps is not None and len(fmaps) != M):
+            raise ValueError(f"an ensemble of {M} members needs {M} feature tensors (and feature maps)")
+        if members[0][0] is not self:
+            raise ValueError("the ensemble's first member must be the engine the search is called on")
+        mine = bytes(self.dims(1, 1))
+        seen = {}
+        for m, (eng, _) in enumerate(members):
+            if type(eng) is not type(self) or bytes(eng.dims(1, 1)) != mine:
+                raise ValueError(f"ensemble member {m} differs from member 0 in decoder kind, dims or compute dtype")
+        for m, (eng, params) in enumerate(members):
+            eng.check_params(params)
+            if seen.setdefault(id(eng), _key(params)) != _key(params):
+                raise ValueError(f"ensemble member {m} shares its engine with another member but not its weights: one engine holds one "
+                                 "set of weight images")
+        feats = [_decode_features(f, self.E) for f in features]
+        B, dev = feats[0].shape[0], feats[0].device
+        if any(f.shape[0] != B for f in feats):
+            raise ValueError("the members' features differ in batch size")
+        require_gpu(*feats, *(fmaps or ()))
+        maps = [] if fmaps is None else [self._decode_maps(f, B)[0] for f in fmaps]
+        keep = []
+        for eng, params in members:
+            eng.prepare(params)
+            keep.append((eng._pstruct(params), eng._shadow_struct(params)))
+        parr = (C.c_void_p * M)(*[C.addressof(p) for p, _ in keep])
+        sarr = (C.c_void_p * M)(*[C.addressof(s) for _, s in keep])
+        farr = (C.c_void_p * M)(*[ptr(f) for f in feats])
+        ins = [farr] + ([(C.c_void_p * M)(*[ptr(f) for f in maps])] if maps else [])
+        return M, B, dev, parr, sarr, ins, (keep, feats, maps)
+
+    def _ensemble_call(self, what: str, B, Lc, M, parr, sarr, eopts, opts, cons, rows, ws, ins, outs, draw=()):
+        name = f"{self._PREFIX}_ensemble_{what}"
+        cws = None if cons is None else _constraints_ws(cons, rows, Lc, ws.device)
+        L.check(getattr(L.load(), name)(C.byref(self.dims(B, Lc)), M, parr, sarr, C.byref(eopts), C.byref(opts),
+                                        None if cons is None else C.byref(cons), ptr(ws), ptr(cws), *ins, *draw, *map(ptr, outs),
+                                        stream_ptr()), name)
+
+    def ensemble_beam_search(self, members, features, fmaps, Lc: int, beam: int, weights=None, mode: str = "prob", groups: int = 1,
+                             diversity: float = 0.0, eos_id: int = 2, pad_id: int = 0, length_penalty: float = 0.0,
+                             ws: Optional[torch.Tensor] = None, no_repeat_ngram: int = 0, min_length: int = 0, suppress_tokens=()):
+        """gic_*_ensemble_beam_search on this engine (member 0's): ``members`` = [(engine, params)] of one decoder kind, dims and compute
+        dtype, ``features`` a list of M f32 [B, E] tensors (``fmaps``: M [B, P, C] tensors for the attention decoder, else None).
+        ``weights`` (None: uniform) / ``mode`` ("prob" / "logprob"): ensemble_opts.  Returns (ids int64 [B, beam, Lc], scores f32
+        [B, beam], lengths int32 [B, beam]) as beam_search / diverse_beam_search (``groups``, ``diversity``) do; the decode constraints
+        as for beam_search."""
+        M, B, dev, parr, sarr, ins, keep = self._ensemble_members(members, features, fmaps)
+        eopts = ensemble_opts(M, weights, mode)
+        cons = decode_constraints(no_repeat_ngram, min_length, suppress_tokens)
+        opts = L.DecoderBeamOpts()
+        opts.beam, opts.eos_id, opts.pad_id, opts.length_penalty = int(beam), int(eos_id), int(pad_id), float(length_penalty)
+        ws = _aligned_ws(ws, self.ensemble_beam_ws_bytes(B, Lc, M, beam), dev)
+        outs = _decode_outputs(B, beam, Lc, dev)
+        self._ensemble_call("beam_search", B, Lc, M, parr, sarr, eopts, _diverse_opts(opts, groups, diversity), cons, B * int(beam), ws, ins,
+                            outs)
+        return outs
+
+    def ensemble_sample_captions(self, members, features, fmaps, Lc: int, num_samples: int, weights=None, mode: str = "prob", top_k: int = 0,
+                                 top_p: float = 1.0, temperature: float = 1.0, eos_id: int = 2, pad_id: int = 0, seed: int = 0,
+                                 noise_u: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, no_repeat_ngram: int = 0,
+                                 min_length: int = 0, suppress_tokens=()):
+        """gic_*_ensemble_sample_captions: ensemble_beam_search's members, sample_captions' draw on the mixed logits.  Returns (ids int64
+        [B, n, Lc], scores f32 [B, n], lengths int32 [B, n]) in row order."""
+        M, B, dev, parr, sarr, ins, keep = self._ensemble_members(members, features, fmaps)
+        eopts = ensemble_opts(M, weights, mode)
+        cons = decode_constraints(no_repeat_ngram, min_length, suppress_tokens)
+        n = int(num_samples)
+        noise_u = _sample_noise(noise_u, Lc, B * n, self.V)
+        opts = sample_opts(n, top_k, top_p, temperature, eos_id, pad_id)
+        ws = _aligned_ws(ws, self.ensemble_sample_ws_bytes(B, Lc, M, n), dev)
+        outs = _decode_outputs(B, n, Lc, dev)
+        self._ensemble_call("sample_captions", B, Lc, M, parr, sarr, eopts, opts, cons, B * n, ws, ins, outs,
+                            (ptr(noise_u), int(seed) & (2 ** 64 - 1)))
+        return outs
+
+
+def ensemble_opts(M: int, weights=None, mode: str = "prob") -> L.EnsembleOpts:
+    """gic_ensemble_opts: ``weights`` None = uniform, else M finite values > 0 (the library normalises them); ``mode`` "prob" (the
+    arithmetic mean of the members' probabilities) or "logprob" (the geometric mean)."""
+    if mode not in L.ENSEMBLE_MODES:
+        raise ValueError(f"ensemble mode must be one of {sorted(L.ENSEMBLE_MODES)}, got {mode!r}")
+    if not 1 <= int(M) <= L.MAX_ENSEMBLE:
+        raise ValueError(f"an ensemble has 1..{L.MAX_ENSEMBLE} members, got {M}")
+    w = [1.0] * int(M) if weights is None else [float(v) for v in weights]
+    if len(w) != int(M):
+        raise ValueError(f"ensemble weights: {len(w)} values for {M} members")
+    if not all(0.0 < v < float("inf") for v in w):
+        raise ValueError("ensemble weights must be finite and > 0")
+    o = L.EnsembleOpts()
+    o.M, o.mode = int(M), L.ENSEMBLE_MODES[mode]
+    for i, v in enumerate(w):
+        o.weights[i] = v
+    return o
+
+
+def ensemble_mix(logits: torch.Tensor, weights=None, mode: str = "prob") -> torch.Tensor:
+    """gic_ensemble_mix: the members' f32 logits [M, rows, V] -> the ensemble's logits z f32 [rows, V].  With lp_m = log_softmax(l_m),
+    "prob": z = log sum_m w_m exp(lp_m); "logprob": z = sum_m w_m lp_m; ``weights`` (None: uniform) are normalised to sum 1."""
+    require_gpu(logits)
+    if logits.dim() != 3 or logits.dtype != torch.float32:
+        raise ValueError("logits must be float32 [M, rows, V]")
+    M, rows, V = logits.shape
+    o = ensemble_opts(M, weights, mode)
+    logits = logits.contiguous()
+    out = torch.empty(rows, V, device=logits.device, dtype=torch.float32)
+    L.check(L.load().gic_ensemble_mix(ptr(logits), M, rows, V, o.weights, o.mode, ptr(out), stream_ptr()), "gic_ensemble_mix")
+    return out
+
+
 def gan_losses(loss_type: str, d_real, d_fake, g_out, want_grads: bool = True):
     """Returns (losses[2] device tensor: [g_loss, d_loss], grads dict or None)."""
     if loss_type not in L.LOSS_TYPES:

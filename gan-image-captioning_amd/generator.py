@@ -662,6 +662,12 @@ class Encoder(nn.Module):
                                     self.linear.weight, self.linear.bias, self.bn.weight, self.bn.bias,
                                     self.bn.running_mean, self.bn.running_var)
 
+    def head(self, feats):
+        """Linear -> BatchNorm1d on given pooled trunk features [B, F] (an Ensemble's members that share one trunk)."""
+        return _EncoderHeadFn.apply(_compute_dtype(self.args), self.training, self.bn.momentum, self.bn.eps, feats,
+                                    self.linear.weight, self.linear.bias, self.bn.weight, self.bn.bias,
+                                    self.bn.running_mean, self.bn.running_var)
+
     def forward_with_map(self, images, next_images=None):
         """(features [B,E] as forward(), feature map [B, P, C] = the trunk's last activation, detached) for the attention decoder.
         ``next_images``: as in forward() -- the look-ahead pass also keeps a copy of its feature map."""
@@ -916,3 +922,144 @@ class Generator(nn.Module):
                     torch.nn.init.uniform_(param, a=-0.05, b=0.05)
                 elif self.args.gen_init == "normal":
                     torch.nn.init.normal_(param, std=1 / math.sqrt(param.shape[0]))
+
+
+class Ensemble:
+    """Decode-time ensemble of ``Generator`` modules of one decoder kind, dims and compute dtype (gicap.h gic_*_ensemble_*).  At every
+    step each member, in its own recurrent state, gives its logits; with lp_m = log_softmax(l_m) the search runs on z = log sum_m w_m
+    exp(lp_m) (``mode`` "prob": the arithmetic mean of the probabilities) or z = sum_m w_m lp_m ("logprob": the geometric mean), exactly
+    as it runs on one model's logits; ``weights`` (None: uniform) are normalised to sum 1.  Members that share one trunk module object
+    (``encoder.resnet``) run the trunk once and their own heads on it.  Not a module: it owns no parameters and nothing trains
+    through it.  ``eval()`` / ``train()`` / ``training`` / ``encoder`` / ``decoder`` / ``args`` follow member 0, so the evaluations can
+    be handed an Ensemble where they take a Generator."""
+
+    def __init__(self, members, weights=None, mode="prob"):
+        self.members = list(members)
+        if not self.members:
+            raise ValueError("an ensemble needs at least one member")
+        g0 = self.members[0]
+        for m, g in enumerate(self.members):
+            if not isinstance(g, Generator) or type(g.decoder) is not type(g0.decoder):
+                raise ValueError(f"ensemble member {m}: the members must be Generator modules of one decoder kind")
+        self.opts = engine.ensemble_opts(len(self.members), weights, mode)       # (checks the count, the weights and the mode)
+        self.weights = None if weights is None else [float(w) for w in weights]
+        self.mode = mode
+
+    # ---- the Generator surface the evaluations read
+    encoder = property(lambda self: self.members[0].encoder)
+    decoder = property(lambda self: self.members[0].decoder)
+    args = property(lambda self: self.members[0].args)
+    training = property(lambda self: self.members[0].training)
+
+    def train(self, mode=True):
+        for g in self.members:
+            g.train(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    def _features(self, images):
+        """Every member's (features, fmap or None): Generator._features per member, except that a member whose trunk module is an
+        earlier member's takes that member's pooled trunk features (and feature map) and runs its own head on them."""
+        out, trunks = [], {}
+        for g in self.members:
+            key = (id(g.encoder.resnet), bool(g.encoder.training))
+            if not g.args.conditional_gan or key not in trunks:
+                f, fmap = g._features(images)
+                if g.args.conditional_gan:
+                    trunks[key] = (g.encoder.last_trunk, fmap)
+            else:
+                feats, fmap = trunks[key]
+                f = g.encoder.head(feats)
+            out.append((f, fmap))
+        return out
+
+    def _members(self):
+        return [(g.decoder.engine(), [p.detach() for p in g.decoder.param_list()]) for g in self.members]
+
+    def _inputs(self, images):
+        fm = self._features(images)
+        feats = [f.detach().float() for f, _ in fm]
+        maps = None if fm[0][1] is None else [m.detach() for _, m in fm]
+        return feats, maps
+
+    def _len(self, max_caption_len):
+        return int(self.decoder.max_seq_length if max_caption_len is None else max_caption_len)
+
+    def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False, return_alphas=False,
+                beam_groups=1, diversity=0.0, rerank_disc=None, rerank_weight=1.0, return_rerank=False, consensus=None, consensus_weight=1.0,
+                return_consensus=False, no_repeat_ngram=0, min_length=0, suppress_tokens=(), states=None):
+        """Generator.caption on the ensemble's logits: the same keywords, outputs and re-rankings (a conditioned ``rerank_disc`` reads
+        member 0's pooled trunk features).  ``return_alphas`` and ``states`` are refused: an ensemble has no one attention map and no
+        one initial state."""
+        if return_alphas:
+            raise ValueError("an ensemble returns no attention weights (return_alphas): every member attends on its own")
+        if states is not None:
+            raise ValueError("an ensemble search takes no initial states (states=)")
+        if rerank_disc is None and return_rerank:
+            raise ValueError("return_rerank needs rerank_disc")
+        g0 = self.members[0]
+        g0._check_consensus(consensus, rerank_disc, return_consensus)
+        with torch.no_grad():
+            feats, maps = self._inputs(images)
+            out = g0.decoder.engine().ensemble_beam_search(self._members(), feats, maps, self._len(max_caption_len), int(beam_size),
+                                                           self.weights, self.mode, int(beam_groups), float(diversity), int(eos_id), 0,
+                                                           float(length_penalty), no_repeat_ngram=no_repeat_ngram, min_length=min_length,
+                                                           suppress_tokens=suppress_tokens)
+            if rerank_disc is None and consensus is None:
+                return out if return_beams else tuple(t[:, 0] for t in out)
+            if consensus is not None:
+                r = g0._rerank_consensus(consensus, out, consensus_weight, length_penalty)
+            else:
+                r = g0._rerank(rerank_disc, out, rerank_weight, length_penalty)
+        res = (r["ids"], r["scores"], r["lengths"])
+        if not return_beams:
+            res = tuple(t[:, 0] for t in res)
+        return res + (((r["final"], r["d"]),) if return_rerank or return_consensus else ())
+
+    def sample_captions(self, images, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
+                        noise_u=None, rerank_disc=None, rerank_weight=1.0, consensus=None, consensus_weight=1.0, no_repeat_ngram=0,
+                        min_length=0, suppress_tokens=(), states=None):
+        """Generator.sample_captions on the ensemble's logits: the same keywords, outputs and re-rankings."""
+        if states is not None:
+            raise ValueError("an ensemble search takes no initial states (states=)")
+        g0 = self.members[0]
+        g0._check_consensus(consensus, rerank_disc)
+        seed = (0 if noise_u is not None else SEEDS.next()) if seed is None else int(seed)
+        with torch.no_grad():
+            feats, maps = self._inputs(images)
+            out = g0.decoder.engine().ensemble_sample_captions(self._members(), feats, maps, self._len(max_caption_len), int(num_samples),
+                                                               self.weights, self.mode, int(top_k), float(top_p), float(temperature),
+                                                               int(eos_id), 0, seed, noise_u, no_repeat_ngram=no_repeat_ngram,
+                                                               min_length=min_length, suppress_tokens=suppress_tokens)
+            if rerank_disc is None and consensus is None:
+                return out
+            r = g0._rerank_consensus(consensus, out, consensus_weight) if consensus is not None else g0._rerank(rerank_disc, out, rerank_weight)
+        return r["ids"], r["scores"], r["lengths"]
+
+    def score_captions(self, images, ids, lengths):
+        """Generator.score_captions under the ensemble: every member's teacher-forced no-grad logits, engine.ensemble_mix over
+        [M, B * L, V], then gic_xent_seq masked by ``lengths``: (logp, tokens) in the shape of ``lengths``, in the units of the
+        ensemble's beam and sample scores."""
+        lengths = torch.as_tensor(lengths).to(ids.device)
+        if ids.dim() not in (2, 3) or tuple(lengths.shape) != tuple(ids.shape[:-1]) or ids.shape[0] != len(images):
+            raise ValueError("score_captions: ids must be [B, L] with lengths [B], or [B, K, L] with lengths [B, K], B = len(images)")
+        if ids.dtype != torch.int64 or ids.shape[-1] < 2:
+            raise ValueError("score_captions: ids must be int64 with L >= 2")
+        K = ids.shape[1] if ids.dim() == 3 else 1
+        flat, L = ids.reshape(-1, ids.shape[-1]), ids.shape[-1]
+        n = flat.shape[0]
+        lens = lengths.reshape(-1).to(torch.int32)
+        with torch.no_grad():
+            preds = []
+            for g, (f, fmap) in zip(self.members, self._features(images)):
+                if K > 1:
+                    f = f.repeat_interleave(K, 0)
+                    fmap = None if fmap is None else fmap.repeat_interleave(K, 0)
+                maps = () if fmap is None else (fmap,)
+                pred = g.decoder._forward_no_grad(f, *maps, flat[:, :-1].contiguous(), lens.clamp(1, L), True, None, 0, L)[0]
+                preds.append(pred.reshape(n * L, pred.shape[-1]).float())
+            z = engine.ensemble_mix(torch.stack(preds), self.weights, self.mode)
+            out = engine.xent_seq(z, flat.reshape(-1), L, lengths=lens, want_grad=False)
+        return (-out["cap_nll"]).view(lengths.shape), out["cap_tokens"].view(lengths.shape)

@@ -25,11 +25,11 @@ from torch.utils.data import DataLoader
 from tqdm import tqdm
 
 from . import engine, parallel
-from .args import check_image_pipeline
+from .args import check_eval_ensemble, check_image_pipeline
 from .discriminator import Discriminator
 from .fused_step import FusedAdvStep
 from .seqgan import SeqGANStep
-from .generator import Generator
+from .generator import Ensemble, Generator
 from .optim import ArenaEMA, FusedClipAdam, LRSchedule, ParamArena
 from .tasks import make_collate, stack_images
 from .utils import create_logger, get_fixed_temperature, get_losses
@@ -203,6 +203,10 @@ class GANInstructor:
     ema = None              # ArenaEMA of gen_arena under --gen-ema-decay
     eval_ema = False        # --eval-ema
     _ema_held = False       # True: evaluate* stays on the weights that are live now (nested evaluations, checkpoint selection)
+    eval_ensemble = None    # --eval-ensemble*: what check_eval_ensemble returned
+    _ensemble = None        # the evaluations' Ensemble, built at the first evaluation that needs it
+    _ensemble_ema = None    # its EMA member, refreshed at the start of every evaluation
+    _live_only = False      # True: evaluate* stays on the live generator alone (checkpoint selection)
     scst_opt = None         # SCST's own optimizer over gen_arena, once scst_train has built it
     _train_state = None     # a loaded --resume-train-state, for the optimizers built later (SCST)
 
@@ -215,6 +219,7 @@ class GANInstructor:
         self.ignore_pad, self.label_smoothing = check_seq_loss(args)
         check_image_pipeline(args)
         oc = check_optimizer(args)
+        self.eval_ensemble = check_eval_ensemble(args)       # None: the evaluations run on the one generator
         self.dist = parallel.DistInfo.from_env()
         from .generator import SEEDS
         SEEDS.rank = self.dist.rank            # replicas share weights and the torch seed, not the device noise streams
@@ -545,6 +550,8 @@ class GANInstructor:
 
     @contextlib.contextmanager
     def _eval_weights(self):
+        if self.eval_ensemble is not None and not self._live_only and self._ensemble_ema is not None:
+            self._load_ema_member(self._ensemble_ema)             # the average has moved since the last evaluation
         if not self.eval_ema or self._ema_held:
             yield
             return
@@ -559,10 +566,55 @@ class GANInstructor:
     def _live_weights(self):
         """Evaluations inside the block stay on the live weights (checkpoint selection)."""
         held, self._ema_held = self._ema_held, True
+        live, self._live_only = self._live_only, True
         try:
             yield
         finally:
-            self._ema_held = held
+            self._ema_held, self._live_only = held, live
+
+    # ------------------------------------------------------------------ decode-time ensembles (generator.Ensemble)
+    def _member_copy(self, share_trunk: bool = False):
+        """A generator of the live one's configuration for an ensemble member, in the live one's mode.  ``share_trunk``: on the live
+        trunk module itself (the frozen trunk is not averaged), so that an Ensemble runs the trunk once for both."""
+        g = Generator(self.args).to(self.args.device)
+        if share_trunk:
+            g.encoder.resnet = self.gen.encoder.resnet
+        g.train(self.gen.training)
+        return g
+
+    def _load_ema_member(self, g) -> None:
+        with self.ema.swapped():
+            g.load_state_dict(self.gen.state_dict())
+        engine.bump_param_epoch()
+
+    def ensemble(self, paths=(), with_ema=False, weights=None, mode="prob"):
+        """An Ensemble (generator.py) of, in this order, the live generator, one copy per checkpoint of ``paths`` (load_checkpoint's
+        formats: a generator state dict, or {"generator", "discriminator"}) and, with ``with_ema``, a copy that holds the averaged
+        weights as they are now, on the live trunk.  ``weights`` (None: uniform) in the same order; ``mode`` "prob" / "logprob"."""
+        if with_ema and self.ema is None:
+            raise ValueError("ensemble(with_ema=True) needs --gen-ema-decay > 0")
+        members = [self.gen]
+        for path in paths:
+            ckpt = torch.load(path, map_location=self.args.device)
+            g = self._member_copy()
+            g.load_state_dict(ckpt["generator"] if isinstance(ckpt, dict) and set(ckpt) == {"generator", "discriminator"} else ckpt)
+            members.append(g)
+        if with_ema:
+            g = self._member_copy(share_trunk=True)
+            self._load_ema_member(g)
+            members.append(g)
+        engine.bump_param_epoch()
+        return Ensemble(members, weights, mode)
+
+    def _eval_gen(self):
+        """The generator the evaluations decode and score with: the live one, or under --eval-ensemble* (and outside checkpoint
+        selection) the ensemble around it."""
+        if self.eval_ensemble is None or self._live_only:
+            return self.gen
+        if self._ensemble is None:
+            self._ensemble = self.ensemble(**self.eval_ensemble)
+            self._ensemble_ema = self._ensemble.members[-1] if self.eval_ensemble["with_ema"] else None
+        return self._ensemble
 
     def _save(self, obj, name):
         """A model checkpoint, its ``<stem>.train_state`` and, with an EMA, ``<stem>_ema.ckpt``: the same format with the averaged
@@ -746,12 +798,18 @@ class GANInstructor:
         dev = self.args.device
         sums = torch.zeros(2, dtype=torch.float64, device=dev)           # nll, tokens
         n = 0
-        was_training = self.gen.training
-        self.gen.eval()                              # the encoder's BatchNorm on its running statistics, which stay as they are
+        gen = self._eval_gen()
+        was_training = gen.training
+        gen.eval()                                   # the encoder's BatchNorm on its running statistics, which stay as they are
         try:
             with torch.no_grad():
                 for batch in loader:
                     images, captions, lengths = batch[0].to(dev), batch[1].to(dev), batch[2]
+                    if gen is not self.gen:          # an ensemble scores through its own members' features
+                        logp, tokens = gen.score_captions(images, captions, lengths)
+                        sums += torch.stack([-logp.double().sum(), tokens.double().sum()])
+                        n += captions.shape[0]
+                        continue
                     feats = self._features(images, captions.shape[0])
                     if self.attention:
                         logp, tokens = self.gen.decoder.log_likelihood(feats[0], feats[1], captions, lengths)
@@ -760,7 +818,7 @@ class GANInstructor:
                     sums += torch.stack([-logp.double().sum(), tokens.double().sum()])
                     n += captions.shape[0]
         finally:
-            self.gen.train(was_training)
+            gen.train(was_training)
         nll, tokens = sums.tolist() if n else (0.0, 0.0)                  # the one sync
         per_token = nll / tokens if tokens else 0.0
         out = {"nll_per_token": per_token, "perplexity": math.exp(per_token) if per_token < 700.0 else float("inf"),
@@ -866,7 +924,8 @@ class GANInstructor:
     def _beam_decode(self, what, beam_size, max_caption_len=None, batch_size=None):
         """The decode of ``evaluate`` / ``evaluate_cider``: the best beam of each image (``_decode_batches``)."""
         def decode(images, L, _):
-            ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L, **self._eval_constraints(), **self._eval_rerank())
+            ids, _, lengths = self._eval_gen().caption(images, beam_size=beam_size, max_caption_len=L, **self._eval_constraints(),
+                                                        **self._eval_rerank())
             return ids, lengths
         return self._decode_batches(what, decode, max_caption_len, batch_size)
 
@@ -875,8 +934,9 @@ class GANInstructor:
         ``decode(images, L, batch_index)`` gives (ids, lengths) of the batch.  Yields per batch (ids and lengths on the device, the
         images' reference token lists)."""
         ds, groups, order, coco, coco_ids, _ = self._eval_groups(what)
-        was_training = self.gen.training
-        self.gen.eval()
+        gen = self._eval_gen()
+        was_training = gen.training
+        gen.eval()
         bs = int(batch_size or getattr(self.args, "adv_eval_batch_size", 32))
         try:
             for bi, s in enumerate(range(0, len(order), bs)):
@@ -889,7 +949,7 @@ class GANInstructor:
                 ids, lengths = decode(images, L, bi)
                 yield ids, lengths, caps
         finally:
-            self.gen.train(was_training)
+            gen.train(was_training)
 
     @_on_eval_weights
     def evaluate_cider(self, what="val", beam_size=3, max_caption_len=None, batch_size=None):
@@ -974,8 +1034,8 @@ class GANInstructor:
         ``distinct1`` / ``distinct2`` = unique / total uni- and bigrams over all samples, ``vocab`` = distinct words used.  Logs the
         values and writes the scalars ``<Name>_<what>`` (BLEU4S, mBLEU4, Distinct1, Distinct2, Vocab).  ``seed`` fixes the draws."""
         def decode(images, L, bi):
-            ids, _, lengths = self.gen.sample_captions(images, num_samples=num_samples, top_k=top_k, top_p=top_p, temperature=temperature,
-                                                       max_caption_len=L, seed=int(seed) + bi, **self._eval_constraints())
+            ids, _, lengths = self._eval_gen().sample_captions(images, num_samples=num_samples, top_k=top_k, top_p=top_p, temperature=temperature,
+                                                               max_caption_len=L, seed=int(seed) + bi, **self._eval_constraints())
             return ids, lengths
         out = self._diversity(what, decode, max_caption_len, batch_size)
         self.log.info("[EVAL] diversity (%s, n %d, top-k %d, top-p %.3f, temperature %.3f): BLEU-4 %.4f | mBLEU-4 %.4f | distinct-1 %.4f"
@@ -992,8 +1052,8 @@ class GANInstructor:
         ``bleu4`` of slot 0 (group 0's best beam), ``mbleu4`` / ``distinct1`` / ``distinct2`` / ``vocab`` over the beams.  Logs the
         values and writes the scalars ``<Name>_<what>`` (BLEU4DBS, mBLEU4DBS, Distinct1DBS, Distinct2DBS, VocabDBS)."""
         def decode(images, L, _):
-            ids, _, lengths = self.gen.caption(images, beam_size=beam_size, max_caption_len=L, length_penalty=length_penalty,
-                                               return_beams=True, beam_groups=groups, diversity=diversity, **self._eval_constraints())
+            ids, _, lengths = self._eval_gen().caption(images, beam_size=beam_size, max_caption_len=L, length_penalty=length_penalty,
+                                                       return_beams=True, beam_groups=groups, diversity=diversity, **self._eval_constraints())
             return ids, lengths
         out = self._diversity(what, decode, max_caption_len, batch_size)
         self.log.info("[EVAL] diverse beam (%s, beam %d, groups %d, diversity %.3f): BLEU-4 %.4f | mBLEU-4 %.4f | distinct-1 %.4f"
@@ -1023,9 +1083,9 @@ class GANInstructor:
         drawn = {}
 
         def decode(images, L, bi):
-            ids, drawn["scores"], lengths = self.gen.sample_captions(images, num_samples=num_samples, top_k=top_k, top_p=top_p,
-                                                                     temperature=temperature, max_caption_len=L, seed=int(seed) + bi,
-                                                                     **self._eval_constraints())
+            ids, drawn["scores"], lengths = self._eval_gen().sample_captions(images, num_samples=num_samples, top_k=top_k, top_p=top_p,
+                                                                             temperature=temperature, max_caption_len=L, seed=int(seed) + bi,
+                                                                             **self._eval_constraints())
             return ids, lengths
         sums = torch.zeros(3, dtype=torch.float64, device=dev)              # CIDEr-D of the first draw, of the pick, Self-CIDEr
         n_images = 0

@@ -537,6 +537,59 @@ int gic_attn_constrained_sample_captions(const gic_attn_dims* dims, const gic_at
                                          const float* features, const void* fmap, const float* noise_u, uint64_t seed, int64_t* ids,
                                          float* scores, int32_t* lengths, void* stream);
 
+/* Ensemble decoding: M members (1..GIC_MAX_ENSEMBLE) of one decoder kind, dims and compute dtype share one search.  weights w_m > 0
+ * are normalised to sum 1 by the library.  At a step, member m, in its own recurrent state, gives the f32 logits l_m[r, :] of row r;
+ * with lp_m = l_m - logsumexp(l_m) the ensemble's logits are
+ *   GIC_ENSEMBLE_PROB      z[r, v] = log sum_m w_m exp(lp_m[r, v])      (arithmetic mean of the probabilities)
+ *   GIC_ENSEMBLE_LOGPROB   z[r, v] = sum_m w_m lp_m[r, v]               (geometric mean, product of experts; not normalised)
+ * and the heads treat z exactly as they treat one model's logits: selection by z, a token's log-probability z - logsumexp(z) (the units
+ * of the scores), the sampler's temperature / top-k / top-p, the diverse groups, the decode constraints and the early stop.  Every
+ * member advances with the same chosen tokens and parent pointers.
+ * gic_ensemble_mix: the mixing step itself.  logits f32 [M][rows][V] (contiguous), weights: HOST f32 [M], out f32 [rows][V]; rows
+ * 1..2^24, V >= 2.  Every exp has its maximum subtracted first (finite for logits of magnitude 1e4); a member whose probability
+ * underflows adds 0 (prob) and its true log-probability (logprob).  No atomics and a fixed reduction order: the same bits on every
+ * call, in and out of the deterministic mode.
+ * The searches: dims are those of every member; params / shadows: arrays of M pointers to the members' structs; features: array of M
+ * device pointers, f32 [B, E] each (fmaps: M device pointers, act [B, P, C] each); opts->beam.h0 / c0 and the sampler's h0 / c0 must
+ * be NULL.  dopts with groups = 1, diversity = 0 is the plain beam search; c may be NULL (no constraints; cws then unread), else c / cws
+ * as for the gic_*_constrained_* decodes.  ids / scores / lengths as for the single-model searches.  Each member's logits are
+ * materialised (the fused vocabulary product's logits form, else the GEMM), mixed into one [rows, V] slab and handed to the heads'
+ * generic path.  The workspace: gic_*_ensemble_*_ws_bytes (host-only: no GPU needed), 256-byte aligned.  Every argument check runs
+ * before any launch and returns GIC_STATUS_INVALID_ARG: those of the single-model searches and M out of range, a bad mode, a weight
+ * that is not finite and > 0, a null member or member array. */
+#define GIC_MAX_ENSEMBLE 4
+#define GIC_ENSEMBLE_PROB 0
+#define GIC_ENSEMBLE_LOGPROB 1
+typedef struct gic_ensemble_opts {
+  int32_t M;                             /* members: 1..GIC_MAX_ENSEMBLE */
+  int32_t mode;                          /* GIC_ENSEMBLE_PROB / GIC_ENSEMBLE_LOGPROB */
+  float weights[GIC_MAX_ENSEMBLE];       /* the first M are read: finite, > 0; normalised by the library */
+} gic_ensemble_opts;
+int gic_ensemble_mix(const float* logits, int32_t M, int64_t rows, int32_t V, const float* weights, int32_t mode, float* out, void* stream);
+int gic_decoder_ensemble_beam_ws_bytes(const gic_decoder_dims* dims, int32_t M, int32_t beam, uint64_t* out);
+int gic_attn_ensemble_beam_ws_bytes(const gic_attn_dims* dims, int32_t M, int32_t beam, uint64_t* out);
+int gic_decoder_ensemble_sample_ws_bytes(const gic_decoder_dims* dims, int32_t M, int32_t num_samples, uint64_t* out);
+int gic_attn_ensemble_sample_ws_bytes(const gic_attn_dims* dims, int32_t M, int32_t num_samples, uint64_t* out);
+int gic_decoder_ensemble_beam_search(const gic_decoder_dims* dims, int32_t M, const gic_decoder_params* const* params,
+                                     const gic_decoder_shadow* const* shadows, const gic_ensemble_opts* eopts,
+                                     const gic_diverse_beam_opts* dopts, const gic_decode_constraints* c, void* ws, void* cws,
+                                     const float* const* features, int64_t* ids, float* scores, int32_t* lengths, void* stream);
+int gic_attn_ensemble_beam_search(const gic_attn_dims* dims, int32_t M, const gic_attn_params* const* params,
+                                  const gic_attn_shadow* const* shadows, const gic_ensemble_opts* eopts,
+                                  const gic_diverse_beam_opts* dopts, const gic_decode_constraints* c, void* ws, void* cws,
+                                  const float* const* features, const void* const* fmaps, int64_t* ids, float* scores,
+                                  int32_t* lengths, void* stream);
+int gic_decoder_ensemble_sample_captions(const gic_decoder_dims* dims, int32_t M, const gic_decoder_params* const* params,
+                                         const gic_decoder_shadow* const* shadows, const gic_ensemble_opts* eopts,
+                                         const gic_sample_opts* sopts, const gic_decode_constraints* c, void* ws, void* cws,
+                                         const float* const* features, const float* noise_u, uint64_t seed, int64_t* ids,
+                                         float* scores, int32_t* lengths, void* stream);
+int gic_attn_ensemble_sample_captions(const gic_attn_dims* dims, int32_t M, const gic_attn_params* const* params,
+                                      const gic_attn_shadow* const* shadows, const gic_ensemble_opts* eopts,
+                                      const gic_sample_opts* sopts, const gic_decode_constraints* c, void* ws, void* cws,
+                                      const float* const* features, const void* const* fmaps, const float* noise_u, uint64_t seed,
+                                      int64_t* ids, float* scores, int32_t* lengths, void* stream);
+
 /* Teacher-forced decode with the attention decoder: the semantics of gic_decoder_forward_tf with the step of gic_attn_sample_fwd.
  * dims->L = T = caption length + 1: step 0 is fed `features`, step t > 0 embed(caps[b, t-1]) (caps int64 [B, T-1]; may be NULL when
  * T = 1); the attention of step t uses h_{t-1} and the LSTM input is [x_t ; z_t].  lengths int32 [B] (each 1..T) with
