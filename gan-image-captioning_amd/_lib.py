@@ -193,6 +193,9 @@ _SIGNATURES = {
     "gic_debug_last_route": (C.c_char_p, []),
     "gic_debug_wgrad_fold": (C.c_int, [c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "gic_debug_wgrad_launches": (None, [_P(C.c_int64), _P(C.c_int64)]),
+    "gic_debug_gemm_desc": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
+                                      c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int, c_void_p]),
     "gic_gemm": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                            C.c_int, C.c_int, C.c_int, C.c_int, c_void_p, C.c_int, C.c_float, c_void_p]),
     "gic_cast2d": (C.c_int, [c_void_p, C.c_int, C.c_int64, c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, c_void_p]),

@@ -362,6 +362,19 @@ int gic_debug_wgrad_fold(const void* A, const void* B, int M, int N, int K, int6
   return gic::wgrad_folds_a_sum(d) ? gic::wgrad_tile_n(d) : 0;
 }
 
+int gic_debug_gemm_desc(const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int a_kc, int b_kc,
+                        int in_dtype, int out_dtype, const float* bias, int accumulate, float alpha, int c_zeroed, int no_split, int wgrad,
+                        float* a_sum, float* a_sum2, void* C2, int64_t ldc2, int n_split, void* stream) {
+  gic::GemmDesc d;
+  d.A = A; d.B = B; d.C = C; d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldb = ldb; d.ldc = ldc;
+  d.a_kc = a_kc; d.b_kc = b_kc; d.in_dtype = in_dtype; d.out_dtype = out_dtype;
+  d.bias = bias; d.accumulate = accumulate; d.alpha = alpha; d.c_zeroed = c_zeroed; d.no_split = no_split;
+  if (wgrad) {      // (union members, gemm.h: a descriptor that does not say `wgrad` leaves them alone)
+    d.wgrad = wgrad; d.a_sum = a_sum; d.a_sum2 = a_sum2; d.C2 = C2; d.ldc2 = ldc2; d.n_split = n_split;
+  }
+  return gic::gemm(d, (hipStream_t)stream);
+}
+
 void gic_debug_wgrad_launches(int64_t* launches, int64_t* two_matrix) {
   long a = 0, b = 0;
   gic::wgrad_launch_counts(&a, &b);

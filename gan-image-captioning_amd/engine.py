@@ -157,6 +157,18 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, bias=None, ac
     return Cout
 
 
+def gemm_desc(A, B, Cout, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, bias=None, accumulate=False, alpha=1.0, c_zeroed=False,
+              no_split=False, wgrad=False, a_sum=None, a_sum2=None, C2=None, ldc2=0, n_split=0):
+    """``gemm`` with the descriptor fields only the library's own call sites set (gicap.h gic_debug_gemm_desc): tests run them through it."""
+    require_gpu(A, B, Cout, a_sum, a_sum2, C2)
+    in_dt = L.F32 if A.dtype == torch.float32 else L.BF16
+    out_dt = L.F32 if Cout.dtype == torch.float32 else L.BF16
+    L.check(L.load().gic_debug_gemm_desc(ptr(A), ptr(B), ptr(Cout), M, N, K, lda, ldb, ldc, int(a_kc), int(b_kc), in_dt, out_dt, ptr(bias),
+                                         int(accumulate), float(alpha), int(c_zeroed), int(no_split), int(wgrad), ptr(a_sum), ptr(a_sum2),
+                                         ptr(C2), ldc2, n_split, stream_ptr()), "gic_debug_gemm_desc")
+    return Cout
+
+
 def cast2d(src: torch.Tensor, dst: torch.Tensor, rows: int, cols: int, lds: int, ldd: int):
     require_gpu(src, dst)
     sd = L.F32 if src.dtype == torch.float32 else L.BF16

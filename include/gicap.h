@@ -65,6 +65,19 @@ int gic_debug_wgrad_fold(const void* A, const void* B, int M, int N, int K, int6
 /* How many weight-gradient products this process has launched in that folding form since the library was loaded, and how many of them
  * wrote two output matrices (dW_ih | dW_hh as one product): what a test reads before and after a call to see which route it took. */
 void gic_debug_wgrad_launches(int64_t* launches, int64_t* two_matrix);
+/* gic_gemm (below) with the descriptor fields that only the library's own call sites set, so that a test can run them in isolation:
+ *   c_zeroed  the caller guarantees that C is all zero: a split-K launch skips its zero fill
+ *   no_split  K is never split: the same bits on every call, in or out of the deterministic mode
+ *   wgrad     != 0: the weight-gradient extras follow; 0: they are not looked at (and not set in the descriptor)
+ *   a_sum, a_sum2   [M] f32, a_sum[m] (+)= sum_k A(m,k), a_sum2 (optional) the same values; OPTIONAL: written only where the product runs
+ *                   in the folding form (the route line then ends in " a_sum=.. n_split=.."), left untouched otherwise
+ *   C2, ldc2, n_split   the columns n >= n_split go to C2[m * ldc2 + (n - n_split)] instead of C; GIC_STATUS_UNSUPPORTED where the
+ *                   selection cannot honour it (n_split off the tile boundary, at 0 or at N; f32, k-contiguous or unaligned operands;
+ *                   c_zeroed; the deterministic mode)
+ * Goes through the same dispatch as gic_gemm, route-only mode included; no selection logic of its own. */
+int gic_debug_gemm_desc(const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int a_kc, int b_kc,
+                        int in_dtype, int out_dtype, const float* bias, int accumulate, float alpha, int c_zeroed, int no_split, int wgrad,
+                        float* a_sum, float* a_sum2, void* C2, int64_t ldc2, int n_split, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-step scalars resident in DEVICE memory (ABI v3).  The values that change from one train step to the next -- the decoder's

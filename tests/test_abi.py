@@ -33,6 +33,9 @@ def test_argument_validation_returns_status_not_crash():
     lib = _lib.load()
     assert lib.gic_gemm(None, None, None, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, None, 0, 1.0, None) == -1
     assert b"null operand" in lib.gic_last_error()
+    # gic_gemm with the caller-only descriptor fields: the same dispatch, the same validation
+    assert lib.gic_debug_gemm_desc(None, None, None, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, None, 0, 1.0, 0, 0, 0, None, None, None, 0, 0, None) == -1
+    assert b"null operand" in lib.gic_last_error()
     with pytest.raises(ValueError):
         _lib.check(lib.gic_gan_losses(99, None, None, None, 0, None, None, None, None, None, None, None), "gan_losses")
     d = _lib.DecoderDims(4, 5, 50, 8, 16, 9, 0)          # NL out of range
