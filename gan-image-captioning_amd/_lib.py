@@ -78,6 +78,11 @@ class DecodeConstraints(C.Structure):
                 ("suppress", C.c_int32 * MAX_SUPPRESS)]
 
 
+class ForcedWords(C.Structure):
+    """gic_forced_words (gic_decoder_forced_beam_search, gic_attn_forced_beam_search)."""
+    _fields_ = [("C", C.c_int32), ("D", C.c_int32), ("ids", c_void_p)]
+
+
 MAX_ENSEMBLE = 4              # GIC_MAX_ENSEMBLE
 ENSEMBLE_MODES = {"prob": 0, "logprob": 1}       # GIC_ENSEMBLE_PROB / GIC_ENSEMBLE_LOGPROB
 
@@ -252,6 +257,14 @@ _SIGNATURES = {
     "gic_attn_constrained_sample_captions": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(SampleOpts), _P(DecodeConstraints),
                                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint64, c_void_p, c_void_p,
                                                        c_void_p, c_void_p]),
+    "gic_decoder_forced_beam_ws_bytes": (C.c_int, [_P(DecoderDims), C.c_int32, c_void_p]),
+    "gic_attn_forced_beam_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int32, c_void_p]),
+    "gic_decoder_forced_beam_search": (C.c_int, [_P(DecoderDims), _P(DecoderParams), _P(DecoderShadow), _P(DiverseBeamOpts), _P(ForcedWords),
+                                                 _P(DecodeConstraints), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p]),
+    "gic_attn_forced_beam_search": (C.c_int, [_P(AttnDims), _P(AttnParams), _P(AttnShadow), _P(DiverseBeamOpts), _P(ForcedWords),
+                                              _P(DecodeConstraints), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p]),
     "gic_ensemble_mix": (C.c_int, [c_void_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, C.c_int32, c_void_p, c_void_p]),
     "gic_decoder_ensemble_beam_ws_bytes": (C.c_int, [_P(DecoderDims), C.c_int32, C.c_int32, c_void_p]),
     "gic_attn_ensemble_beam_ws_bytes": (C.c_int, [_P(AttnDims), C.c_int32, C.c_int32, c_void_p]),

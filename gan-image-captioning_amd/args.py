@@ -193,6 +193,12 @@ _NATIVE = [
                                     "> 0; not with --eval-ema 1)", {"choices": [0, 1]}),
     ("--eval-ensemble-weights", "floatlist", "", "comma-separated weights of the ensemble's members in the order live, checkpoints, EMA "
                                                  "(each > 0; normalised to sum 1); empty = uniform"),
+    ("--eval-force-words", int, 0, "forced-words evaluation (GANInstructor.evaluate_forced, the oracle-tags protocol: per validation image "
+                                   "the N reference tokens with the lowest document frequency among those in at least half of its "
+                                   "references are forced into the caption by lexically constrained beam search; BLEU-4, CIDEr-D and the "
+                                   "share of captions that hold their words, beside plain beam search's share) after each adversarial "
+                                   "epoch's validation; N in 0..3, 0 = off", {"choices": [0, 1, 2, 3]}),
+    ("--eval-force-beam-size", int, 8, "beam size of that evaluation (at most 8; 2^N must divide it)"),
     ("--eval-ensemble-mode", str, "prob", "how the members' next-token distributions are mixed: prob = the weighted arithmetic mean of the "
                                           "probabilities, logprob = the weighted geometric mean", {"choices": ["prob", "logprob"]}),
 ]
@@ -244,6 +250,25 @@ def check_eval_ensemble(args):
         if not all(0.0 < w < float("inf") for w in weights):
             raise ValueError("--eval-ensemble-weights must be finite and > 0")
     return {"paths": paths, "with_ema": with_ema, "weights": weights or None, "mode": mode}
+
+
+def check_eval_forced(args):
+    """The forced-words evaluation as the flags ask for it: None when --eval-force-words is 0, else (N, beam size).  Refused: N outside
+    0..3, a beam size outside 1..8 or one that 2^N does not divide, and the combinations a forced search does not take -- an ensemble
+    (--eval-ensemble*) and discriminator re-ranking (--eval-rerank-weight)."""
+    n = int(getattr(args, "eval_force_words", 0) or 0)
+    if n == 0:
+        return None
+    k = int(getattr(args, "eval_force_beam_size", 8) or 0)
+    if not 1 <= n <= 3:
+        raise ValueError(f"--eval-force-words must be 0..3, got {n}")
+    if not 1 <= k <= 8 or k % (1 << n):
+        raise ValueError(f"--eval-force-beam-size must be 1..8 and a multiple of 2^N = {1 << n} (--eval-force-words {n}), got {k}")
+    if _pathlist(getattr(args, "eval_ensemble", "") or "") or int(getattr(args, "eval_ensemble_ema", 0) or 0):
+        raise ValueError("--eval-force-words with --eval-ensemble*: the forced search runs one model")
+    if float(getattr(args, "eval_rerank_weight", 0.0) or 0.0) != 0.0:
+        raise ValueError("--eval-force-words with --eval-rerank-weight: a forced search keeps its own order (constraints met first)")
+    return n, k
 
 
 def _intlist(text):

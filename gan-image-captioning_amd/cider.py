@@ -46,6 +46,14 @@ def unpack_key(key: int) -> Tuple[int, ...]:
     return tuple((key >> (15 * (3 - j))) & 0x7FFF for j in range(n))
 
 
+def unigram_df(keys: np.ndarray, df: np.ndarray) -> dict:
+    """{token id: document frequency} of the 1-gram keys among ``keys`` uint64 / ``df`` (``document_frequency``'s outputs)."""
+    keys = np.asarray(keys, dtype=np.uint64)
+    one = (keys >> np.uint64(60)) == 0
+    tok = (keys[one] >> np.uint64(45)) & np.uint64(0x7FFF)
+    return dict(zip(tok.tolist(), np.asarray(df)[one].tolist()))
+
+
 def _pad(captions: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
     """Stripped captions as a zero-padded int64 matrix [rows, Lmax] and their lengths."""
     rows = [strip(c) for c in captions]
@@ -149,6 +157,7 @@ class CiderD:
         self.keys = torch.from_numpy(keys.view(np.int64).copy()).to(device)     # all keys < 2^62: int64 order = uint64 order
         self.idf = torch.from_numpy(idf.astype(np.float32)).to(device)
         self.df = df
+        self.keys_host = keys                                 # the table's keys on the host (unigram_df: no device read)
 
     def score(self, cand_ids: torch.Tensor, cand_lengths: torch.Tensor, refs: RefBatch, cand_img: torch.Tensor = None) -> torch.Tensor:
         """CIDEr-D of candidates int64 [B, n, L] (n per image, image-major) or [rows, L] with ``cand_img`` int [rows] (None with

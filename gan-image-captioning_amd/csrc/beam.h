@@ -168,10 +168,43 @@ __device__ __forceinline__ void ban_apply8(float (&x)[8], int (&ix)[8], int v0, 
   }
 }
 
+// ---- forced words (gicap.h gic_forced_words; forced_beam.hip): a row's hop tokens, the ids of its image's constraint sets that its
+// state has not met.  A row's state is its beam's state group, so its hop list never changes during a search: forced_init writes it once
+constexpr int kForceSetsMax = 3, kForceIdsMax = 4, kHopMax = kForceSetsMax * kForceIdsMax;
+// id i32 [rows][kHopMax] (slot c * D + d; -1: not a hop token of the row), val f32 [rows][kHopMax]: the raw logit of each hop token, written
+// by the step's vocabulary side; n = C * D, the slots in use (the walk reads no further).  null id = no forced words
+struct HopLists { const int* id = nullptr; float* val = nullptr; int n = 0; };
+
+// ban_apply8 for the hop list, after it: a hop token leaves the copy like a banned one, and its raw logit -- the element the walk has in
+// hand -- goes to the row's slot (store: this lane's row is a real one).  One lane of the grid holds a given (row, id): a single writer.
+// The row's kHopMax ids (48 bytes, 16-byte aligned: the region is 256-byte aligned) come in three loads issued together, before the
+// compares: a loop that loads id by id pays one L2 latency per slot (measured: 1.2 us per slot and step at cfg2)
+__device__ __forceinline__ void hop_apply8(float (&x)[8], int (&ix)[8], int v0, const int* __restrict__ ids, float* __restrict__ vals, int n,
+                                           bool store) {
+  static_assert(kHopMax == 12, "three 16-byte loads");
+  const int4 q0 = ((const int4*)ids)[0], q1 = ((const int4*)ids)[1], q2 = ((const int4*)ids)[2];
+  const int id[kHopMax] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+#pragma unroll
+  for (int i = 0; i < kHopMax; ++i) {
+    if (i < n) {                                             // (uniform: n = C * D)
+      const int d = id[i] - v0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (d == e) {
+          if (store) vals[i] = x[e];
+          x[e] = -INFINITY; ix[e] = INT_MAX;
+        }
+    }
+  }
+}
+
 // the fused vocabulary product of vocab_step with the beam epilogue (decoder_step.hip): a.B = rows, a.part_m / part_s [rows][nblk],
 // a.part_v / part_i [rows][nblk][K]; a.stop / stop_at; the sampling fields (u, seed, temperature, out, rowkey) are unused.  bans (decode
 // constraints): the epilogue that takes each row's top-K among the ids outside its ban list
 int vocab_step_beam(const VocabStepArgs& a, int K, int dtype, hipStream_t stream, const BanLists& bans = BanLists());
+// the forced search's instantiation (K even): the ban epilogue, which also keeps each row's hop tokens out of the tile top-K and records
+// their raw logits; bans and hops both set
+int vocab_step_beam_hop(const VocabStepArgs& a, int K, int dtype, hipStream_t stream, const BanLists& bans, const HopLists& hops);
 
 // ---- the kernels of a caption decode (decode.hip drives them: one step loop for both decoders and both heads)
 struct BeamLayerPtrs { void* xh[GIC_MAX_LAYERS]; float* c[GIC_MAX_LAYERS]; };
@@ -228,6 +261,24 @@ int ban_init(const BanOut& out, const BanRule& rule, int rows, hipStream_t strea
 // (image * K + beam) of step t whose logits gave the t-th token of each returned beam (-1 past the last step that ran)
 int beam_finalize(const BeamState& s, int B, int K, int L, int pad, float length_penalty, int width, int64_t* ids, float* scores,
                   int32_t* lengths, int32_t* anc, hipStream_t stream);
+
+// ---- forced_beam.hip: lexically constrained beam search (gicap.h gic_forced_words).  The K beams of an image are S = 2^C state groups
+// of Kg = K / S beams, beam j in state j / Kg (the bitmask of met constraint sets)
+// force i32 [B][C][D] (the caller's, -1 padded); hop_id / hop_tgt i32, hop_val f32 [rows][kHopMax]: each row's hop tokens, the state each
+// leads to, and its raw logit of the current step; init i32 [B]: the image's initial state (the bits of its absent sets).  The ids live on
+// the device, so the host cannot refuse one outside [0, V): forced_init drops it (no row ever proposes it)
+struct ForcedArgs { const int* force; int C, D, V; int* hop_id; int* hop_tgt; float* hop_val; int* init; };
+// after beam_init: the rows' hop lists, init, and the scores of t = 0 (the first beam of the initial state's group at 0, the others -inf)
+int forced_init(const ForcedArgs& f, const BeamState& s, int B, int K, hipStream_t stream);
+// beam_tile_topk's forced form: bans and hops both set
+int forced_tile_topk(const float* logits, int rows, int V, int K, float* part_m, float* part_s, float* part_v, int* part_i, const int* stop,
+                     int stop_at, hipStream_t stream, const BanLists& bans, const HopLists& hops);
+// the selection per state group (a.groups / a.diversity unused); its tail builds the ban lists of step t + 1 as beam_select's BAN form does
+int forced_select(const BeamSelectArgs& a, const ForcedArgs& f, int K, int B, hipStream_t stream, const BanOut& bans, const BanRule& rule);
+// beam_finalize in the forced order: real constraints met (descending), score / length^alpha (descending), beam index; dead beams last,
+// as all-pad ids of length 0 and score -inf.  met i32 [B, K]: the returned beams' states (a dead beam's: the initial state)
+int forced_finalize(const BeamState& s, const ForcedArgs& f, int B, int K, int L, int pad, float length_penalty, int64_t* ids, float* scores,
+                    int32_t* lengths, int32_t* met, int32_t* anc, hipStream_t stream);
 
 // attn_beam.hip: the attention kernels of one step (K rows per image, row r reads hp of row par[r]; the sampler's par[r] = r).  With
 // lengths set, the packed form of teacher forcing (K = 1): row b = caption b reads its own hp row and takes part while t < lengths[b]

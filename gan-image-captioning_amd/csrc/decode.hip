@@ -45,6 +45,14 @@
 // listed first), then slabs f32 [M][rows][V], then xh / c / gpre / fproj / hp / e of members 1..M-1.
 // The single-model entry points launch what they launched before.
 //
+// Forced words (gic_forced_words; gic_*_forced_beam_search): lexically constrained beam search is one more head, ForcedHead, around the
+// same recurrences (forced_beam.hip).  Its vocabulary side is vocab_step_beam_hop / forced_tile_topk, the ban forms that also keep each
+// row's hop tokens out of the tile top-K and record their raw logits; its selection is forced_select, a beam per state; its final order
+// forced_finalize's.  It always runs with ban lists (empty without decode constraints).  Workspace: the beam search's regions, then
+// hop_id / hop_tgt i32 and hop_val f32 [rows][12], init i32 [B] and the ban-list regions of a search without decode constraints.
+// Order of checks: beam_entry's, then groups == 1, C, D, null ids, 2^C | K, the constraints, the feasibility bound grown by the C * D
+// hop tokens, the workspaces' alignment.  No existing head, kernel or entry point changes.
+//
 // Entry path: every extern "C" decode is a model (LstmModel / AttnModel: the decoder's dims, weights and, with attention, the feature
 // map; its shape check, its argument check, run()), the two prefixes of its error texts and one call of beam_entry or sample_entry;
 // the four *_ws_bytes are ws_bytes_entry.  Order of checks -- beam: null options, shapes, arguments and weights, options; sampler: null
@@ -343,6 +351,7 @@ struct BeamHead {
   const Constraints* cons = nullptr;       // decode constraints (null: none)
   int live_stride(const DecodeDims& d) const { return d.K / groups; }
   int eos() const { return o->eos_id; }
+  int begin(const Search&) const { return GIC_OK; }
   int vocab(VocabStepArgs& v, const Search& s) const {
     v.part_m = s.w.pm; v.part_s = s.w.ps; v.part_v = s.w.pv; v.part_i = s.w.pi; v.nblk = s.d.nblk;
     return vocab_step_beam(v, s.d.K, s.d.dt, s.stream, cons ? cons->lists() : BanLists());
@@ -374,6 +383,7 @@ struct SampleHead {
   const Constraints* cons = nullptr;       // decode constraints (null: none)
   int live_stride(const DecodeDims&) const { return 1; }        // every row live from step 0
   int eos() const { return o->eos_id; }
+  int begin(const Search&) const { return GIC_OK; }
   int vocab(VocabStepArgs& v, const Search& s) const {
     v.logits = s.w.logits; v.ld_logits = s.d.V;
     return vocab_step_logits(v, s.d.dt, s.stream);
@@ -384,6 +394,41 @@ struct SampleHead {
     return sample_step(s.w.logits, s.d.rows, s.d.V, o, noise_u, seed, t, s.w.st, s.stream, cons->lists(), cons->out(), cons->rule(o->eos_id));
   }
   int finish(const Search& s) const { return sample_finalize(s.w.st, s.d.rows, s.d.L, o->pad_id, ids, scores, lengths, s.stream); }
+};
+
+// the forced search's head (forced_beam.hip; gicap.h gic_forced_words): the beam head's places with the hop lists beside the ban lists
+// (cons is always set: with no decode constraints the lists are empty), the selection per state group and the forced final order
+struct ForcedHead {
+  static constexpr bool kBeam = true;
+  const gic_decoder_beam_opts* o;
+  int64_t* ids; float* scores; int32_t* lengths; int32_t* met;
+  float* alphas;                 // attention: f32 [B, K, L, P] or null
+  ForcedArgs f;
+  const Constraints* cons = nullptr;
+  HopLists hops() const { HopLists h; h.id = f.hop_id; h.val = f.hop_val; h.n = f.C * f.D; return h; }
+  int live_stride(const DecodeDims& d) const { return d.K; }
+  int eos() const { return o->eos_id; }
+  int begin(const Search& s) const { return forced_init(f, s.w.st, s.d.B, s.d.K, s.stream); }       // (after beam_init: rewrites the scores)
+  int vocab(VocabStepArgs& v, const Search& s) const {
+    v.part_m = s.w.pm; v.part_s = s.w.ps; v.part_v = s.w.pv; v.part_i = s.w.pi; v.nblk = s.d.nblk;
+    return vocab_step_beam_hop(v, s.d.K, s.d.dt, s.stream, cons->lists(), hops());
+  }
+  int logits(const Search& s) const {
+    return forced_tile_topk(s.w.logits, s.d.rows, s.d.V, s.d.K, s.w.pm, s.w.ps, s.w.pv, s.w.pi, s.w.st.count, s.stop_at, s.stream,
+                            cons->lists(), hops());
+  }
+  int select(const Search& s, int t) const {
+    const BeamState& st = s.w.st;
+    const BeamSelectArgs a{s.w.pm, s.w.ps, s.w.pv, s.w.pi, st.score, st.fin, st.len, st.tok, st.par, st.htok, st.hpar, st.last, st.done,
+                           st.count, s.d.nblk, s.d.rows, t, o->eos_id, o->pad_id, 1, 0.f};
+    return forced_select(a, f, s.d.K, s.d.B, s.stream, cons->out(), cons->rule(o->eos_id));
+  }
+  int finish(const Search& s) const {
+    const DecodeDims& d = s.d;
+    GIC_PROPAGATE(forced_finalize(s.w.st, f, d.B, d.K, d.L, o->pad_id, o->length_penalty, ids, scores, lengths, met,
+                                  alphas ? s.w.anc : nullptr, s.stream));
+    return alphas ? attn_beam_alphas(s.w.ahist, s.w.anc, lengths, d.rows, d.L, d.P, alphas, s.stream) : GIC_OK;
+  }
 };
 
 // the step's vocabulary product of one recurrence: the fused product's arguments (the head finishes them), or the GEMM into w.logits
@@ -423,6 +468,7 @@ int decode(const DecodeDims& d, const Rec& rec, const Head& head, void* ws, cons
   const Search s{d, w, Head::kBeam ? d.B : d.rows, (hipStream_t)stream};
   GIC_PROPAGATE(beam_init(w.slot[0], d.NL, d.din(0), d.E, d.H, d.B, d.K, d.dt, features, h0, c0, w.st, s.stream, head.live_stride(d)));
   if (head.cons) GIC_PROPAGATE(ban_init(head.cons->out(), head.cons->rule(head.eos()), d.rows, s.stream));
+  GIC_PROPAGATE(head.begin(s));
   GIC_PROPAGATE(rec.begin(s));
   for (int t = 0; t < d.L; ++t) {
     GIC_PROPAGATE(rec.step(s, t));
@@ -575,6 +621,66 @@ int beam_entry(const Model& m, Who who, const gic_decoder_beam_opts* o, const gi
   GIC_PROPAGATE(dv ? check_diverse_opts(dv, d.V, who.call) : check_beam_opts(o, d.V, who.call));
   const BeamHead head{o, io.ids, io.scores, io.lengths, alphas, dv ? dv->groups : 1, dv ? dv->diversity : 0.f};
   return entry_tail(m, d, head, who.call, k, io);
+}
+
+// the forced search's workspace: the beam search's regions, then hop_id / hop_tgt i32 and hop_val f32 [rows][kHopMax], init i32 [B], and
+// the ban-list regions of a search without decode constraints (constraints_layout at S = 0; a call with constraints uses its cws)
+struct ForcedBufs { ForcedArgs f; void* cws0; size_t total; };
+
+ForcedBufs forced_layout(const DecodeDims& d, void* ws) {
+  static const gic_decode_constraints none{};
+  ForcedBufs o{};
+  Carver cv{ws};
+  cv.at = decode_layout(d, true, nullptr).total;
+  const size_t hb = (size_t)d.rows * kHopMax * 4;
+  o.f.hop_id = (int*)cv.take(hb); o.f.hop_tgt = (int*)cv.take(hb); o.f.hop_val = (float*)cv.take(hb);
+  o.f.init = (int*)cv.take((size_t)d.B * 4);
+  o.cws0 = cv.take(constraints_layout(&none, (size_t)d.rows, d.L, nullptr).total);
+  o.total = cv.at;
+  return o;
+}
+
+template <typename Model>
+int forced_ws_bytes_entry(const Model& m, int K, const char* who, uint64_t* out) {
+  DecodeDims d;
+  GIC_PROPAGATE(m.shape(K, true, who, d));
+  GIC_CHECK_ARG(out, "%s_ws_bytes: null out", who);
+  *out = (uint64_t)forced_layout(d, nullptr).total;
+  return GIC_OK;
+}
+
+// beam_entry's order -- null options, shapes, arguments and weights, options -- then the forced words (groups, C, D, the beam size's
+// divisibility), the constraints with the feasibility bound grown by the C * D hop tokens, the workspaces' alignment
+template <typename Model>
+int forced_entry(const Model& m, Who who, const gic_diverse_beam_opts* dv, const gic_forced_words* fw, const ConsArgs& k, const Io& io,
+                 float* alphas, int32_t* met) {
+  static const gic_decode_constraints none{};
+  GIC_CHECK_ARG(dv, "%s: null options", who.call);
+  const gic_decoder_beam_opts* o = &dv->beam;
+  DecodeDims d;
+  GIC_PROPAGATE(m.shape(o->beam, true, who.dims, d));
+  GIC_PROPAGATE(m.check(d, io.set() && met && fw, who.call));
+  GIC_PROPAGATE(check_diverse_opts(dv, d.V, who.call));
+  GIC_CHECK_ARG(dv->groups == 1, "%s: forced words do not combine with diverse groups (groups must be 1, got %d)", who.call, dv->groups);
+  GIC_CHECK_ARG(fw->C >= 1 && fw->C <= kForceSetsMax, "%s: forced words: C must be 1..%d, got %d (with no constraint set use the plain search)",
+                who.call, kForceSetsMax, fw->C);
+  GIC_CHECK_ARG(fw->D >= 1 && fw->D <= kForceIdsMax, "%s: forced words: D must be 1..%d, got %d", who.call, kForceIdsMax, fw->D);
+  GIC_CHECK_ARG(fw->ids, "%s: forced words: null ids", who.call);
+  GIC_CHECK_ARG(d.K % (1 << fw->C) == 0, "%s: forced words: 2^C = %d must divide the beam size %d", who.call, 1 << fw->C, d.K);
+  const gic_decode_constraints* c = k.c ? k.c : &none;
+  GIC_PROPAGATE(check_constraints(c, d.L, d.V, d.K, o->eos_id, who.call));
+  const int n = c->no_repeat_ngram, hop = fw->C * fw->D;
+  const long banned = c->num_suppress + 1 + (n >= 1 ? d.L - n : 0) + hop;
+  GIC_CHECK_ARG((long)d.V - banned >= d.K, "%s: infeasible constraints: up to %ld of %d tokens banned or forced (no_repeat_ngram %d, num_suppress %d, "
+                "L %d, %d hop tokens) leave fewer than the %d a row proposes", who.call, banned, d.V, n, c->num_suppress, d.L, hop, d.K);
+  GIC_CHECK_ARG(((uintptr_t)io.ws & 255) == 0, "%s: the workspace must be 256-byte aligned", who.call);
+  const bool own = constraints_off(c);
+  GIC_CHECK_ARG(own || (k.cws && ((uintptr_t)k.cws & 255) == 0), "%s: the constraint workspace must be non-null and 256-byte aligned", who.call);
+  ForcedBufs fb = forced_layout(d, io.ws);
+  fb.f.force = fw->ids; fb.f.C = fw->C; fb.f.D = fw->D; fb.f.V = d.V;
+  const Constraints cons = constraints_layout(c, (size_t)d.rows, d.L, own ? fb.cws0 : k.cws);
+  ForcedHead head{o, io.ids, io.scores, io.lengths, met, alphas, fb.f, &cons};
+  return m.run(d, head, io.ws, io.features, io.stream);
 }
 
 template <typename Model>
@@ -767,6 +873,29 @@ int gic_attn_constrained_beam_search(const gic_attn_dims* dims, const gic_attn_p
   const ConsArgs k{c, cws};
   return beam_entry(AttnModel{dims, P, S, fmap, alphas != nullptr}, {"attn_constrained_beam_search", "attn_constrained_beam"}, nullptr, o, &k,
                     {ws, features, ids, scores, lengths, stream}, alphas);
+}
+
+int gic_decoder_forced_beam_ws_bytes(const gic_decoder_dims* dims, int32_t beam, uint64_t* out) {
+  return forced_ws_bytes_entry(LstmModel{dims}, beam, "decoder_forced_beam", out);
+}
+
+int gic_attn_forced_beam_ws_bytes(const gic_attn_dims* dims, int32_t beam, uint64_t* out) {
+  return forced_ws_bytes_entry(AttnModel{dims}, beam, "attn_forced_beam", out);
+}
+
+int gic_decoder_forced_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S,
+                                   const gic_diverse_beam_opts* o, const gic_forced_words* fw, const gic_decode_constraints* c, void* ws,
+                                   void* cws, const float* features, int64_t* ids, float* scores, int32_t* lengths, int32_t* met,
+                                   void* stream) {
+  return forced_entry(LstmModel{dims, P, S}, {"decoder_forced_beam_search", "decoder_forced_beam"}, o, fw, {c, cws},
+                      {ws, features, ids, scores, lengths, stream}, nullptr, met);
+}
+
+int gic_attn_forced_beam_search(const gic_attn_dims* dims, const gic_attn_params* P, const gic_attn_shadow* S, const gic_diverse_beam_opts* o,
+                                const gic_forced_words* fw, const gic_decode_constraints* c, void* ws, void* cws, const float* features,
+                                const void* fmap, int64_t* ids, float* scores, int32_t* lengths, float* alphas, int32_t* met, void* stream) {
+  return forced_entry(AttnModel{dims, P, S, fmap, alphas != nullptr}, {"attn_forced_beam_search", "attn_forced_beam"}, o, fw, {c, cws},
+                      {ws, features, ids, scores, lengths, stream}, alphas, met);
 }
 
 int gic_decoder_sample_captions(const gic_decoder_dims* dims, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_sample_opts* o,

@@ -370,9 +370,10 @@ __global__ __launch_bounds__(512) void lstm_step_beam_kernel(const LstmStepArgs 
 // BEAMK < 0: the logits epilogue (vocab_step_logits) -- y = o + b_out stored in f32, one 16-byte store per lane and batch sub-tile
 // BAN (with BEAMK > 0): the tile's top-BEAMK pairs are taken from the copy without the ids of the row's ban list (bans, a kernel
 // argument of its own: VocabStepArgs and with it the other instantiations' argument layout stay as they were)
-template <typename TA, bool FAST, int BEAMK = 0, bool BAN = false>
+// HOP (with BAN): the forced search's form -- the row's hop tokens (hops) leave the copy too, and the walk stores their raw logits
+template <typename TA, bool FAST, int BEAMK = 0, bool BAN = false, bool HOP = false>
 __device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const int KC, const int bx, const int by, unsigned char* vs_smem,
-                                                const BanLists& bans = BanLists()) {
+                                                const BanLists& bans = BanLists(), const HopLists& hops = HopLists()) {
   constexpr int SZ = sizeof(TA), VE = 16 / SZ;
   const int H = a.H, V = a.V;
   const int hs = KC * SZ + 16;                             // LDS row stride of both tiles: 16-B skew against bank conflicts
@@ -550,6 +551,7 @@ __device__ __forceinline__ void vocab_step_body(const VocabStepArgs& a, const in
       for (int e = 0; e < 8; ++e) { xs[e] = x[e]; ixs[e] = ix[e]; }
       const int br = min(b0 + row, a.B - 1);
       ban_apply8(xs, ixs, v0 + seg * 8, bans.ban + (long)br * bans.cap, bans.nban[br]);
+      if constexpr (HOP) hop_apply8(xs, ixs, v0 + seg * 8, hops.id + (long)br * kHopMax, hops.val + (long)br * kHopMax, hops.n, b0 + row < a.B);
       beam_tile_reduce8_sel<BEAMK>(x, xs, ixs, seg == 0 && b0 + row < a.B, (long)(b0 + row) * a.nblk + bx, a.part_m, a.part_s, a.part_v, a.part_i);
     } else {
       beam_tile_reduce8<BEAMK>(x, ix, seg == 0 && b0 + row < a.B, (long)(b0 + row) * a.nblk + bx, a.part_m, a.part_s, a.part_v, a.part_i);
@@ -667,6 +669,12 @@ template <typename TA, int K>
 __global__ __launch_bounds__(512) void vocab_step_beam_ban_kernel(const VocabStepArgs a, const int KC, const BanLists bans) {
   extern __shared__ __attribute__((aligned(16))) unsigned char vs_smem[];
   vocab_step_body<TA, false, K, true>(a, KC, blockIdx.x, blockIdx.y, vs_smem, bans);
+}
+
+template <typename TA, int K>
+__global__ __launch_bounds__(512) void vocab_step_beam_hop_kernel(const VocabStepArgs a, const int KC, const BanLists bans, const HopLists hops) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char vs_smem[];
+  vocab_step_body<TA, false, K, true, true>(a, KC, blockIdx.x, blockIdx.y, vs_smem, bans, hops);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -998,6 +1006,44 @@ int vocab_step_beam(const VocabStepArgs& a0, int K, int dtype, hipStream_t strea
   const int KC = vocab_chunk(dtype, a.H);
   const dim3 grid((unsigned)a.nblk, (unsigned)cdiv(a.B, kStepRows));
   return with_beam_k(K, [&](auto k) { return vocab_beam_launch<k>(a, dtype, lds, KC, grid, stream, bans); });
+}
+
+template <int K>
+int vocab_hop_launch(const VocabStepArgs& a, int dtype, size_t lds, int KC, dim3 grid, hipStream_t stream, const BanLists& bans,
+                     const HopLists& hops) {
+  if (dtype == DT_F32) {
+    static LdsGrant h32;
+    GIC_PROPAGATE(allow_lds(vocab_step_beam_hop_kernel<float, K>, lds, h32));
+    hipLaunchKernelGGL((vocab_step_beam_hop_kernel<float, K>), grid, dim3(512), lds, stream, a, KC, bans, hops);
+  } else {
+    static LdsGrant h16;
+    GIC_PROPAGATE(allow_lds(vocab_step_beam_hop_kernel<bf16_t, K>, lds, h16));
+    hipLaunchKernelGGL((vocab_step_beam_hop_kernel<bf16_t, K>), grid, dim3(512), lds, stream, a, KC, bans, hops);
+  }
+  GIC_CHECK_LAUNCH("vocab_step_beam_hop");
+  return GIC_OK;
+}
+
+int vocab_step_beam_hop(const VocabStepArgs& a0, int K, int dtype, hipStream_t stream, const BanLists& bans, const HopLists& hops) {
+  VocabStepArgs a = a0;
+  a.dbg = 0; a.pretrain = 1; a.u = nullptr; a.out = nullptr; a.rowkey = nullptr;
+  GIC_CHECK_ARG(a.h && a.wout && a.bias && a.part_m && a.part_s && a.part_v && a.part_i, "vocab_step_beam_hop: null buffer");
+  GIC_CHECK_ARG(a.B > 0 && a.V >= 4 && a.V % 4 == 0 && a.H % 8 == 0 && a.ldh % 8 == 0 && K >= 2 && K <= kBeamMax && K % 2 == 0,
+                "vocab_step_beam_hop: bad dims");
+  GIC_CHECK_ARG(a.nblk == cdiv(a.V, kVocabTile), "vocab_step_beam_hop: nblk must be ceil(V / %d)", kVocabTile);
+  GIC_CHECK_ARG(bans.nban && bans.ban && bans.cap > 0 && hops.id && hops.val && hops.n >= 1 && hops.n <= kHopMax,
+                "vocab_step_beam_hop: ban and hop lists must be set");
+  const size_t tile = (size_t)kStepRows * (kVocabTile + 1) * sizeof(float);
+  size_t lds = vocab_lds_bytes(dtype, a.H);
+  if (lds < tile) lds = tile;
+  const int KC = vocab_chunk(dtype, a.H);
+  const dim3 grid((unsigned)a.nblk, (unsigned)cdiv(a.B, kStepRows));
+  switch (K) {                                                // (2^C divides K: the forced search's beam sizes are even)
+    case 2: return vocab_hop_launch<2>(a, dtype, lds, KC, grid, stream, bans, hops);
+    case 4: return vocab_hop_launch<4>(a, dtype, lds, KC, grid, stream, bans, hops);
+    case 6: return vocab_hop_launch<6>(a, dtype, lds, KC, grid, stream, bans, hops);
+    default: return vocab_hop_launch<8>(a, dtype, lds, KC, grid, stream, bans, hops);
+  }
 }
 
 int sample_finish(const SampleFinishArgs& a, int dtype, hipStream_t stream) {

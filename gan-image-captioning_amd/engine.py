@@ -8,6 +8,7 @@ library as a raw device pointer.  All launches go to the current PyTorch HIP str
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -348,6 +349,79 @@ def _constraints_ws(c, rows: int, Lc: int, dev) -> torch.Tensor:
     return _aligned_ws(None, int(out.value), dev)
 
 
+FORCE_MAX_SETS, FORCE_MAX_IDS = 3, 4          # gic_forced_words: C <= 3 constraint sets per image of D <= 4 ids
+
+
+def pack_force_words(force_words, B: int) -> torch.Tensor:
+    """``force_words`` as the int32 [B, C, D] tensor of gic_forced_words, padded with -1.  Either that tensor already (any device), or
+    a list per image of constraints, each an int (one id) or a tuple of ints (a disjunctive set): C = the most constraints of any
+    image (at least 1), D = the largest set.  The list form is packed on the host."""
+    if isinstance(force_words, torch.Tensor):
+        if force_words.dim() != 3 or force_words.shape[0] != B or force_words.dtype != torch.int32:
+            raise ValueError(f"force_words must be int32 [B={B}, C, D], got {tuple(force_words.shape)} {force_words.dtype}")
+        t = force_words
+    else:
+        one = lambda c: isinstance(c, numbers.Integral) or (isinstance(c, torch.Tensor) and c.dim() == 0)     # noqa: E731
+        per = [[(int(c),) if one(c) else tuple(int(v) for v in c) for c in img] for img in force_words]
+        if len(per) != B:
+            raise ValueError(f"force_words must hold one list of constraints per image ({B}), got {len(per)}")
+        Cn = max([len(img) for img in per] + [1])
+        Dn = max([len(c) for img in per for c in img] + [1])
+        t = torch.full((B, Cn, Dn), -1, dtype=torch.int32)
+        for b, img in enumerate(per):
+            for c, ids in enumerate(img):
+                if any(v < 0 for v in ids):
+                    raise ValueError(f"force_words: image {b}, constraint {c}: id outside [0, V)")
+                t[b, c, :len(ids)] = torch.tensor(ids, dtype=torch.int32)
+    if t.shape[1] > FORCE_MAX_SETS:
+        raise ValueError(f"force_words: at most {FORCE_MAX_SETS} constraints per image (C), got {t.shape[1]}")
+    if t.shape[2] > FORCE_MAX_IDS:
+        raise ValueError(f"force_words: at most {FORCE_MAX_IDS} ids per constraint (D), got {t.shape[2]}")
+    if t.shape[1] < 1 or t.shape[2] < 1:
+        raise ValueError("force_words: C and D must be at least 1")
+    return t
+
+
+_FORCE_CHECKED = [None]      # the last device tensor check_force_words passed, as (storage, version, shape, the check's arguments)
+
+
+def check_force_words(t: torch.Tensor, V: int, beam: int, eos_id: int, pad_id: int, suppress_tokens=()) -> None:
+    """The refusals of a forced search that the library cannot make (the ids live on the device): run on a host copy of the packed
+    tensor before anything is launched.  A device tensor costs one blocking device-to-host copy; the same tensor, unmodified since
+    (torch's version counter), passed again with the same arguments is not read a second time, so a decode loop that reuses its
+    constraint tensor syncs once."""
+    key = None
+    if t.device.type != "cpu":
+        key = (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), int(V), int(beam), int(eos_id), int(pad_id),
+               tuple(int(v) for v in suppress_tokens))
+        if _FORCE_CHECKED[0] is not None and _FORCE_CHECKED[0][0] is t and _FORCE_CHECKED[0][1] == key:
+            return
+    _check_force_words_host(t.detach().cpu(), V, beam, eos_id, pad_id, suppress_tokens)
+    if key is not None:
+        _FORCE_CHECKED[0] = (t, key)
+
+
+def _check_force_words_host(h: torch.Tensor, V: int, beam: int, eos_id: int, pad_id: int, suppress_tokens=()) -> None:
+    B, Cn, Dn = h.shape
+    if int(beam) % (1 << Cn):
+        raise ValueError(f"force_words: 2^C = {1 << Cn} must divide the beam size {int(beam)}")
+    if bool((h < -1).any()) or bool((h >= V).any()):
+        raise ValueError(f"force_words: id outside [0, {V}) (-1 pads a set)")
+    live = h[h >= 0]
+    if live.numel() == 0:
+        raise ValueError("force_words: every constraint of every image is absent; use the plain beam search")
+    if bool((live == pad_id).any()):
+        raise ValueError(f"force_words: <PAD> ({pad_id}) in a constraint")
+    if bool((live == eos_id).any()):
+        raise ValueError(f"force_words: <E> ({eos_id}) in a constraint")
+    sup = set(int(v) for v in suppress_tokens)
+    if sup and any(int(v) in sup for v in live.tolist()):
+        raise ValueError("force_words: a suppressed id (suppress_tokens) in a constraint")
+    s = h.sort(dim=-1).values
+    if bool(((s[..., 1:] == s[..., :-1]) & (s[..., 1:] >= 0)).any()):
+        raise ValueError("force_words: duplicate id within a constraint")
+
+
 def _sample_noise(noise_u: Optional[torch.Tensor], Lc: int, rows: int, V: int) -> Optional[torch.Tensor]:
     if noise_u is None:
         return None
@@ -411,6 +485,39 @@ class _CaptionDecodes:
             what, o = "beam_search", opts
         self._decode_call(what, params, B, Lc, o, cons, B * int(beam), ws, (features, *maps), outs)
         return outs if want_alphas else outs[:3]
+
+    def forced_beam_ws_bytes(self, B: int, Lc: int, beam: int) -> int:
+        """Bytes of gic_*_forced_beam_search's workspace (host-only query)."""
+        return self._ws_bytes("forced_beam", B, Lc, beam)
+
+    def _forced_beam(self, params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, force_words, cons,
+                     suppress_tokens):
+        """gic_*_forced_beam_search (lexically constrained beam search): _beam's outputs plus met int32 [B, beam], the mask of
+        constraints each returned beam has met (absent ones set)."""
+        self.check_params(params)
+        require_gpu(features, fmap)
+        features = _decode_features(features, self.E)
+        B, dev = features.shape[0], features.device
+        force = pack_force_words(force_words, B)
+        check_force_words(force, self.V, beam, eos_id, pad_id, suppress_tokens)
+        force = force.to(dev).contiguous()
+        maps = self._decode_maps(fmap, B)
+        self.prepare(params)
+        ws = _aligned_ws(ws, self.forced_beam_ws_bytes(B, Lc, beam), dev)
+        opts = L.DecoderBeamOpts()
+        opts.beam, opts.eos_id, opts.pad_id, opts.length_penalty = int(beam), int(eos_id), int(pad_id), float(length_penalty)
+        keep = self._states(opts, states, B)                         # (h0, c0): referenced until the call has returned
+        outs = _decode_outputs(B, beam, Lc, dev) + self._beam_alphas(want_alphas, B, beam, Lc, dev)
+        met = torch.empty(B, int(beam), device=dev, dtype=torch.int32)
+        fw = L.ForcedWords()
+        fw.C, fw.D, fw.ids = int(force.shape[1]), int(force.shape[2]), ptr(force)
+        name = f"{self._PREFIX}_forced_beam_search"
+        cws = _constraints_ws(cons, B * int(beam), Lc, dev) if cons is not None else None
+        o = _diverse_opts(opts, 1, 0.0)
+        L.check(getattr(L.load(), name)(C.byref(self.dims(B, Lc)), C.byref(self._pstruct(params)), C.byref(self._shadow_struct(params)),
+                                        C.byref(o), C.byref(fw), C.byref(cons) if cons is not None else None, ptr(ws), ptr(cws),
+                                        *map(ptr, (features, *maps)), *map(ptr, outs), ptr(met), stream_ptr()), name)
+        return (outs if want_alphas else outs[:3]) + (met,)
 
     def _sample(self, params, features, fmap, Lc, num_samples, top_k, top_p, temperature, eos_id, pad_id, seed, noise_u, states, ws, cons):
         self.check_params(params)
@@ -1322,12 +1429,17 @@ class DecoderEngine(_CaptionDecodes, _TeacherForced):
         return B * beam <= self.fused_rollout_rows()
 
     def beam_search(self, params, features: torch.Tensor, Lc: int, beam: int, eos_id: int = 2, pad_id: int = 0,
-                    length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None, no_repeat_ngram: int = 0,
+                    length_penalty: float = 0.0, states=None, ws: Optional[torch.Tensor] = None, force_words=None, no_repeat_ngram: int = 0,
                     min_length: int = 0, suppress_tokens=()):
         """gic_decoder_beam_search: (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam]), beams best first.
         ``states`` = (h0, c0), each f32 [NL, B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned).
         ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``: decode constraints (gic_decode_constraints); any of them set runs
-        gic_decoder_constrained_beam_search."""
+        gic_decoder_constrained_beam_search.  ``force_words`` (pack_force_words; None = off, nothing new runs): lexically constrained
+        beam search, gic_decoder_forced_beam_search -- the outputs in its order plus met int32 [B, beam]; ``ws`` then holds
+        forced_beam_ws_bytes() bytes."""
+        if force_words is not None:
+            return self._forced_beam(params, features, None, Lc, beam, eos_id, pad_id, length_penalty, states, ws, False, force_words,
+                                     decode_constraints(no_repeat_ngram, min_length, suppress_tokens), suppress_tokens)
         return self._beam(params, features, None, Lc, beam, eos_id, pad_id, length_penalty, states, ws, False, None,
                           decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
 
@@ -1889,12 +2001,17 @@ class AttnDecoderEngine(_CaptionDecodes, _TeacherForced):
         return self._ws_bytes("beam", B, Lc, beam)
 
     def beam_search(self, params, features, fmap, Lc: int, beam: int, eos_id: int = 2, pad_id: int = 0, length_penalty: float = 0.0,
-                    states=None, ws: Optional[torch.Tensor] = None, want_alphas: bool = False, no_repeat_ngram: int = 0,
+                    states=None, ws: Optional[torch.Tensor] = None, want_alphas: bool = False, force_words=None, no_repeat_ngram: int = 0,
                     min_length: int = 0, suppress_tokens=()):
         """gic_attn_beam_search: (ids int64 [B, beam, Lc], scores f32 [B, beam], lengths int32 [B, beam][, alphas f32 [B, beam, Lc, P]]),
         beams best first.  ``fmap`` [B, P, C] is cast to the compute dtype as in sample_fwd.  ``states`` = (h0, c0), each [1, B, H] or
         [B, H].  ``ws``: a uint8 workspace of at least beam_ws_bytes() bytes (256-aligned).  ``no_repeat_ngram`` / ``min_length`` /
-        ``suppress_tokens``: decode constraints (gic_decode_constraints); any of them set runs gic_attn_constrained_beam_search."""
+        ``suppress_tokens``: decode constraints (gic_decode_constraints); any of them set runs gic_attn_constrained_beam_search.
+        ``force_words`` (pack_force_words; None = off, nothing new runs): gic_attn_forced_beam_search -- the outputs in its order, the
+        alphas re-ordered alongside, plus met int32 [B, beam] last; ``ws`` then holds forced_beam_ws_bytes() bytes."""
+        if force_words is not None:
+            return self._forced_beam(params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, force_words,
+                                     decode_constraints(no_repeat_ngram, min_length, suppress_tokens), suppress_tokens)
         return self._beam(params, features, fmap, Lc, beam, eos_id, pad_id, length_penalty, states, ws, want_alphas, None,
                           decode_constraints(no_repeat_ngram, min_length, suppress_tokens))
 

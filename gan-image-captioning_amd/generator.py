@@ -204,13 +204,22 @@ def _teacher_inputs(caps, vocab: int):
     return caps.clamp(0, vocab - 1), torch.zeros(caps.shape, dtype=torch.int32, device=caps.device)
 
 
-def _beam_search(dec, features, maps, beam_size, max_caption_len, eos_id, length_penalty, states, return_beams, beam_groups, diversity, **kw):
+def _beam_search(dec, features, maps, beam_size, max_caption_len, eos_id, length_penalty, states, return_beams, beam_groups, diversity,
+                 force_words=None, return_met=False, **kw):
     """Decoder.beam_search / AttnDecoder.beam_search: ``maps`` = () or (fmap,), ``kw`` = the engine's further keywords (the decode
-    constraints, want_alphas).  One group without diversity is the plain search."""
+    constraints, want_alphas).  One group without diversity is the plain search; ``force_words`` the forced one (met comes last)."""
     L = int(dec.max_seq_length if max_caption_len is None else max_caption_len)
+    if force_words is None and return_met:
+        raise ValueError("return_met needs force_words")
     with torch.no_grad():
         args = ([p.detach() for p in dec.param_list()], features.detach().float(), *(m.detach() for m in maps), L, int(beam_size))
-        if int(beam_groups) == 1 and float(diversity) == 0.0:
+        if force_words is not None:
+            if int(beam_groups) != 1 or float(diversity) != 0.0:
+                raise ValueError("force_words with beam_groups > 1 or diversity: forced words do not combine with diverse beam search")
+            out = dec.engine().beam_search(*args, int(eos_id), 0, float(length_penalty), states=states, force_words=force_words, **kw)
+            if not return_met:
+                out = out[:-1]
+        elif int(beam_groups) == 1 and float(diversity) == 0.0:
             out = dec.engine().beam_search(*args, int(eos_id), 0, float(length_penalty), states=states, **kw)
         else:
             out = dec.engine().diverse_beam_search(*args, int(beam_groups), float(diversity), int(eos_id), 0, float(length_penalty),
@@ -335,7 +344,7 @@ class Decoder(nn.Module):
         return (pred, hc, (inputs, replaced)) if return_inputs else (pred, hc)
 
     def beam_search(self, features, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None, return_beams=False,
-                    beam_groups=1, diversity=0.0, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
+                    beam_groups=1, diversity=0.0, force_words=None, return_met=False, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """Beam-search caption decode (gicap.h gic_decoder_beam_search): token log-probabilities of sample(pretrain=True)'s
         distribution, ``beam_size`` (1..8) hypotheses per image, <E> = ``eos_id`` ends a beam, <PAD> (0) after it; final order by
         score / length**length_penalty.  Returns detached (ids int64 [B, L], scores f32 [B], lengths int32 [B]) of the best beam, or
@@ -344,9 +353,14 @@ class Decoder(nn.Module):
         beam_groups beams with the Hamming penalty ``diversity``; the beams come in group-major order, the best beam is group 0's.
         ``no_repeat_ngram`` (n: no n-gram occurs twice in a caption; 0 = off), ``min_length`` (<E> not before that many
         tokens; 0 = off) and ``suppress_tokens`` (up to 16 ids never emitted): decode constraints (gicap.h gic_decode_constraints),
-        applied inside the search."""
+        applied inside the search.
+        ``force_words`` (None = off): lexically constrained beam search (gicap.h gic_forced_words) -- an int32 tensor [B, C, D] padded
+        with -1, or a list per image of constraints, each an int or a tuple of ints (a caption meets a constraint by emitting any id
+        of it); C <= 3, D <= 4, 2^C must divide ``beam_size``, one beam group.  The beams come ordered by constraints met, then
+        score / length**length_penalty: the best beam is the best caption that meets everything, if the search found one.
+        ``return_met`` appends met int32 [B] ([B, k]): the bitmask of constraints each caption meets (absent ones set)."""
         return _beam_search(self, features, (), beam_size, max_caption_len, eos_id, length_penalty, states, return_beams, beam_groups, diversity,
-                            no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
+                            force_words=force_words, return_met=return_met, no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
 
     def sample_captions(self, features, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2, seed=None,
                         noise_u=None, states=None, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
@@ -487,21 +501,22 @@ class AttnDecoder(nn.Module):
                                                                    self.attn.w_h, self.attn.w_a]
 
     def beam_search(self, features, fmap=None, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, states=None,
-                    return_beams=False, return_alphas=False, beam_groups=1, diversity=0.0, no_repeat_ngram=0, min_length=0,
-                    suppress_tokens=()):
+                    return_beams=False, return_alphas=False, beam_groups=1, diversity=0.0, force_words=None, return_met=False,
+                    no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """Beam-search caption decode with attention (gicap.h gic_attn_beam_search): Decoder.beam_search's search over the token
         log-probabilities of sample(features, fmap, pretrain=True).  ``fmap`` [B, P, C]: the trunk's last feature map
         (Encoder.forward_with_map).  Returns detached (ids int64 [B, L], scores f32 [B], lengths int32 [B]) of the best beam, or all beams
         ([B, k, L], [B, k], [B, k]) with ``return_beams``; ``return_alphas`` appends the attention weights with which each token was
         produced, f32 [B, L, P] (all beams: [B, k, L, P]), zero past a beam's length.  ``states`` = (h0, c0), each [1, B, H].
         ``beam_groups`` / ``diversity``: diverse beam search (gic_attn_diverse_beam_search) as in Decoder.beam_search, and so are the
-        decode constraints ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``."""
+        decode constraints ``no_repeat_ngram`` / ``min_length`` / ``suppress_tokens``.  ``force_words`` / ``return_met``: lexically
+        constrained beam search as in Decoder.beam_search (gic_attn_forced_beam_search); met comes after the alphas."""
         if fmap is None:                # (checked before anything touches self: the LSTM decoder's call form has no map)
             raise NotImplementedError("the attention decoder's beam search needs the trunk's feature map: beam_search(features, fmap), "
                                       "or Generator.caption(images)")
         return _beam_search(self, features, (fmap,), beam_size, max_caption_len, eos_id, length_penalty, states, return_beams, beam_groups,
-                            diversity, want_alphas=bool(return_alphas), no_repeat_ngram=no_repeat_ngram, min_length=min_length,
-                            suppress_tokens=suppress_tokens)
+                            diversity, force_words=force_words, return_met=return_met, want_alphas=bool(return_alphas),
+                            no_repeat_ngram=no_repeat_ngram, min_length=min_length, suppress_tokens=suppress_tokens)
 
     def sample_captions(self, features, fmap=None, num_samples=5, top_k=0, top_p=1.0, temperature=1.0, max_caption_len=None, eos_id=2,
                         seed=None, noise_u=None, states=None, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
@@ -792,8 +807,8 @@ class Generator(nn.Module):
         self.init_params()
 
     def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False, return_alphas=False,
-                beam_groups=1, diversity=0.0, rerank_disc=None, rerank_weight=1.0, return_rerank=False, consensus=None, consensus_weight=1.0,
-                return_consensus=False, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
+                beam_groups=1, diversity=0.0, force_words=None, return_met=False, rerank_disc=None, rerank_weight=1.0, return_rerank=False,
+                consensus=None, consensus_weight=1.0, return_consensus=False, no_repeat_ngram=0, min_length=0, suppress_tokens=()):
         """Captions for ``images`` by beam search: features as the trainer forms them (training.py:66-68) -- the encoder in the
         module's current mode, or embed(<S>) with --conditional-gan 0 -- under no-grad, then ``decoder.beam_search``.  With
         --decoder attention the encoder also gives the feature map, and ``return_alphas`` appends the attention weights
@@ -807,10 +822,18 @@ class Generator(nn.Module):
         ``consensus`` (a CiderD; None = nothing else runs): consensus (minimum-Bayes-risk) selection instead -- the beams are re-ranked by
         score / max(len, 1) ** length_penalty + ``consensus_weight`` * each beam's mean CIDEr-D against the other beams
         (CiderD.pairwise, then the same gic_rerank: its order, tie rule and outputs); ``return_consensus`` appends (final [B, k],
-        consensus [B, k]) in the new order.  One re-ranking at a time: ``consensus`` with ``rerank_disc`` is refused."""
+        consensus [B, k]) in the new order.  One re-ranking at a time: ``consensus`` with ``rerank_disc`` is refused.
+        ``force_words`` / ``return_met``: lexically constrained beam search (Decoder.beam_search): words the caption must contain; met
+        comes last.  Its order is the search's own: ``rerank_disc`` and ``consensus`` are refused with it."""
         kw = dict(beam_size=beam_size, max_caption_len=max_caption_len, eos_id=eos_id, length_penalty=length_penalty, return_beams=return_beams,
                   beam_groups=beam_groups, diversity=diversity, no_repeat_ngram=no_repeat_ngram, min_length=min_length,
                   suppress_tokens=suppress_tokens)
+        if force_words is not None:
+            if rerank_disc is not None or consensus is not None:
+                raise ValueError("force_words with rerank_disc or consensus: a forced search keeps its own order (constraints met first)")
+            kw.update(force_words=force_words, return_met=return_met)
+        elif return_met:
+            raise ValueError("return_met needs force_words")
         if return_alphas and not isinstance(self.decoder, AttnDecoder):
             raise ValueError("attention weights exist for --decoder attention only")
         if rerank_disc is None and return_rerank:
@@ -988,11 +1011,13 @@ class Ensemble:
         return int(self.decoder.max_seq_length if max_caption_len is None else max_caption_len)
 
     def caption(self, images, beam_size=3, max_caption_len=None, eos_id=2, length_penalty=0.0, return_beams=False, return_alphas=False,
-                beam_groups=1, diversity=0.0, rerank_disc=None, rerank_weight=1.0, return_rerank=False, consensus=None, consensus_weight=1.0,
-                return_consensus=False, no_repeat_ngram=0, min_length=0, suppress_tokens=(), states=None):
+                beam_groups=1, diversity=0.0, force_words=None, return_met=False, rerank_disc=None, rerank_weight=1.0, return_rerank=False,
+                consensus=None, consensus_weight=1.0, return_consensus=False, no_repeat_ngram=0, min_length=0, suppress_tokens=(), states=None):
         """Generator.caption on the ensemble's logits: the same keywords, outputs and re-rankings (a conditioned ``rerank_disc`` reads
         member 0's pooled trunk features).  ``return_alphas`` and ``states`` are refused: an ensemble has no one attention map and no
         one initial state."""
+        if force_words is not None or return_met:              # (Generator.caption's keywords, in its positions; refused here)
+            raise ValueError("force_words with an ensemble: the forced search runs one model")
         if return_alphas:
             raise ValueError("an ensemble returns no attention weights (return_alphas): every member attends on its own")
         if states is not None:

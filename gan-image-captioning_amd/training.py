@@ -25,7 +25,7 @@ from torch.utils.data import DataLoader
 from tqdm import tqdm
 
 from . import engine, parallel
-from .args import check_eval_ensemble, check_image_pipeline
+from .args import check_eval_ensemble, check_eval_forced, check_image_pipeline
 from .discriminator import Discriminator
 from .fused_step import FusedAdvStep
 from .seqgan import SeqGANStep
@@ -204,6 +204,7 @@ class GANInstructor:
     eval_ema = False        # --eval-ema
     _ema_held = False       # True: evaluate* stays on the weights that are live now (nested evaluations, checkpoint selection)
     eval_ensemble = None    # --eval-ensemble*: what check_eval_ensemble returned
+    eval_forced = None      # --eval-force-words / --eval-force-beam-size: what check_eval_forced returned
     _ensemble = None        # the evaluations' Ensemble, built at the first evaluation that needs it
     _ensemble_ema = None    # its EMA member, refreshed at the start of every evaluation
     _live_only = False      # True: evaluate* stays on the live generator alone (checkpoint selection)
@@ -220,6 +221,7 @@ class GANInstructor:
         check_image_pipeline(args)
         oc = check_optimizer(args)
         self.eval_ensemble = check_eval_ensemble(args)       # None: the evaluations run on the one generator
+        self.eval_forced = check_eval_forced(args)           # None: no forced-words evaluation; else (N, beam size)
         self.dist = parallel.DistInfo.from_env()
         from .generator import SEEDS
         SEEDS.rank = self.dist.rank            # replicas share weights and the torch seed, not the device noise streams
@@ -721,6 +723,8 @@ class GANInstructor:
                 self.evaluate_diverse_beam("val", beam_size=int(self.args.eval_diverse_beam_size),
                                            groups=int(getattr(self.args, "eval_diverse_groups", 2)),
                                            diversity=float(getattr(self.args, "eval_diversity_strength", 0.5)))
+            if self.eval_forced is not None and self.dist.rank == 0:
+                self.evaluate_forced("val", num_words=self.eval_forced[0], beam_size=self.eval_forced[1])
             if int(getattr(self.args, "eval_consensus_samples", 0)) > 0 and self.dist.rank == 0:
                 self.evaluate_consensus("val", num_samples=int(self.args.eval_consensus_samples), top_k=int(getattr(self.args, "eval_top_k", 0)),
                                         top_p=float(getattr(self.args, "eval_top_p", 1.0)),
@@ -929,10 +933,10 @@ class GANInstructor:
             return ids, lengths
         return self._decode_batches(what, decode, max_caption_len, batch_size)
 
-    def _decode_batches(self, what, decode, max_caption_len=None, batch_size=None):
+    def _decode_batches(self, what, decode, max_caption_len=None, batch_size=None, with_caps=False):
         """The decode loop of the evaluations: every image of the split once (``_eval_groups``), the generator in eval mode;
-        ``decode(images, L, batch_index)`` gives (ids, lengths) of the batch.  Yields per batch (ids and lengths on the device, the
-        images' reference token lists)."""
+        ``decode(images, L, batch_index)`` gives (ids, lengths) of the batch (``with_caps``: decode(images, L, batch_index, the
+        images' reference token lists)).  Yields per batch (ids and lengths on the device, the images' reference token lists)."""
         ds, groups, order, coco, coco_ids, _ = self._eval_groups(what)
         gen = self._eval_gen()
         was_training = gen.training
@@ -946,7 +950,7 @@ class GANInstructor:
                 caps = [[coco_ids(ds.captions[j]) for j in groups[k]] if coco else [it[1]] for k, it in zip(keys, firsts)]
                 L = max_caption_len or max(int(getattr(self.args, "max_seq_len", 0) or 0),
                                            max(len(c) for group in caps for c in group) + 2)
-                ids, lengths = decode(images, L, bi)
+                ids, lengths = decode(images, L, bi, caps) if with_caps else decode(images, L, bi)
                 yield ids, lengths, caps
         finally:
             gen.train(was_training)
@@ -1007,6 +1011,93 @@ class GANInstructor:
         step = max(self.adv_epoch, 0)
         for name, key in (("BLEU1M", "bleu1"), ("BLEU2M", "bleu2"), ("BLEU3M", "bleu3"), ("BLEU4M", "bleu4"), ("ROUGEL", "rouge_l"),
                           ("CIDErDM", "cider_d")):
+            self.writer.add_scalar(f"{name}_{what}", out[key], step)
+        return out
+
+    @staticmethod
+    def oracle_tags(refs, n, df, barred=()):
+        """The oracle-tags protocol's forced words of one image: among the tokens that occur in at least half of its references
+        ``refs`` (token lists) and are not ``barred``, the ``n`` with the lowest document frequency ``df`` {token: count}, ties to the
+        lower id.  Fewer than ``n`` such tokens give fewer words."""
+        counts = {}
+        for r in refs:
+            for t in set(int(v) for v in r):
+                counts[t] = counts.get(t, 0) + 1
+        ok = [t for t, c in counts.items() if 2 * c >= len(refs) and t not in barred]
+        return sorted(ok, key=lambda t: (df.get(t, 0), t))[:int(n)]
+
+    @_on_eval_weights
+    def evaluate_forced(self, what="val", num_words=1, beam_size=8, length_penalty=0.0, max_caption_len=None, batch_size=None):
+        """The forced-words evaluation (--eval-force-words N, --eval-force-beam-size K), the "oracle tags" protocol of Anderson et al.
+        (2017): per image of ``evaluate`` the ``num_words`` reference tokens of ``oracle_tags`` (document frequencies from the CiderD
+        table of ``evaluate_cider``; the specials and the suppressed ids are barred) are forced into the caption by lexically constrained
+        beam search (Generator.caption force_words; one constraint per word), next to plain beam search of the same ``beam_size``.
+        The decode constraints of the evaluations apply to both.  Returns {"bleu4", "cider_d": corpus BLEU-4 and mean CIDEr-D of the
+        forced search's best captions, scored on the GPU as in ``evaluate_metrics``; "satisfied": the share of images whose best forced
+        caption holds all its words; "satisfied_plain": the same share for plain beam search}.  The sums stay on the device and are read
+        with one sync at the end; the words are chosen on the host from the scorer's host copy of its table, and the ids are checked on
+        the host before they are uploaded.  The plain search runs for every batch; a batch in which no image has a word to force runs
+        it alone and counts its captions as the forced ones.  Logs them and
+        writes the scalars ``BLEU4F_<what>``, ``CIDErDF_<what>``, ``ForcedSat_<what>``, ``PlainSat_<what>``."""
+        from .cider import CiderD, RefBatch, unigram_df
+        from .metrics import STAT_COLUMNS, OverlapScorer, corpus_bleu
+        from .tasks import SPECIALS, ImageGroups
+        N, K = int(num_words), int(beam_size)
+        if not 1 <= N <= 3 or K % (1 << N):
+            raise ValueError(f"evaluate_forced: num_words must be 1..3 and 2^num_words must divide beam_size, got {N} and {K}")
+        gen = self._eval_gen()
+        if gen is not self.gen:
+            raise ValueError("evaluate_forced with an ensemble: the forced search runs one model")
+        dev = self.args.device
+        ds = self.dev_dataset if what == "val" else self.train_dataset
+        if what not in self._cider:
+            self._cider[what] = CiderD(ImageGroups(ds).references(), self.args.vocab_size, dev)
+        cider = self._cider[what]
+        df = unigram_df(cider.keys_host, cider.df)                   # (the table's host copy: no device read)
+        cons = self._eval_constraints()
+        barred = {ds.word_to_index[w] for w in SPECIALS if w in ds.word_to_index} | {0, 1, 2} | set(cons["suppress_tokens"])
+        overlap = OverlapScorer(self.args.vocab_size, dev)
+        stats = torch.zeros(len(STAT_COLUMNS), dtype=torch.int64, device=dev)
+        sat = torch.zeros(2, dtype=torch.int64, device=dev)             # images satisfied: forced, plain
+        cd, n_img = [], 0
+
+        def held(ids, lengths, tags):
+            pos = torch.arange(ids.shape[1], device=ids.device)[None, :, None] < lengths.long()[:, None, None]
+            return (((ids[:, :, None] == tags[:, None, :]) & pos).any(1) | (tags < 0)[:, :]).all(1)
+
+        def decode(images, L, bi, caps):
+            words = [self.oracle_tags(group, N, df, barred) for group in caps]
+            tags = torch.full((len(caps), N), -1, dtype=torch.int32)
+            for b, w in enumerate(words):
+                tags[b, :len(w)] = torch.tensor(w, dtype=torch.int32)
+            pid, _, plen = gen.caption(images, beam_size=K, max_caption_len=L, length_penalty=length_penalty, **cons)
+            tags_d = tags.to(dev)
+            if any(words):
+                ids, _, lengths, met = gen.caption(images, beam_size=K, max_caption_len=L, length_penalty=length_penalty,
+                                                   force_words=tags[:, :, None].contiguous(), return_met=True, **cons)   # (host ids: checked without a sync)
+                ok = met == (1 << N) - 1
+            else:                                                        # no image of the batch has a word to force: the plain search
+                ids, lengths = pid, plen
+                ok = torch.ones(len(caps), dtype=torch.bool, device=dev)
+            sat.add_(torch.stack([ok.sum(), held(pid, plen, tags_d.long()).sum()]))
+            return ids, lengths
+
+        for ids, lengths, caps in self._decode_batches(what, decode, max_caption_len, batch_size, with_caps=True):
+            refs = RefBatch.pack(caps).to(dev)
+            st, _, _ = overlap.score(ids, lengths, refs)
+            cd.append(cider.score(ids, lengths, refs))
+            stats += st.sum(0, dtype=torch.int64)
+            n_img += len(caps)
+        if cd:                                                           # the one sync
+            *sums, fs, ps, cider_d = torch.cat([stats.double(), sat.double(), torch.cat(cd).double().mean()[None]]).tolist()
+        else:
+            sums, fs, ps, cider_d = [0] * len(STAT_COLUMNS), 0.0, 0.0, 0.0
+        out = {"bleu4": corpus_bleu(sums)[3], "cider_d": cider_d, "satisfied": fs / n_img if n_img else 0.0,
+               "satisfied_plain": ps / n_img if n_img else 0.0}
+        self.log.info("[EVAL] forced words (%s, %d words, beam %d): BLEU-4 %.4f | CIDEr-D %.4f | satisfied %.4f | plain beam satisfied %.4f",
+                      what, N, K, out["bleu4"], out["cider_d"], out["satisfied"], out["satisfied_plain"])
+        step = max(self.adv_epoch, 0)
+        for name, key in (("BLEU4F", "bleu4"), ("CIDErDF", "cider_d"), ("ForcedSat", "satisfied"), ("PlainSat", "satisfied_plain")):
             self.writer.add_scalar(f"{name}_{what}", out[key], step)
         return out
 

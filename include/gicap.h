@@ -550,6 +550,50 @@ int gic_attn_constrained_sample_captions(const gic_attn_dims* dims, const gic_at
                                          const float* features, const void* fmap, const float* noise_u, uint64_t seed, int64_t* ids,
                                          float* scores, int32_t* lengths, void* stream);
 
+/* Forced words: lexically constrained beam search (Anderson et al., "Guided Open Vocabulary Image Captioning with Constrained Beam
+ * Search", EMNLP 2017) for either decoder: what a caption MUST contain.  Image b carries C (1..3) constraint sets of up to D (1..4)
+ * token ids, ids = int32 [B, C, D] on the device, padded with -1.  A set is met once the caption has emitted any of its ids; an all -1
+ * set is absent and met from the start, so the images of one batch may carry different numbers of constraints.  A token may belong
+ * to several sets.  The caller keeps <PAD>, <E>, suppressed ids, ids outside [0, V) and duplicates within a set out of the sets (the
+ * ids live on the device: the library reads them in its kernels only, and drops an id >= V there).
+ *   state      s = the bitmask of met sets.  The K (<= 8) beams of an image are S = 2^C state groups of Kg = K / S beams, beam j in
+ *              state j / Kg.  At t = 0 the first beam of the initial state (the bits of the absent sets) is live, the others at -inf.
+ *   one step   for a live parent in state s the hop tokens are the ids of the sets outside s; token w moves the hypothesis to
+ *              s | m(w), m(w) = the mask of every set that holds w; any other token stays in s.  State group g keeps the Kg best of:
+ *              the stay candidates (the top-K admissible non-hop tokens of its live parents; the decode constraints apply as in the
+ *              constrained search), the single pad proposal of each of its finished parents, and every hop token that lands in g
+ *              from a live parent of another group.  Score = parent score + logit - logsumexp(all V logits), never renormalised; a
+ *              hop token's logit is the same element of the same vocabulary product.  A parent at -inf proposes nothing.  A group
+ *              with fewer than Kg candidates leaves the remaining beams dead: score -inf, finished.  <E> in a non-accepting state
+ *              finishes the beam there.  min_length acts on <E> as before; a no-repeat rule never bans a hop token (the row has not
+ *              emitted it).
+ *   ties       score, then the lower parent beam, then stay before hop, then the rank in the parent's row (stay) or the slot
+ *              c * D + d of the token's first unmet set (hop).
+ *   early stop as in the beam search; dead beams count as finished.
+ *   outputs    the K beams sorted by (real -- non-absent -- constraints met, descending; score / length^alpha, descending; beam
+ *              index); dead beams last, as all-pad ids of length 0 and score -inf.  met int32 [B, K]: each returned beam's state
+ *              (absent sets set; a dead beam's: the initial state).  alphas as in gic_attn_beam_search.
+ * opts: groups must be 1.  c may be NULL (no decode constraints; cws unread), else c / cws as for gic_*_constrained_beam_search, with
+ * the feasibility bound grown by the C * D hop tokens: V - (S + 1 + max(0, L - n) + C * D) >= K.  ws: 256-byte aligned,
+ * gic_*_forced_beam_ws_bytes(dims, beam) bytes.  Limits: K <= 8, 2^C divides K, C <= 3, D <= 4; no groups, ensemble, re-ranking or
+ * sampling.  Every check runs before any launch.  Integer atomics only, no split-K: the same bits run to run, in and out of the
+ * deterministic mode. */
+typedef struct gic_forced_words {
+  int32_t C;                             /* constraint sets per image: 1..3 */
+  int32_t D;                             /* ids per set: 1..4 */
+  const int32_t* ids;                    /* device: int32 [B, C, D], -1 padded */
+} gic_forced_words;
+int gic_decoder_forced_beam_ws_bytes(const gic_decoder_dims* dims, int32_t beam, uint64_t* out);   /* host-only: no GPU needed */
+int gic_attn_forced_beam_ws_bytes(const gic_attn_dims* dims, int32_t beam, uint64_t* out);         /* host-only: no GPU needed */
+int gic_decoder_forced_beam_search(const gic_decoder_dims* dims, const gic_decoder_params* params, const gic_decoder_shadow* shadow,
+                                   const gic_diverse_beam_opts* opts, const gic_forced_words* forced, const gic_decode_constraints* c,
+                                   void* ws, void* cws, const float* features, int64_t* ids, float* scores, int32_t* lengths,
+                                   int32_t* met, void* stream);
+int gic_attn_forced_beam_search(const gic_attn_dims* dims, const gic_attn_params* params, const gic_attn_shadow* shadow,
+                                const gic_diverse_beam_opts* opts, const gic_forced_words* forced, const gic_decode_constraints* c,
+                                void* ws, void* cws, const float* features, const void* fmap, int64_t* ids, float* scores,
+                                int32_t* lengths, float* alphas, int32_t* met, void* stream);
+
 /* Ensemble decoding: M members (1..GIC_MAX_ENSEMBLE) of one decoder kind, dims and compute dtype share one search.  weights w_m > 0
  * are normalised to sum 1 by the library.  At a step, member m, in its own recurrent state, gives the f32 logits l_m[r, :] of row r;
  * with lp_m = l_m - logsumexp(l_m) the ensemble's logits are
