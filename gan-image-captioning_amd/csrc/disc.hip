@@ -9,6 +9,14 @@
 // Activations [B*R, Fp] keep a zero-padded leading dim Fp (multiple of 8) so the bf16 GEMMs
 // can use 16-byte chunks along K; pad columns are zero (written by these kernels or, for
 // `ydrop`, left from a zero-initialised allocation - the GEMM epilogue never touches them).
+//
+// Host side, below the kernels (the convention of gemm.h): select_disc_fwd / select_disc_bwd are pure host functions that turn the
+// shapes (DCtx), the mode and the buffers' alignment into a plan -- the variant of every conv / pool kernel, the highway backward's form,
+// each grid, block and dynamic LDS request, the deterministic mode's block counts and folds, the one refusal (conv weights beyond the LDS
+// staging) -- under the four escape switches GIC_NO_DISC_CONV_MFMA, GIC_NO_DISC_CONV_BF16, GIC_NO_DISC_BWDW_LDS and GIC_BWDX_RPB=n, read
+// once per process (switches()).  launch_disc_* take a plan, switch on the variant and launch, with no condition of their own;
+// disc_fwd_t / disc_bwd_t are "select, then the stages in order".  gic_debug_disc_plan prints the two plans without touching the GPU
+// (tests/test_disc_cases.py, tests/test_route.py pin them); in route-only mode (gemm.h) every entry point returns before its first launch.
 #include <stdlib.h>
 #include "../../include/gicap.h"
 #include "kernels.h"
@@ -653,6 +661,7 @@ __global__ __launch_bounds__(256) void disc_highway_bwd_vec_kernel(const float* 
 
 struct DCtx {
   int B, L, V, De, R, s, F, Fp, dt;
+  int max_taps;              // the bank's largest f * s
   float drop_p;              // nn.Dropout p of discriminator.py:10,30
   long rowsBL, rowsBR;
   float keep_scale(int train) const { return train ? 1.f / (1.f - drop_p) : 1.f; }
@@ -675,9 +684,11 @@ int make_ctx(const gic_disc_dims* d, const gic_disc_params* P, const gic_disc_gr
   ConvMeta& cm = c.cm;
   cm.nconv = d->nconv; cm.F = c.F; cm.Fp = c.Fp; cm.s = c.s;
   int off = 0;
+  c.max_taps = 0;
   for (int k = 0; k < d->nconv; ++k) {
     GIC_CHECK_ARG(d->fsize[k] >= 1 && d->fsize[k] <= d->L, "disc: filter size %d does not fit caption length %d", d->fsize[k], d->L);
     GIC_CHECK_ARG(d->fsize[k] * c.s <= kMaxTaps, "disc: filter taps f*s=%d exceed %d", d->fsize[k] * c.s, kMaxTaps);
+    c.max_taps = d->fsize[k] * c.s > c.max_taps ? d->fsize[k] * c.s : c.max_taps;
     cm.fsize[k] = d->fsize[k]; cm.nfilt[k] = d->nfilt[k]; cm.foff[k] = off; off += d->nfilt[k];
     cm.w[k] = P ? P->conv_w[k] : nullptr; cm.b[k] = P ? P->conv_b[k] : nullptr;
     cm.dw[k] = G ? G->conv_w[k] : nullptr; cm.db[k] = G ? G->conv_b[k] : nullptr;
@@ -692,6 +703,118 @@ inline int grid1d(long total, int cap = 2048) {
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
+// ---------------------------------------------------------------- selection (gemm.h: select_* fills a plan, launch_* switches on it)
+// The escape switches, read once per process
+struct Switches { bool no_conv_mfma, no_conv_bf16, no_bwdw_lds; int bwdx_rpb; };
+const Switches& switches() {
+  static const Switches s = [] {
+    auto env = [](const char* name) { return getenv(name); };
+    const char* rpb = env("GIC_BWDX_RPB");
+    return Switches{env("GIC_NO_DISC_CONV_MFMA") != nullptr, env("GIC_NO_DISC_CONV_BF16") != nullptr, env("GIC_NO_DISC_BWDW_LDS") != nullptr,
+                    rpb ? atoi(rpb) : 0};
+  }();
+  return s;
+}
+
+struct Launch { unsigned gx = 1, gy = 1, block = 256; size_t lds = 0; };
+// Enqueue `kernel` as `l` says; every argument is converted to the kernel's own parameter type (a void* buffer to its element type)
+template <typename... KA, typename... A>
+int launch(const char* what, void (*kernel)(KA...), const Launch& l, hipStream_t stream, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(l.gx, l.gy), dim3(l.block), l.lds, stream, static_cast<KA>(args)...);
+  GIC_CHECK_LAUNCH(what);
+  return GIC_OK;
+}
+
+enum FwdConv { FWD_BF16, FWD_MFMA, FWD_SCALAR8, FWD_SCALAR32 };
+struct DiscFwdPlan { FwdConv conv; Launch at; };
+
+// The forward conv + pool step.  The bf16-product kernel writes no argmax: for a forward that no backward follows (keeps_argmax == false)
+void select_disc_fwd(const DCtx& c, bool keeps_argmax, DiscFwdPlan& p) {
+  const Switches& sw = switches();
+  const bool mfma = c.s == 1 && c.max_taps <= 8 && !sw.no_conv_mfma;
+  if (mfma && !sw.no_conv_bf16 && c.dt == DT_BF16 && !keeps_argmax && c.L <= 64)
+    p = {FWD_BF16, {(unsigned)((c.rowsBR + 31) / 32), 1, 512, (size_t)32 * c.L * 16 + (size_t)32 * (c.L + 9) * 4}};
+  else if (mfma)
+    p = {FWD_MFMA, {(unsigned)((c.rowsBR + 15) / 16), 1, 512, 0}};
+  else
+    p = {c.max_taps <= 8 ? FWD_SCALAR8 : FWD_SCALAR32, {(unsigned)c.rowsBR, 1, 256, c.L * c.s * sizeof(float)}};
+}
+
+enum BwdW { BWD_W_LDS, BWD_W_8, BWD_W_32 };
+enum BwdX { BWD_X_SMALL, BWD_X_GENERAL };
+struct DiscBwdPlan {
+  Launch out, out_fold{1, 1, 128}; bool out_part;     // disc_out_bwd: out.gx blocks; out_part: their partials go to dydrop and disc_out_fold sums them
+  Launch hw; bool hw_vec;                             // highway backward: 8 elements per thread | element-wise
+  Launch wg, w_fold; BwdW w; bool wgrad, w_part; int mt1, ncap;   // conv weight gradient over wg.gy block rows; w_part as out_part
+  Launch xg; BwdX x; int rpb;                         // conv input gradient; rpb: the small kernel's rows per block
+};
+
+// The backward's own kernels.  det_on: the library's deterministic mode; hw_aligned16: dydrop, hpre, pooled, dh and dpooled are 16-byte
+// aligned; keep_aligned8: so is the keep mask to 8 bytes (read in train mode only).
+// Deterministic mode (with parameter gradients): the blocks' partials of the output-layer gradients go to dydrop (MR * Fp floats) and are
+// folded in block order, with as many blocks as it holds partials for (the kernels stride their rows over the grid); room for one block
+// only: that block adds into the zeroed / accumulated gradient alone (one add per address, no order).  The conv weight gradient's block
+// rows use dydrop the same way.
+int select_disc_bwd(const DCtx& c, bool want_grads, bool det_on, bool train, bool hw_aligned16, bool keep_aligned8, DiscBwdPlan& p) {
+  const long MR = c.rowsBR, dy_floats = MR * c.Fp;
+  const bool det = want_grads && det_on, taps8 = c.max_taps <= 8;
+  long out_blocks = 256;
+  if (det && out_blocks * (kOutDim + 1) > dy_floats) out_blocks = dy_floats / (kOutDim + 1);
+  p.out = {(unsigned)(out_blocks < 1 ? 1 : out_blocks)};
+  p.out_part = det && p.out.gx > 1;
+  p.hw_vec = dy_floats / 8 < (1l << 31) && hw_aligned16 && (!train || keep_aligned8);
+  p.hw = {(unsigned)grid1d(p.hw_vec ? dy_floats / 8 : dy_floats)};
+  // conv weight gradient: 64 filters per block column; the LDS kernel's block rows stride over the ncap captions, the others' over 32-row groups
+  const bool lds = taps8 && c.s == 1 && c.R <= 64 && c.R <= c.De && MR % c.R == 0 && c.L <= 64 && !switches().no_bwdw_lds;
+  p.wgrad = want_grads;
+  p.w = lds ? BWD_W_LDS : (taps8 ? BWD_W_8 : BWD_W_32);
+  p.ncap = (int)(MR / c.R);
+  p.mt1 = (taps8 ? 8 : kMaxTaps) + 1;
+  long rows_y = lds ? p.ncap : cdiv(MR, 4 * 8);
+  rows_y = rows_y > 64 ? 64 : rows_y;
+  if (det && rows_y * c.F * p.mt1 > dy_floats) rows_y = dy_floats / ((long)c.F * p.mt1);
+  rows_y = rows_y < 1 ? 1 : rows_y;
+  p.wg = {(unsigned)cdiv(c.F, 64), (unsigned)rows_y, 256, lds ? (size_t)c.R * ((c.L + 8) | 1) * sizeof(float) : 0};
+  p.w_part = det && rows_y > 1;
+  p.w_fold = {(unsigned)cdiv((long)c.F * p.mt1, 256)};
+  // conv input gradient; the general kernel stages geff, tst and meta [Fp], part [NG][n_out] and every conv weight
+  const int n_out = c.L * c.s;
+  size_t conv_w_total = 0;
+  for (int k = 0; k < c.cm.nconv; ++k) conv_w_total += (size_t)c.cm.nfilt[k] * c.cm.fsize[k] * c.s;
+  const size_t general_lds = ((size_t)3 * c.Fp + (size_t)(n_out >= 256 ? 1 : 256 / n_out) * n_out + conv_w_total) * sizeof(float);
+  GIC_CHECK_ARG(general_lds <= 160 * 1024, "disc_bwd: conv weights (%zu floats) do not fit the LDS staging", conv_w_total);
+  p.x = n_out <= 32 && c.F <= 1024 && taps8 ? BWD_X_SMALL : BWD_X_GENERAL;
+  p.rpb = p.x == BWD_X_GENERAL ? 1 : (switches().bwdx_rpb > 0 ? switches().bwdx_rpb : (MR >= 2048 ? 4 : 1));
+  p.xg = {(unsigned)cdiv(MR, p.rpb), 1, 256, p.x == BWD_X_SMALL ? (size_t)n_out * 256 * sizeof(float) : general_lds};
+  return GIC_OK;
+}
+
+// gic_debug_disc_plan: one line per launch of the two plans, in launch order
+int plan_lines(const DCtx& c, const DiscFwdPlan& f, const DiscBwdPlan& b, char* out, size_t len) {
+  static const char* const fwd[] = {"disc_conv_pool_fwd_bf16_kernel<%s>", "disc_conv_pool_fwd_mfma_kernel<%s>", "disc_conv_pool_fwd_kernel<%s,8>",
+                                   "disc_conv_pool_fwd_kernel<%s,32>"};
+  static const char* const bw[] = {"disc_conv_pool_bwd_w_lds_kernel<%s,8>", "disc_conv_pool_bwd_w_kernel<%s,8>", "disc_conv_pool_bwd_w_kernel<%s,32>"};
+  static const char* const bx[] = {"disc_conv_pool_bwd_x_small_kernel<%s,32,8>", "disc_conv_pool_bwd_x_kernel<%s>"};
+  size_t n = 0;
+  auto line = [&](const char* kernel, const Launch& l, const char* extra = "", unsigned v0 = 0, unsigned v1 = 0) {
+    char text[192];
+    int w = snprintf(text, sizeof text, kernel, c.dt == DT_BF16 ? "bf16" : "f32");
+    w += snprintf(text + w, sizeof text - w, &l == &b.wg ? " grid=%ux%u" : " grid=%u", l.gx, l.gy);     // (the one two-dimensional grid)
+    w += snprintf(text + w, sizeof text - w, " block=%u lds=%zu", l.block, l.lds);
+    snprintf(text + w, sizeof text - w, extra, v0, v1);
+    n += snprintf(n < len ? out + n : nullptr, n < len ? len - n : 0, "%s\n", text);
+  };
+  line(fwd[f.conv], f.at);
+  line("disc_out_bwd_kernel<%s>", b.out, " blocks=%u part=%u", b.out.gx, b.out_part);
+  if (b.out_part) line("disc_out_fold_kernel", b.out_fold);
+  line(b.hw_vec ? "disc_highway_bwd_vec_kernel<%s>" : "disc_highway_bwd_kernel<%s>", b.hw);
+  if (b.wgrad) line(bw[b.w], b.wg, " rows_y=%u part=%u", b.wg.gy, b.w_part);
+  if (b.wgrad && b.w_part) line("disc_wgrad_fold_kernel", b.w_fold);
+  line(bx[b.x], b.xg, b.x == BWD_X_SMALL ? " rpb=%u" : "", b.rpb);
+  GIC_CHECK_ARG(n < len, "debug_disc_plan: the plan takes %zu bytes, out_len is %zu", n + 1, len);
+  return GIC_OK;
+}
+
 // feature2out + out2logits on st->ydrop
 int disc_head_fwd(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S, const gic_disc_state* st, float* logits,
                   hipStream_t stream) {
@@ -699,10 +822,7 @@ int disc_head_fwd(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow
   g.A = st->ydrop; g.lda = c.Fp; g.B = S->f2o_w; g.ldb = c.Fp; g.C = st->feat; g.ldc = kOutDim;
   g.M = (int)c.rowsBR; g.N = kOutDim; g.K = c.Fp; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = P->f2o_b;
   GIC_PROPAGATE(gemm(g, stream));
-  hipLaunchKernelGGL(disc_out_fwd_kernel, dim3(cdiv(c.rowsBR, 256)), dim3(256), 0, stream, (const float*)st->feat, P->o2l_w, P->o2l_b,
-                     logits, c.rowsBR);
-  GIC_CHECK_LAUNCH("disc_out_fwd");
-  return GIC_OK;
+  return launch("disc_out_fwd", disc_out_fwd_kernel, {(unsigned)cdiv(c.rowsBR, 256)}, stream, st->feat, P->o2l_w, P->o2l_b, logits, c.rowsBR);
 }
 
 // highway + dropout (fused epilogue): st->pooled -> st->hpre, st->keep, st->ydrop
@@ -722,16 +842,30 @@ int disc_highway_fwd(const DCtx& c, const gic_disc_params* P, const gic_disc_sha
 }
 
 template <typename TA>
+int launch_disc_fwd(const DiscFwdPlan& p, const DCtx& c, const gic_disc_state* st, hipStream_t stream) {
+  const char* what = "disc_conv_pool_fwd";
+  switch (p.conv) {
+    case FWD_BF16: return launch(what, disc_conv_pool_fwd_bf16_kernel<TA>, p.at, stream, st->emb, c.cm, c.L, c.De, c.R, c.rowsBR, st->pooled);
+    case FWD_MFMA:
+      return launch(what, disc_conv_pool_fwd_mfma_kernel<TA>, p.at, stream, st->emb, c.cm, c.L, c.De, c.R, c.rowsBR, st->pooled, st->argmax);
+    case FWD_SCALAR8: return launch(what, disc_conv_pool_fwd_kernel<TA, 8>, p.at, stream, st->emb, c.cm, c.L, c.De, c.R, st->pooled, st->argmax);
+    case FWD_SCALAR32: break;
+  }
+  return launch(what, disc_conv_pool_fwd_kernel<TA, kMaxTaps>, p.at, stream, st->emb, c.cm, c.L, c.De, c.R, st->pooled, st->argmax);
+}
+
+template <typename TA>
 int disc_fwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S, const gic_disc_state* st,
                const void* inp_soft, long ld_inp, const int64_t* inp_ids, int train, const uint8_t* keep_mask,
                uint64_t seed, const uint64_t* seed_dev, float* logits, hipStream_t stream) {
   // route-only mode (gemm.h): the selection of the highway product, the one product of this pass with an epilogue of its own; nothing is launched
   if (route_only()) return disc_highway_fwd(c, P, S, st, train, keep_mask, seed, seed_dev, stream);
+  DiscFwdPlan plan;
+  select_disc_fwd(c, st->argmax != nullptr, plan);
   // 1. embedding
   if (inp_ids) {
-    hipLaunchKernelGGL(disc_emb_gather_kernel, dim3(grid1d(c.rowsBL * c.De)), dim3(256), 0, stream, P->emb, inp_ids, st->emb,
-                       c.rowsBL, c.De, c.V);
-    GIC_CHECK_LAUNCH("disc_emb_gather");
+    GIC_PROPAGATE(launch("disc_emb_gather", disc_emb_gather_kernel, {(unsigned)grid1d(c.rowsBL * c.De)}, stream, P->emb, inp_ids, st->emb, c.rowsBL,
+                         c.De, c.V));
   } else {
     GemmDesc g;
     g.A = inp_soft; g.lda = ld_inp; g.B = S->emb; g.ldb = c.V; g.C = st->emb; g.ldc = c.De;
@@ -739,24 +873,7 @@ int disc_fwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
     GIC_PROPAGATE(gemm(g, stream));
   }
   // 2. conv + relu + max over time
-  int max_taps = 0;
-  for (int k = 0; k < c.cm.nconv; ++k) max_taps = c.cm.fsize[k] * c.s > max_taps ? c.cm.fsize[k] * c.s : max_taps;
-  static const bool no_mfma = getenv("GIC_NO_DISC_CONV_MFMA") != nullptr;
-  static const bool no_bf16 = getenv("GIC_NO_DISC_CONV_BF16") != nullptr;
-  if (c.s == 1 && max_taps <= 8 && !no_mfma && !no_bf16 && sizeof(TA) == 2 && !st->argmax && c.L <= 64)
-    hipLaunchKernelGGL((disc_conv_pool_fwd_bf16_kernel<TA>), dim3((unsigned)((c.rowsBR + 31) / 32)), dim3(512),
-                       (size_t)32 * c.L * 16 + (size_t)32 * (c.L + 9) * 4, stream,
-                       (const float*)st->emb, c.cm, c.L, c.De, c.R, c.rowsBR, (TA*)st->pooled);
-  else if (c.s == 1 && max_taps <= 8 && !no_mfma)
-    hipLaunchKernelGGL((disc_conv_pool_fwd_mfma_kernel<TA>), dim3((unsigned)((c.rowsBR + 15) / 16)), dim3(512), 0, stream,
-                       (const float*)st->emb, c.cm, c.L, c.De, c.R, c.rowsBR, (TA*)st->pooled, st->argmax);
-  else if (max_taps <= 8)
-    hipLaunchKernelGGL((disc_conv_pool_fwd_kernel<TA, 8>), dim3((unsigned)c.rowsBR), dim3(256), c.L * c.s * sizeof(float), stream,
-                       (const float*)st->emb, c.cm, c.L, c.De, c.R, (TA*)st->pooled, st->argmax);
-  else
-    hipLaunchKernelGGL((disc_conv_pool_fwd_kernel<TA, kMaxTaps>), dim3((unsigned)c.rowsBR), dim3(256), c.L * c.s * sizeof(float), stream,
-                       (const float*)st->emb, c.cm, c.L, c.De, c.R, (TA*)st->pooled, st->argmax);
-  GIC_CHECK_LAUNCH("disc_conv_pool_fwd");
+  GIC_PROPAGATE(launch_disc_fwd<TA>(plan, c, st, stream));
   // 3. highway + dropout
   GIC_PROPAGATE(disc_highway_fwd(c, P, S, st, train, keep_mask, seed, seed_dev, stream));
   return disc_head_fwd(c, P, S, st, logits, stream);
@@ -794,13 +911,73 @@ template <typename TA>
 int disc_fwd_redrop_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S, const gic_disc_state* src,
                       const gic_disc_state* dst, int train, const uint8_t* keep_mask, uint64_t seed, const uint64_t* seed_dev, float* logits,
                       hipStream_t stream) {
+  if (route_only()) return GIC_OK;     // (gemm.h) validated; this pass selects nothing: one kernel and the head's plain product
   const long groups = (c.rowsBR + 3) / 4;
-  hipLaunchKernelGGL((disc_highway_redrop_kernel<TA>), dim3(grid1d(groups * c.F)), dim3(256), 0, stream, (const float*)src->hpre,
-                     (const TA*)src->pooled, keep_mask, train, seed, seed_dev, c.drop_p, c.keep_scale(train), (TA*)dst->ydrop,
-                     train ? dst->keep : nullptr, c.rowsBR, c.F, c.Fp);
-  GIC_CHECK_LAUNCH("disc_highway_redrop");
+  GIC_PROPAGATE(launch("disc_highway_redrop", disc_highway_redrop_kernel<TA>, {(unsigned)grid1d(groups * c.F)}, stream, src->hpre, src->pooled, keep_mask,
+                       train, seed, seed_dev, c.drop_p, c.keep_scale(train), dst->ydrop, train ? dst->keep : nullptr, c.rowsBR, c.F, c.Fp));
   return disc_head_fwd(c, P, S, dst, logits, stream);
 }
+
+// What the backward's launchers read beside the plan
+struct BwdArgs {
+  const DCtx& c; const gic_disc_params* P; const gic_disc_state* st; const gic_disc_bwd_ws* ws; const float* d_logits;
+  gic_disc_grads G;            // all null without parameter gradients
+  const uint8_t* keep;         // null in eval mode
+  hipStream_t stream;
+};
+
+template <typename TA>
+int launch_disc_out_bwd(const DiscBwdPlan& p, const BwdArgs& a) {
+  float* part = p.out_part ? a.ws->dydrop : nullptr;
+  GIC_PROPAGATE(launch("disc_out_bwd", disc_out_bwd_kernel<TA>, p.out, a.stream, a.d_logits, a.st->feat, a.P->o2l_w, a.ws->dfeat, a.G.o2l_w, a.G.o2l_b,
+                       a.c.rowsBR, part));
+  return p.out_part ? launch("disc_out_fold", disc_out_fold_kernel, p.out_fold, a.stream, part, p.out.gx, a.G.o2l_w, a.G.o2l_b) : GIC_OK;
+}
+
+template <typename TA>
+int launch_disc_highway_bwd(const DiscBwdPlan& p, const BwdArgs& a) {
+  const DCtx& c = a.c;
+  const float scale = c.keep_scale(a.keep != nullptr);
+  if (p.hw_vec)
+    return launch("disc_highway_bwd", disc_highway_bwd_vec_kernel<TA>, p.hw, a.stream, a.ws->dydrop, a.keep, scale, a.st->hpre, a.st->pooled, a.ws->dh,
+                  a.ws->dpooled, c.rowsBR * c.Fp / 8, c.F, c.Fp / 8);
+  return launch("disc_highway_bwd", disc_highway_bwd_kernel<TA>, p.hw, a.stream, a.ws->dydrop, a.keep, scale, a.st->hpre, a.st->pooled, a.ws->dh,
+                a.ws->dpooled, c.rowsBR, c.F, c.Fp);
+}
+
+template <typename TA>
+int launch_disc_bwd_w(const DiscBwdPlan& p, const BwdArgs& a) {
+  const DCtx& c = a.c;
+  const gic_disc_state* st = a.st;
+  const char* what = "disc_conv_pool_bwd_w";
+  float* part = p.w_part ? a.ws->dydrop : nullptr;
+  if (p.w == BWD_W_LDS) {
+    GIC_PROPAGATE(launch(what, disc_conv_pool_bwd_w_lds_kernel<TA, 8>, p.wg, a.stream, a.ws->dpooled, st->pooled, st->argmax, st->emb, c.cm, c.L, c.De, c.R,
+                         p.ncap, part));
+  } else {
+    const auto kernel = p.w == BWD_W_8 ? disc_conv_pool_bwd_w_kernel<TA, 8> : disc_conv_pool_bwd_w_kernel<TA, kMaxTaps>;
+    GIC_PROPAGATE(launch(what, kernel, p.wg, a.stream, a.ws->dpooled, st->pooled, st->argmax, st->emb, c.cm, c.L, c.De, c.R, c.rowsBR, part));
+  }
+  return p.w_part ? launch("disc_wgrad_fold", disc_wgrad_fold_kernel, p.w_fold, a.stream, part, p.wg.gy, p.mt1, c.cm) : GIC_OK;
+}
+
+template <typename TA>
+int launch_disc_bwd_x(const DiscBwdPlan& p, const BwdArgs& a) {
+  const DCtx& c = a.c;
+  const gic_disc_state* st = a.st;
+  const char* what = "disc_conv_pool_bwd_x";
+  if (p.x == BWD_X_SMALL)
+    return launch(what, disc_conv_pool_bwd_x_small_kernel<TA, 32, 8>, p.xg, a.stream, a.ws->dpooled, st->pooled, st->argmax, c.cm, c.L, c.De, c.R, a.ws->demb,
+                  c.rowsBR, p.rpb);
+  static LdsGrant granted;       // one per instantiation (common.h): the staged weights can take the general kernel's request past 64 KB
+  if (!grant_lds(disc_conv_pool_bwd_x_kernel<TA>, p.xg.lds, granted)) {
+    set_last_error("disc_conv_pool_bwd_x: cannot reserve %zu bytes of LDS", p.xg.lds);
+    return GIC_ERR_LAUNCH;
+  }
+  return launch(what, disc_conv_pool_bwd_x_kernel<TA>, p.xg, a.stream, a.ws->dpooled, st->pooled, st->argmax, c.cm, c.L, c.De, c.R, a.ws->demb);
+}
+
+inline bool aligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
 
 template <typename TA>
 int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S, const gic_disc_state* st,
@@ -808,6 +985,11 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
                const float* d_logits, const gic_disc_grads* G, int accumulate, void* d_inp, long ld_dinp, hipStream_t stream,
                const float* cond_q = nullptr, float cond_scale = 0.f, float* cond_dq = nullptr) {
   const long MR = c.rowsBR;
+  const bool hw_aligned16 = aligned(ws->dydrop, 16) && aligned(st->hpre, 16) && aligned(st->pooled, 16) && aligned(ws->dh, 16) && aligned(ws->dpooled, 16);
+  DiscBwdPlan plan;
+  GIC_PROPAGATE(select_disc_bwd(c, G != nullptr, det_mode(), train != 0, hw_aligned16, aligned(st->keep, 8), plan));
+  if (route_only()) return GIC_OK;     // (gemm.h) validated and selected; the products of this pass are plain ones
+  const BwdArgs a{c, P, st, ws, d_logits, G ? *G : gic_disc_grads{}, train ? (const uint8_t*)st->keep : nullptr, stream};
   if (G && !accumulate) {   // atomically-accumulated small grads start from zero
     GIC_PROPAGATE(fill_zero(G->o2l_w, kOutDim * sizeof(float), stream));
     GIC_PROPAGATE(fill_zero(G->o2l_b, sizeof(float), stream));
@@ -817,24 +999,9 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
     }
     if (inp_ids) GIC_PROPAGATE(fill_zero(G->emb, (size_t)c.De * c.V * sizeof(float), stream));
   }
-  // 1. out2logits backward
-  // deterministic mode: the blocks' partials of the output-layer gradients go to ws->dydrop (free until step 2 writes it, MR * Fp
-  // floats) and are folded in block order, with as many blocks as it holds partials for (the kernel strides its rows over the grid);
-  // room for one block only: that block adds into the zeroed / accumulated gradient alone (one add per address, no order).  The conv
-  // weight gradients (step 4) and the column sums reuse dydrop / dh the same way (each free at that point).
-  const bool det = G && det_mode();
-  const long dy_floats = MR * c.Fp;
-  int out_blocks = 256;
-  if (det && (long)out_blocks * (kOutDim + 1) > dy_floats) out_blocks = (int)(dy_floats / (kOutDim + 1));
-  if (out_blocks < 1) out_blocks = 1;
-  const bool out_part = det && out_blocks > 1;
-  hipLaunchKernelGGL((disc_out_bwd_kernel<TA>), dim3(out_blocks), dim3(256), 0, stream, d_logits, (const float*)st->feat, P->o2l_w,
-                     (TA*)ws->dfeat, G ? G->o2l_w : nullptr, G ? G->o2l_b : nullptr, MR, out_part ? ws->dydrop : nullptr);
-  GIC_CHECK_LAUNCH("disc_out_bwd");
-  if (out_part) {
-    hipLaunchKernelGGL(disc_out_fold_kernel, dim3(1), dim3(128), 0, stream, (const float*)ws->dydrop, out_blocks, G->o2l_w, G->o2l_b);
-    GIC_CHECK_LAUNCH("disc_out_fold");
-  }
+  // 1. out2logits backward.  Deterministic mode: its partials live in ws->dydrop, free until step 2 writes it, and are folded here.  The
+  // conv weight gradients (step 4) and the column sums reuse dydrop / dh the same way (each free at that point).
+  GIC_PROPAGATE(launch_disc_out_bwd<TA>(plan, a));
   // 1b. conditioned D (disc_cond.hip): the match term's share of dydrop and d_q.  Behind disc_out_fold: the deterministic mode's
   // partials of step 1 lived in dydrop until then.  The feature2out product below then adds onto it
   if (cond_q)
@@ -856,17 +1023,7 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
     }
   }
   // 3. highway backward
-  const bool hb_vec = MR * c.Fp / 8 < (1l << 31) && ((((uintptr_t)ws->dydrop) | ((uintptr_t)st->hpre) | ((uintptr_t)st->pooled) | ((uintptr_t)ws->dh) |
-                                                     ((uintptr_t)ws->dpooled)) & 15) == 0 && (!train || (((uintptr_t)st->keep) & 7) == 0);
-  if (hb_vec)
-    hipLaunchKernelGGL((disc_highway_bwd_vec_kernel<TA>), dim3(grid1d(MR * c.Fp / 8)), dim3(256), 0, stream, (const float*)ws->dydrop,
-                       train ? (const uint8_t*)st->keep : nullptr, c.keep_scale(train), (const float*)st->hpre,
-                       (const TA*)st->pooled, (TA*)ws->dh, ws->dpooled, (unsigned)(MR * c.Fp / 8), c.F, c.Fp / 8);
-  else
-    hipLaunchKernelGGL((disc_highway_bwd_kernel<TA>), dim3(grid1d(MR * c.Fp)), dim3(256), 0, stream, (const float*)ws->dydrop,
-                       train ? (const uint8_t*)st->keep : nullptr, c.keep_scale(train), (const float*)st->hpre,
-                       (const TA*)st->pooled, (TA*)ws->dh, ws->dpooled, MR, c.F, c.Fp);
-  GIC_CHECK_LAUNCH("disc_highway_bwd");
+  GIC_PROPAGATE(launch_disc_highway_bwd<TA>(plan, a));
   {
     GemmDesc g;   // dpooled += dh hw_w
     g.A = ws->dh; g.lda = c.Fp; g.a_kc = 1; g.B = S->hw_w_t ? S->hw_w_t : S->hw_w; g.ldb = c.Fp; g.b_kc = S->hw_w_t ? 1 : 0;
@@ -884,87 +1041,23 @@ int disc_bwd_t(const DCtx& c, const gic_disc_params* P, const gic_disc_shadow* S
       if (!folded) GIC_PROPAGATE(colsum(ws->dh, c.dt, c.Fp, MR, c.F, G->hw_b, nullptr, accumulate, stream, ws->dydrop, (long)(MR * c.Fp)));
     }
   }
-  // 4. conv / pool backward
+  // 4. conv / pool backward (deterministic mode: the weight gradient's block-row partials live in ws->dydrop, free again, and are folded)
+  if (plan.wgrad) GIC_PROPAGATE(launch_disc_bwd_w<TA>(plan, a));
+  GIC_PROPAGATE(launch_disc_bwd_x<TA>(plan, a));
+  // 5. embedding backward.  Rows that came in as token ids scatter (G->emb zeroed above or accumulated into), soft rows go through the
+  // product.  A mixed batch (one backward for the step's real and fake passes) has both: ids for the first half of the captions
   if (G) {
-    int gy = cdiv(MR, 4 * 8);
-    gy = gy > 64 ? 64 : gy;
-    int mt = 0;
-    for (int k = 0; k < c.cm.nconv; ++k) mt = c.cm.fsize[k] * c.s > mt ? c.cm.fsize[k] * c.s : mt;
-    static const bool no_lds = getenv("GIC_NO_DISC_BWDW_LDS") != nullptr;
-    const bool lds = mt <= 8 && c.s == 1 && c.R <= 64 && c.R <= c.De && MR % c.R == 0 && c.L <= 64 && !no_lds;
-    const int ncap = (int)(MR / c.R);
-    const int mt1 = (mt <= 8 ? 8 : kMaxTaps) + 1;
-    int rows_y = lds ? (ncap < 64 ? ncap : 64) : gy;
-    // deterministic mode: as many block rows as dydrop holds partials for (the kernels stride over gridDim.y); one block row adds
-    // alone (one add per address)
-    if (det && (long)rows_y * c.F * mt1 > dy_floats) rows_y = (int)(dy_floats / ((long)c.F * mt1));
-    if (rows_y < 1) rows_y = 1;
-    gy = lds ? gy : rows_y;
-    float* part = det && rows_y > 1 ? ws->dydrop : nullptr;
-    if (lds) {
-      hipLaunchKernelGGL((disc_conv_pool_bwd_w_lds_kernel<TA, 8>), dim3(cdiv(c.F, 64), rows_y), dim3(256),
-                         (size_t)c.R * ((c.L + 8) | 1) * sizeof(float), stream, (const float*)ws->dpooled, (const TA*)st->pooled,
-                         (const uint8_t*)st->argmax, (const float*)st->emb, c.cm, c.L, c.De, c.R, ncap, part);
-    } else if (mt <= 8)
-      hipLaunchKernelGGL((disc_conv_pool_bwd_w_kernel<TA, 8>), dim3(cdiv(c.F, 64), gy), dim3(256), 0, stream, (const float*)ws->dpooled,
-                         (const TA*)st->pooled, (const uint8_t*)st->argmax, (const float*)st->emb, c.cm, c.L, c.De, c.R, MR, part);
-    else
-      hipLaunchKernelGGL((disc_conv_pool_bwd_w_kernel<TA, kMaxTaps>), dim3(cdiv(c.F, 64), gy), dim3(256), 0, stream, (const float*)ws->dpooled,
-                         (const TA*)st->pooled, (const uint8_t*)st->argmax, (const float*)st->emb, c.cm, c.L, c.De, c.R, MR, part);
-    GIC_CHECK_LAUNCH("disc_conv_pool_bwd_w");
-    if (part) {
-      hipLaunchKernelGGL(disc_wgrad_fold_kernel, dim3(cdiv((long)c.F * mt1, 256)), dim3(256), 0, stream, (const float*)ws->dydrop, rows_y, mt1, c.cm);
-      GIC_CHECK_LAUNCH("disc_wgrad_fold");
-    }
-  }
-  const int n_out = c.L * c.s;
-  size_t conv_w_total = 0;
-  for (int k = 0; k < c.cm.nconv; ++k) conv_w_total += (size_t)c.cm.nfilt[k] * c.cm.fsize[k] * c.s;
-  const size_t bwd_x_lds = ((size_t)3 * c.Fp + (size_t)(n_out >= 256 ? 1 : 256 / n_out) * n_out + conv_w_total) * sizeof(float);
-  GIC_CHECK_ARG(bwd_x_lds <= 160 * 1024, "disc_bwd: conv weights (%zu floats) do not fit the LDS staging", conv_w_total);
-  int max_taps_x = 0;
-  for (int k = 0; k < c.cm.nconv; ++k) max_taps_x = c.cm.fsize[k] * c.s > max_taps_x ? c.cm.fsize[k] * c.s : max_taps_x;
-  if (n_out <= 32 && c.F <= 1024 && max_taps_x <= 8) {
-    static const int rpb_env = [] { const char* e = getenv("GIC_BWDX_RPB"); return e ? atoi(e) : 0; }();
-    const int rpb = rpb_env > 0 ? rpb_env : (MR >= 2048 ? 4 : 1);                // rows per block
-    hipLaunchKernelGGL((disc_conv_pool_bwd_x_small_kernel<TA, 32, 8>), dim3((unsigned)cdiv(MR, rpb)), dim3(256), (size_t)n_out * 256 * sizeof(float), stream,
-                       (const float*)ws->dpooled, (const TA*)st->pooled, (const uint8_t*)st->argmax, c.cm, c.L, c.De, c.R,
-                       (TA*)ws->demb, (int)MR, rpb);
-  } else {
-    hipLaunchKernelGGL((disc_conv_pool_bwd_x_kernel<TA>), dim3((unsigned)MR), dim3(256), bwd_x_lds, stream,
-                       (const float*)ws->dpooled, (const TA*)st->pooled, (const uint8_t*)st->argmax, c.cm, c.L, c.De, c.R, (TA*)ws->demb);
-  }
-  GIC_CHECK_LAUNCH("disc_conv_pool_bwd_x");
-  // 5. embedding backward
-  if (G) {
-    if (inp_ids && inp_soft) {
-      // mixed batch (one backward for the step's real and fake passes): the first half of the captions came in as token ids,
-      // the second half as soft rows; the gathered half scatters first (G->emb zeroed above or accumulated into)
-      const long half = c.rowsBL / 2;
-      if (det_mode()) {
-        GIC_PROPAGATE(det_scatter(ws->demb, c.dt, c.De, 0, inp_ids, (int)half, 1, 0, half, G->emb, 1, c.V, c.De, c.V, stream));
-      } else {
-        hipLaunchKernelGGL(disc_emb_scatter_kernel, dim3(grid1d(half * c.De)), dim3(256), 0, stream, (const float*)nullptr,
-                           (const void*)ws->demb, c.dt, inp_ids, G->emb, half, c.De, c.V);
-        GIC_CHECK_LAUNCH("disc_emb_scatter");
-      }
-      GemmDesc w;   // dW_emb[De, V] += demb[half:]^T inp
-      w.A = (const char*)ws->demb + (size_t)half * c.De * dtype_size(c.dt); w.lda = c.De; w.a_kc = 0; w.B = inp_soft; w.ldb = ld_inp; w.b_kc = 0;
+    const long id_rows = !inp_ids ? 0 : (inp_soft ? c.rowsBL / 2 : c.rowsBL);
+    if (id_rows && det_mode())
+      GIC_PROPAGATE(det_scatter(ws->demb, c.dt, c.De, 0, inp_ids, (int)id_rows, 1, 0, id_rows, G->emb, 1, c.V, c.De, c.V, stream));
+    else if (id_rows)
+      GIC_PROPAGATE(launch("disc_emb_scatter", disc_emb_scatter_kernel, {(unsigned)grid1d(id_rows * c.De)}, stream, nullptr, ws->demb, c.dt, inp_ids, G->emb,
+                           id_rows, c.De, c.V));
+    if (inp_soft) {
+      GemmDesc w;   // dW_emb[De, V] (+)= demb[id_rows:]^T inp
+      w.A = (const char*)ws->demb + (size_t)id_rows * c.De * dtype_size(c.dt); w.lda = c.De; w.a_kc = 0; w.B = inp_soft; w.ldb = ld_inp; w.b_kc = 0;
       w.C = G->emb; w.ldc = c.V;
-      w.M = c.De; w.N = c.V; w.K = (int)half; w.in_dtype = c.dt; w.out_dtype = DT_F32; w.accumulate = 1;
-      GIC_PROPAGATE(gemm(w, stream));
-    } else if (inp_ids) {
-      if (det_mode()) {
-        GIC_PROPAGATE(det_scatter(ws->demb, c.dt, c.De, 0, inp_ids, (int)c.rowsBL, 1, 0, c.rowsBL, G->emb, 1, c.V, c.De, c.V, stream));
-      } else {
-        hipLaunchKernelGGL(disc_emb_scatter_kernel, dim3(grid1d(c.rowsBL * c.De)), dim3(256), 0, stream, (const float*)nullptr,
-                           (const void*)ws->demb, c.dt, inp_ids, G->emb, c.rowsBL, c.De, c.V);
-        GIC_CHECK_LAUNCH("disc_emb_scatter");
-      }
-    } else {
-      GemmDesc w;   // dW_emb[De, V] = demb^T inp
-      w.A = ws->demb; w.lda = c.De; w.a_kc = 0; w.B = inp_soft; w.ldb = ld_inp; w.b_kc = 0; w.C = G->emb; w.ldc = c.V;
-      w.M = c.De; w.N = c.V; w.K = (int)c.rowsBL; w.in_dtype = c.dt; w.out_dtype = DT_F32; w.accumulate = accumulate;
+      w.M = c.De; w.N = c.V; w.K = (int)(c.rowsBL - id_rows); w.in_dtype = c.dt; w.out_dtype = DT_F32; w.accumulate = id_rows ? 1 : accumulate;
       GIC_PROPAGATE(gemm(w, stream));
     }
   }
@@ -1097,6 +1190,19 @@ int gic_disc_bwd_cond(const gic_disc_dims* dims, const gic_disc_params* P, const
                       float* d_q, void* stream) {
   return disc_bwd_entry("disc_bwd_cond", dims, P, S, st, ws, inp_soft, ld_inp, inp_ids, train, d_logits, G, accumulate, d_inp, ld_dinp, q, scale,
                         d_q, stream);
+}
+
+int gic_debug_disc_plan(const gic_disc_dims* dims, int flags, char* out, int64_t out_len) {
+  DCtx c;
+  GIC_PROPAGATE(make_ctx(dims, nullptr, nullptr, c));
+  GIC_CHECK_ARG(out && out_len > 0, "debug_disc_plan: no output buffer");
+  GIC_CHECK_ARG((flags & ~15) == 0, "debug_disc_plan: unknown flag in %d", flags);
+  DiscFwdPlan f;
+  DiscBwdPlan b;
+  select_disc_fwd(c, !(flags & GIC_DISC_PLAN_NO_ARGMAX), f);
+  const bool hw_aligned = !(flags & GIC_DISC_PLAN_HW_UNALIGNED);
+  GIC_PROPAGATE(select_disc_bwd(c, (flags & GIC_DISC_PLAN_GRADS) != 0, det_mode(), (flags & GIC_DISC_PLAN_TRAIN) != 0, hw_aligned, hw_aligned, b));
+  return plan_lines(c, f, b, out, (size_t)out_len);
 }
 
 }  // extern "C"

@@ -133,7 +133,9 @@ void wgrad_launch_counts(long* launches, long* two_matrix);
 
 // Route-only mode (gic_debug_route_only, util.hip): gemm(), gemm_gumbelmax() and gic_conv_b2b validate and select, write the plan as one
 // line into route_line() and return their status without touching the GPU.  gic_disc_fwd (disc.hip) answers with the selection of its
-// highway product, the one caller of EPI_HIGHWAY, and launches none of its own kernels.
+// highway product, the one caller of EPI_HIGHWAY, and launches none of its own kernels.  gic_disc_bwd, gic_disc_bwd_cond and
+// gic_disc_fwd_redrop validate, run select_disc_bwd (the pair of this convention in disc.hip; gic_debug_disc_plan prints its plans) and
+// return before their first launch or product.
 bool route_only();
 char* route_line();                    // thread-local, kRouteLen bytes
 constexpr int kRouteLen = 160;

@@ -1510,6 +1510,15 @@ class DiscEngine:
         d.F, d.Fp, d.dtype, d.drop_p = self.F, self.Fp, self.dt, self.drop_p
         return d
 
+    def plan(self, B: int, Lc: int, want_param_grads: bool = True, train: bool = True, keeps_argmax: bool = True, hw_aligned: bool = True):
+        """gic_debug_disc_plan: the kernels gic_disc_fwd / gic_disc_bwd select for these shapes in the library's current deterministic
+        mode, one line per launch (line 0: the forward's conv + pool kernel).  Host-only."""
+        flags = (0 if keeps_argmax else L.DISC_PLAN_NO_ARGMAX) | (L.DISC_PLAN_GRADS if want_param_grads else 0) | \
+                (L.DISC_PLAN_TRAIN if train else 0) | (0 if hw_aligned else L.DISC_PLAN_HW_UNALIGNED)
+        out = C.create_string_buffer(2048)
+        L.check(L.load().gic_debug_disc_plan(C.byref(self.dims(B, Lc)), flags, out, len(out)), "gic_debug_disc_plan")
+        return out.value.decode().splitlines()
+
     def _pstruct(self, params, cls=L.DiscParams):
         n = len(self.fs)
         s = cls()

@@ -52,7 +52,10 @@ const char* gic_last_error(void);
  * validate their arguments, select a kernel and return the status they would return -- GIC_STATUS_UNSUPPORTED included -- WITHOUT touching
  * the GPU (pointers are only checked for null and alignment).  gic_debug_last_route() is this thread's last selection as one line: the
  * kernel with its template arguments, grid, block, dynamic LDS bytes and, for the 4-wave kernel, splits / per / pipe, e.g.
- * "tile8<bf16,128,2,true,2,true,false,1024> grid=1568 block=512 lds=0"; "unsupported" when nothing was selected. */
+ * "tile8<bf16,128,2,true,2,true,false,1024> grid=1568 block=512 lds=0"; "unsupported" when nothing was selected.
+ * The sequence discriminator's entry points honour it too: gic_disc_fwd answers with the selection of its highway product; gic_disc_bwd,
+ * gic_disc_bwd_cond and gic_disc_fwd_redrop validate, select their own kernels (gic_debug_disc_plan prints that selection) and return
+ * their status without a launch, the route line left as it was. */
 void gic_debug_route_only(int on);
 const char* gic_debug_last_route(void);
 /* Host-only: what the selection answers the library's own weight-gradient call sites (dW = dy^T x with the bias gradient as the column
@@ -849,6 +852,20 @@ int gic_disc_bwd(const gic_disc_dims* dims, const gic_disc_params* params, const
                  const gic_disc_state* state, const gic_disc_bwd_ws* ws, const void* inp_soft, int64_t ld_inp,
                  const int64_t* inp_ids, int train, const float* d_logits, const gic_disc_grads* grads,
                  int accumulate, void* d_inp, int64_t ld_dinp, void* stream);
+
+/* (an addition to ABI v5) Host-only: the kernels gic_disc_fwd and gic_disc_bwd / gic_disc_bwd_cond launch of their own for these dims (the
+ * library's very selection, csrc/disc.hip select_disc_fwd / select_disc_bwd; their GEMMs are gic_gemm's business), one line per launch in
+ * launch order, '\n'-terminated, written to out (out_len bytes, the terminating 0 included): the kernel with its template arguments,
+ * grid= (workgroups), block=, lds= (dynamic bytes) as in gic_debug_last_route, and where they apply blocks= / rows_y= with part= (1: the
+ * deterministic mode's partials are written and folded; the fold is the next line) and rpb= (rows per block).  Line 0 is the forward's
+ * conv + pool kernel, the others the backward's.  flags: GIC_DISC_PLAN_* below.  The deterministic mode is the library's current one.
+ * Never touches the GPU and looks at no pointer (dims->B .. drop_p are validated as gic_disc_fwd validates them).
+ * GIC_STATUS_INVALID_ARG: bad dims, the conv weights do not fit gic_disc_bwd's LDS staging (its message), out too small. */
+#define GIC_DISC_PLAN_NO_ARGMAX 1      /* the forward keeps no argmax (state->argmax == NULL: no backward follows); line 0 only */
+#define GIC_DISC_PLAN_GRADS 2          /* parameter gradients wanted (grads != NULL) */
+#define GIC_DISC_PLAN_TRAIN 4          /* train != 0 */
+#define GIC_DISC_PLAN_HW_UNALIGNED 8   /* a buffer of the highway backward is off its 16-byte (keep: 8-byte) alignment */
+int gic_debug_disc_plan(const gic_disc_dims* dims, int flags, char* out, int64_t out_len);
 
 /* Image-conditioned discriminator (--disc-cond projection; no reference counterpart): the projection match term
  *   logits[m] (+)= scale * sum_{n<F} ydrop[m, n] * q[m / R, n]       q: f32 [B, F], one row per caption; scale = F^-1/2

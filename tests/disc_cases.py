@@ -1,5 +1,5 @@
 """The sequence discriminator (csrc/disc.hip) stage by stage: the case table, the fp64 reference of every stage, the per-element bounds
-and the checker behind tests/test_disc_cases.py (no GPU: route pins, selection restatement, checker self-test) and
+and the checker behind tests/test_disc_cases.py (no GPU: route pins, the selection restated and held to the library's own, checker self-test) and
 tests/test_gpu_disc_stages.py (which runs every case on the GPU).  Nothing here touches the GPU.
 
 Every stage is checked against an fp64 reference formed from the buffers the kernels themselves wrote upstream of it (`emb`, `pooled`,
@@ -74,7 +74,8 @@ class Case(NamedTuple):
 
 
 def select(case):
-    """disc_fwd_t's and disc_bwd_t's choice of convolution kernels, restated: (fwd, bwd_x, bwd_w)."""
+    """select_disc_fwd's and select_disc_bwd's choice of convolution kernels (csrc/disc.hip), restated without the library: (fwd, bwd_x,
+    bwd_w).  tests/test_disc_cases.py::test_library_plan_is_the_restated_selection holds it to gic_debug_disc_plan on every case."""
     s, MR = case.s, case.MR
     mt = max(f * s for f in case.fs)
     assert mt <= K_MAX_TAPS and case.L <= 255 and all(1 <= f <= case.L for f in case.fs)
@@ -95,21 +96,22 @@ def select(case):
     return fwd, bwd_x, bwd_w
 
 
-def det_plan(case):
-    """Deterministic mode's grids in disc_bwd_t: (blocks of disc_out_bwd, whether their partials are folded, block rows of the conv
-    weight gradient, whether theirs are): what `dydrop` (MR * Fp floats) has room for."""
+def det_plan(case, det=True):
+    """select_disc_bwd's grids, restated without the library (held to it by the same test as `select`): (blocks of disc_out_bwd, whether
+    their partials are folded, block rows of the conv weight gradient, whether theirs are).  Deterministic mode: what `dydrop` (MR * Fp
+    floats) has room for; det=False: the grids outside it, nothing folded."""
     s, MR = case.s, case.MR
     dy = MR * case.Fp
-    out_blocks = max(1, min(256, dy // (OUT + 1)))
+    out_blocks = max(1, min(256, dy // (OUT + 1))) if det else 256
     mt = max(f * s for f in case.fs)
     lds = select(case)[2] == "lds"
     gy = min(64, -(-MR // 32))
     rows_y = min(MR // case.R, 64) if lds else gy
     mt1 = (8 if mt <= 8 else K_MAX_TAPS) + 1
-    if rows_y * case.F * mt1 > dy:
+    if det and rows_y * case.F * mt1 > dy:
         rows_y = dy // (case.F * mt1)
     rows_y = max(1, rows_y)
-    return out_blocks, out_blocks > 1, rows_y, rows_y > 1
+    return out_blocks, det and out_blocks > 1, rows_y, det and rows_y > 1
 
 
 W5 = ((1, 2, 4, 5, 8), (5, 16, 17, 33, 20))          # nine filter tiles of 16 (the `tile & 7` round robin wraps), five of 32; F = 91
@@ -137,6 +139,10 @@ CASES = (
     + _both("s4-L12", 30, 12, 4, 16, (2, 8), (40, 24), "scalar32", "general", "w32", det=True)
     # 5. F > 1024 leaves the four-filters-per-thread bwd_x_small
     + _both("f1030", 2, 4, 4, 4, (1,), (1030,), "mfma", "general", "lds")
+    # 5b. the general bwd_x past 64 KB of dynamic LDS, which its launcher asks the grant for (common.h grant_lds): geff, tst, meta [Fp = 1472]
+    # + part [NG = 32][n_out = 8] + the staged weights [1465 * 8] = (3 * 1472 + 256 + 11720) * 4 = 65568 bytes; one filter fewer is 65536,
+    # within the default.  The smallest bank of the width-8 / L = 8 family that crosses it (one window per filter: no ties, no integer regime)
+    + _both("lds-grant", 2, 8, 3, 3, (8,), (1465,), "mfma", "general", "lds", exact=False)
     # 7. no pad columns at all
     + _both("fp8", 3, 11, 24, 24, (1, 2, 4, 5, 8), (5, 16, 17, 30, 20), "mfma", "small1", "lds", fp_align=8)
     # 10. deterministic mode with room in dydrop for one block row only (MR = 5, Fp = 64, F = 40); then for one disc_out_bwd block only

@@ -38,6 +38,24 @@ def test_argument_validation_returns_status_not_crash():
     assert b"null operand" in lib.gic_last_error()
     with pytest.raises(ValueError):
         _lib.check(lib.gic_gan_losses(99, None, None, None, 0, None, None, None, None, None, None, None), "gan_losses")
+    # gic_debug_disc_plan(dims, flags, out, out_len): host-only; dims validated as gic_disc_fwd validates them, then the buffer and the flags
+    assert lib.gic_debug_disc_plan(None, 0, None, 0) == -1
+    assert b"null dims" in lib.gic_last_error()
+    dd = _lib.DiscDims()
+    dd.B, dd.L, dd.V, dd.De, dd.R, dd.nconv, dd.F, dd.Fp, dd.dtype, dd.drop_p = 2, 6, 50, 4, 4, 1, 24, 64, _lib.BF16, 0.2
+    dd.fsize[0], dd.nfilt[0] = 3, 24
+    out = ctypes.create_string_buffer(1024)
+    assert lib.gic_debug_disc_plan(ctypes.byref(dd), 0, None, 1024) == -1 and b"no output buffer" in lib.gic_last_error()
+    assert lib.gic_debug_disc_plan(ctypes.byref(dd), 16, out, 1024) == -1 and b"unknown flag" in lib.gic_last_error()
+    assert lib.gic_debug_disc_plan(ctypes.byref(dd), _lib.DISC_PLAN_GRADS | _lib.DISC_PLAN_TRAIN, out, 1024) == 0
+    lines = out.value.decode().splitlines()
+    assert len(lines) == 5 and all(" grid=" in l and " block=" in l and " lds=" in l for l in lines), lines
+    assert out.value.endswith(b"\n") and lines[0].startswith("disc_conv_pool_fwd_mfma_kernel<bf16> ")
+    need = len(out.value) + 1                           # the terminating 0 included: one byte less is refused, nothing beyond out_len written
+    small = ctypes.create_string_buffer(b"\x7f" * (need + 8), need + 8)
+    assert lib.gic_debug_disc_plan(ctypes.byref(dd), _lib.DISC_PLAN_GRADS | _lib.DISC_PLAN_TRAIN, small, need - 1) == -1
+    assert b"out_len" in lib.gic_last_error() and small.raw[need - 1:] == b"\x7f" * 9
+    assert lib.gic_debug_disc_plan(ctypes.byref(dd), _lib.DISC_PLAN_GRADS | _lib.DISC_PLAN_TRAIN, small, need) == 0 and small.value == out.value
     d = _lib.DecoderDims(4, 5, 50, 8, 16, 9, 0)          # NL out of range
     assert lib.gic_decoder_prepare(ctypes.byref(d), None, None, None) == -1
     assert b"gen_num_layers" in lib.gic_last_error()

@@ -1,7 +1,10 @@
-"""The discriminator case table (tests/disc_cases.py) without a GPU: every case names the convolution kernels disc_fwd_t / disc_bwd_t
-select for it (a pure restatement of their conditions, so a changed threshold has to move the table deliberately), every highway route
-the scan reaches is pinned on one small shape, the integer regime of every case really has ties and zeros, and the checker flags the
+"""The discriminator case table (tests/disc_cases.py) without a GPU: every case names the convolution kernels select_disc_fwd /
+select_disc_bwd (csrc/disc.hip) take for it -- by a Python restatement of their conditions AND by the library's own plan
+(gic_debug_disc_plan), which must agree in both modes of gic_set_deterministic, so a threshold that moves in either has to move the table
+deliberately and the table's coverage of every variant is the library's --, every highway route the scan reaches is pinned on one small shape, the integer regime of every case really has ties and zeros, and the checker flags the
 failures this kernel family can have, each at the stage it belongs to."""
+import ctypes
+
 import pytest
 import torch
 
@@ -23,6 +26,68 @@ def test_ids_are_unique():
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_case_names_the_kernels_the_selection_takes(case):
     assert D.select(case) == (case.fwd, case.bwd_x, case.bwd_w)
+
+
+def dims_of(case):
+    d = L.DiscDims()
+    d.B, d.L, d.V, d.De, d.R, d.nconv = case.B, case.L, case.V, case.De, case.R, len(case.fs)
+    for k, (f, n) in enumerate(zip(case.fs, case.nf)):
+        d.fsize[k], d.nfilt[k] = f, n
+    d.F, d.Fp, d.dtype, d.drop_p = case.F, case.Fp, DT[case.dtype], D.DROP_P
+    return d
+
+
+def library_plan(d, flags):
+    """gic_debug_disc_plan's lines (host-only; no pointer is involved)."""
+    out = ctypes.create_string_buffer(2048)
+    status = L.load().gic_debug_disc_plan(ctypes.byref(d), flags, out, len(out))
+    assert status == 0, L.load().gic_last_error()
+    return out.value.decode().splitlines()
+
+
+FWD_KERNEL = {"bf16": "disc_conv_pool_fwd_bf16_kernel<{t}>", "mfma": "disc_conv_pool_fwd_mfma_kernel<{t}>",
+              "scalar8": "disc_conv_pool_fwd_kernel<{t},8>", "scalar32": "disc_conv_pool_fwd_kernel<{t},32>"}
+BWD_W_KERNEL = {"lds": "disc_conv_pool_bwd_w_lds_kernel<{t},8>", "w8": "disc_conv_pool_bwd_w_kernel<{t},8>", "w32": "disc_conv_pool_bwd_w_kernel<{t},32>"}
+BWD_X_KERNEL = {"small1": ("disc_conv_pool_bwd_x_small_kernel<{t},32,8>", " rpb=1"), "small4": ("disc_conv_pool_bwd_x_small_kernel<{t},32,8>", " rpb=4"),
+                "general": ("disc_conv_pool_bwd_x_kernel<{t}>", "")}
+
+
+def kernel_and_extras(line):
+    """'kernel<..> grid=.. block=.. lds=.. extras' -> (kernel, ' extras')."""
+    head, _, tail = line.partition(" lds=")
+    return head.split(" grid=")[0], tail.partition(" ")[1] + tail.partition(" ")[2]
+
+
+@pytest.mark.parametrize("det", [False, True], ids=["", "det"])
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
+def test_library_plan_is_the_restated_selection(case, det):
+    """The library's own selection (gic_debug_disc_plan = make_ctx + select_disc_fwd + select_disc_bwd) names exactly the kernels, rows
+    per block, disc_out_bwd blocks, weight-gradient block rows and fold launches that D.select / D.det_plan restate, in both modes of
+    gic_set_deterministic: neither side can drift alone, and test_table_reaches_every_kernel_and_edge speaks for the library."""
+    t = case.dtype
+    fwd, bwd_x, bwd_w = D.select(case)
+    engine.set_deterministic(det)
+    try:
+        if case.forward_only:
+            lines = library_plan(dims_of(case), L.DISC_PLAN_NO_ARGMAX)
+            assert kernel_and_extras(lines[0]) == (FWD_KERNEL[fwd].format(t=t), "")
+            return
+        lines = library_plan(dims_of(case), L.DISC_PLAN_GRADS | L.DISC_PLAN_TRAIN)
+        no_grads = library_plan(dims_of(case), L.DISC_PLAN_TRAIN | L.DISC_PLAN_HW_UNALIGNED)
+    finally:
+        engine.set_deterministic(False)
+    out_blocks, out_fold, rows_y, w_fold = D.det_plan(case, det)
+    xk, xe = BWD_X_KERNEL[bwd_x]
+    want = [(FWD_KERNEL[fwd], ""), ("disc_out_bwd_kernel<{t}>", f" blocks={out_blocks} part={int(out_fold)}")]
+    want += [("disc_out_fold_kernel", "")] * out_fold
+    want += [("disc_highway_bwd_vec_kernel<{t}>", ""), (BWD_W_KERNEL[bwd_w], f" rows_y={rows_y} part={int(w_fold)}")]
+    want += [("disc_wgrad_fold_kernel", "")] * w_fold
+    want += [(xk, xe)]
+    assert [kernel_and_extras(l) for l in lines] == [(k.format(t=t), e) for k, e in want]
+    # the generator's path (no parameter gradients: no weight gradient, nothing folded in either mode), `dh` off its alignment
+    assert [kernel_and_extras(l) for l in no_grads] == [(k.format(t=t), e) for k, e in
+                                                       [(FWD_KERNEL[fwd], ""), ("disc_out_bwd_kernel<{t}>", " blocks=256 part=0"),
+                                                        ("disc_highway_bwd_kernel<{t}>", ""), (xk, xe)]]
 
 
 def test_table_reaches_every_kernel_and_edge():

@@ -20,6 +20,7 @@ from gan_image_captioning_amd import engine
 P = 0x7F0000010000          # a fake, aligned, non-null device pointer
 BF16, F32 = L.BF16, L.F32
 UNSUPPORTED = L.ERR_UNSUPPORTED
+INVALID_ARG = -1            # gic_status GIC_STATUS_INVALID_ARG
 
 
 def conv2d(N, H, cin, cout, k, stride, pad, W=None, kw=None, dtype=BF16):
@@ -242,6 +243,121 @@ def test_highway_off_its_row_padded_form_takes_the_4_wave_kernel(state):
     assert kernel_and_grid(line) == "gemm<bf16,bf16,true,true,128,128,true,1,false,true> grid=256x1 block=256"     # (K = 15 tiles over 256 blocks: the LDS-DMA ring)
     status, line = route(disc_fwd(4096, 1))
     assert status == 0 and line.startswith("tile8<bf16,128,1,"), line
+
+
+# ---------------------------------------------------------------------------------------------------------------- the discriminator's own kernels
+def disc_dims(rows, dtype=BF16, L_=20, fs=(3, 4, 5), nf=(300, 300, 300), R=64, fp_align=64):
+    """cfg2's discriminator as bench.py builds it (default_args: disc_embed_dim = disc_num_rep = 64, filter sizes 3 / 4 / 5 with 300 filters
+    each, captions of 20 tokens, 10000 words; Fp = F rounded up to 64 columns) over rows = B * 64 feature rows."""
+    d = L.DiscDims()
+    d.B, d.L, d.V, d.De, d.R, d.nconv = rows // R, L_, 10000, R, R, len(fs)
+    for k, (f, n) in enumerate(zip(fs, nf)):
+        d.fsize[k], d.nfilt[k] = f, n
+    d.F = sum(nf)
+    d.Fp, d.dtype, d.drop_p = (d.F + fp_align - 1) // fp_align * fp_align, dtype, 0.2
+    return d
+
+
+def disc_plan(d, flags):
+    import ctypes
+    out = ctypes.create_string_buffer(2048)
+    status = L.load().gic_debug_disc_plan(ctypes.byref(d), flags, out, len(out))
+    return status, out.value.decode().splitlines()
+
+
+# (kernel, workgroups at 4096 rows, at 8192 rows, workgroup size, dynamic LDS bytes); the LDS figure is the parent's launch-site expression
+# at L = 20, s = 1, R = 64, worked out by hand:
+CFG2_DISC_FWD_TRAIN = ("disc_conv_pool_fwd_mfma_kernel<bf16>", "256", "512", 512, 0)             # `0`: the kernel's LDS is static
+CFG2_DISC_FWD_ONLY = ("disc_conv_pool_fwd_bf16_kernel<bf16>", "128", "256", 512, 13952)          # 32 * L * 16 + 32 * (L + 9) * 4 = 10240 + 3712
+CFG2_DISC_BWD = [
+    ("disc_out_bwd_kernel<bf16>", "256", "256", 256, 0),                                          # `0`
+    ("disc_out_fold_kernel", "1", "1", 128, 0),                                                   # `0`; deterministic mode only
+    ("disc_highway_bwd_vec_kernel<bf16>", "1920", "2048", 256, 0),                                # `0`
+    ("disc_conv_pool_bwd_w_lds_kernel<bf16,8>", "15x64", "15x64", 256, 7424),                     # R * ((L + 8) | 1) * sizeof(float) = 64 * 29 * 4
+    ("disc_wgrad_fold_kernel", "32", "32", 256, 0),                                               # `0`; deterministic mode only
+    ("disc_conv_pool_bwd_x_small_kernel<bf16,32,8>", "1024", "2048", 256, 20480),                 # n_out * 256 * sizeof(float) = 20 * 256 * 4
+]
+FOLDS = ("disc_out_fold_kernel", "disc_wgrad_fold_kernel")
+
+
+@pytest.mark.parametrize("rows", [4096, 8192])
+def test_cfg2_discriminator_plan(rows):
+    """The kernels gic_disc_fwd / gic_disc_bwd launch of their own for the bench.py cfg2 discriminator, per mode, as gic_debug_disc_plan
+    (the library's select_disc_fwd / select_disc_bwd) prints them.  Kernel names with their template arguments, grids and workgroup
+    sizes are rows of ONE rocprofv3 --kernel-trace run (no counters, MI355X) of the commit before selection and launch were separated in
+    csrc/disc.hip: an eager DiscEngine.fwd + .bwd (token ids, parameter gradients) per mode -- train, forward-only (eval, no saved state),
+    deterministic -- at B = 64 and 128; the rows are kept in profiles/disc_plan_trace.txt (Grid_Size / Workgroup_Size = workgroups).
+    The trace does not report dynamic LDS: each figure is that commit's launch-site expression, quoted beside its value above.
+    Outside the deterministic mode nothing is folded; in it both partial sums are (dydrop's 4096 * 960 floats hold 256 * 101 and
+    64 * 900 * 9 of them), and rpb = 4 from 2048 rows on."""
+    col = 1 if rows == 4096 else 2
+    line = lambda r, extra="": f"{r[0]} grid={r[col]} block={r[3]} lds={r[4]}{extra}"
+    bwd = lambda det: [line(r, {0: f" blocks=256 part={det}", 3: f" rows_y=64 part={det}", 5: " rpb=4"}.get(i, ""))
+                       for i, r in enumerate(CFG2_DISC_BWD) if det or r[0] not in FOLDS]
+    d = disc_dims(rows)
+    assert disc_plan(d, L.DISC_PLAN_GRADS | L.DISC_PLAN_TRAIN) == (0, [line(CFG2_DISC_FWD_TRAIN)] + bwd(0))
+    status, lines = disc_plan(d, L.DISC_PLAN_NO_ARGMAX)
+    assert status == 0 and lines[0] == line(CFG2_DISC_FWD_ONLY)
+    eng = engine.DiscEngine(10000, 64, 64, [3, 4, 5], [300, 300, 300], BF16)                  # the Python wrapper: the same lines
+    assert eng.plan(rows // 64, 20) == [line(CFG2_DISC_FWD_TRAIN)] + bwd(0)
+    assert eng.plan(rows // 64, 20, want_param_grads=False, train=False, keeps_argmax=False)[0] == line(CFG2_DISC_FWD_ONLY)
+    engine.set_deterministic(True)
+    try:
+        assert disc_plan(d, L.DISC_PLAN_GRADS | L.DISC_PLAN_TRAIN) == (0, [line(CFG2_DISC_FWD_TRAIN)] + bwd(1))
+        # the generator's path through D (no parameter gradients): nothing to fold in either mode, no weight gradient
+        assert disc_plan(d, L.DISC_PLAN_TRAIN)[1] == [line(CFG2_DISC_FWD_TRAIN)] + [l for l in bwd(0) if "bwd_w" not in l]
+    finally:
+        engine.set_deterministic(False)
+
+
+def fake(struct):
+    for name, ctype in struct._fields_:
+        setattr(struct, name, P if ctype is L.c_void_p else ctype(*[P] * ctype._length_))
+    return struct
+
+
+def disc_bwd_call(d, grads=True):
+    import ctypes
+    g = ctypes.byref(fake(L.DiscGrads())) if grads else None
+    return ("gic_disc_bwd", (d, fake(L.DiscParams()), fake(L.DiscShadow()), fake(L.DiscState()), fake(L.DiscBwdWs()), None, 0, P, 1, P, g, 0, None, 0, None))
+
+
+def test_conv_weights_beyond_the_lds_staging_are_refused():
+    """The general input-gradient kernel stages every conv weight in LDS beside 3 * Fp + NG * n_out floats (256 at L * s = 32): 1168
+    filters of 32 taps (s = 1, L = 32: f * s <= 32, f <= L and nconv <= 8 hold, make_ctx accepts the bank; Fp = F) come to 3504 + 256 +
+    37376 = 41136 floats, past the 160 KB = 40960 floats a workgroup can have; 1160 filters to 40856.  The query and the backward
+    (route-only mode: fake pointers) refuse the first with select_disc_bwd's message."""
+    lib = L.load()
+    d = disc_dims(64, L_=32, fs=(32,), nf=(1168,), fp_align=8)
+    assert lib.gic_disc_state_bytes(d, (L.C.c_uint64 * 7)()) == 0                      # make_ctx's own limits do not refuse it
+    assert disc_plan(d, L.DISC_PLAN_GRADS | L.DISC_PLAN_TRAIN) == (INVALID_ARG, [])
+    assert lib.gic_last_error() == b"disc_bwd: conv weights (37376 floats) do not fit the LDS staging"
+    assert lib.gic_disc_state_bytes(None, None) == INVALID_ARG                         # (another message in between)
+    assert route(disc_bwd_call(d))[0] == INVALID_ARG
+    assert lib.gic_last_error() == b"disc_bwd: conv weights (37376 floats) do not fit the LDS staging"
+    ok = disc_dims(64, L_=32, fs=(32,), nf=(1160,), fp_align=8)
+    assert disc_plan(ok, L.DISC_PLAN_GRADS)[1][-1] == "disc_conv_pool_bwd_x_kernel<bf16> grid=64 block=256 lds=163424"
+    assert route(disc_bwd_call(ok))[0] == 0
+
+
+def test_route_only_discriminator_backward_and_redrop_launch_nothing():
+    """gic_disc_bwd, gic_disc_bwd_cond and gic_disc_fwd_redrop in route-only mode: validated, selected, status returned -- over fake
+    pointers, on a machine that may have no GPU at all.  (They used to run their fills, column sums and own kernels over them.)"""
+    lib = L.load()
+    d = disc_dims(4096)
+    with engine.route_only() as r:
+        lib.gic_gemm(*gemm(64, 512, 2048, 1, 1, BF16, F32, 0)[1])
+        line = r.last()
+        for grads in (True, False):
+            assert getattr(lib, "gic_disc_bwd")(*disc_bwd_call(d, grads)[1]) == 0, lib.gic_last_error()
+        assert lib.gic_disc_bwd_cond(*disc_bwd_call(d)[1][:-1], P, 0.03, P, None) == 0, lib.gic_last_error()
+        assert lib.gic_disc_fwd_redrop(d, fake(L.DiscParams()), fake(L.DiscShadow()), fake(L.DiscState()), fake(L.DiscState()), 1, None, 1, P,
+                                       None, 0, None) == 0, lib.gic_last_error()
+        assert r.last() == line                                 # none of them selects a product of its own
+        # ... and validation still comes first
+        assert lib.gic_disc_bwd(d, fake(L.DiscParams()), fake(L.DiscShadow()), fake(L.DiscState()), fake(L.DiscBwdWs()), None, 0, None, 1, P, None, 0,
+                                None, 0, None) == INVALID_ARG
+        assert b"pass inp_soft, inp_ids" in lib.gic_last_error()
 
 
 def test_fp32_highway_takes_the_4_wave_kernel():
