@@ -327,6 +327,8 @@ _SIGNATURES = {
     "gic_disc_bwd": (C.c_int, [_P(DiscDims), _P(DiscParams), _P(DiscShadow), _P(DiscState), _P(DiscBwdWs), c_void_p,
                                C.c_int64, c_void_p, C.c_int, c_void_p, _P(DiscGrads), C.c_int, c_void_p, C.c_int64, c_void_p]),
     "gic_debug_disc_plan": (C.c_int, [_P(DiscDims), C.c_int, C.c_char_p, C.c_int64]),
+    "gic_debug_decoder_plan": (C.c_int, [_P(DecoderDims), C.c_int, C.c_char_p, C.c_int64]),
+    "gic_debug_step_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_char_p, C.c_int64]),
     "gic_disc_match_fwd": (C.c_int, [_P(DiscDims), _P(DiscState), c_void_p, C.c_float, C.c_int, c_void_p, c_void_p]),
     "gic_disc_bwd_cond": (C.c_int, [_P(DiscDims), _P(DiscParams), _P(DiscShadow), _P(DiscState), _P(DiscBwdWs), c_void_p,
                                     C.c_int64, c_void_p, C.c_int, c_void_p, _P(DiscGrads), C.c_int, c_void_p, C.c_int64, c_void_p, C.c_float,
@@ -389,6 +391,8 @@ CIDER_MAX_LEN, CIDER_MAX_REFS, CIDER_MAX_VOCAB = 64, 32, 32768      # GIC_CIDER_
 CIDER_PAIR_MAX_K, CIDER_PAIR_SQUARINGS = 32, 16      # GIC_CIDER_PAIR_MAX_K / _SQUARINGS
 OVERLAP_STATS = 10           # GIC_OVERLAP_STATS: clipped 1..4, total 1..4, length, closest reference length
 DISC_PLAN_NO_ARGMAX, DISC_PLAN_GRADS, DISC_PLAN_TRAIN, DISC_PLAN_HW_UNALIGNED = 1, 2, 4, 8      # GIC_DISC_PLAN_*
+(DECODER_PLAN_TRAIN, DECODER_PLAN_PRETRAIN, DECODER_PLAN_DEV_SCALARS, DECODER_PLAN_RESUMED, DECODER_PLAN_NO_PART, DECODER_PLAN_NO_WCAT_T,
+ DECODER_PLAN_STATE_GRADS, DECODER_PLAN_LOGITS_UNALIGNED) = 1, 2, 4, 8, 16, 32, 64, 128      # GIC_DECODER_PLAN_*
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _lib = None
 

@@ -316,13 +316,17 @@ int attn_rollout_run(const ACtx& c, const gic_attn_params* P, const gic_attn_sha
   const long ld = c.ldx();
   const size_t asz = c.asz();
   const RolloutBufs w = rollout_layout(c, rows, ws);
-  {
+  // a step of at least `from` rows takes the fused vocabulary product (the logits scratch holds only the steps below it)
+  RowkeySteps keyed{gumbelmax_from_rows(c), true, false};
+  // route-only mode (gemm.h): the steps' products are selected in launch order; nothing is launched or filled
+  const bool probe = route_only();
+  if (!probe) {
     const long total = (long)rows * L;
     const unsigned grid = (unsigned)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
     hipLaunchKernelGGL(rollout_ids_init_kernel, dim3(grid), dim3(256), 0, stream, caps, force_len, ids, (long)rows, B, L);
     GIC_CHECK_LAUNCH("rollout_ids_init");
   }
-  GIC_PROPAGATE(fill_zero(w.rowkey, (size_t)L * rows * sizeof(unsigned long long), stream));        // atomicMax targets start below every key
+  if (!probe) GIC_PROPAGATE(fill_zero(w.rowkey, (size_t)L * rows * sizeof(unsigned long long), stream));        // atomicMax targets start below every key
   char* xh = (char*)w.xh;
   char* h = xh + (size_t)c.din() * asz;                  // the h columns of row 0
   for (int t = 0; t < L; ++t) {
@@ -342,7 +346,7 @@ int attn_rollout_run(const ACtx& c, const gic_attn_params* P, const gic_attn_sha
       AttnRowsArgs f;
       f.fproj = from->fproj; f.fmap = fmap; f.w_a = P->w_a; f.hp = w.hp; f.z = xh + (size_t)E * asz; f.ldx = ld;
       f.B = B; f.M = Mp; f.P = c.P; f.A = c.A; f.C = c.C;
-      GIC_PROPAGATE(attn_rows(f, c.dt, stream));
+      if (!probe) GIC_PROPAGATE(attn_rows(f, c.dt, stream));
     }
     {
       GemmDesc g;                // gate pre-activations of all M rows
@@ -355,7 +359,7 @@ int attn_rollout_run(const ACtx& c, const gic_attn_params* P, const gic_attn_sha
     const float* u_t = noise_u ? noise_u + (long)t * rows * V : nullptr;
     int s = GIC_ERR_UNSUPPORTED;
     unsigned long long* key = w.rowkey + (long)t * rows;
-    {
+    if (keyed.take(M)) {
       GemmDesc g;                // vocabulary product with Gumbel-max in its epilogue
       g.A = S->wout; g.lda = H; g.B = h; g.ldb = ld;
       g.M = V; g.N = M; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32;

@@ -94,7 +94,7 @@ int decode_dims(DecodeDims& d, int K, bool beam, const char* who) {
   d.K = K;
   d.rows = d.B * K;
   d.nblk = cdiv(d.V, kBeamTile);
-  d.fused = d.attn() || (d.rows <= decoder_step_max_rows() && decoder_step_supported(d.dt, d.V, d.E, d.H, d.NL));
+  d.fused = d.attn() || d.rows <= decoder_fused_rows(d.dt, d.V, d.E, d.H, d.NL);
   return GIC_OK;
 }
 

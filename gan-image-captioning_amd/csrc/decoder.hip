@@ -381,6 +381,18 @@ __global__ __launch_bounds__(256) void rollout_pick_kernel(const unsigned long l
     for (int e = lane; e < E; e += 64) x_next[(long)b * ld_x + e] = from_f32<TA>(embed[(long)id * E + e]);
 }
 
+// layer l's weight gradient as one product: dW_ih | dW_hh over xh = [x | h], the two bias gradients as its A column sums (G null: the
+// selection's copy, whose outputs nothing reads)
+GemmDesc wgrad_folded_desc(const DCtx& c, int l, const void* dgates, const void* xh, const gic_decoder_grads* G) {
+  static float none;
+  GemmDesc m;
+  m.A = dgates; m.lda = 4 * c.H; m.a_kc = 0; m.b_kc = 0; m.ldb = c.ldx(l);
+  m.M = 4 * c.H; m.K = c.B * c.L; m.in_dtype = c.dt; m.out_dtype = DT_F32;
+  m.B = xh; m.N = (int)c.ldx(l); m.C = G ? G->w_ih[l] : &none; m.ldc = c.din(l); m.C2 = G ? G->w_hh[l] : &none; m.ldc2 = c.H; m.n_split = c.din(l);
+  m.wgrad = 1; m.a_sum = G ? G->b_ih[l] : &none; m.a_sum2 = G ? G->b_hh[l] : &none;
+  return m;
+}
+
 // slot 0 of the recurrent buffers: initial (h, c) -- zeros, or the caller's states (generator.py:55,61) -- and features -> x_0
 int init_slot0(const DCtx& c, const gic_decoder_state* st, const float* features, const gic_decoder_sample_opts* opt, hipStream_t stream) {
   const int B = c.B, E = c.E, H = c.H;
@@ -447,29 +459,26 @@ int sample_fwd_t(const DCtx& c, const gic_decoder_params* P, const gic_decoder_s
                  const float* features, const float* noise_u, uint64_t seed, float temperature, int pretrain,
                  void* out, int64_t* ids, const gic_decoder_sample_opts* opt, hipStream_t stream) {
   const int B = c.B, L = c.L, V = c.V, E = c.E, H = c.H, NL = c.NL;
-  GIC_PROPAGATE(init_slot0(c, st, features, opt, stream));
-  // up to a few hundred rows the per-step products are latency-bound: the fused step kernels; beyond that (Monte-Carlo
-  // roll-out batches) they are large GEMMs and the generic 128-row-tile kernels are the efficient form
-  if (st->part && B <= decoder_step_max_rows() && !(opt && opt->resume_from) && decoder_step_supported(c.dt, V, E, H, NL))
-    return sample_fwd_fused<TA>(c, P, S, st, noise_u, seed, temperature, pretrain, out, ids, opt, stream);
-  if (opt && opt->dev_scalars) {
-    set_last_error("decoder_sample_fwd: device-resident step scalars need the fused step kernels (state->part, B <= %d, V %% 4 == 0, E, H %% 8 == 0)",
-                   decoder_step_max_rows());
-    return GIC_ERR_UNSUPPORTED;
-  }
-  GIC_CHECK_ARG(st->logits && st->gpre, "decoder_sample_fwd: the unfused path needs state->logits and state->gpre");
+  DecoderPlan plan;
+  const DecoderFwdCall call{st->part != nullptr, opt && opt->resume_from, opt && opt->dev_scalars, out != nullptr, pretrain != 0, st->logits};
+  GIC_PROPAGATE(select_decoder_fwd(c, call, plan));
+  GIC_CHECK_ARG(plan.fwd == DEC_FUSED || (st->logits && st->gpre), "decoder_sample_fwd: the unfused path needs state->logits and state->gpre");
+  // resumed roll-outs: at step t only the first act[t] rows exist; the rows that join take their state from the earlier call
+  const int32_t* act = (opt && opt->resume_from) ? opt->host_active_rows : nullptr;
+  RowkeySteps keyed{plan.rowkey_from, plan.fwd == DEC_GENERIC_ROWKEY};
+  // route-only mode (gemm.h): validated and selected.  The fused path has no product to select; the generic ones walk their steps and
+  // select each step's products in launch order, launching, filling and copying nothing (the per-step launchers below return at once)
+  const bool probe = route_only();
+  if (probe && plan.fwd == DEC_FUSED) return GIC_OK;
+  if (!probe) GIC_PROPAGATE(init_slot0(c, st, features, opt, stream));
+  if (plan.fwd == DEC_FUSED) return sample_fwd_fused<TA>(c, P, S, st, noise_u, seed, temperature, pretrain, out, ids, opt, stream);
   const bool keep = !(opt && opt->no_state);
   const int64_t* f_ids = opt ? opt->force_ids : nullptr;
   const int32_t* f_len = opt ? opt->force_len : nullptr;
-  // resumed roll-outs: at step t only the first act[t] rows exist; the rows that join take their state from the earlier call
-  const int32_t* act = (opt && opt->resume_from) ? opt->host_active_rows : nullptr;
-  if (act) GIC_PROPAGATE(hipMemcpyAsync(ids, f_ids, (size_t)B * L * sizeof(int64_t), hipMemcpyDeviceToDevice, stream) == hipSuccess ? GIC_OK : GIC_ERR_LAUNCH);
-  // ids-only roll-outs in the bf16 mode: one 64-bit argmax key per (step, row) in the logits scratch (gemm_gumbelmax); zeroed once
-  unsigned long long* rowkeys = nullptr;
-  if (!out && !pretrain && c.dt == DT_BF16 && V % 4 == 0 && (long)L * 8 <= (long)V * 4 && ((uintptr_t)st->logits & 7) == 0) {
-    rowkeys = (unsigned long long*)st->logits;                  // [L][B] keys inside the [B, V] f32 scratch (L * 8 <= V * 4 bytes per row)
-    GIC_PROPAGATE(fill_zero(rowkeys, (size_t)L * B * sizeof(unsigned long long), stream));
-  }
+  if (act && !probe) GIC_PROPAGATE(hipMemcpyAsync(ids, f_ids, (size_t)B * L * sizeof(int64_t), hipMemcpyDeviceToDevice, stream) == hipSuccess ? GIC_OK : GIC_ERR_LAUNCH);
+  // DEC_GENERIC_ROWKEY: [L][B] keys inside the [B, V] f32 scratch (L * 8 <= V * 4 bytes per row; gemm_gumbelmax); zeroed once
+  unsigned long long* const rowkeys = (unsigned long long*)st->logits;
+  if (keyed.on && !probe) GIC_PROPAGATE(fill_zero(rowkeys, (size_t)L * B * sizeof(unsigned long long), stream));
 
   for (int t = 0; t < L; ++t) {
     const int M = act ? act[t] : B;                     // rows that take part in this step
@@ -502,9 +511,10 @@ int sample_fwd_t(const DCtx& c, const gic_decoder_params* P, const gic_decoder_s
     }
     TA* x_next = (TA*)st->xh[0] + (long)(t + 1) * B * c.ldx(0);
     const float* u_t = noise_u ? noise_u + (long)t * B * V : nullptr;
-    if (!out && !pretrain && rowkeys) {
+    if (keyed.take(M)) {
       // ids only (Monte-Carlo roll-outs): vocabulary product with the Gumbel-max in its epilogue -- the [rows, V] logits never reach
-      // memory (389 MB written and read again per step at 9728 rows), then key -> token -> next input row
+      // memory (389 MB written and read again per step at 9728 rows), then key -> token -> next input row.  A step the plan does not
+      // take (fewer rows than rowkey_from) ends the keyed steps: the separate launches from there on
       const int l = NL - 1;
       const long ld = c.ldx(l);
       GemmDesc g;
@@ -519,7 +529,7 @@ int sample_fwd_t(const DCtx& c, const gic_decoder_params* P, const gic_decoder_s
         continue;
       }
       if (s != GIC_ERR_UNSUPPORTED) return s;
-      rowkeys = nullptr;                        // shapes the fused product declines: the separate launches from here on
+      keyed.decline();                          // what the plan cannot see: b_out, the wout image or u off 16 bytes, a temperature <= 0
     }
     {  // vocabulary projection on the last layer's h_t (lives in XH_last[t+1][:, Din:])
       const int l = NL - 1;
@@ -543,15 +553,18 @@ int sample_bwd_t(const DCtx& c, const gic_decoder_params* P, const gic_decoder_s
   const int B = c.B, L = c.L, V = c.V, E = c.E, H = c.H, NL = c.NL;
   const long BL = (long)B * L;
   const int pw_grid = cdiv((long)B * H, 256);
+  DecoderBwdCall call{phases, pretrain != 0, probs, d_out, ws->dlogits};
+  for (int l = 0; l < NL; ++l) { call.wcat_t[l] = S->wcat_t[l]; call.dgates[l] = ws->dgates[l]; call.xh[l] = st->xh[l]; }
+  DecoderPlan plan;
+  select_decoder_bwd(c, call, plan);
+  if (route_only()) return GIC_OK;       // (gemm.h) validated and selected: gic_debug_decoder_plan prints the plan
   // 1. + 2. output layer: d_logits [B,L,V], d_hout = d_logits W_out, dW_out = d_logits^T hout, db_out = colsum(d_logits)
   if (phases & GIC_DECODER_BWD_OUTPUT)
     GIC_PROPAGATE(decoder_output_bwd(c.dt, B, L, V, H, probs, d_out, temperature, t_dev, pretrain, ws->dlogits, S->wout, st->hout, ws->dhout,
                                      G->w_out, G->b_out, stream));
   if (!(phases & GIC_DECODER_BWD_RECURRENT)) return GIC_OK;
   // 3. BPTT
-  bool fused = decoder_step_supported(c.dt, 4, 8, H, NL) && H % 2 == 0 && B <= decoder_step_max_rows();
-  for (int l = 0; l < NL; ++l) fused = fused && S->wcat_t[l] != nullptr;
-  if (fused) {
+  if (plan.bwd_fused) {
     // one launch per (step, layer): the recurrent (and, below the top layer, the upper layer's input) gradient product fused with
     // the cell's pointwise backward (decoder_step.h); the x-side input gradients leave the serial chain as ONE product afterwards
     for (int t = L - 1; t >= 0; --t) {
@@ -614,20 +627,15 @@ int sample_bwd_t(const DCtx& c, const gic_decoder_params* P, const gic_decoder_s
   // 4. batched weight gradients over all L*B rows
   for (int l = 0; l < NL; ++l) {
     const long ld = c.ldx(l);
+    if (plan.wgrad_folded[l]) {
+      // dW_ih | dW_hh as ONE product over xh = [x | h] with the two bias gradients as its A column sums (select_decoder_bwd: the
+      // kernel folds them and din sits on a tile boundary); else the two products and the column-sum pass
+      GIC_PROPAGATE(gemm(wgrad_folded_desc(c, l, ws->dgates[l], st->xh[l], G), stream));
+      continue;
+    }
     GemmDesc w;
     w.A = ws->dgates[l]; w.lda = 4 * H; w.a_kc = 0; w.b_kc = 0; w.ldb = ld;
     w.M = 4 * H; w.K = (int)BL; w.in_dtype = c.dt; w.out_dtype = DT_F32;
-    {  // dW_ih | dW_hh as ONE product over xh = [x | h] with the two bias gradients as its A column sums, where the kernel folds them and
-       // din sits on a tile boundary; else the two products and the column-sum pass
-      GemmDesc m = w;
-      m.B = st->xh[l]; m.N = (int)ld; m.C = G->w_ih[l]; m.ldc = c.din(l); m.C2 = G->w_hh[l]; m.ldc2 = H; m.n_split = c.din(l);
-      m.wgrad = 1; m.a_sum = G->b_ih[l]; m.a_sum2 = G->b_hh[l];
-      const int tn = wgrad_tile_n(m);
-      if (tn && c.din(l) % tn == 0 && wgrad_folds_a_sum(m)) {
-        GIC_PROPAGATE(gemm(m, stream));
-        continue;
-      }
-    }
     w.B = st->xh[l]; w.N = c.din(l); w.C = G->w_ih[l]; w.ldc = c.din(l);
     GIC_PROPAGATE(gemm(w, stream));
     w.B = (const TA*)st->xh[l] + c.din(l); w.N = H; w.C = G->w_hh[l]; w.ldc = H;
@@ -684,6 +692,44 @@ __global__ __launch_bounds__(256) void embed_scatter_rows_kernel(const float* __
 
 }  // namespace
 
+// ---- the selection (decoder_step.h)
+int select_decoder_fwd(const DCtx& c, const DecoderFwdCall& f, DecoderPlan& p) {
+  const int l = c.NL - 1;
+  p.rowkey_from = 0;
+  if (f.part && !f.resumed && c.B <= decoder_fused_rows(c.dt, c.V, c.E, c.H, c.NL)) {
+    p.fwd = DEC_FUSED;
+    return GIC_OK;
+  }
+  if (f.dev_scalars) {
+    set_last_error("decoder_sample_fwd: device-resident step scalars need the fused step kernels (state->part, B <= %d, V %% 4 == 0, E, H %% 8 == 0)",
+                   decoder_step_max_rows());
+    return GIC_ERR_UNSUPPORTED;
+  }
+  // ids-only roll-outs in the bf16 mode: the row keys fit the logits scratch
+  const bool keyed = !f.out && !f.pretrain && c.dt == DT_BF16 && c.V % 4 == 0 && (long)c.L * 8 <= (long)c.V * 4 && ((uintptr_t)f.logits & 7) == 0;
+  p.fwd = keyed ? DEC_GENERIC_ROWKEY : DEC_GENERIC;
+  if (keyed) p.rowkey_from = gemm_gumbelmax_from_cols(c.dt, c.V, c.H, c.H, c.ldx(l));
+  return GIC_OK;
+}
+
+int select_softmax_bwd(int dt, int V, const void* probs, const void* d_out, const void* dlogits) {
+  const bool al = ((((uintptr_t)probs) | ((uintptr_t)d_out) | ((uintptr_t)dlogits)) & 15) == 0;
+  if (dt == DT_F32) return al && V % 4 == 0 && V <= 256 * 8 * 4 ? 8 : 0;
+  if (!al || V % 8) return 0;
+  return V <= 256 * 5 * 8 ? 5 : (V <= 256 * 8 * 8 ? 8 : 0);
+}
+
+void select_decoder_bwd(const DCtx& c, const DecoderBwdCall& b, DecoderPlan& p) {
+  p.softmax_nch = b.pretrain ? 0 : select_softmax_bwd(c.dt, c.V, b.probs, b.d_out, b.dlogits);
+  p.bwd_fused = c.B <= decoder_bwd_fused_rows(c.H, c.NL);
+  for (int l = 0; l < c.NL; ++l) {
+    p.bwd_fused = p.bwd_fused && b.wcat_t[l] != nullptr;
+    const GemmDesc m = wgrad_folded_desc(c, l, b.dgates[l], b.xh[l], nullptr);
+    const int tn = wgrad_tile_n(m);
+    p.wgrad_folded[l] = tn && c.din(l) % tn == 0 && wgrad_folds_a_sum(m);
+  }
+}
+
 // Output layer of the decoder, backward (shared by the LSTM and the attention decoder): softmax/Gumbel backward (adversarial mode),
 // d_hout, and the complete gradients of the vocabulary projection.
 int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, const void* d_out, float temperature, const float* t_dev, int pretrain,
@@ -691,19 +737,19 @@ int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, co
   const long BL = (long)B * L;
   const void* dlog = pretrain ? d_out : (const void*)dlogits_ws;
   if (!pretrain) {
-    const bool al = ((((uintptr_t)probs) | ((uintptr_t)d_out) | ((uintptr_t)dlogits_ws)) & 15) == 0;
+    const int nch = select_softmax_bwd(dt, V, probs, d_out, dlogits_ws);
     if (dt == DT_F32) {
-      if (al && V % 4 == 0 && V <= 256 * 8 * 4)
+      if (nch)
         hipLaunchKernelGGL((softmax_bwd_vec_kernel<float, 8>), dim3((unsigned)BL), dim3(256), 0, stream, (const float*)probs, (const float*)d_out,
                            (float*)dlogits_ws, temperature, t_dev, V);
       else
         hipLaunchKernelGGL((softmax_bwd_kernel<float>), dim3((unsigned)BL), dim3(256), 0, stream, (const float*)probs, (const float*)d_out,
                            (float*)dlogits_ws, temperature, t_dev, V);
     } else {
-      if (al && V % 8 == 0 && V <= 256 * 5 * 8)
+      if (nch == 5)
         hipLaunchKernelGGL((softmax_bwd_vec_kernel<bf16_t, 5>), dim3((unsigned)BL), dim3(256), 0, stream, (const bf16_t*)probs, (const bf16_t*)d_out,
                            (bf16_t*)dlogits_ws, temperature, t_dev, V);
-      else if (al && V % 8 == 0 && V <= 256 * 8 * 8)
+      else if (nch == 8)
         hipLaunchKernelGGL((softmax_bwd_vec_kernel<bf16_t, 8>), dim3((unsigned)BL), dim3(256), 0, stream, (const bf16_t*)probs, (const bf16_t*)d_out,
                            (bf16_t*)dlogits_ws, temperature, t_dev, V);
       else
@@ -725,9 +771,10 @@ int decoder_output_bwd(int dt, int B, int L, int V, int H, const void* probs, co
   return folded ? GIC_OK : colsum(dlog, dt, V, BL, V, d_bout, nullptr, 0, stream);
 }
 
-// ---- the generic roll-out's per-step launches, shared with the attention decoder's roll-out (attn_rollout.hip)
+// ---- the generic roll-out's per-step launches, shared with the attention decoder's roll-out (attn_rollout.hip); route-only mode: none
 int rollout_join(const unsigned char* src_xh, unsigned char* dst_xh, long rowbytes, const float* src_c, float* dst_c, int H, long r0, long r1,
                  int srcB, hipStream_t stream) {
+  if (route_only()) return GIC_OK;
   const int pb = rowbytes % 16 == 0 ? 16 : (rowbytes % 4 == 0 ? 4 : 2);      // rowbytes is a multiple of the element size
   const long work = (r1 - r0) * (rowbytes / pb);
   const dim3 jgrid((unsigned)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256));
@@ -740,6 +787,7 @@ int rollout_join(const unsigned char* src_xh, unsigned char* dst_xh, long rowbyt
 
 int rollout_pick(int dt, const unsigned long long* rowkey, int64_t* ids, long ids_stride, const float* embed, void* x_next, long ld_x, int rows,
                  int V, int E, const int64_t* force_ids, const int32_t* force_len, int t, hipStream_t stream) {
+  if (route_only()) return GIC_OK;
   const dim3 grid((unsigned)cdiv(rows, 4));
   if (dt == DT_F32)
     hipLaunchKernelGGL((rollout_pick_kernel<float>), grid, dim3(256), 0, stream, rowkey, ids, ids_stride, embed, (float*)x_next, ld_x, rows, V, E,
@@ -752,15 +800,19 @@ int rollout_pick(int dt, const unsigned long long* rowkey, int64_t* ids, long id
 }
 
 namespace {
+// gumbel_softmax_argmax_reg_kernel's registers per lane (rows of V % 4 == 0 up to 4096 / 16384 entries), 0: the kernel that walks the row
+int select_rollout_argmax(int V) { return V % 4 == 0 && V <= 4096 ? 1 : (V % 4 == 0 && V <= 16384 ? 4 : 0); }
+
 template <typename TA>
 int rollout_argmax_t(float* logits, const float* u, uint64_t seed, uint64_t rng_stream, float temperature, int pretrain, TA* out, long out_stride,
                      int64_t* ids, long ids_stride, const float* embed, TA* x_next, long ld_x, int rows, int V, int E, const int64_t* force_ids,
                      const int32_t* force_len, int t, hipStream_t stream) {
   constexpr bool kFast = sizeof(TA) == 2;
-  if (V % 4 == 0 && V <= 4096) {
+  const int nreg = select_rollout_argmax(V);
+  if (nreg == 1) {
     hipLaunchKernelGGL((gumbel_softmax_argmax_reg_kernel<TA, 1, kFast>), dim3(rows), dim3(1024), 0, stream, (const float*)logits, u, seed, rng_stream,
                        temperature, pretrain, out, out_stride, ids, ids_stride, embed, x_next, ld_x, V, E, force_ids, force_len, t);
-  } else if (V % 4 == 0 && V <= 16384) {
+  } else if (nreg == 4) {
     hipLaunchKernelGGL((gumbel_softmax_argmax_reg_kernel<TA, 4, kFast>), dim3(rows), dim3(1024), 0, stream, (const float*)logits, u, seed, rng_stream,
                        temperature, pretrain, out, out_stride, ids, ids_stride, embed, x_next, ld_x, V, E, force_ids, force_len, t);
   } else {
@@ -775,6 +827,7 @@ int rollout_argmax_t(float* logits, const float* u, uint64_t seed, uint64_t rng_
 int rollout_argmax(int dt, float* logits, const float* u, uint64_t seed, uint64_t rng_stream, float temperature, int pretrain, void* out,
                    long out_stride, int64_t* ids, long ids_stride, const float* embed, void* x_next, long ld_x, int rows, int V, int E,
                    const int64_t* force_ids, const int32_t* force_len, int t, hipStream_t stream) {
+  if (route_only()) return GIC_OK;
   if (dt == DT_F32)
     return rollout_argmax_t<float>(logits, u, seed, rng_stream, temperature, pretrain, (float*)out, out_stride, ids, ids_stride, embed, (float*)x_next,
                                    ld_x, rows, V, E, force_ids, force_len, t, stream);
@@ -785,6 +838,7 @@ int rollout_argmax(int dt, float* logits, const float* u, uint64_t seed, uint64_
 int lstm_pointwise_fwd(int dt, const float* gpre, const float* c_prev, float* c_new, void* h_next, long ld_next, void* h_up, long ld_up,
                        int rows, int H, hipStream_t stream, void* h_out, long ld_out, float* gates, const int32_t* lengths, int t,
                        const void* h_prev, long ld_prev) {
+  if (route_only()) return GIC_OK;
   const dim3 grid((unsigned)cdiv((long)rows * H, 256));
   if (dt == DT_F32)
     hipLaunchKernelGGL((lstm_pointwise_fwd_kernel<float>), grid, dim3(256), 0, stream, gpre, c_prev, gates, c_new, (float*)h_next, ld_next,
@@ -846,8 +900,136 @@ int decoder_bwd_recurrent(const DCtx& c, const gic_decoder_params* P, const gic_
                     ? sample_bwd_t<float>(c, P, S, st, ws, nullptr, ids, nullptr, 1.f, nullptr, 0, G, GIC_DECODER_BWD_RECURRENT, stream)
                     : sample_bwd_t<bf16_t>(c, P, S, st, ws, nullptr, ids, nullptr, 1.f, nullptr, 0, G, GIC_DECODER_BWD_RECURRENT, stream);
   GIC_PROPAGATE(s);
+  if (route_only()) return GIC_OK;
   return embed_scatter_time((const float*)ws->dxh[0], c.ldx(0), ids, G->embed, c.B, c.L, c.E, c.V, stream, ids_stride);
 }
+
+// ---- gic_debug_decoder_plan: the two plans as text, one line per distinct launch in launch order with its count per call
+namespace {
+struct PlanText {
+  char* out; size_t len; size_t n = 0;
+  void put(const char* text, long times) { n += snprintf(n < len ? out + n : nullptr, n < len ? len - n : 0, times ? "%s x%ld\n" : "%s\n", text, times); }
+  void kernel(const char* name, int dt, const char* targs, unsigned gx, unsigned gy, int block, long times) {
+    char text[160];
+    int w = snprintf(text, sizeof text, "%s<%s%s>", name, dt == DT_F32 ? "f32" : "bf16", targs);
+    if (gy) snprintf(text + w, sizeof text - w, " grid=%ux%u block=%d lds=0", gx, gy, block);
+    else snprintf(text + w, sizeof text - w, " grid=%u block=%d lds=0", gx, block);
+    put(text, times);
+  }
+  void step(const StepPlan& p, long times) {
+    char text[160];
+    step_plan_line(p, text, sizeof text);
+    put(text, times);
+  }
+  // a product's line as gemm() / gemm_gumbelmax() select it over aligned operands (route-only mode: nothing is launched)
+  void product(GemmDesc g, long times) {
+    static float fake[4] __attribute__((aligned(16)));
+    g.A = g.B = fake;
+    if (g.gm_rowkey) g.gm_bias = fake; else g.C = fake;
+    if (g.bias) g.bias = fake;
+    if (g.wgrad) { g.a_sum = g.a_sum2 = fake; g.C2 = g.C2 ? fake : nullptr; if (!g.C2) g.a_sum2 = nullptr; }
+    const bool was = route_only();
+    gic_debug_route_only(1);
+    const int s = g.gm_rowkey ? gemm_gumbelmax(g, nullptr) : gemm(g, nullptr);
+    gic_debug_route_only(was);
+    char text[kRouteLen + 64];
+    snprintf(text, sizeof text, "%s M=%d N=%d K=%d", s == GIC_OK ? route_line() : "unsupported", g.M, g.N, g.K);
+    put(text, times);
+  }
+};
+
+int decoder_plan_text(const DCtx& c, int flags, char* out, size_t len) {
+  const int B = c.B, L = c.L, V = c.V, E = c.E, H = c.H, NL = c.NL;
+  static float fake[4] __attribute__((aligned(16)));
+  const bool train = flags & GIC_DECODER_PLAN_TRAIN, pretrain = flags & GIC_DECODER_PLAN_PRETRAIN;
+  PlanText t{out, len};
+  DecoderPlan p;
+  const DecoderFwdCall f{!(flags & GIC_DECODER_PLAN_NO_PART), (flags & GIC_DECODER_PLAN_RESUMED) != 0, (flags & GIC_DECODER_PLAN_DEV_SCALARS) != 0,
+                         train, pretrain, (const char*)fake + ((flags & GIC_DECODER_PLAN_LOGITS_UNALIGNED) ? 4 : 0)};
+  GIC_PROPAGATE(select_decoder_fwd(c, f, p));
+  static const char* const path[] = {"FUSED", "GENERIC", "GENERIC_ROWKEY"};
+  char head[96];
+  snprintf(head, sizeof head, "forward path=%s from=%ld", path[p.fwd], p.rowkey_from);
+  t.put(head, 0);
+  const bool two = NL > 1;                       // layers above the first share one shape
+  if (p.fwd == DEC_FUSED) {
+    t.step(select_lstm_step(LSTM_PLAIN, c.dt, B, H, c.ldx(0)), L);
+    if (two) t.step(select_lstm_step(LSTM_PLAIN, c.dt, B, H, c.ldx(1)), (long)L * (NL - 1));
+    t.step(select_vocab_step(VOCAB_SAMPLE, c.dt, 0, B, V, H), L);
+    t.kernel("sample_finish_kernel", c.dt, "", (unsigned)((long)B * L), 0, 256, 1);
+  } else {
+    for (int l = 0; l < (two ? 2 : 1); ++l) {
+      GemmDesc g;
+      g.lda = c.ldx(l); g.ldb = c.ldx(l); g.ldc = 4 * H; g.M = B; g.N = 4 * H; g.K = (int)c.ldx(l); g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = fake;
+      t.product(g, l ? (long)L * (NL - 1) : L);
+    }
+    t.kernel("lstm_pointwise_fwd_kernel", c.dt, "", (unsigned)cdiv((long)B * H, 256), 0, 256, (long)L * NL);
+    RowkeySteps keyed{p.rowkey_from, p.fwd == DEC_GENERIC_ROWKEY};
+    if (keyed.take(B)) {
+      GemmDesc g;
+      g.lda = H; g.ldb = c.ldx(NL - 1); g.M = V; g.N = B; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32;
+      g.gm_rowkey = (unsigned long long*)fake; g.gm_ldu = V; g.gm_temperature = 1.f;
+      t.product(g, L);
+      t.kernel("rollout_pick_kernel", c.dt, "", (unsigned)cdiv(B, 4), 0, 256, L);
+    } else {
+      GemmDesc g;
+      g.lda = c.ldx(NL - 1); g.ldb = H; g.ldc = V; g.M = B; g.N = V; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = fake;
+      t.product(g, L);
+      const int nreg = select_rollout_argmax(V);
+      char ta[24];
+      snprintf(ta, sizeof ta, nreg ? ",%d,%s" : "", nreg, c.dt == DT_F32 ? "false" : "true");
+      t.kernel(nreg ? "gumbel_softmax_argmax_reg_kernel" : "gumbel_softmax_argmax_kernel", c.dt, ta, (unsigned)B, 0, nreg ? 1024 : 256, L);
+    }
+  }
+  if (!train) return GIC_OK;                     // an ids-only roll-out keeps no state: no backward follows
+
+  DecoderBwdCall b{GIC_DECODER_BWD_ALL | ((flags & GIC_DECODER_PLAN_STATE_GRADS) ? GIC_DECODER_BWD_STATE_GRADS : 0), pretrain, fake, fake, fake};
+  for (int l = 0; l < NL; ++l) {
+    b.wcat_t[l] = (flags & GIC_DECODER_PLAN_NO_WCAT_T) && l == NL - 1 ? nullptr : fake;
+    b.dgates[l] = fake; b.xh[l] = fake;
+  }
+  select_decoder_bwd(c, b, p);
+  snprintf(head, sizeof head, "backward path=%s", p.bwd_fused ? "FUSED" : "GENERIC");
+  t.put(head, 0);
+  if (!pretrain) {
+    char ta[8];
+    snprintf(ta, sizeof ta, p.softmax_nch ? ",%d" : "", p.softmax_nch);
+    t.kernel(p.softmax_nch ? "softmax_bwd_vec_kernel" : "softmax_bwd_kernel", c.dt, ta, (unsigned)((long)B * L), 0, 256, 1);
+  }
+  if (p.bwd_fused) {
+    t.kernel("lstm_bwd_step_kernel", c.dt, c.dt == DT_F32 ? ",4" : ",8", (unsigned)cdiv(H, 16), (unsigned)cdiv(B, 16), 512, (long)L * NL);
+    GemmDesc g;       // d x_t of layer 0 for every step
+    g.lda = 4 * H; g.a_kc = 1; g.ldb = 4 * H; g.b_kc = 1; g.ldc = c.ldx(0); g.M = B * L; g.N = E; g.K = 4 * H; g.in_dtype = c.dt; g.out_dtype = DT_F32;
+    t.product(g, 1);
+    if (b.phases & GIC_DECODER_BWD_STATE_GRADS) {
+      for (int l = 0; l < (two ? 2 : 1); ++l) {
+        g.ldc = c.ldx(l); g.M = B; g.N = H;
+        t.product(g, l ? NL - 1 : 1);
+      }
+    }
+  } else {
+    t.kernel("lstm_pointwise_bwd_kernel", c.dt, "", (unsigned)cdiv((long)B * H, 256), 0, 256, (long)L * NL);
+    for (int l = 0; l < NL; ++l) {      // d[x | h_prev] = d_gates Wcat, per layer: the operand is the transposed image where there is one
+      GemmDesc g;
+      g.lda = 4 * H; g.a_kc = 1; g.ldb = b.wcat_t[l] ? 4 * H : c.ldx(l); g.b_kc = b.wcat_t[l] ? 1 : 0;
+      g.ldc = c.ldx(l); g.c_zeroed = 1; g.M = B; g.N = (int)c.ldx(l); g.K = 4 * H; g.in_dtype = c.dt; g.out_dtype = DT_F32;
+      t.product(g, L);
+    }
+  }
+  for (int l = 0; l < NL; ++l) {        // the batched weight gradients
+    GemmDesc m = wgrad_folded_desc(c, l, fake, fake, nullptr);
+    if (p.wgrad_folded[l]) { t.product(m, 1); continue; }
+    m.wgrad = 0; m.C2 = nullptr; m.a_sum = m.a_sum2 = nullptr; m.n_split = 0;
+    m.N = c.din(l);
+    t.product(m, 1);
+    m.N = H; m.ldc = H;
+    t.product(m, 1);
+    t.put("colsum", 1);
+  }
+  GIC_CHECK_ARG(t.n < len, "debug_decoder_plan: the plan takes %zu bytes, out_len is %zu", t.n + 1, len);
+  return GIC_OK;
+}
+}  // namespace
 
 }  // namespace gic
 
@@ -871,7 +1053,7 @@ int gic_decoder_fused_rollout_rows(const gic_decoder_dims* dims, int32_t* out) {
   DCtx c;
   GIC_PROPAGATE(check_decoder_dims(dims, c));
   GIC_CHECK_ARG(out, "decoder_fused_rollout_rows: null out");
-  *out = decoder_step_supported(c.dt, c.V, c.E, c.H, c.NL) ? decoder_step_max_rows() : 0;
+  *out = decoder_fused_rows(c.dt, c.V, c.E, c.H, c.NL);
   return GIC_OK;
 }
 
@@ -978,8 +1160,25 @@ int gic_decoder_sample_bwd(const gic_decoder_dims* dims, const gic_decoder_param
               ? sample_bwd_t<float>(c, P, S, st, ws, probs, ids, d_out, temperature, t_dev, pretrain, G, phases, stream)
               : sample_bwd_t<bf16_t>(c, P, S, st, ws, probs, ids, d_out, temperature, t_dev, pretrain, G, phases, stream);
   GIC_PROPAGATE(s);
+  if (route_only()) return GIC_OK;
   if (phases & GIC_DECODER_BWD_RECURRENT)
     GIC_PROPAGATE(embed_scatter_time((const float*)ws->dxh[0], c.ldx(0), ids, G->embed, c.B, c.L, c.E, c.V, stream));
+  return GIC_OK;
+}
+
+int gic_debug_decoder_plan(const gic_decoder_dims* dims, int flags, char* out, int64_t out_len) {
+  DCtx c;
+  GIC_PROPAGATE(check_decoder_dims(dims, c));
+  GIC_CHECK_ARG(out && out_len > 0, "debug_decoder_plan: no output buffer");
+  GIC_CHECK_ARG((flags & ~255) == 0, "debug_decoder_plan: unknown flag in %d", flags);
+  return decoder_plan_text(c, flags, out, (size_t)out_len);
+}
+
+int gic_debug_step_plan(int lstm, int variant, int dtype, int B, int H, int64_t ldx_or_V, int K, char* out, int64_t out_len) {
+  GIC_CHECK_ARG(out && out_len > 0, "debug_step_plan: no output buffer");
+  GIC_CHECK_ARG((dtype == DT_F32 || dtype == DT_BF16) && B > 0 && H > 0 && ldx_or_V > 0 && variant >= 0 && variant <= (lstm ? LSTM_BEAM : VOCAB_BEAM_HOP),
+                "debug_step_plan: bad arguments");
+  step_plan_line(lstm ? select_lstm_step(variant, dtype, B, H, ldx_or_V) : select_vocab_step(variant, dtype, K, B, (int)ldx_or_V, H), out, (size_t)out_len);
   return GIC_OK;
 }
 

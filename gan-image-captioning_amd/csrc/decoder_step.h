@@ -14,6 +14,7 @@
 // the 14 MB of decoder weights stay resident in the eight XCD L2s (4 MB each) between steps because the block -> weight-slice
 // map is the same in every step.
 #pragma once
+#include "../../include/gicap.h"
 #include "common.h"
 
 struct gic_decoder_dims;
@@ -114,10 +115,16 @@ struct LstmBwdStepArgs {
 };
 int lstm_bwd_step(const LstmBwdStepArgs& a, int dtype, hipStream_t stream);
 
-// true if the fused kernels take these shapes (else the caller uses the generic GEMM + pointwise launches)
-bool decoder_step_supported(int dtype, int V, int E, int H, int NL);
-// most batch rows the fused roll-out takes (GIC_FUSED_ROLLOUT_MAX_ROWS, default 512): beyond it the per-step products are large GEMMs
-int decoder_step_max_rows();
+// THE predicate "fused step kernels or generic products": the most batch rows for which a pass over these shapes runs lstm_step /
+// vocab_step* (up to a few hundred rows the per-step products are latency-bound; beyond that they are large GEMMs and the generic
+// 128-row-tile kernels are the efficient form), 0 where the kernels do not take the shapes at all.  V >= 4, V % 4 == 0, E % 8 == 0,
+// H % 8 == 0, NL >= 1, at most 1024 vocabulary tiles (sample_finish's scale table); the rows are GIC_FUSED_ROLLOUT_MAX_ROWS (default
+// 512); GIC_NO_FUSED_ROLLOUT switches every fused pass off.  Every caller compares its rows with this one answer.
+int decoder_fused_rows(int dtype, int V, int E, int H, int NL);
+// the backward's own condition, lstm_bwd_step's chain: H % 8 == 0 (the transposed images' 16-byte rows; the kernel's unit pairs need
+// H % 2 == 0), NL >= 1, the same row limit and switch -- V and E do not enter it.  The caller adds that every wcat_t[l] exists.
+int decoder_bwd_fused_rows(int H, int NL);
+int decoder_step_max_rows();                                // the row limit alone (GIC_FUSED_ROLLOUT_MAX_ROWS), for messages
 size_t decoder_step_part_floats(int B, int L, int V);       // floats in the partials scratch: [2][L][B][nblk] floats + [L][B] 64-bit keys + 4 reserved words
 void decoder_step_debug(int v);                             // phase-ablation knob of tools/rollout_bench.py (0 = normal)
 
@@ -150,6 +157,19 @@ int sample_finish(const SampleFinishArgs& a, int dtype, hipStream_t stream);
 // (caption sampling, sample.hip); a.stop / stop_at; the sampling and beam fields are unused
 int vocab_step_logits(const VocabStepArgs& a, int dtype, hipStream_t stream);
 
+// ---- the launchers' plans (gemm.h's convention: select_* is a pure host function that fills a plan, launch_* asks for the LDS grant,
+// switches on the variant and launches).  lstm_step / vocab_step* above and in beam.h are "check the arguments, select, launch".
+enum { LSTM_PLAIN, LSTM_PACK, LSTM_BEAM };
+enum { VOCAB_SAMPLE, VOCAB_LOGITS, VOCAB_BEAM, VOCAB_BEAM_BAN, VOCAB_BEAM_HOP };      // (the three beam forms last: select_vocab_step)
+struct StepPlan {
+  bool lstm; int variant, dtype, K;       // K: the beam forms' template argument, else 0
+  dim3 grid; int block; size_t lds; int KC;
+};
+StepPlan select_lstm_step(int variant, int dtype, int B, int H, long ldx);
+StepPlan select_vocab_step(int variant, int dtype, int K, int B, int V, int H);
+// the plan as one line in the route line's format: kernel<template args> grid=XxY block=.. lds=.. KC=..
+void step_plan_line(const StepPlan& p, char* out, size_t len);
+
 // ---- the LSTM decoder's (decoder.hip) shapes, shared with the teacher-forced decode (teacher_forced.hip)
 struct DCtx {
   int B, L, V, E, H, NL, dt;
@@ -158,6 +178,44 @@ struct DCtx {
   size_t asz() const { return (size_t)dtype_size(dt); }
 };
 int check_decoder_dims(const gic_decoder_dims* d, DCtx& c);   // B, L, E, H > 0, V > 1, NL in 1..GIC_MAX_LAYERS
+
+// ---- one plan for gic_decoder_sample_fwd / gic_decoder_sample_bwd (decoder.hip: "select, then the stages").  select_decoder_* are pure
+// host functions of the shapes and of the facts about the call below; pointers are read for their alignment only.
+enum { DEC_FUSED, DEC_GENERIC, DEC_GENERIC_ROWKEY };
+struct DecoderFwdCall {
+  bool part, resumed, dev_scalars, out, pretrain;      // state->part, opts->resume_from, opts->dev_scalars, out present; pretrain != 0
+  const void* logits;                                  // state->logits
+};
+struct DecoderBwdCall {
+  int phases; bool pretrain;
+  const void* probs; const void* d_out; const void* dlogits;
+  const void* wcat_t[GIC_MAX_LAYERS];                  // presence
+  const void* dgates[GIC_MAX_LAYERS]; const void* xh[GIC_MAX_LAYERS];      // the weight-gradient products' operands
+};
+struct DecoderPlan {
+  // forward.  DEC_GENERIC_ROWKEY: the generic path of an ids-only bf16 roll-out, one 64-bit argmax key per (step, row) in the logits
+  // scratch and the Gumbel-max in the vocabulary product's epilogue for every step of at least rowkey_from rows (0: no step)
+  int fwd = DEC_GENERIC; long rowkey_from = 0;
+  // backward: lstm_bwd_step's chain or pointwise + product per (step, layer); per layer ONE weight-gradient product with the bias sums
+  // folded in, or two products and colsum; softmax_bwd_vec_kernel's NCH (0: the scalar kernel)
+  bool bwd_fused = false; bool wgrad_folded[GIC_MAX_LAYERS] = {}; int softmax_nch = 0;
+};
+// GIC_OK, or GIC_ERR_UNSUPPORTED with its message: device-resident step scalars off the fused path
+int select_decoder_fwd(const DCtx& c, const DecoderFwdCall& f, DecoderPlan& p);
+void select_decoder_bwd(const DCtx& c, const DecoderBwdCall& b, DecoderPlan& p);
+int select_softmax_bwd(int dt, int V, const void* probs, const void* d_out, const void* dlogits);      // decoder_output_bwd's variant (NCH | 0)
+// The steps of a DEC_GENERIC_ROWKEY roll-out: step t's M rows take the fused product iff M >= from and no earlier step was declined --
+// after one decline the separate launches run from there on, whatever a later step's rows.
+struct RowkeySteps {
+  long from; bool on;
+  bool sticky = true;                   // gic_attn_rollout: false -- each step on its own rows (its logits scratch holds only the steps below `from`)
+  bool take(int M) {
+    const bool ok = on && from > 0 && M >= from;
+    if (sticky) on = ok;
+    return ok;
+  }
+  void decline() { on = false; }        // the product's own status is the last word (gemm_gumbelmax also reads pointers and the temperature)
+};
 // decoder.hip: the recurrent phase of gic_decoder_sample_bwd (ws->dhout filled) over c.L steps and the embedding scatter over ids
 // (rows ids_stride apart; 0 = c.L)
 int decoder_bwd_recurrent(const DCtx& c, const gic_decoder_params* P, const gic_decoder_shadow* S, const gic_decoder_state* st,

@@ -793,12 +793,18 @@ __global__ __launch_bounds__(512) void lstm_bwd_step_kernel(const LstmBwdStepArg
 
 static int g_step_dbg = 0;      // gic_debug_decoder_step: 1 | 2 | 4 load-ablation bits of tools/rollout_bench.py
 
-// dynamic LDS beyond 64 KB: per kernel and per device (common.h grant_lds)
-template <typename K>
-int allow_lds(K kernel, size_t bytes, LdsGrant& g) {
-  if (grant_lds(kernel, bytes, g)) return GIC_OK;
-  set_last_error("decoder step kernel: cannot reserve %zu bytes of LDS", bytes);
-  return GIC_ERR_LAUNCH;
+// The "grant, then launch" pair of a step kernel, keyed on the instantiation: dynamic LDS beyond 64 KB is granted per kernel and per
+// device (common.h grant_lds), so each instantiation keeps its own function-local grant.  The kernels take (args, KC) and, the ban and
+// hop epilogues, their lists behind them
+template <auto Kernel, typename A, typename... Lists>
+int launch_step(const StepPlan& p, hipStream_t stream, const A& a, const Lists&... lists) {
+  static LdsGrant g;
+  if (!grant_lds(Kernel, p.lds, g)) {
+    set_last_error("decoder step kernel: cannot reserve %zu bytes of LDS", p.lds);
+    return GIC_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(Kernel, p.grid, dim3(p.block), p.lds, stream, a, p.KC, lists...);
+  return GIC_OK;
 }
 
 // K chunk (elements) staged per pass: 1 KiB of a row in vocab_step (two tiles), 2 KiB in lstm_step (one tile); multiples of 32
@@ -817,12 +823,26 @@ size_t lstm_lds_bytes(int dtype, int ldx) {
 
 }  // namespace
 
-bool decoder_step_supported(int dtype, int V, int E, int H, int NL) {
+// the two cached switches behind every fused pass
+static bool fused_off() {
   static const bool off = getenv("GIC_NO_FUSED_ROLLOUT") != nullptr;
-  if (off) return false;
-  if (V < 4 || V % 4 || E % 8 || H % 8 || NL < 1) return false;
+  return off;
+}
+int decoder_step_max_rows() {
+  static const int rows = [] { const char* e = getenv("GIC_FUSED_ROLLOUT_MAX_ROWS"); return e ? atoi(e) : 512; }();
+  return rows;
+}
+
+int decoder_fused_rows(int dtype, int V, int E, int H, int NL) {
   (void)dtype;
-  return (V + kVocabTile - 1) / kVocabTile <= 1024;                    // sample_finish's scale table
+  if (fused_off() || V < 4 || V % 4 || E % 8 || H % 8 || NL < 1) return 0;
+  if ((V + kVocabTile - 1) / kVocabTile > 1024) return 0;               // sample_finish's scale table
+  return decoder_step_max_rows();
+}
+
+int decoder_bwd_fused_rows(int H, int NL) {
+  if (fused_off() || H % 8 || H % 2 || NL < 1) return 0;
+  return decoder_step_max_rows();
 }
 
 // state->part: part_m | part_s (per = [L][B][nblk] floats each) | the 64-bit row keys [L][B] on the next 8-byte boundary
@@ -859,10 +879,53 @@ SampleFinishArgs step_finish_args(const StepScratch& s, const StepDraw& d, int E
 
 void decoder_step_debug(int v) { g_step_dbg = v; }
 
-int decoder_step_max_rows() {
-  static const int rows = [] { const char* e = getenv("GIC_FUSED_ROLLOUT_MAX_ROWS"); return e ? atoi(e) : 512; }();
-  return rows;
+StepPlan select_lstm_step(int variant, int dtype, int B, int H, long ldx) {
+  return StepPlan{true, variant, dtype, 0, dim3((unsigned)cdiv(H, kUnitsPerBlock), (unsigned)cdiv(B, kStepRows)), 512, lstm_lds_bytes(dtype, (int)ldx),
+                  lstm_chunk(dtype, (int)ldx)};
 }
+
+StepPlan select_vocab_step(int variant, int dtype, int K, int B, int V, int H) {
+  size_t lds = vocab_lds_bytes(dtype, H);
+  const size_t tile = (size_t)kStepRows * (kVocabTile + 1) * sizeof(float);      // the beam epilogues' logits tile
+  if (variant >= VOCAB_BEAM && lds < tile) lds = tile;
+  return StepPlan{false, variant, dtype, K, dim3((unsigned)cdiv(V, kVocabTile), (unsigned)cdiv(B, kStepRows)), 512, lds, vocab_chunk(dtype, H)};
+}
+
+void step_plan_line(const StepPlan& p, char* out, size_t len) {
+  static const char* const lstm[] = {"lstm_step_kernel<%s>", "lstm_step_pack_kernel<%s>", "lstm_step_beam_kernel<%s>"};
+  static const char* const vocab[] = {"vocab_step_kernel<%s,%s>", "vocab_step_logits_kernel<%s>", "vocab_step_beam_kernel<%s,%d>",
+                                      "vocab_step_beam_ban_kernel<%s,%d>", "vocab_step_beam_hop_kernel<%s,%d>"};
+  const char* t = p.dtype == DT_F32 ? "f32" : "bf16";
+  int n;
+  if (p.lstm) n = snprintf(out, len, lstm[p.variant], t);
+  else if (p.variant == VOCAB_SAMPLE) n = snprintf(out, len, vocab[p.variant], t, p.dtype == DT_F32 ? "false" : "true");
+  else n = snprintf(out, len, vocab[p.variant], t, p.K);
+  if (n >= 0 && (size_t)n < len) snprintf(out + n, len - n, " grid=%ux%u block=%d lds=%zu KC=%d", p.grid.x, p.grid.y, p.block, p.lds, p.KC);
+}
+
+namespace {
+
+// both dtypes' instantiations of one kernel template (f32 first: the code object lists the kernels in the order of these calls)
+template <auto K32, auto K16, typename... A>
+int launch_step_as(const StepPlan& p, hipStream_t stream, const A&... a) {
+  return p.dtype == DT_F32 ? launch_step<K32>(p, stream, a...) : launch_step<K16>(p, stream, a...);
+}
+
+int launch_lstm_step(const StepPlan& p, const LstmStepArgs& a, hipStream_t stream) {
+  switch (p.variant) {
+    case LSTM_PACK: return launch_step_as<lstm_step_pack_kernel<float>, lstm_step_pack_kernel<bf16_t>>(p, stream, a);
+    case LSTM_BEAM: return launch_step_as<lstm_step_beam_kernel<float>, lstm_step_beam_kernel<bf16_t>>(p, stream, a);
+    default: return launch_step_as<lstm_step_kernel<float>, lstm_step_kernel<bf16_t>>(p, stream, a);
+  }
+}
+
+// route-only mode (gemm.h): the plan is the route line, nothing is launched
+int step_route(const StepPlan& p) {
+  step_plan_line(p, route_line(), kRouteLen);
+  return GIC_OK;
+}
+
+}  // namespace
 
 int lstm_step(const LstmStepArgs& a, int dtype, hipStream_t stream) {
   GIC_CHECK_ARG(a.xh_t && a.xh_next && a.wcat && a.bsum && a.c_prev && a.c_new, "lstm_step: null buffer");
@@ -870,41 +933,12 @@ int lstm_step(const LstmStepArgs& a, int dtype, hipStream_t stream) {
   GIC_CHECK_ARG(a.B > 0 && a.H > 0 && a.din > 0 && a.ldx == (long)a.din + a.H && a.ldx % 8 == 0 && a.din % 8 == 0 && a.gw % 8 == 0 && a.gw <= a.din,
                 "lstm_step: bad dims");
   GIC_CHECK_ARG(!a.gather || (a.embed && a.V > 0 && (a.rowkey || a.force_ids || a.token)), "lstm_step: bad gather arguments");
-  const dim3 grid((unsigned)cdiv(a.H, kUnitsPerBlock), (unsigned)cdiv(a.B, kStepRows));
+  GIC_CHECK_ARG(!(beam && a.pack_len), "lstm_step: packed rows and the beam arguments do not combine");
   LstmStepArgs b = a;
   b.dbg = g_step_dbg;
-  const int KC = lstm_chunk(dtype, (int)a.ldx);
-  const size_t lds = lstm_lds_bytes(dtype, (int)a.ldx);
-  GIC_CHECK_ARG(!(beam && a.pack_len), "lstm_step: packed rows and the beam arguments do not combine");
-  if (a.pack_len) {
-    if (dtype == DT_F32) {
-      static LdsGrant p32;
-      GIC_PROPAGATE(allow_lds(lstm_step_pack_kernel<float>, lds, p32));
-      hipLaunchKernelGGL((lstm_step_pack_kernel<float>), grid, dim3(512), lds, stream, b, KC);
-    } else {
-      static LdsGrant p16;
-      GIC_PROPAGATE(allow_lds(lstm_step_pack_kernel<bf16_t>, lds, p16));
-      hipLaunchKernelGGL((lstm_step_pack_kernel<bf16_t>), grid, dim3(512), lds, stream, b, KC);
-    }
-  } else if (beam) {
-    if (dtype == DT_F32) {
-      static LdsGrant b32;
-      GIC_PROPAGATE(allow_lds(lstm_step_beam_kernel<float>, lds, b32));
-      hipLaunchKernelGGL((lstm_step_beam_kernel<float>), grid, dim3(512), lds, stream, b, KC);
-    } else {
-      static LdsGrant b16;
-      GIC_PROPAGATE(allow_lds(lstm_step_beam_kernel<bf16_t>, lds, b16));
-      hipLaunchKernelGGL((lstm_step_beam_kernel<bf16_t>), grid, dim3(512), lds, stream, b, KC);
-    }
-  } else if (dtype == DT_F32) {
-    static LdsGrant g32;
-    GIC_PROPAGATE(allow_lds(lstm_step_kernel<float>, lds, g32));
-    hipLaunchKernelGGL((lstm_step_kernel<float>), grid, dim3(512), lds, stream, b, KC);
-  } else {
-    static LdsGrant g16;
-    GIC_PROPAGATE(allow_lds(lstm_step_kernel<bf16_t>, lds, g16));
-    hipLaunchKernelGGL((lstm_step_kernel<bf16_t>), grid, dim3(512), lds, stream, b, KC);
-  }
+  const StepPlan p = select_lstm_step(a.pack_len ? LSTM_PACK : (beam ? LSTM_BEAM : LSTM_PLAIN), dtype, a.B, a.H, a.ldx);
+  if (route_only()) return step_route(p);
+  GIC_PROPAGATE(launch_lstm_step(p, b, stream));
   GIC_CHECK_LAUNCH("lstm_step");
   return GIC_OK;
 }
@@ -919,6 +953,34 @@ int lstm_bwd_step(const LstmBwdStepArgs& a, int dtype, hipStream_t stream) {
   return GIC_OK;
 }
 
+namespace {
+
+int launch_vocab_step(const StepPlan& p, const VocabStepArgs& a, hipStream_t stream, const BanLists& bans = BanLists(),
+                      const HopLists& hops = HopLists()) {
+  if (p.variant == VOCAB_SAMPLE) return launch_step_as<vocab_step_kernel<float, false>, vocab_step_kernel<bf16_t, true>>(p, stream, a);
+  if (p.variant == VOCAB_LOGITS) return launch_step_as<vocab_step_logits_kernel<float>, vocab_step_logits_kernel<bf16_t>>(p, stream, a);
+  if (p.variant != VOCAB_BEAM_HOP)
+    return with_beam_k(p.K, [&](auto k) {
+      if (p.variant == VOCAB_BEAM_BAN) return launch_step_as<vocab_step_beam_ban_kernel<float, k>, vocab_step_beam_ban_kernel<bf16_t, k>>(p, stream, a, bans);
+      return launch_step_as<vocab_step_beam_kernel<float, k>, vocab_step_beam_kernel<bf16_t, k>>(p, stream, a);
+    });
+  switch (p.K) {                                                // (2^C divides K: the forced search's beam sizes are even)
+    case 2: return launch_step_as<vocab_step_beam_hop_kernel<float, 2>, vocab_step_beam_hop_kernel<bf16_t, 2>>(p, stream, a, bans, hops);
+    case 4: return launch_step_as<vocab_step_beam_hop_kernel<float, 4>, vocab_step_beam_hop_kernel<bf16_t, 4>>(p, stream, a, bans, hops);
+    case 6: return launch_step_as<vocab_step_beam_hop_kernel<float, 6>, vocab_step_beam_hop_kernel<bf16_t, 6>>(p, stream, a, bans, hops);
+    default: return launch_step_as<vocab_step_beam_hop_kernel<float, 8>, vocab_step_beam_hop_kernel<bf16_t, 8>>(p, stream, a, bans, hops);
+  }
+}
+
+// the logits and beam epilogues draw nothing: the sampling fields leave the arguments
+VocabStepArgs without_sampling(const VocabStepArgs& a0) {
+  VocabStepArgs a = a0;
+  a.dbg = 0; a.pretrain = 1; a.u = nullptr; a.out = nullptr; a.rowkey = nullptr;
+  return a;
+}
+
+}  // namespace
+
 int vocab_step(const VocabStepArgs& a0, int dtype, hipStream_t stream) {
   VocabStepArgs a = a0;
   a.dbg = g_step_dbg;
@@ -926,124 +988,53 @@ int vocab_step(const VocabStepArgs& a0, int dtype, hipStream_t stream) {
   GIC_CHECK_ARG(a.B > 0 && a.V >= 4 && a.V % 4 == 0 && a.H % 8 == 0 && a.ldh % 8 == 0, "vocab_step: bad dims");
   GIC_CHECK_ARG(a.nblk == cdiv(a.V, kVocabTile), "vocab_step: nblk must be ceil(V / %d)", kVocabTile);
   GIC_CHECK_ARG(!a.out || a.out_stride % 4 == 0, "vocab_step: out row stride must be a multiple of 4");
-  const size_t lds = vocab_lds_bytes(dtype, a.H);
-  const int KC = vocab_chunk(dtype, a.H);
-  const dim3 grid((unsigned)a.nblk, (unsigned)cdiv(a.B, kStepRows));
-  if (dtype == DT_F32) {
-    static LdsGrant g32;
-    GIC_PROPAGATE(allow_lds(vocab_step_kernel<float, false>, lds, g32));
-    hipLaunchKernelGGL((vocab_step_kernel<float, false>), grid, dim3(512), lds, stream, a, KC);
-  } else {
-    static LdsGrant g16;
-    GIC_PROPAGATE(allow_lds(vocab_step_kernel<bf16_t, true>, lds, g16));
-    hipLaunchKernelGGL((vocab_step_kernel<bf16_t, true>), grid, dim3(512), lds, stream, a, KC);
-  }
+  const StepPlan p = select_vocab_step(VOCAB_SAMPLE, dtype, 0, a.B, a.V, a.H);
+  if (route_only()) return step_route(p);
+  GIC_PROPAGATE(launch_vocab_step(p, a, stream));
   GIC_CHECK_LAUNCH("vocab_step");
   return GIC_OK;
 }
 
 int vocab_step_logits(const VocabStepArgs& a0, int dtype, hipStream_t stream) {
-  VocabStepArgs a = a0;
-  a.dbg = 0; a.pretrain = 1; a.u = nullptr; a.out = nullptr; a.rowkey = nullptr;
+  const VocabStepArgs a = without_sampling(a0);
   GIC_CHECK_ARG(a.h && a.wout && a.bias && a.logits, "vocab_step_logits: null buffer");
   GIC_CHECK_ARG(a.B > 0 && a.V >= 4 && a.V % 4 == 0 && a.H % 8 == 0 && a.ldh % 8 == 0 && a.ld_logits >= a.V && a.ld_logits % 4 == 0,
                 "vocab_step_logits: bad dims");
   GIC_CHECK_ARG(((uintptr_t)a.logits & 15) == 0, "vocab_step_logits: logits must be 16-byte aligned");
-  const size_t lds = vocab_lds_bytes(dtype, a.H);
-  const int KC = vocab_chunk(dtype, a.H);
-  const dim3 grid((unsigned)cdiv(a.V, kVocabTile), (unsigned)cdiv(a.B, kStepRows));
-  if (dtype == DT_F32) {
-    static LdsGrant g32;
-    GIC_PROPAGATE(allow_lds(vocab_step_logits_kernel<float>, lds, g32));
-    hipLaunchKernelGGL((vocab_step_logits_kernel<float>), grid, dim3(512), lds, stream, a, KC);
-  } else {
-    static LdsGrant g16;
-    GIC_PROPAGATE(allow_lds(vocab_step_logits_kernel<bf16_t>, lds, g16));
-    hipLaunchKernelGGL((vocab_step_logits_kernel<bf16_t>), grid, dim3(512), lds, stream, a, KC);
-  }
+  const StepPlan p = select_vocab_step(VOCAB_LOGITS, dtype, 0, a.B, a.V, a.H);
+  if (route_only()) return step_route(p);
+  GIC_PROPAGATE(launch_vocab_step(p, a, stream));
   GIC_CHECK_LAUNCH("vocab_step_logits");
   return GIC_OK;
 }
 
-template <int K>
-int vocab_beam_launch(const VocabStepArgs& a, int dtype, size_t lds, int KC, dim3 grid, hipStream_t stream, const BanLists& bans) {
-  if (bans.nban) {                                            // decode constraints: the epilogue that reads the ban lists
-    if (dtype == DT_F32) {
-      static LdsGrant b32;
-      GIC_PROPAGATE(allow_lds(vocab_step_beam_ban_kernel<float, K>, lds, b32));
-      hipLaunchKernelGGL((vocab_step_beam_ban_kernel<float, K>), grid, dim3(512), lds, stream, a, KC, bans);
-    } else {
-      static LdsGrant b16;
-      GIC_PROPAGATE(allow_lds(vocab_step_beam_ban_kernel<bf16_t, K>, lds, b16));
-      hipLaunchKernelGGL((vocab_step_beam_ban_kernel<bf16_t, K>), grid, dim3(512), lds, stream, a, KC, bans);
-    }
-    GIC_CHECK_LAUNCH("vocab_step_beam");
-    return GIC_OK;
-  }
-  if (dtype == DT_F32) {
-    static LdsGrant g32;
-    GIC_PROPAGATE(allow_lds(vocab_step_beam_kernel<float, K>, lds, g32));
-    hipLaunchKernelGGL((vocab_step_beam_kernel<float, K>), grid, dim3(512), lds, stream, a, KC);
-  } else {
-    static LdsGrant g16;
-    GIC_PROPAGATE(allow_lds(vocab_step_beam_kernel<bf16_t, K>, lds, g16));
-    hipLaunchKernelGGL((vocab_step_beam_kernel<bf16_t, K>), grid, dim3(512), lds, stream, a, KC);
-  }
-  GIC_CHECK_LAUNCH("vocab_step_beam");
-  return GIC_OK;
-}
-
 int vocab_step_beam(const VocabStepArgs& a0, int K, int dtype, hipStream_t stream, const BanLists& bans) {
-  VocabStepArgs a = a0;
-  a.dbg = 0; a.pretrain = 1; a.u = nullptr; a.out = nullptr; a.rowkey = nullptr;
+  const VocabStepArgs a = without_sampling(a0);
   GIC_CHECK_ARG(a.h && a.wout && a.bias && a.part_m && a.part_s && a.part_v && a.part_i, "vocab_step_beam: null buffer");
   GIC_CHECK_ARG(a.B > 0 && a.V >= 4 && a.V % 4 == 0 && a.H % 8 == 0 && a.ldh % 8 == 0 && K >= 1 && K <= kBeamMax, "vocab_step_beam: bad dims");
   GIC_CHECK_ARG(a.nblk == cdiv(a.V, kVocabTile), "vocab_step_beam: nblk must be ceil(V / %d)", kVocabTile);
   GIC_CHECK_ARG(!bans.nban || (bans.ban && bans.cap > 0), "vocab_step_beam: ban lists without their buffer");
-  const size_t tile = (size_t)kStepRows * (kVocabTile + 1) * sizeof(float);
-  size_t lds = vocab_lds_bytes(dtype, a.H);
-  if (lds < tile) lds = tile;
-  const int KC = vocab_chunk(dtype, a.H);
-  const dim3 grid((unsigned)a.nblk, (unsigned)cdiv(a.B, kStepRows));
-  return with_beam_k(K, [&](auto k) { return vocab_beam_launch<k>(a, dtype, lds, KC, grid, stream, bans); });
-}
-
-template <int K>
-int vocab_hop_launch(const VocabStepArgs& a, int dtype, size_t lds, int KC, dim3 grid, hipStream_t stream, const BanLists& bans,
-                     const HopLists& hops) {
-  if (dtype == DT_F32) {
-    static LdsGrant h32;
-    GIC_PROPAGATE(allow_lds(vocab_step_beam_hop_kernel<float, K>, lds, h32));
-    hipLaunchKernelGGL((vocab_step_beam_hop_kernel<float, K>), grid, dim3(512), lds, stream, a, KC, bans, hops);
-  } else {
-    static LdsGrant h16;
-    GIC_PROPAGATE(allow_lds(vocab_step_beam_hop_kernel<bf16_t, K>, lds, h16));
-    hipLaunchKernelGGL((vocab_step_beam_hop_kernel<bf16_t, K>), grid, dim3(512), lds, stream, a, KC, bans, hops);
-  }
-  GIC_CHECK_LAUNCH("vocab_step_beam_hop");
+  // decode constraints: the epilogue that reads the ban lists
+  const StepPlan p = select_vocab_step(bans.nban ? VOCAB_BEAM_BAN : VOCAB_BEAM, dtype, K, a.B, a.V, a.H);
+  if (route_only()) return step_route(p);
+  GIC_PROPAGATE(launch_vocab_step(p, a, stream, bans));
+  GIC_CHECK_LAUNCH("vocab_step_beam");
   return GIC_OK;
 }
 
 int vocab_step_beam_hop(const VocabStepArgs& a0, int K, int dtype, hipStream_t stream, const BanLists& bans, const HopLists& hops) {
-  VocabStepArgs a = a0;
-  a.dbg = 0; a.pretrain = 1; a.u = nullptr; a.out = nullptr; a.rowkey = nullptr;
+  const VocabStepArgs a = without_sampling(a0);
   GIC_CHECK_ARG(a.h && a.wout && a.bias && a.part_m && a.part_s && a.part_v && a.part_i, "vocab_step_beam_hop: null buffer");
   GIC_CHECK_ARG(a.B > 0 && a.V >= 4 && a.V % 4 == 0 && a.H % 8 == 0 && a.ldh % 8 == 0 && K >= 2 && K <= kBeamMax && K % 2 == 0,
                 "vocab_step_beam_hop: bad dims");
   GIC_CHECK_ARG(a.nblk == cdiv(a.V, kVocabTile), "vocab_step_beam_hop: nblk must be ceil(V / %d)", kVocabTile);
   GIC_CHECK_ARG(bans.nban && bans.ban && bans.cap > 0 && hops.id && hops.val && hops.n >= 1 && hops.n <= kHopMax,
                 "vocab_step_beam_hop: ban and hop lists must be set");
-  const size_t tile = (size_t)kStepRows * (kVocabTile + 1) * sizeof(float);
-  size_t lds = vocab_lds_bytes(dtype, a.H);
-  if (lds < tile) lds = tile;
-  const int KC = vocab_chunk(dtype, a.H);
-  const dim3 grid((unsigned)a.nblk, (unsigned)cdiv(a.B, kStepRows));
-  switch (K) {                                                // (2^C divides K: the forced search's beam sizes are even)
-    case 2: return vocab_hop_launch<2>(a, dtype, lds, KC, grid, stream, bans, hops);
-    case 4: return vocab_hop_launch<4>(a, dtype, lds, KC, grid, stream, bans, hops);
-    case 6: return vocab_hop_launch<6>(a, dtype, lds, KC, grid, stream, bans, hops);
-    default: return vocab_hop_launch<8>(a, dtype, lds, KC, grid, stream, bans, hops);
-  }
+  const StepPlan p = select_vocab_step(VOCAB_BEAM_HOP, dtype, K, a.B, a.V, a.H);
+  if (route_only()) return step_route(p);
+  GIC_PROPAGATE(launch_vocab_step(p, a, stream, bans, hops));
+  GIC_CHECK_LAUNCH("vocab_step_beam_hop");
+  return GIC_OK;
 }
 
 int sample_finish(const SampleFinishArgs& a, int dtype, hipStream_t stream) {

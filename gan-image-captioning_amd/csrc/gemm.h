@@ -135,7 +135,12 @@ void wgrad_launch_counts(long* launches, long* two_matrix);
 // line into route_line() and return their status without touching the GPU.  gic_disc_fwd (disc.hip) answers with the selection of its
 // highway product, the one caller of EPI_HIGHWAY, and launches none of its own kernels.  gic_disc_bwd, gic_disc_bwd_cond and
 // gic_disc_fwd_redrop validate, run select_disc_bwd (the pair of this convention in disc.hip; gic_debug_disc_plan prints its plans) and
-// return before their first launch or product.
+// return before their first launch or product.  So do the decoder passes (decoder_step.h: select_decoder_fwd / select_decoder_bwd,
+// select_lstm_step / select_vocab_step; gic_debug_decoder_plan prints the plans): gic_decoder_sample_fwd, gic_decoder_sample_bwd, the
+// teacher-forced entries of teacher_forced.hip (forward, scheduled sampling and backward, both decoders) and gic_attn_rollout.  lstm_step /
+// vocab_step* answer with their plan as the route line; the fused roll-out and the backward entries return before their first product;
+// the generic roll-outs and the teacher-forced forwards walk their steps and select each product in launch order, launching nothing, so
+// the route line is their last product's (teacher_forced.hip: " ss_logits=fused" where vocab_step_logits replaces it).
 bool route_only();
 char* route_line();                    // thread-local, kRouteLen bytes
 constexpr int kRouteLen = 160;

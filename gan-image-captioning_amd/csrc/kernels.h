@@ -57,8 +57,8 @@ int embed_scatter_time(const float* dx, long ld, const int64_t* ids, float* d_em
 
 // sched_sample.hip: scheduled sampling inside the teacher-forced decodes (gic_decoder_forward_ss, gic_attn_forward_ss).
 //   ss_check_opts    the argument checks of gic_sched_sample_opts (`what` names the entry point in the message)
-//   ss_fused_logits  whether the per-step vocabulary product is vocab_step_logits (decoder_step_supported and the rows fit) or the GEMM
-//   ss_step_logits   logits[b, t, :] = hout[b, t, :] W_out^T + b_out in f32 for every caption b (hout act [B, Tmax, H], logits [B, Tmax, V])
+//   ss_step_logits   logits[b, t, :] = hout[b, t, :] W_out^T + b_out in f32 for every caption b (hout act [B, Tmax, H], logits [B, Tmax, V]);
+//                    fused: vocab_step_logits (the caller's B <= decoder_fused_rows, decoder_step.h) instead of the GEMM
 //   ss_pick          between steps t-1 and t: coin, pick and the pick's embedding row into x_next (= x of slot t), one launch
 //   ss_tail          inputs[:, from:] = caps[:, from:], replaced = 0 there (the positions no step is fed from)
 struct SsPickArgs {
@@ -76,7 +76,6 @@ struct SsPickArgs {
   int64_t* inputs = nullptr; int32_t* replaced = nullptr;   // [B, Tm1]; replaced may be null
 };
 int ss_check_opts(const gic_sched_sample_opts* o, int L, const char* what);
-bool ss_fused_logits(int dt, int B, int V, int E, int H, int NL);
 int ss_step_logits(int dt, const void* hout, int t, int Tmax, const void* wout, const float* b_out, float* logits, int B, int V, int H,
                    bool fused, hipStream_t stream);
 int ss_pick(const SsPickArgs& a, int dt, hipStream_t stream);

@@ -156,10 +156,6 @@ int ss_tail(const int64_t* caps, int64_t* inputs, int32_t* replaced, int B, int 
   return GIC_OK;
 }
 
-bool ss_fused_logits(int dt, int B, int V, int E, int H, int NL) {
-  return B <= decoder_step_max_rows() && decoder_step_supported(dt, V, E, H, NL);
-}
-
 int ss_step_logits(int dt, const void* hout, int t, int Tmax, const void* wout, const float* b_out, float* logits, int B, int V, int H,
                    bool fused, hipStream_t stream) {
   const void* h = (const char*)hout + (size_t)t * H * dtype_size(dt);

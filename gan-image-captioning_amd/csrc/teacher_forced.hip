@@ -41,6 +41,9 @@
 // options and the workspace's alignment, then the model's buffers; gic_attn_forward_ss is refused by the deterministic mode before
 // all of them, gic_attn_forward_tf and gic_attn_forward_tf_bwd are not.  tests/test_train_entry_errors.py pins texts and order with
 // a recorded table.
+#include <stdio.h>
+#include <string.h>
+
 #include "../../include/gicap.h"
 #include "beam.h"
 #include "kernels.h"
@@ -131,17 +134,25 @@ struct LstmTf {
     }
     return tf_inputs(c.dt, io, P->embed, st->xh[0], c.ldx(0), c.B, c.L, c.E, c.V);
   }
+  GemmDesc gates_product(const TfIo& io, int l, int t) const {      // layer l's gate pre-activations of step t
+    const long ld = c.ldx(l);
+    GemmDesc g;
+    g.A = act(st->xh[l], (long)t * c.B * ld, c.asz()); g.lda = ld; g.B = S->wcat[l]; g.ldb = ld; g.C = st->gpre; g.ldc = 4 * c.H;
+    g.M = c.B; g.N = 4 * c.H; g.K = (int)ld; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = S->bsum[l];
+    g.no_split = io.ss != nullptr;          // the picks are discrete: the same inputs must give the same bits
+    return g;
+  }
+  int route(const TfIo& io) const {          // route-only mode: a step's products, selected in launch order
+    for (int l = 0; l < c.NL; ++l) GIC_PROPAGATE(gemm(gates_product(io, l, 0), io.stream));
+    return GIC_OK;
+  }
   int step(const TfIo& io, int t) const {
     const int B = c.B, H = c.H;
     for (int l = 0; l < c.NL; ++l) {
       const long ld = c.ldx(l);
       void* xh_t = act(st->xh[l], (long)t * B * ld, c.asz());
       void* xh_n = act(st->xh[l], (long)(t + 1) * B * ld, c.asz());
-      GemmDesc g;
-      g.A = xh_t; g.lda = ld; g.B = S->wcat[l]; g.ldb = ld; g.C = st->gpre; g.ldc = 4 * H;
-      g.M = B; g.N = 4 * H; g.K = (int)ld; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = S->bsum[l];
-      g.no_split = io.ss != nullptr;          // the picks are discrete: the same inputs must give the same bits
-      GIC_PROPAGATE(gemm(g, io.stream));
+      GIC_PROPAGATE(gemm(gates_product(io, l, t), io.stream));
       const bool top = l + 1 == c.NL;
       GIC_PROPAGATE(lstm_pointwise_fwd(c.dt, st->gpre, st->c[l] + (long)t * B * H, st->c[l] + (long)(t + 1) * B * H, act(xh_n, c.din(l), c.asz()), ld,
                                        top ? nullptr : act(st->xh[l + 1], (long)t * B * c.ldx(l + 1), c.asz()), top ? 0 : c.ldx(l + 1), B, H,
@@ -174,18 +185,21 @@ struct AttnTf {
     g.no_split = 1;
     return gemm(g, io.stream);
   }
+  GemmDesc hp_product(int t) const {          // hp [B, A] = h_{t-1} W_h^T
+    GemmDesc g;
+    g.A = act(st->xh, (long)t * c.B * c.ldx() + c.din(), c.asz()); g.lda = c.ldx(); g.B = S->wh; g.ldb = c.H;
+    g.C = st->hproj + (long)t * c.B * c.A; g.ldc = c.A;
+    g.M = c.B; g.N = c.A; g.K = c.H; g.in_dtype = c.dt; g.out_dtype = DT_F32;
+    g.no_split = 1;
+    return g;
+  }
+  int route(const TfIo& io) const { return gemm(hp_product(0), io.stream); }      // route-only mode: a step's product
   int step(const TfIo& io, int t) const {
     const int B = c.B, E = c.E, H = c.H, Tmax = io.Tmax;
     const long ld = c.ldx();
     void* xh_t = act(st->xh, (long)t * B * ld, c.asz());
     float* hp = st->hproj + (long)t * B * c.A;
-    {  // hp [B, A] = h_{t-1} W_h^T
-      GemmDesc g;
-      g.A = act(xh_t, c.din(), c.asz()); g.lda = ld; g.B = S->wh; g.ldb = H; g.C = hp; g.ldc = c.A;
-      g.M = B; g.N = c.A; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32;
-      g.no_split = 1;
-      GIC_PROPAGATE(gemm(g, io.stream));
-    }
+    GIC_PROPAGATE(gemm(hp_product(t), io.stream));
     AttnStepArgs f{};                // par and stop stay null: the packed form reads lengths instead
     f.fproj = st->fproj; f.fmap = fmap; f.w_a = P->w_a; f.hp = hp;
     f.e = io.ss ? io.logits_ws + (size_t)B * Tmax * c.V : io.logits_ws;      // scheduled sampling: the logits are live inside the loop
@@ -211,9 +225,29 @@ int teacher_forced(const Rec& rec, const TfIo& io) {
   const auto& c = rec.c;
   const int B = c.B, T = c.L, V = c.V, E = c.E, H = c.H, Tmax = io.Tmax;
   const gic_sched_sample_opts* ss = io.ss;
-  const bool ss_fused = ss && ss_fused_logits(c.dt, B, V, E, H, rec.layers());
+  const bool ss_fused = ss && B <= decoder_fused_rows(c.dt, V, E, H, rec.layers());
   const gic_decoder_dropout* dr = io.drop;
   const void* hproj = dr ? dr->hdrop : rec.st->hout;       // what the vocabulary projection consumes
+  const long rows = (long)B * Tmax;
+  auto projection = [&] {      // the logits of all B * Tmax rows at once
+    GemmDesc g;
+    g.A = hproj; g.lda = H; g.B = rec.S->wout; g.ldb = H; g.C = io.logits_ws; g.ldc = V;
+    g.M = (int)rows; g.N = V; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = rec.P->b_out;
+    g.no_split = Rec::kNoSplitVocab;
+    return g;
+  };
+  // route-only mode (gemm.h): nothing is launched; the pass's products are selected in launch order -- a step's recurrence, then the
+  // logits: the projection, or scheduled sampling's per-step product, or " ss_logits=fused" behind the recurrence's line where
+  // vocab_step_logits takes that product's place
+  if (route_only()) {
+    GIC_PROPAGATE(rec.route(io));
+    if (!ss) return gemm(projection(), io.stream);
+    if (!ss_fused) return ss_step_logits(c.dt, hproj, 0, Tmax, rec.S->wout, rec.P->b_out, io.logits_ws, B, V, H, false, io.stream);
+    char* line = route_line();
+    const size_t n = strlen(line);
+    snprintf(line + n, kRouteLen - n, " ss_logits=fused");
+    return GIC_OK;
+  }
   // ss_tail depends on nothing begin() enqueues and nothing there on it.  That it precedes the attention decoder's begin() and follows
   // the LSTM decoder's is history, not design: kept, so that a kernel trace of either call lists the launches it always listed
   auto tail = [&] { return ss ? ss_tail(io.caps, ss->inputs, ss->replaced, B, T - 1, Tmax - 1, io.stream) : (int)GIC_OK; };
@@ -235,14 +269,9 @@ int teacher_forced(const Rec& rec, const TfIo& io) {
       GIC_PROPAGATE(ss_pick(a, c.dt, io.stream));
     }
   }
-  const long rows = (long)B * Tmax;
   if (!ss) {  // one projection over all B * Tmax rows
     if (dr) GIC_PROPAGATE(hidden_dropout_fwd(c.dt, rec.st->hout, dr->hdrop, dr->keep_u, dr->seed, dr->p, B, Tmax, H, -1, io.stream));
-    GemmDesc g;
-    g.A = hproj; g.lda = H; g.B = rec.S->wout; g.ldb = H; g.C = io.logits_ws; g.ldc = V;
-    g.M = (int)rows; g.N = V; g.K = H; g.in_dtype = c.dt; g.out_dtype = DT_F32; g.bias = rec.P->b_out;
-    g.no_split = Rec::kNoSplitVocab;
-    GIC_PROPAGATE(gemm(g, io.stream));
+    GIC_PROPAGATE(gemm(projection(), io.stream));
   }
   GIC_PROPAGATE(gumbel_softmax_rows(c.dt, io.logits_ws, io.noise_u, io.seed, (uint64_t)0x7466, io.temperature, io.pretrain, io.out, rows, V, io.stream));
   for (int l = 0; l < rec.layers(); ++l) {
@@ -354,6 +383,7 @@ int backward_entry(Model m, const char* who, const TfGrad& g, bool dropout = fal
   GIC_PROPAGATE(open_entry(m, who, m.ws && m.G && g.pred && g.lengths && g.d_pred, g.caps, g.Tmax));
   GIC_PROPAGATE(m.check_bwd(who));
   if (dropout) GIC_PROPAGATE(drop_check(g.drop, who));
+  if (route_only()) return GIC_OK;       // (gemm.h) validated; gic_debug_decoder_plan prints the LSTM decoder's backward selection
   auto view = m.c;
   view.L = g.Tmax;
   GIC_PROPAGATE(decoder_output_bwd(view.dt, view.B, g.Tmax, view.V, view.H, g.pred, g.d_pred, g.temperature, nullptr, g.pretrain, m.ws->dlogits,

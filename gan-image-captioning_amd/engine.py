@@ -1154,6 +1154,18 @@ class DecoderEngine(_CaptionDecodes, _TeacherForced):
         return L.DecoderDims(B, Lc, self.V, self.E, self.H, self.NL, self.dt)
 
     # params: [embed, (w_ih, w_hh, b_ih, b_hh) * NL, w_out, b_out]
+    def plan(self, B: int, Lc: int, train: bool = True, pretrain: bool = False, dev_scalars: bool = False, resumed: bool = False,
+             part: bool = True, transposed_images: bool = True, state_grads: bool = False, logits_aligned: bool = True):
+        """gic_debug_decoder_plan: what sample_fwd / sample_bwd select for these shapes -- the forward's path and its per-step launches
+        and, with `train`, the backward's -- as lines (gicap.h).  Host-only."""
+        flags = (L.DECODER_PLAN_TRAIN if train else 0) | (L.DECODER_PLAN_PRETRAIN if pretrain else 0) | \
+                (L.DECODER_PLAN_DEV_SCALARS if dev_scalars else 0) | (L.DECODER_PLAN_RESUMED if resumed else 0) | \
+                (0 if part else L.DECODER_PLAN_NO_PART) | (0 if transposed_images else L.DECODER_PLAN_NO_WCAT_T) | \
+                (L.DECODER_PLAN_STATE_GRADS if state_grads else 0) | (0 if logits_aligned else L.DECODER_PLAN_LOGITS_UNALIGNED)
+        out = C.create_string_buffer(4096)
+        L.check(L.load().gic_debug_decoder_plan(C.byref(self.dims(B, Lc)), flags, out, len(out)), "gic_debug_decoder_plan")
+        return out.value.decode().splitlines()
+
     def _pstruct(self, params, cls=L.DecoderParams, extra=None):
         nl = self.NL
         s = cls()

@@ -55,7 +55,16 @@ const char* gic_last_error(void);
  * "tile8<bf16,128,2,true,2,true,false,1024> grid=1568 block=512 lds=0"; "unsupported" when nothing was selected.
  * The sequence discriminator's entry points honour it too: gic_disc_fwd answers with the selection of its highway product; gic_disc_bwd,
  * gic_disc_bwd_cond and gic_disc_fwd_redrop validate, select their own kernels (gic_debug_disc_plan prints that selection) and return
- * their status without a launch, the route line left as it was. */
+ * their status without a launch, the route line left as it was.
+ * So do the LSTM decoder's passes and the attention decoder's roll-out: gic_decoder_sample_fwd, gic_decoder_sample_bwd, the teacher-forced
+ * entries (gic_decoder_forward_tf / _ss / _tf_bwd and their _drop and gic_attn_ twins) and gic_attn_rollout validate, select
+ * (gic_debug_decoder_plan prints that selection) and launch, fill and copy nothing.  What they leave as the route line is, as ever, the
+ * last product they select: none on the fused paths of gic_decoder_sample_fwd and in the backward entries (they return before their first
+ * product: the line stays as it was); on the generic roll-out paths and in gic_attn_rollout the last step's vocabulary product (the
+ * steps are walked over host_active_rows: the tile8 kernel with the Gumbel-max epilogue where the step took it); in the teacher-forced
+ * forwards the logits product -- the projection, or scheduled sampling's per-step product, or the recurrence's product with
+ * " ss_logits=fused" behind it where the vocab_step_logits kernel takes that product's place.  The step kernels' own launchers answer
+ * with their plan (gic_debug_step_plan's line). */
 void gic_debug_route_only(int on);
 const char* gic_debug_last_route(void);
 /* Host-only: what the selection answers the library's own weight-gradient call sites (dW = dy^T x with the bias gradient as the column
@@ -201,8 +210,8 @@ typedef struct gic_decoder_sample_opts {
   const struct gic_decoder_state* resume_from;
   int32_t resume_B;
   const int32_t* host_active_rows;
-  /* device-resident temperature and Philox seed (gic_step_scalars above; fused step kernels only: GIC_STATUS_UNSUPPORTED on the
-   * generic-product path) */
+  /* device-resident temperature and Philox seed (gic_step_scalars above; fused step kernels only: GIC_STATUS_UNSUPPORTED where
+   * gic_debug_decoder_plan's forward path is not FUSED) */
   const gic_step_scalars* dev_scalars;
   int32_t seed_slot;
 } gic_decoder_sample_opts;
@@ -226,6 +235,32 @@ void gic_debug_decoder_step(int mask);
  * the generic products and NEEDS state->logits and state->gpre; a caller that sizes its buffers by this query never trips that check
  * (Decoder.sample, src/generator.py:55-81, takes any vocabulary / embedding size). */
 int gic_decoder_fused_rollout_rows(const gic_decoder_dims* dims, int32_t* out_rows);
+
+/* (an addition to ABI v5) Host-only: what gic_decoder_sample_fwd and gic_decoder_sample_bwd select for these dims (csrc/decoder_step.h
+ * select_decoder_fwd / select_decoder_bwd, the library's very selection), as '\n'-terminated lines written to out (out_len bytes, the
+ * terminating 0 included).  "forward path=FUSED | GENERIC | GENERIC_ROWKEY from=<rows>" (from: the rows from which a GENERIC_ROWKEY step's
+ * vocabulary product carries the Gumbel-max, 0 = never), then one line per distinct launch of the roll-out's steps in launch order, as in
+ * gic_debug_last_route -- kernel<template args> grid= block= lds= (the step kernels: KC= too; products: their gemm / tile8 line and
+ * M= N= K=) -- with " x<count>", the launches of that line per call (layers above the first share a line).  With GIC_DECODER_PLAN_TRAIN,
+ * "backward path=FUSED | GENERIC" and the backward's lines follow: softmax_bwd's variant, lstm_bwd_step's chain or the pointwise kernel and
+ * the per-layer products, then per layer the weight gradient as one folded product or two and "colsum" (the output layer's two products
+ * are gic_gemm's business).  Slot 0's fills and casts, the copies of a resumed roll-out and the embedding scatter are not listed.
+ * A resumed roll-out's steps run over host_active_rows[t] <= B rows: the lines are those of a step with all B rows, the last step's
+ * upper bound; gic_decoder_sample_fwd in route-only mode walks a call's own rows.  The deterministic mode is the library's current one.
+ * GIC_STATUS_UNSUPPORTED with gic_decoder_sample_fwd's message: GIC_DECODER_PLAN_DEV_SCALARS off the fused path. */
+#define GIC_DECODER_PLAN_TRAIN 1             /* out and the saved state are there and a backward follows; else an ids-only roll-out */
+#define GIC_DECODER_PLAN_PRETRAIN 2          /* pretrain != 0 */
+#define GIC_DECODER_PLAN_DEV_SCALARS 4       /* opts->dev_scalars */
+#define GIC_DECODER_PLAN_RESUMED 8           /* opts->resume_from */
+#define GIC_DECODER_PLAN_NO_PART 16          /* state->part == NULL */
+#define GIC_DECODER_PLAN_NO_WCAT_T 32        /* the last layer's shadow->wcat_t is NULL */
+#define GIC_DECODER_PLAN_STATE_GRADS 64      /* phases has GIC_DECODER_BWD_STATE_GRADS */
+#define GIC_DECODER_PLAN_LOGITS_UNALIGNED 128 /* state->logits is 4-byte, not 8-byte aligned */
+int gic_debug_decoder_plan(const gic_decoder_dims* dims, int flags, char* out, int64_t out_len);
+/* Host-only: the launch plan of one fused step kernel as one line.  lstm != 0: lstm_step's variant 0 plain | 1 packed rows | 2 beam over
+ * B rows, H units and input rows of ldx_or_V values; else vocab_step's variant 0 sample | 1 logits | 2 beam | 3 beam + ban lists | 4 beam +
+ * ban + hop lists (K: the beam width) over B rows, H units and ldx_or_V words. */
+int gic_debug_step_plan(int lstm, int variant, int dtype, int B, int H, int64_t ldx_or_V, int K, char* out, int64_t out_len);
 
 /* Beam-search caption decode (the reference's unbuilt evaluation step; no sampling noise, no temperature: sample(pretrain=True)'s
  * distribution).  dims->B = images, dims->L = maximum caption length.  Rows = B * beam (row r = image r / beam, beam r % beam).

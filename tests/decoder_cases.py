@@ -106,7 +106,7 @@ def select(case):
     """The routes and kernels gic_decoder_sample_fwd / _bwd take for a case, restated."""
     c, bf = case, case.dtype == "bf16"
     sz = 2 if bf else 4
-    step_ok = c.V >= 4 and c.V % 4 == 0 and c.E % 8 == 0 and c.H % 8 == 0 and c.nblk <= 1024       # decoder_step_supported
+    step_ok = c.V >= 4 and c.V % 4 == 0 and c.E % 8 == 0 and c.H % 8 == 0 and c.nblk <= 1024       # decoder_fused_rows
     fwd = "fused" if c.part and c.B <= MAX_ROWS and step_ok else "generic"
     bwd = "fused" if c.H % 8 == 0 and c.B <= MAX_ROWS else "generic"
     argmax = None

@@ -110,11 +110,11 @@ def select(case):
     """The routes gic_decoder_forward_tf / _ss / _tf_bwd take for a case, restated."""
     c = case
     s = D.select(view_case(c, False))
-    step_ok = c.V >= 4 and c.V % 4 == 0 and c.E % 8 == 0 and c.H % 8 == 0 and c.nblk <= 1024           # decoder_step_supported
+    step_ok = c.V >= 4 and c.V % 4 == 0 and c.E % 8 == 0 and c.H % 8 == 0 and c.nblk <= 1024           # decoder_fused_rows
     scatter = "none" if c.Tmax == 1 else ("rows" if c.E % 4 == 0 and c.ldx(0) % 4 == 0 else "scalar")   # embed_scatter_time
     nv = 4 if c.dtype == "f32" else 8
     return {"bwd": s["bwd"], "softmax_bwd": s["softmax_bwd"], "scatter": scatter,
-            "ss_logits": "fused" if c.B <= D.MAX_ROWS and step_ok else "gemm",                        # ss_fused_logits
+            "ss_logits": "fused" if c.B <= D.MAX_ROWS and step_ok else "gemm",                        # teacher_forced()'s ss_fused
             "drop": ("vec" if c.H % nv == 0 else "scalar") + "/" + ("vec" if c.H % 4 == 0 else "scalar"),   # hidden_dropout_fwd / _bwd
             "view": f"{c.Tmax}/{c.T}"}
 

@@ -56,6 +56,27 @@ def test_argument_validation_returns_status_not_crash():
     assert lib.gic_debug_disc_plan(ctypes.byref(dd), _lib.DISC_PLAN_GRADS | _lib.DISC_PLAN_TRAIN, small, need - 1) == -1
     assert b"out_len" in lib.gic_last_error() and small.raw[need - 1:] == b"\x7f" * 9
     assert lib.gic_debug_disc_plan(ctypes.byref(dd), _lib.DISC_PLAN_GRADS | _lib.DISC_PLAN_TRAIN, small, need) == 0 and small.value == out.value
+    # gic_debug_decoder_plan / gic_debug_step_plan: host-only; dims validated as gic_decoder_sample_fwd validates them, then buffer and flags
+    assert lib.gic_debug_decoder_plan(None, 0, None, 0) == -1 and b"null dims" in lib.gic_last_error()
+    gd = _lib.DecoderDims(2, 3, 8, 8, 8, 1, _lib.BF16)
+    train = _lib.DECODER_PLAN_TRAIN
+    assert lib.gic_debug_decoder_plan(ctypes.byref(gd), 0, None, 1024) == -1 and b"no output buffer" in lib.gic_last_error()
+    assert lib.gic_debug_decoder_plan(ctypes.byref(gd), 256, out, 1024) == -1 and b"unknown flag" in lib.gic_last_error()
+    assert (_lib.DECODER_PLAN_TRAIN, _lib.DECODER_PLAN_PRETRAIN, _lib.DECODER_PLAN_DEV_SCALARS, _lib.DECODER_PLAN_RESUMED, _lib.DECODER_PLAN_NO_PART,
+            _lib.DECODER_PLAN_NO_WCAT_T, _lib.DECODER_PLAN_STATE_GRADS, _lib.DECODER_PLAN_LOGITS_UNALIGNED) == tuple(
+                int(re.search(rf"#define GIC_DECODER_PLAN_{n} (\d+)", open(os.path.join(ROOT, "include", "gicap.h")).read()).group(1))
+                for n in ("TRAIN", "PRETRAIN", "DEV_SCALARS", "RESUMED", "NO_PART", "NO_WCAT_T", "STATE_GRADS", "LOGITS_UNALIGNED"))
+    assert lib.gic_debug_decoder_plan(ctypes.byref(gd), train, out, 1024) == 0
+    lines = out.value.decode().splitlines()
+    assert lines[0] == "forward path=FUSED from=0" and "backward path=FUSED" in lines and out.value.endswith(b"\n")
+    assert all(" grid=" in l and " block=" in l and " lds=" in l for l in lines if "path=" not in l and not l.startswith("colsum")), lines
+    need = len(out.value) + 1
+    small = ctypes.create_string_buffer(b"\x7f" * (need + 8), need + 8)
+    assert lib.gic_debug_decoder_plan(ctypes.byref(gd), train, small, need - 1) == -1
+    assert b"out_len" in lib.gic_last_error() and small.raw[need - 1:] == b"\x7f" * 9
+    assert lib.gic_debug_decoder_plan(ctypes.byref(gd), train, small, need) == 0 and small.value == out.value
+    assert lib.gic_debug_step_plan(1, 3, _lib.BF16, 2, 8, 16, 0, out, 1024) == -1 and b"bad arguments" in lib.gic_last_error()
+    assert lib.gic_debug_step_plan(0, 4, _lib.BF16, 2, 8, 8, 2, out, 1024) == 0 and out.value.startswith(b"vocab_step_beam_hop_kernel<bf16,2> ")
     d = _lib.DecoderDims(4, 5, 50, 8, 16, 9, 0)          # NL out of range
     assert lib.gic_decoder_prepare(ctypes.byref(d), None, None, None) == -1
     assert b"gen_num_layers" in lib.gic_last_error()

@@ -10,7 +10,7 @@ order-independent; the attention decoder refuses that mode and needs none, like 
 split) and, where the launch goes through the GEMM selection, that both modes select the same kernel (engine.route_only: the line of
 the last product the call selects).  A route-only pass skips the products and still launches everything else, so it runs on zeroed
 buffers (or, the composed step, on those a complete step has just filled): nothing then indexes by an uninitialised value.  The fused
-step kernels (lstm_step / vocab_step / sample_finish) are not selected per call: decoder_step_supported is a function of the shapes
+step kernels (lstm_step / vocab_step / sample_finish) are not selected per call: decoder_fused_rows is a function of the shapes
 alone; nor are the segments of the replayed graphs, which make the calls of the eager step.  Two seeds everywhere: 1 and one with a non-zero upper
 half; the two must give different results (the comparison is not vacuous).
 
